@@ -2,6 +2,7 @@
 """bench.py -- headline benchmark of the MI355X-native speechsauce hot path.
 
     python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|cfg4|cfg5] [--gather-mode root|all|none]
+                    [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): frames/sec (+ real-time factor) for 16 kHz MFCC n_fft=512 at 1/2/4/8 MI355X.
 A "step" is one pass of the hot path over one batch of synthetic clips that already sit in HBM:
@@ -23,7 +24,15 @@ own time and the per-link rate it reached, so the line says how much of the step
 cfg4 (the 100 h corpus, 360 000 clips) is the one strong-scaling workload: the corpus is split into
 contiguous clip shards (speechsauce_amd.distributed.shard_bounds), one launch per shard per step.
 
-A default N = 1 run (headline workload, no measurement switches) also times, after the headline region and outside it: the headline
+A plain run sets up, pre-rolls and warms up, times the K steps, writes the last timed step's output if --dump-outputs is given, and
+prints its line: no CPU baseline, no board or clock readings, no stored profile, no secondary legs.  Those are --full's (below).
+
+--dump-outputs DIR: after the timed region, the output block of its last step (what a caller of the path receives; rank 0's own
+block when N > 1) is written as DIR/mfcc.npy or DIR/mel_spectrogram.npy, float32.  A block above 64 MB (cfg4) is written as a fixed
+sample of whole clips: the clip indices numpy.random.default_rng(0).choice(clips, k, replace=False), sorted, k as many as fit.
+The inputs are seeded: the same arguments give the same inputs on every run.
+
+A --full N = 1 run (headline workload, no measurement switches) also times, after the headline region and outside it: the headline
 workload over 1000 single-stream steps with time AND shader clock taken from those same launches (`secondary.cfg2`: the stable figure
 rounds are compared on; its `cycles_per_launch` is the only one whose factors share launches), four independent batches per launch
 (`secondary.cfg2_x4`, ss_mfcc_batches_device), the other BASELINE configurations -- `secondary.cfg3`, `secondary.cfg5` (1000 steps
@@ -33,8 +42,9 @@ tail under the next ones' heads; whole-job throughput, not a kernel duration and
 
 Rank 0 prints ONE JSON line.  `roofline.achieved` = algorithmic bytes per launch (4 B per input
 sample + 4 B per output element) / average launch duration measured with HIP events
-on the launch stream over the timed (path-only when N > 1) region.  `cpu_baseline` = the oracle's
-reference-shaped single-thread f32 port (oracle/ss_oracle.c, "port") timed on this host on a bounded sample.
+on the launch stream over the timed (path-only when N > 1) region.  With --full: `roofline` adds the stored
+PMC traffic, the shader clock and the board's power, and `cpu_baseline` = the oracle's reference-shaped
+single-thread f32 port (oracle/ss_oracle.c, "port") timed on this host on a bounded sample.
 """
 from __future__ import annotations
 
@@ -70,7 +80,7 @@ WORKLOADS = {
 }
 
 
-# The legs a default N = 1 run appends behind the headline (`secondary.<name>`): name -> (workload, measure_simple arguments).
+# The legs a --full N = 1 run appends behind the headline (`secondary.<name>`): name -> (workload, measure_simple arguments).
 # `python bench.py --leg <name>` runs one of them alone (what tools/profile.sh wraps in rocprofv3 for the batch-table builds).
 #   cfg2: the headline workload and kernel over 1000 single-stream steps, run inside the library -- HIP events around the launches AND
 #     the in-kernel stamps of ALL of those same launches (every wave's cycles / lifetime, summed on the device): the one
@@ -490,6 +500,23 @@ def measure_simple(torch, ss_mod, workload, device, steps, warmup, prewarm_ms=30
     return res
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(torch, out_dir, name, out):
+    """--dump-outputs: `out` (a float32 [clips, ...] block on the device) as out_dir/<name>.npy; above DUMP_MAX_BYTES, the clips
+    numpy.random.default_rng(0).choice(clips, k, replace=False), sorted, with k as many as fit (the same clips on every run)."""
+    import numpy as np
+
+    clips = out.shape[0]
+    per_clip = out[0].numel() * out.element_size()
+    if clips * per_clip > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(clips, DUMP_MAX_BYTES // per_clip, replace=False))
+        out = out[torch.from_numpy(idx).to(out.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), out.cpu().numpy().astype(np.float32, copy=False))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes (RANK / LOCAL_RANK / WORLD_SIZE set) and
     relay rank 0's JSON line.  Runs before this process imports torch or touches the GPU; nothing is re-exec'd."""
@@ -536,21 +563,27 @@ def main():
     ap.add_argument("--kind", default="", choices=["", "mfcc", "mel"], help="run the workload's clips through the other path (mfcc / mel_spectrogram); not the headline config")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="single-thread CPU baseline budget (the all-cores run takes half of it)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines (cfg2 over 1000 steps, the batch-table legs, cfg3, cfg5, cfg4) and value_pipelined that a default N = 1 run appends")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines (cfg2 over 1000 steps, the batch-table legs, cfg3, cfg5, cfg4) and value_pipelined that a --full N = 1 run appends")
     ap.add_argument("--corpus-clips", type=int, default=0, help="cfg4: size of the corpus that is split over the ranks (default 360 000); keeps strong scaling, unlike --clips")
     ap.add_argument("--gather-chunks", type=int, default=8, help="cfg4 with a gather: a rank's shard is computed and gathered in this many chunks, "
                     "chunk i's collective under chunk i+1's kernel")
     ap.add_argument("--ring-mib", type=int, default=300, help="size of the rotated input ring (measurement aid: below 256 MiB the Infinity Cache serves the input)")
     ap.add_argument("--one-device", action="store_true", help="test aid: every rank uses device 0 (gloo instead of RCCL; control flow only)")
     ap.add_argument("--link-gbps", type=float, default=64.0, help="one-way xGMI rate per link assumed by scaling_model (unmeasured here)")
-    ap.add_argument("--leg", default="", choices=[""] + sorted(LEGS), help="run ONE of the default run's secondary legs alone and print its JSON "
+    ap.add_argument("--leg", default="", choices=[""] + sorted(LEGS), help="run ONE of the --full run's secondary legs alone and print its JSON "
                     "(an explicit --steps / --warmup replaces the leg's own; measurement aid: rocprofv3 passes of the batch-table builds)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: CPU baselines, board power and shader clock, "
+                    "stored PMC traffic, and (N = 1, headline workload) the secondary legs and value_pipelined")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's output as DIR/<name>.npy (float32, "
+                    "at most 64 MB: a seeded sample of whole clips beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
 
-    if args.gpus == 1 and not args.no_cpu_baseline:
+    if args.gpus == 1 and args.full and not args.no_cpu_baseline:
         # the CPU leg's port is compiled for this host NOW, before anything touches the GPU (a compiler run is a child process;
         # none is started once the device is initialised), not in the middle of the run
         import oracle_c
@@ -781,7 +814,7 @@ def main():
         e0.record(stream)
         t0 = time.perf_counter()
         for i in range(steps):
-            reg.step(i)
+            last_out = reg.step(i)
             reg.after_step(i, i + 1 == steps)
             if args.streams == 1 and steps >= 200 and (i + 1) % seg_every == 0 and i + 1 < steps:  # (an event between launches costs ~1 us)
                 ev = torch.cuda.Event(enable_timing=True)
@@ -807,13 +840,14 @@ def main():
         segs = sorted(a_ev.elapsed_time(b_ev) * 1e3 / (b_i - a_i) for (a_i, a_ev), (b_i, b_ev) in zip(marks[:-1], marks[1:]) if b_i > a_i)
         comm_ms = [c0.elapsed_time(c1) for c0, c1, _ in reg.comm_events]
         comm_steps = sum(n for _, _, n in reg.comm_events)
-        return {"elapsed": elapsed, "dev_ms": e0.elapsed_time(e1), "segs": segs, "comm_ms": comm_ms, "comm_steps": comm_steps}
+        return {"elapsed": elapsed, "dev_ms": e0.elapsed_time(e1), "segs": segs, "comm_ms": comm_ms, "comm_steps": comm_steps,
+                "last_out": last_out[:clips]}  # (a cfg4 bucket is padded to the largest shard)
 
     warm = Region(True)
     board = None
     if args.prewarm_ms > 0:  # leave the idle power state before the (possibly few) warm-up steps
         pre = Region(False)
-        probe = BoardProbe(torch, device) if rank == 0 else None  # socket power / shader clock while these launches run
+        probe = BoardProbe(torch, device) if rank == 0 and args.full else None  # socket power / shader clock while these launches run
         t_end = time.perf_counter() + args.prewarm_ms * 1e-3
         k = 0
         while time.perf_counter() < t_end:
@@ -832,19 +866,23 @@ def main():
     t_path = run_timed(False, args.steps)
     t_full = run_timed(True, args.steps) if do_gather else t_path
     elapsed, dev_ms, segs = t_full["elapsed"], t_path["dev_ms"], t_path["segs"]
+    if args.dump_outputs and rank == 0:
+        # before anything else launches into the output ring: the block of the last step of the region `value` comes from
+        dump_outputs(torch, args.dump_outputs, "mfcc" if kind == "mfcc" else "mel_spectrogram", t_full["last_out"])
 
     # Shader clock during the launches (512-point MFCC kernel only): thirty more launches right behind the timed ones through the
     # library's per-call diagnostic ss_mfcc_shader_clock (per-wave lifetime in shader cycles / on the 100 MHz clock, written into
-    # a buffer that call owns)
+    # a buffer that call owns).  --full only: these launches are a run of their own.
     clock_ghz = None
-    if world == 1 and kind == "mfcc" and lib.ss_last_kernel_name().decode().startswith("ss_mfcc_c256<") and args.streams == 1:
+    clock_full = args.full and world == 1 and args.streams == 1
+    if clock_full and kind == "mfcc" and lib.ss_last_kernel_name().decode().startswith("ss_mfcc_c256<"):
         g = C.c_float(0.0)
         torch.cuda.synchronize()
         rc = lib.ss_mfcc_shader_clock(cfg.handle, xs[0].data_ptr(), clips, n_samples, n_samples, outs[0].data_ptr(), sptr, 30, C.byref(g))
         if rc == 0 and g.value > 0:
             clock_ghz = float(g.value)
     clock_source = "in-kernel stamps of the same launches (ss_mfcc_shader_clock)"
-    if clock_ghz is None and world == 1 and args.streams == 1:
+    if clock_ghz is None and clock_full:
         # every other kernel: the library's one-wave probe beside more launches of the same step (ss_shader_clock_probe)
         clock_ghz = probe_clock(torch, lib, lambda i: Region(False).step(i), dev_ms * 1e-3 / args.steps, device)
         clock_source = "one-wave probe beside the same launches (ss_shader_clock_probe)"
@@ -913,7 +951,8 @@ def main():
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS,
-                **load_profile(kernel, args.workload, headline=not (args.params or args.kind or args.clips or args.force_generic)),
+                **(load_profile(kernel, args.workload, headline=not (args.params or args.kind or args.clips or args.force_generic))
+                   if args.full else {}),  # (stored figures, checked against this run's kernel: --full)
                 "algorithmic_bytes_per_launch": bytes_per_launch,
                 "avg_launch_us": avg_launch_s * 1e6,
                 "launch_us_median_min_max_over_tenths": [segs[len(segs) // 2], segs[0], segs[-1]],
@@ -950,14 +989,14 @@ def main():
                 "note": "root mode: (N-1) peers each fill one direct link into rank 0; the bound counts N producers at one link's rate each "
                         "(rank 0's own block needs no link, so it is slightly pessimistic); unmeasured on hardware",
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(kind, pkw, n_samples, args.cpu_seconds)
             res["cpu_baseline_all_cores"] = cpu_baseline_all_cores(kind, pkw, n_samples, args.cpu_seconds / 2)
         if board:
             res["roofline"]["board"] = board
             if board.get("power_w_mean") and args.streams == 1:
                 res["roofline"]["energy_mj_per_launch"] = board["power_w_mean"] * avg_launch_s * 1e3  # (see measure_simple)
-        headline = world == 1 and args.workload == "cfg2" and args.streams == 1 and not (
+        headline = args.full and world == 1 and args.workload == "cfg2" and args.streams == 1 and not (
             args.params or args.kind or args.clips or args.force_generic or args.no_secondary or args.ring_mib != 300)
         if clock_ghz is not None:
             rf = res["roofline"]

@@ -129,11 +129,6 @@ def test_mirrors_carry_the_reference_signatures_of_the_two_stage_functions():
     assert ("pub fn stack_frames(signal: ArrayView1<f32>, sample_rate: usize, frame_length: f32, frame_stride: f32, "
             "filter: Option<fn(usize) -> Array2<f32>>, zero_padding: bool) -> Array2<f32>") in flat
     assert "pub fn power_spectrum(frames: Array2<f32>, fft_points: usize) -> Array2<f32>" in flat
-    ref = re.sub(r"/\*.*?\*/", "", open("/root/reference/speechsauce/src/processing.rs").read(), flags=re.S) if os.path.exists("/root/reference") else None
-    if ref is not None:  # (this container only: the GPU box has no reference checkout)
-        rflat = re.sub(r"\s+", " ", ref)
-        assert "pub fn stack_frames( signal: ArrayView1<f32>, sample_rate: usize, frame_length: f32, frame_stride: f32, filter: Option<fn(usize) -> Array2<f32>>, zero_padding: bool, ) -> Array2<f32>" in rflat
-        assert "pub fn power_spectrum(frames: Array2<f32>, fft_points: usize ) -> Array2<f32>" in rflat
     hpp = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "speechsauce_amd.hpp")).read())
     assert ("inline Array2 stack_frames(const float *signal, std::size_t n, std::size_t sample_rate, float frame_length, float frame_stride, "
             "FrameFilter filter, bool zero_padding)") in hpp
@@ -166,12 +161,6 @@ def test_rust_shim_is_drop_in_by_module_path_on_paper():
         assert names <= body, (mod, names - body)
         for n in names:  # and every re-exported name is defined at the crate root
             assert re.search(r"pub (fn|struct|trait) %s\b" % n, rs), n
-    if os.path.exists("/root/reference"):  # (this container only) the lists above are the reference's public items
-        ref_lib = open("/root/reference/speechsauce/src/lib.rs").read()
-        assert set(re.findall(r"^pub mod (\w+);", ref_lib, flags=re.M)) == set(want)
-        for mod in ("feature", "processing", "functions"):
-            ref = open(f"/root/reference/speechsauce/src/{mod}.rs").read()
-            assert set(re.findall(r"^pub fn (\w+)", ref, flags=re.M)) == want[mod], mod
     # Clone over a shared handle; the handle is destroyed once, by the last clone
     assert "#[derive(Clone)] pub struct SpeechConfig {" in flat
     assert "handle: Arc<Handle>," in flat and "impl Drop for Handle" in flat and "impl Drop for SpeechConfig" not in flat
@@ -181,13 +170,6 @@ def test_rust_shim_is_drop_in_by_module_path_on_paper():
         "sample_rate": "usize", "window_size": "usize", "window_size_half": "usize", "frame_length": "f32", "frame_stride": "f32",
         "num_cepstral": "usize", "num_filters": "usize", "low_frequency": "f32", "high_frequency": "f32", "freq_size": "usize",
         "frame_size": "usize", "dc_elimination": "bool", "wnorm": "f32", "window": "Vec<f32>"}
-    if os.path.exists("/root/reference"):
-        ref = open("/root/reference/speechsauce/src/config.rs").read()
-        body = re.search(r"pub struct SpeechConfig \{(.*?)\n\}", ref, flags=re.S).group(1)
-        ref_fields = dict(re.findall(r"pub (\w+):\s*([^,]+),", re.sub(r"//[^\n]*", "", body)))
-        plain = {k: v for k, v in ref_fields.items() if v in ("usize", "f32", "bool", "Vec<f32>")}
-        assert plain == dict(pub_fields)  # every plain-data field; the plan / state objects are documented as absent
-        assert set(ref_fields) - set(plain) == {"analysis_mem", "dct_handler", "fft_handler", "fft_forward", "analysis_scratch"}
     # the try_ form reports instead of asserting (round-4 advisor finding)
     body = re.search(r"pub fn try_stack_frames\(.*?\n\}", rs, flags=re.S).group(0)
     assert "assert" not in body and "SS_ERR_ARG" in body and "u32::MAX" in body
@@ -207,9 +189,6 @@ def test_rust_shim_paper_compile_guards():
     assert "impl<A: num_traits::real::Real, I: Dimension> ArrayLog<A, I> for Array<A, I>" in flat
     cargo = open(os.path.join(os.path.dirname(os.path.dirname(SHIM)), "Cargo.toml")).read()
     assert re.search(r'^num-traits\s*=', cargo, flags=re.M) and re.search(r'^ndarray\s*=\s*"\^0\.15"', cargo, flags=re.M)
-    if os.path.exists("/root/reference"):
-        ref = re.sub(r"\s+", " ", open("/root/reference/speechsauce/src/util.rs").read())
-        assert "pub trait ArrayLog<A: num_traits::real::Real, I: ndarray::Dimension> { fn log(self) -> Array<A, I>; }" in ref
     # 3. slices handed to ArrayView2::from_shape are plain &[f32]
     assert flat.count("ArrayView2::from_shape((1, x.len()), &x[..])") == 2 and "from_shape((1, x.len()), &x)" not in flat
     # 4. every extern declaration is called somewhere, and every call of an ss_ function has a declaration

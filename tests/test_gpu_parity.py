@@ -994,7 +994,7 @@ def test_cfg4_corpus_properties(ss, oracle):
 
 
 def test_bench_default_line_carries_the_contract_and_the_secondary_configs():
-    """The driver's command (`python bench.py --steps 20 --warmup 5`, here with a short CPU leg): ONE JSON line with the contract's
+    """The driver's command with --full (`python bench.py --steps 20 --warmup 5 --full`, here with a short CPU leg): ONE JSON line with the contract's
     keys, `roofline` and `cpu_baseline` (the port built on this host, its flags named), the other BASELINE configurations
     (`secondary`: the kernels of BENCH_KERNELS, the ones the parity tests above compare with the oracle), the four-stream figure with
     its one-stream twin, and -- round 6 -- `secondary.cfg2` (time and clock from the same 1000 launches) and `secondary.cfg2_x4`."""
@@ -1003,7 +1003,7 @@ def test_bench_default_line_carries_the_contract_and_the_secondary_configs():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--cpu-seconds", "1"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--cpu-seconds", "1", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
