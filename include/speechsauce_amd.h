@@ -223,6 +223,34 @@ int ss_stft_device(const ss_config *cfg, const float *d_x, size_t channels, size
 int ss_stack_frames_device(const ss_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld,
                            float *d_frames, void *stream);
 
+/* ---- packed variable-length clips (a loop over speechsauce::feature::mfcc / mfe, feature.rs:99-148 / :200-233, per clip) ----
+ * Clips of different lengths packed end to end in one float buffer: clip b is x[so[b] : so[b+1]], so = sample_offsets, n_clips + 1
+ * non-decreasing entries with so[0] = 0 (the cu_seqlens convention).  Features are packed in clip order: clip b owns rows
+ * fo[b] .. fo[b+1] of [total_frames x num_cepstral] (mfcc) or [total_frames x num_filters] + [total_frames] (mfe), fo =
+ * frame_offsets.  Per clip, every result is what ss_mfcc / ss_mfe returns for that clip alone: its own frame count T_b and DCT
+ * scaling (n = T_b * M, feature.rs:126-131), its [0,0] element, pre-emphasis modulo its own length, literal framing's T_b > 2 rule,
+ * centred / padded framing at its own edges.  n_clips == 0 is SS_OK with nothing launched.
+ * Every call is ONE launch.  MFCC of the headline shape (fft_points 512 with the default frame shape and bank, contract framing,
+ * reference DCT, no window / pre-emphasis) runs on the varlen build of that shape's dedicated kernel: per clip the same bits as
+ * ss_mfcc_batch_device.  Every other configuration, and mfe, runs on the varlen build of the generic kernel (any fft_points, chirp-z
+ * included; windows, pre-emphasis, every framing, ortho DCT, spectrum_exponent 2, librosa banks): per clip the same bits as the
+ * generic kernel's equal-length path.  The dedicated 256 / 1024 / 2048 / 4096-point kernels have no varlen builds. */
+/* host only, no device needed: fo[0..n_clips] for clips x[so[b] : so[b+1]]; SS_ERR_SHORT_SIGNAL names the first clip with zero
+ * frames (ss_last_error_string), SS_ERR_ARG for decreasing offsets / so[0] != 0 / a clip of more than 2^31 - 1 samples */
+int ss_packed_frame_offsets(const ss_params *p, size_t n_clips, const int64_t *sample_offsets, int64_t *frame_offsets);
+/* host pointers (H2D, one device call, D2H); sample_offsets is a host array.  out: [fo[n_clips] x num_cepstral] */
+int ss_mfcc_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out);
+int ss_mfe_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *feat, float *energy);
+/* device pointers, asynchronous on `stream`, graph-capturable: d_sample_offsets / d_frame_offsets are DEVICE arrays of n_clips + 1
+ * entries (fo from ss_packed_frame_offsets, or computed by the caller on the device); total_frames = the rows d_out holds.  The
+ * kernel checks the tables against each other: a clip whose rows are not the T_b frames its samples give, or that end past
+ * total_frames, is skipped (nothing is written outside d_out / d_energy) and the config's device error word is raised -- the next
+ * call on the config (or ss_config_device_status) returns SS_ERR_DEVICE. */
+int ss_mfcc_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                          const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream);
+int ss_mfe_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                         const int64_t *d_frame_offsets, size_t total_frames, float *d_feat, float *d_energy, void *stream);
+
 /* ss_stack_frames_signal on device pointers (d_window: frame_len floats in device memory, or NULL) */
 int ss_stack_frames_signal_device(const float *d_x, size_t n_samples, uint32_t sample_rate, float frame_length, float frame_stride,
                                   const float *d_window, int zero_padding, float *d_frames, void *stream);

@@ -906,6 +906,143 @@ int host_pipeline(const ss_config *cfg, const float *x, size_t units, size_t n, 
     return rc;
 }
 
+// ---- packed variable-length clips (ss_*_packed*) ---------------------------------------------------
+// Clip b is d_x[so[b] : so[b+1]], its features rows fo[b] .. fo[b+1] of out0 (and out1); the offset tables are device arrays, read
+// by the kernel only (nothing of them passes through the host here: the launch is graph-capturable).  One launch over every
+// clip's frames; the kernel checks the tables against each other (VarlenArgs, ss_device.h).
+int launch_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n_clips, const int64_t *d_so, const int64_t *d_fo,
+                  size_t total_frames, float *out0, float *out1, hipStream_t stream)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_clips == 0) return SS_OK;
+    if (!d_x || !d_so || !d_fo || !out0 || (out_kind == ss::OUT_MFE && !out1)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_clips > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many clips");
+    {
+        const int drc = check_device(cfg);  // see launch_frames
+        if (drc) return drc;
+        const int erc = pending_device_error(cfg);
+        if (erc) return erc;
+    }
+    const ss::HostTables &h = cfg->host;
+    ss::FrontArgs a{};
+    fill_common(cfg, a);
+    a.x = d_x;
+    a.flen = h.d.flen;
+    a.step = h.d.step;
+    // literal framing: the kernel picks FRAME_ZERO / FRAME_FIRST from each clip's frame count
+    if (h.params.framing == SS_FRAMING_CENTER) a.frame_mode = ss::FRAME_CENTER;
+    else if (h.params.framing == SS_FRAMING_PADDED) a.frame_mode = ss::FRAME_PADDED;
+    else a.frame_mode = ss::FRAME_NORMAL;
+    a.pad_reflect = h.params.pad_mode == SS_PAD_REFLECT;
+    a.preemph = h.params.preemph_coef;
+    a.preemph_shift = static_cast<uint32_t>(h.params.preemph_shift > 0 ? h.params.preemph_shift : 1);
+    a.window = cfg->d_window_mfcc;
+    a.scale = 1.0f / static_cast<float>(h.params.fft_points);  // processing.rs:180
+    const float g = h.params.dct2_gain;
+    const float M = static_cast<float>(h.params.num_filters);
+    if (h.params.dct_norm == SS_DCT_ORTHO) {  // as launch_frames; the reference scaling is formed per clip on the device
+        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * M));
+        a.dct_scale_0 = a.dct_scale_00 = g * (1.0f / sqrtf(4.0f * M));
+    } else {
+        a.dct_scale_0 = g;
+    }
+    a.out_kind = out_kind;
+    a.out0 = out0;
+    a.out1 = out1;
+    ss::VarlenArgs v{};
+    v.so = reinterpret_cast<const long long *>(d_so);
+    v.fo = reinterpret_cast<const long long *>(d_fo);
+    v.total_frames = total_frames;
+    v.n_clips = static_cast<uint32_t>(n_clips);
+    v.framing = h.params.framing;
+    v.pad_reflect = a.pad_reflect;
+    v.dct_ortho = h.params.dct_norm == SS_DCT_ORTHO;
+    v.dct2_gain = g;
+    v.err = cfg->d_err;
+    ss::LaunchInfo info{};
+    // the headline shape (512-point MFCC, default frame shape and bank): the varlen build of the dedicated kernel -- the same bits as
+    // ss_mfcc_batch_device per clip; hipErrorInvalidValue before the launch for every other configuration
+    if (cfg->fast.ok && !cfg->fast.fullp && out_kind == ss::OUT_MFCC && !ss::dbg_force_generic()) {
+        ss::Fast512Args f{};
+        f.x = d_x;
+        f.flen = a.flen;
+        f.step = a.step;
+        f.scale = a.scale;
+        f.spectrum_exponent = a.spectrum_exponent;
+        f.tab = cfg->d_fast_tab;
+        f.mel_wpitch = cfg->fast.wpitch;
+        for (int s = 0; s < 3; ++s) f.mel_q4[s] = cfg->fast.q4[s];
+        f.n_filters = a.n_filters;
+        f.n_ceps = a.n_ceps;
+        f.dct_scale_k = a.dct_scale_k;
+        f.dct_scale_0 = a.dct_scale_0;
+        f.dct_scale_00 = a.dct_scale_00;
+        f.dc_elimination = a.dc_elimination;
+        f.out = out0;
+        f.win_floats = a.window ? cfg->fast.win_floats : 0;
+        f.preemph = a.preemph;
+        f.preemph_shift = a.preemph_shift;
+        f.center = a.frame_mode == ss::FRAME_CENTER;
+        f.pad_reflect = a.pad_reflect;
+        f.fullp = cfg->fast.fullp;
+        f.paired = cfg->fast.paired ? (cfg->fast.tight ? 2 : 1) : 0;
+        const hipError_t ef = ss::launch_mfcc_c256_varlen(f, v, stream, cfg->num_cus, &info);
+        if (ef == hipSuccess) {
+            g_last_kernel = info.kernel_name;
+            return SS_OK;
+        }
+        if (ef != hipErrorInvalidValue) return hip_fail(ef, "launch_mfcc_c256_varlen");
+    }
+    const hipError_t e = ss::launch_front_generic_varlen(a, v, h.d.log2c, stream, cfg->num_cus, &info);
+    if (e != hipSuccess) return hip_fail(e, "launch_front_generic_varlen");
+    g_last_kernel = info.kernel_name;
+    return SS_OK;
+}
+
+// Host-pointer form: the frame offsets from the host's sample offsets, one upload, one launch, one download on the config's
+// first host-pipeline stream (the host calls of a config are serialised by its mutex).
+int packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_clips, const int64_t *so, float *out0, float *out1)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_clips == 0) return SS_OK;
+    if (!x || !so || !out0 || (out_kind == ss::OUT_MFE && !out1)) return ss::fail(SS_ERR_ARG, "null buffer");
+    std::vector<int64_t> fo(n_clips + 1);
+    int rc = ss_packed_frame_offsets(&cfg->host.params, n_clips, so, fo.data());
+    if (rc) return rc;
+    if ((rc = check_device(cfg))) return rc;
+    const size_t rows = static_cast<size_t>(fo[n_clips]), samples = static_cast<size_t>(so[n_clips]);
+    const size_t cols = out_kind == ss::OUT_MFCC ? cfg->host.params.num_cepstral : cfg->host.params.num_filters;
+    ss_config::HostPipe &hp = cfg->pipe;
+    std::lock_guard<std::mutex> lock(hp.mu);
+    if (!hp.stream[0]) {
+        SS_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
+        SS_HIP(hipEventCreateWithFlags(&hp.done[0], hipEventDisableTiming));
+    }
+    hipStream_t st = hp.stream[0];
+    DeviceBuf dx, dso, dfo, d0, d1;
+    if ((rc = dx.alloc(samples * sizeof(float))) || (rc = dso.alloc((n_clips + 1) * sizeof(int64_t))) ||
+        (rc = dfo.alloc((n_clips + 1) * sizeof(int64_t))) || (rc = d0.alloc(rows * cols * sizeof(float))) ||
+        (out1 && (rc = d1.alloc(rows * sizeof(float)))))
+        return rc;
+    hipError_t e = hipMemcpyAsync(dx.p, x, samples * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dfo.p, fo.data(), (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
+    if (rc == SS_OK)
+        rc = launch_packed(cfg, out_kind, dx.as<const float>(), n_clips, dso.as<const int64_t>(), dfo.as<const int64_t>(), rows,
+                           d0.as<float>(), out1 ? d1.as<float>() : nullptr, st);
+    if (rc == SS_OK) {
+        e = hipMemcpyAsync(out0, d0.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out1) e = hipMemcpyAsync(out1, d1.p, rows * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (D2H)");
+    }
+    // the copies may still touch the caller's buffers and ours: synchronise whatever happened
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "packed host call");
+    if (rc == SS_OK) rc = pending_device_error(cfg);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1108,6 +1245,30 @@ int ss_mfe_batch_device(const ss_config *cfg, const float *d_x, size_t batch, si
 {
     if (!d_energy) return ss::fail(SS_ERR_ARG, "null buffer");
     return launch_frames(cfg, ss::OUT_MFE, d_x, batch, n_samples, ld, d_feat, d_energy, static_cast<hipStream_t>(stream));
+}
+
+int ss_mfcc_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                          const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream)
+{
+    return launch_packed(cfg, ss::OUT_MFCC, d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, nullptr,
+                         static_cast<hipStream_t>(stream));
+}
+
+int ss_mfe_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                         const int64_t *d_frame_offsets, size_t total_frames, float *d_feat, float *d_energy, void *stream)
+{
+    return launch_packed(cfg, ss::OUT_MFE, d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_feat, d_energy,
+                         static_cast<hipStream_t>(stream));
+}
+
+int ss_mfcc_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out)
+{
+    return packed_host(cfg, ss::OUT_MFCC, x, n_clips, sample_offsets, out, nullptr);
+}
+
+int ss_mfe_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *feat, float *energy)
+{
+    return packed_host(cfg, ss::OUT_MFE, x, n_clips, sample_offsets, feat, energy);
 }
 
 // lmfe (feature.rs:242-245): ln of mfe's zero-handled filterbank energies.  The frame energies mfe also returns are

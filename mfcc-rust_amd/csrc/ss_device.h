@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "speechsauce_amd.h"
+
 // Product / lab builds.  The shipped library is the PRODUCT build: kernel selection is a pure function of the configuration
 // and the call -- no environment knob is read anywhere, and the timing-attribution switches of the headline kernel
 // (SS_ABLATE) are compiled out.  `make lab` (-DSS_LAB=1) builds libspeechsauce_amd_lab.so with the A/B knobs (SS_RES,
@@ -93,6 +95,90 @@ struct LaunchInfo {
 // Generic front-end (any power-of-two fft_points in [32, 4096]; with a.blu_n != 0 the chirp-z build for other lengths, log2c then
 // being the length of its complex FFT).
 hipError_t launch_front_generic(const FrontArgs &a, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info);
+
+// Packed variable-length clips (ss_mfcc_packed_device / ss_mfe_packed_device): clip b is x[so[b] : so[b+1]], its frames are rows
+// fo[b] .. fo[b+1] of the output.  Both tables are device arrays the host may never have seen, so the kernels recompute every
+// clip's frame count from `so` (the host's ss::num_frames in f32, bit for bit) and skip -- and report through `err` -- a clip whose
+// rows disagree with it or end past total_frames.  The per-clip DCT scales (feature.rs:126-131, n = T_b * M) are formed on the
+// device with correctly rounded operations: the same bits as the host's for an equal-length batch of that clip.
+struct VarlenArgs {
+    const long long *so;  // [n_clips + 1] sample offsets
+    const long long *fo;  // [n_clips + 1] frame (output row) offsets
+    unsigned long long total_frames;  // rows of the output block
+    uint32_t n_clips;
+    int32_t framing;      // SS_FRAMING_* (literal framing: FRAME_ZERO / FRAME_FIRST from each clip's own T_b)
+    int32_t pad_reflect;  // centred frames: clips of <= flen / 2 samples have no frames with np.pad 'reflect'
+    int32_t dct_ortho;    // SS_DCT_ORTHO: the scales do not depend on T_b (FrontArgs / Fast512Args carry them)
+    float dct2_gain;
+    unsigned *err;        // the config's device error word (set to kVarlenError on a bad clip)
+};
+constexpr unsigned kVarlenError = 2u;
+
+// Frames of a clip of L samples, as ss::num_frames computes them on the host (processing.rs:101 in f32; padded: ceil; centred:
+// 1 + L / step).  0: the clip yields none (the host rejects it) or is longer than 2^31 - 1 samples.
+__device__ __forceinline__ unsigned varlen_frames(const VarlenArgs &v, uint32_t flen, uint32_t step, long long L)
+{
+    if (L < 0 || L > 0x7fffffffll) return 0u;
+    const unsigned n = static_cast<unsigned>(L);
+    if (v.framing == SS_FRAMING_CENTER) return (n == 0u || (v.pad_reflect && n <= flen / 2)) ? 0u : 1u + n / step;
+    if (n < flen) return 0u;
+    const float q = __fdiv_rn(__uint2float_rn(n - flen), __uint2float_rn(step));
+    return static_cast<unsigned>(v.framing == SS_FRAMING_PADDED ? ceilf(q) : floorf(q));
+}
+
+// Clip b of a packed launch: where its samples start, how many there are, its frame count and its first output row.  ok: the
+// offsets agree with each other (rows fo[b] .. fo[b+1] are exactly the T_b frames `so` implies, inside the output block).
+struct VarClip {
+    long long s0, f0;
+    unsigned n, T;
+    bool ok;
+};
+__device__ __forceinline__ VarClip varlen_clip(const VarlenArgs &v, uint32_t flen, uint32_t step, unsigned b)
+{
+    VarClip c;
+    c.s0 = v.so[b];
+    c.f0 = v.fo[b];
+    const long long s1 = v.so[b + 1], f1 = v.fo[b + 1];
+    c.T = varlen_frames(v, flen, step, s1 - c.s0);
+    c.n = static_cast<unsigned>(s1 - c.s0);
+    c.ok = c.T > 0u && c.s0 >= 0 && c.f0 >= 0 && f1 - c.f0 == static_cast<long long>(c.T) &&
+           static_cast<unsigned long long>(f1) <= v.total_frames;
+    return c;
+}
+// The clip that owns output row g: the last b < n_clips with fo[b] <= g (binary search; any b for offsets that are not
+// non-decreasing -- varlen_clip then finds them inconsistent, or g outside the clip's rows).
+__device__ __forceinline__ unsigned varlen_find(const VarlenArgs &v, unsigned long long g)
+{
+    unsigned lo = 0u, hi = v.n_clips;
+    const long long gs = static_cast<long long>(g);
+    while (hi - lo > 1u) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (v.fo[mid] <= gs) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// feature.rs:126-131 for a clip of T frames (n = T * M as f32): the host's g * (1 / sqrtf(2 n)) and g * (1 / sqrtf(4 n)),
+// correctly rounded step by step.  (sqrtf and the division are correctly rounded in HIP's default fp32 mode; __fsqrt_rn is not
+// here -- it maps to the native square root unless OCML_BASIC_ROUNDED_OPERATIONS is defined.)
+__device__ __forceinline__ void varlen_dct_scales(const VarlenArgs &v, unsigned T, unsigned M, float &scale_k, float &scale_00)
+{
+    const float nn = __ull2float_rn(static_cast<unsigned long long>(T) * M);
+    scale_k = __fmul_rn(v.dct2_gain, __fdiv_rn(1.0f, sqrtf(__fmul_rn(2.0f, nn))));
+    scale_00 = __fmul_rn(v.dct2_gain, __fdiv_rn(1.0f, sqrtf(__fmul_rn(4.0f, nn))));
+}
+// One pass over the clips, spread over the grid: a clip whose offsets are inconsistent sets the error word (its frames are
+// skipped where they are computed).  A vector store to the pinned word.
+__device__ __forceinline__ void varlen_check_clips(const VarlenArgs &v, uint32_t flen, uint32_t step, unsigned tid, unsigned nthreads)
+{
+    bool bad = false;
+    for (unsigned b = tid; b < v.n_clips; b += nthreads) bad |= !varlen_clip(v, flen, step, b).ok;
+    if (bad && v.err) __hip_atomic_store(v.err, kVarlenError, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// every configuration (fft_points, windows, pre-emphasis, framing, DCT norm, exponent, banks): the varlen build of
+// ss_front_generic.  a: as for launch_front_generic with x = the packed samples; batch / n_samples / n_frames are unused.
+hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
+                                       LaunchInfo *info);
 #if SS_LAB
 // Test aid (lab library): every word of every CU's LDS := 0xFFFFFFFF (ss_debug_poison_lds).
 hipError_t launch_poison_lds(hipStream_t stream, int num_cus);
@@ -169,6 +255,10 @@ struct MultiArg<true> {
 // hipErrorInvalidValue before the launch: the configuration has no multi-batch build (the caller launches batch by batch).
 hipError_t launch_mfcc_c256_multi(const Fast512Args &a, int n_batches, const float *const *d_x, float *const *d_out, const size_t *clips,
                                   hipStream_t stream, int num_cus, LaunchInfo *info);
+// Packed variable-length clips on the headline build (MFCC, default frame shape and bank, contract framing, reference DCT): one launch
+// over the packed output rows (VarlenArgs, declared below).  hipErrorInvalidValue before the launch for every other configuration.
+struct VarlenArgs;
+hipError_t launch_mfcc_c256_varlen(const Fast512Args &a, const VarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
 // whether the kernel has an mfe-output / windowed / pre-emphasised build for this shape (the default bank at flen 320)
 bool mfcc_c256_has_mfe(const Fast512Args &a);
 

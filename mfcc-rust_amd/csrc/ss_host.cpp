@@ -1290,6 +1290,27 @@ int ss_num_frames(const ss_params *p, size_t n_samples, size_t *n_frames)
     return SS_OK;
 }
 
+int ss_packed_frame_offsets(const ss_params *p, size_t n_clips, const int64_t *sample_offsets, int64_t *frame_offsets)
+{
+    if (!p || !sample_offsets || !frame_offsets) return ss::fail(SS_ERR_ARG, "null argument");
+    int rc = ss::validate(*p);
+    if (rc) return rc;
+    if (sample_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "sample_offsets[0] must be 0");
+    int64_t rows = 0;
+    frame_offsets[0] = 0;
+    for (size_t b = 0; b < n_clips; ++b) {
+        const int64_t len = sample_offsets[b + 1] - sample_offsets[b];
+        if (len < 0) return ss::fail(SS_ERR_ARG, "sample_offsets decrease at clip " + std::to_string(b));
+        if (len > 0x7fffffff) return ss::fail(SS_ERR_ARG, "clip " + std::to_string(b) + " is longer than 2^31 - 1 samples");
+        size_t t = 0;
+        rc = ss::num_frames(*p, static_cast<size_t>(len), t);
+        if (rc) return ss::fail(rc, "clip " + std::to_string(b) + " (" + std::to_string(len) + " samples): " + std::string(ss::last_error()));
+        rows += static_cast<int64_t>(t);
+        frame_offsets[b + 1] = rows;
+    }
+    return SS_OK;
+}
+
 int ss_stft_sizes(const ss_params *p, size_t *hop, size_t *n_pad, float *wnorm)
 {
     if (!p || !hop || !n_pad || !wnorm) return ss::fail(SS_ERR_ARG, "null argument");

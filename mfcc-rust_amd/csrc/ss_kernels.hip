@@ -2,6 +2,8 @@
 //
 // ss_front_generic<LOG2C>: framing -> (pre-emphasis, window) -> R2C FFT -> magnitude/power ->
 // sparse mel -> log -> DCT-II, one launch, any power-of-two fft_points in [32, 4096].
+// ss_front_generic<LOG2C, BLU, VarlenArgs> (reported as ss_front_generic_varlen<LOG2C>): the same MFCC / mfe path over packed
+// clips of different lengths (VarlenArgs, ss_device.h).
 //
 //   * A real frame of N = 2C samples is packed as C complex points z[n] = x[2n] + i x[2n+1]
 //     and transformed by a Stockham autosort FFT whose butterflies live in registers: every
@@ -229,9 +231,21 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
     return s;
 }
 
-template <int LOG2C, bool BLU>
-__global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a)
+// VAR: packed variable-length clips (launch_front_generic_varlen): the flat frame index is the output row, and the clip / frame
+// split, the clip's samples, its length, its literal-framing mode and its DCT scales come from the offset tables (VarlenArgs).
+// (V: empty, or one VarlenArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
+template <typename... V>
+__device__ __forceinline__ const VarlenArgs *varlen_of(const V &...v)
 {
+    if constexpr (sizeof...(V) == 0) return nullptr;
+    else return (&v, ...);
+}
+
+template <int LOG2C, bool BLU, typename... V>
+__global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
+{
+    constexpr bool VAR = sizeof...(V) > 0;
+    [[maybe_unused]] const VarlenArgs *va = varlen_of(vargs...);
     using G = Geo<LOG2C>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
@@ -250,35 +264,53 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a)
     // MEL mode: transposed output tile [M][rows_tile + 1] after all slots
     float *tile = reinterpret_cast<float *>(smem_raw + slot_bytes * G::FPB);
 
-    const bool mel_mode = a.out_kind == OUT_MEL || a.out_kind == OUT_STFT;
+    const bool mel_mode = !VAR && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT);
     const int F = BLU ? static_cast<int>(a.blu_n / 2 + 1) : G::F;  // bins per row
 
     if (!mel_mode) {
         // ---------------- MFCC / MFE / power-spectrum path: flat list of B*T frames ----------------
-        const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
+        if constexpr (VAR) varlen_check_clips(*va, a.flen, a.step, blockIdx.x * kBlock + tid, gridDim.x * kBlock);
+        const unsigned long long total = VAR ? va->total_frames : static_cast<unsigned long long>(a.batch) * a.n_frames;
         const unsigned long long groups = (total + G::FPB - 1) / G::FPB;
         for (unsigned long long g = blockIdx.x; g < groups; g += gridDim.x) {
             const unsigned long long gf = g * G::FPB + slot;
-            const bool active = gf < total;
-            const unsigned gf32 = static_cast<unsigned>(gf);  // launch_one rejects batches with >= 2^32 frames
-            const unsigned clip = active ? gf32 / a.n_frames : 0u;
-            const unsigned t = active ? gf32 - clip * a.n_frames : 0u;
-            const float *xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
+            bool active = gf < total;
+            const float *xc;
+            unsigned t;
+            unsigned n_samples = a.n_samples;
+            int frame_mode = a.frame_mode;
+            float dct_scale_k = a.dct_scale_k, dct_scale_00 = a.dct_scale_00;
+            if constexpr (VAR) {
+                // rows past the last clip (a larger output block) are left alone; rows of an inconsistent clip are skipped
+                const VarClip c = varlen_clip(*va, a.flen, a.step, active ? varlen_find(*va, gf) : 0u);
+                active = active && c.ok && static_cast<long long>(gf) >= c.f0 && static_cast<long long>(gf) - c.f0 < static_cast<long long>(c.T);
+                t = active ? static_cast<unsigned>(static_cast<long long>(gf) - c.f0) : 0u;
+                xc = a.x + (active ? c.s0 : 0ll);
+                n_samples = active ? c.n : 1u;
+                // processing.rs:110-120 as written, with the clip's own frame count
+                if (va->framing == SS_FRAMING_LITERAL) frame_mode = c.T > 2u ? FRAME_ZERO : FRAME_FIRST;
+                if (!va->dct_ortho) varlen_dct_scales(*va, c.T, a.n_filters, dct_scale_k, dct_scale_00);
+            } else {
+                const unsigned gf32 = static_cast<unsigned>(gf);  // launch_one rejects batches with >= 2^32 frames
+                const unsigned clip = active ? gf32 / a.n_frames : 0u;
+                t = active ? gf32 - clip * a.n_frames : 0u;
+                xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
+            }
             // stack_frames (processing.rs:65-129, contract framing) + zero pad to N (:147-156)
-            const unsigned base = (a.frame_mode == FRAME_NORMAL || a.frame_mode == FRAME_PADDED) ? t * a.step : 0u;
-            const unsigned lim = a.frame_mode == FRAME_ZERO ? 0u : (a.frame_mode == FRAME_FIRST ? (a.flen & ~1u) : a.flen);
+            const unsigned base = (frame_mode == FRAME_NORMAL || frame_mode == FRAME_PADDED) ? t * a.step : 0u;
+            const unsigned lim = frame_mode == FRAME_ZERO ? 0u : (frame_mode == FRAME_FIRST ? (a.flen & ~1u) : a.flen);
             // sample i of the frame after framing, fused pre-emphasis and the optional window (zero beyond the frame)
             auto sample = [&](unsigned i) -> float {
                 float val = 0.0f;
                 if (active && i < lim) {
                     unsigned idx = base + i;
                     // FRAME_PADDED (stack_frames zero_padding = true, processing.rs:85-97): zeros past the signal
-                    bool inside = a.frame_mode != FRAME_PADDED || idx < a.n_samples;
-                    if (a.frame_mode == FRAME_CENTER) {
+                    bool inside = frame_mode != FRAME_PADDED || idx < n_samples;
+                    if (frame_mode == FRAME_CENTER) {
                         // librosa center=True: the frame is centred on t*step; outside the clip np.pad 'reflect'
                         // (mirror without repeating the edge sample) or zeros
                         long long pos = static_cast<long long>(t) * a.step + i - a.flen / 2;
-                        const long long ns = a.n_samples;
+                        const long long ns = n_samples;
                         if (pos < 0 || pos >= ns) {
                             if (a.pad_reflect) pos = pos < 0 ? -pos : 2 * (ns - 1) - pos;
                             else inside = false;
@@ -288,8 +320,8 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a)
                     if (inside) {
                         val = xc[idx];
                         if (a.preemph != 0.0f) {  // processing.rs:31-53 fused
-                            const unsigned sh = a.preemph_shift % a.n_samples;
-                            const unsigned jdx = idx >= sh ? idx - sh : idx + a.n_samples - sh;
+                            const unsigned sh = a.preemph_shift % n_samples;
+                            const unsigned jdx = idx >= sh ? idx - sh : idx + n_samples - sh;
                             val -= a.preemph * xc[jdx];
                         }
                     }
@@ -366,8 +398,8 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a)
                             float tot = 0.0f;
                             for (int p = 0; p < parts; ++p) tot += red[p * Cc + j];
                             float o;
-                            if (j == 0) o = a.dc_elimination ? fast_ln(energy) : tot * (t == 0 ? a.dct_scale_00 : a.dct_scale_0);
-                            else o = tot * a.dct_scale_k;
+                            if (j == 0) o = a.dc_elimination ? fast_ln(energy) : tot * (t == 0 ? dct_scale_00 : a.dct_scale_0);
+                            else o = tot * dct_scale_k;
                             if (active) a.out0[gf * Cc + j] = o;
                         }
                     } else {
@@ -376,8 +408,8 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a)
                             float s = 0.0f;
                             for (int m = 0; m < M; ++m) s = fmaf(frow[m], row[m], s);
                             float o;
-                            if (c == 0) o = a.dc_elimination ? fast_ln(energy) : s * (t == 0 ? a.dct_scale_00 : a.dct_scale_0);
-                            else o = s * a.dct_scale_k;
+                            if (c == 0) o = a.dc_elimination ? fast_ln(energy) : s * (t == 0 ? dct_scale_00 : a.dct_scale_0);
+                            else o = s * dct_scale_k;
                             if (active) a.out0[gf * Cc + c] = o;
                         }
                     }
@@ -385,7 +417,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a)
             }
             frame_sync<LOG2C>();  // zbuf / prow / frow / red are private to the frame's slot
         }
-    } else {
+    } else if constexpr (!VAR) {
         // ---------------- STFT / mel-spectrogram path: one clip (channel) per workgroup visit -------
         const int R = static_cast<int>(a.rows);
         const int Rreal = static_cast<int>(a.real_rows);
@@ -484,6 +516,27 @@ hipError_t launch_one(const FrontArgs &a, hipStream_t stream, int num_cus, Launc
     return hipGetLastError();
 }
 
+template <int LOG2C, bool BLU>
+hipError_t launch_one_varlen(const FrontArgs &a, const VarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info, const char *name)
+{
+    using G = Geo<LOG2C>;
+    const size_t lds = front_lds_bytes<LOG2C>(a);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, VarlenArgs>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    // at least one workgroup: the clip pass runs even where the output block has no rows
+    unsigned long long work = (v.total_frames + G::FPB - 1) / G::FPB;
+    if (work == 0) work = 1;
+    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
+    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
+    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
+    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, VarlenArgs>), dim3(grid), dim3(kBlock), lds, stream, a, v);
+    return hipGetLastError();
+}
+
 __global__ void ss_preemphasis_kernel(const float *__restrict__ x, float *__restrict__ y, size_t n, size_t shift, float cof)
 {
     // processing.rs:31-53: y[i] = x[i] - cof * x[(i - shift) mod n]
@@ -548,6 +601,38 @@ hipError_t launch_front_generic(const FrontArgs &a, uint32_t log2c, hipStream_t 
         case 10: return launch_one<10, false>(a, stream, num_cus, info, "ss_front_generic<10>");
         case 11: return launch_one<11, false>(a, stream, num_cus, info, "ss_front_generic<11>");
         case 12: return launch_one<12, false>(a, stream, num_cus, info, "ss_front_generic<12>");
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
+                                       LaunchInfo *info)
+{
+    if (a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE) return hipErrorInvalidValue;
+    if (a.blu_n) {
+        switch (log2c) {
+            case 4: return launch_one_varlen<4, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<4,chirpz>");
+            case 5: return launch_one_varlen<5, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<5,chirpz>");
+            case 6: return launch_one_varlen<6, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<6,chirpz>");
+            case 7: return launch_one_varlen<7, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<7,chirpz>");
+            case 8: return launch_one_varlen<8, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<8,chirpz>");
+            case 9: return launch_one_varlen<9, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<9,chirpz>");
+            case 10: return launch_one_varlen<10, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<10,chirpz>");
+            case 11: return launch_one_varlen<11, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<11,chirpz>");
+            case 12: return launch_one_varlen<12, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<12,chirpz>");
+            default: return hipErrorInvalidValue;
+        }
+    }
+    switch (log2c) {
+        case 4: return launch_one_varlen<4, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<4>");
+        case 5: return launch_one_varlen<5, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<5>");
+        case 6: return launch_one_varlen<6, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<6>");
+        case 7: return launch_one_varlen<7, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<7>");
+        case 8: return launch_one_varlen<8, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<8>");
+        case 9: return launch_one_varlen<9, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<9>");
+        case 10: return launch_one_varlen<10, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<10>");
+        case 11: return launch_one_varlen<11, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<11>");
+        case 12: return launch_one_varlen<12, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<12>");
         default: return hipErrorInvalidValue;
     }
 }

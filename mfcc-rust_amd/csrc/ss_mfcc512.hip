@@ -55,6 +55,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 // Timing-attribution builds (lab build only: tools/ablate.sh passes -DSS_LAB=1 -DSS_ABLATE=<bits>): each bit removes one
 // stage; results are then wrong by design.  The product build compiles the switch out (SS_ABLATE is the constant 0 there,
@@ -255,6 +256,36 @@ __device__ __forceinline__ QuadSrc quad_src(const Fast512Args &a, unsigned quad,
     return r;
 }
 
+// VAR builds (ss_mfcc_packed_device): the frame of `quad` this lane computes is output row q4 + f of a packed launch.  `cursor` is the
+// wave's clip of its last quad's first row: a wave's claims only increase, so it walks forward (a few uniform steps, a binary
+// search when it is far behind); a lane's frame lies at most three clips further (every clip has at least one frame).  Per lane:
+// the frame's first sample (64-bit clip base, either parity: the sample pairs load at dword alignment), its index in the clip,
+// the clip's DCT scales and whether the offsets are consistent (a lane of an inconsistent clip, or past the last clip, stores
+// nothing; varlen_check_clips raises the error word).
+struct VarFrame {
+    float sk, s00;  // dct_scale_k / dct_scale_00 of the frame's clip
+    int ok;
+};
+__device__ __forceinline__ const char *var_src(const Fast512Args &a, const VarlenArgs &v, unsigned quad, unsigned total, int f,
+                                               unsigned &cursor, unsigned &t_out, VarFrame &vf)
+{
+    const unsigned q4 = quad * 4;                                        // uniform
+    const unsigned g = q4 + min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last row redo it
+    unsigned c = cursor;
+    for (int k = 0; k < 4 && c + 1 < v.n_clips && v.fo[c + 1] <= static_cast<long long>(q4); ++k) ++c;
+    if (c + 1 < v.n_clips && v.fo[c + 1] <= static_cast<long long>(q4)) c = varlen_find(v, q4);
+    cursor = c;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c += (c + 1 < v.n_clips && v.fo[c + 1] <= static_cast<long long>(g)) ? 1u : 0u;
+    const VarClip cl = varlen_clip(v, a.flen, a.step, c);
+    const long long tl = static_cast<long long>(g) - cl.f0;
+    vf.ok = cl.ok && tl >= 0 && tl < static_cast<long long>(cl.T);
+    t_out = vf.ok ? static_cast<unsigned>(tl) : 0u;
+    varlen_dct_scales(v, cl.T, a.n_filters, vf.sk, vf.s00);
+    // (a lane that stores nothing reads the buffer's first frame)
+    return reinterpret_cast<const char *>(a.x + (vf.ok ? cl.s0 + static_cast<long long>(t_out) * a.step : 0ll));
+}
+
 // One mel slot with a compile-time tap count (multiple of 4): weights and P taps are all requested before
 // the first FMA.  `w4` = this lane's weight row at the slot's offset, `p` = P row at the slot's start bin.
 template <int Q4>
@@ -319,9 +350,10 @@ __device__ __forceinline__ float mel_slot_loop(const float4 *w4, const float *p,
 
 // MULTI builds (ss_mfcc_batches_device): the launch's quad range is the concatenation of up to kMaxLaunchBatches independent batches'
 // quad ranges, each batch with its own input and output block (BatchTable, ss_device.h; Seg / seg_of, ss_wave.h).
+// VAR builds (ss_mfcc_packed_device): the second argument is a VarlenArgs; the quad range covers the packed output rows (var_src).
 template <int NE, bool EXACT, bool POW2, int WAVES, bool BANK421, int NQ, int RES = 0, int OUTK = 0, int FRONT = 0, bool FULLP = false,
-          bool CENTER = false, bool MULTI = false>
-__global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_in, const MultiArg<MULTI> mt)
+          bool CENTER = false, bool MULTI = false, bool VAR = false>
+__global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_in, const std::conditional_t<VAR, VarlenArgs, MultiArg<MULTI>> mt)
 {
     // Everything in front of a wave's first sample loads is start-up latency of the launch (nothing can be computed before
     // the samples are here), so the kernel arguments that lead to those loads are fetched by ONE batch of scalar loads at the
@@ -375,7 +407,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     unsigned *s_next = reinterpret_cast<unsigned *>(s_tab + L::kMelW + 16 * a.mel_wpitch + (WIN ? a.win_floats : 0));
 
     // quad range of this workgroup (contiguous, balanced to within one quad)
-    const unsigned total = a.batch * a.n_frames;
+    unsigned total = a.batch * a.n_frames;
+    if constexpr (VAR) total = static_cast<unsigned>(mt.total_frames);  // (the launcher keeps it below 2^31)
     const unsigned q_lo = blockIdx.x * a.q_base + min(blockIdx.x, a.q_rem);
     const unsigned q_hi = q_lo + a.q_base + (blockIdx.x < a.q_rem ? 1u : 0u);
 
@@ -399,7 +432,13 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     unsigned t_next = 0;  // frame index within the clip of the quad whose samples are in vin
     Seg ns{};                // MULTI: the batch of the quad whose samples are being fetched ...
     Fast512Args an = a_in;   // ... and the argument block with that batch's input
-    if constexpr (MULTI) {
+    [[maybe_unused]] unsigned cursor = 0;  // VAR: the wave's clip cursor ...
+    [[maybe_unused]] VarFrame vnext{};     // ... and the clip data of the frame whose samples are in vin
+    if constexpr (VAR) {
+        const char *p = var_src(a, mt, min(quad, q_hi - 1), total, f, cursor, t_next, vnext);
+#pragma unroll
+        for (int e = 0; e < NE; ++e) vin[e] = *reinterpret_cast<const float2 *>(p + 8 * (j + 16 * e));
+    } else if constexpr (MULTI) {
         an = a;
         ns = seg_of(mt.m, min(quad, q_hi - 1));
         an.x = ns.x;
@@ -522,6 +561,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         SS_PH(1);  // claim
         if (!PREFETCH && n_done > 1) t_next = load_quad<NE, EXACT, PRE, CENTER>(a, quad, total, f, j, vin, pin);
         const unsigned t_cur = t_next;
+        [[maybe_unused]] const VarFrame vcur = vnext;
 #if SS_PROF2
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -566,8 +606,11 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         // iteration of a wave fetches the block's last quad again and drops it
         constexpr bool SPREAD = PREFETCH && EXACT && !PRE && !CENTER && !(SS_ABLATE & 16);
         static_assert(!MULTI || (SPREAD && OUTK == 0), "the multi-batch build exists for the spread-prefetch MFCC builds");
+        static_assert(!VAR || (SPREAD && OUTK == 0 && !MULTI), "the varlen build exists for the spread-prefetch MFCC builds");
         QuadSrc nsrc{nullptr, 0u};
-        if constexpr (MULTI) {
+        if constexpr (VAR) {
+            nsrc.base = var_src(a, mt, min(next, q_hi - 1), total, f, cursor, t_next, vnext) + 8 * j;
+        } else if constexpr (MULTI) {
             const unsigned nq = min(next, q_hi - 1);
             if (nq >= ns.u1) {  // (uniform, rare: the claimed quad starts the next batch)
                 ns = seg_of(mt.m, nq);
@@ -834,11 +877,12 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             // (sc_lane: this lane's column scale, a loop invariant; the two special cases of column 0 sit behind a uniform branch each,
             // so that the default path pays one product and one select)
             float o = acc * sc_lane;
+            if constexpr (VAR) o = acc * (j == 0 ? (a.dc_elimination ? 0.f : a.dct_scale_0) : vcur.sk);  // the clip's own scale
             if (a.dc_elimination) {
                 const float le = ln_scaled(energy);
                 o = j == 0 ? le : o;
             } else if (t_cur == 0 && j == 0) {
-                o = acc * a.dct_scale_00;
+                o = acc * (VAR ? vcur.s00 : a.dct_scale_00);
             }
             // unconditional, counted store (ss_wave.h): the descriptor covers the quad's valid frames, lanes j >= n_ceps are
             // dropped by its range check -- the next quad's samples are waited for with this store still in flight
@@ -853,13 +897,17 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             }
             const unsigned nvalid = min(4u, q_total - quad_s * 4);
             const __amdgpu_buffer_rsrc_t orow = out_rsrc(q_out + static_cast<unsigned long long>(quad_s) * 4ull * Cc, nvalid * Cc * 4u);
-            buf_store(o, orow, j < Cc ? (f * Cc + j) * 4 : kOobOffset);
+            bool store = j < Cc;
+            if constexpr (VAR) store = store && vcur.ok;
+            buf_store(o, orow, store ? (f * Cc + j) * 4 : kOobOffset);
         }
         wave_order();
         SS_PH(9);  // store
         SS_PRIOL(SS_P2_TOP);
         quad = next;
     }
+    // VAR: the consistency pass over every clip (at the end: its loads would otherwise wait in line with the first samples)
+    if constexpr (VAR) varlen_check_clips(mt, a.flen, a.step, blockIdx.x * (WAVES * 64) + tid, gridDim.x * (WAVES * 64));
 #if SS_PROF2
     if (a.dbg && lane == 0) {
         unsigned long long *o = a.dbg + 16ull * (blockIdx.x * WAVES + wave);
@@ -1072,6 +1120,37 @@ hipError_t launch_mfcc_c256_multi(const Fast512Args &a_in, int n_batches, const 
     }
     if (info) *info = LaunchInfo{"ss_mfcc_c256m<10,exact,bank421,sym>", grid, static_cast<unsigned>(WAVES * 64), lds};
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<true>{m});
+    return hipGetLastError();
+}
+
+hipError_t launch_mfcc_c256_varlen(const Fast512Args &a_in, const VarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    constexpr int WAVES = 12;
+    Fast512Args a = a_in;
+    // the headline build only: MFCC of the default frame shape and bank, 40 filters in the paired tight-tap layout, contract framing
+    const bool b421 = a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1;
+    if (a.fullp || a.center || a.out_mfe || a.win_floats > 0 || a.preemph != 0.0f || a.flen != 320 || a.spectrum_exponent == 2 ||
+        !b421 || a.n_filters != 40 || a.paired != 2 || v.framing != SS_FRAMING_CONTRACT || v.dct_ortho || v.n_clips == 0 ||
+        v.total_frames + 4 >= (1ull << 31))
+        return hipErrorInvalidValue;
+    a.nf_magic = a.nf_shift = 0;
+    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * a.mel_wpitch) * sizeof(float) + 16;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    // an empty output block still gets one workgroup: the clip pass runs
+    const unsigned long long quads = (v.total_frames + 3) / 4;
+    unsigned long long blocks = quads ? (quads + WAVES - 1) / WAVES : 1;
+    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
+    if (blocks > cap) blocks = cap;
+    const unsigned grid = static_cast<unsigned>(blocks);
+    a.q_base = static_cast<uint32_t>(quads / grid);
+    a.q_rem = static_cast<uint32_t>(quads % grid);
+    auto kern = ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, true>;
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    if (info) *info = LaunchInfo{"ss_mfcc_c256v<10,exact,bank421,sym>", grid, static_cast<unsigned>(WAVES * 64), lds};
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, v);
     return hipGetLastError();
 }
 

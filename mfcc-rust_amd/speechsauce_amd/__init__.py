@@ -22,7 +22,7 @@ from ._lib import SpeechSauceError, SsParams, make_params  # noqa: F401
 
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
-           "power_spectrum_of_signal", "SpeechConfig", "SpeechSauceError"]
+           "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "SpeechConfig", "SpeechSauceError"]
 
 
 def _is_torch(x) -> bool:
@@ -314,6 +314,119 @@ def mfe_batch(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01
     config = _cfg(sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
                   low_frequency, high_frequency, True, switches, sig)
     return _internal_mfe_batch(sig, config)
+
+
+# ---- packed variable-length clips (ss_*_packed*): one call over clips of different lengths ------------------------
+
+def _sample_offsets(lengths, n_buffer: int, what: str):
+    """Clip lengths (list, ndarray or tensor on any device) -> sample offsets, an int64 host array of n + 1 (no device needed)."""
+    if _is_torch(lengths):
+        lengths = lengths.detach().cpu().numpy()
+    lens = np.asarray(lengths)
+    if lens.ndim != 1:
+        raise ValueError(f"{what}: lengths must be 1-D")
+    if lens.size and not np.issubdtype(lens.dtype, np.integer):
+        raise TypeError(f"{what}: lengths must be integers, got {lens.dtype}")
+    lens = lens.astype(np.int64)
+    if (lens < 0).any():
+        raise ValueError(f"{what}: negative clip length")
+    so = np.zeros(lens.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=so[1:])
+    if so[-1] > n_buffer:
+        raise ValueError(f"{what}: the lengths sum to {so[-1]} samples, the signal holds {n_buffer}")
+    return so
+
+
+def _frame_offsets(config: SpeechConfig, so):
+    """Sample offsets -> frame offsets (ss_packed_frame_offsets), an int64 host array of n + 1."""
+    fo = np.empty_like(so)
+    _lib.check(_lib.lib().ss_packed_frame_offsets(C.byref(config.params), so.size - 1, so.ctypes.data, fo.ctypes.data))
+    return fo
+
+
+def _packed_offsets(config: SpeechConfig, lengths, n_buffer: int, what: str):
+    """-> sample offsets and frame offsets, int64 host arrays of n + 1."""
+    so = _sample_offsets(lengths, n_buffer, what)
+    return so, _frame_offsets(config, so)
+
+
+def _internal_packed(signal, so, config: SpeechConfig, mfe: bool):
+    """signal [N] packed clips, sample offsets so -> (features [sum T_b, cols], energy [sum T_b] or None, frame_offsets [n + 1])."""
+    lib = _lib.lib()
+    fo = _frame_offsets(config, so)
+    n, rows = so.size - 1, int(fo[-1])
+    cols = config.params.num_filters if mfe else config.params.num_cepstral
+    if _is_torch(signal):
+        import torch
+
+        x = signal.contiguous()
+        with torch.cuda.device(x.device):
+            dso, dfo = torch.from_numpy(so).to(x.device), torch.from_numpy(fo).to(x.device)
+            out = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
+            en = torch.empty((rows,), dtype=torch.float32, device=x.device) if mfe else None
+            if mfe:
+                _lib.check(lib.ss_mfe_packed_device(config.handle, x.data_ptr(), n, dso.data_ptr(), dfo.data_ptr(), rows,
+                                                    out.data_ptr(), en.data_ptr(), _stream_ptr()))
+            else:
+                _lib.check(lib.ss_mfcc_packed_device(config.handle, x.data_ptr(), n, dso.data_ptr(), dfo.data_ptr(), rows,
+                                                     out.data_ptr(), _stream_ptr()))
+        return out, en, dfo
+    x = np.ascontiguousarray(signal)
+    out = np.empty((rows, cols), dtype=np.float32)
+    en = np.empty((rows,), dtype=np.float32) if mfe else None
+    if mfe:
+        _lib.check(lib.ss_mfe_packed(config.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data, en.ctypes.data))
+    else:
+        _lib.check(lib.ss_mfcc_packed(config.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data))
+    return out, en, fo
+
+
+def mfcc_packed(signal, lengths, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
+                fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+    """MFCC of clips of different lengths packed end to end in one 1-D float32 signal (clip b = the lengths[b] samples after
+    the clips before it) -> (features [sum T_b, num_cepstral], frame_offsets [n + 1] int64): clip b's rows are
+    frame_offsets[b] : frame_offsets[b + 1], each what ``mfcc`` returns for that clip alone.  One launch for all clips."""
+    sig = _require_f32(signal, (1,), "mfcc_packed")
+    so = _sample_offsets(lengths, sig.shape[0], "mfcc_packed")
+    config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
+                  low_frequency, high_frequency, dc_elimination, switches, sig)
+    out, _, fo = _internal_packed(sig, so, config, False)
+    return out, fo
+
+
+def mfe_packed(signal, lengths, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_filters=40, fft_length=512,
+               low_frequency=0, high_frequency=None, **switches):
+    """``mfe`` of packed clips (see mfcc_packed) -> (feat [sum T_b, num_filters], energy [sum T_b], frame_offsets [n + 1])."""
+    sig = _require_f32(signal, (1,), "mfe_packed")
+    so = _sample_offsets(lengths, sig.shape[0], "mfe_packed")
+    config = _cfg(sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
+                  low_frequency, high_frequency, True, switches, sig)
+    return _internal_packed(sig, so, config, True)
+
+
+def mfcc_list(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
+              fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+    """A list of 1-D float32 clips of any lengths -> the list of their [T_b, num_cepstral] features (views of one block): the
+    clips are packed once and served by one mfcc_packed call."""
+    sigs = [_require_f32(x, (1,), "mfcc_list") for x in signals]
+    if not sigs:
+        return []
+    on_device = [_is_torch(x) for x in sigs]  # (_require_f32 turns host tensors into arrays)
+    if any(on_device) and not all(on_device):
+        raise ValueError("mfcc_list: the clips of one call must all be device tensors or all host arrays")
+    if all(on_device):
+        import torch
+
+        if any(x.device != sigs[0].device for x in sigs):
+            raise ValueError("mfcc_list: the clips of one call must live on one device")
+        packed = torch.cat(sigs)
+    else:
+        packed = np.concatenate(sigs)
+    lengths = [int(x.shape[0]) for x in sigs]
+    out, fo = mfcc_packed(packed, lengths, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters,
+                          fft_length, low_frequency, high_frequency, dc_elimination, **switches)
+    fo = fo.tolist()
+    return [out[fo[b]:fo[b + 1]] for b in range(len(sigs))]
 
 
 def _internal_lmfe_batch(signal, config: SpeechConfig):
