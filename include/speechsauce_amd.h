@@ -17,8 +17,9 @@
  *     functions.rs:136; asserts feature.rs:47-51).
  *   - `*_device` variants take device pointers and a hipStream_t (passed as void*) and are
  *     asynchronous; the others take host pointers and are synchronous (H2D + kernels + D2H).
- *   - a config handle is immutable after creation (no STFT carry-over state, unlike
- *     config.rs:126,130) and may be used from several threads / streams concurrently.
+ *   - a config handle is immutable after creation and may be used from several threads /
+ *     streams concurrently.  The STFT carry-over state of config.rs:126,162 lives in
+ *     caller-owned buffers instead: the ss_*_stream entry points take and update it.
  *   - there is NO CPU fallback: without a usable HIP device every compute entry point fails
  *     with SS_ERR_HIP.
  */
@@ -250,6 +251,43 @@ int ss_mfcc_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips
                           const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream);
 int ss_mfe_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
                          const int64_t *d_frame_offsets, size_t total_frames, float *d_feat, float *d_energy, void *stream);
+
+/* ---- streaming STFT / mel spectrogram with carried state (functions.rs:86-170, config.rs:126,162) ----
+ * The reference keeps the last S = fft_points - frame_size samples in SpeechConfig::analysis_mem (config.rs:162) and opens every
+ * stft1 / stft2 / mel_spectrogram call with them (frame_analysis, functions.rs:137-160), so audio fed chunk by chunk gives frames
+ * whose window reaches back into earlier chunks.  Here the config stays immutable and the state lives in a caller-owned buffer:
+ * [n_streams x S] floats, contiguous, updated in place by every call.  All zeros is a fresh stream (what a new SpeechConfig
+ * gives); zeroing a row resets that stream.  Streams are independent: stream s behaves like its own SpeechConfig fed through
+ * stft1 / mel_spectrogram1 (stft2's hand-over of channel c - 1's tail to channel c, SURVEY Q6, is not reproduced).
+ * H = frame_size (config.rs:154), W = fft_points, n_pad = W / H - 1 (functions.rs:96); the STFT path needs W >= 2H.
+ *   SS_STREAM_CONTINUOUS: n_samples a multiple of H (else SS_ERR_ARG, state untouched).  R = n_samples / H rows, all real: row g
+ *     of a stream, counted in hops since its reset, is wnorm * rfft(window * s[(g+1)H - W : (g+1)H]) with zeros before the
+ *     stream's start (functions.rs:137-169).  Consecutive calls concatenate to the same rows however the stream was cut; they
+ *     equal the real rows of the one-shot ss_stft / ss_mel_spectrogram on zeros(n_pad * H) ++ s.
+ *   SS_STREAM_REFERENCE: exactly what stft1 / mel_spectrogram1 return on a SpeechConfig that has seen the earlier chunks:
+ *     ceil(n / H) rows (functions.rs:97), row i the frame ending at this call's chunk i + n_pad, the trailing n_pad rows exact
+ *     zeros (:121); a partial last chunk is zero-padded to H and those zeros enter the state (:112-117, :158-160).  Any
+ *     n_samples >= 1; real_rows may be 0 (the state still advances).
+ * Outputs as the stateless calls: mel [n_streams x num_filters x R], stft [n_streams x R x (W/2+1) x 2].  Every switch and bank of
+ * the config applies.  Arguments as ss_stft_device: n_streams == 0 is SS_OK with nothing launched; null buffers, ld < n_samples,
+ * n_samples == 0, more than 2^31 - 1 samples or streams, and a state range that overlaps x or out are SS_ERR_ARG; a config with
+ * no STFT path is SS_ERR_BAD_CONFIG.  A rejected call leaves the state as it was. */
+enum { SS_STREAM_REFERENCE = 0, SS_STREAM_CONTINUOUS = 1 };
+/* host only, no device needed: S = fft_points - frame_size (config.rs:162) */
+int ss_stream_state_len(const ss_params *p, size_t *state_len);
+/* host only: the rows a call of n_samples returns and how many of them are real (the rest are the zeros of functions.rs:121) */
+int ss_stream_rows(const ss_params *p, int mode, size_t n_samples, size_t *rows, size_t *real_rows);
+/* host pointers, synchronous: one upload of x and state, the device call, one download of out and state */
+int ss_stft_stream(const ss_config *cfg, int mode, const float *x, size_t n_streams, size_t n_samples, size_t ld, float *state,
+                   float *out);
+int ss_mel_spectrogram_stream(const ss_config *cfg, int mode, const float *x, size_t n_streams, size_t n_samples, size_t ld,
+                              float *state, float *out);
+/* device pointers, asynchronous on `stream`, graph-capturable (two stream-ordered launches, a linear chain: the rows, then the
+ * state advance) */
+int ss_stft_stream_device(const ss_config *cfg, int mode, const float *d_x, size_t n_streams, size_t n_samples, size_t ld,
+                          float *d_state, float *d_out, void *stream);
+int ss_mel_spectrogram_stream_device(const ss_config *cfg, int mode, const float *d_x, size_t n_streams, size_t n_samples, size_t ld,
+                                     float *d_state, float *d_out, void *stream);
 
 /* ss_stack_frames_signal on device pointers (d_window: frame_len floats in device memory, or NULL) */
 int ss_stack_frames_signal_device(const float *d_x, size_t n_samples, uint32_t sample_rate, float frame_length, float frame_stride,

@@ -717,6 +717,146 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
     return SS_OK;
 }
 
+// Streaming STFT-path launch (ss_*_stream_device): the rows of one call over a carried state per stream, then the state advance --
+// two kernels on `stream`, nothing else (a captured call is a linear chain of two nodes).  Candidate order as launch_stft's: the
+// streaming build of the 2048-point mel kernel where mel2048.ok, else the streaming build of the generic kernel.
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+int launch_stft_stream(const ss_config *cfg, int out_kind, int mode, const float *d_x, size_t n_streams, size_t n, size_t ld,
+                       float *d_state, float *out0, hipStream_t stream)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_streams == 0) return SS_OK;
+    if (!d_x || !d_state || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (ld < n) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
+    if (n == 0 || n > 0x7fffffffull || n_streams > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "bad chunk length / stream count");
+    {
+        const int drc = check_device(cfg);  // see launch_frames
+        if (drc) return drc;
+        const int erc = pending_device_error(cfg);
+        if (erc) return erc;
+    }
+    const ss::HostTables &h = cfg->host;
+    size_t R = 0, Rreal = 0;
+    int rc = ss_stream_rows(&h.params, mode, n, &R, &Rreal);
+    if (rc) return rc;
+    const size_t S = h.params.fft_points - h.d.hop;
+    const size_t F = h.params.fft_points / 2 + 1;
+    const size_t out_floats = n_streams * R * (out_kind == ss::OUT_STFT ? 2 * F : h.params.num_filters);
+    if (ranges_overlap(d_state, n_streams * S * sizeof(float), d_x, ((n_streams - 1) * ld + n) * sizeof(float)) ||
+        ranges_overlap(d_state, n_streams * S * sizeof(float), out0, out_floats * sizeof(float)))
+        return ss::fail(SS_ERR_ARG, "the state buffer overlaps the input or the output");
+    // reference mode: the chunk is zero-padded to whole hops (functions.rs:112-117) and the rows end at chunk i + n_pad
+    const bool continuous = mode == SS_STREAM_CONTINUOUS;
+    const size_t advance = continuous ? n : R * h.d.hop;
+    if (advance > 0xffffffffull || R > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "chunk too long");
+    ss::FrontArgs a{};
+    fill_common(cfg, a);
+    a.x = d_x;
+    a.ld = ld;
+    a.n_samples = static_cast<uint32_t>(n);
+    a.batch = static_cast<uint32_t>(n_streams);
+    a.hop = h.d.hop;
+    a.n_pad = continuous ? 0u : h.d.n_pad;
+    a.rows = static_cast<uint32_t>(R);
+    a.real_rows = static_cast<uint32_t>(Rreal);
+    a.window = cfg->d_window_stft;
+    a.scale = h.d.wnorm;
+    a.out_kind = out_kind;
+    a.out0 = out0;
+    ss::StreamArgs sa{d_state, static_cast<uint32_t>(S)};
+    ss::LaunchInfo info{};
+    hipError_t e = hipErrorInvalidValue;
+    if (!ss::dbg_force_generic() && out_kind == ss::OUT_MEL && cfg->mel2048.ok &&
+        static_cast<unsigned long long>(a.rows + a.n_pad + 1) * a.hop < 0x7fffffffull) {
+        ss::Mel2048Args m{};
+        m.x = d_x;
+        m.ld = ld;
+        m.n_samples = a.n_samples;
+        m.batch = a.batch;
+        m.hop = a.hop;
+        m.n_pad = a.n_pad;
+        m.rows = a.rows;
+        m.real_rows = a.real_rows;
+        m.scale = a.scale;
+        m.tab = cfg->d_mel2048_tab;
+        m.fullp = cfg->mel2048.fullp;
+        m.mel_wpitch = cfg->mel2048.wpitch;
+        for (int s = 0; s < 4; ++s) m.mel_q4[s] = cfg->mel2048.q4[s];
+        m.n_filters = a.n_filters;
+        m.out = out0;
+        m.ctl = cfg->d_err;
+        e = ss::launch_mel_c1024_stream(m, sa, stream, cfg->num_cus, &info);
+        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel -> the generic build
+        if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mel_c1024_stream");
+    }
+    if (e != hipSuccess) {
+        e = ss::launch_front_generic_stream(a, sa, h.d.log2c, stream, cfg->num_cus, &info);
+        if (e != hipSuccess) return hip_fail(e, "launch_front_generic_stream");
+    }
+    g_last_kernel = info.kernel_name;
+    e = ss::launch_stream_advance(d_state, static_cast<uint32_t>(S), d_x, ld, a.n_samples, static_cast<uint32_t>(advance), a.batch, stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_stream_advance");
+    return SS_OK;
+}
+
+// Host-pointer form: one upload of x and the state, the device call, one download of out and the state on the config's first
+// host-pipeline stream (host calls of a config are serialised by its mutex).  The caller's state is written only once everything
+// before it succeeded.
+int stream_host(const ss_config *cfg, int out_kind, int mode, const float *x, size_t n_streams, size_t n, size_t ld, float *state,
+                float *out0)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_streams == 0) return SS_OK;
+    if (!x || !state || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (ld < n) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
+    if (n == 0 || n > 0x7fffffffull || n_streams > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "bad chunk length / stream count");
+    const ss::HostTables &h = cfg->host;
+    size_t R = 0, Rreal = 0;
+    int rc = ss_stream_rows(&h.params, mode, n, &R, &Rreal);
+    if (rc) return rc;
+    const size_t S = h.params.fft_points - h.d.hop;
+    const size_t out_floats = n_streams * R * (out_kind == ss::OUT_STFT ? 2 * (h.params.fft_points / 2 + 1) : h.params.num_filters);
+    const size_t in_floats = (n_streams - 1) * ld + n;
+    if (ranges_overlap(state, n_streams * S * sizeof(float), x, in_floats * sizeof(float)) ||
+        ranges_overlap(state, n_streams * S * sizeof(float), out0, out_floats * sizeof(float)))
+        return ss::fail(SS_ERR_ARG, "the state buffer overlaps the input or the output");
+    if ((rc = check_device(cfg))) return rc;
+    ss_config::HostPipe &hp = cfg->pipe;
+    std::lock_guard<std::mutex> lock(hp.mu);
+    if (!hp.stream[0]) {
+        SS_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
+        SS_HIP(hipEventCreateWithFlags(&hp.done[0], hipEventDisableTiming));
+    }
+    hipStream_t st = hp.stream[0];
+    DeviceBuf dx, ds, d0;
+    if ((rc = dx.alloc(in_floats * sizeof(float))) || (rc = ds.alloc(n_streams * S * sizeof(float))) ||
+        (rc = d0.alloc(out_floats * sizeof(float))))
+        return rc;
+    hipError_t e = hipMemcpyAsync(dx.p, x, in_floats * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(ds.p, state, n_streams * S * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
+    if (rc == SS_OK) rc = launch_stft_stream(cfg, out_kind, mode, dx.as<const float>(), n_streams, n, ld, ds.as<float>(), d0.as<float>(), st);
+    if (rc == SS_OK) {
+        e = hipMemcpyAsync(out0, d0.p, out_floats * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (D2H)");
+    }
+    // the copies may still touch the caller's buffers and ours: synchronise whatever happened
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "stream host call");
+    if (rc == SS_OK) rc = pending_device_error(cfg);
+    if (rc == SS_OK) {
+        e = hipMemcpyAsync(state, ds.p, n_streams * S * sizeof(float), hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e != hipSuccess || es != hipSuccess) rc = hip_fail(e != hipSuccess ? e : es, "hipMemcpyAsync (state D2H)");
+    }
+    return rc;
+}
+
 // stack_frames (processing.rs:65-129): frames[clip][t][i] = x[clip][t * step + i] (* window[i]); one thread per element,
 // neighbouring threads on neighbouring samples of a frame.  frame_mode as in the fused kernels' loaders: contract framing,
 // zero_padding = true (zeros past the signal), the literal exact_chunks copy (all-zero rows for > 2 frames, x[0 .. flen & ~1]
@@ -1766,6 +1906,30 @@ int ss_stft_device(const ss_config *cfg, const float *d_x, size_t channels, size
                    float *d_out, void *stream)
 {
     return launch_stft(cfg, ss::OUT_STFT, d_x, channels, n_samples, ld, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_stft_stream_device(const ss_config *cfg, int mode, const float *d_x, size_t n_streams, size_t n_samples, size_t ld,
+                          float *d_state, float *d_out, void *stream)
+{
+    return launch_stft_stream(cfg, ss::OUT_STFT, mode, d_x, n_streams, n_samples, ld, d_state, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_mel_spectrogram_stream_device(const ss_config *cfg, int mode, const float *d_x, size_t n_streams, size_t n_samples, size_t ld,
+                                     float *d_state, float *d_out, void *stream)
+{
+    return launch_stft_stream(cfg, ss::OUT_MEL, mode, d_x, n_streams, n_samples, ld, d_state, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_stft_stream(const ss_config *cfg, int mode, const float *x, size_t n_streams, size_t n_samples, size_t ld, float *state,
+                   float *out)
+{
+    return stream_host(cfg, ss::OUT_STFT, mode, x, n_streams, n_samples, ld, state, out);
+}
+
+int ss_mel_spectrogram_stream(const ss_config *cfg, int mode, const float *x, size_t n_streams, size_t n_samples, size_t ld,
+                              float *state, float *out)
+{
+    return stream_host(cfg, ss::OUT_MEL, mode, x, n_streams, n_samples, ld, state, out);
 }
 
 int ss_preemphasis_device(const float *d_x, size_t n_samples, long shift, float cof, float *d_y, void *stream)

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "speechsauce_amd.h"
 
@@ -179,6 +180,36 @@ __device__ __forceinline__ void varlen_check_clips(const VarlenArgs &v, uint32_t
 // ss_front_generic.  a: as for launch_front_generic with x = the packed samples; batch / n_samples / n_frames are unused.
 hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
                                        LaunchInfo *info);
+
+// Streaming STFT (ss_stft_stream_device / ss_mel_spectrogram_stream_device): every stream (a row of the batch) carries the last
+// S = fft_points - hop samples it was fed (config.rs:162, functions.rs:137-160).  A window that reaches before the chunk reads them:
+// sample p < 0 of stream s is state[s * S + S + p] (p >= -S always holds: a row's window ends at least one hop into the chunk).
+struct StreamArgs {
+    const float *state;  // [batch][state_len]
+    uint32_t state_len;  // S
+};
+// The argument of type T in a kernel's trailing argument pack (empty pack: none) -- the builds with an empty pack keep the argument
+// block, and the code, they had before the pack existed.
+template <typename T, typename... V>
+__device__ __forceinline__ const T *pack_arg(const V &...v)
+{
+    const T *p = nullptr;
+    (
+        [&] {
+            if constexpr (std::is_same_v<T, V>) p = &v;
+        }(),
+        ...);
+    return p;
+}
+// the streaming build of ss_front_generic's STFT / mel path (any fft_points, chirp-z included): a as for launch_front_generic's
+// STFT path, on the chunk (n_pad 0 and real_rows = rows in continuous mode)
+hipError_t launch_front_generic_stream(const FrontArgs &a, const StreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
+                                       LaunchInfo *info);
+// The state advance, a second stream-ordered launch behind the rows: state row s := the last S samples of (old row ++ the chunk's
+// first `advance` samples, zeros past n_samples).  One workgroup per stream, in place (every read of a block of the row is done
+// before any lane of the workgroup writes it).
+hipError_t launch_stream_advance(float *state, uint32_t state_len, const float *x, unsigned long long ld, uint32_t n_samples,
+                                 uint32_t advance, uint32_t batch, hipStream_t stream);
 #if SS_LAB
 // Test aid (lab library): every word of every CU's LDS := 0xFFFFFFFF (ss_debug_poison_lds).
 hipError_t launch_poison_lds(hipStream_t stream, int num_cus);
@@ -287,6 +318,9 @@ struct Mel2048Args {
 };
 
 hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cus, LaunchInfo *info);
+// the streaming builds (mel output; StreamArgs above), chosen between eight and twelve waves by launch_mel_c1024's rule;
+// hipErrorInvalidValue before the launch for stft output or a shape that does not fit
+hipError_t launch_mel_c1024_stream(const Mel2048Args &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info);
 // several blocks of channels in one launch of the twelve-wave mel build (a: one block's arguments; x / out / batch are ignored);
 // hipErrorInvalidValue before the launch where the shape has no batch-table build
 hipError_t launch_mel_c1024_multi(const Mel2048Args &a, int n_batches, const float *const *d_x, float *const *d_out, const size_t *channels,

@@ -1330,6 +1330,35 @@ int ss_stft_rows(const ss_params *p, size_t n_samples, size_t *rows, size_t *rea
     return ss::stft_rows(*p, n_samples, *rows, *real_rows);
 }
 
+int ss_stream_state_len(const ss_params *p, size_t *state_len)
+{
+    if (!p || !state_len) return ss::fail(SS_ERR_ARG, "null argument");
+    int rc = ss::validate(*p);
+    if (rc) return rc;
+    ss::Derived d;
+    if ((rc = ss::derive(*p, d))) return rc;
+    if (!d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
+    *state_len = p->fft_points - d.hop;  // config.rs:162: analysis_mem holds fft_points - frame_size samples
+    return SS_OK;
+}
+
+int ss_stream_rows(const ss_params *p, int mode, size_t n_samples, size_t *rows, size_t *real_rows)
+{
+    if (!p || !rows || !real_rows) return ss::fail(SS_ERR_ARG, "null argument");
+    if (mode != SS_STREAM_REFERENCE && mode != SS_STREAM_CONTINUOUS) return ss::fail(SS_ERR_ARG, "mode must be SS_STREAM_REFERENCE or SS_STREAM_CONTINUOUS");
+    if (n_samples == 0) return ss::fail(SS_ERR_ARG, "a streaming call needs at least one sample");
+    int rc = ss::validate(*p);
+    if (rc) return rc;
+    ss::Derived d;
+    if ((rc = ss::derive(*p, d))) return rc;
+    if (!d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
+    if (mode == SS_STREAM_REFERENCE) return ss::stft_rows(*p, n_samples, *rows, *real_rows);  // functions.rs:96-97,121
+    if (n_samples % d.hop)
+        return ss::fail(SS_ERR_ARG, "continuous streaming takes whole hops: n_samples must be a multiple of " + std::to_string(d.hop));
+    *rows = *real_rows = n_samples / d.hop;  // one row per hop, every one real
+    return SS_OK;
+}
+
 int ss_filterbank(const ss_params *p, float *fb, int32_t *idx)
 {
     if (!p || !fb) return ss::fail(SS_ERR_ARG, "null argument");

@@ -4,6 +4,8 @@
 // sparse mel -> log -> DCT-II, one launch, any power-of-two fft_points in [32, 4096].
 // ss_front_generic<LOG2C, BLU, VarlenArgs> (reported as ss_front_generic_varlen<LOG2C>): the same MFCC / mfe path over packed
 // clips of different lengths (VarlenArgs, ss_device.h).
+// ss_front_generic<LOG2C, BLU, StreamArgs> (reported as ss_front_generic_stream<LOG2C>): the STFT / mel path with a carried state
+// per stream (StreamArgs, ss_device.h); ss_stream_advance moves the state on behind it.
 //
 //   * A real frame of N = 2C samples is packed as C complex points z[n] = x[2n] + i x[2n+1]
 //     and transformed by a Stockham autosort FFT whose butterflies live in registers: every
@@ -233,19 +235,15 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
 
 // VAR: packed variable-length clips (launch_front_generic_varlen): the flat frame index is the output row, and the clip / frame
 // split, the clip's samples, its length, its literal-framing mode and its DCT scales come from the offset tables (VarlenArgs).
-// (V: empty, or one VarlenArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
-template <typename... V>
-__device__ __forceinline__ const VarlenArgs *varlen_of(const V &...v)
-{
-    if constexpr (sizeof...(V) == 0) return nullptr;
-    else return (&v, ...);
-}
-
+// STREAM: the STFT / mel path of launch_front_generic_stream -- a window sample before the chunk comes from the stream's state.
+// (V: empty, one VarlenArgs or one StreamArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
 template <int LOG2C, bool BLU, typename... V>
 __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
 {
-    constexpr bool VAR = sizeof...(V) > 0;
-    [[maybe_unused]] const VarlenArgs *va = varlen_of(vargs...);
+    constexpr bool VAR = (std::is_same_v<V, VarlenArgs> || ...);
+    constexpr bool STREAM = (std::is_same_v<V, StreamArgs> || ...);
+    [[maybe_unused]] const VarlenArgs *va = pack_arg<VarlenArgs>(vargs...);
+    [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(vargs...);
     using G = Geo<LOG2C>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     // MEL mode: transposed output tile [M][rows_tile + 1] after all slots
     float *tile = reinterpret_cast<float *>(smem_raw + slot_bytes * G::FPB);
 
-    const bool mel_mode = !VAR && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT);
+    const bool mel_mode = STREAM || (!VAR && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT));
     const int F = BLU ? static_cast<int>(a.blu_n / 2 + 1) : G::F;  // bins per row
 
     if (!mel_mode) {
@@ -425,6 +423,9 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
         constexpr int TILE = 32;  // rows buffered before a transposed, coalesced flush
         for (unsigned clip = blockIdx.x; clip < a.batch; clip += gridDim.x) {
             const float *xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
+            // STREAM: the stream's state, indexed from its end (sample p < 0 of the stream is srow[p], p >= -S)
+            [[maybe_unused]] const float *srow = nullptr;
+            if constexpr (STREAM) srow = sa->state + static_cast<unsigned long long>(clip) * sa->state_len + sa->state_len;
             for (int r0 = 0; r0 < R; r0 += TILE) {
                 const int rt = min(TILE, R - r0);
                 for (int rp = 0; rp < rt; rp += G::FPB) {
@@ -435,6 +436,10 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                     const long long start = static_cast<long long>(r + a.n_pad + 1) * a.hop - W;
                     auto wsample = [&](int i) -> float {
                         const long long idx = start + i;
+                        if constexpr (STREAM) {
+                            if (!active || i >= W || idx >= static_cast<long long>(a.n_samples)) return 0.0f;
+                            return (idx < 0 ? srow[idx] : xc[idx]) * a.window[i];
+                        }
                         return active && i < W && idx >= 0 && idx < static_cast<long long>(a.n_samples) ? xc[idx] * a.window[i] : 0.0f;
                     };
                     float2 v[16];
@@ -537,6 +542,48 @@ hipError_t launch_one_varlen(const FrontArgs &a, const VarlenArgs &v, hipStream_
     return hipGetLastError();
 }
 
+template <int LOG2C, bool BLU>
+hipError_t launch_one_stream(const FrontArgs &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info, const char *name)
+{
+    const size_t lds = front_lds_bytes<LOG2C>(a);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, StreamArgs>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    if (a.batch == 0) return hipSuccess;
+    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
+    const unsigned grid = static_cast<unsigned>(a.batch < cap ? a.batch : cap);
+    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
+    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, StreamArgs>), dim3(grid), dim3(kBlock), lds, stream, a, s);
+    return hipGetLastError();
+}
+
+// State advance (functions.rs:152-160 over a call's chunks): row s := the last S samples of old row ++ x_s[0 .. advance), zeros
+// past n_samples.  A workgroup per stream (grid-stride over the streams) walks its row upwards in blocks of 256: block i0 reads
+// state[i0 + advance ..] (above every index written so far: advance >= 1) and the chunk, waits at the barrier until every lane has
+// read, then writes state[i0 ..].  Plain vector loads and stores.
+__global__ __launch_bounds__(256) void ss_stream_advance(float *__restrict__ state, unsigned S, const float *__restrict__ x,
+                                                          unsigned long long ld, unsigned n_samples, unsigned advance, unsigned batch)
+{
+    for (unsigned s = blockIdx.x; s < batch; s += gridDim.x) {
+        float *st = state + static_cast<unsigned long long>(s) * S;
+        const float *xc = x + static_cast<unsigned long long>(s) * ld;
+        for (unsigned i0 = 0; i0 < S; i0 += 256) {
+            const unsigned i = i0 + threadIdx.x;
+            float v = 0.0f;
+            if (i < S) {
+                const unsigned long long k = static_cast<unsigned long long>(i) + advance;  // index into old row ++ chunk
+                if (k < S) v = st[k];
+                else if (k - S < n_samples) v = xc[k - S];
+            }
+            __syncthreads();
+            if (i < S) st[i] = v;
+        }
+    }
+}
+
 __global__ void ss_preemphasis_kernel(const float *__restrict__ x, float *__restrict__ y, size_t n, size_t shift, float cof)
 {
     // processing.rs:31-53: y[i] = x[i] - cof * x[(i - shift) mod n]
@@ -635,6 +682,48 @@ hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, 
         case 12: return launch_one_varlen<12, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<12>");
         default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_front_generic_stream(const FrontArgs &a, const StreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
+                                       LaunchInfo *info)
+{
+    if (a.out_kind != OUT_MEL && a.out_kind != OUT_STFT) return hipErrorInvalidValue;
+    if (a.blu_n) {
+        switch (log2c) {
+            case 4: return launch_one_stream<4, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<4,chirpz>");
+            case 5: return launch_one_stream<5, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<5,chirpz>");
+            case 6: return launch_one_stream<6, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<6,chirpz>");
+            case 7: return launch_one_stream<7, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<7,chirpz>");
+            case 8: return launch_one_stream<8, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<8,chirpz>");
+            case 9: return launch_one_stream<9, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<9,chirpz>");
+            case 10: return launch_one_stream<10, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<10,chirpz>");
+            case 11: return launch_one_stream<11, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<11,chirpz>");
+            case 12: return launch_one_stream<12, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<12,chirpz>");
+            default: return hipErrorInvalidValue;
+        }
+    }
+    switch (log2c) {
+        case 4: return launch_one_stream<4, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<4>");
+        case 5: return launch_one_stream<5, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<5>");
+        case 6: return launch_one_stream<6, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<6>");
+        case 7: return launch_one_stream<7, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<7>");
+        case 8: return launch_one_stream<8, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<8>");
+        case 9: return launch_one_stream<9, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<9>");
+        case 10: return launch_one_stream<10, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<10>");
+        case 11: return launch_one_stream<11, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<11>");
+        case 12: return launch_one_stream<12, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<12>");
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_stream_advance(float *state, uint32_t state_len, const float *x, unsigned long long ld, uint32_t n_samples,
+                                 uint32_t advance, uint32_t batch, hipStream_t stream)
+{
+    if (batch == 0 || state_len == 0) return hipSuccess;
+    if (advance == 0) return hipErrorInvalidValue;
+    const unsigned grid = batch < 65536u ? batch : 65536u;
+    hipLaunchKernelGGL(ss_stream_advance, dim3(grid), dim3(256), 0, stream, state, state_len, x, ld, n_samples, advance, batch);
+    return hipGetLastError();
 }
 
 hipError_t launch_preemphasis(const float *x, float *y, size_t n, size_t shift, float cof, hipStream_t stream)

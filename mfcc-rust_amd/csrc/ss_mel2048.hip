@@ -22,6 +22,9 @@
 //   * stft output [clip][row][1025] complex64: see the note on write-dominated streams in DESIGN.md (the 1024-clip shape's
 //     269 MB output sits on the edge of the 256 MiB Infinity Cache).
 // Rows >= real_rows (the trailing n_pad rows the reference never writes, functions.rs:121) come out as exact zeros.
+// Streaming builds (a StreamArgs in the trailing argument pack, launch_mel_c1024_stream, reported as ss_mel_c1024s<...>): the
+// samples a window takes from before the chunk come from the stream's carried state instead of zero (functions.rs:137-160); only
+// the edge branch of the loader differs.
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 #include "ss_internal.h"
@@ -70,9 +73,25 @@ constexpr int kWaveFloatsM = kExSlots * 2;  // one exchange region; the two P ro
 // Row pairs of a clip a mel build spends a unit on: every pair, the trailing all-zero ones (functions.rs:121) included.
 __host__ __device__ inline unsigned mel_work_pairs(unsigned rows, unsigned /*real_rows*/) { return (rows + 1) / 2; }
 
-template <int kWavesM, bool STFT, bool FULLP = false>
-__global__ __launch_bounds__(kWavesM * 64) void ss_mel_c1024(const Mel2048Args a)
+// Streaming builds, edge branch of the loader: this lane's 64 samples x[base + 64 e + {0, 1}] of the window, where a sample at p < 0
+// is the stream's carried state[clip * S + S + p] (p >= -S: a window ends at least one hop into the chunk), one past the chunk's
+// end is zero (reference mode: the zero padding of a partial last chunk), an inactive row is all zeros.  Per sample: a state row
+// of odd length, an odd hop or an odd chunk may split any pair.
+__device__ __forceinline__ void stream_window(const StreamArgs &s, const float *xc, unsigned clip, int base, int n, bool active, float2 (&vv)[32])
 {
+    const float *sr = s.state + static_cast<unsigned long long>(clip) * s.state_len + s.state_len;
+#pragma unroll
+    for (int e = 0; e < 32; ++e) {
+        const int p0 = base + 64 * e;
+        vv[e] = make_float2(active && p0 < n ? (p0 < 0 ? sr[p0] : xc[p0]) : 0.f, active && p0 + 1 < n ? (p0 + 1 < 0 ? sr[p0 + 1] : xc[p0 + 1]) : 0.f);
+    }
+}
+
+template <int kWavesM, bool STFT, bool FULLP = false, typename... SA>
+__global__ __launch_bounds__(kWavesM * 64) void ss_mel_c1024(const Mel2048Args a, const SA... sargs)
+{
+    constexpr bool STREAM = sizeof...(SA) > 0;
+    [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(sargs...);
     constexpr bool PREFETCH_M = kWavesM <= 8;  // the next unit's samples are requested while the current one is in its second pass
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -147,7 +166,9 @@ __global__ __launch_bounds__(kWavesM * 64) void ss_mel_c1024(const Mel2048Args a
             // (the address may lie before the clip; it is never dereferenced) and read as zero.
             const int base = start + 2 * j;
             const int n = static_cast<int>(a.n_samples);
-            if (((start | n) & 1) == 0) {
+            if constexpr (STREAM) {
+                stream_window(*sa, xc, clip, base, n, active, vv);
+            } else if (((start | n) & 1) == 0) {
                 int e_lo = base >= 0 ? 0 : (63 - base) >> 6;
                 int e_hi = base >= n ? 0 : min(32, (n - base + 63) >> 6);
                 if (!active) e_hi = 0;
@@ -330,10 +351,13 @@ __global__ __launch_bounds__(kWavesM * 64) void ss_mel_c1024(const Mel2048Args a
 // fit beside them: the rows leave as 8-byte pieces of lines (HBM writes 1.4x the output, traffic 1.09x the algorithmic bytes).
 // MULTI (ss_mel_spectrogram_batches_device): the launch's units are the concatenation of up to kMaxLaunchBatches blocks' row
 // pairs, each block with its own input and output (BatchTable, ss_device.h; Seg / seg_of, ss_wave.h).
-template <bool FIXMEL, bool STFT = false, bool MULTI = false>
-__global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args a, const MultiArg<MULTI> mt)
+template <bool FIXMEL, bool STFT = false, bool MULTI = false, typename... SA>
+__global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args a, const MultiArg<MULTI> mt, const SA... sargs)
 {
+    constexpr bool STREAM = sizeof...(SA) > 0;
+    [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(sargs...);
     static_assert(!(MULTI && STFT), "the batch-table build is a mel-output build");
+    static_assert(!(MULTI && STREAM), "the streaming build takes one block");
     const LifeStamp life = life_begin(a.stamps);  // (diagnostic: null in every ordinary launch)
     constexpr int kWavesM = 12;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -424,7 +448,9 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
                 // clip edges (zero initial state, zero padding of the last chunk, D3) and inactive rows: see ss_mel_c1024
                 const int base = start + 2 * j;
                 const int n = static_cast<int>(a.n_samples);
-                if (((start | n) & 1) == 0) {
+                if constexpr (STREAM) {
+                    stream_window(*sa, xc, clip, base, n, active, v);
+                } else if (((start | n) & 1) == 0) {
                     int e_lo = base >= 0 ? 0 : (63 - base) >> 6;
                     int e_hi = base >= n ? 0 : min(32, (n - base + 63) >> 6);
                     if (!active) e_hi = 0;
@@ -676,6 +702,31 @@ hipError_t launch_mel_w12(const Mel2048Args &a, hipStream_t stream, int num_cus,
                  : mel_go(ss_mel_c1024_w12<false>, "ss_mel_c1024<w12>", grid, 12, lds, stream, info, a, none);
 }
 
+// the streaming builds (mel output): eight waves (the reference bank shape or every bin) / twelve waves (the reference bank shape)
+hipError_t launch_mel_w8_stream(const Mel2048Args &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    const size_t lds = mel_lds_bytes(8, a.mel_wpitch);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const unsigned long long units = static_cast<unsigned long long>(a.batch) * mel_work_pairs(a.rows, a.real_rows);
+    if (units >= 0xffffffffull) return hipErrorInvalidValue;
+    const unsigned grid = mel_grid(units, 8, num_cus);
+    if (a.fullp) return mel_go(ss_mel_c1024<8, false, true, StreamArgs>, "ss_mel_c1024s<fullp>", grid, 8, lds, stream, info, a, s);
+    return mel_go(ss_mel_c1024<8, false, false, StreamArgs>, "ss_mel_c1024s", grid, 8, lds, stream, info, a, s);
+}
+hipError_t launch_mel_w12_stream(const Mel2048Args &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    if (a.fullp) return hipErrorInvalidValue;
+    const size_t lds = mel_lds_bytes(12, a.mel_wpitch);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const unsigned long long units = static_cast<unsigned long long>(a.batch) * mel_work_pairs(a.rows, a.real_rows);
+    if (units >= 0xffffffffull) return hipErrorInvalidValue;
+    const unsigned grid = mel_grid(units, 12, num_cus);
+    const MultiArg<false> none{};
+    const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
+    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, StreamArgs>, "ss_mel_c1024s<w12,mel6321>", grid, 12, lds, stream, info, a, none, s)
+                 : mel_go(ss_mel_c1024_w12<false, false, false, StreamArgs>, "ss_mel_c1024s<w12>", grid, 12, lds, stream, info, a, none, s);
+}
+
 }  // namespace
 
 hipError_t launch_mel_c1024_multi(const Mel2048Args &a_in, int n_batches, const float *const *d_x, float *const *d_out, const size_t *channels,
@@ -743,6 +794,21 @@ hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cu
         if (e != hipErrorInvalidValue) return e;
     }
     return launch_mel_w<8>(a, stream, num_cus, info);
+}
+
+hipError_t launch_mel_c1024_stream(const Mel2048Args &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    if (a.out_stft) return hipErrorInvalidValue;  // (stft output streams on the generic build)
+    if (a.batch == 0) return hipSuccess;
+    // launch_mel_c1024's rule for mel output, so that a continuous stream gets the bits of the one-shot call on the same rows (the
+    // eight- and twelve-wave builds round a few FMAs differently in the last bit).  The lab library's ss_debug_mel_tile(1 / 2) asks
+    // for eight waves (there is no streaming tile build), ss_debug_mel_tile(3) for twelve wherever that build exists.
+    const unsigned long long units = static_cast<unsigned long long>(a.batch) * mel_work_pairs(a.rows, a.real_rows);
+    if (!a.fullp && dbg_mel_build() != 1 && dbg_mel_build() != 2 && (twelve_waves_win(units, num_cus) || dbg_mel_build() == 3)) {
+        const hipError_t e = launch_mel_w12_stream(a, s, stream, num_cus, info);
+        if (e != hipErrorInvalidValue) return e;
+    }
+    return launch_mel_w8_stream(a, s, stream, num_cus, info);
 }
 
 }  // namespace ss

@@ -22,7 +22,8 @@ from ._lib import SpeechSauceError, SsParams, make_params  # noqa: F401
 
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
-           "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "SpeechConfig", "SpeechSauceError"]
+           "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "MelSpectrogramStream", "StftStream",
+           "SpeechConfig", "SpeechSauceError"]
 
 
 def _is_torch(x) -> bool:
@@ -547,6 +548,152 @@ def stft(signal, sampling_frequency, frame_length=0.020, fft_length=512, **switc
         _lib.check(lib.ss_stft(config.handle, x.ctypes.data, ch, L, out.ctypes.data))
         z = out.view(np.complex64)[..., 0]
     return z[0] if one_d else z
+
+
+# ---- streaming STFT / mel spectrogram with carried state (functions.rs:86-170, config.rs:126,162) --------------------------
+
+STREAM_MODES = {"reference": 0, "continuous": 1}  # SS_STREAM_REFERENCE, SS_STREAM_CONTINUOUS
+
+
+class _StreamBase:
+    """Chunks of ``n_streams`` live audio streams in, spectrogram rows out, with the last ``fft_length - hop`` samples of every
+    stream carried from call to call (the reference's ``analysis_mem``).  ``mode="continuous"``: chunks of whole hops, one real
+    row per hop; ``mode="reference"``: exactly what the reference's ``stft1`` / ``mel_spectrogram1`` return on a ``SpeechConfig``
+    that has seen the earlier chunks.  See ``ss_mel_spectrogram_stream`` in ``include/speechsauce_amd.h``."""
+
+    _what = ""
+
+    def __init__(self, n_streams, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
+                 low_frequency, high_frequency, dc_elimination, mode, switches):
+        if mode not in STREAM_MODES:
+            raise ValueError(f"{self._what}: mode must be one of {sorted(STREAM_MODES)}, got {mode!r}")
+        if int(n_streams) < 1:
+            raise ValueError(f"{self._what}: n_streams must be at least 1")
+        self.n_streams = int(n_streams)
+        self.mode = mode
+        self._args = (sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length, low_frequency,
+                      high_frequency, dc_elimination, dict(switches))
+        self._params = make_params(sample_rate=sampling_frequency, fft_points=fft_length, frame_length=frame_length,
+                                   frame_stride=frame_stride, num_cepstral=num_cepstral, num_filters=num_filters,
+                                   low_frequency=low_frequency, high_frequency=high_frequency, dc_elimination=dc_elimination,
+                                   **switches)
+        S = C.c_size_t()
+        _lib.check(_lib.lib().ss_stream_state_len(C.byref(self._params), C.byref(S)))  # no STFT path: SS_ERR_BAD_CONFIG here
+        self.state_len = S.value
+        self.hop = int(fft_length) - self.state_len
+        self._state = None
+        self._where = None
+
+    @property
+    def state(self):
+        """[n_streams, fft_length - hop] float32: a torch tensor on the device of the first chunk, or a numpy array; None before
+        the first call."""
+        return self._state
+
+    def reset(self, streams=None):
+        """Zero the state of every stream, or of the given stream indices (a fresh stream)."""
+        if self._state is None:
+            return
+        if streams is None:
+            self._state[...] = 0
+        else:
+            idx = list(np.atleast_1d(np.asarray(streams, dtype=np.int64)))
+            if idx:
+                self._state[idx] = 0
+
+    def _rows(self, n):
+        r, rr = C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.lib().ss_stream_rows(C.byref(self._params), STREAM_MODES[self.mode], n, C.byref(r), C.byref(rr)))
+        return r.value
+
+    def _prepare(self, chunk):
+        sig = _require_f32(chunk, (1, 2), self._what)
+        if sig.ndim == 1:
+            if self.n_streams != 1:
+                raise ValueError(f"{self._what}: a 1-D chunk needs n_streams == 1, this object has {self.n_streams}")
+            sig = sig[None, :]
+        if sig.shape[0] != self.n_streams:
+            raise ValueError(f"{self._what}: chunk has {sig.shape[0]} streams, expected {self.n_streams}")
+        n = sig.shape[1]
+        if n == 0:
+            raise ValueError(f"{self._what}: empty chunk")
+        if self.mode == "continuous" and n % self.hop:
+            raise ValueError(f"{self._what}: continuous mode takes whole hops: {n} samples is not a multiple of {self.hop}")
+        on_dev = _is_torch(sig)
+        where = ("cuda", sig.device.index) if on_dev else ("host",)
+        if self._state is None:
+            if on_dev:
+                import torch
+
+                self._state = torch.zeros((self.n_streams, self.state_len), dtype=torch.float32, device=sig.device)
+            else:
+                self._state = np.zeros((self.n_streams, self.state_len), dtype=np.float32)
+            self._where = where
+        elif where != self._where:
+            raise ValueError(f"{self._what}: the state lives on {self._where}, this chunk on {where}")
+        a = self._args
+        config = _cfg(*a[:9], a[9], sig)
+        return sig, n, self._rows(n), config
+
+    def _launch(self, sig, n, config, out, dev_fn, host_fn):
+        lib = _lib.lib()
+        B = self.n_streams
+        mode = STREAM_MODES[self.mode]
+        if _is_torch(sig):
+            import torch
+
+            x = sig if sig.stride(1) == 1 else sig.contiguous()
+            with torch.cuda.device(x.device):
+                _lib.check(getattr(lib, dev_fn)(config.handle, mode, x.data_ptr(), B, n, x.stride(0) if B > 1 else n,
+                                                self._state.data_ptr(), out.data_ptr(), _stream_ptr()))
+        else:
+            x = np.ascontiguousarray(sig)
+            _lib.check(getattr(lib, host_fn)(config.handle, mode, x.ctypes.data, B, n, n, self._state.ctypes.data, out.ctypes.data))
+
+
+class MelSpectrogramStream(_StreamBase):
+    """Streaming ``mel_spectrogram``: ``__call__(chunk [n_streams, n])`` -> ``[n_streams, num_filters, rows]``."""
+
+    _what = "MelSpectrogramStream"
+
+    def __init__(self, n_streams, sampling_frequency, frame_length=0.020, num_filters=40, fft_length=512, low_frequency=0,
+                 high_frequency=None, mode="continuous", **switches):
+        super().__init__(n_streams, sampling_frequency, frame_length, 0.01, 13, num_filters, fft_length, low_frequency,
+                         high_frequency, True, mode, switches)
+
+    def __call__(self, chunk):
+        sig, n, R, config = self._prepare(chunk)
+        M = config.params.num_filters
+        if _is_torch(sig):
+            import torch
+
+            out = torch.empty((self.n_streams, M, R), dtype=torch.float32, device=sig.device)
+        else:
+            out = np.empty((self.n_streams, M, R), dtype=np.float32)
+        self._launch(sig, n, config, out, "ss_mel_spectrogram_stream_device", "ss_mel_spectrogram_stream")
+        return out
+
+
+class StftStream(_StreamBase):
+    """Streaming ``stft``: ``__call__(chunk [n_streams, n])`` -> complex64 ``[n_streams, rows, fft_length // 2 + 1]``."""
+
+    _what = "StftStream"
+
+    def __init__(self, n_streams, sampling_frequency, frame_length=0.020, fft_length=512, mode="continuous", **switches):
+        super().__init__(n_streams, sampling_frequency, frame_length, 0.01, 13, 40, fft_length, 0, None, True, mode, switches)
+
+    def __call__(self, chunk):
+        sig, n, R, config = self._prepare(chunk)
+        F = config.params.fft_points // 2 + 1
+        if _is_torch(sig):
+            import torch
+
+            out = torch.empty((self.n_streams, R, F, 2), dtype=torch.float32, device=sig.device)
+            self._launch(sig, n, config, out, "ss_stft_stream_device", "ss_stft_stream")
+            return torch.view_as_complex(out)
+        out = np.empty((self.n_streams, R, F, 2), dtype=np.float32)
+        self._launch(sig, n, config, out, "ss_stft_stream_device", "ss_stft_stream")
+        return out.view(np.complex64)[..., 0]
 
 
 def stack_frames(signal, sampling_frequency, frame_length=0.020, frame_stride=0.020, filter=None, zero_padding=False, **switches):
