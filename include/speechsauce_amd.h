@@ -289,6 +289,49 @@ int ss_stft_stream_device(const ss_config *cfg, int mode, const float *d_x, size
 int ss_mel_spectrogram_stream_device(const ss_config *cfg, int mode, const float *d_x, size_t n_streams, size_t n_samples, size_t ld,
                                      float *d_state, float *d_out, void *stream);
 
+/* ---- streaming MFCC / mfe with carried frame state (feature.rs:99-233 over live audio) ----
+ * The reference's mfcc / mfe keep no state; these entry points give a live stream one new row per hop, with no recomputation of
+ * overlapping frames.  flen / step as ss_frame_sizes; sh = preemph_shift if preemph_coef != 0, else 0.  Every stream carries the
+ * last S = max(flen + sh - step, 0) samples it was fed in a caller-owned buffer: [n_streams x S] floats, contiguous, updated in place
+ * by every call.  All zeros is a fresh stream; zeroing a row resets that stream.  S == 0 is legal (the state pointer may then be
+ * NULL and no state advance is launched).
+ *   Chunks: n_samples a multiple of step (else SS_ERR_ARG, state untouched); R = n_samples / step rows per stream.  Row g of a
+ *   stream, counted in hops since its reset, is the frame s[(g+1) step - flen : (g+1) step] of the stream's samples s with zeros
+ *   before its start, through every per-frame stage of the config: pre-emphasis y[n] = s[n] - c s[n - sh] (same zeros; no circular
+ *   wrap: a stream has no end), mfcc_window, fft_points (chirp-z included), spectrum_exponent, the bank, dct2_gain, dc_elimination,
+ *   zero handling.  Consecutive calls concatenate to the same rows however the stream was cut.
+ *   Framing: SS_FRAMING_CONTRACT and SS_FRAMING_PADDED stream alike (they differ only at a clip's end); SS_FRAMING_LITERAL and
+ *   SS_FRAMING_CENTER are SS_ERR_BAD_CONFIG, from ss_frame_stream_state_len as well.
+ *   DCT scaling: SS_DCT_REFERENCE scales by n = T * M (feature.rs:126-131), and T is the caller's norm_frames (>= 1; 0 is SS_ERR_ARG;
+ *   typically the frame count of the model's input window).  Every streamed row is scaled as rows t >= 1 of the one-shot call are:
+ *   column 0 unscaled (times dct2_gain), columns 1.. times dct2_gain / sqrtf(2n), with the host's bits.  The one-shot [0,0] factor
+ *   belongs to a clip's first frame, and a stream has no first frame: it is never applied.  With dc_elimination on (the default)
+ *   column 0 is ln(energy) either way.  SS_DCT_ORTHO ignores norm_frames.
+ *   One-shot equivalence: let G be the rows fed since reset and sh <= step.  The concatenated MFCC rows equal rows 1 .. G of
+ *   ss_mfcc on zeros(flen) ++ s ++ zeros(step) (exactly G + 1 frames) on a config with norm_frames = G + 1 frames, and likewise the
+ *   mfe features and energies (the trailing zeros make the one-shot's circular pre-emphasis wrap read zeros).  Where both calls run
+ *   the same kernel family, bit for bit: the default 512-point MFCC / mfe shape runs on streaming builds of the dedicated kernel
+ *   (ss_mfcc_c256s), everything else on the streaming build of the generic kernel (the other dedicated kernels -- 256 / 1024 /
+ *   2048 / 4096 points -- have no streaming build).
+ * Outputs: MFCC [n_streams x R x num_cepstral]; mfe feat [n_streams x R x num_filters], energy [n_streams x R].  Arguments as
+ * ss_stft_stream_device: n_streams == 0 is SS_OK with nothing launched; null buffers, ld < n_samples, n_samples == 0, more than
+ * 2^31 - 1 samples or streams, and a state range that overlaps x or an output are SS_ERR_ARG.  A rejected call leaves the state as
+ * it was. */
+/* host only, no device: S = max(flen + sh - step, 0); SS_ERR_BAD_CONFIG for literal / centred framing */
+int ss_frame_stream_state_len(const ss_params *p, size_t *state_len);
+/* host only: rows = n_samples / step; SS_ERR_ARG if n_samples is 0 or not a multiple of step */
+int ss_frame_stream_rows(const ss_params *p, size_t n_samples, size_t *rows);
+/* host pointers, synchronous: one upload of x and state, the device call, one download of the outputs and state */
+int ss_mfcc_stream(const ss_config *cfg, const float *x, size_t n_streams, size_t n_samples, size_t ld, uint32_t norm_frames,
+                   float *state, float *out);
+int ss_mfe_stream(const ss_config *cfg, const float *x, size_t n_streams, size_t n_samples, size_t ld, float *state, float *feat,
+                  float *energy);
+/* device pointers, asynchronous on `stream`, graph-capturable: two stream-ordered launches (the rows, then the state advance) */
+int ss_mfcc_stream_device(const ss_config *cfg, const float *d_x, size_t n_streams, size_t n_samples, size_t ld, uint32_t norm_frames,
+                          float *d_state, float *d_out, void *stream);
+int ss_mfe_stream_device(const ss_config *cfg, const float *d_x, size_t n_streams, size_t n_samples, size_t ld, float *d_state,
+                         float *d_feat, float *d_energy, void *stream);
+
 /* ss_stack_frames_signal on device pointers (d_window: frame_len floats in device memory, or NULL) */
 int ss_stack_frames_signal_device(const float *d_x, size_t n_samples, uint32_t sample_rate, float frame_length, float frame_stride,
                                   const float *d_window, int zero_padding, float *d_frames, void *stream);

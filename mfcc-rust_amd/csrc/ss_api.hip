@@ -857,6 +857,165 @@ int stream_host(const ss_config *cfg, int out_kind, int mode, const float *x, si
     return rc;
 }
 
+// Streaming MFCC / mfe launch (ss_mfcc_stream_device / ss_mfe_stream_device): the rows of one call over a carried state per
+// stream, then the state advance -- two kernels on `stream` (none for the advance where S == 0).  Candidate order: the streaming
+// build of the 512-point headline kernel where it has one for the shape, else the streaming build of the generic kernel.
+int launch_frame_stream(const ss_config *cfg, int out_kind, const float *d_x, size_t n_streams, size_t n, size_t ld, uint32_t norm_frames,
+                        float *d_state, float *out0, float *out1, hipStream_t stream)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_streams == 0) return SS_OK;
+    const ss::HostTables &h = cfg->host;
+    size_t S = 0, R = 0;
+    int rc = ss_frame_stream_state_len(&h.params, &S);
+    if (rc) return rc;
+    if (!d_x || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !d_state)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (ld < n) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
+    if (n == 0 || n > 0x7fffffffull || n_streams > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "bad chunk length / stream count");
+    const bool ortho = h.params.dct_norm == SS_DCT_ORTHO;
+    if (out_kind == ss::OUT_MFCC && !ortho && norm_frames == 0)
+        return ss::fail(SS_ERR_ARG, "norm_frames must be >= 1: the reference DCT scaling needs a frame count");
+    if ((rc = ss_frame_stream_rows(&h.params, n, &R))) return rc;
+    if (static_cast<unsigned long long>(n_streams) * R >= 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many rows in one call");
+    const size_t cols = out_kind == ss::OUT_MFCC ? h.params.num_cepstral : h.params.num_filters;
+    const size_t sbytes = n_streams * S * sizeof(float);
+    if (S > 0 && (ranges_overlap(d_state, sbytes, d_x, ((n_streams - 1) * ld + n) * sizeof(float)) ||
+                  ranges_overlap(d_state, sbytes, out0, n_streams * R * cols * sizeof(float)) ||
+                  (out1 && ranges_overlap(d_state, sbytes, out1, n_streams * R * sizeof(float)))))
+        return ss::fail(SS_ERR_ARG, "the state buffer overlaps the input or an output");
+    {
+        const int drc = check_device(cfg);  // see launch_frames
+        if (drc) return drc;
+        const int erc = pending_device_error(cfg);
+        if (erc) return erc;
+    }
+    ss::FrontArgs a{};
+    fill_common(cfg, a);
+    a.x = d_x;
+    a.ld = ld;
+    a.n_samples = static_cast<uint32_t>(n);
+    a.batch = static_cast<uint32_t>(n_streams);
+    a.flen = h.d.flen;
+    a.step = h.d.step;
+    a.n_frames = static_cast<uint32_t>(R);
+    a.frame_mode = ss::FRAME_NORMAL;  // every row's frame ends inside the chunk: contract and padded framing agree
+    a.pad_reflect = h.params.pad_mode == SS_PAD_REFLECT;
+    a.preemph = h.params.preemph_coef;
+    a.preemph_shift = static_cast<uint32_t>(h.params.preemph_shift > 0 ? h.params.preemph_shift : 1);
+    a.window = cfg->d_window_mfcc;
+    a.scale = 1.0f / static_cast<float>(h.params.fft_points);  // processing.rs:180
+    // the scales of launch_frames with T = norm_frames; a stream has no first frame, so [0,0] gets column 0's scale
+    const float g = h.params.dct2_gain;
+    const float M = static_cast<float>(h.params.num_filters);
+    if (ortho) {
+        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * M));
+        a.dct_scale_0 = a.dct_scale_00 = g * (1.0f / sqrtf(4.0f * M));
+    } else {
+        const float nn = static_cast<float>(static_cast<size_t>(norm_frames > 0 ? norm_frames : 1u) * h.params.num_filters);
+        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * nn));
+        a.dct_scale_0 = a.dct_scale_00 = g;
+    }
+    a.out_kind = out_kind;
+    a.out0 = out0;
+    a.out1 = out1;
+    ss::FrameStreamArgs fsa{d_state, static_cast<uint32_t>(S), static_cast<int32_t>(h.d.flen) - static_cast<int32_t>(h.d.step)};
+    ss::LaunchInfo info{};
+    hipError_t e = hipErrorInvalidValue;
+    if (!ss::dbg_force_generic() && cfg->fast.ok && !cfg->fast.fullp && a.window == nullptr && a.preemph == 0.0f && !ortho) {
+        ss::Fast512Args f{};
+        f.x = d_x;
+        f.ld = ld;
+        f.n_samples = a.n_samples;
+        f.batch = a.batch;
+        f.flen = a.flen;
+        f.step = a.step;
+        f.n_frames = a.n_frames;
+        f.scale = a.scale;
+        f.spectrum_exponent = a.spectrum_exponent;
+        f.tab = cfg->d_fast_tab;
+        f.mel_wpitch = cfg->fast.wpitch;
+        for (int s = 0; s < 3; ++s) f.mel_q4[s] = cfg->fast.q4[s];
+        f.n_filters = a.n_filters;
+        f.n_ceps = a.n_ceps;
+        f.dct_scale_k = a.dct_scale_k;
+        f.dct_scale_0 = a.dct_scale_0;
+        f.dct_scale_00 = a.dct_scale_00;
+        f.dc_elimination = a.dc_elimination;
+        f.out = out0;
+        f.out_energy = out1;
+        f.out_mfe = out_kind == ss::OUT_MFE ? 1 : 0;
+        f.paired = cfg->fast.paired ? (cfg->fast.tight ? 2 : 1) : 0;
+        e = ss::launch_mfcc_c256_stream(f, fsa, stream, cfg->num_cus, &info);
+        // hipErrorInvalidValue before the launch: the configuration has no streaming build of this kernel -> the generic build
+        if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mfcc_c256_stream");
+    }
+    if (e != hipSuccess) {
+        e = ss::launch_front_generic_frame_stream(a, fsa, h.d.log2c, stream, cfg->num_cus, &info);
+        if (e != hipSuccess) return hip_fail(e, "launch_front_generic_frame_stream");
+    }
+    g_last_kernel = info.kernel_name;
+    e = ss::launch_stream_advance(d_state, static_cast<uint32_t>(S), d_x, ld, a.n_samples, a.n_samples, a.batch, stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_stream_advance");
+    return SS_OK;
+}
+
+// Host-pointer form, as stream_host: one upload of x and the state, the device call, one download of the outputs and the state on
+// the config's first host-pipeline stream.  The caller's state is written only once everything before it succeeded.
+int frame_stream_host(const ss_config *cfg, int out_kind, const float *x, size_t n_streams, size_t n, size_t ld, uint32_t norm_frames,
+                      float *state, float *out0, float *out1)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_streams == 0) return SS_OK;
+    const ss::HostTables &h = cfg->host;
+    size_t S = 0, R = 0;
+    int rc = ss_frame_stream_state_len(&h.params, &S);
+    if (rc) return rc;
+    if (!x || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !state)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (ld < n) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
+    if (n == 0 || n > 0x7fffffffull || n_streams > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "bad chunk length / stream count");
+    if ((rc = ss_frame_stream_rows(&h.params, n, &R))) return rc;
+    const size_t cols = out_kind == ss::OUT_MFCC ? h.params.num_cepstral : h.params.num_filters;
+    const size_t out0_floats = n_streams * R * cols, out1_floats = out1 ? n_streams * R : 0;
+    const size_t in_floats = (n_streams - 1) * ld + n;
+    const size_t sbytes = n_streams * S * sizeof(float);
+    if (S > 0 && (ranges_overlap(state, sbytes, x, in_floats * sizeof(float)) || ranges_overlap(state, sbytes, out0, out0_floats * sizeof(float)) ||
+                  (out1 && ranges_overlap(state, sbytes, out1, out1_floats * sizeof(float)))))
+        return ss::fail(SS_ERR_ARG, "the state buffer overlaps the input or an output");
+    if ((rc = check_device(cfg))) return rc;
+    ss_config::HostPipe &hp = cfg->pipe;
+    std::lock_guard<std::mutex> lock(hp.mu);
+    if (!hp.stream[0]) {
+        SS_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
+        SS_HIP(hipEventCreateWithFlags(&hp.done[0], hipEventDisableTiming));
+    }
+    hipStream_t st = hp.stream[0];
+    DeviceBuf dx, ds, d0, d1;
+    if ((rc = dx.alloc(in_floats * sizeof(float))) || (S > 0 && (rc = ds.alloc(sbytes))) || (rc = d0.alloc(out0_floats * sizeof(float))) ||
+        (out1 && (rc = d1.alloc(out1_floats * sizeof(float)))))
+        return rc;
+    hipError_t e = hipMemcpyAsync(dx.p, x, in_floats * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && S > 0) e = hipMemcpyAsync(ds.p, state, sbytes, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
+    if (rc == SS_OK)
+        rc = launch_frame_stream(cfg, out_kind, dx.as<const float>(), n_streams, n, ld, norm_frames, S > 0 ? ds.as<float>() : nullptr,
+                                 d0.as<float>(), out1 ? d1.as<float>() : nullptr, st);
+    if (rc == SS_OK) {
+        e = hipMemcpyAsync(out0, d0.p, out0_floats * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out1) e = hipMemcpyAsync(out1, d1.p, out1_floats * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (D2H)");
+    }
+    // the copies may still touch the caller's buffers and ours: synchronise whatever happened
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "frame stream host call");
+    if (rc == SS_OK) rc = pending_device_error(cfg);
+    if (rc == SS_OK && S > 0) {
+        e = hipMemcpyAsync(state, ds.p, sbytes, hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e != hipSuccess || es != hipSuccess) rc = hip_fail(e != hipSuccess ? e : es, "hipMemcpyAsync (state D2H)");
+    }
+    return rc;
+}
+
 // stack_frames (processing.rs:65-129): frames[clip][t][i] = x[clip][t * step + i] (* window[i]); one thread per element,
 // neighbouring threads on neighbouring samples of a frame.  frame_mode as in the fused kernels' loaders: contract framing,
 // zero_padding = true (zeros past the signal), the literal exact_chunks copy (all-zero rows for > 2 frames, x[0 .. flen & ~1]
@@ -1930,6 +2089,31 @@ int ss_mel_spectrogram_stream(const ss_config *cfg, int mode, const float *x, si
                               float *state, float *out)
 {
     return stream_host(cfg, ss::OUT_MEL, mode, x, n_streams, n_samples, ld, state, out);
+}
+
+int ss_mfcc_stream_device(const ss_config *cfg, const float *d_x, size_t n_streams, size_t n_samples, size_t ld, uint32_t norm_frames,
+                          float *d_state, float *d_out, void *stream)
+{
+    return launch_frame_stream(cfg, ss::OUT_MFCC, d_x, n_streams, n_samples, ld, norm_frames, d_state, d_out, nullptr,
+                               static_cast<hipStream_t>(stream));
+}
+
+int ss_mfe_stream_device(const ss_config *cfg, const float *d_x, size_t n_streams, size_t n_samples, size_t ld, float *d_state,
+                         float *d_feat, float *d_energy, void *stream)
+{
+    return launch_frame_stream(cfg, ss::OUT_MFE, d_x, n_streams, n_samples, ld, 1u, d_state, d_feat, d_energy, static_cast<hipStream_t>(stream));
+}
+
+int ss_mfcc_stream(const ss_config *cfg, const float *x, size_t n_streams, size_t n_samples, size_t ld, uint32_t norm_frames,
+                   float *state, float *out)
+{
+    return frame_stream_host(cfg, ss::OUT_MFCC, x, n_streams, n_samples, ld, norm_frames, state, out, nullptr);
+}
+
+int ss_mfe_stream(const ss_config *cfg, const float *x, size_t n_streams, size_t n_samples, size_t ld, float *state, float *feat,
+                  float *energy)
+{
+    return frame_stream_host(cfg, ss::OUT_MFE, x, n_streams, n_samples, ld, 1u, state, feat, energy);
 }
 
 int ss_preemphasis_device(const float *d_x, size_t n_samples, long shift, float cof, float *d_y, void *stream)

@@ -210,6 +210,20 @@ hipError_t launch_front_generic_stream(const FrontArgs &a, const StreamArgs &s, 
 // before any lane of the workgroup writes it).
 hipError_t launch_stream_advance(float *state, uint32_t state_len, const float *x, unsigned long long ld, uint32_t n_samples,
                                  uint32_t advance, uint32_t batch, hipStream_t stream);
+
+// Streaming MFCC / mfe (ss_mfcc_stream_device / ss_mfe_stream_device): row t of a call (the stream's frame that ends at chunk
+// sample (t + 1) * step) starts at chunk sample t * step - lead, lead = flen - step.  Stream s carries the last
+// S = max(flen + sh - step, 0) samples it was fed (sh: the pre-emphasis shift, 0 without pre-emphasis): sample p < 0 of stream s is
+// state[s * S + S + p], and every frame sample and pre-emphasis tap that a row reads has p >= -S.
+struct FrameStreamArgs {
+    const float *state;  // [batch][state_len]; null where state_len == 0
+    uint32_t state_len;  // S
+    int32_t lead;        // flen - step (negative where frames are shorter than the hop)
+};
+// the streaming build of ss_front_generic's MFCC / mfe path (any configuration the generic kernel serves, contract or padded framing):
+// a as for launch_front_generic's MFCC path with n_frames = rows per stream, frame_mode FRAME_NORMAL and dct_scale_00 = dct_scale_0
+hipError_t launch_front_generic_frame_stream(const FrontArgs &a, const FrameStreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
+                                             LaunchInfo *info);
 #if SS_LAB
 // Test aid (lab library): every word of every CU's LDS := 0xFFFFFFFF (ss_debug_poison_lds).
 hipError_t launch_poison_lds(hipStream_t stream, int num_cus);
@@ -290,6 +304,11 @@ hipError_t launch_mfcc_c256_multi(const Fast512Args &a, int n_batches, const flo
 // over the packed output rows (VarlenArgs, declared below).  hipErrorInvalidValue before the launch for every other configuration.
 struct VarlenArgs;
 hipError_t launch_mfcc_c256_varlen(const Fast512Args &a, const VarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
+// Streaming MFCC / mfe on the headline build (FrameStreamArgs, declared above): a as for launch_mfcc_c256 with batch = streams,
+// n_frames = rows per stream, n_samples = the chunk; MFCC of the default frame shape and bank (40 filters, paired tight-tap layout)
+// or mfe of the default bank, no window, no pre-emphasis, reference DCT scales with dct_scale_00 = dct_scale_0.
+// hipErrorInvalidValue before the launch for every other configuration.
+hipError_t launch_mfcc_c256_stream(const Fast512Args &a, const FrameStreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info);
 // whether the kernel has an mfe-output / windowed / pre-emphasised build for this shape (the default bank at flen 320)
 bool mfcc_c256_has_mfe(const Fast512Args &a);
 

@@ -1359,6 +1359,37 @@ int ss_stream_rows(const ss_params *p, int mode, size_t n_samples, size_t *rows,
     return SS_OK;
 }
 
+int ss_frame_stream_state_len(const ss_params *p, size_t *state_len)
+{
+    if (!p || !state_len) return ss::fail(SS_ERR_ARG, "null argument");
+    int rc = ss::validate(*p);
+    if (rc) return rc;
+    // literal framing (processing.rs:110-120 as written) and centred frames depend on a clip's end; a stream has none
+    if (p->framing == SS_FRAMING_LITERAL || p->framing == SS_FRAMING_CENTER)
+        return ss::fail(SS_ERR_BAD_CONFIG, "streaming MFCC / mfe takes contract or padded framing");
+    ss::Derived d;
+    if ((rc = ss::derive(*p, d))) return rc;
+    // a row reads flen samples ending at a hop boundary, and pre-emphasis reaches sh samples further back
+    const size_t sh = p->preemph_coef != 0.0f ? static_cast<size_t>(p->preemph_shift) : 0u;
+    *state_len = d.flen + sh > d.step ? d.flen + sh - d.step : 0u;
+    return SS_OK;
+}
+
+int ss_frame_stream_rows(const ss_params *p, size_t n_samples, size_t *rows)
+{
+    if (!p || !rows) return ss::fail(SS_ERR_ARG, "null argument");
+    size_t S = 0;
+    int rc = ss_frame_stream_state_len(p, &S);
+    if (rc) return rc;
+    ss::Derived d;
+    if ((rc = ss::derive(*p, d))) return rc;
+    if (n_samples == 0) return ss::fail(SS_ERR_ARG, "a streaming call needs at least one hop");
+    if (n_samples % d.step)
+        return ss::fail(SS_ERR_ARG, "streaming MFCC / mfe takes whole hops: n_samples must be a multiple of " + std::to_string(d.step));
+    *rows = n_samples / d.step;  // one row per hop
+    return SS_OK;
+}
+
 int ss_filterbank(const ss_params *p, float *fb, int32_t *idx)
 {
     if (!p || !fb) return ss::fail(SS_ERR_ARG, "null argument");

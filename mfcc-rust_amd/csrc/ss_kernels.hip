@@ -6,6 +6,8 @@
 // clips of different lengths (VarlenArgs, ss_device.h).
 // ss_front_generic<LOG2C, BLU, StreamArgs> (reported as ss_front_generic_stream<LOG2C>): the STFT / mel path with a carried state
 // per stream (StreamArgs, ss_device.h); ss_stream_advance moves the state on behind it.
+// ss_front_generic<LOG2C, BLU, FrameStreamArgs> (reported as ss_front_generic_fstream<LOG2C>): the MFCC / mfe path with a carried
+// state per stream (FrameStreamArgs, ss_device.h): frames and pre-emphasis taps before the chunk read the stream's state.
 //
 //   * A real frame of N = 2C samples is packed as C complex points z[n] = x[2n] + i x[2n+1]
 //     and transformed by a Stockham autosort FFT whose butterflies live in registers: every
@@ -236,14 +238,19 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
 // VAR: packed variable-length clips (launch_front_generic_varlen): the flat frame index is the output row, and the clip / frame
 // split, the clip's samples, its length, its literal-framing mode and its DCT scales come from the offset tables (VarlenArgs).
 // STREAM: the STFT / mel path of launch_front_generic_stream -- a window sample before the chunk comes from the stream's state.
-// (V: empty, one VarlenArgs or one StreamArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
+// FSTREAM: the MFCC / mfe path of launch_front_generic_frame_stream -- clip = stream, frame = row of this call; row t starts at chunk
+// sample t * step - lead, and a frame sample or pre-emphasis tap before the chunk comes from the stream's state (no circular wrap).
+// (V: empty, one VarlenArgs, one StreamArgs or one FrameStreamArgs -- an empty pack leaves the argument block of the equal-length
+// builds exactly as it was)
 template <int LOG2C, bool BLU, typename... V>
 __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
 {
     constexpr bool VAR = (std::is_same_v<V, VarlenArgs> || ...);
     constexpr bool STREAM = (std::is_same_v<V, StreamArgs> || ...);
+    constexpr bool FSTREAM = (std::is_same_v<V, FrameStreamArgs> || ...);
     [[maybe_unused]] const VarlenArgs *va = pack_arg<VarlenArgs>(vargs...);
     [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(vargs...);
+    [[maybe_unused]] const FrameStreamArgs *fa = pack_arg<FrameStreamArgs>(vargs...);
     using G = Geo<LOG2C>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
@@ -262,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     // MEL mode: transposed output tile [M][rows_tile + 1] after all slots
     float *tile = reinterpret_cast<float *>(smem_raw + slot_bytes * G::FPB);
 
-    const bool mel_mode = STREAM || (!VAR && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT));
+    const bool mel_mode = STREAM || (!VAR && !FSTREAM && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT));
     const int F = BLU ? static_cast<int>(a.blu_n / 2 + 1) : G::F;  // bins per row
 
     if (!mel_mode) {
@@ -278,6 +285,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
             unsigned n_samples = a.n_samples;
             int frame_mode = a.frame_mode;
             float dct_scale_k = a.dct_scale_k, dct_scale_00 = a.dct_scale_00;
+            [[maybe_unused]] const float *srow = nullptr;  // FSTREAM: the stream's state, indexed from its end (sample p < 0 is srow[p])
             if constexpr (VAR) {
                 // rows past the last clip (a larger output block) are left alone; rows of an inconsistent clip are skipped
                 const VarClip c = varlen_clip(*va, a.flen, a.step, active ? varlen_find(*va, gf) : 0u);
@@ -293,6 +301,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 const unsigned clip = active ? gf32 / a.n_frames : 0u;
                 t = active ? gf32 - clip * a.n_frames : 0u;
                 xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
+                if constexpr (FSTREAM) srow = fa->state + static_cast<unsigned long long>(clip) * fa->state_len + fa->state_len;
             }
             // stack_frames (processing.rs:65-129, contract framing) + zero pad to N (:147-156)
             const unsigned base = (frame_mode == FRAME_NORMAL || frame_mode == FRAME_PADDED) ? t * a.step : 0u;
@@ -300,6 +309,20 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
             // sample i of the frame after framing, fused pre-emphasis and the optional window (zero beyond the frame)
             auto sample = [&](unsigned i) -> float {
                 float val = 0.0f;
+                if constexpr (FSTREAM) {
+                    // the stream's samples s[p], p = t * step - lead + i, with zeros before its start (the zeroed state);
+                    // pre-emphasis y[p] = s[p] - c s[p - sh] reaches back into the state, never round the chunk
+                    if (active && i < a.flen) {
+                        const long long p = static_cast<long long>(t) * a.step - fa->lead + i;
+                        val = p < 0 ? srow[p] : xc[p];
+                        if (a.preemph != 0.0f) {
+                            const long long q = p - static_cast<long long>(a.preemph_shift);
+                            val -= a.preemph * (q < 0 ? srow[q] : xc[q]);
+                        }
+                        if (a.window) val *= a.window[i];
+                    }
+                    return val;
+                }
                 if (active && i < lim) {
                     unsigned idx = base + i;
                     // FRAME_PADDED (stack_frames zero_padding = true, processing.rs:85-97): zeros past the signal
@@ -543,6 +566,29 @@ hipError_t launch_one_varlen(const FrontArgs &a, const VarlenArgs &v, hipStream_
 }
 
 template <int LOG2C, bool BLU>
+hipError_t launch_one_fstream(const FrontArgs &a, const FrameStreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info,
+                              const char *name)
+{
+    using G = Geo<LOG2C>;
+    const size_t lds = front_lds_bytes<LOG2C>(a);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, FrameStreamArgs>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    const unsigned long long rows = static_cast<unsigned long long>(a.batch) * a.n_frames;
+    if (rows == 0) return hipSuccess;
+    if (rows >= 0xffffffffull) return hipErrorInvalidValue;
+    const unsigned long long work = (rows + G::FPB - 1) / G::FPB;
+    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
+    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
+    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
+    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, FrameStreamArgs>), dim3(grid), dim3(kBlock), lds, stream, a, s);
+    return hipGetLastError();
+}
+
+template <int LOG2C, bool BLU>
 hipError_t launch_one_stream(const FrontArgs &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info, const char *name)
 {
     const size_t lds = front_lds_bytes<LOG2C>(a);
@@ -712,6 +758,38 @@ hipError_t launch_front_generic_stream(const FrontArgs &a, const StreamArgs &s, 
         case 10: return launch_one_stream<10, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<10>");
         case 11: return launch_one_stream<11, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<11>");
         case 12: return launch_one_stream<12, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<12>");
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_front_generic_frame_stream(const FrontArgs &a, const FrameStreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
+                                             LaunchInfo *info)
+{
+    if (a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE) return hipErrorInvalidValue;
+    if (a.blu_n) {
+        switch (log2c) {
+            case 4: return launch_one_fstream<4, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<4,chirpz>");
+            case 5: return launch_one_fstream<5, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<5,chirpz>");
+            case 6: return launch_one_fstream<6, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<6,chirpz>");
+            case 7: return launch_one_fstream<7, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<7,chirpz>");
+            case 8: return launch_one_fstream<8, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<8,chirpz>");
+            case 9: return launch_one_fstream<9, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<9,chirpz>");
+            case 10: return launch_one_fstream<10, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<10,chirpz>");
+            case 11: return launch_one_fstream<11, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<11,chirpz>");
+            case 12: return launch_one_fstream<12, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<12,chirpz>");
+            default: return hipErrorInvalidValue;
+        }
+    }
+    switch (log2c) {
+        case 4: return launch_one_fstream<4, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<4>");
+        case 5: return launch_one_fstream<5, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<5>");
+        case 6: return launch_one_fstream<6, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<6>");
+        case 7: return launch_one_fstream<7, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<7>");
+        case 8: return launch_one_fstream<8, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<8>");
+        case 9: return launch_one_fstream<9, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<9>");
+        case 10: return launch_one_fstream<10, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<10>");
+        case 11: return launch_one_fstream<11, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<11>");
+        case 12: return launch_one_fstream<12, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<12>");
         default: return hipErrorInvalidValue;
     }
 }

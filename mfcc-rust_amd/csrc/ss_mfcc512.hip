@@ -219,6 +219,47 @@ __device__ __forceinline__ unsigned load_quad(const Fast512Args &a, unsigned qua
     return t;
 }
 
+// STRM builds (ss_mfcc_stream_device): clip = stream, frame = row of this call; frame t of stream `clip` starts at chunk sample
+// t * step - lead (FrameStreamArgs).  A quad whose frames all lie inside the chunk takes the plain path; one with a frame that
+// reaches before the chunk takes the edge branch, where every frame is two contiguous runs -- the tail of the stream's state, then
+// the head of the chunk -- and a lane's sample pair comes whole from one of them (the launcher keeps step and lead even, so no pair
+// straddles the two; pairs load as 8-byte words at dword alignment, so odd row strides or state lengths are fine).  At one hop per
+// call every frame is an edge frame: per pair the edge costs an address select, not a per-sample path.
+template <int NE>
+__device__ __forceinline__ unsigned load_quad_stream(const Fast512Args &a, const FrameStreamArgs &s, unsigned quad, unsigned total, int f,
+                                                     int j, float2 (&vin)[NE])
+{
+    const unsigned q4 = quad * 4;                                       // uniform
+    const unsigned fl = min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last frame redo it
+    unsigned clip, t;
+    if (a.nf_magic) {
+        clip = __umulhi(q4, a.nf_magic) >> a.nf_shift;
+        t = q4 - clip * a.n_frames + fl;
+        const bool wrap = t >= a.n_frames;
+        t -= wrap ? a.n_frames : 0u;
+        clip += wrap ? 1u : 0u;
+    } else {
+        const unsigned gf = q4 + fl;
+        clip = gf / a.n_frames;
+        t = gf - clip * a.n_frames;
+    }
+    const float *xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
+    const int s0 = static_cast<int>(t * a.step) - s.lead;  // (t * step < n_samples < 2^31; the frame ends inside the chunk)
+    if (__all(s0 >= 0)) {
+        const float2 *src = reinterpret_cast<const float2 *>(xc + s0);
+#pragma unroll
+        for (int e = 0; e < NE; ++e) vin[e] = src[j + 16 * e];
+    } else {
+        const float *sr = s.state + static_cast<unsigned long long>(clip) * s.state_len + s.state_len;  // sample p < 0 is sr[p]
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int p = s0 + 2 * (j + 16 * e);
+            vin[e] = *reinterpret_cast<const float2 *>((p < 0 ? sr : xc) + p);
+        }
+    }
+    return t;
+}
+
 // Contract framing only: where this lane's frame of `quad` starts (frame t of its clip begins at sample t * step), and t.
 // `quad` is uniform: the clip / frame split of the quad's first frame, the clip's address and the frame's offset in it are scalar
 // work, and what a lane adds is a 32-bit byte offset (its frame within the quad, its sample pair, one conditional step into the
@@ -351,10 +392,16 @@ __device__ __forceinline__ float mel_slot_loop(const float4 *w4, const float *p,
 // MULTI builds (ss_mfcc_batches_device): the launch's quad range is the concatenation of up to kMaxLaunchBatches independent batches'
 // quad ranges, each batch with its own input and output block (BatchTable, ss_device.h; Seg / seg_of, ss_wave.h).
 // VAR builds (ss_mfcc_packed_device): the second argument is a VarlenArgs; the quad range covers the packed output rows (var_src).
+// STRM builds (ss_mfcc_stream_device): a trailing FrameStreamArgs (SP; an empty pack leaves the other builds' argument block and
+// code as they were); clips are streams, frames the rows of this call (load_quad_stream), and the DCT's [0,0] special case of a
+// clip's first frame is never taken (a stream has no first frame).
 template <int NE, bool EXACT, bool POW2, int WAVES, bool BANK421, int NQ, int RES = 0, int OUTK = 0, int FRONT = 0, bool FULLP = false,
-          bool CENTER = false, bool MULTI = false, bool VAR = false>
-__global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_in, const std::conditional_t<VAR, VarlenArgs, MultiArg<MULTI>> mt)
+          bool CENTER = false, bool MULTI = false, bool VAR = false, typename... SP>
+__global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_in, const std::conditional_t<VAR, VarlenArgs, MultiArg<MULTI>> mt,
+                                                           const SP... sp)
 {
+    constexpr bool STRM = (std::is_same_v<SP, FrameStreamArgs> || ...);
+    [[maybe_unused]] const FrameStreamArgs *fs = pack_arg<FrameStreamArgs>(sp...);
     // Everything in front of a wave's first sample loads is start-up latency of the launch (nothing can be computed before
     // the samples are here), so the kernel arguments that lead to those loads are fetched by ONE batch of scalar loads at the
     // very top (pinned: left alone, the compiler fetches them where they are first used -- three dependent scalar-memory
@@ -438,6 +485,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         const char *p = var_src(a, mt, min(quad, q_hi - 1), total, f, cursor, t_next, vnext);
 #pragma unroll
         for (int e = 0; e < NE; ++e) vin[e] = *reinterpret_cast<const float2 *>(p + 8 * (j + 16 * e));
+    } else if constexpr (STRM) {
+        t_next = load_quad_stream<NE>(a, *fs, min(quad, q_hi - 1), total, f, j, vin);
     } else if constexpr (MULTI) {
         an = a;
         ns = seg_of(mt.m, min(quad, q_hi - 1));
@@ -604,9 +653,11 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         // SPREAD: the ten sample loads of the next quad go out one per twiddle step instead of as a burst (a wave issues in
         // order: behind a burst of vector-memory instructions its own VALU work waits); no branch surrounds them -- the last
         // iteration of a wave fetches the block's last quad again and drops it
-        constexpr bool SPREAD = PREFETCH && EXACT && !PRE && !CENTER && !(SS_ABLATE & 16);
+        constexpr bool SPREAD = PREFETCH && EXACT && !PRE && !CENTER && !STRM && !(SS_ABLATE & 16);
         static_assert(!MULTI || (SPREAD && OUTK == 0), "the multi-batch build exists for the spread-prefetch MFCC builds");
         static_assert(!VAR || (SPREAD && OUTK == 0 && !MULTI), "the varlen build exists for the spread-prefetch MFCC builds");
+        static_assert(!STRM || (EXACT && !PRE && !CENTER && !MULTI && !VAR && OUTK != 2 && (FRONT & 1) == 0),
+                      "the streaming builds exist for the default frame shape's MFCC / mfe without window or pre-emphasis");
         QuadSrc nsrc{nullptr, 0u};
         if constexpr (VAR) {
             nsrc.base = var_src(a, mt, min(next, q_hi - 1), total, f, cursor, t_next, vnext) + 8 * j;
@@ -620,7 +671,12 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         } else {
             if (SPREAD) nsrc = quad_src(a, min(next, q_hi - 1), total, f, j, t_next);
         }
-        if (!SPREAD && PREFETCH && next < q_hi && !(SS_ABLATE & 16)) t_next = load_quad<NE, EXACT, PRE, CENTER>(a, next, total, f, j, vin, pin);
+        if constexpr (STRM) {
+            // (the whole quad's loads as one burst behind pass 1: the edge branch's address selects do not split into the twiddle steps)
+            if (next < q_hi) t_next = load_quad_stream<NE>(a, *fs, next, total, f, j, vin);
+        } else if (!SPREAD && PREFETCH && next < q_hi && !(SS_ABLATE & 16)) {
+            t_next = load_quad<NE, EXACT, PRE, CENTER>(a, next, total, f, j, vin, pin);
+        }
         float2 u[16];
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
@@ -881,7 +937,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             if (a.dc_elimination) {
                 const float le = ln_scaled(energy);
                 o = j == 0 ? le : o;
-            } else if (t_cur == 0 && j == 0) {
+            } else if (!STRM && t_cur == 0 && j == 0) {
                 o = acc * (VAR ? vcur.s00 : a.dct_scale_00);
             }
             // unconditional, counted store (ss_wave.h): the descriptor covers the quad's valid frames, lanes j >= n_ceps are
@@ -1152,6 +1208,55 @@ hipError_t launch_mfcc_c256_varlen(const Fast512Args &a_in, const VarlenArgs &v,
     if (info) *info = LaunchInfo{"ss_mfcc_c256v<10,exact,bank421,sym>", grid, static_cast<unsigned>(WAVES * 64), lds};
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, v);
     return hipGetLastError();
+}
+
+hipError_t launch_mfcc_c256_stream(const Fast512Args &a_in, const FrameStreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    constexpr int WAVES = 12;
+    Fast512Args a = a_in;
+    // the headline shape only: 320-sample frames, the default bank (4 / 2 / 1 taps), no window, no pre-emphasis, contract / padded
+    // framing (both stream alike); MFCC with 40 filters in the paired tight-tap layout, or mfe.  Even hops keep sample pairs whole.
+    const bool b421 = a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1;
+    const bool mfcc = a.out_mfe == 0 && a.n_filters == 40 && a.paired == 2;
+    const bool mfe = a.out_mfe == 1 && a.n_filters <= 40;
+    if (a.fullp || a.center || a.win_floats > 0 || a.preemph != 0.0f || a.flen != 320 || a.spectrum_exponent == 2 || !b421 || !(mfcc || mfe) ||
+        (a.step & 1u) || a.step > a.flen || s.lead != static_cast<int>(a.flen - a.step) || s.state_len < static_cast<unsigned>(s.lead) ||
+        (s.state_len > 0 && !s.state))
+        return hipErrorInvalidValue;
+    const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
+    if (total + 4 >= (1ull << 31)) return hipErrorInvalidValue;
+    a.nf_magic = a.nf_shift = 0;
+    if (a.n_frames >= 4) {  // the reciprocal of launch_w (its one-wrap lane fix-up needs n_frames >= 4)
+        const unsigned long long d = a.n_frames;
+        unsigned l = 0;
+        while ((1ull << l) < d) ++l;
+        const unsigned __int128 num = static_cast<unsigned __int128>(1) << (31 + l);
+        a.nf_magic = static_cast<uint32_t>((num + d - 1) / d);
+        a.nf_shift = l - 1;
+    }
+    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * a.mel_wpitch) * sizeof(float) + 16;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (total == 0) return hipSuccess;
+    const unsigned long long quads = (total + 3) / 4;
+    unsigned long long blocks = (quads + WAVES - 1) / WAVES;
+    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
+    if (blocks > cap) blocks = cap;
+    const unsigned grid = static_cast<unsigned>(blocks);
+    a.q_base = static_cast<uint32_t>(quads / grid);
+    a.q_rem = static_cast<uint32_t>(quads % grid);
+    auto go = [&](auto kern, const char *name) {
+        if (lds > 48 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     static_cast<int>(lds));
+            if (e != hipSuccess) return e;
+        }
+        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{}, s);
+        return hipGetLastError();
+    };
+    // the one-shot builds' template arguments (RES 30 / 2) with STRM: the same arithmetic per frame, bit for bit
+    if (mfcc) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, false, FrameStreamArgs>, "ss_mfcc_c256s<10,exact,bank421,sym>");
+    return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, FrameStreamArgs>, "ss_mfcc_c256s<10,exact,bank421,mfe>");
 }
 
 bool mfcc_c256_has_mfe(const Fast512Args &a)

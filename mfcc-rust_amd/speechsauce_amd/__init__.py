@@ -23,7 +23,7 @@ from ._lib import SpeechSauceError, SsParams, make_params  # noqa: F401
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
            "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "MelSpectrogramStream", "StftStream",
-           "SpeechConfig", "SpeechSauceError"]
+           "MfccStream", "MfeStream", "SpeechConfig", "SpeechSauceError"]
 
 
 def _is_torch(x) -> bool:
@@ -694,6 +694,116 @@ class StftStream(_StreamBase):
         out = np.empty((self.n_streams, R, F, 2), dtype=np.float32)
         self._launch(sig, n, config, out, "ss_stft_stream_device", "ss_stft_stream")
         return out.view(np.complex64)[..., 0]
+
+
+# ---- streaming MFCC / mfe with carried frame state (feature.rs:99-233 over live audio) --------------------------------------
+
+class _FrameStreamBase(_StreamBase):
+    """Chunks of whole hops of ``n_streams`` live audio streams in, one MFCC / mfe row per hop out, with the last
+    ``max(frame_len + preemph_shift - hop, 0)`` samples of every stream carried from call to call (continuous mode only: the
+    reference's ``mfcc`` / ``mfe`` keep no state).  The state handling and chunk checks are ``_StreamBase``'s.  See
+    ``ss_mfcc_stream`` in ``include/speechsauce_amd.h``."""
+
+    def __init__(self, n_streams, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
+                 low_frequency, high_frequency, dc_elimination, switches):
+        if int(n_streams) < 1:
+            raise ValueError(f"{self._what}: n_streams must be at least 1")
+        self.n_streams = int(n_streams)
+        self.mode = "continuous"
+        self._args = (sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length, low_frequency,
+                      high_frequency, dc_elimination, dict(switches))
+        self._params = make_params(sample_rate=sampling_frequency, fft_points=fft_length, frame_length=frame_length,
+                                   frame_stride=frame_stride, num_cepstral=num_cepstral, num_filters=num_filters,
+                                   low_frequency=low_frequency, high_frequency=high_frequency, dc_elimination=dc_elimination,
+                                   **switches)
+        lib = _lib.lib()
+        S, fl, st = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _lib.check(lib.ss_frame_stream_state_len(C.byref(self._params), C.byref(S)))  # literal / centred framing: SS_ERR_BAD_CONFIG
+        _lib.check(lib.ss_frame_sizes(C.byref(self._params), C.byref(fl), C.byref(st)))
+        self.state_len = S.value
+        self.frame_len = fl.value
+        self.hop = st.value
+        self._state = None
+        self._where = None
+
+    def _rows(self, n):
+        r = C.c_size_t()
+        _lib.check(_lib.lib().ss_frame_stream_rows(C.byref(self._params), n, C.byref(r)))
+        return r.value
+
+    def _call(self, sig, n, config, outs, dev_fn, host_fn, extra):
+        lib = _lib.lib()
+        B = self.n_streams
+        ptrs = [o.data_ptr() if _is_torch(o) else o.ctypes.data for o in outs]
+        if _is_torch(sig):
+            import torch
+
+            x = sig if sig.stride(1) == 1 else sig.contiguous()
+            with torch.cuda.device(x.device):
+                st = self._state.data_ptr() if self.state_len else None
+                _lib.check(getattr(lib, dev_fn)(config.handle, x.data_ptr(), B, n, x.stride(0) if B > 1 else n, *extra, st, *ptrs,
+                                                _stream_ptr()))
+        else:
+            x = np.ascontiguousarray(sig)
+            st = self._state.ctypes.data if self.state_len else None
+            _lib.check(getattr(lib, host_fn)(config.handle, x.ctypes.data, B, n, n, *extra, st, *ptrs))
+
+
+class MfccStream(_FrameStreamBase):
+    """Streaming ``mfcc``: ``__call__(chunk [n_streams, n])`` -> ``[n_streams, n // hop, num_cepstral]``, one row per hop.
+    ``norm_frames``: the frame count T of the reference DCT scaling n = T * num_filters (feature.rs:126-131), typically the
+    frame count of the model's input window; required under the reference DCT, ignored with ``dct_norm="ortho"``."""
+
+    _what = "MfccStream"
+
+    def __init__(self, n_streams, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
+                 fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, norm_frames=None, **switches):
+        super().__init__(n_streams, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
+                         low_frequency, high_frequency, dc_elimination, switches)
+        if self._params.dct_norm == 0:  # SS_DCT_REFERENCE
+            if norm_frames is None or int(norm_frames) < 1:
+                raise ValueError("MfccStream: the reference DCT scaling needs norm_frames >= 1 (the frame count it scales by)")
+            self.norm_frames = int(norm_frames)
+        else:
+            self.norm_frames = int(norm_frames) if norm_frames is not None else 1
+
+    def __call__(self, chunk):
+        sig, n, R, config = self._prepare(chunk)
+        Cc = config.params.num_cepstral
+        if _is_torch(sig):
+            import torch
+
+            out = torch.empty((self.n_streams, R, Cc), dtype=torch.float32, device=sig.device)
+        else:
+            out = np.empty((self.n_streams, R, Cc), dtype=np.float32)
+        self._call(sig, n, config, [out], "ss_mfcc_stream_device", "ss_mfcc_stream", [self.norm_frames])
+        return out
+
+
+class MfeStream(_FrameStreamBase):
+    """Streaming ``mfe``: ``__call__(chunk [n_streams, n])`` -> ``(feat [n_streams, n // hop, num_filters], energy [n_streams,
+    n // hop])``, one row per hop."""
+
+    _what = "MfeStream"
+
+    def __init__(self, n_streams, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_filters=40, fft_length=512,
+                 low_frequency=0, high_frequency=None, **switches):
+        super().__init__(n_streams, sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
+                         low_frequency, high_frequency, True, switches)
+
+    def __call__(self, chunk):
+        sig, n, R, config = self._prepare(chunk)
+        M = config.params.num_filters
+        if _is_torch(sig):
+            import torch
+
+            feat = torch.empty((self.n_streams, R, M), dtype=torch.float32, device=sig.device)
+            energy = torch.empty((self.n_streams, R), dtype=torch.float32, device=sig.device)
+        else:
+            feat = np.empty((self.n_streams, R, M), dtype=np.float32)
+            energy = np.empty((self.n_streams, R), dtype=np.float32)
+        self._call(sig, n, config, [feat, energy], "ss_mfe_stream_device", "ss_mfe_stream", [])
+        return feat, energy
 
 
 def stack_frames(signal, sampling_frequency, frame_length=0.020, frame_stride=0.020, filter=None, zero_padding=False, **switches):
