@@ -252,6 +252,36 @@ int ss_mfcc_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips
 int ss_mfe_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
                          const int64_t *d_frame_offsets, size_t total_frames, float *d_feat, float *d_energy, void *stream);
 
+/* ---- packed variable-length clips, STFT path (a loop over speechsauce::feature::mel_spectrogram / functions::stft2 per clip) ----
+ * Sample offsets as above (so[0] = 0, non-decreasing, n_clips + 1 entries).  Clip b has R_b = ceil(n_b / hop) rows (f32, as
+ * ss_stft_rows computes them); ro = row_offsets, ro[b+1] - ro[b] = R_b.  mel: clip b's block [num_filters x R_b] (the (n_mels, time)
+ * layout of ss_mel_spectrogram) is contiguous and starts at out + num_filters * ro[b].  stft: [ro[n_clips] x (fft_points/2+1) x 2]
+ * interleaved re / im, clip b owns rows ro[b] .. ro[b+1].  Per clip, every result is what ss_mel_spectrogram / ss_stft returns for
+ * that clip alone: zero initial state, the zero padding of a partial last hop, its last n_pad rows exact zeros (functions.rs:121),
+ * every switch and bank of the config.  n_clips == 0 is SS_OK with nothing launched; a config without an STFT path
+ * (fft_points < 2 * hop, functions.rs:136) is SS_ERR_BAD_CONFIG.
+ * Every call is ONE launch.  mel output of the 2048-point shape with a bank within bins 0..512 (cfg3: hop 512, 128 mels) runs on the
+ * packed build of the twelve-wave kernel: per clip the same bits as ss_mel_spectrogram_device on that clip where the twelve-wave
+ * build serves it.  Every other configuration (any fft_points, chirp-z included; every bank; a 2048-point bank past bin 512) and all
+ * stft output run on the packed build of the generic kernel: per clip the same bits as the generic kernel's equal-length path.  The
+ * dedicated 512 / 1024 / 4096-point mel kernels and the 2048-point stft build have no packed builds. */
+/* host only, no device needed: ro[0..n_clips] for clips x[so[b] : so[b+1]]; SS_ERR_ARG for decreasing offsets / so[0] != 0 / an
+ * empty clip (named in ss_last_error_string) / a clip of more than 2^31 - 1 samples */
+int ss_packed_row_offsets(const ss_params *p, size_t n_clips, const int64_t *sample_offsets, int64_t *row_offsets);
+/* host pointers (H2D, one device call, D2H); sample_offsets is a host array.  out: num_filters * ro[n_clips] floats (mel) /
+ * ro[n_clips] * (fft_points/2+1) * 2 floats (stft) */
+int ss_mel_spectrogram_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out);
+int ss_stft_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out);
+/* device pointers, asynchronous on `stream`, graph-capturable: d_sample_offsets / d_row_offsets are DEVICE arrays of n_clips + 1
+ * entries (ro from ss_packed_row_offsets, or computed by the caller on the device); total_rows = the rows d_out holds.  The kernel
+ * recomputes every R_b from the sample offsets with the host's bits: a clip whose rows disagree with ro, or that end past
+ * total_rows, is skipped (nothing is written outside d_out) and the config's device error word is raised -- the next call on the
+ * config (or ss_config_device_status) returns SS_ERR_DEVICE. */
+int ss_mel_spectrogram_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                     const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream);
+int ss_stft_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                          const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream);
+
 /* ---- streaming STFT / mel spectrogram with carried state (functions.rs:86-170, config.rs:126,162) ----
  * The reference keeps the last S = fft_points - frame_size samples in SpeechConfig::analysis_mem (config.rs:162) and opens every
  * stft1 / stft2 / mel_spectrogram call with them (frame_analysis, functions.rs:137-160), so audio fed chunk by chunk gives frames

@@ -1342,6 +1342,114 @@ int packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_cli
     return rc;
 }
 
+
+// ---- packed variable-length clips on the STFT path (ss_mel_spectrogram_packed* / ss_stft_packed*) ------------------------------
+// Clip b is d_x[so[b] : so[b+1]], its rows ro[b] .. ro[b+1] of the packed row space; the offset tables are device arrays, read by the
+// kernel only (the launch is graph-capturable).  One launch over every clip's rows; the kernel checks the tables against each other
+// (VarRowsArgs, ss_device.h).
+int launch_packed_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t n_clips, const int64_t *d_so, const int64_t *d_ro,
+                       size_t total_rows, float *out0, hipStream_t stream)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    const ss::HostTables &h = cfg->host;
+    if (!h.d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
+    if (n_clips == 0) return SS_OK;
+    if (!d_x || !d_so || !d_ro || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_clips > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many clips");
+    {
+        const int drc = check_device(cfg);  // see launch_frames
+        if (drc) return drc;
+        const int erc = pending_device_error(cfg);
+        if (erc) return erc;
+    }
+    ss::FrontArgs a{};
+    fill_common(cfg, a);
+    a.x = d_x;
+    a.hop = h.d.hop;
+    a.n_pad = h.d.n_pad;
+    a.window = cfg->d_window_stft;
+    a.scale = h.d.wnorm;
+    a.out_kind = out_kind;
+    a.out0 = out0;
+    ss::VarRowsArgs v{};
+    v.so = reinterpret_cast<const long long *>(d_so);
+    v.ro = reinterpret_cast<const long long *>(d_ro);
+    v.total_rows = total_rows;
+    v.n_clips = static_cast<uint32_t>(n_clips);
+    v.hop = h.d.hop;
+    v.err = cfg->d_err;
+    ss::LaunchInfo info{};
+    // the 2048-point mel shape (bank within bins 0..512): the packed build of the twelve-wave kernel -- per clip the bits of
+    // ss_mel_spectrogram_device's twelve-wave build; hipErrorInvalidValue before the launch for every other configuration
+    if (!ss::dbg_force_generic() && out_kind == ss::OUT_MEL && cfg->mel2048.ok && !cfg->mel2048.fullp) {
+        ss::Mel2048Args m{};
+        m.x = d_x;
+        m.hop = a.hop;
+        m.n_pad = a.n_pad;
+        m.scale = a.scale;
+        m.tab = cfg->d_mel2048_tab;
+        m.fullp = cfg->mel2048.fullp;
+        m.mel_wpitch = cfg->mel2048.wpitch;
+        for (int s = 0; s < 4; ++s) m.mel_q4[s] = cfg->mel2048.q4[s];
+        m.n_filters = a.n_filters;
+        m.out = out0;
+        m.ctl = cfg->d_err;
+        const hipError_t em = ss::launch_mel_c1024_varlen(m, v, stream, cfg->num_cus, &info);
+        if (em == hipSuccess) {
+            g_last_kernel = info.kernel_name;
+            return SS_OK;
+        }
+        if (em != hipErrorInvalidValue) return hip_fail(em, "launch_mel_c1024_varlen");
+    }
+    const hipError_t e = ss::launch_front_generic_varrows(a, v, h.d.log2c, stream, cfg->num_cus, &info);
+    if (e != hipSuccess) return hip_fail(e, "launch_front_generic_varrows");
+    g_last_kernel = info.kernel_name;
+    return SS_OK;
+}
+
+// Host-pointer form: the row offsets from the host's sample offsets, one upload, one launch, one download on the config's first
+// host-pipeline stream (the host calls of a config are serialised by its mutex).
+int packed_stft_host(const ss_config *cfg, int out_kind, const float *x, size_t n_clips, const int64_t *so, float *out0)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (!cfg->host.d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
+    if (n_clips == 0) return SS_OK;
+    if (!x || !so || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    std::vector<int64_t> ro(n_clips + 1);
+    int rc = ss_packed_row_offsets(&cfg->host.params, n_clips, so, ro.data());
+    if (rc) return rc;
+    if ((rc = check_device(cfg))) return rc;
+    const size_t rows = static_cast<size_t>(ro[n_clips]), samples = static_cast<size_t>(so[n_clips]);
+    const size_t cols = out_kind == ss::OUT_MEL ? cfg->host.params.num_filters : 2 * (cfg->host.params.fft_points / 2 + 1);
+    ss_config::HostPipe &hp = cfg->pipe;
+    std::lock_guard<std::mutex> lock(hp.mu);
+    if (!hp.stream[0]) {
+        SS_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
+        SS_HIP(hipEventCreateWithFlags(&hp.done[0], hipEventDisableTiming));
+    }
+    hipStream_t st = hp.stream[0];
+    DeviceBuf dx, dso, dro, d0;
+    if ((rc = dx.alloc(samples * sizeof(float))) || (rc = dso.alloc((n_clips + 1) * sizeof(int64_t))) ||
+        (rc = dro.alloc((n_clips + 1) * sizeof(int64_t))) || (rc = d0.alloc(rows * cols * sizeof(float))))
+        return rc;
+    hipError_t e = hipMemcpyAsync(dx.p, x, samples * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dro.p, ro.data(), (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
+    if (rc == SS_OK)
+        rc = launch_packed_stft(cfg, out_kind, dx.as<const float>(), n_clips, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
+                                d0.as<float>(), st);
+    if (rc == SS_OK) {
+        e = hipMemcpyAsync(out0, d0.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (D2H)");
+    }
+    // the copies may still touch the caller's buffers and ours: synchronise whatever happened
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "packed host call");
+    if (rc == SS_OK) rc = pending_device_error(cfg);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1568,6 +1676,30 @@ int ss_mfcc_packed(const ss_config *cfg, const float *x, size_t n_clips, const i
 int ss_mfe_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *feat, float *energy)
 {
     return packed_host(cfg, ss::OUT_MFE, x, n_clips, sample_offsets, feat, energy);
+}
+
+int ss_mel_spectrogram_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                     const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream)
+{
+    return launch_packed_stft(cfg, ss::OUT_MEL, d_x, n_clips, d_sample_offsets, d_row_offsets, total_rows, d_out,
+                              static_cast<hipStream_t>(stream));
+}
+
+int ss_stft_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                          const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream)
+{
+    return launch_packed_stft(cfg, ss::OUT_STFT, d_x, n_clips, d_sample_offsets, d_row_offsets, total_rows, d_out,
+                              static_cast<hipStream_t>(stream));
+}
+
+int ss_mel_spectrogram_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out)
+{
+    return packed_stft_host(cfg, ss::OUT_MEL, x, n_clips, sample_offsets, out);
+}
+
+int ss_stft_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out)
+{
+    return packed_stft_host(cfg, ss::OUT_STFT, x, n_clips, sample_offsets, out);
 }
 
 // lmfe (feature.rs:242-245): ln of mfe's zero-handled filterbank energies.  The frame energies mfe also returns are

@@ -181,6 +181,69 @@ __device__ __forceinline__ void varlen_check_clips(const VarlenArgs &v, uint32_t
 hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
                                        LaunchInfo *info);
 
+// Packed variable-length clips on the STFT path (ss_mel_spectrogram_packed_device / ss_stft_packed_device): clip b is
+// x[so[b] : so[b+1]], its R_b = ceil(n_b / hop) rows are rows ro[b] .. ro[b+1] of the packed row space -- mel: clip b's [M x R_b]
+// block starts at out + M ro[b]; stft: rows ro[b] .. ro[b+1] of [total_rows x F].  As with VarlenArgs, the kernels recompute every
+// R_b from `so` (the host's ss::stft_rows in f32, bit for bit) and skip -- and report through `err` -- a clip whose rows disagree
+// with it or end past total_rows.
+struct VarRowsArgs {
+    const long long *so;  // [n_clips + 1] sample offsets
+    const long long *ro;  // [n_clips + 1] row offsets
+    unsigned long long total_rows;  // rows of the output block
+    uint32_t n_clips;
+    uint32_t hop;
+    unsigned *err;        // the config's device error word (set to kVarlenError on a bad clip)
+};
+// Rows of a clip of L samples, as ss::stft_rows computes them on the host (functions.rs:97 in f32).  0: an empty clip (the host
+// rejects it) or one longer than 2^31 - 1 samples.
+__device__ __forceinline__ unsigned varrows_rows(uint32_t hop, long long L)
+{
+    if (L <= 0 || L > 0x7fffffffll) return 0u;
+    return static_cast<unsigned>(ceilf(__fdiv_rn(__uint2float_rn(static_cast<unsigned>(L)), __uint2float_rn(hop))));
+}
+// Clip b of a packed STFT-path launch: its first sample, its length, its rows and its first packed row.  ok: the offsets agree
+// with each other (rows ro[b] .. ro[b+1] are exactly the R_b rows `so` implies, inside the output block).
+struct VarRowClip {
+    long long s0, r0;
+    unsigned n, R;
+    bool ok;
+};
+__device__ __forceinline__ VarRowClip varrows_clip(const VarRowsArgs &v, unsigned b)
+{
+    VarRowClip c;
+    c.s0 = v.so[b];
+    c.r0 = v.ro[b];
+    const long long s1 = v.so[b + 1], r1 = v.ro[b + 1];
+    c.R = varrows_rows(v.hop, s1 - c.s0);
+    c.n = static_cast<unsigned>(s1 - c.s0);
+    c.ok = c.R > 0u && c.s0 >= 0 && c.r0 >= 0 && r1 - c.r0 == static_cast<long long>(c.R) &&
+           static_cast<unsigned long long>(r1) <= v.total_rows;
+    return c;
+}
+// The clip that owns packed row g: the last b < n_clips with ro[b] <= g (binary search; see varlen_find)
+__device__ __forceinline__ unsigned varrows_find(const VarRowsArgs &v, unsigned long long g)
+{
+    unsigned lo = 0u, hi = v.n_clips;
+    const long long gs = static_cast<long long>(g);
+    while (hi - lo > 1u) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (v.ro[mid] <= gs) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// One pass over the clips, spread over the grid (see varlen_check_clips).  A vector store to the pinned word.
+__device__ __forceinline__ void varrows_check_clips(const VarRowsArgs &v, unsigned tid, unsigned nthreads)
+{
+    bool bad = false;
+    for (unsigned b = tid; b < v.n_clips; b += nthreads) bad |= !varrows_clip(v, b).ok;
+    if (bad && v.err) __hip_atomic_store(v.err, kVarlenError, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// mel output at any fft_points (chirp-z included) and every stft output: the packed-rows build of ss_front_generic's STFT / mel path.
+// a: as for launch_front_generic's STFT path with x = the packed samples; batch / n_samples / rows / real_rows are unused.
+hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
+                                        LaunchInfo *info);
+
 // Streaming STFT (ss_stft_stream_device / ss_mel_spectrogram_stream_device): every stream (a row of the batch) carries the last
 // S = fft_points - hop samples it was fed (config.rs:162, functions.rs:137-160).  A window that reaches before the chunk reads them:
 // sample p < 0 of stream s is state[s * S + S + p] (p >= -S always holds: a row's window ends at least one hop into the chunk).
@@ -340,6 +403,10 @@ hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cu
 // the streaming builds (mel output; StreamArgs above), chosen between eight and twelve waves by launch_mel_c1024's rule;
 // hipErrorInvalidValue before the launch for stft output or a shape that does not fit
 hipError_t launch_mel_c1024_stream(const Mel2048Args &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info);
+// packed variable-length clips (VarRowsArgs above) on the twelve-wave mel build, whatever the unit count (a clip's bits must not
+// depend on the clips beside it); a: x / out = the packed blocks, batch / n_samples / rows / real_rows unused.  hipErrorInvalidValue
+// before the launch for stft output, a bank that reaches past (F+1)/2 (fullp) or a shape that does not fit
+hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
 // several blocks of channels in one launch of the twelve-wave mel build (a: one block's arguments; x / out / batch are ignored);
 // hipErrorInvalidValue before the launch where the shape has no batch-table build
 hipError_t launch_mel_c1024_multi(const Mel2048Args &a, int n_batches, const float *const *d_x, float *const *d_out, const size_t *channels,

@@ -1311,6 +1311,28 @@ int ss_packed_frame_offsets(const ss_params *p, size_t n_clips, const int64_t *s
     return SS_OK;
 }
 
+int ss_packed_row_offsets(const ss_params *p, size_t n_clips, const int64_t *sample_offsets, int64_t *row_offsets)
+{
+    if (!p || !sample_offsets || !row_offsets) return ss::fail(SS_ERR_ARG, "null argument");
+    int rc = ss::validate(*p);
+    if (rc) return rc;
+    size_t R = 0, Rreal = 0;
+    if ((rc = ss::stft_rows(*p, 1, R, Rreal))) return rc;  // SS_ERR_BAD_CONFIG: no STFT path (functions.rs:136)
+    if (sample_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "sample_offsets[0] must be 0");
+    int64_t rows = 0;
+    row_offsets[0] = 0;
+    for (size_t b = 0; b < n_clips; ++b) {
+        const int64_t len = sample_offsets[b + 1] - sample_offsets[b];
+        if (len < 0) return ss::fail(SS_ERR_ARG, "sample_offsets decrease at clip " + std::to_string(b));
+        if (len == 0) return ss::fail(SS_ERR_ARG, "clip " + std::to_string(b) + " is empty");
+        if (len > 0x7fffffff) return ss::fail(SS_ERR_ARG, "clip " + std::to_string(b) + " is longer than 2^31 - 1 samples");
+        if ((rc = ss::stft_rows(*p, static_cast<size_t>(len), R, Rreal))) return rc;
+        rows += static_cast<int64_t>(R);
+        row_offsets[b + 1] = rows;
+    }
+    return SS_OK;
+}
+
 int ss_stft_sizes(const ss_params *p, size_t *hop, size_t *n_pad, float *wnorm)
 {
     if (!p || !hop || !n_pad || !wnorm) return ss::fail(SS_ERR_ARG, "null argument");

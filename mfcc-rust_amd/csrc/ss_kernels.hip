@@ -8,6 +8,8 @@
 // per stream (StreamArgs, ss_device.h); ss_stream_advance moves the state on behind it.
 // ss_front_generic<LOG2C, BLU, FrameStreamArgs> (reported as ss_front_generic_fstream<LOG2C>): the MFCC / mfe path with a carried
 // state per stream (FrameStreamArgs, ss_device.h): frames and pre-emphasis taps before the chunk read the stream's state.
+// ss_front_generic<LOG2C, BLU, VarRowsArgs> (reported as ss_front_generic_varrows<LOG2C>): the STFT / mel path over packed clips of
+// different lengths (VarRowsArgs, ss_device.h), handed out in tiles of packed rows.
 //
 //   * A real frame of N = 2C samples is packed as C complex points z[n] = x[2n] + i x[2n+1]
 //     and transformed by a Stockham autosort FFT whose butterflies live in registers: every
@@ -240,14 +242,18 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
 // STREAM: the STFT / mel path of launch_front_generic_stream -- a window sample before the chunk comes from the stream's state.
 // FSTREAM: the MFCC / mfe path of launch_front_generic_frame_stream -- clip = stream, frame = row of this call; row t starts at chunk
 // sample t * step - lead, and a frame sample or pre-emphasis tap before the chunk comes from the stream's state (no circular wrap).
-// (V: empty, one VarlenArgs, one StreamArgs or one FrameStreamArgs -- an empty pack leaves the argument block of the equal-length
-// builds exactly as it was)
+// VARR: the STFT / mel path of launch_front_generic_varrows -- a workgroup visit is a tile of packed rows, every row finds its own
+// clip; the transposed mel flush writes each row into its clip's [M x R_b] block.
+// (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs or one VarRowsArgs -- an empty pack leaves the argument block of the
+// equal-length builds exactly as it was)
 template <int LOG2C, bool BLU, typename... V>
 __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
 {
     constexpr bool VAR = (std::is_same_v<V, VarlenArgs> || ...);
     constexpr bool STREAM = (std::is_same_v<V, StreamArgs> || ...);
     constexpr bool FSTREAM = (std::is_same_v<V, FrameStreamArgs> || ...);
+    constexpr bool VARR = (std::is_same_v<V, VarRowsArgs> || ...);
+    [[maybe_unused]] const VarRowsArgs *ra = pack_arg<VarRowsArgs>(vargs...);
     [[maybe_unused]] const VarlenArgs *va = pack_arg<VarlenArgs>(vargs...);
     [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(vargs...);
     [[maybe_unused]] const FrameStreamArgs *fa = pack_arg<FrameStreamArgs>(vargs...);
@@ -269,7 +275,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     // MEL mode: transposed output tile [M][rows_tile + 1] after all slots
     float *tile = reinterpret_cast<float *>(smem_raw + slot_bytes * G::FPB);
 
-    const bool mel_mode = STREAM || (!VAR && !FSTREAM && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT));
+    const bool mel_mode = STREAM || VARR || (!VAR && !FSTREAM && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT));
     const int F = BLU ? static_cast<int>(a.blu_n / 2 + 1) : G::F;  // bins per row
 
     if (!mel_mode) {
@@ -438,6 +444,84 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
             }
             frame_sync<LOG2C>();  // zbuf / prow / frow / red are private to the frame's slot
         }
+    } else if constexpr (VARR) {
+        // ---------------- STFT / mel-spectrogram path over packed clips: tiles of TILE packed rows -------
+        // (the rows of one tile may belong to several clips: a long clip among short ones is spread over the grid like the rest)
+        varrows_check_clips(*ra, blockIdx.x * kBlock + tid, gridDim.x * kBlock);
+        const int W = BLU ? static_cast<int>(a.blu_n) : G::N;
+        constexpr int TILE = 32;  // rows buffered before a transposed flush
+        // per tile row, behind the mel tile: the output word of its (m = 0, r) element (-1: the row is not written) and its clip's R_b
+        size_t rtab = slot_bytes * G::FPB + (a.out_kind == OUT_MEL ? sizeof(float) * M * (TILE + 1) : 0);
+        rtab = (rtab + 7) & ~static_cast<size_t>(7);
+        long long *t_base = reinterpret_cast<long long *>(smem_raw + rtab);
+        unsigned *t_rows = reinterpret_cast<unsigned *>(t_base + TILE);
+        const unsigned long long total = ra->total_rows;
+        const unsigned long long tiles = (total + TILE - 1) / TILE;
+        for (unsigned long long tg = blockIdx.x; tg < tiles; tg += gridDim.x) {
+            const unsigned long long g0 = tg * TILE;
+            const int rt = static_cast<int>(min(static_cast<unsigned long long>(TILE), total - g0));
+            for (int rp = 0; rp < rt; rp += G::FPB) {
+                const int rl = rp + slot;  // row within the tile
+                const unsigned long long g = g0 + rl;
+                // rows past the last clip (a larger output block) are left alone; rows of an inconsistent clip are skipped
+                const VarRowClip c = varrows_clip(*ra, rl < rt ? varrows_find(*ra, g) : 0u);
+                const long long r = static_cast<long long>(g) - c.r0;  // row within the clip
+                const bool valid = rl < rt && c.ok && r >= 0 && r < static_cast<long long>(c.R);
+                const long long Rreal = c.R > a.n_pad ? static_cast<long long>(c.R - a.n_pad) : 0ll;
+                const bool active = valid && r < Rreal;
+                const float *xc = a.x + (valid ? c.s0 : 0ll);
+                const long long ns = valid ? static_cast<long long>(c.n) : 0ll;
+                // functions.rs:137-151: window over the last W samples ending at chunk r + n_pad of the clip
+                const long long start = (r + a.n_pad + 1) * static_cast<long long>(a.hop) - W;
+                auto wsample = [&](int i) -> float {
+                    const long long idx = start + i;
+                    return active && i < W && idx >= 0 && idx < ns ? xc[idx] * a.window[i] : 0.0f;
+                };
+                float2 v[16];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int n = j + e * G::TPF;
+                    if (BLU) {
+                        const float xv = wsample(n);
+                        const float2 cc = n < W ? a.blu_c[n] : make_float2(0.f, 0.f);
+                        v[e] = make_float2(xv * cc.x, xv * cc.y);
+                    } else {
+                        v[e] = make_float2(wsample(2 * n), wsample(2 * n + 1));
+                    }
+                }
+                frame_fft<LOG2C>(zbuf, j, a.tw_c, v);
+                float2 *stft_row = nullptr;
+                if (a.out_kind == OUT_STFT && valid) stft_row = reinterpret_cast<float2 *>(a.out0) + g * F;
+                if (BLU) {
+                    blu_convolve<LOG2C>(zbuf, j, a, v);
+                    blu_row<LOG2C>(zbuf, prow, stft_row, j, a, true, active, F);
+                } else {
+                    untangle_row<LOG2C>(zbuf, prow, stft_row, j, a, true, active);
+                }
+                frame_sync<LOG2C>();  // prow is private to the frame; the shared tile has its own barriers below
+                if (a.out_kind == OUT_MEL && rl < rt) {
+                    // feature.rs:173: out[m, r] = sum_f P[r, f] fb[m, f]; rows >= real_rows stay zero
+                    for (int m = j; m < M; m += G::TPF) tile[m * (TILE + 1) + rl] = active ? mel_dot(prow, a, m) : 0.0f;
+                    if (j == 0) {
+                        t_base[rl] = valid ? c.r0 * M + r : -1ll;
+                        t_rows[rl] = c.R;
+                    }
+                }
+                if (a.out_kind == OUT_STFT && valid && !active) {
+                    for (int k = j; k < F; k += G::TPF) stft_row[k] = make_float2(0.0f, 0.0f);
+                }
+                __syncthreads();
+            }
+            if (a.out_kind == OUT_MEL) {
+                // clip b's block [M x R_b] starts at out + M ro[b]: element (m, r) is word M ro[b] + m R_b + r
+                for (int i = tid; i < M * rt; i += kBlock) {
+                    const int m = i / rt, rl = i - m * rt;
+                    const long long b0 = t_base[rl];
+                    if (b0 >= 0) a.out0[b0 + static_cast<long long>(m) * t_rows[rl]] = tile[m * (TILE + 1) + rl];
+                }
+                __syncthreads();
+            }
+        }
     } else if constexpr (!VAR) {
         // ---------------- STFT / mel-spectrogram path: one clip (channel) per workgroup visit -------
         const int R = static_cast<int>(a.rows);
@@ -562,6 +646,28 @@ hipError_t launch_one_varlen(const FrontArgs &a, const VarlenArgs &v, hipStream_
     const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
     if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
     hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, VarlenArgs>), dim3(grid), dim3(kBlock), lds, stream, a, v);
+    return hipGetLastError();
+}
+
+template <int LOG2C, bool BLU>
+hipError_t launch_one_varrows(const FrontArgs &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info,
+                              const char *name)
+{
+    // the equal-length carve plus the tile's row table (32 offsets + 32 row counts, 8-byte aligned)
+    const size_t lds = front_lds_bytes<LOG2C>(a) + 32 * (sizeof(long long) + sizeof(unsigned)) + 16;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, VarRowsArgs>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    // at least one workgroup: the clip pass runs even where the output block has no rows
+    unsigned long long work = (v.total_rows + 31) / 32;
+    if (work == 0) work = 1;
+    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
+    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
+    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
+    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, VarRowsArgs>), dim3(grid), dim3(kBlock), lds, stream, a, v);
     return hipGetLastError();
 }
 
@@ -726,6 +832,38 @@ hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, 
         case 10: return launch_one_varlen<10, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<10>");
         case 11: return launch_one_varlen<11, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<11>");
         case 12: return launch_one_varlen<12, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<12>");
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
+                                        LaunchInfo *info)
+{
+    if (a.out_kind != OUT_MEL && a.out_kind != OUT_STFT) return hipErrorInvalidValue;
+    if (a.blu_n) {
+        switch (log2c) {
+            case 4: return launch_one_varrows<4, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<4,chirpz>");
+            case 5: return launch_one_varrows<5, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<5,chirpz>");
+            case 6: return launch_one_varrows<6, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<6,chirpz>");
+            case 7: return launch_one_varrows<7, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<7,chirpz>");
+            case 8: return launch_one_varrows<8, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<8,chirpz>");
+            case 9: return launch_one_varrows<9, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<9,chirpz>");
+            case 10: return launch_one_varrows<10, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<10,chirpz>");
+            case 11: return launch_one_varrows<11, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<11,chirpz>");
+            case 12: return launch_one_varrows<12, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<12,chirpz>");
+            default: return hipErrorInvalidValue;
+        }
+    }
+    switch (log2c) {
+        case 4: return launch_one_varrows<4, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<4>");
+        case 5: return launch_one_varrows<5, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<5>");
+        case 6: return launch_one_varrows<6, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<6>");
+        case 7: return launch_one_varrows<7, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<7>");
+        case 8: return launch_one_varrows<8, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<8>");
+        case 9: return launch_one_varrows<9, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<9>");
+        case 10: return launch_one_varrows<10, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<10>");
+        case 11: return launch_one_varrows<11, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<11>");
+        case 12: return launch_one_varrows<12, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<12>");
         default: return hipErrorInvalidValue;
     }
 }

@@ -25,6 +25,9 @@
 // Streaming builds (a StreamArgs in the trailing argument pack, launch_mel_c1024_stream, reported as ss_mel_c1024s<...>): the
 // samples a window takes from before the chunk come from the stream's carried state instead of zero (functions.rs:137-160); only
 // the edge branch of the loader differs.
+// Packed builds of the twelve-wave kernel (a VarRowsArgs in the trailing argument pack, launch_mel_c1024_varlen, reported as
+// ss_mel_c1024v<...>): units are row pairs of the packed row space, every half-wave finds its own clip (a pair may straddle two:
+// the two rows of a wave are computed independently -- own registers, own exchange region, own P row, partners within the half).
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 #include "ss_internal.h"
@@ -351,13 +354,18 @@ __global__ __launch_bounds__(kWavesM * 64) void ss_mel_c1024(const Mel2048Args a
 // fit beside them: the rows leave as 8-byte pieces of lines (HBM writes 1.4x the output, traffic 1.09x the algorithmic bytes).
 // MULTI (ss_mel_spectrogram_batches_device): the launch's units are the concatenation of up to kMaxLaunchBatches blocks' row
 // pairs, each block with its own input and output (BatchTable, ss_device.h; Seg / seg_of, ss_wave.h).
+// VARR (ss_mel_spectrogram_packed_device): the units are the row pairs of the packed row space (VarRowsArgs); a per-wave cursor over
+// the row offsets finds the clip of the unit's first row, a half-wave's row lies at most one clip further (every clip has a row).
 template <bool FIXMEL, bool STFT = false, bool MULTI = false, typename... SA>
 __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args a, const MultiArg<MULTI> mt, const SA... sargs)
 {
-    constexpr bool STREAM = sizeof...(SA) > 0;
+    constexpr bool STREAM = (std::is_same_v<SA, StreamArgs> || ...);
+    constexpr bool VARR = (std::is_same_v<SA, VarRowsArgs> || ...);
     [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(sargs...);
+    [[maybe_unused]] const VarRowsArgs *ra = pack_arg<VarRowsArgs>(sargs...);
     static_assert(!(MULTI && STFT), "the batch-table build is a mel-output build");
     static_assert(!(MULTI && STREAM), "the streaming build takes one block");
+    static_assert(!VARR || (!STFT && !MULTI && !STREAM), "the packed build is a one-block mel-output build");
     const LifeStamp life = life_begin(a.stamps);  // (diagnostic: null in every ordinary launch)
     constexpr int kWavesM = 12;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -369,6 +377,7 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
     const unsigned pairs = STFT ? (a.rows + 1) / 2 : mel_work_pairs(a.rows, a.real_rows);
     unsigned long long units = static_cast<unsigned long long>(a.batch) * pairs;
     if constexpr (MULTI) units = a.batch;  // (the launcher hands over the launch's unit count: the sum over the blocks)
+    if constexpr (VARR) units = (ra->total_rows + 1) / 2;  // (the launcher keeps it below 2^30)
     // Work distribution: the workgroup owns a contiguous range of units (neighbouring units share three quarters of their samples:
     // L1 / L2 locality), its waves pull them from an LDS counter.
     const unsigned u_lo = static_cast<unsigned>(units * blockIdx.x / gridDim.x);
@@ -394,6 +403,7 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
 #define SS_P3(k) do { } while (0)
 #endif
     unsigned item = u_lo + wave;
+    [[maybe_unused]] unsigned cursor = 0;  // VARR: the clip of the wave's last unit's first row (a wave's claims only increase)
     Seg cs{};  // MULTI: the block of the current unit
     if constexpr (MULTI) cs = seg_of(mt.m, min(static_cast<unsigned>(__builtin_amdgcn_readfirstlane(item)), u_hi - 1));
     SS_PRIOL(SS_P_TOP);
@@ -421,13 +431,59 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
         const float4 *s_tw2 = reinterpret_cast<const float4 *>(s_tab + L::kTw2 + j * L::kTw2Pitch);
         const float4 *s_twn4 = reinterpret_cast<const float4 *>(s_tab + L::kTwn + j * L::kTwnPitch);
         const float4 *s_win4 = reinterpret_cast<const float4 *>(s_tab + L::kWin + j * L::kWinPitch);
-        const unsigned clip = unit / pairs;
-        const int r = static_cast<int>(unit - clip * pairs) * 2 + half;
-        const bool in_rows = r < R;
+        const unsigned clip = VARR ? 0u : unit / pairs;
+        const int r = VARR ? 0 : static_cast<int>(unit - clip * pairs) * 2 + half;
+        [[maybe_unused]] VarRowClip vc{};     // VARR: this half-wave's clip ...
+        [[maybe_unused]] long long vr = 0;    // ... its row in that clip
+        [[maybe_unused]] bool vvalid = false;  // ... and whether the row is one of the clip's (consistent offsets) and is written
+        [[maybe_unused]] bool vsame = false;   // ... and whether it is in the clip of the unit's first row
+        if constexpr (VARR) {
+            const long long g0 = 2ll * unit;
+            unsigned c = cursor;
+            for (int k = 0; k < 4 && c + 1 < ra->n_clips && ra->ro[c + 1] <= g0; ++k) ++c;
+            if (c + 1 < ra->n_clips && ra->ro[c + 1] <= g0) c = varrows_find(*ra, static_cast<unsigned long long>(g0));
+            cursor = c;
+            const long long g = g0 + half;
+            vsame = !(c + 1 < ra->n_clips && ra->ro[c + 1] <= g);
+            if (!vsame) ++c;
+            vc = varrows_clip(*ra, c);
+            vr = g - vc.r0;
+            vvalid = static_cast<unsigned long long>(g) < ra->total_rows && vc.ok && vr >= 0 && vr < static_cast<long long>(vc.R);
+        }
+        const bool in_rows = VARR ? vvalid : r < R;
         SS_P3(0);
         // ---- the window of this half-wave's row (functions.rs:137-151: the last W samples ending at chunk r + n_pad) ----
         float2 v[32];
-        {
+        if constexpr (VARR) {
+            // the clip's own edges: zero before its first sample and past its last, 64-bit sample indices (a clip may start past
+            // sample 2^31 of the packed buffer, and at either parity); rows >= real_rows of the clip are inactive (exact zeros)
+            const long long rreal = vc.R > a.n_pad ? static_cast<long long>(vc.R - a.n_pad) : 0ll;
+            const bool active = vvalid && vr < rreal;
+            const long long start = (vr + a.n_pad + 1) * static_cast<long long>(a.hop) - 2048;
+            const long long n = vc.n;
+            const bool inside = active && vsame && start >= 0 && start + 2048 <= n;
+            if (__all(inside)) {
+                // both rows of the pair in one clip, well inside it: the loads of the equal-length build from the uniform base of the
+                // pair's first row (lane 0's row) + this lane's 32-bit byte offset
+                const long long s0 = vc.s0 + start;
+                const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(s0));
+                const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(static_cast<unsigned long long>(s0) >> 32));
+                const char *sb = reinterpret_cast<const char *>(x_b + ((static_cast<unsigned long long>(hi) << 32) | lo));
+                const unsigned so = static_cast<unsigned>(j) * 8u;  // (lane 0 is the pair's first row: half 1 starts a hop later)
+                unsigned so2[2] = {so + static_cast<unsigned>(half) * a.hop * 4u, so + static_cast<unsigned>(half) * a.hop * 4u + 4096u};
+                asm volatile("" : "+v"(so2[1]));
+#pragma unroll
+                for (int e = 0; e < 32; ++e) v[e] = *reinterpret_cast<const float2 *>(sb + so2[e / 16] + 256u * (e % 16));
+            } else {
+                const float *xc = x_b + (vvalid ? vc.s0 : 0ll);
+                const long long base = start + 2 * j;
+#pragma unroll
+                for (int e = 0; e < 32; ++e) {
+                    const long long p0 = base + 64 * e;
+                    v[e] = make_float2(active && p0 >= 0 && p0 < n ? xc[p0] : 0.f, active && p0 + 1 >= 0 && p0 + 1 < n ? xc[p0 + 1] : 0.f);
+                }
+            }
+        } else {
             const float *xc = x_b + static_cast<unsigned long long>(clip) * a.ld;
             const bool active = r < Rreal;
             const int start = static_cast<int>(r + a.n_pad + 1) * static_cast<int>(a.hop) - 2048;
@@ -620,11 +676,21 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
                         off += a.mel_q4[s];
                     }
                 }
-                float *dst = out_b + static_cast<unsigned long long>(clip) * M * R + r;
-                if (in_rows) {
+                if constexpr (VARR) {
+                    // clip b's block [M x R_b] starts at out + M ro[b]
+                    float *dst = out_b + vc.r0 * M + vr;
+                    if (in_rows) {
 #pragma unroll
-                    for (int s = 0; s < 4; ++s)
-                        if (fi[s] >= 0) dst[static_cast<unsigned long long>(fi[s]) * R] = mv[s];
+                        for (int s = 0; s < 4; ++s)
+                            if (fi[s] >= 0) dst[static_cast<long long>(fi[s]) * vc.R] = mv[s];
+                    }
+                } else {
+                    float *dst = out_b + static_cast<unsigned long long>(clip) * M * R + r;
+                    if (in_rows) {
+#pragma unroll
+                        for (int s = 0; s < 4; ++s)
+                            if (fi[s] >= 0) dst[static_cast<unsigned long long>(fi[s]) * R] = mv[s];
+                    }
                 }
             }
             wave_order();
@@ -637,6 +703,8 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
         item = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(next_v));
     }
     life_end(a.stamps, life, blockIdx.x * kWavesM + (threadIdx.x >> 6));
+    // VARR: the consistency pass over every clip (at the end: its loads would otherwise wait in line with the first samples)
+    if constexpr (VARR) varrows_check_clips(*ra, blockIdx.x * (kWavesM * 64) + threadIdx.x, gridDim.x * (kWavesM * 64));
 #if SS_LAB && defined(SS_PROF3)
     if ((threadIdx.x & 63) == 0) p3[0] = p3n | (static_cast<unsigned long long>(__builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20)) << 32);
 #endif
@@ -727,6 +795,19 @@ hipError_t launch_mel_w12_stream(const Mel2048Args &a, const StreamArgs &s, hipS
                  : mel_go(ss_mel_c1024_w12<false, false, false, StreamArgs>, "ss_mel_c1024s<w12>", grid, 12, lds, stream, info, a, none, s);
 }
 
+hipError_t launch_mel_w12_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    const size_t lds = mel_lds_bytes(12, a.mel_wpitch);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    // an empty output block still gets one workgroup: the clip pass runs
+    const unsigned long long units = (v.total_rows + 1) / 2;
+    const unsigned grid = units ? mel_grid(units, 12, num_cus) : 1u;
+    const MultiArg<false> none{};
+    const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
+    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, VarRowsArgs>, "ss_mel_c1024v<w12,mel6321>", grid, 12, lds, stream, info, a, none, v)
+                 : mel_go(ss_mel_c1024_w12<false, false, false, VarRowsArgs>, "ss_mel_c1024v<w12>", grid, 12, lds, stream, info, a, none, v);
+}
+
 }  // namespace
 
 hipError_t launch_mel_c1024_multi(const Mel2048Args &a_in, int n_batches, const float *const *d_x, float *const *d_out, const size_t *channels,
@@ -809,6 +890,14 @@ hipError_t launch_mel_c1024_stream(const Mel2048Args &a, const StreamArgs &s, hi
         if (e != hipErrorInvalidValue) return e;
     }
     return launch_mel_w8_stream(a, s, stream, num_cus, info);
+}
+
+hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    // always twelve waves (never twelve_waves_win): the eight- and twelve-wave builds round a few FMAs differently in the last bit,
+    // and a clip's bits must not depend on which other clips share the call
+    if (a.out_stft || a.fullp || v.n_clips == 0 || v.total_rows >= (1ull << 31)) return hipErrorInvalidValue;
+    return launch_mel_w12_varlen(a, v, stream, num_cus, info);
 }
 
 }  // namespace ss

@@ -22,7 +22,8 @@ from ._lib import SpeechSauceError, SsParams, make_params  # noqa: F401
 
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
-           "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "MelSpectrogramStream", "StftStream",
+           "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "mel_spectrogram_packed",
+           "mel_spectrogram_list", "stft_packed", "MelSpectrogramStream", "StftStream",
            "MfccStream", "MfeStream", "SpeechConfig", "SpeechSauceError"]
 
 
@@ -428,6 +429,92 @@ def mfcc_list(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01
                           fft_length, low_frequency, high_frequency, dc_elimination, **switches)
     fo = fo.tolist()
     return [out[fo[b]:fo[b + 1]] for b in range(len(sigs))]
+
+
+def _row_offsets(config: SpeechConfig, so):
+    """Sample offsets -> spectrogram row offsets (ss_packed_row_offsets), an int64 host array of n + 1."""
+    ro = np.empty_like(so)
+    _lib.check(_lib.lib().ss_packed_row_offsets(C.byref(config.params), so.size - 1, so.ctypes.data, ro.ctypes.data))
+    return ro
+
+
+def _internal_stft_packed(signal, so, config: SpeechConfig, stft: bool):
+    """signal [N] packed clips, sample offsets so -> (flat float32 block, row_offsets [n + 1]): mel [num_filters * sum R_b] or stft
+    [sum R_b, F, 2].  The row offsets are a device tensor where the signal is one."""
+    lib = _lib.lib()
+    ro = _row_offsets(config, so)
+    n, rows = so.size - 1, int(ro[-1])
+    F = config.params.fft_points // 2 + 1
+    shape = (rows, F, 2) if stft else (config.params.num_filters * rows,)
+    if _is_torch(signal):
+        import torch
+
+        x = signal.contiguous()
+        with torch.cuda.device(x.device):
+            dso, dro = torch.from_numpy(so).to(x.device), torch.from_numpy(ro).to(x.device)
+            out = torch.empty(shape, dtype=torch.float32, device=x.device)
+            fn = lib.ss_stft_packed_device if stft else lib.ss_mel_spectrogram_packed_device
+            _lib.check(fn(config.handle, x.data_ptr(), n, dso.data_ptr(), dro.data_ptr(), rows, out.data_ptr(), _stream_ptr()))
+        return out, dro
+    x = np.ascontiguousarray(signal)
+    out = np.empty(shape, dtype=np.float32)
+    fn = lib.ss_stft_packed if stft else lib.ss_mel_spectrogram_packed
+    _lib.check(fn(config.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data))
+    return out, ro
+
+
+def mel_spectrogram_packed(signal, lengths, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13,
+                           num_filters=40, fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+    """Mel spectrogram of clips of different lengths packed end to end in one 1-D float32 signal (clip b = the lengths[b]
+    samples after the clips before it) -> (out, row_offsets [n + 1] int64).  ``out`` is the flat float32 block of
+    num_filters * sum R_b values: clip b's [num_filters, R_b] block, what ``mel_spectrogram`` returns for that clip alone, starts
+    at num_filters * row_offsets[b].  One launch for all clips."""
+    sig = _require_f32(signal, (1,), "mel_spectrogram_packed")
+    so = _sample_offsets(lengths, sig.shape[0], "mel_spectrogram_packed")
+    config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
+                  low_frequency, high_frequency, dc_elimination, switches, sig)
+    return _internal_stft_packed(sig, so, config, False)
+
+
+def mel_spectrogram_list(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
+                         fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+    """A list of 1-D float32 clips of any lengths -> the list of their [num_filters, R_b] mel spectrograms (views of one block):
+    the clips are packed once and served by one mel_spectrogram_packed call."""
+    sigs = [_require_f32(x, (1,), "mel_spectrogram_list") for x in signals]
+    if not sigs:
+        return []
+    on_device = [_is_torch(x) for x in sigs]  # (_require_f32 turns host tensors into arrays)
+    if any(on_device) and not all(on_device):
+        raise ValueError("mel_spectrogram_list: the clips of one call must all be device tensors or all host arrays")
+    if all(on_device):
+        import torch
+
+        if any(x.device != sigs[0].device for x in sigs):
+            raise ValueError("mel_spectrogram_list: the clips of one call must live on one device")
+        packed = torch.cat(sigs)
+    else:
+        packed = np.concatenate(sigs)
+    lengths = [int(x.shape[0]) for x in sigs]
+    out, ro = mel_spectrogram_packed(packed, lengths, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters,
+                                     fft_length, low_frequency, high_frequency, dc_elimination, **switches)
+    ro = ro.tolist()
+    M = int(num_filters)
+    return [out[M * ro[b]:M * ro[b + 1]].reshape(M, ro[b + 1] - ro[b]) for b in range(len(sigs))]
+
+
+def stft_packed(signal, lengths, sampling_frequency, frame_length=0.020, fft_length=512, **switches):
+    """``stft`` of packed clips (see mel_spectrogram_packed) -> (complex64 [sum R_b, fft_length // 2 + 1], row_offsets [n + 1]):
+    clip b's rows are row_offsets[b] : row_offsets[b + 1], what ``stft`` returns for that clip alone.  numpy in -> numpy out; a
+    ROCm tensor stays on the device (torch.complex64 view of the interleaved block)."""
+    sig = _require_f32(signal, (1,), "stft_packed")
+    so = _sample_offsets(lengths, sig.shape[0], "stft_packed")
+    config = _cfg(sampling_frequency, frame_length, 0.01, 13, 40, fft_length, 0, None, True, switches, sig)
+    out, ro = _internal_stft_packed(sig, so, config, True)
+    if _is_torch(out):
+        import torch
+
+        return torch.view_as_complex(out), ro
+    return out.view(np.complex64)[..., 0], ro
 
 
 def _internal_lmfe_batch(signal, config: SpeechConfig):

@@ -100,6 +100,11 @@ PROTOTYPES = {
     "ss_mfe_packed": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, _fp, _fp]),
     "ss_mfcc_packed_device": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
     "ss_mfe_packed_device": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_packed_row_offsets": (C.c_int, [_P(SsParams), C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ss_mel_spectrogram_packed": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, _fp]),
+    "ss_stft_packed": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, _fp]),
+    "ss_mel_spectrogram_packed_device": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
+    "ss_stft_packed_device": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
     "ss_stream_state_len": (C.c_int, [_P(SsParams), _P(C.c_size_t)]),
     "ss_stream_rows": (C.c_int, [_P(SsParams), C.c_int, C.c_size_t, _P(C.c_size_t), _P(C.c_size_t)]),
     "ss_stft_stream": (C.c_int, [_cfg, C.c_int, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp]),
