@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SS_ABI_VERSION 7 /* 7: ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region; 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
+#define SS_ABI_VERSION 7 /* 7: ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region, the packed post-processing calls (ss_cmvn_packed*, ss_cmvnw_packed*, ss_power_to_db_packed*, ss_lmfe_packed*); 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
 
 typedef enum ss_status {
     SS_OK = 0,
@@ -403,6 +403,53 @@ int ss_ln_device(float *d_x, size_t n, void *stream);
  * |ref|)), then floored at max(result) - top_db; top_db < 0 switches the floor off.  amin > 0. */
 int ss_power_to_db(const float *s, size_t n, float ref, float amin, float top_db, float *out);
 int ss_power_to_db_device(const float *d_s, size_t n, float ref, float amin, float top_db, float *d_out, void *stream);
+
+/* ---- post-processing of packed variable-length clips (a loop over processing::cmvn / cmvnw, feature::lmfe, power_to_db per clip) ----
+ * The normalising steps behind the packed calls above.  A segment table is the offsets array those calls return: `offsets`,
+ * n_clips + 1 non-decreasing entries with offsets[0] = 0 (fo of ss_packed_frame_offsets, ro of ss_packed_row_offsets); clip b owns
+ * rows offsets[b] .. offsets[b+1] of a row-major [total_rows x cols] float block.  Per clip, every result is what the one-matrix
+ * call returns for that clip alone:
+ *   cmvn_packed         ss_cmvn on the clip's rows: its own column means and population std (+ 2^-30).
+ *   cmvnw_packed        ss_cmvnw on the clip's rows: the np.pad 'symmetric' reflection happens at the clip's own first and last row
+ *                       (period 2 * rows_b: a window wider than the clip wraps inside the clip, never into a neighbour).  An even
+ *                       win_size is SS_ERR_BAD_CONFIG.
+ *   power_to_db_packed  clip b's segment is elements cols * offsets[b] .. cols * offsets[b+1] -- the layout of the frame blocks and of
+ *                       the [num_filters x R_b] mel blocks of ss_mel_spectrogram_packed (cols = num_filters, offsets = ro).  The
+ *                       arithmetic of ss_power_to_db_device, with the top_db floor of an element at max(its own clip's result) -
+ *                       top_db; top_db < 0 switches the floor off.
+ *   lmfe_packed         ss_mfe_packed* followed by the in-place ln (feature.rs:242-245); d_energy may be NULL as in
+ *                       ss_lmfe_batch_device.  Tables and errors as ss_mfe_packed_device (after SS_ERR_DEVICE the block's contents are
+ *                       unspecified).
+ * n_clips == 0 is SS_OK with nothing launched (for the three config-free calls also on a host without a device); an empty segment
+ * writes nothing; null buffers, cols == 0, total_rows / cols / n_clips >= 2^31 are SS_ERR_ARG.
+ * Host-pointer forms (synchronous; offsets is a host array) check the table before they touch the device: offsets[0] != 0, a
+ * decreasing pair, offsets[n_clips] > total_rows are SS_ERR_ARG with the first bad clip named in ss_last_error_string.  Rows past
+ * offsets[n_clips] are left as they were.
+ * Device forms (asynchronous on `stream`, d_offsets a DEVICE array that only the kernels read) are graph-capturable as a linear
+ * chain: cmvn one launch and no scratch; cmvnw one launch, with variance normalisation two and a stream-ordered scratch block;
+ * power_to_db two launches and one stream-ordered word per clip.  The launch count does not depend on n_clips.  They have no
+ * config to carry an error word, so their contract for a bad table is containment: a segment that is reversed, starts below 0 or
+ * ends past total_rows is skipped, no kernel reads or writes outside [0, total_rows) x cols whatever the table holds, and rows
+ * that belong to no valid segment are left unwritten.  (Valid segments that overlap -- possible only in a table that is not
+ * monotone -- race with each other inside the block.)
+ * Results are bit-reproducible (f64 accumulators in a fixed order, no float atomics) and position independent: the bits of clip
+ * b's output depend on clip b's rows and the scalar arguments only, not on the clip's place in the block or on its neighbours. */
+int ss_cmvn_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols,
+                   int variance_normalization, float *out);
+int ss_cmvnw_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, size_t win_size,
+                    int variance_normalization, float *out);
+int ss_power_to_db_packed(const float *s, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, float ref,
+                          float amin, float top_db, float *out);
+/* feat: [fo[n_clips] x num_filters], fo = ss_packed_frame_offsets of sample_offsets */
+int ss_lmfe_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *feat);
+int ss_cmvn_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols,
+                          int variance_normalization, float *d_out, void *stream);
+int ss_cmvnw_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols,
+                           size_t win_size, int variance_normalization, float *d_out, void *stream);
+int ss_power_to_db_packed_device(const float *d_s, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols,
+                                 float ref, float amin, float top_db, float *d_out, void *stream);
+int ss_lmfe_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                          const int64_t *d_frame_offsets, size_t total_frames, float *d_feat, float *d_energy, void *stream);
 
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`

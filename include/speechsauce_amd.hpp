@@ -297,6 +297,37 @@ inline std::vector<float> cmvnw(const std::vector<float> &vec, size_t rows, size
     return out;
 }
 
+// cmvn / cmvnw / power_to_db of every clip of a packed block on its own rows (ss_*_packed): clip b owns rows offsets[b] ..
+// offsets[b+1] of the [total_rows x cols] block `vec`; offsets has n_clips + 1 non-decreasing entries and starts at 0
+inline std::vector<float> cmvn_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols,
+                                      bool variance_normalization = false)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty()) throw Error(SS_ERR_ARG, "cmvn_packed: shape mismatch");
+    std::vector<float> out(vec.size());
+    check(ss_cmvn_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, variance_normalization ? 1 : 0, out.data()));
+    return out;
+}
+
+inline std::vector<float> cmvnw_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t win_size = 301,
+                                       bool variance_normalization = false)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty()) throw Error(SS_ERR_ARG, "cmvnw_packed: shape mismatch");
+    std::vector<float> out(vec.size());
+    check(ss_cmvnw_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, win_size, variance_normalization ? 1 : 0,
+                          out.data()));
+    return out;
+}
+
+// top_db < 0: no floor
+inline std::vector<float> power_to_db_packed(const std::vector<float> &s, const std::vector<int64_t> &offsets, size_t cols, float ref = 1.0f,
+                                             float amin = 1e-10f, float top_db = 80.0f)
+{
+    if (cols == 0 || s.size() % cols || offsets.empty()) throw Error(SS_ERR_ARG, "power_to_db_packed: shape mismatch");
+    std::vector<float> out(s.size());
+    check(ss_power_to_db_packed(s.data(), offsets.size() - 1, offsets.data(), s.size() / cols, cols, ref, amin, top_db, out.data()));
+    return out;
+}
+
 // processing.rs:222-254
 inline std::vector<float> derivative_extraction(const std::vector<float> &feat, size_t rows, size_t cols, size_t delta_windows)
 {

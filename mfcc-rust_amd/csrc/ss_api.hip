@@ -1300,11 +1300,13 @@ int launch_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n
 
 // Host-pointer form: the frame offsets from the host's sample offsets, one upload, one launch, one download on the config's
 // first host-pipeline stream (the host calls of a config are serialised by its mutex).
-int packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_clips, const int64_t *so, float *out0, float *out1)
+// ln: lmfe -- the features go through the in-place ln on the device and the frame energies stay there (out1 is NULL).
+int packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_clips, const int64_t *so, float *out0, float *out1,
+                bool ln = false)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
     if (n_clips == 0) return SS_OK;
-    if (!x || !so || !out0 || (out_kind == ss::OUT_MFE && !out1)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (!x || !so || !out0 || (out_kind == ss::OUT_MFE && !out1 && !ln)) return ss::fail(SS_ERR_ARG, "null buffer");
     std::vector<int64_t> fo(n_clips + 1);
     int rc = ss_packed_frame_offsets(&cfg->host.params, n_clips, so, fo.data());
     if (rc) return rc;
@@ -1321,7 +1323,7 @@ int packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_cli
     DeviceBuf dx, dso, dfo, d0, d1;
     if ((rc = dx.alloc(samples * sizeof(float))) || (rc = dso.alloc((n_clips + 1) * sizeof(int64_t))) ||
         (rc = dfo.alloc((n_clips + 1) * sizeof(int64_t))) || (rc = d0.alloc(rows * cols * sizeof(float))) ||
-        (out1 && (rc = d1.alloc(rows * sizeof(float)))))
+        ((out1 || ln) && (rc = d1.alloc(rows * sizeof(float)))))
         return rc;
     hipError_t e = hipMemcpyAsync(dx.p, x, samples * sizeof(float), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
@@ -1329,7 +1331,8 @@ int packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_cli
     if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
     if (rc == SS_OK)
         rc = launch_packed(cfg, out_kind, dx.as<const float>(), n_clips, dso.as<const int64_t>(), dfo.as<const int64_t>(), rows,
-                           d0.as<float>(), out1 ? d1.as<float>() : nullptr, st);
+                           d0.as<float>(), (out1 || ln) ? d1.as<float>() : nullptr, st);
+    if (rc == SS_OK && ln) rc = ss_ln_device(d0.as<float>(), rows * cols, st);
     if (rc == SS_OK) {
         e = hipMemcpyAsync(out0, d0.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && out1) e = hipMemcpyAsync(out1, d1.p, rows * sizeof(float), hipMemcpyDeviceToHost, st);
@@ -1700,6 +1703,34 @@ int ss_mel_spectrogram_packed(const ss_config *cfg, const float *x, size_t n_cli
 int ss_stft_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out)
 {
     return packed_stft_host(cfg, ss::OUT_STFT, x, n_clips, sample_offsets, out);
+}
+
+// lmfe of packed clips: ss_mfe_packed_device, then the in-place ln over the block (two stream-ordered launches, a linear chain)
+int ss_lmfe_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                          const int64_t *d_frame_offsets, size_t total_frames, float *d_feat, float *d_energy, void *stream)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_clips == 0) return SS_OK;
+    if (!d_x || !d_sample_offsets || !d_frame_offsets || !d_feat) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (total_frames >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "feature block too large");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *tmp = nullptr;
+    if (!d_energy && total_frames) {
+        SS_HIP(hipMallocAsync(reinterpret_cast<void **>(&tmp), total_frames * sizeof(float), st));
+        d_energy = tmp;
+    }
+    int rc = launch_packed(cfg, ss::OUT_MFE, d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_feat, d_energy, st);
+    if (rc == SS_OK) rc = ss_ln_device(d_feat, total_frames * cfg->host.params.num_filters, stream);
+    if (tmp) {
+        const hipError_t e = hipFreeAsync(tmp, st);
+        if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "hipFreeAsync");
+    }
+    return rc;
+}
+
+int ss_lmfe_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *feat)
+{
+    return packed_host(cfg, ss::OUT_MFE, x, n_clips, sample_offsets, feat, nullptr, true);
 }
 
 // lmfe (feature.rs:242-245): ln of mfe's zero-handled filterbank energies.  The frame energies mfe also returns are

@@ -241,6 +241,197 @@ __global__ __launch_bounds__(256) void ss_derivative_cube_kernel(const float *__
     cube[3 * g + 2] = acc * inv10;
 }
 
+// ---- packed variable-length clips (ss_cmvn_packed* / ss_cmvnw_packed* / ss_power_to_db_packed*) ----
+// Clip b owns rows off[b] .. off[b+1] of the [total_rows x cols] block; the table is a device array that only the kernels read.
+// Workgroup (b, z) = blockIdx (x, y) serves clip b: every chunk boundary and summation order is counted from the clip's own first
+// row and depends on its row count and the scalar arguments only, so a clip's bits do not depend on where it sits in the block.
+// gridDim.y workgroups share a long clip (strided over its tasks); for a short clip the ones past its work return at once.
+// Containment: a segment that is reversed, starts below 0 or ends past total_rows is skipped, and every address a workgroup forms
+// lies inside its own validated segment.
+struct Segment {
+    unsigned long long row0;
+    unsigned rows;  // 0: nothing to do (empty or rejected segment)
+};
+
+__device__ __forceinline__ Segment packed_segment(const long long *__restrict__ off, unsigned long long total_rows)
+{
+    const long long lo = off[blockIdx.x], hi = off[blockIdx.x + 1];
+    Segment s{0, 0};
+    if (lo >= 0 && lo < hi && static_cast<unsigned long long>(hi) <= total_rows) {  // total_rows < 2^31: the row count fits
+        s.row0 = static_cast<unsigned long long>(lo);
+        s.rows = static_cast<unsigned>(hi - lo);
+    }
+    return s;
+}
+
+constexpr unsigned kCmvnChunks = 64;   // chunks = min(64, ceil(rows / 32)), as ss_cmvn_batch_device
+constexpr unsigned kCmvnTile = 32;     // columns whose chunk partials sit in LDS at a time: 64 x 32 x 2 doubles = 32 KiB
+constexpr unsigned kCmvnSplitRows = 2048;  // a clip gets one workgroup per 2048 rows (up to gridDim.y)
+
+// cmvn of one clip per workgroup, one launch, no scratch: the chunk partials of ss_cmvn_partial_kernel go to LDS instead of HBM,
+// the column statistics are summed from them in the same order, then the workgroup normalises the clip's elements.  The
+// workgroups that share a long clip each compute the (identical) statistics and normalise a strided share of the elements.
+__global__ __launch_bounds__(256) void ss_cmvn_packed_kernel(const float *__restrict__ x, const long long *__restrict__ off, float *__restrict__ out,
+                                                            unsigned long long total_rows, unsigned cols, int variance)
+{
+    __shared__ double part[kCmvnChunks * kCmvnTile * 2];
+    __shared__ double stat[kCmvnTile * 2];  // mean, 1 / (std + 2^-30)
+    const Segment seg = packed_segment(off, total_rows);
+    if (seg.rows == 0) return;
+    const unsigned rows = seg.rows;
+    const unsigned share = min(gridDim.y, (rows + kCmvnSplitRows - 1) / kCmvnSplitRows);
+    if (blockIdx.y >= share) return;
+    const unsigned chunks = min(kCmvnChunks, (rows + 31) / 32);
+    const unsigned rpc = (rows + chunks - 1) / chunks;
+    const float *src = x + seg.row0 * cols;
+    float *dst = out + seg.row0 * cols;
+    for (unsigned c0 = 0; c0 < cols; c0 += kCmvnTile) {
+        const unsigned ct = min(kCmvnTile, cols - c0);
+        for (unsigned k = threadIdx.x; k < chunks * ct; k += 256) {  // task = (chunk, column), columns fastest
+            const unsigned chunk = k / ct, c = k - chunk * ct;
+            const unsigned r0 = chunk * rpc, r1 = min(rows, r0 + rpc);
+            const float *p = src + c0 + c;
+            double s1 = 0.0, s2 = 0.0;
+            for (unsigned r = r0; r < r1; ++r) {
+                const double v = static_cast<double>(p[static_cast<size_t>(r) * cols]);
+                s1 += v;
+                s2 += v * v;
+            }
+            part[2 * k] = s1;
+            part[2 * k + 1] = s2;
+        }
+        __syncthreads();
+        if (threadIdx.x < ct) {
+            double s1 = 0.0, s2 = 0.0;
+            for (unsigned k = 0; k < chunks; ++k) {
+                s1 += part[2 * (k * ct + threadIdx.x)];
+                s2 += part[2 * (k * ct + threadIdx.x) + 1];
+            }
+            const double mean = s1 / rows;
+            double inv = 1.0;
+            if (variance) {
+                const double var = fmax(s2 / rows - mean * mean, 0.0);  // as ss_cmvn_apply_kernel
+                inv = 1.0 / (sqrt(var) + kEps30);
+            }
+            stat[2 * threadIdx.x] = mean;
+            stat[2 * threadIdx.x + 1] = inv;
+        }
+        __syncthreads();
+        const unsigned long long n = static_cast<unsigned long long>(rows) * ct;
+        for (unsigned long long e = static_cast<unsigned long long>(blockIdx.y) * 256 + threadIdx.x; e < n; e += static_cast<unsigned long long>(share) * 256) {
+            const unsigned long long r = e / ct;
+            const unsigned c = static_cast<unsigned>(e - r * ct);
+            const size_t at = static_cast<size_t>(r) * cols + c0 + c;
+            dst[at] = static_cast<float>((static_cast<double>(src[at]) - stat[2 * c]) * stat[2 * c + 1]);
+        }
+        __syncthreads();  // the next column tile overwrites part / stat
+    }
+}
+
+// cmvnw: the chunk bodies of ss_cmvnw_mean_kernel / ss_cmvnw_var_kernel on rows i0 .. i1 of a column of ONE clip (src / dst point
+// at that clip's column; rows is the clip's own row count, so the symmetric reflection wraps inside the clip)
+__device__ __forceinline__ void cmvnw_mean_chunk(const float *__restrict__ src, float *__restrict__ dst, unsigned rows, unsigned cols, unsigned win,
+                                                 unsigned i0, unsigned i1)
+{
+    const long long pad = (win - 1) / 2;
+    SymWalk head(static_cast<long long>(i0) - pad, rows), tail = head;
+    double s = 0.0;
+#pragma unroll 4
+    for (unsigned w = 0; w < win; ++w) {
+        s += static_cast<double>(src[static_cast<size_t>(head.idx) * cols]);
+        head.step();
+    }
+    for (unsigned i = i0; i < i1; ++i) {
+        dst[static_cast<size_t>(i) * cols] = static_cast<float>(static_cast<double>(src[static_cast<size_t>(i) * cols]) - s / win);
+        s += static_cast<double>(src[static_cast<size_t>(head.idx) * cols]) - static_cast<double>(src[static_cast<size_t>(tail.idx) * cols]);
+        head.step();
+        tail.step();
+    }
+}
+
+__device__ __forceinline__ void cmvnw_var_chunk(const float *__restrict__ src, float *__restrict__ dst, unsigned rows, unsigned cols, unsigned win,
+                                                unsigned i0, unsigned i1)
+{
+    const long long pad = (win - 1) / 2;
+    SymWalk head(static_cast<long long>(i0) - pad, rows), tail = head;
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll 4
+    for (unsigned w = 0; w < win; ++w) {
+        const double v = static_cast<double>(src[static_cast<size_t>(head.idx) * cols]);
+        s1 += v;
+        s2 += v * v;
+        head.step();
+    }
+    for (unsigned i = i0; i < i1; ++i) {
+        const double m = s1 / win;
+        const double var = fmax(s2 / win - m * m, 0.0);
+        dst[static_cast<size_t>(i) * cols] = static_cast<float>(static_cast<double>(src[static_cast<size_t>(i) * cols]) / (sqrt(var) + kEps30));
+        const double vin = static_cast<double>(src[static_cast<size_t>(head.idx) * cols]);
+        const double vout = static_cast<double>(src[static_cast<size_t>(tail.idx) * cols]);
+        s1 += vin - vout;
+        s2 += vin * vin - vout * vout;
+        head.step();
+        tail.step();
+    }
+}
+
+// pass 1 (VAR = false) or pass 2 (VAR = true) of cmvnw over packed clips: task = (chunk of rpc rows counted from the clip's first
+// row, column), columns fastest; the gridDim.y workgroups of a clip stride over its tasks
+template <bool VAR>
+__global__ __launch_bounds__(256) void ss_cmvnw_packed_kernel(const float *__restrict__ in, const long long *__restrict__ off, float *__restrict__ out,
+                                                             unsigned long long total_rows, unsigned cols, unsigned win, unsigned rpc)
+{
+    const Segment seg = packed_segment(off, total_rows);
+    if (seg.rows == 0) return;
+    const unsigned rows = seg.rows;
+    const unsigned chunks = (rows + rpc - 1) / rpc;
+    const unsigned long long tasks = static_cast<unsigned long long>(chunks) * cols;
+    const float *src = in + seg.row0 * cols;
+    float *dst = out + seg.row0 * cols;
+    for (unsigned long long k = static_cast<unsigned long long>(blockIdx.y) * 256 + threadIdx.x; k < tasks; k += static_cast<unsigned long long>(gridDim.y) * 256) {
+        const unsigned chunk = static_cast<unsigned>(k / cols);
+        const unsigned c = static_cast<unsigned>(k - static_cast<unsigned long long>(chunk) * cols);
+        const unsigned i0 = chunk * rpc, i1 = min(rows, i0 + rpc);
+        if (VAR) cmvnw_var_chunk(src + c, dst + c, rows, cols, win, i0, i1);
+        else cmvnw_mean_chunk(src + c, dst + c, rows, cols, win, i0, i1);
+    }
+}
+
+// power_to_db over packed clips: clip b's segment is elements cols * off[b] .. cols * off[b+1]; its maximum goes to max_key[b]
+// (ordered-integer atomicMax: a maximum does not depend on the order of arrival), the floor pass reads it back
+__global__ __launch_bounds__(256) void ss_power_to_db_packed_kernel(const float *__restrict__ s, const long long *__restrict__ off, float *__restrict__ out,
+                                                                   unsigned long long total_rows, unsigned cols, float amin, float ref_db,
+                                                                   int *__restrict__ max_key)
+{
+    const Segment seg = packed_segment(off, total_rows);
+    if (seg.rows == 0) return;
+    const unsigned long long n = static_cast<unsigned long long>(seg.rows) * cols;
+    const float *src = s + seg.row0 * cols;
+    float *dst = out + seg.row0 * cols;
+    float mx = -INFINITY;
+    for (unsigned long long g = static_cast<unsigned long long>(blockIdx.y) * 256 + threadIdx.x; g < n; g += static_cast<unsigned long long>(gridDim.y) * 256) {
+        const float db = 10.0f * log10f(fmaxf(amin, src[g])) - ref_db;
+        dst[g] = db;
+        mx = fmaxf(mx, db);
+    }
+    if (max_key) {
+        for (int m = 1; m < 64; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+        if ((threadIdx.x & 63) == 0 && mx > -INFINITY) atomicMax(max_key + blockIdx.x, float_key(mx));
+    }
+}
+
+__global__ __launch_bounds__(256) void ss_db_floor_packed_kernel(float *__restrict__ out, const long long *__restrict__ off, unsigned long long total_rows,
+                                                                unsigned cols, float top_db, const int *__restrict__ max_key)
+{
+    const Segment seg = packed_segment(off, total_rows);
+    if (seg.rows == 0) return;
+    const unsigned long long n = static_cast<unsigned long long>(seg.rows) * cols;
+    float *dst = out + seg.row0 * cols;
+    const float floor_db = key_float(max_key[blockIdx.x]) - top_db;
+    for (unsigned long long g = static_cast<unsigned long long>(blockIdx.y) * 256 + threadIdx.x; g < n; g += static_cast<unsigned long long>(gridDim.y) * 256)
+        dst[g] = fmaxf(dst[g], floor_db);
+}
+
 int hip_err(hipError_t e, const char *what) { return fail(SS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 
 unsigned blocks_for(unsigned long long n) { return static_cast<unsigned>((n + 255) / 256); }
@@ -271,6 +462,66 @@ int via_device(const float *in, size_t n_in, float *out, size_t n_out, F &&run)
     }
     if (d_in) (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);
+    return rc;
+}
+
+// ---- packed clips: argument checks, grid shape, host staging ----
+
+int check_packed(const void *a, const void *off, const void *b, size_t n_clips, size_t total_rows, size_t cols)
+{
+    if (!a || !off || !b) return fail(SS_ERR_ARG, "null buffer");
+    if (cols == 0) return fail(SS_ERR_ARG, "empty feature matrix (cols == 0)");
+    if (total_rows >= (1ull << 31) || cols >= (1ull << 31) || n_clips >= (1ull << 31)) return fail(SS_ERR_ARG, "feature block too large");
+    return SS_OK;
+}
+
+// the segment table of a host-pointer call, checked before the device is touched
+int check_table(const int64_t *off, size_t n_clips, size_t total_rows)
+{
+    if (off[0] != 0) return fail(SS_ERR_ARG, "offsets[0] must be 0 (clip 0)");
+    for (size_t b = 0; b < n_clips; ++b)
+        if (off[b + 1] < off[b]) return fail(SS_ERR_ARG, "decreasing offsets at clip " + std::to_string(b));
+    if (static_cast<uint64_t>(off[n_clips]) > total_rows)
+        for (size_t b = 0; b < n_clips; ++b)
+            if (static_cast<uint64_t>(off[b + 1]) > total_rows)
+                return fail(SS_ERR_ARG, "clip " + std::to_string(b) + " ends past total_rows");
+    return SS_OK;
+}
+
+// Workgroups per clip (gridDim.y): about 8192 workgroups in all, so that a block of few long clips still fills the device, and
+// never more than the longest possible clip (all of total_rows) has work for.  Sized from what the host knows; the bits of the
+// results do not depend on it.
+unsigned packed_split(size_t n_clips, unsigned long long most_useful)
+{
+    const unsigned long long want = std::max<unsigned long long>(1, 8192 / n_clips);
+    return static_cast<unsigned>(std::min<unsigned long long>(64, std::min(want, std::max<unsigned long long>(1, most_useful))));
+}
+
+// host-pointer wrapper of the packed calls: upload the block (n floats) and the checked table, run the device entry point,
+// download the rows the table covers (n_written floats from the start: a host table is gap-free; rows past offsets[n_clips] stay
+// as the caller left them)
+template <typename F>
+int via_device_packed(const float *in, const int64_t *off, size_t n_clips, size_t n, size_t n_written, float *out, F &&run)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd path has no CPU fallback");
+    float *d_in = nullptr, *d_out = nullptr;
+    int64_t *d_off = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_in), n * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), n * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_off), (n_clips + 1) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMemcpy(d_in, in, n * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off, off, (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? run(d_in, d_off, d_out) : hip_err(e, "host staging");
+    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "packed post-processing: device error");
+    if (rc == SS_OK) {
+        e = hipMemcpy(out, d_out, n_written * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_err(e, "hipMemcpy D2H");
+    }
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (d_off) (void)hipFree(d_off);
     return rc;
 }
 
@@ -453,6 +704,133 @@ int ss_power_to_db(const float *s, size_t n, float ref, float amin, float top_db
         if (r == SS_OK && hipDeviceSynchronize() != hipSuccess) r = ss::fail(SS_ERR_HIP, "ss_power_to_db: device error");
         return r;
     });
+}
+
+// ---- packed variable-length clips: clip b owns rows offsets[b] .. offsets[b+1] of the [total_rows x cols] block ----
+
+int ss_cmvn_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols,
+                          int variance_normalization, float *d_out, void *stream)
+{
+    if (n_clips == 0) return SS_OK;
+    int rc = ss::check_packed(d_vec, d_offsets, d_out, n_clips, total_rows, cols);
+    if (rc) return rc;
+    if (total_rows == 0) return SS_OK;
+    const unsigned split = ss::packed_split(n_clips, (total_rows + ss::kCmvnSplitRows - 1) / ss::kCmvnSplitRows);
+    hipLaunchKernelGGL(ss::ss_cmvn_packed_kernel, dim3(static_cast<unsigned>(n_clips), split), dim3(256), 0, static_cast<hipStream_t>(stream), d_vec,
+                       reinterpret_cast<const long long *>(d_offsets), d_out, static_cast<unsigned long long>(total_rows), static_cast<unsigned>(cols),
+                       variance_normalization);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_cmvn_packed_kernel");
+}
+
+int ss_cmvnw_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols, size_t win_size,
+                           int variance_normalization, float *d_out, void *stream)
+{
+    if (n_clips == 0) return SS_OK;
+    int rc = ss::check_packed(d_vec, d_offsets, d_out, n_clips, total_rows, cols);
+    if (rc) return rc;
+    if (win_size % 2 != 1) return ss::fail(SS_ERR_BAD_CONFIG, "Windows size must be odd!");  // assert, processing.rs:327
+    if (win_size >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "window too large");
+    if (total_rows == 0) return SS_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned c = static_cast<unsigned>(cols), w = static_cast<unsigned>(win_size);
+    const unsigned long long tr = total_rows;
+    const long long *off = reinterpret_cast<const long long *>(d_offsets);
+    const unsigned rpc = static_cast<unsigned>(std::min<size_t>(256, std::max<size_t>(8, (win_size + 15) / 16)));  // as ss_cmvnw_batch_device
+    const unsigned split = ss::packed_split(n_clips, ((tr + rpc - 1) / rpc * cols + 255) / 256);
+    const dim3 grid(static_cast<unsigned>(n_clips), split);
+    if (!variance_normalization) {
+        hipLaunchKernelGGL(ss::ss_cmvnw_packed_kernel<false>, grid, dim3(256), 0, s, d_vec, off, d_out, tr, c, w, rpc);
+    } else {
+        // the second pass reads its neighbours' mean-subtracted values: they go through a stream-ordered scratch block
+        float *d_ms = nullptr;
+        hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&d_ms), total_rows * cols * sizeof(float), s);
+        if (e != hipSuccess) return ss::hip_err(e, "hipMallocAsync");
+        hipLaunchKernelGGL(ss::ss_cmvnw_packed_kernel<false>, grid, dim3(256), 0, s, d_vec, off, d_ms, tr, c, w, rpc);
+        hipLaunchKernelGGL(ss::ss_cmvnw_packed_kernel<true>, grid, dim3(256), 0, s, d_ms, off, d_out, tr, c, w, rpc);
+        e = hipFreeAsync(d_ms, s);
+        if (e != hipSuccess) return ss::hip_err(e, "hipFreeAsync");
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_cmvnw_packed kernels");
+}
+
+int ss_power_to_db_packed_device(const float *d_s, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols, float ref,
+                                 float amin, float top_db, float *d_out, void *stream)
+{
+    if (n_clips == 0) return SS_OK;
+    int rc = ss::check_packed(d_s, d_offsets, d_out, n_clips, total_rows, cols);
+    if (rc) return rc;
+    if (!(amin > 0.0f)) return ss::fail(SS_ERR_ARG, "amin must be strictly positive");
+    if (ref != ref) return ss::fail(SS_ERR_ARG, "ref must not be NaN");
+    if (total_rows == 0) return SS_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float ref_db = 10.0f * std::log10(std::max(amin, std::fabs(ref)));
+    const unsigned long long tr = total_rows;
+    const long long *off = reinterpret_cast<const long long *>(d_offsets);
+    const dim3 grid(static_cast<unsigned>(n_clips), ss::packed_split(n_clips, (tr * cols + 1023) / 1024));
+    int *d_max = nullptr;  // one ordered-integer maximum per clip
+    if (top_db >= 0.0f) {
+        hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&d_max), n_clips * sizeof(int), st);
+        if (e != hipSuccess) return ss::hip_err(e, "hipMallocAsync");
+        e = hipMemsetAsync(d_max, 0x80, n_clips * sizeof(int), st);  // 0x80808080: below the key of every finite float
+        if (e != hipSuccess) return ss::hip_err(e, "hipMemsetAsync");
+    }
+    hipLaunchKernelGGL(ss::ss_power_to_db_packed_kernel, grid, dim3(256), 0, st, d_s, off, d_out, tr, static_cast<unsigned>(cols), amin, ref_db, d_max);
+    if (d_max) {
+        hipLaunchKernelGGL(ss::ss_db_floor_packed_kernel, grid, dim3(256), 0, st, d_out, off, tr, static_cast<unsigned>(cols), top_db, d_max);
+        const hipError_t e = hipFreeAsync(d_max, st);
+        if (e != hipSuccess) return ss::hip_err(e, "hipFreeAsync");
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_power_to_db_packed kernels");
+}
+
+// host-pointer forms (synchronous): the table is checked on the host before the device is touched
+
+int ss_cmvn_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, int variance_normalization,
+                   float *out)
+{
+    if (n_clips == 0) return SS_OK;
+    int rc = ss::check_packed(vec, offsets, out, n_clips, total_rows, cols);
+    if (rc || (rc = ss::check_table(offsets, n_clips, total_rows))) return rc;
+    if (offsets[n_clips] == 0) return SS_OK;
+    return ss::via_device_packed(vec, offsets, n_clips, total_rows * cols, static_cast<size_t>(offsets[n_clips]) * cols, out,
+                                 [&](const float *di, const int64_t *doff, float *dout) {
+                                     return ss_cmvn_packed_device(di, n_clips, doff, total_rows, cols, variance_normalization, dout, nullptr);
+                                 });
+}
+
+int ss_cmvnw_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, size_t win_size,
+                    int variance_normalization, float *out)
+{
+    if (n_clips == 0) return SS_OK;
+    int rc = ss::check_packed(vec, offsets, out, n_clips, total_rows, cols);
+    if (rc) return rc;
+    if (win_size % 2 != 1) return ss::fail(SS_ERR_BAD_CONFIG, "Windows size must be odd!");
+    if (win_size >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "window too large");
+    if ((rc = ss::check_table(offsets, n_clips, total_rows))) return rc;
+    if (offsets[n_clips] == 0) return SS_OK;
+    return ss::via_device_packed(vec, offsets, n_clips, total_rows * cols, static_cast<size_t>(offsets[n_clips]) * cols, out,
+                                 [&](const float *di, const int64_t *doff, float *dout) {
+                                     return ss_cmvnw_packed_device(di, n_clips, doff, total_rows, cols, win_size, variance_normalization, dout, nullptr);
+                                 });
+}
+
+int ss_power_to_db_packed(const float *s, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, float ref, float amin,
+                          float top_db, float *out)
+{
+    if (n_clips == 0) return SS_OK;
+    int rc = ss::check_packed(s, offsets, out, n_clips, total_rows, cols);
+    if (rc) return rc;
+    if (!(amin > 0.0f)) return ss::fail(SS_ERR_ARG, "amin must be strictly positive");
+    if (ref != ref) return ss::fail(SS_ERR_ARG, "ref must not be NaN");
+    if ((rc = ss::check_table(offsets, n_clips, total_rows))) return rc;
+    if (offsets[n_clips] == 0) return SS_OK;
+    return ss::via_device_packed(s, offsets, n_clips, total_rows * cols, static_cast<size_t>(offsets[n_clips]) * cols, out,
+                                 [&](const float *di, const int64_t *doff, float *dout) {
+                                     return ss_power_to_db_packed_device(di, n_clips, doff, total_rows, cols, ref, amin, top_db, dout, nullptr);
+                                 });
 }
 
 }  // extern "C"

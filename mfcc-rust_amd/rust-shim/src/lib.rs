@@ -94,6 +94,12 @@ extern "C" {
     fn ss_config_device_status(cfg: *const SsConfig) -> c_int;
     fn ss_cmvn(vec: *const f32, rows: usize, cols: usize, variance_normalization: c_int, out: *mut f32) -> c_int;
     fn ss_cmvnw(vec: *const f32, rows: usize, cols: usize, win_size: usize, variance_normalization: c_int, out: *mut f32) -> c_int;
+    fn ss_cmvn_packed(vec: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize,
+                      variance_normalization: c_int, out: *mut f32) -> c_int;
+    fn ss_cmvnw_packed(vec: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize, win_size: usize,
+                       variance_normalization: c_int, out: *mut f32) -> c_int;
+    fn ss_power_to_db_packed(s: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize, ref_value: f32,
+                             amin: f32, top_db: f32, out: *mut f32) -> c_int;
     fn ss_derivative_extraction(feat: *const f32, rows: usize, cols: usize, delta_windows: usize, out: *mut f32) -> c_int;
     fn ss_extract_derivative_feature(feat: *const f32, rows: usize, cols: usize, cube: *mut f32) -> c_int;
     fn ss_shard_bounds(n_items: usize, world: c_int, rank: c_int, lo: *mut usize, hi: *mut usize) -> c_int;
@@ -539,6 +545,45 @@ pub fn cmvnw(vec: Array2<f32>, win_size: usize, variance_normalization: bool) ->
     check(unsafe { ss_cmvnw(x.as_ptr(), rows, cols, win_size, variance_normalization as c_int, out.as_mut_ptr()) })
         .expect("Windows size must be odd!");
     out
+}
+
+/// `cmvn` of every clip of a packed block on its own rows (a loop over processing.rs:265-300 per clip, one launch): clip b owns rows
+/// `offsets[b] .. offsets[b + 1]` of `vec`; `offsets` has n_clips + 1 non-decreasing entries and starts at 0.
+pub fn try_cmvn_packed(vec: ArrayView2<f32>, offsets: &[i64], variance_normalization: bool) -> Result<Array2<f32>, Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    let mut out = Array2::<f32>::zeros((rows, cols));
+    check(unsafe {
+        ss_cmvn_packed(x.as_ptr(), offsets.len().saturating_sub(1), offsets.as_ptr(), rows, cols, variance_normalization as c_int,
+                       out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// `cmvnw` of every clip of a packed block on its own rows (processing.rs:315-371 per clip): the symmetric padding reflects at the
+/// clip's own first and last row.  `Err` with status 2 for an even `win_size`.
+pub fn try_cmvnw_packed(vec: ArrayView2<f32>, offsets: &[i64], win_size: usize, variance_normalization: bool) -> Result<Array2<f32>, Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    let mut out = Array2::<f32>::zeros((rows, cols));
+    check(unsafe {
+        ss_cmvnw_packed(x.as_ptr(), offsets.len().saturating_sub(1), offsets.as_ptr(), rows, cols, win_size,
+                        variance_normalization as c_int, out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// librosa's power_to_db of every clip of a packed block with the clip's own `top_db` floor (`None`: no floor); clip b's segment
+/// is elements `cols * offsets[b] .. cols * offsets[b + 1]` of `s`.
+pub fn try_power_to_db_packed(s: ArrayView2<f32>, offsets: &[i64], ref_value: f32, amin: f32, top_db: Option<f32>) -> Result<Array2<f32>, Error> {
+    let x = s.as_standard_layout();
+    let (rows, cols) = x.dim();
+    let mut out = Array2::<f32>::zeros((rows, cols));
+    check(unsafe {
+        ss_power_to_db_packed(x.as_ptr(), offsets.len().saturating_sub(1), offsets.as_ptr(), rows, cols, ref_value, amin,
+                              top_db.unwrap_or(-1.0), out.as_mut_ptr())
+    })?;
+    Ok(out)
 }
 
 /// processing.rs:222-254

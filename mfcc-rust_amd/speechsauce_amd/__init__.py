@@ -23,7 +23,8 @@ from ._lib import SpeechSauceError, SsParams, make_params  # noqa: F401
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
            "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "mel_spectrogram_packed",
-           "mel_spectrogram_list", "stft_packed", "MelSpectrogramStream", "StftStream",
+           "mel_spectrogram_list", "stft_packed", "cmvn_packed", "cmvnw_packed", "power_to_db_packed", "lmfe_packed",
+           "MelSpectrogramStream", "StftStream",
            "MfccStream", "MfeStream", "SpeechConfig", "SpeechSauceError"]
 
 
@@ -552,6 +553,33 @@ def lmfe_batch(signals, sampling_frequency, frame_length=0.020, frame_stride=0.0
     config = _cfg(sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
                   low_frequency, high_frequency, True, switches, sig)
     return _internal_lmfe_batch(sig, config)
+
+
+def lmfe_packed(signal, lengths, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_filters=40, fft_length=512,
+                low_frequency=0, high_frequency=None, **switches):
+    """``lmfe`` of packed clips (see mfcc_packed) -> (feat [sum T_b, num_filters], frame_offsets [n + 1]): clip b's rows are what
+    ``lmfe`` returns for that clip alone."""
+    lib = _lib.lib()
+    sig = _require_f32(signal, (1,), "lmfe_packed")
+    so = _sample_offsets(lengths, sig.shape[0], "lmfe_packed")
+    config = _cfg(sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
+                  low_frequency, high_frequency, True, switches, sig)
+    fo = _frame_offsets(config, so)
+    n, rows, M = so.size - 1, int(fo[-1]), config.params.num_filters
+    if _is_torch(sig):
+        import torch
+
+        x = sig.contiguous()
+        with torch.cuda.device(x.device):
+            dso, dfo = torch.from_numpy(so).to(x.device), torch.from_numpy(fo).to(x.device)
+            feat = torch.empty((rows, M), dtype=torch.float32, device=x.device)
+            _lib.check(lib.ss_lmfe_packed_device(config.handle, x.data_ptr(), n, dso.data_ptr(), dfo.data_ptr(), rows,
+                                                 feat.data_ptr(), None, _stream_ptr()))
+        return feat, dfo
+    x = np.ascontiguousarray(sig)
+    feat = np.empty((rows, M), dtype=np.float32)
+    _lib.check(lib.ss_lmfe_packed(config.handle, x.ctypes.data, n, so.ctypes.data, feat.ctypes.data))
+    return feat, fo
 
 
 def power_to_db(S, ref=1.0, amin=1e-10, top_db=80.0):
@@ -1115,3 +1143,113 @@ def extract_derivative_feature(feature):
     lib = _lib.lib()
     return _post(feature, "extract_derivative_feature", lambda p, r, c, o: lib.ss_extract_derivative_feature(p, r, c, o),
                  lambda p, b, r, c, o, s: lib.ss_extract_derivative_feature_device(p, b * r, c, o, s), out_tail=(3,))
+
+
+# ---- the same steps on packed variable-length clips (ss_*_packed*): `offsets` is the table mfcc_packed / mfe_packed /
+# mel_spectrogram_packed returned (n + 1 int64, offsets[0] = 0); clip b owns rows offsets[b] : offsets[b + 1] of the block ----
+
+def _packed_block(S, cols, what):
+    """-> (contiguous float32 block, on_device, total_rows, cols); a 2-D block is [total_rows, cols], a flat one needs cols."""
+    if _is_torch(S):
+        import torch
+
+        if S.dtype != torch.float32:
+            raise TypeError(f"{what}: expected float32, got {S.dtype}")
+        on_device = S.is_cuda
+        x = S.contiguous() if on_device else np.ascontiguousarray(S.detach().numpy())
+    else:
+        x = np.asarray(S)
+        if x.dtype != np.float32:
+            raise TypeError(f"{what}: expected float32, got {x.dtype}")
+        x, on_device = np.ascontiguousarray(x), False
+    ndim = x.dim() if on_device else x.ndim
+    if ndim == 2:
+        if cols is not None and int(cols) != x.shape[1]:
+            raise ValueError(f"{what}: cols = {cols} but the block has {x.shape[1]} columns")
+        return x, on_device, int(x.shape[0]), int(x.shape[1])
+    if ndim != 1:
+        raise ValueError(f"{what}: expected a [total_rows, cols] block (or a flat block and cols)")
+    if cols is None:
+        raise ValueError(f"{what}: a flat block needs cols")
+    cols = int(cols)
+    if cols <= 0 or x.shape[0] % cols:
+        raise ValueError(f"{what}: the block of {x.shape[0]} values is not a whole number of rows of {cols}")
+    return x, on_device, int(x.shape[0]) // cols, cols
+
+
+def _segment_table(offsets, on_device, device, total_rows, what):
+    """-> (table for the call, n_clips): a device int64 tensor is used as it is (the kernels contain a bad table, nothing of it is
+    read back); a host table is validated here and, for a device block, uploaded."""
+    if _is_torch(offsets):
+        import torch
+
+        if offsets.dtype != torch.int64:
+            raise TypeError(f"{what}: offsets must be int64, got {offsets.dtype}")
+        if offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError(f"{what}: offsets must be 1-D with n_clips + 1 entries")
+        if offsets.is_cuda:
+            if not on_device:
+                offsets = offsets.cpu()  # host block: the host entry point validates a host table
+            elif offsets.device != device:
+                raise ValueError(f"{what}: offsets and the block live on different devices")
+            else:
+                return offsets.contiguous(), offsets.numel() - 1
+        offsets = offsets.numpy()
+    off = np.asarray(offsets)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError(f"{what}: offsets must be 1-D with n_clips + 1 entries")
+    if not np.issubdtype(off.dtype, np.integer):
+        raise TypeError(f"{what}: offsets must be integers, got {off.dtype}")
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] > total_rows:
+        raise ValueError(f"{what}: offsets must start at 0, not decrease and end within the block's {total_rows} rows")
+    if on_device:
+        import torch
+
+        return torch.from_numpy(off).to(device), off.size - 1
+    return off, off.size - 1
+
+
+def _post_packed(S, offsets, cols, what, host_fn, dev_fn):
+    x, on_device, rows, cols = _packed_block(S, cols, what)
+    table, n = _segment_table(offsets, on_device, x.device if on_device else None, rows, what)
+    if on_device:
+        import torch
+
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(dev_fn(x.data_ptr(), n, table.data_ptr(), rows, cols, out.data_ptr(), _stream_ptr()))
+        return out
+    out = np.empty_like(x)
+    _lib.check(host_fn(x.ctypes.data, n, table.ctypes.data, rows, cols, out.ctypes.data))
+    return out
+
+
+def cmvn_packed(vec, offsets, variance_normalization=False):
+    """``cmvn`` of every clip of a packed block [sum T_b, cols] on its own rows, one launch for all clips.  numpy in -> numpy out; a
+    ROCm tensor stays on the device (current stream), and ``offsets`` may be the device tensor ``mfcc_packed`` returned (used as it
+    is) or a host array (validated, uploaded).  Rows that the table does not cover are left uninitialised."""
+    lib, var = _lib.lib(), int(bool(variance_normalization))
+    return _post_packed(vec, offsets, None, "cmvn_packed", lambda p, n, t, r, c, o: lib.ss_cmvn_packed(p, n, t, r, c, var, o),
+                        lambda p, n, t, r, c, o, s: lib.ss_cmvn_packed_device(p, n, t, r, c, var, o, s))
+
+
+def cmvnw_packed(vec, offsets, win_size=301, variance_normalization=False):
+    """``cmvnw`` of every clip of a packed block on its own rows: the symmetric padding reflects at the clip's own first and last
+    row.  See cmvn_packed."""
+    lib, var, w = _lib.lib(), int(bool(variance_normalization)), int(win_size)
+    return _post_packed(vec, offsets, None, "cmvnw_packed", lambda p, n, t, r, c, o: lib.ss_cmvnw_packed(p, n, t, r, c, w, var, o),
+                        lambda p, n, t, r, c, o, s: lib.ss_cmvnw_packed_device(p, n, t, r, c, w, var, o, s))
+
+
+def power_to_db_packed(S, offsets, cols=None, ref=1.0, amin=1e-10, top_db=80.0):
+    """``power_to_db`` of every clip of a packed block with the clip's own ``top_db`` floor.  Clip b's segment is elements
+    cols * offsets[b] : cols * offsets[b + 1]: a [sum T_b, cols] block (cols defaults to its width), or the flat block of
+    ``mel_spectrogram_packed`` with cols = num_filters and its row offsets.  See cmvn_packed."""
+    lib = _lib.lib()
+    if top_db is not None and top_db < 0:
+        raise ValueError("top_db must be non-negative")
+    td, rf, am = -1.0 if top_db is None else float(top_db), float(ref), float(amin)
+    return _post_packed(S, offsets, cols, "power_to_db_packed",
+                        lambda p, n, t, r, c, o: lib.ss_power_to_db_packed(p, n, t, r, c, rf, am, td, o),
+                        lambda p, n, t, r, c, o, s: lib.ss_power_to_db_packed_device(p, n, t, r, c, rf, am, td, o, s))
