@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SS_ABI_VERSION 7 /* 7: ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region, the packed post-processing calls (ss_cmvn_packed*, ss_cmvnw_packed*, ss_power_to_db_packed*, ss_lmfe_packed*); 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
+#define SS_ABI_VERSION 7 /* 7: the ragged streaming calls over a pool of stream states (ss_frame_stream_packed_row_offsets, ss_mfcc_stream_packed*, ss_mfe_stream_packed*), ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region, the packed post-processing calls (ss_cmvn_packed*, ss_cmvnw_packed*, ss_power_to_db_packed*, ss_lmfe_packed*); 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
 
 typedef enum ss_status {
     SS_OK = 0,
@@ -361,6 +361,61 @@ int ss_mfcc_stream_device(const ss_config *cfg, const float *d_x, size_t n_strea
                           float *d_state, float *d_out, void *stream);
 int ss_mfe_stream_device(const ss_config *cfg, const float *d_x, size_t n_streams, size_t n_samples, size_t ld, float *d_state,
                          float *d_feat, float *d_energy, void *stream);
+
+/* ---- ragged streaming MFCC / mfe over a pool of stream states ----
+ * The streaming calls above take a dense chunk block: every stream of the state block takes part, each with the same number of
+ * hops.  A server holds a pool of open streams of which, in any tick, only some have new audio, and those a hop count of their
+ * own.  These entry points serve such a tick in one call.
+ *   Pool: a caller-owned block [pool_streams x S] of floats, S = ss_frame_stream_state_len -- the state block of the calls above,
+ *   row for row (all zeros = fresh stream, zeroing a row resets it; S == 0 allows a NULL pool).
+ *   Entries: a call serves n_active entries.  Entry i's chunk is x[so[i] : so[i+1]] of one packed buffer (so: n_active + 1
+ *   non-decreasing int64 sample offsets, so[0] = 0, as ss_mfcc_packed); its length n_i is a whole number of hops R_i = n_i / step,
+ *   and R_i = 0 is legal: no rows, the state row untouched (a captured graph of fixed n_active serves a changing set of streams
+ *   that way).  Its state is pool row slots[i] (int32, 0 <= slots[i] < pool_streams, distinct within a call).  Its rows are rows
+ *   ro[i] .. ro[i+1] of the packed outputs (ro: n_active + 1 row offsets, ro[0] = 0, ro[i+1] - ro[i] = R_i; from
+ *   ss_frame_stream_packed_row_offsets or computed by the caller on the device): MFCC [total_rows x num_cepstral]; mfe feat
+ *   [total_rows x num_filters], energy [total_rows].  total_rows is the rows the outputs hold (>= ro[n_active]; rows past it are
+ *   left alone).
+ *   Equivalence: per entry the rows, and the pool row afterwards, are what ss_mfcc_stream_device / ss_mfe_stream_device give for
+ *   that stream alone (n_streams = 1, that chunk, that state row, the same norm_frames), bit for bit, wherever the entry stands in
+ *   the call.  Everything the dense streaming contract says carries over: the per-frame stages, pre-emphasis reading zeros / the
+ *   state and never wrapping, norm_frames, no [0,0] factor, contract and padded framing alike, literal / centred framing
+ *   SS_ERR_BAD_CONFIG.  Pool rows not named in `slots` are neither read nor written.
+ *   Kernels: the default 512-point MFCC / mfe shape runs on the ragged streaming builds of the dedicated kernel, reported by
+ *   ss_last_kernel_name() as ss_mfcc_c256sp<10,exact,bank421,sym> / ss_mfcc_c256sp<10,exact,bank421,mfe>; every other
+ *   configuration the dense generic streaming build serves runs on ss_front_generic_fstreamp<LOG2C[,chirpz]>.  A second
+ *   stream-ordered launch (ss_stream_advance_packed) moves the named pool rows on; it is skipped where S == 0.  The device forms
+ *   are a linear chain of these two launches whose grids depend on n_active and total_rows only: capturable, and replayable with
+ *   other table contents.
+ *   Containment: the device forms never see the tables on the host.  Both kernels decode every entry with one shared function; an
+ *   entry is skipped -- no row written, its pool row untouched -- unless so[i] >= 0, 0 <= n_i <= 2^31 - 1, n_i % step == 0,
+ *   ro[i] >= 0, ro[i+1] - ro[i] == n_i / step, ro[i+1] <= total_rows and 0 <= slots[i] < pool_streams.  Whatever the tables hold,
+ *   nothing is read or written outside x's entry ranges, rows [0, total_rows) of the outputs and rows [0, pool_streams) of the
+ *   pool.  A skipped entry raises the config's device error word: the call itself returns SS_OK, the next call on the config (or
+ *   ss_config_device_status) returns SS_ERR_DEVICE once.
+ *   Duplicate slots in a device-form call are a caller error that is NOT detected: the rows and the pool rows of the entries
+ *   that share a slot are unspecified; everything stays inside the pool.  The host-pointer forms reject them.
+ * Arguments: n_active == 0 is SS_OK with nothing launched.  SS_ERR_ARG, pool and outputs untouched: null buffers (the pool may be
+ * NULL iff S == 0), n_active, pool_streams or total_rows >= 2^31, norm_frames == 0 with SS_DCT_REFERENCE, a pool range that
+ * overlaps an output.  The host-pointer forms also check the tables before they touch the device -- so[0] != 0, a decreasing
+ * pair, a chunk that is not whole hops, a slot outside the pool, a slot named twice; ss_last_error_string() names the first bad
+ * entry -- and move only what the call touches: x, the tables and the n_active named pool rows up, the outputs and those rows
+ * down; the caller's pool is written only after everything before it succeeded. */
+/* host only, no device: ro[0] = 0, ro[i+1] = ro[i] + (so[i+1] - so[i]) / step.  SS_ERR_ARG: so[0] != 0, a decreasing pair, a chunk
+ * that is not whole hops or longer than 2^31 - 1 samples; SS_ERR_BAD_CONFIG for literal / centred framing */
+int ss_frame_stream_packed_row_offsets(const ss_params *p, size_t n_active, const int64_t *sample_offsets, int64_t *row_offsets);
+/* device pointers, asynchronous on `stream`, graph-capturable: a linear chain of two launches (the rows, then the pool advance) */
+int ss_mfcc_stream_packed_device(const ss_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                 const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                 uint32_t norm_frames, float *d_pool, float *d_out, void *stream);
+int ss_mfe_stream_packed_device(const ss_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                float *d_pool, float *d_feat, float *d_energy, void *stream);
+/* host pointers, synchronous; the tables are host arrays; out: [ro[n_active] x num_cepstral] (feat / energy likewise) */
+int ss_mfcc_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets,
+                          const int32_t *slots, size_t pool_streams, uint32_t norm_frames, float *pool, float *out);
+int ss_mfe_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets,
+                         const int32_t *slots, size_t pool_streams, float *pool, float *feat, float *energy);
 
 /* ss_stack_frames_signal on device pointers (d_window: frame_len floats in device memory, or NULL) */
 int ss_stack_frames_signal_device(const float *d_x, size_t n_samples, uint32_t sample_rate, float frame_length, float frame_stride,

@@ -14,6 +14,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_set>
 #include <vector>
 
 #include "ss_device.h"
@@ -857,6 +858,73 @@ int stream_host(const ss_config *cfg, int out_kind, int mode, const float *x, si
     return rc;
 }
 
+// The argument block of a streaming MFCC / mfe launch without its shape (ld / n_samples / batch / n_frames: the caller's), shared by
+// the dense and the ragged (pool) form: the same configuration gives the same block, so the same bits per frame.
+ss::FrontArgs frame_stream_front_args(const ss_config *cfg, int out_kind, const float *d_x, uint32_t norm_frames, float *out0, float *out1)
+{
+    const ss::HostTables &h = cfg->host;
+    ss::FrontArgs a{};
+    fill_common(cfg, a);
+    a.x = d_x;
+    a.flen = h.d.flen;
+    a.step = h.d.step;
+    a.frame_mode = ss::FRAME_NORMAL;  // every row's frame ends inside the chunk: contract and padded framing agree
+    a.pad_reflect = h.params.pad_mode == SS_PAD_REFLECT;
+    a.preemph = h.params.preemph_coef;
+    a.preemph_shift = static_cast<uint32_t>(h.params.preemph_shift > 0 ? h.params.preemph_shift : 1);
+    a.window = cfg->d_window_mfcc;
+    a.scale = 1.0f / static_cast<float>(h.params.fft_points);  // processing.rs:180
+    // the scales of launch_frames with T = norm_frames; a stream has no first frame, so [0,0] gets column 0's scale
+    const float g = h.params.dct2_gain;
+    const float M = static_cast<float>(h.params.num_filters);
+    if (h.params.dct_norm == SS_DCT_ORTHO) {
+        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * M));
+        a.dct_scale_0 = a.dct_scale_00 = g * (1.0f / sqrtf(4.0f * M));
+    } else {
+        const float nn = static_cast<float>(static_cast<size_t>(norm_frames > 0 ? norm_frames : 1u) * h.params.num_filters);
+        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * nn));
+        a.dct_scale_0 = a.dct_scale_00 = g;
+    }
+    a.out_kind = out_kind;
+    a.out0 = out0;
+    a.out1 = out1;
+    return a;
+}
+// whether the streaming builds of the 512-point headline kernel are candidates for the configuration (their launchers decide)
+bool frame_stream_fast_candidate(const ss_config *cfg, const ss::FrontArgs &a)
+{
+    return !ss::dbg_force_generic() && cfg->fast.ok && !cfg->fast.fullp && a.window == nullptr && a.preemph == 0.0f &&
+           cfg->host.params.dct_norm != SS_DCT_ORTHO;
+}
+// ... and their argument block, from the generic one
+ss::Fast512Args frame_stream_fast_args(const ss_config *cfg, const ss::FrontArgs &a)
+{
+    ss::Fast512Args f{};
+    f.x = a.x;
+    f.ld = a.ld;
+    f.n_samples = a.n_samples;
+    f.batch = a.batch;
+    f.flen = a.flen;
+    f.step = a.step;
+    f.n_frames = a.n_frames;
+    f.scale = a.scale;
+    f.spectrum_exponent = a.spectrum_exponent;
+    f.tab = cfg->d_fast_tab;
+    f.mel_wpitch = cfg->fast.wpitch;
+    for (int s = 0; s < 3; ++s) f.mel_q4[s] = cfg->fast.q4[s];
+    f.n_filters = a.n_filters;
+    f.n_ceps = a.n_ceps;
+    f.dct_scale_k = a.dct_scale_k;
+    f.dct_scale_0 = a.dct_scale_0;
+    f.dct_scale_00 = a.dct_scale_00;
+    f.dc_elimination = a.dc_elimination;
+    f.out = a.out0;
+    f.out_energy = a.out1;
+    f.out_mfe = a.out_kind == ss::OUT_MFE ? 1 : 0;
+    f.paired = cfg->fast.paired ? (cfg->fast.tight ? 2 : 1) : 0;
+    return f;
+}
+
 // Streaming MFCC / mfe launch (ss_mfcc_stream_device / ss_mfe_stream_device): the rows of one call over a carried state per
 // stream, then the state advance -- two kernels on `stream` (none for the advance where S == 0).  Candidate order: the streaming
 // build of the 512-point headline kernel where it has one for the shape, else the streaming build of the generic kernel.
@@ -889,62 +957,16 @@ int launch_frame_stream(const ss_config *cfg, int out_kind, const float *d_x, si
         const int erc = pending_device_error(cfg);
         if (erc) return erc;
     }
-    ss::FrontArgs a{};
-    fill_common(cfg, a);
-    a.x = d_x;
+    ss::FrontArgs a = frame_stream_front_args(cfg, out_kind, d_x, norm_frames, out0, out1);
     a.ld = ld;
     a.n_samples = static_cast<uint32_t>(n);
     a.batch = static_cast<uint32_t>(n_streams);
-    a.flen = h.d.flen;
-    a.step = h.d.step;
     a.n_frames = static_cast<uint32_t>(R);
-    a.frame_mode = ss::FRAME_NORMAL;  // every row's frame ends inside the chunk: contract and padded framing agree
-    a.pad_reflect = h.params.pad_mode == SS_PAD_REFLECT;
-    a.preemph = h.params.preemph_coef;
-    a.preemph_shift = static_cast<uint32_t>(h.params.preemph_shift > 0 ? h.params.preemph_shift : 1);
-    a.window = cfg->d_window_mfcc;
-    a.scale = 1.0f / static_cast<float>(h.params.fft_points);  // processing.rs:180
-    // the scales of launch_frames with T = norm_frames; a stream has no first frame, so [0,0] gets column 0's scale
-    const float g = h.params.dct2_gain;
-    const float M = static_cast<float>(h.params.num_filters);
-    if (ortho) {
-        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * M));
-        a.dct_scale_0 = a.dct_scale_00 = g * (1.0f / sqrtf(4.0f * M));
-    } else {
-        const float nn = static_cast<float>(static_cast<size_t>(norm_frames > 0 ? norm_frames : 1u) * h.params.num_filters);
-        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * nn));
-        a.dct_scale_0 = a.dct_scale_00 = g;
-    }
-    a.out_kind = out_kind;
-    a.out0 = out0;
-    a.out1 = out1;
     ss::FrameStreamArgs fsa{d_state, static_cast<uint32_t>(S), static_cast<int32_t>(h.d.flen) - static_cast<int32_t>(h.d.step)};
     ss::LaunchInfo info{};
     hipError_t e = hipErrorInvalidValue;
-    if (!ss::dbg_force_generic() && cfg->fast.ok && !cfg->fast.fullp && a.window == nullptr && a.preemph == 0.0f && !ortho) {
-        ss::Fast512Args f{};
-        f.x = d_x;
-        f.ld = ld;
-        f.n_samples = a.n_samples;
-        f.batch = a.batch;
-        f.flen = a.flen;
-        f.step = a.step;
-        f.n_frames = a.n_frames;
-        f.scale = a.scale;
-        f.spectrum_exponent = a.spectrum_exponent;
-        f.tab = cfg->d_fast_tab;
-        f.mel_wpitch = cfg->fast.wpitch;
-        for (int s = 0; s < 3; ++s) f.mel_q4[s] = cfg->fast.q4[s];
-        f.n_filters = a.n_filters;
-        f.n_ceps = a.n_ceps;
-        f.dct_scale_k = a.dct_scale_k;
-        f.dct_scale_0 = a.dct_scale_0;
-        f.dct_scale_00 = a.dct_scale_00;
-        f.dc_elimination = a.dc_elimination;
-        f.out = out0;
-        f.out_energy = out1;
-        f.out_mfe = out_kind == ss::OUT_MFE ? 1 : 0;
-        f.paired = cfg->fast.paired ? (cfg->fast.tight ? 2 : 1) : 0;
+    if (frame_stream_fast_candidate(cfg, a)) {
+        const ss::Fast512Args f = frame_stream_fast_args(cfg, a);
         e = ss::launch_mfcc_c256_stream(f, fsa, stream, cfg->num_cus, &info);
         // hipErrorInvalidValue before the launch: the configuration has no streaming build of this kernel -> the generic build
         if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mfcc_c256_stream");
@@ -1012,6 +1034,154 @@ int frame_stream_host(const ss_config *cfg, int out_kind, const float *x, size_t
         e = hipMemcpyAsync(state, ds.p, sbytes, hipMemcpyDeviceToHost, st);
         const hipError_t es = hipStreamSynchronize(st);
         if (e != hipSuccess || es != hipSuccess) rc = hip_fail(e != hipSuccess ? e : es, "hipMemcpyAsync (state D2H)");
+    }
+    return rc;
+}
+
+// Ragged streaming MFCC / mfe over a pool of stream states (ss_mfcc_stream_packed_device / ss_mfe_stream_packed_device): the rows of
+// n_active entries of different hop counts, each over the pool row its slot names, then the advance of the named rows -- a linear
+// chain of two kernels on `stream` (none for the advance where S == 0).  The tables are device arrays read by the kernels only
+// (FrameStreamPackedArgs, ss_device.h); the grids come from n_active and total_rows.  Candidate order as launch_frame_stream.
+int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n_active, const int64_t *d_so, const int64_t *d_ro,
+                               size_t total_rows, const int32_t *d_slots, size_t pool_streams, uint32_t norm_frames, float *d_pool,
+                               float *out0, float *out1, hipStream_t stream)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_active == 0) return SS_OK;
+    const ss::HostTables &h = cfg->host;
+    size_t S = 0;
+    int rc = ss_frame_stream_state_len(&h.params, &S);
+    if (rc) return rc;
+    if (!d_x || !d_so || !d_ro || !d_slots || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !d_pool))
+        return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull || total_rows >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
+    if (out_kind == ss::OUT_MFCC && h.params.dct_norm != SS_DCT_ORTHO && norm_frames == 0)
+        return ss::fail(SS_ERR_ARG, "norm_frames must be >= 1: the reference DCT scaling needs a frame count");
+    const size_t cols = out_kind == ss::OUT_MFCC ? h.params.num_cepstral : h.params.num_filters;
+    const size_t pbytes = pool_streams * S * sizeof(float);
+    if (S > 0 && (ranges_overlap(d_pool, pbytes, out0, total_rows * cols * sizeof(float)) ||
+                  (out1 && ranges_overlap(d_pool, pbytes, out1, total_rows * sizeof(float)))))
+        return ss::fail(SS_ERR_ARG, "the pool overlaps an output");
+    {
+        const int drc = check_device(cfg);  // see launch_frames
+        if (drc) return drc;
+        const int erc = pending_device_error(cfg);
+        if (erc) return erc;
+    }
+    const ss::FrontArgs a = frame_stream_front_args(cfg, out_kind, d_x, norm_frames, out0, out1);
+    ss::FrameStreamPackedArgs fsp{};
+    fsp.pool = d_pool;
+    fsp.state_len = static_cast<uint32_t>(S);
+    fsp.lead = static_cast<int32_t>(h.d.flen) - static_cast<int32_t>(h.d.step);
+    fsp.so = reinterpret_cast<const long long *>(d_so);
+    fsp.ro = reinterpret_cast<const long long *>(d_ro);
+    fsp.slots = d_slots;
+    fsp.n_active = static_cast<uint32_t>(n_active);
+    fsp.pool_streams = static_cast<uint32_t>(pool_streams);
+    fsp.total_rows = static_cast<uint32_t>(total_rows);
+    fsp.step = h.d.step;
+    fsp.err = cfg->d_err;
+    ss::LaunchInfo info{};
+    hipError_t e = hipErrorInvalidValue;
+    if (frame_stream_fast_candidate(cfg, a)) {
+        const ss::Fast512Args f = frame_stream_fast_args(cfg, a);
+        e = ss::launch_mfcc_c256_stream_packed(f, fsp, stream, cfg->num_cus, &info);
+        // hipErrorInvalidValue before the launch: the configuration has no ragged streaming build of this kernel -> the generic build
+        if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mfcc_c256_stream_packed");
+    }
+    if (e != hipSuccess) {
+        e = ss::launch_front_generic_frame_stream_packed(a, fsp, h.d.log2c, stream, cfg->num_cus, &info);
+        if (e != hipSuccess) return hip_fail(e, "launch_front_generic_frame_stream_packed");
+    }
+    g_last_kernel = info.kernel_name;
+    e = ss::launch_stream_advance_packed(fsp, d_x, stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_stream_advance_packed");
+    return SS_OK;
+}
+
+// Host-pointer form: the tables are checked here, before anything touches the device; then x, the tables and the n_active named
+// pool rows (gathered into a compact block whose row i is entry i's: the device call runs on slots 0 .. n_active - 1) go up, the
+// outputs and the named rows come down on the config's first host-pipeline stream.  The caller's pool is written only once
+// everything before it succeeded.
+int frame_stream_packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_active, const int64_t *so, const int32_t *slots,
+                             size_t pool_streams, uint32_t norm_frames, float *pool, float *out0, float *out1)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_active == 0) return SS_OK;
+    const ss::HostTables &h = cfg->host;
+    size_t S = 0;
+    int rc = ss_frame_stream_state_len(&h.params, &S);
+    if (rc) return rc;
+    if (!x || !so || !slots || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !pool)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (out_kind == ss::OUT_MFCC && h.params.dct_norm != SS_DCT_ORTHO && norm_frames == 0)
+        return ss::fail(SS_ERR_ARG, "norm_frames must be >= 1: the reference DCT scaling needs a frame count");
+    std::vector<int64_t> ro(n_active + 1);
+    if ((rc = ss_frame_stream_packed_row_offsets(&h.params, n_active, so, ro.data()))) return rc;
+    {
+        std::unordered_set<int32_t> seen;
+        seen.reserve(n_active);
+        for (size_t i = 0; i < n_active; ++i) {
+            if (slots[i] < 0 || static_cast<size_t>(slots[i]) >= pool_streams)
+                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is outside the pool of " +
+                                                std::to_string(pool_streams) + " rows");
+            if (!seen.insert(slots[i]).second)
+                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is named twice in one call");
+        }
+    }
+    const size_t rows = static_cast<size_t>(ro[n_active]), samples = static_cast<size_t>(so[n_active]);
+    if (rows >= 0x80000000ull) return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    const size_t cols = out_kind == ss::OUT_MFCC ? h.params.num_cepstral : h.params.num_filters;
+    if ((rc = check_device(cfg))) return rc;
+    // the named pool rows, row i = entry i's
+    std::vector<float> rows_host(n_active * S);
+    std::vector<int32_t> iota(n_active);
+    for (size_t i = 0; i < n_active; ++i) {
+        iota[i] = static_cast<int32_t>(i);
+        if (S > 0) std::memcpy(rows_host.data() + i * S, pool + static_cast<size_t>(slots[i]) * S, S * sizeof(float));
+    }
+    ss_config::HostPipe &hp = cfg->pipe;
+    std::lock_guard<std::mutex> lock(hp.mu);
+    if (!hp.stream[0]) {
+        SS_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
+        SS_HIP(hipEventCreateWithFlags(&hp.done[0], hipEventDisableTiming));
+    }
+    hipStream_t st = hp.stream[0];
+    const size_t tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * S * sizeof(float);
+    DeviceBuf dx, dso, dro, dsl, dp, d0, d1;
+    if ((rc = dx.alloc(samples * sizeof(float))) || (rc = dso.alloc(tbytes)) || (rc = dro.alloc(tbytes)) ||
+        (rc = dsl.alloc(n_active * sizeof(int32_t))) || (S > 0 && (rc = dp.alloc(sbytes))) || (rc = d0.alloc(rows * cols * sizeof(float))) ||
+        (out1 && (rc = d1.alloc(rows * sizeof(float)))))
+        return rc;
+    hipError_t e = samples ? hipMemcpyAsync(dx.p, x, samples * sizeof(float), hipMemcpyHostToDevice, st) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, tbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dro.p, ro.data(), tbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dsl.p, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && S > 0) e = hipMemcpyAsync(dp.p, rows_host.data(), sbytes, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
+    if (rc == SS_OK)
+        rc = launch_frame_stream_packed(cfg, out_kind, dx.as<const float>(), n_active, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
+                                        dsl.as<const int32_t>(), n_active, norm_frames, S > 0 ? dp.as<float>() : nullptr, d0.as<float>(),
+                                        out1 ? d1.as<float>() : nullptr, st);
+    if (rc == SS_OK && rows > 0) {
+        e = hipMemcpyAsync(out0, d0.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && out1) e = hipMemcpyAsync(out1, d1.p, rows * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (D2H)");
+    }
+    // the copies may still touch the caller's buffers and ours: synchronise whatever happened
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "frame stream pool host call");
+    if (rc == SS_OK) rc = pending_device_error(cfg);
+    if (rc == SS_OK && S > 0) {
+        e = hipMemcpyAsync(rows_host.data(), dp.p, sbytes, hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e != hipSuccess || es != hipSuccess) rc = hip_fail(e != hipSuccess ? e : es, "hipMemcpyAsync (pool rows D2H)");
+        if (rc == SS_OK)
+            for (size_t i = 0; i < n_active; ++i)
+                std::memcpy(pool + static_cast<size_t>(slots[i]) * S, rows_host.data() + i * S, S * sizeof(float));
     }
     return rc;
 }
@@ -2277,6 +2447,34 @@ int ss_mfe_stream(const ss_config *cfg, const float *x, size_t n_streams, size_t
                   float *energy)
 {
     return frame_stream_host(cfg, ss::OUT_MFE, x, n_streams, n_samples, ld, 1u, state, feat, energy);
+}
+
+int ss_mfcc_stream_packed_device(const ss_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                 const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                 uint32_t norm_frames, float *d_pool, float *d_out, void *stream)
+{
+    return launch_frame_stream_packed(cfg, ss::OUT_MFCC, d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams,
+                                      norm_frames, d_pool, d_out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int ss_mfe_stream_packed_device(const ss_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                float *d_pool, float *d_feat, float *d_energy, void *stream)
+{
+    return launch_frame_stream_packed(cfg, ss::OUT_MFE, d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams, 1u,
+                                      d_pool, d_feat, d_energy, static_cast<hipStream_t>(stream));
+}
+
+int ss_mfcc_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                          size_t pool_streams, uint32_t norm_frames, float *pool, float *out)
+{
+    return frame_stream_packed_host(cfg, ss::OUT_MFCC, x, n_active, sample_offsets, slots, pool_streams, norm_frames, pool, out, nullptr);
+}
+
+int ss_mfe_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                         size_t pool_streams, float *pool, float *feat, float *energy)
+{
+    return frame_stream_packed_host(cfg, ss::OUT_MFE, x, n_active, sample_offsets, slots, pool_streams, 1u, pool, feat, energy);
 }
 
 int ss_preemphasis_device(const float *d_x, size_t n_samples, long shift, float cof, float *d_y, void *stream)

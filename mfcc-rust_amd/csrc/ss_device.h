@@ -287,6 +287,76 @@ struct FrameStreamArgs {
 // a as for launch_front_generic's MFCC path with n_frames = rows per stream, frame_mode FRAME_NORMAL and dct_scale_00 = dct_scale_0
 hipError_t launch_front_generic_frame_stream(const FrontArgs &a, const FrameStreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
                                              LaunchInfo *info);
+
+// Ragged streaming MFCC / mfe over a pool of stream states (ss_mfcc_stream_packed_device / ss_mfe_stream_packed_device): entry i of
+// a call is the chunk x[so[i] : so[i+1]] (R_i = n_i / step whole hops, R_i = 0 allowed) of the stream whose state is row slots[i] of
+// the pool; its rows are rows ro[i] .. ro[i+1] of the packed output.  Row t of an entry reads as row t of a dense streaming call on
+// that stream alone (FrameStreamArgs above): sample p < 0 is pool[slots[i] * S + S + p].  The three tables are device arrays the
+// host may never have seen (and may change between graph replays), so both kernels decode every entry with stream_entry() and
+// skip -- and report through `err` -- one that is inconsistent.
+struct FrameStreamPackedArgs {
+    float *pool;             // [pool_streams][state_len]; null where state_len == 0
+    uint32_t state_len;      // S
+    int32_t lead;            // flen - step (negative where frames are shorter than the hop)
+    const long long *so;     // [n_active + 1] sample offsets
+    const long long *ro;     // [n_active + 1] row offsets
+    const int32_t *slots;    // [n_active] pool row of each entry
+    uint32_t n_active;
+    uint32_t pool_streams;
+    uint32_t total_rows;     // rows of the output block
+    uint32_t step;
+    unsigned *err;           // the config's device error word (set to kVarlenError on a bad entry)
+};
+// Entry i of a ragged streaming launch: where its chunk starts, its length, its rows, its first output row and its pool row.
+// ok: the chunk is whole hops, rows ro[i] .. ro[i+1] are exactly its R_i rows inside the output block, and the slot names a pool
+// row.  The rows kernels and ss_stream_advance_packed both decide by this one function which entries they skip.
+struct StreamEntry {
+    long long s0, r0;
+    unsigned n, R, slot;
+    bool ok;
+};
+__device__ __forceinline__ StreamEntry stream_entry(const FrameStreamPackedArgs &v, unsigned i)
+{
+    StreamEntry e;
+    e.s0 = v.so[i];
+    e.r0 = v.ro[i];
+    const long long s1 = v.so[i + 1], r1 = v.ro[i + 1];
+    const int slot = v.slots[i];
+    const bool len_ok = e.s0 >= 0 && s1 >= e.s0 && s1 - e.s0 <= 0x7fffffffll;
+    e.n = len_ok ? static_cast<unsigned>(s1 - e.s0) : 0u;
+    e.R = e.n / v.step;
+    e.slot = static_cast<unsigned>(slot);
+    e.ok = len_ok && e.R * v.step == e.n && e.r0 >= 0 && r1 >= e.r0 && r1 - e.r0 == static_cast<long long>(e.R) &&
+           r1 <= static_cast<long long>(v.total_rows) && slot >= 0 && e.slot < v.pool_streams;
+    return e;
+}
+// The entry that owns packed row g: the last i < n_active with ro[i] <= g (binary search as varlen_find; entries without rows
+// share their ro with their successor and are stepped over, and the caller still checks g < ro[i + 1])
+__device__ __forceinline__ unsigned stream_entry_find(const FrameStreamPackedArgs &v, unsigned g)
+{
+    unsigned lo = 0u, hi = v.n_active;
+    const long long gs = static_cast<long long>(g);
+    while (hi - lo > 1u) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (v.ro[mid] <= gs) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// One pass over the entries, spread over the grid (see varlen_check_clips).  A vector store to the pinned word.
+__device__ __forceinline__ void stream_check_entries(const FrameStreamPackedArgs &v, unsigned tid, unsigned nthreads)
+{
+    bool bad = false;
+    for (unsigned i = tid; i < v.n_active; i += nthreads) bad |= !stream_entry(v, i).ok;
+    if (bad && v.err) __hip_atomic_store(v.err, kVarlenError, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// the ragged streaming build of ss_front_generic's MFCC / mfe path: a as for launch_front_generic_frame_stream with x = the packed
+// chunks; batch / n_samples / n_frames / ld are unused.  The grid comes from s.total_rows (one workgroup where it is 0: the entry pass).
+hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const FrameStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
+                                                    int num_cus, LaunchInfo *info);
+// The pool's state advance, a second stream-ordered launch behind the rows: for every ok entry with n_i > 0, pool row slots[i] := the
+// last S samples of (old row ++ the entry's chunk), in place (ss_stream_advance's discipline).  Grid-stride over the entries.
+hipError_t launch_stream_advance_packed(const FrameStreamPackedArgs &s, const float *x, hipStream_t stream);
 #if SS_LAB
 // Test aid (lab library): every word of every CU's LDS := 0xFFFFFFFF (ss_debug_poison_lds).
 hipError_t launch_poison_lds(hipStream_t stream, int num_cus);
@@ -372,6 +442,11 @@ hipError_t launch_mfcc_c256_varlen(const Fast512Args &a, const VarlenArgs &v, hi
 // or mfe of the default bank, no window, no pre-emphasis, reference DCT scales with dct_scale_00 = dct_scale_0.
 // hipErrorInvalidValue before the launch for every other configuration.
 hipError_t launch_mfcc_c256_stream(const Fast512Args &a, const FrameStreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info);
+// Ragged streaming MFCC / mfe on the headline build (FrameStreamPackedArgs, declared above): the shapes launch_mfcc_c256_stream
+// serves, with a.x = the packed chunks (batch / n_samples / n_frames / ld unused) and the quad range over s.total_rows.
+// hipErrorInvalidValue before the launch for every other configuration.
+hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a, const FrameStreamPackedArgs &s, hipStream_t stream, int num_cus,
+                                          LaunchInfo *info);
 // whether the kernel has an mfe-output / windowed / pre-emphasised build for this shape (the default bank at flen 320)
 bool mfcc_c256_has_mfe(const Fast512Args &a);
 

@@ -8,6 +8,9 @@
 // per stream (StreamArgs, ss_device.h); ss_stream_advance moves the state on behind it.
 // ss_front_generic<LOG2C, BLU, FrameStreamArgs> (reported as ss_front_generic_fstream<LOG2C>): the MFCC / mfe path with a carried
 // state per stream (FrameStreamArgs, ss_device.h): frames and pre-emphasis taps before the chunk read the stream's state.
+// ss_front_generic<LOG2C, BLU, FrameStreamPackedArgs> (reported as ss_front_generic_fstreamp<LOG2C>): the same over a pool of stream
+// states -- packed chunks of different hop counts, each on the pool row its entry names (FrameStreamPackedArgs, ss_device.h);
+// ss_stream_advance_packed moves the named pool rows on behind it.
 // ss_front_generic<LOG2C, BLU, VarRowsArgs> (reported as ss_front_generic_varrows<LOG2C>): the STFT / mel path over packed clips of
 // different lengths (VarRowsArgs, ss_device.h), handed out in tiles of packed rows.
 //
@@ -242,21 +245,25 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
 // STREAM: the STFT / mel path of launch_front_generic_stream -- a window sample before the chunk comes from the stream's state.
 // FSTREAM: the MFCC / mfe path of launch_front_generic_frame_stream -- clip = stream, frame = row of this call; row t starts at chunk
 // sample t * step - lead, and a frame sample or pre-emphasis tap before the chunk comes from the stream's state (no circular wrap).
+// FSP: FSTREAM over a pool of states (launch_front_generic_frame_stream_packed) -- the flat frame index is the packed output row, and
+// the row's entry (its chunk, its row within the chunk, its pool row) comes from the device tables (FrameStreamPackedArgs).
 // VARR: the STFT / mel path of launch_front_generic_varrows -- a workgroup visit is a tile of packed rows, every row finds its own
 // clip; the transposed mel flush writes each row into its clip's [M x R_b] block.
-// (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs or one VarRowsArgs -- an empty pack leaves the argument block of the
+// (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs, one FrameStreamPackedArgs or one VarRowsArgs -- an empty pack leaves the argument block of the
 // equal-length builds exactly as it was)
 template <int LOG2C, bool BLU, typename... V>
 __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
 {
     constexpr bool VAR = (std::is_same_v<V, VarlenArgs> || ...);
     constexpr bool STREAM = (std::is_same_v<V, StreamArgs> || ...);
-    constexpr bool FSTREAM = (std::is_same_v<V, FrameStreamArgs> || ...);
+    constexpr bool FSP = (std::is_same_v<V, FrameStreamPackedArgs> || ...);
+    constexpr bool FSTREAM = FSP || (std::is_same_v<V, FrameStreamArgs> || ...);
     constexpr bool VARR = (std::is_same_v<V, VarRowsArgs> || ...);
     [[maybe_unused]] const VarRowsArgs *ra = pack_arg<VarRowsArgs>(vargs...);
     [[maybe_unused]] const VarlenArgs *va = pack_arg<VarlenArgs>(vargs...);
     [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(vargs...);
     [[maybe_unused]] const FrameStreamArgs *fa = pack_arg<FrameStreamArgs>(vargs...);
+    [[maybe_unused]] const FrameStreamPackedArgs *fp = pack_arg<FrameStreamPackedArgs>(vargs...);
     using G = Geo<LOG2C>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
@@ -281,7 +288,10 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     if (!mel_mode) {
         // ---------------- MFCC / MFE / power-spectrum path: flat list of B*T frames ----------------
         if constexpr (VAR) varlen_check_clips(*va, a.flen, a.step, blockIdx.x * kBlock + tid, gridDim.x * kBlock);
-        const unsigned long long total = VAR ? va->total_frames : static_cast<unsigned long long>(a.batch) * a.n_frames;
+        if constexpr (FSP) stream_check_entries(*fp, blockIdx.x * kBlock + tid, gridDim.x * kBlock);
+        unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
+        if constexpr (VAR) total = va->total_frames;
+        if constexpr (FSP) total = fp->total_rows;
         const unsigned long long groups = (total + G::FPB - 1) / G::FPB;
         for (unsigned long long g = blockIdx.x; g < groups; g += gridDim.x) {
             const unsigned long long gf = g * G::FPB + slot;
@@ -302,6 +312,14 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 // processing.rs:110-120 as written, with the clip's own frame count
                 if (va->framing == SS_FRAMING_LITERAL) frame_mode = c.T > 2u ? FRAME_ZERO : FRAME_FIRST;
                 if (!va->dct_ortho) varlen_dct_scales(*va, c.T, a.n_filters, dct_scale_k, dct_scale_00);
+            } else if constexpr (FSP) {
+                // rows past the last entry (a larger output block) are left alone; rows of an inconsistent entry are skipped
+                const unsigned g32 = static_cast<unsigned>(gf);
+                const StreamEntry en = stream_entry(*fp, active ? stream_entry_find(*fp, g32) : 0u);
+                active = active && en.ok && static_cast<long long>(gf) >= en.r0 && static_cast<long long>(gf) - en.r0 < static_cast<long long>(en.R);
+                t = active ? static_cast<unsigned>(static_cast<long long>(gf) - en.r0) : 0u;
+                xc = a.x + (active ? en.s0 : 0ll);
+                if (active && fp->state_len) srow = fp->pool + static_cast<unsigned long long>(en.slot) * fp->state_len + fp->state_len;
             } else {
                 const unsigned gf32 = static_cast<unsigned>(gf);  // launch_one rejects batches with >= 2^32 frames
                 const unsigned clip = active ? gf32 / a.n_frames : 0u;
@@ -319,7 +337,10 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                     // the stream's samples s[p], p = t * step - lead + i, with zeros before its start (the zeroed state);
                     // pre-emphasis y[p] = s[p] - c s[p - sh] reaches back into the state, never round the chunk
                     if (active && i < a.flen) {
-                        const long long p = static_cast<long long>(t) * a.step - fa->lead + i;
+                        int lead;
+                        if constexpr (FSP) lead = fp->lead;
+                        else lead = fa->lead;
+                        const long long p = static_cast<long long>(t) * a.step - lead + i;
                         val = p < 0 ? srow[p] : xc[p];
                         if (a.preemph != 0.0f) {
                             const long long q = p - static_cast<long long>(a.preemph_shift);
@@ -695,6 +716,28 @@ hipError_t launch_one_fstream(const FrontArgs &a, const FrameStreamArgs &s, hipS
 }
 
 template <int LOG2C, bool BLU>
+hipError_t launch_one_fstreamp(const FrontArgs &a, const FrameStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info,
+                               const char *name)
+{
+    using G = Geo<LOG2C>;
+    const size_t lds = front_lds_bytes<LOG2C>(a);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, FrameStreamPackedArgs>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    // at least one workgroup: the entry pass runs even where the output block has no rows
+    unsigned long long work = (static_cast<unsigned long long>(s.total_rows) + G::FPB - 1) / G::FPB;
+    if (work == 0) work = 1;
+    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
+    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
+    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
+    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, FrameStreamPackedArgs>), dim3(grid), dim3(kBlock), lds, stream, a, s);
+    return hipGetLastError();
+}
+
+template <int LOG2C, bool BLU>
 hipError_t launch_one_stream(const FrontArgs &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info, const char *name)
 {
     const size_t lds = front_lds_bytes<LOG2C>(a);
@@ -732,6 +775,30 @@ __global__ __launch_bounds__(256) void ss_stream_advance(float *__restrict__ sta
             }
             __syncthreads();
             if (i < S) st[i] = v;
+        }
+    }
+}
+
+// The same over a pool of states (launch_stream_advance_packed): a workgroup per entry (grid-stride over the entries); an entry that
+// stream_entry() finds inconsistent, or that has no samples, leaves its pool row alone.  (The entry is uniform over the workgroup:
+// every lane reaches the barriers.)
+__global__ __launch_bounds__(256) void ss_stream_advance_packed(const FrameStreamPackedArgs v, const float *__restrict__ x)
+{
+    const unsigned S = v.state_len;
+    for (unsigned e = blockIdx.x; e < v.n_active; e += gridDim.x) {
+        const StreamEntry en = stream_entry(v, e);
+        if (!en.ok || en.n == 0u) continue;
+        float *st = v.pool + static_cast<unsigned long long>(en.slot) * S;
+        const float *xc = x + en.s0;
+        for (unsigned i0 = 0; i0 < S; i0 += 256) {
+            const unsigned i = i0 + threadIdx.x;
+            float val = 0.0f;
+            if (i < S) {
+                const unsigned long long k = static_cast<unsigned long long>(i) + en.n;  // index into old row ++ chunk
+                val = k < S ? st[k] : xc[k - S];  // (k - S < n: i < S)
+            }
+            __syncthreads();
+            if (i < S) st[i] = val;
         }
     }
 }
@@ -930,6 +997,48 @@ hipError_t launch_front_generic_frame_stream(const FrontArgs &a, const FrameStre
         case 12: return launch_one_fstream<12, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<12>");
         default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const FrameStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
+                                                    int num_cus, LaunchInfo *info)
+{
+    if (a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE) return hipErrorInvalidValue;
+    if (s.n_active == 0 || s.step == 0 || (s.state_len > 0 && !s.pool) || s.total_rows >= 0x7fffffffu) return hipErrorInvalidValue;
+    if (a.blu_n) {
+        switch (log2c) {
+            case 4: return launch_one_fstreamp<4, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<4,chirpz>");
+            case 5: return launch_one_fstreamp<5, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<5,chirpz>");
+            case 6: return launch_one_fstreamp<6, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<6,chirpz>");
+            case 7: return launch_one_fstreamp<7, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<7,chirpz>");
+            case 8: return launch_one_fstreamp<8, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<8,chirpz>");
+            case 9: return launch_one_fstreamp<9, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<9,chirpz>");
+            case 10: return launch_one_fstreamp<10, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<10,chirpz>");
+            case 11: return launch_one_fstreamp<11, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<11,chirpz>");
+            case 12: return launch_one_fstreamp<12, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<12,chirpz>");
+            default: return hipErrorInvalidValue;
+        }
+    }
+    switch (log2c) {
+        case 4: return launch_one_fstreamp<4, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<4>");
+        case 5: return launch_one_fstreamp<5, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<5>");
+        case 6: return launch_one_fstreamp<6, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<6>");
+        case 7: return launch_one_fstreamp<7, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<7>");
+        case 8: return launch_one_fstreamp<8, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<8>");
+        case 9: return launch_one_fstreamp<9, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<9>");
+        case 10: return launch_one_fstreamp<10, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<10>");
+        case 11: return launch_one_fstreamp<11, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<11>");
+        case 12: return launch_one_fstreamp<12, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<12>");
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_stream_advance_packed(const FrameStreamPackedArgs &s, const float *x, hipStream_t stream)
+{
+    if (s.n_active == 0 || s.state_len == 0) return hipSuccess;
+    if (!s.pool || s.step == 0) return hipErrorInvalidValue;
+    const unsigned grid = s.n_active < 65536u ? s.n_active : 65536u;
+    hipLaunchKernelGGL(ss_stream_advance_packed, dim3(grid), dim3(256), 0, stream, s, x);
+    return hipGetLastError();
 }
 
 hipError_t launch_stream_advance(float *state, uint32_t state_len, const float *x, unsigned long long ld, uint32_t n_samples,

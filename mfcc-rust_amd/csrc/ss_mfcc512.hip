@@ -260,6 +260,40 @@ __device__ __forceinline__ unsigned load_quad_stream(const Fast512Args &a, const
     return t;
 }
 
+// STRP builds (ss_mfcc_stream_packed_device): the frame of `quad` this lane computes is packed output row q4 + f of a ragged
+// streaming launch.  The entry of the quad's first row comes from one uniform binary search; a lane's row lies a few entries further
+// (a short walk, or its own search behind a run of entries without rows).  The row then loads as load_quad_stream's edge branch
+// does -- the tail of the entry's pool row, then the head of its chunk; every so[i] is a multiple of the even step, so sample pairs
+// stay whole -- and a lane whose entry stream_entry() finds inconsistent, or whose row lies past the last entry, loads nothing and
+// (ok = 0) stores nothing.
+template <int NE>
+__device__ __forceinline__ unsigned load_quad_stream_packed(const Fast512Args &a, const FrameStreamPackedArgs &s, unsigned quad, unsigned total,
+                                                            int f, int j, float2 (&vin)[NE], int &ok)
+{
+    const unsigned q4 = quad * 4;                                              // uniform
+    const unsigned g = q4 + min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last row redo it
+    unsigned c = stream_entry_find(s, q4);
+    for (int k = 0; k < 4 && c + 1 < s.n_active && s.ro[c + 1] <= static_cast<long long>(g); ++k) ++c;
+    if (c + 1 < s.n_active && s.ro[c + 1] <= static_cast<long long>(g)) c = stream_entry_find(s, g);
+    const StreamEntry en = stream_entry(s, c);
+    const long long tl = static_cast<long long>(g) - en.r0;
+    ok = en.ok && g < total && tl >= 0 && tl < static_cast<long long>(en.R);
+    const unsigned t = ok ? static_cast<unsigned>(tl) : 0u;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) vin[e] = make_float2(0.f, 0.f);
+    if (ok) {
+        const float *xc = a.x + en.s0;
+        const float *sr = s.pool + static_cast<unsigned long long>(en.slot) * s.state_len + s.state_len;  // sample p < 0 is sr[p]
+        const int s0 = static_cast<int>(t * a.step) - s.lead;  // (t * step < n_i < 2^31; the frame ends inside the chunk)
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int p = s0 + 2 * (j + 16 * e);
+            vin[e] = *reinterpret_cast<const float2 *>((p < 0 ? sr : xc) + p);
+        }
+    }
+    return t;
+}
+
 // Contract framing only: where this lane's frame of `quad` starts (frame t of its clip begins at sample t * step), and t.
 // `quad` is uniform: the clip / frame split of the quad's first frame, the clip's address and the frame's offset in it are scalar
 // work, and what a lane adds is a 32-bit byte offset (its frame within the quad, its sample pair, one conditional step into the
@@ -395,6 +429,8 @@ __device__ __forceinline__ float mel_slot_loop(const float4 *w4, const float *p,
 // STRM builds (ss_mfcc_stream_device): a trailing FrameStreamArgs (SP; an empty pack leaves the other builds' argument block and
 // code as they were); clips are streams, frames the rows of this call (load_quad_stream), and the DCT's [0,0] special case of a
 // clip's first frame is never taken (a stream has no first frame).
+// STRP builds (ss_mfcc_stream_packed_device): a trailing FrameStreamPackedArgs; the quad range covers the packed output rows of a
+// ragged streaming call (load_quad_stream_packed), otherwise as STRM.
 template <int NE, bool EXACT, bool POW2, int WAVES, bool BANK421, int NQ, int RES = 0, int OUTK = 0, int FRONT = 0, bool FULLP = false,
           bool CENTER = false, bool MULTI = false, bool VAR = false, typename... SP>
 __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_in, const std::conditional_t<VAR, VarlenArgs, MultiArg<MULTI>> mt,
@@ -402,6 +438,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
 {
     constexpr bool STRM = (std::is_same_v<SP, FrameStreamArgs> || ...);
     [[maybe_unused]] const FrameStreamArgs *fs = pack_arg<FrameStreamArgs>(sp...);
+    constexpr bool STRP = (std::is_same_v<SP, FrameStreamPackedArgs> || ...);
+    [[maybe_unused]] const FrameStreamPackedArgs *fp = pack_arg<FrameStreamPackedArgs>(sp...);
     // Everything in front of a wave's first sample loads is start-up latency of the launch (nothing can be computed before
     // the samples are here), so the kernel arguments that lead to those loads are fetched by ONE batch of scalar loads at the
     // very top (pinned: left alone, the compiler fetches them where they are first used -- three dependent scalar-memory
@@ -456,6 +494,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     // quad range of this workgroup (contiguous, balanced to within one quad)
     unsigned total = a.batch * a.n_frames;
     if constexpr (VAR) total = static_cast<unsigned>(mt.total_frames);  // (the launcher keeps it below 2^31)
+    if constexpr (STRP) total = fp->total_rows;
     const unsigned q_lo = blockIdx.x * a.q_base + min(blockIdx.x, a.q_rem);
     const unsigned q_hi = q_lo + a.q_base + (blockIdx.x < a.q_rem ? 1u : 0u);
 
@@ -480,13 +519,15 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     Seg ns{};                // MULTI: the batch of the quad whose samples are being fetched ...
     Fast512Args an = a_in;   // ... and the argument block with that batch's input
     [[maybe_unused]] unsigned cursor = 0;  // VAR: the wave's clip cursor ...
-    [[maybe_unused]] VarFrame vnext{};     // ... and the clip data of the frame whose samples are in vin
+    [[maybe_unused]] VarFrame vnext{};     // ... and the clip data of the frame whose samples are in vin (STRP: its ok alone)
     if constexpr (VAR) {
         const char *p = var_src(a, mt, min(quad, q_hi - 1), total, f, cursor, t_next, vnext);
 #pragma unroll
         for (int e = 0; e < NE; ++e) vin[e] = *reinterpret_cast<const float2 *>(p + 8 * (j + 16 * e));
     } else if constexpr (STRM) {
         t_next = load_quad_stream<NE>(a, *fs, min(quad, q_hi - 1), total, f, j, vin);
+    } else if constexpr (STRP) {
+        t_next = load_quad_stream_packed<NE>(a, *fp, min(quad, q_hi - 1), total, f, j, vin, vnext.ok);
     } else if constexpr (MULTI) {
         an = a;
         ns = seg_of(mt.m, min(quad, q_hi - 1));
@@ -653,10 +694,10 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         // SPREAD: the ten sample loads of the next quad go out one per twiddle step instead of as a burst (a wave issues in
         // order: behind a burst of vector-memory instructions its own VALU work waits); no branch surrounds them -- the last
         // iteration of a wave fetches the block's last quad again and drops it
-        constexpr bool SPREAD = PREFETCH && EXACT && !PRE && !CENTER && !STRM && !(SS_ABLATE & 16);
+        constexpr bool SPREAD = PREFETCH && EXACT && !PRE && !CENTER && !STRM && !STRP && !(SS_ABLATE & 16);
         static_assert(!MULTI || (SPREAD && OUTK == 0), "the multi-batch build exists for the spread-prefetch MFCC builds");
         static_assert(!VAR || (SPREAD && OUTK == 0 && !MULTI), "the varlen build exists for the spread-prefetch MFCC builds");
-        static_assert(!STRM || (EXACT && !PRE && !CENTER && !MULTI && !VAR && OUTK != 2 && (FRONT & 1) == 0),
+        static_assert(!(STRM || STRP) || (EXACT && !PRE && !CENTER && !MULTI && !VAR && OUTK != 2 && (FRONT & 1) == 0),
                       "the streaming builds exist for the default frame shape's MFCC / mfe without window or pre-emphasis");
         QuadSrc nsrc{nullptr, 0u};
         if constexpr (VAR) {
@@ -674,6 +715,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         if constexpr (STRM) {
             // (the whole quad's loads as one burst behind pass 1: the edge branch's address selects do not split into the twiddle steps)
             if (next < q_hi) t_next = load_quad_stream<NE>(a, *fs, next, total, f, j, vin);
+        } else if constexpr (STRP) {
+            if (next < q_hi) t_next = load_quad_stream_packed<NE>(a, *fp, next, total, f, j, vin, vnext.ok);
         } else if (!SPREAD && PREFETCH && next < q_hi && !(SS_ABLATE & 16)) {
             t_next = load_quad<NE, EXACT, PRE, CENTER>(a, next, total, f, j, vin, pin);
         }
@@ -821,11 +864,13 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
                 const __amdgpu_buffer_rsrc_t ers = out_rsrc(a.out_energy + static_cast<unsigned long long>(quad_s) * 4ull, nvalid * 4u);
                 const int rowb = f * static_cast<int>(nfl);
                 const float e0 = m0 * hs, e1 = m1 * hs, e2 = m2 * hs;
-                buf_store(e0 == 0.f ? kEps : e0, frs, fidx0 >= 0 ? (rowb + fidx0) * 4 : kOobOffset);
-                buf_store(e1 == 0.f ? kEps : e1, frs, fidx1 >= 0 ? (rowb + fidx1) * 4 : kOobOffset);
-                buf_store(e2 == 0.f ? kEps : e2, frs, fidx2 >= 0 ? (rowb + fidx2) * 4 : kOobOffset);
+                bool row_ok = true;
+                if constexpr (STRP) row_ok = vcur.ok;  // a row of a skipped entry keeps what the caller put there
+                buf_store(e0 == 0.f ? kEps : e0, frs, row_ok && fidx0 >= 0 ? (rowb + fidx0) * 4 : kOobOffset);
+                buf_store(e1 == 0.f ? kEps : e1, frs, row_ok && fidx1 >= 0 ? (rowb + fidx1) * 4 : kOobOffset);
+                buf_store(e2 == 0.f ? kEps : e2, frs, row_ok && fidx2 >= 0 ? (rowb + fidx2) * 4 : kOobOffset);
                 const float en = energy * (1.0f / kTwo32);  // exact: power-of-two scaling
-                buf_store(en, ers, j == 0 ? f * 4 : kOobOffset);
+                buf_store(en, ers, row_ok && j == 0 ? f * 4 : kOobOffset);
             }
             wave_order();
             quad = next;
@@ -937,7 +982,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             if (a.dc_elimination) {
                 const float le = ln_scaled(energy);
                 o = j == 0 ? le : o;
-            } else if (!STRM && t_cur == 0 && j == 0) {
+            } else if (!STRM && !STRP && t_cur == 0 && j == 0) {
                 o = acc * (VAR ? vcur.s00 : a.dct_scale_00);
             }
             // unconditional, counted store (ss_wave.h): the descriptor covers the quad's valid frames, lanes j >= n_ceps are
@@ -954,7 +999,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             const unsigned nvalid = min(4u, q_total - quad_s * 4);
             const __amdgpu_buffer_rsrc_t orow = out_rsrc(q_out + static_cast<unsigned long long>(quad_s) * 4ull * Cc, nvalid * Cc * 4u);
             bool store = j < Cc;
-            if constexpr (VAR) store = store && vcur.ok;
+            if constexpr (VAR || STRP) store = store && vcur.ok;
             buf_store(o, orow, store ? (f * Cc + j) * 4 : kOobOffset);
         }
         wave_order();
@@ -964,6 +1009,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     }
     // VAR: the consistency pass over every clip (at the end: its loads would otherwise wait in line with the first samples)
     if constexpr (VAR) varlen_check_clips(mt, a.flen, a.step, blockIdx.x * (WAVES * 64) + tid, gridDim.x * (WAVES * 64));
+    if constexpr (STRP) stream_check_entries(*fp, blockIdx.x * (WAVES * 64) + tid, gridDim.x * (WAVES * 64));
 #if SS_PROF2
     if (a.dbg && lane == 0) {
         unsigned long long *o = a.dbg + 16ull * (blockIdx.x * WAVES + wave);
@@ -1257,6 +1303,50 @@ hipError_t launch_mfcc_c256_stream(const Fast512Args &a_in, const FrameStreamArg
     // the one-shot builds' template arguments (RES 30 / 2) with STRM: the same arithmetic per frame, bit for bit
     if (mfcc) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, false, FrameStreamArgs>, "ss_mfcc_c256s<10,exact,bank421,sym>");
     return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, FrameStreamArgs>, "ss_mfcc_c256s<10,exact,bank421,mfe>");
+}
+
+hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a_in, const FrameStreamPackedArgs &s, hipStream_t stream, int num_cus,
+                                          LaunchInfo *info)
+{
+    constexpr int WAVES = 12;
+    Fast512Args a = a_in;
+    // the shapes of launch_mfcc_c256_stream
+    const bool b421 = a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1;
+    const bool mfcc = a.out_mfe == 0 && a.n_filters == 40 && a.paired == 2;
+    const bool mfe = a.out_mfe == 1 && a.n_filters <= 40;
+    if (a.fullp || a.center || a.win_floats > 0 || a.preemph != 0.0f || a.flen != 320 || a.spectrum_exponent == 2 || !b421 || !(mfcc || mfe) ||
+        (a.step & 1u) || a.step == 0 || a.step > a.flen || s.step != a.step || s.lead != static_cast<int>(a.flen - a.step) ||
+        s.state_len < static_cast<unsigned>(s.lead) || (s.state_len > 0 && !s.pool) || s.n_active == 0)
+        return hipErrorInvalidValue;
+    const unsigned long long total = s.total_rows;
+    if (total + 4 >= (1ull << 31)) return hipErrorInvalidValue;
+    a.nf_magic = a.nf_shift = 0;
+    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * a.mel_wpitch) * sizeof(float) + 16;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    // an empty output block still gets one workgroup: the entry pass runs
+    const unsigned long long quads = (total + 3) / 4;
+    unsigned long long blocks = quads ? (quads + WAVES - 1) / WAVES : 1;
+    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
+    if (blocks > cap) blocks = cap;
+    const unsigned grid = static_cast<unsigned>(blocks);
+    a.q_base = static_cast<uint32_t>(quads / grid);
+    a.q_rem = static_cast<uint32_t>(quads % grid);
+    auto go = [&](auto kern, const char *name) {
+        if (lds > 48 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     static_cast<int>(lds));
+            if (e != hipSuccess) return e;
+        }
+        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{}, s);
+        return hipGetLastError();
+    };
+    // the dense streaming builds' template arguments with the packed argument pack: the same arithmetic per frame, bit for bit
+    if (mfcc)
+        return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, false, FrameStreamPackedArgs>,
+                  "ss_mfcc_c256sp<10,exact,bank421,sym>");
+    return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, FrameStreamPackedArgs>,
+              "ss_mfcc_c256sp<10,exact,bank421,mfe>");
 }
 
 bool mfcc_c256_has_mfe(const Fast512Args &a)

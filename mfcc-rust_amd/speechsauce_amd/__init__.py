@@ -25,7 +25,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "mel_spectrogram_packed",
            "mel_spectrogram_list", "stft_packed", "cmvn_packed", "cmvnw_packed", "power_to_db_packed", "lmfe_packed",
            "MelSpectrogramStream", "StftStream",
-           "MfccStream", "MfeStream", "SpeechConfig", "SpeechSauceError"]
+           "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "SpeechConfig", "SpeechSauceError"]
 
 
 def _is_torch(x) -> bool:
@@ -919,6 +919,172 @@ class MfeStream(_FrameStreamBase):
             energy = np.empty((self.n_streams, R), dtype=np.float32)
         self._call(sig, n, config, [feat, energy], "ss_mfe_stream_device", "ss_mfe_stream", [])
         return feat, energy
+
+# ---- ragged streaming MFCC / mfe over a pool of stream states ----------------------------------------------------------------
+
+class _FrameStreamPoolBase(_FrameStreamBase):
+    """A pool of ``pool_streams`` live audio streams, each with the carried state of ``MfccStream`` / ``MfeStream``.  One call
+    serves any subset of them, each with its own number of whole hops (zero included): ``pool(chunks, slots)`` with ``chunks`` a
+    list of 1-D float32 arrays / tensors, or one packed 1-D buffer plus ``lengths=``, and ``slots`` the pool row of each chunk
+    (distinct).  Per stream the rows and the carried state are those of the dense class on that stream alone.  numpy in -> the
+    host-pointer call, ROCm tensors in -> the device call on the current stream.  See ``ss_mfcc_stream_packed`` in
+    ``include/speechsauce_amd.h``."""
+
+    def __init__(self, pool_streams, *args):
+        super().__init__(pool_streams, *args)
+        self.pool_streams = self.n_streams
+
+    @property
+    def state(self):
+        """[pool_streams, state_len] float32: a torch tensor on the device of the first chunks, or a numpy array; None before
+        the first call."""
+        return self._state
+
+    def reset(self, slots=None):
+        """Zero the state of every stream of the pool, or of the given slots (fresh streams)."""
+        super().reset(slots)
+
+    def _prepare_pool(self, chunks, slots, lengths):
+        what = self._what
+        if lengths is None:
+            if _is_torch(chunks) or isinstance(chunks, np.ndarray):
+                raise TypeError(f"{what}: chunks must be a list of 1-D arrays (or pass a packed buffer with lengths=)")
+            parts = [_require_f32(c, (1,), what) for c in chunks]
+            lens = [int(c.shape[0]) for c in parts]
+            kinds = {_is_torch(c) for c in parts}
+            if len(kinds) > 1:
+                raise TypeError(f"{what}: chunks must be all numpy arrays or all tensors on one device")
+            packed = None
+        else:
+            packed = _require_f32(chunks, (1,), what)
+            parts = None
+            lens = [int(v) for v in lengths]
+            if any(v < 0 for v in lens) or sum(lens) != int(packed.shape[0]):
+                raise ValueError(f"{what}: lengths must be non-negative and sum to the packed buffer's {int(packed.shape[0])} samples")
+        slot_list = [int(v) for v in slots]
+        if len(slot_list) != len(lens):
+            raise ValueError(f"{what}: {len(lens)} chunks but {len(slot_list)} slots")
+        for i, n in enumerate(lens):
+            if n % self.hop:
+                raise ValueError(f"{what}: chunk {i} has {n} samples, not a multiple of the hop {self.hop}")
+        seen = set()
+        for i, v in enumerate(slot_list):
+            if not 0 <= v < self.pool_streams:
+                raise ValueError(f"{what}: slot {v} of chunk {i} is outside the pool of {self.pool_streams} streams")
+            if v in seen:
+                raise ValueError(f"{what}: slot {v} is named twice in one call")
+            seen.add(v)
+        first = packed if packed is not None else (parts[0] if parts else None)
+        on_dev = first is not None and _is_torch(first)
+        if first is None:  # nothing to serve: the place of the pool decides, the host before any call
+            on_dev = self._where is not None and self._where[0] == "cuda"
+        if on_dev:
+            import torch
+
+            dev = first.device if first is not None else self._state.device
+            if packed is None:
+                if any(c.device != dev for c in parts):
+                    raise TypeError(f"{what}: chunks must be all numpy arrays or all tensors on one device")
+                packed = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device=dev)
+            where = ("cuda", dev.index)
+        else:
+            if packed is None:
+                packed = np.concatenate(parts) if parts else np.empty(0, dtype=np.float32)
+            where = ("host",)
+        if self._where is not None and where != self._where:
+            raise ValueError(f"{what}: the pool lives on {self._where}, these chunks on {where}")
+        a = self._args
+        config = _cfg(*a[:9], a[9], packed)
+        if self._state is None:
+            if on_dev:
+                self._state = torch.zeros((self.pool_streams, self.state_len), dtype=torch.float32, device=packed.device)
+            else:
+                self._state = np.zeros((self.pool_streams, self.state_len), dtype=np.float32)
+            self._where = where
+        so = np.zeros(len(lens) + 1, dtype=np.int64)
+        np.cumsum(lens, out=so[1:])
+        ro = so // self.hop
+        return packed, so, ro, np.asarray(slot_list, dtype=np.int32), config
+
+    def _call_pool(self, packed, so, ro, sl, config, outs, dev_fn, host_fn, extra):
+        lib = _lib.lib()
+        n_active = sl.size
+        if n_active == 0:
+            return
+        ptrs = [o.data_ptr() if _is_torch(o) else o.ctypes.data for o in outs]
+        if _is_torch(packed):
+            import torch
+
+            x = packed.contiguous()
+            with torch.cuda.device(x.device):
+                d_so, d_ro, d_sl = (torch.from_numpy(t).to(x.device) for t in (so, ro, sl))
+                st = self._state.data_ptr() if self.state_len else None
+                _lib.check(getattr(lib, dev_fn)(config.handle, x.data_ptr(), n_active, d_so.data_ptr(), d_ro.data_ptr(), int(ro[-1]),
+                                                d_sl.data_ptr(), self.pool_streams, *extra, st, *ptrs, _stream_ptr()))
+                for t in (x, d_so, d_ro, d_sl):  # the launches are asynchronous: keep the temporaries until the stream has passed them
+                    t.record_stream(torch.cuda.current_stream())
+        else:
+            x = np.ascontiguousarray(packed)
+            st = self._state.ctypes.data if self.state_len else None
+            _lib.check(getattr(lib, host_fn)(config.handle, x.ctypes.data, n_active, so.ctypes.data, sl.ctypes.data, self.pool_streams,
+                                             *extra, st, *ptrs))
+
+
+class MfccStreamPool(_FrameStreamPoolBase):
+    """Ragged streaming ``mfcc``: ``pool(chunks, slots)`` -> ``(rows [total_rows, num_cepstral], row_offsets)``; chunk ``i``'s
+    ``len(chunk) // hop`` rows are ``rows[row_offsets[i]:row_offsets[i + 1]]`` (``row_offsets``: int64 numpy array).
+    ``norm_frames`` as for ``MfccStream``."""
+
+    _what = "MfccStreamPool"
+
+    def __init__(self, pool_streams, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
+                 fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, norm_frames=None, **switches):
+        super().__init__(pool_streams, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
+                         low_frequency, high_frequency, dc_elimination, switches)
+        if self._params.dct_norm == 0:  # SS_DCT_REFERENCE
+            if norm_frames is None or int(norm_frames) < 1:
+                raise ValueError("MfccStreamPool: the reference DCT scaling needs norm_frames >= 1 (the frame count it scales by)")
+            self.norm_frames = int(norm_frames)
+        else:
+            self.norm_frames = int(norm_frames) if norm_frames is not None else 1
+
+    def __call__(self, chunks, slots, lengths=None):
+        packed, so, ro, sl, config = self._prepare_pool(chunks, slots, lengths)
+        Cc, R = config.params.num_cepstral, int(ro[-1])
+        if _is_torch(packed):
+            import torch
+
+            out = torch.empty((R, Cc), dtype=torch.float32, device=packed.device)
+        else:
+            out = np.empty((R, Cc), dtype=np.float32)
+        self._call_pool(packed, so, ro, sl, config, [out], "ss_mfcc_stream_packed_device", "ss_mfcc_stream_packed", [self.norm_frames])
+        return out, ro
+
+
+class MfeStreamPool(_FrameStreamPoolBase):
+    """Ragged streaming ``mfe``: ``pool(chunks, slots)`` -> ``(feat [total_rows, num_filters], energy [total_rows],
+    row_offsets)``."""
+
+    _what = "MfeStreamPool"
+
+    def __init__(self, pool_streams, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_filters=40, fft_length=512,
+                 low_frequency=0, high_frequency=None, **switches):
+        super().__init__(pool_streams, sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
+                         low_frequency, high_frequency, True, switches)
+
+    def __call__(self, chunks, slots, lengths=None):
+        packed, so, ro, sl, config = self._prepare_pool(chunks, slots, lengths)
+        M, R = config.params.num_filters, int(ro[-1])
+        if _is_torch(packed):
+            import torch
+
+            feat = torch.empty((R, M), dtype=torch.float32, device=packed.device)
+            energy = torch.empty((R,), dtype=torch.float32, device=packed.device)
+        else:
+            feat = np.empty((R, M), dtype=np.float32)
+            energy = np.empty((R,), dtype=np.float32)
+        self._call_pool(packed, so, ro, sl, config, [feat, energy], "ss_mfe_stream_packed_device", "ss_mfe_stream_packed", [])
+        return feat, energy, ro
 
 
 def stack_frames(signal, sampling_frequency, frame_length=0.020, frame_stride=0.020, filter=None, zero_padding=False, **switches):
