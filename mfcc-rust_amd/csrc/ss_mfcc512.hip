@@ -12,8 +12,12 @@
 //     (n1,k1) -> 34*(n1>>1) + 2*k1 + (n1&1), read back with 8 ds_read_b128 per lane; conflict-free on
 //     both sides (2304 B = 9 bank rows keeps the b128 lane groups of neighbouring frames apart).  Zero padding
 //     is compile-time (template NE: a 320-sample frame fills 10 of the 16 first-pass inputs).
-//   * The real-FFT untangle needs Z[256-k], which sits in lane 16-j, register 15-r: fetched with
-//     ds_bpermute_b32 (LDS crossbar, no memory round trip).
+//   * The real-FFT untangle needs Z[256-k], register 15-r of the lane that holds column 16-c.  From the exchange on the lanes
+//     of a row hold the columns in the order 0, 1..7, 9..15, 8 (untangle_col, ss_wave.h): the partner lane is then the
+//     row_mirror lane and the value is read through DPP by the instruction that consumes it -- no ds_bpermute_b32, no trip
+//     through the LDS queue and no wait (the exchange reads the same 16 addresses per frame, dealt to other lanes: still
+//     conflict-free).  Columns 0 and 8 pair with themselves: lanes 0 and 15 select a register of their own.  The first pass,
+//     the sample loads, the mel / ln / DCT stages and the output store keep the plain lane order.
 //   * |X|/N for bins 0..128 goes to a P row in LDS (the mel bank ends at bin (F+1)/2, feature.rs:69-70);
 //     all 257 bins feed the frame energy, reduced over the DPP row.
 //   * mel: banded reduction -- each lane owns up to three filters (host-sorted by tap count so the
@@ -60,7 +64,7 @@
 // Timing-attribution builds (lab build only: tools/ablate.sh passes -DSS_LAB=1 -DSS_ABLATE=<bits>): each bit removes one
 // stage; results are then wrong by design.  The product build compiles the switch out (SS_ABLATE is the constant 0 there,
 // whatever the command line says).
-//   1 partner fetch (ds_bpermute)   2 mel + ln + DCT   4 LDS exchange   8 square roots   16 sample loads in the loop
+//   1 partner read (row_mirror DPP)   2 mel + ln + DCT   4 LDS exchange   8 square roots   16 sample loads in the loop
 //   32 DCT only   64 second radix-16 pass
 //   128 all sample loads from clip 0 (L2-resident: removes the HBM misses)
 #if !SS_LAB
@@ -69,7 +73,7 @@
 #ifndef SS_ABLATE
 #define SS_ABLATE 0
 #endif
-// LDS stores, partner fetches and sample loads leave in small groups from inside the butterflies and the twiddle loop instead
+// LDS stores and sample loads leave in small groups from inside the butterflies and the twiddle loop instead
 // of as bursts behind them -- a wave issues in order, so a burst of 8..16 memory instructions holds back its own VALU work
 // while the LDS / vector-memory queue drains (-1.0 us of 30.8 on one box against the round-1 bursts).
 
@@ -473,7 +477,10 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         stamp(4, 0ull);
     }
     const int f = lane >> 4;  // frame within the quad
-    const int j = lane & 15;  // column of the frame's 16 x 16 point matrix owned by this lane of the DPP row
+    const int j = lane & 15;  // lane of the frame's DPP row: first-pass row n1, mel filter slot, cepstral column
+    // column k1 of the frame's 16 x 16 point matrix that this lane owns from the exchange on (second pass, untangle, P row):
+    // dealt so that the untangle partner sits in the row_mirror lane (ss_wave.h)
+    const int cj = untangle_col(j);
 
     // ---- LDS carve: per-wave regions, then the shared read-only table block, then the quad counter ----
     float *wbase = reinterpret_cast<float *>(smem) + wave * WF;
@@ -569,8 +576,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         if (!FULLP && !ALIAS && j < 3) prow[129 + j] = 0.f;  // pad bins read (with zero weight) by the mel stage; never written again
     }
 
-    const int paddr = ((lane & 48) | ((16 - j) & 15)) << 2;  // lane holding Z[256 - k]
-    const int wbase1 = 34 * (j >> 1) + (j & 1);              // exchange write base (float2 units)
+    const int wbase1 = 34 * (j >> 1) + (j & 1);  // exchange write base (float2 units): the first pass keeps n1 = j
     const int Cc = static_cast<int>(a.n_ceps);
     // |X| = (1/2)|...|: the 1/2 of the untangle is folded into the scale (1/4 for the squared form)
     const float hscale32 = (POW2 ? 0.25f * a.scale : 0.5f * a.scale) * kTwo32;
@@ -601,10 +607,10 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     float *sd = ALIAS ? prow + 192 : wbase + 192 + f * (PAIRED ? 48 : 40);
     const float4 *w4 = reinterpret_cast<const float4 *>(s_melw + j * a.mel_wpitch);
     const float4 *c4 = reinterpret_cast<const float4 *>(s_cos + j * 52);
-    float2 twn[8];  // exp(-2 pi i (j + 16 r) / 512): resident when the register budget allows (<= 3 waves per SIMD)
+    float2 twn[8];  // exp(-2 pi i (cj + 16 r) / 512): resident when the register budget allows (<= 3 waves per SIMD)
     if (TABREG) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) twn[r] = s_twn[r * 16 + j];
+        for (int r = 0; r < 8; ++r) twn[r] = s_twn[r * 16 + cj];
     }
     // RES bit 0: this lane's cosine row stays in registers; bit 1: the 15 pass-2 twiddles do
     float4 cr[(RES & 1) ? NQ : 1];
@@ -615,7 +621,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     }
     if (RES & 2) {
 #pragma unroll
-        for (int p = 0; p < 8; ++p) tw2r[p] = s_tw2[p * 16 + j];
+        for (int p = 0; p < 8; ++p) tw2r[p] = s_tw2[p * 16 + cj];
     }
     // column scale of this lane (feature.rs:126-146): column 0 has its own (and none when the frame energy replaces it)
     const float sc_lane = j == 0 ? (a.dc_elimination ? 0.f : a.dct_scale_0) : a.dct_scale_k;
@@ -728,14 +734,16 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
                 u[2 * p + 1] = v[2 * p + 1];
                 continue;
             }
-            const float4 t4 = *reinterpret_cast<const float4 *>(&zh[34 * p + 2 * j]);
+            // column k1 = cj (the same 16 addresses per frame as with k1 = j, dealt to other lanes: every ds_read_b128 lane group
+            // still covers the sixteen 16-byte bank slots once)
+            const float4 t4 = *reinterpret_cast<const float4 *>(&zh[34 * p + 2 * cj]);
             u[2 * p] = make_float2(t4.x, t4.y);
             u[2 * p + 1] = make_float2(t4.z, t4.w);
         }
         wave_order();
 #pragma unroll
         for (int p = 0; p < 8; ++p) {  // two twiddles per ds_read_b128
-            const float4 w2 = (RES & 2) ? tw2r[p] : s_tw2[p * 16 + j];
+            const float4 w2 = (RES & 2) ? tw2r[p] : s_tw2[p * 16 + cj];
             u[2 * p + 1] = cmul(u[2 * p + 1], make_float2(w2.x, w2.y));
             if (p < 7) u[2 * p + 2] = cmul(u[2 * p + 2], make_float2(w2.z, w2.w));
             if (SPREAD) {
@@ -750,27 +758,16 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         SS_PRIOL(SS_P2_F2);
         SS_PH(4);  // exchange reads + twiddles (+ prefetch issue)
         // ---- untangle Z -> X; |X| (processing.rs:168) * 1/N (:180); row sum (feature.rs:216) ----
-        // the partner of bin j + 16 r is register 15 - r of lane 16 - j: fetched with ds_bpermute
-        float2 zcs[8];
-        if (!(SS_ABLATE & 65)) {
-            // the fetches of the upper registers go out as soon as the butterfly has produced them, group by group
+        // the partner of bin cj + 16 r is register 15 - r of the row_mirror lane (lanes 0 and 15: a register of their own): read
+        // through DPP where the untangle consumes it, nothing is fetched here
+        if (!(SS_ABLATE & 64)) {
             float2 uo[16];  // (the butterfly still reads its input registers while the first groups' outputs appear)
-            fft16_emit(
-                u,
-                [&](int k, float2 val) {
-                    uo[k] = val;
-                    if (k >= 8) zcs[15 - k] = make_float2(bperm(paddr, val.x), bperm(paddr, val.y));
-                },
-                [] { __builtin_amdgcn_sched_barrier(0); });
+            fft16_emit(u, [&](int k, float2 val) { uo[k] = val; }, [] {});
 #pragma unroll
-            for (int k = 0; k < 16; ++k) u[k] = uo[k];
-        } else {  // stage-removal builds only
-            if (!(SS_ABLATE & 64)) fft16_reg(u);  // u[r] = Z[j + 16 r]
-#pragma unroll
-            for (int r = 0; r < 8; ++r) zcs[r] = (SS_ABLATE & 1) ? u[15 - r] : make_float2(bperm(paddr, u[15 - r].x), bperm(paddr, u[15 - r].y));
+            for (int k = 0; k < 16; ++k) u[k] = uo[k];  // u[r] = Z[cj + 16 r]
         }
         SS_PRIOL(SS_P2_UN);
-        SS_PH(5);  // pass 2 + partner fetches
+        SS_PH(5);  // pass 2
         float esum = 0.f;
         // power_spectrum output (processing.rs:179-181): the scaled |X| of all 257 bins of the frame, 64 contiguous bytes
         // per register and frame on either side of the spectrum
@@ -785,9 +782,11 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const float2 zk = u[r];
-            // lane 0 pairs with itself: Z[256 - 16 r] = own register (16 - r) & 15
-            const float2 zc = j == 0 ? u[(16 - r) & 15] : zcs[r];
-            const float2 w = TABREG ? twn[r] : s_twn[r * 16 + j];
+            // Z[256 - k]: register 15 - r of the row_mirror lane; columns 0 and 8 pair with themselves -- lane 0:
+            // Z[256 - 16 r] = own register (16 - r) & 15, lane 15: Z[256 - 8 - 16 r] = own register 15 - r
+            const float2 own = j == 0 ? u[(16 - r) & 15] : u[15 - r];
+            const float2 zc = untangle_partner<!(SS_ABLATE & 1)>(u[15 - r], own);
+            const float2 w = TABREG ? twn[r] : s_twn[r * 16 + cj];
             const float2 s = make_float2(zk.x + zc.x, zk.y - zc.y);  // 2 E[k]
             const float2 d = make_float2(zk.x - zc.x, zk.y + zc.y);
             // 2 X[k] = s - i w d, 2 conj X[256-k] = s + i w d = 2 s - 2 X[k]: six FMAs instead of a product and four adds
@@ -798,12 +797,12 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             const float pa = (POW2 || (SS_ABLATE & 8)) ? na : __builtin_amdgcn_sqrtf(na);  // unscaled; hscale is applied to the sums below
             const float pb = (POW2 || (SS_ABLATE & 8)) ? nb : __builtin_amdgcn_sqrtf(nb);
             if (PWR) {
-                buf_store(hs_pw * pa, pw_rsrc, pw_off + (j + 16 * r) * 4);
-                buf_store(hs_pw * pb, pw_rsrc, pw_off + (256 - j - 16 * r) * 4);
+                buf_store(hs_pw * pa, pw_rsrc, pw_off + (cj + 16 * r) * 4);
+                buf_store(hs_pw * pb, pw_rsrc, pw_off + (256 - cj - 16 * r) * 4);
                 continue;
             }
-            prow[j + 16 * r] = pa;  // only bins <= 128 can carry mel weight (the bank ends at (F+1)/2, feature.rs:69-70) ...
-            if (FULLP) prow[256 - j - 16 * r] = pb;  // ... unless the bank covers the whole spectrum
+            prow[cj + 16 * r] = pa;  // only bins <= 128 can carry mel weight (the bank ends at (F+1)/2, feature.rs:69-70) ...
+            if (FULLP) prow[256 - cj - 16 * r] = pb;  // ... unless the bank covers the whole spectrum
             esum += pa + pb;
         }
         if (j == 0) {
@@ -827,7 +826,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             quad = next;
             continue;
         }
-        float energy = hscale32 * row16_sum(esum);      // E * 2^32
+        // (the lanes' partial sums are per column: back in column order, so that the row sum rounds as it did in lane = column order)
+        float energy = hscale32 * row16_sum(untangle_by_col(esum, j));  // E * 2^32
         energy = energy == 0.f ? kEps * kTwo32 : energy;  // zero_handling, feature.rs:219
         wave_order();
         SS_PRIOL(SS_P2_MEL);

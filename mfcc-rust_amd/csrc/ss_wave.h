@@ -129,6 +129,44 @@ __device__ __forceinline__ float dpp(float v)
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
 }
 
+// Real-FFT untangle of a 256-point transform whose 16 x 16 matrix is spread over one DPP row (16 lanes, one column each, register r
+// of the lane with column c = Z[c + 16 r]): bin k = c + 16 r pairs with Z[256 - k], which is register 15 - r of the lane that
+// holds column (16 - c) & 15.  With the columns dealt to the lanes as
+//     lane 0 -> 0,  lanes 1..7 -> 1..7,  lanes 8..14 -> 9..15,  lane 15 -> 8
+// col(15 - l) = 16 - col(l) for the lanes 1..14: the partner lane is the row_mirror lane, and the value arrives as a DPP source
+// modifier on the instruction that consumes it -- no ds_bpermute_b32, no LDS queue, no wait.  Columns 0 and 8 are their own
+// partners (256 - 16 r = 16 (16 - r), 256 - (8 + 16 r) = 8 + 16 (15 - r)): lanes 0 and 15 take a register of their own.
+__device__ __forceinline__ int untangle_col(int l) { return l == 15 ? 8 : l + (l >> 3); }
+// `v`: this lane's register 15 - r; `own`: its own partner register where it has one (lane 0: register (16 - r) & 15, lane 15: v).
+// FETCH = false (stage-removal lab builds): no lane crossing at all, the value is wrong by design.
+template <bool FETCH = true>
+__device__ __forceinline__ float2 untangle_partner(float2 v, float2 own)
+{
+    if (!FETCH) return v;
+    // v_cndmask_b32 is VOP2 and takes the DPP modifier on its first source: select and lane crossing in one instruction per
+    // component, lanes 0 and 15 of every row (the mask) keep `own`.  Written out: the compiler keeps a lane mask in an arbitrary
+    // SGPR pair, which is the VOP3 form of the select, and that has no DPP on gfx9.  s_nop: a VGPR written by the VALU may be read through DPP two wait states later.
+    float2 z;
+    asm("s_mov_b64 vcc, %4\n\ts_nop 0\n\t"
+        "v_cndmask_b32_dpp %0, %2, %3, vcc row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_cndmask_b32_dpp %1, %5, %6, vcc row_mirror row_mask:0xf bank_mask:0xf"
+        : "=&v"(z.x), "=&v"(z.y)
+        : "v"(v.x), "v"(own.x), "s"(0x8001800180018001ull), "v"(v.y), "v"(own.y)
+        : "vcc");
+    return z;
+}
+
+// The inverse deal for one value per lane: lane l ends with `v` of the lane that holds column l (lanes 9..15 take their left
+// neighbour's, lane 8 takes lane 15's, lanes 0..7 keep theirs).  A per-column partial sum goes through this before row16_sum, so
+// that the sum's tree adds the columns in the order it always did and rounds the same.
+__device__ __forceinline__ float untangle_by_col(float v, int l)
+{
+    const int vi = __builtin_bit_cast(int, v);
+    const int a = __builtin_amdgcn_update_dpp(vi, vi, 0x111, 0xf, 0xc, false);  // row_shr:1 into lanes 8..15 (bank mask)
+    const int b = __builtin_amdgcn_mov_dpp(vi, 0x129, 0xf, 0xf, false);        // row_ror:9: lane 8 <- lane 15
+    return __builtin_bit_cast(float, l == 8 ? b : a);
+}
+
 // sum over the 16 lanes of a DPP row; every lane ends with the same bits
 __device__ __forceinline__ float row16_sum(float v)
 {
