@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SS_ABI_VERSION 7 /* 7: the ragged streaming calls over a pool of stream states (ss_frame_stream_packed_row_offsets, ss_mfcc_stream_packed*, ss_mfe_stream_packed*), ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region, the packed post-processing calls (ss_cmvn_packed*, ss_cmvnw_packed*, ss_power_to_db_packed*, ss_lmfe_packed*); 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
+#define SS_ABI_VERSION 7 /* 7: the ragged streaming calls over a pool of stream states (ss_frame_stream_packed_row_offsets, ss_mfcc_stream_packed*, ss_mfe_stream_packed*; ss_stream_packed_row_offsets, ss_mel_spectrogram_stream_packed*, ss_stft_stream_packed*), ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region, the packed post-processing calls (ss_cmvn_packed*, ss_cmvnw_packed*, ss_power_to_db_packed*, ss_lmfe_packed*); 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
 
 typedef enum ss_status {
     SS_OK = 0,
@@ -416,6 +416,65 @@ int ss_mfcc_stream_packed(const ss_config *cfg, const float *x, size_t n_active,
                           const int32_t *slots, size_t pool_streams, uint32_t norm_frames, float *pool, float *out);
 int ss_mfe_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets,
                          const int32_t *slots, size_t pool_streams, float *pool, float *feat, float *energy);
+
+/* ---- ragged streaming STFT / mel spectrogram over a pool of stream states ----
+ * The frame-path pool above, carried over to the STFT path (ss_stft_stream* / ss_mel_spectrogram_stream*), SS_STREAM_CONTINUOUS
+ * only: SS_STREAM_REFERENCE's partial chunks and trailing n_pad zero rows have no meaning for a live pool.  H = the hop of
+ * ss_stft_sizes, W = fft_points, S = ss_stream_state_len = W - H; a config without an STFT path (W < 2H) is SS_ERR_BAD_CONFIG.
+ *   Pool: a caller-owned block [pool_streams x S] of floats -- the state block of ss_*_stream_device, row for row (all zeros =
+ *   fresh stream, zeroing a row resets it).
+ *   Entries: a call serves n_active entries.  Entry i's chunk is x[so[i] : so[i+1]] of one packed buffer (so: n_active + 1
+ *   non-decreasing int64 sample offsets, so[0] = 0); its length n_i is a whole number of hops R_i = n_i / H, and R_i = 0 is legal:
+ *   no rows, the state row untouched.  Its state is pool row slots[i] (int32, 0 <= slots[i] < pool_streams, distinct within a
+ *   call).  Its rows are rows ro[i] .. ro[i+1] of the packed row space (ro: n_active + 1 row offsets, ro[0] = 0, ro[i+1] - ro[i] =
+ *   R_i; from ss_stream_packed_row_offsets or computed by the caller on the device).
+ *   Outputs: mel -- entry i's block [num_filters x R_i] is contiguous at out + num_filters * ro[i] (the layout of
+ *   ss_mel_spectrogram_packed, and of the dense stream with n_streams = 1); stft -- [total_rows x (W/2+1) x 2], entry i owns rows
+ *   ro[i] .. ro[i+1].  total_rows is the rows the output holds (>= ro[n_active]; rows at or past ro[n_active] are left alone).
+ *   Equivalence: per entry the rows, and the pool row afterwards, are what ss_mel_spectrogram_stream_device /
+ *   ss_stft_stream_device give in SS_STREAM_CONTINUOUS mode for that stream alone (n_streams = 1, that chunk, that state row),
+ *   wherever the entry stands in the call and whatever else shares the call -- bit for bit where both run the same kernel family
+ *   and build (below).  Every switch and bank of the config applies.  Pool rows not named in `slots` are neither read nor written.
+ *   Kernels: mel output on a 2048-point configuration whose bank fits the dedicated kernel's twelve-wave build runs on its ragged
+ *   streaming build, reported by ss_last_kernel_name() as ss_mel_c1024sp<w12,mel6321> / ss_mel_c1024sp<w12> -- always twelve
+ *   waves, so that an entry's bits do not depend on what shares the call.  The dense stream picks eight or twelve waves by its
+ *   unit count, and the two builds round a few FMAs differently in the last bit: the pool equals the dense stream bit for bit
+ *   where that one runs ss_mel_c1024s<w12...> too; a lone small dense call picks eight waves and agrees to that last-bit rounding
+ *   only.  Everything else the dense generic streaming build serves -- any fft_points, chirp-z included; every bank; all stft
+ *   output -- runs on ss_front_generic_streamp<LOG2C[,chirpz]> with the bits of ss_front_generic_stream<...>.  A second
+ *   stream-ordered launch (ss_stream_advance_packed, the frame pool's) moves the named pool rows on.  The device forms are a linear
+ *   chain of these two launches whose grids depend on n_active and total_rows only: capturable, and replayable with other table
+ *   contents.
+ *   Containment: exactly the frame pool's.  The device forms never see the tables on the host.  Both kernels decode every entry
+ *   with one shared function (the frame pool's); an entry is skipped -- no row written, its pool row untouched -- unless
+ *   so[i] >= 0, 0 <= n_i <= 2^31 - 1, n_i % H == 0, ro[i] >= 0, ro[i+1] - ro[i] == n_i / H, ro[i+1] <= total_rows and
+ *   0 <= slots[i] < pool_streams.  Whatever the tables hold, nothing is read or written outside x's entry ranges, rows
+ *   [0, total_rows) of the output and rows [0, pool_streams) of the pool.  A skipped entry raises the config's device error word:
+ *   the call itself returns SS_OK, the next call on the config (or ss_config_device_status) returns SS_ERR_DEVICE once.
+ *   Duplicate slots in a device-form call are a caller error that is NOT detected: the rows and the pool rows of the entries
+ *   that share a slot are unspecified; everything stays inside the pool.  The host-pointer forms reject them.
+ * Arguments: n_active == 0 is SS_OK with nothing launched.  SS_ERR_ARG, pool and output untouched: null buffers, n_active,
+ * pool_streams or total_rows >= 2^31, pool_streams == 0, a pool range that overlaps x or the output (the device forms know x by
+ * its first sample; the host forms check its whole range).  The host-pointer forms also check the tables before they touch the
+ * device -- so[0] != 0, a decreasing pair, a chunk that is not whole hops, a slot outside the pool, a slot named twice;
+ * ss_last_error_string() names the first bad entry -- and move only what the call touches: x, the tables and the n_active named
+ * pool rows up, the output and those rows down; the caller's pool is written only after everything before it succeeded. */
+/* host only, no device: ro[0] = 0, ro[i+1] = ro[i] + (so[i+1] - so[i]) / H.  SS_ERR_ARG: so[0] != 0, a decreasing pair, a chunk
+ * that is not whole hops or longer than 2^31 - 1 samples; SS_ERR_BAD_CONFIG for a config with no STFT path */
+int ss_stream_packed_row_offsets(const ss_params *p, size_t n_active, const int64_t *sample_offsets, int64_t *row_offsets);
+/* device pointers, asynchronous on `stream`, graph-capturable: a linear chain of two launches (the rows, then the pool advance) */
+int ss_mel_spectrogram_stream_packed_device(const ss_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                            const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots,
+                                            size_t pool_streams, float *d_pool, float *d_out, void *stream);
+int ss_stft_stream_packed_device(const ss_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                 const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                 float *d_pool, float *d_out, void *stream);
+/* host pointers, synchronous; the tables are host arrays; out: num_filters * ro[n_active] floats (mel) /
+ * ro[n_active] * (fft_points/2+1) * 2 floats (stft) */
+int ss_mel_spectrogram_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets,
+                                     const int32_t *slots, size_t pool_streams, float *pool, float *out);
+int ss_stft_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets,
+                          const int32_t *slots, size_t pool_streams, float *pool, float *out);
 
 /* ss_stack_frames_signal on device pointers (d_window: frame_len floats in device memory, or NULL) */
 int ss_stack_frames_signal_device(const float *d_x, size_t n_samples, uint32_t sample_rate, float frame_length, float frame_stride,

@@ -1186,6 +1186,167 @@ int frame_stream_packed_host(const ss_config *cfg, int out_kind, const float *x,
     return rc;
 }
 
+// Ragged streaming STFT / mel spectrogram over a pool of stream states (ss_mel_spectrogram_stream_packed_device /
+// ss_stft_stream_packed_device), continuous mode: the rows of n_active entries of different hop counts, each over the pool row its
+// slot names, then the advance of the named rows -- a linear chain of two kernels on `stream`.  The tables are device arrays read by
+// the kernels only (StftStreamPackedArgs, ss_device.h); the grids come from n_active and total_rows.  Candidate order as
+// launch_stft_stream: the ragged streaming build of the 2048-point mel kernel where mel2048.ok, else that of the generic kernel.
+int launch_stft_stream_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n_active, const int64_t *d_so, const int64_t *d_ro,
+                              size_t total_rows, const int32_t *d_slots, size_t pool_streams, float *d_pool, float *out0, hipStream_t stream)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_active == 0) return SS_OK;
+    const ss::HostTables &h = cfg->host;
+    if (!h.d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
+    if (!d_x || !d_so || !d_ro || !d_slots || !d_pool || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull || total_rows >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
+    const size_t S = h.params.fft_points - h.d.hop;  // >= hop >= 1
+    const size_t F = h.params.fft_points / 2 + 1;
+    const size_t out_floats = total_rows * (out_kind == ss::OUT_STFT ? 2 * F : h.params.num_filters);
+    const size_t pbytes = pool_streams * S * sizeof(float);
+    // (how far x reaches is in the device tables: its first sample stands for it here, the host form checks the whole range)
+    if (ranges_overlap(d_pool, pbytes, out0, out_floats * sizeof(float)) || ranges_overlap(d_pool, pbytes, d_x, sizeof(float)))
+        return ss::fail(SS_ERR_ARG, "the pool overlaps the input or the output");
+    {
+        const int drc = check_device(cfg);  // see launch_frames
+        if (drc) return drc;
+        const int erc = pending_device_error(cfg);
+        if (erc) return erc;
+    }
+    ss::FrontArgs a{};
+    fill_common(cfg, a);
+    a.x = d_x;
+    a.hop = h.d.hop;
+    a.n_pad = 0u;  // continuous mode: every row is real
+    a.window = cfg->d_window_stft;
+    a.scale = h.d.wnorm;
+    a.out_kind = out_kind;
+    a.out0 = out0;
+    ss::StftStreamPackedArgs sp{};
+    sp.e.pool = d_pool;
+    sp.e.state_len = static_cast<uint32_t>(S);
+    sp.e.so = reinterpret_cast<const long long *>(d_so);
+    sp.e.ro = reinterpret_cast<const long long *>(d_ro);
+    sp.e.slots = d_slots;
+    sp.e.n_active = static_cast<uint32_t>(n_active);
+    sp.e.pool_streams = static_cast<uint32_t>(pool_streams);
+    sp.e.total_rows = static_cast<uint32_t>(total_rows);
+    sp.e.step = h.d.hop;
+    sp.e.err = cfg->d_err;
+    ss::LaunchInfo info{};
+    hipError_t e = hipErrorInvalidValue;
+    if (!ss::dbg_force_generic() && out_kind == ss::OUT_MEL && cfg->mel2048.ok) {
+        ss::Mel2048Args m{};
+        m.x = d_x;
+        m.hop = a.hop;
+        m.scale = a.scale;
+        m.tab = cfg->d_mel2048_tab;
+        m.fullp = cfg->mel2048.fullp;
+        m.mel_wpitch = cfg->mel2048.wpitch;
+        for (int s = 0; s < 4; ++s) m.mel_q4[s] = cfg->mel2048.q4[s];
+        m.n_filters = a.n_filters;
+        m.out = out0;
+        m.ctl = cfg->d_err;
+        e = ss::launch_mel_c1024_stream_packed(m, sp, stream, cfg->num_cus, &info);
+        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel -> the generic build
+        if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mel_c1024_stream_packed");
+    }
+    if (e != hipSuccess) {
+        e = ss::launch_front_generic_stream_packed(a, sp, h.d.log2c, stream, cfg->num_cus, &info);
+        if (e != hipSuccess) return hip_fail(e, "launch_front_generic_stream_packed");
+    }
+    g_last_kernel = info.kernel_name;
+    e = ss::launch_stream_advance_packed(sp.e, d_x, stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_stream_advance_packed");
+    return SS_OK;
+}
+
+// Host-pointer form, as frame_stream_packed_host: the tables are checked here, before anything touches the device; then x, the
+// tables and the n_active named pool rows (a compact block whose row i is entry i's) go up, the output and the named rows come down
+// on the config's first host-pipeline stream.  The caller's pool is written only once everything before it succeeded.
+int stft_stream_packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_active, const int64_t *so, const int32_t *slots,
+                            size_t pool_streams, float *pool, float *out0)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (n_active == 0) return SS_OK;
+    const ss::HostTables &h = cfg->host;
+    if (!h.d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
+    if (!x || !so || !slots || !pool || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
+    std::vector<int64_t> ro(n_active + 1);
+    int rc = ss_stream_packed_row_offsets(&h.params, n_active, so, ro.data());
+    if (rc) return rc;
+    {
+        std::unordered_set<int32_t> seen;
+        seen.reserve(n_active);
+        for (size_t i = 0; i < n_active; ++i) {
+            if (slots[i] < 0 || static_cast<size_t>(slots[i]) >= pool_streams)
+                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is outside the pool of " +
+                                                std::to_string(pool_streams) + " rows");
+            if (!seen.insert(slots[i]).second)
+                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is named twice in one call");
+        }
+    }
+    const size_t rows = static_cast<size_t>(ro[n_active]), samples = static_cast<size_t>(so[n_active]);
+    if (rows >= 0x80000000ull) return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    const size_t S = h.params.fft_points - h.d.hop;
+    const size_t out_floats = rows * (out_kind == ss::OUT_STFT ? 2 * (h.params.fft_points / 2 + 1) : h.params.num_filters);
+    const size_t pbytes = pool_streams * S * sizeof(float);
+    if (ranges_overlap(pool, pbytes, x, samples * sizeof(float)) || ranges_overlap(pool, pbytes, out0, out_floats * sizeof(float)))
+        return ss::fail(SS_ERR_ARG, "the pool overlaps the input or the output");
+    if ((rc = check_device(cfg))) return rc;
+    // the named pool rows, row i = entry i's
+    std::vector<float> rows_host(n_active * S);
+    std::vector<int32_t> iota(n_active);
+    for (size_t i = 0; i < n_active; ++i) {
+        iota[i] = static_cast<int32_t>(i);
+        std::memcpy(rows_host.data() + i * S, pool + static_cast<size_t>(slots[i]) * S, S * sizeof(float));
+    }
+    ss_config::HostPipe &hp = cfg->pipe;
+    std::lock_guard<std::mutex> lock(hp.mu);
+    if (!hp.stream[0]) {
+        SS_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
+        SS_HIP(hipEventCreateWithFlags(&hp.done[0], hipEventDisableTiming));
+    }
+    hipStream_t st = hp.stream[0];
+    const size_t tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * S * sizeof(float);
+    DeviceBuf dx, dso, dro, dsl, dp, d0;
+    // (x and the output keep one float where the call has none: the device form takes no null buffer)
+    if ((rc = dx.alloc((samples ? samples : 1) * sizeof(float))) || (rc = dso.alloc(tbytes)) || (rc = dro.alloc(tbytes)) ||
+        (rc = dsl.alloc(n_active * sizeof(int32_t))) || (rc = dp.alloc(sbytes)) || (rc = d0.alloc((out_floats ? out_floats : 1) * sizeof(float))))
+        return rc;
+    hipError_t e = samples ? hipMemcpyAsync(dx.p, x, samples * sizeof(float), hipMemcpyHostToDevice, st) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, tbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dro.p, ro.data(), tbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dsl.p, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dp.p, rows_host.data(), sbytes, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
+    if (rc == SS_OK)
+        rc = launch_stft_stream_packed(cfg, out_kind, dx.as<const float>(), n_active, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
+                                       dsl.as<const int32_t>(), n_active, dp.as<float>(), d0.as<float>(), st);
+    if (rc == SS_OK && out_floats > 0) {
+        e = hipMemcpyAsync(out0, d0.p, out_floats * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (D2H)");
+    }
+    // the copies may still touch the caller's buffers and ours: synchronise whatever happened
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "stream pool host call");
+    if (rc == SS_OK) rc = pending_device_error(cfg);
+    if (rc == SS_OK) {
+        e = hipMemcpyAsync(rows_host.data(), dp.p, sbytes, hipMemcpyDeviceToHost, st);
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e != hipSuccess || es != hipSuccess) rc = hip_fail(e != hipSuccess ? e : es, "hipMemcpyAsync (pool rows D2H)");
+        if (rc == SS_OK)
+            for (size_t i = 0; i < n_active; ++i)
+                std::memcpy(pool + static_cast<size_t>(slots[i]) * S, rows_host.data() + i * S, S * sizeof(float));
+    }
+    return rc;
+}
+
 // stack_frames (processing.rs:65-129): frames[clip][t][i] = x[clip][t * step + i] (* window[i]); one thread per element,
 // neighbouring threads on neighbouring samples of a frame.  frame_mode as in the fused kernels' loaders: contract framing,
 // zero_padding = true (zeros past the signal), the literal exact_chunks copy (all-zero rows for > 2 frames, x[0 .. flen & ~1]
@@ -2475,6 +2636,34 @@ int ss_mfe_stream_packed(const ss_config *cfg, const float *x, size_t n_active, 
                          size_t pool_streams, float *pool, float *feat, float *energy)
 {
     return frame_stream_packed_host(cfg, ss::OUT_MFE, x, n_active, sample_offsets, slots, pool_streams, 1u, pool, feat, energy);
+}
+
+int ss_mel_spectrogram_stream_packed_device(const ss_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                            const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                            float *d_pool, float *d_out, void *stream)
+{
+    return launch_stft_stream_packed(cfg, ss::OUT_MEL, d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams,
+                                     d_pool, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_stft_stream_packed_device(const ss_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                 const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                 float *d_pool, float *d_out, void *stream)
+{
+    return launch_stft_stream_packed(cfg, ss::OUT_STFT, d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams,
+                                     d_pool, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_mel_spectrogram_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets,
+                                     const int32_t *slots, size_t pool_streams, float *pool, float *out)
+{
+    return stft_stream_packed_host(cfg, ss::OUT_MEL, x, n_active, sample_offsets, slots, pool_streams, pool, out);
+}
+
+int ss_stft_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                          size_t pool_streams, float *pool, float *out)
+{
+    return stft_stream_packed_host(cfg, ss::OUT_STFT, x, n_active, sample_offsets, slots, pool_streams, pool, out);
 }
 
 int ss_preemphasis_device(const float *d_x, size_t n_samples, long shift, float cof, float *d_y, void *stream)

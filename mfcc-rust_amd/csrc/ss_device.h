@@ -357,6 +357,32 @@ hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const Fr
 // The pool's state advance, a second stream-ordered launch behind the rows: for every ok entry with n_i > 0, pool row slots[i] := the
 // last S samples of (old row ++ the entry's chunk), in place (ss_stream_advance's discipline).  Grid-stride over the entries.
 hipError_t launch_stream_advance_packed(const FrameStreamPackedArgs &s, const float *x, hipStream_t stream);
+
+// Ragged streaming STFT / mel spectrogram over a pool of stream states (ss_mel_spectrogram_stream_packed_device /
+// ss_stft_stream_packed_device): the same tables on the STFT path, continuous mode.  The entry block is the frame pool's, with
+// step = hop, state_len = fft_points - hop and lead unused, so that stream_entry(), stream_entry_find(), stream_check_entries() and
+// ss_stream_advance_packed ("last S samples of old row ++ chunk": the dense continuous advance) serve both families; the type of
+// its own only selects the STFT-path builds in the kernels' trailing argument packs.  Row t of an entry is row t of a dense
+// continuous call on that stream alone (StreamArgs above): its window is the W samples that end at chunk sample (t + 1) * hop, and
+// sample p < 0 is pool[slots[i] * S + S + p].
+struct StftStreamPackedArgs {
+    FrameStreamPackedArgs e;
+};
+// The last i < n_active with ro[i] <= g, as stream_entry_find gives it, from a lower bound c the caller already knows (the entry
+// of an earlier row): a few steps along the row offsets -- entries without rows share their ro with their successor and are
+// stepped over -- and the binary search where that does not get there.
+__device__ __forceinline__ unsigned stream_entry_seek(const FrameStreamPackedArgs &v, unsigned c, unsigned g)
+{
+    const long long gs = static_cast<long long>(g);
+    for (int k = 0; k < 4 && c + 1 < v.n_active && v.ro[c + 1] <= gs; ++k) ++c;
+    if (c + 1 < v.n_active && v.ro[c + 1] <= gs) c = stream_entry_find(v, g);
+    return c;
+}
+// the ragged streaming build of ss_front_generic's STFT / mel path (any fft_points, chirp-z included; mel and stft output): a as
+// for launch_front_generic_stream with x = the packed chunks and n_pad = 0; batch / n_samples / rows / real_rows / ld are unused.
+// The grid comes from s.e.total_rows (one workgroup where it is 0: the entry pass).
+hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
+                                              int num_cus, LaunchInfo *info);
 #if SS_LAB
 // Test aid (lab library): every word of every CU's LDS := 0xFFFFFFFF (ss_debug_poison_lds).
 hipError_t launch_poison_lds(hipStream_t stream, int num_cus);
@@ -482,6 +508,12 @@ hipError_t launch_mel_c1024_stream(const Mel2048Args &a, const StreamArgs &s, hi
 // depend on the clips beside it); a: x / out = the packed blocks, batch / n_samples / rows / real_rows unused.  hipErrorInvalidValue
 // before the launch for stft output, a bank that reaches past (F+1)/2 (fullp) or a shape that does not fit
 hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
+// ragged streaming over a pool of stream states (StftStreamPackedArgs above) on the twelve-wave mel build, whatever the unit count
+// (an entry's bits must not depend on the entries beside it); a: x / out = the packed blocks, n_pad = 0, batch / n_samples / rows /
+// real_rows unused.  hipErrorInvalidValue before the launch for stft output, a bank that reaches past (F+1)/2 (fullp) or a shape
+// that does not fit
+hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, hipStream_t stream, int num_cus,
+                                          LaunchInfo *info);
 // several blocks of channels in one launch of the twelve-wave mel build (a: one block's arguments; x / out / batch are ignored);
 // hipErrorInvalidValue before the launch where the shape has no batch-table build
 hipError_t launch_mel_c1024_multi(const Mel2048Args &a, int n_batches, const float *const *d_x, float *const *d_out, const size_t *channels,

@@ -1438,6 +1438,32 @@ int ss_frame_stream_packed_row_offsets(const ss_params *p, size_t n_active, cons
     return SS_OK;
 }
 
+int ss_stream_packed_row_offsets(const ss_params *p, size_t n_active, const int64_t *sample_offsets, int64_t *row_offsets)
+{
+    if (!p || !sample_offsets || !row_offsets) return ss::fail(SS_ERR_ARG, "null argument");
+    size_t S = 0;
+    int rc = ss_stream_state_len(p, &S);  // no STFT path: SS_ERR_BAD_CONFIG
+    if (rc) return rc;
+    ss::Derived d;
+    if ((rc = ss::derive(*p, d))) return rc;
+    if (n_active > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many entries");
+    if (sample_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "sample_offsets[0] must be 0");
+    const int64_t hop = static_cast<int64_t>(d.hop);
+    int64_t rows = 0;
+    row_offsets[0] = 0;
+    for (size_t i = 0; i < n_active; ++i) {
+        const int64_t len = sample_offsets[i + 1] - sample_offsets[i];
+        if (sample_offsets[i + 1] < sample_offsets[i]) return ss::fail(SS_ERR_ARG, "sample_offsets decrease at entry " + std::to_string(i));
+        if (len > 0x7fffffff) return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + " is longer than 2^31 - 1 samples");
+        if (len % hop)
+            return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + " (" + std::to_string(len) +
+                                            " samples): continuous streaming takes whole hops of " + std::to_string(hop) + " samples");
+        rows += len / hop;  // one row per hop; an entry without samples has none
+        row_offsets[i + 1] = rows;
+    }
+    return SS_OK;
+}
+
 int ss_filterbank(const ss_params *p, float *fb, int32_t *idx)
 {
     if (!p || !fb) return ss::fail(SS_ERR_ARG, "null argument");

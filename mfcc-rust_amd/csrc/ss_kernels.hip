@@ -13,6 +13,9 @@
 // ss_stream_advance_packed moves the named pool rows on behind it.
 // ss_front_generic<LOG2C, BLU, VarRowsArgs> (reported as ss_front_generic_varrows<LOG2C>): the STFT / mel path over packed clips of
 // different lengths (VarRowsArgs, ss_device.h), handed out in tiles of packed rows.
+// ss_front_generic<LOG2C, BLU, StftStreamPackedArgs> (reported as ss_front_generic_streamp<LOG2C>): the STFT / mel path over a pool
+// of stream states -- the packed-rows tiles with every row on the pool row its entry names (StftStreamPackedArgs, ss_device.h);
+// ss_stream_advance_packed moves the named pool rows on behind it.
 //
 //   * A real frame of N = 2C samples is packed as C complex points z[n] = x[2n] + i x[2n+1]
 //     and transformed by a Stockham autosort FFT whose butterflies live in registers: every
@@ -249,8 +252,10 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
 // the row's entry (its chunk, its row within the chunk, its pool row) comes from the device tables (FrameStreamPackedArgs).
 // VARR: the STFT / mel path of launch_front_generic_varrows -- a workgroup visit is a tile of packed rows, every row finds its own
 // clip; the transposed mel flush writes each row into its clip's [M x R_b] block.
-// (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs, one FrameStreamPackedArgs or one VarRowsArgs -- an empty pack leaves the argument block of the
-// equal-length builds exactly as it was)
+// SPR: VARR's tiles over the entries of a ragged streaming call (launch_front_generic_stream_packed) -- a row's entry (its chunk, its
+// row within the chunk, its pool row) comes from the device tables (StftStreamPackedArgs), its window as in STREAM.
+// (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs, one FrameStreamPackedArgs, one VarRowsArgs or one
+// StftStreamPackedArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
 template <int LOG2C, bool BLU, typename... V>
 __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
 {
@@ -259,6 +264,8 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     constexpr bool FSP = (std::is_same_v<V, FrameStreamPackedArgs> || ...);
     constexpr bool FSTREAM = FSP || (std::is_same_v<V, FrameStreamArgs> || ...);
     constexpr bool VARR = (std::is_same_v<V, VarRowsArgs> || ...);
+    constexpr bool SPR = (std::is_same_v<V, StftStreamPackedArgs> || ...);
+    [[maybe_unused]] const StftStreamPackedArgs *sp = pack_arg<StftStreamPackedArgs>(vargs...);
     [[maybe_unused]] const VarRowsArgs *ra = pack_arg<VarRowsArgs>(vargs...);
     [[maybe_unused]] const VarlenArgs *va = pack_arg<VarlenArgs>(vargs...);
     [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(vargs...);
@@ -282,7 +289,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     // MEL mode: transposed output tile [M][rows_tile + 1] after all slots
     float *tile = reinterpret_cast<float *>(smem_raw + slot_bytes * G::FPB);
 
-    const bool mel_mode = STREAM || VARR || (!VAR && !FSTREAM && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT));
+    const bool mel_mode = STREAM || VARR || SPR || (!VAR && !FSTREAM && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT));
     const int F = BLU ? static_cast<int>(a.blu_n / 2 + 1) : G::F;  // bins per row
 
     if (!mel_mode) {
@@ -465,10 +472,13 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
             }
             frame_sync<LOG2C>();  // zbuf / prow / frow / red are private to the frame's slot
         }
-    } else if constexpr (VARR) {
+    } else if constexpr (VARR || SPR) {
         // ---------------- STFT / mel-spectrogram path over packed clips: tiles of TILE packed rows -------
         // (the rows of one tile may belong to several clips: a long clip among short ones is spread over the grid like the rest)
-        varrows_check_clips(*ra, blockIdx.x * kBlock + tid, gridDim.x * kBlock);
+        // SPR: the "clips" are the entries of a ragged streaming call -- whole hops, no padding rows, and a window sample before the
+        // chunk comes from the entry's pool row
+        if constexpr (SPR) stream_check_entries(sp->e, blockIdx.x * kBlock + tid, gridDim.x * kBlock);
+        else varrows_check_clips(*ra, blockIdx.x * kBlock + tid, gridDim.x * kBlock);
         const int W = BLU ? static_cast<int>(a.blu_n) : G::N;
         constexpr int TILE = 32;  // rows buffered before a transposed flush
         // per tile row, behind the mel tile: the output word of its (m = 0, r) element (-1: the row is not written) and its clip's R_b
@@ -476,7 +486,9 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
         rtab = (rtab + 7) & ~static_cast<size_t>(7);
         long long *t_base = reinterpret_cast<long long *>(smem_raw + rtab);
         unsigned *t_rows = reinterpret_cast<unsigned *>(t_base + TILE);
-        const unsigned long long total = ra->total_rows;
+        unsigned long long total;
+        if constexpr (SPR) total = sp->e.total_rows;
+        else total = ra->total_rows;
         const unsigned long long tiles = (total + TILE - 1) / TILE;
         for (unsigned long long tg = blockIdx.x; tg < tiles; tg += gridDim.x) {
             const unsigned long long g0 = tg * TILE;
@@ -485,7 +497,15 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 const int rl = rp + slot;  // row within the tile
                 const unsigned long long g = g0 + rl;
                 // rows past the last clip (a larger output block) are left alone; rows of an inconsistent clip are skipped
-                const VarRowClip c = varrows_clip(*ra, rl < rt ? varrows_find(*ra, g) : 0u);
+                VarRowClip c;
+                [[maybe_unused]] const float *srow = nullptr;  // SPR: the entry's pool row, indexed from its end (sample p < 0 is srow[p])
+                if constexpr (SPR) {
+                    const StreamEntry en = stream_entry(sp->e, rl < rt ? stream_entry_find(sp->e, static_cast<unsigned>(g)) : 0u);
+                    c = VarRowClip{en.s0, en.r0, en.n, en.R, en.ok};
+                    if (en.ok) srow = sp->e.pool + static_cast<unsigned long long>(en.slot) * sp->e.state_len + sp->e.state_len;
+                } else {
+                    c = varrows_clip(*ra, rl < rt ? varrows_find(*ra, g) : 0u);
+                }
                 const long long r = static_cast<long long>(g) - c.r0;  // row within the clip
                 const bool valid = rl < rt && c.ok && r >= 0 && r < static_cast<long long>(c.R);
                 const long long Rreal = c.R > a.n_pad ? static_cast<long long>(c.R - a.n_pad) : 0ll;
@@ -496,6 +516,10 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 const long long start = (r + a.n_pad + 1) * static_cast<long long>(a.hop) - W;
                 auto wsample = [&](int i) -> float {
                     const long long idx = start + i;
+                    if constexpr (SPR) {  // (idx >= -S: a row's window ends at least one hop into the chunk)
+                        if (!active || i >= W || idx >= ns) return 0.0f;
+                        return (idx < 0 ? srow[idx] : xc[idx]) * a.window[i];
+                    }
                     return active && i < W && idx >= 0 && idx < ns ? xc[idx] * a.window[i] : 0.0f;
                 };
                 float2 v[16];
@@ -689,6 +713,28 @@ hipError_t launch_one_varrows(const FrontArgs &a, const VarRowsArgs &v, hipStrea
     const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
     if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
     hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, VarRowsArgs>), dim3(grid), dim3(kBlock), lds, stream, a, v);
+    return hipGetLastError();
+}
+
+template <int LOG2C, bool BLU>
+hipError_t launch_one_streamp(const FrontArgs &a, const StftStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info,
+                              const char *name)
+{
+    // the packed-rows carve (launch_one_varrows)
+    const size_t lds = front_lds_bytes<LOG2C>(a) + 32 * (sizeof(long long) + sizeof(unsigned)) + 16;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, StftStreamPackedArgs>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    // at least one workgroup: the entry pass runs even where the output block has no rows
+    unsigned long long work = (static_cast<unsigned long long>(s.e.total_rows) + 31) / 32;
+    if (work == 0) work = 1;
+    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
+    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
+    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
+    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, StftStreamPackedArgs>), dim3(grid), dim3(kBlock), lds, stream, a, s);
     return hipGetLastError();
 }
 
@@ -1028,6 +1074,43 @@ hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const Fr
         case 10: return launch_one_fstreamp<10, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<10>");
         case 11: return launch_one_fstreamp<11, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<11>");
         case 12: return launch_one_fstreamp<12, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<12>");
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
+                                              int num_cus, LaunchInfo *info)
+{
+    if (a.out_kind != OUT_MEL && a.out_kind != OUT_STFT) return hipErrorInvalidValue;
+    // the windows the kernel reads: W samples ending (t + 1) hops into the chunk, the first W - hop = S of them at most in the pool row
+    const uint32_t W = a.blu_n ? a.blu_n : 2u << log2c;
+    if (s.e.n_active == 0 || a.hop == 0 || s.e.step != a.hop || a.n_pad != 0 || s.e.state_len + a.hop != W || !s.e.pool ||
+        s.e.total_rows >= 0x7fffffffu)
+        return hipErrorInvalidValue;
+    if (a.blu_n) {
+        switch (log2c) {
+            case 4: return launch_one_streamp<4, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<4,chirpz>");
+            case 5: return launch_one_streamp<5, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<5,chirpz>");
+            case 6: return launch_one_streamp<6, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<6,chirpz>");
+            case 7: return launch_one_streamp<7, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<7,chirpz>");
+            case 8: return launch_one_streamp<8, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<8,chirpz>");
+            case 9: return launch_one_streamp<9, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<9,chirpz>");
+            case 10: return launch_one_streamp<10, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<10,chirpz>");
+            case 11: return launch_one_streamp<11, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<11,chirpz>");
+            case 12: return launch_one_streamp<12, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<12,chirpz>");
+            default: return hipErrorInvalidValue;
+        }
+    }
+    switch (log2c) {
+        case 4: return launch_one_streamp<4, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<4>");
+        case 5: return launch_one_streamp<5, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<5>");
+        case 6: return launch_one_streamp<6, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<6>");
+        case 7: return launch_one_streamp<7, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<7>");
+        case 8: return launch_one_streamp<8, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<8>");
+        case 9: return launch_one_streamp<9, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<9>");
+        case 10: return launch_one_streamp<10, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<10>");
+        case 11: return launch_one_streamp<11, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<11>");
+        case 12: return launch_one_streamp<12, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<12>");
         default: return hipErrorInvalidValue;
     }
 }

@@ -28,6 +28,9 @@
 // Packed builds of the twelve-wave kernel (a VarRowsArgs in the trailing argument pack, launch_mel_c1024_varlen, reported as
 // ss_mel_c1024v<...>): units are row pairs of the packed row space, every half-wave finds its own clip (a pair may straddle two:
 // the two rows of a wave are computed independently -- own registers, own exchange region, own P row, partners within the half).
+// Ragged streaming builds of the twelve-wave kernel (a StftStreamPackedArgs in the trailing argument pack,
+// launch_mel_c1024_stream_packed, reported as ss_mel_c1024sp<...>): the packed builds' units over the entries of a pool call; an
+// entry may have no rows, so the cursor steps over such entries, and the edge branch reads the entry's pool row.
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 #include "ss_internal.h"
@@ -356,13 +359,21 @@ __global__ __launch_bounds__(kWavesM * 64) void ss_mel_c1024(const Mel2048Args a
 // pairs, each block with its own input and output (BatchTable, ss_device.h; Seg / seg_of, ss_wave.h).
 // VARR (ss_mel_spectrogram_packed_device): the units are the row pairs of the packed row space (VarRowsArgs); a per-wave cursor over
 // the row offsets finds the clip of the unit's first row, a half-wave's row lies at most one clip further (every clip has a row).
+// SPOOL (ss_mel_spectrogram_stream_packed_device): VARR's units over the entries of a ragged streaming call (StftStreamPackedArgs);
+// entries without rows share their row offset with their successor, so any number of them may lie between the two rows of a pair:
+// both lookups go through stream_entry_seek (a few cursor steps, else the binary search).  Samples before the chunk come from the
+// entry's pool row (stream_window); a pair inside one chunk takes the equal-length loads.
 template <bool FIXMEL, bool STFT = false, bool MULTI = false, typename... SA>
 __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args a, const MultiArg<MULTI> mt, const SA... sargs)
 {
     constexpr bool STREAM = (std::is_same_v<SA, StreamArgs> || ...);
     constexpr bool VARR = (std::is_same_v<SA, VarRowsArgs> || ...);
     [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(sargs...);
+    constexpr bool SPOOL = (std::is_same_v<SA, StftStreamPackedArgs> || ...);
+    constexpr bool PACKED = VARR || SPOOL;  // units are row pairs of a packed row space
     [[maybe_unused]] const VarRowsArgs *ra = pack_arg<VarRowsArgs>(sargs...);
+    [[maybe_unused]] const StftStreamPackedArgs *pa = pack_arg<StftStreamPackedArgs>(sargs...);
+    static_assert(!SPOOL || (!STFT && !MULTI && !STREAM && !VARR), "the ragged streaming build is a one-block mel-output build");
     static_assert(!(MULTI && STFT), "the batch-table build is a mel-output build");
     static_assert(!(MULTI && STREAM), "the streaming build takes one block");
     static_assert(!VARR || (!STFT && !MULTI && !STREAM), "the packed build is a one-block mel-output build");
@@ -378,6 +389,7 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
     unsigned long long units = static_cast<unsigned long long>(a.batch) * pairs;
     if constexpr (MULTI) units = a.batch;  // (the launcher hands over the launch's unit count: the sum over the blocks)
     if constexpr (VARR) units = (ra->total_rows + 1) / 2;  // (the launcher keeps it below 2^30)
+    if constexpr (SPOOL) units = (static_cast<unsigned long long>(pa->e.total_rows) + 1) / 2;
     // Work distribution: the workgroup owns a contiguous range of units (neighbouring units share three quarters of their samples:
     // L1 / L2 locality), its waves pull them from an LDS counter.
     const unsigned u_lo = static_cast<unsigned>(units * blockIdx.x / gridDim.x);
@@ -403,7 +415,7 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
 #define SS_P3(k) do { } while (0)
 #endif
     unsigned item = u_lo + wave;
-    [[maybe_unused]] unsigned cursor = 0;  // VARR: the clip of the wave's last unit's first row (a wave's claims only increase)
+    [[maybe_unused]] unsigned cursor = 0;  // VARR / SPOOL: the clip of the wave's last unit's first row (a wave's claims only increase)
     Seg cs{};  // MULTI: the block of the current unit
     if constexpr (MULTI) cs = seg_of(mt.m, min(static_cast<unsigned>(__builtin_amdgcn_readfirstlane(item)), u_hi - 1));
     SS_PRIOL(SS_P_TOP);
@@ -431,12 +443,13 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
         const float4 *s_tw2 = reinterpret_cast<const float4 *>(s_tab + L::kTw2 + j * L::kTw2Pitch);
         const float4 *s_twn4 = reinterpret_cast<const float4 *>(s_tab + L::kTwn + j * L::kTwnPitch);
         const float4 *s_win4 = reinterpret_cast<const float4 *>(s_tab + L::kWin + j * L::kWinPitch);
-        const unsigned clip = VARR ? 0u : unit / pairs;
-        const int r = VARR ? 0 : static_cast<int>(unit - clip * pairs) * 2 + half;
-        [[maybe_unused]] VarRowClip vc{};     // VARR: this half-wave's clip ...
+        const unsigned clip = PACKED ? 0u : unit / pairs;
+        const int r = PACKED ? 0 : static_cast<int>(unit - clip * pairs) * 2 + half;
+        [[maybe_unused]] VarRowClip vc{};     // VARR / SPOOL: this half-wave's clip (entry) ...
         [[maybe_unused]] long long vr = 0;    // ... its row in that clip
         [[maybe_unused]] bool vvalid = false;  // ... and whether the row is one of the clip's (consistent offsets) and is written
         [[maybe_unused]] bool vsame = false;   // ... and whether it is in the clip of the unit's first row
+        [[maybe_unused]] unsigned pslot = 0;   // SPOOL: the entry's pool row
         if constexpr (VARR) {
             const long long g0 = 2ll * unit;
             unsigned c = cursor;
@@ -450,11 +463,24 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
             vr = g - vc.r0;
             vvalid = static_cast<unsigned long long>(g) < ra->total_rows && vc.ok && vr >= 0 && vr < static_cast<long long>(vc.R);
         }
-        const bool in_rows = VARR ? vvalid : r < R;
+        if constexpr (SPOOL) {
+            const unsigned g0 = 2u * unit;
+            const unsigned c0 = stream_entry_seek(pa->e, cursor, g0);
+            cursor = c0;
+            const unsigned g = g0 + half;
+            const unsigned c = stream_entry_seek(pa->e, c0, g);  // (any number of entries without rows may lie between the two)
+            vsame = c == c0;
+            const StreamEntry en = stream_entry(pa->e, c);
+            vc = VarRowClip{en.s0, en.r0, en.n, en.R, en.ok};
+            vr = static_cast<long long>(g) - vc.r0;
+            vvalid = g < pa->e.total_rows && vc.ok && vr >= 0 && vr < static_cast<long long>(vc.R);
+            pslot = vvalid ? en.slot : 0u;
+        }
+        const bool in_rows = PACKED ? vvalid : r < R;
         SS_P3(0);
         // ---- the window of this half-wave's row (functions.rs:137-151: the last W samples ending at chunk r + n_pad) ----
         float2 v[32];
-        if constexpr (VARR) {
+        if constexpr (PACKED) {
             // the clip's own edges: zero before its first sample and past its last, 64-bit sample indices (a clip may start past
             // sample 2^31 of the packed buffer, and at either parity); rows >= real_rows of the clip are inactive (exact zeros)
             const long long rreal = vc.R > a.n_pad ? static_cast<long long>(vc.R - a.n_pad) : 0ll;
@@ -477,10 +503,17 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
             } else {
                 const float *xc = x_b + (vvalid ? vc.s0 : 0ll);
                 const long long base = start + 2 * j;
+                if constexpr (SPOOL) {
+                    // the dense streaming build's edge loads on the entry's chunk and pool row (an active row's window starts at most
+                    // S samples before the chunk and ends inside it: 32-bit indices)
+                    const StreamArgs row{pa->e.pool, pa->e.state_len};
+                    stream_window(row, xc, pslot, static_cast<int>(base), static_cast<int>(n), active, v);
+                } else {
 #pragma unroll
-                for (int e = 0; e < 32; ++e) {
-                    const long long p0 = base + 64 * e;
-                    v[e] = make_float2(active && p0 >= 0 && p0 < n ? xc[p0] : 0.f, active && p0 + 1 >= 0 && p0 + 1 < n ? xc[p0 + 1] : 0.f);
+                    for (int e = 0; e < 32; ++e) {
+                        const long long p0 = base + 64 * e;
+                        v[e] = make_float2(active && p0 >= 0 && p0 < n ? xc[p0] : 0.f, active && p0 + 1 >= 0 && p0 + 1 < n ? xc[p0 + 1] : 0.f);
+                    }
                 }
             }
         } else {
@@ -676,7 +709,7 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
                         off += a.mel_q4[s];
                     }
                 }
-                if constexpr (VARR) {
+                if constexpr (PACKED) {
                     // clip b's block [M x R_b] starts at out + M ro[b]
                     float *dst = out_b + vc.r0 * M + vr;
                     if (in_rows) {
@@ -705,6 +738,7 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
     life_end(a.stamps, life, blockIdx.x * kWavesM + (threadIdx.x >> 6));
     // VARR: the consistency pass over every clip (at the end: its loads would otherwise wait in line with the first samples)
     if constexpr (VARR) varrows_check_clips(*ra, blockIdx.x * (kWavesM * 64) + threadIdx.x, gridDim.x * (kWavesM * 64));
+    if constexpr (SPOOL) stream_check_entries(pa->e, blockIdx.x * (kWavesM * 64) + threadIdx.x, gridDim.x * (kWavesM * 64));
 #if SS_LAB && defined(SS_PROF3)
     if ((threadIdx.x & 63) == 0) p3[0] = p3n | (static_cast<unsigned long long>(__builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20)) << 32);
 #endif
@@ -808,6 +842,19 @@ hipError_t launch_mel_w12_varlen(const Mel2048Args &a, const VarRowsArgs &v, hip
                  : mel_go(ss_mel_c1024_w12<false, false, false, VarRowsArgs>, "ss_mel_c1024v<w12>", grid, 12, lds, stream, info, a, none, v);
 }
 
+hipError_t launch_mel_w12_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    const size_t lds = mel_lds_bytes(12, a.mel_wpitch);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    // an empty output block still gets one workgroup: the entry pass runs
+    const unsigned long long units = (static_cast<unsigned long long>(s.e.total_rows) + 1) / 2;
+    const unsigned grid = units ? mel_grid(units, 12, num_cus) : 1u;
+    const MultiArg<false> none{};
+    const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
+    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, StftStreamPackedArgs>, "ss_mel_c1024sp<w12,mel6321>", grid, 12, lds, stream, info, a, none, s)
+                 : mel_go(ss_mel_c1024_w12<false, false, false, StftStreamPackedArgs>, "ss_mel_c1024sp<w12>", grid, 12, lds, stream, info, a, none, s);
+}
+
 }  // namespace
 
 hipError_t launch_mel_c1024_multi(const Mel2048Args &a_in, int n_batches, const float *const *d_x, float *const *d_out, const size_t *channels,
@@ -898,6 +945,16 @@ hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, h
     // and a clip's bits must not depend on which other clips share the call
     if (a.out_stft || a.fullp || v.n_clips == 0 || v.total_rows >= (1ull << 31)) return hipErrorInvalidValue;
     return launch_mel_w12_varlen(a, v, stream, num_cus, info);
+}
+
+hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    // always twelve waves (never twelve_waves_win): see launch_mel_c1024_varlen -- an entry's bits must not depend on which other
+    // entries share the call.  The pool row holds the S = 2048 - hop samples in front of the chunk that a window can reach.
+    if (a.out_stft || a.fullp || s.e.n_active == 0 || s.e.total_rows >= 0x7fffffffu || a.hop == 0 || a.n_pad != 0 || s.e.step != a.hop ||
+        s.e.state_len + a.hop != 2048u || !s.e.pool)
+        return hipErrorInvalidValue;
+    return launch_mel_w12_stream_packed(a, s, stream, num_cus, info);
 }
 
 }  // namespace ss

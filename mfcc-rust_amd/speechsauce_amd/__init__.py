@@ -25,7 +25,8 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "mel_spectrogram_packed",
            "mel_spectrogram_list", "stft_packed", "cmvn_packed", "cmvnw_packed", "power_to_db_packed", "lmfe_packed",
            "MelSpectrogramStream", "StftStream",
-           "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "SpeechConfig", "SpeechSauceError"]
+           "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool",
+           "SpeechConfig", "SpeechSauceError"]
 
 
 def _is_torch(x) -> bool:
@@ -920,15 +921,12 @@ class MfeStream(_FrameStreamBase):
         self._call(sig, n, config, [feat, energy], "ss_mfe_stream_device", "ss_mfe_stream", [])
         return feat, energy
 
-# ---- ragged streaming MFCC / mfe over a pool of stream states ----------------------------------------------------------------
+# ---- ragged streaming over a pool of stream states ---------------------------------------------------------------------------
 
-class _FrameStreamPoolBase(_FrameStreamBase):
-    """A pool of ``pool_streams`` live audio streams, each with the carried state of ``MfccStream`` / ``MfeStream``.  One call
-    serves any subset of them, each with its own number of whole hops (zero included): ``pool(chunks, slots)`` with ``chunks`` a
-    list of 1-D float32 arrays / tensors, or one packed 1-D buffer plus ``lengths=``, and ``slots`` the pool row of each chunk
-    (distinct).  Per stream the rows and the carried state are those of the dense class on that stream alone.  numpy in -> the
-    host-pointer call, ROCm tensors in -> the device call on the current stream.  See ``ss_mfcc_stream_packed`` in
-    ``include/speechsauce_amd.h``."""
+class _StreamPoolMixin:
+    """The pool plumbing of the ragged streaming classes, in front of a dense streaming base (``_FrameStreamBase`` or
+    ``_StreamBase``) whose ``n_streams`` is the pool size: the argument rules of ``pool(chunks, slots, lengths=None)``, the pool
+    block and its place, the offset tables and the call itself."""
 
     def __init__(self, pool_streams, *args):
         super().__init__(pool_streams, *args)
@@ -1030,6 +1028,15 @@ class _FrameStreamPoolBase(_FrameStreamBase):
                                              *extra, st, *ptrs))
 
 
+class _FrameStreamPoolBase(_StreamPoolMixin, _FrameStreamBase):
+    """A pool of ``pool_streams`` live audio streams, each with the carried state of ``MfccStream`` / ``MfeStream``.  One call
+    serves any subset of them, each with its own number of whole hops (zero included): ``pool(chunks, slots)`` with ``chunks`` a
+    list of 1-D float32 arrays / tensors, or one packed 1-D buffer plus ``lengths=``, and ``slots`` the pool row of each chunk
+    (distinct).  Per stream the rows and the carried state are those of the dense class on that stream alone.  numpy in -> the
+    host-pointer call, ROCm tensors in -> the device call on the current stream.  See ``ss_mfcc_stream_packed`` in
+    ``include/speechsauce_amd.h``."""
+
+
 class MfccStreamPool(_FrameStreamPoolBase):
     """Ragged streaming ``mfcc``: ``pool(chunks, slots)`` -> ``(rows [total_rows, num_cepstral], row_offsets)``; chunk ``i``'s
     ``len(chunk) // hop`` rows are ``rows[row_offsets[i]:row_offsets[i + 1]]`` (``row_offsets``: int64 numpy array).
@@ -1085,6 +1092,66 @@ class MfeStreamPool(_FrameStreamPoolBase):
             energy = np.empty((R,), dtype=np.float32)
         self._call_pool(packed, so, ro, sl, config, [feat, energy], "ss_mfe_stream_packed_device", "ss_mfe_stream_packed", [])
         return feat, energy, ro
+
+
+# ---- ragged streaming STFT / mel spectrogram over a pool of stream states ----------------------------------------------------
+
+class _StftStreamPoolBase(_StreamPoolMixin, _StreamBase):
+    """A pool of ``pool_streams`` live audio streams, each with the carried state of ``MelSpectrogramStream`` / ``StftStream`` in
+    continuous mode.  Called as the frame-path pools are: ``pool(chunks, slots, lengths=None)``, every chunk a whole number of
+    hops (zero included).  Per stream the rows and the carried state are those of the dense class on that stream alone.  See
+    ``ss_mel_spectrogram_stream_packed`` in ``include/speechsauce_amd.h``."""
+
+
+class MelSpectrogramStreamPool(_StftStreamPoolBase):
+    """Ragged streaming ``mel_spectrogram``: ``pool(chunks, slots)`` -> ``(out, row_offsets)``.  ``out`` is the flat float32 block
+    of ``num_filters * total_rows`` values in the layout of ``mel_spectrogram_packed``: chunk ``i``'s ``[num_filters, R_i]`` block,
+    ``R_i = len(chunk) // hop``, is ``out[num_filters * row_offsets[i]:num_filters * row_offsets[i + 1]]`` (``row_offsets``: int64
+    numpy array)."""
+
+    _what = "MelSpectrogramStreamPool"
+
+    def __init__(self, pool_streams, sampling_frequency, frame_length=0.020, num_filters=40, fft_length=512, low_frequency=0,
+                 high_frequency=None, **switches):
+        super().__init__(pool_streams, sampling_frequency, frame_length, 0.01, 13, num_filters, fft_length, low_frequency,
+                         high_frequency, True, "continuous", switches)
+
+    def __call__(self, chunks, slots, lengths=None):
+        packed, so, ro, sl, config = self._prepare_pool(chunks, slots, lengths)
+        n = config.params.num_filters * int(ro[-1])
+        if _is_torch(packed):
+            import torch
+
+            out = torch.empty((n,), dtype=torch.float32, device=packed.device)
+        else:
+            out = np.empty((n,), dtype=np.float32)
+        self._call_pool(packed, so, ro, sl, config, [out], "ss_mel_spectrogram_stream_packed_device",
+                        "ss_mel_spectrogram_stream_packed", [])
+        return out, ro
+
+
+class StftStreamPool(_StftStreamPoolBase):
+    """Ragged streaming ``stft``: ``pool(chunks, slots)`` -> ``(complex64 [total_rows, fft_length // 2 + 1], row_offsets)``; chunk
+    ``i``'s rows are ``row_offsets[i]:row_offsets[i + 1]``."""
+
+    _what = "StftStreamPool"
+
+    def __init__(self, pool_streams, sampling_frequency, frame_length=0.020, fft_length=512, **switches):
+        super().__init__(pool_streams, sampling_frequency, frame_length, 0.01, 13, 40, fft_length, 0, None, True, "continuous",
+                         switches)
+
+    def __call__(self, chunks, slots, lengths=None):
+        packed, so, ro, sl, config = self._prepare_pool(chunks, slots, lengths)
+        shape = (int(ro[-1]), config.params.fft_points // 2 + 1, 2)
+        if _is_torch(packed):
+            import torch
+
+            out = torch.empty(shape, dtype=torch.float32, device=packed.device)
+            self._call_pool(packed, so, ro, sl, config, [out], "ss_stft_stream_packed_device", "ss_stft_stream_packed", [])
+            return torch.view_as_complex(out), ro
+        out = np.empty(shape, dtype=np.float32)
+        self._call_pool(packed, so, ro, sl, config, [out], "ss_stft_stream_packed_device", "ss_stft_stream_packed", [])
+        return out.view(np.complex64)[..., 0], ro
 
 
 def stack_frames(signal, sampling_frequency, frame_length=0.020, frame_stride=0.020, filter=None, zero_padding=False, **switches):
