@@ -115,6 +115,29 @@ struct VarlenArgs {
 };
 constexpr unsigned kVarlenError = 2u;
 
+// The offset tables of the packed layouts (fo / ro below: n non-decreasing offsets, the rows of clip or entry i start at off[i]).
+// The owner of row g: the last i < n with off[i] <= g (binary search; any i for offsets that are not non-decreasing -- the decoders
+// below then find them inconsistent, or g outside the owner's rows.  Entries without rows share their offset with their successor
+// and are stepped over; the caller still checks g < off[i + 1]).
+__device__ __forceinline__ unsigned offset_find(const long long *off, unsigned n, long long g)
+{
+    unsigned lo = 0u, hi = n;
+    while (hi - lo > 1u) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (off[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// The same from a lower bound c the caller already knows (the owner of an earlier row): a few steps along the offsets, and the
+// binary search where that does not get there.
+__device__ __forceinline__ unsigned offset_seek(const long long *off, unsigned n, unsigned c, long long g)
+{
+    for (int k = 0; k < 4 && c + 1 < n && off[c + 1] <= g; ++k) ++c;
+    if (c + 1 < n && off[c + 1] <= g) c = offset_find(off, n, g);
+    return c;
+}
+
 // Frames of a clip of L samples, as ss::num_frames computes them on the host (processing.rs:101 in f32; padded: ceil; centred:
 // 1 + L / step).  0: the clip yields none (the host rejects it) or is longer than 2^31 - 1 samples.
 __device__ __forceinline__ unsigned varlen_frames(const VarlenArgs &v, uint32_t flen, uint32_t step, long long L)
@@ -145,19 +168,6 @@ __device__ __forceinline__ VarClip varlen_clip(const VarlenArgs &v, uint32_t fle
     c.ok = c.T > 0u && c.s0 >= 0 && c.f0 >= 0 && f1 - c.f0 == static_cast<long long>(c.T) &&
            static_cast<unsigned long long>(f1) <= v.total_frames;
     return c;
-}
-// The clip that owns output row g: the last b < n_clips with fo[b] <= g (binary search; any b for offsets that are not
-// non-decreasing -- varlen_clip then finds them inconsistent, or g outside the clip's rows).
-__device__ __forceinline__ unsigned varlen_find(const VarlenArgs &v, unsigned long long g)
-{
-    unsigned lo = 0u, hi = v.n_clips;
-    const long long gs = static_cast<long long>(g);
-    while (hi - lo > 1u) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (v.fo[mid] <= gs) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 // feature.rs:126-131 for a clip of T frames (n = T * M as f32): the host's g * (1 / sqrtf(2 n)) and g * (1 / sqrtf(4 n)),
 // correctly rounded step by step.  (sqrtf and the division are correctly rounded in HIP's default fp32 mode; __fsqrt_rn is not
@@ -219,18 +229,6 @@ __device__ __forceinline__ VarRowClip varrows_clip(const VarRowsArgs &v, unsigne
     c.ok = c.R > 0u && c.s0 >= 0 && c.r0 >= 0 && r1 - c.r0 == static_cast<long long>(c.R) &&
            static_cast<unsigned long long>(r1) <= v.total_rows;
     return c;
-}
-// The clip that owns packed row g: the last b < n_clips with ro[b] <= g (binary search; see varlen_find)
-__device__ __forceinline__ unsigned varrows_find(const VarRowsArgs &v, unsigned long long g)
-{
-    unsigned lo = 0u, hi = v.n_clips;
-    const long long gs = static_cast<long long>(g);
-    while (hi - lo > 1u) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (v.ro[mid] <= gs) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 // One pass over the clips, spread over the grid (see varlen_check_clips).  A vector store to the pinned word.
 __device__ __forceinline__ void varrows_check_clips(const VarRowsArgs &v, unsigned tid, unsigned nthreads)
@@ -330,19 +328,6 @@ __device__ __forceinline__ StreamEntry stream_entry(const FrameStreamPackedArgs 
            r1 <= static_cast<long long>(v.total_rows) && slot >= 0 && e.slot < v.pool_streams;
     return e;
 }
-// The entry that owns packed row g: the last i < n_active with ro[i] <= g (binary search as varlen_find; entries without rows
-// share their ro with their successor and are stepped over, and the caller still checks g < ro[i + 1])
-__device__ __forceinline__ unsigned stream_entry_find(const FrameStreamPackedArgs &v, unsigned g)
-{
-    unsigned lo = 0u, hi = v.n_active;
-    const long long gs = static_cast<long long>(g);
-    while (hi - lo > 1u) {
-        const unsigned mid = (lo + hi) >> 1;
-        if (v.ro[mid] <= gs) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 // One pass over the entries, spread over the grid (see varlen_check_clips).  A vector store to the pinned word.
 __device__ __forceinline__ void stream_check_entries(const FrameStreamPackedArgs &v, unsigned tid, unsigned nthreads)
 {
@@ -360,7 +345,7 @@ hipError_t launch_stream_advance_packed(const FrameStreamPackedArgs &s, const fl
 
 // Ragged streaming STFT / mel spectrogram over a pool of stream states (ss_mel_spectrogram_stream_packed_device /
 // ss_stft_stream_packed_device): the same tables on the STFT path, continuous mode.  The entry block is the frame pool's, with
-// step = hop, state_len = fft_points - hop and lead unused, so that stream_entry(), stream_entry_find(), stream_check_entries() and
+// step = hop, state_len = fft_points - hop and lead unused, so that stream_entry(), stream_check_entries(), the lookups over its tables and
 // ss_stream_advance_packed ("last S samples of old row ++ chunk": the dense continuous advance) serve both families; the type of
 // its own only selects the STFT-path builds in the kernels' trailing argument packs.  Row t of an entry is row t of a dense
 // continuous call on that stream alone (StreamArgs above): its window is the W samples that end at chunk sample (t + 1) * hop, and
@@ -368,16 +353,6 @@ hipError_t launch_stream_advance_packed(const FrameStreamPackedArgs &s, const fl
 struct StftStreamPackedArgs {
     FrameStreamPackedArgs e;
 };
-// The last i < n_active with ro[i] <= g, as stream_entry_find gives it, from a lower bound c the caller already knows (the entry
-// of an earlier row): a few steps along the row offsets -- entries without rows share their ro with their successor and are
-// stepped over -- and the binary search where that does not get there.
-__device__ __forceinline__ unsigned stream_entry_seek(const FrameStreamPackedArgs &v, unsigned c, unsigned g)
-{
-    const long long gs = static_cast<long long>(g);
-    for (int k = 0; k < 4 && c + 1 < v.n_active && v.ro[c + 1] <= gs; ++k) ++c;
-    if (c + 1 < v.n_active && v.ro[c + 1] <= gs) c = stream_entry_find(v, g);
-    return c;
-}
 // the ragged streaming build of ss_front_generic's STFT / mel path (any fft_points, chirp-z included; mel and stft output): a as
 // for launch_front_generic_stream with x = the packed chunks and n_pad = 0; batch / n_samples / rows / real_rows / ld are unused.
 // The grid comes from s.e.total_rows (one workgroup where it is 0: the entry pass).

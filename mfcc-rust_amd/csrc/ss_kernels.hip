@@ -37,6 +37,8 @@
 //     a completeness path, not a fast one.
 //
 // Reference semantics (file:line relative to the reference checkout) are cited at each stage.
+#include <cstdio>
+
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 
@@ -311,7 +313,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
             [[maybe_unused]] const float *srow = nullptr;  // FSTREAM: the stream's state, indexed from its end (sample p < 0 is srow[p])
             if constexpr (VAR) {
                 // rows past the last clip (a larger output block) are left alone; rows of an inconsistent clip are skipped
-                const VarClip c = varlen_clip(*va, a.flen, a.step, active ? varlen_find(*va, gf) : 0u);
+                const VarClip c = varlen_clip(*va, a.flen, a.step, active ? offset_find(va->fo, va->n_clips, static_cast<long long>(gf)) : 0u);
                 active = active && c.ok && static_cast<long long>(gf) >= c.f0 && static_cast<long long>(gf) - c.f0 < static_cast<long long>(c.T);
                 t = active ? static_cast<unsigned>(static_cast<long long>(gf) - c.f0) : 0u;
                 xc = a.x + (active ? c.s0 : 0ll);
@@ -322,7 +324,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
             } else if constexpr (FSP) {
                 // rows past the last entry (a larger output block) are left alone; rows of an inconsistent entry are skipped
                 const unsigned g32 = static_cast<unsigned>(gf);
-                const StreamEntry en = stream_entry(*fp, active ? stream_entry_find(*fp, g32) : 0u);
+                const StreamEntry en = stream_entry(*fp, active ? offset_find(fp->ro, fp->n_active, g32) : 0u);
                 active = active && en.ok && static_cast<long long>(gf) >= en.r0 && static_cast<long long>(gf) - en.r0 < static_cast<long long>(en.R);
                 t = active ? static_cast<unsigned>(static_cast<long long>(gf) - en.r0) : 0u;
                 xc = a.x + (active ? en.s0 : 0ll);
@@ -500,11 +502,11 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 VarRowClip c;
                 [[maybe_unused]] const float *srow = nullptr;  // SPR: the entry's pool row, indexed from its end (sample p < 0 is srow[p])
                 if constexpr (SPR) {
-                    const StreamEntry en = stream_entry(sp->e, rl < rt ? stream_entry_find(sp->e, static_cast<unsigned>(g)) : 0u);
+                    const StreamEntry en = stream_entry(sp->e, rl < rt ? offset_find(sp->e.ro, sp->e.n_active, static_cast<unsigned>(g)) : 0u);
                     c = VarRowClip{en.s0, en.r0, en.n, en.R, en.ok};
                     if (en.ok) srow = sp->e.pool + static_cast<unsigned long long>(en.slot) * sp->e.state_len + sp->e.state_len;
                 } else {
-                    c = varrows_clip(*ra, rl < rt ? varrows_find(*ra, g) : 0u);
+                    c = varrows_clip(*ra, rl < rt ? offset_find(ra->ro, ra->n_clips, static_cast<long long>(g)) : 0u);
                 }
                 const long long r = static_cast<long long>(g) - c.r0;  // row within the clip
                 const bool valid = rl < rt && c.ok && r >= 0 && r < static_cast<long long>(c.R);
@@ -650,155 +652,120 @@ size_t front_lds_bytes(const FrontArgs &a)
     return (total + 15) & ~static_cast<size_t>(15);
 }
 
-template <int LOG2C, bool BLU>
-hipError_t launch_one(const FrontArgs &a, hipStream_t stream, int num_cus, LaunchInfo *info, const char *name)
-{
-    using G = Geo<LOG2C>;
-    const size_t lds = front_lds_bytes<LOG2C>(a);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-    }
-    unsigned long long work;
-    if (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT) work = a.batch;
-    else work = (static_cast<unsigned long long>(a.batch) * a.n_frames + G::FPB - 1) / G::FPB;
-    if (work == 0) return hipSuccess;
-    if (static_cast<unsigned long long>(a.batch) * a.n_frames >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
-    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
-    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
-    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU>), dim3(grid), dim3(kBlock), lds, stream, a);
-    return hipGetLastError();
-}
+// The parts of a launch that depend on the layout, chosen by the type of the kernel's trailing argument (none: the equal-length
+// builds): the suffix of the reported name, the LDS behind the equal-length carve, and the workgroup visits of the call.
+constexpr const char *layout_suffix() { return ""; }
+constexpr const char *layout_suffix(const VarlenArgs &) { return "_varlen"; }
+constexpr const char *layout_suffix(const VarRowsArgs &) { return "_varrows"; }
+constexpr const char *layout_suffix(const StreamArgs &) { return "_stream"; }
+constexpr const char *layout_suffix(const FrameStreamArgs &) { return "_fstream"; }
+constexpr const char *layout_suffix(const FrameStreamPackedArgs &) { return "_fstreamp"; }
+constexpr const char *layout_suffix(const StftStreamPackedArgs &) { return "_streamp"; }
 
-template <int LOG2C, bool BLU>
-hipError_t launch_one_varlen(const FrontArgs &a, const VarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info, const char *name)
-{
-    using G = Geo<LOG2C>;
-    const size_t lds = front_lds_bytes<LOG2C>(a);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, VarlenArgs>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-    }
-    // at least one workgroup: the clip pass runs even where the output block has no rows
-    unsigned long long work = (v.total_frames + G::FPB - 1) / G::FPB;
-    if (work == 0) work = 1;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
-    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
-    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
-    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, VarlenArgs>), dim3(grid), dim3(kBlock), lds, stream, a, v);
-    return hipGetLastError();
-}
+// the packed-rows builds: the tile's row table (32 offsets + 32 row counts, 8-byte aligned)
+constexpr size_t kRowTableBytes = 32 * (sizeof(long long) + sizeof(unsigned)) + 16;
+template <typename... V>
+constexpr size_t layout_lds(const V &...) { return 0; }
+constexpr size_t layout_lds(const VarRowsArgs &) { return kRowTableBytes; }
+constexpr size_t layout_lds(const StftStreamPackedArgs &) { return kRowTableBytes; }
 
-template <int LOG2C, bool BLU>
-hipError_t launch_one_varrows(const FrontArgs &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info,
-                              const char *name)
+// Workgroup visits of a call at `fpb` frames per visit.  0: nothing to launch; kTooManyRows: the kernel's 32-bit row index does not
+// reach the last row.
+constexpr unsigned long long kTooManyRows = ~0ull;
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb)
 {
-    // the equal-length carve plus the tile's row table (32 offsets + 32 row counts, 8-byte aligned)
-    const size_t lds = front_lds_bytes<LOG2C>(a) + 32 * (sizeof(long long) + sizeof(unsigned)) + 16;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, VarRowsArgs>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-    }
-    // at least one workgroup: the clip pass runs even where the output block has no rows
-    unsigned long long work = (v.total_rows + 31) / 32;
-    if (work == 0) work = 1;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
-    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
-    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
-    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, VarRowsArgs>), dim3(grid), dim3(kBlock), lds, stream, a, v);
-    return hipGetLastError();
+    const unsigned long long frames = static_cast<unsigned long long>(a.batch) * a.n_frames;
+    const unsigned long long work = (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT) ? a.batch : (frames + fpb - 1) / fpb;
+    return work != 0 && frames >= 0xffffffffull ? kTooManyRows : work;
 }
-
-template <int LOG2C, bool BLU>
-hipError_t launch_one_streamp(const FrontArgs &a, const StftStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info,
-                              const char *name)
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long, const StreamArgs &) { return a.batch; }
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const FrameStreamArgs &)
 {
-    // the packed-rows carve (launch_one_varrows)
-    const size_t lds = front_lds_bytes<LOG2C>(a) + 32 * (sizeof(long long) + sizeof(unsigned)) + 16;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, StftStreamPackedArgs>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-    }
-    // at least one workgroup: the entry pass runs even where the output block has no rows
-    unsigned long long work = (static_cast<unsigned long long>(s.e.total_rows) + 31) / 32;
-    if (work == 0) work = 1;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
-    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
-    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
-    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, StftStreamPackedArgs>), dim3(grid), dim3(kBlock), lds, stream, a, s);
-    return hipGetLastError();
-}
-
-template <int LOG2C, bool BLU>
-hipError_t launch_one_fstream(const FrontArgs &a, const FrameStreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info,
-                              const char *name)
-{
-    using G = Geo<LOG2C>;
-    const size_t lds = front_lds_bytes<LOG2C>(a);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, FrameStreamArgs>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-    }
     const unsigned long long rows = static_cast<unsigned long long>(a.batch) * a.n_frames;
-    if (rows == 0) return hipSuccess;
-    if (rows >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned long long work = (rows + G::FPB - 1) / G::FPB;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
-    const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
-    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
-    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, FrameStreamArgs>), dim3(grid), dim3(kBlock), lds, stream, a, s);
-    return hipGetLastError();
+    return rows >= 0xffffffffull ? kTooManyRows : (rows + fpb - 1) / fpb;
+}
+// The table-driven layouts launch at least one workgroup: the pass over the clips / entries runs even where the output block has
+// no rows.
+constexpr unsigned long long at_least_one(unsigned long long units) { return units ? units : 1; }
+inline unsigned long long layout_work(const FrontArgs &, unsigned long long fpb, const VarlenArgs &v)
+{
+    return at_least_one((v.total_frames + fpb - 1) / fpb);
+}
+inline unsigned long long layout_work(const FrontArgs &, unsigned long long fpb, const FrameStreamPackedArgs &s)
+{
+    return at_least_one((s.total_rows + fpb - 1) / fpb);
+}
+inline unsigned long long layout_work(const FrontArgs &, unsigned long long, const VarRowsArgs &v) { return at_least_one((v.total_rows + 31) / 32); }
+inline unsigned long long layout_work(const FrontArgs &, unsigned long long, const StftStreamPackedArgs &s)
+{
+    return at_least_one((static_cast<unsigned long long>(s.e.total_rows) + 31) / 32);
 }
 
-template <int LOG2C, bool BLU>
-hipError_t launch_one_fstreamp(const FrontArgs &a, const FrameStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info,
-                               const char *name)
+// What ss_last_kernel_name() reports for an instantiation: ss_front_generic<suffix><LOG2C[,chirpz]>, built once, kept for the process.
+template <int LOG2C, bool BLU, typename... V>
+const char *front_kernel_name(const V &...v)
 {
-    using G = Geo<LOG2C>;
-    const size_t lds = front_lds_bytes<LOG2C>(a);
+    struct Name {
+        char s[48];
+    };
+    static const Name name = [&] {
+        Name n;
+        snprintf(n.s, sizeof n.s, "ss_front_generic%s<%d%s>", layout_suffix(v...), LOG2C, BLU ? ",chirpz" : "");
+        return n;
+    }();
+    return name.s;
+}
+
+template <int LOG2C, bool BLU, typename... V>
+hipError_t launch_one(const FrontArgs &a, hipStream_t stream, int num_cus, LaunchInfo *info, const V &...v)
+{
+    const size_t lds = front_lds_bytes<LOG2C>(a) + layout_lds(v...);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, FrameStreamPackedArgs>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, V...>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
         if (e != hipSuccess) return e;
     }
-    // at least one workgroup: the entry pass runs even where the output block has no rows
-    unsigned long long work = (static_cast<unsigned long long>(s.total_rows) + G::FPB - 1) / G::FPB;
-    if (work == 0) work = 1;
+    const unsigned long long work = layout_work(a, Geo<LOG2C>::FPB, v...);
+    if (work == 0) return hipSuccess;
+    if (work == kTooManyRows) return hipErrorInvalidValue;
     const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
     const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
-    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
-    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, FrameStreamPackedArgs>), dim3(grid), dim3(kBlock), lds, stream, a, s);
+    if (info) *info = LaunchInfo{front_kernel_name<LOG2C, BLU>(v...), grid, static_cast<unsigned>(kBlock), lds};
+    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, V...>), dim3(grid), dim3(kBlock), lds, stream, a, v...);
     return hipGetLastError();
 }
 
-template <int LOG2C, bool BLU>
-hipError_t launch_one_stream(const FrontArgs &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info, const char *name)
+// every build of the generic kernel for one layout: log2c 4 .. 12, chirp-z (a.blu_n != 0) or not
+template <typename... V>
+hipError_t dispatch_front(const FrontArgs &a, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info, const V &...v)
 {
-    const size_t lds = front_lds_bytes<LOG2C>(a);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_front_generic<LOG2C, BLU, StreamArgs>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
+    if (a.blu_n) {
+        switch (log2c) {
+            case 4: return launch_one<4, true>(a, stream, num_cus, info, v...);
+            case 5: return launch_one<5, true>(a, stream, num_cus, info, v...);
+            case 6: return launch_one<6, true>(a, stream, num_cus, info, v...);
+            case 7: return launch_one<7, true>(a, stream, num_cus, info, v...);
+            case 8: return launch_one<8, true>(a, stream, num_cus, info, v...);
+            case 9: return launch_one<9, true>(a, stream, num_cus, info, v...);
+            case 10: return launch_one<10, true>(a, stream, num_cus, info, v...);
+            case 11: return launch_one<11, true>(a, stream, num_cus, info, v...);
+            case 12: return launch_one<12, true>(a, stream, num_cus, info, v...);
+            default: return hipErrorInvalidValue;
+        }
     }
-    if (a.batch == 0) return hipSuccess;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
-    const unsigned grid = static_cast<unsigned>(a.batch < cap ? a.batch : cap);
-    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(kBlock), lds};
-    hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, StreamArgs>), dim3(grid), dim3(kBlock), lds, stream, a, s);
-    return hipGetLastError();
+    switch (log2c) {
+        case 4: return launch_one<4, false>(a, stream, num_cus, info, v...);
+        case 5: return launch_one<5, false>(a, stream, num_cus, info, v...);
+        case 6: return launch_one<6, false>(a, stream, num_cus, info, v...);
+        case 7: return launch_one<7, false>(a, stream, num_cus, info, v...);
+        case 8: return launch_one<8, false>(a, stream, num_cus, info, v...);
+        case 9: return launch_one<9, false>(a, stream, num_cus, info, v...);
+        case 10: return launch_one<10, false>(a, stream, num_cus, info, v...);
+        case 11: return launch_one<11, false>(a, stream, num_cus, info, v...);
+        case 12: return launch_one<12, false>(a, stream, num_cus, info, v...);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 // State advance (functions.rs:152-160 over a call's chunks): row s := the last S samples of old row ++ x_s[0 .. advance), zeros
@@ -889,160 +856,35 @@ hipError_t launch_poison_lds(hipStream_t stream, int num_cus)
 
 hipError_t launch_front_generic(const FrontArgs &a, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
-    if (a.blu_n) {
-        switch (log2c) {
-            case 4: return launch_one<4, true>(a, stream, num_cus, info, "ss_front_generic<4,chirpz>");
-            case 5: return launch_one<5, true>(a, stream, num_cus, info, "ss_front_generic<5,chirpz>");
-            case 6: return launch_one<6, true>(a, stream, num_cus, info, "ss_front_generic<6,chirpz>");
-            case 7: return launch_one<7, true>(a, stream, num_cus, info, "ss_front_generic<7,chirpz>");
-            case 8: return launch_one<8, true>(a, stream, num_cus, info, "ss_front_generic<8,chirpz>");
-            case 9: return launch_one<9, true>(a, stream, num_cus, info, "ss_front_generic<9,chirpz>");
-            case 10: return launch_one<10, true>(a, stream, num_cus, info, "ss_front_generic<10,chirpz>");
-            case 11: return launch_one<11, true>(a, stream, num_cus, info, "ss_front_generic<11,chirpz>");
-            case 12: return launch_one<12, true>(a, stream, num_cus, info, "ss_front_generic<12,chirpz>");
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (log2c) {
-        case 4: return launch_one<4, false>(a, stream, num_cus, info, "ss_front_generic<4>");
-        case 5: return launch_one<5, false>(a, stream, num_cus, info, "ss_front_generic<5>");
-        case 6: return launch_one<6, false>(a, stream, num_cus, info, "ss_front_generic<6>");
-        case 7: return launch_one<7, false>(a, stream, num_cus, info, "ss_front_generic<7>");
-        case 8: return launch_one<8, false>(a, stream, num_cus, info, "ss_front_generic<8>");
-        case 9: return launch_one<9, false>(a, stream, num_cus, info, "ss_front_generic<9>");
-        case 10: return launch_one<10, false>(a, stream, num_cus, info, "ss_front_generic<10>");
-        case 11: return launch_one<11, false>(a, stream, num_cus, info, "ss_front_generic<11>");
-        case 12: return launch_one<12, false>(a, stream, num_cus, info, "ss_front_generic<12>");
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_front(a, log2c, stream, num_cus, info);
 }
 
 hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
                                        LaunchInfo *info)
 {
     if (a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE) return hipErrorInvalidValue;
-    if (a.blu_n) {
-        switch (log2c) {
-            case 4: return launch_one_varlen<4, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<4,chirpz>");
-            case 5: return launch_one_varlen<5, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<5,chirpz>");
-            case 6: return launch_one_varlen<6, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<6,chirpz>");
-            case 7: return launch_one_varlen<7, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<7,chirpz>");
-            case 8: return launch_one_varlen<8, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<8,chirpz>");
-            case 9: return launch_one_varlen<9, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<9,chirpz>");
-            case 10: return launch_one_varlen<10, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<10,chirpz>");
-            case 11: return launch_one_varlen<11, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<11,chirpz>");
-            case 12: return launch_one_varlen<12, true>(a, v, stream, num_cus, info, "ss_front_generic_varlen<12,chirpz>");
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (log2c) {
-        case 4: return launch_one_varlen<4, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<4>");
-        case 5: return launch_one_varlen<5, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<5>");
-        case 6: return launch_one_varlen<6, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<6>");
-        case 7: return launch_one_varlen<7, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<7>");
-        case 8: return launch_one_varlen<8, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<8>");
-        case 9: return launch_one_varlen<9, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<9>");
-        case 10: return launch_one_varlen<10, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<10>");
-        case 11: return launch_one_varlen<11, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<11>");
-        case 12: return launch_one_varlen<12, false>(a, v, stream, num_cus, info, "ss_front_generic_varlen<12>");
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_front(a, log2c, stream, num_cus, info, v);
 }
 
 hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
                                         LaunchInfo *info)
 {
     if (a.out_kind != OUT_MEL && a.out_kind != OUT_STFT) return hipErrorInvalidValue;
-    if (a.blu_n) {
-        switch (log2c) {
-            case 4: return launch_one_varrows<4, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<4,chirpz>");
-            case 5: return launch_one_varrows<5, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<5,chirpz>");
-            case 6: return launch_one_varrows<6, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<6,chirpz>");
-            case 7: return launch_one_varrows<7, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<7,chirpz>");
-            case 8: return launch_one_varrows<8, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<8,chirpz>");
-            case 9: return launch_one_varrows<9, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<9,chirpz>");
-            case 10: return launch_one_varrows<10, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<10,chirpz>");
-            case 11: return launch_one_varrows<11, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<11,chirpz>");
-            case 12: return launch_one_varrows<12, true>(a, v, stream, num_cus, info, "ss_front_generic_varrows<12,chirpz>");
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (log2c) {
-        case 4: return launch_one_varrows<4, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<4>");
-        case 5: return launch_one_varrows<5, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<5>");
-        case 6: return launch_one_varrows<6, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<6>");
-        case 7: return launch_one_varrows<7, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<7>");
-        case 8: return launch_one_varrows<8, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<8>");
-        case 9: return launch_one_varrows<9, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<9>");
-        case 10: return launch_one_varrows<10, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<10>");
-        case 11: return launch_one_varrows<11, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<11>");
-        case 12: return launch_one_varrows<12, false>(a, v, stream, num_cus, info, "ss_front_generic_varrows<12>");
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_front(a, log2c, stream, num_cus, info, v);
 }
 
 hipError_t launch_front_generic_stream(const FrontArgs &a, const StreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
                                        LaunchInfo *info)
 {
     if (a.out_kind != OUT_MEL && a.out_kind != OUT_STFT) return hipErrorInvalidValue;
-    if (a.blu_n) {
-        switch (log2c) {
-            case 4: return launch_one_stream<4, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<4,chirpz>");
-            case 5: return launch_one_stream<5, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<5,chirpz>");
-            case 6: return launch_one_stream<6, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<6,chirpz>");
-            case 7: return launch_one_stream<7, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<7,chirpz>");
-            case 8: return launch_one_stream<8, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<8,chirpz>");
-            case 9: return launch_one_stream<9, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<9,chirpz>");
-            case 10: return launch_one_stream<10, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<10,chirpz>");
-            case 11: return launch_one_stream<11, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<11,chirpz>");
-            case 12: return launch_one_stream<12, true>(a, s, stream, num_cus, info, "ss_front_generic_stream<12,chirpz>");
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (log2c) {
-        case 4: return launch_one_stream<4, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<4>");
-        case 5: return launch_one_stream<5, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<5>");
-        case 6: return launch_one_stream<6, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<6>");
-        case 7: return launch_one_stream<7, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<7>");
-        case 8: return launch_one_stream<8, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<8>");
-        case 9: return launch_one_stream<9, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<9>");
-        case 10: return launch_one_stream<10, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<10>");
-        case 11: return launch_one_stream<11, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<11>");
-        case 12: return launch_one_stream<12, false>(a, s, stream, num_cus, info, "ss_front_generic_stream<12>");
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_front(a, log2c, stream, num_cus, info, s);
 }
 
 hipError_t launch_front_generic_frame_stream(const FrontArgs &a, const FrameStreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
                                              LaunchInfo *info)
 {
     if (a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE) return hipErrorInvalidValue;
-    if (a.blu_n) {
-        switch (log2c) {
-            case 4: return launch_one_fstream<4, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<4,chirpz>");
-            case 5: return launch_one_fstream<5, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<5,chirpz>");
-            case 6: return launch_one_fstream<6, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<6,chirpz>");
-            case 7: return launch_one_fstream<7, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<7,chirpz>");
-            case 8: return launch_one_fstream<8, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<8,chirpz>");
-            case 9: return launch_one_fstream<9, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<9,chirpz>");
-            case 10: return launch_one_fstream<10, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<10,chirpz>");
-            case 11: return launch_one_fstream<11, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<11,chirpz>");
-            case 12: return launch_one_fstream<12, true>(a, s, stream, num_cus, info, "ss_front_generic_fstream<12,chirpz>");
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (log2c) {
-        case 4: return launch_one_fstream<4, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<4>");
-        case 5: return launch_one_fstream<5, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<5>");
-        case 6: return launch_one_fstream<6, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<6>");
-        case 7: return launch_one_fstream<7, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<7>");
-        case 8: return launch_one_fstream<8, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<8>");
-        case 9: return launch_one_fstream<9, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<9>");
-        case 10: return launch_one_fstream<10, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<10>");
-        case 11: return launch_one_fstream<11, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<11>");
-        case 12: return launch_one_fstream<12, false>(a, s, stream, num_cus, info, "ss_front_generic_fstream<12>");
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_front(a, log2c, stream, num_cus, info, s);
 }
 
 hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const FrameStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
@@ -1050,32 +892,7 @@ hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const Fr
 {
     if (a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE) return hipErrorInvalidValue;
     if (s.n_active == 0 || s.step == 0 || (s.state_len > 0 && !s.pool) || s.total_rows >= 0x7fffffffu) return hipErrorInvalidValue;
-    if (a.blu_n) {
-        switch (log2c) {
-            case 4: return launch_one_fstreamp<4, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<4,chirpz>");
-            case 5: return launch_one_fstreamp<5, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<5,chirpz>");
-            case 6: return launch_one_fstreamp<6, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<6,chirpz>");
-            case 7: return launch_one_fstreamp<7, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<7,chirpz>");
-            case 8: return launch_one_fstreamp<8, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<8,chirpz>");
-            case 9: return launch_one_fstreamp<9, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<9,chirpz>");
-            case 10: return launch_one_fstreamp<10, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<10,chirpz>");
-            case 11: return launch_one_fstreamp<11, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<11,chirpz>");
-            case 12: return launch_one_fstreamp<12, true>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<12,chirpz>");
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (log2c) {
-        case 4: return launch_one_fstreamp<4, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<4>");
-        case 5: return launch_one_fstreamp<5, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<5>");
-        case 6: return launch_one_fstreamp<6, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<6>");
-        case 7: return launch_one_fstreamp<7, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<7>");
-        case 8: return launch_one_fstreamp<8, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<8>");
-        case 9: return launch_one_fstreamp<9, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<9>");
-        case 10: return launch_one_fstreamp<10, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<10>");
-        case 11: return launch_one_fstreamp<11, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<11>");
-        case 12: return launch_one_fstreamp<12, false>(a, s, stream, num_cus, info, "ss_front_generic_fstreamp<12>");
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_front(a, log2c, stream, num_cus, info, s);
 }
 
 hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
@@ -1087,32 +904,7 @@ hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStre
     if (s.e.n_active == 0 || a.hop == 0 || s.e.step != a.hop || a.n_pad != 0 || s.e.state_len + a.hop != W || !s.e.pool ||
         s.e.total_rows >= 0x7fffffffu)
         return hipErrorInvalidValue;
-    if (a.blu_n) {
-        switch (log2c) {
-            case 4: return launch_one_streamp<4, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<4,chirpz>");
-            case 5: return launch_one_streamp<5, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<5,chirpz>");
-            case 6: return launch_one_streamp<6, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<6,chirpz>");
-            case 7: return launch_one_streamp<7, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<7,chirpz>");
-            case 8: return launch_one_streamp<8, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<8,chirpz>");
-            case 9: return launch_one_streamp<9, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<9,chirpz>");
-            case 10: return launch_one_streamp<10, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<10,chirpz>");
-            case 11: return launch_one_streamp<11, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<11,chirpz>");
-            case 12: return launch_one_streamp<12, true>(a, s, stream, num_cus, info, "ss_front_generic_streamp<12,chirpz>");
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (log2c) {
-        case 4: return launch_one_streamp<4, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<4>");
-        case 5: return launch_one_streamp<5, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<5>");
-        case 6: return launch_one_streamp<6, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<6>");
-        case 7: return launch_one_streamp<7, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<7>");
-        case 8: return launch_one_streamp<8, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<8>");
-        case 9: return launch_one_streamp<9, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<9>");
-        case 10: return launch_one_streamp<10, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<10>");
-        case 11: return launch_one_streamp<11, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<11>");
-        case 12: return launch_one_streamp<12, false>(a, s, stream, num_cus, info, "ss_front_generic_streamp<12>");
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_front(a, log2c, stream, num_cus, info, s);
 }
 
 hipError_t launch_stream_advance_packed(const FrameStreamPackedArgs &s, const float *x, hipStream_t stream)

@@ -361,7 +361,7 @@ __global__ __launch_bounds__(kWavesM * 64) void ss_mel_c1024(const Mel2048Args a
 // the row offsets finds the clip of the unit's first row, a half-wave's row lies at most one clip further (every clip has a row).
 // SPOOL (ss_mel_spectrogram_stream_packed_device): VARR's units over the entries of a ragged streaming call (StftStreamPackedArgs);
 // entries without rows share their row offset with their successor, so any number of them may lie between the two rows of a pair:
-// both lookups go through stream_entry_seek (a few cursor steps, else the binary search).  Samples before the chunk come from the
+// both lookups go through offset_seek (a few cursor steps, else the binary search).  Samples before the chunk come from the
 // entry's pool row (stream_window); a pair inside one chunk takes the equal-length loads.
 template <bool FIXMEL, bool STFT = false, bool MULTI = false, typename... SA>
 __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args a, const MultiArg<MULTI> mt, const SA... sargs)
@@ -452,9 +452,7 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
         [[maybe_unused]] unsigned pslot = 0;   // SPOOL: the entry's pool row
         if constexpr (VARR) {
             const long long g0 = 2ll * unit;
-            unsigned c = cursor;
-            for (int k = 0; k < 4 && c + 1 < ra->n_clips && ra->ro[c + 1] <= g0; ++k) ++c;
-            if (c + 1 < ra->n_clips && ra->ro[c + 1] <= g0) c = varrows_find(*ra, static_cast<unsigned long long>(g0));
+            unsigned c = offset_seek(ra->ro, ra->n_clips, cursor, g0);
             cursor = c;
             const long long g = g0 + half;
             vsame = !(c + 1 < ra->n_clips && ra->ro[c + 1] <= g);
@@ -465,10 +463,10 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
         }
         if constexpr (SPOOL) {
             const unsigned g0 = 2u * unit;
-            const unsigned c0 = stream_entry_seek(pa->e, cursor, g0);
+            const unsigned c0 = offset_seek(pa->e.ro, pa->e.n_active, cursor, g0);
             cursor = c0;
             const unsigned g = g0 + half;
-            const unsigned c = stream_entry_seek(pa->e, c0, g);  // (any number of entries without rows may lie between the two)
+            const unsigned c = offset_seek(pa->e.ro, pa->e.n_active, c0, g);  // (any number of entries without rows may lie between the two)
             vsame = c == c0;
             const StreamEntry en = stream_entry(pa->e, c);
             vc = VarRowClip{en.s0, en.r0, en.n, en.R, en.ok};

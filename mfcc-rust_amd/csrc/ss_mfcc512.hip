@@ -276,9 +276,7 @@ __device__ __forceinline__ unsigned load_quad_stream_packed(const Fast512Args &a
 {
     const unsigned q4 = quad * 4;                                              // uniform
     const unsigned g = q4 + min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last row redo it
-    unsigned c = stream_entry_find(s, q4);
-    for (int k = 0; k < 4 && c + 1 < s.n_active && s.ro[c + 1] <= static_cast<long long>(g); ++k) ++c;
-    if (c + 1 < s.n_active && s.ro[c + 1] <= static_cast<long long>(g)) c = stream_entry_find(s, g);
+    const unsigned c = offset_seek(s.ro, s.n_active, offset_find(s.ro, s.n_active, q4), g);
     const StreamEntry en = stream_entry(s, c);
     const long long tl = static_cast<long long>(g) - en.r0;
     ok = en.ok && g < total && tl >= 0 && tl < static_cast<long long>(en.R);
@@ -350,9 +348,7 @@ __device__ __forceinline__ const char *var_src(const Fast512Args &a, const Varle
 {
     const unsigned q4 = quad * 4;                                        // uniform
     const unsigned g = q4 + min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last row redo it
-    unsigned c = cursor;
-    for (int k = 0; k < 4 && c + 1 < v.n_clips && v.fo[c + 1] <= static_cast<long long>(q4); ++k) ++c;
-    if (c + 1 < v.n_clips && v.fo[c + 1] <= static_cast<long long>(q4)) c = varlen_find(v, q4);
+    unsigned c = offset_seek(v.fo, v.n_clips, cursor, q4);
     cursor = c;
 #pragma unroll
     for (int k = 0; k < 3; ++k) c += (c + 1 < v.n_clips && v.fo[c + 1] <= static_cast<long long>(g)) ? 1u : 0u;

@@ -1434,3 +1434,59 @@ def test_kernel_variants_agree(ss, sslib, sslab):
     assert _rel(gen, prod) <= 2e-5
 
 
+
+
+# The generic kernel's reported names, per input layout: a power of two it serves on both paths (fft_points 256 at 8 kHz; the dense
+# case goes through the STFT path, whose 256-point rows have no dedicated kernel) and a chirp-z length (fft_points 400).  The strings
+# are the literals of the per-case tables the library had when the names were still typed out (log2c 7; chirp-z 400 -> 1024 points).
+_GENERIC_CFGS = {
+    "pow2": dict(sr=8000, fft=256, flen=160, step=80, hop=128, M=20),
+    "chirpz": dict(sr=16000, fft=400, flen=400, step=160, hop=200, M=40),
+}
+_GENERIC_NAMES = {
+    ("dense", "pow2"): b"ss_front_generic<7>",
+    ("dense", "chirpz"): b"ss_front_generic<10,chirpz>",
+    ("varlen", "pow2"): b"ss_front_generic_varlen<7>",
+    ("varlen", "chirpz"): b"ss_front_generic_varlen<10,chirpz>",
+    ("varrows", "pow2"): b"ss_front_generic_varrows<7>",
+    ("varrows", "chirpz"): b"ss_front_generic_varrows<10,chirpz>",
+    ("stream", "pow2"): b"ss_front_generic_stream<7>",
+    ("stream", "chirpz"): b"ss_front_generic_stream<10,chirpz>",
+    ("fstream", "pow2"): b"ss_front_generic_fstream<7>",
+    ("fstream", "chirpz"): b"ss_front_generic_fstream<10,chirpz>",
+    ("fstreamp", "pow2"): b"ss_front_generic_fstreamp<7>",
+    ("fstreamp", "chirpz"): b"ss_front_generic_fstreamp<10,chirpz>",
+    ("streamp", "pow2"): b"ss_front_generic_streamp<7>",
+    ("streamp", "chirpz"): b"ss_front_generic_streamp<10,chirpz>",
+}
+
+
+@pytest.mark.parametrize("variant,cfg", sorted(_GENERIC_NAMES))
+def test_generic_kernel_names_per_layout(ss, sslib, variant, cfg):
+    """ss_last_kernel_name() of every input layout of the generic front end, exactly: two clips / streams / entries of a few rows."""
+    import torch
+
+    c = _GENERIC_CFGS[cfg]
+    sr, fft, M = c["sr"], c["fft"], c["M"]
+    frame = dict(frame_length=c["flen"] / sr, frame_stride=c["step"] / sr, num_filters=M, fft_length=fft)  # MFCC path
+    rows = dict(frame_length=c["hop"] / sr, num_filters=M, fft_length=fft)                                 # STFT / mel path
+    x = torch.from_numpy(_signal(17, (2, 8 * c["flen"]))).cuda()
+    if variant == "dense":
+        out = ss.mel_spectrogram(x, sr, frame_stride=c["hop"] / sr, **rows)
+    elif variant == "varlen":
+        out = torch.cat(ss.mfcc_list([x[0, :c["flen"] + 3 * c["step"]], x[1, :c["flen"] + c["step"] + 5]], sr, **frame))
+    elif variant == "varrows":
+        out = torch.cat([m.flatten() for m in ss.mel_spectrogram_list([x[0, :3 * c["hop"]], x[1, :c["hop"] + 5]], sr,
+                                                                      frame_stride=c["hop"] / sr, **rows)])
+    elif variant == "stream":
+        out = ss.MelSpectrogramStream(2, sr, **rows)(x[:, :3 * c["hop"]])
+    elif variant == "fstream":
+        out = ss.MfccStream(2, sr, norm_frames=100, **frame)(x[:, :3 * c["step"]])
+    elif variant == "fstreamp":
+        out, _ = ss.MfccStreamPool(4, sr, norm_frames=100, **frame)([x[0, :3 * c["step"]], x[1, :c["step"]]], [2, 0])
+    else:
+        out, _ = ss.MelSpectrogramStreamPool(4, sr, **rows)([x[0, :3 * c["hop"]], x[1, :c["hop"]]], [2, 0])
+    name = sslib.ss_last_kernel_name()
+    print(f"generic kernel name [{variant}, {cfg}]: {name!r}")
+    assert out.numel() > 0 and bool(torch.isfinite(out).all())
+    assert name == _GENERIC_NAMES[(variant, cfg)]
