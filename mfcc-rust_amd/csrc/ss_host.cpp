@@ -484,6 +484,153 @@ static void balance_slots(const HostTables &t, int lanes, int nslots, const int3
     order = dealt;
 }
 
+// ---- steps the table builders share; what is specific to a kernel stays in its builder ----
+
+// The two spans the sorted deal knows.  The 16-lane kernels read a filter's taps one by one from its first bin ...
+static int32_t tap_span(const HostTables &t, int32_t m) { return t.bank.len[m]; }
+// ... the others as aligned float4s of the P row: the span starts at the first bin rounded down to a multiple of 4
+static int32_t aligned_span(const HostTables &t, int32_t m) { return t.bank.len[m] ? (t.bank.start[m] & 3) + t.bank.len[m] : 0; }
+
+// Orders the filters by span, longest first, and deals them `lanes` per slot so that the lock-step tap loops are short:
+// q4[s] = the longest span of slot s in float4s.  (Callers have checked num_filters <= slots * lanes.)
+static std::vector<int32_t> sorted_deal(const HostTables &t, int lanes, int slots, int32_t (*span)(const HostTables &, int32_t), int32_t *q4)
+{
+    std::vector<int32_t> order(t.params.num_filters);
+    for (size_t m = 0; m < order.size(); ++m) order[m] = static_cast<int32_t>(m);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return span(t, a) > span(t, b); });
+    for (int s = 0; s < slots; ++s) q4[s] = 0;
+    for (size_t q = 0; q < order.size(); ++q) q4[q / lanes] = std::max(q4[q / lanes], span(t, order[q]));
+    for (int s = 0; s < slots; ++s) q4[s] = (q4[s] + 3) / 4;
+    return order;
+}
+
+// Floats per lane row of the weight block: the slots' spans one behind the other.  odd: an odd pitch in 16-byte units, so that
+// the lanes' ds_read_b128 of their rows spread over all banks.
+static int32_t row_pitch(const int32_t *q4, int slots, bool odd)
+{
+    int32_t wpitch = 0;
+    for (int s = 0; s < slots; ++s) wpitch += 4 * q4[s];
+    if (wpitch == 0) wpitch = 4;
+    if (odd && (wpitch / 4) % 2 == 0) wpitch += 4;
+    return wpitch;
+}
+
+static int32_t *words(std::vector<float> &tab, int at) { return reinterpret_cast<int32_t *>(tab.data() + at); }
+
+// Slots of 16 lanes whose taps are read one by one: filter order[s * 16 + j] goes to lane j of slot s and starts at its own
+// first bin -- earlier (zero weights in front) where the `span` taps of the lock-step loop would pass the P row.  start / filt
+// [slots][16]: first P bin and filter index (-1: unused -- zero weights -> 0 -> EPS -> ln, times a zero cosine column).
+static void place_slots_b32(const HostTables &t, int slots, int32_t kRow, const std::vector<int32_t> &order, const int32_t *q4, int32_t wpitch,
+                            float *melw, int32_t *start, int32_t *filt)
+{
+    int32_t off = 0;
+    for (int s = 0; s < slots; ++s) {
+        const int32_t span = 4 * q4[s];
+        for (int j = 0; j < 16; ++j) {
+            const size_t q = static_cast<size_t>(s) * 16 + j;
+            start[q] = 0;
+            filt[q] = -1;
+            if (q >= order.size()) continue;
+            const int32_t m = order[q], len = t.bank.len[m];
+            const int32_t shift = std::max(0, t.bank.start[m] + span - kRow);
+            start[q] = t.bank.start[m] - shift;
+            filt[q] = m;
+            for (int32_t i = 0; i < len; ++i) melw[static_cast<size_t>(j) * wpitch + off + shift + i] = t.bank.w[t.bank.off[m] + i];
+        }
+        off += span;
+    }
+}
+
+// Slots of `lanes` (32 or 64) lanes that share one P row and read taps as aligned float4s: the filters order[s * lanes ..] of
+// slot s go to lanes and first float4 slots that keep the lock-step ds_read_b128 tap reads conflict-free (place_taps_b128).
+// start / filt [slots][lanes]: first P bin (a multiple of 4) and filter index (-1: none, reading a harmless place).
+static void place_slots_b128(const HostTables &t, int lanes, int slots, int32_t kRow, const std::vector<int32_t> &order, const int32_t *q4,
+                             int32_t wpitch, float *melw, int32_t *start, int32_t *filt)
+{
+    std::vector<int32_t> lo4, hi4, lane_of, start4_of, idle;
+    int32_t off = 0;
+    for (int s = 0; s < slots; ++s) {
+        const int32_t span = 4 * q4[s];
+        const size_t q0 = static_cast<size_t>(s) * lanes;
+        lo4.clear();
+        hi4.clear();
+        for (size_t q = q0; q < q0 + lanes && q < order.size(); ++q) {
+            const int32_t m = order[q], len = t.bank.len[m], st = len ? t.bank.start[m] : 0;
+            hi4.push_back(len ? std::min(st, kRow - span) / 4 : (kRow - span) / 4);  // an empty filter may read anywhere
+            lo4.push_back(std::max<int32_t>(0, st + len - span + 3) / 4);
+            if (lo4.back() > hi4.back()) lo4.back() = hi4.back();
+        }
+        place_taps_b128(lanes, lo4, hi4, lane_of, start4_of, idle, (kRow - span) / 4);
+        for (int j = 0; j < lanes; ++j) {
+            start[q0 + j] = 4 * idle[j];
+            filt[q0 + j] = -1;
+        }
+        for (size_t k = 0; k < lo4.size(); ++k) {
+            const int32_t m = order[q0 + k], len = t.bank.len[m], j = lane_of[k], st = 4 * start4_of[k];
+            const int32_t shift = len ? t.bank.start[m] - st : 0;  // zero weights in front of the filter's first tap
+            start[q0 + j] = st;
+            filt[q0 + j] = m;
+            for (int32_t i = 0; i < len; ++i) melw[static_cast<size_t>(j) * wpitch + off + shift + i] = t.bank.w[t.bank.off[m] + i];
+        }
+        off += span;
+    }
+}
+
+// exp(-2 pi i num / den) as (re, im)
+static void cis(double num, double den, float *dst)
+{
+    const double ang = -2.0 * 3.14159265358979323846 * num / den;
+    dst[0] = static_cast<float>(std::cos(ang));
+    dst[1] = static_cast<float>(std::sin(ang));
+}
+
+// Twiddles of a radix-n pass over n lanes, two per 16-byte slot: float4 p of lane j = (W^(j(2p+1)), W^(j(2p+2))),
+// W = exp(-2 pi i / n^2), at dst[p * p_stride + j * lane_stride]; the last .zw stays zero.
+static void fill_pass_twiddles(float *dst, int n, int p_stride, int lane_stride)
+{
+    for (int r = 1; r < n; ++r)
+        for (int j = 0; j < n; ++j) cis(j * r, n * n, dst + (r - 1) / 2 * p_stride + j * lane_stride + 2 * ((r - 1) % 2));
+}
+
+// Untangle twiddles of the real transform: exp(-2 pi i (j + n r) / (4 n rows)) of lane j < n, row r, at dst[r * r_stride + j * lane_stride]
+static void fill_untangle_twiddles(float *dst, int n, int rows, int r_stride, int lane_stride)
+{
+    for (int r = 0; r < rows; ++r)
+        for (int j = 0; j < n; ++j) cis(j + n * r, 4 * n * rows, dst + r * r_stride + j * lane_stride);
+}
+
+// A window of at most n floats into a region of n zeros; append_window puts that region behind the block.
+static void copy_window(const std::vector<float> &w, size_t n, float *dst)
+{
+    for (size_t i = 0; i < w.size() && i < n; ++i) dst[i] = w[i];
+}
+static void append_window(std::vector<float> &tab, const std::vector<float> &w, size_t n)
+{
+    const size_t base = tab.size();
+    tab.resize(base + n, 0.0f);
+    copy_window(w, n, &tab[base]);
+}
+
+// Cosine rows of the kernels that fold the DCT once: row c = cos(pi c (2m+1) / 2M), m < (M+1)/2 (the other half by symmetry)
+static void store_half_cosines(const HostTables &t, size_t Cc, int pitch, float *dst)
+{
+    const size_t M = t.params.num_filters;
+    for (size_t c = 0; c < Cc; ++c)
+        for (size_t m = 0; m < (M + 1) / 2; ++m) dst[c * pitch + m] = t.dct[c * M + m];
+}
+
+// The mel-spectrogram kernels: when the bank does not fit the kernel's mel stage, the block is built once more without
+// filters and marked stft_only (see without_bank).
+template <class Tables, class Build>
+static void build_or_stft_only(const HostTables &t, Tables &f, Build build)
+{
+    build(t, f);
+    if (f.ok) return;
+    build(without_bank(t), f);
+    f.stft_only = f.ok;
+    f.ok = false;
+}
+
 void build_fast512(const HostTables &t, Fast512Tables &f)
 {
     namespace L = fast512_layout;
@@ -495,20 +642,15 @@ void build_fast512(const HostTables &t, Fast512Tables &f)
     if (t.bank.last_bin > 257) return;
     f.fullp = t.bank.last_bin > 129;
     const int32_t kRow = f.fullp ? 260 : 132;  // P bins a tap may touch, including three zero pad bins
-    // order filters by tap count (longest first) and deal them 16 per slot
-    std::vector<int32_t> order(M);
-    for (size_t m = 0; m < M; ++m) order[m] = static_cast<int32_t>(m);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return t.bank.len[a] > t.bank.len[b]; });
+    const std::vector<int32_t> order = sorted_deal(t, 16, 3, tap_span, f.q4);
     // (slot, lane) cell -> filter, -1: unused
     std::vector<int32_t> cell(48, -1);
     for (size_t q = 0; q < M; ++q) cell[q] = order[q];
-    auto spans = [&](const std::vector<int32_t> &c, int32_t (&q4)[3]) {
-        int32_t maxlen[3] = {0, 0, 0};
+    auto longest = [&](const std::vector<int32_t> &c, int32_t (&maxlen)[3]) {
+        for (int s = 0; s < 3; ++s) maxlen[s] = 0;
         for (size_t q = 0; q < 48; ++q)
             if (c[q] >= 0) maxlen[q / 16] = std::max(maxlen[q / 16], t.bank.len[c[q]]);
-        for (int s = 0; s < 3; ++s) q4[s] = (maxlen[s] + 3) / 4;
     };
-    spans(cell, f.q4);
     if (M == 40 && !f.fullp) {
         // PAIRED layout for the symmetric DCT of the default filter count (ss_mfcc512.hip): the DCT needs s[m] = L[m] + L[39-m] and
         // d[m] = L[m] - L[39-m]; with filter 39 - m in slot 0 and filter m in slot 2 (m < 8) or slot 1 (8 <= m < 16) of the SAME
@@ -526,7 +668,8 @@ void build_fast512(const HostTables &t, Fast512Tables &f)
             pc[16 + 2 * i + 1] = 23 - i;
         }
         int32_t pq4[3];
-        spans(pc, pq4);
+        longest(pc, pq4);
+        for (int s = 0; s < 3; ++s) pq4[s] = (pq4[s] + 3) / 4;
         if (pq4[0] <= f.q4[0] && pq4[1] <= f.q4[1] && pq4[2] <= f.q4[2]) {
             cell = pc;
             f.paired = true;
@@ -538,32 +681,20 @@ void build_fast512(const HostTables &t, Fast512Tables &f)
     // their float4 pitch, and every other build of the kernel reads the same table with its 8 and 4 taps: zeros behind).
     int32_t tspan[3] = {4 * f.q4[0], 4 * f.q4[1], 4 * f.q4[2]};
     if (f.paired && f.q4[0] == 4 && f.q4[1] == 2 && f.q4[2] == 1) {
-        int32_t maxlen[3] = {0, 0, 0};
-        for (size_t q = 0; q < 48; ++q)
-            if (cell[q] >= 0) maxlen[q / 16] = std::max(maxlen[q / 16], t.bank.len[cell[q]]);
+        int32_t maxlen[3];
+        longest(cell, maxlen);
         if (maxlen[1] <= 6 && maxlen[2] <= 2) {
             f.tight = true;
             tspan[1] = 6;
             tspan[2] = 2;
         }
     }
-    f.wpitch = 4 * (f.q4[0] + f.q4[1] + f.q4[2]);
-    if (f.wpitch == 0) f.wpitch = 4;
+    f.wpitch = row_pitch(f.q4, 3, false);  // (this kernel's tap reads are ds_read_b32: no odd pitch)
     if (f.wpitch > 160) return;
     f.tab.assign(static_cast<size_t>(L::kMelW) + 16 * f.wpitch, 0.0f);
-    for (int r = 1; r < 16; ++r)
-        for (int j = 0; j < 16; ++j) {  // exp(-2 pi i j r / 256) = tw_c[j r]; two twiddles per 16-byte slot
-            const int p = (r - 1) / 2, half = (r - 1) % 2;
-            f.tab[L::kTw2 + (p * 16 + j) * 4 + 2 * half] = t.tw_c[2 * (j * r)];
-            f.tab[L::kTw2 + (p * 16 + j) * 4 + 2 * half + 1] = t.tw_c[2 * (j * r) + 1];
-        }
-    for (int r = 0; r < 8; ++r)
-        for (int j = 0; j < 16; ++j) {  // exp(-2 pi i (j + 16 r) / 512) = tw_n[j + 16 r]
-            f.tab[L::kTwn + (r * 16 + j) * 2] = t.tw_n[2 * (j + 16 * r)];
-            f.tab[L::kTwn + (r * 16 + j) * 2 + 1] = t.tw_n[2 * (j + 16 * r) + 1];
-        }
-    int32_t *start = reinterpret_cast<int32_t *>(f.tab.data() + L::kStart);
-    int32_t *filt = reinterpret_cast<int32_t *>(f.tab.data() + L::kFilt);
+    fill_pass_twiddles(&f.tab[L::kTw2], 16, 64, 4);
+    fill_untangle_twiddles(&f.tab[L::kTwn], 16, 8, 32, 2);
+    int32_t *start = words(f.tab, L::kStart), *filt = words(f.tab, L::kFilt);
     int32_t off = 0;
     for (int s = 0; s < 3; ++s) {
         const int32_t span = 4 * f.q4[s];
@@ -635,9 +766,7 @@ void build_fast512(const HostTables &t, Fast512Tables &f)
         // all 256 pairs a 16-input build may touch (zero beyond flen): a shorter table would let the padded inputs multiply
         // whatever follows it in LDS -- 0 x NaN-patterned table words of an earlier kernel is NaN
         f.win_floats = 512;
-        const size_t base = f.tab.size();
-        f.tab.resize(base + static_cast<size_t>(f.win_floats), 0.0f);
-        for (size_t i = 0; i < t.window_mfcc.size(); ++i) f.tab[base + i] = t.window_mfcc[i];
+        append_window(f.tab, t.window_mfcc, 512);
     }
     f.ok = true;
 }
@@ -651,58 +780,20 @@ static void build_mel512_bank(const HostTables &t, Mel512Tables &f)
     if (t.bank.last_bin > 257) return;
     f.fullp = t.bank.last_bin > 129;  // reference banks end at (F+1)/2
     const int32_t kRow = f.fullp ? 260 : 132;  // P bins a tap may touch, including three zero pad bins
-    std::vector<int32_t> order(M);
-    for (size_t m = 0; m < M; ++m) order[m] = static_cast<int32_t>(m);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return t.bank.len[a] > t.bank.len[b]; });
-    int32_t maxlen[5] = {0, 0, 0, 0, 0};
-    for (size_t q = 0; q < M; ++q) maxlen[q / 16] = std::max(maxlen[q / 16], t.bank.len[order[q]]);
-    f.wpitch = 0;
-    for (int s = 0; s < 5; ++s) {
-        f.q4[s] = (maxlen[s] + 3) / 4;
+    const std::vector<int32_t> order = sorted_deal(t, 16, 5, tap_span, f.q4);
+    for (int s = 0; s < 5; ++s)
         if (static_cast<size_t>(s) * 16 < M && f.q4[s] == 0) f.q4[s] = 1;  // the kernel stops at the first empty slot
-        f.wpitch += 4 * f.q4[s];
-    }
-    if (f.wpitch == 0) f.wpitch = 4;
-    if ((f.wpitch / 4) % 2 == 0) f.wpitch += 4;  // odd pitch in 16-byte units: the 16 lanes' ds_read_b128 rows spread over the banks
+    f.wpitch = row_pitch(f.q4, 5, true);
     if (f.wpitch > 320) return;
     f.tab.assign(static_cast<size_t>(L::kMelW) + 16 * static_cast<size_t>(f.wpitch), 0.0f);
-    for (int r = 1; r < 16; ++r)
-        for (int j = 0; j < 16; ++j) {  // exp(-2 pi i j r / 256) = tw_c[j r]; two twiddles per 16-byte slot
-            const int p = (r - 1) / 2, half = (r - 1) % 2;
-            f.tab[L::kTw2 + (p * 16 + j) * 4 + 2 * half] = t.tw_c[2 * (j * r)];
-            f.tab[L::kTw2 + (p * 16 + j) * 4 + 2 * half + 1] = t.tw_c[2 * (j * r) + 1];
-        }
-    for (int r = 0; r < 8; ++r)
-        for (int j = 0; j < 16; ++j) {  // exp(-2 pi i (j + 16 r) / 512) = tw_n[j + 16 r]
-            f.tab[L::kTwn + (r * 16 + j) * 2] = t.tw_n[2 * (j + 16 * r)];
-            f.tab[L::kTwn + (r * 16 + j) * 2 + 1] = t.tw_n[2 * (j + 16 * r) + 1];
-        }
-    for (int i = 0; i < 512; ++i) f.tab[L::kWin + i] = t.window_stft[i];
-    int32_t *start = reinterpret_cast<int32_t *>(f.tab.data() + L::kStart);
-    int32_t *filt = reinterpret_cast<int32_t *>(f.tab.data() + L::kFilt);
-    int32_t off = 0;
-    for (int s = 0; s < 5; ++s) {
-        const int32_t span = 4 * f.q4[s];
-        for (int j = 0; j < 16; ++j) {
-            const size_t q = static_cast<size_t>(s) * 16 + j;
-            start[q] = 0;
-            filt[q] = -1;
-            if (q >= M) continue;
-            const int32_t m = order[q];
-            filt[q] = m;
-            int32_t st = t.bank.start[m];
-            const int32_t len = t.bank.len[m];
-            int32_t shift = 0;  // the lock-step loop reads `span` taps: keep st + span inside the row
-            if (st + span > kRow) shift = st + span - kRow;
-            st -= shift;
-            start[q] = st;
-            for (int32_t i = 0; i < len; ++i)
-                f.tab[L::kMelW + static_cast<size_t>(j) * f.wpitch + off + shift + i] = t.bank.w[t.bank.off[m] + i];
-        }
-        off += span;
-    }
+    fill_pass_twiddles(&f.tab[L::kTw2], 16, 64, 4);
+    fill_untangle_twiddles(&f.tab[L::kTwn], 16, 8, 32, 2);
+    copy_window(t.window_stft, 512, &f.tab[L::kWin]);
+    place_slots_b32(t, 5, kRow, order, f.q4, f.wpitch, &f.tab[L::kMelW], words(f.tab, L::kStart), words(f.tab, L::kFilt));
     f.ok = true;
 }
+
+void build_mel512(const HostTables &t, Mel512Tables &f) { build_or_stft_only(t, f, build_mel512_bank); }
 
 void build_mfcc512w(const HostTables &t, Mfcc512wTables &f)
 {
@@ -712,60 +803,18 @@ void build_mfcc512w(const HostTables &t, Mfcc512wTables &f)
     if (t.d.n_fft != 512 || M > 80 || Cc > 32) return;
     if (t.bank.last_bin > 257) return;
     constexpr int32_t kRow = 260;  // P bins a tap may touch: 0..256 plus three zero pad bins
-    std::vector<int32_t> order(M);
-    for (size_t m = 0; m < M; ++m) order[m] = static_cast<int32_t>(m);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return t.bank.len[a] > t.bank.len[b]; });
-    int32_t maxlen[5] = {0, 0, 0, 0, 0};
-    for (size_t q = 0; q < M; ++q) maxlen[q / 16] = std::max(maxlen[q / 16], t.bank.len[order[q]]);
-    f.wpitch = 0;
-    for (int s = 0; s < 5; ++s) {
-        f.q4[s] = (maxlen[s] + 3) / 4;
-        f.wpitch += 4 * f.q4[s];
-    }
-    if (f.wpitch == 0) f.wpitch = 4;
-    if ((f.wpitch / 4) % 2 == 0) f.wpitch += 4;  // odd pitch in 16-byte units: the 16 lanes' ds_read_b128 rows spread over the banks
+    const std::vector<int32_t> order = sorted_deal(t, 16, 5, tap_span, f.q4);
+    f.wpitch = row_pitch(f.q4, 5, true);
     if (f.wpitch > 320) return;
     f.tab.assign(static_cast<size_t>(L::kMelW) + 16 * static_cast<size_t>(f.wpitch), 0.0f);
-    for (int r = 1; r < 16; ++r)
-        for (int j = 0; j < 16; ++j) {  // exp(-2 pi i j r / 256) = tw_c[j r]; two twiddles per 16-byte slot
-            const int p = (r - 1) / 2, half = (r - 1) % 2;
-            f.tab[L::kTw2 + (p * 16 + j) * 4 + 2 * half] = t.tw_c[2 * (j * r)];
-            f.tab[L::kTw2 + (p * 16 + j) * 4 + 2 * half + 1] = t.tw_c[2 * (j * r) + 1];
-        }
-    for (int r = 0; r < 8; ++r)
-        for (int j = 0; j < 16; ++j) {  // exp(-2 pi i (j + 16 r) / 512) = tw_n[j + 16 r]
-            f.tab[L::kTwn + (r * 16 + j) * 2] = t.tw_n[2 * (j + 16 * r)];
-            f.tab[L::kTwn + (r * 16 + j) * 2 + 1] = t.tw_n[2 * (j + 16 * r) + 1];
-        }
-    int32_t *start = reinterpret_cast<int32_t *>(f.tab.data() + L::kStart);
-    int32_t *filt = reinterpret_cast<int32_t *>(f.tab.data() + L::kFilt);
-    int32_t off = 0;
-    for (int s = 0; s < 5; ++s) {
-        const int32_t span = 4 * f.q4[s];
-        for (int j = 0; j < 16; ++j) {
-            const size_t q = static_cast<size_t>(s) * 16 + j;
-            start[q] = 0;
-            filt[q] = -1;
-            if (q >= M) continue;  // unused (slot, lane): zero weights -> 0 -> EPS -> ln, times a zero cosine column
-            const int32_t m = order[q];
-            filt[q] = m;
-            int32_t st = t.bank.start[m];
-            const int32_t len = t.bank.len[m];
-            int32_t shift = 0;  // the lock-step loop reads `span` taps: keep st + span inside the row
-            if (st + span > kRow) shift = st + span - kRow;
-            st -= shift;
-            start[q] = st;
-            for (int32_t i = 0; i < len; ++i)
-                f.tab[L::kMelW + static_cast<size_t>(j) * f.wpitch + off + shift + i] = t.bank.w[t.bank.off[m] + i];
-            for (size_t c = 0; c < Cc; ++c) f.tab[L::kCos + c * L::kCosPitch + q] = t.dct[c * M + m];
-        }
-        off += span;
-    }
+    fill_pass_twiddles(&f.tab[L::kTw2], 16, 64, 4);
+    fill_untangle_twiddles(&f.tab[L::kTwn], 16, 8, 32, 2);
+    place_slots_b32(t, 5, kRow, order, f.q4, f.wpitch, &f.tab[L::kMelW], words(f.tab, L::kStart), words(f.tab, L::kFilt));
+    for (size_t q = 0; q < M; ++q)  // cosine columns in (slot, lane) order
+        for (size_t c = 0; c < Cc; ++c) f.tab[L::kCos + c * L::kCosPitch + q] = t.dct[c * M + order[q]];
     if (!t.window_mfcc.empty()) {  // optional frame window (mfcc_window switch), read as sample pairs
         f.windowed = true;
-        const size_t base = f.tab.size();
-        f.tab.resize(base + 512, 0.0f);
-        for (size_t i = 0; i < t.window_mfcc.size() && i < 512; ++i) f.tab[base + i] = t.window_mfcc[i];
+        append_window(f.tab, t.window_mfcc, 512);
     }
     f.ok = true;
 }
@@ -778,60 +827,20 @@ void build_mfcc256(const HostTables &t, Mfcc256Tables &f)
     if (t.d.n_fft != 256 || M > 48 || Cc > 32) return;
     if (t.bank.last_bin > 129) return;
     constexpr int32_t kRow = 132;  // P bins a tap may touch: 0..128 plus three zero pad bins
-    // order filters by tap count (longest first) and deal them 16 per slot
-    std::vector<int32_t> order(M);
-    for (size_t m = 0; m < M; ++m) order[m] = static_cast<int32_t>(m);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return t.bank.len[a] > t.bank.len[b]; });
-    int32_t maxlen[3] = {0, 0, 0};
-    for (size_t q = 0; q < M; ++q) maxlen[q / 16] = std::max(maxlen[q / 16], t.bank.len[order[q]]);
-    for (int s = 0; s < 3; ++s) f.q4[s] = (maxlen[s] + 3) / 4;
-    f.wpitch = 4 * (f.q4[0] + f.q4[1] + f.q4[2]);
-    if (f.wpitch == 0) f.wpitch = 4;
-    if ((f.wpitch / 4) % 2 == 0) f.wpitch += 4;  // odd pitch in 16-byte units: the 16 lanes' ds_read_b128 rows spread over the banks
+    const std::vector<int32_t> order = sorted_deal(t, 16, 3, tap_span, f.q4);
+    f.wpitch = row_pitch(f.q4, 3, true);
     if (f.wpitch > 160) return;
     f.tab.assign(static_cast<size_t>(L::kMelW) + 16 * static_cast<size_t>(f.wpitch), 0.0f);
-    const double pi = 3.14159265358979323846;
-    for (int r = 1; r < 16; ++r)
-        for (int j = 0; j < 16; ++j) {  // exp(-2 pi i j r / 256); two twiddles per 16-byte slot
-            const int p = (r - 1) / 2, half = (r - 1) % 2;
-            const double ang = -2.0 * pi * static_cast<double>(j * r) / 256.0;
-            f.tab[L::kTw2 + (p * 16 + j) * 4 + 2 * half] = static_cast<float>(std::cos(ang));
-            f.tab[L::kTw2 + (p * 16 + j) * 4 + 2 * half + 1] = static_cast<float>(std::sin(ang));
-        }
-    int32_t *start = reinterpret_cast<int32_t *>(f.tab.data() + L::kStart);
-    int32_t *filt = reinterpret_cast<int32_t *>(f.tab.data() + L::kFilt);
-    int32_t off = 0;
-    for (int s = 0; s < 3; ++s) {
-        const int32_t span = 4 * f.q4[s];
-        for (int j = 0; j < 16; ++j) {
-            const size_t q = static_cast<size_t>(s) * 16 + j;
-            start[q] = 0;
-            filt[q] = -1;
-            if (q >= M) continue;  // unused (slot, lane): zero weights -> 0 -> EPS -> ln, times a zero cosine column
-            const int32_t m = order[q];
-            filt[q] = m;
-            int32_t st = t.bank.start[m];
-            const int32_t len = t.bank.len[m];
-            int32_t shift = 0;  // the lock-step loop reads `span` taps: keep st + span inside the row
-            if (st + span > kRow) shift = st + span - kRow;
-            st -= shift;
-            start[q] = st;
-            for (int32_t i = 0; i < len; ++i)
-                f.tab[L::kMelW + static_cast<size_t>(j) * f.wpitch + off + shift + i] = t.bank.w[t.bank.off[m] + i];
-            for (size_t c = 0; c < Cc; ++c) f.tab[L::kCos + c * 52 + q] = t.dct[c * M + m];
-        }
-        off += span;
-    }
+    fill_pass_twiddles(&f.tab[L::kTw2], 16, 64, 4);
+    place_slots_b32(t, 3, kRow, order, f.q4, f.wpitch, &f.tab[L::kMelW], words(f.tab, L::kStart), words(f.tab, L::kFilt));
+    for (size_t q = 0; q < M; ++q)  // cosine columns in (slot, lane) order
+        for (size_t c = 0; c < Cc; ++c) f.tab[L::kCos + c * 52 + q] = t.dct[c * M + order[q]];
     if (!t.window_mfcc.empty()) {  // optional frame window (mfcc_window switch)
         f.windowed = true;
-        const size_t base = f.tab.size();
-        f.tab.resize(base + 256, 0.0f);
-        for (size_t i = 0; i < t.window_mfcc.size() && i < 256; ++i) f.tab[base + i] = t.window_mfcc[i];
+        append_window(f.tab, t.window_mfcc, 256);
     }
     f.ok = true;
 }
-
-
 
 static void build_mel2048_bank(const HostTables &t, Mel2048Tables &f)
 {
@@ -842,18 +851,9 @@ static void build_mel2048_bank(const HostTables &t, Mel2048Tables &f)
     if (t.bank.last_bin > 1025) return;
     f.fullp = t.bank.last_bin > 513;  // reference banks end at (F+1)/2 (P bins 0..512); others get rows of all 1025 bins
     const int32_t kRow = f.fullp ? 1028 : 516;  // P bins a tap may touch, including three zero pad bins
-    std::vector<int32_t> order(M);
-    for (size_t m = 0; m < M; ++m) order[m] = static_cast<int32_t>(m);
-    // taps are read as aligned float4s of the P row: a filter's span starts at its first bin rounded down to a multiple of 4
-    auto alen = [&](int32_t m) { return t.bank.len[m] ? (t.bank.start[m] & 3) + t.bank.len[m] : 0; };
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return alen(a) > alen(b); });
-    int32_t maxlen[4] = {0, 0, 0, 0};
-    for (size_t q = 0; q < M; ++q) maxlen[q / 32] = std::max(maxlen[q / 32], alen(order[q]));
-    for (int s = 0; s < 4; ++s) f.q4[s] = (maxlen[s] + 3) / 4;
+    std::vector<int32_t> order = sorted_deal(t, 32, 4, aligned_span, f.q4);
     balance_slots(t, 32, 4, f.q4, kRow, order);  // (the slots keep their spans; see balance_slots)
-    f.wpitch = 4 * (f.q4[0] + f.q4[1] + f.q4[2] + f.q4[3]);
-    if (f.wpitch == 0) f.wpitch = 4;
-    if ((f.wpitch / 4) % 2 == 0) f.wpitch += 4;  // odd pitch in 16-byte units: the lanes' ds_read_b128 of their rows spread over all banks
+    f.wpitch = row_pitch(f.q4, 4, true);
     if (f.wpitch > 256) return;
     // (+4 words behind the block: [0] = how many polls the whole-line tile build waits for a hand-off before it reports a
     // protocol error, as an integer -- device-resident so that the kernel's cold path reads it from L2, not over PCIe)
@@ -862,79 +862,19 @@ static void build_mel2048_bank(const HostTables &t, Mel2048Tables &f)
         const uint32_t lim = 1u << 24;
         std::memcpy(&f.tab[static_cast<size_t>(L::kMelW) + 32 * f.wpitch], &lim, sizeof lim);
     }
-    const double pi = 3.14159265358979323846;
-    for (int r = 1; r < 32; ++r)
-        for (int j = 0; j < 32; ++j) {  // exp(-2 pi i j r / 1024) = tw_c[j r]
-            const int p = (r - 1) / 2, half = (r - 1) % 2;
-            f.tab[L::kTw2 + j * L::kTw2Pitch + p * 4 + 2 * half] = t.tw_c[2 * (j * r)];
-            f.tab[L::kTw2 + j * L::kTw2Pitch + p * 4 + 2 * half + 1] = t.tw_c[2 * (j * r) + 1];
-        }
-    for (int r = 0; r < 16; ++r)
-        for (int j = 0; j < 32; ++j) {  // exp(-2 pi i (j + 32 r) / 2048) = tw_n[j + 32 r]
-            f.tab[L::kTwn + j * L::kTwnPitch + 2 * r] = t.tw_n[2 * (j + 32 * r)];
-            f.tab[L::kTwn + j * L::kTwnPitch + 2 * r + 1] = t.tw_n[2 * (j + 32 * r) + 1];
-        }
-    (void)pi;
+    // twiddles and window are stored per lane (ss_internal.h): lane-major, pitched rows
+    fill_pass_twiddles(&f.tab[L::kTw2], 32, 4, L::kTw2Pitch);
+    fill_untangle_twiddles(&f.tab[L::kTwn], 32, 16, 2, L::kTwnPitch);
     for (int e = 0; e < 32; ++e)
         for (int j = 0; j < 32; ++j) {  // the sample pair of lane j, register e
             f.tab[L::kWin + j * L::kWinPitch + 2 * e] = t.window_stft[2 * (j + 32 * e)];
             f.tab[L::kWin + j * L::kWinPitch + 2 * e + 1] = t.window_stft[2 * (j + 32 * e) + 1];
         }
-    int32_t *start = reinterpret_cast<int32_t *>(f.tab.data() + L::kStart);
-    int32_t *filt = reinterpret_cast<int32_t *>(f.tab.data() + L::kFilt);
-    int32_t off = 0;
-    for (int s = 0; s < 4; ++s) {
-        const int32_t span = 4 * f.q4[s];
-        // the slot's filters go to lanes and first float4 slots that keep the lock-step ds_read_b128 tap reads conflict-free
-        // (32 lanes share a P row: two read groups of 16 lanes)
-        std::vector<int32_t> lo4, hi4, lane_of, start4_of, idle;
-        for (int j = 0; j < 32; ++j) {
-            const size_t q = static_cast<size_t>(s) * 32 + j;
-            if (q >= M) break;
-            const int32_t m = order[q], len = t.bank.len[m], st = len ? t.bank.start[m] : 0;
-            hi4.push_back(len ? std::min(st, kRow - span) / 4 : (kRow - span) / 4);  // an empty filter may read anywhere
-            lo4.push_back(std::max<int32_t>(0, st + len - span + 3) / 4);
-            if (lo4.back() > hi4.back()) lo4.back() = hi4.back();
-        }
-        place_taps_b128(32, lo4, hi4, lane_of, start4_of, idle, (kRow - span) / 4);
-        for (int j = 0; j < 32; ++j) {
-            start[s * 32 + j] = 4 * idle[j];
-            filt[s * 32 + j] = -1;
-        }
-        for (size_t k = 0; k < lo4.size(); ++k) {
-            const size_t q = static_cast<size_t>(s) * 32 + k;
-            const int32_t m = order[q], len = t.bank.len[m], j = lane_of[k], st = 4 * start4_of[k];
-            const int32_t shift = len ? t.bank.start[m] - st : 0;  // zero weights in front of the filter's first tap
-            start[s * 32 + j] = st;
-            filt[s * 32 + j] = m;
-            for (int32_t i = 0; i < len; ++i)
-                f.tab[L::kMelW + static_cast<size_t>(j) * f.wpitch + off + shift + i] = t.bank.w[t.bank.off[m] + i];
-        }
-        off += span;
-    }
+    place_slots_b128(t, 32, 4, kRow, order, f.q4, f.wpitch, &f.tab[L::kMelW], words(f.tab, L::kStart), words(f.tab, L::kFilt));
     f.ok = true;
 }
 
-
-void build_mel2048(const HostTables &t, Mel2048Tables &f)
-{
-    build_mel2048_bank(t, f);
-    if (f.ok) return;
-    HostTables e = without_bank(t);
-    build_mel2048_bank(e, f);
-    f.stft_only = f.ok;
-    f.ok = false;
-}
-
-void build_mel512(const HostTables &t, Mel512Tables &f)
-{
-    build_mel512_bank(t, f);
-    if (f.ok) return;
-    HostTables e = without_bank(t);
-    build_mel512_bank(e, f);
-    f.stft_only = f.ok;
-    f.ok = false;
-}
+void build_mel2048(const HostTables &t, Mel2048Tables &f) { build_or_stft_only(t, f, build_mel2048_bank); }
 
 // mel = false: the frame-path kernel (ss_mfcc_c512); mel = true: the mel-spectrogram kernel (ss_mel_c512) -- same FFT tables
 // and bank layout, the Vorbis STFT window in kWin, no cosine rows
@@ -948,89 +888,29 @@ static void build_1024(const HostTables &t, Mfcc1024Tables &f, bool mel)
     if (t.bank.last_bin > 513) return;
     f.fullp = t.bank.last_bin > 257;  // reference banks end at (F+1)/2 (P bins 0..256); librosa-style ones need all 513
     const int32_t kRow = f.fullp ? 516 : 260;
-    std::vector<int32_t> order(M);
-    for (size_t m = 0; m < M; ++m) order[m] = static_cast<int32_t>(m);
-    auto alen = [&](int32_t m) { return t.bank.len[m] ? (t.bank.start[m] & 3) + t.bank.len[m] : 0; };
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return alen(a) > alen(b); });
-    int32_t maxlen[4] = {0, 0, 0, 0};
-    for (size_t q = 0; q < M; ++q) maxlen[q / 32] = std::max(maxlen[q / 32], alen(order[q]));
-    for (int s = 0; s < 4; ++s) f.q4[s] = (maxlen[s] + 3) / 4;
+    std::vector<int32_t> order = sorted_deal(t, 32, 4, aligned_span, f.q4);
     balance_slots(t, 32, 4, f.q4, kRow, order);  // (the slots keep their spans; see balance_slots)
-    f.wpitch = 4 * (f.q4[0] + f.q4[1] + f.q4[2] + f.q4[3]);
-    if (f.wpitch == 0) f.wpitch = 4;
-    if ((f.wpitch / 4) % 2 == 0) f.wpitch += 4;  // odd pitch in 16-byte units: conflict-free ds_read_b128 of the lanes' rows
+    f.wpitch = row_pitch(f.q4, 4, true);
     if (f.wpitch > 256) return;
     f.tab.assign(static_cast<size_t>(L::kMelW) + 32 * static_cast<size_t>(f.wpitch), 0.0f);
-    const double pi = 3.14159265358979323846;
-    auto cis = [&](double num, double den, float *dst) {
-        const double ang = -2.0 * pi * num / den;
-        dst[0] = static_cast<float>(std::cos(ang));
-        dst[1] = static_cast<float>(std::sin(ang));
-    };
-    for (int r = 1; r < 16; ++r)
-        for (int k1 = 0; k1 < 16; ++k1) {
-            const int p = (r - 1) / 2, half = (r - 1) % 2;
-            cis(static_cast<double>(k1 * r), 256.0, &f.tab[L::kT1 + (p * 16 + k1) * 4 + 2 * half]);
-        }
+    fill_pass_twiddles(&f.tab[L::kT1], 16, 64, 4);
     for (int i = 0; i < 8; ++i)
         for (int jj = 0; jj < 32; ++jj) {
             const int k1 = jj & 15, hh = jj >> 4;
-            cis(static_cast<double>(k1 + 16 * (i + 8 * hh)), 512.0, &f.tab[L::kT2 + (i * 32 + jj) * 2]);
-            cis(static_cast<double>(k1 + 16 * i + 128 * hh), 1024.0, &f.tab[L::kTwn + (i * 32 + jj) * 2]);
+            cis(k1 + 16 * (i + 8 * hh), 512.0, &f.tab[L::kT2 + (i * 32 + jj) * 2]);
+            cis(k1 + 16 * i + 128 * hh, 1024.0, &f.tab[L::kTwn + (i * 32 + jj) * 2]);
         }
-    if (mel) {
-        f.windowed = true;
-        for (size_t i = 0; i < 1024; ++i) f.tab[L::kWin + i] = t.window_stft[i];
-    } else if (!t.window_mfcc.empty()) {
-        f.windowed = true;
-        for (size_t i = 0; i < t.window_mfcc.size() && i < 1024; ++i) f.tab[L::kWin + i] = t.window_mfcc[i];
-    }
-    int32_t *start = reinterpret_cast<int32_t *>(f.tab.data() + L::kStart);
-    int32_t *filt = reinterpret_cast<int32_t *>(f.tab.data() + L::kFilt);
-    int32_t off = 0;
-    for (int s = 0; s < 4; ++s) {
-        const int32_t span = 4 * f.q4[s];
-        // the slot's filters go to lanes and first float4 slots that keep the lock-step ds_read_b128 tap reads conflict-free
-        // (32 lanes share a P row: two read groups of 16 lanes; see place_taps_b128)
-        std::vector<int32_t> lo4, hi4, lane_of, start4_of, idle;
-        for (int j = 0; j < 32; ++j) {
-            const size_t q = static_cast<size_t>(s) * 32 + j;
-            if (q >= M) break;
-            const int32_t m = order[q], len = t.bank.len[m], st = len ? t.bank.start[m] : 0;
-            hi4.push_back(len ? std::min(st, kRow - span) / 4 : (kRow - span) / 4);  // an empty filter may read anywhere
-            lo4.push_back(std::max<int32_t>(0, st + len - span + 3) / 4);
-            if (lo4.back() > hi4.back()) lo4.back() = hi4.back();
-        }
-        place_taps_b128(32, lo4, hi4, lane_of, start4_of, idle, (kRow - span) / 4);
-        for (int j = 0; j < 32; ++j) {
-            start[s * 32 + j] = 4 * idle[j];
-            filt[s * 32 + j] = -1;
-        }
-        for (size_t k = 0; k < lo4.size(); ++k) {
-            const size_t q = static_cast<size_t>(s) * 32 + k;
-            const int32_t m = order[q], len = t.bank.len[m], j = lane_of[k], st = 4 * start4_of[k];
-            const int32_t shift = len ? t.bank.start[m] - st : 0;  // zero weights in front of the filter's first tap
-            start[s * 32 + j] = st;
-            filt[s * 32 + j] = m;
-            for (int32_t i = 0; i < len; ++i)
-                f.tab[L::kMelW + static_cast<size_t>(j) * f.wpitch + off + shift + i] = t.bank.w[t.bank.off[m] + i];
-        }
-        off += span;
-    }
-    for (size_t c = 0; c < Cc; ++c)
-        for (size_t m = 0; m < (M + 1) / 2; ++m) f.tab[L::kCos + c * L::kCosPitch + m] = t.dct[c * M + m];
+    f.windowed = mel || !t.window_mfcc.empty();
+    copy_window(mel ? t.window_stft : t.window_mfcc, 1024, &f.tab[L::kWin]);
+    place_slots_b128(t, 32, 4, kRow, order, f.q4, f.wpitch, &f.tab[L::kMelW], words(f.tab, L::kStart), words(f.tab, L::kFilt));
+    store_half_cosines(t, Cc, L::kCosPitch, &f.tab[L::kCos]);
     f.ok = true;
 }
 
 void build_mfcc1024(const HostTables &t, Mfcc1024Tables &f) { build_1024(t, f, false); }
 void build_mel1024(const HostTables &t, Mfcc1024Tables &f)
 {
-    build_1024(t, f, true);
-    if (f.ok) return;
-    HostTables e = without_bank(t);
-    build_1024(e, f, true);
-    f.stft_only = f.ok;
-    f.ok = false;
+    build_or_stft_only(t, f, [](const HostTables &tt, Mfcc1024Tables &ff) { build_1024(tt, ff, true); });
 }
 
 void build_mfcc2048(const HostTables &t, Mfcc2048Tables &f)
@@ -1042,70 +922,17 @@ void build_mfcc2048(const HostTables &t, Mfcc2048Tables &f)
     if (t.bank.last_bin > 1025) return;
     f.fullp = t.bank.last_bin > 513;  // reference banks end at (F+1)/2 (P bins 0..512); librosa-style ones need all 1025
     const int32_t kRow = f.fullp ? 1028 : 516;
-    std::vector<int32_t> order(M);
-    for (size_t m = 0; m < M; ++m) order[m] = static_cast<int32_t>(m);
-    auto alen = [&](int32_t m) { return t.bank.len[m] ? (t.bank.start[m] & 3) + t.bank.len[m] : 0; };
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return alen(a) > alen(b); });
-    int32_t maxlen[4] = {0, 0, 0, 0};
-    for (size_t q = 0; q < M; ++q) maxlen[q / 32] = std::max(maxlen[q / 32], alen(order[q]));
-    for (int s = 0; s < 4; ++s) f.q4[s] = (maxlen[s] + 3) / 4;
+    std::vector<int32_t> order = sorted_deal(t, 32, 4, aligned_span, f.q4);
     balance_slots(t, 32, 4, f.q4, kRow, order);  // (the slots keep their spans; see balance_slots)
-    f.wpitch = 4 * (f.q4[0] + f.q4[1] + f.q4[2] + f.q4[3]);
-    if (f.wpitch == 0) f.wpitch = 4;
-    if ((f.wpitch / 4) % 2 == 0) f.wpitch += 4;  // odd pitch in 16-byte units: conflict-free ds_read_b128 of the lanes' rows
+    f.wpitch = row_pitch(f.q4, 4, true);
     if (f.wpitch > 256) return;
     f.tab.assign(static_cast<size_t>(L::kMelW) + 32 * static_cast<size_t>(f.wpitch), 0.0f);
-    const double pi = 3.14159265358979323846;
-    auto cis = [&](double num, double den, float *dst) {
-        const double ang = -2.0 * pi * num / den;
-        dst[0] = static_cast<float>(std::cos(ang));
-        dst[1] = static_cast<float>(std::sin(ang));
-    };
-    for (int r = 1; r < 32; ++r)
-        for (int j = 0; j < 32; ++j) {
-            const int p = (r - 1) / 2, half = (r - 1) % 2;
-            cis(static_cast<double>(j * r), 1024.0, &f.tab[L::kTw2 + (p * 32 + j) * 4 + 2 * half]);
-        }
-    for (int r = 0; r < 16; ++r)
-        for (int j = 0; j < 32; ++j) cis(static_cast<double>(j + 32 * r), 2048.0, &f.tab[L::kTwn + (r * 32 + j) * 2]);
-    if (!t.window_mfcc.empty()) {
-        f.windowed = true;
-        for (size_t i = 0; i < t.window_mfcc.size() && i < 2048; ++i) f.tab[L::kWin + i] = t.window_mfcc[i];
-    }
-    int32_t *start = reinterpret_cast<int32_t *>(f.tab.data() + L::kStart);
-    int32_t *filt = reinterpret_cast<int32_t *>(f.tab.data() + L::kFilt);
-    int32_t off = 0;
-    for (int s = 0; s < 4; ++s) {
-        const int32_t span = 4 * f.q4[s];
-        // the slot's filters go to lanes and first float4 slots that keep the lock-step ds_read_b128 tap reads conflict-free
-        // (32 lanes share a P row: two read groups of 16 lanes; see place_taps_b128)
-        std::vector<int32_t> lo4, hi4, lane_of, start4_of, idle;
-        for (int j = 0; j < 32; ++j) {
-            const size_t q = static_cast<size_t>(s) * 32 + j;
-            if (q >= M) break;
-            const int32_t m = order[q], len = t.bank.len[m], st = len ? t.bank.start[m] : 0;
-            hi4.push_back(len ? std::min(st, kRow - span) / 4 : (kRow - span) / 4);  // an empty filter may read anywhere
-            lo4.push_back(std::max<int32_t>(0, st + len - span + 3) / 4);
-            if (lo4.back() > hi4.back()) lo4.back() = hi4.back();
-        }
-        place_taps_b128(32, lo4, hi4, lane_of, start4_of, idle, (kRow - span) / 4);
-        for (int j = 0; j < 32; ++j) {
-            start[s * 32 + j] = 4 * idle[j];
-            filt[s * 32 + j] = -1;
-        }
-        for (size_t k = 0; k < lo4.size(); ++k) {
-            const size_t q = static_cast<size_t>(s) * 32 + k;
-            const int32_t m = order[q], len = t.bank.len[m], j = lane_of[k], st = 4 * start4_of[k];
-            const int32_t shift = len ? t.bank.start[m] - st : 0;  // zero weights in front of the filter's first tap
-            start[s * 32 + j] = st;
-            filt[s * 32 + j] = m;
-            for (int32_t i = 0; i < len; ++i)
-                f.tab[L::kMelW + static_cast<size_t>(j) * f.wpitch + off + shift + i] = t.bank.w[t.bank.off[m] + i];
-        }
-        off += span;
-    }
-    for (size_t c = 0; c < Cc; ++c)
-        for (size_t m = 0; m < (M + 1) / 2; ++m) f.tab[L::kCos + c * L::kCosPitch + m] = t.dct[c * M + m];
+    fill_pass_twiddles(&f.tab[L::kTw2], 32, 128, 4);
+    fill_untangle_twiddles(&f.tab[L::kTwn], 32, 16, 64, 2);
+    f.windowed = !t.window_mfcc.empty();
+    copy_window(t.window_mfcc, 2048, &f.tab[L::kWin]);
+    place_slots_b128(t, 32, 4, kRow, order, f.q4, f.wpitch, &f.tab[L::kMelW], words(f.tab, L::kStart), words(f.tab, L::kFilt));
+    store_half_cosines(t, Cc, L::kCosPitch, &f.tab[L::kCos]);
     f.ok = true;
 }
 
@@ -1120,18 +947,9 @@ static void build_4096(const HostTables &t, Mfcc4096Tables &f, bool mel)
     if (mel && (!t.d.stft_ok || t.window_stft.size() != 4096)) return;
     if (t.bank.last_bin > 1025) return;  // the kernel keeps P bins 0..1024
     constexpr int32_t kRow = 1028;       // P bins a tap may touch: 0..1024 plus three zero pad bins
-    std::vector<int32_t> order(M);
-    for (size_t m = 0; m < M; ++m) order[m] = static_cast<int32_t>(m);
-    // taps are read as aligned float4s of the P row: a filter's span starts at its first bin rounded down to a multiple of 4
-    auto alen = [&](int32_t m) { return t.bank.len[m] ? (t.bank.start[m] & 3) + t.bank.len[m] : 0; };
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return alen(a) > alen(b); });
-    int32_t maxlen[4] = {0, 0, 0, 0};
-    for (size_t q = 0; q < M; ++q) maxlen[q / 64] = std::max(maxlen[q / 64], alen(order[q]));
-    for (int s = 0; s < 4; ++s) f.q4[s] = (maxlen[s] + 3) / 4;
+    std::vector<int32_t> order = sorted_deal(t, 64, 4, aligned_span, f.q4);
     balance_slots(t, 64, 4, f.q4, kRow, order);  // (the slots keep their spans; see balance_slots)
-    f.wpitch = 4 * (f.q4[0] + f.q4[1] + f.q4[2] + f.q4[3]);
-    if (f.wpitch == 0) f.wpitch = 4;
-    if ((f.wpitch / 4) % 2 == 0) f.wpitch += 4;  // odd pitch in 16-byte units: the lanes' ds_read_b128 of their rows spread over all banks
+    f.wpitch = row_pitch(f.q4, 4, true);
     if (f.wpitch > 128) return;
     // DCT stage: with n_filters % 4 == 0 the 256-term product folds twice (an even coefficient is 64 terms, an odd one two
     // halves of 64) and 64 lanes cover up to 43 coefficients in one pass; the cosine block is then one 64-term row per lane
@@ -1140,58 +958,18 @@ static void build_4096(const HostTables &t, Mfcc4096Tables &f, bool mel)
     f.cos_floats = static_cast<int32_t>(f.dct_fold2 ? 63 * L::kCosLanePitch + 64 : Cc * L::kCosPitch);
     const size_t melw0 = static_cast<size_t>(L::kCos) + f.cos_floats;
     f.tab.assign(melw0 + 64 * static_cast<size_t>(f.wpitch), 0.0f);
-    const double pi = 3.14159265358979323846;
-    auto cis = [&](double num, double den, float *dst) {
-        const double ang = -2.0 * pi * num / den;
-        dst[0] = static_cast<float>(std::cos(ang));
-        dst[1] = static_cast<float>(std::sin(ang));
-    };
-    for (int r = 1; r < 32; ++r)
-        for (int k1 = 0; k1 < 32; ++k1) {
-            const int p = (r - 1) / 2, half = (r - 1) % 2;
-            cis(static_cast<double>(k1 * r), 1024.0, &f.tab[L::kT1 + (p * 32 + k1) * 4 + 2 * half]);
-        }
+    fill_pass_twiddles(&f.tab[L::kT1], 32, 128, 4);
     for (int i = 0; i < 16; ++i)
         for (int lane = 0; lane < 64; ++lane) {
             const int k1 = lane & 31, hh = lane >> 5;
-            cis(static_cast<double>(k1 + 32 * (i + 16 * hh)), 2048.0, &f.tab[L::kT2 + (i * 64 + lane) * 2]);
-            cis(static_cast<double>(k1 + 32 * i + 512 * hh), 4096.0, &f.tab[L::kTwn + (i * 64 + lane) * 2]);
+            cis(k1 + 32 * (i + 16 * hh), 2048.0, &f.tab[L::kT2 + (i * 64 + lane) * 2]);
+            cis(k1 + 32 * i + 512 * hh, 4096.0, &f.tab[L::kTwn + (i * 64 + lane) * 2]);
         }
     // one word per (slot, lane): first P bin | filter index << 16 (one register in the kernel; one table less in its LDS)
     std::vector<int32_t> start(256, 0), filt(256, -1);
-    int32_t off = 0;
-    for (int s = 0; s < 4; ++s) {
-        const int32_t span = 4 * f.q4[s];
-        // the slot's filters go to lanes and first float4 slots that keep the lock-step ds_read_b128 tap reads conflict-free
-        std::vector<int32_t> lo4, hi4, lane_of, start4_of, idle;
-        for (int j = 0; j < 64; ++j) {
-            const size_t q = static_cast<size_t>(s) * 64 + j;
-            if (q >= M) break;
-            const int32_t m = order[q], len = t.bank.len[m], st = len ? t.bank.start[m] : 0;
-            hi4.push_back(len ? std::min(st, kRow - span) / 4 : (kRow - span) / 4);  // an empty filter may read anywhere
-            lo4.push_back(std::max<int32_t>(0, st + len - span + 3) / 4);
-            if (lo4.back() > hi4.back()) lo4.back() = hi4.back();
-        }
-        place_taps_b128(64, lo4, hi4, lane_of, start4_of, idle, (kRow - span) / 4);
-        for (int j = 0; j < 64; ++j) {
-            start[s * 64 + j] = 4 * idle[j];
-            filt[s * 64 + j] = -1;
-        }
-        for (size_t k = 0; k < lo4.size(); ++k) {
-            const size_t q = static_cast<size_t>(s) * 64 + k;
-            const int32_t m = order[q], len = t.bank.len[m], j = lane_of[k], st = 4 * start4_of[k];
-            const int32_t shift = len ? t.bank.start[m] - st : 0;  // zero weights in front of the filter's first tap
-            start[s * 64 + j] = st;
-            filt[s * 64 + j] = m;
-            for (int32_t i = 0; i < len; ++i)
-                f.tab[melw0 + static_cast<size_t>(j) * f.wpitch + off + shift + i] = t.bank.w[t.bank.off[m] + i];
-        }
-        off += span;
-    }
-    {
-        int32_t *packed = reinterpret_cast<int32_t *>(f.tab.data() + L::kStart);
-        for (int q = 0; q < 256; ++q) packed[q] = (start[q] & 0xffff) | static_cast<int32_t>(static_cast<uint32_t>(filt[q]) << 16);
-    }
+    place_slots_b128(t, 64, 4, kRow, order, f.q4, f.wpitch, &f.tab[melw0], start.data(), filt.data());
+    int32_t *packed = words(f.tab, L::kStart);
+    for (int q = 0; q < 256; ++q) packed[q] = (start[q] & 0xffff) | static_cast<int32_t>(static_cast<uint32_t>(filt[q]) << 16);
     if (f.dct_fold2) {
         // lane assignment of ss_mfcc_c2048's product stage: lanes 0 .. ne-1 the even coefficients 2 lane (filters 0 .. M/4-1),
         // then from the next even lane on pairs of lanes per odd coefficient (filters 0..63 and 64..127 of its M/2)
@@ -1206,26 +984,16 @@ static void build_4096(const HostTables &t, Mfcc4096Tables &f, bool mel)
             }
         }
     } else {
-        for (size_t cc = 0; cc < Cc; ++cc)
-            for (size_t m = 0; m < (M + 1) / 2; ++m) f.tab[L::kCos + cc * L::kCosPitch + m] = t.dct[cc * M + m];
+        store_half_cosines(t, Cc, L::kCosPitch, &f.tab[L::kCos]);
     }
-    if (mel) {
-        const size_t base = f.tab.size();
-        f.tab.resize(base + 4096);
-        for (size_t i = 0; i < 4096; ++i) f.tab[base + i] = t.window_stft[i];
-    }
+    if (mel) append_window(f.tab, t.window_stft, 4096);
     f.ok = true;
 }
 
 void build_mfcc4096(const HostTables &t, Mfcc4096Tables &f) { build_4096(t, f, false); }
 void build_mel4096(const HostTables &t, Mfcc4096Tables &f)
 {
-    build_4096(t, f, true);
-    if (f.ok) return;
-    HostTables e = without_bank(t);
-    build_4096(e, f, true);
-    f.stft_only = f.ok;
-    f.ok = false;
+    build_or_stft_only(t, f, [](const HostTables &tt, Mfcc4096Tables &ff) { build_4096(tt, ff, true); });
 }
 
 }  // namespace ss
@@ -1233,6 +1001,40 @@ void build_mel4096(const HostTables &t, Mfcc4096Tables &f)
 // ---- host-only C ABI entry points ------------------------------------------------------------
 
 namespace ss { const std::string &last_error(); }
+
+// Shared walk of the packed-call offset tables: sample_offsets[0] == 0, no entry ("clip" or "entry" in the messages) of
+// negative length or longer than 2^31 - 1 samples, then rows_of(i, len, r) gives entry i's rows or fails; `out` is the prefix sum.
+template <class RowsOf>
+static int walk_offsets(size_t n, const int64_t *sample_offsets, int64_t *out, const char *what, RowsOf rows_of)
+{
+    if (sample_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "sample_offsets[0] must be 0");
+    int64_t rows = 0;
+    out[0] = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (sample_offsets[i + 1] < sample_offsets[i])
+            return ss::fail(SS_ERR_ARG, "sample_offsets decrease at " + std::string(what) + " " + std::to_string(i));
+        const int64_t len = sample_offsets[i + 1] - sample_offsets[i];
+        if (len > 0x7fffffff) return ss::fail(SS_ERR_ARG, std::string(what) + " " + std::to_string(i) + " is longer than 2^31 - 1 samples");
+        int64_t r = 0;
+        if (int rc = rows_of(i, len, r)) return rc;
+        rows += r;
+        out[i + 1] = rows;
+    }
+    return SS_OK;
+}
+
+// the two streaming forms: one row per hop of `hop` samples; an entry without samples has none
+static int walk_stream_offsets(size_t n, const int64_t *sample_offsets, int64_t *out, int64_t hop, const char *mode)
+{
+    if (n > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many entries");
+    return walk_offsets(n, sample_offsets, out, "entry", [&](size_t i, int64_t len, int64_t &r) -> int {
+        if (len % hop)
+            return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + " (" + std::to_string(len) + " samples): " + mode + " takes whole hops of " +
+                                            std::to_string(hop) + " samples");
+        r = len / hop;
+        return SS_OK;
+    });
+}
 
 extern "C" {
 
@@ -1295,20 +1097,13 @@ int ss_packed_frame_offsets(const ss_params *p, size_t n_clips, const int64_t *s
     if (!p || !sample_offsets || !frame_offsets) return ss::fail(SS_ERR_ARG, "null argument");
     int rc = ss::validate(*p);
     if (rc) return rc;
-    if (sample_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "sample_offsets[0] must be 0");
-    int64_t rows = 0;
-    frame_offsets[0] = 0;
-    for (size_t b = 0; b < n_clips; ++b) {
-        const int64_t len = sample_offsets[b + 1] - sample_offsets[b];
-        if (len < 0) return ss::fail(SS_ERR_ARG, "sample_offsets decrease at clip " + std::to_string(b));
-        if (len > 0x7fffffff) return ss::fail(SS_ERR_ARG, "clip " + std::to_string(b) + " is longer than 2^31 - 1 samples");
+    return walk_offsets(n_clips, sample_offsets, frame_offsets, "clip", [&](size_t b, int64_t len, int64_t &r) -> int {
         size_t t = 0;
-        rc = ss::num_frames(*p, static_cast<size_t>(len), t);
-        if (rc) return ss::fail(rc, "clip " + std::to_string(b) + " (" + std::to_string(len) + " samples): " + std::string(ss::last_error()));
-        rows += static_cast<int64_t>(t);
-        frame_offsets[b + 1] = rows;
-    }
-    return SS_OK;
+        if (int e = ss::num_frames(*p, static_cast<size_t>(len), t))
+            return ss::fail(e, "clip " + std::to_string(b) + " (" + std::to_string(len) + " samples): " + std::string(ss::last_error()));
+        r = static_cast<int64_t>(t);
+        return SS_OK;
+    });
 }
 
 int ss_packed_row_offsets(const ss_params *p, size_t n_clips, const int64_t *sample_offsets, int64_t *row_offsets)
@@ -1318,19 +1113,12 @@ int ss_packed_row_offsets(const ss_params *p, size_t n_clips, const int64_t *sam
     if (rc) return rc;
     size_t R = 0, Rreal = 0;
     if ((rc = ss::stft_rows(*p, 1, R, Rreal))) return rc;  // SS_ERR_BAD_CONFIG: no STFT path (functions.rs:136)
-    if (sample_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "sample_offsets[0] must be 0");
-    int64_t rows = 0;
-    row_offsets[0] = 0;
-    for (size_t b = 0; b < n_clips; ++b) {
-        const int64_t len = sample_offsets[b + 1] - sample_offsets[b];
-        if (len < 0) return ss::fail(SS_ERR_ARG, "sample_offsets decrease at clip " + std::to_string(b));
+    return walk_offsets(n_clips, sample_offsets, row_offsets, "clip", [&](size_t b, int64_t len, int64_t &r) -> int {
         if (len == 0) return ss::fail(SS_ERR_ARG, "clip " + std::to_string(b) + " is empty");
-        if (len > 0x7fffffff) return ss::fail(SS_ERR_ARG, "clip " + std::to_string(b) + " is longer than 2^31 - 1 samples");
-        if ((rc = ss::stft_rows(*p, static_cast<size_t>(len), R, Rreal))) return rc;
-        rows += static_cast<int64_t>(R);
-        row_offsets[b + 1] = rows;
-    }
-    return SS_OK;
+        const int e = ss::stft_rows(*p, static_cast<size_t>(len), R, Rreal);
+        r = static_cast<int64_t>(R);
+        return e;
+    });
 }
 
 int ss_stft_sizes(const ss_params *p, size_t *hop, size_t *n_pad, float *wnorm)
@@ -1420,22 +1208,7 @@ int ss_frame_stream_packed_row_offsets(const ss_params *p, size_t n_active, cons
     if (rc) return rc;
     ss::Derived d;
     if ((rc = ss::derive(*p, d))) return rc;
-    if (n_active > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many entries");
-    if (sample_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "sample_offsets[0] must be 0");
-    const int64_t step = static_cast<int64_t>(d.step);
-    int64_t rows = 0;
-    row_offsets[0] = 0;
-    for (size_t i = 0; i < n_active; ++i) {
-        const int64_t len = sample_offsets[i + 1] - sample_offsets[i];
-        if (sample_offsets[i + 1] < sample_offsets[i]) return ss::fail(SS_ERR_ARG, "sample_offsets decrease at entry " + std::to_string(i));
-        if (len > 0x7fffffff) return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + " is longer than 2^31 - 1 samples");
-        if (len % step)
-            return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + " (" + std::to_string(len) +
-                                            " samples): streaming MFCC / mfe takes whole hops of " + std::to_string(step) + " samples");
-        rows += len / step;  // one row per hop; an entry without samples has none
-        row_offsets[i + 1] = rows;
-    }
-    return SS_OK;
+    return walk_stream_offsets(n_active, sample_offsets, row_offsets, static_cast<int64_t>(d.step), "streaming MFCC / mfe");
 }
 
 int ss_stream_packed_row_offsets(const ss_params *p, size_t n_active, const int64_t *sample_offsets, int64_t *row_offsets)
@@ -1446,22 +1219,7 @@ int ss_stream_packed_row_offsets(const ss_params *p, size_t n_active, const int6
     if (rc) return rc;
     ss::Derived d;
     if ((rc = ss::derive(*p, d))) return rc;
-    if (n_active > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many entries");
-    if (sample_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "sample_offsets[0] must be 0");
-    const int64_t hop = static_cast<int64_t>(d.hop);
-    int64_t rows = 0;
-    row_offsets[0] = 0;
-    for (size_t i = 0; i < n_active; ++i) {
-        const int64_t len = sample_offsets[i + 1] - sample_offsets[i];
-        if (sample_offsets[i + 1] < sample_offsets[i]) return ss::fail(SS_ERR_ARG, "sample_offsets decrease at entry " + std::to_string(i));
-        if (len > 0x7fffffff) return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + " is longer than 2^31 - 1 samples");
-        if (len % hop)
-            return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + " (" + std::to_string(len) +
-                                            " samples): continuous streaming takes whole hops of " + std::to_string(hop) + " samples");
-        rows += len / hop;  // one row per hop; an entry without samples has none
-        row_offsets[i + 1] = rows;
-    }
-    return SS_OK;
+    return walk_stream_offsets(n_active, sample_offsets, row_offsets, static_cast<int64_t>(d.hop), "continuous streaming");
 }
 
 int ss_filterbank(const ss_params *p, float *fb, int32_t *idx)

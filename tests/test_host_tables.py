@@ -1,6 +1,8 @@
 """Host-side table builders under AddressSanitizer + UBSan (CPU only): tools/hosttest/fuzz_tables.cpp builds the LDS blocks of
 every kernel for pseudo-random valid configurations and checks that each filter's weights reach exactly one (slot, lane) bit
-for bit, that no lane reads past its P row and that the cosine rows are the host DCT table in the kernel's layout."""
+for bit, that no lane reads past its P row and that the cosine rows are the host DCT table in the kernel's layout.  Its --digest
+mode (one line of flags, sizes and a hash of the table bytes per block: what two builds of ss_host.cpp are compared by) runs here
+too, twice, so that it stays buildable, clean under the sanitizers and deterministic."""
 import os
 import shutil
 import subprocess
@@ -21,3 +23,9 @@ def test_table_builders_sanitized(tmp_path):
         r = subprocess.run([exe, "1000", seed], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
         assert "all checks passed" in r.stdout
+    digests = [subprocess.run([exe, "--digest", "60", "12345"], capture_output=True, text=True, timeout=300) for _ in range(2)]
+    for r in digests:
+        assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+    assert digests[0].stdout and digests[0].stdout == digests[1].stdout
+    # the named configurations and the random ones, ten blocks each, none rejected by build_tables
+    assert digests[0].stdout.count("\n") >= 10 * 60 and " fnv " in digests[0].stdout

@@ -7,6 +7,10 @@
 //     block, starting at the P bin in the start table -- are, bit for bit, the dense bank's row (zero outside);
 //   * no (slot, lane) reads past the P row the kernel keeps;
 //   * the cosine rows equal the host DCT table in the layout the kernel indexes (twice-folded per-lane rows of the 4096 kernel).
+// `fuzz_tables --digest [cases] [seed]` checks nothing and prints, for a fixed list of named configurations and then the same
+// pseudo-random ones, one line per kernel block: every flag and integer of its struct, the table's size and a 64-bit FNV-1a hash of
+// its bytes.  Two builds of ss_host.cpp compute the same tables exactly when these outputs are equal (the hashes depend on the
+// host's cos / sin, so they compare builds on one machine and are pinned nowhere).
 #include "ss_internal.h"
 
 #include <cmath>
@@ -79,33 +83,196 @@ static void check_mel_block(const std::string &what, const ss::HostTables &t, co
     for (size_t m = 0; m < M; ++m) CHECK(seen[m] == 1, "filter %zu placed %d times", m, seen[m]);
 }
 
-int main(int argc, char **argv)
+static ss_params random_params()
 {
-    const int cases = argc > 1 ? std::atoi(argv[1]) : 600;
-    g_state = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 12345;
     static const unsigned rates[] = {8000, 11025, 16000, 22050, 32000, 44100, 48000};
     static const unsigned ffts[] = {256, 512, 512, 1024, 2048, 2048, 4096, 4096, 400, 128, 8192};
+    ss_params p;
+    const unsigned sr = rates[rnd() % 7];
+    ss_params_default(&p, sr);
+    p.fft_points = ffts[rnd() % 11];
+    const double fl = (0.25 + 0.75 * urand()) * p.fft_points / sr;
+    p.frame_length = static_cast<float>(rnd() % 4 == 0 ? static_cast<double>(p.fft_points) / sr : fl);
+    p.frame_stride = static_cast<float>(p.frame_length * (rnd() % 3 == 0 ? 1.0 : 0.1 + 0.6 * urand()));
+    static const unsigned fcounts[] = {1, 2, 5, 13, 20, 23, 26, 32, 40, 40, 48, 64, 80, 100, 101, 128, 128, 130, 200, 252, 255, 256, 256, 300};
+    p.num_filters = fcounts[rnd() % 24];
+    p.num_cepstral = 1 + rnd() % (p.num_filters < 64 ? p.num_filters : 64);
+    if (rnd() % 3 == 0) p.low_frequency = static_cast<float>(urand() * sr / 8);
+    if (rnd() % 2 == 0) p.high_frequency = static_cast<float>(sr / 2.0 * (0.3 + 0.7 * urand()));
+    p.mel_scale = rnd() % 4 == 0 ? 1 + rnd() % 2 : 0;
+    p.mel_norm = p.mel_scale && rnd() % 2 ? 1 : 0;
+    p.mfcc_window = rnd() % 3;
+    p.spectrum_exponent = 1 + rnd() % 2;
+    p.dc_elimination = rnd() % 2;
+    p.framing = rnd() % 8 == 0 ? SS_FRAMING_CENTER : SS_FRAMING_CONTRACT;
+    return p;
+}
+
+// ---- digest mode ----
+
+// one line per block; a field the block's struct does not have prints as -1
+struct Digest {
+    int ok = -1, stft_only = -1, windowed = -1, fullp = -1, paired = -1, tight = -1, dct_fold2 = -1, cos_floats = -1, win_floats = -1;
+};
+
+template <class Tables, int NQ>
+static void digest_line(const char *cfg, const char *block, const Tables &f, const int32_t (&q4)[NQ], Digest d)
+{
+    unsigned long long h = 1469598103934665603ull;  // FNV-1a over the raw bytes of tab
+    const unsigned char *b = reinterpret_cast<const unsigned char *>(f.tab.data());
+    for (size_t i = 0; i < f.tab.size() * sizeof(float); ++i) h = (h ^ b[i]) * 1099511628211ull;
+    std::printf("%s | %s ok %d stft_only %d windowed %d fullp %d paired %d tight %d dct_fold2 %d cos_floats %d win_floats %d wpitch %d q4", cfg, block, f.ok,
+                d.stft_only, d.windowed, d.fullp, d.paired, d.tight, d.dct_fold2, d.cos_floats, d.win_floats, f.wpitch);
+    for (int s = 0; s < NQ; ++s) std::printf(" %d", q4[s]);
+    std::printf(" size %zu fnv %016llx\n", f.tab.size(), h);
+}
+
+static void digest_config(const char *cfg, const ss_params &p)
+{
+    ss::HostTables t;
+    const int rc = ss::build_tables(p, t);
+    if (rc != 0) {
+        std::printf("%s | rejected %d\n", cfg, rc);
+        return;
+    }
+    Digest d;
+    {
+        ss::Fast512Tables f;
+        ss::build_fast512(t, f);
+        d = Digest{};
+        d.fullp = f.fullp, d.paired = f.paired, d.tight = f.tight, d.win_floats = f.win_floats;
+        digest_line(cfg, "fast512", f, f.q4, d);
+    }
+    {
+        ss::Mfcc512wTables f;
+        ss::build_mfcc512w(t, f);
+        d = Digest{};
+        d.windowed = f.windowed;
+        digest_line(cfg, "mfcc512w", f, f.q4, d);
+    }
+    {
+        ss::Mel512Tables f;
+        ss::build_mel512(t, f);
+        d = Digest{};
+        d.stft_only = f.stft_only, d.fullp = f.fullp;
+        digest_line(cfg, "mel512", f, f.q4, d);
+    }
+    {
+        ss::Mfcc256Tables f;
+        ss::build_mfcc256(t, f);
+        d = Digest{};
+        d.windowed = f.windowed;
+        digest_line(cfg, "mfcc256", f, f.q4, d);
+    }
+    for (int mel = 0; mel < 2; ++mel) {
+        ss::Mfcc1024Tables f;
+        if (mel) ss::build_mel1024(t, f);
+        else ss::build_mfcc1024(t, f);
+        d = Digest{};
+        d.stft_only = f.stft_only, d.windowed = f.windowed, d.fullp = f.fullp;
+        digest_line(cfg, mel ? "mel1024" : "mfcc1024", f, f.q4, d);
+    }
+    {
+        ss::Mfcc2048Tables f;
+        ss::build_mfcc2048(t, f);
+        d = Digest{};
+        d.windowed = f.windowed, d.fullp = f.fullp;
+        digest_line(cfg, "mfcc2048", f, f.q4, d);
+    }
+    {
+        ss::Mel2048Tables f;
+        ss::build_mel2048(t, f);
+        d = Digest{};
+        d.stft_only = f.stft_only, d.fullp = f.fullp;
+        digest_line(cfg, "mel2048", f, f.q4, d);
+    }
+    for (int mel = 0; mel < 2; ++mel) {
+        ss::Mfcc4096Tables f;
+        if (mel) ss::build_mel4096(t, f);
+        else ss::build_mfcc4096(t, f);
+        d = Digest{};
+        d.stft_only = f.stft_only, d.dct_fold2 = f.dct_fold2, d.cos_floats = f.cos_floats;
+        digest_line(cfg, mel ? "mel4096" : "mfcc4096", f, f.q4, d);
+    }
+}
+
+// The shapes the benchmark and the dedicated kernels' tests run, which random draws rarely hit.  frame_length 0 = half the
+// transform (the STFT path needs fft_points >= 2 * frame_size); high_frequency 0 = fs / 2.
+struct Named {
+    const char *name;
+    unsigned sr, fft;
+    double frame_length, frame_stride;
+    unsigned filters, ceps;
+    double high;
+    int mel_scale, window;
+};
+static const Named kNamed[] = {
+    {"cfg2", 16000, 512, 0.02, 0.01, 40, 13, 0, 0, 0},
+    {"cfg3", 16000, 2048, 0.032, 0.032, 128, 13, 8000.0, 0, 0},
+    {"cfg5", 44100, 4096, 4096 / 44100.0, 1024 / 44100.0, 256, 40, 22050.0, 0, 0},
+    {"cfg2 hann", 16000, 512, 0.02, 0.01, 40, 13, 0, 0, SS_WINDOW_HANN},
+    {"cfg2 vorbis", 16000, 512, 0.02, 0.01, 40, 13, 0, 0, SS_WINDOW_VORBIS},
+    {"cfg2 slaney to fs/2", 16000, 512, 0.02, 0.01, 40, 13, 0, SS_MEL_SLANEY, 0},
+    {"cfg2 htk to fs/2", 16000, 512, 0.02, 0.01, 40, 13, 0, SS_MEL_HTK, 0},
+    {"512 x 80 filters x 32", 16000, 512, 0.02, 0.01, 80, 32, 0, 0, 0},
+    {"512 x 80 filters x 32 hann", 16000, 512, 0.02, 0.01, 80, 32, 0, 0, SS_WINDOW_HANN},
+    {"512 stft", 16000, 512, 0, 0, 40, 13, 0, 0, 0},
+    {"512 stft 80 filters", 16000, 512, 0, 0, 80, 13, 0, 0, 0},
+    {"512 stft slaney to fs/2", 16000, 512, 0, 0, 64, 13, 0, SS_MEL_SLANEY, 0},
+    {"512 stft 100 filters", 16000, 512, 0, 0, 100, 13, 0, 0, 0},
+    {"256 at 8 kHz", 8000, 256, 0.02, 0.01, 40, 13, 0, 0, 0},
+    {"256 at 8 kHz vorbis", 8000, 256, 0.02, 0.01, 32, 20, 0, 0, SS_WINDOW_VORBIS},
+    {"1024 x 128", 16000, 1024, 0, 0, 128, 20, 0, 0, 0},
+    {"1024 x 128 hann", 16000, 1024, 0, 0, 128, 20, 0, 0, SS_WINDOW_HANN},
+    {"1024 x 128 slaney to fs/2", 16000, 1024, 0, 0, 128, 20, 0, SS_MEL_SLANEY, 0},
+    {"1024 x 200 filters", 16000, 1024, 0, 0, 200, 20, 0, 0, 0},
+    {"2048 x 128", 16000, 2048, 0, 0, 128, 20, 0, 0, 0},
+    {"2048 x 128 vorbis", 16000, 2048, 0, 0, 128, 20, 0, 0, SS_WINDOW_VORBIS},
+    {"2048 x 128 slaney to fs/2", 16000, 2048, 0, 0, 128, 20, 0, SS_MEL_SLANEY, 0},
+    {"2048 x 128 htk to fs/2", 22050, 2048, 0, 0, 128, 40, 0, SS_MEL_HTK, 0},
+    {"2048 x 300 filters", 16000, 2048, 0, 0, 300, 20, 0, 0, 0},
+    {"4096 x 255", 44100, 4096, 0, 0, 255, 40, 0, 0, 0},
+    {"4096 x 256 x 44", 44100, 4096, 0, 0, 256, 44, 0, 0, 0},
+    {"4096 x 256 slaney", 44100, 4096, 0, 0, 256, 40, 11025.0, SS_MEL_SLANEY, 0},
+    {"4096 x 300 filters", 44100, 4096, 0, 0, 300, 40, 0, 0, 0},
+};
+
+static int digest_main(int cases)
+{
+    for (const Named &n : kNamed) {
+        ss_params p;
+        ss_params_default(&p, n.sr);
+        p.fft_points = n.fft;
+        p.frame_length = static_cast<float>(n.frame_length > 0 ? n.frame_length : n.fft / 2.0 / n.sr);
+        p.frame_stride = static_cast<float>(n.frame_stride > 0 ? n.frame_stride : n.fft / 2.0 / n.sr);
+        p.num_filters = n.filters;
+        p.num_cepstral = n.ceps;
+        if (n.high > 0) p.high_frequency = static_cast<float>(n.high);
+        p.mel_scale = n.mel_scale;
+        p.mfcc_window = n.window;
+        digest_config(n.name, p);
+    }
+    for (int it = 0; it < cases; ++it) {
+        const ss_params p = random_params();
+        char name[32];
+        std::snprintf(name, sizeof name, "case %d", it);
+        digest_config(name, p);
+    }
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    const bool digest = argc > 1 && std::strcmp(argv[1], "--digest") == 0;
+    if (digest) --argc, ++argv;
+    const int cases = argc > 1 ? std::atoi(argv[1]) : 600;
+    g_state = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 12345;
+    if (digest) return digest_main(cases);
     int built[10] = {0};
     int valid = 0;
     for (int it = 0; it < cases; ++it) {
-        ss_params p;
-        const unsigned sr = rates[rnd() % 7];
-        ss_params_default(&p, sr);
-        p.fft_points = ffts[rnd() % 11];
-        const double fl = (0.25 + 0.75 * urand()) * p.fft_points / sr;
-        p.frame_length = static_cast<float>(rnd() % 4 == 0 ? static_cast<double>(p.fft_points) / sr : fl);
-        p.frame_stride = static_cast<float>(p.frame_length * (rnd() % 3 == 0 ? 1.0 : 0.1 + 0.6 * urand()));
-        static const unsigned fcounts[] = {1, 2, 5, 13, 20, 23, 26, 32, 40, 40, 48, 64, 80, 100, 101, 128, 128, 130, 200, 252, 255, 256, 256, 300};
-        p.num_filters = fcounts[rnd() % 24];
-        p.num_cepstral = 1 + rnd() % (p.num_filters < 64 ? p.num_filters : 64);
-        if (rnd() % 3 == 0) p.low_frequency = static_cast<float>(urand() * sr / 8);
-        if (rnd() % 2 == 0) p.high_frequency = static_cast<float>(sr / 2.0 * (0.3 + 0.7 * urand()));
-        p.mel_scale = rnd() % 4 == 0 ? 1 + rnd() % 2 : 0;
-        p.mel_norm = p.mel_scale && rnd() % 2 ? 1 : 0;
-        p.mfcc_window = rnd() % 3;
-        p.spectrum_exponent = 1 + rnd() % 2;
-        p.dc_elimination = rnd() % 2;
-        p.framing = rnd() % 8 == 0 ? SS_FRAMING_CENTER : SS_FRAMING_CONTRACT;
+        const ss_params p = random_params();
+        const unsigned sr = p.sample_rate;
         ss::HostTables t;
         if (ss::build_tables(p, t) != 0) continue;  // rejected configurations (band edges, frame longer than fft_points ...) are fine
         ++valid;
