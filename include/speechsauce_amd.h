@@ -417,6 +417,35 @@ int ss_mfcc_stream_packed(const ss_config *cfg, const float *x, size_t n_active,
 int ss_mfe_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets,
                          const int32_t *slots, size_t pool_streams, float *pool, float *feat, float *energy);
 
+/* ---- the same pool fed signed 16-bit PCM ----
+ * Live audio arrives as int16 (RTP, WAV, capture devices).  These four entry points take the packed chunks as int16 and convert
+ * on load: stream sample s = (float)pcm * scale.  Everything else is the float pool's contract above, word for word -- entries,
+ * R_i = 0, slots, total_rows, containment and the error word, capturability as a two-launch linear chain whose grids depend on
+ * n_active and total_rows only, the host forms' table checks and the rule that the caller's pool is written only after everything
+ * before it succeeded.  Offsets are in samples, not bytes.  The pool stays float: a stream may be fed PCM on one call and floats
+ * on the next.
+ *   scale: a power of two in [2^-64, 2^64], otherwise SS_ERR_ARG -- 2^-15 for normalised audio, 1.0 for integer-valued floats
+ *   (the python_speech_features habit).  With a power of two the product is exact, so fusing it into what follows changes no bit.
+ *   Equivalence: per entry the rows, and the pool row afterwards, are bit for bit those of ss_mfcc_stream_packed_device /
+ *   ss_mfe_stream_packed_device on the float buffer x_f[k] = (float)pcm[k] * scale with the same tables, the same pool and the
+ *   same norm_frames.
+ *   Kernels: the float call's kernel family with a PCM loader, by the same selection rule -- ss_mfcc_c256spi<10,exact,bank421,sym>
+ *   / ss_mfcc_c256spi<10,exact,bank421,mfe> for the default 512-point shape, ss_front_generic_fstreampi<LOG2C[,chirpz]> for every
+ *   other configuration, then ss_stream_advance_packed_i16 (skipped where S == 0).
+ *   Alignment: d_x must be 4-byte aligned in the device forms (a sample pair is one dword), SS_ERR_ARG otherwise; the host forms
+ *   stage the buffer and have no such rule.
+ * The scale and alignment checks come before any launch and before the pool or the outputs are touched. */
+int ss_mfcc_stream_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                     const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                     float scale, uint32_t norm_frames, float *d_pool, float *d_out, void *stream);
+int ss_mfe_stream_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                    const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                    float scale, float *d_pool, float *d_feat, float *d_energy, void *stream);
+int ss_mfcc_stream_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
+                              const int32_t *slots, size_t pool_streams, float scale, uint32_t norm_frames, float *pool, float *out);
+int ss_mfe_stream_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
+                             const int32_t *slots, size_t pool_streams, float scale, float *pool, float *feat, float *energy);
+
 /* ---- ragged streaming STFT / mel spectrogram over a pool of stream states ----
  * The frame-path pool above, carried over to the STFT path (ss_stft_stream* / ss_mel_spectrogram_stream*), SS_STREAM_CONTINUOUS
  * only: SS_STREAM_REFERENCE's partial chunks and trailing n_pad zero rows have no meaning for a live pool.  H = the hop of

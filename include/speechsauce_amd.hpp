@@ -297,6 +297,44 @@ inline std::vector<float> cmvnw(const std::vector<float> &vec, size_t rows, size
     return out;
 }
 
+// Ragged streaming MFCC / mfe over a pool of stream states, fed signed 16-bit PCM (ss_*_stream_packed_i16*): stream sample =
+// pcm * scale, scale a power of two in [2^-64, 2^64]; the pool stays float.  Device forms: raw device pointers and a hipStream_t,
+// asynchronous (d_x 4-byte aligned).  Host forms: x the packed chunks, sample_offsets n_active + 1 offsets in samples, slots the
+// pool row of each entry, pool the [pool_streams x S] states (updated in place); rows = sample_offsets.back() / hop.
+inline void mfcc_stream_packed_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t n_active, const int64_t *d_sample_offsets,
+                                          const int64_t *d_row_offsets, std::size_t total_rows, const int32_t *d_slots,
+                                          std::size_t pool_streams, float scale, uint32_t norm_frames, float *d_pool, float *d_out, void *stream)
+{
+    check(ss_mfcc_stream_packed_i16_device(cfg.handle(), d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams,
+                                           scale, norm_frames, d_pool, d_out, stream));
+}
+
+inline void mfe_stream_packed_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t n_active, const int64_t *d_sample_offsets,
+                                         const int64_t *d_row_offsets, std::size_t total_rows, const int32_t *d_slots,
+                                         std::size_t pool_streams, float scale, float *d_pool, float *d_feat, float *d_energy, void *stream)
+{
+    check(ss_mfe_stream_packed_i16_device(cfg.handle(), d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams,
+                                          scale, d_pool, d_feat, d_energy, stream));
+}
+
+inline void mfcc_stream_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
+                                   const std::vector<int32_t> &slots, std::size_t pool_streams, float scale, uint32_t norm_frames,
+                                   std::vector<float> &pool, std::vector<float> &out)
+{
+    if (sample_offsets.size() != slots.size() + 1) throw Error(SS_ERR_ARG, "mfcc_stream_packed_i16: one offset more than slots");
+    check(ss_mfcc_stream_packed_i16(cfg.handle(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_streams, scale,
+                                    norm_frames, pool.data(), out.data()));
+}
+
+inline void mfe_stream_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
+                                  const std::vector<int32_t> &slots, std::size_t pool_streams, float scale, std::vector<float> &pool,
+                                  std::vector<float> &feat, std::vector<float> &energy)
+{
+    if (sample_offsets.size() != slots.size() + 1) throw Error(SS_ERR_ARG, "mfe_stream_packed_i16: one offset more than slots");
+    check(ss_mfe_stream_packed_i16(cfg.handle(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_streams, scale,
+                                   pool.data(), feat.data(), energy.data()));
+}
+
 // cmvn / cmvnw / power_to_db of every clip of a packed block on its own rows (ss_*_packed): clip b owns rows offsets[b] ..
 // offsets[b+1] of the [total_rows x cols] block `vec`; offsets has n_clips + 1 non-decreasing entries and starts at 0
 inline std::vector<float> cmvn_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols,

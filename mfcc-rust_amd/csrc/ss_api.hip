@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -1042,7 +1043,25 @@ int frame_stream_host(const ss_config *cfg, int out_kind, const float *x, size_t
 // n_active entries of different hop counts, each over the pool row its slot names, then the advance of the named rows -- a linear
 // chain of two kernels on `stream` (none for the advance where S == 0).  The tables are device arrays read by the kernels only
 // (FrameStreamPackedArgs, ss_device.h); the grids come from n_active and total_rows.  Candidate order as launch_frame_stream.
-int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n_active, const int64_t *d_so, const int64_t *d_ro,
+// The chunks of a call: floats, or signed 16-bit PCM with its scale (the _i16 entry points: the same chain on the kernels' PCM builds).
+struct PoolChunks {
+    const float *f = nullptr;
+    const int16_t *pcm = nullptr;
+    float scale = 1.0f;
+    bool is_pcm = false;
+    PoolChunks(const float *x) : f(x) {}
+    PoolChunks(const int16_t *x, float s) : pcm(x), scale(s), is_pcm(true) {}
+    const void *ptr() const { return is_pcm ? static_cast<const void *>(pcm) : f; }
+    size_t sample_bytes() const { return is_pcm ? sizeof(int16_t) : sizeof(float); }
+};
+// a power of two in [2^-64, 2^64]: the product with an int16 is exact (and never subnormal)
+bool pcm_scale_ok(float scale)
+{
+    int ex = 0;
+    return std::isfinite(scale) && scale > 0.0f && std::frexp(scale, &ex) == 0.5f && ex - 1 >= -64 && ex - 1 <= 64;
+}
+
+int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_active, const int64_t *d_so, const int64_t *d_ro,
                                size_t total_rows, const int32_t *d_slots, size_t pool_streams, uint32_t norm_frames, float *d_pool,
                                float *out0, float *out1, hipStream_t stream)
 {
@@ -1052,8 +1071,10 @@ int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const float *
     size_t S = 0;
     int rc = ss_frame_stream_state_len(&h.params, &S);
     if (rc) return rc;
-    if (!d_x || !d_so || !d_ro || !d_slots || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !d_pool))
+    if (!x.ptr() || !d_so || !d_ro || !d_slots || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !d_pool))
         return ss::fail(SS_ERR_ARG, "null buffer");
+    if (x.is_pcm && !pcm_scale_ok(x.scale)) return ss::fail(SS_ERR_ARG, "scale must be a power of two in [2^-64, 2^64]");
+    if (x.is_pcm && (reinterpret_cast<uintptr_t>(x.pcm) & 3u)) return ss::fail(SS_ERR_ARG, "the PCM buffer must be 4-byte aligned");
     if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull || total_rows >= 0x80000000ull)
         return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
     if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
@@ -1070,7 +1091,7 @@ int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const float *
         const int erc = pending_device_error(cfg);
         if (erc) return erc;
     }
-    const ss::FrontArgs a = frame_stream_front_args(cfg, out_kind, d_x, norm_frames, out0, out1);
+    const ss::FrontArgs a = frame_stream_front_args(cfg, out_kind, x.f, norm_frames, out0, out1);
     ss::FrameStreamPackedArgs fsp{};
     fsp.pool = d_pool;
     fsp.state_len = static_cast<uint32_t>(S);
@@ -1083,20 +1104,23 @@ int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const float *
     fsp.total_rows = static_cast<uint32_t>(total_rows);
     fsp.step = h.d.step;
     fsp.err = cfg->d_err;
+    const ss::FrameStreamPackedPcmArgs pcm{fsp, x.pcm, x.scale};
     ss::LaunchInfo info{};
     hipError_t e = hipErrorInvalidValue;
     if (frame_stream_fast_candidate(cfg, a)) {
         const ss::Fast512Args f = frame_stream_fast_args(cfg, a);
-        e = ss::launch_mfcc_c256_stream_packed(f, fsp, stream, cfg->num_cus, &info);
+        e = x.is_pcm ? ss::launch_mfcc_c256_stream_packed(f, pcm, stream, cfg->num_cus, &info)
+                     : ss::launch_mfcc_c256_stream_packed(f, fsp, stream, cfg->num_cus, &info);
         // hipErrorInvalidValue before the launch: the configuration has no ragged streaming build of this kernel -> the generic build
         if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mfcc_c256_stream_packed");
     }
     if (e != hipSuccess) {
-        e = ss::launch_front_generic_frame_stream_packed(a, fsp, h.d.log2c, stream, cfg->num_cus, &info);
+        e = x.is_pcm ? ss::launch_front_generic_frame_stream_packed(a, pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                     : ss::launch_front_generic_frame_stream_packed(a, fsp, h.d.log2c, stream, cfg->num_cus, &info);
         if (e != hipSuccess) return hip_fail(e, "launch_front_generic_frame_stream_packed");
     }
     g_last_kernel = info.kernel_name;
-    e = ss::launch_stream_advance_packed(fsp, d_x, stream);
+    e = x.is_pcm ? ss::launch_stream_advance_packed(pcm, stream) : ss::launch_stream_advance_packed(fsp, x.f, stream);
     if (e != hipSuccess) return hip_fail(e, "launch_stream_advance_packed");
     return SS_OK;
 }
@@ -1105,7 +1129,7 @@ int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const float *
 // pool rows (gathered into a compact block whose row i is entry i's: the device call runs on slots 0 .. n_active - 1) go up, the
 // outputs and the named rows come down on the config's first host-pipeline stream.  The caller's pool is written only once
 // everything before it succeeded.
-int frame_stream_packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_active, const int64_t *so, const int32_t *slots,
+int frame_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_active, const int64_t *so, const int32_t *slots,
                              size_t pool_streams, uint32_t norm_frames, float *pool, float *out0, float *out1)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
@@ -1114,7 +1138,8 @@ int frame_stream_packed_host(const ss_config *cfg, int out_kind, const float *x,
     size_t S = 0;
     int rc = ss_frame_stream_state_len(&h.params, &S);
     if (rc) return rc;
-    if (!x || !so || !slots || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !pool)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (!x.ptr() || !so || !slots || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !pool)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (x.is_pcm && !pcm_scale_ok(x.scale)) return ss::fail(SS_ERR_ARG, "scale must be a power of two in [2^-64, 2^64]");
     if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull)
         return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
     if (out_kind == ss::OUT_MFCC && h.params.dct_norm != SS_DCT_ORTHO && norm_frames == 0)
@@ -1152,18 +1177,19 @@ int frame_stream_packed_host(const ss_config *cfg, int out_kind, const float *x,
     hipStream_t st = hp.stream[0];
     const size_t tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * S * sizeof(float);
     DeviceBuf dx, dso, dro, dsl, dp, d0, d1;
-    if ((rc = dx.alloc(samples * sizeof(float))) || (rc = dso.alloc(tbytes)) || (rc = dro.alloc(tbytes)) ||
+    if ((rc = dx.alloc(samples * x.sample_bytes())) || (rc = dso.alloc(tbytes)) || (rc = dro.alloc(tbytes)) ||
         (rc = dsl.alloc(n_active * sizeof(int32_t))) || (S > 0 && (rc = dp.alloc(sbytes))) || (rc = d0.alloc(rows * cols * sizeof(float))) ||
         (out1 && (rc = d1.alloc(rows * sizeof(float)))))
         return rc;
-    hipError_t e = samples ? hipMemcpyAsync(dx.p, x, samples * sizeof(float), hipMemcpyHostToDevice, st) : hipSuccess;
+    hipError_t e = samples ? hipMemcpyAsync(dx.p, x.ptr(), samples * x.sample_bytes(), hipMemcpyHostToDevice, st) : hipSuccess;
     if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, tbytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dro.p, ro.data(), tbytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dsl.p, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && S > 0) e = hipMemcpyAsync(dp.p, rows_host.data(), sbytes, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
     if (rc == SS_OK)
-        rc = launch_frame_stream_packed(cfg, out_kind, dx.as<const float>(), n_active, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
+        rc = launch_frame_stream_packed(cfg, out_kind, x.is_pcm ? PoolChunks(dx.as<const int16_t>(), x.scale) : PoolChunks(dx.as<const float>()),
+                                        n_active, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
                                         dsl.as<const int32_t>(), n_active, norm_frames, S > 0 ? dp.as<float>() : nullptr, d0.as<float>(),
                                         out1 ? d1.as<float>() : nullptr, st);
     if (rc == SS_OK && rows > 0) {
@@ -2636,6 +2662,36 @@ int ss_mfe_stream_packed(const ss_config *cfg, const float *x, size_t n_active, 
                          size_t pool_streams, float *pool, float *feat, float *energy)
 {
     return frame_stream_packed_host(cfg, ss::OUT_MFE, x, n_active, sample_offsets, slots, pool_streams, 1u, pool, feat, energy);
+}
+
+int ss_mfcc_stream_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                     const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                     float scale, uint32_t norm_frames, float *d_pool, float *d_out, void *stream)
+{
+    return launch_frame_stream_packed(cfg, ss::OUT_MFCC, PoolChunks(d_x, scale), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots,
+                                      pool_streams, norm_frames, d_pool, d_out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int ss_mfe_stream_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                    const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                    float scale, float *d_pool, float *d_feat, float *d_energy, void *stream)
+{
+    return launch_frame_stream_packed(cfg, ss::OUT_MFE, PoolChunks(d_x, scale), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots,
+                                      pool_streams, 1u, d_pool, d_feat, d_energy, static_cast<hipStream_t>(stream));
+}
+
+int ss_mfcc_stream_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                              size_t pool_streams, float scale, uint32_t norm_frames, float *pool, float *out)
+{
+    return frame_stream_packed_host(cfg, ss::OUT_MFCC, PoolChunks(x, scale), n_active, sample_offsets, slots, pool_streams, norm_frames, pool,
+                                    out, nullptr);
+}
+
+int ss_mfe_stream_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                             size_t pool_streams, float scale, float *pool, float *feat, float *energy)
+{
+    return frame_stream_packed_host(cfg, ss::OUT_MFE, PoolChunks(x, scale), n_active, sample_offsets, slots, pool_streams, 1u, pool, feat,
+                                    energy);
 }
 
 int ss_mel_spectrogram_stream_packed_device(const ss_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,

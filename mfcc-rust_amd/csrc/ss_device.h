@@ -343,6 +343,25 @@ hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const Fr
 // last S samples of (old row ++ the entry's chunk), in place (ss_stream_advance's discipline).  Grid-stride over the entries.
 hipError_t launch_stream_advance_packed(const FrameStreamPackedArgs &s, const float *x, hipStream_t stream);
 
+// The same pool fed signed 16-bit PCM (ss_mfcc_stream_packed_i16_device / ss_mfe_stream_packed_i16_device): chunk sample k of the
+// call is (float)x[k] * scale, scale a power of two (the product is exact, so contracting it into what follows changes no bit).
+// The entry block is the float pool's, so that stream_entry(), stream_check_entries() and the lookups over its tables serve both;
+// the type of its own selects the PCM builds in the kernels' trailing argument packs (FrontArgs::x / Fast512Args::x are unused
+// there).  Offsets stay in samples.  x is 4-byte aligned where the headline build runs (a sample pair is one dword: every so[i] is
+// a multiple of the even step); the generic build and the advance read single samples.
+struct FrameStreamPackedPcmArgs {
+    FrameStreamPackedArgs e;
+    const int16_t *x;  // the packed chunks
+    float scale;
+};
+// sample k of a PCM buffer
+__device__ __forceinline__ float pcm_sample(const int16_t *x, long long k, float scale) { return static_cast<float>(x[k]) * scale; }
+// a as for launch_front_generic_frame_stream_packed (a.x unused)
+hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const FrameStreamPackedPcmArgs &s, uint32_t log2c, hipStream_t stream,
+                                                    int num_cus, LaunchInfo *info);
+// ss_stream_advance_packed with the chunk read as PCM: the pool rows end up holding the floats the float call would have stored
+hipError_t launch_stream_advance_packed(const FrameStreamPackedPcmArgs &s, hipStream_t stream);
+
 // Ragged streaming STFT / mel spectrogram over a pool of stream states (ss_mel_spectrogram_stream_packed_device /
 // ss_stft_stream_packed_device): the same tables on the STFT path, continuous mode.  The entry block is the frame pool's, with
 // step = hop, state_len = fft_points - hop and lead unused, so that stream_entry(), stream_check_entries(), the lookups over its tables and
@@ -447,6 +466,10 @@ hipError_t launch_mfcc_c256_stream(const Fast512Args &a, const FrameStreamArgs &
 // serves, with a.x = the packed chunks (batch / n_samples / n_frames / ld unused) and the quad range over s.total_rows.
 // hipErrorInvalidValue before the launch for every other configuration.
 hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a, const FrameStreamPackedArgs &s, hipStream_t stream, int num_cus,
+                                          LaunchInfo *info);
+// the same shapes fed 16-bit PCM (FrameStreamPackedPcmArgs, declared above; a.x unused), reported as ss_mfcc_c256spi<...>; s.x not
+// 4-byte aligned is hipErrorInvalidValue too
+hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a, const FrameStreamPackedPcmArgs &s, hipStream_t stream, int num_cus,
                                           LaunchInfo *info);
 // whether the kernel has an mfe-output / windowed / pre-emphasised build for this shape (the default bank at flen 320)
 bool mfcc_c256_has_mfe(const Fast512Args &a);

@@ -11,6 +11,9 @@
 // ss_front_generic<LOG2C, BLU, FrameStreamPackedArgs> (reported as ss_front_generic_fstreamp<LOG2C>): the same over a pool of stream
 // states -- packed chunks of different hop counts, each on the pool row its entry names (FrameStreamPackedArgs, ss_device.h);
 // ss_stream_advance_packed moves the named pool rows on behind it.
+// ss_front_generic<LOG2C, BLU, FrameStreamPackedPcmArgs> (reported as ss_front_generic_fstreampi<LOG2C>): that pool fed signed
+// 16-bit PCM -- a chunk sample or pre-emphasis tap is (float)int16 * scale (FrameStreamPackedPcmArgs, ss_device.h), the state stays
+// float; ss_stream_advance_packed_i16 moves the named pool rows on behind it.
 // ss_front_generic<LOG2C, BLU, VarRowsArgs> (reported as ss_front_generic_varrows<LOG2C>): the STFT / mel path over packed clips of
 // different lengths (VarRowsArgs, ss_device.h), handed out in tiles of packed rows.
 // ss_front_generic<LOG2C, BLU, StftStreamPackedArgs> (reported as ss_front_generic_streamp<LOG2C>): the STFT / mel path over a pool
@@ -252,18 +255,20 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
 // sample t * step - lead, and a frame sample or pre-emphasis tap before the chunk comes from the stream's state (no circular wrap).
 // FSP: FSTREAM over a pool of states (launch_front_generic_frame_stream_packed) -- the flat frame index is the packed output row, and
 // the row's entry (its chunk, its row within the chunk, its pool row) comes from the device tables (FrameStreamPackedArgs).
+// FSPI: FSP with the chunks as 16-bit PCM (FrameStreamPackedPcmArgs: its entry block is FSP's; state reads are unchanged).
 // VARR: the STFT / mel path of launch_front_generic_varrows -- a workgroup visit is a tile of packed rows, every row finds its own
 // clip; the transposed mel flush writes each row into its clip's [M x R_b] block.
 // SPR: VARR's tiles over the entries of a ragged streaming call (launch_front_generic_stream_packed) -- a row's entry (its chunk, its
 // row within the chunk, its pool row) comes from the device tables (StftStreamPackedArgs), its window as in STREAM.
-// (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs, one FrameStreamPackedArgs, one VarRowsArgs or one
-// StftStreamPackedArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
+// (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs, one FrameStreamPackedArgs, one FrameStreamPackedPcmArgs, one
+// VarRowsArgs or one StftStreamPackedArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
 template <int LOG2C, bool BLU, typename... V>
 __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
 {
     constexpr bool VAR = (std::is_same_v<V, VarlenArgs> || ...);
     constexpr bool STREAM = (std::is_same_v<V, StreamArgs> || ...);
-    constexpr bool FSP = (std::is_same_v<V, FrameStreamPackedArgs> || ...);
+    constexpr bool FSPI = (std::is_same_v<V, FrameStreamPackedPcmArgs> || ...);
+    constexpr bool FSP = FSPI || (std::is_same_v<V, FrameStreamPackedArgs> || ...);
     constexpr bool FSTREAM = FSP || (std::is_same_v<V, FrameStreamArgs> || ...);
     constexpr bool VARR = (std::is_same_v<V, VarRowsArgs> || ...);
     constexpr bool SPR = (std::is_same_v<V, StftStreamPackedArgs> || ...);
@@ -272,7 +277,9 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     [[maybe_unused]] const VarlenArgs *va = pack_arg<VarlenArgs>(vargs...);
     [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(vargs...);
     [[maybe_unused]] const FrameStreamArgs *fa = pack_arg<FrameStreamArgs>(vargs...);
+    [[maybe_unused]] const FrameStreamPackedPcmArgs *fpi = pack_arg<FrameStreamPackedPcmArgs>(vargs...);
     [[maybe_unused]] const FrameStreamPackedArgs *fp = pack_arg<FrameStreamPackedArgs>(vargs...);
+    if constexpr (FSPI) fp = &fpi->e;
     using G = Geo<LOG2C>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
@@ -306,6 +313,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
             const unsigned long long gf = g * G::FPB + slot;
             bool active = gf < total;
             const float *xc;
+            [[maybe_unused]] const int16_t *xi = nullptr;  // FSPI: the entry's chunk
             unsigned t;
             unsigned n_samples = a.n_samples;
             int frame_mode = a.frame_mode;
@@ -327,7 +335,12 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 const StreamEntry en = stream_entry(*fp, active ? offset_find(fp->ro, fp->n_active, g32) : 0u);
                 active = active && en.ok && static_cast<long long>(gf) >= en.r0 && static_cast<long long>(gf) - en.r0 < static_cast<long long>(en.R);
                 t = active ? static_cast<unsigned>(static_cast<long long>(gf) - en.r0) : 0u;
-                xc = a.x + (active ? en.s0 : 0ll);
+                if constexpr (FSPI) {
+                    xc = nullptr;
+                    xi = fpi->x + (active ? en.s0 : 0ll);
+                } else {
+                    xc = a.x + (active ? en.s0 : 0ll);
+                }
                 if (active && fp->state_len) srow = fp->pool + static_cast<unsigned long long>(en.slot) * fp->state_len + fp->state_len;
             } else {
                 const unsigned gf32 = static_cast<unsigned>(gf);  // launch_one rejects batches with >= 2^32 frames
@@ -350,10 +363,15 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                         if constexpr (FSP) lead = fp->lead;
                         else lead = fa->lead;
                         const long long p = static_cast<long long>(t) * a.step - lead + i;
-                        val = p < 0 ? srow[p] : xc[p];
+                        // the chunk's sample k (FSPI: int16 times the power-of-two scale, exact)
+                        auto chunk = [&](long long k) -> float {
+                            if constexpr (FSPI) return pcm_sample(xi, k, fpi->scale);
+                            else return xc[k];
+                        };
+                        val = p < 0 ? srow[p] : chunk(p);
                         if (a.preemph != 0.0f) {
                             const long long q = p - static_cast<long long>(a.preemph_shift);
-                            val -= a.preemph * (q < 0 ? srow[q] : xc[q]);
+                            val -= a.preemph * (q < 0 ? srow[q] : chunk(q));
                         }
                         if (a.window) val *= a.window[i];
                     }
@@ -660,6 +678,7 @@ constexpr const char *layout_suffix(const VarRowsArgs &) { return "_varrows"; }
 constexpr const char *layout_suffix(const StreamArgs &) { return "_stream"; }
 constexpr const char *layout_suffix(const FrameStreamArgs &) { return "_fstream"; }
 constexpr const char *layout_suffix(const FrameStreamPackedArgs &) { return "_fstreamp"; }
+constexpr const char *layout_suffix(const FrameStreamPackedPcmArgs &) { return "_fstreampi"; }
 constexpr const char *layout_suffix(const StftStreamPackedArgs &) { return "_streamp"; }
 
 // the packed-rows builds: the tile's row table (32 offsets + 32 row counts, 8-byte aligned)
@@ -668,6 +687,7 @@ template <typename... V>
 constexpr size_t layout_lds(const V &...) { return 0; }
 constexpr size_t layout_lds(const VarRowsArgs &) { return kRowTableBytes; }
 constexpr size_t layout_lds(const StftStreamPackedArgs &) { return kRowTableBytes; }
+constexpr size_t layout_lds(const FrameStreamPackedPcmArgs &) { return 0; }
 
 // Workgroup visits of a call at `fpb` frames per visit.  0: nothing to launch; kTooManyRows: the kernel's 32-bit row index does not
 // reach the last row.
@@ -694,6 +714,10 @@ inline unsigned long long layout_work(const FrontArgs &, unsigned long long fpb,
 inline unsigned long long layout_work(const FrontArgs &, unsigned long long fpb, const FrameStreamPackedArgs &s)
 {
     return at_least_one((s.total_rows + fpb - 1) / fpb);
+}
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const FrameStreamPackedPcmArgs &s)
+{
+    return layout_work(a, fpb, s.e);
 }
 inline unsigned long long layout_work(const FrontArgs &, unsigned long long, const VarRowsArgs &v) { return at_least_one((v.total_rows + 31) / 32); }
 inline unsigned long long layout_work(const FrontArgs &, unsigned long long, const StftStreamPackedArgs &s)
@@ -816,6 +840,31 @@ __global__ __launch_bounds__(256) void ss_stream_advance_packed(const FrameStrea
     }
 }
 
+// ss_stream_advance_packed behind a PCM call (launch_stream_advance_packed, FrameStreamPackedPcmArgs): the chunk's samples are
+// (float)int16 * scale, so a pool row ends up holding exactly the floats the float call would have stored.  Same blocks, same
+// read-all-then-write discipline; plain vector loads and stores.
+__global__ __launch_bounds__(256) void ss_stream_advance_packed_i16(const FrameStreamPackedPcmArgs vp)
+{
+    const FrameStreamPackedArgs &v = vp.e;
+    const unsigned S = v.state_len;
+    for (unsigned e = blockIdx.x; e < v.n_active; e += gridDim.x) {
+        const StreamEntry en = stream_entry(v, e);
+        if (!en.ok || en.n == 0u) continue;
+        float *st = v.pool + static_cast<unsigned long long>(en.slot) * S;
+        const int16_t *xc = vp.x + en.s0;
+        for (unsigned i0 = 0; i0 < S; i0 += 256) {
+            const unsigned i = i0 + threadIdx.x;
+            float val = 0.0f;
+            if (i < S) {
+                const unsigned long long k = static_cast<unsigned long long>(i) + en.n;  // index into old row ++ chunk
+                val = k < S ? st[k] : pcm_sample(xc, static_cast<long long>(k - S), vp.scale);  // (k - S < n: i < S)
+            }
+            __syncthreads();
+            if (i < S) st[i] = val;
+        }
+    }
+}
+
 __global__ void ss_preemphasis_kernel(const float *__restrict__ x, float *__restrict__ y, size_t n, size_t shift, float cof)
 {
     // processing.rs:31-53: y[i] = x[i] - cof * x[(i - shift) mod n]
@@ -895,6 +944,15 @@ hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const Fr
     return dispatch_front(a, log2c, stream, num_cus, info, s);
 }
 
+hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const FrameStreamPackedPcmArgs &s, uint32_t log2c, hipStream_t stream,
+                                                    int num_cus, LaunchInfo *info)
+{
+    if (a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE) return hipErrorInvalidValue;
+    if (!s.x || s.e.n_active == 0 || s.e.step == 0 || (s.e.state_len > 0 && !s.e.pool) || s.e.total_rows >= 0x7fffffffu)
+        return hipErrorInvalidValue;
+    return dispatch_front(a, log2c, stream, num_cus, info, s);
+}
+
 hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
                                               int num_cus, LaunchInfo *info)
 {
@@ -913,6 +971,15 @@ hipError_t launch_stream_advance_packed(const FrameStreamPackedArgs &s, const fl
     if (!s.pool || s.step == 0) return hipErrorInvalidValue;
     const unsigned grid = s.n_active < 65536u ? s.n_active : 65536u;
     hipLaunchKernelGGL(ss_stream_advance_packed, dim3(grid), dim3(256), 0, stream, s, x);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_advance_packed(const FrameStreamPackedPcmArgs &s, hipStream_t stream)
+{
+    if (s.e.n_active == 0 || s.e.state_len == 0) return hipSuccess;
+    if (!s.e.pool || s.e.step == 0 || !s.x) return hipErrorInvalidValue;
+    const unsigned grid = s.e.n_active < 65536u ? s.e.n_active : 65536u;
+    hipLaunchKernelGGL(ss_stream_advance_packed_i16, dim3(grid), dim3(256), 0, stream, s);
     return hipGetLastError();
 }
 

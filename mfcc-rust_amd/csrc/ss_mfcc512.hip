@@ -296,6 +296,57 @@ __device__ __forceinline__ unsigned load_quad_stream_packed(const Fast512Args &a
     return t;
 }
 
+// STRPI builds (ss_mfcc_stream_packed_i16_device): load_quad_stream_packed with the chunks as signed 16-bit PCM
+// (FrameStreamPackedPcmArgs).  The entry lookup is the float loader's; a lane's sample pair is either the float2 of the pool row's
+// tail (p < 0) or one dword of the chunk that holds two int16.  The loader only fetches: the dword stays, as raw bits, in the
+// pair's .x until the quad's turn comes (pcm_pair below, at the top of the iteration that consumes vin[]) -- converting here would
+// wait for the loads right behind pass 1 instead of three quarters of an iteration later.  s0 is the frame's first sample relative
+// to its chunk (pair e is PCM where s0 + 2 (j + 16 e) >= 0); a lane that loads nothing gets kNoPcm: no pair converts, the zeros stay.
+// Every so[i] is a multiple of the even step and the launcher takes a 4-byte aligned buffer only, so a pair is a whole dword; the
+// load itself is declared 2-byte aligned, which also covers a chunk at an odd sample (possible only behind an entry that is not
+// whole hops, which the entry pass reports).
+constexpr int kNoPcm = -(1 << 30);
+template <int NE>
+__device__ __forceinline__ unsigned load_quad_stream_packed_pcm(const Fast512Args &a, const FrameStreamPackedPcmArgs &sp, unsigned quad,
+                                                                unsigned total, int f, int j, float2 (&vin)[NE], int &ok, int &s0_out)
+{
+    const FrameStreamPackedArgs &s = sp.e;
+    const unsigned q4 = quad * 4;                                              // uniform
+    const unsigned g = q4 + min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last row redo it
+    const unsigned c = offset_seek(s.ro, s.n_active, offset_find(s.ro, s.n_active, q4), g);
+    const StreamEntry en = stream_entry(s, c);
+    const long long tl = static_cast<long long>(g) - en.r0;
+    ok = en.ok && g < total && tl >= 0 && tl < static_cast<long long>(en.R);
+    const unsigned t = ok ? static_cast<unsigned>(tl) : 0u;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) vin[e] = make_float2(0.f, 0.f);
+    s0_out = kNoPcm;
+    if (ok) {
+        const int16_t *xc = sp.x + en.s0;
+        const float *sr = s.pool + static_cast<unsigned long long>(en.slot) * s.state_len + s.state_len;  // sample p < 0 is sr[p]
+        const int s0 = static_cast<int>(t * a.step) - s.lead;  // (t * step < n_i < 2^31; the frame ends inside the chunk)
+        s0_out = s0;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int p = s0 + 2 * (j + 16 * e);
+            if (p < 0) {
+                vin[e] = *reinterpret_cast<const float2 *>(sr + p);
+            } else {
+                int w;
+                __builtin_memcpy(&w, xc + p, sizeof w);
+                vin[e].x = __int_as_float(w);
+            }
+        }
+    }
+    return t;
+}
+// the two samples of a PCM dword: sign-extended, converted, times the power-of-two scale (exact: the bits the float loader finds in
+// the converted buffer)
+__device__ __forceinline__ float2 pcm_pair(int w, float scale)
+{
+    return make_float2(static_cast<float>(static_cast<int16_t>(w)) * scale, static_cast<float>(w >> 16) * scale);
+}
+
 // Contract framing only: where this lane's frame of `quad` starts (frame t of its clip begins at sample t * step), and t.
 // `quad` is uniform: the clip / frame split of the quad's first frame, the clip's address and the frame's offset in it are scalar
 // work, and what a lane adds is a 32-bit byte offset (its frame within the quad, its sample pair, one conditional step into the
@@ -431,6 +482,8 @@ __device__ __forceinline__ float mel_slot_loop(const float4 *w4, const float *p,
 // clip's first frame is never taken (a stream has no first frame).
 // STRP builds (ss_mfcc_stream_packed_device): a trailing FrameStreamPackedArgs; the quad range covers the packed output rows of a
 // ragged streaming call (load_quad_stream_packed), otherwise as STRM.
+// STRPI builds (ss_mfcc_stream_packed_i16_device): a trailing FrameStreamPackedPcmArgs; STRP with its entry block and the chunks read
+// as 16-bit PCM (load_quad_stream_packed_pcm fetches, pcm_pair converts where vin[] is consumed) -- from v[] on the code is STRP's.
 template <int NE, bool EXACT, bool POW2, int WAVES, bool BANK421, int NQ, int RES = 0, int OUTK = 0, int FRONT = 0, bool FULLP = false,
           bool CENTER = false, bool MULTI = false, bool VAR = false, typename... SP>
 __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_in, const std::conditional_t<VAR, VarlenArgs, MultiArg<MULTI>> mt,
@@ -438,8 +491,11 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
 {
     constexpr bool STRM = (std::is_same_v<SP, FrameStreamArgs> || ...);
     [[maybe_unused]] const FrameStreamArgs *fs = pack_arg<FrameStreamArgs>(sp...);
-    constexpr bool STRP = (std::is_same_v<SP, FrameStreamPackedArgs> || ...);
+    constexpr bool STRPI = (std::is_same_v<SP, FrameStreamPackedPcmArgs> || ...);
+    [[maybe_unused]] const FrameStreamPackedPcmArgs *fpi = pack_arg<FrameStreamPackedPcmArgs>(sp...);
+    constexpr bool STRP = STRPI || (std::is_same_v<SP, FrameStreamPackedArgs> || ...);
     [[maybe_unused]] const FrameStreamPackedArgs *fp = pack_arg<FrameStreamPackedArgs>(sp...);
+    if constexpr (STRPI) fp = &fpi->e;
     // Everything in front of a wave's first sample loads is start-up latency of the launch (nothing can be computed before
     // the samples are here), so the kernel arguments that lead to those loads are fetched by ONE batch of scalar loads at the
     // very top (pinned: left alone, the compiler fetches them where they are first used -- three dependent scalar-memory
@@ -523,12 +579,15 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     Fast512Args an = a_in;   // ... and the argument block with that batch's input
     [[maybe_unused]] unsigned cursor = 0;  // VAR: the wave's clip cursor ...
     [[maybe_unused]] VarFrame vnext{};     // ... and the clip data of the frame whose samples are in vin (STRP: its ok alone)
+    [[maybe_unused]] int s0_next = kNoPcm;  // STRPI: that frame's first sample relative to its chunk (which pairs of vin are raw PCM)
     if constexpr (VAR) {
         const char *p = var_src(a, mt, min(quad, q_hi - 1), total, f, cursor, t_next, vnext);
 #pragma unroll
         for (int e = 0; e < NE; ++e) vin[e] = *reinterpret_cast<const float2 *>(p + 8 * (j + 16 * e));
     } else if constexpr (STRM) {
         t_next = load_quad_stream<NE>(a, *fs, min(quad, q_hi - 1), total, f, j, vin);
+    } else if constexpr (STRPI) {
+        t_next = load_quad_stream_packed_pcm<NE>(a, *fpi, min(quad, q_hi - 1), total, f, j, vin, vnext.ok, s0_next);
     } else if constexpr (STRP) {
         t_next = load_quad_stream_packed<NE>(a, *fp, min(quad, q_hi - 1), total, f, j, vin, vnext.ok);
     } else if constexpr (MULTI) {
@@ -654,6 +713,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         if (!PREFETCH && n_done > 1) t_next = load_quad<NE, EXACT, PRE, CENTER>(a, quad, total, f, j, vin, pin);
         const unsigned t_cur = t_next;
         [[maybe_unused]] const VarFrame vcur = vnext;
+        [[maybe_unused]] const int s0_cur = s0_next;
 #if SS_PROF2
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -671,6 +731,9 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             float2 s = e < NE ? vin[e] : make_float2(0.f, 0.f);  // zero pad, processing.rs:147-156
+            if constexpr (STRPI) {
+                if (e < NE && s0_cur + 2 * (j + 16 * e) >= 0) s = pcm_pair(__float_as_int(s.x), fpi->scale);
+            }
             if (PRE && e < NE) s = make_float2(fmaf(-a.preemph, pin[e].x, s.x), fmaf(-a.preemph, pin[e].y, s.y));
             if (WIN && e < NE) {
                 const float2 w = s_win[j + 16 * e];
@@ -717,6 +780,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         if constexpr (STRM) {
             // (the whole quad's loads as one burst behind pass 1: the edge branch's address selects do not split into the twiddle steps)
             if (next < q_hi) t_next = load_quad_stream<NE>(a, *fs, next, total, f, j, vin);
+        } else if constexpr (STRPI) {
+            if (next < q_hi) t_next = load_quad_stream_packed_pcm<NE>(a, *fpi, next, total, f, j, vin, vnext.ok, s0_next);
         } else if constexpr (STRP) {
             if (next < q_hi) t_next = load_quad_stream_packed<NE>(a, *fp, next, total, f, j, vin, vnext.ok);
         } else if (!SPREAD && PREFETCH && next < q_hi && !(SS_ABLATE & 16)) {
@@ -1301,8 +1366,11 @@ hipError_t launch_mfcc_c256_stream(const Fast512Args &a_in, const FrameStreamArg
     return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, FrameStreamArgs>, "ss_mfcc_c256s<10,exact,bank421,mfe>");
 }
 
-hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a_in, const FrameStreamPackedArgs &s, hipStream_t stream, int num_cus,
-                                          LaunchInfo *info)
+// the ragged streaming launch for either chunk format: SPT = FrameStreamPackedArgs (float chunks) or FrameStreamPackedPcmArgs (16-bit
+// PCM); s = its entry block
+template <typename SPT>
+static hipError_t launch_stream_packed_w12(const Fast512Args &a_in, const SPT &sp, const FrameStreamPackedArgs &s, const char *mfcc_name,
+                                           const char *mfe_name, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
     constexpr int WAVES = 12;
     Fast512Args a = a_in;
@@ -1334,15 +1402,28 @@ hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a_in, const FrameSt
             if (e != hipSuccess) return e;
         }
         if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{}, s);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{}, sp);
         return hipGetLastError();
     };
     // the dense streaming builds' template arguments with the packed argument pack: the same arithmetic per frame, bit for bit
-    if (mfcc)
-        return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, false, FrameStreamPackedArgs>,
-                  "ss_mfcc_c256sp<10,exact,bank421,sym>");
-    return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, FrameStreamPackedArgs>,
-              "ss_mfcc_c256sp<10,exact,bank421,mfe>");
+    if (mfcc) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, false, SPT>, mfcc_name);
+    return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, SPT>, mfe_name);
+}
+
+hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a, const FrameStreamPackedArgs &s, hipStream_t stream, int num_cus,
+                                          LaunchInfo *info)
+{
+    return launch_stream_packed_w12(a, s, s, "ss_mfcc_c256sp<10,exact,bank421,sym>", "ss_mfcc_c256sp<10,exact,bank421,mfe>", stream, num_cus,
+                                    info);
+}
+
+hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a, const FrameStreamPackedPcmArgs &s, hipStream_t stream, int num_cus,
+                                          LaunchInfo *info)
+{
+    // a sample pair is one dword of the buffer
+    if (!s.x || (reinterpret_cast<uintptr_t>(s.x) & 3u)) return hipErrorInvalidValue;
+    return launch_stream_packed_w12(a, s, s.e, "ss_mfcc_c256spi<10,exact,bank421,sym>", "ss_mfcc_c256spi<10,exact,bank421,mfe>", stream,
+                                    num_cus, info);
 }
 
 bool mfcc_c256_has_mfe(const Fast512Args &a)

@@ -81,6 +81,16 @@ extern "C" {
                             stream: *mut c_void) -> c_int;
     fn ss_mfcc_batches_device(cfg: *const SsConfig, n_batches: usize, d_x: *const *const f32, batch: *const usize, n: usize, ld: usize,
                               d_out: *const *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_mfcc_stream_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_active: usize, d_sample_offsets: *const i64,
+                                        d_row_offsets: *const i64, total_rows: usize, d_slots: *const i32, pool_streams: usize,
+                                        scale: f32, norm_frames: u32, d_pool: *mut f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_mfe_stream_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_active: usize, d_sample_offsets: *const i64,
+                                       d_row_offsets: *const i64, total_rows: usize, d_slots: *const i32, pool_streams: usize,
+                                       scale: f32, d_pool: *mut f32, d_feat: *mut f32, d_energy: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_mfcc_stream_packed_i16(cfg: *const SsConfig, x: *const i16, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                                 pool_streams: usize, scale: f32, norm_frames: u32, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_mfe_stream_packed_i16(cfg: *const SsConfig, x: *const i16, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                                pool_streams: usize, scale: f32, pool: *mut f32, feat: *mut f32, energy: *mut f32) -> c_int;
     fn ss_preemphasis(x: *const f32, n: usize, shift: c_long, cof: f32, y: *mut f32) -> c_int;
     fn ss_frame_sizes(p: *const SsParams, frame_len: *mut usize, frame_step: *mut usize) -> c_int;
     fn ss_stft(cfg: *const SsConfig, x: *const f32, channels: usize, n: usize, out: *mut f32) -> c_int;
@@ -380,6 +390,53 @@ pub unsafe fn mfcc_batches_device(cfg: &SpeechConfig, d_x: &[*const f32], batch:
         return Err(Error { status: SS_ERR_ARG, detail: "d_x, batch and d_out must have one entry per batch".to_string() });
     }
     check(ss_mfcc_batches_device(cfg.raw(), batch.len(), d_x.as_ptr(), batch.as_ptr(), n, ld, d_out.as_ptr(), stream))
+}
+
+/// Ragged streaming MFCC over a pool of stream states, fed signed 16-bit PCM (`ss_mfcc_stream_packed_i16_device`): entry `i` is
+/// the chunk `d_x[so[i]..so[i + 1]]` (whole hops) of the stream whose state is row `d_slots[i]` of the `[pool_streams x S]` float
+/// pool; stream sample = `pcm as f32 * scale`, `scale` a power of two in `[2^-64, 2^64]`.  Two asynchronous launches on `stream`.
+/// # Safety
+/// Every pointer is a device allocation of the size the header states, on the device the config was created on; `d_x` is 4-byte
+/// aligned.
+pub unsafe fn mfcc_stream_packed_i16_device(cfg: &SpeechConfig, d_x: *const i16, n_active: usize, d_sample_offsets: *const i64,
+                                            d_row_offsets: *const i64, total_rows: usize, d_slots: *const i32, pool_streams: usize,
+                                            scale: f32, norm_frames: u32, d_pool: *mut f32, d_out: *mut f32, stream: *mut c_void)
+                                            -> Result<(), Error> {
+    check(ss_mfcc_stream_packed_i16_device(cfg.raw(), d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams,
+                                           scale, norm_frames, d_pool, d_out, stream))
+}
+
+/// The mfe form of `mfcc_stream_packed_i16_device`: `d_feat` `[total_rows x num_filters]`, `d_energy` `[total_rows]`.
+/// # Safety
+/// As `mfcc_stream_packed_i16_device`.
+pub unsafe fn mfe_stream_packed_i16_device(cfg: &SpeechConfig, d_x: *const i16, n_active: usize, d_sample_offsets: *const i64,
+                                           d_row_offsets: *const i64, total_rows: usize, d_slots: *const i32, pool_streams: usize,
+                                           scale: f32, d_pool: *mut f32, d_feat: *mut f32, d_energy: *mut f32, stream: *mut c_void)
+                                           -> Result<(), Error> {
+    check(ss_mfe_stream_packed_i16_device(cfg.raw(), d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams,
+                                          scale, d_pool, d_feat, d_energy, stream))
+}
+
+/// Host-pointer form of the PCM pool call: `x` the packed int16 chunks, `sample_offsets` `n_active + 1` offsets in samples, `slots`
+/// the pool row of each entry, `pool` the `[pool_streams x S]` float states (updated in place), `out` `[rows x num_cepstral]` with
+/// `rows = sample_offsets[n_active] / hop`.  Synchronous; the tables are checked before anything touches the device.
+pub fn try_mfcc_stream_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64], slots: &[i32], pool_streams: usize, scale: f32,
+                                  norm_frames: u32, pool: &mut [f32], out: &mut [f32]) -> Result<(), Error> {
+    if sample_offsets.len() != slots.len() + 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have one entry more than slots".to_string() });
+    }
+    check(unsafe { ss_mfcc_stream_packed_i16(cfg.raw(), x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams,
+                                             scale, norm_frames, pool.as_mut_ptr(), out.as_mut_ptr()) })
+}
+
+/// The mfe form of `try_mfcc_stream_packed_i16`: `feat` `[rows x num_filters]`, `energy` `[rows]`.
+pub fn try_mfe_stream_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64], slots: &[i32], pool_streams: usize, scale: f32,
+                                 pool: &mut [f32], feat: &mut [f32], energy: &mut [f32]) -> Result<(), Error> {
+    if sample_offsets.len() != slots.len() + 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have one entry more than slots".to_string() });
+    }
+    check(unsafe { ss_mfe_stream_packed_i16(cfg.raw(), x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams,
+                                            scale, pool.as_mut_ptr(), feat.as_mut_ptr(), energy.as_mut_ptr()) })
 }
 
 /// functions.rs:86-123: `[channels, samples]` -> `Array3<Complex32>` `[channels, rows, freq_size]`

@@ -138,6 +138,36 @@ def _require_f32(signal, ndims: tuple[int, ...], what: str):
     return arr
 
 
+def _require_i16(signal, what: str):
+    """The PCM forms (``pcm_scale=``) take 1-D int16 only: no silent casts."""
+    if _is_torch(signal):
+        import torch
+
+        if signal.dtype != torch.int16:
+            raise TypeError(f"{what}: with pcm_scale the signal must be int16, got {signal.dtype}")
+        if signal.dim() != 1:
+            raise ValueError(f"{what}: Input signal must be 1d")
+        if not signal.is_cuda:
+            signal = signal.detach().numpy()
+        return signal
+    arr = np.asarray(signal)
+    if arr.dtype != np.int16:
+        raise TypeError(f"{what}: with pcm_scale the signal must be int16, got {arr.dtype}")
+    if arr.ndim != 1:
+        raise ValueError(f"{what}: Input signal must be 1d")
+    return arr
+
+
+def _check_pcm_scale(pcm_scale, what: str) -> float:
+    """``pcm_scale`` of the PCM forms: a power of two in [2**-64, 2**64] (the product with an int16 is then exact)."""
+    import math
+
+    v = float(pcm_scale)
+    if not (math.isfinite(v) and v > 0.0 and math.frexp(v)[0] == 0.5 and -64 <= math.frexp(v)[1] - 1 <= 64):
+        raise ValueError(f"{what}: pcm_scale must be a power of two in [2**-64, 2**64], got {pcm_scale!r}")
+    return v
+
+
 def _stream_ptr():
     import torch
 
@@ -942,19 +972,20 @@ class _StreamPoolMixin:
         """Zero the state of every stream of the pool, or of the given slots (fresh streams)."""
         super().reset(slots)
 
-    def _prepare_pool(self, chunks, slots, lengths):
+    def _prepare_pool(self, chunks, slots, lengths, pcm=False):
         what = self._what
+        require = (lambda c: _require_i16(c, what)) if pcm else (lambda c: _require_f32(c, (1,), what))
         if lengths is None:
             if _is_torch(chunks) or isinstance(chunks, np.ndarray):
                 raise TypeError(f"{what}: chunks must be a list of 1-D arrays (or pass a packed buffer with lengths=)")
-            parts = [_require_f32(c, (1,), what) for c in chunks]
+            parts = [require(c) for c in chunks]
             lens = [int(c.shape[0]) for c in parts]
             kinds = {_is_torch(c) for c in parts}
             if len(kinds) > 1:
                 raise TypeError(f"{what}: chunks must be all numpy arrays or all tensors on one device")
             packed = None
         else:
-            packed = _require_f32(chunks, (1,), what)
+            packed = require(chunks)
             parts = None
             lens = [int(v) for v in lengths]
             if any(v < 0 for v in lens) or sum(lens) != int(packed.shape[0]):
@@ -983,11 +1014,11 @@ class _StreamPoolMixin:
             if packed is None:
                 if any(c.device != dev for c in parts):
                     raise TypeError(f"{what}: chunks must be all numpy arrays or all tensors on one device")
-                packed = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device=dev)
+                packed = torch.cat(parts) if parts else torch.empty(0, dtype=torch.int16 if pcm else torch.float32, device=dev)
             where = ("cuda", dev.index)
         else:
             if packed is None:
-                packed = np.concatenate(parts) if parts else np.empty(0, dtype=np.float32)
+                packed = np.concatenate(parts) if parts else np.empty(0, dtype=np.int16 if pcm else np.float32)
             where = ("host",)
         if self._where is not None and where != self._where:
             raise ValueError(f"{what}: the pool lives on {self._where}, these chunks on {where}")
@@ -1014,6 +1045,8 @@ class _StreamPoolMixin:
             import torch
 
             x = packed.contiguous()
+            if x.data_ptr() & 3:  # (int16 only: the device form reads sample pairs as dwords)
+                x = x.clone()
             with torch.cuda.device(x.device):
                 d_so, d_ro, d_sl = (torch.from_numpy(t).to(x.device) for t in (so, ro, sl))
                 st = self._state.data_ptr() if self.state_len else None
@@ -1034,7 +1067,20 @@ class _FrameStreamPoolBase(_StreamPoolMixin, _FrameStreamBase):
     list of 1-D float32 arrays / tensors, or one packed 1-D buffer plus ``lengths=``, and ``slots`` the pool row of each chunk
     (distinct).  Per stream the rows and the carried state are those of the dense class on that stream alone.  numpy in -> the
     host-pointer call, ROCm tensors in -> the device call on the current stream.  See ``ss_mfcc_stream_packed`` in
-    ``include/speechsauce_amd.h``."""
+    ``include/speechsauce_amd.h``.
+
+    ``pool(chunks, slots, pcm_scale=2**-15)`` takes the chunks (or the packed buffer) as signed 16-bit PCM instead -- int16
+    arrays / tensors only -- and converts on load: stream sample = ``int16 * pcm_scale``, ``pcm_scale`` a power of two in
+    ``[2**-64, 2**64]``.  The rows and the state are bit for bit those of the float call on ``chunk.astype(float32) * pcm_scale``;
+    the state stays float32, so a stream may be fed PCM on one call and floats on the next (``ss_mfcc_stream_packed_i16``)."""
+
+    def _prepare_pcm(self, chunks, slots, lengths, pcm_scale):
+        """``_prepare_pool`` of either chunk format, and what ``_call_pool`` needs for it: the suffix of the entry points' names
+        and the arguments between ``pool_streams`` and the state."""
+        if pcm_scale is None:
+            return self._prepare_pool(chunks, slots, lengths), "", []
+        scale = _check_pcm_scale(pcm_scale, self._what)
+        return self._prepare_pool(chunks, slots, lengths, pcm=True), "_i16", [scale]
 
 
 class MfccStreamPool(_FrameStreamPoolBase):
@@ -1055,8 +1101,8 @@ class MfccStreamPool(_FrameStreamPoolBase):
         else:
             self.norm_frames = int(norm_frames) if norm_frames is not None else 1
 
-    def __call__(self, chunks, slots, lengths=None):
-        packed, so, ro, sl, config = self._prepare_pool(chunks, slots, lengths)
+    def __call__(self, chunks, slots, lengths=None, pcm_scale=None):
+        (packed, so, ro, sl, config), i16, scale = self._prepare_pcm(chunks, slots, lengths, pcm_scale)
         Cc, R = config.params.num_cepstral, int(ro[-1])
         if _is_torch(packed):
             import torch
@@ -1064,7 +1110,8 @@ class MfccStreamPool(_FrameStreamPoolBase):
             out = torch.empty((R, Cc), dtype=torch.float32, device=packed.device)
         else:
             out = np.empty((R, Cc), dtype=np.float32)
-        self._call_pool(packed, so, ro, sl, config, [out], "ss_mfcc_stream_packed_device", "ss_mfcc_stream_packed", [self.norm_frames])
+        self._call_pool(packed, so, ro, sl, config, [out], f"ss_mfcc_stream_packed{i16}_device", f"ss_mfcc_stream_packed{i16}",
+                        scale + [self.norm_frames])
         return out, ro
 
 
@@ -1079,8 +1126,8 @@ class MfeStreamPool(_FrameStreamPoolBase):
         super().__init__(pool_streams, sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
                          low_frequency, high_frequency, True, switches)
 
-    def __call__(self, chunks, slots, lengths=None):
-        packed, so, ro, sl, config = self._prepare_pool(chunks, slots, lengths)
+    def __call__(self, chunks, slots, lengths=None, pcm_scale=None):
+        (packed, so, ro, sl, config), i16, scale = self._prepare_pcm(chunks, slots, lengths, pcm_scale)
         M, R = config.params.num_filters, int(ro[-1])
         if _is_torch(packed):
             import torch
@@ -1090,7 +1137,7 @@ class MfeStreamPool(_FrameStreamPoolBase):
         else:
             feat = np.empty((R, M), dtype=np.float32)
             energy = np.empty((R,), dtype=np.float32)
-        self._call_pool(packed, so, ro, sl, config, [feat, energy], "ss_mfe_stream_packed_device", "ss_mfe_stream_packed", [])
+        self._call_pool(packed, so, ro, sl, config, [feat, energy], f"ss_mfe_stream_packed{i16}_device", f"ss_mfe_stream_packed{i16}", scale)
         return feat, energy, ro
 
 

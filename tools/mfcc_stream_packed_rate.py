@@ -1,7 +1,7 @@
 """Rows/s and µs per call of the ragged streaming MFCC over a pool of stream states (ss_mfcc_stream_packed_device) beside what a
 caller could do without it.
 
-    python tools/mfcc_stream_packed_rate.py [--pool 4096] [--active 1024] [--max-hops 4] [--reps 200] [--ring-mb 320]
+    python tools/mfcc_stream_packed_rate.py [--pool 4096] [--active 1024] [--max-hops 4] [--reps 200] [--ring-mb 320] [--pcm16]
 
 Workload: 16 kHz MFCC at the default shape (512 points, 320-sample frames, 160-sample hop, 40 filters); a pool of `--pool` stream
 states of which `--active` deliver audio in a call, in random slot order, each 1 .. `--max-hops` hops (uniform).  Measured with HIP
@@ -16,6 +16,12 @@ does not find its samples in the caches an earlier call left them in.
   bucketed      baseline (b): what a caller does with the dense call alone -- per hop count R an index_select of the chunks and of
                 the state rows into dense blocks, one dense call, an index_copy_ of the state rows back.  The bucket index lists are
                 built outside the timed loop (the host-side bucketing is not charged to the baseline).
+With --pcm16 the same ticks are fed as signed 16-bit PCM instead (ss_mfcc_stream_packed_i16_device, scale 2^-15), three legs,
+each measured twice (the spread between the two runs is the resolution of the comparison):
+  pcm           the PCM ragged call on the int16 chunks
+  float         the float ragged call on the same ticks, converted outside the timed loop
+  convert_float what a caller does without the PCM call: pcm.to(torch.float32).mul_(scale) in front of the float call
+The float ring alone is sized to --ring-mb (the PCM ring is half of it in bytes: still the same ticks).
 Prints one JSON line.  Measuring only: not collected by pytest, not part of bench.py.
 """
 import argparse
@@ -37,6 +43,7 @@ def main():
     ap.add_argument("--max-hops", type=int, default=4)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--ring-mb", type=int, default=320)
+    ap.add_argument("--pcm16", action="store_true")
     args = ap.parse_args()
 
     import numpy as np
@@ -95,6 +102,46 @@ def main():
 
     res = {"pool": P, "active": N, "max_hops": H, "ring": n_ring, "device": torch.cuda.get_device_name()}
     out = torch.empty((cap, NCEP), device="cuda")
+
+    if args.pcm16:
+        scale = 2.0 ** -15
+        for t in ticks:
+            t["pcm"] = torch.randint(-32768, 32768, (t["x"].numel(),), device="cuda", dtype=torch.int32).to(torch.int16)
+            t["x"] = t["pcm"].to(torch.float32).mul_(scale)
+            del t["dense"], t["buckets"]
+        cur = torch.cuda.current_stream().cuda_stream
+
+        def pcm():
+            t = nxt()
+            _lib.check(lib.ss_mfcc_stream_packed_i16_device(cfg.handle, t["pcm"].data_ptr(), N, t["so"].data_ptr(), t["ro"].data_ptr(), t["rows"],
+                                                            t["slots"].data_ptr(), P, scale, 100, pool.data_ptr(), out.data_ptr(), C.c_void_p(cur)))
+
+        def flt_on(x, t):
+            _lib.check(lib.ss_mfcc_stream_packed_device(cfg.handle, x.data_ptr(), N, t["so"].data_ptr(), t["ro"].data_ptr(), t["rows"],
+                                                        t["slots"].data_ptr(), P, 100, pool.data_ptr(), out.data_ptr(), C.c_void_p(cur)))
+
+        def flt():
+            t = nxt()
+            flt_on(t["x"], t)
+
+        def convert_float():
+            t = nxt()
+            flt_on(t["pcm"].to(torch.float32).mul_(scale), t)
+
+        for leg, fn in (("pcm", pcm), ("float", flt), ("convert_float", convert_float)):
+            res[leg] = {"us_per_call": [], "rows_per_s": []}
+        for _ in range(2):
+            for leg, fn in (("pcm", pcm), ("float", flt), ("convert_float", convert_float)):
+                sec, rows, k = timed(fn, args.reps)
+                res[leg]["us_per_call"].append(sec * 1e6)
+                res[leg]["rows_per_s"].append(rows / sec)
+                res[leg]["rows_per_call"] = rows
+                res[leg]["kernel"] = k
+        best = {leg: min(res[leg]["us_per_call"]) for leg in ("pcm", "float", "convert_float")}
+        res["pcm_over_convert_float_time"] = best["pcm"] / best["convert_float"]
+        res["pcm_over_float_time"] = best["pcm"] / best["float"]
+        print(json.dumps(res))
+        return
 
     def ragged_on(x, so, ro, slots, total_rows):
         _lib.check(lib.ss_mfcc_stream_packed_device(cfg.handle, x.data_ptr(), N, so.data_ptr(), ro.data_ptr(), total_rows, slots.data_ptr(),
