@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SS_ABI_VERSION 7 /* 7: the ragged streaming calls over a pool of stream states (ss_frame_stream_packed_row_offsets, ss_mfcc_stream_packed*, ss_mfe_stream_packed*; ss_stream_packed_row_offsets, ss_mel_spectrogram_stream_packed*, ss_stft_stream_packed*), ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region, the packed post-processing calls (ss_cmvn_packed*, ss_cmvnw_packed*, ss_power_to_db_packed*, ss_lmfe_packed*); 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
+#define SS_ABI_VERSION 7 /* 7: the ragged streaming calls over a pool of stream states (ss_frame_stream_packed_row_offsets, ss_mfcc_stream_packed*, ss_mfe_stream_packed*; ss_stream_packed_row_offsets, ss_mel_spectrogram_stream_packed*, ss_stft_stream_packed*), the one-shot calls' 16-bit PCM forms (ss_mfcc_batch_i16*, ss_mfe_batch_i16*, ss_mfcc_packed_i16*, ss_mfe_packed_i16*), ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region, the packed post-processing calls (ss_cmvn_packed*, ss_cmvnw_packed*, ss_power_to_db_packed*, ss_lmfe_packed*); 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
 
 typedef enum ss_status {
     SS_OK = 0,
@@ -242,6 +242,40 @@ int ss_packed_frame_offsets(const ss_params *p, size_t n_clips, const int64_t *s
 /* host pointers (H2D, one device call, D2H); sample_offsets is a host array.  out: [fo[n_clips] x num_cepstral] */
 int ss_mfcc_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out);
 int ss_mfe_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *feat, float *energy);
+
+/* ---- the one-shot MFCC / mfe calls fed signed 16-bit PCM ----
+ * Speech corpora and decoded WAV files are int16.  These eight entry points are ss_mfcc_batch* / ss_mfe_batch* / ss_mfcc_packed* /
+ * ss_mfe_packed* with the samples as int16 and a scale behind the sample-layout arguments: sample s = (float)pcm * scale, converted
+ * on load.  Everything else is the float forms' contract, word for word -- shapes, errors, empty batches, the packed tables'
+ * containment and the SS_ERR_DEVICE reporting of the packed device forms.  ld and the offsets are in samples, not bytes.
+ *   scale: a power of two in [2^-64, 2^64], otherwise SS_ERR_ARG before anything runs -- 2^-15 for normalised audio, 1.0 for
+ *   integer-valued floats.  With a power of two the product is exact, so fusing it into what follows changes no bit.
+ *   Equivalence: every output (features, energies) is bit for bit what the float form returns on x_f[k] = (float)pcm[k] * scale,
+ *   for every configuration the float form accepts.
+ *   Kernels: the PCM build of the kernel the float call picks, where it has one -- ss_mfcc_c256i<...> (the 512-point kernel's
+ *   contract-framing builds without fused pre-emphasis), ss_mfcc_c256vi<...> (its packed build), ss_front_generic_i16<...> /
+ *   ss_front_generic_varleni<...> (every configuration the generic kernel serves).  The equal-length calls on every other dedicated
+ *   kernel (256 / 1024 / 2048 / 4096 points, the 512-point builds with centred frames, fused pre-emphasis, whole-spectrum banks or
+ *   more than 48 filters) run that kernel behind one conversion launch into a stream-ordered temporary; ss_last_kernel_name() then
+ *   reports the float kernel.  That path allocates and frees in stream order and is not offered for stream capture; the PCM builds
+ *   are single launches and capture like the float calls.
+ *   Alignment: the buffer needs 2-byte alignment only -- an odd ld, an odd base offset and clip offsets of either parity are fine.
+ *   Host forms: the samples cross the link as int16 (half the bytes of the float forms); the 16 MB chunks and the 1 MB small-call
+ *   threshold of the batch forms are in bytes. */
+int ss_mfcc_batch_i16_device(const ss_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale,
+                             float *d_out, void *stream);
+int ss_mfe_batch_i16_device(const ss_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale,
+                            float *d_feat, float *d_energy, void *stream);
+int ss_mfcc_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                              const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream);
+int ss_mfe_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                             const int64_t *d_frame_offsets, size_t total_frames, float *d_feat, float *d_energy, void *stream);
+int ss_mfcc_batch_i16(const ss_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, float *out);
+int ss_mfe_batch_i16(const ss_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, float *feat,
+                     float *energy);
+int ss_mfcc_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out);
+int ss_mfe_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *feat,
+                      float *energy);
 /* device pointers, asynchronous on `stream`, graph-capturable: d_sample_offsets / d_frame_offsets are DEVICE arrays of n_clips + 1
  * entries (fo from ss_packed_frame_offsets, or computed by the caller on the device); total_frames = the rows d_out holds.  The
  * kernel checks the tables against each other: a clip whose rows are not the T_b frames its samples give, or that end past

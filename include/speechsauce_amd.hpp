@@ -335,6 +335,65 @@ inline void mfe_stream_packed_i16(const SpeechConfig &cfg, const std::vector<int
                                    pool.data(), feat.data(), energy.data()));
 }
 
+// The one-shot MFCC / mfe calls fed signed 16-bit PCM (ss_*_batch_i16*, ss_*_packed_i16*): sample = pcm * scale, scale a power of two
+// in [2^-64, 2^64]; bit for bit the float calls on the converted buffer.  ld and the offsets are in samples; 2-byte alignment is
+// enough.  Device forms: raw device pointers and a hipStream_t, asynchronous.  Host forms: the samples cross the link as int16.
+inline void mfcc_batch_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t batch, std::size_t n_samples, std::size_t ld,
+                                  float scale, float *d_out, void *stream)
+{
+    check(ss_mfcc_batch_i16_device(cfg.handle(), d_x, batch, n_samples, ld, scale, d_out, stream));
+}
+
+inline void mfe_batch_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t batch, std::size_t n_samples, std::size_t ld,
+                                 float scale, float *d_feat, float *d_energy, void *stream)
+{
+    check(ss_mfe_batch_i16_device(cfg.handle(), d_x, batch, n_samples, ld, scale, d_feat, d_energy, stream));
+}
+
+inline void mfcc_packed_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t n_clips, const int64_t *d_sample_offsets,
+                                   float scale, const int64_t *d_frame_offsets, std::size_t total_frames, float *d_out, void *stream)
+{
+    check(ss_mfcc_packed_i16_device(cfg.handle(), d_x, n_clips, d_sample_offsets, scale, d_frame_offsets, total_frames, d_out, stream));
+}
+
+inline void mfe_packed_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t n_clips, const int64_t *d_sample_offsets,
+                                  float scale, const int64_t *d_frame_offsets, std::size_t total_frames, float *d_feat, float *d_energy,
+                                  void *stream)
+{
+    check(ss_mfe_packed_i16_device(cfg.handle(), d_x, n_clips, d_sample_offsets, scale, d_frame_offsets, total_frames, d_feat, d_energy,
+                                   stream));
+}
+
+// x: batch rows of n_samples at row stride ld; out [batch x frames x num_cepstral] (feat [.. x num_filters], energy [batch x frames])
+inline void mfcc_batch_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, std::size_t batch, std::size_t n_samples, std::size_t ld,
+                           float scale, std::vector<float> &out)
+{
+    if (batch && (ld < n_samples || x.size() < (batch - 1) * ld + n_samples)) throw Error(SS_ERR_ARG, "mfcc_batch_i16: x is too short");
+    check(ss_mfcc_batch_i16(cfg.handle(), x.data(), batch, n_samples, ld, scale, out.data()));
+}
+
+inline void mfe_batch_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, std::size_t batch, std::size_t n_samples, std::size_t ld,
+                          float scale, std::vector<float> &feat, std::vector<float> &energy)
+{
+    if (batch && (ld < n_samples || x.size() < (batch - 1) * ld + n_samples)) throw Error(SS_ERR_ARG, "mfe_batch_i16: x is too short");
+    check(ss_mfe_batch_i16(cfg.handle(), x.data(), batch, n_samples, ld, scale, feat.data(), energy.data()));
+}
+
+// x: the packed clips, sample_offsets n_clips + 1 offsets in samples; the outputs hold the clips' rows end to end
+inline void mfcc_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets, float scale,
+                            std::vector<float> &out)
+{
+    if (sample_offsets.empty()) throw Error(SS_ERR_ARG, "mfcc_packed_i16: n_clips + 1 offsets");
+    check(ss_mfcc_packed_i16(cfg.handle(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), scale, out.data()));
+}
+
+inline void mfe_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets, float scale,
+                           std::vector<float> &feat, std::vector<float> &energy)
+{
+    if (sample_offsets.empty()) throw Error(SS_ERR_ARG, "mfe_packed_i16: n_clips + 1 offsets");
+    check(ss_mfe_packed_i16(cfg.handle(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), scale, feat.data(), energy.data()));
+}
+
 // cmvn / cmvnw / power_to_db of every clip of a packed block on its own rows (ss_*_packed): clip b owns rows offsets[b] ..
 // offsets[b+1] of the [total_rows x cols] block `vec`; offsets has n_clips + 1 non-decreasing entries and starts at 0
 inline std::vector<float> cmvn_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols,

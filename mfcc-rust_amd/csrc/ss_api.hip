@@ -187,12 +187,40 @@ void fill_common(const ss_config *cfg, ss::FrontArgs &a)
     a.spectrum_exponent = h.params.spectrum_exponent;
 }
 
+// The samples of a call: floats, or signed 16-bit PCM with its scale (the _i16 entry points -- the pool's chunks, the packed one-shot
+// calls' clips: the same chain on the kernels' PCM builds).
+struct PoolChunks {
+    const float *f = nullptr;
+    const int16_t *pcm = nullptr;
+    float scale = 1.0f;
+    bool is_pcm = false;
+    PoolChunks(const float *x) : f(x) {}
+    PoolChunks(const int16_t *x, float s) : pcm(x), scale(s), is_pcm(true) {}
+    const void *ptr() const { return is_pcm ? static_cast<const void *>(pcm) : f; }
+    size_t sample_bytes() const { return is_pcm ? sizeof(int16_t) : sizeof(float); }
+};
+// a power of two in [2^-64, 2^64]: the product with an int16 is exact (and never subnormal)
+bool pcm_scale_ok(float scale)
+{
+    int ex = 0;
+    return std::isfinite(scale) && scale > 0.0f && std::frexp(scale, &ex) == 0.5f && ex - 1 >= -64 && ex - 1 <= 64;
+}
+// the _i16 entry points' check of it, before anything runs
+int check_pcm_scale(float scale)
+{
+    return pcm_scale_ok(scale) ? SS_OK : ss::fail(SS_ERR_ARG, "scale must be a power of two in [2^-64, 2^64]");
+}
+
 // MFCC-path launch (OUT_MFCC / OUT_MFE / OUT_POWER).
 // rows_are_frames: d_x is a frames matrix [batch x n] (row stride ld) -- every row is one frame of n <= fft_points samples,
 // no window, no pre-emphasis (processing::power_spectrum(frames, fft_points), processing.rs:179-181).
 // `multi` (ss_mfcc_batches_device): several independent batches of the same clip shape for ONE launch; d_x / batch / out0 then
 // describe the first of them.  Only the kernel builds that take a batch table serve it: for every other configuration NOTHING is
 // launched and kNoMultiBuild comes back (the caller then launches batch by batch).
+// `pcm` (the _i16 entry points; d_x is null then): the batch as signed 16-bit PCM.  The call runs the PCM build of the kernel the
+// float call would pick where that kernel has one (the 512-point kernel's contract-framing builds without fused pre-emphasis, the
+// generic kernel); every other dedicated kernel runs behind one conversion launch into a stream-ordered temporary (to_float below)
+// and reports its own name.  Either way the outputs are bit for bit those of the float call on (float)pcm * scale.
 struct MultiBatches {
     int n;
     const float *const *x;
@@ -202,11 +230,16 @@ struct MultiBatches {
 constexpr int kNoMultiBuild = -1;
 
 int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t batch, size_t n, size_t ld,
-                  float *out0, float *out1, hipStream_t stream, bool rows_are_frames = false, const MultiBatches *multi = nullptr)
+                  float *out0, float *out1, hipStream_t stream, bool rows_are_frames = false, const MultiBatches *multi = nullptr,
+                  const ss::BatchPcmArgs *pcm = nullptr)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (pcm) {
+        const int src = check_pcm_scale(pcm->scale);
+        if (src) return src;
+    }
     if (batch == 0) return SS_OK;  // an empty batch has no buffers (a zero-row tensor's data pointer is null)
-    if (!d_x || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (!(pcm ? static_cast<const void *>(pcm->x) : d_x) || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
     if (ld < n) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
     if (n > 0x7fffffffull || batch > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "clip too long / batch too large");
     {
@@ -263,6 +296,25 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
     a.out0 = out0;
     a.out1 = out1;
     ss::LaunchInfo info{};
+    // pcm: the float copy of the batch for a kernel without a PCM build -- made once, on the first candidate that needs it, freed
+    // in stream order when this call returns
+    struct Temp {
+        float *p = nullptr;
+        hipStream_t st = nullptr;
+        ~Temp()
+        {
+            if (p) (void)hipFreeAsync(p, st);
+        }
+    } tmp;
+    auto to_float = [&]() -> int {
+        if (!pcm || d_x) return SS_OK;
+        tmp.st = stream;
+        SS_HIP(hipMallocAsync(reinterpret_cast<void **>(&tmp.p), ((batch - 1) * ld + n) * sizeof(float), stream));
+        const hipError_t ec = ss::launch_pcm_to_float(pcm->x, tmp.p, batch, n, ld, pcm->scale, stream);
+        if (ec != hipSuccess) return hip_fail(ec, "launch_pcm_to_float");
+        a.x = d_x = tmp.p;
+        return SS_OK;
+    };
     // fft_points = 512 MFCC: the specialised wave-private kernel (its builds: default bank / run-time bank, window,
     // pre-emphasis, mfe and power outputs, librosa variants)
     const bool force_generic = ss::dbg_force_generic();
@@ -317,7 +369,7 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
         f.fullp = cfg->fast.fullp;
         f.paired = cfg->fast.paired ? (cfg->fast.tight ? 2 : 1) : 0;
 #if SS_LAB
-        if (dbg_path && !dbg_done && !f.out_mfe && !multi) {
+        if (dbg_path && !dbg_done && !f.out_mfe && !multi && !pcm) {
             dbg_done = true;
             const size_t nwaves = static_cast<size_t>(cfg->num_cus) * 16;
             DeviceBuf db;
@@ -362,6 +414,17 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
             if (em != hipSuccess) return hip_fail(em, "launch_mfcc_c256_multi");
             g_last_kernel = info.kernel_name;
             return SS_OK;
+        }
+        if (pcm) {
+            const hipError_t ep = ss::launch_mfcc_c256(f, *pcm, stream, cfg->num_cus, &info);
+            if (ep == hipSuccess) {
+                g_last_kernel = info.kernel_name;
+                return SS_OK;
+            }
+            // hipErrorInvalidValue before the launch: no PCM build for this shape (or no build at all) -> the float build on the copy
+            if (ep != hipErrorInvalidValue) return hip_fail(ep, "launch_mfcc_c256 (PCM)");
+            if ((rc = to_float())) return rc;
+            f.x = d_x;
         }
         const hipError_t e = ss::launch_mfcc_c256(f, stream, cfg->num_cus, &info);
         if (e == hipSuccess) {
@@ -418,6 +481,7 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
     // headline kernel has no build for (ss_mfcc512w.hip): optional frame window, centred frames, fused pre-emphasis
     if (!force_generic && cfg->mfcc512w.ok && static_cast<unsigned long long>(batch) * T + 4 < 0x7fffffffull &&
         (out_kind == ss::OUT_MFCC || out_kind == ss::OUT_MFE) && (a.frame_mode == ss::FRAME_NORMAL || centre)) {
+        if ((rc = to_float())) return rc;
         ss::Mfcc256Args f{};
         f.center = centre;
         f.pad_reflect = a.pad_reflect;
@@ -456,6 +520,7 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
     // fft_points = 256 MFCC / mfe: two frames per complex transform (ss_mfcc256.hip); optional frame window, fused pre-emphasis
     if (!force_generic && cfg->mfcc256.ok && static_cast<unsigned long long>(batch) * T + 8 < 0x7fffffffull &&
         (out_kind == ss::OUT_MFCC || out_kind == ss::OUT_MFE) && a.frame_mode == ss::FRAME_NORMAL && a.flen <= 256) {
+        if ((rc = to_float())) return rc;
         ss::Mfcc256Args f{};
         f.preemph = a.preemph;
         f.preemph_shift = a.preemph_shift;
@@ -493,6 +558,7 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
     // (both have librosa-compatible builds: centred frames, banks up to fs/2)
     if (!force_generic && (cfg->mfcc2048.ok || cfg->mfcc1024.ok) && fits32 && (out_kind == ss::OUT_MFCC || out_kind == ss::OUT_MFE) &&
         (a.frame_mode == ss::FRAME_NORMAL || centre)) {
+        if ((rc = to_float())) return rc;
         ss::Mfcc2048Args f{};
         f.preemph = a.preemph;
         f.preemph_shift = a.preemph_shift;
@@ -532,6 +598,7 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
     }
     // fft_points = 4096 MFCC / mfe (up to 256 filters): the one-frame-per-wave kernel
     if (!force_generic && cfg->mfcc4096.ok && fits32 && (out_kind == ss::OUT_MFCC || out_kind == ss::OUT_MFE) && a.frame_mode == ss::FRAME_NORMAL) {
+        if ((rc = to_float())) return rc;
         ss::Mfcc4096Args f{};
         fill4096(f);
 #if SS_LAB
@@ -561,7 +628,9 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
             return SS_OK;
         }
     }
-    hipError_t e = ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info);
+    // (pcm: the generic kernel's PCM build, unless a dedicated candidate above already made the float copy and then declined)
+    hipError_t e = pcm && !d_x ? ss::launch_front_generic(a, *pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                               : ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info);
     if (e != hipSuccess) return hip_fail(e, "launch_front_generic");
     g_last_kernel = info.kernel_name;
     return SS_OK;
@@ -1043,24 +1112,6 @@ int frame_stream_host(const ss_config *cfg, int out_kind, const float *x, size_t
 // n_active entries of different hop counts, each over the pool row its slot names, then the advance of the named rows -- a linear
 // chain of two kernels on `stream` (none for the advance where S == 0).  The tables are device arrays read by the kernels only
 // (FrameStreamPackedArgs, ss_device.h); the grids come from n_active and total_rows.  Candidate order as launch_frame_stream.
-// The chunks of a call: floats, or signed 16-bit PCM with its scale (the _i16 entry points: the same chain on the kernels' PCM builds).
-struct PoolChunks {
-    const float *f = nullptr;
-    const int16_t *pcm = nullptr;
-    float scale = 1.0f;
-    bool is_pcm = false;
-    PoolChunks(const float *x) : f(x) {}
-    PoolChunks(const int16_t *x, float s) : pcm(x), scale(s), is_pcm(true) {}
-    const void *ptr() const { return is_pcm ? static_cast<const void *>(pcm) : f; }
-    size_t sample_bytes() const { return is_pcm ? sizeof(int16_t) : sizeof(float); }
-};
-// a power of two in [2^-64, 2^64]: the product with an int16 is exact (and never subnormal)
-bool pcm_scale_ok(float scale)
-{
-    int ex = 0;
-    return std::isfinite(scale) && scale > 0.0f && std::frexp(scale, &ex) == 0.5f && ex - 1 >= -64 && ex - 1 <= 64;
-}
-
 int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_active, const int64_t *d_so, const int64_t *d_ro,
                                size_t total_rows, const int32_t *d_slots, size_t pool_streams, uint32_t norm_frames, float *d_pool,
                                float *out0, float *out1, hipStream_t stream)
@@ -1073,7 +1124,7 @@ int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const PoolChu
     if (rc) return rc;
     if (!x.ptr() || !d_so || !d_ro || !d_slots || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !d_pool))
         return ss::fail(SS_ERR_ARG, "null buffer");
-    if (x.is_pcm && !pcm_scale_ok(x.scale)) return ss::fail(SS_ERR_ARG, "scale must be a power of two in [2^-64, 2^64]");
+    if (x.is_pcm && (rc = check_pcm_scale(x.scale))) return rc;
     if (x.is_pcm && (reinterpret_cast<uintptr_t>(x.pcm) & 3u)) return ss::fail(SS_ERR_ARG, "the PCM buffer must be 4-byte aligned");
     if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull || total_rows >= 0x80000000ull)
         return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
@@ -1139,7 +1190,7 @@ int frame_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunk
     int rc = ss_frame_stream_state_len(&h.params, &S);
     if (rc) return rc;
     if (!x.ptr() || !so || !slots || !out0 || (out_kind == ss::OUT_MFE && !out1) || (S > 0 && !pool)) return ss::fail(SS_ERR_ARG, "null buffer");
-    if (x.is_pcm && !pcm_scale_ok(x.scale)) return ss::fail(SS_ERR_ARG, "scale must be a power of two in [2^-64, 2^64]");
+    if (x.is_pcm && (rc = check_pcm_scale(x.scale))) return rc;
     if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull)
         return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
     if (out_kind == ss::OUT_MFCC && h.params.dct_norm != SS_DCT_ORTHO && norm_frames == 0)
@@ -1448,8 +1499,10 @@ int check_device(const ss_config *cfg)
 // returns (PCIe is full duplex).  Pinned caller memory (hipHostMalloc / hipHostRegister / torch pin_memory) is DMA'd directly;
 // for pageable memory the runtime stages the copy and hipMemcpyAsync returns once the staging is done.
 // launch(d_x, units_in_chunk, d_out0, d_out1, stream) issues the kernels for one chunk.
-template <typename Launch>
-int host_pipeline(const ss_config *cfg, const float *x, size_t units, size_t n, size_t ld, float *out0, size_t out0_per_unit,
+// T: the sample type -- float, or int16_t for the _i16 host forms, whose samples cross the link (and the mapped staging) as int16;
+// the chunk size and the small-call threshold are in bytes either way.
+template <typename T, typename Launch>
+int host_pipeline(const ss_config *cfg, const T *x, size_t units, size_t n, size_t ld, float *out0, size_t out0_per_unit,
                   float *out1, size_t out1_per_unit, Launch launch)
 {
     ss_config::HostPipe &hp = cfg->pipe;
@@ -1483,7 +1536,7 @@ int host_pipeline(const ss_config *cfg, const float *x, size_t units, size_t n, 
 #else
     constexpr size_t small_bytes = size_t(1024) << 10;
 #endif
-    const size_t in_all = ((units - 1) * ld + n) * sizeof(float), o0_all = units * out0_per_unit * sizeof(float),
+    const size_t in_all = ((units - 1) * ld + n) * sizeof(T), o0_all = units * out0_per_unit * sizeof(float),
                  o1_all = out1 ? units * out1_per_unit * sizeof(float) : 0;
     if (units > 0 && in_all <= small_bytes && o0_all <= small_bytes && o1_all <= small_bytes) {
         const size_t need[3] = {in_all, o0_all, o1_all};
@@ -1499,7 +1552,7 @@ int host_pipeline(const ss_config *cfg, const float *x, size_t units, size_t n, 
             hp.cap_small[i] = cap;
         }
         std::memcpy(hp.h_small[0], x, in_all);
-        int rc = launch(static_cast<const float *>(hp.d_small[0]), units, static_cast<float *>(hp.d_small[1]), static_cast<float *>(hp.d_small[2]), hp.stream[0]);
+        int rc = launch(static_cast<const T *>(hp.d_small[0]), units, static_cast<float *>(hp.d_small[1]), static_cast<float *>(hp.d_small[2]), hp.stream[0]);
         const hipError_t e = hipStreamSynchronize(hp.stream[0]);
         if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "host call (mapped staging)");
         if (rc == SS_OK) rc = pending_device_error(cfg);
@@ -1509,10 +1562,10 @@ int host_pipeline(const ss_config *cfg, const float *x, size_t units, size_t n, 
         }
         return rc;
     }
-    size_t cu = chunk_bytes / (ld * sizeof(float));
+    size_t cu = chunk_bytes / (ld * sizeof(T));
     if (cu == 0) cu = 1;
     if (cu > units) cu = units;
-    const size_t in_cap = ((cu - 1) * ld + n) * sizeof(float), o0_cap = cu * out0_per_unit * sizeof(float), o1_cap = cu * out1_per_unit * sizeof(float);
+    const size_t in_cap = ((cu - 1) * ld + n) * sizeof(T), o0_cap = cu * out0_per_unit * sizeof(float), o1_cap = cu * out1_per_unit * sizeof(float);
     auto grow = [&](void *(&buf)[2], size_t &cap, size_t need) -> int {
         if (need <= cap) return SS_OK;
         // the capacity is void until BOTH new buffers exist: a failed hipMalloc must not leave a non-zero cap beside a
@@ -1546,9 +1599,9 @@ int host_pipeline(const ss_config *cfg, const float *x, size_t units, size_t n, 
         // the stream orders this chunk behind the previous use of the same buffer set.  A failure only breaks out of the
         // loop: earlier chunks may still have copies in flight that touch the caller's x / out buffers, so both streams are
         // synchronised below before this function returns, whatever happened.
-        hipError_t e = hipMemcpyAsync(hp.d_in[b], x + u0 * ld, ((c - 1) * ld + n) * sizeof(float), hipMemcpyHostToDevice, st);
+        hipError_t e = hipMemcpyAsync(hp.d_in[b], x + u0 * ld, ((c - 1) * ld + n) * sizeof(T), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) { rc = hip_fail(e, "hipMemcpyAsync (H2D)"); break; }
-        rc = launch(static_cast<const float *>(hp.d_in[b]), c, static_cast<float *>(hp.d_out0[b]), static_cast<float *>(hp.d_out1[b]), st);
+        rc = launch(static_cast<const T *>(hp.d_in[b]), c, static_cast<float *>(hp.d_out0[b]), static_cast<float *>(hp.d_out1[b]), st);
         if (rc) break;
         e = hipMemcpyAsync(out0 + u0 * out0_per_unit, hp.d_out0[b], c * out0_per_unit * sizeof(float), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && out1) e = hipMemcpyAsync(out1 + u0 * out1_per_unit, hp.d_out1[b], c * out1_per_unit * sizeof(float), hipMemcpyDeviceToHost, st);
@@ -1566,12 +1619,18 @@ int host_pipeline(const ss_config *cfg, const float *x, size_t units, size_t n, 
 // Clip b is d_x[so[b] : so[b+1]], its features rows fo[b] .. fo[b+1] of out0 (and out1); the offset tables are device arrays, read
 // by the kernel only (nothing of them passes through the host here: the launch is graph-capturable).  One launch over every
 // clip's frames; the kernel checks the tables against each other (VarlenArgs, ss_device.h).
-int launch_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n_clips, const int64_t *d_so, const int64_t *d_fo,
+// x: the packed samples, floats or 16-bit PCM (the _i16 entry points: both kernels have a PCM build, so no call converts first).
+int launch_packed(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_clips, const int64_t *d_so, const int64_t *d_fo,
                   size_t total_frames, float *out0, float *out1, hipStream_t stream)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (x.is_pcm) {
+        const int src = check_pcm_scale(x.scale);
+        if (src) return src;
+    }
     if (n_clips == 0) return SS_OK;
-    if (!d_x || !d_so || !d_fo || !out0 || (out_kind == ss::OUT_MFE && !out1)) return ss::fail(SS_ERR_ARG, "null buffer");
+    const float *d_x = x.f;
+    if (!x.ptr() || !d_so || !d_fo || !out0 || (out_kind == ss::OUT_MFE && !out1)) return ss::fail(SS_ERR_ARG, "null buffer");
     if (n_clips > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many clips");
     {
         const int drc = check_device(cfg);  // see launch_frames
@@ -1615,6 +1674,7 @@ int launch_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n
     v.dct_ortho = h.params.dct_norm == SS_DCT_ORTHO;
     v.dct2_gain = g;
     v.err = cfg->d_err;
+    const ss::VarlenPcmArgs vp{v, x.pcm, x.scale};
     ss::LaunchInfo info{};
     // the headline shape (512-point MFCC, default frame shape and bank): the varlen build of the dedicated kernel -- the same bits as
     // ss_mfcc_batch_device per clip; hipErrorInvalidValue before the launch for every other configuration
@@ -1642,14 +1702,16 @@ int launch_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n
         f.pad_reflect = a.pad_reflect;
         f.fullp = cfg->fast.fullp;
         f.paired = cfg->fast.paired ? (cfg->fast.tight ? 2 : 1) : 0;
-        const hipError_t ef = ss::launch_mfcc_c256_varlen(f, v, stream, cfg->num_cus, &info);
+        const hipError_t ef = x.is_pcm ? ss::launch_mfcc_c256_varlen(f, vp, stream, cfg->num_cus, &info)
+                                       : ss::launch_mfcc_c256_varlen(f, v, stream, cfg->num_cus, &info);
         if (ef == hipSuccess) {
             g_last_kernel = info.kernel_name;
             return SS_OK;
         }
         if (ef != hipErrorInvalidValue) return hip_fail(ef, "launch_mfcc_c256_varlen");
     }
-    const hipError_t e = ss::launch_front_generic_varlen(a, v, h.d.log2c, stream, cfg->num_cus, &info);
+    const hipError_t e = x.is_pcm ? ss::launch_front_generic_varlen(a, vp, h.d.log2c, stream, cfg->num_cus, &info)
+                                  : ss::launch_front_generic_varlen(a, v, h.d.log2c, stream, cfg->num_cus, &info);
     if (e != hipSuccess) return hip_fail(e, "launch_front_generic_varlen");
     g_last_kernel = info.kernel_name;
     return SS_OK;
@@ -1658,12 +1720,17 @@ int launch_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n
 // Host-pointer form: the frame offsets from the host's sample offsets, one upload, one launch, one download on the config's
 // first host-pipeline stream (the host calls of a config are serialised by its mutex).
 // ln: lmfe -- the features go through the in-place ln on the device and the frame energies stay there (out1 is NULL).
-int packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_clips, const int64_t *so, float *out0, float *out1,
+// x: floats or 16-bit PCM; the samples go up as they are (2 B per sample for PCM) and the device call converts on load.
+int packed_host(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_clips, const int64_t *so, float *out0, float *out1,
                 bool ln = false)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (x.is_pcm) {
+        const int src = check_pcm_scale(x.scale);
+        if (src) return src;
+    }
     if (n_clips == 0) return SS_OK;
-    if (!x || !so || !out0 || (out_kind == ss::OUT_MFE && !out1 && !ln)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (!x.ptr() || !so || !out0 || (out_kind == ss::OUT_MFE && !out1 && !ln)) return ss::fail(SS_ERR_ARG, "null buffer");
     std::vector<int64_t> fo(n_clips + 1);
     int rc = ss_packed_frame_offsets(&cfg->host.params, n_clips, so, fo.data());
     if (rc) return rc;
@@ -1678,17 +1745,17 @@ int packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_cli
     }
     hipStream_t st = hp.stream[0];
     DeviceBuf dx, dso, dfo, d0, d1;
-    if ((rc = dx.alloc(samples * sizeof(float))) || (rc = dso.alloc((n_clips + 1) * sizeof(int64_t))) ||
+    if ((rc = dx.alloc(samples * x.sample_bytes())) || (rc = dso.alloc((n_clips + 1) * sizeof(int64_t))) ||
         (rc = dfo.alloc((n_clips + 1) * sizeof(int64_t))) || (rc = d0.alloc(rows * cols * sizeof(float))) ||
         ((out1 || ln) && (rc = d1.alloc(rows * sizeof(float)))))
         return rc;
-    hipError_t e = hipMemcpyAsync(dx.p, x, samples * sizeof(float), hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(dx.p, x.ptr(), samples * x.sample_bytes(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dfo.p, fo.data(), (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
     if (rc == SS_OK)
-        rc = launch_packed(cfg, out_kind, dx.as<const float>(), n_clips, dso.as<const int64_t>(), dfo.as<const int64_t>(), rows,
-                           d0.as<float>(), (out1 || ln) ? d1.as<float>() : nullptr, st);
+        rc = launch_packed(cfg, out_kind, x.is_pcm ? PoolChunks(dx.as<const int16_t>(), x.scale) : PoolChunks(dx.as<const float>()), n_clips,
+                           dso.as<const int64_t>(), dfo.as<const int64_t>(), rows, d0.as<float>(), (out1 || ln) ? d1.as<float>() : nullptr, st);
     if (rc == SS_OK && ln) rc = ss_ln_device(d0.as<float>(), rows * cols, st);
     if (rc == SS_OK) {
         e = hipMemcpyAsync(out0, d0.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost, st);
@@ -2026,6 +2093,49 @@ int ss_mfe_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips,
 {
     return launch_packed(cfg, ss::OUT_MFE, d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_feat, d_energy,
                          static_cast<hipStream_t>(stream));
+}
+
+// ---- the one-shot calls fed signed 16-bit PCM: sample = (float)pcm * scale (speechsauce_amd.h) ----
+int ss_mfcc_batch_i16_device(const ss_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale,
+                             float *d_out, void *stream)
+{
+    const ss::BatchPcmArgs pcm{d_x, scale};
+    return launch_frames(cfg, ss::OUT_MFCC, nullptr, batch, n_samples, ld, d_out, nullptr, static_cast<hipStream_t>(stream), false, nullptr,
+                         &pcm);
+}
+
+int ss_mfe_batch_i16_device(const ss_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale,
+                            float *d_feat, float *d_energy, void *stream)
+{
+    if (!d_energy) return ss::fail(SS_ERR_ARG, "null buffer");
+    const ss::BatchPcmArgs pcm{d_x, scale};
+    return launch_frames(cfg, ss::OUT_MFE, nullptr, batch, n_samples, ld, d_feat, d_energy, static_cast<hipStream_t>(stream), false, nullptr,
+                         &pcm);
+}
+
+int ss_mfcc_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                              const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream)
+{
+    return launch_packed(cfg, ss::OUT_MFCC, PoolChunks(d_x, scale), n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, nullptr,
+                         static_cast<hipStream_t>(stream));
+}
+
+int ss_mfe_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                             const int64_t *d_frame_offsets, size_t total_frames, float *d_feat, float *d_energy, void *stream)
+{
+    return launch_packed(cfg, ss::OUT_MFE, PoolChunks(d_x, scale), n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_feat, d_energy,
+                         static_cast<hipStream_t>(stream));
+}
+
+int ss_mfcc_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out)
+{
+    return packed_host(cfg, ss::OUT_MFCC, PoolChunks(x, scale), n_clips, sample_offsets, out, nullptr);
+}
+
+int ss_mfe_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *feat,
+                      float *energy)
+{
+    return packed_host(cfg, ss::OUT_MFE, PoolChunks(x, scale), n_clips, sample_offsets, feat, energy);
 }
 
 int ss_mfcc_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out)
@@ -2776,6 +2886,44 @@ int ss_mfe_batch(const ss_config *cfg, const float *x, size_t batch, size_t n_sa
 int ss_mfe(const ss_config *cfg, const float *x, size_t n_samples, float *feat, float *energy)
 {
     return ss_mfe_batch(cfg, x, 1, n_samples, n_samples, feat, energy);
+}
+
+// the same two from int16 host buffers: the samples cross the link as int16 (host_pipeline<int16_t>) and the device call converts
+int ss_mfcc_batch_i16(const ss_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, float *out)
+{
+    if (!cfg || !x || !out) return ss::fail(SS_ERR_ARG, "null argument");
+    int rc = check_pcm_scale(scale);
+    if (rc) return rc;
+    if (ld < n_samples) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
+    size_t T = 0;
+    rc = ss::num_frames(cfg->host.params, n_samples, T);
+    if (rc) return rc;
+    if (batch == 0) return SS_OK;
+    rc = check_device(cfg);
+    if (rc) return rc;
+    return host_pipeline(cfg, x, batch, n_samples, ld, out, T * cfg->host.params.num_cepstral, nullptr, 0,
+                         [&](const int16_t *d_x, size_t c, float *d_o0, float *, hipStream_t st) {
+                             return ss_mfcc_batch_i16_device(cfg, d_x, c, n_samples, ld, scale, d_o0, st);
+                         });
+}
+
+int ss_mfe_batch_i16(const ss_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, float *feat,
+                     float *energy)
+{
+    if (!cfg || !x || !feat || !energy) return ss::fail(SS_ERR_ARG, "null argument");
+    int rc = check_pcm_scale(scale);
+    if (rc) return rc;
+    if (ld < n_samples) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
+    size_t T = 0;
+    rc = ss::num_frames(cfg->host.params, n_samples, T);
+    if (rc) return rc;
+    if (batch == 0) return SS_OK;
+    rc = check_device(cfg);
+    if (rc) return rc;
+    return host_pipeline(cfg, x, batch, n_samples, ld, feat, T * cfg->host.params.num_filters, energy, T,
+                         [&](const int16_t *d_x, size_t c, float *d_o0, float *d_o1, hipStream_t st) {
+                             return ss_mfe_batch_i16_device(cfg, d_x, c, n_samples, ld, scale, d_o0, d_o1, st);
+                         });
 }
 
 int ss_mel_spectrogram(const ss_config *cfg, const float *x, size_t channels, size_t n_samples, float *out)

@@ -362,6 +362,28 @@ hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const Fr
 // ss_stream_advance_packed with the chunk read as PCM: the pool rows end up holding the floats the float call would have stored
 hipError_t launch_stream_advance_packed(const FrameStreamPackedPcmArgs &s, hipStream_t stream);
 
+// The one-shot calls fed signed 16-bit PCM (ss_mfcc_batch_i16_device / ss_mfe_batch_i16_device / ss_mfcc_packed_i16_device /
+// ss_mfe_packed_i16_device): sample k is (float)x[k] * scale, scale a power of two (the product is exact).  Trailing argument packs
+// of the kernels' PCM builds, as FrameStreamPackedPcmArgs is; FrontArgs::x / Fast512Args::x are unused there.  ld and the offsets
+// stay in samples; x needs 2-byte alignment only (the generic builds read single samples, the headline builds read a sample pair as
+// one dword at 2-byte alignment).
+struct BatchPcmArgs {  // equal-length clips: clip b starts at x + b * ld
+    const int16_t *x;
+    float scale;
+};
+struct VarlenPcmArgs {  // packed clips: the float layout's tables (varlen_clip(), varlen_check_clips() serve both)
+    VarlenArgs v;
+    const int16_t *x;
+    float scale;
+};
+// a as for launch_front_generic / launch_front_generic_varlen (a.x unused); MFCC / mfe / power outputs as the float layouts
+hipError_t launch_front_generic(const FrontArgs &a, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info);
+hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenPcmArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
+                                       LaunchInfo *info);
+// The fallback of the equal-length PCM calls whose kernel has no PCM build (both packed kernels have one): dst[r * ld + k] = (float)src[r * ld + k] * scale for k < n, r < rows
+// (the gaps between rows are left alone).  Grid-stride, plain vector loads and stores.
+hipError_t launch_pcm_to_float(const int16_t *src, float *dst, size_t rows, size_t n, size_t ld, float scale, hipStream_t stream);
+
 // Ragged streaming STFT / mel spectrogram over a pool of stream states (ss_mel_spectrogram_stream_packed_device /
 // ss_stft_stream_packed_device): the same tables on the STFT path, continuous mode.  The entry block is the frame pool's, with
 // step = hop, state_len = fft_points - hop and lead unused, so that stream_entry(), stream_check_entries(), the lookups over its tables and
@@ -471,6 +493,12 @@ hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a, const FrameStrea
 // 4-byte aligned is hipErrorInvalidValue too
 hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a, const FrameStreamPackedPcmArgs &s, hipStream_t stream, int num_cus,
                                           LaunchInfo *info);
+// launch_mfcc_c256 / launch_mfcc_c256_varlen fed 16-bit PCM (BatchPcmArgs / VarlenPcmArgs, declared above; a.x unused), reported as
+// ss_mfcc_c256i<...> / ss_mfcc_c256vi<...>.  The equal-length PCM builds: what launch_mfcc_c256 serves with contract framing and no
+// fused pre-emphasis (MFCC, mfe, the optional window; every frame length, an odd one's half pair included); the varlen PCM build:
+// what launch_mfcc_c256_varlen serves.  hipErrorInvalidValue before the launch for every other configuration.
+hipError_t launch_mfcc_c256(const Fast512Args &a, const BatchPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info);
+hipError_t launch_mfcc_c256_varlen(const Fast512Args &a, const VarlenPcmArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
 // whether the kernel has an mfe-output / windowed / pre-emphasised build for this shape (the default bank at flen 320)
 bool mfcc_c256_has_mfe(const Fast512Args &a);
 

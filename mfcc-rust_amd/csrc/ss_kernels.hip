@@ -14,6 +14,9 @@
 // ss_front_generic<LOG2C, BLU, FrameStreamPackedPcmArgs> (reported as ss_front_generic_fstreampi<LOG2C>): that pool fed signed
 // 16-bit PCM -- a chunk sample or pre-emphasis tap is (float)int16 * scale (FrameStreamPackedPcmArgs, ss_device.h), the state stays
 // float; ss_stream_advance_packed_i16 moves the named pool rows on behind it.
+// ss_front_generic<LOG2C, BLU, BatchPcmArgs> / <LOG2C, BLU, VarlenPcmArgs> (reported as ss_front_generic_i16<LOG2C> /
+// ss_front_generic_varleni<LOG2C>): the equal-length and the packed MFCC / mfe path fed signed 16-bit PCM -- every sample or
+// pre-emphasis tap is (float)int16 * scale (BatchPcmArgs / VarlenPcmArgs, ss_device.h).
 // ss_front_generic<LOG2C, BLU, VarRowsArgs> (reported as ss_front_generic_varrows<LOG2C>): the STFT / mel path over packed clips of
 // different lengths (VarRowsArgs, ss_device.h), handed out in tiles of packed rows.
 // ss_front_generic<LOG2C, BLU, StftStreamPackedArgs> (reported as ss_front_generic_streamp<LOG2C>): the STFT / mel path over a pool
@@ -256,16 +259,19 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
 // FSP: FSTREAM over a pool of states (launch_front_generic_frame_stream_packed) -- the flat frame index is the packed output row, and
 // the row's entry (its chunk, its row within the chunk, its pool row) comes from the device tables (FrameStreamPackedArgs).
 // FSPI: FSP with the chunks as 16-bit PCM (FrameStreamPackedPcmArgs: its entry block is FSP's; state reads are unchanged).
+// EQI / VARI: the equal-length layout / VAR with the samples as 16-bit PCM (BatchPcmArgs / VarlenPcmArgs: VARI's tables are VAR's).
 // VARR: the STFT / mel path of launch_front_generic_varrows -- a workgroup visit is a tile of packed rows, every row finds its own
 // clip; the transposed mel flush writes each row into its clip's [M x R_b] block.
 // SPR: VARR's tiles over the entries of a ragged streaming call (launch_front_generic_stream_packed) -- a row's entry (its chunk, its
 // row within the chunk, its pool row) comes from the device tables (StftStreamPackedArgs), its window as in STREAM.
 // (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs, one FrameStreamPackedArgs, one FrameStreamPackedPcmArgs, one
-// VarRowsArgs or one StftStreamPackedArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
+// BatchPcmArgs, one VarlenPcmArgs, one VarRowsArgs or one StftStreamPackedArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
 template <int LOG2C, bool BLU, typename... V>
 __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
 {
-    constexpr bool VAR = (std::is_same_v<V, VarlenArgs> || ...);
+    constexpr bool EQI = (std::is_same_v<V, BatchPcmArgs> || ...);
+    constexpr bool VARI = (std::is_same_v<V, VarlenPcmArgs> || ...);
+    constexpr bool VAR = VARI || (std::is_same_v<V, VarlenArgs> || ...);
     constexpr bool STREAM = (std::is_same_v<V, StreamArgs> || ...);
     constexpr bool FSPI = (std::is_same_v<V, FrameStreamPackedPcmArgs> || ...);
     constexpr bool FSP = FSPI || (std::is_same_v<V, FrameStreamPackedArgs> || ...);
@@ -274,7 +280,10 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     constexpr bool SPR = (std::is_same_v<V, StftStreamPackedArgs> || ...);
     [[maybe_unused]] const StftStreamPackedArgs *sp = pack_arg<StftStreamPackedArgs>(vargs...);
     [[maybe_unused]] const VarRowsArgs *ra = pack_arg<VarRowsArgs>(vargs...);
+    [[maybe_unused]] const BatchPcmArgs *bpi = pack_arg<BatchPcmArgs>(vargs...);
+    [[maybe_unused]] const VarlenPcmArgs *vpi = pack_arg<VarlenPcmArgs>(vargs...);
     [[maybe_unused]] const VarlenArgs *va = pack_arg<VarlenArgs>(vargs...);
+    if constexpr (VARI) va = &vpi->v;
     [[maybe_unused]] const StreamArgs *sa = pack_arg<StreamArgs>(vargs...);
     [[maybe_unused]] const FrameStreamArgs *fa = pack_arg<FrameStreamArgs>(vargs...);
     [[maybe_unused]] const FrameStreamPackedPcmArgs *fpi = pack_arg<FrameStreamPackedPcmArgs>(vargs...);
@@ -313,7 +322,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
             const unsigned long long gf = g * G::FPB + slot;
             bool active = gf < total;
             const float *xc;
-            [[maybe_unused]] const int16_t *xi = nullptr;  // FSPI: the entry's chunk
+            [[maybe_unused]] const int16_t *xi = nullptr;  // FSPI: the entry's chunk; EQI / VARI: the clip
             unsigned t;
             unsigned n_samples = a.n_samples;
             int frame_mode = a.frame_mode;
@@ -324,7 +333,12 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 const VarClip c = varlen_clip(*va, a.flen, a.step, active ? offset_find(va->fo, va->n_clips, static_cast<long long>(gf)) : 0u);
                 active = active && c.ok && static_cast<long long>(gf) >= c.f0 && static_cast<long long>(gf) - c.f0 < static_cast<long long>(c.T);
                 t = active ? static_cast<unsigned>(static_cast<long long>(gf) - c.f0) : 0u;
-                xc = a.x + (active ? c.s0 : 0ll);
+                if constexpr (VARI) {
+                    xc = nullptr;
+                    xi = vpi->x + (active ? c.s0 : 0ll);
+                } else {
+                    xc = a.x + (active ? c.s0 : 0ll);
+                }
                 n_samples = active ? c.n : 1u;
                 // processing.rs:110-120 as written, with the clip's own frame count
                 if (va->framing == SS_FRAMING_LITERAL) frame_mode = c.T > 2u ? FRAME_ZERO : FRAME_FIRST;
@@ -346,7 +360,12 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 const unsigned gf32 = static_cast<unsigned>(gf);  // launch_one rejects batches with >= 2^32 frames
                 const unsigned clip = active ? gf32 / a.n_frames : 0u;
                 t = active ? gf32 - clip * a.n_frames : 0u;
-                xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
+                if constexpr (EQI) {
+                    xc = nullptr;
+                    xi = bpi->x + static_cast<unsigned long long>(clip) * a.ld;
+                } else {
+                    xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
+                }
                 if constexpr (FSTREAM) srow = fa->state + static_cast<unsigned long long>(clip) * fa->state_len + fa->state_len;
             }
             // stack_frames (processing.rs:65-129, contract framing) + zero pad to N (:147-156)
@@ -392,12 +411,18 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                         }
                         idx = static_cast<unsigned>(pos);
                     }
+                    // the clip's sample k (EQI / VARI: int16 times the power-of-two scale, exact)
+                    auto clip_sample = [&](unsigned k) -> float {
+                        if constexpr (EQI) return pcm_sample(xi, k, bpi->scale);
+                        else if constexpr (VARI) return pcm_sample(xi, k, vpi->scale);
+                        else return xc[k];
+                    };
                     if (inside) {
-                        val = xc[idx];
+                        val = clip_sample(idx);
                         if (a.preemph != 0.0f) {  // processing.rs:31-53 fused
                             const unsigned sh = a.preemph_shift % n_samples;
                             const unsigned jdx = idx >= sh ? idx - sh : idx + n_samples - sh;
-                            val -= a.preemph * xc[jdx];
+                            val -= a.preemph * clip_sample(jdx);
                         }
                     }
                     if (a.window) val *= a.window[i];
@@ -674,6 +699,8 @@ size_t front_lds_bytes(const FrontArgs &a)
 // builds): the suffix of the reported name, the LDS behind the equal-length carve, and the workgroup visits of the call.
 constexpr const char *layout_suffix() { return ""; }
 constexpr const char *layout_suffix(const VarlenArgs &) { return "_varlen"; }
+constexpr const char *layout_suffix(const BatchPcmArgs &) { return "_i16"; }
+constexpr const char *layout_suffix(const VarlenPcmArgs &) { return "_varleni"; }
 constexpr const char *layout_suffix(const VarRowsArgs &) { return "_varrows"; }
 constexpr const char *layout_suffix(const StreamArgs &) { return "_stream"; }
 constexpr const char *layout_suffix(const FrameStreamArgs &) { return "_fstream"; }
@@ -688,6 +715,8 @@ constexpr size_t layout_lds(const V &...) { return 0; }
 constexpr size_t layout_lds(const VarRowsArgs &) { return kRowTableBytes; }
 constexpr size_t layout_lds(const StftStreamPackedArgs &) { return kRowTableBytes; }
 constexpr size_t layout_lds(const FrameStreamPackedPcmArgs &) { return 0; }
+constexpr size_t layout_lds(const BatchPcmArgs &) { return 0; }
+constexpr size_t layout_lds(const VarlenPcmArgs &) { return 0; }
 
 // Workgroup visits of a call at `fpb` frames per visit.  0: nothing to launch; kTooManyRows: the kernel's 32-bit row index does not
 // reach the last row.
@@ -719,6 +748,8 @@ inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb
 {
     return layout_work(a, fpb, s.e);
 }
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const BatchPcmArgs &) { return layout_work(a, fpb); }
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const VarlenPcmArgs &v) { return layout_work(a, fpb, v.v); }
 inline unsigned long long layout_work(const FrontArgs &, unsigned long long, const VarRowsArgs &v) { return at_least_one((v.total_rows + 31) / 32); }
 inline unsigned long long layout_work(const FrontArgs &, unsigned long long, const StftStreamPackedArgs &s)
 {
@@ -913,6 +944,42 @@ hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, 
 {
     if (a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE) return hipErrorInvalidValue;
     return dispatch_front(a, log2c, stream, num_cus, info, v);
+}
+
+hipError_t launch_front_generic(const FrontArgs &a, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    if ((a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE && a.out_kind != OUT_POWER) || !p.x) return hipErrorInvalidValue;
+    return dispatch_front(a, log2c, stream, num_cus, info, p);
+}
+
+hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenPcmArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
+                                       LaunchInfo *info)
+{
+    if ((a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE) || !v.x) return hipErrorInvalidValue;
+    return dispatch_front(a, log2c, stream, num_cus, info, v);
+}
+
+// The PCM calls' fallback (launch_pcm_to_float): dst[r * ld + k] = (float)src[r * ld + k] * scale, k < n.  Grid-stride over the
+// rows' samples; plain vector loads and stores.
+__global__ __launch_bounds__(256) void ss_pcm_to_float(const int16_t *__restrict__ src, float *__restrict__ dst, unsigned long long rows,
+                                                        unsigned long long n, unsigned long long ld, float scale)
+{
+    const unsigned long long total = rows * n, stride = static_cast<unsigned long long>(gridDim.x) * 256u;
+    for (unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256u + threadIdx.x; i < total; i += stride) {
+        const unsigned long long r = ld == n ? 0ull : i / n;
+        const unsigned long long k = i - r * n + r * ld;
+        dst[k] = pcm_sample(src, static_cast<long long>(k), scale);
+    }
+}
+
+hipError_t launch_pcm_to_float(const int16_t *src, float *dst, size_t rows, size_t n, size_t ld, float scale, hipStream_t stream)
+{
+    if (rows == 0 || n == 0) return hipSuccess;
+    if (!src || !dst || ld < n) return hipErrorInvalidValue;
+    const unsigned long long total = static_cast<unsigned long long>(rows) * n, blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(ss_pcm_to_float, dim3(static_cast<unsigned>(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, src, dst,
+                       static_cast<unsigned long long>(rows), static_cast<unsigned long long>(n), static_cast<unsigned long long>(ld), scale);
+    return hipGetLastError();
 }
 
 hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,

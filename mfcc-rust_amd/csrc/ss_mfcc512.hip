@@ -59,6 +59,9 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <string>
 #include <type_traits>
 
 // Timing-attribution builds (lab build only: tools/ablate.sh passes -DSS_LAB=1 -DSS_ABLATE=<bits>): each bit removes one
@@ -347,6 +350,53 @@ __device__ __forceinline__ float2 pcm_pair(int w, float scale)
     return make_float2(static_cast<float>(static_cast<int16_t>(w)) * scale, static_cast<float>(w >> 16) * scale);
 }
 
+// The raw dword of a PCM sample pair: two int16, fetched by one 32-bit load at 2-byte alignment (a pair may start at an odd sample:
+// odd ld, odd base, odd clip offset).  gfx950 global loads take any alignment in the unaligned access mode the HSA ABI sets -- the
+// mode the float builds' 8-byte pair loads at dword alignment already rely on -- so one load serves either parity.
+__device__ __forceinline__ float pcm_raw_pair(const void *p)
+{
+    int w;
+    __builtin_memcpy(&w, __builtin_assume_aligned(p, 2), sizeof w);
+    return __int_as_float(w);
+}
+
+// PCM builds (a trailing BatchPcmArgs): load_quad's contract framing with the samples as signed 16-bit PCM.  The loader only
+// fetches: a pair's dword stays, as raw bits, in vin[e].x until the quad is consumed (pcm_pair) -- as in the STRPI builds, converting
+// here would wait for the loads right behind pass 1.  An odd frame length's half pair is one zero-extended 16-bit load: its high
+// half converts to the zero the float loader pads with.
+template <int NE, bool EXACT>
+__device__ __forceinline__ unsigned load_quad_pcm(const Fast512Args &a, const int16_t *x, unsigned quad, unsigned total, int f, int j,
+                                                  float2 (&vin)[NE])
+{
+    const unsigned q4 = quad * 4;                                       // uniform
+    const unsigned fl = min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last frame redo it
+    unsigned clip, t;
+    if (a.nf_magic) {
+        clip = __umulhi(q4, a.nf_magic) >> a.nf_shift;
+        t = q4 - clip * a.n_frames + fl;
+        const bool wrap = t >= a.n_frames;
+        t -= wrap ? a.n_frames : 0u;
+        clip += wrap ? 1u : 0u;
+    } else {
+        const unsigned gf = q4 + fl;
+        clip = gf / a.n_frames;
+        t = gf - clip * a.n_frames;
+    }
+    const int16_t *src = x + static_cast<unsigned long long>(clip) * a.ld + t * a.step;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int n = j + 16 * e;
+        if (EXACT) {
+            vin[e] = make_float2(pcm_raw_pair(src + 2 * n), 0.f);
+        } else {
+            const int rem = static_cast<int>(a.flen) - 2 * n;
+            vin[e] = make_float2(rem >= 2 ? pcm_raw_pair(src + 2 * n)
+                                          : __int_as_float(rem == 1 ? static_cast<int>(static_cast<uint16_t>(src[2 * n])) : 0), 0.f);
+        }
+    }
+    return t;
+}
+
 // Contract framing only: where this lane's frame of `quad` starts (frame t of its clip begins at sample t * step), and t.
 // `quad` is uniform: the clip / frame split of the quad's first frame, the clip's address and the frame's offset in it are scalar
 // work, and what a lane adds is a 32-bit byte offset (its frame within the quad, its sample pair, one conditional step into the
@@ -355,8 +405,11 @@ struct QuadSrc {
     const char *base;  // uniform
     unsigned off;      // this lane's byte offset
 };
-__device__ __forceinline__ QuadSrc quad_src(const Fast512Args &a, unsigned quad, unsigned total, int f, int j, unsigned &t_out)
+// (x: the batch's samples, floats or 16-bit PCM -- the byte offsets scale with the sample size)
+template <typename T>
+__device__ __forceinline__ QuadSrc quad_src_of(const Fast512Args &a, const T *x, unsigned quad, unsigned total, int f, int j, unsigned &t_out)
 {
+    constexpr unsigned SB = sizeof(T);
     const unsigned q4 = quad * 4;
     const unsigned fl = min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last frame redo it
     if (a.nf_magic) {
@@ -366,10 +419,10 @@ __device__ __forceinline__ QuadSrc quad_src(const Fast512Args &a, unsigned quad,
         const bool wrap = traw >= a.n_frames;
         t_out = min(traw, traw - a.n_frames);  // (unsigned: the difference is huge unless the frame belongs to the next clip)
         // a step into the next clip: + ld samples, - n_frames * step of them
-        const unsigned into_next = (static_cast<unsigned>(a.ld) - a.n_frames * a.step) * 4u;
+        const unsigned into_next = (static_cast<unsigned>(a.ld) - a.n_frames * a.step) * SB;
         QuadSrc r;
-        r.base = reinterpret_cast<const char *>(a.x + static_cast<unsigned long long>(clip) * a.ld + static_cast<unsigned long long>(t0) * a.step);
-        r.off = __umul24(fl, a.step * 4u) + static_cast<unsigned>(j) * 8u + (wrap ? into_next : 0u);
+        r.base = reinterpret_cast<const char *>(x + static_cast<unsigned long long>(clip) * a.ld + static_cast<unsigned long long>(t0) * a.step);
+        r.off = __umul24(fl, a.step * SB) + static_cast<unsigned>(j) * (2u * SB) + (wrap ? into_next : 0u);
         return r;
     }
     // clips of fewer than four frames (no reciprocal: a quad may span several clips): the lane's offset from the first clip's first
@@ -379,9 +432,13 @@ __device__ __forceinline__ QuadSrc quad_src(const Fast512Args &a, unsigned quad,
     const unsigned t = gf - clip * a.n_frames;
     t_out = t;
     QuadSrc r;
-    r.base = reinterpret_cast<const char *>(a.x);
-    r.off = (clip * static_cast<unsigned>(a.ld) + t * a.step) * 4u + static_cast<unsigned>(j) * 8u;
+    r.base = reinterpret_cast<const char *>(x);
+    r.off = (clip * static_cast<unsigned>(a.ld) + t * a.step) * SB + static_cast<unsigned>(j) * (2u * SB);
     return r;
+}
+__device__ __forceinline__ QuadSrc quad_src(const Fast512Args &a, unsigned quad, unsigned total, int f, int j, unsigned &t_out)
+{
+    return quad_src_of(a, a.x, quad, total, f, j, t_out);
 }
 
 // VAR builds (ss_mfcc_packed_device): the frame of `quad` this lane computes is output row q4 + f of a packed launch.  `cursor` is the
@@ -394,8 +451,10 @@ struct VarFrame {
     float sk, s00;  // dct_scale_k / dct_scale_00 of the frame's clip
     int ok;
 };
-__device__ __forceinline__ const char *var_src(const Fast512Args &a, const VarlenArgs &v, unsigned quad, unsigned total, int f,
-                                               unsigned &cursor, unsigned &t_out, VarFrame &vf)
+// (x: the packed samples, floats or 16-bit PCM)
+template <typename T>
+__device__ __forceinline__ const char *var_src_of(const Fast512Args &a, const T *x, const VarlenArgs &v, unsigned quad, unsigned total, int f,
+                                                  unsigned &cursor, unsigned &t_out, VarFrame &vf)
 {
     const unsigned q4 = quad * 4;                                        // uniform
     const unsigned g = q4 + min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last row redo it
@@ -409,7 +468,12 @@ __device__ __forceinline__ const char *var_src(const Fast512Args &a, const Varle
     t_out = vf.ok ? static_cast<unsigned>(tl) : 0u;
     varlen_dct_scales(v, cl.T, a.n_filters, vf.sk, vf.s00);
     // (a lane that stores nothing reads the buffer's first frame)
-    return reinterpret_cast<const char *>(a.x + (vf.ok ? cl.s0 + static_cast<long long>(t_out) * a.step : 0ll));
+    return reinterpret_cast<const char *>(x + (vf.ok ? cl.s0 + static_cast<long long>(t_out) * a.step : 0ll));
+}
+__device__ __forceinline__ const char *var_src(const Fast512Args &a, const VarlenArgs &v, unsigned quad, unsigned total, int f,
+                                               unsigned &cursor, unsigned &t_out, VarFrame &vf)
+{
+    return var_src_of(a, a.x, v, quad, total, f, cursor, t_out, vf);
 }
 
 // One mel slot with a compile-time tap count (multiple of 4): weights and P taps are all requested before
@@ -484,6 +548,9 @@ __device__ __forceinline__ float mel_slot_loop(const float4 *w4, const float *p,
 // ragged streaming call (load_quad_stream_packed), otherwise as STRM.
 // STRPI builds (ss_mfcc_stream_packed_i16_device): a trailing FrameStreamPackedPcmArgs; STRP with its entry block and the chunks read
 // as 16-bit PCM (load_quad_stream_packed_pcm fetches, pcm_pair converts where vin[] is consumed) -- from v[] on the code is STRP's.
+// PCM builds (ss_mfcc_batch_i16_device / ss_mfe_batch_i16_device / ss_mfcc_packed_i16_device): a trailing BatchPcmArgs, alone or behind
+// VAR's VarlenArgs; the samples are signed 16-bit PCM (load_quad_pcm / pcm_raw_pair fetch, pcm_pair converts where vin[] is
+// consumed) -- from v[] on the code is the float build's.  Contract framing, no fused pre-emphasis.
 template <int NE, bool EXACT, bool POW2, int WAVES, bool BANK421, int NQ, int RES = 0, int OUTK = 0, int FRONT = 0, bool FULLP = false,
           bool CENTER = false, bool MULTI = false, bool VAR = false, typename... SP>
 __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_in, const std::conditional_t<VAR, VarlenArgs, MultiArg<MULTI>> mt,
@@ -496,6 +563,10 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     constexpr bool STRP = STRPI || (std::is_same_v<SP, FrameStreamPackedArgs> || ...);
     [[maybe_unused]] const FrameStreamPackedArgs *fp = pack_arg<FrameStreamPackedArgs>(sp...);
     if constexpr (STRPI) fp = &fpi->e;
+    constexpr bool PCM = (std::is_same_v<SP, BatchPcmArgs> || ...);
+    [[maybe_unused]] const BatchPcmArgs *pc = pack_arg<BatchPcmArgs>(sp...);
+    static_assert(!PCM || (!CENTER && !MULTI && !FULLP && OUTK != 2 && (FRONT & 2) == 0),
+                  "the PCM builds exist for contract framing without fused pre-emphasis, MFCC / mfe output");
     // Everything in front of a wave's first sample loads is start-up latency of the launch (nothing can be computed before
     // the samples are here), so the kernel arguments that lead to those loads are fetched by ONE batch of scalar loads at the
     // very top (pinned: left alone, the compiler fetches them where they are first used -- three dependent scalar-memory
@@ -580,7 +651,13 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
     [[maybe_unused]] unsigned cursor = 0;  // VAR: the wave's clip cursor ...
     [[maybe_unused]] VarFrame vnext{};     // ... and the clip data of the frame whose samples are in vin (STRP: its ok alone)
     [[maybe_unused]] int s0_next = kNoPcm;  // STRPI: that frame's first sample relative to its chunk (which pairs of vin are raw PCM)
-    if constexpr (VAR) {
+    if constexpr (VAR && PCM) {
+        const char *p = var_src_of(a, pc->x, mt, min(quad, q_hi - 1), total, f, cursor, t_next, vnext);
+#pragma unroll
+        for (int e = 0; e < NE; ++e) vin[e] = make_float2(pcm_raw_pair(p + 4 * (j + 16 * e)), 0.f);
+    } else if constexpr (PCM) {
+        t_next = load_quad_pcm<NE, EXACT>(a, pc->x, min(quad, q_hi - 1), total, f, j, vin);
+    } else if constexpr (VAR) {
         const char *p = var_src(a, mt, min(quad, q_hi - 1), total, f, cursor, t_next, vnext);
 #pragma unroll
         for (int e = 0; e < NE; ++e) vin[e] = *reinterpret_cast<const float2 *>(p + 8 * (j + 16 * e));
@@ -734,6 +811,9 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             if constexpr (STRPI) {
                 if (e < NE && s0_cur + 2 * (j + 16 * e) >= 0) s = pcm_pair(__float_as_int(s.x), fpi->scale);
             }
+            if constexpr (PCM) {
+                if (e < NE) s = pcm_pair(__float_as_int(s.x), pc->scale);
+            }
             if (PRE && e < NE) s = make_float2(fmaf(-a.preemph, pin[e].x, s.x), fmaf(-a.preemph, pin[e].y, s.y));
             if (WIN && e < NE) {
                 const float2 w = s_win[j + 16 * e];
@@ -765,7 +845,9 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         static_assert(!(STRM || STRP) || (EXACT && !PRE && !CENTER && !MULTI && !VAR && OUTK != 2 && (FRONT & 1) == 0),
                       "the streaming builds exist for the default frame shape's MFCC / mfe without window or pre-emphasis");
         QuadSrc nsrc{nullptr, 0u};
-        if constexpr (VAR) {
+        if constexpr (VAR && PCM) {
+            nsrc.base = var_src_of(a, pc->x, mt, min(next, q_hi - 1), total, f, cursor, t_next, vnext) + 4 * j;
+        } else if constexpr (VAR) {
             nsrc.base = var_src(a, mt, min(next, q_hi - 1), total, f, cursor, t_next, vnext) + 8 * j;
         } else if constexpr (MULTI) {
             const unsigned nq = min(next, q_hi - 1);
@@ -775,7 +857,11 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             }
             nsrc = quad_src(an, nq - ns.u0, ns.total, f, j, t_next);
         } else {
-            if (SPREAD) nsrc = quad_src(a, min(next, q_hi - 1), total, f, j, t_next);
+            if constexpr (PCM) {
+                if (SPREAD) nsrc = quad_src_of(a, pc->x, min(next, q_hi - 1), total, f, j, t_next);
+            } else {
+                if (SPREAD) nsrc = quad_src(a, min(next, q_hi - 1), total, f, j, t_next);
+            }
         }
         if constexpr (STRM) {
             // (the whole quad's loads as one burst behind pass 1: the edge branch's address selects do not split into the twiddle steps)
@@ -785,7 +871,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
         } else if constexpr (STRP) {
             if (next < q_hi) t_next = load_quad_stream_packed<NE>(a, *fp, next, total, f, j, vin, vnext.ok);
         } else if (!SPREAD && PREFETCH && next < q_hi && !(SS_ABLATE & 16)) {
-            t_next = load_quad<NE, EXACT, PRE, CENTER>(a, next, total, f, j, vin, pin);
+            if constexpr (PCM) t_next = load_quad_pcm<NE, EXACT>(a, pc->x, next, total, f, j, vin);
+            else t_next = load_quad<NE, EXACT, PRE, CENTER>(a, next, total, f, j, vin, pin);
         }
         float2 u[16];
 #pragma unroll
@@ -807,7 +894,14 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
             const float4 w2 = (RES & 2) ? tw2r[p] : s_tw2[p * 16 + cj];
             u[2 * p + 1] = cmul(u[2 * p + 1], make_float2(w2.x, w2.y));
             if (p < 7) u[2 * p + 2] = cmul(u[2 * p + 2], make_float2(w2.z, w2.w));
-            if (SPREAD) {
+            if constexpr (SPREAD && PCM) {  // (a pair is 4 bytes: the loads are 64 bytes apart)
+                if (p < NE) vin[p] = make_float2(pcm_raw_pair(nsrc.base + nsrc.off + 64 * p), 0.f);
+                if (p == 7) {
+#pragma unroll
+                    for (int e = 8; e < NE; ++e) vin[e] = make_float2(pcm_raw_pair(nsrc.base + nsrc.off + 64 * e), 0.f);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            } else if (SPREAD) {
                 if (p < NE) vin[p] = *reinterpret_cast<const float2 *>(nsrc.base + nsrc.off + 128 * p);
                 if (p == 7) {
 #pragma unroll
@@ -1090,9 +1184,35 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256(const Fast512Args a_i
 
 constexpr int NE13RES = 4;  // resident-table set of the 13-input default-bank build (symmetric DCT; the twiddles would spill)
 
-template <int WAVES>
-hipError_t launch_w(const Fast512Args &a_in, hipStream_t stream, int num_cus, LaunchInfo *info)
+// What ss_last_kernel_name() reports for a PCM build: the float build's name with `tag` behind "ss_mfcc_c256" (built once per name,
+// kept for the process).
+const char *pcm_kernel_name(const char *name, const char *tag)
 {
+    static std::mutex mu;
+    static std::map<std::string, std::string> names;
+    std::lock_guard<std::mutex> lock(mu);
+    std::string &n = names[name];
+    if (n.empty()) n = std::string("ss_mfcc_c256") + tag + (name + sizeof("ss_mfcc_c256") - 1);
+    return n.c_str();
+}
+
+// the kernel build of a launch: the one-shot template arguments, then the launch's trailing argument pack (none: the float builds)
+template <typename... SP>
+struct C256 {
+    template <int NE, bool EXACT, bool POW2, int WAVES, bool BANK421, int NQ, int RES = 0, int OUTK = 0, int FRONT = 0>
+    static constexpr auto kern()
+    {
+        return ss_mfcc_c256<NE, EXACT, POW2, WAVES, BANK421, NQ, RES, OUTK, FRONT, false, false, false, false, SP...>;
+    }
+};
+
+// sp: empty (float samples at a.x) or one BatchPcmArgs (the PCM builds: contract framing, no fused pre-emphasis, MFCC / mfe)
+template <int WAVES, typename... SP>
+hipError_t launch_w(const Fast512Args &a_in, hipStream_t stream, int num_cus, LaunchInfo *info, const SP &...sp)
+{
+    constexpr bool PCM = sizeof...(SP) != 0;
+    using K = C256<SP...>;
+    if (PCM && (a_in.fullp || a_in.center || a_in.preemph != 0.0f || a_in.out_mfe == 2)) return hipErrorInvalidValue;
     Fast512Args a = a_in;
     a.nf_magic = 0;
     a.nf_shift = 0;
@@ -1137,8 +1257,8 @@ hipError_t launch_w(const Fast512Args &a_in, hipStream_t stream, int num_cus, La
                                                static_cast<int>(lds));
             if (e != hipSuccess) return e;
         }
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{});
+        if (info) *info = LaunchInfo{PCM ? pcm_kernel_name(name, "i") : name, grid, static_cast<unsigned>(WAVES * 64), lds};
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{}, sp...);
         return hipGetLastError();
     };
     const bool pow2 = a.spectrum_exponent == 2;
@@ -1146,7 +1266,7 @@ hipError_t launch_w(const Fast512Args &a_in, hipStream_t stream, int num_cus, La
     if (a.fullp || a.center) {
         // librosa-compatible variants: P rows of all 257 bins (banks that cover the whole spectrum) and / or centred frames;
         // MFCC output, optional frame window, no fused pre-emphasis
-        if constexpr (WAVES != 12) {
+        if constexpr (WAVES != 12 || PCM) {
             return hipErrorInvalidValue;
         } else {
             if (a.out_mfe || a.preemph != 0.0f) return hipErrorInvalidValue;
@@ -1177,51 +1297,57 @@ hipError_t launch_w(const Fast512Args &a_in, hipStream_t stream, int num_cus, La
 #endif
     if (a.flen == 320 && !pow2 && b421 && a.n_filters <= 40) {
         const int front = (a.win_floats > 0 ? 1 : 0) | (a.preemph != 0.0f ? 2 : 0);
-        if (a.out_mfe == 2) {
-            if (front || WAVES > 12) return hipErrorInvalidValue;
-            return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 2>, "ss_mfcc_c256<10,exact,power>");
+        if constexpr (!PCM) {
+            if (a.out_mfe == 2) {
+                if (front || WAVES > 12) return hipErrorInvalidValue;
+                return go(K::template kern<10, true, false, WAVES, true, 10, 2, 2>(), "ss_mfcc_c256<10,exact,power>");
+            }
         }
         if (front) {
             if (WAVES > 12) return hipErrorInvalidValue;
             if (a.out_mfe) {
-                if (front == 1) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 1>, "ss_mfcc_c256<10,exact,bank421,mfe,win>");
-                if (front == 2) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 0, 1, 2>, "ss_mfcc_c256<10,exact,bank421,mfe,pre>");
-                return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 0, 1, 3>, "ss_mfcc_c256<10,exact,bank421,mfe,win,pre>");
+                if (front == 1) return go(K::template kern<10, true, false, WAVES, true, 10, 2, 1, 1>(), "ss_mfcc_c256<10,exact,bank421,mfe,win>");
+                if constexpr (!PCM) {
+                    if (front == 2) return go(K::template kern<10, true, false, WAVES, true, 10, 0, 1, 2>(), "ss_mfcc_c256<10,exact,bank421,mfe,pre>");
+                    return go(K::template kern<10, true, false, WAVES, true, 10, 0, 1, 3>(), "ss_mfcc_c256<10,exact,bank421,mfe,win,pre>");
+                }
             }
-            if (front == 1) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 0, 1>, "ss_mfcc_c256<10,exact,bank421,win>");
-            if (front == 2) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 0, 2>, "ss_mfcc_c256<10,exact,bank421,pre>");
-            return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 0, 3>, "ss_mfcc_c256<10,exact,bank421,win,pre>");
+            if (front == 1) return go(K::template kern<10, true, false, WAVES, true, 10, 2, 0, 1>(), "ss_mfcc_c256<10,exact,bank421,win>");
+            if constexpr (!PCM) {
+                if (front == 2) return go(K::template kern<10, true, false, WAVES, true, 10, 2, 0, 2>(), "ss_mfcc_c256<10,exact,bank421,pre>");
+                return go(K::template kern<10, true, false, WAVES, true, 10, 2, 0, 3>(), "ss_mfcc_c256<10,exact,bank421,win,pre>");
+            }
         }
-        if (a.out_mfe) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1>, "ss_mfcc_c256<10,exact,bank421,mfe>");
+        if (a.out_mfe) return go(K::template kern<10, true, false, WAVES, true, 10, 2, 1>(), "ss_mfcc_c256<10,exact,bank421,mfe>");
         if (res == 6 && a.n_filters == 40 && a.paired == 2 && WAVES <= 12)
-            return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30>, "ss_mfcc_c256<10,exact,bank421,sym>");
+            return go(K::template kern<10, true, false, WAVES, true, 10, 30>(), "ss_mfcc_c256<10,exact,bank421,sym>");
         if (res == 6 && a.n_filters == 40 && a.paired && WAVES <= 12)
-            return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 14>, "ss_mfcc_c256<10,exact,bank421,sym,taps84>");
+            return go(K::template kern<10, true, false, WAVES, true, 10, 14>(), "ss_mfcc_c256<10,exact,bank421,sym,taps84>");
         if (res == 6 && a.n_filters == 40)
-            return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, WAVES <= 12 ? 6 : 4>, WAVES <= 12 ? "ss_mfcc_c256<10,exact,bank421,symrow>" : "ss_mfcc_c256<10,exact,bank421,sym,w16>");
+            return go(K::template kern<10, true, false, WAVES, true, 10, WAVES <= 12 ? 6 : 4>(), WAVES <= 12 ? "ss_mfcc_c256<10,exact,bank421,symrow>" : "ss_mfcc_c256<10,exact,bank421,sym,w16>");
         if (res == 6) res = 2;  // the symmetric DCT is written for exactly 40 filters
-        if (WAVES <= 12 && res == 1) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 1>, "ss_mfcc_c256<10,exact,bank421,res1>");
-        if (WAVES <= 12 && res == 2) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2>, "ss_mfcc_c256<10,exact,bank421,res2>");
-        if (WAVES <= 12 && res == 3) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 3>, "ss_mfcc_c256<10,exact,bank421,res3>");
-        return go(ss_mfcc_c256<10, true, false, WAVES, true, 10>, "ss_mfcc_c256<10,exact,bank421>");
+        if (WAVES <= 12 && res == 1) return go(K::template kern<10, true, false, WAVES, true, 10, 1>(), "ss_mfcc_c256<10,exact,bank421,res1>");
+        if (WAVES <= 12 && res == 2) return go(K::template kern<10, true, false, WAVES, true, 10, 2>(), "ss_mfcc_c256<10,exact,bank421,res2>");
+        if (WAVES <= 12 && res == 3) return go(K::template kern<10, true, false, WAVES, true, 10, 3>(), "ss_mfcc_c256<10,exact,bank421,res3>");
+        return go(K::template kern<10, true, false, WAVES, true, 10>(), "ss_mfcc_c256<10,exact,bank421>");
     }
     if (a.flen == 320) {
-        return pow2 ? go(ss_mfcc_c256<10, true, true, WAVES, false, 12>, "ss_mfcc_c256<10,exact,pow2>")
-                    : go(ss_mfcc_c256<10, true, false, WAVES, false, 12>, "ss_mfcc_c256<10,exact>");
+        return pow2 ? go(K::template kern<10, true, true, WAVES, false, 12>(), "ss_mfcc_c256<10,exact,pow2>")
+                    : go(K::template kern<10, true, false, WAVES, false, 12>(), "ss_mfcc_c256<10,exact>");
     }
     if (a.flen <= 320) {
-        return pow2 ? go(ss_mfcc_c256<10, false, true, WAVES, false, 12>, "ss_mfcc_c256<10,pow2>")
-                    : go(ss_mfcc_c256<10, false, false, WAVES, false, 12>, "ss_mfcc_c256<10>");
+        return pow2 ? go(K::template kern<10, false, true, WAVES, false, 12>(), "ss_mfcc_c256<10,pow2>")
+                    : go(K::template kern<10, false, false, WAVES, false, 12>(), "ss_mfcc_c256<10>");
     }
     if (a.flen <= 416) {  // 25 ms at 16 kHz (400 samples): 13 of the 16 first-pass inputs
         // the bank does not depend on the frame length: the default bank keeps its fixed tap counts and symmetric DCT
         if (!pow2 && b421 && a.n_filters == 40 && WAVES <= 12 && !a.out_mfe && a.win_floats == 0 && a.preemph == 0.0f)
-            return go(ss_mfcc_c256<13, false, false, WAVES, true, 10, NE13RES>, "ss_mfcc_c256<13,bank421,sym>");
-        return pow2 ? go(ss_mfcc_c256<13, false, true, WAVES, false, 12>, "ss_mfcc_c256<13,pow2>")
-                    : go(ss_mfcc_c256<13, false, false, WAVES, false, 12>, "ss_mfcc_c256<13>");
+            return go(K::template kern<13, false, false, WAVES, true, 10, NE13RES>(), "ss_mfcc_c256<13,bank421,sym>");
+        return pow2 ? go(K::template kern<13, false, true, WAVES, false, 12>(), "ss_mfcc_c256<13,pow2>")
+                    : go(K::template kern<13, false, false, WAVES, false, 12>(), "ss_mfcc_c256<13>");
     }
-    return pow2 ? go(ss_mfcc_c256<16, false, true, WAVES, false, 12>, "ss_mfcc_c256<16,pow2>")
-                : go(ss_mfcc_c256<16, false, false, WAVES, false, 12>, "ss_mfcc_c256<16>");
+    return pow2 ? go(K::template kern<16, false, true, WAVES, false, 12>(), "ss_mfcc_c256<16,pow2>")
+                : go(K::template kern<16, false, false, WAVES, false, 12>(), "ss_mfcc_c256<16>");
 }
 
 }  // namespace
@@ -1286,7 +1412,10 @@ hipError_t launch_mfcc_c256_multi(const Fast512Args &a_in, int n_batches, const 
     return hipGetLastError();
 }
 
-hipError_t launch_mfcc_c256_varlen(const Fast512Args &a_in, const VarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+// the packed launch for either sample format: sp = empty (floats at a.x) or one BatchPcmArgs
+template <typename... SP>
+static hipError_t launch_varlen_w12(const Fast512Args &a_in, const VarlenArgs &v, const char *name, hipStream_t stream, int num_cus,
+                                    LaunchInfo *info, const SP &...sp)
 {
     constexpr int WAVES = 12;
     Fast512Args a = a_in;
@@ -1307,14 +1436,25 @@ hipError_t launch_mfcc_c256_varlen(const Fast512Args &a_in, const VarlenArgs &v,
     const unsigned grid = static_cast<unsigned>(blocks);
     a.q_base = static_cast<uint32_t>(quads / grid);
     a.q_rem = static_cast<uint32_t>(quads % grid);
-    auto kern = ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, true>;
+    auto kern = ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, true, SP...>;
     if (lds > 48 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
         if (e != hipSuccess) return e;
     }
-    if (info) *info = LaunchInfo{"ss_mfcc_c256v<10,exact,bank421,sym>", grid, static_cast<unsigned>(WAVES * 64), lds};
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, v);
+    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, v, sp...);
     return hipGetLastError();
+}
+
+hipError_t launch_mfcc_c256_varlen(const Fast512Args &a, const VarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    return launch_varlen_w12(a, v, "ss_mfcc_c256v<10,exact,bank421,sym>", stream, num_cus, info);
+}
+
+hipError_t launch_mfcc_c256_varlen(const Fast512Args &a, const VarlenPcmArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    if (!v.x) return hipErrorInvalidValue;
+    return launch_varlen_w12(a, v.v, "ss_mfcc_c256vi<10,exact,bank421,sym>", stream, num_cus, info, BatchPcmArgs{v.x, v.scale});
 }
 
 hipError_t launch_mfcc_c256_stream(const Fast512Args &a_in, const FrameStreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
@@ -1445,6 +1585,13 @@ hipError_t launch_mfcc_c256(const Fast512Args &a, hipStream_t stream, int num_cu
     if (w && std::atoi(w) == 9 && !a.fullp && !a.center) return launch_w<9>(a, stream, num_cus, info);
 #endif
     return launch_w<12>(a, stream, num_cus, info);
+}
+
+hipError_t launch_mfcc_c256(const Fast512Args &a, const BatchPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    if (!p.x) return hipErrorInvalidValue;
+    if ((a.out_mfe || a.win_floats > 0) && !mfcc_c256_has_mfe(a)) return hipErrorInvalidValue;  // as the float launch
+    return launch_w<12>(a, stream, num_cus, info, p);
 }
 
 }  // namespace ss

@@ -91,6 +91,22 @@ extern "C" {
                                  pool_streams: usize, scale: f32, norm_frames: u32, pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_mfe_stream_packed_i16(cfg: *const SsConfig, x: *const i16, n_active: usize, sample_offsets: *const i64, slots: *const i32,
                                 pool_streams: usize, scale: f32, pool: *mut f32, feat: *mut f32, energy: *mut f32) -> c_int;
+    fn ss_mfcc_batch_i16_device(cfg: *const SsConfig, d_x: *const i16, batch: usize, n: usize, ld: usize, scale: f32, d_out: *mut f32,
+                                stream: *mut c_void) -> c_int;
+    fn ss_mfe_batch_i16_device(cfg: *const SsConfig, d_x: *const i16, batch: usize, n: usize, ld: usize, scale: f32, d_feat: *mut f32,
+                               d_energy: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_mfcc_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64, scale: f32,
+                                 d_frame_offsets: *const i64, total_frames: usize, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_mfe_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64, scale: f32,
+                                d_frame_offsets: *const i64, total_frames: usize, d_feat: *mut f32, d_energy: *mut f32,
+                                stream: *mut c_void) -> c_int;
+    fn ss_mfcc_batch_i16(cfg: *const SsConfig, x: *const i16, batch: usize, n: usize, ld: usize, scale: f32, out: *mut f32) -> c_int;
+    fn ss_mfe_batch_i16(cfg: *const SsConfig, x: *const i16, batch: usize, n: usize, ld: usize, scale: f32, feat: *mut f32,
+                        energy: *mut f32) -> c_int;
+    fn ss_mfcc_packed_i16(cfg: *const SsConfig, x: *const i16, n_clips: usize, sample_offsets: *const i64, scale: f32,
+                          out: *mut f32) -> c_int;
+    fn ss_mfe_packed_i16(cfg: *const SsConfig, x: *const i16, n_clips: usize, sample_offsets: *const i64, scale: f32, feat: *mut f32,
+                         energy: *mut f32) -> c_int;
     fn ss_preemphasis(x: *const f32, n: usize, shift: c_long, cof: f32, y: *mut f32) -> c_int;
     fn ss_frame_sizes(p: *const SsParams, frame_len: *mut usize, frame_step: *mut usize) -> c_int;
     fn ss_stft(cfg: *const SsConfig, x: *const f32, channels: usize, n: usize, out: *mut f32) -> c_int;
@@ -437,6 +453,81 @@ pub fn try_mfe_stream_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: 
     }
     check(unsafe { ss_mfe_stream_packed_i16(cfg.raw(), x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams,
                                             scale, pool.as_mut_ptr(), feat.as_mut_ptr(), energy.as_mut_ptr()) })
+}
+
+/// The one-shot MFCC of equal-length clips fed signed 16-bit PCM (`ss_mfcc_batch_i16_device`): `mfcc_batch_device` with the samples as
+/// int16, sample = `pcm as f32 * scale`, `scale` a power of two in `[2^-64, 2^64]`; bit for bit the float call on the converted
+/// buffer.  `ld` is in samples; `d_x` needs 2-byte alignment only.
+/// # Safety
+/// As `mfcc_batch_device`.
+pub unsafe fn mfcc_batch_i16_device(cfg: &SpeechConfig, d_x: *const i16, batch: usize, n: usize, ld: usize, scale: f32, d_out: *mut f32,
+                                    stream: *mut c_void) -> Result<(), Error> {
+    check(ss_mfcc_batch_i16_device(cfg.raw(), d_x, batch, n, ld, scale, d_out, stream))
+}
+
+/// The mfe form of `mfcc_batch_i16_device`: `d_feat` `[batch x frames x num_filters]`, `d_energy` `[batch x frames]`.
+/// # Safety
+/// As `mfcc_batch_device`.
+pub unsafe fn mfe_batch_i16_device(cfg: &SpeechConfig, d_x: *const i16, batch: usize, n: usize, ld: usize, scale: f32, d_feat: *mut f32,
+                                   d_energy: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_mfe_batch_i16_device(cfg.raw(), d_x, batch, n, ld, scale, d_feat, d_energy, stream))
+}
+
+/// MFCC of packed variable-length clips fed signed 16-bit PCM (`ss_mfcc_packed_i16_device`): clip `b` is
+/// `d_x[so[b]..so[b + 1]]`, its rows `fo[b]..fo[b + 1]` of `d_out`; the tables are device arrays, offsets in samples.
+/// # Safety
+/// Every pointer is a device allocation of the size the header states, on the device the config was created on.
+pub unsafe fn mfcc_packed_i16_device(cfg: &SpeechConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64, scale: f32,
+                                     d_frame_offsets: *const i64, total_frames: usize, d_out: *mut f32, stream: *mut c_void)
+                                     -> Result<(), Error> {
+    check(ss_mfcc_packed_i16_device(cfg.raw(), d_x, n_clips, d_sample_offsets, scale, d_frame_offsets, total_frames, d_out, stream))
+}
+
+/// The mfe form of `mfcc_packed_i16_device`.
+/// # Safety
+/// As `mfcc_packed_i16_device`.
+pub unsafe fn mfe_packed_i16_device(cfg: &SpeechConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64, scale: f32,
+                                    d_frame_offsets: *const i64, total_frames: usize, d_feat: *mut f32, d_energy: *mut f32,
+                                    stream: *mut c_void) -> Result<(), Error> {
+    check(ss_mfe_packed_i16_device(cfg.raw(), d_x, n_clips, d_sample_offsets, scale, d_frame_offsets, total_frames, d_feat, d_energy,
+                                   stream))
+}
+
+/// Host-pointer forms: the samples cross the link as int16.  `x` holds `batch` rows of `n` samples at row stride `ld`; `out` is
+/// `[batch x frames x num_cepstral]`.  Synchronous.
+pub fn try_mfcc_batch_i16(cfg: &SpeechConfig, x: &[i16], batch: usize, n: usize, ld: usize, scale: f32, out: &mut [f32])
+                          -> Result<(), Error> {
+    if batch > 0 && (ld < n || x.len() < (batch - 1) * ld + n) {
+        return Err(Error { status: SS_ERR_ARG, detail: "x is shorter than batch rows of n samples at stride ld".to_string() });
+    }
+    check(unsafe { ss_mfcc_batch_i16(cfg.raw(), x.as_ptr(), batch, n, ld, scale, out.as_mut_ptr()) })
+}
+
+/// The mfe form of `try_mfcc_batch_i16`: `feat` `[batch x frames x num_filters]`, `energy` `[batch x frames]`.
+pub fn try_mfe_batch_i16(cfg: &SpeechConfig, x: &[i16], batch: usize, n: usize, ld: usize, scale: f32, feat: &mut [f32],
+                         energy: &mut [f32]) -> Result<(), Error> {
+    if batch > 0 && (ld < n || x.len() < (batch - 1) * ld + n) {
+        return Err(Error { status: SS_ERR_ARG, detail: "x is shorter than batch rows of n samples at stride ld".to_string() });
+    }
+    check(unsafe { ss_mfe_batch_i16(cfg.raw(), x.as_ptr(), batch, n, ld, scale, feat.as_mut_ptr(), energy.as_mut_ptr()) })
+}
+
+/// Packed clips from an int16 host buffer: `sample_offsets` holds `n_clips + 1` offsets in samples, `out` the clips' rows end to end.
+pub fn try_mfcc_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64], scale: f32, out: &mut [f32]) -> Result<(), Error> {
+    if sample_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have n_clips + 1 entries".to_string() });
+    }
+    check(unsafe { ss_mfcc_packed_i16(cfg.raw(), x.as_ptr(), sample_offsets.len() - 1, sample_offsets.as_ptr(), scale, out.as_mut_ptr()) })
+}
+
+/// The mfe form of `try_mfcc_packed_i16`.
+pub fn try_mfe_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64], scale: f32, feat: &mut [f32], energy: &mut [f32])
+                          -> Result<(), Error> {
+    if sample_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have n_clips + 1 entries".to_string() });
+    }
+    check(unsafe { ss_mfe_packed_i16(cfg.raw(), x.as_ptr(), sample_offsets.len() - 1, sample_offsets.as_ptr(), scale, feat.as_mut_ptr(),
+                                     energy.as_mut_ptr()) })
 }
 
 /// functions.rs:86-123: `[channels, samples]` -> `Array3<Complex32>` `[channels, rows, freq_size]`

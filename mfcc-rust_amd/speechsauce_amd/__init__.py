@@ -138,23 +138,23 @@ def _require_f32(signal, ndims: tuple[int, ...], what: str):
     return arr
 
 
-def _require_i16(signal, what: str):
-    """The PCM forms (``pcm_scale=``) take 1-D int16 only: no silent casts."""
+def _require_i16(signal, what: str, ndims: tuple[int, ...] = (1,)):
+    """The PCM forms (``pcm_scale=``) take int16 only, of the dimensions the call takes: no silent casts."""
     if _is_torch(signal):
         import torch
 
         if signal.dtype != torch.int16:
             raise TypeError(f"{what}: with pcm_scale the signal must be int16, got {signal.dtype}")
-        if signal.dim() != 1:
-            raise ValueError(f"{what}: Input signal must be 1d")
+        if signal.dim() not in ndims:
+            raise ValueError(f"{what}: Input signal must be {' or '.join(str(d) + 'd' for d in ndims)}")
         if not signal.is_cuda:
             signal = signal.detach().numpy()
         return signal
     arr = np.asarray(signal)
     if arr.dtype != np.int16:
         raise TypeError(f"{what}: with pcm_scale the signal must be int16, got {arr.dtype}")
-    if arr.ndim != 1:
-        raise ValueError(f"{what}: Input signal must be 1d")
+    if arr.ndim not in ndims:
+        raise ValueError(f"{what}: Input signal must be {' or '.join(str(d) + 'd' for d in ndims)}")
     return arr
 
 
@@ -168,6 +168,14 @@ def _check_pcm_scale(pcm_scale, what: str) -> float:
     return v
 
 
+def _require_signal(signal, ndims: tuple[int, ...], what: str, pcm_scale):
+    """The signal of a one-shot call and its scale: float32 and None, or -- with ``pcm_scale`` -- int16 and the checked scale."""
+    if pcm_scale is None:
+        return _require_f32(signal, ndims, what), None
+    scale = _check_pcm_scale(pcm_scale, what)
+    return _require_i16(signal, what, ndims), scale
+
+
 def _stream_ptr():
     import torch
 
@@ -176,9 +184,10 @@ def _stream_ptr():
 
 # ---- internal entry points (the `_internal` pyfns, py-speechsauce/src/lib.rs:167-204) -------------
 
-def _internal_mfcc_batch(signal, config: SpeechConfig):
-    """signal [B, L] -> [B, T, num_cepstral]"""
+def _internal_mfcc_batch(signal, config: SpeechConfig, scale=None):
+    """signal [B, L] -> [B, T, num_cepstral]; scale: the signal is int16 PCM, sample = int16 * scale (the ``_i16`` entry points)"""
     lib = _lib.lib()
+    i16, sc = ("", []) if scale is None else ("_i16", [scale])
     B, L = signal.shape
     T = config.num_frames(L)
     Cc = config.params.num_cepstral
@@ -188,17 +197,18 @@ def _internal_mfcc_batch(signal, config: SpeechConfig):
         x = signal if signal.stride(1) == 1 else signal.contiguous()
         out = torch.empty((B, T, Cc), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.ss_mfcc_batch_device(config.handle, x.data_ptr(), B, L, x.stride(0) if B > 1 else L,
-                                                out.data_ptr(), _stream_ptr()))
+            _lib.check(getattr(lib, f"ss_mfcc_batch{i16}_device")(config.handle, x.data_ptr(), B, L, x.stride(0) if B > 1 else L, *sc,
+                                                                  out.data_ptr(), _stream_ptr()))
         return out
     x = np.ascontiguousarray(signal)
     out = np.empty((B, T, Cc), dtype=np.float32)
-    _lib.check(lib.ss_mfcc_batch(config.handle, x.ctypes.data, B, L, L, out.ctypes.data))
+    _lib.check(getattr(lib, f"ss_mfcc_batch{i16}")(config.handle, x.ctypes.data, B, L, L, *sc, out.ctypes.data))
     return out
 
 
-def _internal_mfe_batch(signal, config: SpeechConfig):
+def _internal_mfe_batch(signal, config: SpeechConfig, scale=None):
     lib = _lib.lib()
+    i16, sc = ("", []) if scale is None else ("_i16", [scale])
     B, L = signal.shape
     T = config.num_frames(L)
     M = config.params.num_filters
@@ -209,13 +219,13 @@ def _internal_mfe_batch(signal, config: SpeechConfig):
         feat = torch.empty((B, T, M), dtype=torch.float32, device=x.device)
         en = torch.empty((B, T), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.ss_mfe_batch_device(config.handle, x.data_ptr(), B, L, x.stride(0) if B > 1 else L,
-                                               feat.data_ptr(), en.data_ptr(), _stream_ptr()))
+            _lib.check(getattr(lib, f"ss_mfe_batch{i16}_device")(config.handle, x.data_ptr(), B, L, x.stride(0) if B > 1 else L, *sc,
+                                                                 feat.data_ptr(), en.data_ptr(), _stream_ptr()))
         return feat, en
     x = np.ascontiguousarray(signal)
     feat = np.empty((B, T, M), dtype=np.float32)
     en = np.empty((B, T), dtype=np.float32)
-    _lib.check(lib.ss_mfe_batch(config.handle, x.ctypes.data, B, L, L, feat.ctypes.data, en.ctypes.data))
+    _lib.check(getattr(lib, f"ss_mfe_batch{i16}")(config.handle, x.ctypes.data, B, L, L, *sc, feat.ctypes.data, en.ctypes.data))
     return feat, en
 
 
@@ -276,17 +286,22 @@ def _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filte
 
 
 def mfcc(signal, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
-         fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+         fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, pcm_scale=None, **switches):
     """MFCC features of a 1-D float32 signal -> (num_frames, num_cepstral).
 
     Mirrors ``speechsauce.mfcc`` (py-speechsauce/speechsauce/__init__.py:37-83 -> feature.rs:99-148).
     ``switches`` are the SURVEY section-0 options (framing, spectrum_exponent, dct_norm, dct2_gain,
     mfcc_window, preemph_coef, preemph_shift); none given == reference mode.
+
+    ``pcm_scale``: the signal is int16 PCM, converted on load as ``int16 * pcm_scale`` (a power of two in [2**-64, 2**64]:
+    2**-15 for normalised audio, 1.0 for integer-valued floats) -- bit for bit the features of that float32 signal, without the
+    conversion pass and with half the bytes over the link for host arrays.  ``mfcc_batch``, ``mfe``, ``mfe_batch``,
+    ``mfcc_packed``, ``mfe_packed`` and ``mfcc_list`` take it too.  Without it an int16 signal is a ``TypeError``.
     """
-    sig = _require_f32(signal, (1,), "mfcc")
+    sig, scale = _require_signal(signal, (1,), "mfcc", pcm_scale)
     config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
                   low_frequency, high_frequency, dc_elimination, switches, sig)
-    return _internal_mfcc_batch(sig[None, :], config)[0]
+    return _internal_mfcc_batch(sig[None, :], config, scale)[0]
 
 
 def _internal_mfcc_batches(signals, config: SpeechConfig):
@@ -315,39 +330,42 @@ def _internal_mfcc_batches(signals, config: SpeechConfig):
 
 
 def mfcc_batch(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
-               fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+               fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, pcm_scale=None, **switches):
     """Batch form: [B, L] float32 -> [B, num_frames, num_cepstral] in one launch.  A list / tuple of such batches (same clip
     length; e.g. the blocks a data loader hands over) -> the list of their feature blocks from ONE call: device tensors share one
-    kernel launch where the configuration's kernel takes a batch table (ss_mfcc_batches_device)."""
+    kernel launch where the configuration's kernel takes a batch table (ss_mfcc_batches_device).  ``pcm_scale`` (see ``mfcc``):
+    a single [B, L] int16 block only."""
     if isinstance(signals, (list, tuple)):
+        if pcm_scale is not None:
+            raise ValueError("mfcc_batch: pcm_scale takes a single [B, L] block, not a list of batches")
         sigs = [_require_f32(x, (2,), "mfcc_batch") for x in signals]
         if not sigs:
             return []
         config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
                       low_frequency, high_frequency, dc_elimination, switches, sigs[0])
         return _internal_mfcc_batches(sigs, config)
-    sig = _require_f32(signals, (2,), "mfcc_batch")
+    sig, scale = _require_signal(signals, (2,), "mfcc_batch", pcm_scale)
     config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
                   low_frequency, high_frequency, dc_elimination, switches, sig)
-    return _internal_mfcc_batch(sig, config)
+    return _internal_mfcc_batch(sig, config, scale)
 
 
 def mfe(signal, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_filters=40, fft_length=512,
-        low_frequency=0, high_frequency=None, **switches):
-    """Mel filterbank energies and frame energies (feature.rs:200-233): ((T, num_filters), (T,))."""
-    sig = _require_f32(signal, (1,), "mfe")
+        low_frequency=0, high_frequency=None, pcm_scale=None, **switches):
+    """Mel filterbank energies and frame energies (feature.rs:200-233): ((T, num_filters), (T,)).  ``pcm_scale``: see ``mfcc``."""
+    sig, scale = _require_signal(signal, (1,), "mfe", pcm_scale)
     config = _cfg(sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
                   low_frequency, high_frequency, True, switches, sig)
-    feat, en = _internal_mfe_batch(sig[None, :], config)
+    feat, en = _internal_mfe_batch(sig[None, :], config, scale)
     return feat[0], en[0]
 
 
 def mfe_batch(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_filters=40, fft_length=512,
-              low_frequency=0, high_frequency=None, **switches):
-    sig = _require_f32(signals, (2,), "mfe_batch")
+              low_frequency=0, high_frequency=None, pcm_scale=None, **switches):
+    sig, scale = _require_signal(signals, (2,), "mfe_batch", pcm_scale)
     config = _cfg(sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
                   low_frequency, high_frequency, True, switches, sig)
-    return _internal_mfe_batch(sig, config)
+    return _internal_mfe_batch(sig, config, scale)
 
 
 # ---- packed variable-length clips (ss_*_packed*): one call over clips of different lengths ------------------------
@@ -384,9 +402,11 @@ def _packed_offsets(config: SpeechConfig, lengths, n_buffer: int, what: str):
     return so, _frame_offsets(config, so)
 
 
-def _internal_packed(signal, so, config: SpeechConfig, mfe: bool):
-    """signal [N] packed clips, sample offsets so -> (features [sum T_b, cols], energy [sum T_b] or None, frame_offsets [n + 1])."""
+def _internal_packed(signal, so, config: SpeechConfig, mfe: bool, scale=None):
+    """signal [N] packed clips, sample offsets so -> (features [sum T_b, cols], energy [sum T_b] or None, frame_offsets [n + 1]);
+    scale: the signal is int16 PCM (the ``_i16`` entry points)."""
     lib = _lib.lib()
+    i16, sc = ("", []) if scale is None else ("_i16", [scale])
     fo = _frame_offsets(config, so)
     n, rows = so.size - 1, int(fo[-1])
     cols = config.params.num_filters if mfe else config.params.num_cepstral
@@ -399,50 +419,51 @@ def _internal_packed(signal, so, config: SpeechConfig, mfe: bool):
             out = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
             en = torch.empty((rows,), dtype=torch.float32, device=x.device) if mfe else None
             if mfe:
-                _lib.check(lib.ss_mfe_packed_device(config.handle, x.data_ptr(), n, dso.data_ptr(), dfo.data_ptr(), rows,
-                                                    out.data_ptr(), en.data_ptr(), _stream_ptr()))
+                _lib.check(getattr(lib, f"ss_mfe_packed{i16}_device")(config.handle, x.data_ptr(), n, dso.data_ptr(), *sc, dfo.data_ptr(),
+                                                                      rows, out.data_ptr(), en.data_ptr(), _stream_ptr()))
             else:
-                _lib.check(lib.ss_mfcc_packed_device(config.handle, x.data_ptr(), n, dso.data_ptr(), dfo.data_ptr(), rows,
-                                                     out.data_ptr(), _stream_ptr()))
+                _lib.check(getattr(lib, f"ss_mfcc_packed{i16}_device")(config.handle, x.data_ptr(), n, dso.data_ptr(), *sc, dfo.data_ptr(),
+                                                                       rows, out.data_ptr(), _stream_ptr()))
         return out, en, dfo
     x = np.ascontiguousarray(signal)
     out = np.empty((rows, cols), dtype=np.float32)
     en = np.empty((rows,), dtype=np.float32) if mfe else None
     if mfe:
-        _lib.check(lib.ss_mfe_packed(config.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data, en.ctypes.data))
+        _lib.check(getattr(lib, f"ss_mfe_packed{i16}")(config.handle, x.ctypes.data, n, so.ctypes.data, *sc, out.ctypes.data, en.ctypes.data))
     else:
-        _lib.check(lib.ss_mfcc_packed(config.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data))
+        _lib.check(getattr(lib, f"ss_mfcc_packed{i16}")(config.handle, x.ctypes.data, n, so.ctypes.data, *sc, out.ctypes.data))
     return out, en, fo
 
 
 def mfcc_packed(signal, lengths, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
-                fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+                fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, pcm_scale=None, **switches):
     """MFCC of clips of different lengths packed end to end in one 1-D float32 signal (clip b = the lengths[b] samples after
     the clips before it) -> (features [sum T_b, num_cepstral], frame_offsets [n + 1] int64): clip b's rows are
-    frame_offsets[b] : frame_offsets[b + 1], each what ``mfcc`` returns for that clip alone.  One launch for all clips."""
-    sig = _require_f32(signal, (1,), "mfcc_packed")
+    frame_offsets[b] : frame_offsets[b + 1], each what ``mfcc`` returns for that clip alone.  One launch for all clips.
+    ``pcm_scale``: the packed signal is int16 PCM (see ``mfcc``)."""
+    sig, scale = _require_signal(signal, (1,), "mfcc_packed", pcm_scale)
     so = _sample_offsets(lengths, sig.shape[0], "mfcc_packed")
     config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
                   low_frequency, high_frequency, dc_elimination, switches, sig)
-    out, _, fo = _internal_packed(sig, so, config, False)
+    out, _, fo = _internal_packed(sig, so, config, False, scale)
     return out, fo
 
 
 def mfe_packed(signal, lengths, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_filters=40, fft_length=512,
-               low_frequency=0, high_frequency=None, **switches):
+               low_frequency=0, high_frequency=None, pcm_scale=None, **switches):
     """``mfe`` of packed clips (see mfcc_packed) -> (feat [sum T_b, num_filters], energy [sum T_b], frame_offsets [n + 1])."""
-    sig = _require_f32(signal, (1,), "mfe_packed")
+    sig, scale = _require_signal(signal, (1,), "mfe_packed", pcm_scale)
     so = _sample_offsets(lengths, sig.shape[0], "mfe_packed")
     config = _cfg(sampling_frequency, frame_length, frame_stride, min(13, num_filters), num_filters, fft_length,
                   low_frequency, high_frequency, True, switches, sig)
-    return _internal_packed(sig, so, config, True)
+    return _internal_packed(sig, so, config, True, scale)
 
 
 def mfcc_list(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
-              fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+              fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, pcm_scale=None, **switches):
     """A list of 1-D float32 clips of any lengths -> the list of their [T_b, num_cepstral] features (views of one block): the
-    clips are packed once and served by one mfcc_packed call."""
-    sigs = [_require_f32(x, (1,), "mfcc_list") for x in signals]
+    clips are packed once and served by one mfcc_packed call.  ``pcm_scale``: the clips are int16 PCM (see ``mfcc``)."""
+    sigs = [_require_signal(x, (1,), "mfcc_list", pcm_scale)[0] for x in signals]
     if not sigs:
         return []
     on_device = [_is_torch(x) for x in sigs]  # (_require_f32 turns host tensors into arrays)
@@ -458,7 +479,7 @@ def mfcc_list(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01
         packed = np.concatenate(sigs)
     lengths = [int(x.shape[0]) for x in sigs]
     out, fo = mfcc_packed(packed, lengths, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters,
-                          fft_length, low_frequency, high_frequency, dc_elimination, **switches)
+                          fft_length, low_frequency, high_frequency, dc_elimination, pcm_scale, **switches)
     fo = fo.tolist()
     return [out[fo[b]:fo[b + 1]] for b in range(len(sigs))]
 

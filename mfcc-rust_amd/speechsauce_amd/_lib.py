@@ -124,6 +124,15 @@ PROTOTYPES = {
                                               _fp, _fp, _fp, C.c_void_p]),
     "ss_mfcc_stream_packed": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, _fp, _fp]),
     "ss_mfe_stream_packed": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, _fp, _fp]),
+    "ss_mfcc_batch_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_void_p]),
+    "ss_mfe_batch_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, _fp, C.c_void_p]),
+    "ss_mfcc_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
+    "ss_mfe_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, _fp, _fp,
+                                           C.c_void_p]),
+    "ss_mfcc_batch_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp]),
+    "ss_mfe_batch_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, _fp]),
+    "ss_mfcc_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, _fp]),
+    "ss_mfe_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, _fp, _fp]),
     "ss_mfcc_stream_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                    C.c_float, C.c_uint32, _fp, _fp, C.c_void_p]),
     "ss_mfe_stream_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
