@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SS_ABI_VERSION 7 /* 7: the ragged streaming calls over a pool of stream states (ss_frame_stream_packed_row_offsets, ss_mfcc_stream_packed*, ss_mfe_stream_packed*; ss_stream_packed_row_offsets, ss_mel_spectrogram_stream_packed*, ss_stft_stream_packed*), the one-shot calls' 16-bit PCM forms (ss_mfcc_batch_i16*, ss_mfe_batch_i16*, ss_mfcc_packed_i16*, ss_mfe_packed_i16*), ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region, the packed post-processing calls (ss_cmvn_packed*, ss_cmvnw_packed*, ss_power_to_db_packed*, ss_lmfe_packed*); 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
+#define SS_ABI_VERSION 7 /* 7: the ragged streaming calls over a pool of stream states (ss_frame_stream_packed_row_offsets, ss_mfcc_stream_packed*, ss_mfe_stream_packed*; ss_stream_packed_row_offsets, ss_mel_spectrogram_stream_packed*, ss_stft_stream_packed*), the one-shot calls' 16-bit PCM forms (ss_mfcc_batch_i16*, ss_mfe_batch_i16*, ss_mfcc_packed_i16*, ss_mfe_packed_i16*; ss_mel_spectrogram_i16*, ss_stft_i16*, ss_mel_spectrogram_packed_i16*, ss_stft_packed_i16*, ss_mel_spectrogram_stream_packed_i16*, ss_stft_stream_packed_i16*), ss_mfcc_batches_device, ss_mel_spectrogram_batches_device, ss_mfcc_timed_region, the packed post-processing calls (ss_cmvn_packed*, ss_cmvnw_packed*, ss_power_to_db_packed*, ss_lmfe_packed*); 6: ss_shader_clock_probe; 5: config-free stack_frames entry points, ss_mfcc_shader_clock; the ss_debug_* test aids left the product library */
 
 typedef enum ss_status {
     SS_OK = 0,
@@ -220,6 +220,29 @@ int ss_power_spectrum_frames_device(const ss_config *cfg, const float *d_frames,
 /* stft2 (functions.rs:86-123): interleaved re,im  [channels x rows x (fft_points/2+1) x 2] */
 int ss_stft_device(const ss_config *cfg, const float *d_x, size_t channels, size_t n_samples, size_t ld,
                    float *d_out, void *stream);
+/* ---- ss_mel_spectrogram* / ss_stft* fed signed 16-bit PCM ----
+ * The STFT path's share of the PCM forms (the MFCC / mfe ones are below): ss_mel_spectrogram_device / ss_stft_device /
+ * ss_mel_spectrogram / ss_stft with the samples as int16 and a scale behind the sample-layout arguments: sample s = (float)pcm * scale,
+ * converted on load.  Everything else is the float forms' contract, word for word -- shapes, errors, channels == 0, the trailing
+ * n_pad zero rows.  ld is in samples, not bytes.
+ *   scale: a power of two in [2^-64, 2^64], otherwise SS_ERR_ARG before anything runs -- 2^-15 for normalised audio, 1.0 for
+ *   integer-valued floats.  With a power of two the product is exact, so fusing it into what follows changes no bit.
+ *   Equivalence: the output is bit for bit what the float form returns on x_f[k] = (float)pcm[k] * scale, for every configuration
+ *   the float form accepts.
+ *   Kernels: the PCM build of the kernel the float call picks, where it has one -- ss_mel_c1024i<w12,...> (mel output of the
+ *   2048-point shape where the float call's own rule picks the twelve-wave build) and ss_front_generic_i16<...> (every configuration
+ *   the generic kernel serves, mel and stft output).  The eight-wave 2048-point family (small calls, stft output, banks past bin 512)
+ *   and the 512 / 1024 / 4096-point mel kernels run behind one conversion launch into a stream-ordered temporary;
+ *   ss_last_kernel_name() then reports the float kernel.  That path allocates and frees in stream order and is not offered for stream
+ *   capture.
+ *   Alignment: the device buffer needs 2-byte alignment only -- an odd ld and an odd base offset are fine.
+ *   Host forms: the samples cross the link as int16 (half the bytes of the float forms); no alignment rule. */
+int ss_mel_spectrogram_i16_device(const ss_config *cfg, const int16_t *d_x, size_t channels, size_t n_samples, size_t ld, float scale,
+                                  float *d_out, void *stream);
+int ss_stft_i16_device(const ss_config *cfg, const int16_t *d_x, size_t channels, size_t n_samples, size_t ld, float scale, float *d_out,
+                       void *stream);
+int ss_mel_spectrogram_i16(const ss_config *cfg, const int16_t *x, size_t channels, size_t n_samples, float scale, float *out);
+int ss_stft_i16(const ss_config *cfg, const int16_t *x, size_t channels, size_t n_samples, float scale, float *out);
 /* stack_frames over a batch of clips: frames [batch x n_frames x frame_len] */
 int ss_stack_frames_device(const ss_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld,
                            float *d_frames, void *stream);
@@ -315,6 +338,19 @@ int ss_mel_spectrogram_packed_device(const ss_config *cfg, const float *d_x, siz
                                      const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream);
 int ss_stft_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
                           const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream);
+/* The same four fed signed 16-bit PCM: sample s = (float)pcm * scale, scale a power of two in [2^-64, 2^64] (else SS_ERR_ARG before
+ * anything runs), the offsets in samples.  Every output is bit for bit what the float form returns on x_f[k] = (float)pcm[k] * scale;
+ * everything else -- errors, n_clips == 0, the tables' containment and the SS_ERR_DEVICE reporting, capturability of the device
+ * forms -- is the float forms' contract.  Each float call picks one of two kernels and both have PCM builds, so every call is ONE
+ * launch and nothing converts first: ss_mel_c1024vi<...> (the packed twelve-wave build) / ss_front_generic_varrowsi<...> (everything
+ * else, all stft output).  The device buffer needs 2-byte alignment only (clip offsets of either parity); the host forms stage the
+ * buffer as int16 and have no alignment rule. */
+int ss_mel_spectrogram_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                                         const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream);
+int ss_stft_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                              const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream);
+int ss_mel_spectrogram_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out);
+int ss_stft_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out);
 
 /* ---- streaming STFT / mel spectrogram with carried state (functions.rs:86-170, config.rs:126,162) ----
  * The reference keeps the last S = fft_points - frame_size samples in SpeechConfig::analysis_mem (config.rs:162) and opens every
@@ -538,6 +574,25 @@ int ss_mel_spectrogram_stream_packed(const ss_config *cfg, const float *x, size_
                                      const int32_t *slots, size_t pool_streams, float *pool, float *out);
 int ss_stft_stream_packed(const ss_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets,
                           const int32_t *slots, size_t pool_streams, float *pool, float *out);
+/* The same pool fed signed 16-bit PCM chunks: chunk sample s = (float)pcm * scale, scale a power of two in [2^-64, 2^64] (else
+ * SS_ERR_ARG before anything is launched or touched), behind the sample-layout arguments; the offsets stay in samples.  The pool
+ * stays float, so a stream may be fed PCM on one tick and floats on the next.  Every output row, and every pool row afterwards, is
+ * bit for bit what the float form leaves on x_f[k] = (float)pcm[k] * scale; everything else -- errors, R_i = 0 entries, slots,
+ * total_rows, containment and the error word, the duplicate-slot rules, capturability as a two-launch linear chain -- is the float
+ * forms' contract.  Kernels: ss_mel_c1024spi<...> (the ragged streaming twelve-wave build) or ss_front_generic_streampi<...>
+ * (everything else, all stft output), then ss_stream_advance_packed_i16 -- the frame pool's; no call converts first.
+ *   Alignment: the device forms take a 4-byte aligned d_x only (else SS_ERR_ARG), as the frame pool's _i16 forms; the host forms
+ *   stage the buffer and have no alignment rule.  The pool / x / output overlap checks work in bytes of the int16 buffer. */
+int ss_mel_spectrogram_stream_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                                const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots,
+                                                size_t pool_streams, float scale, float *d_pool, float *d_out, void *stream);
+int ss_stft_stream_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                     const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                     float scale, float *d_pool, float *d_out, void *stream);
+int ss_mel_spectrogram_stream_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
+                                         const int32_t *slots, size_t pool_streams, float scale, float *pool, float *out);
+int ss_stft_stream_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
+                              const int32_t *slots, size_t pool_streams, float scale, float *pool, float *out);
 
 /* ss_stack_frames_signal on device pointers (d_window: frame_len floats in device memory, or NULL) */
 int ss_stack_frames_signal_device(const float *d_x, size_t n_samples, uint32_t sample_rate, float frame_length, float frame_stride,

@@ -394,6 +394,101 @@ inline void mfe_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &
     check(ss_mfe_packed_i16(cfg.handle(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), scale, feat.data(), energy.data()));
 }
 
+// The mel spectrogram / STFT calls fed signed 16-bit PCM (ss_mel_spectrogram*_i16*, ss_stft*_i16*): sample = pcm * scale, scale a
+// power of two in [2^-64, 2^64]; bit for bit the float calls on the converted buffer.  ld and the offsets are in samples; 2-byte
+// alignment is enough (4-byte for the pool's device forms; the pool stays float).  Device forms: raw device pointers and a
+// hipStream_t, asynchronous.  Host forms: the samples cross the link as int16.
+inline void mel_spectrogram_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t channels, std::size_t n_samples,
+                                       std::size_t ld, float scale, float *d_out, void *stream)
+{
+    check(ss_mel_spectrogram_i16_device(cfg.handle(), d_x, channels, n_samples, ld, scale, d_out, stream));
+}
+
+inline void stft_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t channels, std::size_t n_samples, std::size_t ld,
+                            float scale, float *d_out, void *stream)
+{
+    check(ss_stft_i16_device(cfg.handle(), d_x, channels, n_samples, ld, scale, d_out, stream));
+}
+
+inline void mel_spectrogram_packed_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t n_clips,
+                                              const int64_t *d_sample_offsets, float scale, const int64_t *d_row_offsets,
+                                              std::size_t total_rows, float *d_out, void *stream)
+{
+    check(ss_mel_spectrogram_packed_i16_device(cfg.handle(), d_x, n_clips, d_sample_offsets, scale, d_row_offsets, total_rows, d_out, stream));
+}
+
+inline void stft_packed_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t n_clips, const int64_t *d_sample_offsets,
+                                   float scale, const int64_t *d_row_offsets, std::size_t total_rows, float *d_out, void *stream)
+{
+    check(ss_stft_packed_i16_device(cfg.handle(), d_x, n_clips, d_sample_offsets, scale, d_row_offsets, total_rows, d_out, stream));
+}
+
+inline void mel_spectrogram_stream_packed_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t n_active,
+                                                     const int64_t *d_sample_offsets, const int64_t *d_row_offsets, std::size_t total_rows,
+                                                     const int32_t *d_slots, std::size_t pool_streams, float scale, float *d_pool,
+                                                     float *d_out, void *stream)
+{
+    check(ss_mel_spectrogram_stream_packed_i16_device(cfg.handle(), d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots,
+                                                      pool_streams, scale, d_pool, d_out, stream));
+}
+
+inline void stft_stream_packed_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t n_active, const int64_t *d_sample_offsets,
+                                          const int64_t *d_row_offsets, std::size_t total_rows, const int32_t *d_slots,
+                                          std::size_t pool_streams, float scale, float *d_pool, float *d_out, void *stream)
+{
+    check(ss_stft_stream_packed_i16_device(cfg.handle(), d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams,
+                                           scale, d_pool, d_out, stream));
+}
+
+// x: channels rows of n_samples; out [channels x num_filters x rows] (stft: [channels x rows x (fft_points / 2 + 1) x 2])
+inline void mel_spectrogram_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, std::size_t channels, std::size_t n_samples,
+                                float scale, std::vector<float> &out)
+{
+    if (x.size() < channels * n_samples) throw Error(SS_ERR_ARG, "mel_spectrogram_i16: x is too short");
+    check(ss_mel_spectrogram_i16(cfg.handle(), x.data(), channels, n_samples, scale, out.data()));
+}
+
+inline void stft_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, std::size_t channels, std::size_t n_samples, float scale,
+                     std::vector<float> &out)
+{
+    if (x.size() < channels * n_samples) throw Error(SS_ERR_ARG, "stft_i16: x is too short");
+    check(ss_stft_i16(cfg.handle(), x.data(), channels, n_samples, scale, out.data()));
+}
+
+// x: the packed clips, sample_offsets n_clips + 1 offsets in samples; out holds the clips' blocks / rows end to end
+inline void mel_spectrogram_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
+                                       float scale, std::vector<float> &out)
+{
+    if (sample_offsets.empty()) throw Error(SS_ERR_ARG, "mel_spectrogram_packed_i16: n_clips + 1 offsets");
+    check(ss_mel_spectrogram_packed_i16(cfg.handle(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), scale, out.data()));
+}
+
+inline void stft_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets, float scale,
+                            std::vector<float> &out)
+{
+    if (sample_offsets.empty()) throw Error(SS_ERR_ARG, "stft_packed_i16: n_clips + 1 offsets");
+    check(ss_stft_packed_i16(cfg.handle(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), scale, out.data()));
+}
+
+// x the packed chunks, slots the pool row of each entry, pool the [pool_streams x S] states (updated in place)
+inline void mel_spectrogram_stream_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
+                                              const std::vector<int32_t> &slots, std::size_t pool_streams, float scale,
+                                              std::vector<float> &pool, std::vector<float> &out)
+{
+    if (sample_offsets.size() != slots.size() + 1) throw Error(SS_ERR_ARG, "mel_spectrogram_stream_packed_i16: one offset more than slots");
+    check(ss_mel_spectrogram_stream_packed_i16(cfg.handle(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_streams, scale,
+                                               pool.data(), out.data()));
+}
+
+inline void stft_stream_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
+                                   const std::vector<int32_t> &slots, std::size_t pool_streams, float scale, std::vector<float> &pool,
+                                   std::vector<float> &out)
+{
+    if (sample_offsets.size() != slots.size() + 1) throw Error(SS_ERR_ARG, "stft_stream_packed_i16: one offset more than slots");
+    check(ss_stft_stream_packed_i16(cfg.handle(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_streams, scale,
+                                    pool.data(), out.data()));
+}
+
 // cmvn / cmvnw / power_to_db of every clip of a packed block on its own rows (ss_*_packed): clip b owns rows offsets[b] ..
 // offsets[b+1] of the [total_rows x cols] block `vec`; offsets has n_clips + 1 non-decreasing entries and starts at 0
 inline std::vector<float> cmvn_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols,

@@ -211,6 +211,26 @@ int check_pcm_scale(float scale)
     return pcm_scale_ok(scale) ? SS_OK : ss::fail(SS_ERR_ARG, "scale must be a power of two in [2^-64, 2^64]");
 }
 
+// The float copy of an equal-length PCM batch for a kernel without a PCM build (launch_frames, launch_stft): one conversion launch
+// into a stream-ordered temporary, freed in stream order when the call returns.  (Stream-ordered allocation: this path is not
+// offered for stream capture.)
+struct PcmFloatCopy {
+    float *p = nullptr;
+    hipStream_t st = nullptr;
+    ~PcmFloatCopy()
+    {
+        if (p) (void)hipFreeAsync(p, st);
+    }
+    int make(const ss::BatchPcmArgs &pcm, size_t batch, size_t n, size_t ld, hipStream_t stream)
+    {
+        st = stream;
+        SS_HIP(hipMallocAsync(reinterpret_cast<void **>(&p), ((batch - 1) * ld + n) * sizeof(float), stream));
+        const hipError_t ec = ss::launch_pcm_to_float(pcm.x, p, batch, n, ld, pcm.scale, stream);
+        if (ec != hipSuccess) return hip_fail(ec, "launch_pcm_to_float");
+        return SS_OK;
+    }
+};
+
 // MFCC-path launch (OUT_MFCC / OUT_MFE / OUT_POWER).
 // rows_are_frames: d_x is a frames matrix [batch x n] (row stride ld) -- every row is one frame of n <= fft_points samples,
 // no window, no pre-emphasis (processing::power_spectrum(frames, fft_points), processing.rs:179-181).
@@ -296,22 +316,12 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
     a.out0 = out0;
     a.out1 = out1;
     ss::LaunchInfo info{};
-    // pcm: the float copy of the batch for a kernel without a PCM build -- made once, on the first candidate that needs it, freed
-    // in stream order when this call returns
-    struct Temp {
-        float *p = nullptr;
-        hipStream_t st = nullptr;
-        ~Temp()
-        {
-            if (p) (void)hipFreeAsync(p, st);
-        }
-    } tmp;
+    // pcm: the float copy of the batch for a kernel without a PCM build -- made once, on the first candidate that needs it
+    PcmFloatCopy tmp;
     auto to_float = [&]() -> int {
         if (!pcm || d_x) return SS_OK;
-        tmp.st = stream;
-        SS_HIP(hipMallocAsync(reinterpret_cast<void **>(&tmp.p), ((batch - 1) * ld + n) * sizeof(float), stream));
-        const hipError_t ec = ss::launch_pcm_to_float(pcm->x, tmp.p, batch, n, ld, pcm->scale, stream);
-        if (ec != hipSuccess) return hip_fail(ec, "launch_pcm_to_float");
+        const int trc = tmp.make(*pcm, batch, n, ld, stream);
+        if (trc) return trc;
         a.x = d_x = tmp.p;
         return SS_OK;
     };
@@ -637,12 +647,20 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
 }
 
 // STFT-path launch (OUT_MEL / OUT_STFT).
+// `pcm` (the _i16 entry points; d_x is null then): the channels as signed 16-bit PCM, as in launch_frames.  The call runs the PCM
+// build of the kernel the float call would pick where that kernel has one (the twelve-wave 2048-point mel build, chosen by the
+// float call's own rule; the generic kernel); the eight-wave 2048-point family and the 512 / 1024 / 4096-point mel kernels run
+// behind one conversion launch into a stream-ordered temporary and report their own names.
 int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t channels, size_t n, size_t ld,
-                float *out0, hipStream_t stream, const MultiBatches *multi = nullptr)
+                float *out0, hipStream_t stream, const MultiBatches *multi = nullptr, const ss::BatchPcmArgs *pcm = nullptr)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
+    if (pcm) {
+        const int src = check_pcm_scale(pcm->scale);
+        if (src) return src;
+    }
     if (channels == 0) return SS_OK;  // nothing to do, and no buffers to check
-    if (!d_x || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (!(pcm ? static_cast<const void *>(pcm->x) : d_x) || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
     if (ld < n) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
     if (n == 0 || n > 0x7fffffffull || channels > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "bad clip length / channel count");
     {
@@ -670,6 +688,15 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
     a.out_kind = out_kind;
     a.out0 = out0;
     ss::LaunchInfo info{};
+    // pcm: the float copy of the channels for a kernel without a PCM build -- made once, on the first candidate that needs it
+    PcmFloatCopy tmp;
+    auto to_float = [&]() -> int {
+        if (!pcm || d_x) return SS_OK;
+        const int trc = tmp.make(*pcm, channels, n, ld, stream);
+        if (trc) return trc;
+        a.x = d_x = tmp.p;
+        return SS_OK;
+    };
     // fft_points = 2048 mel spectrogram: the wave-private kernel when its layout assumptions hold
     const bool force_generic = ss::dbg_force_generic();
     const bool want_stft = out_kind == ss::OUT_STFT;  // the stft builds do not use the bank (stft_only table blocks)
@@ -714,6 +741,17 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
             g_last_kernel = info.kernel_name;
             return SS_OK;
         }
+        if (pcm) {
+            const hipError_t ep = ss::launch_mel_c1024(m, *pcm, stream, cfg->num_cus, &info);
+            if (ep == hipSuccess) {
+                g_last_kernel = info.kernel_name;
+                return SS_OK;
+            }
+            // hipErrorInvalidValue before the launch: the float call would not run the twelve-wave mel build -> its build on the copy
+            if (ep != hipErrorInvalidValue) return hip_fail(ep, "launch_mel_c1024 (PCM)");
+            if ((rc = to_float())) return rc;
+            m.x = d_x;
+        }
         const hipError_t e = ss::launch_mel_c1024(m, stream, cfg->num_cus, &info);
         if (e == hipSuccess) {
             g_last_kernel = info.kernel_name;
@@ -726,6 +764,7 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
     // fft_points = 512 mel spectrogram: four rows per wave (ss_mel512.hip), same layout assumptions
     if (!force_generic && (out_kind == ss::OUT_MEL || want_stft) && (cfg->mel512.ok || (want_stft && cfg->mel512.stft_only)) &&
         static_cast<unsigned long long>(a.rows + a.n_pad + 1) * a.hop < 0x7fffffffull) {
+        if ((rc = to_float())) return rc;
         ss::Mel512Args m{};
         m.x = d_x;
         m.ld = ld;
@@ -756,6 +795,7 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
     const bool use1024 = cfg->mel1024.ok || (want_stft && cfg->mel1024.stft_only), use4096 = cfg->mel4096.ok || (want_stft && cfg->mel4096.stft_only);
     if (!force_generic && (out_kind == ss::OUT_MEL || want_stft) && (use1024 || use4096) &&
         static_cast<unsigned long long>(a.rows + a.n_pad + 1) * a.hop < 0x7fffffffull) {
+        if ((rc = to_float())) return rc;
         ss::Mel2048Args m{};
         m.x = d_x;
         m.ld = ld;
@@ -782,7 +822,9 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
         // hipErrorInvalidValue before the launch: the configuration does not fit this kernel (LDS budget) -> next candidate
         if (e != hipErrorInvalidValue) return hip_fail(e, k1024 ? "launch_mel_c512" : "launch_mel_c2048");
     }
-    hipError_t e = ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info);
+    // (pcm: the generic kernel's PCM build, unless a dedicated candidate above already made the float copy and then declined)
+    hipError_t e = pcm && !d_x ? ss::launch_front_generic(a, *pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                               : ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info);
     if (e != hipSuccess) return hip_fail(e, "launch_front_generic");
     g_last_kernel = info.kernel_name;
     return SS_OK;
@@ -1268,14 +1310,22 @@ int frame_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunk
 // slot names, then the advance of the named rows -- a linear chain of two kernels on `stream`.  The tables are device arrays read by
 // the kernels only (StftStreamPackedArgs, ss_device.h); the grids come from n_active and total_rows.  Candidate order as
 // launch_stft_stream: the ragged streaming build of the 2048-point mel kernel where mel2048.ok, else that of the generic kernel.
-int launch_stft_stream_packed(const ss_config *cfg, int out_kind, const float *d_x, size_t n_active, const int64_t *d_so, const int64_t *d_ro,
+// x: the packed chunks, floats or 16-bit PCM (the _i16 entry points: both kernels have a PCM build, and the advance is the frame
+// pool's ss_stream_advance_packed_i16 -- the pool rows stay float either way).
+int launch_stft_stream_packed(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_active, const int64_t *d_so, const int64_t *d_ro,
                               size_t total_rows, const int32_t *d_slots, size_t pool_streams, float *d_pool, float *out0, hipStream_t stream)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
     if (n_active == 0) return SS_OK;
     const ss::HostTables &h = cfg->host;
     if (!h.d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
-    if (!d_x || !d_so || !d_ro || !d_slots || !d_pool || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    const float *d_x = x.f;
+    if (!x.ptr() || !d_so || !d_ro || !d_slots || !d_pool || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (x.is_pcm) {
+        const int src = check_pcm_scale(x.scale);
+        if (src) return src;
+        if (reinterpret_cast<uintptr_t>(x.pcm) & 3u) return ss::fail(SS_ERR_ARG, "the PCM buffer must be 4-byte aligned");
+    }
     if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull || total_rows >= 0x80000000ull)
         return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
     if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
@@ -1284,7 +1334,7 @@ int launch_stft_stream_packed(const ss_config *cfg, int out_kind, const float *d
     const size_t out_floats = total_rows * (out_kind == ss::OUT_STFT ? 2 * F : h.params.num_filters);
     const size_t pbytes = pool_streams * S * sizeof(float);
     // (how far x reaches is in the device tables: its first sample stands for it here, the host form checks the whole range)
-    if (ranges_overlap(d_pool, pbytes, out0, out_floats * sizeof(float)) || ranges_overlap(d_pool, pbytes, d_x, sizeof(float)))
+    if (ranges_overlap(d_pool, pbytes, out0, out_floats * sizeof(float)) || ranges_overlap(d_pool, pbytes, x.ptr(), x.sample_bytes()))
         return ss::fail(SS_ERR_ARG, "the pool overlaps the input or the output");
     {
         const int drc = check_device(cfg);  // see launch_frames
@@ -1312,6 +1362,7 @@ int launch_stft_stream_packed(const ss_config *cfg, int out_kind, const float *d
     sp.e.total_rows = static_cast<uint32_t>(total_rows);
     sp.e.step = h.d.hop;
     sp.e.err = cfg->d_err;
+    const ss::BatchPcmArgs pcm{x.pcm, x.scale};
     ss::LaunchInfo info{};
     hipError_t e = hipErrorInvalidValue;
     if (!ss::dbg_force_generic() && out_kind == ss::OUT_MEL && cfg->mel2048.ok) {
@@ -1326,16 +1377,19 @@ int launch_stft_stream_packed(const ss_config *cfg, int out_kind, const float *d
         m.n_filters = a.n_filters;
         m.out = out0;
         m.ctl = cfg->d_err;
-        e = ss::launch_mel_c1024_stream_packed(m, sp, stream, cfg->num_cus, &info);
+        e = x.is_pcm ? ss::launch_mel_c1024_stream_packed(m, sp, pcm, stream, cfg->num_cus, &info)
+                     : ss::launch_mel_c1024_stream_packed(m, sp, stream, cfg->num_cus, &info);
         // hipErrorInvalidValue before the launch: the configuration does not fit this kernel -> the generic build
         if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mel_c1024_stream_packed");
     }
     if (e != hipSuccess) {
-        e = ss::launch_front_generic_stream_packed(a, sp, h.d.log2c, stream, cfg->num_cus, &info);
+        e = x.is_pcm ? ss::launch_front_generic_stream_packed(a, sp, pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                     : ss::launch_front_generic_stream_packed(a, sp, h.d.log2c, stream, cfg->num_cus, &info);
         if (e != hipSuccess) return hip_fail(e, "launch_front_generic_stream_packed");
     }
     g_last_kernel = info.kernel_name;
-    e = ss::launch_stream_advance_packed(sp.e, d_x, stream);
+    e = x.is_pcm ? ss::launch_stream_advance_packed(ss::FrameStreamPackedPcmArgs{sp.e, x.pcm, x.scale}, stream)
+                 : ss::launch_stream_advance_packed(sp.e, d_x, stream);
     if (e != hipSuccess) return hip_fail(e, "launch_stream_advance_packed");
     return SS_OK;
 }
@@ -1343,19 +1397,22 @@ int launch_stft_stream_packed(const ss_config *cfg, int out_kind, const float *d
 // Host-pointer form, as frame_stream_packed_host: the tables are checked here, before anything touches the device; then x, the
 // tables and the n_active named pool rows (a compact block whose row i is entry i's) go up, the output and the named rows come down
 // on the config's first host-pipeline stream.  The caller's pool is written only once everything before it succeeded.
-int stft_stream_packed_host(const ss_config *cfg, int out_kind, const float *x, size_t n_active, const int64_t *so, const int32_t *slots,
+// x: floats or 16-bit PCM; the chunks go up as they are (2 B per sample for PCM) and the device call converts on load.
+int stft_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_active, const int64_t *so, const int32_t *slots,
                             size_t pool_streams, float *pool, float *out0)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
     if (n_active == 0) return SS_OK;
     const ss::HostTables &h = cfg->host;
     if (!h.d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
-    if (!x || !so || !slots || !pool || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (!x.ptr() || !so || !slots || !pool || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    int rc = x.is_pcm ? check_pcm_scale(x.scale) : SS_OK;
+    if (rc) return rc;
     if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull)
         return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
     if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
     std::vector<int64_t> ro(n_active + 1);
-    int rc = ss_stream_packed_row_offsets(&h.params, n_active, so, ro.data());
+    rc = ss_stream_packed_row_offsets(&h.params, n_active, so, ro.data());
     if (rc) return rc;
     {
         std::unordered_set<int32_t> seen;
@@ -1373,7 +1430,7 @@ int stft_stream_packed_host(const ss_config *cfg, int out_kind, const float *x, 
     const size_t S = h.params.fft_points - h.d.hop;
     const size_t out_floats = rows * (out_kind == ss::OUT_STFT ? 2 * (h.params.fft_points / 2 + 1) : h.params.num_filters);
     const size_t pbytes = pool_streams * S * sizeof(float);
-    if (ranges_overlap(pool, pbytes, x, samples * sizeof(float)) || ranges_overlap(pool, pbytes, out0, out_floats * sizeof(float)))
+    if (ranges_overlap(pool, pbytes, x.ptr(), samples * x.sample_bytes()) || ranges_overlap(pool, pbytes, out0, out_floats * sizeof(float)))
         return ss::fail(SS_ERR_ARG, "the pool overlaps the input or the output");
     if ((rc = check_device(cfg))) return rc;
     // the named pool rows, row i = entry i's
@@ -1392,18 +1449,18 @@ int stft_stream_packed_host(const ss_config *cfg, int out_kind, const float *x, 
     hipStream_t st = hp.stream[0];
     const size_t tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * S * sizeof(float);
     DeviceBuf dx, dso, dro, dsl, dp, d0;
-    // (x and the output keep one float where the call has none: the device form takes no null buffer)
-    if ((rc = dx.alloc((samples ? samples : 1) * sizeof(float))) || (rc = dso.alloc(tbytes)) || (rc = dro.alloc(tbytes)) ||
+    // (x and the output keep one sample / float where the call has none: the device form takes no null buffer)
+    if ((rc = dx.alloc((samples ? samples : 1) * x.sample_bytes())) || (rc = dso.alloc(tbytes)) || (rc = dro.alloc(tbytes)) ||
         (rc = dsl.alloc(n_active * sizeof(int32_t))) || (rc = dp.alloc(sbytes)) || (rc = d0.alloc((out_floats ? out_floats : 1) * sizeof(float))))
         return rc;
-    hipError_t e = samples ? hipMemcpyAsync(dx.p, x, samples * sizeof(float), hipMemcpyHostToDevice, st) : hipSuccess;
+    hipError_t e = samples ? hipMemcpyAsync(dx.p, x.ptr(), samples * x.sample_bytes(), hipMemcpyHostToDevice, st) : hipSuccess;
     if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, tbytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dro.p, ro.data(), tbytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dsl.p, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dp.p, rows_host.data(), sbytes, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
     if (rc == SS_OK)
-        rc = launch_stft_stream_packed(cfg, out_kind, dx.as<const float>(), n_active, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
+        rc = launch_stft_stream_packed(cfg, out_kind, x.is_pcm ? PoolChunks(dx.as<const int16_t>(), x.scale) : PoolChunks(dx.as<const float>()), n_active, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
                                        dsl.as<const int32_t>(), n_active, dp.as<float>(), d0.as<float>(), st);
     if (rc == SS_OK && out_floats > 0) {
         e = hipMemcpyAsync(out0, d0.p, out_floats * sizeof(float), hipMemcpyDeviceToHost, st);
@@ -1774,14 +1831,20 @@ int packed_host(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t 
 // Clip b is d_x[so[b] : so[b+1]], its rows ro[b] .. ro[b+1] of the packed row space; the offset tables are device arrays, read by the
 // kernel only (the launch is graph-capturable).  One launch over every clip's rows; the kernel checks the tables against each other
 // (VarRowsArgs, ss_device.h).
-int launch_packed_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t n_clips, const int64_t *d_so, const int64_t *d_ro,
+// x: the packed samples, floats or 16-bit PCM (the _i16 entry points: both kernels have a PCM build, so no call converts first).
+int launch_packed_stft(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_clips, const int64_t *d_so, const int64_t *d_ro,
                        size_t total_rows, float *out0, hipStream_t stream)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
     const ss::HostTables &h = cfg->host;
     if (!h.d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
+    if (x.is_pcm) {
+        const int src = check_pcm_scale(x.scale);
+        if (src) return src;
+    }
     if (n_clips == 0) return SS_OK;
-    if (!d_x || !d_so || !d_ro || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    const float *d_x = x.f;
+    if (!x.ptr() || !d_so || !d_ro || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
     if (n_clips > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many clips");
     {
         const int drc = check_device(cfg);  // see launch_frames
@@ -1805,6 +1868,7 @@ int launch_packed_stft(const ss_config *cfg, int out_kind, const float *d_x, siz
     v.n_clips = static_cast<uint32_t>(n_clips);
     v.hop = h.d.hop;
     v.err = cfg->d_err;
+    const ss::BatchPcmArgs pcm{x.pcm, x.scale};
     ss::LaunchInfo info{};
     // the 2048-point mel shape (bank within bins 0..512): the packed build of the twelve-wave kernel -- per clip the bits of
     // ss_mel_spectrogram_device's twelve-wave build; hipErrorInvalidValue before the launch for every other configuration
@@ -1821,14 +1885,16 @@ int launch_packed_stft(const ss_config *cfg, int out_kind, const float *d_x, siz
         m.n_filters = a.n_filters;
         m.out = out0;
         m.ctl = cfg->d_err;
-        const hipError_t em = ss::launch_mel_c1024_varlen(m, v, stream, cfg->num_cus, &info);
+        const hipError_t em = x.is_pcm ? ss::launch_mel_c1024_varlen(m, v, pcm, stream, cfg->num_cus, &info)
+                                       : ss::launch_mel_c1024_varlen(m, v, stream, cfg->num_cus, &info);
         if (em == hipSuccess) {
             g_last_kernel = info.kernel_name;
             return SS_OK;
         }
         if (em != hipErrorInvalidValue) return hip_fail(em, "launch_mel_c1024_varlen");
     }
-    const hipError_t e = ss::launch_front_generic_varrows(a, v, h.d.log2c, stream, cfg->num_cus, &info);
+    const hipError_t e = x.is_pcm ? ss::launch_front_generic_varrows(a, v, pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                                  : ss::launch_front_generic_varrows(a, v, h.d.log2c, stream, cfg->num_cus, &info);
     if (e != hipSuccess) return hip_fail(e, "launch_front_generic_varrows");
     g_last_kernel = info.kernel_name;
     return SS_OK;
@@ -1836,14 +1902,17 @@ int launch_packed_stft(const ss_config *cfg, int out_kind, const float *d_x, siz
 
 // Host-pointer form: the row offsets from the host's sample offsets, one upload, one launch, one download on the config's first
 // host-pipeline stream (the host calls of a config are serialised by its mutex).
-int packed_stft_host(const ss_config *cfg, int out_kind, const float *x, size_t n_clips, const int64_t *so, float *out0)
+// x: floats or 16-bit PCM; the samples go up as they are (2 B per sample for PCM) and the device call converts on load.
+int packed_stft_host(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_clips, const int64_t *so, float *out0)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
     if (!cfg->host.d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
+    int rc = x.is_pcm ? check_pcm_scale(x.scale) : SS_OK;
+    if (rc) return rc;
     if (n_clips == 0) return SS_OK;
-    if (!x || !so || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (!x.ptr() || !so || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
     std::vector<int64_t> ro(n_clips + 1);
-    int rc = ss_packed_row_offsets(&cfg->host.params, n_clips, so, ro.data());
+    rc = ss_packed_row_offsets(&cfg->host.params, n_clips, so, ro.data());
     if (rc) return rc;
     if ((rc = check_device(cfg))) return rc;
     const size_t rows = static_cast<size_t>(ro[n_clips]), samples = static_cast<size_t>(so[n_clips]);
@@ -1856,15 +1925,15 @@ int packed_stft_host(const ss_config *cfg, int out_kind, const float *x, size_t 
     }
     hipStream_t st = hp.stream[0];
     DeviceBuf dx, dso, dro, d0;
-    if ((rc = dx.alloc(samples * sizeof(float))) || (rc = dso.alloc((n_clips + 1) * sizeof(int64_t))) ||
+    if ((rc = dx.alloc(samples * x.sample_bytes())) || (rc = dso.alloc((n_clips + 1) * sizeof(int64_t))) ||
         (rc = dro.alloc((n_clips + 1) * sizeof(int64_t))) || (rc = d0.alloc(rows * cols * sizeof(float))))
         return rc;
-    hipError_t e = hipMemcpyAsync(dx.p, x, samples * sizeof(float), hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(dx.p, x.ptr(), samples * x.sample_bytes(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dro.p, ro.data(), (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
     if (rc == SS_OK)
-        rc = launch_packed_stft(cfg, out_kind, dx.as<const float>(), n_clips, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
+        rc = launch_packed_stft(cfg, out_kind, x.is_pcm ? PoolChunks(dx.as<const int16_t>(), x.scale) : PoolChunks(dx.as<const float>()), n_clips, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
                                 d0.as<float>(), st);
     if (rc == SS_OK) {
         e = hipMemcpyAsync(out0, d0.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost, st);
@@ -1875,6 +1944,34 @@ int packed_stft_host(const ss_config *cfg, int out_kind, const float *x, size_t 
     if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "packed host call");
     if (rc == SS_OK) rc = pending_device_error(cfg);
     return rc;
+}
+
+// Host-pointer form of the equal-length STFT-path calls (ss_stft / ss_mel_spectrogram and their _i16 forms): T = float, or int16_t
+// with pcm_scale -- the samples then cross the link as int16 (host_pipeline<int16_t>) and the device call converts.
+template <typename T>
+int stft_host(const ss_config *cfg, int out_kind, const T *x, size_t channels, size_t n_samples, float pcm_scale, float *out)
+{
+    constexpr bool kPcm = std::is_same_v<T, int16_t>;
+    if (!cfg || !x || !out) return ss::fail(SS_ERR_ARG, "null argument");
+    int rc = kPcm ? check_pcm_scale(pcm_scale) : SS_OK;
+    if (rc) return rc;
+    size_t R = 0, Rreal = 0;
+    rc = ss::stft_rows(cfg->host.params, n_samples, R, Rreal);
+    if (rc) return rc;
+    if (channels == 0) return SS_OK;
+    if (n_samples == 0) return ss::fail(SS_ERR_ARG, "empty signal");
+    rc = check_device(cfg);
+    if (rc) return rc;
+    const size_t per_channel = out_kind == ss::OUT_STFT ? R * (cfg->host.params.fft_points / 2 + 1) * 2 : cfg->host.params.num_filters * R;
+    return host_pipeline(cfg, x, channels, n_samples, n_samples, out, per_channel, nullptr, 0,
+                         [&](const T *d_x, size_t c, float *d_o0, float *, hipStream_t st) {
+                             if constexpr (kPcm) {
+                                 const ss::BatchPcmArgs pcm{d_x, pcm_scale};
+                                 return launch_stft(cfg, out_kind, nullptr, c, n_samples, n_samples, d_o0, st, nullptr, &pcm);
+                             } else {
+                                 return launch_stft(cfg, out_kind, d_x, c, n_samples, n_samples, d_o0, st);
+                             }
+                         });
 }
 
 }  // namespace
@@ -2625,18 +2722,12 @@ int ss_stack_frames(const ss_config *cfg, const float *x, size_t n_samples, floa
 
 int ss_stft(const ss_config *cfg, const float *x, size_t channels, size_t n_samples, float *out)
 {
-    if (!cfg || !x || !out) return ss::fail(SS_ERR_ARG, "null argument");
-    size_t R = 0, Rreal = 0;
-    int rc = ss::stft_rows(cfg->host.params, n_samples, R, Rreal);
-    if (rc) return rc;
-    if (channels == 0) return SS_OK;
-    if (n_samples == 0) return ss::fail(SS_ERR_ARG, "empty signal");
-    rc = check_device(cfg);
-    if (rc) return rc;
-    return host_pipeline(cfg, x, channels, n_samples, n_samples, out, R * (cfg->host.params.fft_points / 2 + 1) * 2, nullptr, 0,
-                         [&](const float *d_x, size_t c, float *d_o0, float *, hipStream_t st) {
-                             return ss_stft_device(cfg, d_x, c, n_samples, n_samples, d_o0, st);
-                         });
+    return stft_host(cfg, ss::OUT_STFT, x, channels, n_samples, 1.0f, out);
+}
+
+int ss_stft_i16(const ss_config *cfg, const int16_t *x, size_t channels, size_t n_samples, float scale, float *out)
+{
+    return stft_host(cfg, ss::OUT_STFT, x, channels, n_samples, scale, out);
 }
 
 int ss_mel_spectrogram_device(const ss_config *cfg, const float *d_x, size_t channels, size_t n_samples,
@@ -2695,6 +2786,73 @@ int ss_stft_device(const ss_config *cfg, const float *d_x, size_t channels, size
                    float *d_out, void *stream)
 {
     return launch_stft(cfg, ss::OUT_STFT, d_x, channels, n_samples, ld, d_out, static_cast<hipStream_t>(stream));
+}
+
+// ---- the STFT-path calls fed signed 16-bit PCM: sample = (float)pcm * scale (speechsauce_amd.h) ----
+int ss_mel_spectrogram_i16_device(const ss_config *cfg, const int16_t *d_x, size_t channels, size_t n_samples, size_t ld, float scale,
+                                  float *d_out, void *stream)
+{
+    const ss::BatchPcmArgs pcm{d_x, scale};
+    return launch_stft(cfg, ss::OUT_MEL, nullptr, channels, n_samples, ld, d_out, static_cast<hipStream_t>(stream), nullptr, &pcm);
+}
+
+int ss_stft_i16_device(const ss_config *cfg, const int16_t *d_x, size_t channels, size_t n_samples, size_t ld, float scale, float *d_out,
+                       void *stream)
+{
+    const ss::BatchPcmArgs pcm{d_x, scale};
+    return launch_stft(cfg, ss::OUT_STFT, nullptr, channels, n_samples, ld, d_out, static_cast<hipStream_t>(stream), nullptr, &pcm);
+}
+
+int ss_mel_spectrogram_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                                         const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream)
+{
+    return launch_packed_stft(cfg, ss::OUT_MEL, PoolChunks(d_x, scale), n_clips, d_sample_offsets, d_row_offsets, total_rows, d_out,
+                              static_cast<hipStream_t>(stream));
+}
+
+int ss_stft_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                              const int64_t *d_row_offsets, size_t total_rows, float *d_out, void *stream)
+{
+    return launch_packed_stft(cfg, ss::OUT_STFT, PoolChunks(d_x, scale), n_clips, d_sample_offsets, d_row_offsets, total_rows, d_out,
+                              static_cast<hipStream_t>(stream));
+}
+
+int ss_mel_spectrogram_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out)
+{
+    return packed_stft_host(cfg, ss::OUT_MEL, PoolChunks(x, scale), n_clips, sample_offsets, out);
+}
+
+int ss_stft_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out)
+{
+    return packed_stft_host(cfg, ss::OUT_STFT, PoolChunks(x, scale), n_clips, sample_offsets, out);
+}
+
+int ss_mel_spectrogram_stream_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                                const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams,
+                                                float scale, float *d_pool, float *d_out, void *stream)
+{
+    return launch_stft_stream_packed(cfg, ss::OUT_MEL, PoolChunks(d_x, scale), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots,
+                                     pool_streams, d_pool, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_stft_stream_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                     const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float scale,
+                                     float *d_pool, float *d_out, void *stream)
+{
+    return launch_stft_stream_packed(cfg, ss::OUT_STFT, PoolChunks(d_x, scale), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots,
+                                     pool_streams, d_pool, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_mel_spectrogram_stream_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
+                                         const int32_t *slots, size_t pool_streams, float scale, float *pool, float *out)
+{
+    return stft_stream_packed_host(cfg, ss::OUT_MEL, PoolChunks(x, scale), n_active, sample_offsets, slots, pool_streams, pool, out);
+}
+
+int ss_stft_stream_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                              size_t pool_streams, float scale, float *pool, float *out)
+{
+    return stft_stream_packed_host(cfg, ss::OUT_STFT, PoolChunks(x, scale), n_active, sample_offsets, slots, pool_streams, pool, out);
 }
 
 int ss_stft_stream_device(const ss_config *cfg, int mode, const float *d_x, size_t n_streams, size_t n_samples, size_t ld,
@@ -2928,18 +3086,12 @@ int ss_mfe_batch_i16(const ss_config *cfg, const int16_t *x, size_t batch, size_
 
 int ss_mel_spectrogram(const ss_config *cfg, const float *x, size_t channels, size_t n_samples, float *out)
 {
-    if (!cfg || !x || !out) return ss::fail(SS_ERR_ARG, "null argument");
-    size_t R = 0, Rreal = 0;
-    int rc = ss::stft_rows(cfg->host.params, n_samples, R, Rreal);
-    if (rc) return rc;
-    if (channels == 0) return SS_OK;
-    if (n_samples == 0) return ss::fail(SS_ERR_ARG, "empty signal");
-    rc = check_device(cfg);
-    if (rc) return rc;
-    return host_pipeline(cfg, x, channels, n_samples, n_samples, out, cfg->host.params.num_filters * R, nullptr, 0,
-                         [&](const float *d_x, size_t c, float *d_o0, float *, hipStream_t st) {
-                             return ss_mel_spectrogram_device(cfg, d_x, c, n_samples, n_samples, d_o0, st);
-                         });
+    return stft_host(cfg, ss::OUT_MEL, x, channels, n_samples, 1.0f, out);
+}
+
+int ss_mel_spectrogram_i16(const ss_config *cfg, const int16_t *x, size_t channels, size_t n_samples, float scale, float *out)
+{
+    return stft_host(cfg, ss::OUT_MEL, x, channels, n_samples, scale, out);
 }
 
 int ss_preemphasis(const float *x, size_t n_samples, long shift, float cof, float *y)

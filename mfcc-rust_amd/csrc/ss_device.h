@@ -356,6 +356,21 @@ struct FrameStreamPackedPcmArgs {
 };
 // sample k of a PCM buffer
 __device__ __forceinline__ float pcm_sample(const int16_t *x, long long k, float scale) { return static_cast<float>(x[k]) * scale; }
+// the two samples of a PCM dword: sign-extended, converted, times the power-of-two scale (exact: the bits the float loader finds in
+// the converted buffer)
+__device__ __forceinline__ float2 pcm_pair(int w, float scale)
+{
+    return make_float2(static_cast<float>(static_cast<int16_t>(w)) * scale, static_cast<float>(w >> 16) * scale);
+}
+// The raw dword of a PCM sample pair: two int16, fetched by one 32-bit load at 2-byte alignment (a pair may start at an odd sample:
+// odd ld, odd base, odd clip offset).  gfx950 global loads take any alignment in the unaligned access mode the HSA ABI sets -- the
+// mode the float builds' 8-byte pair loads at dword alignment already rely on -- so one load serves either parity.
+__device__ __forceinline__ float pcm_raw_pair(const void *p)
+{
+    int w;
+    __builtin_memcpy(&w, __builtin_assume_aligned(p, 2), sizeof w);
+    return __int_as_float(w);
+}
 // a as for launch_front_generic_frame_stream_packed (a.x unused)
 hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const FrameStreamPackedPcmArgs &s, uint32_t log2c, hipStream_t stream,
                                                     int num_cus, LaunchInfo *info);
@@ -399,6 +414,16 @@ struct StftStreamPackedArgs {
 // The grid comes from s.e.total_rows (one workgroup where it is 0: the entry pass).
 hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
                                               int num_cus, LaunchInfo *info);
+
+// The STFT path fed signed 16-bit PCM (the ss_mel_spectrogram*_i16* / ss_stft*_i16* entry points): a BatchPcmArgs behind the layout's
+// own argument in the kernels' trailing packs selects the PCM loader -- alone (equal-length clips: launch_front_generic above with
+// out_kind OUT_MEL / OUT_STFT), behind a VarRowsArgs (packed clips) or behind a StftStreamPackedArgs (the pool: chunk samples are
+// PCM, the pool rows stay float; launch_stream_advance_packed(FrameStreamPackedPcmArgs) moves them on).  The tables, the offsets
+// (in samples) and every check are the float layouts'; a.x is unused.  Reported as ss_front_generic_varrowsi / _streampi.
+hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream,
+                                        int num_cus, LaunchInfo *info);
+hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, const BatchPcmArgs &p, uint32_t log2c,
+                                              hipStream_t stream, int num_cus, LaunchInfo *info);
 #if SS_LAB
 // Test aid (lab library): every word of every CU's LDS := 0xFFFFFFFF (ss_debug_poison_lds).
 hipError_t launch_poison_lds(hipStream_t stream, int num_cus);
@@ -544,6 +569,16 @@ hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStream
 // hipErrorInvalidValue before the launch where the shape has no batch-table build
 hipError_t launch_mel_c1024_multi(const Mel2048Args &a, int n_batches, const float *const *d_x, float *const *d_out, const size_t *channels,
                                   hipStream_t stream, int num_cus, LaunchInfo *info);
+// The three twelve-wave mel layouts fed 16-bit PCM (BatchPcmArgs above; a.x unused), reported as ss_mel_c1024i<w12,...> /
+// ss_mel_c1024vi<...> / ss_mel_c1024spi<...>: a lane's sample pair is one dword of two int16, loaded at 2-byte alignment (ld, base and
+// offsets of either parity).  The equal-length form serves exactly the calls launch_mel_c1024 gives the twelve-wave mel build (the
+// same rule, so the bits are the float call's); hipErrorInvalidValue before the launch for every other call -- eight waves, stft
+// output, fullp -- which the caller runs on the float build behind a conversion.
+hipError_t launch_mel_c1024(const Mel2048Args &a, const BatchPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info);
+hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, const BatchPcmArgs &p, hipStream_t stream, int num_cus,
+                                   LaunchInfo *info);
+hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, const BatchPcmArgs &p, hipStream_t stream,
+                                          int num_cus, LaunchInfo *info);
 #if SS_LAB
 // the retired whole-line-tile build (tools/experiments/ss_mel2048_tile.hip, linked into the lab library only);
 // hipErrorInvalidValue where the shape has no tile build

@@ -22,6 +22,10 @@
 // ss_front_generic<LOG2C, BLU, StftStreamPackedArgs> (reported as ss_front_generic_streamp<LOG2C>): the STFT / mel path over a pool
 // of stream states -- the packed-rows tiles with every row on the pool row its entry names (StftStreamPackedArgs, ss_device.h);
 // ss_stream_advance_packed moves the named pool rows on behind it.
+// ss_front_generic<LOG2C, BLU, VarRowsArgs, BatchPcmArgs> / <LOG2C, BLU, StftStreamPackedArgs, BatchPcmArgs> (reported as
+// ss_front_generic_varrowsi<LOG2C> / ss_front_generic_streampi<LOG2C>), and ss_front_generic_i16 with mel or stft output: the three
+// STFT / mel layouts fed signed 16-bit PCM -- a clip or chunk sample is (float)int16 * scale, the pool rows stay float
+// (ss_stream_advance_packed_i16 moves them on).
 //
 //   * A real frame of N = 2C samples is packed as C complex points z[n] = x[2n] + i x[2n+1]
 //     and transformed by a Stockham autosort FFT whose butterflies live in registers: every
@@ -260,16 +264,17 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
 // the row's entry (its chunk, its row within the chunk, its pool row) comes from the device tables (FrameStreamPackedArgs).
 // FSPI: FSP with the chunks as 16-bit PCM (FrameStreamPackedPcmArgs: its entry block is FSP's; state reads are unchanged).
 // EQI / VARI: the equal-length layout / VAR with the samples as 16-bit PCM (BatchPcmArgs / VarlenPcmArgs: VARI's tables are VAR's).
+// A BatchPcmArgs behind a VarRowsArgs or a StftStreamPackedArgs: VARR / SPR with the clips / chunks as 16-bit PCM (state reads unchanged).
 // VARR: the STFT / mel path of launch_front_generic_varrows -- a workgroup visit is a tile of packed rows, every row finds its own
 // clip; the transposed mel flush writes each row into its clip's [M x R_b] block.
 // SPR: VARR's tiles over the entries of a ragged streaming call (launch_front_generic_stream_packed) -- a row's entry (its chunk, its
 // row within the chunk, its pool row) comes from the device tables (StftStreamPackedArgs), its window as in STREAM.
 // (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs, one FrameStreamPackedArgs, one FrameStreamPackedPcmArgs, one
-// BatchPcmArgs, one VarlenPcmArgs, one VarRowsArgs or one StftStreamPackedArgs -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
+// BatchPcmArgs, one VarlenPcmArgs, one VarRowsArgs or one StftStreamPackedArgs, the last two also with a BatchPcmArgs behind them -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
 template <int LOG2C, bool BLU, typename... V>
 __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
 {
-    constexpr bool EQI = (std::is_same_v<V, BatchPcmArgs> || ...);
+    constexpr bool PCMX = (std::is_same_v<V, BatchPcmArgs> || ...);  // the layout's samples are 16-bit PCM at bpi->x
     constexpr bool VARI = (std::is_same_v<V, VarlenPcmArgs> || ...);
     constexpr bool VAR = VARI || (std::is_same_v<V, VarlenArgs> || ...);
     constexpr bool STREAM = (std::is_same_v<V, StreamArgs> || ...);
@@ -278,6 +283,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     constexpr bool FSTREAM = FSP || (std::is_same_v<V, FrameStreamArgs> || ...);
     constexpr bool VARR = (std::is_same_v<V, VarRowsArgs> || ...);
     constexpr bool SPR = (std::is_same_v<V, StftStreamPackedArgs> || ...);
+    constexpr bool EQI = PCMX && !VARR && !SPR;
     [[maybe_unused]] const StftStreamPackedArgs *sp = pack_arg<StftStreamPackedArgs>(vargs...);
     [[maybe_unused]] const VarRowsArgs *ra = pack_arg<VarRowsArgs>(vargs...);
     [[maybe_unused]] const BatchPcmArgs *bpi = pack_arg<BatchPcmArgs>(vargs...);
@@ -555,7 +561,9 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 const bool valid = rl < rt && c.ok && r >= 0 && r < static_cast<long long>(c.R);
                 const long long Rreal = c.R > a.n_pad ? static_cast<long long>(c.R - a.n_pad) : 0ll;
                 const bool active = valid && r < Rreal;
-                const float *xc = a.x + (valid ? c.s0 : 0ll);
+                const float *xc = PCMX ? nullptr : a.x + (valid ? c.s0 : 0ll);
+                [[maybe_unused]] const int16_t *xi = nullptr;  // a trailing BatchPcmArgs: the clip / chunk as PCM
+                if constexpr (PCMX) xi = bpi->x + (valid ? c.s0 : 0ll);
                 const long long ns = valid ? static_cast<long long>(c.n) : 0ll;
                 // functions.rs:137-151: window over the last W samples ending at chunk r + n_pad of the clip
                 const long long start = (r + a.n_pad + 1) * static_cast<long long>(a.hop) - W;
@@ -563,9 +571,12 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                     const long long idx = start + i;
                     if constexpr (SPR) {  // (idx >= -S: a row's window ends at least one hop into the chunk)
                         if (!active || i >= W || idx >= ns) return 0.0f;
-                        return (idx < 0 ? srow[idx] : xc[idx]) * a.window[i];
+                        // (PCM: int16 times the power-of-two scale, exact -- the float the float build reads; the pool row is float)
+                        if constexpr (PCMX) return (idx < 0 ? srow[idx] : pcm_sample(xi, idx, bpi->scale)) * a.window[i];
+                        else return (idx < 0 ? srow[idx] : xc[idx]) * a.window[i];
                     }
-                    return active && i < W && idx >= 0 && idx < ns ? xc[idx] * a.window[i] : 0.0f;
+                    if constexpr (PCMX) return active && i < W && idx >= 0 && idx < ns ? pcm_sample(xi, idx, bpi->scale) * a.window[i] : 0.0f;
+                    else return active && i < W && idx >= 0 && idx < ns ? xc[idx] * a.window[i] : 0.0f;
                 };
                 float2 v[16];
 #pragma unroll
@@ -619,7 +630,9 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
         const int W = BLU ? static_cast<int>(a.blu_n) : G::N;
         constexpr int TILE = 32;  // rows buffered before a transposed, coalesced flush
         for (unsigned clip = blockIdx.x; clip < a.batch; clip += gridDim.x) {
-            const float *xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
+            const float *xc = EQI ? nullptr : a.x + static_cast<unsigned long long>(clip) * a.ld;
+            [[maybe_unused]] const int16_t *xi = nullptr;  // EQI: the clip as PCM
+            if constexpr (EQI) xi = bpi->x + static_cast<unsigned long long>(clip) * a.ld;
             // STREAM: the stream's state, indexed from its end (sample p < 0 of the stream is srow[p], p >= -S)
             [[maybe_unused]] const float *srow = nullptr;
             if constexpr (STREAM) srow = sa->state + static_cast<unsigned long long>(clip) * sa->state_len + sa->state_len;
@@ -637,7 +650,10 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                             if (!active || i >= W || idx >= static_cast<long long>(a.n_samples)) return 0.0f;
                             return (idx < 0 ? srow[idx] : xc[idx]) * a.window[i];
                         }
-                        return active && i < W && idx >= 0 && idx < static_cast<long long>(a.n_samples) ? xc[idx] * a.window[i] : 0.0f;
+                        // (EQI: int16 times the power-of-two scale, exact -- the float the float build reads)
+                        if constexpr (EQI)
+                            return active && i < W && idx >= 0 && idx < static_cast<long long>(a.n_samples) ? pcm_sample(xi, idx, bpi->scale) * a.window[i] : 0.0f;
+                        else return active && i < W && idx >= 0 && idx < static_cast<long long>(a.n_samples) ? xc[idx] * a.window[i] : 0.0f;
                     };
                     float2 v[16];
 #pragma unroll
@@ -707,6 +723,8 @@ constexpr const char *layout_suffix(const FrameStreamArgs &) { return "_fstream"
 constexpr const char *layout_suffix(const FrameStreamPackedArgs &) { return "_fstreamp"; }
 constexpr const char *layout_suffix(const FrameStreamPackedPcmArgs &) { return "_fstreampi"; }
 constexpr const char *layout_suffix(const StftStreamPackedArgs &) { return "_streamp"; }
+constexpr const char *layout_suffix(const VarRowsArgs &, const BatchPcmArgs &) { return "_varrowsi"; }
+constexpr const char *layout_suffix(const StftStreamPackedArgs &, const BatchPcmArgs &) { return "_streampi"; }
 
 // the packed-rows builds: the tile's row table (32 offsets + 32 row counts, 8-byte aligned)
 constexpr size_t kRowTableBytes = 32 * (sizeof(long long) + sizeof(unsigned)) + 16;
@@ -717,6 +735,8 @@ constexpr size_t layout_lds(const StftStreamPackedArgs &) { return kRowTableByte
 constexpr size_t layout_lds(const FrameStreamPackedPcmArgs &) { return 0; }
 constexpr size_t layout_lds(const BatchPcmArgs &) { return 0; }
 constexpr size_t layout_lds(const VarlenPcmArgs &) { return 0; }
+constexpr size_t layout_lds(const VarRowsArgs &, const BatchPcmArgs &) { return kRowTableBytes; }
+constexpr size_t layout_lds(const StftStreamPackedArgs &, const BatchPcmArgs &) { return kRowTableBytes; }
 
 // Workgroup visits of a call at `fpb` frames per visit.  0: nothing to launch; kTooManyRows: the kernel's 32-bit row index does not
 // reach the last row.
@@ -754,6 +774,11 @@ inline unsigned long long layout_work(const FrontArgs &, unsigned long long, con
 inline unsigned long long layout_work(const FrontArgs &, unsigned long long, const StftStreamPackedArgs &s)
 {
     return at_least_one((static_cast<unsigned long long>(s.e.total_rows) + 31) / 32);
+}
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const VarRowsArgs &v, const BatchPcmArgs &) { return layout_work(a, fpb, v); }
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const StftStreamPackedArgs &s, const BatchPcmArgs &)
+{
+    return layout_work(a, fpb, s);
 }
 
 // What ss_last_kernel_name() reports for an instantiation: ss_front_generic<suffix><LOG2C[,chirpz]>, built once, kept for the process.
@@ -948,7 +973,7 @@ hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, 
 
 hipError_t launch_front_generic(const FrontArgs &a, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
-    if ((a.out_kind != OUT_MFCC && a.out_kind != OUT_MFE && a.out_kind != OUT_POWER) || !p.x) return hipErrorInvalidValue;
+    if (!p.x) return hipErrorInvalidValue;  // (every output: MFCC / mfe / power, and the mel / stft rows of the STFT path)
     return dispatch_front(a, log2c, stream, num_cus, info, p);
 }
 
@@ -989,6 +1014,13 @@ hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v
     return dispatch_front(a, log2c, stream, num_cus, info, v);
 }
 
+hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream,
+                                        int num_cus, LaunchInfo *info)
+{
+    if ((a.out_kind != OUT_MEL && a.out_kind != OUT_STFT) || !p.x) return hipErrorInvalidValue;
+    return dispatch_front(a, log2c, stream, num_cus, info, v, p);
+}
+
 hipError_t launch_front_generic_stream(const FrontArgs &a, const StreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
                                        LaunchInfo *info)
 {
@@ -1020,8 +1052,10 @@ hipError_t launch_front_generic_frame_stream_packed(const FrontArgs &a, const Fr
     return dispatch_front(a, log2c, stream, num_cus, info, s);
 }
 
-hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
-                                              int num_cus, LaunchInfo *info)
+// the ragged streaming launch for either chunk format: p = empty (floats at a.x) or one BatchPcmArgs
+template <typename... P>
+static hipError_t launch_stream_packed_any(const FrontArgs &a, const StftStreamPackedArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
+                                           LaunchInfo *info, const P &...p)
 {
     if (a.out_kind != OUT_MEL && a.out_kind != OUT_STFT) return hipErrorInvalidValue;
     // the windows the kernel reads: W samples ending (t + 1) hops into the chunk, the first W - hop = S of them at most in the pool row
@@ -1029,7 +1063,20 @@ hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStre
     if (s.e.n_active == 0 || a.hop == 0 || s.e.step != a.hop || a.n_pad != 0 || s.e.state_len + a.hop != W || !s.e.pool ||
         s.e.total_rows >= 0x7fffffffu)
         return hipErrorInvalidValue;
-    return dispatch_front(a, log2c, stream, num_cus, info, s);
+    return dispatch_front(a, log2c, stream, num_cus, info, s, p...);
+}
+
+hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, uint32_t log2c, hipStream_t stream,
+                                              int num_cus, LaunchInfo *info)
+{
+    return launch_stream_packed_any(a, s, log2c, stream, num_cus, info);
+}
+
+hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, const BatchPcmArgs &p, uint32_t log2c,
+                                              hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    if (!p.x) return hipErrorInvalidValue;
+    return launch_stream_packed_any(a, s, log2c, stream, num_cus, info, p);
 }
 
 hipError_t launch_stream_advance_packed(const FrameStreamPackedArgs &s, const float *x, hipStream_t stream)

@@ -31,6 +31,10 @@
 // Ragged streaming builds of the twelve-wave kernel (a StftStreamPackedArgs in the trailing argument pack,
 // launch_mel_c1024_stream_packed, reported as ss_mel_c1024sp<...>): the packed builds' units over the entries of a pool call; an
 // entry may have no rows, so the cursor steps over such entries, and the edge branch reads the entry's pool row.
+// PCM builds of the twelve-wave kernel's three mel layouts (a BatchPcmArgs at the end of the trailing argument pack, reported as
+// ss_mel_c1024i<w12,...> / ss_mel_c1024vi<...> / ss_mel_c1024spi<...>): the samples are signed 16-bit PCM, a lane's 32 window pairs 32
+// dwords of two int16 each, fetched where the float pairs are and converted where the window product consumes them; only the loader
+// and that product differ.
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 #include "ss_internal.h"
@@ -82,15 +86,22 @@ __host__ __device__ inline unsigned mel_work_pairs(unsigned rows, unsigned /*rea
 // Streaming builds, edge branch of the loader: this lane's 64 samples x[base + 64 e + {0, 1}] of the window, where a sample at p < 0
 // is the stream's carried state[clip * S + S + p] (p >= -S: a window ends at least one hop into the chunk), one past the chunk's
 // end is zero (reference mode: the zero padding of a partial last chunk), an inactive row is all zeros.  Per sample: a state row
-// of odd length, an odd hop or an odd chunk may split any pair.
-__device__ __forceinline__ void stream_window(const StreamArgs &s, const float *xc, unsigned clip, int base, int n, bool active, float2 (&vv)[32])
+// of odd length, an odd hop or an odd chunk may split any pair.  chunk(p): the chunk's sample p >= 0 (floats, or PCM through
+// pcm_sample); the state is float either way.
+template <typename Chunk>
+__device__ __forceinline__ void stream_window(const StreamArgs &s, Chunk chunk, unsigned clip, int base, int n, bool active, float2 (&vv)[32])
 {
     const float *sr = s.state + static_cast<unsigned long long>(clip) * s.state_len + s.state_len;
 #pragma unroll
     for (int e = 0; e < 32; ++e) {
         const int p0 = base + 64 * e;
-        vv[e] = make_float2(active && p0 < n ? (p0 < 0 ? sr[p0] : xc[p0]) : 0.f, active && p0 + 1 < n ? (p0 + 1 < 0 ? sr[p0 + 1] : xc[p0 + 1]) : 0.f);
+        vv[e] = make_float2(active && p0 < n ? (p0 < 0 ? sr[p0] : chunk(p0)) : 0.f, active && p0 + 1 < n ? (p0 + 1 < 0 ? sr[p0 + 1] : chunk(p0 + 1)) : 0.f);
     }
+}
+// the float chunk at xc
+__device__ __forceinline__ auto float_chunk(const float *xc)
+{
+    return [xc](int p) -> const float & { return xc[p]; };  // (an lvalue, as the state's: the select is between two addresses)
 }
 
 template <int kWavesM, bool STFT, bool FULLP = false, typename... SA>
@@ -173,7 +184,7 @@ __global__ __launch_bounds__(kWavesM * 64) void ss_mel_c1024(const Mel2048Args a
             const int base = start + 2 * j;
             const int n = static_cast<int>(a.n_samples);
             if constexpr (STREAM) {
-                stream_window(*sa, xc, clip, base, n, active, vv);
+                stream_window(*sa, float_chunk(xc), clip, base, n, active, vv);
             } else if (((start | n) & 1) == 0) {
                 int e_lo = base >= 0 ? 0 : (63 - base) >> 6;
                 int e_hi = base >= n ? 0 : min(32, (n - base + 63) >> 6);
@@ -363,6 +374,11 @@ __global__ __launch_bounds__(kWavesM * 64) void ss_mel_c1024(const Mel2048Args a
 // entries without rows share their row offset with their successor, so any number of them may lie between the two rows of a pair:
 // both lookups go through offset_seek (a few cursor steps, else the binary search).  Samples before the chunk come from the
 // entry's pool row (stream_window); a pair inside one chunk takes the equal-length loads.
+// PCM (a BatchPcmArgs last in the pack, alone or behind VARR's / SPOOL's argument): the samples are 16-bit PCM at pc->x.  Where
+// the float build loads a lane's pair as 8 bytes the PCM build loads it as ONE dword at 2-byte alignment (any ld, base or offset
+// parity) and keeps the raw bits in the pair's .x until the window product, where pcm_pair converts them; the edge branches convert
+// sample by sample (pcm_sample; pool rows stay float).  Half the sample registers until the product, the same
+// ones from there on.
 template <bool FIXMEL, bool STFT = false, bool MULTI = false, typename... SA>
 __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args a, const MultiArg<MULTI> mt, const SA... sargs)
 {
@@ -373,6 +389,9 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
     constexpr bool PACKED = VARR || SPOOL;  // units are row pairs of a packed row space
     [[maybe_unused]] const VarRowsArgs *ra = pack_arg<VarRowsArgs>(sargs...);
     [[maybe_unused]] const StftStreamPackedArgs *pa = pack_arg<StftStreamPackedArgs>(sargs...);
+    constexpr bool PCM = (std::is_same_v<SA, BatchPcmArgs> || ...);
+    [[maybe_unused]] const BatchPcmArgs *pc = pack_arg<BatchPcmArgs>(sargs...);
+    static_assert(!PCM || (!STFT && !MULTI && !STREAM), "the PCM builds are the one-block mel-output builds of the three layouts");
     static_assert(!SPOOL || (!STFT && !MULTI && !STREAM && !VARR), "the ragged streaming build is a one-block mel-output build");
     static_assert(!(MULTI && STFT), "the batch-table build is a mel-output build");
     static_assert(!(MULTI && STREAM), "the streaming build takes one block");
@@ -478,6 +497,11 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
         SS_P3(0);
         // ---- the window of this half-wave's row (functions.rs:137-151: the last W samples ending at chunk r + n_pad) ----
         float2 v[32];
+        [[maybe_unused]] bool rawp = false;  // PCM: v[e].x holds the pair's raw dword (the loads of the branch that all lanes are inside)
+        // PCM: sample p of the clip / chunk at xi
+        [[maybe_unused]] auto pcm_chunk = [&](const int16_t *xi) {
+            return [xi, scale = pc ? pc->scale : 0.f](long long p) { return pcm_sample(xi, p, scale); };
+        };
         if constexpr (PACKED) {
             // the clip's own edges: zero before its first sample and past its last, 64-bit sample indices (a clip may start past
             // sample 2^31 of the packed buffer, and at either parity); rows >= real_rows of the clip are inactive (exact zeros)
@@ -492,25 +516,42 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
                 const long long s0 = vc.s0 + start;
                 const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(s0));
                 const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(static_cast<unsigned long long>(s0) >> 32));
-                const char *sb = reinterpret_cast<const char *>(x_b + ((static_cast<unsigned long long>(hi) << 32) | lo));
-                const unsigned so = static_cast<unsigned>(j) * 8u;  // (lane 0 is the pair's first row: half 1 starts a hop later)
-                unsigned so2[2] = {so + static_cast<unsigned>(half) * a.hop * 4u, so + static_cast<unsigned>(half) * a.hop * 4u + 4096u};
-                asm volatile("" : "+v"(so2[1]));
+                if constexpr (PCM) {
+                    // (2 bytes per sample: the 32 dwords of a lane lie within one 4096-byte reach of its offset)
+                    const char *sb = reinterpret_cast<const char *>(pc->x + ((static_cast<unsigned long long>(hi) << 32) | lo));
+                    const unsigned so = static_cast<unsigned>(j) * 4u + static_cast<unsigned>(half) * a.hop * 2u;
 #pragma unroll
-                for (int e = 0; e < 32; ++e) v[e] = *reinterpret_cast<const float2 *>(sb + so2[e / 16] + 256u * (e % 16));
+                    for (int e = 0; e < 32; ++e) v[e] = make_float2(pcm_raw_pair(sb + so + 128u * e), 0.f);
+                    rawp = true;
+                } else {
+                    const char *sb = reinterpret_cast<const char *>(x_b + ((static_cast<unsigned long long>(hi) << 32) | lo));
+                    const unsigned so = static_cast<unsigned>(j) * 8u;  // (lane 0 is the pair's first row: half 1 starts a hop later)
+                    unsigned so2[2] = {so + static_cast<unsigned>(half) * a.hop * 4u, so + static_cast<unsigned>(half) * a.hop * 4u + 4096u};
+                    asm volatile("" : "+v"(so2[1]));
+#pragma unroll
+                    for (int e = 0; e < 32; ++e) v[e] = *reinterpret_cast<const float2 *>(sb + so2[e / 16] + 256u * (e % 16));
+                }
             } else {
                 const float *xc = x_b + (vvalid ? vc.s0 : 0ll);
+                [[maybe_unused]] const int16_t *xi = nullptr;
+                if constexpr (PCM) xi = pc->x + (vvalid ? vc.s0 : 0ll);
                 const long long base = start + 2 * j;
                 if constexpr (SPOOL) {
                     // the dense streaming build's edge loads on the entry's chunk and pool row (an active row's window starts at most
                     // S samples before the chunk and ends inside it: 32-bit indices)
                     const StreamArgs row{pa->e.pool, pa->e.state_len};
-                    stream_window(row, xc, pslot, static_cast<int>(base), static_cast<int>(n), active, v);
+                    if constexpr (PCM) stream_window(row, pcm_chunk(xi), pslot, static_cast<int>(base), static_cast<int>(n), active, v);
+                    else stream_window(row, float_chunk(xc), pslot, static_cast<int>(base), static_cast<int>(n), active, v);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 32; ++e) {
                         const long long p0 = base + 64 * e;
-                        v[e] = make_float2(active && p0 >= 0 && p0 < n ? xc[p0] : 0.f, active && p0 + 1 >= 0 && p0 + 1 < n ? xc[p0 + 1] : 0.f);
+                        if constexpr (PCM) {
+                            const auto xs = pcm_chunk(xi);
+                            v[e] = make_float2(active && p0 >= 0 && p0 < n ? xs(p0) : 0.f, active && p0 + 1 >= 0 && p0 + 1 < n ? xs(p0 + 1) : 0.f);
+                        } else {
+                            v[e] = make_float2(active && p0 >= 0 && p0 < n ? xc[p0] : 0.f, active && p0 + 1 >= 0 && p0 + 1 < n ? xc[p0 + 1] : 0.f);
+                        }
                     }
                 }
             }
@@ -525,18 +566,35 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
                 const unsigned unit_s = __builtin_amdgcn_readfirstlane(unit);
                 const unsigned clip_s = unit_s / pairs;
                 const long long start0 = static_cast<long long>((unit_s - clip_s * pairs) * 2 + a.n_pad + 1) * static_cast<long long>(a.hop) - 2048;
-                const char *sb = reinterpret_cast<const char *>(x_b + static_cast<unsigned long long>(clip_s) * a.ld) + start0 * 4;
-                const unsigned so = static_cast<unsigned>(half) * a.hop * 4u + static_cast<unsigned>(j) * 8u;
-                unsigned so2[2] = {so, so + 4096u};  // (a 32-bit lane offset per 4096 bytes, pinned: left alone the second half's addresses become 64-bit VALU sums)
-                asm volatile("" : "+v"(so2[1]));
+                if constexpr (PCM) {
+                    // (2 bytes per sample: the 32 dwords of a lane lie within one 4096-byte reach of its offset)
+                    const char *sb = reinterpret_cast<const char *>(pc->x + static_cast<unsigned long long>(clip_s) * a.ld) + start0 * 2;
+                    const unsigned so = static_cast<unsigned>(half) * a.hop * 2u + static_cast<unsigned>(j) * 4u;
 #pragma unroll
-                for (int e = 0; e < 32; ++e) v[e] = *reinterpret_cast<const float2 *>(sb + so2[e / 16] + 256u * (e % 16));
+                    for (int e = 0; e < 32; ++e) v[e] = make_float2(pcm_raw_pair(sb + so + 128u * e), 0.f);
+                    rawp = true;
+                } else {
+                    const char *sb = reinterpret_cast<const char *>(x_b + static_cast<unsigned long long>(clip_s) * a.ld) + start0 * 4;
+                    const unsigned so = static_cast<unsigned>(half) * a.hop * 4u + static_cast<unsigned>(j) * 8u;
+                    unsigned so2[2] = {so, so + 4096u};  // (a 32-bit lane offset per 4096 bytes, pinned: left alone the second half's addresses become 64-bit VALU sums)
+                    asm volatile("" : "+v"(so2[1]));
+#pragma unroll
+                    for (int e = 0; e < 32; ++e) v[e] = *reinterpret_cast<const float2 *>(sb + so2[e / 16] + 256u * (e % 16));
+                }
             } else {
                 // clip edges (zero initial state, zero padding of the last chunk, D3) and inactive rows: see ss_mel_c1024
                 const int base = start + 2 * j;
                 const int n = static_cast<int>(a.n_samples);
-                if constexpr (STREAM) {
-                    stream_window(*sa, xc, clip, base, n, active, v);
+                if constexpr (PCM) {
+                    // per sample at either parity (an even start and length would let a pair go as one dword: the edge rows are few)
+                    const auto xs = pcm_chunk(pc->x + static_cast<unsigned long long>(clip) * a.ld);
+#pragma unroll
+                    for (int e = 0; e < 32; ++e) {
+                        const int p0 = base + 64 * e;
+                        v[e] = make_float2(active && p0 >= 0 && p0 < n ? xs(p0) : 0.f, active && p0 + 1 >= 0 && p0 + 1 < n ? xs(p0 + 1) : 0.f);
+                    }
+                } else if constexpr (STREAM) {
+                    stream_window(*sa, float_chunk(xc), clip, base, n, active, v);
                 } else if (((start | n) & 1) == 0) {
                     int e_lo = base >= 0 ? 0 : (63 - base) >> 6;
                     int e_hi = base >= n ? 0 : min(32, (n - base + 63) >> 6);
@@ -560,6 +618,14 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         SS_P3(1);
 #endif
+        // PCM: the pairs the loads above left as raw dwords become the floats the float build loads (pcm_pair: exact) here, in front of
+        // the product that consumes them -- nothing waited for the samples before (rawp is uniform)
+        if constexpr (PCM) {
+            if (rawp) {
+#pragma unroll
+                for (int e = 0; e < 32; ++e) v[e] = pcm_pair(__float_as_int(v[e].x), pc->scale);
+            }
+        }
         // Vorbis window (config.rs:151-160): two batches of eight reads, each in front of its products
 #pragma unroll
         for (int eb = 0; eb < 16; eb += 8) {
@@ -787,19 +853,26 @@ hipError_t launch_mel_w(const Mel2048Args &a, hipStream_t stream, int num_cus, L
 }
 
 // three waves per SIMD, direct stores (see ss_mel_c1024_w12): mel output with the reference bank shape, and stft
-hipError_t launch_mel_w12(const Mel2048Args &a, hipStream_t stream, int num_cus, LaunchInfo *info)
+// (p, here and in the two packed launchers below: empty -- floats at a.x -- or one BatchPcmArgs, the PCM builds: mel output only)
+template <typename... P>
+hipError_t launch_mel_w12(const Mel2048Args &a, hipStream_t stream, int num_cus, LaunchInfo *info, const P &...p)
 {
-    if (a.fullp || a.batch == 0) return hipErrorInvalidValue;
+    constexpr bool PCM = sizeof...(P) != 0;
+    if (a.fullp || a.batch == 0 || (PCM && a.out_stft)) return hipErrorInvalidValue;
     const size_t lds = mel_lds_bytes(12, a.mel_wpitch);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * (a.out_stft ? (a.rows + 1) / 2 : mel_work_pairs(a.rows, a.real_rows));
     if (units >= 0xffffffffull) return hipErrorInvalidValue;
     const unsigned grid = mel_grid(units, 12, num_cus);
     const MultiArg<false> none{};
-    if (a.out_stft) return mel_go(ss_mel_c1024_w12<false, true>, "ss_mel_c1024<w12,stft>", grid, 12, lds, stream, info, a, none);
+    if constexpr (!PCM) {
+        if (a.out_stft) return mel_go(ss_mel_c1024_w12<false, true>, "ss_mel_c1024<w12,stft>", grid, 12, lds, stream, info, a, none);
+    }
     const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
-    return m6321 ? mel_go(ss_mel_c1024_w12<true>, "ss_mel_c1024<w12,mel6321>", grid, 12, lds, stream, info, a, none)
-                 : mel_go(ss_mel_c1024_w12<false>, "ss_mel_c1024<w12>", grid, 12, lds, stream, info, a, none);
+    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, P...>, PCM ? "ss_mel_c1024i<w12,mel6321>" : "ss_mel_c1024<w12,mel6321>", grid, 12, lds,
+                          stream, info, a, none, p...)
+                 : mel_go(ss_mel_c1024_w12<false, false, false, P...>, PCM ? "ss_mel_c1024i<w12>" : "ss_mel_c1024<w12>", grid, 12, lds, stream, info, a,
+                          none, p...);
 }
 
 // the streaming builds (mel output): eight waves (the reference bank shape or every bin) / twelve waves (the reference bank shape)
@@ -827,8 +900,10 @@ hipError_t launch_mel_w12_stream(const Mel2048Args &a, const StreamArgs &s, hipS
                  : mel_go(ss_mel_c1024_w12<false, false, false, StreamArgs>, "ss_mel_c1024s<w12>", grid, 12, lds, stream, info, a, none, s);
 }
 
-hipError_t launch_mel_w12_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+template <typename... P>
+hipError_t launch_mel_w12_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info, const P &...p)
 {
+    constexpr bool PCM = sizeof...(P) != 0;
     const size_t lds = mel_lds_bytes(12, a.mel_wpitch);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     // an empty output block still gets one workgroup: the clip pass runs
@@ -836,12 +911,17 @@ hipError_t launch_mel_w12_varlen(const Mel2048Args &a, const VarRowsArgs &v, hip
     const unsigned grid = units ? mel_grid(units, 12, num_cus) : 1u;
     const MultiArg<false> none{};
     const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
-    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, VarRowsArgs>, "ss_mel_c1024v<w12,mel6321>", grid, 12, lds, stream, info, a, none, v)
-                 : mel_go(ss_mel_c1024_w12<false, false, false, VarRowsArgs>, "ss_mel_c1024v<w12>", grid, 12, lds, stream, info, a, none, v);
+    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, VarRowsArgs, P...>, PCM ? "ss_mel_c1024vi<w12,mel6321>" : "ss_mel_c1024v<w12,mel6321>",
+                          grid, 12, lds, stream, info, a, none, v, p...)
+                 : mel_go(ss_mel_c1024_w12<false, false, false, VarRowsArgs, P...>, PCM ? "ss_mel_c1024vi<w12>" : "ss_mel_c1024v<w12>", grid, 12, lds,
+                          stream, info, a, none, v, p...);
 }
 
-hipError_t launch_mel_w12_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
+template <typename... P>
+hipError_t launch_mel_w12_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info,
+                                        const P &...p)
 {
+    constexpr bool PCM = sizeof...(P) != 0;
     const size_t lds = mel_lds_bytes(12, a.mel_wpitch);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     // an empty output block still gets one workgroup: the entry pass runs
@@ -849,8 +929,10 @@ hipError_t launch_mel_w12_stream_packed(const Mel2048Args &a, const StftStreamPa
     const unsigned grid = units ? mel_grid(units, 12, num_cus) : 1u;
     const MultiArg<false> none{};
     const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
-    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, StftStreamPackedArgs>, "ss_mel_c1024sp<w12,mel6321>", grid, 12, lds, stream, info, a, none, s)
-                 : mel_go(ss_mel_c1024_w12<false, false, false, StftStreamPackedArgs>, "ss_mel_c1024sp<w12>", grid, 12, lds, stream, info, a, none, s);
+    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, StftStreamPackedArgs, P...>,
+                          PCM ? "ss_mel_c1024spi<w12,mel6321>" : "ss_mel_c1024sp<w12,mel6321>", grid, 12, lds, stream, info, a, none, s, p...)
+                 : mel_go(ss_mel_c1024_w12<false, false, false, StftStreamPackedArgs, P...>, PCM ? "ss_mel_c1024spi<w12>" : "ss_mel_c1024sp<w12>", grid,
+                          12, lds, stream, info, a, none, s, p...);
 }
 
 }  // namespace
@@ -888,6 +970,22 @@ hipError_t launch_mel_c1024_multi(const Mel2048Args &a_in, int n_batches, const 
     return mel_go(ss_mel_c1024_w12<true, false, true>, "ss_mel_c1024m<w12,mel6321>", mel_grid(units, 12, num_cus), 12, lds, stream, info, a, mt);
 }
 
+// mel output, launch_mel_c1024's choice between the eight- and the twelve-wave build (ss_debug_mel_tile(1 / 2) asks for eight waves,
+// ss_debug_mel_tile(3) for twelve wherever that build exists)
+static bool mel_takes_twelve_waves(const Mel2048Args &a, unsigned long long units, int num_cus)
+{
+    return !a.out_stft && !a.fullp && dbg_mel_build() != 1 && dbg_mel_build() != 2 && (twelve_waves_win(units, num_cus) || dbg_mel_build() == 3);
+}
+// lab library: an A/B knob of launch_mel_c1024 is set (those builds exist for floats only)
+static bool mel_lab_knobs()
+{
+#if SS_LAB
+    return std::getenv("SS_MEL_WAVES") != nullptr;
+#else
+    return false;
+#endif
+}
+
 hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * (a.out_stft ? (a.rows + 1) / 2 : mel_work_pairs(a.rows, a.real_rows));
@@ -915,11 +1013,20 @@ hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cu
         }
         return launch_mel_w<8>(a, stream, num_cus, info);
     }
-    if (!a.out_stft && !a.fullp && dbg_mel_build() != 1 && dbg_mel_build() != 2 && (twelve_waves_win(units, num_cus) || dbg_mel_build() == 3)) {
+    if (mel_takes_twelve_waves(a, units, num_cus)) {
         const hipError_t e = launch_mel_w12(a, stream, num_cus, info);
         if (e != hipErrorInvalidValue) return e;
     }
     return launch_mel_w<8>(a, stream, num_cus, info);
+}
+
+hipError_t launch_mel_c1024(const Mel2048Args &a, const BatchPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    // the float call's rule, so that the PCM call runs the PCM build of the very kernel the float call runs (the eight- and
+    // twelve-wave builds round a few FMAs differently in the last bit); everything else is the caller's conversion fallback
+    const unsigned long long units = static_cast<unsigned long long>(a.batch) * mel_work_pairs(a.rows, a.real_rows);
+    if (!p.x || a.out_stft || mel_lab_knobs() || !mel_takes_twelve_waves(a, units, num_cus)) return hipErrorInvalidValue;
+    return launch_mel_w12(a, stream, num_cus, info, p);
 }
 
 hipError_t launch_mel_c1024_stream(const Mel2048Args &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
@@ -945,6 +1052,13 @@ hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, h
     return launch_mel_w12_varlen(a, v, stream, num_cus, info);
 }
 
+hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, const BatchPcmArgs &p, hipStream_t stream, int num_cus,
+                                   LaunchInfo *info)
+{
+    if (!p.x || a.out_stft || a.fullp || v.n_clips == 0 || v.total_rows >= (1ull << 31)) return hipErrorInvalidValue;  // (as above)
+    return launch_mel_w12_varlen(a, v, stream, num_cus, info, p);
+}
+
 hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
     // always twelve waves (never twelve_waves_win): see launch_mel_c1024_varlen -- an entry's bits must not depend on which other
@@ -953,6 +1067,15 @@ hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStream
         s.e.state_len + a.hop != 2048u || !s.e.pool)
         return hipErrorInvalidValue;
     return launch_mel_w12_stream_packed(a, s, stream, num_cus, info);
+}
+
+hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, const BatchPcmArgs &p, hipStream_t stream,
+                                          int num_cus, LaunchInfo *info)
+{
+    if (!p.x || a.out_stft || a.fullp || s.e.n_active == 0 || s.e.total_rows >= 0x7fffffffu || a.hop == 0 || a.n_pad != 0 ||
+        s.e.step != a.hop || s.e.state_len + a.hop != 2048u || !s.e.pool)
+        return hipErrorInvalidValue;  // (as above)
+    return launch_mel_w12_stream_packed(a, s, stream, num_cus, info, p);
 }
 
 }  // namespace ss

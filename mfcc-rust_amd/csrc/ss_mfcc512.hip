@@ -343,22 +343,7 @@ __device__ __forceinline__ unsigned load_quad_stream_packed_pcm(const Fast512Arg
     }
     return t;
 }
-// the two samples of a PCM dword: sign-extended, converted, times the power-of-two scale (exact: the bits the float loader finds in
-// the converted buffer)
-__device__ __forceinline__ float2 pcm_pair(int w, float scale)
-{
-    return make_float2(static_cast<float>(static_cast<int16_t>(w)) * scale, static_cast<float>(w >> 16) * scale);
-}
 
-// The raw dword of a PCM sample pair: two int16, fetched by one 32-bit load at 2-byte alignment (a pair may start at an odd sample:
-// odd ld, odd base, odd clip offset).  gfx950 global loads take any alignment in the unaligned access mode the HSA ABI sets -- the
-// mode the float builds' 8-byte pair loads at dword alignment already rely on -- so one load serves either parity.
-__device__ __forceinline__ float pcm_raw_pair(const void *p)
-{
-    int w;
-    __builtin_memcpy(&w, __builtin_assume_aligned(p, 2), sizeof w);
-    return __int_as_float(w);
-}
 
 // PCM builds (a trailing BatchPcmArgs): load_quad's contract framing with the samples as signed 16-bit PCM.  The loader only
 // fetches: a pair's dword stays, as raw bits, in vin[e].x until the quad is consumed (pcm_pair) -- as in the STRPI builds, converting

@@ -107,6 +107,31 @@ extern "C" {
                           out: *mut f32) -> c_int;
     fn ss_mfe_packed_i16(cfg: *const SsConfig, x: *const i16, n_clips: usize, sample_offsets: *const i64, scale: f32, feat: *mut f32,
                          energy: *mut f32) -> c_int;
+    fn ss_mel_spectrogram_i16_device(cfg: *const SsConfig, d_x: *const i16, channels: usize, n: usize, ld: usize, scale: f32,
+                                     d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_stft_i16_device(cfg: *const SsConfig, d_x: *const i16, channels: usize, n: usize, ld: usize, scale: f32, d_out: *mut f32,
+                          stream: *mut c_void) -> c_int;
+    fn ss_mel_spectrogram_i16(cfg: *const SsConfig, x: *const i16, channels: usize, n: usize, scale: f32, out: *mut f32) -> c_int;
+    fn ss_stft_i16(cfg: *const SsConfig, x: *const i16, channels: usize, n: usize, scale: f32, out: *mut f32) -> c_int;
+    fn ss_mel_spectrogram_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64,
+                                            scale: f32, d_row_offsets: *const i64, total_rows: usize, d_out: *mut f32,
+                                            stream: *mut c_void) -> c_int;
+    fn ss_stft_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64, scale: f32,
+                                 d_row_offsets: *const i64, total_rows: usize, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_mel_spectrogram_packed_i16(cfg: *const SsConfig, x: *const i16, n_clips: usize, sample_offsets: *const i64, scale: f32,
+                                     out: *mut f32) -> c_int;
+    fn ss_stft_packed_i16(cfg: *const SsConfig, x: *const i16, n_clips: usize, sample_offsets: *const i64, scale: f32,
+                          out: *mut f32) -> c_int;
+    fn ss_mel_spectrogram_stream_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_active: usize, d_sample_offsets: *const i64,
+                                                   d_row_offsets: *const i64, total_rows: usize, d_slots: *const i32, pool_streams: usize,
+                                                   scale: f32, d_pool: *mut f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_stft_stream_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_active: usize, d_sample_offsets: *const i64,
+                                        d_row_offsets: *const i64, total_rows: usize, d_slots: *const i32, pool_streams: usize,
+                                        scale: f32, d_pool: *mut f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_mel_spectrogram_stream_packed_i16(cfg: *const SsConfig, x: *const i16, n_active: usize, sample_offsets: *const i64,
+                                            slots: *const i32, pool_streams: usize, scale: f32, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_stft_stream_packed_i16(cfg: *const SsConfig, x: *const i16, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                                 pool_streams: usize, scale: f32, pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_preemphasis(x: *const f32, n: usize, shift: c_long, cof: f32, y: *mut f32) -> c_int;
     fn ss_frame_sizes(p: *const SsParams, frame_len: *mut usize, frame_step: *mut usize) -> c_int;
     fn ss_stft(cfg: *const SsConfig, x: *const f32, channels: usize, n: usize, out: *mut f32) -> c_int;
@@ -528,6 +553,122 @@ pub fn try_mfe_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64],
     }
     check(unsafe { ss_mfe_packed_i16(cfg.raw(), x.as_ptr(), sample_offsets.len() - 1, sample_offsets.as_ptr(), scale, feat.as_mut_ptr(),
                                      energy.as_mut_ptr()) })
+}
+
+/// The mel spectrogram / STFT calls fed signed 16-bit PCM (`ss_mel_spectrogram_i16_device`, `ss_stft_i16_device` and their packed and
+/// pool forms): the float forms with the samples as int16, sample = `pcm as f32 * scale`, `scale` a power of two in `[2^-64, 2^64]`;
+/// bit for bit the float call on the converted buffer.  `ld` and the offsets are in samples; `d_x` needs 2-byte alignment only
+/// (4-byte for the pool forms).  `d_out`: `[channels x num_filters x rows]`.
+/// # Safety
+/// Every pointer is a device allocation of the size the header states, on the device the config was created on.
+pub unsafe fn mel_spectrogram_i16_device(cfg: &SpeechConfig, d_x: *const i16, channels: usize, n: usize, ld: usize, scale: f32,
+                                         d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_mel_spectrogram_i16_device(cfg.raw(), d_x, channels, n, ld, scale, d_out, stream))
+}
+
+/// The stft form of `mel_spectrogram_i16_device`: `d_out` `[channels x rows x (fft_points / 2 + 1) x 2]`.
+/// # Safety
+/// As `mel_spectrogram_i16_device`.
+pub unsafe fn stft_i16_device(cfg: &SpeechConfig, d_x: *const i16, channels: usize, n: usize, ld: usize, scale: f32, d_out: *mut f32,
+                              stream: *mut c_void) -> Result<(), Error> {
+    check(ss_stft_i16_device(cfg.raw(), d_x, channels, n, ld, scale, d_out, stream))
+}
+
+/// Packed variable-length clips (`ss_mel_spectrogram_packed_i16_device`): clip `b` is `d_x[so[b]..so[b + 1]]`, its `[num_filters x R_b]`
+/// block starts at `d_out + num_filters * ro[b]`; the tables are device arrays.
+/// # Safety
+/// As `mel_spectrogram_i16_device`.
+pub unsafe fn mel_spectrogram_packed_i16_device(cfg: &SpeechConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64,
+                                                scale: f32, d_row_offsets: *const i64, total_rows: usize, d_out: *mut f32,
+                                                stream: *mut c_void) -> Result<(), Error> {
+    check(ss_mel_spectrogram_packed_i16_device(cfg.raw(), d_x, n_clips, d_sample_offsets, scale, d_row_offsets, total_rows, d_out, stream))
+}
+
+/// The stft form of `mel_spectrogram_packed_i16_device`: clip `b` owns rows `ro[b]..ro[b + 1]` of `d_out`.
+/// # Safety
+/// As `mel_spectrogram_i16_device`.
+pub unsafe fn stft_packed_i16_device(cfg: &SpeechConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64, scale: f32,
+                                     d_row_offsets: *const i64, total_rows: usize, d_out: *mut f32, stream: *mut c_void)
+                                     -> Result<(), Error> {
+    check(ss_stft_packed_i16_device(cfg.raw(), d_x, n_clips, d_sample_offsets, scale, d_row_offsets, total_rows, d_out, stream))
+}
+
+/// The ragged streaming pool (`ss_mel_spectrogram_stream_packed_i16_device`): entry `i` is the chunk `d_x[so[i]..so[i + 1]]` (whole
+/// hops) of the stream whose state is row `d_slots[i]` of the `[pool_streams x S]` float pool.  Two asynchronous launches.
+/// # Safety
+/// As `mel_spectrogram_i16_device`; `d_x` is 4-byte aligned.
+pub unsafe fn mel_spectrogram_stream_packed_i16_device(cfg: &SpeechConfig, d_x: *const i16, n_active: usize, d_sample_offsets: *const i64,
+                                                       d_row_offsets: *const i64, total_rows: usize, d_slots: *const i32,
+                                                       pool_streams: usize, scale: f32, d_pool: *mut f32, d_out: *mut f32,
+                                                       stream: *mut c_void) -> Result<(), Error> {
+    check(ss_mel_spectrogram_stream_packed_i16_device(cfg.raw(), d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots,
+                                                      pool_streams, scale, d_pool, d_out, stream))
+}
+
+/// The stft form of `mel_spectrogram_stream_packed_i16_device`.
+/// # Safety
+/// As `mel_spectrogram_stream_packed_i16_device`.
+pub unsafe fn stft_stream_packed_i16_device(cfg: &SpeechConfig, d_x: *const i16, n_active: usize, d_sample_offsets: *const i64,
+                                            d_row_offsets: *const i64, total_rows: usize, d_slots: *const i32, pool_streams: usize,
+                                            scale: f32, d_pool: *mut f32, d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_stft_stream_packed_i16_device(cfg.raw(), d_x, n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams,
+                                           scale, d_pool, d_out, stream))
+}
+
+/// Host-pointer forms: the samples cross the link as int16.  `x` holds `channels` rows of `n` samples; `out` is
+/// `[channels x num_filters x rows]`.  Synchronous.
+pub fn try_mel_spectrogram_i16(cfg: &SpeechConfig, x: &[i16], channels: usize, n: usize, scale: f32, out: &mut [f32]) -> Result<(), Error> {
+    if x.len() < channels * n {
+        return Err(Error { status: SS_ERR_ARG, detail: "x is shorter than channels rows of n samples".to_string() });
+    }
+    check(unsafe { ss_mel_spectrogram_i16(cfg.raw(), x.as_ptr(), channels, n, scale, out.as_mut_ptr()) })
+}
+
+/// The stft form of `try_mel_spectrogram_i16`: `out` `[channels x rows x (fft_points / 2 + 1) x 2]`.
+pub fn try_stft_i16(cfg: &SpeechConfig, x: &[i16], channels: usize, n: usize, scale: f32, out: &mut [f32]) -> Result<(), Error> {
+    if x.len() < channels * n {
+        return Err(Error { status: SS_ERR_ARG, detail: "x is shorter than channels rows of n samples".to_string() });
+    }
+    check(unsafe { ss_stft_i16(cfg.raw(), x.as_ptr(), channels, n, scale, out.as_mut_ptr()) })
+}
+
+/// Packed clips from an int16 host buffer: `sample_offsets` holds `n_clips + 1` offsets in samples, `out` the clips' blocks end to end.
+pub fn try_mel_spectrogram_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64], scale: f32, out: &mut [f32])
+                                      -> Result<(), Error> {
+    if sample_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have n_clips + 1 entries".to_string() });
+    }
+    check(unsafe { ss_mel_spectrogram_packed_i16(cfg.raw(), x.as_ptr(), sample_offsets.len() - 1, sample_offsets.as_ptr(), scale,
+                                                 out.as_mut_ptr()) })
+}
+
+/// The stft form of `try_mel_spectrogram_packed_i16`.
+pub fn try_stft_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64], scale: f32, out: &mut [f32]) -> Result<(), Error> {
+    if sample_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have n_clips + 1 entries".to_string() });
+    }
+    check(unsafe { ss_stft_packed_i16(cfg.raw(), x.as_ptr(), sample_offsets.len() - 1, sample_offsets.as_ptr(), scale, out.as_mut_ptr()) })
+}
+
+/// Host-pointer form of the PCM pool call: `x` the packed int16 chunks, `sample_offsets` `n_active + 1` offsets in samples, `slots`
+/// the pool row of each entry, `pool` the `[pool_streams x S]` float states (updated in place).  Synchronous.
+pub fn try_mel_spectrogram_stream_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64], slots: &[i32], pool_streams: usize,
+                                             scale: f32, pool: &mut [f32], out: &mut [f32]) -> Result<(), Error> {
+    if sample_offsets.len() != slots.len() + 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have one entry more than slots".to_string() });
+    }
+    check(unsafe { ss_mel_spectrogram_stream_packed_i16(cfg.raw(), x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(),
+                                                        pool_streams, scale, pool.as_mut_ptr(), out.as_mut_ptr()) })
+}
+
+/// The stft form of `try_mel_spectrogram_stream_packed_i16`.
+pub fn try_stft_stream_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64], slots: &[i32], pool_streams: usize, scale: f32,
+                                  pool: &mut [f32], out: &mut [f32]) -> Result<(), Error> {
+    if sample_offsets.len() != slots.len() + 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have one entry more than slots".to_string() });
+    }
+    check(unsafe { ss_stft_stream_packed_i16(cfg.raw(), x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams,
+                                             scale, pool.as_mut_ptr(), out.as_mut_ptr()) })
 }
 
 /// functions.rs:86-123: `[channels, samples]` -> `Array3<Complex32>` `[channels, rows, freq_size]`

@@ -229,9 +229,11 @@ def _internal_mfe_batch(signal, config: SpeechConfig, scale=None):
     return feat, en
 
 
-def _internal_mel_spectrogram(signal, config: SpeechConfig):
-    """1-D -> [n_mels, rows]; 2-D [C, L] -> [C, n_mels, rows] (py-speechsauce/src/lib.rs:179-204)."""
+def _internal_mel_spectrogram(signal, config: SpeechConfig, scale=None):
+    """1-D -> [n_mels, rows]; 2-D [C, L] -> [C, n_mels, rows] (py-speechsauce/src/lib.rs:179-204); scale: the signal is int16
+    PCM, sample = int16 * scale (the ``_i16`` entry points)."""
     lib = _lib.lib()
+    i16, sc = ("", []) if scale is None else ("_i16", [scale])
     one_d = signal.ndim == 1
     sig2 = signal[None, :] if one_d else signal
     ch, L = sig2.shape
@@ -243,12 +245,12 @@ def _internal_mel_spectrogram(signal, config: SpeechConfig):
         x = sig2 if sig2.stride(1) == 1 else sig2.contiguous()
         out = torch.empty((ch, M, R), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.ss_mel_spectrogram_device(config.handle, x.data_ptr(), ch, L, x.stride(0) if ch > 1 else L,
-                                                     out.data_ptr(), _stream_ptr()))
+            _lib.check(getattr(lib, f"ss_mel_spectrogram{i16}_device")(config.handle, x.data_ptr(), ch, L, x.stride(0) if ch > 1 else L, *sc,
+                                                                       out.data_ptr(), _stream_ptr()))
     else:
         x = np.ascontiguousarray(sig2)
         out = np.empty((ch, M, R), dtype=np.float32)
-        _lib.check(lib.ss_mel_spectrogram(config.handle, x.ctypes.data, ch, L, out.ctypes.data))
+        _lib.check(getattr(lib, f"ss_mel_spectrogram{i16}")(config.handle, x.ctypes.data, ch, L, *sc, out.ctypes.data))
     return out[0] if one_d else out
 
 
@@ -491,10 +493,13 @@ def _row_offsets(config: SpeechConfig, so):
     return ro
 
 
-def _internal_stft_packed(signal, so, config: SpeechConfig, stft: bool):
+def _internal_stft_packed(signal, so, config: SpeechConfig, stft: bool, scale=None):
     """signal [N] packed clips, sample offsets so -> (flat float32 block, row_offsets [n + 1]): mel [num_filters * sum R_b] or stft
-    [sum R_b, F, 2].  The row offsets are a device tensor where the signal is one."""
+    [sum R_b, F, 2].  The row offsets are a device tensor where the signal is one.  scale: the signal is int16 PCM (the ``_i16``
+    entry points)."""
     lib = _lib.lib()
+    i16, sc = ("", []) if scale is None else ("_i16", [scale])
+    name = "ss_stft_packed" if stft else "ss_mel_spectrogram_packed"
     ro = _row_offsets(config, so)
     n, rows = so.size - 1, int(ro[-1])
     F = config.params.fft_points // 2 + 1
@@ -506,34 +511,36 @@ def _internal_stft_packed(signal, so, config: SpeechConfig, stft: bool):
         with torch.cuda.device(x.device):
             dso, dro = torch.from_numpy(so).to(x.device), torch.from_numpy(ro).to(x.device)
             out = torch.empty(shape, dtype=torch.float32, device=x.device)
-            fn = lib.ss_stft_packed_device if stft else lib.ss_mel_spectrogram_packed_device
-            _lib.check(fn(config.handle, x.data_ptr(), n, dso.data_ptr(), dro.data_ptr(), rows, out.data_ptr(), _stream_ptr()))
+            _lib.check(getattr(lib, f"{name}{i16}_device")(config.handle, x.data_ptr(), n, dso.data_ptr(), *sc, dro.data_ptr(), rows,
+                                                           out.data_ptr(), _stream_ptr()))
         return out, dro
     x = np.ascontiguousarray(signal)
     out = np.empty(shape, dtype=np.float32)
-    fn = lib.ss_stft_packed if stft else lib.ss_mel_spectrogram_packed
-    _lib.check(fn(config.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data))
+    _lib.check(getattr(lib, f"{name}{i16}")(config.handle, x.ctypes.data, n, so.ctypes.data, *sc, out.ctypes.data))
     return out, ro
 
 
 def mel_spectrogram_packed(signal, lengths, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13,
-                           num_filters=40, fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+                           num_filters=40, fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, pcm_scale=None,
+                           **switches):
     """Mel spectrogram of clips of different lengths packed end to end in one 1-D float32 signal (clip b = the lengths[b]
     samples after the clips before it) -> (out, row_offsets [n + 1] int64).  ``out`` is the flat float32 block of
     num_filters * sum R_b values: clip b's [num_filters, R_b] block, what ``mel_spectrogram`` returns for that clip alone, starts
-    at num_filters * row_offsets[b].  One launch for all clips."""
-    sig = _require_f32(signal, (1,), "mel_spectrogram_packed")
+    at num_filters * row_offsets[b].  One launch for all clips.  ``pcm_scale``: the packed signal is int16 PCM (see
+    ``mel_spectrogram``)."""
+    sig, scale = _require_signal(signal, (1,), "mel_spectrogram_packed", pcm_scale)
     so = _sample_offsets(lengths, sig.shape[0], "mel_spectrogram_packed")
     config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
                   low_frequency, high_frequency, dc_elimination, switches, sig)
-    return _internal_stft_packed(sig, so, config, False)
+    return _internal_stft_packed(sig, so, config, False, scale)
 
 
 def mel_spectrogram_list(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
-                         fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, **switches):
+                         fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, pcm_scale=None, **switches):
     """A list of 1-D float32 clips of any lengths -> the list of their [num_filters, R_b] mel spectrograms (views of one block):
-    the clips are packed once and served by one mel_spectrogram_packed call."""
-    sigs = [_require_f32(x, (1,), "mel_spectrogram_list") for x in signals]
+    the clips are packed once and served by one mel_spectrogram_packed call.  ``pcm_scale``: the clips are int16 PCM (see
+    ``mel_spectrogram``)."""
+    sigs = [_require_signal(x, (1,), "mel_spectrogram_list", pcm_scale)[0] for x in signals]
     if not sigs:
         return []
     on_device = [_is_torch(x) for x in sigs]  # (_require_f32 turns host tensors into arrays)
@@ -549,20 +556,21 @@ def mel_spectrogram_list(signals, sampling_frequency, frame_length=0.020, frame_
         packed = np.concatenate(sigs)
     lengths = [int(x.shape[0]) for x in sigs]
     out, ro = mel_spectrogram_packed(packed, lengths, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters,
-                                     fft_length, low_frequency, high_frequency, dc_elimination, **switches)
+                                     fft_length, low_frequency, high_frequency, dc_elimination, pcm_scale, **switches)
     ro = ro.tolist()
     M = int(num_filters)
     return [out[M * ro[b]:M * ro[b + 1]].reshape(M, ro[b + 1] - ro[b]) for b in range(len(sigs))]
 
 
-def stft_packed(signal, lengths, sampling_frequency, frame_length=0.020, fft_length=512, **switches):
+def stft_packed(signal, lengths, sampling_frequency, frame_length=0.020, fft_length=512, pcm_scale=None, **switches):
     """``stft`` of packed clips (see mel_spectrogram_packed) -> (complex64 [sum R_b, fft_length // 2 + 1], row_offsets [n + 1]):
     clip b's rows are row_offsets[b] : row_offsets[b + 1], what ``stft`` returns for that clip alone.  numpy in -> numpy out; a
-    ROCm tensor stays on the device (torch.complex64 view of the interleaved block)."""
-    sig = _require_f32(signal, (1,), "stft_packed")
+    ROCm tensor stays on the device (torch.complex64 view of the interleaved block).  ``pcm_scale``: the packed signal is int16
+    PCM (see ``mel_spectrogram``)."""
+    sig, scale = _require_signal(signal, (1,), "stft_packed", pcm_scale)
     so = _sample_offsets(lengths, sig.shape[0], "stft_packed")
     config = _cfg(sampling_frequency, frame_length, 0.01, 13, 40, fft_length, 0, None, True, switches, sig)
-    out, ro = _internal_stft_packed(sig, so, config, True)
+    out, ro = _internal_stft_packed(sig, so, config, True, scale)
     if _is_torch(out):
         import torch
 
@@ -662,15 +670,20 @@ def power_to_db(S, ref=1.0, amin=1e-10, top_db=80.0):
 
 def mel_spectrogram(signal, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13,
                     num_filters=40, fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True,
-                    **switches):
+                    pcm_scale=None, **switches):
     """Mel spectrogram of a 1-D or 2-D float32 signal -> (..., n_mels, time).
 
     Mirrors ``speechsauce.mel_spectrogram`` (py-speechsauce/speechsauce/__init__.py:85-132 ->
     feature.rs:151-174).  The STFT hop is ``frame_length * sampling_frequency`` samples and the
     window is ``fft_length`` samples (config.rs:154, functions.rs:96-101); the reference panics
     unless ``fft_length >= 2 * hop`` -- that raises SpeechSauceError here.
+
+    ``pcm_scale``: the signal is int16 PCM, converted on load as ``int16 * pcm_scale`` (see ``mfcc``); the result is bit for bit
+    that of the float call on ``signal.astype(float32) * pcm_scale`` (``ss_mel_spectrogram_i16*``).
     """
     if isinstance(signal, (list, tuple)):
+        if pcm_scale is not None:
+            raise ValueError("mel_spectrogram: pcm_scale takes a single signal, not a list of blocks")
         # several [C_i, L] blocks (same L) -> the list of their [C_i, n_mels, time] spectrograms from ONE call (device tensors:
         # ss_mel_spectrogram_batches_device -- one launch where the configuration's kernel takes a batch table)
         sigs = [_require_f32(x, (2,), "mel_spectrogram") for x in signal]
@@ -679,23 +692,25 @@ def mel_spectrogram(signal, sampling_frequency, frame_length=0.020, frame_stride
         config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
                       low_frequency, high_frequency, dc_elimination, switches, sigs[0])
         return _internal_mel_spectrogram_batches(sigs, config)
-    sig = _require_f32(signal, (1, 2), "mel_spectrogram")
+    sig, scale = _require_signal(signal, (1, 2), "mel_spectrogram", pcm_scale)
     config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
                   low_frequency, high_frequency, dc_elimination, switches, sig)
-    return _internal_mel_spectrogram(sig, config)
+    return _internal_mel_spectrogram(sig, config, scale)
 
 
 # ---- stage outputs the reference exposes as pub fns: processing::{stack_frames, power_spectrum}, functions::{stft1, stft2} ----
 
-def stft(signal, sampling_frequency, frame_length=0.020, fft_length=512, **switches):
+def stft(signal, sampling_frequency, frame_length=0.020, fft_length=512, pcm_scale=None, **switches):
     """``speechsauce::functions::stft1`` (1-D signal, functions.rs:199-233) / ``stft2`` (2-D [C, L], functions.rs:86-123):
     complex64 spectrum rows ``(..., rows, fft_length // 2 + 1)`` of the Vorbis-windowed chunks, scaled by wnorm, from zero
     state per clip.  The hop is ``frame_length * sampling_frequency`` samples, the window ``fft_length`` samples
     (config.rs:154); ``fft_length >= 2 * hop`` as in ``mel_spectrogram``.  numpy in -> numpy out; a ROCm tensor stays on
-    the device (torch.complex64 view of the interleaved block)."""
-    sig = _require_f32(signal, (1, 2), "stft")
+    the device (torch.complex64 view of the interleaved block).  ``pcm_scale``: the signal is int16 PCM (see
+    ``mel_spectrogram``)."""
+    sig, scale = _require_signal(signal, (1, 2), "stft", pcm_scale)
     config = _cfg(sampling_frequency, frame_length, 0.01, 13, 40, fft_length, 0, None, True, switches, sig)
     lib = _lib.lib()
+    i16, sc = ("", []) if scale is None else ("_i16", [scale])
     one_d = sig.ndim == 1
     sig2 = sig[None, :] if one_d else sig
     ch, L = sig2.shape
@@ -707,12 +722,13 @@ def stft(signal, sampling_frequency, frame_length=0.020, fft_length=512, **switc
         x = sig2 if sig2.stride(1) == 1 else sig2.contiguous()
         out = torch.empty((ch, R, F, 2), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.ss_stft_device(config.handle, x.data_ptr(), ch, L, x.stride(0) if ch > 1 else L, out.data_ptr(), _stream_ptr()))
+            _lib.check(getattr(lib, f"ss_stft{i16}_device")(config.handle, x.data_ptr(), ch, L, x.stride(0) if ch > 1 else L, *sc, out.data_ptr(),
+                                                            _stream_ptr()))
         z = torch.view_as_complex(out)
     else:
         x = np.ascontiguousarray(sig2)
         out = np.empty((ch, R, F, 2), dtype=np.float32)
-        _lib.check(lib.ss_stft(config.handle, x.ctypes.data, ch, L, out.ctypes.data))
+        _lib.check(getattr(lib, f"ss_stft{i16}")(config.handle, x.ctypes.data, ch, L, *sc, out.ctypes.data))
         z = out.view(np.complex64)[..., 0]
     return z[0] if one_d else z
 
@@ -1056,6 +1072,14 @@ class _StreamPoolMixin:
         ro = so // self.hop
         return packed, so, ro, np.asarray(slot_list, dtype=np.int32), config
 
+    def _prepare_pcm(self, chunks, slots, lengths, pcm_scale):
+        """``_prepare_pool`` of either chunk format, and what ``_call_pool`` needs for it: the suffix of the entry points' names
+        and the arguments between ``pool_streams`` and the state."""
+        if pcm_scale is None:
+            return self._prepare_pool(chunks, slots, lengths), "", []
+        scale = _check_pcm_scale(pcm_scale, self._what)
+        return self._prepare_pool(chunks, slots, lengths, pcm=True), "_i16", [scale]
+
     def _call_pool(self, packed, so, ro, sl, config, outs, dev_fn, host_fn, extra):
         lib = _lib.lib()
         n_active = sl.size
@@ -1094,14 +1118,6 @@ class _FrameStreamPoolBase(_StreamPoolMixin, _FrameStreamBase):
     arrays / tensors only -- and converts on load: stream sample = ``int16 * pcm_scale``, ``pcm_scale`` a power of two in
     ``[2**-64, 2**64]``.  The rows and the state are bit for bit those of the float call on ``chunk.astype(float32) * pcm_scale``;
     the state stays float32, so a stream may be fed PCM on one call and floats on the next (``ss_mfcc_stream_packed_i16``)."""
-
-    def _prepare_pcm(self, chunks, slots, lengths, pcm_scale):
-        """``_prepare_pool`` of either chunk format, and what ``_call_pool`` needs for it: the suffix of the entry points' names
-        and the arguments between ``pool_streams`` and the state."""
-        if pcm_scale is None:
-            return self._prepare_pool(chunks, slots, lengths), "", []
-        scale = _check_pcm_scale(pcm_scale, self._what)
-        return self._prepare_pool(chunks, slots, lengths, pcm=True), "_i16", [scale]
 
 
 class MfccStreamPool(_FrameStreamPoolBase):
@@ -1168,7 +1184,9 @@ class _StftStreamPoolBase(_StreamPoolMixin, _StreamBase):
     """A pool of ``pool_streams`` live audio streams, each with the carried state of ``MelSpectrogramStream`` / ``StftStream`` in
     continuous mode.  Called as the frame-path pools are: ``pool(chunks, slots, lengths=None)``, every chunk a whole number of
     hops (zero included).  Per stream the rows and the carried state are those of the dense class on that stream alone.  See
-    ``ss_mel_spectrogram_stream_packed`` in ``include/speechsauce_amd.h``."""
+    ``ss_mel_spectrogram_stream_packed`` in ``include/speechsauce_amd.h``.  ``pool(chunks, slots, pcm_scale=2**-15)`` takes int16
+    PCM chunks as the frame-path pools do (``ss_mel_spectrogram_stream_packed_i16``): same rows, same state, bit for bit; the state
+    stays float32, so a stream may be fed PCM on one call and floats on the next."""
 
 
 class MelSpectrogramStreamPool(_StftStreamPoolBase):
@@ -1184,8 +1202,8 @@ class MelSpectrogramStreamPool(_StftStreamPoolBase):
         super().__init__(pool_streams, sampling_frequency, frame_length, 0.01, 13, num_filters, fft_length, low_frequency,
                          high_frequency, True, "continuous", switches)
 
-    def __call__(self, chunks, slots, lengths=None):
-        packed, so, ro, sl, config = self._prepare_pool(chunks, slots, lengths)
+    def __call__(self, chunks, slots, lengths=None, pcm_scale=None):
+        (packed, so, ro, sl, config), i16, scale = self._prepare_pcm(chunks, slots, lengths, pcm_scale)
         n = config.params.num_filters * int(ro[-1])
         if _is_torch(packed):
             import torch
@@ -1193,8 +1211,8 @@ class MelSpectrogramStreamPool(_StftStreamPoolBase):
             out = torch.empty((n,), dtype=torch.float32, device=packed.device)
         else:
             out = np.empty((n,), dtype=np.float32)
-        self._call_pool(packed, so, ro, sl, config, [out], "ss_mel_spectrogram_stream_packed_device",
-                        "ss_mel_spectrogram_stream_packed", [])
+        self._call_pool(packed, so, ro, sl, config, [out], f"ss_mel_spectrogram_stream_packed{i16}_device",
+                        f"ss_mel_spectrogram_stream_packed{i16}", scale)
         return out, ro
 
 
@@ -1208,17 +1226,18 @@ class StftStreamPool(_StftStreamPoolBase):
         super().__init__(pool_streams, sampling_frequency, frame_length, 0.01, 13, 40, fft_length, 0, None, True, "continuous",
                          switches)
 
-    def __call__(self, chunks, slots, lengths=None):
-        packed, so, ro, sl, config = self._prepare_pool(chunks, slots, lengths)
+    def __call__(self, chunks, slots, lengths=None, pcm_scale=None):
+        (packed, so, ro, sl, config), i16, scale = self._prepare_pcm(chunks, slots, lengths, pcm_scale)
         shape = (int(ro[-1]), config.params.fft_points // 2 + 1, 2)
+        dev_fn, host_fn = f"ss_stft_stream_packed{i16}_device", f"ss_stft_stream_packed{i16}"
         if _is_torch(packed):
             import torch
 
             out = torch.empty(shape, dtype=torch.float32, device=packed.device)
-            self._call_pool(packed, so, ro, sl, config, [out], "ss_stft_stream_packed_device", "ss_stft_stream_packed", [])
+            self._call_pool(packed, so, ro, sl, config, [out], dev_fn, host_fn, scale)
             return torch.view_as_complex(out), ro
         out = np.empty(shape, dtype=np.float32)
-        self._call_pool(packed, so, ro, sl, config, [out], "ss_stft_stream_packed_device", "ss_stft_stream_packed", [])
+        self._call_pool(packed, so, ro, sl, config, [out], dev_fn, host_fn, scale)
         return out.view(np.complex64)[..., 0], ro
 
 

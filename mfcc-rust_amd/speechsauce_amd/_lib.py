@@ -139,6 +139,21 @@ PROTOTYPES = {
                                                   C.c_float, _fp, _fp, _fp, C.c_void_p]),
     "ss_mfcc_stream_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, _fp, _fp]),
     "ss_mfe_stream_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp, _fp]),
+    "ss_mel_spectrogram_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_void_p]),
+    "ss_stft_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_void_p]),
+    "ss_mel_spectrogram_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, _fp]),
+    "ss_stft_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, _fp]),
+    "ss_mel_spectrogram_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, _fp,
+                                                       C.c_void_p]),
+    "ss_stft_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
+    "ss_mel_spectrogram_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, _fp]),
+    "ss_stft_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, _fp]),
+    "ss_mel_spectrogram_stream_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                              C.c_size_t, C.c_float, _fp, _fp, C.c_void_p]),
+    "ss_stft_stream_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_float, _fp, _fp, C.c_void_p]),
+    "ss_mel_spectrogram_stream_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp]),
+    "ss_stft_stream_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp]),
     "ss_stream_packed_row_offsets": (C.c_int, [_P(SsParams), C.c_size_t, C.c_void_p, C.c_void_p]),
     "ss_mel_spectrogram_stream_packed_device": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                           _fp, _fp, C.c_void_p]),

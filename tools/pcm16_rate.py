@@ -1,6 +1,7 @@
 """Frames/s of the one-shot MFCC calls fed 16-bit PCM beside the float calls: what converting on load buys.
 
     python tools/pcm16_rate.py [--clips 1024] [--samples 16000] [--min-s 1] [--max-s 16] [--reps 20] [--host-reps 5]
+    python tools/pcm16_rate.py --mel [--clips 1024] [--samples 16000] [--min-s 1] [--max-s 16] [--pool 4096] [--max-hops 4] [--reps 20]
 
 16 kHz MFCC in reference mode (cfg1 parameters).  Device legs, HIP events on one stream after warm-up, every call on the next of
 a set of input buffers that together hold more than 256 MiB (no call finds its samples in the Infinity Cache):
@@ -11,6 +12,9 @@ a set of input buffers that together hold more than 256 MiB (no call finds its s
   packed  --clips clips, lengths uniform in [min-s, max-s] seconds: the same three on ss_mfcc_packed[_i16]_device
 Host leg, pinned buffers, wall clock: ss_mfcc_batch_i16 against ss_mfcc_batch on the same clips (PCIe included).
 The decision rule of DESIGN section 4: a PCM build stays where pcm is not slower than 1.02 x convert on its shape.
+--mel: the mel spectrogram of the cfg3 shape (2048 / 512, 128 mels) instead, rows/s, the same three legs on three layouts: dense
+(ss_mel_spectrogram[_i16]_device), packed (ss_mel_spectrogram_packed[_i16]_device) and the pool workload of
+tools/mel_stream_packed_rate.py (--clips entries of 1 .. --max-hops hops on a --pool row pool, ss_mel_spectrogram_stream_packed[_i16]_device).
 Prints one JSON line.  Measuring only: not collected by pytest, not part of bench.py.
 """
 import argparse
@@ -38,6 +42,9 @@ def main():
     ap.add_argument("--host-reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--legs", default="batch,packed,host")
+    ap.add_argument("--mel", action="store_true")
+    ap.add_argument("--pool", type=int, default=4096)
+    ap.add_argument("--max-hops", type=int, default=4)
     args = ap.parse_args()
 
     import torch
@@ -82,6 +89,59 @@ def main():
         out["pcm_over_convert"] = out["pcm"]["frames_per_s"] / out["convert"]["frames_per_s"]
         out["pcm_over_float"] = out["pcm"]["frames_per_s"] / out["float"]["frames_per_s"]
         return out
+
+    if args.mel:
+        cfg = ss.SpeechConfig(_lib.make_params(sample_rate=sr, fft_points=2048, frame_length=0.032, frame_stride=0.032, num_filters=128,
+                                               high_frequency=8000.0))
+        H, M, rng = 512, 128, np.random.default_rng(args.seed)
+        # dense
+        B, L = args.clips, args.samples
+        R = cfg.stft_rows(L)[0]
+        ps, fs = pcm_sets(B * L)
+        tmp, out = torch.empty(B * L, device="cuda"), torch.empty((B, M, R), device="cuda")
+        res["dense"] = three(B * R, len(ps),
+                             lambda i: _lib.check(lib.ss_mel_spectrogram_i16_device(cfg.handle, ps[i].data_ptr(), B, L, L, scale, out.data_ptr(), sp)),
+                             lambda i: _lib.check(lib.ss_mel_spectrogram_device(cfg.handle, (tmp if i < 0 else fs[i]).data_ptr(), B, L, L,
+                                                                                out.data_ptr(), sp)),
+                             lambda i: torch.mul(ps[i], scale, out=tmp))
+        del ps, fs, tmp, out
+        # packed
+        lens = rng.integers(int(args.min_s * sr), int(args.max_s * sr) + 1, args.clips).astype(np.int64)
+        so = ss._sample_offsets(lens, int(lens.sum()), "pcm16_rate")
+        ro = ss._row_offsets(cfg, so)
+        rows, n = int(ro[-1]), int(so[-1])
+        dso, dro = torch.from_numpy(so).cuda(), torch.from_numpy(ro).cuda()
+        ps, fs = pcm_sets(n)
+        tmp, out = torch.empty(n, device="cuda"), torch.empty(M * rows, device="cuda")
+        res["packed"] = three(rows, len(ps),
+                              lambda i: _lib.check(lib.ss_mel_spectrogram_packed_i16_device(cfg.handle, ps[i].data_ptr(), args.clips, dso.data_ptr(),
+                                                                                            scale, dro.data_ptr(), rows, out.data_ptr(), sp)),
+                              lambda i: _lib.check(lib.ss_mel_spectrogram_packed_device(cfg.handle, (tmp if i < 0 else fs[i]).data_ptr(), args.clips,
+                                                                                        dso.data_ptr(), dro.data_ptr(), rows, out.data_ptr(), sp)),
+                              lambda i: torch.mul(ps[i], scale, out=tmp))
+        del ps, fs, tmp, out
+        # pool
+        hops = rng.integers(1, args.max_hops + 1, args.clips).astype(np.int64)
+        so = np.zeros(args.clips + 1, np.int64)
+        np.cumsum(hops * H, out=so[1:])
+        ro = so // H
+        rows, n = int(ro[-1]), int(so[-1])
+        dso, dro = torch.from_numpy(so).cuda(), torch.from_numpy(ro).cuda()
+        dsl = torch.from_numpy(rng.permutation(args.pool)[:args.clips].astype(np.int32)).cuda()
+        pool = torch.zeros((args.pool, 2048 - H), device="cuda")
+        ps, fs = pcm_sets(n)
+        tmp, out = torch.empty(n, device="cuda"), torch.empty(M * rows, device="cuda")
+        res["pool"] = three(rows, len(ps),
+                            lambda i: _lib.check(lib.ss_mel_spectrogram_stream_packed_i16_device(
+                                cfg.handle, ps[i].data_ptr(), args.clips, dso.data_ptr(), dro.data_ptr(), rows, dsl.data_ptr(), args.pool, scale,
+                                pool.data_ptr(), out.data_ptr(), sp)),
+                            lambda i: _lib.check(lib.ss_mel_spectrogram_stream_packed_device(
+                                cfg.handle, (tmp if i < 0 else fs[i]).data_ptr(), args.clips, dso.data_ptr(), dro.data_ptr(), rows, dsl.data_ptr(),
+                                args.pool, pool.data_ptr(), out.data_ptr(), sp)),
+                            lambda i: torch.mul(ps[i], scale, out=tmp))
+        res["pool"].update(pool=args.pool, max_hops=args.max_hops, samples=n)
+        print(json.dumps(res))
+        return
 
     if "batch" in args.legs:
         B, L = args.clips, args.samples
