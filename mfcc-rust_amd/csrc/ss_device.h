@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "speechsauce_amd.h"
+#include "ss_launch_plan.h"
 
 // Product / lab builds.  The shipped library is the PRODUCT build: kernel selection is a pure function of the configuration
 // and the call -- no environment knob is read anywhere, and the timing-attribution switches of the headline kernel
@@ -92,6 +93,18 @@ struct LaunchInfo {
     unsigned grid, block;
     size_t lds_bytes;
 };
+
+// The launch step of the fused kernels: `waves` waves per workgroup, `lds` bytes of dynamic LDS (the attribute lifts the 48 KiB a
+// kernel gets without it), what ran reported through `info`.
+template <typename Kern, typename... Args>
+hipError_t launch_kernel(Kern kern, const char *name, unsigned grid, int waves, size_t lds, hipStream_t stream, LaunchInfo *info, const Args &...args)
+{
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(waves * 64), lds};
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(waves * 64), lds, stream, args...);
+    return hipGetLastError();
+}
 
 // Generic front-end (any power-of-two fft_points in [32, 4096]; with a.blu_n != 0 the chirp-z build for other lengths, log2c then
 // being the length of its complex FFT).

@@ -809,7 +809,7 @@ hipError_t launch_one(const FrontArgs &a, hipStream_t stream, int num_cus, Launc
     const unsigned long long work = layout_work(a, Geo<LOG2C>::FPB, v...);
     if (work == 0) return hipSuccess;
     if (work == kTooManyRows) return hipErrorInvalidValue;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256) * 8;
+    const unsigned long long cap = cu_cap(num_cus) * 8ull;
     const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
     if (info) *info = LaunchInfo{front_kernel_name<LOG2C, BLU>(v...), grid, static_cast<unsigned>(kBlock), lds};
     hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, V...>), dim3(grid), dim3(kBlock), lds, stream, a, v...);
@@ -953,7 +953,7 @@ hipError_t launch_poison_lds(hipStream_t stream, int num_cus)
     const size_t lds = 160 * 1024;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ss_poison_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (e != hipSuccess) return e;
-    const unsigned grid = static_cast<unsigned>(num_cus > 0 ? num_cus : 256) * 4;
+    const unsigned grid = cu_cap(num_cus) * 4;
     hipLaunchKernelGGL(ss_poison_lds_kernel, dim3(grid), dim3(256), lds, stream, static_cast<unsigned>(lds / 4));
     return hipGetLastError();
 }

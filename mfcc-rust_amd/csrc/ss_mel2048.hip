@@ -813,27 +813,18 @@ size_t mel_lds_bytes(int waves, int wpitch)
 {
     return (static_cast<size_t>(waves) * kWaveFloatsM + L::kMelW + 8 + 32 * static_cast<size_t>(wpitch)) * sizeof(float);
 }
-unsigned mel_grid(unsigned long long units, int waves, int num_cus)
+// the reference bank shape: compile-time tap counts 6 / 3 / 2 / 1 (FIXMEL)
+bool mel6321(const Mel2048Args &a)
 {
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256), blocks = (units + waves - 1) / waves;
-    return static_cast<unsigned>(blocks < cap ? blocks : cap);
+    return a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
 }
 // Eight waves per CU or twelve?  A unit (two rows) takes a wave 1.29 x as long with three waves on its SIMD as with two (cfg3, one
 // box: 8.0 us against 6.2), and a CU's units go round in ceil(units / waves) rounds: twelve waves win unless the CU's share of
 // units fits eight waves much better (cfg3: 64 units per CU, 8 rounds of 8 against 5.3 -> 6 of 12: 46.5 us against 49.7).
 bool twelve_waves_win(unsigned long long units, int num_cus)
 {
-    const unsigned long long cus = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256), per_cu = (units + cus - 1) / cus;
+    const unsigned long long cus = cu_cap(num_cus), per_cu = (units + cus - 1) / cus;
     return 1.29 * static_cast<double>((per_cu + 11) / 12) < static_cast<double>((per_cu + 7) / 8);
-}
-template <typename Kern, typename... Args>
-hipError_t mel_go(Kern kern, const char *name, unsigned grid, int waves, size_t lds, hipStream_t stream, LaunchInfo *info, const Args &...args)
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(waves * 64), lds};
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(waves * 64), lds, stream, args...);
-    return hipGetLastError();
 }
 
 template <int kWavesM>
@@ -844,12 +835,12 @@ hipError_t launch_mel_w(const Mel2048Args &a, hipStream_t stream, int num_cus, L
     if (a.batch == 0) return hipSuccess;
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * (a.out_stft ? (a.rows + 1) / 2 : mel_work_pairs(a.rows, a.real_rows));
     if (units >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned grid = mel_grid(units, kWavesM, num_cus);
+    const unsigned grid = cu_capped_grid(units, kWavesM, num_cus);
     // (a fixed-shape mel stage costs this kernel 84 bytes of scratch per lane beside the prefetched unit: measured 77 us against
     // 50; the run-time loops stay, with their remainders fetched in one batch)
-    if (a.out_stft) return mel_go(ss_mel_c1024<kWavesM, true>, "ss_mel_c1024<stft>", grid, kWavesM, lds, stream, info, a);
-    if (a.fullp) return mel_go(ss_mel_c1024<kWavesM, false, true>, "ss_mel_c1024<fullp>", grid, kWavesM, lds, stream, info, a);
-    return mel_go(ss_mel_c1024<kWavesM, false>, "ss_mel_c1024", grid, kWavesM, lds, stream, info, a);
+    if (a.out_stft) return launch_kernel(ss_mel_c1024<kWavesM, true>, "ss_mel_c1024<stft>", grid, kWavesM, lds, stream, info, a);
+    if (a.fullp) return launch_kernel(ss_mel_c1024<kWavesM, false, true>, "ss_mel_c1024<fullp>", grid, kWavesM, lds, stream, info, a);
+    return launch_kernel(ss_mel_c1024<kWavesM, false>, "ss_mel_c1024", grid, kWavesM, lds, stream, info, a);
 }
 
 // three waves per SIMD, direct stores (see ss_mel_c1024_w12): mel output with the reference bank shape, and stft
@@ -863,16 +854,16 @@ hipError_t launch_mel_w12(const Mel2048Args &a, hipStream_t stream, int num_cus,
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * (a.out_stft ? (a.rows + 1) / 2 : mel_work_pairs(a.rows, a.real_rows));
     if (units >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned grid = mel_grid(units, 12, num_cus);
+    const unsigned grid = cu_capped_grid(units, 12, num_cus);
     const MultiArg<false> none{};
     if constexpr (!PCM) {
-        if (a.out_stft) return mel_go(ss_mel_c1024_w12<false, true>, "ss_mel_c1024<w12,stft>", grid, 12, lds, stream, info, a, none);
+        if (a.out_stft) return launch_kernel(ss_mel_c1024_w12<false, true>, "ss_mel_c1024<w12,stft>", grid, 12, lds, stream, info, a, none);
     }
-    const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
-    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, P...>, PCM ? "ss_mel_c1024i<w12,mel6321>" : "ss_mel_c1024<w12,mel6321>", grid, 12, lds,
-                          stream, info, a, none, p...)
-                 : mel_go(ss_mel_c1024_w12<false, false, false, P...>, PCM ? "ss_mel_c1024i<w12>" : "ss_mel_c1024<w12>", grid, 12, lds, stream, info, a,
-                          none, p...);
+    if (mel6321(a))
+        return launch_kernel(ss_mel_c1024_w12<true, false, false, P...>, PCM ? "ss_mel_c1024i<w12,mel6321>" : "ss_mel_c1024<w12,mel6321>", grid, 12, lds,
+                             stream, info, a, none, p...);
+    return launch_kernel(ss_mel_c1024_w12<false, false, false, P...>, PCM ? "ss_mel_c1024i<w12>" : "ss_mel_c1024<w12>", grid, 12, lds, stream, info, a,
+                         none, p...);
 }
 
 // the streaming builds (mel output): eight waves (the reference bank shape or every bin) / twelve waves (the reference bank shape)
@@ -882,9 +873,9 @@ hipError_t launch_mel_w8_stream(const Mel2048Args &a, const StreamArgs &s, hipSt
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * mel_work_pairs(a.rows, a.real_rows);
     if (units >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned grid = mel_grid(units, 8, num_cus);
-    if (a.fullp) return mel_go(ss_mel_c1024<8, false, true, StreamArgs>, "ss_mel_c1024s<fullp>", grid, 8, lds, stream, info, a, s);
-    return mel_go(ss_mel_c1024<8, false, false, StreamArgs>, "ss_mel_c1024s", grid, 8, lds, stream, info, a, s);
+    const unsigned grid = cu_capped_grid(units, 8, num_cus);
+    if (a.fullp) return launch_kernel(ss_mel_c1024<8, false, true, StreamArgs>, "ss_mel_c1024s<fullp>", grid, 8, lds, stream, info, a, s);
+    return launch_kernel(ss_mel_c1024<8, false, false, StreamArgs>, "ss_mel_c1024s", grid, 8, lds, stream, info, a, s);
 }
 hipError_t launch_mel_w12_stream(const Mel2048Args &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
@@ -893,11 +884,11 @@ hipError_t launch_mel_w12_stream(const Mel2048Args &a, const StreamArgs &s, hipS
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * mel_work_pairs(a.rows, a.real_rows);
     if (units >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned grid = mel_grid(units, 12, num_cus);
+    const unsigned grid = cu_capped_grid(units, 12, num_cus);
     const MultiArg<false> none{};
-    const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
-    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, StreamArgs>, "ss_mel_c1024s<w12,mel6321>", grid, 12, lds, stream, info, a, none, s)
-                 : mel_go(ss_mel_c1024_w12<false, false, false, StreamArgs>, "ss_mel_c1024s<w12>", grid, 12, lds, stream, info, a, none, s);
+    if (mel6321(a))
+        return launch_kernel(ss_mel_c1024_w12<true, false, false, StreamArgs>, "ss_mel_c1024s<w12,mel6321>", grid, 12, lds, stream, info, a, none, s);
+    return launch_kernel(ss_mel_c1024_w12<false, false, false, StreamArgs>, "ss_mel_c1024s<w12>", grid, 12, lds, stream, info, a, none, s);
 }
 
 template <typename... P>
@@ -908,13 +899,13 @@ hipError_t launch_mel_w12_varlen(const Mel2048Args &a, const VarRowsArgs &v, hip
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     // an empty output block still gets one workgroup: the clip pass runs
     const unsigned long long units = (v.total_rows + 1) / 2;
-    const unsigned grid = units ? mel_grid(units, 12, num_cus) : 1u;
+    const unsigned grid = units ? cu_capped_grid(units, 12, num_cus) : 1u;
     const MultiArg<false> none{};
-    const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
-    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, VarRowsArgs, P...>, PCM ? "ss_mel_c1024vi<w12,mel6321>" : "ss_mel_c1024v<w12,mel6321>",
-                          grid, 12, lds, stream, info, a, none, v, p...)
-                 : mel_go(ss_mel_c1024_w12<false, false, false, VarRowsArgs, P...>, PCM ? "ss_mel_c1024vi<w12>" : "ss_mel_c1024v<w12>", grid, 12, lds,
-                          stream, info, a, none, v, p...);
+    if (mel6321(a))
+        return launch_kernel(ss_mel_c1024_w12<true, false, false, VarRowsArgs, P...>, PCM ? "ss_mel_c1024vi<w12,mel6321>" : "ss_mel_c1024v<w12,mel6321>",
+                             grid, 12, lds, stream, info, a, none, v, p...);
+    return launch_kernel(ss_mel_c1024_w12<false, false, false, VarRowsArgs, P...>, PCM ? "ss_mel_c1024vi<w12>" : "ss_mel_c1024v<w12>", grid, 12, lds,
+                         stream, info, a, none, v, p...);
 }
 
 template <typename... P>
@@ -926,13 +917,13 @@ hipError_t launch_mel_w12_stream_packed(const Mel2048Args &a, const StftStreamPa
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     // an empty output block still gets one workgroup: the entry pass runs
     const unsigned long long units = (static_cast<unsigned long long>(s.e.total_rows) + 1) / 2;
-    const unsigned grid = units ? mel_grid(units, 12, num_cus) : 1u;
+    const unsigned grid = units ? cu_capped_grid(units, 12, num_cus) : 1u;
     const MultiArg<false> none{};
-    const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
-    return m6321 ? mel_go(ss_mel_c1024_w12<true, false, false, StftStreamPackedArgs, P...>,
-                          PCM ? "ss_mel_c1024spi<w12,mel6321>" : "ss_mel_c1024sp<w12,mel6321>", grid, 12, lds, stream, info, a, none, s, p...)
-                 : mel_go(ss_mel_c1024_w12<false, false, false, StftStreamPackedArgs, P...>, PCM ? "ss_mel_c1024spi<w12>" : "ss_mel_c1024sp<w12>", grid,
-                          12, lds, stream, info, a, none, s, p...);
+    if (mel6321(a))
+        return launch_kernel(ss_mel_c1024_w12<true, false, false, StftStreamPackedArgs, P...>,
+                             PCM ? "ss_mel_c1024spi<w12,mel6321>" : "ss_mel_c1024sp<w12,mel6321>", grid, 12, lds, stream, info, a, none, s, p...);
+    return launch_kernel(ss_mel_c1024_w12<false, false, false, StftStreamPackedArgs, P...>, PCM ? "ss_mel_c1024spi<w12>" : "ss_mel_c1024sp<w12>", grid,
+                         12, lds, stream, info, a, none, s, p...);
 }
 
 }  // namespace
@@ -942,8 +933,7 @@ hipError_t launch_mel_c1024_multi(const Mel2048Args &a_in, int n_batches, const 
 {
     Mel2048Args a = a_in;
     // the build that exists: mel output, the reference bank shape (P rows of bins 0..512), compile-time tap counts 6 / 3 / 2 / 1
-    const bool m6321 = a.mel_q4[0] == 6 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1;
-    if (n_batches < 1 || n_batches > kMaxLaunchBatches || a.out_stft || a.fullp || !m6321) return hipErrorInvalidValue;
+    if (n_batches < 1 || n_batches > kMaxLaunchBatches || a.out_stft || a.fullp || !mel6321(a)) return hipErrorInvalidValue;
     const size_t lds = mel_lds_bytes(12, a.mel_wpitch);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const unsigned pairs = mel_work_pairs(a.rows, a.real_rows);
@@ -967,7 +957,8 @@ hipError_t launch_mel_c1024_multi(const Mel2048Args &a_in, int n_batches, const 
     a.x = d_x[0];
     a.out = d_out[0];
     a.batch = static_cast<uint32_t>(units);  // MULTI: the launch's unit count (the kernel takes the blocks from the table)
-    return mel_go(ss_mel_c1024_w12<true, false, true>, "ss_mel_c1024m<w12,mel6321>", mel_grid(units, 12, num_cus), 12, lds, stream, info, a, mt);
+    return launch_kernel(ss_mel_c1024_w12<true, false, true>, "ss_mel_c1024m<w12,mel6321>", cu_capped_grid(units, 12, num_cus), 12, lds, stream, info,
+                         a, mt);
 }
 
 // mel output, launch_mel_c1024's choice between the eight- and the twelve-wave build (ss_debug_mel_tile(1 / 2) asks for eight waves,
@@ -1037,44 +1028,53 @@ hipError_t launch_mel_c1024_stream(const Mel2048Args &a, const StreamArgs &s, hi
     // eight- and twelve-wave builds round a few FMAs differently in the last bit).  The lab library's ss_debug_mel_tile(1 / 2) asks
     // for eight waves (there is no streaming tile build), ss_debug_mel_tile(3) for twelve wherever that build exists.
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * mel_work_pairs(a.rows, a.real_rows);
-    if (!a.fullp && dbg_mel_build() != 1 && dbg_mel_build() != 2 && (twelve_waves_win(units, num_cus) || dbg_mel_build() == 3)) {
+    if (mel_takes_twelve_waves(a, units, num_cus)) {
         const hipError_t e = launch_mel_w12_stream(a, s, stream, num_cus, info);
         if (e != hipErrorInvalidValue) return e;
     }
     return launch_mel_w8_stream(a, s, stream, num_cus, info);
 }
 
+// what the packed launches serve: mel output of the reference bank shape, at least one clip.  Always twelve waves (never
+// twelve_waves_win): the eight- and twelve-wave builds round a few FMAs differently in the last bit, and a clip's bits must not
+// depend on which other clips share the call
+static bool mel_varlen_shape(const Mel2048Args &a, const VarRowsArgs &v)
+{
+    return !a.out_stft && !a.fullp && v.n_clips != 0 && v.total_rows < (1ull << 31);
+}
+
 hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
-    // always twelve waves (never twelve_waves_win): the eight- and twelve-wave builds round a few FMAs differently in the last bit,
-    // and a clip's bits must not depend on which other clips share the call
-    if (a.out_stft || a.fullp || v.n_clips == 0 || v.total_rows >= (1ull << 31)) return hipErrorInvalidValue;
+    if (!mel_varlen_shape(a, v)) return hipErrorInvalidValue;
     return launch_mel_w12_varlen(a, v, stream, num_cus, info);
 }
 
 hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, const BatchPcmArgs &p, hipStream_t stream, int num_cus,
                                    LaunchInfo *info)
 {
-    if (!p.x || a.out_stft || a.fullp || v.n_clips == 0 || v.total_rows >= (1ull << 31)) return hipErrorInvalidValue;  // (as above)
+    if (!p.x || !mel_varlen_shape(a, v)) return hipErrorInvalidValue;
     return launch_mel_w12_varlen(a, v, stream, num_cus, info, p);
+}
+
+// what the ragged streaming launches serve.  Always twelve waves (never twelve_waves_win): see mel_varlen_shape -- an entry's bits
+// must not depend on which other entries share the call.  The pool row holds the S = 2048 - hop samples in front of the chunk that
+// a window can reach.
+static bool mel_stream_packed_shape(const Mel2048Args &a, const StftStreamPackedArgs &s)
+{
+    return !a.out_stft && !a.fullp && s.e.n_active != 0 && s.e.total_rows < 0x7fffffffu && a.hop != 0 && a.n_pad == 0 && s.e.step == a.hop &&
+           s.e.state_len + a.hop == 2048u && s.e.pool;
 }
 
 hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
-    // always twelve waves (never twelve_waves_win): see launch_mel_c1024_varlen -- an entry's bits must not depend on which other
-    // entries share the call.  The pool row holds the S = 2048 - hop samples in front of the chunk that a window can reach.
-    if (a.out_stft || a.fullp || s.e.n_active == 0 || s.e.total_rows >= 0x7fffffffu || a.hop == 0 || a.n_pad != 0 || s.e.step != a.hop ||
-        s.e.state_len + a.hop != 2048u || !s.e.pool)
-        return hipErrorInvalidValue;
+    if (!mel_stream_packed_shape(a, s)) return hipErrorInvalidValue;
     return launch_mel_w12_stream_packed(a, s, stream, num_cus, info);
 }
 
 hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, const BatchPcmArgs &p, hipStream_t stream,
                                           int num_cus, LaunchInfo *info)
 {
-    if (!p.x || a.out_stft || a.fullp || s.e.n_active == 0 || s.e.total_rows >= 0x7fffffffu || a.hop == 0 || a.n_pad != 0 ||
-        s.e.step != a.hop || s.e.state_len + a.hop != 2048u || !s.e.pool)
-        return hipErrorInvalidValue;  // (as above)
+    if (!p.x || !mel_stream_packed_shape(a, s)) return hipErrorInvalidValue;
     return launch_mel_w12_stream_packed(a, s, stream, num_cus, info, p);
 }
 

@@ -229,19 +229,11 @@ hipError_t launch_mel_c256(const Mel512Args &a, hipStream_t stream, int num_cus,
     const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloatsE + L::kMelW + 4 + 16 * static_cast<size_t>(a.mel_wpitch)) * sizeof(float);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (a.batch == 0 || a.rows == 0) return hipSuccess;
-    const unsigned cap = static_cast<unsigned>(num_cus > 0 ? num_cus : 256);
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * ((a.rows + 3) / 4);
     if (units >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned long long blocks = (units + WAVES - 1) / WAVES;
-    const unsigned grid = static_cast<unsigned>(blocks < cap ? blocks : cap);
-    auto go = [&](auto kern, const char *name) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
-        return hipGetLastError();
-    };
-    return a.out_stft ? go(ss_mel_c256<WAVES, true>, "ss_mel_c256<stft>") : go(ss_mel_c256<WAVES, false>, "ss_mel_c256");
+    const unsigned grid = cu_capped_grid(units, WAVES, num_cus);
+    return a.out_stft ? launch_kernel(ss_mel_c256<WAVES, true>, "ss_mel_c256<stft>", grid, WAVES, lds, stream, info, a)
+                      : launch_kernel(ss_mel_c256<WAVES, false>, "ss_mel_c256", grid, WAVES, lds, stream, info, a);
 }
 
 }  // namespace ss

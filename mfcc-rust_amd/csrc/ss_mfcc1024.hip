@@ -520,17 +520,8 @@ hipError_t launch_k(const Mfcc1024Args &a, hipStream_t stream, int num_cus, Laun
     if (total == 0) return hipSuccess;
     if (total >= 0xffffffffull) return hipErrorInvalidValue;
     const unsigned long long units = (total + 1) / 2;
-    unsigned long long blocks = (units + WAVES - 1) / WAVES;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    auto go = [&](auto kern, const char *name) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
-        return hipGetLastError();
-    };
+    const unsigned grid = cu_capped_grid(units, WAVES, num_cus);
+    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, grid, WAVES, lds, stream, info, a); };
     const bool pow2 = a.spectrum_exponent == 2, win = a.windowed != 0, lib = a.center != 0 || a.fullp != 0;
 #define SS_K(P, M, W, LB, NAME) go(ss_mfcc_c512<P, M, W, WAVES, LB>, NAME)
     if (lib) {
@@ -563,19 +554,11 @@ hipError_t launch_mel_c512(const Mel2048Args &a, hipStream_t stream, int num_cus
     const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloatsK + L::kMelW + 32 * static_cast<size_t>(a.mel_wpitch) + 4) * sizeof(float);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (a.batch == 0 || a.rows == 0) return hipSuccess;
-    const unsigned cap = static_cast<unsigned>(num_cus > 0 ? num_cus : 256);
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * ((a.rows + 1) / 2);
     if (units >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned long long blocks = (units + WAVES - 1) / WAVES;
-    const unsigned grid = static_cast<unsigned>(blocks < cap ? blocks : cap);
-    auto go = [&](auto kern, const char *name) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
-        return hipGetLastError();
-    };
-    return a.out_stft ? go(ss_mel_c512<WAVES, true>, "ss_mel_c512<stft>") : go(ss_mel_c512<WAVES, false>, "ss_mel_c512");
+    const unsigned grid = cu_capped_grid(units, WAVES, num_cus);
+    return a.out_stft ? launch_kernel(ss_mel_c512<WAVES, true>, "ss_mel_c512<stft>", grid, WAVES, lds, stream, info, a)
+                      : launch_kernel(ss_mel_c512<WAVES, false>, "ss_mel_c512", grid, WAVES, lds, stream, info, a);
 }
 
 }  // namespace ss

@@ -315,17 +315,8 @@ hipError_t launch_g(const Mfcc2048Args &a, hipStream_t stream, int num_cus, Laun
     if (total == 0) return hipSuccess;
     if (total >= 0xffffffffull) return hipErrorInvalidValue;
     const unsigned long long units = (total + 1) / 2;
-    unsigned long long blocks = (units + WAVES - 1) / WAVES;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    auto go = [&](auto kern, const char *name) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
-        return hipGetLastError();
-    };
+    const unsigned grid = cu_capped_grid(units, WAVES, num_cus);
+    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, grid, WAVES, lds, stream, info, a); };
     const bool pow2 = a.spectrum_exponent == 2, win = a.windowed != 0;
 #define SS_G(P, M, W, LB, NAME) go(ss_mfcc_c1024<P, M, W, WAVES, LB>, NAME)
 #define SS_GP(P, M, W, NAME) go(ss_mfcc_c1024<P, M, W, WAVES, true, true>, NAME)

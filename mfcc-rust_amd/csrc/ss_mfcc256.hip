@@ -360,37 +360,20 @@ template <int WAVES>
 hipError_t launch_x(const Mfcc256Args &a_in, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
     Mfcc256Args a = a_in;
-    a.nf_magic = 0;
-    a.nf_shift = 0;
-    {
-        // floor(x / d) for x < 2^31 as umulhi(x, ceil(2^(31+l) / d)) >> (l - 1), l = ceil(log2 d) (Granlund-Montgomery);
-        // the kernel's one-wrap lane fix-up needs d >= 8
-        const unsigned long long tot = static_cast<unsigned long long>(a.batch) * a.n_frames, d = a.n_frames;
-        if (d >= 8 && d < (1ull << 31) && tot + 8 < (1ull << 31)) {
-            unsigned l = 0;
-            while ((1ull << l) < d) ++l;
-            const unsigned __int128 num = static_cast<unsigned __int128>(1) << (31 + l);
-            a.nf_magic = static_cast<uint32_t>((num + d - 1) / d);
-            a.nf_shift = l - 1;
-        }
+    const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
+    a.nf_magic = a.nf_shift = 0;
+    // floor(x / n_frames) by multiply-high where the kernel's one-wrap lane fix-up holds (n_frames >= 8); else it divides
+    if (a.n_frames >= 8 && a.n_frames < (1u << 31) && total + 8 < (1ull << 31)) {
+        const FrameReciprocal r = frame_reciprocal(a.n_frames);
+        a.nf_magic = r.magic;
+        a.nf_shift = r.shift;
     }
     const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloatsX + L::kMelW + 16 * static_cast<size_t>(a.mel_wpitch) + (a.windowed ? 256 : 0) + 4) * sizeof(float);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
     if (total == 0) return hipSuccess;
     if (total + 8 >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned long long octs = (total + 7) / 8;
-    unsigned long long blocks = (octs + WAVES - 1) / WAVES;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    auto go = [&](auto kern, const char *name) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
-        return hipGetLastError();
-    };
+    const unsigned grid = cu_capped_grid((total + 7) / 8, WAVES, num_cus);
+    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, grid, WAVES, lds, stream, info, a); };
     const bool pow2 = a.spectrum_exponent == 2, win = a.windowed != 0;
 #define SS_X(NE, P, M, W, NAME) go(ss_mfcc_c256x2<NE, P, M, W, WAVES>, NAME)
 #define SS_XN(NE, TAG)                                                                                                                          \

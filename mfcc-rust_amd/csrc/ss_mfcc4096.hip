@@ -861,34 +861,33 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c2048(const Mel2048Args a)
     }
 }
 
+size_t c2048_lds_bytes(int waves, const Mfcc4096Args &a)
+{
+    return (static_cast<size_t>(waves) * kExFloats + (a.window ? 4096 : 0) + L::kCos + static_cast<size_t>(a.cos_floats) +
+            64 * static_cast<size_t>(a.mel_wpitch) + 4) * sizeof(float);
+}
+// the default cfg5 shape: exact frames, magnitude spectrum, no window / pre-emphasis / mfe, the 8/3/2/1 bank of 256 filters at its
+// fixed pitch, twice-folded DCT -- what the FIXMEL builds are written for
+bool lean8321(const Mfcc4096Args &a)
+{
+    return a.flen == 4096 && a.preemph == 0.f && a.spectrum_exponent != 2 && !a.window && !a.out_mfe && a.dct_fold2 && a.mel_q4[0] == 8 &&
+           a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1 && a.mel_wpitch == kMelPitch8321 && a.n_filters == 256;
+}
+
 template <int WAVES>
 hipError_t launch_h(const Mfcc4096Args &a, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
-    const size_t lds = (static_cast<size_t>(WAVES) * kExFloats + (a.window ? 4096 : 0) + L::kCos + static_cast<size_t>(a.cos_floats) +
-                        64 * static_cast<size_t>(a.mel_wpitch) + 4) * sizeof(float);
+    const size_t lds = c2048_lds_bytes(WAVES, a);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
     if (total == 0) return hipSuccess;
     if (total >= 0xffffffffull) return hipErrorInvalidValue;
-    unsigned long long blocks = (total + WAVES - 1) / WAVES;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    auto go = [&](auto kern, const char *name) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{});
-        return hipGetLastError();
-    };
+    const unsigned grid = cu_capped_grid(total, WAVES, num_cus);
+    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, grid, WAVES, lds, stream, info, a, MultiArg<false>{}); };
     const bool pow2 = a.spectrum_exponent == 2, exact = a.flen == 4096 && a.preemph == 0.f;
     if constexpr (WAVES == 12) {
-        // only the default cfg5 shape (exact frames, magnitude spectrum, 8/3/2/1 bank, twice-folded DCT, no window / mfe) has a
-        // 12-wave build
-        const bool lean_ok = exact && !pow2 && !a.window && !a.out_mfe && a.dct_fold2 && a.mel_q4[0] == 8 && a.mel_q4[1] == 3 &&
-                             a.mel_q4[2] == 2 && a.mel_q4[3] == 1 && a.mel_wpitch == kMelPitch8321 && a.n_filters == 256;
-        if (!lean_ok) return hipErrorInvalidValue;
+        // only the default cfg5 shape has a 12-wave build
+        if (!lean8321(a)) return hipErrorInvalidValue;
         return go(ss_mfcc_c2048<true, false, 12, false, false, false, true>, "ss_mfcc_c2048<exact,mel8321,w12>");
     } else {
     if (a.preemph != 0.f) {  // fused pre-emphasis builds (run-time frame length)
@@ -913,8 +912,8 @@ hipError_t launch_h(const Mfcc4096Args &a, hipStream_t stream, int num_cus, Laun
         if (exact) return pow2 ? go(ss_mfcc_c2048<true, true, WAVES, true>, "ss_mfcc_c2048<exact,pow2,mfe>") : go(ss_mfcc_c2048<true, false, WAVES, true>, "ss_mfcc_c2048<exact,mfe>");
         return pow2 ? go(ss_mfcc_c2048<false, true, WAVES, true>, "ss_mfcc_c2048<pow2,mfe>") : go(ss_mfcc_c2048<false, false, WAVES, true>, "ss_mfcc_c2048<mfe>");
     }
-    const bool m8321 = a.mel_q4[0] == 8 && a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1 && a.mel_wpitch == kMelPitch8321 && a.n_filters == 256;
-    if (exact && m8321 && !pow2 && a.dct_fold2) return go(ss_mfcc_c2048<true, false, WAVES, false, false, false, true>, "ss_mfcc_c2048<exact,mel8321>");
+    // (the windowed, pre-emphasised and mfe builds were taken above: lean8321's terms for them hold here)
+    if (lean8321(a)) return go(ss_mfcc_c2048<true, false, WAVES, false, false, false, true>, "ss_mfcc_c2048<exact,mel8321>");
     if (exact) return pow2 ? go(ss_mfcc_c2048<true, true, WAVES>, "ss_mfcc_c2048<exact,pow2>") : go(ss_mfcc_c2048<true, false, WAVES>, "ss_mfcc_c2048<exact>");
     return pow2 ? go(ss_mfcc_c2048<false, true, WAVES>, "ss_mfcc_c2048<pow2>") : go(ss_mfcc_c2048<false, false, WAVES>, "ss_mfcc_c2048");
     }
@@ -928,10 +927,8 @@ hipError_t launch_mfcc_c2048_multi(const Mfcc4096Args &a_in, int n_batches, cons
     constexpr int WAVES = 12;
     Mfcc4096Args a = a_in;
     // the build that exists: the default cfg5 shape (see launch_h<12>)
-    const bool lean_ok = a.flen == 4096 && a.preemph == 0.f && a.spectrum_exponent != 2 && !a.window && !a.out_mfe && a.dct_fold2 && a.mel_q4[0] == 8 &&
-                         a.mel_q4[1] == 3 && a.mel_q4[2] == 2 && a.mel_q4[3] == 1 && a.mel_wpitch == kMelPitch8321 && a.n_filters == 256;
-    if (n_batches < 1 || n_batches > kMaxLaunchBatches || !lean_ok) return hipErrorInvalidValue;
-    const size_t lds = (static_cast<size_t>(WAVES) * kExFloats + L::kCos + static_cast<size_t>(a.cos_floats) + 64 * static_cast<size_t>(a.mel_wpitch) + 4) * sizeof(float);
+    if (n_batches < 1 || n_batches > kMaxLaunchBatches || !lean8321(a)) return hipErrorInvalidValue;
+    const size_t lds = c2048_lds_bytes(WAVES, a);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     BatchTable m{};
     unsigned long long total = 0;
@@ -950,16 +947,8 @@ hipError_t launch_mfcc_c2048_multi(const Mfcc4096Args &a_in, int n_batches, cons
     a.x = d_x[0];
     a.out = d_out[0];
     a.batch = static_cast<uint32_t>(total);  // MULTI: the launch's frame count (the kernel takes the batches from the table)
-    unsigned long long blocks = (total + WAVES - 1) / WAVES;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    auto kern = ss_mfcc_c2048<true, false, 12, false, false, false, true, true>;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    if (info) *info = LaunchInfo{"ss_mfcc_c2048m<exact,mel8321,w12>", grid, static_cast<unsigned>(WAVES * 64), lds};
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<true>{m});
-    return hipGetLastError();
+    return launch_kernel(ss_mfcc_c2048<true, false, 12, false, false, false, true, true>, "ss_mfcc_c2048m<exact,mel8321,w12>",
+                         cu_capped_grid(total, WAVES, num_cus), WAVES, lds, stream, info, a, MultiArg<true>{m});
 }
 
 hipError_t launch_mfcc_c2048(const Mfcc4096Args &a, hipStream_t stream, int num_cus, LaunchInfo *info)
@@ -981,17 +970,9 @@ hipError_t launch_mel_c2048(const Mel2048Args &a, hipStream_t stream, int num_cu
     const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.rows;
     if (total == 0) return hipSuccess;
     if (total >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned cap = static_cast<unsigned>(num_cus > 0 ? num_cus : 256);
-    const unsigned long long blocks = (total + WAVES - 1) / WAVES;
-    const unsigned grid = static_cast<unsigned>(blocks < cap ? blocks : cap);
-    auto go = [&](auto kern, const char *name) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
-        return hipGetLastError();
-    };
-    return a.out_stft ? go(ss_mel_c2048<WAVES, true>, "ss_mel_c2048<stft>") : go(ss_mel_c2048<WAVES, false>, "ss_mel_c2048");
+    const unsigned grid = cu_capped_grid(total, WAVES, num_cus);
+    return a.out_stft ? launch_kernel(ss_mel_c2048<WAVES, true>, "ss_mel_c2048<stft>", grid, WAVES, lds, stream, info, a)
+                      : launch_kernel(ss_mel_c2048<WAVES, false>, "ss_mel_c2048", grid, WAVES, lds, stream, info, a);
 }
 
 }  // namespace ss

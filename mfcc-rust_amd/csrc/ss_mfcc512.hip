@@ -113,6 +113,10 @@ constexpr int kZStride = 288;           // float2 per frame exchange slot (2304 
 constexpr int kPRow = 144;              // floats per P row: bins 0..128, 3 zero pad bins, padding
 constexpr int kPOff = 4 * kZStride * 2;  // P rows sit behind the exchange slots: their zero pad bins persist
 constexpr int kWaveFloats = 4 * kZStride * 2 + 4 * kPRow;  // four exchange slots (log-mel rows reuse them) + four P rows
+// The builds that exist have 8 to 16 waves (beyond 12 the P rows alias the exchange slots): every launch needs more dynamic LDS than
+// the 48 KiB a kernel gets without the attribute that launch_kernel (ss_device.h) sets unconditionally.
+static_assert(8 * kWaveFloats * sizeof(float) > 48 * 1024 && 13 * (4 * kZStride * 2) * sizeof(float) > 48 * 1024,
+              "a build within 48 KiB of LDS");
 // Issue priorities of the phases (s_setprio; the reasoning is in ss_mel2048.hip): the two butterflies run at the lowest priority,
 // so that a wave that is about to claim, exchange through LDS, fetch partners or read tables gets those requests out in front of
 // the pure VALU streams of the waves beside it.  cfg2, same box (profiles/r03/ab_cfg2_cfg5_priorities*.txt): 30.8 us without
@@ -1181,6 +1185,53 @@ const char *pcm_kernel_name(const char *name, const char *tag)
     return n.c_str();
 }
 
+// ---- what the five launchers share: shape predicates, the LDS budget, the plan of a launch ----
+// the default bank: compile-time tap counts 4 / 2 / 1 (BANK421)
+bool bank421(const Fast512Args &a)
+{
+    return a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1;
+}
+// the headline shape: 320-sample frames in contract-style framing, no window, no pre-emphasis, magnitude spectrum, the default bank
+bool headline_shape(const Fast512Args &a)
+{
+    return !a.fullp && !a.center && !(a.win_floats > 0) && a.preemph == 0.0f && a.flen == 320 && a.spectrum_exponent != 2 && bank421(a);
+}
+// MFCC output with 40 filters in the paired tight-tap layout: the headline build (RES 30)
+bool paired_mfcc(const Fast512Args &a)
+{
+    return a.out_mfe == 0 && a.n_filters == 40 && a.paired == 2;
+}
+// the streaming builds: the headline shape (contract / padded framing stream alike), MFCC on the headline build or mfe; even hops
+// keep sample pairs whole; the carried state holds the lead = flen - step samples in front of a chunk
+bool stream_shape(const Fast512Args &a, int lead, unsigned state_len, const void *state)
+{
+    const bool mfe = a.out_mfe == 1 && a.n_filters <= 40;
+    return headline_shape(a) && (paired_mfcc(a) || mfe) && !(a.step & 1u) && a.step <= a.flen && lead == static_cast<int>(a.flen - a.step) &&
+           state_len >= static_cast<unsigned>(lead) && (state_len == 0 || state);
+}
+// twelve waves and fewer: a wave's exchange slots and P rows; more: the P rows alias the exchange slots (ALIAS)
+size_t c256_lds_bytes(int waves, const Fast512Args &a)
+{
+    return (static_cast<size_t>(waves) * (waves > 12 ? 4 * kZStride * 2 : kWaveFloats) + L::kMelW + 16 * a.mel_wpitch +
+            (a.win_floats > 0 ? a.win_floats : 0)) * sizeof(float) + 16;
+}
+void set_frame_reciprocal(Fast512Args &a)
+{
+    const FrameReciprocal r = frame_reciprocal(a.n_frames);
+    a.nf_magic = r.magic;
+    a.nf_shift = r.shift;
+}
+// The grid -- one workgroup per CU, fewer when there is not at least one quad per wave -- and each workgroup's share of the quads
+// (a.q_base, a.q_rem).  allow_empty: an empty output block still gets one workgroup (the packed builds' consistency pass runs).
+unsigned plan_quads(Fast512Args &a, unsigned long long quads, int waves, int num_cus, bool allow_empty = false)
+{
+    const unsigned grid = allow_empty && quads == 0 ? 1u : cu_capped_grid(quads, waves, num_cus);
+    const UnitSplit s = split_units(quads, grid);
+    a.q_base = s.q_base;
+    a.q_rem = s.q_rem;
+    return grid;
+}
+
 // the kernel build of a launch: the one-shot template arguments, then the launch's trailing argument pack (none: the float builds)
 template <typename... SP>
 struct C256 {
@@ -1199,55 +1250,26 @@ hipError_t launch_w(const Fast512Args &a_in, hipStream_t stream, int num_cus, La
     using K = C256<SP...>;
     if (PCM && (a_in.fullp || a_in.center || a_in.preemph != 0.0f || a_in.out_mfe == 2)) return hipErrorInvalidValue;
     Fast512Args a = a_in;
-    a.nf_magic = 0;
-    a.nf_shift = 0;
-    {
-        // floor(x / d) for x < 2^31 as umulhi(x, ceil(2^(31+l) / d)) >> (l - 1), l = ceil(log2 d) (Granlund-Montgomery);
-        // the kernel's one-wrap lane fix-up needs d >= 4
-        const unsigned long long tot = static_cast<unsigned long long>(a.batch) * a.n_frames, d = a.n_frames;
-        if (d >= 4 && d < (1ull << 31) && tot + 4 < (1ull << 31)) {
-            unsigned l = 0;
-            while ((1ull << l) < d) ++l;
-            const unsigned __int128 num = static_cast<unsigned __int128>(1) << (31 + l);
-            a.nf_magic = static_cast<uint32_t>((num + d - 1) / d);
-            a.nf_shift = l - 1;
-            // quad_src (the SPREAD builds' sample addresses): a lane's 32-bit byte offset from the quad's uniform base reaches
-            // 3 frames + one step into the next clip + its 16 sample pairs + the sixteen 128-byte strides of the loads, and the
-            // frame-in-quad product is a 24-bit multiply.  Row strides / hops beyond that go to the next kernel
-            // (launch_frames falls through on this value), which forms 64-bit addresses.
-            const unsigned long long span = static_cast<unsigned long long>(a.n_frames) * a.step;
-            // (centred frames never take quad_src, and their n_frames * step may exceed the clip: not checked)
-            if (!a.center && (a.ld < span || static_cast<unsigned long long>(a.step) * 4ull >= (1ull << 24) ||
-                              3ull * a.step * 4ull + (a.ld - span) * 4ull + 16ull * 8ull + 16ull * 128ull >= (1ull << 32)))
-                return hipErrorInvalidValue;
-        } else if (static_cast<unsigned long long>(a.batch) * a.ld * 4ull >= (1ull << 32)) {
-            return hipErrorInvalidValue;  // without the reciprocal the kernel addresses a lane's frame by a 32-bit offset from the batch's first sample
-        }
-    }
-    const size_t lds = (static_cast<size_t>(WAVES) * (WAVES > 12 ? 4 * kZStride * 2 : kWaveFloats) + L::kMelW + 16 * a.mel_wpitch + (a.win_floats > 0 ? a.win_floats : 0)) * sizeof(float) + 16;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
     const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
+    // the kernel's one-wrap lane fix-up needs n_frames >= 4
+    if (a.n_frames >= 4 && a.n_frames < (1u << 31) && total + 4 < (1ull << 31)) {
+        set_frame_reciprocal(a);
+        // Row strides / hops beyond quad_src's range go to the next kernel (launch_frames falls through on this value), which forms
+        // 64-bit addresses.  (Centred frames never take quad_src, and their n_frames * step may exceed the clip: not checked)
+        if (!a.center && !quad_src_in_range(a.n_frames, a.step, a.ld)) return hipErrorInvalidValue;
+    } else {
+        a.nf_magic = a.nf_shift = 0;
+        // without the reciprocal the kernel addresses a lane's frame by a 32-bit offset from the batch's first sample
+        if (static_cast<unsigned long long>(a.batch) * a.ld * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
+    }
+    const size_t lds = c256_lds_bytes(WAVES, a);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (total == 0) return hipSuccess;
-    const unsigned long long quads = (total + 3) / 4;
-    // one workgroup per CU; fewer when there is not at least one quad per wave
-    unsigned long long blocks = (quads + WAVES - 1) / WAVES;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    a.q_base = static_cast<uint32_t>(quads / grid);
-    a.q_rem = static_cast<uint32_t>(quads % grid);
+    const unsigned grid = plan_quads(a, (total + 3) / 4, WAVES, num_cus);
     auto go = [&](auto kern, const char *name) {
-        if (lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               static_cast<int>(lds));
-            if (e != hipSuccess) return e;
-        }
-        if (info) *info = LaunchInfo{PCM ? pcm_kernel_name(name, "i") : name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{}, sp...);
-        return hipGetLastError();
+        return launch_kernel(kern, PCM ? pcm_kernel_name(name, "i") : name, grid, WAVES, lds, stream, info, a, MultiArg<false>{}, sp...);
     };
-    const bool pow2 = a.spectrum_exponent == 2;
-    const bool b421 = a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1;
+    const bool pow2 = a.spectrum_exponent == 2, b421 = bank421(a);
     if (a.fullp || a.center) {
         // librosa-compatible variants: P rows of all 257 bins (banks that cover the whole spectrum) and / or centred frames;
         // MFCC output, optional frame window, no fused pre-emphasis
@@ -1344,12 +1366,9 @@ hipError_t launch_mfcc_c256_multi(const Fast512Args &a_in, int n_batches, const 
     Fast512Args a = a_in;
     // the builds that exist: MFCC output of the default frame shape and bank (what launch_w's first branch serves without a
     // window, pre-emphasis or another output), 40 filters in the paired tight-tap layout -- the headline build
-    const bool b421 = a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1;
-    if (n_batches < 1 || n_batches > kMaxLaunchBatches || a.fullp || a.center || a.out_mfe || a.win_floats > 0 || a.preemph != 0.0f ||
-        a.flen != 320 || a.spectrum_exponent == 2 || !b421 || a.n_filters != 40 || a.paired != 2 || a.n_frames < 4)
-        return hipErrorInvalidValue;
+    if (n_batches < 1 || n_batches > kMaxLaunchBatches || !headline_shape(a) || !paired_mfcc(a) || a.n_frames < 4) return hipErrorInvalidValue;
     Fast512Multi m{};
-    unsigned long long quads = 0, max_total = 0;
+    unsigned long long quads = 0;
     for (int b = 0; b < kMaxLaunchBatches; ++b) {
         m.uend[b] = 0xffffffffu;
         if (b >= n_batches) continue;
@@ -1357,44 +1376,22 @@ hipError_t launch_mfcc_c256_multi(const Fast512Args &a_in, int n_batches, const 
         if (tot == 0 || tot + 4 >= (1ull << 31)) return hipErrorInvalidValue;  // (empty batches are dropped by the caller)
         quads += (tot + 3) / 4;
         if (quads >= 0xffffffffull) return hipErrorInvalidValue;
-        max_total = std::max(max_total, tot);
         m.x[b] = d_x[b];
         m.out[b] = d_out[b];
         m.uend[b] = static_cast<uint32_t>(quads);
         m.total[b] = static_cast<uint32_t>(tot);
     }
-    {
-        // the same reciprocal and address-range conditions as launch_w (every batch has the same clip shape)
-        const unsigned long long d = a.n_frames;
-        unsigned l = 0;
-        while ((1ull << l) < d) ++l;
-        const unsigned __int128 num = static_cast<unsigned __int128>(1) << (31 + l);
-        a.nf_magic = static_cast<uint32_t>((num + d - 1) / d);
-        a.nf_shift = l - 1;
-        const unsigned long long span = static_cast<unsigned long long>(a.n_frames) * a.step;
-        if (a.ld < span || static_cast<unsigned long long>(a.step) * 4ull >= (1ull << 24) ||
-            3ull * a.step * 4ull + (a.ld - span) * 4ull + 16ull * 8ull + 16ull * 128ull >= (1ull << 32))
-            return hipErrorInvalidValue;
-    }
+    // launch_w's reciprocal and address range (every batch has the same clip shape; n_frames >= 4 and every batch's total checked above)
+    set_frame_reciprocal(a);
+    if (!quad_src_in_range(a.n_frames, a.step, a.ld)) return hipErrorInvalidValue;
     a.x = d_x[0];
     a.out = d_out[0];
     a.batch = static_cast<uint32_t>(clips[0]);
-    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * a.mel_wpitch) * sizeof(float) + 16;
+    const size_t lds = c256_lds_bytes(WAVES, a);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    unsigned long long blocks = (quads + WAVES - 1) / WAVES;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    a.q_base = static_cast<uint32_t>(quads / grid);
-    a.q_rem = static_cast<uint32_t>(quads % grid);
-    auto kern = ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, true>;
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-    }
-    if (info) *info = LaunchInfo{"ss_mfcc_c256m<10,exact,bank421,sym>", grid, static_cast<unsigned>(WAVES * 64), lds};
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<true>{m});
-    return hipGetLastError();
+    const unsigned grid = plan_quads(a, quads, WAVES, num_cus);
+    return launch_kernel(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, true>, "ss_mfcc_c256m<10,exact,bank421,sym>", grid,
+                         WAVES, lds, stream, info, a, MultiArg<true>{m});
 }
 
 // the packed launch for either sample format: sp = empty (floats at a.x) or one BatchPcmArgs
@@ -1405,30 +1402,16 @@ static hipError_t launch_varlen_w12(const Fast512Args &a_in, const VarlenArgs &v
     constexpr int WAVES = 12;
     Fast512Args a = a_in;
     // the headline build only: MFCC of the default frame shape and bank, 40 filters in the paired tight-tap layout, contract framing
-    const bool b421 = a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1;
-    if (a.fullp || a.center || a.out_mfe || a.win_floats > 0 || a.preemph != 0.0f || a.flen != 320 || a.spectrum_exponent == 2 ||
-        !b421 || a.n_filters != 40 || a.paired != 2 || v.framing != SS_FRAMING_CONTRACT || v.dct_ortho || v.n_clips == 0 ||
+    if (!headline_shape(a) || !paired_mfcc(a) || v.framing != SS_FRAMING_CONTRACT || v.dct_ortho || v.n_clips == 0 ||
         v.total_frames + 4 >= (1ull << 31))
         return hipErrorInvalidValue;
     a.nf_magic = a.nf_shift = 0;
-    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * a.mel_wpitch) * sizeof(float) + 16;
+    const size_t lds = c256_lds_bytes(WAVES, a);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     // an empty output block still gets one workgroup: the clip pass runs
-    const unsigned long long quads = (v.total_frames + 3) / 4;
-    unsigned long long blocks = quads ? (quads + WAVES - 1) / WAVES : 1;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    a.q_base = static_cast<uint32_t>(quads / grid);
-    a.q_rem = static_cast<uint32_t>(quads % grid);
-    auto kern = ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, true, SP...>;
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-    }
-    if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, v, sp...);
-    return hipGetLastError();
+    const unsigned grid = plan_quads(a, (v.total_frames + 3) / 4, WAVES, num_cus, true);
+    return launch_kernel(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, true, SP...>, name, grid, WAVES, lds, stream,
+                         info, a, v, sp...);
 }
 
 hipError_t launch_mfcc_c256_varlen(const Fast512Args &a, const VarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
@@ -1448,47 +1431,22 @@ hipError_t launch_mfcc_c256_stream(const Fast512Args &a_in, const FrameStreamArg
     Fast512Args a = a_in;
     // the headline shape only: 320-sample frames, the default bank (4 / 2 / 1 taps), no window, no pre-emphasis, contract / padded
     // framing (both stream alike); MFCC with 40 filters in the paired tight-tap layout, or mfe.  Even hops keep sample pairs whole.
-    const bool b421 = a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1;
-    const bool mfcc = a.out_mfe == 0 && a.n_filters == 40 && a.paired == 2;
-    const bool mfe = a.out_mfe == 1 && a.n_filters <= 40;
-    if (a.fullp || a.center || a.win_floats > 0 || a.preemph != 0.0f || a.flen != 320 || a.spectrum_exponent == 2 || !b421 || !(mfcc || mfe) ||
-        (a.step & 1u) || a.step > a.flen || s.lead != static_cast<int>(a.flen - a.step) || s.state_len < static_cast<unsigned>(s.lead) ||
-        (s.state_len > 0 && !s.state))
-        return hipErrorInvalidValue;
+    if (!stream_shape(a, s.lead, s.state_len, s.state)) return hipErrorInvalidValue;
     const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
     if (total + 4 >= (1ull << 31)) return hipErrorInvalidValue;
     a.nf_magic = a.nf_shift = 0;
-    if (a.n_frames >= 4) {  // the reciprocal of launch_w (its one-wrap lane fix-up needs n_frames >= 4)
-        const unsigned long long d = a.n_frames;
-        unsigned l = 0;
-        while ((1ull << l) < d) ++l;
-        const unsigned __int128 num = static_cast<unsigned __int128>(1) << (31 + l);
-        a.nf_magic = static_cast<uint32_t>((num + d - 1) / d);
-        a.nf_shift = l - 1;
-    }
-    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * a.mel_wpitch) * sizeof(float) + 16;
+    if (a.n_frames >= 4) set_frame_reciprocal(a);  // the reciprocal of launch_w (its one-wrap lane fix-up needs n_frames >= 4)
+    const size_t lds = c256_lds_bytes(WAVES, a);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (total == 0) return hipSuccess;
-    const unsigned long long quads = (total + 3) / 4;
-    unsigned long long blocks = (quads + WAVES - 1) / WAVES;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    a.q_base = static_cast<uint32_t>(quads / grid);
-    a.q_rem = static_cast<uint32_t>(quads % grid);
-    auto go = [&](auto kern, const char *name) {
-        if (lds > 48 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     static_cast<int>(lds));
-            if (e != hipSuccess) return e;
-        }
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{}, s);
-        return hipGetLastError();
-    };
+    const unsigned grid = plan_quads(a, (total + 3) / 4, WAVES, num_cus);
+    const MultiArg<false> none{};
     // the one-shot builds' template arguments (RES 30 / 2) with STRM: the same arithmetic per frame, bit for bit
-    if (mfcc) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, false, FrameStreamArgs>, "ss_mfcc_c256s<10,exact,bank421,sym>");
-    return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, FrameStreamArgs>, "ss_mfcc_c256s<10,exact,bank421,mfe>");
+    if (paired_mfcc(a))
+        return launch_kernel(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, false, FrameStreamArgs>,
+                             "ss_mfcc_c256s<10,exact,bank421,sym>", grid, WAVES, lds, stream, info, a, none, s);
+    return launch_kernel(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, FrameStreamArgs>,
+                         "ss_mfcc_c256s<10,exact,bank421,mfe>", grid, WAVES, lds, stream, info, a, none, s);
 }
 
 // the ragged streaming launch for either chunk format: SPT = FrameStreamPackedArgs (float chunks) or FrameStreamPackedPcmArgs (16-bit
@@ -1499,40 +1457,22 @@ static hipError_t launch_stream_packed_w12(const Fast512Args &a_in, const SPT &s
 {
     constexpr int WAVES = 12;
     Fast512Args a = a_in;
-    // the shapes of launch_mfcc_c256_stream
-    const bool b421 = a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1;
-    const bool mfcc = a.out_mfe == 0 && a.n_filters == 40 && a.paired == 2;
-    const bool mfe = a.out_mfe == 1 && a.n_filters <= 40;
-    if (a.fullp || a.center || a.win_floats > 0 || a.preemph != 0.0f || a.flen != 320 || a.spectrum_exponent == 2 || !b421 || !(mfcc || mfe) ||
-        (a.step & 1u) || a.step == 0 || a.step > a.flen || s.step != a.step || s.lead != static_cast<int>(a.flen - a.step) ||
-        s.state_len < static_cast<unsigned>(s.lead) || (s.state_len > 0 && !s.pool) || s.n_active == 0)
-        return hipErrorInvalidValue;
+    // the shapes of launch_mfcc_c256_stream, whole hops of the pool's own step, at least one entry
+    if (!stream_shape(a, s.lead, s.state_len, s.pool) || a.step == 0 || s.step != a.step || s.n_active == 0) return hipErrorInvalidValue;
     const unsigned long long total = s.total_rows;
     if (total + 4 >= (1ull << 31)) return hipErrorInvalidValue;
     a.nf_magic = a.nf_shift = 0;
-    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * a.mel_wpitch) * sizeof(float) + 16;
+    const size_t lds = c256_lds_bytes(WAVES, a);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     // an empty output block still gets one workgroup: the entry pass runs
-    const unsigned long long quads = (total + 3) / 4;
-    unsigned long long blocks = quads ? (quads + WAVES - 1) / WAVES : 1;
-    const unsigned long long cap = static_cast<unsigned long long>(num_cus > 0 ? num_cus : 256);
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = static_cast<unsigned>(blocks);
-    a.q_base = static_cast<uint32_t>(quads / grid);
-    a.q_rem = static_cast<uint32_t>(quads % grid);
-    auto go = [&](auto kern, const char *name) {
-        if (lds > 48 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     static_cast<int>(lds));
-            if (e != hipSuccess) return e;
-        }
-        if (info) *info = LaunchInfo{name, grid, static_cast<unsigned>(WAVES * 64), lds};
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a, MultiArg<false>{}, sp);
-        return hipGetLastError();
-    };
+    const unsigned grid = plan_quads(a, (total + 3) / 4, WAVES, num_cus, true);
+    const MultiArg<false> none{};
     // the dense streaming builds' template arguments with the packed argument pack: the same arithmetic per frame, bit for bit
-    if (mfcc) return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, false, SPT>, mfcc_name);
-    return go(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, SPT>, mfe_name);
+    if (paired_mfcc(a))
+        return launch_kernel(ss_mfcc_c256<10, true, false, WAVES, true, 10, 30, 0, 0, false, false, false, false, SPT>, mfcc_name, grid, WAVES, lds,
+                             stream, info, a, none, sp);
+    return launch_kernel(ss_mfcc_c256<10, true, false, WAVES, true, 10, 2, 1, 0, false, false, false, false, SPT>, mfe_name, grid, WAVES, lds, stream,
+                         info, a, none, sp);
 }
 
 hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a, const FrameStreamPackedArgs &s, hipStream_t stream, int num_cus,
@@ -1553,7 +1493,7 @@ hipError_t launch_mfcc_c256_stream_packed(const Fast512Args &a, const FrameStrea
 
 bool mfcc_c256_has_mfe(const Fast512Args &a)
 {
-    return a.flen == 320 && a.spectrum_exponent != 2 && a.mel_q4[0] == 4 && a.mel_q4[1] == 2 && a.mel_q4[2] == 1 && a.n_filters <= 40;
+    return a.flen == 320 && a.spectrum_exponent != 2 && bank421(a) && a.n_filters <= 40;
 }
 
 hipError_t launch_mfcc_c256(const Fast512Args &a, hipStream_t stream, int num_cus, LaunchInfo *info)

@@ -450,19 +450,12 @@ hipError_t launch_mel_c1024_tile(const Mel2048Args &a, hipStream_t stream, int n
     size_t lds = (static_cast<size_t>(kWavesM) * kWaveFloatsM + L::kMelW + 8 + 32 * static_cast<size_t>(a.mel_wpitch)) * sizeof(float);
     lds += (kTileFloats + 2 * kTileBufs + 2) * sizeof(float);
     const bool tile = !a.out_stft && !a.fullp && a.rows <= kTileRows && a.rows % 4 == 0 && a.n_filters <= 128 && a.n_filters % 8 == 0 &&
-                      lds <= 160 * 1024 && a.batch >= static_cast<uint32_t>(num_cus > 0 ? num_cus : 256);
+                      lds <= 160 * 1024 && a.batch >= cu_cap(num_cus);
     if (!tile) return hipErrorInvalidValue;
-    const unsigned cap = static_cast<unsigned>(num_cus > 0 ? num_cus : 256);
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * ((a.rows + 1) / 2);
     if (units >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned long long blocks = (units + kWavesM - 1) / kWavesM;
-    const unsigned grid = static_cast<unsigned>(blocks < cap ? blocks : cap);
-    auto kern = ss_mel_c1024<kWavesM, false, false, true>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    if (info) *info = LaunchInfo{"ss_mel_c1024<tile>", grid, static_cast<unsigned>(kWavesM * 64), lds};
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kWavesM * 64), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(ss_mel_c1024<kWavesM, false, false, true>, "ss_mel_c1024<tile>", cu_capped_grid(units, kWavesM, num_cus), kWavesM, lds,
+                         stream, info, a);
 }
 
 }  // namespace ss
