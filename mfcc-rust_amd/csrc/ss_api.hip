@@ -20,6 +20,7 @@
 
 #include "ss_device.h"
 #include "ss_internal.h"
+#include "ss_launch_args.h"
 
 struct ss_config {
     ss::HostTables host;
@@ -187,6 +188,77 @@ void fill_common(const ss_config *cfg, ss::FrontArgs &a)
     a.spectrum_exponent = h.params.spectrum_exponent;
 }
 
+// The device-side launchers' prologue.  The tables live on the device the config was created on: a launch from another current
+// device would hand this device pointers into that one's memory; and no more work goes behind a launch that reported a
+// device-side error.
+int device_ready(const ss_config *cfg)
+{
+    const int drc = check_device(cfg);
+    return drc ? drc : pending_device_error(cfg);
+}
+
+// The configuration's part of an MFCC-path argument block (OUT_MFCC / OUT_MFE / OUT_POWER): frame shape, pad mode, pre-emphasis,
+// window, the 1/N scale and the outputs.  The caller adds the samples, its shape, frame_mode and the DCT scales.
+ss::FrontArgs mfcc_front_args(const ss_config *cfg, int out_kind, float *out0, float *out1)
+{
+    const ss::HostTables &h = cfg->host;
+    ss::FrontArgs a{};
+    fill_common(cfg, a);
+    a.flen = h.d.flen;
+    a.step = h.d.step;
+    a.pad_reflect = h.params.pad_mode == SS_PAD_REFLECT;
+    a.preemph = h.params.preemph_coef;
+    a.preemph_shift = static_cast<uint32_t>(h.params.preemph_shift > 0 ? h.params.preemph_shift : 1);
+    a.window = cfg->d_window_mfcc;
+    a.scale = 1.0f / static_cast<float>(h.params.fft_points);  // processing.rs:180
+    a.out_kind = out_kind;
+    a.out0 = out0;
+    a.out1 = out1;
+    return a;
+}
+void set_dct_scales(ss::FrontArgs &a, const ss::DctScales &s)
+{
+    a.dct_scale_k = s.k;
+    a.dct_scale_0 = s.s0;
+    a.dct_scale_00 = s.s00;
+}
+
+// The configuration's part of an STFT-path argument block (OUT_MEL / OUT_STFT): hop, padding rows, the Vorbis window, wnorm and
+// the output.  The caller adds the samples and its shape (a continuous stream has no padding rows and says n_pad = 0).
+ss::FrontArgs stft_front_args(const ss_config *cfg, int out_kind, float *out0)
+{
+    const ss::HostTables &h = cfg->host;
+    ss::FrontArgs a{};
+    fill_common(cfg, a);
+    a.hop = h.d.hop;
+    a.n_pad = h.d.n_pad;
+    a.window = cfg->d_window_stft;
+    a.scale = h.d.wnorm;
+    a.out_kind = out_kind;
+    a.out0 = out0;
+    return a;
+}
+
+// One rung of a launcher's candidate ladder, from what its launch function returned: launched (g_last_kernel names what ran),
+// declined -- hipErrorInvalidValue BEFORE the launch: the configuration does not fit this kernel (no build for the shape, LDS
+// budget), the next candidate is tried -- or failed (rc: the SS_ERR_HIP code, `what` in its message).  last: nothing stands behind
+// this candidate, so whatever is not a launch is a failure.
+enum class Tried { launched, declined, failed };
+struct Step {
+    Tried t;
+    int rc;
+    bool done() const { return t != Tried::declined; }
+};
+Step tried(hipError_t e, const char *what, const ss::LaunchInfo &info, bool last = false)
+{
+    if (e == hipSuccess) {
+        g_last_kernel = info.kernel_name;
+        return {Tried::launched, SS_OK};
+    }
+    if (e == hipErrorInvalidValue && !last) return {Tried::declined, SS_OK};
+    return {Tried::failed, hip_fail(e, what)};
+}
+
 // The samples of a call: floats, or signed 16-bit PCM with its scale (the _i16 entry points -- the pool's chunks, the packed one-shot
 // calls' clips: the same chain on the kernels' PCM builds).
 struct PoolChunks {
@@ -213,23 +285,103 @@ int check_pcm_scale(float scale)
 
 // The float copy of an equal-length PCM batch for a kernel without a PCM build (launch_frames, launch_stft): one conversion launch
 // into a stream-ordered temporary, freed in stream order when the call returns.  (Stream-ordered allocation: this path is not
-// offered for stream capture.)
+// offered for stream capture.)  Made once, on the first candidate that needs it: need() is a no-op for a float call and once
+// a.x is set.
 struct PcmFloatCopy {
+    const ss::BatchPcmArgs *pcm;
+    size_t batch, n, ld;
+    hipStream_t st;
     float *p = nullptr;
-    hipStream_t st = nullptr;
     ~PcmFloatCopy()
     {
         if (p) (void)hipFreeAsync(p, st);
     }
-    int make(const ss::BatchPcmArgs &pcm, size_t batch, size_t n, size_t ld, hipStream_t stream)
+    int need(ss::FrontArgs &a)
     {
-        st = stream;
-        SS_HIP(hipMallocAsync(reinterpret_cast<void **>(&p), ((batch - 1) * ld + n) * sizeof(float), stream));
-        const hipError_t ec = ss::launch_pcm_to_float(pcm.x, p, batch, n, ld, pcm.scale, stream);
+        if (!pcm || a.x) return SS_OK;
+        SS_HIP(hipMallocAsync(reinterpret_cast<void **>(&p), ((batch - 1) * ld + n) * sizeof(float), st));
+        const hipError_t ec = ss::launch_pcm_to_float(pcm->x, p, batch, n, ld, pcm->scale, st);
         if (ec != hipSuccess) return hip_fail(ec, "launch_pcm_to_float");
+        a.x = p;
         return SS_OK;
     }
 };
+
+// SS_DEBUG_TIMES=<file> (lab build, diagnostic only): per-wave realtime stamps of ONE float MFCC launch of the 512-point kernel,
+// taken on extra launches of the call's own argument block in front of the real one.
+#if SS_LAB
+int debug_times_launches(const ss_config *cfg, ss::Fast512Args f, hipStream_t stream)
+{
+    static const char *dbg_path = std::getenv("SS_DEBUG_TIMES");
+    static bool dbg_done = false;
+    if (!dbg_path || dbg_done || f.out_mfe) return SS_OK;
+    dbg_done = true;
+    ss::LaunchInfo info{};
+    const size_t nwaves = static_cast<size_t>(cfg->num_cus) * 16;
+    DeviceBuf db;
+    int rc2 = db.alloc(nwaves * 6 * sizeof(unsigned long long));
+    if (rc2) return rc2;
+    DeviceBuf flush;  // larger than the Infinity Cache: the stamped launch reads its samples from HBM like a bench step
+    rc2 = flush.alloc(512ull << 20);
+    if (rc2) return rc2;
+    // the last repetition has warm code / tables and cold samples; SS_DEBUG_TIMES_REPS=<n> stamps n launches and
+    // writes <file>.<k> for each from the third on (are the same workgroups late every time?)
+    const char *reps_env = std::getenv("SS_DEBUG_TIMES_REPS");
+    const int reps = reps_env && std::atoi(reps_env) > 3 ? std::atoi(reps_env) : 3;
+    std::vector<unsigned long long> hb(nwaves * 6);
+    for (int rep = 0; rep < reps; ++rep) {
+        SS_HIP(hipMemsetAsync(flush.p, rep, 512ull << 20, stream));
+        SS_HIP(hipMemsetAsync(db.p, 0, nwaves * 6 * sizeof(unsigned long long), stream));
+        f.dbg = db.as<unsigned long long>();
+        hipError_t e2 = ss::launch_mfcc_c256(f, stream, cfg->num_cus, &info);
+        if (e2 != hipSuccess) return hip_fail(e2, "launch_mfcc_c256");
+        SS_HIP(hipStreamSynchronize(stream));
+        if (rep < 2) continue;
+        SS_HIP(hipMemcpy(hb.data(), db.p, hb.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        const std::string path = rep == reps - 1 ? std::string(dbg_path) : std::string(dbg_path) + "." + std::to_string(rep);
+        if (FILE *fp = std::fopen(path.c_str(), "w")) {
+            for (size_t w = 0; w < nwaves; ++w)
+                if (hb[6 * w + 2])
+                    std::fprintf(fp, "%zu %llu %llu %llu %llu %llu %llu %llu\n", w, hb[6 * w], hb[6 * w + 1], hb[6 * w + 2],
+                                 hb[6 * w + 3] >> 32, hb[6 * w + 3] & 0xffffffffull, hb[6 * w + 4], hb[6 * w + 5]);
+            std::fclose(fp);
+        }
+    }
+    return SS_OK;
+}
+#else
+constexpr int debug_times_launches(const ss_config *, const ss::Fast512Args &, hipStream_t) { return SS_OK; }
+#endif
+
+// launch_mfcc_c2048, in the lab build with SS_DEBUG_ROWS=<file> (diagnostic only): frame 0's P row and ln(mel) row of the launch,
+// dumped to the file once it ran.
+#if SS_LAB
+hipError_t launch_mfcc_c2048_rows(ss::Mfcc4096Args &f, hipStream_t stream, int num_cus, ss::LaunchInfo *info)
+{
+    static const char *rows_path = std::getenv("SS_DEBUG_ROWS");
+    constexpr size_t kDbgFloats = 131072;  // >= 1028 + 256 + 4 * 4096 (stage dumps) and >= waves x 16 x 2 (SS_PROF5 phase sums)
+    if (rows_path && hipMalloc(reinterpret_cast<void **>(&f.dbg), kDbgFloats * sizeof(float)) == hipSuccess)
+        (void)hipMemsetAsync(f.dbg, 0, kDbgFloats * sizeof(float), stream);
+    const hipError_t e4 = ss::launch_mfcc_c2048(f, stream, num_cus, info);
+    if (e4 != hipSuccess && f.dbg) (void)hipFree(f.dbg);
+    if (e4 == hipSuccess && f.dbg) {
+        std::vector<float> rows(kDbgFloats);
+        (void)hipStreamSynchronize(stream);
+        (void)hipMemcpy(rows.data(), f.dbg, rows.size() * sizeof(float), hipMemcpyDeviceToHost);
+        (void)hipFree(f.dbg);
+        if (FILE *fp = std::fopen(rows_path, "wb")) {
+            std::fwrite(rows.data(), sizeof(float), rows.size(), fp);
+            std::fclose(fp);
+        }
+    }
+    return e4;
+}
+#else
+inline hipError_t launch_mfcc_c2048_rows(const ss::Mfcc4096Args &f, hipStream_t stream, int num_cus, ss::LaunchInfo *info)
+{
+    return ss::launch_mfcc_c2048(f, stream, num_cus, info);
+}
+#endif
 
 // MFCC-path launch (OUT_MFCC / OUT_MFE / OUT_POWER).
 // rows_are_frames: d_x is a frames matrix [batch x n] (row stride ld) -- every row is one frame of n <= fft_points samples,
@@ -239,7 +391,7 @@ struct PcmFloatCopy {
 // launched and kNoMultiBuild comes back (the caller then launches batch by batch).
 // `pcm` (the _i16 entry points; d_x is null then): the batch as signed 16-bit PCM.  The call runs the PCM build of the kernel the
 // float call would pick where that kernel has one (the 512-point kernel's contract-framing builds without fused pre-emphasis, the
-// generic kernel); every other dedicated kernel runs behind one conversion launch into a stream-ordered temporary (to_float below)
+// generic kernel); every other dedicated kernel runs behind one conversion launch into a stream-ordered temporary (PcmFloatCopy)
 // and reports its own name.  Either way the outputs are bit for bit those of the float call on (float)pcm * scale.
 struct MultiBatches {
     int n;
@@ -262,17 +414,10 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
     if (!(pcm ? static_cast<const void *>(pcm->x) : d_x) || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
     if (ld < n) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
     if (n > 0x7fffffffull || batch > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "clip too long / batch too large");
-    {
-        // the tables live on the device the config was created on: a launch from another current device would hand this
-        // device pointers into that one's memory
-        const int drc = check_device(cfg);
-        if (drc) return drc;
-        const int erc = pending_device_error(cfg);  // no more work behind a launch that reported a device-side error
-        if (erc) return erc;
-    }
+    int rc = device_ready(cfg);
+    if (rc) return rc;
     const ss::HostTables &h = cfg->host;
     size_t T = 0;
-    int rc = SS_OK;
     if (rows_are_frames) {
         if (n == 0 || n > h.params.fft_points) return ss::fail(SS_ERR_ARG, "frame length must be in [1, fft_points]");
         T = 1;
@@ -280,51 +425,27 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
         rc = ss::num_frames(h.params, n, T);
     }
     if (rc) return rc;
-    ss::FrontArgs a{};
-    fill_common(cfg, a);
+    ss::FrontArgs a = mfcc_front_args(cfg, out_kind, out0, out1);
     a.x = d_x;
     a.ld = ld;
     a.n_samples = static_cast<uint32_t>(n);
     a.batch = static_cast<uint32_t>(batch);
-    a.flen = rows_are_frames ? static_cast<uint32_t>(n) : h.d.flen;
-    a.step = rows_are_frames ? static_cast<uint32_t>(n) : h.d.step;
     a.n_frames = static_cast<uint32_t>(T);
+    if (rows_are_frames) {  // every row is one frame of n samples: no window, no pre-emphasis
+        a.flen = a.step = static_cast<uint32_t>(n);
+        a.preemph = 0.0f;
+        a.window = nullptr;
+    }
     // processing.rs:110-120 as written: nothing is copied for > 2 frames, x[0..flen] into every row otherwise
     if (rows_are_frames) a.frame_mode = ss::FRAME_NORMAL;
     else if (h.params.framing == SS_FRAMING_LITERAL) a.frame_mode = T > 2 ? ss::FRAME_ZERO : ss::FRAME_FIRST;
     else if (h.params.framing == SS_FRAMING_CENTER) a.frame_mode = ss::FRAME_CENTER;  // librosa center=True (generic kernel only)
     else if (h.params.framing == SS_FRAMING_PADDED) a.frame_mode = ss::FRAME_PADDED;  // zero_padding = true (generic kernel only)
     else a.frame_mode = ss::FRAME_NORMAL;
-    a.pad_reflect = h.params.pad_mode == SS_PAD_REFLECT;
-    a.preemph = rows_are_frames ? 0.0f : h.params.preemph_coef;
-    a.preemph_shift = static_cast<uint32_t>(h.params.preemph_shift > 0 ? h.params.preemph_shift : 1);
-    a.window = rows_are_frames ? nullptr : cfg->d_window_mfcc;
-    a.scale = 1.0f / static_cast<float>(h.params.fft_points);  // processing.rs:180
-    // feature.rs:126-131 (n = T * M as f32) or scipy ortho over the axis length
-    const float g = h.params.dct2_gain;
-    const float M = static_cast<float>(h.params.num_filters);
-    if (h.params.dct_norm == SS_DCT_ORTHO) {
-        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * M));
-        a.dct_scale_0 = a.dct_scale_00 = g * (1.0f / sqrtf(4.0f * M));
-    } else {
-        const float nn = static_cast<float>(T * h.params.num_filters);
-        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * nn));
-        a.dct_scale_0 = g;
-        a.dct_scale_00 = g * (1.0f / sqrtf(4.0f * nn));
-    }
-    a.out_kind = out_kind;
-    a.out0 = out0;
-    a.out1 = out1;
+    set_dct_scales(a, ss::dct_scales(h.params, T));
     ss::LaunchInfo info{};
     // pcm: the float copy of the batch for a kernel without a PCM build -- made once, on the first candidate that needs it
-    PcmFloatCopy tmp;
-    auto to_float = [&]() -> int {
-        if (!pcm || d_x) return SS_OK;
-        const int trc = tmp.make(*pcm, batch, n, ld, stream);
-        if (trc) return trc;
-        a.x = d_x = tmp.p;
-        return SS_OK;
-    };
+    PcmFloatCopy tmp{pcm, batch, n, ld, stream};
     // fft_points = 512 MFCC: the specialised wave-private kernel (its builds: default bank / run-time bank, window,
     // pre-emphasis, mfe and power outputs, librosa variants)
     const bool force_generic = ss::dbg_force_generic();
@@ -344,146 +465,36 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
                          (out_kind == ss::OUT_MFCC || (out_kind == ss::OUT_MFE && mfe_shape) || (out_kind == ss::OUT_POWER && mfe_shape && !front)) &&
                          (lib_variant ? lib_ok : (!front || mfe_shape)) && (a.frame_mode == ss::FRAME_NORMAL || centre);
     const bool fits32 = static_cast<unsigned long long>(batch) * T < 0xffffffffull;
-#if SS_LAB
-    static const char *dbg_path = std::getenv("SS_DEBUG_TIMES");  // diagnostic only (lab build): per-wave realtime stamps of ONE launch
-    static bool dbg_done = false;
-#endif
     if (fast_ok && fits32) {
-        ss::Fast512Args f{};
-        f.x = d_x;
-        f.ld = ld;
-        f.n_samples = a.n_samples;
-        f.batch = a.batch;
-        f.flen = a.flen;
-        f.step = a.step;
-        f.n_frames = a.n_frames;
-        f.scale = a.scale;
-        f.spectrum_exponent = a.spectrum_exponent;
-        f.tab = cfg->d_fast_tab;
-        f.mel_wpitch = cfg->fast.wpitch;
-        for (int s = 0; s < 3; ++s) f.mel_q4[s] = cfg->fast.q4[s];
-        f.n_filters = a.n_filters;
-        f.n_ceps = a.n_ceps;
-        f.dct_scale_k = a.dct_scale_k;
-        f.dct_scale_0 = a.dct_scale_0;
-        f.dct_scale_00 = a.dct_scale_00;
-        f.dc_elimination = a.dc_elimination;
-        f.out = out0;
-        f.out_energy = out1;
-        f.out_mfe = out_kind == ss::OUT_MFE ? 1 : (out_kind == ss::OUT_POWER ? 2 : 0);
-        f.win_floats = a.window ? cfg->fast.win_floats : 0;
-        f.preemph = a.preemph;
-        f.preemph_shift = a.preemph_shift;
-        f.center = centre;
-        f.pad_reflect = a.pad_reflect;
-        f.fullp = cfg->fast.fullp;
-        f.paired = cfg->fast.paired ? (cfg->fast.tight ? 2 : 1) : 0;
-#if SS_LAB
-        if (dbg_path && !dbg_done && !f.out_mfe && !multi && !pcm) {
-            dbg_done = true;
-            const size_t nwaves = static_cast<size_t>(cfg->num_cus) * 16;
-            DeviceBuf db;
-            int rc2 = db.alloc(nwaves * 6 * sizeof(unsigned long long));
-            if (rc2) return rc2;
-            DeviceBuf flush;  // larger than the Infinity Cache: the stamped launch reads its samples from HBM like a bench step
-            rc2 = flush.alloc(512ull << 20);
-            if (rc2) return rc2;
-            // the last repetition has warm code / tables and cold samples; SS_DEBUG_TIMES_REPS=<n> stamps n launches and
-            // writes <file>.<k> for each from the third on (are the same workgroups late every time?)
-            const char *reps_env = std::getenv("SS_DEBUG_TIMES_REPS");
-            const int reps = reps_env && std::atoi(reps_env) > 3 ? std::atoi(reps_env) : 3;
-            std::vector<unsigned long long> hb(nwaves * 6);
-            for (int rep = 0; rep < reps; ++rep) {
-                SS_HIP(hipMemsetAsync(flush.p, rep, 512ull << 20, stream));
-                SS_HIP(hipMemsetAsync(db.p, 0, nwaves * 6 * sizeof(unsigned long long), stream));
-                f.dbg = db.as<unsigned long long>();
-                hipError_t e2 = ss::launch_mfcc_c256(f, stream, cfg->num_cus, &info);
-                if (e2 != hipSuccess) return hip_fail(e2, "launch_mfcc_c256");
-                SS_HIP(hipStreamSynchronize(stream));
-                if (rep < 2) continue;
-                SS_HIP(hipMemcpy(hb.data(), db.p, hb.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                const std::string path = rep == reps - 1 ? std::string(dbg_path) : std::string(dbg_path) + "." + std::to_string(rep);
-                if (FILE *fp = std::fopen(path.c_str(), "w")) {
-                    for (size_t w = 0; w < nwaves; ++w)
-                        if (hb[6 * w + 2])
-                            std::fprintf(fp, "%zu %llu %llu %llu %llu %llu %llu %llu\n", w, hb[6 * w], hb[6 * w + 1], hb[6 * w + 2],
-                                         hb[6 * w + 3] >> 32, hb[6 * w + 3] & 0xffffffffull, hb[6 * w + 4], hb[6 * w + 5]);
-                    std::fclose(fp);
-                }
-            }
-            f.dbg = nullptr;
-        }
-#endif
+        ss::Fast512Args f = ss::fast512_args(cfg->fast, cfg->d_fast_tab, a);
+        if (!multi && !pcm && (rc = debug_times_launches(cfg, f, stream))) return rc;
         f.dbg = g_call_stamps;
 #if SS_LAB
         if (!f.dbg) f.dbg = g_stamp_buffer.load(std::memory_order_relaxed);
 #endif
         if (multi) {
-            const hipError_t em = ss::launch_mfcc_c256_multi(f, multi->n, multi->x, multi->out, multi->clips, stream, cfg->num_cus, &info);
-            if (em == hipErrorInvalidValue) return kNoMultiBuild;  // (before the launch: this shape has no batch-table build)
-            if (em != hipSuccess) return hip_fail(em, "launch_mfcc_c256_multi");
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
+            const Step s = tried(ss::launch_mfcc_c256_multi(f, multi->n, multi->x, multi->out, multi->clips, stream, cfg->num_cus, &info),
+                                 "launch_mfcc_c256_multi", info);
+            return s.done() ? s.rc : kNoMultiBuild;  // (declined before the launch: this shape has no batch-table build)
         }
         if (pcm) {
-            const hipError_t ep = ss::launch_mfcc_c256(f, *pcm, stream, cfg->num_cus, &info);
-            if (ep == hipSuccess) {
-                g_last_kernel = info.kernel_name;
-                return SS_OK;
-            }
-            // hipErrorInvalidValue before the launch: no PCM build for this shape (or no build at all) -> the float build on the copy
-            if (ep != hipErrorInvalidValue) return hip_fail(ep, "launch_mfcc_c256 (PCM)");
-            if ((rc = to_float())) return rc;
-            f.x = d_x;
+            // declined: no PCM build for this shape (or no build at all) -> the float build on the copy
+            const Step s = tried(ss::launch_mfcc_c256(f, *pcm, stream, cfg->num_cus, &info), "launch_mfcc_c256 (PCM)", info);
+            if (s.done()) return s.rc;
+            if ((rc = tmp.need(a))) return rc;
+            f.x = a.x;
         }
-        const hipError_t e = ss::launch_mfcc_c256(f, stream, cfg->num_cus, &info);
-        if (e == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel (LDS budget) -> next candidate
-        if (e != hipErrorInvalidValue) return hip_fail(e, "launch_mfcc_c256");
+        const Step s = tried(ss::launch_mfcc_c256(f, stream, cfg->num_cus, &info), "launch_mfcc_c256", info);
+        if (s.done()) return s.rc;
     }
     // fft_points = 4096 MFCC: the twelve-wave default-shape build takes a batch table too
-    auto fill4096 = [&](ss::Mfcc4096Args &f) {
-        f.preemph = a.preemph;
-        f.preemph_shift = a.preemph_shift;
-        f.x = d_x;
-        f.ld = ld;
-        f.n_samples = a.n_samples;
-        f.batch = a.batch;
-        f.flen = a.flen;
-        f.step = a.step;
-        f.n_frames = a.n_frames;
-        f.scale = a.scale;
-        f.spectrum_exponent = a.spectrum_exponent;
-        f.tab = cfg->d_mfcc4096_tab;
-        f.mel_wpitch = cfg->mfcc4096.wpitch;
-        for (int s = 0; s < 4; ++s) f.mel_q4[s] = cfg->mfcc4096.q4[s];
-        f.cos_floats = cfg->mfcc4096.cos_floats;
-        f.dct_fold2 = cfg->mfcc4096.dct_fold2 ? 1 : 0;
-        f.n_filters = a.n_filters;
-        f.n_ceps = a.n_ceps;
-        f.dct_scale_k = a.dct_scale_k;
-        f.dct_scale_0 = a.dct_scale_0;
-        f.dct_scale_00 = a.dct_scale_00;
-        f.dc_elimination = a.dc_elimination;
-        f.out = out0;
-        f.out_energy = out1;
-        f.out_mfe = out_kind == ss::OUT_MFE;
-        f.window = a.window;
-        f.stamps = g_call_stamps2;
-    };
     if (multi) {
         if (!force_generic && cfg->mfcc4096.ok && out_kind == ss::OUT_MFCC && a.frame_mode == ss::FRAME_NORMAL) {
-            ss::Mfcc4096Args f{};
-            fill4096(f);
-            const hipError_t em = ss::launch_mfcc_c2048_multi(f, multi->n, multi->x, multi->out, multi->clips, stream, cfg->num_cus, &info);
-            if (em == hipSuccess) {
-                g_last_kernel = info.kernel_name;
-                return SS_OK;
-            }
-            if (em != hipErrorInvalidValue) return hip_fail(em, "launch_mfcc_c2048_multi");
+            ss::Mfcc4096Args f = ss::mfcc4096_args(cfg->mfcc4096, cfg->d_mfcc4096_tab, a);
+            f.stamps = g_call_stamps2;
+            const Step s = tried(ss::launch_mfcc_c2048_multi(f, multi->n, multi->x, multi->out, multi->clips, stream, cfg->num_cus, &info),
+                                 "launch_mfcc_c2048_multi", info);
+            if (s.done()) return s.rc;
         }
         return kNoMultiBuild;  // the other kernels take one batch per launch
     }
@@ -491,159 +502,43 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
     // headline kernel has no build for (ss_mfcc512w.hip): optional frame window, centred frames, fused pre-emphasis
     if (!force_generic && cfg->mfcc512w.ok && static_cast<unsigned long long>(batch) * T + 4 < 0x7fffffffull &&
         (out_kind == ss::OUT_MFCC || out_kind == ss::OUT_MFE) && (a.frame_mode == ss::FRAME_NORMAL || centre)) {
-        if ((rc = to_float())) return rc;
-        ss::Mfcc256Args f{};
-        f.center = centre;
-        f.pad_reflect = a.pad_reflect;
-        f.preemph = a.preemph;
-        f.preemph_shift = a.preemph_shift;
-        f.x = d_x;
-        f.ld = ld;
-        f.n_samples = a.n_samples;
-        f.batch = a.batch;
-        f.flen = a.flen;
-        f.step = a.step;
-        f.n_frames = a.n_frames;
-        f.scale = a.scale;
-        f.spectrum_exponent = a.spectrum_exponent;
-        f.tab = cfg->d_mfcc512w_tab;
-        f.mel_wpitch = cfg->mfcc512w.wpitch;
-        for (int s = 0; s < 5; ++s) f.mel_q4[s] = cfg->mfcc512w.q4[s];
-        f.n_filters = a.n_filters;
-        f.n_ceps = a.n_ceps;
-        f.dct_scale_k = a.dct_scale_k;
-        f.dct_scale_0 = a.dct_scale_0;
-        f.dct_scale_00 = a.dct_scale_00;
-        f.dc_elimination = a.dc_elimination;
-        f.windowed = cfg->mfcc512w.windowed;
-        f.out_mfe = out_kind == ss::OUT_MFE;
-        f.out = out0;
-        f.out_energy = out1;
-        const hipError_t e5 = ss::launch_mfcc_c256w(f, stream, cfg->num_cus, &info);
-        if (e5 == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel (LDS budget) -> next candidate
-        if (e5 != hipErrorInvalidValue) return hip_fail(e5, "launch_mfcc_c256w");
+        if ((rc = tmp.need(a))) return rc;
+        const ss::Mfcc256Args f = ss::mfcc256_args(cfg->mfcc512w, cfg->d_mfcc512w_tab, a);
+        const Step s = tried(ss::launch_mfcc_c256w(f, stream, cfg->num_cus, &info), "launch_mfcc_c256w", info);
+        if (s.done()) return s.rc;
     }
     // fft_points = 256 MFCC / mfe: two frames per complex transform (ss_mfcc256.hip); optional frame window, fused pre-emphasis
     if (!force_generic && cfg->mfcc256.ok && static_cast<unsigned long long>(batch) * T + 8 < 0x7fffffffull &&
         (out_kind == ss::OUT_MFCC || out_kind == ss::OUT_MFE) && a.frame_mode == ss::FRAME_NORMAL && a.flen <= 256) {
-        if ((rc = to_float())) return rc;
-        ss::Mfcc256Args f{};
-        f.preemph = a.preemph;
-        f.preemph_shift = a.preemph_shift;
-        f.x = d_x;
-        f.ld = ld;
-        f.n_samples = a.n_samples;
-        f.batch = a.batch;
-        f.flen = a.flen;
-        f.step = a.step;
-        f.n_frames = a.n_frames;
-        f.scale = a.scale;
-        f.spectrum_exponent = a.spectrum_exponent;
-        f.tab = cfg->d_mfcc256_tab;
-        f.mel_wpitch = cfg->mfcc256.wpitch;
-        for (int s = 0; s < 3; ++s) f.mel_q4[s] = cfg->mfcc256.q4[s];
-        f.n_filters = a.n_filters;
-        f.n_ceps = a.n_ceps;
-        f.dct_scale_k = a.dct_scale_k;
-        f.dct_scale_0 = a.dct_scale_0;
-        f.dct_scale_00 = a.dct_scale_00;
-        f.dc_elimination = a.dc_elimination;
-        f.windowed = cfg->mfcc256.windowed;
-        f.out_mfe = out_kind == ss::OUT_MFE;
-        f.out = out0;
-        f.out_energy = out1;
-        const hipError_t e3 = ss::launch_mfcc_c256x2(f, stream, cfg->num_cus, &info);
-        if (e3 == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel (LDS budget) -> next candidate
-        if (e3 != hipErrorInvalidValue) return hip_fail(e3, "launch_mfcc_c256x2");
+        if ((rc = tmp.need(a))) return rc;
+        const ss::Mfcc256Args f = ss::mfcc256_args(cfg->mfcc256, cfg->d_mfcc256_tab, a);
+        const Step s = tried(ss::launch_mfcc_c256x2(f, stream, cfg->num_cus, &info), "launch_mfcc_c256x2", info);
+        if (s.done()) return s.rc;
     }
     // fft_points = 2048 / 1024 MFCC / mfe: two frames per wave (ss_mfcc2048.hip, ss_mfcc1024.hip), optional frame window
     // (both have librosa-compatible builds: centred frames, banks up to fs/2)
     if (!force_generic && (cfg->mfcc2048.ok || cfg->mfcc1024.ok) && fits32 && (out_kind == ss::OUT_MFCC || out_kind == ss::OUT_MFE) &&
         (a.frame_mode == ss::FRAME_NORMAL || centre)) {
-        if ((rc = to_float())) return rc;
-        ss::Mfcc2048Args f{};
-        f.preemph = a.preemph;
-        f.preemph_shift = a.preemph_shift;
-        f.x = d_x;
-        f.ld = ld;
-        f.n_samples = a.n_samples;
-        f.batch = a.batch;
-        f.flen = a.flen;
-        f.step = a.step;
-        f.n_frames = a.n_frames;
-        f.scale = a.scale;
-        f.spectrum_exponent = a.spectrum_exponent;
+        if ((rc = tmp.need(a))) return rc;
         const bool k2048 = cfg->mfcc2048.ok;
-        f.tab = k2048 ? cfg->d_mfcc2048_tab : cfg->d_mfcc1024_tab;
-        f.mel_wpitch = k2048 ? cfg->mfcc2048.wpitch : cfg->mfcc1024.wpitch;
-        for (int s = 0; s < 4; ++s) f.mel_q4[s] = k2048 ? cfg->mfcc2048.q4[s] : cfg->mfcc1024.q4[s];
-        f.n_filters = a.n_filters;
-        f.n_ceps = a.n_ceps;
-        f.dct_scale_k = a.dct_scale_k;
-        f.dct_scale_0 = a.dct_scale_0;
-        f.dct_scale_00 = a.dct_scale_00;
-        f.dc_elimination = a.dc_elimination;
-        f.windowed = k2048 ? cfg->mfcc2048.windowed : cfg->mfcc1024.windowed;
-        f.out_mfe = out_kind == ss::OUT_MFE;
-        f.center = centre;
-        f.pad_reflect = a.pad_reflect;
-        f.fullp = k2048 ? cfg->mfcc2048.fullp : cfg->mfcc1024.fullp;
-        f.out = out0;
-        f.out_energy = out1;
-        const hipError_t e2 = k2048 ? ss::launch_mfcc_c1024(f, stream, cfg->num_cus, &info) : ss::launch_mfcc_c512(f, stream, cfg->num_cus, &info);
-        if (e2 == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel (LDS budget) -> next candidate
-        if (e2 != hipErrorInvalidValue) return hip_fail(e2, k2048 ? "launch_mfcc_c1024" : "launch_mfcc_c512");
+        const ss::Mfcc2048Args f = k2048 ? ss::mfcc2048_args(cfg->mfcc2048, cfg->d_mfcc2048_tab, a) : ss::mfcc2048_args(cfg->mfcc1024, cfg->d_mfcc1024_tab, a);
+        const hipError_t e = k2048 ? ss::launch_mfcc_c1024(f, stream, cfg->num_cus, &info) : ss::launch_mfcc_c512(f, stream, cfg->num_cus, &info);
+        const Step s = tried(e, k2048 ? "launch_mfcc_c1024" : "launch_mfcc_c512", info);
+        if (s.done()) return s.rc;
     }
     // fft_points = 4096 MFCC / mfe (up to 256 filters): the one-frame-per-wave kernel
     if (!force_generic && cfg->mfcc4096.ok && fits32 && (out_kind == ss::OUT_MFCC || out_kind == ss::OUT_MFE) && a.frame_mode == ss::FRAME_NORMAL) {
-        if ((rc = to_float())) return rc;
-        ss::Mfcc4096Args f{};
-        fill4096(f);
-#if SS_LAB
-        static const char *rows_path = std::getenv("SS_DEBUG_ROWS");  // diagnostic only (lab build): frame 0's P row and ln(mel) row
-#else
-        constexpr const char *rows_path = nullptr;
-#endif
-        constexpr size_t kDbgFloats = 131072;  // >= 1028 + 256 + 4 * 4096 (stage dumps) and >= waves x 16 x 2 (SS_PROF5 phase sums)
-        if (rows_path && hipMalloc(reinterpret_cast<void **>(&f.dbg), kDbgFloats * sizeof(float)) == hipSuccess)
-            (void)hipMemsetAsync(f.dbg, 0, kDbgFloats * sizeof(float), stream);
-        const hipError_t e4 = ss::launch_mfcc_c2048(f, stream, cfg->num_cus, &info);
-        if (e4 != hipSuccess && f.dbg) (void)hipFree(f.dbg);
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel (LDS budget) -> generic kernel
-        if (e4 != hipSuccess && e4 != hipErrorInvalidValue) return hip_fail(e4, "launch_mfcc_c2048");
-        if (e4 == hipSuccess && f.dbg) {
-            std::vector<float> rows(kDbgFloats);
-            (void)hipStreamSynchronize(stream);
-            (void)hipMemcpy(rows.data(), f.dbg, rows.size() * sizeof(float), hipMemcpyDeviceToHost);
-            (void)hipFree(f.dbg);
-            if (FILE *fp = std::fopen(rows_path, "wb")) {
-                std::fwrite(rows.data(), sizeof(float), rows.size(), fp);
-                std::fclose(fp);
-            }
-        }
-        if (e4 == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
+        if ((rc = tmp.need(a))) return rc;
+        ss::Mfcc4096Args f = ss::mfcc4096_args(cfg->mfcc4096, cfg->d_mfcc4096_tab, a);
+        f.stamps = g_call_stamps2;
+        const Step s = tried(launch_mfcc_c2048_rows(f, stream, cfg->num_cus, &info), "launch_mfcc_c2048", info);
+        if (s.done()) return s.rc;
     }
     // (pcm: the generic kernel's PCM build, unless a dedicated candidate above already made the float copy and then declined)
-    hipError_t e = pcm && !d_x ? ss::launch_front_generic(a, *pcm, h.d.log2c, stream, cfg->num_cus, &info)
-                               : ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info);
-    if (e != hipSuccess) return hip_fail(e, "launch_front_generic");
-    g_last_kernel = info.kernel_name;
-    return SS_OK;
+    return tried(pcm && !a.x ? ss::launch_front_generic(a, *pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                             : ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info),
+                 "launch_front_generic", info, true)
+        .rc;
 }
 
 // STFT-path launch (OUT_MEL / OUT_STFT).
@@ -663,62 +558,27 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
     if (!(pcm ? static_cast<const void *>(pcm->x) : d_x) || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
     if (ld < n) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
     if (n == 0 || n > 0x7fffffffull || channels > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "bad clip length / channel count");
-    {
-        const int drc = check_device(cfg);  // see launch_frames
-        if (drc) return drc;
-        const int erc = pending_device_error(cfg);
-        if (erc) return erc;
-    }
+    int rc = device_ready(cfg);  // see launch_frames
+    if (rc) return rc;
     const ss::HostTables &h = cfg->host;
     size_t R = 0, Rreal = 0;
-    int rc = ss::stft_rows(h.params, n, R, Rreal);
-    if (rc) return rc;
-    ss::FrontArgs a{};
-    fill_common(cfg, a);
+    if ((rc = ss::stft_rows(h.params, n, R, Rreal))) return rc;
+    ss::FrontArgs a = stft_front_args(cfg, out_kind, out0);
     a.x = d_x;
     a.ld = ld;
     a.n_samples = static_cast<uint32_t>(n);
     a.batch = static_cast<uint32_t>(channels);
-    a.hop = h.d.hop;
-    a.n_pad = h.d.n_pad;
     a.rows = static_cast<uint32_t>(R);
     a.real_rows = static_cast<uint32_t>(Rreal);
-    a.window = cfg->d_window_stft;
-    a.scale = h.d.wnorm;
-    a.out_kind = out_kind;
-    a.out0 = out0;
     ss::LaunchInfo info{};
     // pcm: the float copy of the channels for a kernel without a PCM build -- made once, on the first candidate that needs it
-    PcmFloatCopy tmp;
-    auto to_float = [&]() -> int {
-        if (!pcm || d_x) return SS_OK;
-        const int trc = tmp.make(*pcm, channels, n, ld, stream);
-        if (trc) return trc;
-        a.x = d_x = tmp.p;
-        return SS_OK;
-    };
+    PcmFloatCopy tmp{pcm, channels, n, ld, stream};
     // fft_points = 2048 mel spectrogram: the wave-private kernel when its layout assumptions hold
     const bool force_generic = ss::dbg_force_generic();
     const bool want_stft = out_kind == ss::OUT_STFT;  // the stft builds do not use the bank (stft_only table blocks)
     if (!force_generic && (out_kind == ss::OUT_MEL || want_stft) && (cfg->mel2048.ok || (want_stft && cfg->mel2048.stft_only)) &&
         static_cast<unsigned long long>(a.rows + a.n_pad + 1) * a.hop < 0x7fffffffull) {
-        ss::Mel2048Args m{};
-        m.x = d_x;
-        m.ld = ld;
-        m.n_samples = a.n_samples;
-        m.batch = a.batch;
-        m.hop = a.hop;
-        m.n_pad = a.n_pad;
-        m.rows = a.rows;
-        m.real_rows = a.real_rows;
-        m.scale = a.scale;
-        m.tab = cfg->d_mel2048_tab;
-        m.fullp = cfg->mel2048.fullp;
-        m.mel_wpitch = cfg->mel2048.wpitch;
-        for (int s = 0; s < 4; ++s) m.mel_q4[s] = cfg->mel2048.q4[s];
-        m.n_filters = a.n_filters;
-        m.out = out0;
-        m.out_stft = out_kind == ss::OUT_STFT;
+        ss::Mel2048Args m = ss::mel2048_args(ss::mel_view(cfg->mel2048, cfg->d_mel2048_tab), a);
         m.ctl = cfg->d_err;
         m.stamps = g_call_stamps2;
         {
@@ -735,98 +595,84 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
         }
         if (multi) {
             // several blocks for one launch (ss_mel_spectrogram_batches_device): the twelve-wave mel build takes a batch table
-            const hipError_t em = ss::launch_mel_c1024_multi(m, multi->n, multi->x, multi->out, multi->clips, stream, cfg->num_cus, &info);
-            if (em == hipErrorInvalidValue) return kNoMultiBuild;
-            if (em != hipSuccess) return hip_fail(em, "launch_mel_c1024_multi");
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
+            const Step s = tried(ss::launch_mel_c1024_multi(m, multi->n, multi->x, multi->out, multi->clips, stream, cfg->num_cus, &info),
+                                 "launch_mel_c1024_multi", info);
+            return s.done() ? s.rc : kNoMultiBuild;
         }
         if (pcm) {
-            const hipError_t ep = ss::launch_mel_c1024(m, *pcm, stream, cfg->num_cus, &info);
-            if (ep == hipSuccess) {
-                g_last_kernel = info.kernel_name;
-                return SS_OK;
-            }
-            // hipErrorInvalidValue before the launch: the float call would not run the twelve-wave mel build -> its build on the copy
-            if (ep != hipErrorInvalidValue) return hip_fail(ep, "launch_mel_c1024 (PCM)");
-            if ((rc = to_float())) return rc;
-            m.x = d_x;
+            // declined: the float call would not run the twelve-wave mel build -> its build on the copy
+            const Step s = tried(ss::launch_mel_c1024(m, *pcm, stream, cfg->num_cus, &info), "launch_mel_c1024 (PCM)", info);
+            if (s.done()) return s.rc;
+            if ((rc = tmp.need(a))) return rc;
+            m.x = a.x;
         }
-        const hipError_t e = ss::launch_mel_c1024(m, stream, cfg->num_cus, &info);
-        if (e == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel (LDS budget) -> next candidate
-        if (e != hipErrorInvalidValue) return hip_fail(e, "launch_mel_c1024");
+        const Step s = tried(ss::launch_mel_c1024(m, stream, cfg->num_cus, &info), "launch_mel_c1024", info);
+        if (s.done()) return s.rc;
     }
     if (multi) return kNoMultiBuild;  // the other STFT-path kernels take one block per launch
     // fft_points = 512 mel spectrogram: four rows per wave (ss_mel512.hip), same layout assumptions
     if (!force_generic && (out_kind == ss::OUT_MEL || want_stft) && (cfg->mel512.ok || (want_stft && cfg->mel512.stft_only)) &&
         static_cast<unsigned long long>(a.rows + a.n_pad + 1) * a.hop < 0x7fffffffull) {
-        if ((rc = to_float())) return rc;
-        ss::Mel512Args m{};
-        m.x = d_x;
-        m.ld = ld;
-        m.n_samples = a.n_samples;
-        m.batch = a.batch;
-        m.hop = a.hop;
-        m.n_pad = a.n_pad;
-        m.rows = a.rows;
-        m.real_rows = a.real_rows;
-        m.scale = a.scale;
-        m.tab = cfg->d_mel512_tab;
-        m.mel_wpitch = cfg->mel512.wpitch;
-        for (int s = 0; s < 5; ++s) m.mel_q4[s] = cfg->mel512.q4[s];
-        m.fullp = cfg->mel512.fullp;
-        m.n_filters = a.n_filters;
-        m.out = out0;
-        m.out_stft = out_kind == ss::OUT_STFT;
-        const hipError_t e = ss::launch_mel_c256(m, stream, cfg->num_cus, &info);
-        if (e == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel (LDS budget) -> next candidate
-        if (e != hipErrorInvalidValue) return hip_fail(e, "launch_mel_c256");
+        if ((rc = tmp.need(a))) return rc;
+        const ss::Mel512Args m = ss::mel512_args(cfg->mel512, cfg->d_mel512_tab, a);
+        const Step s = tried(ss::launch_mel_c256(m, stream, cfg->num_cus, &info), "launch_mel_c256", info);
+        if (s.done()) return s.rc;
     }
     // fft_points = 1024 / 4096 mel spectrogram: two rows / one row per wave (ss_mel_c512 in ss_mfcc1024.hip, ss_mel_c2048 in
     // ss_mfcc4096.hip), same layout assumptions
     const bool use1024 = cfg->mel1024.ok || (want_stft && cfg->mel1024.stft_only), use4096 = cfg->mel4096.ok || (want_stft && cfg->mel4096.stft_only);
     if (!force_generic && (out_kind == ss::OUT_MEL || want_stft) && (use1024 || use4096) &&
         static_cast<unsigned long long>(a.rows + a.n_pad + 1) * a.hop < 0x7fffffffull) {
-        if ((rc = to_float())) return rc;
-        ss::Mel2048Args m{};
-        m.x = d_x;
-        m.ld = ld;
-        m.n_samples = a.n_samples;
-        m.batch = a.batch;
-        m.hop = a.hop;
-        m.n_pad = a.n_pad;
-        m.rows = a.rows;
-        m.real_rows = a.real_rows;
-        m.scale = a.scale;
-        const bool k1024 = use1024;
-        m.tab = k1024 ? cfg->d_mel1024_tab : cfg->d_mel4096_tab;
-        m.mel_wpitch = k1024 ? cfg->mel1024.wpitch : cfg->mel4096.wpitch;
-        for (int s = 0; s < 4; ++s) m.mel_q4[s] = k1024 ? cfg->mel1024.q4[s] : cfg->mel4096.q4[s];
-        m.fullp = k1024 && cfg->mel1024.fullp;
-        m.n_filters = a.n_filters;
-        m.out = out0;
-        m.out_stft = out_kind == ss::OUT_STFT;
-        const hipError_t e = k1024 ? ss::launch_mel_c512(m, stream, cfg->num_cus, &info) : ss::launch_mel_c2048(m, stream, cfg->num_cus, &info);
-        if (e == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel (LDS budget) -> next candidate
-        if (e != hipErrorInvalidValue) return hip_fail(e, k1024 ? "launch_mel_c512" : "launch_mel_c2048");
+        if ((rc = tmp.need(a))) return rc;
+        const ss::Mel2048Args m = ss::mel2048_args(use1024 ? ss::mel_view(cfg->mel1024, cfg->d_mel1024_tab) : ss::mel_view(cfg->mel4096, cfg->d_mel4096_tab), a);
+        const hipError_t e = use1024 ? ss::launch_mel_c512(m, stream, cfg->num_cus, &info) : ss::launch_mel_c2048(m, stream, cfg->num_cus, &info);
+        const Step s = tried(e, use1024 ? "launch_mel_c512" : "launch_mel_c2048", info);
+        if (s.done()) return s.rc;
     }
     // (pcm: the generic kernel's PCM build, unless a dedicated candidate above already made the float copy and then declined)
-    hipError_t e = pcm && !d_x ? ss::launch_front_generic(a, *pcm, h.d.log2c, stream, cfg->num_cus, &info)
-                               : ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info);
-    if (e != hipSuccess) return hip_fail(e, "launch_front_generic");
-    g_last_kernel = info.kernel_name;
+    return tried(pcm && !a.x ? ss::launch_front_generic(a, *pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                             : ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info),
+                 "launch_front_generic", info, true)
+        .rc;
+}
+
+// The loop of the two *_batches_device calls over their gathered non-empty batches: groups of up to ss::kMaxLaunchBatches go to ONE
+// launch where launch(x, count, out, &group) finds a batch-table build, and batch by batch (launch(x, count, out, nullptr)) where
+// it returns kNoMultiBuild.  too_large: the form's message for a count past 2^31.
+template <typename Launch>
+int launch_batches(size_t n_batches, const float *const *d_x, const size_t *count, float *const *d_out, const char *too_large, Launch launch)
+{
+    std::vector<const float *> xs;
+    std::vector<float *> outs;
+    std::vector<size_t> counts;
+    try {  // (nothing unwinds across the boundary: a failed allocation of the three small tables is an error code)
+        xs.reserve(n_batches);
+        outs.reserve(n_batches);
+        counts.reserve(n_batches);
+    } catch (const std::exception &) {
+        return ss::fail(SS_ERR_ARG, "n_batches too large for this host's memory");
+    }
+    for (size_t b = 0; b < n_batches; ++b) {
+        if (count[b] == 0) continue;  // an empty batch has no buffers
+        if (!d_x[b] || !d_out[b]) return ss::fail(SS_ERR_ARG, "null buffer in batch " + std::to_string(b));
+        if (count[b] > 0x7fffffffull) return ss::fail(SS_ERR_ARG, too_large);
+        xs.push_back(d_x[b]);
+        outs.push_back(d_out[b]);
+        counts.push_back(count[b]);
+    }
+    for (size_t g0 = 0; g0 < xs.size(); g0 += ss::kMaxLaunchBatches) {
+        const size_t gn = std::min<size_t>(ss::kMaxLaunchBatches, xs.size() - g0);
+        int rc = kNoMultiBuild;
+        if (gn > 1) {
+            const MultiBatches mb{static_cast<int>(gn), xs.data() + g0, outs.data() + g0, counts.data() + g0};
+            rc = launch(xs[g0], counts[g0], outs[g0], &mb);
+        }
+        if (rc == kNoMultiBuild) {
+            rc = SS_OK;
+            for (size_t b = g0; b < g0 + gn && rc == SS_OK; ++b) rc = launch(xs[b], counts[b], outs[b], nullptr);
+        }
+        if (rc) return rc;
+    }
     return SS_OK;
 }
 
@@ -847,16 +693,11 @@ int launch_stft_stream(const ss_config *cfg, int out_kind, int mode, const float
     if (!d_x || !d_state || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
     if (ld < n) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
     if (n == 0 || n > 0x7fffffffull || n_streams > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "bad chunk length / stream count");
-    {
-        const int drc = check_device(cfg);  // see launch_frames
-        if (drc) return drc;
-        const int erc = pending_device_error(cfg);
-        if (erc) return erc;
-    }
+    int rc = device_ready(cfg);  // see launch_frames
+    if (rc) return rc;
     const ss::HostTables &h = cfg->host;
     size_t R = 0, Rreal = 0;
-    int rc = ss_stream_rows(&h.params, mode, n, &R, &Rreal);
-    if (rc) return rc;
+    if ((rc = ss_stream_rows(&h.params, mode, n, &R, &Rreal))) return rc;
     const size_t S = h.params.fft_points - h.d.hop;
     const size_t F = h.params.fft_points / 2 + 1;
     const size_t out_floats = n_streams * R * (out_kind == ss::OUT_STFT ? 2 * F : h.params.num_filters);
@@ -867,52 +708,27 @@ int launch_stft_stream(const ss_config *cfg, int out_kind, int mode, const float
     const bool continuous = mode == SS_STREAM_CONTINUOUS;
     const size_t advance = continuous ? n : R * h.d.hop;
     if (advance > 0xffffffffull || R > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "chunk too long");
-    ss::FrontArgs a{};
-    fill_common(cfg, a);
+    ss::FrontArgs a = stft_front_args(cfg, out_kind, out0);
     a.x = d_x;
     a.ld = ld;
     a.n_samples = static_cast<uint32_t>(n);
     a.batch = static_cast<uint32_t>(n_streams);
-    a.hop = h.d.hop;
-    a.n_pad = continuous ? 0u : h.d.n_pad;
+    if (continuous) a.n_pad = 0u;  // every row is real
     a.rows = static_cast<uint32_t>(R);
     a.real_rows = static_cast<uint32_t>(Rreal);
-    a.window = cfg->d_window_stft;
-    a.scale = h.d.wnorm;
-    a.out_kind = out_kind;
-    a.out0 = out0;
     ss::StreamArgs sa{d_state, static_cast<uint32_t>(S)};
     ss::LaunchInfo info{};
-    hipError_t e = hipErrorInvalidValue;
+    Step s{Tried::declined, SS_OK};
     if (!ss::dbg_force_generic() && out_kind == ss::OUT_MEL && cfg->mel2048.ok &&
         static_cast<unsigned long long>(a.rows + a.n_pad + 1) * a.hop < 0x7fffffffull) {
-        ss::Mel2048Args m{};
-        m.x = d_x;
-        m.ld = ld;
-        m.n_samples = a.n_samples;
-        m.batch = a.batch;
-        m.hop = a.hop;
-        m.n_pad = a.n_pad;
-        m.rows = a.rows;
-        m.real_rows = a.real_rows;
-        m.scale = a.scale;
-        m.tab = cfg->d_mel2048_tab;
-        m.fullp = cfg->mel2048.fullp;
-        m.mel_wpitch = cfg->mel2048.wpitch;
-        for (int s = 0; s < 4; ++s) m.mel_q4[s] = cfg->mel2048.q4[s];
-        m.n_filters = a.n_filters;
-        m.out = out0;
+        ss::Mel2048Args m = ss::mel2048_args(ss::mel_view(cfg->mel2048, cfg->d_mel2048_tab), a);
         m.ctl = cfg->d_err;
-        e = ss::launch_mel_c1024_stream(m, sa, stream, cfg->num_cus, &info);
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel -> the generic build
-        if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mel_c1024_stream");
+        // declined: the configuration does not fit this kernel -> the generic build
+        s = tried(ss::launch_mel_c1024_stream(m, sa, stream, cfg->num_cus, &info), "launch_mel_c1024_stream", info);
     }
-    if (e != hipSuccess) {
-        e = ss::launch_front_generic_stream(a, sa, h.d.log2c, stream, cfg->num_cus, &info);
-        if (e != hipSuccess) return hip_fail(e, "launch_front_generic_stream");
-    }
-    g_last_kernel = info.kernel_name;
-    e = ss::launch_stream_advance(d_state, static_cast<uint32_t>(S), d_x, ld, a.n_samples, static_cast<uint32_t>(advance), a.batch, stream);
+    if (!s.done()) s = tried(ss::launch_front_generic_stream(a, sa, h.d.log2c, stream, cfg->num_cus, &info), "launch_front_generic_stream", info, true);
+    if (s.rc) return s.rc;
+    const hipError_t e = ss::launch_stream_advance(d_state, static_cast<uint32_t>(S), d_x, ld, a.n_samples, static_cast<uint32_t>(advance), a.batch, stream);
     if (e != hipSuccess) return hip_fail(e, "launch_stream_advance");
     return SS_OK;
 }
@@ -974,32 +790,12 @@ int stream_host(const ss_config *cfg, int out_kind, int mode, const float *x, si
 // the dense and the ragged (pool) form: the same configuration gives the same block, so the same bits per frame.
 ss::FrontArgs frame_stream_front_args(const ss_config *cfg, int out_kind, const float *d_x, uint32_t norm_frames, float *out0, float *out1)
 {
-    const ss::HostTables &h = cfg->host;
-    ss::FrontArgs a{};
-    fill_common(cfg, a);
+    ss::FrontArgs a = mfcc_front_args(cfg, out_kind, out0, out1);
     a.x = d_x;
-    a.flen = h.d.flen;
-    a.step = h.d.step;
     a.frame_mode = ss::FRAME_NORMAL;  // every row's frame ends inside the chunk: contract and padded framing agree
-    a.pad_reflect = h.params.pad_mode == SS_PAD_REFLECT;
-    a.preemph = h.params.preemph_coef;
-    a.preemph_shift = static_cast<uint32_t>(h.params.preemph_shift > 0 ? h.params.preemph_shift : 1);
-    a.window = cfg->d_window_mfcc;
-    a.scale = 1.0f / static_cast<float>(h.params.fft_points);  // processing.rs:180
     // the scales of launch_frames with T = norm_frames; a stream has no first frame, so [0,0] gets column 0's scale
-    const float g = h.params.dct2_gain;
-    const float M = static_cast<float>(h.params.num_filters);
-    if (h.params.dct_norm == SS_DCT_ORTHO) {
-        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * M));
-        a.dct_scale_0 = a.dct_scale_00 = g * (1.0f / sqrtf(4.0f * M));
-    } else {
-        const float nn = static_cast<float>(static_cast<size_t>(norm_frames > 0 ? norm_frames : 1u) * h.params.num_filters);
-        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * nn));
-        a.dct_scale_0 = a.dct_scale_00 = g;
-    }
-    a.out_kind = out_kind;
-    a.out0 = out0;
-    a.out1 = out1;
+    set_dct_scales(a, ss::dct_scales(cfg->host.params, norm_frames > 0 ? norm_frames : 1u));
+    a.dct_scale_00 = a.dct_scale_0;
     return a;
 }
 // whether the streaming builds of the 512-point headline kernel are candidates for the configuration (their launchers decide)
@@ -1008,33 +804,24 @@ bool frame_stream_fast_candidate(const ss_config *cfg, const ss::FrontArgs &a)
     return !ss::dbg_force_generic() && cfg->fast.ok && !cfg->fast.fullp && a.window == nullptr && a.preemph == 0.0f &&
            cfg->host.params.dct_norm != SS_DCT_ORTHO;
 }
-// ... and their argument block, from the generic one
-ss::Fast512Args frame_stream_fast_args(const ss_config *cfg, const ss::FrontArgs &a)
+// The entry tables of a ragged streaming launch over a pool of stream states (either path: lead is the MFCC path's flen - step and
+// unused on the STFT path, step the path's hop)
+ss::FrameStreamPackedArgs stream_packed_args(const ss_config *cfg, size_t S, int32_t lead, uint32_t step, const int64_t *d_so, const int64_t *d_ro,
+                                             const int32_t *d_slots, size_t n_active, size_t pool_streams, size_t total_rows, float *d_pool)
 {
-    ss::Fast512Args f{};
-    f.x = a.x;
-    f.ld = a.ld;
-    f.n_samples = a.n_samples;
-    f.batch = a.batch;
-    f.flen = a.flen;
-    f.step = a.step;
-    f.n_frames = a.n_frames;
-    f.scale = a.scale;
-    f.spectrum_exponent = a.spectrum_exponent;
-    f.tab = cfg->d_fast_tab;
-    f.mel_wpitch = cfg->fast.wpitch;
-    for (int s = 0; s < 3; ++s) f.mel_q4[s] = cfg->fast.q4[s];
-    f.n_filters = a.n_filters;
-    f.n_ceps = a.n_ceps;
-    f.dct_scale_k = a.dct_scale_k;
-    f.dct_scale_0 = a.dct_scale_0;
-    f.dct_scale_00 = a.dct_scale_00;
-    f.dc_elimination = a.dc_elimination;
-    f.out = a.out0;
-    f.out_energy = a.out1;
-    f.out_mfe = a.out_kind == ss::OUT_MFE ? 1 : 0;
-    f.paired = cfg->fast.paired ? (cfg->fast.tight ? 2 : 1) : 0;
-    return f;
+    ss::FrameStreamPackedArgs e{};
+    e.pool = d_pool;
+    e.state_len = static_cast<uint32_t>(S);
+    e.lead = lead;
+    e.so = reinterpret_cast<const long long *>(d_so);
+    e.ro = reinterpret_cast<const long long *>(d_ro);
+    e.slots = d_slots;
+    e.n_active = static_cast<uint32_t>(n_active);
+    e.pool_streams = static_cast<uint32_t>(pool_streams);
+    e.total_rows = static_cast<uint32_t>(total_rows);
+    e.step = step;
+    e.err = cfg->d_err;
+    return e;
 }
 
 // Streaming MFCC / mfe launch (ss_mfcc_stream_device / ss_mfe_stream_device): the rows of one call over a carried state per
@@ -1063,12 +850,7 @@ int launch_frame_stream(const ss_config *cfg, int out_kind, const float *d_x, si
                   ranges_overlap(d_state, sbytes, out0, n_streams * R * cols * sizeof(float)) ||
                   (out1 && ranges_overlap(d_state, sbytes, out1, n_streams * R * sizeof(float)))))
         return ss::fail(SS_ERR_ARG, "the state buffer overlaps the input or an output");
-    {
-        const int drc = check_device(cfg);  // see launch_frames
-        if (drc) return drc;
-        const int erc = pending_device_error(cfg);
-        if (erc) return erc;
-    }
+    if ((rc = device_ready(cfg))) return rc;  // see launch_frames
     ss::FrontArgs a = frame_stream_front_args(cfg, out_kind, d_x, norm_frames, out0, out1);
     a.ld = ld;
     a.n_samples = static_cast<uint32_t>(n);
@@ -1076,19 +858,16 @@ int launch_frame_stream(const ss_config *cfg, int out_kind, const float *d_x, si
     a.n_frames = static_cast<uint32_t>(R);
     ss::FrameStreamArgs fsa{d_state, static_cast<uint32_t>(S), static_cast<int32_t>(h.d.flen) - static_cast<int32_t>(h.d.step)};
     ss::LaunchInfo info{};
-    hipError_t e = hipErrorInvalidValue;
+    Step s{Tried::declined, SS_OK};
     if (frame_stream_fast_candidate(cfg, a)) {
-        const ss::Fast512Args f = frame_stream_fast_args(cfg, a);
-        e = ss::launch_mfcc_c256_stream(f, fsa, stream, cfg->num_cus, &info);
-        // hipErrorInvalidValue before the launch: the configuration has no streaming build of this kernel -> the generic build
-        if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mfcc_c256_stream");
+        const ss::Fast512Args f = ss::fast512_args(cfg->fast, cfg->d_fast_tab, a);
+        // declined: the configuration has no streaming build of this kernel -> the generic build
+        s = tried(ss::launch_mfcc_c256_stream(f, fsa, stream, cfg->num_cus, &info), "launch_mfcc_c256_stream", info);
     }
-    if (e != hipSuccess) {
-        e = ss::launch_front_generic_frame_stream(a, fsa, h.d.log2c, stream, cfg->num_cus, &info);
-        if (e != hipSuccess) return hip_fail(e, "launch_front_generic_frame_stream");
-    }
-    g_last_kernel = info.kernel_name;
-    e = ss::launch_stream_advance(d_state, static_cast<uint32_t>(S), d_x, ld, a.n_samples, a.n_samples, a.batch, stream);
+    if (!s.done())
+        s = tried(ss::launch_front_generic_frame_stream(a, fsa, h.d.log2c, stream, cfg->num_cus, &info), "launch_front_generic_frame_stream", info, true);
+    if (s.rc) return s.rc;
+    const hipError_t e = ss::launch_stream_advance(d_state, static_cast<uint32_t>(S), d_x, ld, a.n_samples, a.n_samples, a.batch, stream);
     if (e != hipSuccess) return hip_fail(e, "launch_stream_advance");
     return SS_OK;
 }
@@ -1178,42 +957,26 @@ int launch_frame_stream_packed(const ss_config *cfg, int out_kind, const PoolChu
     if (S > 0 && (ranges_overlap(d_pool, pbytes, out0, total_rows * cols * sizeof(float)) ||
                   (out1 && ranges_overlap(d_pool, pbytes, out1, total_rows * sizeof(float)))))
         return ss::fail(SS_ERR_ARG, "the pool overlaps an output");
-    {
-        const int drc = check_device(cfg);  // see launch_frames
-        if (drc) return drc;
-        const int erc = pending_device_error(cfg);
-        if (erc) return erc;
-    }
+    if ((rc = device_ready(cfg))) return rc;  // see launch_frames
     const ss::FrontArgs a = frame_stream_front_args(cfg, out_kind, x.f, norm_frames, out0, out1);
-    ss::FrameStreamPackedArgs fsp{};
-    fsp.pool = d_pool;
-    fsp.state_len = static_cast<uint32_t>(S);
-    fsp.lead = static_cast<int32_t>(h.d.flen) - static_cast<int32_t>(h.d.step);
-    fsp.so = reinterpret_cast<const long long *>(d_so);
-    fsp.ro = reinterpret_cast<const long long *>(d_ro);
-    fsp.slots = d_slots;
-    fsp.n_active = static_cast<uint32_t>(n_active);
-    fsp.pool_streams = static_cast<uint32_t>(pool_streams);
-    fsp.total_rows = static_cast<uint32_t>(total_rows);
-    fsp.step = h.d.step;
-    fsp.err = cfg->d_err;
+    const ss::FrameStreamPackedArgs fsp = stream_packed_args(cfg, S, static_cast<int32_t>(h.d.flen) - static_cast<int32_t>(h.d.step), h.d.step, d_so,
+                                                             d_ro, d_slots, n_active, pool_streams, total_rows, d_pool);
     const ss::FrameStreamPackedPcmArgs pcm{fsp, x.pcm, x.scale};
     ss::LaunchInfo info{};
-    hipError_t e = hipErrorInvalidValue;
+    Step s{Tried::declined, SS_OK};
     if (frame_stream_fast_candidate(cfg, a)) {
-        const ss::Fast512Args f = frame_stream_fast_args(cfg, a);
-        e = x.is_pcm ? ss::launch_mfcc_c256_stream_packed(f, pcm, stream, cfg->num_cus, &info)
-                     : ss::launch_mfcc_c256_stream_packed(f, fsp, stream, cfg->num_cus, &info);
-        // hipErrorInvalidValue before the launch: the configuration has no ragged streaming build of this kernel -> the generic build
-        if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mfcc_c256_stream_packed");
+        const ss::Fast512Args f = ss::fast512_args(cfg->fast, cfg->d_fast_tab, a);
+        // declined: the configuration has no ragged streaming build of this kernel -> the generic build
+        s = tried(x.is_pcm ? ss::launch_mfcc_c256_stream_packed(f, pcm, stream, cfg->num_cus, &info)
+                           : ss::launch_mfcc_c256_stream_packed(f, fsp, stream, cfg->num_cus, &info),
+                  "launch_mfcc_c256_stream_packed", info);
     }
-    if (e != hipSuccess) {
-        e = x.is_pcm ? ss::launch_front_generic_frame_stream_packed(a, pcm, h.d.log2c, stream, cfg->num_cus, &info)
-                     : ss::launch_front_generic_frame_stream_packed(a, fsp, h.d.log2c, stream, cfg->num_cus, &info);
-        if (e != hipSuccess) return hip_fail(e, "launch_front_generic_frame_stream_packed");
-    }
-    g_last_kernel = info.kernel_name;
-    e = x.is_pcm ? ss::launch_stream_advance_packed(pcm, stream) : ss::launch_stream_advance_packed(fsp, x.f, stream);
+    if (!s.done())
+        s = tried(x.is_pcm ? ss::launch_front_generic_frame_stream_packed(a, pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                           : ss::launch_front_generic_frame_stream_packed(a, fsp, h.d.log2c, stream, cfg->num_cus, &info),
+                  "launch_front_generic_frame_stream_packed", info, true);
+    if (s.rc) return s.rc;
+    const hipError_t e = x.is_pcm ? ss::launch_stream_advance_packed(pcm, stream) : ss::launch_stream_advance_packed(fsp, x.f, stream);
     if (e != hipSuccess) return hip_fail(e, "launch_stream_advance_packed");
     return SS_OK;
 }
@@ -1336,60 +1099,30 @@ int launch_stft_stream_packed(const ss_config *cfg, int out_kind, const PoolChun
     // (how far x reaches is in the device tables: its first sample stands for it here, the host form checks the whole range)
     if (ranges_overlap(d_pool, pbytes, out0, out_floats * sizeof(float)) || ranges_overlap(d_pool, pbytes, x.ptr(), x.sample_bytes()))
         return ss::fail(SS_ERR_ARG, "the pool overlaps the input or the output");
-    {
-        const int drc = check_device(cfg);  // see launch_frames
-        if (drc) return drc;
-        const int erc = pending_device_error(cfg);
-        if (erc) return erc;
-    }
-    ss::FrontArgs a{};
-    fill_common(cfg, a);
+    const int drc = device_ready(cfg);  // see launch_frames
+    if (drc) return drc;
+    ss::FrontArgs a = stft_front_args(cfg, out_kind, out0);
     a.x = d_x;
-    a.hop = h.d.hop;
     a.n_pad = 0u;  // continuous mode: every row is real
-    a.window = cfg->d_window_stft;
-    a.scale = h.d.wnorm;
-    a.out_kind = out_kind;
-    a.out0 = out0;
-    ss::StftStreamPackedArgs sp{};
-    sp.e.pool = d_pool;
-    sp.e.state_len = static_cast<uint32_t>(S);
-    sp.e.so = reinterpret_cast<const long long *>(d_so);
-    sp.e.ro = reinterpret_cast<const long long *>(d_ro);
-    sp.e.slots = d_slots;
-    sp.e.n_active = static_cast<uint32_t>(n_active);
-    sp.e.pool_streams = static_cast<uint32_t>(pool_streams);
-    sp.e.total_rows = static_cast<uint32_t>(total_rows);
-    sp.e.step = h.d.hop;
-    sp.e.err = cfg->d_err;
+    const ss::StftStreamPackedArgs sp{stream_packed_args(cfg, S, 0, h.d.hop, d_so, d_ro, d_slots, n_active, pool_streams, total_rows, d_pool)};
     const ss::BatchPcmArgs pcm{x.pcm, x.scale};
     ss::LaunchInfo info{};
-    hipError_t e = hipErrorInvalidValue;
+    Step s{Tried::declined, SS_OK};
     if (!ss::dbg_force_generic() && out_kind == ss::OUT_MEL && cfg->mel2048.ok) {
-        ss::Mel2048Args m{};
-        m.x = d_x;
-        m.hop = a.hop;
-        m.scale = a.scale;
-        m.tab = cfg->d_mel2048_tab;
-        m.fullp = cfg->mel2048.fullp;
-        m.mel_wpitch = cfg->mel2048.wpitch;
-        for (int s = 0; s < 4; ++s) m.mel_q4[s] = cfg->mel2048.q4[s];
-        m.n_filters = a.n_filters;
-        m.out = out0;
+        ss::Mel2048Args m = ss::mel2048_args(ss::mel_view(cfg->mel2048, cfg->d_mel2048_tab), a);
         m.ctl = cfg->d_err;
-        e = x.is_pcm ? ss::launch_mel_c1024_stream_packed(m, sp, pcm, stream, cfg->num_cus, &info)
-                     : ss::launch_mel_c1024_stream_packed(m, sp, stream, cfg->num_cus, &info);
-        // hipErrorInvalidValue before the launch: the configuration does not fit this kernel -> the generic build
-        if (e != hipSuccess && e != hipErrorInvalidValue) return hip_fail(e, "launch_mel_c1024_stream_packed");
+        // declined: the configuration does not fit this kernel -> the generic build
+        s = tried(x.is_pcm ? ss::launch_mel_c1024_stream_packed(m, sp, pcm, stream, cfg->num_cus, &info)
+                           : ss::launch_mel_c1024_stream_packed(m, sp, stream, cfg->num_cus, &info),
+                  "launch_mel_c1024_stream_packed", info);
     }
-    if (e != hipSuccess) {
-        e = x.is_pcm ? ss::launch_front_generic_stream_packed(a, sp, pcm, h.d.log2c, stream, cfg->num_cus, &info)
-                     : ss::launch_front_generic_stream_packed(a, sp, h.d.log2c, stream, cfg->num_cus, &info);
-        if (e != hipSuccess) return hip_fail(e, "launch_front_generic_stream_packed");
-    }
-    g_last_kernel = info.kernel_name;
-    e = x.is_pcm ? ss::launch_stream_advance_packed(ss::FrameStreamPackedPcmArgs{sp.e, x.pcm, x.scale}, stream)
-                 : ss::launch_stream_advance_packed(sp.e, d_x, stream);
+    if (!s.done())
+        s = tried(x.is_pcm ? ss::launch_front_generic_stream_packed(a, sp, pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                           : ss::launch_front_generic_stream_packed(a, sp, h.d.log2c, stream, cfg->num_cus, &info),
+                  "launch_front_generic_stream_packed", info, true);
+    if (s.rc) return s.rc;
+    const hipError_t e = x.is_pcm ? ss::launch_stream_advance_packed(ss::FrameStreamPackedPcmArgs{sp.e, x.pcm, x.scale}, stream)
+                                  : ss::launch_stream_advance_packed(sp.e, d_x, stream);
     if (e != hipSuccess) return hip_fail(e, "launch_stream_advance_packed");
     return SS_OK;
 }
@@ -1689,38 +1422,16 @@ int launch_packed(const ss_config *cfg, int out_kind, const PoolChunks &x, size_
     const float *d_x = x.f;
     if (!x.ptr() || !d_so || !d_fo || !out0 || (out_kind == ss::OUT_MFE && !out1)) return ss::fail(SS_ERR_ARG, "null buffer");
     if (n_clips > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many clips");
-    {
-        const int drc = check_device(cfg);  // see launch_frames
-        if (drc) return drc;
-        const int erc = pending_device_error(cfg);
-        if (erc) return erc;
-    }
+    const int drc = device_ready(cfg);  // see launch_frames
+    if (drc) return drc;
     const ss::HostTables &h = cfg->host;
-    ss::FrontArgs a{};
-    fill_common(cfg, a);
+    ss::FrontArgs a = mfcc_front_args(cfg, out_kind, out0, out1);
     a.x = d_x;
-    a.flen = h.d.flen;
-    a.step = h.d.step;
     // literal framing: the kernel picks FRAME_ZERO / FRAME_FIRST from each clip's frame count
     if (h.params.framing == SS_FRAMING_CENTER) a.frame_mode = ss::FRAME_CENTER;
     else if (h.params.framing == SS_FRAMING_PADDED) a.frame_mode = ss::FRAME_PADDED;
     else a.frame_mode = ss::FRAME_NORMAL;
-    a.pad_reflect = h.params.pad_mode == SS_PAD_REFLECT;
-    a.preemph = h.params.preemph_coef;
-    a.preemph_shift = static_cast<uint32_t>(h.params.preemph_shift > 0 ? h.params.preemph_shift : 1);
-    a.window = cfg->d_window_mfcc;
-    a.scale = 1.0f / static_cast<float>(h.params.fft_points);  // processing.rs:180
-    const float g = h.params.dct2_gain;
-    const float M = static_cast<float>(h.params.num_filters);
-    if (h.params.dct_norm == SS_DCT_ORTHO) {  // as launch_frames; the reference scaling is formed per clip on the device
-        a.dct_scale_k = g * (1.0f / sqrtf(2.0f * M));
-        a.dct_scale_0 = a.dct_scale_00 = g * (1.0f / sqrtf(4.0f * M));
-    } else {
-        a.dct_scale_0 = g;
-    }
-    a.out_kind = out_kind;
-    a.out0 = out0;
-    a.out1 = out1;
+    set_dct_scales(a, ss::dct_scales_per_clip(h.params));  // as launch_frames; the reference scaling is formed per clip on the device
     ss::VarlenArgs v{};
     v.so = reinterpret_cast<const long long *>(d_so);
     v.fo = reinterpret_cast<const long long *>(d_fo);
@@ -1729,49 +1440,23 @@ int launch_packed(const ss_config *cfg, int out_kind, const PoolChunks &x, size_
     v.framing = h.params.framing;
     v.pad_reflect = a.pad_reflect;
     v.dct_ortho = h.params.dct_norm == SS_DCT_ORTHO;
-    v.dct2_gain = g;
+    v.dct2_gain = h.params.dct2_gain;
     v.err = cfg->d_err;
     const ss::VarlenPcmArgs vp{v, x.pcm, x.scale};
     ss::LaunchInfo info{};
     // the headline shape (512-point MFCC, default frame shape and bank): the varlen build of the dedicated kernel -- the same bits as
     // ss_mfcc_batch_device per clip; hipErrorInvalidValue before the launch for every other configuration
     if (cfg->fast.ok && !cfg->fast.fullp && out_kind == ss::OUT_MFCC && !ss::dbg_force_generic()) {
-        ss::Fast512Args f{};
-        f.x = d_x;
-        f.flen = a.flen;
-        f.step = a.step;
-        f.scale = a.scale;
-        f.spectrum_exponent = a.spectrum_exponent;
-        f.tab = cfg->d_fast_tab;
-        f.mel_wpitch = cfg->fast.wpitch;
-        for (int s = 0; s < 3; ++s) f.mel_q4[s] = cfg->fast.q4[s];
-        f.n_filters = a.n_filters;
-        f.n_ceps = a.n_ceps;
-        f.dct_scale_k = a.dct_scale_k;
-        f.dct_scale_0 = a.dct_scale_0;
-        f.dct_scale_00 = a.dct_scale_00;
-        f.dc_elimination = a.dc_elimination;
-        f.out = out0;
-        f.win_floats = a.window ? cfg->fast.win_floats : 0;
-        f.preemph = a.preemph;
-        f.preemph_shift = a.preemph_shift;
-        f.center = a.frame_mode == ss::FRAME_CENTER;
-        f.pad_reflect = a.pad_reflect;
-        f.fullp = cfg->fast.fullp;
-        f.paired = cfg->fast.paired ? (cfg->fast.tight ? 2 : 1) : 0;
-        const hipError_t ef = x.is_pcm ? ss::launch_mfcc_c256_varlen(f, vp, stream, cfg->num_cus, &info)
-                                       : ss::launch_mfcc_c256_varlen(f, v, stream, cfg->num_cus, &info);
-        if (ef == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
-        if (ef != hipErrorInvalidValue) return hip_fail(ef, "launch_mfcc_c256_varlen");
+        const ss::Fast512Args f = ss::fast512_args(cfg->fast, cfg->d_fast_tab, a);
+        const Step s = tried(x.is_pcm ? ss::launch_mfcc_c256_varlen(f, vp, stream, cfg->num_cus, &info)
+                                      : ss::launch_mfcc_c256_varlen(f, v, stream, cfg->num_cus, &info),
+                             "launch_mfcc_c256_varlen", info);
+        if (s.done()) return s.rc;
     }
-    const hipError_t e = x.is_pcm ? ss::launch_front_generic_varlen(a, vp, h.d.log2c, stream, cfg->num_cus, &info)
-                                  : ss::launch_front_generic_varlen(a, v, h.d.log2c, stream, cfg->num_cus, &info);
-    if (e != hipSuccess) return hip_fail(e, "launch_front_generic_varlen");
-    g_last_kernel = info.kernel_name;
-    return SS_OK;
+    return tried(x.is_pcm ? ss::launch_front_generic_varlen(a, vp, h.d.log2c, stream, cfg->num_cus, &info)
+                          : ss::launch_front_generic_varlen(a, v, h.d.log2c, stream, cfg->num_cus, &info),
+                 "launch_front_generic_varlen", info, true)
+        .rc;
 }
 
 // Host-pointer form: the frame offsets from the host's sample offsets, one upload, one launch, one download on the config's
@@ -1846,21 +1531,10 @@ int launch_packed_stft(const ss_config *cfg, int out_kind, const PoolChunks &x, 
     const float *d_x = x.f;
     if (!x.ptr() || !d_so || !d_ro || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
     if (n_clips > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "too many clips");
-    {
-        const int drc = check_device(cfg);  // see launch_frames
-        if (drc) return drc;
-        const int erc = pending_device_error(cfg);
-        if (erc) return erc;
-    }
-    ss::FrontArgs a{};
-    fill_common(cfg, a);
+    const int drc = device_ready(cfg);  // see launch_frames
+    if (drc) return drc;
+    ss::FrontArgs a = stft_front_args(cfg, out_kind, out0);
     a.x = d_x;
-    a.hop = h.d.hop;
-    a.n_pad = h.d.n_pad;
-    a.window = cfg->d_window_stft;
-    a.scale = h.d.wnorm;
-    a.out_kind = out_kind;
-    a.out0 = out0;
     ss::VarRowsArgs v{};
     v.so = reinterpret_cast<const long long *>(d_so);
     v.ro = reinterpret_cast<const long long *>(d_ro);
@@ -1873,31 +1547,17 @@ int launch_packed_stft(const ss_config *cfg, int out_kind, const PoolChunks &x, 
     // the 2048-point mel shape (bank within bins 0..512): the packed build of the twelve-wave kernel -- per clip the bits of
     // ss_mel_spectrogram_device's twelve-wave build; hipErrorInvalidValue before the launch for every other configuration
     if (!ss::dbg_force_generic() && out_kind == ss::OUT_MEL && cfg->mel2048.ok && !cfg->mel2048.fullp) {
-        ss::Mel2048Args m{};
-        m.x = d_x;
-        m.hop = a.hop;
-        m.n_pad = a.n_pad;
-        m.scale = a.scale;
-        m.tab = cfg->d_mel2048_tab;
-        m.fullp = cfg->mel2048.fullp;
-        m.mel_wpitch = cfg->mel2048.wpitch;
-        for (int s = 0; s < 4; ++s) m.mel_q4[s] = cfg->mel2048.q4[s];
-        m.n_filters = a.n_filters;
-        m.out = out0;
+        ss::Mel2048Args m = ss::mel2048_args(ss::mel_view(cfg->mel2048, cfg->d_mel2048_tab), a);
         m.ctl = cfg->d_err;
-        const hipError_t em = x.is_pcm ? ss::launch_mel_c1024_varlen(m, v, pcm, stream, cfg->num_cus, &info)
-                                       : ss::launch_mel_c1024_varlen(m, v, stream, cfg->num_cus, &info);
-        if (em == hipSuccess) {
-            g_last_kernel = info.kernel_name;
-            return SS_OK;
-        }
-        if (em != hipErrorInvalidValue) return hip_fail(em, "launch_mel_c1024_varlen");
+        const Step s = tried(x.is_pcm ? ss::launch_mel_c1024_varlen(m, v, pcm, stream, cfg->num_cus, &info)
+                                      : ss::launch_mel_c1024_varlen(m, v, stream, cfg->num_cus, &info),
+                             "launch_mel_c1024_varlen", info);
+        if (s.done()) return s.rc;
     }
-    const hipError_t e = x.is_pcm ? ss::launch_front_generic_varrows(a, v, pcm, h.d.log2c, stream, cfg->num_cus, &info)
-                                  : ss::launch_front_generic_varrows(a, v, h.d.log2c, stream, cfg->num_cus, &info);
-    if (e != hipSuccess) return hip_fail(e, "launch_front_generic_varrows");
-    g_last_kernel = info.kernel_name;
-    return SS_OK;
+    return tried(x.is_pcm ? ss::launch_front_generic_varrows(a, v, pcm, h.d.log2c, stream, cfg->num_cus, &info)
+                          : ss::launch_front_generic_varrows(a, v, h.d.log2c, stream, cfg->num_cus, &info),
+                 "launch_front_generic_varrows", info, true)
+        .rc;
 }
 
 // Host-pointer form: the row offsets from the host's sample offsets, one upload, one launch, one download on the config's first
@@ -2135,40 +1795,10 @@ int ss_mfcc_batches_device(const ss_config *cfg, size_t n_batches, const float *
         const int rc = ss::num_frames(cfg->host.params, n_samples, T);
         if (rc) return rc;
     }
-    std::vector<const float *> xs;
-    std::vector<float *> outs;
-    std::vector<size_t> clips;
-    try {  // (nothing unwinds across the boundary: a failed allocation of the three small tables is an error code)
-        xs.reserve(n_batches);
-        outs.reserve(n_batches);
-        clips.reserve(n_batches);
-    } catch (const std::exception &) {
-        return ss::fail(SS_ERR_ARG, "n_batches too large for this host's memory");
-    }
-    for (size_t b = 0; b < n_batches; ++b) {
-        if (batch[b] == 0) continue;  // an empty batch has no buffers
-        if (!d_x[b] || !d_out[b]) return ss::fail(SS_ERR_ARG, "null buffer in batch " + std::to_string(b));
-        if (batch[b] > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "batch too large");
-        xs.push_back(d_x[b]);
-        outs.push_back(d_out[b]);
-        clips.push_back(batch[b]);
-    }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (size_t g0 = 0; g0 < xs.size(); g0 += ss::kMaxLaunchBatches) {
-        const size_t gn = std::min<size_t>(ss::kMaxLaunchBatches, xs.size() - g0);
-        int rc = kNoMultiBuild;
-        if (gn > 1) {
-            const MultiBatches mb{static_cast<int>(gn), xs.data() + g0, outs.data() + g0, clips.data() + g0};
-            rc = launch_frames(cfg, ss::OUT_MFCC, xs[g0], clips[g0], n_samples, ld, outs[g0], nullptr, st, false, &mb);
-        }
-        if (rc == kNoMultiBuild) {
-            rc = SS_OK;
-            for (size_t b = g0; b < g0 + gn && rc == SS_OK; ++b)
-                rc = launch_frames(cfg, ss::OUT_MFCC, xs[b], clips[b], n_samples, ld, outs[b], nullptr, st);
-        }
-        if (rc) return rc;
-    }
-    return SS_OK;
+    return launch_batches(n_batches, d_x, batch, d_out, "batch too large", [&](const float *x, size_t clips, float *out, const MultiBatches *mb) {
+        return launch_frames(cfg, ss::OUT_MFCC, x, clips, n_samples, ld, out, nullptr, st, false, mb);
+    });
 }
 
 int ss_mfe_batch_device(const ss_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld,
@@ -2747,39 +2377,11 @@ int ss_mel_spectrogram_batches_device(const ss_config *cfg, size_t n_batches, co
     if (n_batches == 0) return SS_OK;
     if (!d_x || !channels || !d_out) return ss::fail(SS_ERR_ARG, "null batch table");
     if (ld < n_samples) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
-    std::vector<const float *> xs;
-    std::vector<float *> outs;
-    std::vector<size_t> chans;
-    try {
-        xs.reserve(n_batches);
-        outs.reserve(n_batches);
-        chans.reserve(n_batches);
-    } catch (const std::exception &) {
-        return ss::fail(SS_ERR_ARG, "n_batches too large for this host's memory");
-    }
-    for (size_t b = 0; b < n_batches; ++b) {
-        if (channels[b] == 0) continue;  // an empty block has no buffers
-        if (!d_x[b] || !d_out[b]) return ss::fail(SS_ERR_ARG, "null buffer in batch " + std::to_string(b));
-        if (channels[b] > 0x7fffffffull) return ss::fail(SS_ERR_ARG, "bad clip length / channel count");
-        xs.push_back(d_x[b]);
-        outs.push_back(d_out[b]);
-        chans.push_back(channels[b]);
-    }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (size_t g0 = 0; g0 < xs.size(); g0 += ss::kMaxLaunchBatches) {
-        const size_t gn = std::min<size_t>(ss::kMaxLaunchBatches, xs.size() - g0);
-        int rc = kNoMultiBuild;
-        if (gn > 1) {
-            const MultiBatches mb{static_cast<int>(gn), xs.data() + g0, outs.data() + g0, chans.data() + g0};
-            rc = launch_stft(cfg, ss::OUT_MEL, xs[g0], chans[g0], n_samples, ld, outs[g0], st, &mb);
-        }
-        if (rc == kNoMultiBuild) {
-            rc = SS_OK;
-            for (size_t b = g0; b < g0 + gn && rc == SS_OK; ++b) rc = launch_stft(cfg, ss::OUT_MEL, xs[b], chans[b], n_samples, ld, outs[b], st);
-        }
-        if (rc) return rc;
-    }
-    return SS_OK;
+    return launch_batches(n_batches, d_x, channels, d_out, "bad clip length / channel count",
+                          [&](const float *x, size_t chans, float *out, const MultiBatches *mb) {
+                              return launch_stft(cfg, ss::OUT_MEL, x, chans, n_samples, ld, out, st, mb);
+                          });
 }
 
 int ss_stft_device(const ss_config *cfg, const float *d_x, size_t channels, size_t n_samples, size_t ld,
