@@ -9,6 +9,10 @@ frames (tools/parity_report.py builds them; the same code writes profiles/r02/pa
     oracle's f32 port of the reference's own operation order misses the f64 oracle by 6.8e-4 on cfg1.  The HIP path has to
     stay within 1e-4 or within 1.5x of that port's error (worst case over the signal classes), whichever is larger --
     i.e. it may not be worse than the reference's own arithmetic -- and every case under an absolute cap of 2e-3.
+
+These are three builds through the single-clip call.  tests/test_gpu_parity_families.py holds every kernel family behind the
+dispatcher to the same kind of bar through the batch calls -- every cepstral column and every mel band against its own
+maximum (col_norm, band_norm) -- together with the bit-exact batch invariants.
 """
 import os
 import sys

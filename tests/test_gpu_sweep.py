@@ -1,6 +1,12 @@
 """Seeded sweep over the configuration space: every case goes through the public Python front (hence through whichever
 kernel build the dispatcher picks: the builds of the 512-point kernel, the wide-bank one, the 256-, 1024-, 2048- and
-4096-point kernels, the mel-spectrogram kernels, the generic kernel) and is compared with the oracle."""
+4096-point kernels, the mel-spectrogram kernels, the generic kernel) and is compared with the oracle.
+
+The metric here is the block metric, max|got - want| / max|want| over the whole block, on white noise: it finds a wrong
+kernel, table or dispatch for any shape, but on MFCC it is dominated by column 0 (ln of the frame energy) and on mel outputs
+by the loudest band.  The strict bars -- column 0 and the cepstra apart, every cepstral column and every mel band against its
+own maximum -- live in tests/test_gpu_parity_strict.py (the three BASELINE configurations) and
+tests/test_gpu_parity_families.py (one configuration per kernel family)."""
 import numpy as np
 import pytest
 
