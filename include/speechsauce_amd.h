@@ -352,6 +352,50 @@ int ss_stft_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n
 int ss_mel_spectrogram_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out);
 int ss_stft_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out);
 
+/* ---- log-mel spectrogram: ss_mel_spectrogram* with librosa's power_to_db per clip, converted in the mel kernels' epilogue ----
+ * Eight entry points, each its mel counterpart with `float ref, float amin, float top_db` in front of the output pointer.  Shapes,
+ * layouts ([channels x num_filters x rows]; packed: clip b's [num_filters x R_b] block at out + num_filters * ro[b]), errors and edge
+ * cases are the mel calls' own: channels == 0 / n_clips == 0 is SS_OK with nothing launched, the packed tables' containment and the
+ * SS_ERR_DEVICE reporting are unchanged, pcm scale as in the _i16 mel forms.  amin must be > 0 and ref must not be NaN, else
+ * SS_ERR_ARG before anything runs (|ref| is used, as in ss_power_to_db).
+ *   Contract: per clip (channel), every output is bit for bit what the two-step path returns -- the mel call on the same input, then
+ *   ss_power_to_db_packed_device over its result with every clip as its own segment (cols = num_filters, offsets = the row offsets)
+ *   and the same ref / amin / top_db.  Element: fmaf(10, log10f(fmaxf(amin, S)), -ref_db), ref_db = 10 log10(max(amin, |ref|)) formed
+ *   on the host.
+ *   top_db: the floor is PER CLIP -- max(that clip's dB values) - top_db; top_db < 0 switches it off.  The trailing n_pad zero rows
+ *   (functions.rs:121) come out as 10 log10(amin) - ref_db and take part in the maximum, as in the two-step path.  This is NOT what
+ *   ss_power_to_db_device does on a multi-channel block: that call takes ONE maximum over the whole block.
+ *   Launches: the twelve-wave 2048-point mel kernel (dense where the mel call's own rule picks it, packed always) and the generic
+ *   kernel (every fft_points, chirp-z included; dense and packed) have dB builds, float and PCM: the conversion costs no launch and no
+ *   pass over the block.  top_db < 0: ONE launch, nothing allocated.  Otherwise the launch, then one floor pass; the per-clip maxima
+ *   are a stream-ordered block of n_clips ints, set up by one small launch in front (a kernel, so that a captured call holds no
+ *   memset node).  The floor pass leaves alone every clip the packed table check skipped.  Where the mel
+ *   call runs a kernel without a dB build -- the eight-wave 2048-point builds, the dedicated 512 / 1024 / 4096-point mel kernels --
+ *   that kernel runs as in the mel call and one in-place pass converts the block: same bits, one launch more.
+ *   ss_last_kernel_name(): a dB build carries `db` in its template list (ss_mel_c1024v<w12,mel6321,db>, ss_front_generic_varrows<9,db>);
+ *   the composed path reports the mel kernel's name followed by "+db" (ss_mel_c256+db).
+ *   Kernel selection of every other call is untouched.  The device forms are linear chains on `stream` and capture like the mel
+ *   calls (the PCM conversion fallback of the dense _i16 form excepted, as there).  No streaming / pool forms: a stream has no clip
+ *   maximum. */
+int ss_log_mel_spectrogram(const ss_config *cfg, const float *x, size_t channels, size_t n_samples, float ref, float amin, float top_db,
+                           float *out);
+int ss_log_mel_spectrogram_device(const ss_config *cfg, const float *d_x, size_t channels, size_t n_samples, size_t ld, float ref, float amin,
+                                  float top_db, float *d_out, void *stream);
+int ss_log_mel_spectrogram_i16(const ss_config *cfg, const int16_t *x, size_t channels, size_t n_samples, float scale, float ref, float amin,
+                               float top_db, float *out);
+int ss_log_mel_spectrogram_i16_device(const ss_config *cfg, const int16_t *d_x, size_t channels, size_t n_samples, size_t ld, float scale,
+                                      float ref, float amin, float top_db, float *d_out, void *stream);
+int ss_log_mel_spectrogram_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float ref, float amin,
+                                  float top_db, float *out);
+int ss_log_mel_spectrogram_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                         const int64_t *d_row_offsets, size_t total_rows, float ref, float amin, float top_db, float *d_out,
+                                         void *stream);
+int ss_log_mel_spectrogram_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float ref,
+                                      float amin, float top_db, float *out);
+int ss_log_mel_spectrogram_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                                             const int64_t *d_row_offsets, size_t total_rows, float ref, float amin, float top_db, float *d_out,
+                                             void *stream);
+
 /* ---- streaming STFT / mel spectrogram with carried state (functions.rs:86-170, config.rs:126,162) ----
  * The reference keeps the last S = fft_points - frame_size samples in SpeechConfig::analysis_mem (config.rs:162) and opens every
  * stft1 / stft2 / mel_spectrogram call with them (frame_analysis, functions.rs:137-160), so audio fed chunk by chunk gives frames

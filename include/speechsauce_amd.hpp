@@ -470,6 +470,74 @@ inline void stft_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> 
     check(ss_stft_packed_i16(cfg.handle(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), scale, out.data()));
 }
 
+// Log-mel spectrogram (ss_log_mel_spectrogram*): the mel calls with librosa's power_to_db per clip, converted in the mel kernels'
+// epilogue -- per clip bit for bit the mel call followed by ss_power_to_db_packed_device with every clip as its own segment.  The
+// top_db floor is each clip's own maximum - top_db (top_db < 0: no floor); ss_power_to_db_device on a multi-channel block takes one
+// maximum over the whole block instead.  Shapes, layouts and errors are the mel calls'; amin > 0 and ref not NaN, else SS_ERR_ARG.
+struct DbScale {
+    float ref = 1.0f, amin = 1e-10f, top_db = 80.0f;
+};
+
+inline void log_mel_spectrogram_device(const SpeechConfig &cfg, const float *d_x, std::size_t channels, std::size_t n_samples, std::size_t ld,
+                                       const DbScale &db, float *d_out, void *stream)
+{
+    check(ss_log_mel_spectrogram_device(cfg.handle(), d_x, channels, n_samples, ld, db.ref, db.amin, db.top_db, d_out, stream));
+}
+
+inline void log_mel_spectrogram_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t channels, std::size_t n_samples,
+                                           std::size_t ld, float scale, const DbScale &db, float *d_out, void *stream)
+{
+    check(ss_log_mel_spectrogram_i16_device(cfg.handle(), d_x, channels, n_samples, ld, scale, db.ref, db.amin, db.top_db, d_out, stream));
+}
+
+inline void log_mel_spectrogram_packed_device(const SpeechConfig &cfg, const float *d_x, std::size_t n_clips, const int64_t *d_sample_offsets,
+                                              const int64_t *d_row_offsets, std::size_t total_rows, const DbScale &db, float *d_out,
+                                              void *stream)
+{
+    check(ss_log_mel_spectrogram_packed_device(cfg.handle(), d_x, n_clips, d_sample_offsets, d_row_offsets, total_rows, db.ref, db.amin,
+                                               db.top_db, d_out, stream));
+}
+
+inline void log_mel_spectrogram_packed_i16_device(const SpeechConfig &cfg, const int16_t *d_x, std::size_t n_clips,
+                                                  const int64_t *d_sample_offsets, float scale, const int64_t *d_row_offsets,
+                                                  std::size_t total_rows, const DbScale &db, float *d_out, void *stream)
+{
+    check(ss_log_mel_spectrogram_packed_i16_device(cfg.handle(), d_x, n_clips, d_sample_offsets, scale, d_row_offsets, total_rows, db.ref,
+                                                   db.amin, db.top_db, d_out, stream));
+}
+
+// x: channels rows of n_samples; out [channels x num_filters x rows]
+inline void log_mel_spectrogram(const SpeechConfig &cfg, const std::vector<float> &x, std::size_t channels, std::size_t n_samples,
+                                const DbScale &db, std::vector<float> &out)
+{
+    if (x.size() < channels * n_samples) throw Error(SS_ERR_ARG, "log_mel_spectrogram: x is too short");
+    check(ss_log_mel_spectrogram(cfg.handle(), x.data(), channels, n_samples, db.ref, db.amin, db.top_db, out.data()));
+}
+
+inline void log_mel_spectrogram_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, std::size_t channels, std::size_t n_samples,
+                                    float scale, const DbScale &db, std::vector<float> &out)
+{
+    if (x.size() < channels * n_samples) throw Error(SS_ERR_ARG, "log_mel_spectrogram_i16: x is too short");
+    check(ss_log_mel_spectrogram_i16(cfg.handle(), x.data(), channels, n_samples, scale, db.ref, db.amin, db.top_db, out.data()));
+}
+
+// x: the packed clips, sample_offsets n_clips + 1 offsets in samples; out holds the clips' [num_filters x R_b] blocks end to end
+inline void log_mel_spectrogram_packed(const SpeechConfig &cfg, const std::vector<float> &x, const std::vector<int64_t> &sample_offsets,
+                                       const DbScale &db, std::vector<float> &out)
+{
+    if (sample_offsets.empty()) throw Error(SS_ERR_ARG, "log_mel_spectrogram_packed: n_clips + 1 offsets");
+    check(ss_log_mel_spectrogram_packed(cfg.handle(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), db.ref, db.amin, db.top_db,
+                                        out.data()));
+}
+
+inline void log_mel_spectrogram_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
+                                           float scale, const DbScale &db, std::vector<float> &out)
+{
+    if (sample_offsets.empty()) throw Error(SS_ERR_ARG, "log_mel_spectrogram_packed_i16: n_clips + 1 offsets");
+    check(ss_log_mel_spectrogram_packed_i16(cfg.handle(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), scale, db.ref, db.amin,
+                                            db.top_db, out.data()));
+}
+
 // x the packed chunks, slots the pool row of each entry, pool the [pool_streams x S] states (updated in place)
 inline void mel_spectrogram_stream_packed_i16(const SpeechConfig &cfg, const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
                                               const std::vector<int32_t> &slots, std::size_t pool_streams, float scale,

@@ -307,6 +307,62 @@ struct PcmFloatCopy {
     }
 };
 
+// The dB step of a log-mel call (ss_log_mel_spectrogram*) around its ONE mel launch (launch_stft / launch_packed_stft): `args` goes to
+// the launcher, which runs the dB build of the kernel it would pick anyway where that kernel has one (ran.db_fused) and the plain
+// build everywhere else.  prepare() runs behind the launcher's own checks: with a top_db floor it makes the per-clip maxima, a
+// stream-ordered block of ordered-integer keys (DbArgs::max_key) set to 0x80808080 by one small launch, below the key of every finite
+// float; it is freed in stream order when the call returns.  Without a floor nothing is allocated: the call is the one launch.
+struct DbCall {
+    float ref, amin, top_db;
+};
+// ss_power_to_db_packed_device's checks, before anything runs
+int check_db(const DbCall &c)
+{
+    if (!(c.amin > 0.0f)) return ss::fail(SS_ERR_ARG, "amin must be strictly positive");
+    if (c.ref != c.ref) return ss::fail(SS_ERR_ARG, "ref must not be NaN");
+    return SS_OK;
+}
+struct DbStep {
+    ss::DbArgs args{};
+    float top_db = -1.0f;
+    hipStream_t st = nullptr;
+    ss::LaunchInfo ran{};  // what the mel launch was (kernel_name null: nothing was launched)
+    ~DbStep()
+    {
+        if (args.max_key) (void)hipFreeAsync(args.max_key, st);
+    }
+    // the checks, and ref_db as ss_power_to_db_packed_device forms it
+    int init(const DbCall &c)
+    {
+        const int rc = check_db(c);
+        if (rc) return rc;
+        args.amin = c.amin;
+        args.ref_db = 10.0f * std::log10(std::max(c.amin, std::fabs(c.ref)));
+        top_db = c.top_db;
+        return SS_OK;
+    }
+    int prepare(size_t clips, hipStream_t stream)
+    {
+        st = stream;
+        if (!(top_db >= 0.0f) || clips == 0) return SS_OK;
+        SS_HIP(hipMallocAsync(reinterpret_cast<void **>(&args.max_key), clips * sizeof(int), st));
+        // (a kernel, not hipMemsetAsync: in a captured call a memset node on this block was seen to run unordered against the kernel
+        // behind it when the graph is replayed -- the maxima then start from whatever the replay before left, or are wiped under the
+        // mel kernel)
+        const hipError_t e = ss::launch_db_keys_init(args.max_key, clips, st);
+        return e == hipSuccess ? SS_OK : hip_fail(e, "launch_db_keys_init");
+    }
+};
+// what ss_last_kernel_name() reports where the dB step ran behind a mel kernel without a dB build: that kernel's name + "+db"
+// (a handful of names, kept for the process)
+const char *plus_db_name(const char *kernel)
+{
+    static std::mutex mu;
+    static std::unordered_set<std::string> names;
+    std::lock_guard<std::mutex> lock(mu);
+    return names.insert(std::string(kernel) + "+db").first->c_str();
+}
+
 // SS_DEBUG_TIMES=<file> (lab build, diagnostic only): per-wave realtime stamps of ONE float MFCC launch of the 512-point kernel,
 // taken on extra launches of the call's own argument block in front of the real one.
 #if SS_LAB
@@ -546,8 +602,10 @@ int launch_frames(const ss_config *cfg, int out_kind, const float *d_x, size_t b
 // build of the kernel the float call would pick where that kernel has one (the twelve-wave 2048-point mel build, chosen by the
 // float call's own rule; the generic kernel); the eight-wave 2048-point family and the 512 / 1024 / 4096-point mel kernels run
 // behind one conversion launch into a stream-ordered temporary and report their own names.
+// `dbs` (the ss_log_mel_spectrogram* entry points, OUT_MEL): the same candidates in the same order, each on its dB build where it has
+// one -- the twelve-wave 2048-point mel build and the generic kernel; dbs->ran says what ran.
 int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t channels, size_t n, size_t ld,
-                float *out0, hipStream_t stream, const MultiBatches *multi = nullptr, const ss::BatchPcmArgs *pcm = nullptr)
+                float *out0, hipStream_t stream, const MultiBatches *multi = nullptr, const ss::BatchPcmArgs *pcm = nullptr, DbStep *dbs = nullptr)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
     if (pcm) {
@@ -570,7 +628,10 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
     a.batch = static_cast<uint32_t>(channels);
     a.rows = static_cast<uint32_t>(R);
     a.real_rows = static_cast<uint32_t>(Rreal);
-    ss::LaunchInfo info{};
+    ss::LaunchInfo own{};
+    ss::LaunchInfo &info = dbs ? dbs->ran : own;
+    if (dbs && (rc = dbs->prepare(channels, stream))) return rc;
+    const ss::DbArgs *db = dbs ? &dbs->args : nullptr;
     // pcm: the float copy of the channels for a kernel without a PCM build -- made once, on the first candidate that needs it
     PcmFloatCopy tmp{pcm, channels, n, ld, stream};
     // fft_points = 2048 mel spectrogram: the wave-private kernel when its layout assumptions hold
@@ -601,12 +662,12 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
         }
         if (pcm) {
             // declined: the float call would not run the twelve-wave mel build -> its build on the copy
-            const Step s = tried(ss::launch_mel_c1024(m, *pcm, stream, cfg->num_cus, &info), "launch_mel_c1024 (PCM)", info);
+            const Step s = tried(ss::launch_mel_c1024(m, *pcm, stream, cfg->num_cus, &info, db), "launch_mel_c1024 (PCM)", info);
             if (s.done()) return s.rc;
             if ((rc = tmp.need(a))) return rc;
             m.x = a.x;
         }
-        const Step s = tried(ss::launch_mel_c1024(m, stream, cfg->num_cus, &info), "launch_mel_c1024", info);
+        const Step s = tried(ss::launch_mel_c1024(m, stream, cfg->num_cus, &info, db), "launch_mel_c1024", info);
         if (s.done()) return s.rc;
     }
     if (multi) return kNoMultiBuild;  // the other STFT-path kernels take one block per launch
@@ -630,8 +691,8 @@ int launch_stft(const ss_config *cfg, int out_kind, const float *d_x, size_t cha
         if (s.done()) return s.rc;
     }
     // (pcm: the generic kernel's PCM build, unless a dedicated candidate above already made the float copy and then declined)
-    return tried(pcm && !a.x ? ss::launch_front_generic(a, *pcm, h.d.log2c, stream, cfg->num_cus, &info)
-                             : ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info),
+    return tried(pcm && !a.x ? ss::launch_front_generic(a, *pcm, h.d.log2c, stream, cfg->num_cus, &info, db)
+                             : ss::launch_front_generic(a, h.d.log2c, stream, cfg->num_cus, &info, db),
                  "launch_front_generic", info, true)
         .rc;
 }
@@ -1517,8 +1578,10 @@ int packed_host(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t 
 // kernel only (the launch is graph-capturable).  One launch over every clip's rows; the kernel checks the tables against each other
 // (VarRowsArgs, ss_device.h).
 // x: the packed samples, floats or 16-bit PCM (the _i16 entry points: both kernels have a PCM build, so no call converts first).
+// `dbs` (the ss_log_mel_spectrogram_packed* entry points, OUT_MEL): the dB builds of the same two kernels, and behind them -- with a
+// top_db floor -- the floor pass over the clips the kernel's table check accepts.
 int launch_packed_stft(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_clips, const int64_t *d_so, const int64_t *d_ro,
-                       size_t total_rows, float *out0, hipStream_t stream)
+                       size_t total_rows, float *out0, hipStream_t stream, DbStep *dbs = nullptr)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
     const ss::HostTables &h = cfg->host;
@@ -1543,32 +1606,46 @@ int launch_packed_stft(const ss_config *cfg, int out_kind, const PoolChunks &x, 
     v.hop = h.d.hop;
     v.err = cfg->d_err;
     const ss::BatchPcmArgs pcm{x.pcm, x.scale};
-    ss::LaunchInfo info{};
+    ss::LaunchInfo own{};
+    ss::LaunchInfo &info = dbs ? dbs->ran : own;
+    int rc = dbs ? dbs->prepare(n_clips, stream) : SS_OK;
+    if (rc) return rc;
+    const ss::DbArgs *db = dbs ? &dbs->args : nullptr;
+    // the floor pass behind a dB build (every packed mel launch is one)
+    const auto floored = [&](int launched) {
+        if (launched != SS_OK || !db || !db->max_key || !info.db_fused) return launched;
+        const hipError_t e = ss::launch_db_floor_varrows(out0, v, a.n_filters, dbs->top_db, db->max_key, stream);
+        return e == hipSuccess ? SS_OK : hip_fail(e, "launch_db_floor_varrows");
+    };
     // the 2048-point mel shape (bank within bins 0..512): the packed build of the twelve-wave kernel -- per clip the bits of
     // ss_mel_spectrogram_device's twelve-wave build; hipErrorInvalidValue before the launch for every other configuration
     if (!ss::dbg_force_generic() && out_kind == ss::OUT_MEL && cfg->mel2048.ok && !cfg->mel2048.fullp) {
         ss::Mel2048Args m = ss::mel2048_args(ss::mel_view(cfg->mel2048, cfg->d_mel2048_tab), a);
         m.ctl = cfg->d_err;
-        const Step s = tried(x.is_pcm ? ss::launch_mel_c1024_varlen(m, v, pcm, stream, cfg->num_cus, &info)
-                                      : ss::launch_mel_c1024_varlen(m, v, stream, cfg->num_cus, &info),
+        const Step s = tried(x.is_pcm ? ss::launch_mel_c1024_varlen(m, v, pcm, stream, cfg->num_cus, &info, db)
+                                      : ss::launch_mel_c1024_varlen(m, v, stream, cfg->num_cus, &info, db),
                              "launch_mel_c1024_varlen", info);
-        if (s.done()) return s.rc;
+        if (s.done()) return floored(s.rc);
     }
-    return tried(x.is_pcm ? ss::launch_front_generic_varrows(a, v, pcm, h.d.log2c, stream, cfg->num_cus, &info)
-                          : ss::launch_front_generic_varrows(a, v, h.d.log2c, stream, cfg->num_cus, &info),
-                 "launch_front_generic_varrows", info, true)
-        .rc;
+    return floored(tried(x.is_pcm ? ss::launch_front_generic_varrows(a, v, pcm, h.d.log2c, stream, cfg->num_cus, &info, db)
+                                  : ss::launch_front_generic_varrows(a, v, h.d.log2c, stream, cfg->num_cus, &info, db),
+                         "launch_front_generic_varrows", info, true)
+                       .rc);
 }
 
 // Host-pointer form: the row offsets from the host's sample offsets, one upload, one launch, one download on the config's first
 // host-pipeline stream (the host calls of a config are serialised by its mutex).
 // x: floats or 16-bit PCM; the samples go up as they are (2 B per sample for PCM) and the device call converts on load.
-int packed_stft_host(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_clips, const int64_t *so, float *out0)
+// dbc (ss_log_mel_spectrogram_packed*): the device call is the log-mel one.
+int packed_stft_host(const ss_config *cfg, int out_kind, const PoolChunks &x, size_t n_clips, const int64_t *so, float *out0,
+                     const DbCall *dbc = nullptr)
 {
     if (!cfg) return ss::fail(SS_ERR_ARG, "null config");
     if (!cfg->host.d.stft_ok) return ss::fail(SS_ERR_BAD_CONFIG, "STFT path needs fft_points >= 2 * frame_size (functions.rs:136)");
     int rc = x.is_pcm ? check_pcm_scale(x.scale) : SS_OK;
     if (rc) return rc;
+    DbStep dbs;
+    if (dbc && (rc = dbs.init(*dbc))) return rc;
     if (n_clips == 0) return SS_OK;
     if (!x.ptr() || !so || !out0) return ss::fail(SS_ERR_ARG, "null buffer");
     std::vector<int64_t> ro(n_clips + 1);
@@ -1594,7 +1671,7 @@ int packed_stft_host(const ss_config *cfg, int out_kind, const PoolChunks &x, si
     if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
     if (rc == SS_OK)
         rc = launch_packed_stft(cfg, out_kind, x.is_pcm ? PoolChunks(dx.as<const int16_t>(), x.scale) : PoolChunks(dx.as<const float>()), n_clips, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
-                                d0.as<float>(), st);
+                                d0.as<float>(), st, dbc ? &dbs : nullptr);
     if (rc == SS_OK) {
         e = hipMemcpyAsync(out0, d0.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (D2H)");
@@ -1606,15 +1683,53 @@ int packed_stft_host(const ss_config *cfg, int out_kind, const PoolChunks &x, si
     return rc;
 }
 
+// The equal-length log-mel call (ss_log_mel_spectrogram*_device): launch_stft's mel launch with the dB step around it.  On a dB build
+// that is the whole conversion; behind a kernel without one (the eight-wave 2048-point builds, the 512 / 1024 / 4096-point mel
+// kernels) the in-place pass over the block follows -- the same element arithmetic, the same maxima -- and the name reported is the
+// mel kernel's + "+db".  With a top_db floor the equal-segment floor pass is the last launch.  A linear chain on `stream`.
+int log_mel_dense(const ss_config *cfg, const float *d_x, const ss::BatchPcmArgs *pcm, size_t channels, size_t n, size_t ld, const DbCall &c,
+                  float *d_out, hipStream_t stream)
+{
+    DbStep dbs;
+    int rc = dbs.init(c);
+    if (rc) return rc;
+    rc = launch_stft(cfg, ss::OUT_MEL, d_x, channels, n, ld, d_out, stream, nullptr, pcm, &dbs);
+    if (rc || !dbs.ran.kernel_name) return rc;
+    size_t R = 0, Rreal = 0;
+    if ((rc = ss::stft_rows(cfg->host.params, n, R, Rreal))) return rc;
+    const size_t seg = R * cfg->host.params.num_filters;
+    if (!dbs.ran.db_fused) {
+        const hipError_t e = ss::launch_power_to_db_equal(d_out, channels, seg, dbs.args, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_power_to_db_equal");
+        g_last_kernel = plus_db_name(dbs.ran.kernel_name);
+    }
+    if (dbs.args.max_key) {
+        const hipError_t e = ss::launch_db_floor_equal(d_out, channels, seg, c.top_db, dbs.args.max_key, stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_db_floor_equal");
+    }
+    return SS_OK;
+}
+
+int log_mel_packed(const ss_config *cfg, const PoolChunks &x, size_t n_clips, const int64_t *d_so, const int64_t *d_ro, size_t total_rows,
+                   const DbCall &c, float *d_out, hipStream_t stream)
+{
+    DbStep dbs;
+    const int rc = dbs.init(c);
+    return rc ? rc : launch_packed_stft(cfg, ss::OUT_MEL, x, n_clips, d_so, d_ro, total_rows, d_out, stream, &dbs);
+}
+
 // Host-pointer form of the equal-length STFT-path calls (ss_stft / ss_mel_spectrogram and their _i16 forms): T = float, or int16_t
 // with pcm_scale -- the samples then cross the link as int16 (host_pipeline<int16_t>) and the device call converts.
+// dbc (ss_log_mel_spectrogram / _i16, mel output): every piece of the pipeline is a log-mel device call (a clip's maximum is its own).
 template <typename T>
-int stft_host(const ss_config *cfg, int out_kind, const T *x, size_t channels, size_t n_samples, float pcm_scale, float *out)
+int stft_host(const ss_config *cfg, int out_kind, const T *x, size_t channels, size_t n_samples, float pcm_scale, float *out,
+              const DbCall *dbc = nullptr)
 {
     constexpr bool kPcm = std::is_same_v<T, int16_t>;
     if (!cfg || !x || !out) return ss::fail(SS_ERR_ARG, "null argument");
     int rc = kPcm ? check_pcm_scale(pcm_scale) : SS_OK;
     if (rc) return rc;
+    if (dbc && (rc = check_db(*dbc))) return rc;
     size_t R = 0, Rreal = 0;
     rc = ss::stft_rows(cfg->host.params, n_samples, R, Rreal);
     if (rc) return rc;
@@ -1627,8 +1742,10 @@ int stft_host(const ss_config *cfg, int out_kind, const T *x, size_t channels, s
                          [&](const T *d_x, size_t c, float *d_o0, float *, hipStream_t st) {
                              if constexpr (kPcm) {
                                  const ss::BatchPcmArgs pcm{d_x, pcm_scale};
+                                 if (dbc) return log_mel_dense(cfg, nullptr, &pcm, c, n_samples, n_samples, *dbc, d_o0, st);
                                  return launch_stft(cfg, out_kind, nullptr, c, n_samples, n_samples, d_o0, st, nullptr, &pcm);
                              } else {
+                                 if (dbc) return log_mel_dense(cfg, d_x, nullptr, c, n_samples, n_samples, *dbc, d_o0, st);
                                  return launch_stft(cfg, out_kind, d_x, c, n_samples, n_samples, d_o0, st);
                              }
                          });
@@ -2694,6 +2811,63 @@ int ss_mel_spectrogram(const ss_config *cfg, const float *x, size_t channels, si
 int ss_mel_spectrogram_i16(const ss_config *cfg, const int16_t *x, size_t channels, size_t n_samples, float scale, float *out)
 {
     return stft_host(cfg, ss::OUT_MEL, x, channels, n_samples, scale, out);
+}
+
+// ---- log-mel spectrogram: the mel calls with librosa's power_to_db, per clip, in the kernels' epilogue (speechsauce_amd.h) ----
+int ss_log_mel_spectrogram_device(const ss_config *cfg, const float *d_x, size_t channels, size_t n_samples, size_t ld, float ref, float amin,
+                                  float top_db, float *d_out, void *stream)
+{
+    return log_mel_dense(cfg, d_x, nullptr, channels, n_samples, ld, DbCall{ref, amin, top_db}, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_log_mel_spectrogram_i16_device(const ss_config *cfg, const int16_t *d_x, size_t channels, size_t n_samples, size_t ld, float scale,
+                                      float ref, float amin, float top_db, float *d_out, void *stream)
+{
+    const ss::BatchPcmArgs pcm{d_x, scale};
+    return log_mel_dense(cfg, nullptr, &pcm, channels, n_samples, ld, DbCall{ref, amin, top_db}, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_log_mel_spectrogram_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                         const int64_t *d_row_offsets, size_t total_rows, float ref, float amin, float top_db, float *d_out,
+                                         void *stream)
+{
+    return log_mel_packed(cfg, d_x, n_clips, d_sample_offsets, d_row_offsets, total_rows, DbCall{ref, amin, top_db}, d_out,
+                          static_cast<hipStream_t>(stream));
+}
+
+int ss_log_mel_spectrogram_packed_i16_device(const ss_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                                             const int64_t *d_row_offsets, size_t total_rows, float ref, float amin, float top_db, float *d_out,
+                                             void *stream)
+{
+    return log_mel_packed(cfg, PoolChunks(d_x, scale), n_clips, d_sample_offsets, d_row_offsets, total_rows, DbCall{ref, amin, top_db}, d_out,
+                          static_cast<hipStream_t>(stream));
+}
+
+int ss_log_mel_spectrogram(const ss_config *cfg, const float *x, size_t channels, size_t n_samples, float ref, float amin, float top_db, float *out)
+{
+    const DbCall c{ref, amin, top_db};
+    return stft_host(cfg, ss::OUT_MEL, x, channels, n_samples, 1.0f, out, &c);
+}
+
+int ss_log_mel_spectrogram_i16(const ss_config *cfg, const int16_t *x, size_t channels, size_t n_samples, float scale, float ref, float amin,
+                               float top_db, float *out)
+{
+    const DbCall c{ref, amin, top_db};
+    return stft_host(cfg, ss::OUT_MEL, x, channels, n_samples, scale, out, &c);
+}
+
+int ss_log_mel_spectrogram_packed(const ss_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float ref, float amin,
+                                  float top_db, float *out)
+{
+    const DbCall c{ref, amin, top_db};
+    return packed_stft_host(cfg, ss::OUT_MEL, x, n_clips, sample_offsets, out, &c);
+}
+
+int ss_log_mel_spectrogram_packed_i16(const ss_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float ref,
+                                      float amin, float top_db, float *out)
+{
+    const DbCall c{ref, amin, top_db};
+    return packed_stft_host(cfg, ss::OUT_MEL, PoolChunks(x, scale), n_clips, sample_offsets, out, &c);
 }
 
 int ss_preemphasis(const float *x, size_t n_samples, long shift, float cof, float *y)

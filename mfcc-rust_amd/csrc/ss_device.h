@@ -92,6 +92,7 @@ struct LaunchInfo {
     const char *kernel_name;
     unsigned grid, block;
     size_t lds_bytes;
+    bool db_fused = false;  // the launch was a dB build (DbArgs below): the output already holds decibels
 };
 
 // The launch step of the fused kernels: `waves` waves per workgroup, `lds` bytes of dynamic LDS (the attribute lifts the 48 KiB a
@@ -108,7 +109,8 @@ hipError_t launch_kernel(Kern kern, const char *name, unsigned grid, int waves, 
 
 // Generic front-end (any power-of-two fft_points in [32, 4096]; with a.blu_n != 0 the chirp-z build for other lengths, log2c then
 // being the length of its complex FFT).
-hipError_t launch_front_generic(const FrontArgs &a, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info);
+struct DbArgs;  // (below: the dB builds of the mel output)
+hipError_t launch_front_generic(const FrontArgs &a, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info, const DbArgs *db = nullptr);
 
 // Packed variable-length clips (ss_mfcc_packed_device / ss_mfe_packed_device): clip b is x[so[b] : so[b+1]], its frames are rows
 // fo[b] .. fo[b+1] of the output.  Both tables are device arrays the host may never have seen, so the kernels recompute every
@@ -253,7 +255,7 @@ __device__ __forceinline__ void varrows_check_clips(const VarRowsArgs &v, unsign
 // mel output at any fft_points (chirp-z included) and every stft output: the packed-rows build of ss_front_generic's STFT / mel path.
 // a: as for launch_front_generic's STFT path with x = the packed samples; batch / n_samples / rows / real_rows are unused.
 hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
-                                        LaunchInfo *info);
+                                        LaunchInfo *info, const DbArgs *db = nullptr);
 
 // Streaming STFT (ss_stft_stream_device / ss_mel_spectrogram_stream_device): every stream (a row of the batch) carries the last
 // S = fft_points - hop samples it was fed (config.rs:162, functions.rs:137-160).  A window that reaches before the chunk reads them:
@@ -275,6 +277,35 @@ __device__ __forceinline__ const T *pack_arg(const V &...v)
         ...);
     return p;
 }
+// The dB epilogue of the mel kernels (ss_log_mel_spectrogram*): a DbArgs LAST in the trailing argument pack -- behind the layout's own
+// argument and behind a BatchPcmArgs -- selects it the way a BatchPcmArgs selects the PCM loader.  Every mel value goes through
+// power_db() just before it is stored; with max_key non-null the largest dB value of every clip is gathered into max_key[clip]
+// (float_key order, integer atomicMax: the result does not depend on the order of arrival) for the top_db floor pass behind the
+// launch.  max_key must hold 0x80808080 in every word at launch (below the key of every finite float).
+struct DbArgs {
+    float amin, ref_db;  // ref_db = 10 log10(max(amin, |ref|)), formed on the host
+    int *max_key;        // [clips] or null (no floor: nothing is reduced)
+};
+// librosa's power_to_db of one element: 10 log10(max(amin, s)) - ref_db, the product and the difference as ONE fma (what the device
+// default contraction makes of ss_post.hip's `10.0f * log10f(..) - ref_db`)
+__device__ __forceinline__ float power_db(float s, float amin, float ref_db) { return fmaf(10.0f, log10f(fmaxf(amin, s)), -ref_db); }
+// floats as ordered integers, so that atomicMax on an int finds the largest float (negative values included)
+__device__ __forceinline__ int float_key(float v)
+{
+    const int b = __float_as_int(v);
+    return b >= 0 ? b : b ^ 0x7fffffff;
+}
+__device__ __forceinline__ float key_float(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
+// The launches around a log-mel mel launch (ss_post.hip).  In front of it, with a floor: max_key[0 .. clips) := 0x80808080.  Behind it:
+// the top_db floor out[i] = max(out[i], max of i's clip - top_db) over
+// equal-length clips of `seg` elements each (no table) / over the [M x R_b] blocks of a packed call's clips (cols = M; a clip that
+// the mel kernels' table check skips is left alone); and, behind a mel kernel without a dB build, power_db over equal-length
+// clips in place with the maxima gathered as the dB builds gather them.
+hipError_t launch_db_keys_init(int *max_key, size_t clips, hipStream_t stream);
+hipError_t launch_db_floor_equal(float *out, size_t clips, size_t seg, float top_db, const int *max_key, hipStream_t stream);
+hipError_t launch_db_floor_varrows(float *out, const VarRowsArgs &v, size_t cols, float top_db, const int *max_key, hipStream_t stream);
+hipError_t launch_power_to_db_equal(float *x, size_t clips, size_t seg, const DbArgs &db, hipStream_t stream);
+
 // the streaming build of ss_front_generic's STFT / mel path (any fft_points, chirp-z included): a as for launch_front_generic's
 // STFT path, on the chunk (n_pad 0 and real_rows = rows in continuous mode)
 hipError_t launch_front_generic_stream(const FrontArgs &a, const StreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,
@@ -405,7 +436,8 @@ struct VarlenPcmArgs {  // packed clips: the float layout's tables (varlen_clip(
     float scale;
 };
 // a as for launch_front_generic / launch_front_generic_varlen (a.x unused); MFCC / mfe / power outputs as the float layouts
-hipError_t launch_front_generic(const FrontArgs &a, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info);
+hipError_t launch_front_generic(const FrontArgs &a, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info,
+                                const DbArgs *db = nullptr);
 hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenPcmArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
                                        LaunchInfo *info);
 // The fallback of the equal-length PCM calls whose kernel has no PCM build (both packed kernels have one): dst[r * ld + k] = (float)src[r * ld + k] * scale for k < n, r < rows
@@ -434,7 +466,7 @@ hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStre
 // PCM, the pool rows stay float; launch_stream_advance_packed(FrameStreamPackedPcmArgs) moves them on).  The tables, the offsets
 // (in samples) and every check are the float layouts'; a.x is unused.  Reported as ss_front_generic_varrowsi / _streampi.
 hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream,
-                                        int num_cus, LaunchInfo *info);
+                                        int num_cus, LaunchInfo *info, const DbArgs *db = nullptr);
 hipError_t launch_front_generic_stream_packed(const FrontArgs &a, const StftStreamPackedArgs &s, const BatchPcmArgs &p, uint32_t log2c,
                                               hipStream_t stream, int num_cus, LaunchInfo *info);
 #if SS_LAB
@@ -564,14 +596,17 @@ struct Mel2048Args {
     unsigned long long *stamps;
 };
 
-hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cus, LaunchInfo *info);
+hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cus, LaunchInfo *info, const DbArgs *db = nullptr);
+// (db, here and on the three launchers of the dense and the packed layout below: the dB build of the twelve-wave mel kernel where the
+// call runs that kernel -- info->db_fused says so; the eight-wave builds have no dB build and run as they are)
 // the streaming builds (mel output; StreamArgs above), chosen between eight and twelve waves by launch_mel_c1024's rule;
 // hipErrorInvalidValue before the launch for stft output or a shape that does not fit
 hipError_t launch_mel_c1024_stream(const Mel2048Args &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info);
 // packed variable-length clips (VarRowsArgs above) on the twelve-wave mel build, whatever the unit count (a clip's bits must not
 // depend on the clips beside it); a: x / out = the packed blocks, batch / n_samples / rows / real_rows unused.  hipErrorInvalidValue
 // before the launch for stft output, a bank that reaches past (F+1)/2 (fullp) or a shape that does not fit
-hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
+hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info,
+                                   const DbArgs *db = nullptr);
 // ragged streaming over a pool of stream states (StftStreamPackedArgs above) on the twelve-wave mel build, whatever the unit count
 // (an entry's bits must not depend on the entries beside it); a: x / out = the packed blocks, n_pad = 0, batch / n_samples / rows /
 // real_rows unused.  hipErrorInvalidValue before the launch for stft output, a bank that reaches past (F+1)/2 (fullp) or a shape
@@ -587,9 +622,10 @@ hipError_t launch_mel_c1024_multi(const Mel2048Args &a, int n_batches, const flo
 // offsets of either parity).  The equal-length form serves exactly the calls launch_mel_c1024 gives the twelve-wave mel build (the
 // same rule, so the bits are the float call's); hipErrorInvalidValue before the launch for every other call -- eight waves, stft
 // output, fullp -- which the caller runs on the float build behind a conversion.
-hipError_t launch_mel_c1024(const Mel2048Args &a, const BatchPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info);
+hipError_t launch_mel_c1024(const Mel2048Args &a, const BatchPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info,
+                            const DbArgs *db = nullptr);
 hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, const BatchPcmArgs &p, hipStream_t stream, int num_cus,
-                                   LaunchInfo *info);
+                                   LaunchInfo *info, const DbArgs *db = nullptr);
 hipError_t launch_mel_c1024_stream_packed(const Mel2048Args &a, const StftStreamPackedArgs &s, const BatchPcmArgs &p, hipStream_t stream,
                                           int num_cus, LaunchInfo *info);
 #if SS_LAB

@@ -271,6 +271,9 @@ __device__ __forceinline__ float mel_dot(const float *prow, const FrontArgs &a, 
 // row within the chunk, its pool row) comes from the device tables (StftStreamPackedArgs), its window as in STREAM.
 // (V: empty, one VarlenArgs, one StreamArgs, one FrameStreamArgs, one FrameStreamPackedArgs, one FrameStreamPackedPcmArgs, one
 // BatchPcmArgs, one VarlenPcmArgs, one VarRowsArgs or one StftStreamPackedArgs, the last two also with a BatchPcmArgs behind them -- an empty pack leaves the argument block of the equal-length builds exactly as it was)
+// DB (a DbArgs last in the pack: behind nothing, a BatchPcmArgs, a VarRowsArgs or a VarRowsArgs and a BatchPcmArgs): the mel output of
+// the STFT / mel path in decibels -- a mel value is converted where the tile is filled (the flush is unchanged), the largest value of
+// a row goes through the slot's `red` words to one atomicMax on the row's clip (ss_log_mel_spectrogram*, DbArgs in ss_device.h).
 template <int LOG2C, bool BLU, typename... V>
 __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, const V... vargs)
 {
@@ -284,6 +287,9 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     constexpr bool VARR = (std::is_same_v<V, VarRowsArgs> || ...);
     constexpr bool SPR = (std::is_same_v<V, StftStreamPackedArgs> || ...);
     constexpr bool EQI = PCMX && !VARR && !SPR;
+    constexpr bool DB = (std::is_same_v<V, DbArgs> || ...);
+    static_assert(!DB || !(VAR || STREAM || FSTREAM || SPR), "the dB builds are the equal-length and the packed-rows mel builds");
+    [[maybe_unused]] const DbArgs *db = pack_arg<DbArgs>(vargs...);
     [[maybe_unused]] const StftStreamPackedArgs *sp = pack_arg<StftStreamPackedArgs>(vargs...);
     [[maybe_unused]] const VarRowsArgs *ra = pack_arg<VarRowsArgs>(vargs...);
     [[maybe_unused]] const BatchPcmArgs *bpi = pack_arg<BatchPcmArgs>(vargs...);
@@ -313,7 +319,7 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
     // MEL mode: transposed output tile [M][rows_tile + 1] after all slots
     float *tile = reinterpret_cast<float *>(smem_raw + slot_bytes * G::FPB);
 
-    const bool mel_mode = STREAM || VARR || SPR || (!VAR && !FSTREAM && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT));
+    const bool mel_mode = DB || STREAM || VARR || SPR || (!VAR && !FSTREAM && (a.out_kind == OUT_MEL || a.out_kind == OUT_STFT));
     const int F = BLU ? static_cast<int>(a.blu_n / 2 + 1) : G::F;  // bins per row
 
     if (!mel_mode) {
@@ -549,13 +555,15 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 const unsigned long long g = g0 + rl;
                 // rows past the last clip (a larger output block) are left alone; rows of an inconsistent clip are skipped
                 VarRowClip c;
+                [[maybe_unused]] unsigned cb = 0;  // VARR: the row's clip
                 [[maybe_unused]] const float *srow = nullptr;  // SPR: the entry's pool row, indexed from its end (sample p < 0 is srow[p])
                 if constexpr (SPR) {
                     const StreamEntry en = stream_entry(sp->e, rl < rt ? offset_find(sp->e.ro, sp->e.n_active, static_cast<unsigned>(g)) : 0u);
                     c = VarRowClip{en.s0, en.r0, en.n, en.R, en.ok};
                     if (en.ok) srow = sp->e.pool + static_cast<unsigned long long>(en.slot) * sp->e.state_len + sp->e.state_len;
                 } else {
-                    c = varrows_clip(*ra, rl < rt ? offset_find(ra->ro, ra->n_clips, static_cast<long long>(g)) : 0u);
+                    cb = rl < rt ? offset_find(ra->ro, ra->n_clips, static_cast<long long>(g)) : 0u;
+                    c = varrows_clip(*ra, cb);
                 }
                 const long long r = static_cast<long long>(g) - c.r0;  // row within the clip
                 const bool valid = rl < rt && c.ok && r >= 0 && r < static_cast<long long>(c.R);
@@ -602,7 +610,16 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                 frame_sync<LOG2C>();  // prow is private to the frame; the shared tile has its own barriers below
                 if (a.out_kind == OUT_MEL && rl < rt) {
                     // feature.rs:173: out[m, r] = sum_f P[r, f] fb[m, f]; rows >= real_rows stay zero
-                    for (int m = j; m < M; m += G::TPF) tile[m * (TILE + 1) + rl] = active ? mel_dot(prow, a, m) : 0.0f;
+                    [[maybe_unused]] float mx = -INFINITY;
+                    for (int m = j; m < M; m += G::TPF) {
+                        float val = active ? mel_dot(prow, a, m) : 0.0f;
+                        if constexpr (DB) {
+                            val = power_db(val, db->amin, db->ref_db);
+                            mx = fmaxf(mx, val);
+                        }
+                        tile[m * (TILE + 1) + rl] = val;
+                    }
+                    if constexpr (DB) red[j] = mx;
                     if (j == 0) {
                         t_base[rl] = valid ? c.r0 * M + r : -1ll;
                         t_rows[rl] = c.R;
@@ -612,6 +629,14 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                     for (int k = j; k < F; k += G::TPF) stft_row[k] = make_float2(0.0f, 0.0f);
                 }
                 __syncthreads();
+                if constexpr (DB) {
+                    // the row's maximum into its clip's word: rows that are written only (a skipped clip's word stays as it was)
+                    if (db->max_key && a.out_kind == OUT_MEL && valid && j == 0) {
+                        float mx = red[0];
+                        for (int i = 1; i < G::TPF; ++i) mx = fmaxf(mx, red[i]);
+                        if (mx > -INFINITY) atomicMax(db->max_key + cb, float_key(mx));
+                    }
+                }
             }
             if (a.out_kind == OUT_MEL) {
                 // clip b's block [M x R_b] starts at out + M ro[b]: element (m, r) is word M ro[b] + m R_b + r
@@ -680,12 +705,28 @@ __global__ __launch_bounds__(kBlock) void ss_front_generic(const FrontArgs a, co
                     frame_sync<LOG2C>();  // prow is private to the frame; the shared tile has its own barriers below
                     if (a.out_kind == OUT_MEL && rl < rt) {
                         // feature.rs:173: out[n,m,t] = sum_f P[n,t,f] fb[m,f]; rows >= real_rows stay zero
-                        for (int m = j; m < M; m += G::TPF) tile[m * (TILE + 1) + rl] = active ? mel_dot(prow, a, m) : 0.0f;
+                        [[maybe_unused]] float mx = -INFINITY;
+                        for (int m = j; m < M; m += G::TPF) {
+                            float val = active ? mel_dot(prow, a, m) : 0.0f;
+                            if constexpr (DB) {
+                                val = power_db(val, db->amin, db->ref_db);
+                                mx = fmaxf(mx, val);
+                            }
+                            tile[m * (TILE + 1) + rl] = val;
+                        }
+                        if constexpr (DB) red[j] = mx;
                     }
                     if (a.out_kind == OUT_STFT && rl < rt && r >= Rreal) {
                         for (int k = j; k < F; k += G::TPF) stft_row[k] = make_float2(0.0f, 0.0f);
                     }
                     __syncthreads();
+                    if constexpr (DB) {
+                        if (db->max_key && a.out_kind == OUT_MEL && rl < rt && j == 0) {
+                            float mx = red[0];
+                            for (int i = 1; i < G::TPF; ++i) mx = fmaxf(mx, red[i]);
+                            if (mx > -INFINITY) atomicMax(db->max_key + clip, float_key(mx));
+                        }
+                    }
                 }
                 if (a.out_kind == OUT_MEL) {
                     float *dst = a.out0 + static_cast<unsigned long long>(clip) * M * R;
@@ -725,6 +766,11 @@ constexpr const char *layout_suffix(const FrameStreamPackedPcmArgs &) { return "
 constexpr const char *layout_suffix(const StftStreamPackedArgs &) { return "_streamp"; }
 constexpr const char *layout_suffix(const VarRowsArgs &, const BatchPcmArgs &) { return "_varrowsi"; }
 constexpr const char *layout_suffix(const StftStreamPackedArgs &, const BatchPcmArgs &) { return "_streampi"; }
+// (a DbArgs last: the layout's own suffix -- the dB builds carry `db` in the template list, front_kernel_name)
+constexpr const char *layout_suffix(const DbArgs &) { return ""; }
+constexpr const char *layout_suffix(const BatchPcmArgs &p, const DbArgs &) { return layout_suffix(p); }
+constexpr const char *layout_suffix(const VarRowsArgs &v, const DbArgs &) { return layout_suffix(v); }
+constexpr const char *layout_suffix(const VarRowsArgs &v, const BatchPcmArgs &p, const DbArgs &) { return layout_suffix(v, p); }
 
 // the packed-rows builds: the tile's row table (32 offsets + 32 row counts, 8-byte aligned)
 constexpr size_t kRowTableBytes = 32 * (sizeof(long long) + sizeof(unsigned)) + 16;
@@ -737,6 +783,10 @@ constexpr size_t layout_lds(const BatchPcmArgs &) { return 0; }
 constexpr size_t layout_lds(const VarlenPcmArgs &) { return 0; }
 constexpr size_t layout_lds(const VarRowsArgs &, const BatchPcmArgs &) { return kRowTableBytes; }
 constexpr size_t layout_lds(const StftStreamPackedArgs &, const BatchPcmArgs &) { return kRowTableBytes; }
+constexpr size_t layout_lds(const DbArgs &) { return 0; }
+constexpr size_t layout_lds(const BatchPcmArgs &, const DbArgs &) { return 0; }
+constexpr size_t layout_lds(const VarRowsArgs &, const DbArgs &) { return kRowTableBytes; }
+constexpr size_t layout_lds(const VarRowsArgs &, const BatchPcmArgs &, const DbArgs &) { return kRowTableBytes; }
 
 // Workgroup visits of a call at `fpb` frames per visit.  0: nothing to launch; kTooManyRows: the kernel's 32-bit row index does not
 // reach the last row.
@@ -780,8 +830,15 @@ inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb
 {
     return layout_work(a, fpb, s);
 }
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const DbArgs &) { return layout_work(a, fpb); }
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const BatchPcmArgs &, const DbArgs &) { return layout_work(a, fpb); }
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const VarRowsArgs &v, const DbArgs &) { return layout_work(a, fpb, v); }
+inline unsigned long long layout_work(const FrontArgs &a, unsigned long long fpb, const VarRowsArgs &v, const BatchPcmArgs &, const DbArgs &)
+{
+    return layout_work(a, fpb, v);
+}
 
-// What ss_last_kernel_name() reports for an instantiation: ss_front_generic<suffix><LOG2C[,chirpz]>, built once, kept for the process.
+// What ss_last_kernel_name() reports for an instantiation: ss_front_generic<suffix><LOG2C[,chirpz][,db]>, built once, kept for the process.
 template <int LOG2C, bool BLU, typename... V>
 const char *front_kernel_name(const V &...v)
 {
@@ -790,7 +847,8 @@ const char *front_kernel_name(const V &...v)
     };
     static const Name name = [&] {
         Name n;
-        snprintf(n.s, sizeof n.s, "ss_front_generic%s<%d%s>", layout_suffix(v...), LOG2C, BLU ? ",chirpz" : "");
+        snprintf(n.s, sizeof n.s, "ss_front_generic%s<%d%s%s>", layout_suffix(v...), LOG2C, BLU ? ",chirpz" : "",
+                 (std::is_same_v<V, DbArgs> || ...) ? ",db" : "");
         return n;
     }();
     return name.s;
@@ -811,7 +869,7 @@ hipError_t launch_one(const FrontArgs &a, hipStream_t stream, int num_cus, Launc
     if (work == kTooManyRows) return hipErrorInvalidValue;
     const unsigned long long cap = cu_cap(num_cus) * 8ull;
     const unsigned grid = static_cast<unsigned>(work < cap ? work : cap);
-    if (info) *info = LaunchInfo{front_kernel_name<LOG2C, BLU>(v...), grid, static_cast<unsigned>(kBlock), lds};
+    if (info) *info = LaunchInfo{front_kernel_name<LOG2C, BLU>(v...), grid, static_cast<unsigned>(kBlock), lds, (std::is_same_v<V, DbArgs> || ...)};
     hipLaunchKernelGGL((ss_front_generic<LOG2C, BLU, V...>), dim3(grid), dim3(kBlock), lds, stream, a, v...);
     return hipGetLastError();
 }
@@ -959,8 +1017,10 @@ hipError_t launch_poison_lds(hipStream_t stream, int num_cus)
 }
 #endif
 
-hipError_t launch_front_generic(const FrontArgs &a, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info)
+// (db, here and on the PCM and the two packed-rows launchers below: the dB build of the same layout, mel output only)
+hipError_t launch_front_generic(const FrontArgs &a, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info, const DbArgs *db)
 {
+    if (db) return a.out_kind == OUT_MEL ? dispatch_front(a, log2c, stream, num_cus, info, *db) : hipErrorInvalidValue;
     return dispatch_front(a, log2c, stream, num_cus, info);
 }
 
@@ -971,9 +1031,11 @@ hipError_t launch_front_generic_varlen(const FrontArgs &a, const VarlenArgs &v, 
     return dispatch_front(a, log2c, stream, num_cus, info, v);
 }
 
-hipError_t launch_front_generic(const FrontArgs &a, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info)
+hipError_t launch_front_generic(const FrontArgs &a, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream, int num_cus, LaunchInfo *info,
+                                const DbArgs *db)
 {
     if (!p.x) return hipErrorInvalidValue;  // (every output: MFCC / mfe / power, and the mel / stft rows of the STFT path)
+    if (db) return a.out_kind == OUT_MEL ? dispatch_front(a, log2c, stream, num_cus, info, p, *db) : hipErrorInvalidValue;
     return dispatch_front(a, log2c, stream, num_cus, info, p);
 }
 
@@ -1008,16 +1070,18 @@ hipError_t launch_pcm_to_float(const int16_t *src, float *dst, size_t rows, size
 }
 
 hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, uint32_t log2c, hipStream_t stream, int num_cus,
-                                        LaunchInfo *info)
+                                        LaunchInfo *info, const DbArgs *db)
 {
     if (a.out_kind != OUT_MEL && a.out_kind != OUT_STFT) return hipErrorInvalidValue;
+    if (db) return a.out_kind == OUT_MEL ? dispatch_front(a, log2c, stream, num_cus, info, v, *db) : hipErrorInvalidValue;
     return dispatch_front(a, log2c, stream, num_cus, info, v);
 }
 
 hipError_t launch_front_generic_varrows(const FrontArgs &a, const VarRowsArgs &v, const BatchPcmArgs &p, uint32_t log2c, hipStream_t stream,
-                                        int num_cus, LaunchInfo *info)
+                                        int num_cus, LaunchInfo *info, const DbArgs *db)
 {
     if ((a.out_kind != OUT_MEL && a.out_kind != OUT_STFT) || !p.x) return hipErrorInvalidValue;
+    if (db) return a.out_kind == OUT_MEL ? dispatch_front(a, log2c, stream, num_cus, info, v, p, *db) : hipErrorInvalidValue;
     return dispatch_front(a, log2c, stream, num_cus, info, v, p);
 }
 

@@ -35,6 +35,9 @@
 // ss_mel_c1024i<w12,...> / ss_mel_c1024vi<...> / ss_mel_c1024spi<...>): the samples are signed 16-bit PCM, a lane's 32 window pairs 32
 // dwords of two int16 each, fetched where the float pairs are and converted where the window product consumes them; only the loader
 // and that product differ.
+// dB builds of the twelve-wave kernel's dense and packed mel layouts, float and PCM (a DbArgs LAST in the trailing argument pack, reported
+// with `db` at the end of the template list: ss_mel_c1024<w12,...,db> / i / v / vi): the mel values leave in decibels (power_db,
+// ss_device.h) and, with a top_db floor to follow, every clip's largest value is gathered into DbArgs::max_key; only the epilogue differs.
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 #include "ss_internal.h"
@@ -391,7 +394,10 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
     [[maybe_unused]] const StftStreamPackedArgs *pa = pack_arg<StftStreamPackedArgs>(sargs...);
     constexpr bool PCM = (std::is_same_v<SA, BatchPcmArgs> || ...);
     [[maybe_unused]] const BatchPcmArgs *pc = pack_arg<BatchPcmArgs>(sargs...);
+    constexpr bool DB = (std::is_same_v<SA, DbArgs> || ...);
+    [[maybe_unused]] const DbArgs *da = pack_arg<DbArgs>(sargs...);
     static_assert(!PCM || (!STFT && !MULTI && !STREAM), "the PCM builds are the one-block mel-output builds of the three layouts");
+    static_assert(!DB || (!STFT && !MULTI && !STREAM && !SPOOL), "the dB builds are the dense and the packed one-block mel-output builds");
     static_assert(!SPOOL || (!STFT && !MULTI && !STREAM && !VARR), "the ragged streaming build is a one-block mel-output build");
     static_assert(!(MULTI && STFT), "the batch-table build is a mel-output build");
     static_assert(!(MULTI && STREAM), "the streaming build takes one block");
@@ -468,6 +474,7 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
         [[maybe_unused]] long long vr = 0;    // ... its row in that clip
         [[maybe_unused]] bool vvalid = false;  // ... and whether the row is one of the clip's (consistent offsets) and is written
         [[maybe_unused]] bool vsame = false;   // ... and whether it is in the clip of the unit's first row
+        [[maybe_unused]] unsigned vclip = 0;   // VARR: ... and the clip's index (DB: its word of max_key)
         [[maybe_unused]] unsigned pslot = 0;   // SPOOL: the entry's pool row
         if constexpr (VARR) {
             const long long g0 = 2ll * unit;
@@ -476,6 +483,7 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
             const long long g = g0 + half;
             vsame = !(c + 1 < ra->n_clips && ra->ro[c + 1] <= g);
             if (!vsame) ++c;
+            vclip = c;
             vc = varrows_clip(*ra, c);
             vr = g - vc.r0;
             vvalid = static_cast<unsigned long long>(g) < ra->total_rows && vc.ok && vr >= 0 && vr < static_cast<long long>(vc.R);
@@ -773,6 +781,21 @@ __global__ __launch_bounds__(12 * 64, 3) void ss_mel_c1024_w12(const Mel2048Args
                         off += a.mel_q4[s];
                     }
                 }
+                if constexpr (DB) {
+                    // decibels in the epilogue (DbArgs, ss_device.h); the largest value the row stores joins its clip's maximum: over
+                    // the half-wave in the packed build (a pair may straddle two clips), over both rows of the wave in the dense one
+                    float mx = -INFINITY;
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        mv[s] = power_db(mv[s], da->amin, da->ref_db);
+                        if (in_rows && fi[s] >= 0) mx = fmaxf(mx, mv[s]);
+                    }
+                    if (da->max_key) {  // (uniform)
+#pragma unroll
+                        for (int m = 1; m < (PACKED ? 32 : 64); m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+                        if ((PACKED ? j : lane) == 0 && mx > -INFINITY) atomicMax(da->max_key + (PACKED ? vclip : clip), float_key(mx));
+                    }
+                }
                 if constexpr (PACKED) {
                     // clip b's block [M x R_b] starts at out + M ro[b]
                     float *dst = out_b + vc.r0 * M + vr;
@@ -843,27 +866,40 @@ hipError_t launch_mel_w(const Mel2048Args &a, hipStream_t stream, int num_cus, L
     return launch_kernel(ss_mel_c1024<kWavesM, false>, "ss_mel_c1024", grid, kWavesM, lds, stream, info, a);
 }
 
+// What the dense and the packed twelve-wave mel builds report: [packed][PCM][mel6321][dB]
+const char *w12_name(bool packed, bool pcm, bool fix, bool db)
+{
+    static const char *const names[2][2][2][2] = {
+        {{{"ss_mel_c1024<w12>", "ss_mel_c1024<w12,db>"}, {"ss_mel_c1024<w12,mel6321>", "ss_mel_c1024<w12,mel6321,db>"}},
+         {{"ss_mel_c1024i<w12>", "ss_mel_c1024i<w12,db>"}, {"ss_mel_c1024i<w12,mel6321>", "ss_mel_c1024i<w12,mel6321,db>"}}},
+        {{{"ss_mel_c1024v<w12>", "ss_mel_c1024v<w12,db>"}, {"ss_mel_c1024v<w12,mel6321>", "ss_mel_c1024v<w12,mel6321,db>"}},
+         {{"ss_mel_c1024vi<w12>", "ss_mel_c1024vi<w12,db>"}, {"ss_mel_c1024vi<w12,mel6321>", "ss_mel_c1024vi<w12,mel6321,db>"}}}};
+    return names[packed][pcm][fix][db];
+}
+
 // three waves per SIMD, direct stores (see ss_mel_c1024_w12): mel output with the reference bank shape, and stft
-// (p, here and in the two packed launchers below: empty -- floats at a.x -- or one BatchPcmArgs, the PCM builds: mel output only)
+// (p, here and in the packed launchers below: empty -- floats at a.x -- or a BatchPcmArgs, the PCM builds, and / or a DbArgs last,
+// the dB builds of the dense and the packed layout: mel output only)
 template <typename... P>
 hipError_t launch_mel_w12(const Mel2048Args &a, hipStream_t stream, int num_cus, LaunchInfo *info, const P &...p)
 {
-    constexpr bool PCM = sizeof...(P) != 0;
-    if (a.fullp || a.batch == 0 || (PCM && a.out_stft)) return hipErrorInvalidValue;
+    constexpr bool PCM = (std::is_same_v<P, BatchPcmArgs> || ...), DB = (std::is_same_v<P, DbArgs> || ...);
+    if (a.fullp || a.batch == 0 || ((PCM || DB) && a.out_stft)) return hipErrorInvalidValue;
     const size_t lds = mel_lds_bytes(12, a.mel_wpitch);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * (a.out_stft ? (a.rows + 1) / 2 : mel_work_pairs(a.rows, a.real_rows));
     if (units >= 0xffffffffull) return hipErrorInvalidValue;
     const unsigned grid = cu_capped_grid(units, 12, num_cus);
     const MultiArg<false> none{};
-    if constexpr (!PCM) {
+    if constexpr (!PCM && !DB) {
         if (a.out_stft) return launch_kernel(ss_mel_c1024_w12<false, true>, "ss_mel_c1024<w12,stft>", grid, 12, lds, stream, info, a, none);
     }
-    if (mel6321(a))
-        return launch_kernel(ss_mel_c1024_w12<true, false, false, P...>, PCM ? "ss_mel_c1024i<w12,mel6321>" : "ss_mel_c1024<w12,mel6321>", grid, 12, lds,
-                             stream, info, a, none, p...);
-    return launch_kernel(ss_mel_c1024_w12<false, false, false, P...>, PCM ? "ss_mel_c1024i<w12>" : "ss_mel_c1024<w12>", grid, 12, lds, stream, info, a,
-                         none, p...);
+    const bool fix = mel6321(a);
+    const char *name = w12_name(false, PCM, fix, DB);
+    const hipError_t e = fix ? launch_kernel(ss_mel_c1024_w12<true, false, false, P...>, name, grid, 12, lds, stream, info, a, none, p...)
+                             : launch_kernel(ss_mel_c1024_w12<false, false, false, P...>, name, grid, 12, lds, stream, info, a, none, p...);
+    if (DB && e == hipSuccess && info) info->db_fused = true;
+    return e;
 }
 
 // the streaming builds (mel output): eight waves (the reference bank shape or every bin) / twelve waves (the reference bank shape)
@@ -894,18 +930,19 @@ hipError_t launch_mel_w12_stream(const Mel2048Args &a, const StreamArgs &s, hipS
 template <typename... P>
 hipError_t launch_mel_w12_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info, const P &...p)
 {
-    constexpr bool PCM = sizeof...(P) != 0;
+    constexpr bool PCM = (std::is_same_v<P, BatchPcmArgs> || ...), DB = (std::is_same_v<P, DbArgs> || ...);
     const size_t lds = mel_lds_bytes(12, a.mel_wpitch);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     // an empty output block still gets one workgroup: the clip pass runs
     const unsigned long long units = (v.total_rows + 1) / 2;
     const unsigned grid = units ? cu_capped_grid(units, 12, num_cus) : 1u;
     const MultiArg<false> none{};
-    if (mel6321(a))
-        return launch_kernel(ss_mel_c1024_w12<true, false, false, VarRowsArgs, P...>, PCM ? "ss_mel_c1024vi<w12,mel6321>" : "ss_mel_c1024v<w12,mel6321>",
-                             grid, 12, lds, stream, info, a, none, v, p...);
-    return launch_kernel(ss_mel_c1024_w12<false, false, false, VarRowsArgs, P...>, PCM ? "ss_mel_c1024vi<w12>" : "ss_mel_c1024v<w12>", grid, 12, lds,
-                         stream, info, a, none, v, p...);
+    const bool fix = mel6321(a);
+    const char *name = w12_name(true, PCM, fix, DB);
+    const hipError_t e = fix ? launch_kernel(ss_mel_c1024_w12<true, false, false, VarRowsArgs, P...>, name, grid, 12, lds, stream, info, a, none, v, p...)
+                             : launch_kernel(ss_mel_c1024_w12<false, false, false, VarRowsArgs, P...>, name, grid, 12, lds, stream, info, a, none, v, p...);
+    if (DB && e == hipSuccess && info) info->db_fused = true;
+    return e;
 }
 
 template <typename... P>
@@ -977,7 +1014,7 @@ static bool mel_lab_knobs()
 #endif
 }
 
-hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cus, LaunchInfo *info)
+hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cus, LaunchInfo *info, const DbArgs *db)
 {
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * (a.out_stft ? (a.rows + 1) / 2 : mel_work_pairs(a.rows, a.real_rows));
 #if SS_LAB
@@ -1005,19 +1042,20 @@ hipError_t launch_mel_c1024(const Mel2048Args &a, hipStream_t stream, int num_cu
         return launch_mel_w<8>(a, stream, num_cus, info);
     }
     if (mel_takes_twelve_waves(a, units, num_cus)) {
-        const hipError_t e = launch_mel_w12(a, stream, num_cus, info);
+        // (db: the dB build of the very kernel the plain call runs; the eight-wave builds have none -- info->db_fused stays false)
+        const hipError_t e = db ? launch_mel_w12(a, stream, num_cus, info, *db) : launch_mel_w12(a, stream, num_cus, info);
         if (e != hipErrorInvalidValue) return e;
     }
     return launch_mel_w<8>(a, stream, num_cus, info);
 }
 
-hipError_t launch_mel_c1024(const Mel2048Args &a, const BatchPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info)
+hipError_t launch_mel_c1024(const Mel2048Args &a, const BatchPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info, const DbArgs *db)
 {
     // the float call's rule, so that the PCM call runs the PCM build of the very kernel the float call runs (the eight- and
     // twelve-wave builds round a few FMAs differently in the last bit); everything else is the caller's conversion fallback
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * mel_work_pairs(a.rows, a.real_rows);
     if (!p.x || a.out_stft || mel_lab_knobs() || !mel_takes_twelve_waves(a, units, num_cus)) return hipErrorInvalidValue;
-    return launch_mel_w12(a, stream, num_cus, info, p);
+    return db ? launch_mel_w12(a, stream, num_cus, info, p, *db) : launch_mel_w12(a, stream, num_cus, info, p);
 }
 
 hipError_t launch_mel_c1024_stream(const Mel2048Args &a, const StreamArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info)
@@ -1043,17 +1081,17 @@ static bool mel_varlen_shape(const Mel2048Args &a, const VarRowsArgs &v)
     return !a.out_stft && !a.fullp && v.n_clips != 0 && v.total_rows < (1ull << 31);
 }
 
-hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info, const DbArgs *db)
 {
     if (!mel_varlen_shape(a, v)) return hipErrorInvalidValue;
-    return launch_mel_w12_varlen(a, v, stream, num_cus, info);
+    return db ? launch_mel_w12_varlen(a, v, stream, num_cus, info, *db) : launch_mel_w12_varlen(a, v, stream, num_cus, info);
 }
 
 hipError_t launch_mel_c1024_varlen(const Mel2048Args &a, const VarRowsArgs &v, const BatchPcmArgs &p, hipStream_t stream, int num_cus,
-                                   LaunchInfo *info)
+                                   LaunchInfo *info, const DbArgs *db)
 {
     if (!p.x || !mel_varlen_shape(a, v)) return hipErrorInvalidValue;
-    return launch_mel_w12_varlen(a, v, stream, num_cus, info, p);
+    return db ? launch_mel_w12_varlen(a, v, stream, num_cus, info, p, *db) : launch_mel_w12_varlen(a, v, stream, num_cus, info, p);
 }
 
 // what the ragged streaming launches serve.  Always twelve waves (never twelve_waves_win): see mel_varlen_shape -- an entry's bits

@@ -7,6 +7,7 @@
 // for the statistics (full rate on gfx950; it keeps the result within an ulp of the f64 oracle for 6 000-row matrices too):
 // cmvn sums chunks of rows per thread and normalises per element (two launches, no atomics: bit-reproducible); cmvnw slides
 // its window sums over a chunk of rows per thread (O(rows + win) loads per column chunk instead of O(rows * win)).
+#include "ss_device.h"
 #include "ss_internal.h"
 #include "speechsauce_amd.h"
 
@@ -55,14 +56,7 @@ __global__ __launch_bounds__(256) void ss_ln_kernel(float *__restrict__ x, unsig
     if (g < n) x[g] = logf(x[g]);
 }
 
-// floats as ordered integers, so that atomicMax on an int finds the largest float (negative values included)
-__device__ __forceinline__ int float_key(float v)
-{
-    const int b = __float_as_int(v);
-    return b >= 0 ? b : b ^ 0x7fffffff;
-}
-__device__ __forceinline__ float key_float(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
-
+// (float_key / key_float, the ordered-integer keys of the maxima: ss_device.h)
 // 10 log10(max(amin, S)) - 10 log10(max(amin, ref)); the block maxima go to one word for the top_db clamp
 __global__ __launch_bounds__(256) void ss_power_to_db_kernel(const float *__restrict__ s, float *__restrict__ out, unsigned long long n, float amin,
                                                             float ref_db, int *__restrict__ max_key)
@@ -432,6 +426,61 @@ __global__ __launch_bounds__(256) void ss_db_floor_packed_kernel(float *__restri
         dst[g] = fmaxf(dst[g], floor_db);
 }
 
+// ---- the dB step of the log-mel calls (ss_log_mel_spectrogram*): per-clip maxima in max_key (DbArgs, ss_device.h) ----
+// A clip's block: `seg` elements from element blockIdx.x * seg (equal-length clips, no table), or the [M x R_b] block of clip
+// blockIdx.x of a packed call -- only where the clip passes the mel kernels' own table check (varrows_clip): what they skipped
+// stays as it is.
+struct ClipBlock {
+    unsigned long long first, n;  // n = 0: nothing to do
+};
+__device__ __forceinline__ ClipBlock equal_block(unsigned long long seg) { return {blockIdx.x * seg, seg}; }
+__device__ __forceinline__ ClipBlock varrows_block(const VarRowsArgs &v, unsigned cols)
+{
+    const VarRowClip c = varrows_clip(v, blockIdx.x);
+    if (!c.ok) return {0, 0};
+    return {static_cast<unsigned long long>(c.r0) * cols, static_cast<unsigned long long>(c.R) * cols};
+}
+// the floor of ss_db_floor_packed_kernel over such a block
+__device__ __forceinline__ void db_floor_block(float *__restrict__ out, const ClipBlock b, float top_db, const int *__restrict__ max_key)
+{
+    float *dst = out + b.first;
+    const float floor_db = key_float(max_key[blockIdx.x]) - top_db;
+    for (unsigned long long g = static_cast<unsigned long long>(blockIdx.y) * 256 + threadIdx.x; g < b.n; g += static_cast<unsigned long long>(gridDim.y) * 256)
+        dst[g] = fmaxf(dst[g], floor_db);
+}
+__global__ __launch_bounds__(256) void ss_db_floor_equal_kernel(float *__restrict__ out, unsigned long long seg, float top_db,
+                                                               const int *__restrict__ max_key)
+{
+    db_floor_block(out, equal_block(seg), top_db, max_key);
+}
+__global__ __launch_bounds__(256) void ss_db_floor_varrows_kernel(float *__restrict__ out, const VarRowsArgs v, unsigned cols, float top_db,
+                                                                 const int *__restrict__ max_key)
+{
+    db_floor_block(out, varrows_block(v, cols), top_db, max_key);
+}
+// the maxima's start value in every word: 0x80808080, below the key of every finite float (what ss_power_to_db_packed_device's memset
+// writes) -- as a kernel, so that a captured call is a chain of kernel nodes only
+__global__ __launch_bounds__(256) void ss_db_keys_init_kernel(int *__restrict__ max_key, unsigned n)
+{
+    const unsigned g = blockIdx.x * 256u + threadIdx.x;
+    if (g < n) max_key[g] = static_cast<int>(0x80808080u);
+}
+// ss_power_to_db_packed_kernel's pass over equal-length clips, in place (behind a mel kernel that has no dB build)
+__global__ __launch_bounds__(256) void ss_power_to_db_equal_kernel(float *x, unsigned long long seg, float amin, float ref_db, int *__restrict__ max_key)
+{
+    float *dst = x + blockIdx.x * seg;
+    float mx = -INFINITY;
+    for (unsigned long long g = static_cast<unsigned long long>(blockIdx.y) * 256 + threadIdx.x; g < seg; g += static_cast<unsigned long long>(gridDim.y) * 256) {
+        const float db = power_db(dst[g], amin, ref_db);
+        dst[g] = db;
+        mx = fmaxf(mx, db);
+    }
+    if (max_key) {
+        for (int m = 1; m < 64; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+        if ((threadIdx.x & 63) == 0 && mx > -INFINITY) atomicMax(max_key + blockIdx.x, float_key(mx));
+    }
+}
+
 int hip_err(hipError_t e, const char *what) { return fail(SS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 
 unsigned blocks_for(unsigned long long n) { return static_cast<unsigned>((n + 255) / 256); }
@@ -526,6 +575,35 @@ int via_device_packed(const float *in, const int64_t *off, size_t n_clips, size_
 }
 
 }  // namespace
+
+// the dB step's launches (ss_device.h)
+hipError_t launch_db_keys_init(int *max_key, size_t clips, hipStream_t stream)
+{
+    if (clips == 0) return hipSuccess;
+    hipLaunchKernelGGL(ss_db_keys_init_kernel, dim3(blocks_for(clips)), dim3(256), 0, stream, max_key, static_cast<unsigned>(clips));
+    return hipGetLastError();
+}
+hipError_t launch_db_floor_equal(float *out, size_t clips, size_t seg, float top_db, const int *max_key, hipStream_t stream)
+{
+    if (clips == 0 || seg == 0) return hipSuccess;
+    const dim3 grid(static_cast<unsigned>(clips), packed_split(clips, (seg + 1023) / 1024));
+    hipLaunchKernelGGL(ss_db_floor_equal_kernel, grid, dim3(256), 0, stream, out, static_cast<unsigned long long>(seg), top_db, max_key);
+    return hipGetLastError();
+}
+hipError_t launch_db_floor_varrows(float *out, const VarRowsArgs &v, size_t cols, float top_db, const int *max_key, hipStream_t stream)
+{
+    if (v.n_clips == 0 || v.total_rows == 0) return hipSuccess;
+    const dim3 grid(v.n_clips, packed_split(v.n_clips, (v.total_rows * cols + 1023) / 1024));
+    hipLaunchKernelGGL(ss_db_floor_varrows_kernel, grid, dim3(256), 0, stream, out, v, static_cast<unsigned>(cols), top_db, max_key);
+    return hipGetLastError();
+}
+hipError_t launch_power_to_db_equal(float *x, size_t clips, size_t seg, const DbArgs &db, hipStream_t stream)
+{
+    if (clips == 0 || seg == 0) return hipSuccess;
+    const dim3 grid(static_cast<unsigned>(clips), packed_split(clips, (seg + 1023) / 1024));
+    hipLaunchKernelGGL(ss_power_to_db_equal_kernel, grid, dim3(256), 0, stream, x, static_cast<unsigned long long>(seg), db.amin, db.ref_db, db.max_key);
+    return hipGetLastError();
+}
 
 }  // namespace ss
 

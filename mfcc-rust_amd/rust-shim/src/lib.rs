@@ -122,6 +122,24 @@ extern "C" {
                                      out: *mut f32) -> c_int;
     fn ss_stft_packed_i16(cfg: *const SsConfig, x: *const i16, n_clips: usize, sample_offsets: *const i64, scale: f32,
                           out: *mut f32) -> c_int;
+    fn ss_log_mel_spectrogram(cfg: *const SsConfig, x: *const f32, channels: usize, n: usize, ref_: f32, amin: f32, top_db: f32,
+                              out: *mut f32) -> c_int;
+    fn ss_log_mel_spectrogram_device(cfg: *const SsConfig, d_x: *const f32, channels: usize, n: usize, ld: usize, ref_: f32, amin: f32,
+                                     top_db: f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_log_mel_spectrogram_i16(cfg: *const SsConfig, x: *const i16, channels: usize, n: usize, scale: f32, ref_: f32, amin: f32,
+                                  top_db: f32, out: *mut f32) -> c_int;
+    fn ss_log_mel_spectrogram_i16_device(cfg: *const SsConfig, d_x: *const i16, channels: usize, n: usize, ld: usize, scale: f32,
+                                         ref_: f32, amin: f32, top_db: f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_log_mel_spectrogram_packed(cfg: *const SsConfig, x: *const f32, n_clips: usize, sample_offsets: *const i64, ref_: f32,
+                                     amin: f32, top_db: f32, out: *mut f32) -> c_int;
+    fn ss_log_mel_spectrogram_packed_device(cfg: *const SsConfig, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64,
+                                            d_row_offsets: *const i64, total_rows: usize, ref_: f32, amin: f32, top_db: f32,
+                                            d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_log_mel_spectrogram_packed_i16(cfg: *const SsConfig, x: *const i16, n_clips: usize, sample_offsets: *const i64, scale: f32,
+                                         ref_: f32, amin: f32, top_db: f32, out: *mut f32) -> c_int;
+    fn ss_log_mel_spectrogram_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64,
+                                                scale: f32, d_row_offsets: *const i64, total_rows: usize, ref_: f32, amin: f32,
+                                                top_db: f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
     fn ss_mel_spectrogram_stream_packed_i16_device(cfg: *const SsConfig, d_x: *const i16, n_active: usize, d_sample_offsets: *const i64,
                                                    d_row_offsets: *const i64, total_rows: usize, d_slots: *const i32, pool_streams: usize,
                                                    scale: f32, d_pool: *mut f32, d_out: *mut f32, stream: *mut c_void) -> c_int;
@@ -640,6 +658,97 @@ pub fn try_mel_spectrogram_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offs
     }
     check(unsafe { ss_mel_spectrogram_packed_i16(cfg.raw(), x.as_ptr(), sample_offsets.len() - 1, sample_offsets.as_ptr(), scale,
                                                  out.as_mut_ptr()) })
+}
+
+/// What the log-mel calls add to their mel counterparts: librosa's `power_to_db` arguments.  `top_db < 0.0` switches the floor off.
+#[derive(Clone, Copy, Debug)]
+pub struct DbScale {
+    pub ref_: f32,
+    pub amin: f32,
+    pub top_db: f32,
+}
+
+impl Default for DbScale {
+    fn default() -> Self {
+        DbScale { ref_: 1.0, amin: 1e-10, top_db: 80.0 }
+    }
+}
+
+/// Log-mel spectrogram (`ss_log_mel_spectrogram_device`): `mel_spectrogram` in decibels, converted in the mel kernel's epilogue.  Per
+/// clip (channel) bit for bit the mel call followed by `ss_power_to_db_packed_device` with every clip as its own segment: the `top_db`
+/// floor is the clip's own maximum - `top_db` -- not the one maximum `ss_power_to_db_device` takes over a multi-channel block.
+/// `d_out`: `[channels x num_filters x rows]`.
+/// # Safety
+/// Every pointer is a device allocation of the size the header states, on the device the config was created on.
+pub unsafe fn log_mel_spectrogram_device(cfg: &SpeechConfig, d_x: *const f32, channels: usize, n: usize, ld: usize, db: DbScale,
+                                         d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_log_mel_spectrogram_device(cfg.raw(), d_x, channels, n, ld, db.ref_, db.amin, db.top_db, d_out, stream))
+}
+
+/// `log_mel_spectrogram_device` fed signed 16-bit PCM (`sample = pcm as f32 * scale`, `scale` a power of two).
+/// # Safety
+/// As `log_mel_spectrogram_device`.
+pub unsafe fn log_mel_spectrogram_i16_device(cfg: &SpeechConfig, d_x: *const i16, channels: usize, n: usize, ld: usize, scale: f32,
+                                             db: DbScale, d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_log_mel_spectrogram_i16_device(cfg.raw(), d_x, channels, n, ld, scale, db.ref_, db.amin, db.top_db, d_out, stream))
+}
+
+/// Packed variable-length clips (`ss_log_mel_spectrogram_packed_device`): the layout of `ss_mel_spectrogram_packed_device`, every clip's
+/// block in decibels and floored at its own maximum - `top_db`; the tables are device arrays.
+/// # Safety
+/// As `log_mel_spectrogram_device`.
+pub unsafe fn log_mel_spectrogram_packed_device(cfg: &SpeechConfig, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64,
+                                                d_row_offsets: *const i64, total_rows: usize, db: DbScale, d_out: *mut f32,
+                                                stream: *mut c_void) -> Result<(), Error> {
+    check(ss_log_mel_spectrogram_packed_device(cfg.raw(), d_x, n_clips, d_sample_offsets, d_row_offsets, total_rows, db.ref_, db.amin,
+                                               db.top_db, d_out, stream))
+}
+
+/// `log_mel_spectrogram_packed_device` fed signed 16-bit PCM.
+/// # Safety
+/// As `log_mel_spectrogram_device`.
+pub unsafe fn log_mel_spectrogram_packed_i16_device(cfg: &SpeechConfig, d_x: *const i16, n_clips: usize, d_sample_offsets: *const i64,
+                                                    scale: f32, d_row_offsets: *const i64, total_rows: usize, db: DbScale,
+                                                    d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_log_mel_spectrogram_packed_i16_device(cfg.raw(), d_x, n_clips, d_sample_offsets, scale, d_row_offsets, total_rows, db.ref_,
+                                                   db.amin, db.top_db, d_out, stream))
+}
+
+/// Host-pointer forms of the log-mel calls.  `x` holds `channels` rows of `n` samples; `out` is `[channels x num_filters x rows]`.
+pub fn try_log_mel_spectrogram(cfg: &SpeechConfig, x: &[f32], channels: usize, n: usize, db: DbScale, out: &mut [f32]) -> Result<(), Error> {
+    if x.len() < channels * n {
+        return Err(Error { status: SS_ERR_ARG, detail: "x is shorter than channels rows of n samples".to_string() });
+    }
+    check(unsafe { ss_log_mel_spectrogram(cfg.raw(), x.as_ptr(), channels, n, db.ref_, db.amin, db.top_db, out.as_mut_ptr()) })
+}
+
+/// `try_log_mel_spectrogram` from an int16 host buffer.
+pub fn try_log_mel_spectrogram_i16(cfg: &SpeechConfig, x: &[i16], channels: usize, n: usize, scale: f32, db: DbScale, out: &mut [f32])
+                                   -> Result<(), Error> {
+    if x.len() < channels * n {
+        return Err(Error { status: SS_ERR_ARG, detail: "x is shorter than channels rows of n samples".to_string() });
+    }
+    check(unsafe { ss_log_mel_spectrogram_i16(cfg.raw(), x.as_ptr(), channels, n, scale, db.ref_, db.amin, db.top_db, out.as_mut_ptr()) })
+}
+
+/// Packed clips from a float host buffer: `sample_offsets` holds `n_clips + 1` offsets in samples, `out` the clips' blocks end to end.
+pub fn try_log_mel_spectrogram_packed(cfg: &SpeechConfig, x: &[f32], sample_offsets: &[i64], db: DbScale, out: &mut [f32])
+                                      -> Result<(), Error> {
+    if sample_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have n_clips + 1 entries".to_string() });
+    }
+    check(unsafe { ss_log_mel_spectrogram_packed(cfg.raw(), x.as_ptr(), sample_offsets.len() - 1, sample_offsets.as_ptr(), db.ref_, db.amin,
+                                                 db.top_db, out.as_mut_ptr()) })
+}
+
+/// `try_log_mel_spectrogram_packed` from an int16 host buffer.
+pub fn try_log_mel_spectrogram_packed_i16(cfg: &SpeechConfig, x: &[i16], sample_offsets: &[i64], scale: f32, db: DbScale, out: &mut [f32])
+                                          -> Result<(), Error> {
+    if sample_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have n_clips + 1 entries".to_string() });
+    }
+    check(unsafe { ss_log_mel_spectrogram_packed_i16(cfg.raw(), x.as_ptr(), sample_offsets.len() - 1, sample_offsets.as_ptr(), scale,
+                                                     db.ref_, db.amin, db.top_db, out.as_mut_ptr()) })
 }
 
 /// The stft form of `try_mel_spectrogram_packed_i16`.

@@ -23,7 +23,7 @@ from ._lib import SpeechSauceError, SsParams, make_params  # noqa: F401
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
            "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "mel_spectrogram_packed",
-           "mel_spectrogram_list", "stft_packed", "cmvn_packed", "cmvnw_packed", "power_to_db_packed", "lmfe_packed",
+           "mel_spectrogram_list", "log_mel_spectrogram", "log_mel_spectrogram_packed", "log_mel_spectrogram_list", "stft_packed", "cmvn_packed", "cmvnw_packed", "power_to_db_packed", "lmfe_packed",
            "MelSpectrogramStream", "StftStream",
            "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool",
            "SpeechConfig", "SpeechSauceError"]
@@ -229,11 +229,12 @@ def _internal_mfe_batch(signal, config: SpeechConfig, scale=None):
     return feat, en
 
 
-def _internal_mel_spectrogram(signal, config: SpeechConfig, scale=None):
+def _internal_mel_spectrogram(signal, config: SpeechConfig, scale=None, db=None):
     """1-D -> [n_mels, rows]; 2-D [C, L] -> [C, n_mels, rows] (py-speechsauce/src/lib.rs:179-204); scale: the signal is int16
-    PCM, sample = int16 * scale (the ``_i16`` entry points)."""
+    PCM, sample = int16 * scale (the ``_i16`` entry points); db: [ref, amin, top_db] of the ``ss_log_mel_spectrogram*`` forms."""
     lib = _lib.lib()
     i16, sc = ("", []) if scale is None else ("_i16", [scale])
+    name, dbargs = ("ss_mel_spectrogram", []) if db is None else ("ss_log_mel_spectrogram", db)
     one_d = signal.ndim == 1
     sig2 = signal[None, :] if one_d else signal
     ch, L = sig2.shape
@@ -245,12 +246,12 @@ def _internal_mel_spectrogram(signal, config: SpeechConfig, scale=None):
         x = sig2 if sig2.stride(1) == 1 else sig2.contiguous()
         out = torch.empty((ch, M, R), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(getattr(lib, f"ss_mel_spectrogram{i16}_device")(config.handle, x.data_ptr(), ch, L, x.stride(0) if ch > 1 else L, *sc,
-                                                                       out.data_ptr(), _stream_ptr()))
+            _lib.check(getattr(lib, f"{name}{i16}_device")(config.handle, x.data_ptr(), ch, L, x.stride(0) if ch > 1 else L, *sc, *dbargs,
+                                                           out.data_ptr(), _stream_ptr()))
     else:
         x = np.ascontiguousarray(sig2)
         out = np.empty((ch, M, R), dtype=np.float32)
-        _lib.check(getattr(lib, f"ss_mel_spectrogram{i16}")(config.handle, x.ctypes.data, ch, L, *sc, out.ctypes.data))
+        _lib.check(getattr(lib, f"{name}{i16}")(config.handle, x.ctypes.data, ch, L, *sc, *dbargs, out.ctypes.data))
     return out[0] if one_d else out
 
 
@@ -493,13 +494,14 @@ def _row_offsets(config: SpeechConfig, so):
     return ro
 
 
-def _internal_stft_packed(signal, so, config: SpeechConfig, stft: bool, scale=None):
+def _internal_stft_packed(signal, so, config: SpeechConfig, stft: bool, scale=None, db=None):
     """signal [N] packed clips, sample offsets so -> (flat float32 block, row_offsets [n + 1]): mel [num_filters * sum R_b] or stft
     [sum R_b, F, 2].  The row offsets are a device tensor where the signal is one.  scale: the signal is int16 PCM (the ``_i16``
-    entry points)."""
+    entry points); db: [ref, amin, top_db] of the ``ss_log_mel_spectrogram_packed*`` forms (mel only)."""
     lib = _lib.lib()
     i16, sc = ("", []) if scale is None else ("_i16", [scale])
-    name = "ss_stft_packed" if stft else "ss_mel_spectrogram_packed"
+    name = "ss_stft_packed" if stft else ("ss_mel_spectrogram_packed" if db is None else "ss_log_mel_spectrogram_packed")
+    dbargs = [] if db is None else db
     ro = _row_offsets(config, so)
     n, rows = so.size - 1, int(ro[-1])
     F = config.params.fft_points // 2 + 1
@@ -511,52 +513,54 @@ def _internal_stft_packed(signal, so, config: SpeechConfig, stft: bool, scale=No
         with torch.cuda.device(x.device):
             dso, dro = torch.from_numpy(so).to(x.device), torch.from_numpy(ro).to(x.device)
             out = torch.empty(shape, dtype=torch.float32, device=x.device)
-            _lib.check(getattr(lib, f"{name}{i16}_device")(config.handle, x.data_ptr(), n, dso.data_ptr(), *sc, dro.data_ptr(), rows,
+            _lib.check(getattr(lib, f"{name}{i16}_device")(config.handle, x.data_ptr(), n, dso.data_ptr(), *sc, dro.data_ptr(), rows, *dbargs,
                                                            out.data_ptr(), _stream_ptr()))
         return out, dro
     x = np.ascontiguousarray(signal)
     out = np.empty(shape, dtype=np.float32)
-    _lib.check(getattr(lib, f"{name}{i16}")(config.handle, x.ctypes.data, n, so.ctypes.data, *sc, out.ctypes.data))
+    _lib.check(getattr(lib, f"{name}{i16}")(config.handle, x.ctypes.data, n, so.ctypes.data, *sc, *dbargs, out.ctypes.data))
     return out, ro
 
 
 def mel_spectrogram_packed(signal, lengths, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13,
                            num_filters=40, fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, pcm_scale=None,
-                           **switches):
+                           _db=None, _what="mel_spectrogram_packed", **switches):
     """Mel spectrogram of clips of different lengths packed end to end in one 1-D float32 signal (clip b = the lengths[b]
     samples after the clips before it) -> (out, row_offsets [n + 1] int64).  ``out`` is the flat float32 block of
     num_filters * sum R_b values: clip b's [num_filters, R_b] block, what ``mel_spectrogram`` returns for that clip alone, starts
     at num_filters * row_offsets[b].  One launch for all clips.  ``pcm_scale``: the packed signal is int16 PCM (see
     ``mel_spectrogram``)."""
-    sig, scale = _require_signal(signal, (1,), "mel_spectrogram_packed", pcm_scale)
-    so = _sample_offsets(lengths, sig.shape[0], "mel_spectrogram_packed")
+    sig, scale = _require_signal(signal, (1,), _what, pcm_scale)
+    so = _sample_offsets(lengths, sig.shape[0], _what)
     config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
                   low_frequency, high_frequency, dc_elimination, switches, sig)
-    return _internal_stft_packed(sig, so, config, False, scale)
+    return _internal_stft_packed(sig, so, config, False, scale, _db)
 
 
 def mel_spectrogram_list(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
-                         fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, pcm_scale=None, **switches):
+                         fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, pcm_scale=None, _db=None,
+                         _what="mel_spectrogram_list", **switches):
     """A list of 1-D float32 clips of any lengths -> the list of their [num_filters, R_b] mel spectrograms (views of one block):
     the clips are packed once and served by one mel_spectrogram_packed call.  ``pcm_scale``: the clips are int16 PCM (see
     ``mel_spectrogram``)."""
-    sigs = [_require_signal(x, (1,), "mel_spectrogram_list", pcm_scale)[0] for x in signals]
+    sigs = [_require_signal(x, (1,), _what, pcm_scale)[0] for x in signals]
     if not sigs:
         return []
     on_device = [_is_torch(x) for x in sigs]  # (_require_f32 turns host tensors into arrays)
     if any(on_device) and not all(on_device):
-        raise ValueError("mel_spectrogram_list: the clips of one call must all be device tensors or all host arrays")
+        raise ValueError(f"{_what}: the clips of one call must all be device tensors or all host arrays")
     if all(on_device):
         import torch
 
         if any(x.device != sigs[0].device for x in sigs):
-            raise ValueError("mel_spectrogram_list: the clips of one call must live on one device")
+            raise ValueError(f"{_what}: the clips of one call must live on one device")
         packed = torch.cat(sigs)
     else:
         packed = np.concatenate(sigs)
     lengths = [int(x.shape[0]) for x in sigs]
     out, ro = mel_spectrogram_packed(packed, lengths, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters,
-                                     fft_length, low_frequency, high_frequency, dc_elimination, pcm_scale, **switches)
+                                     fft_length, low_frequency, high_frequency, dc_elimination, pcm_scale, _db,
+                                     "mel_spectrogram_packed" if _db is None else "log_mel_spectrogram_packed", **switches)
     ro = ro.tolist()
     M = int(num_filters)
     return [out[M * ro[b]:M * ro[b + 1]].reshape(M, ro[b + 1] - ro[b]) for b in range(len(sigs))]
@@ -696,6 +700,56 @@ def mel_spectrogram(signal, sampling_frequency, frame_length=0.020, frame_stride
     config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
                   low_frequency, high_frequency, dc_elimination, switches, sig)
     return _internal_mel_spectrogram(sig, config, scale)
+
+
+def _db_args(what, ref, amin, top_db):
+    """[ref, amin, top_db] of the ``ss_log_mel_spectrogram*`` calls; the argument rules of ``power_to_db`` (top_db None: no floor,
+    -1 in the ABI), checked before a device is touched."""
+    if top_db is not None and top_db < 0:
+        raise ValueError(f"{what}: top_db must be non-negative")
+    if not float(amin) > 0:
+        raise ValueError(f"{what}: amin must be strictly positive")
+    if float(ref) != float(ref):
+        raise ValueError(f"{what}: ref must not be NaN")
+    return [float(ref), float(amin), -1.0 if top_db is None else float(top_db)]
+
+
+def log_mel_spectrogram(signal, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13,
+                        num_filters=40, fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True,
+                        ref=1.0, amin=1e-10, top_db=80.0, pcm_scale=None, **switches):
+    """Log-mel spectrogram of a 1-D or 2-D float32 signal -> (..., n_mels, time) in decibels: ``mel_spectrogram`` with librosa's
+    ``power_to_db`` applied PER CLIP (channel) in the mel kernel's epilogue (``ss_log_mel_spectrogram*``).  Bit for bit
+    ``power_to_db_packed(mel_spectrogram(...))`` with every clip as its own segment: the ``top_db`` floor is each clip's own
+    maximum - top_db (``None``: no floor), and the trailing zero rows come out as 10 log10(amin) - ref_db.  This is not
+    ``power_to_db`` of a multi-channel block, which takes one maximum over the whole block.  ``ref`` / ``amin`` / ``top_db`` follow
+    ``power_to_db``'s rules; ``pcm_scale``: the signal is int16 PCM (see ``mel_spectrogram``).  numpy in -> numpy out; a ROCm
+    tensor stays on the device (current stream)."""
+    db = _db_args("log_mel_spectrogram", ref, amin, top_db)
+    sig, scale = _require_signal(signal, (1, 2), "log_mel_spectrogram", pcm_scale)
+    config = _cfg(sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
+                  low_frequency, high_frequency, dc_elimination, switches, sig)
+    return _internal_mel_spectrogram(sig, config, scale, db)
+
+
+def log_mel_spectrogram_packed(signal, lengths, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13,
+                               num_filters=40, fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True,
+                               ref=1.0, amin=1e-10, top_db=80.0, pcm_scale=None, **switches):
+    """``log_mel_spectrogram`` of packed clips -> (out, row_offsets), the layout of ``mel_spectrogram_packed``: clip b's
+    [num_filters, R_b] block in decibels, floored at its own maximum - top_db, starts at num_filters * row_offsets[b].  Bit for bit
+    ``power_to_db_packed(out, row_offsets, cols=num_filters, ...)`` of ``mel_spectrogram_packed``'s result, without that pass."""
+    db = _db_args("log_mel_spectrogram_packed", ref, amin, top_db)
+    return mel_spectrogram_packed(signal, lengths, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
+                                  low_frequency, high_frequency, dc_elimination, pcm_scale, db, "log_mel_spectrogram_packed", **switches)
+
+
+def log_mel_spectrogram_list(signals, sampling_frequency, frame_length=0.020, frame_stride=0.01, num_cepstral=13, num_filters=40,
+                             fft_length=512, low_frequency=0, high_frequency=None, dc_elimination=True, ref=1.0, amin=1e-10,
+                             top_db=80.0, pcm_scale=None, **switches):
+    """A list of 1-D clips of any lengths -> the list of their [num_filters, R_b] log-mel spectrograms (views of one block): the
+    clips are packed once and served by one ``log_mel_spectrogram_packed`` call."""
+    db = _db_args("log_mel_spectrogram_list", ref, amin, top_db)
+    return mel_spectrogram_list(signals, sampling_frequency, frame_length, frame_stride, num_cepstral, num_filters, fft_length,
+                                low_frequency, high_frequency, dc_elimination, pcm_scale, db, "log_mel_spectrogram_list", **switches)
 
 
 # ---- stage outputs the reference exposes as pub fns: processing::{stack_frames, power_spectrum}, functions::{stft1, stft2} ----

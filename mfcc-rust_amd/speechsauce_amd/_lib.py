@@ -148,6 +148,17 @@ PROTOTYPES = {
     "ss_stft_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
     "ss_mel_spectrogram_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, _fp]),
     "ss_stft_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, _fp]),
+    "ss_log_mel_spectrogram": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_float, _fp]),
+    "ss_log_mel_spectrogram_device": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_float, _fp, C.c_void_p]),
+    "ss_log_mel_spectrogram_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, _fp]),
+    "ss_log_mel_spectrogram_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_float,
+                                                    C.c_float, _fp, C.c_void_p]),
+    "ss_log_mel_spectrogram_packed": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, C.c_float, C.c_float, C.c_float, _fp]),
+    "ss_log_mel_spectrogram_packed_device": (C.c_int, [_cfg, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float,
+                                                       C.c_float, _fp, C.c_void_p]),
+    "ss_log_mel_spectrogram_packed_i16": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, _fp]),
+    "ss_log_mel_spectrogram_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t,
+                                                           C.c_float, C.c_float, C.c_float, _fp, C.c_void_p]),
     "ss_mel_spectrogram_stream_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                               C.c_size_t, C.c_float, _fp, _fp, C.c_void_p]),
     "ss_stft_stream_packed_i16_device": (C.c_int, [_cfg, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
