@@ -727,6 +727,57 @@ int ss_power_to_db_packed_device(const float *d_s, size_t n_clips, const int64_t
 int ss_lmfe_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
                           const int64_t *d_frame_offsets, size_t total_frames, float *d_feat, float *d_energy, void *stream);
 
+/* ---- causal sliding-window CMVN over a pool of stream states (the causal counterpart of processing::cmvnw, processing.rs:315-371) ----
+ * The rows ss_mfcc_stream_packed* / ss_mfe_stream_packed* return are unnormalised; ss_cmvn needs the whole clip and ss_cmvnw centres
+ * its window on the row, which a live stream cannot give.  These calls normalise every row over the TRAILING window of its own
+ * stream, with the window carried from tick to tick in a pool of the same shape as the frame pool's.
+ *   Definition (the reference crate has no causal variant: this is the specification): for one stream with rows x[0], x[1], ...
+ *   counted since its reset, win = win_size >= 1 (any parity: a causal window has no centre), per column
+ *     n_t = min(t + 1, win),  W_t = rows x[t - n_t + 1 .. t] (the row itself is the newest member),  mean_t = sum(W_t) / n_t
+ *     out[t] = x[t] - mean_t                                    variance_normalization == 0
+ *     out[t] = (x[t] - mean_t) / (std_t + 2^-30)                variance_normalization != 0
+ *     std_t  = sqrt(max(sum(W_t^2) / n_t - mean_t^2, 0))        population, the eps of processing.rs:324
+ *   No padding at the start: the first rows use the rows that exist (as Kaldi's online CMVN).  win = 1 gives exact zeros; a column
+ *   that is constant over the window gives exact zeros; with variance normalisation |out| <= sqrt(n_t).
+ *   Arithmetic: both sums of every element are formed afresh in f64, oldest row first, from the f32 values -- never a running sum
+ *   carried between rows or calls -- then static_cast<float>((double(x) - mean) * inv), inv = 1 / (std + 2^-30) or 1.  So a row's
+ *   bits depend on its window's values only: not on how the stream was cut into calls, on the entry's place in the call or on its
+ *   slot.
+ *   Pool: a caller-owned block [pool_streams x L] of floats, L = ss_cmvn_stream_state_len = (win_size - 1) * cols + 1.  Floats
+ *   0 .. (win_size - 1) * cols - 1 of a row are the stream's last win_size - 1 raw rows, oldest first, right-aligned (the newest row
+ *   at the end, unused leading rows zero); the last float is the number of valid history rows, min(rows seen, win_size - 1), as a
+ *   float.  All zeros = fresh stream, zeroing a row resets it.  A count word that is not an integer in [0, win_size - 1] (NaN
+ *   included) is read as 0: garbage in the state never widens a read.
+ *   Entries: vec / out are row-major [total_rows x cols]; entry i owns rows ro[i] .. ro[i+1] of both and pool row slots[i] --
+ *   exactly the row_offsets and slots of an ss_mfcc_stream_packed* / ss_mfe_stream_packed* call, so the two calls chain on the same
+ *   device tables.  R_i = 0 is legal: no row written, the pool row untouched bit for bit.  Rows past ro[n_active] and pool rows
+ *   not named are neither read nor written.
+ *   Device form: one launch (ss_cmvn_stream_packed_kernel, one workgroup per entry, which normalises the entry's rows and then
+ *   moves its pool row on), asynchronous on `stream`, no scratch, graph-capturable as a single kernel node whose grid depends on
+ *   n_active only.
+ *   Containment: there is no config, so no error word.  An entry is skipped -- no row written, its pool row untouched -- unless
+ *   0 <= ro[i] <= ro[i+1] <= total_rows and 0 <= slots[i] < pool_streams.  Whatever the tables and the pool's count words hold,
+ *   nothing is read or written outside [0, total_rows) x cols of vec / out and [0, pool_streams) x L of the pool.  Duplicate slots
+ *   in a device-form call are a caller error that is NOT detected: the rows and pool rows of those entries are unspecified;
+ *   everything stays inside the pool.  The host-pointer form rejects them.
+ * Arguments: n_active == 0 is SS_OK with nothing launched, also on a host without a device.  SS_ERR_ARG, decided before the device
+ * is touched, pool and out untouched: null buffers (the pool too, also where win_size == 1 and L == 1); cols == 0, win_size == 0;
+ * n_active, pool_streams, total_rows, cols or L >= 2^31, win_size > 2^24 (the count word must stay an exact float); pool_streams
+ * == 0; out overlapping vec (an in-place call is NOT offered: later rows of an entry need the raw earlier rows); the pool range
+ * overlapping vec or out.  The host-pointer form also checks the tables before it touches the device -- ro[0] != 0, a decreasing
+ * pair, a slot outside the pool, a slot named twice; ss_last_error_string() names the first bad entry -- and moves only what the
+ * call touches: vec, the tables and the n_active named pool rows up, out and those rows down; the caller's pool is written only
+ * after everything before it succeeded. */
+/* host only, no device: L = (win_size - 1) * cols + 1.  SS_ERR_ARG: cols == 0, win_size == 0, L >= 2^31, win_size > 2^24 */
+int ss_cmvn_stream_state_len(size_t cols, size_t win_size, size_t *state_len);
+/* device pointers, asynchronous on `stream`, graph-capturable: one launch whatever n_active is */
+int ss_cmvn_stream_packed_device(const float *d_vec, size_t n_active, const int64_t *d_row_offsets, size_t total_rows,
+                                 const int32_t *d_slots, size_t pool_streams, size_t cols, size_t win_size,
+                                 int variance_normalization, float *d_pool, float *d_out, void *stream);
+/* host pointers, synchronous; row_offsets / slots are host arrays; vec / out: [ro[n_active] x cols] */
+int ss_cmvn_stream_packed(const float *vec, size_t n_active, const int64_t *row_offsets, const int32_t *slots,
+                          size_t pool_streams, size_t cols, size_t win_size, int variance_normalization, float *pool, float *out);
+
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`
  * computes clips [lo, hi) of ss_shard_bounds on its own device with the *_device entry points.  The north-star's "RCCL

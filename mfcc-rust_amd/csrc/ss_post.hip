@@ -15,7 +15,11 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <cstring>
 #include <string>
+#include <unordered_set>
+#include <vector>
 
 namespace ss {
 
@@ -391,6 +395,150 @@ __global__ __launch_bounds__(256) void ss_cmvnw_packed_kernel(const float *__res
     }
 }
 
+// ---- causal sliding-window CMVN over a pool of stream states (ss_cmvn_stream_packed*) ----
+// Entry i owns rows ro[i] .. ro[i+1] of the [total_rows x cols] blocks and pool row slots[i]: L = (win - 1) * cols + 1 floats, the
+// last win - 1 raw rows of its stream (oldest first, right-aligned, zeros in front) and, in the last float, how many of them are
+// valid.  Row t of the stream is normalised over its own trailing window, rows max(t - win + 1, 0) .. t: the valid history rows,
+// then the entry's rows up to the row itself.  Both sums are formed afresh for every element, oldest row first, so an element's
+// bits depend on the window's values only -- not on how the stream was cut into calls, the entry's place in the call or its slot.
+// One workgroup per entry, one launch: the workgroup owns its pool row, normalises the entry's rows and then moves the row on.
+// Containment: an entry is skipped unless 0 <= ro[i] <= ro[i+1] <= total_rows and 0 <= slots[i] < pool_streams; a count word that
+// is not an integer in [0, win - 1] (NaN included) is read as 0, so the window never reaches in front of the pool row.
+struct StreamEntry {
+    unsigned long long row0;
+    unsigned rows;   // 0: nothing to do (no rows or a rejected entry)
+    unsigned count;  // valid history rows, 0 .. win - 1
+    float *state;    // the entry's pool row
+};
+
+__device__ __forceinline__ StreamEntry cmvn_stream_entry(const long long *__restrict__ ro, const int *__restrict__ slots, unsigned long long total_rows,
+                                                         unsigned pool_streams, float *pool, unsigned state_len, unsigned hist)
+{
+    const long long lo = ro[blockIdx.x], hi = ro[blockIdx.x + 1];
+    const int slot = slots[blockIdx.x];
+    StreamEntry e{0, 0, 0, nullptr};
+    if (lo >= 0 && lo < hi && static_cast<unsigned long long>(hi) <= total_rows && slot >= 0 && static_cast<unsigned>(slot) < pool_streams) {
+        e.row0 = static_cast<unsigned long long>(lo);
+        e.rows = static_cast<unsigned>(hi - lo);  // total_rows < 2^31: the row count fits
+        e.state = pool + static_cast<size_t>(slot) * state_len;
+        const float cw = e.state[state_len - 1];
+        if (cw >= 0.0f && cw <= static_cast<float>(hist) && cw == floorf(cw)) e.count = static_cast<unsigned>(cw);  // hist < 2^24: exact
+    }
+    return e;
+}
+
+constexpr unsigned kStreamMove = 4;      // pool-row floats a thread moves per step of the advance in global memory
+constexpr unsigned kStreamTile = 32;     // columns staged in LDS at a time, as kCmvnTile
+constexpr unsigned kStreamLds = 10240;   // floats of LDS (40 KiB: four workgroups per CU): win = 301 with up to 20 new rows per tile
+
+// the two sums of one element over n values `stride` floats apart, oldest first (fma written out: the same bits from every caller)
+__device__ __forceinline__ void stream_window_sums(const float *p, unsigned n, size_t stride, double &s1, double &s2)
+{
+#pragma unroll 8
+    for (unsigned j = 0; j < n; ++j, p += stride) {
+        const double v = static_cast<double>(*p);
+        s1 += v;
+        s2 = fma(v, v, s2);
+    }
+}
+
+// the tail of ss_cmvn_packed_kernel on the sums of a window of n rows
+__device__ __forceinline__ float stream_normalise(float x, double s1, double s2, unsigned n, int variance)
+{
+    const double mean = s1 / n;
+    double inv = 1.0;
+    if (variance) {
+        const double var = fmax(fma(-mean, mean, s2 / n), 0.0);
+        inv = 1.0 / (sqrt(var) + kEps30);
+    }
+    return static_cast<float>((static_cast<double>(x) - mean) * inv);
+}
+
+__global__ __launch_bounds__(256) void ss_cmvn_stream_packed_kernel(const float *__restrict__ x, const long long *__restrict__ ro,
+                                                                   const int *__restrict__ slots, float *__restrict__ out, float *pool,
+                                                                   unsigned long long total_rows, unsigned pool_streams, unsigned cols,
+                                                                   unsigned win, int variance)
+{
+    __shared__ float tile[kStreamLds];
+    const unsigned hist = win - 1, state_len = hist * cols + 1;
+    const StreamEntry e = cmvn_stream_entry(ro, slots, total_rows, pool_streams, pool, state_len, hist);
+    if (e.rows == 0) return;  // the whole workgroup: the pool row stays as it is
+    const unsigned rows = e.rows, count = e.count;
+    const float *src = x + e.row0 * cols;
+    float *dst = out + e.row0 * cols;
+    const float *old = e.state + static_cast<size_t>(hist - count) * cols;  // the oldest valid history row
+    // The stream's rows are counted from the oldest valid history row: 0 .. count - 1 the history, count .. count + rows - 1 the
+    // entry's.  After the call the pool row holds rows count + rows - hist .. count + rows - 1 (zeros where that is below 0).
+    const long long lead = static_cast<long long>(hist) - count - rows;  // rows of zeros in front of the new pool row (<= 0: none)
+    const unsigned long long span = static_cast<unsigned long long>(count) + rows;
+    if (span * min(cols, kStreamTile) <= kStreamLds) {
+        // the usual tick: per column tile the history and the new rows go to LDS once, every element walks its window there, and
+        // the tile's share of the new pool row is written from LDS (nothing of the pool row is read after it was written)
+        for (unsigned c0 = 0; c0 < cols; c0 += kStreamTile) {
+            const unsigned ct = min(kStreamTile, cols - c0);
+            const unsigned staged = static_cast<unsigned>(span) * ct;
+            for (unsigned i = threadIdx.x; i < staged; i += 256) {
+                const unsigned j = i / ct, c = i - j * ct;
+                tile[i] = j < count ? old[static_cast<size_t>(j) * cols + c0 + c] : src[static_cast<size_t>(j - count) * cols + c0 + c];
+            }
+            __syncthreads();
+            for (unsigned k = threadIdx.x; k < rows * ct; k += 256) {  // task = (row, column), columns fastest
+                const unsigned t = k / ct, c = k - t * ct;
+                const unsigned n = min(count + t + 1, win);  // rows in the window, the row itself the newest
+                double s1 = 0.0, s2 = 0.0;
+                stream_window_sums(tile + (count + t + 1 - n) * ct + c, n, ct, s1, s2);
+                dst[static_cast<size_t>(t) * cols + c0 + c] = stream_normalise(tile[(count + t) * ct + c], s1, s2, n, variance);
+            }
+            for (unsigned i = threadIdx.x; i < hist * ct; i += 256) {
+                const unsigned r = i / ct, c = i - r * ct;
+                const long long j = static_cast<long long>(r) - lead;
+                e.state[static_cast<size_t>(r) * cols + c0 + c] = j >= 0 ? tile[static_cast<unsigned>(j) * ct + c] : 0.0f;
+            }
+            __syncthreads();  // the next column tile overwrites the staged rows
+        }
+    } else {
+        // a long catch-up entry or a window too large for LDS: the same walk, in the same order, in global memory
+        const unsigned long long tasks = static_cast<unsigned long long>(rows) * cols;
+        for (unsigned long long k = threadIdx.x; k < tasks; k += 256) {
+            const unsigned t = static_cast<unsigned>(k / cols);
+            const unsigned c = static_cast<unsigned>(k - static_cast<unsigned long long>(t) * cols);
+            const unsigned n = min(count + t + 1, win);
+            const unsigned first = count + t + 1 - n;   // the window's oldest row
+            const unsigned h0 = min(first, count);      // history rows h0 .. count - 1, then the entry's rows first - h0 .. t
+            double s1 = 0.0, s2 = 0.0;
+            stream_window_sums(old + static_cast<size_t>(h0) * cols + c, count - h0, cols, s1, s2);
+            stream_window_sums(src + static_cast<size_t>(first - h0) * cols + c, n - (count - h0), cols, s1, s2);
+            dst[k] = stream_normalise(src[k], s1, s2, n, variance);
+        }
+        // A history row moves towards the front of the pool row it is read from, so the row is rewritten in ascending steps of
+        // 256 * kStreamMove floats, every step read in full before it is written: a later step reads only what lies behind
+        // everything written so far.
+        const unsigned long long hn = static_cast<unsigned long long>(hist) * cols;
+        for (unsigned long long base = 0; base < hn; base += 256 * kStreamMove) {
+            float v[kStreamMove];
+#pragma unroll
+            for (unsigned u = 0; u < kStreamMove; ++u) {
+                const unsigned long long at = base + u * 256 + threadIdx.x;
+                v[u] = 0.0f;
+                if (at < hn) {
+                    const long long j = static_cast<long long>(at / cols) - lead;
+                    const unsigned c = static_cast<unsigned>(at % cols);
+                    if (j >= static_cast<long long>(count)) v[u] = src[static_cast<size_t>(j - count) * cols + c];
+                    else if (j >= 0) v[u] = old[static_cast<size_t>(j) * cols + c];
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (unsigned u = 0; u < kStreamMove; ++u) {
+                const unsigned long long at = base + u * 256 + threadIdx.x;
+                if (at < hn) e.state[at] = v[u];
+            }
+        }
+        __syncthreads();  // (win_size == 1: no step above; the count word is read by every thread before it is written)
+    }
+    if (threadIdx.x == 0) e.state[state_len - 1] = static_cast<float>(min(count + rows, hist));
+}
+
 // power_to_db over packed clips: clip b's segment is elements cols * off[b] .. cols * off[b+1]; its maximum goes to max_key[b]
 // (ordered-integer atomicMax: a maximum does not depend on the order of arrival), the floor pass reads it back
 __global__ __launch_bounds__(256) void ss_power_to_db_packed_kernel(const float *__restrict__ s, const long long *__restrict__ off, float *__restrict__ out,
@@ -572,6 +720,41 @@ int via_device_packed(const float *in, const int64_t *off, size_t n_clips, size_
     if (d_out) (void)hipFree(d_out);
     if (d_off) (void)hipFree(d_off);
     return rc;
+}
+
+// ---- causal CMVN over a pool of stream states: argument checks ----
+
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// L = (win_size - 1) * cols + 1 floats per pool row; the count word is a float, so the window stays below 2^24 rows
+int cmvn_stream_len(size_t cols, size_t win_size, size_t &len)
+{
+    if (cols == 0) return fail(SS_ERR_ARG, "empty feature matrix (cols == 0)");
+    if (win_size == 0) return fail(SS_ERR_ARG, "win_size must be >= 1");
+    if (cols >= (1ull << 31) || win_size > (1ull << 24) || (win_size - 1) * cols + 1 >= (1ull << 31))
+        return fail(SS_ERR_ARG, "stream state too large: (win_size - 1) * cols + 1 must be below 2^31 and win_size at most 2^24");
+    len = (win_size - 1) * cols + 1;
+    return SS_OK;
+}
+
+// what both forms of ss_cmvn_stream_packed* reject before the device is touched (the tables apart)
+int check_cmvn_stream(const float *vec, const void *ro, const void *slots, size_t n_active, size_t total_rows, size_t pool_streams, size_t cols,
+                      size_t win_size, const float *pool, const float *out, size_t &len)
+{
+    if (!vec || !ro || !slots || !pool || !out) return fail(SS_ERR_ARG, "null buffer");
+    const int rc = cmvn_stream_len(cols, win_size, len);
+    if (rc) return rc;
+    if (n_active >= (1ull << 31) || pool_streams >= (1ull << 31) || total_rows >= (1ull << 31))
+        return fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (pool_streams == 0) return fail(SS_ERR_ARG, "the pool has no rows");
+    const size_t bytes = total_rows * cols * sizeof(float), pbytes = pool_streams * len * sizeof(float);
+    if (ranges_overlap(vec, bytes, out, bytes)) return fail(SS_ERR_ARG, "out overlaps vec: the call is not in place (later rows need the raw earlier rows)");
+    if (ranges_overlap(pool, pbytes, vec, bytes) || ranges_overlap(pool, pbytes, out, bytes)) return fail(SS_ERR_ARG, "the pool overlaps vec or out");
+    return SS_OK;
 }
 
 }  // namespace
@@ -909,6 +1092,101 @@ int ss_power_to_db_packed(const float *s, size_t n_clips, const int64_t *offsets
                                  [&](const float *di, const int64_t *doff, float *dout) {
                                      return ss_power_to_db_packed_device(di, n_clips, doff, total_rows, cols, ref, amin, top_db, dout, nullptr);
                                  });
+}
+
+// ---- causal sliding-window CMVN over a pool of stream states: entry i owns rows ro[i] .. ro[i+1] and pool row slots[i] ----
+
+int ss_cmvn_stream_state_len(size_t cols, size_t win_size, size_t *state_len)
+{
+    if (!state_len) return ss::fail(SS_ERR_ARG, "null output");
+    size_t len = 0;
+    const int rc = ss::cmvn_stream_len(cols, win_size, len);
+    if (rc) return rc;
+    *state_len = len;
+    return SS_OK;
+}
+
+int ss_cmvn_stream_packed_device(const float *d_vec, size_t n_active, const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots,
+                                 size_t pool_streams, size_t cols, size_t win_size, int variance_normalization, float *d_pool, float *d_out,
+                                 void *stream)
+{
+    if (n_active == 0) return SS_OK;
+    size_t len = 0;
+    const int rc = ss::check_cmvn_stream(d_vec, d_row_offsets, d_slots, n_active, total_rows, pool_streams, cols, win_size, d_pool, d_out, len);
+    if (rc) return rc;
+    if (total_rows == 0) return SS_OK;  // no entry can own a row
+    // one launch, one workgroup per entry: the grid depends on n_active only
+    hipLaunchKernelGGL(ss::ss_cmvn_stream_packed_kernel, dim3(static_cast<unsigned>(n_active)), dim3(256), 0, static_cast<hipStream_t>(stream), d_vec,
+                       reinterpret_cast<const long long *>(d_row_offsets), reinterpret_cast<const int *>(d_slots), d_out, d_pool,
+                       static_cast<unsigned long long>(total_rows), static_cast<unsigned>(pool_streams), static_cast<unsigned>(cols),
+                       static_cast<unsigned>(win_size), variance_normalization);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_cmvn_stream_packed_kernel");
+}
+
+// Host-pointer form: the tables are checked here, before anything touches the device; then vec, the row offsets and the n_active
+// named pool rows (gathered into a compact block whose row i is entry i's: the device call runs on slots 0 .. n_active - 1) go
+// up, out and the named rows come down.  The caller's pool is written only once everything before it succeeded.
+int ss_cmvn_stream_packed(const float *vec, size_t n_active, const int64_t *row_offsets, const int32_t *slots, size_t pool_streams, size_t cols,
+                          size_t win_size, int variance_normalization, float *pool, float *out)
+{
+    if (n_active == 0) return SS_OK;
+    if (!row_offsets) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_active >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (row_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "row_offsets[0] must be 0 (entry 0)");
+    for (size_t i = 0; i < n_active; ++i)
+        if (row_offsets[i + 1] < row_offsets[i]) return ss::fail(SS_ERR_ARG, "decreasing row offsets at entry " + std::to_string(i));
+    const size_t rows = static_cast<size_t>(row_offsets[n_active]);
+    size_t len = 0;
+    int rc = ss::check_cmvn_stream(vec, row_offsets, slots, n_active, rows, pool_streams, cols, win_size, pool, out, len);
+    if (rc) return rc;
+    {
+        std::unordered_set<int32_t> seen;
+        seen.reserve(n_active);
+        for (size_t i = 0; i < n_active; ++i) {
+            if (slots[i] < 0 || static_cast<size_t>(slots[i]) >= pool_streams)
+                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is outside the pool of " +
+                                                std::to_string(pool_streams) + " rows");
+            if (!seen.insert(slots[i]).second)
+                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is named twice in one call");
+        }
+    }
+    if (rows == 0) return SS_OK;  // entries without rows only: nothing moves
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return ss::fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd path has no CPU fallback");
+    std::vector<float> rows_host(n_active * len);
+    std::vector<int32_t> iota(n_active);
+    for (size_t i = 0; i < n_active; ++i) {
+        iota[i] = static_cast<int32_t>(i);
+        std::memcpy(rows_host.data() + i * len, pool + static_cast<size_t>(slots[i]) * len, len * sizeof(float));
+    }
+    const size_t bytes = rows * cols * sizeof(float), tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * len * sizeof(float);
+    void *d_vec = nullptr, *d_out = nullptr, *d_ro = nullptr, *d_sl = nullptr, *d_pool = nullptr;
+    hipError_t e = hipMalloc(&d_vec, bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_out, bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_ro, tbytes);
+    if (e == hipSuccess) e = hipMalloc(&d_sl, n_active * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&d_pool, sbytes);
+    if (e == hipSuccess) e = hipMemcpy(d_vec, vec, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_ro, row_offsets, tbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_sl, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_pool, rows_host.data(), sbytes, hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? ss_cmvn_stream_packed_device(static_cast<const float *>(d_vec), n_active, static_cast<const int64_t *>(d_ro), rows,
+                                                        static_cast<const int32_t *>(d_sl), n_active, cols, win_size, variance_normalization,
+                                                        static_cast<float *>(d_pool), static_cast<float *>(d_out), nullptr)
+                         : ss::hip_err(e, "host staging");
+    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_cmvn_stream_packed: device error");
+    if (rc == SS_OK) {
+        e = hipMemcpy(rows_host.data(), d_pool, sbytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = ss::hip_err(e, "hipMemcpy D2H");
+    }
+    if (rc == SS_OK)
+        for (size_t i = 0; i < n_active; ++i) std::memcpy(pool + static_cast<size_t>(slots[i]) * len, rows_host.data() + i * len, len * sizeof(float));
+    for (void *p : {d_vec, d_out, d_ro, d_sl, d_pool})
+        if (p) (void)hipFree(p);
+    return rc;
 }
 
 }  // extern "C"

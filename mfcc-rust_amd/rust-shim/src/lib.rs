@@ -169,6 +169,9 @@ extern "C" {
                        variance_normalization: c_int, out: *mut f32) -> c_int;
     fn ss_power_to_db_packed(s: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize, ref_value: f32,
                              amin: f32, top_db: f32, out: *mut f32) -> c_int;
+    fn ss_cmvn_stream_state_len(cols: usize, win_size: usize, state_len: *mut usize) -> c_int;
+    fn ss_cmvn_stream_packed(vec: *const f32, n_active: usize, row_offsets: *const i64, slots: *const i32, pool_streams: usize,
+                             cols: usize, win_size: usize, variance_normalization: c_int, pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_derivative_extraction(feat: *const f32, rows: usize, cols: usize, delta_windows: usize, out: *mut f32) -> c_int;
     fn ss_extract_derivative_feature(feat: *const f32, rows: usize, cols: usize, cube: *mut f32) -> c_int;
     fn ss_shard_bounds(n_items: usize, world: c_int, rank: c_int, lo: *mut usize, hi: *mut usize) -> c_int;
@@ -967,6 +970,39 @@ pub fn try_cmvnw_packed(vec: ArrayView2<f32>, offsets: &[i64], win_size: usize, 
     check(unsafe {
         ss_cmvnw_packed(x.as_ptr(), offsets.len().saturating_sub(1), offsets.as_ptr(), rows, cols, win_size,
                         variance_normalization as c_int, out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// Floats per stream of the pool `try_cmvn_stream_packed` carries: `(win_size - 1) * cols + 1`.
+pub fn try_cmvn_stream_state_len(cols: usize, win_size: usize) -> Result<usize, Error> {
+    let mut len = 0usize;
+    check(unsafe { ss_cmvn_stream_state_len(cols, win_size, &mut len) })?;
+    Ok(len)
+}
+
+/// Causal sliding-window CMVN of the rows of live streams (the causal counterpart of processing.rs:315-371): entry i owns rows
+/// `row_offsets[i] .. row_offsets[i + 1]` of `vec` and row `slots[i]` of `pool`, a `[pool_streams, try_cmvn_stream_state_len]`
+/// block that carries every stream's last `win_size - 1` raw rows from call to call (all zeros: fresh streams).  Every row is
+/// normalised over the trailing `win_size` rows of its own stream, the row itself the newest.
+pub fn try_cmvn_stream_packed(vec: ArrayView2<f32>, row_offsets: &[i64], slots: &[i32], win_size: usize, variance_normalization: bool,
+                              pool: &mut Array2<f32>) -> Result<Array2<f32>, Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    let len = try_cmvn_stream_state_len(cols, win_size)?;
+    if row_offsets.len() != slots.len() + 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "row_offsets must have one entry more than slots".to_string() });
+    }
+    if pool.ncols() != len || !pool.is_standard_layout() {
+        return Err(Error { status: SS_ERR_ARG, detail: "pool must be a standard-layout [pool_streams, state_len] block".to_string() });
+    }
+    if row_offsets[slots.len()] < 0 || row_offsets[slots.len()] as usize > rows {
+        return Err(Error { status: SS_ERR_ARG, detail: "row_offsets ends past the block".to_string() });
+    }
+    let mut out = Array2::<f32>::zeros((rows, cols));
+    check(unsafe {
+        ss_cmvn_stream_packed(x.as_ptr(), slots.len(), row_offsets.as_ptr(), slots.as_ptr(), pool.nrows(), cols, win_size,
+                              variance_normalization as c_int, pool.as_mut_ptr(), out.as_mut_ptr())
     })?;
     Ok(out)
 }

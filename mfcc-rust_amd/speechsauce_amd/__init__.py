@@ -25,7 +25,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "mel_spectrogram_packed",
            "mel_spectrogram_list", "log_mel_spectrogram", "log_mel_spectrogram_packed", "log_mel_spectrogram_list", "stft_packed", "cmvn_packed", "cmvnw_packed", "power_to_db_packed", "lmfe_packed",
            "MelSpectrogramStream", "StftStream",
-           "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool",
+           "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool", "CmvnStreamPool",
            "SpeechConfig", "SpeechSauceError"]
 
 
@@ -1293,6 +1293,111 @@ class StftStreamPool(_StftStreamPoolBase):
         out = np.empty(shape, dtype=np.float32)
         self._call_pool(packed, so, ro, sl, config, [out], dev_fn, host_fn, scale)
         return out.view(np.complex64)[..., 0], ro
+
+
+# ---- causal sliding-window CMVN over a pool of stream states (ss_cmvn_stream_packed*) ---------------------------------------
+
+class CmvnStreamPool:
+    """Causal mean (and variance) normalisation of the rows of live streams: every row over the trailing ``win_size`` rows of its
+    own stream (the row itself the newest, no padding at a stream's start), with the last ``win_size - 1`` raw rows of each of
+    ``pool_streams`` streams carried from call to call.  ``pool(rows, row_offsets, slots)`` takes the ``(rows, row_offsets)`` pair
+    a ``MfccStreamPool`` / ``MfeStreamPool`` call returned and the ``slots`` that call was given, and returns the normalised
+    ``[total_rows, cols]`` block (rows past ``row_offsets[-1]`` are left uninitialised).  numpy in -> the host-pointer call, ROCm
+    tensors in -> the device call on the current stream.  A row's bits depend on its window's values only, however the stream was
+    cut into calls.  See ``ss_cmvn_stream_packed`` in ``include/speechsauce_amd.h``."""
+
+    _what = "CmvnStreamPool"
+
+    def __init__(self, pool_streams, cols, win_size=301, variance_normalization=False):
+        what = self._what
+        if int(pool_streams) < 1:
+            raise ValueError(f"{what}: pool_streams must be at least 1")
+        if int(cols) < 1:
+            raise ValueError(f"{what}: cols must be at least 1")
+        if int(win_size) < 1:
+            raise ValueError(f"{what}: win_size must be at least 1")
+        self.pool_streams = int(pool_streams)
+        self.cols = int(cols)
+        self.win_size = int(win_size)
+        self.variance_normalization = bool(variance_normalization)
+        L = C.c_size_t()
+        _lib.check(_lib.lib().ss_cmvn_stream_state_len(self.cols, self.win_size, C.byref(L)))
+        self.state_len = L.value
+        self._state = None
+        self._where = None
+
+    @property
+    def state(self):
+        """[pool_streams, (win_size - 1) * cols + 1] float32: a torch tensor on the device of the first rows, or a numpy array;
+        None before the first call."""
+        return self._state
+
+    def reset(self, slots=None):
+        """Zero the state of every stream of the pool, or of the given slots (fresh streams)."""
+        if self._state is None:
+            return
+        if slots is None:
+            self._state[...] = 0
+        else:
+            idx = list(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
+            if idx:
+                self._state[idx] = 0
+
+    def __call__(self, rows, row_offsets, slots):
+        what = self._what
+        x = _require_f32(rows, (2,), what)
+        if int(x.shape[1]) != self.cols:
+            raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool normalises {self.cols}")
+        total_rows = int(x.shape[0])
+        ro = np.asarray(row_offsets.cpu() if _is_torch(row_offsets) else row_offsets)
+        if ro.ndim != 1 or ro.size < 1:
+            raise ValueError(f"{what}: row_offsets must be 1-D with one entry more than slots")
+        if not np.issubdtype(ro.dtype, np.integer):
+            raise TypeError(f"{what}: row_offsets must be integers, got {ro.dtype}")
+        ro = np.ascontiguousarray(ro, dtype=np.int64)
+        slot_list = [int(v) for v in slots]
+        if len(slot_list) != ro.size - 1:
+            raise ValueError(f"{what}: {ro.size - 1} entries in row_offsets but {len(slot_list)} slots")
+        if ro[0] != 0 or (np.diff(ro) < 0).any() or ro[-1] > total_rows:
+            raise ValueError(f"{what}: row_offsets must start at 0, not decrease and end within the block's {total_rows} rows")
+        seen = set()
+        for i, v in enumerate(slot_list):
+            if not 0 <= v < self.pool_streams:
+                raise ValueError(f"{what}: slot {v} of entry {i} is outside the pool of {self.pool_streams} streams")
+            if v in seen:
+                raise ValueError(f"{what}: slot {v} is named twice in one call")
+            seen.add(v)
+        on_dev = _is_torch(x)
+        where = ("cuda", x.device.index) if on_dev else ("host",)
+        if self._where is not None and where != self._where:
+            raise ValueError(f"{what}: the pool lives on {self._where}, these rows on {where}")
+        lib, n_active = _lib.lib(), len(slot_list)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        var = int(self.variance_normalization)
+        if on_dev:
+            import torch
+
+            x = x.contiguous()
+            state = self._state if self._state is not None else torch.zeros((self.pool_streams, self.state_len), dtype=torch.float32,
+                                                                            device=x.device)
+            out = torch.empty_like(x)
+            if n_active and total_rows:
+                with torch.cuda.device(x.device):
+                    d_ro, d_sl = torch.from_numpy(ro).to(x.device), torch.from_numpy(sl).to(x.device)
+                    _lib.check(lib.ss_cmvn_stream_packed_device(x.data_ptr(), n_active, d_ro.data_ptr(), total_rows, d_sl.data_ptr(),
+                                                                self.pool_streams, self.cols, self.win_size, var, state.data_ptr(),
+                                                                out.data_ptr(), _stream_ptr()))
+                    for t in (x, d_ro, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                        t.record_stream(torch.cuda.current_stream())
+        else:
+            x = np.ascontiguousarray(x)
+            state = self._state if self._state is not None else np.zeros((self.pool_streams, self.state_len), dtype=np.float32)
+            out = np.empty_like(x)
+            if n_active and total_rows:
+                _lib.check(lib.ss_cmvn_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, self.pool_streams, self.cols,
+                                                     self.win_size, var, state.ctypes.data, out.ctypes.data))
+        self._state, self._where = state, where  # only once the call went through
+        return out
 
 
 def stack_frames(signal, sampling_frequency, frame_length=0.020, frame_stride=0.020, filter=None, zero_padding=False, **switches):
