@@ -778,6 +778,75 @@ int ss_cmvn_stream_packed_device(const float *d_vec, size_t n_active, const int6
 int ss_cmvn_stream_packed(const float *vec, size_t n_active, const int64_t *row_offsets, const int32_t *slots,
                           size_t pool_streams, size_t cols, size_t win_size, int variance_normalization, float *pool, float *out);
 
+/* ---- time-axis delta features (Kaldi's add-deltas) on packed clips and over a pool of stream states ----
+ * ss_derivative_extraction* above mirror the reference, which differences along the FEATURE axis.  These calls append the
+ * regression deltas over neighbouring FRAMES that HTK, Kaldi add-deltas, python_speech_features.delta and
+ * torchaudio.functional.compute_deltas(mode="replicate") mean.  The reference crate has none: this is the specification.
+ *   Parameters: order in {1, 2}, window >= 1, lag L = order * window <= 32.
+ *   Taps (integers): k0 = [1], ko = k(o-1) convolved with [-window, .., -1, 0, 1, .., window]; Do = (2 * sum n^2, n = 1..window)^o.
+ *   order 1, window 2: [-2,-1,0,1,2] / 10; order 2, window 2: [4,4,1,-4,-10,-4,1,4,4] / 100.
+ *   One clip or stream with rows x[0 .. T-1], per column, for o = 1 .. order:
+ *     acc = +0.0 (f64); for j = -o*window .. +o*window ascending, taps with ko[j] == 0 skipped:
+ *         acc = acc + double(ko[j]) * double(x[clamp(t + j, 0, T - 1)])
+ *     do[t] = float(acc * invo),  invo = 1.0 / double(Do) formed once on the host
+ *   The clamp is on the RAW row index (edge replication of the clip itself): the second delta is the composite filter on the raw
+ *   rows, not the first delta applied to an edge-padded first delta (the two differ within 2 * window rows of a clip's ends).
+ *   Every product is exact in f64, so the bits depend on the summation order only (not on FMA contraction), there is no f64
+ *   division on the device, a constant column gives exact +0.0, and a NaN / Inf at row t reaches exactly the outputs whose
+ *   non-zero taps cover row t (the first delta of row t itself stays finite: its centre tap is zero).
+ *   Output row: [ x[t] | d1[t] | d2[t] ], (order + 1) * cols floats (Kaldi's layout); the static block is a bit copy.
+ * Packed clips (ss_add_deltas_packed*): vec is [total_rows x cols], out is [total_rows x (order + 1) * cols], clip b owns rows
+ * offsets[b] .. offsets[b+1] of both.  Contract, containment and argument rules are those of ss_cmvn_packed*: the table is a device
+ * array that only the kernel reads; a segment that is reversed, starts below 0 or ends past total_rows is skipped; nothing outside
+ * [0, total_rows) is touched; rows in no valid segment are left unwritten; one launch (ss_add_deltas_packed_kernel) whatever the
+ * clip count; a clip's bits depend on its own rows and the scalars only.  A dense matrix is n_clips == 1.  n_clips == 0 is SS_OK
+ * without a device.  SS_ERR_ARG, decided before the device is touched: null buffers, cols == 0, n_clips / total_rows / cols >=
+ * 2^31, order outside {1, 2}, window == 0, L > 32, out overlapping vec.  The host form checks the table first and names the first
+ * bad clip. */
+int ss_add_deltas_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols,
+                                size_t order, size_t window, float *d_out, void *stream);
+int ss_add_deltas_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, size_t order,
+                         size_t window, float *out);
+/* Pool of stream states, fixed latency L (ss_add_deltas_stream_*): deltas need L rows of look-ahead, so a live stream gets its
+ * rows L rows late.  Pool: a caller-owned block [pool_streams x len] of floats, len = ss_add_deltas_stream_state_len = 2L * cols
+ * + 1, laid out as the CMVN pool: the stream's last 2L raw rows, oldest first, right-aligned, zeros in front, then the count word
+ * min(rows seen, 2L) as a float.  All zeros = fresh stream.  A count word that is not an integer in [0, 2L] (NaN included) is
+ * read as 0.
+ *   Entry i owns rows ro[i] .. ro[i+1] of vec [total_rows x cols] and of out [total_rows x (order + 1) * cols], and pool row
+ *   slots[i]: it brings R_i raw rows and gets exactly R_i output rows, so the row_offsets / slots of the feature call and of
+ *   ss_cmvn_stream_packed* are reused unchanged.  Output row k of the entry is the feature row of stream time tau = seen + k - L
+ *   (seen: rows of the stream before this call).  tau < 0 (the first L rows after a reset): the whole row is +0.0, a warm-up row.
+ *   tau >= 0: the row defined above with left clamping at stream row 0 and no right clamping (row tau + L has just arrived).
+ *   R_i == 0 writes nothing and leaves the pool row bit for bit.
+ *   Flush (ss_add_deltas_stream_flush*): entry i gets exactly L rows, out[i*L .. (i+1)*L) of [n_active * L x (order + 1) * cols]:
+ *   the stream's last rows seen - L .. seen - 1 with right clamping at the stream's last row; times below 0 are +0.0 rows.
+ *   Afterwards the pool row is all zeros (a fresh stream).
+ *   Invariant: however a stream is cut into calls (empty entries included), the rows of all its calls plus the flush, the first L
+ *   dropped, are bit for bit ss_add_deltas_packed* on the whole clip.
+ *   One launch each (ss_add_deltas_stream_kernel), one workgroup per entry, asynchronous on `stream`, no scratch, graph-capturable
+ *   as a single kernel node whose grid depends on n_active only.  Containment as ss_cmvn_stream_packed*: an entry is skipped -- no
+ *   row written, its pool row untouched -- unless 0 <= ro[i] <= ro[i+1] <= total_rows and 0 <= slots[i] < pool_streams (flush: the
+ *   slot rule); whatever the tables and count words hold, nothing outside the blocks is read or written.  Duplicate slots in a
+ *   device-form call are a caller error that is NOT detected (results of those entries unspecified, everything stays inside the
+ *   pool); the host forms reject them.
+ * Arguments: n_active == 0 is SS_OK with nothing launched, also without a device.  SS_ERR_ARG, decided before the device is
+ * touched, pool and out untouched: null buffers; cols == 0; order outside {1, 2}, window == 0, L > 32; n_active, pool_streams,
+ * total_rows, cols or len >= 2^31; pool_streams == 0; out overlapping vec; the pool overlapping vec or out.  The host forms also
+ * check the tables first -- ro[0] != 0, a decreasing pair, a slot outside the pool, a slot named twice; ss_last_error_string()
+ * names the first bad entry -- and move only what the call touches; the caller's pool is written only after everything before it
+ * succeeded. */
+/* host only, no device: len = 2 * order * window * cols + 1 */
+int ss_add_deltas_stream_state_len(size_t cols, size_t order, size_t window, size_t *state_len);
+int ss_add_deltas_stream_packed_device(const float *d_vec, size_t n_active, const int64_t *d_row_offsets, size_t total_rows,
+                                       const int32_t *d_slots, size_t pool_streams, size_t cols, size_t order, size_t window,
+                                       float *d_pool, float *d_out, void *stream);
+int ss_add_deltas_stream_packed(const float *vec, size_t n_active, const int64_t *row_offsets, const int32_t *slots,
+                                size_t pool_streams, size_t cols, size_t order, size_t window, float *pool, float *out);
+int ss_add_deltas_stream_flush_device(size_t n_active, const int32_t *d_slots, size_t pool_streams, size_t cols, size_t order,
+                                      size_t window, float *d_pool, float *d_out, void *stream);
+int ss_add_deltas_stream_flush(size_t n_active, const int32_t *slots, size_t pool_streams, size_t cols, size_t order, size_t window,
+                               float *pool, float *out);
+
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`
  * computes clips [lo, hi) of ss_shard_bounds on its own device with the *_device entry points.  The north-star's "RCCL

@@ -568,6 +568,17 @@ inline std::vector<float> cmvn_packed(const std::vector<float> &vec, const std::
     return out;
 }
 
+// Kaldi add-deltas of every clip of a packed block on its own rows (ss_add_deltas_packed): -> [total_rows x (order + 1) * cols], row t =
+// [x[t] | delta | delta-delta] over neighbouring frames; order 1 or 2, order * window at most 32.  A dense matrix: offsets = {0, rows}
+inline std::vector<float> add_deltas_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t order = 2,
+                                            size_t window = 2)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty() || order == 0 || order > 2) throw Error(SS_ERR_ARG, "add_deltas_packed: shape mismatch");
+    std::vector<float> out(vec.size() * (order + 1));
+    check(ss_add_deltas_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, order, window, out.data()));
+    return out;
+}
+
 inline std::vector<float> cmvnw_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t win_size = 301,
                                        bool variance_normalization = false)
 {

@@ -172,6 +172,13 @@ extern "C" {
     fn ss_cmvn_stream_state_len(cols: usize, win_size: usize, state_len: *mut usize) -> c_int;
     fn ss_cmvn_stream_packed(vec: *const f32, n_active: usize, row_offsets: *const i64, slots: *const i32, pool_streams: usize,
                              cols: usize, win_size: usize, variance_normalization: c_int, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_add_deltas_packed(vec: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize, order: usize,
+                            window: usize, out: *mut f32) -> c_int;
+    fn ss_add_deltas_stream_state_len(cols: usize, order: usize, window: usize, state_len: *mut usize) -> c_int;
+    fn ss_add_deltas_stream_packed(vec: *const f32, n_active: usize, row_offsets: *const i64, slots: *const i32, pool_streams: usize,
+                                   cols: usize, order: usize, window: usize, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_add_deltas_stream_flush(n_active: usize, slots: *const i32, pool_streams: usize, cols: usize, order: usize, window: usize,
+                                  pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_derivative_extraction(feat: *const f32, rows: usize, cols: usize, delta_windows: usize, out: *mut f32) -> c_int;
     fn ss_extract_derivative_feature(feat: *const f32, rows: usize, cols: usize, cube: *mut f32) -> c_int;
     fn ss_shard_bounds(n_items: usize, world: c_int, rank: c_int, lo: *mut usize, hi: *mut usize) -> c_int;
@@ -1003,6 +1010,67 @@ pub fn try_cmvn_stream_packed(vec: ArrayView2<f32>, row_offsets: &[i64], slots: 
     check(unsafe {
         ss_cmvn_stream_packed(x.as_ptr(), slots.len(), row_offsets.as_ptr(), slots.as_ptr(), pool.nrows(), cols, win_size,
                               variance_normalization as c_int, pool.as_mut_ptr(), out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// Kaldi add-deltas of every clip of a packed block on its own rows (edge replication at the clip's own ends): row t of the result is
+/// `[x[t] | delta | delta-delta]`, `(order + 1) * cols` floats.  `order` is 1 or 2, `order * window` at most 32.  A dense matrix is
+/// the one-clip call `offsets = [0, rows]`.
+pub fn try_add_deltas_packed(vec: ArrayView2<f32>, offsets: &[i64], order: usize, window: usize) -> Result<Array2<f32>, Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    if offsets.is_empty() || order == 0 || order > 2 {
+        return Err(Error { status: SS_ERR_ARG, detail: "add_deltas_packed: offsets must not be empty and order must be 1 or 2".to_string() });
+    }
+    let mut out = Array2::<f32>::zeros((rows, (order + 1) * cols));
+    check(unsafe { ss_add_deltas_packed(x.as_ptr(), offsets.len() - 1, offsets.as_ptr(), rows, cols, order, window, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// Floats per stream of the pool `try_add_deltas_stream_packed` carries: `2 * order * window * cols + 1`.
+pub fn try_add_deltas_stream_state_len(cols: usize, order: usize, window: usize) -> Result<usize, Error> {
+    let mut len = 0usize;
+    check(unsafe { ss_add_deltas_stream_state_len(cols, order, window, &mut len) })?;
+    Ok(len)
+}
+
+/// Kaldi add-deltas over the rows of live streams with a fixed latency of `order * window` rows: entry i owns rows
+/// `row_offsets[i] .. row_offsets[i + 1]` of `vec` and of the result, and row `slots[i]` of `pool`, a `[pool_streams,
+/// try_add_deltas_stream_state_len]` block that carries every stream's last `2 * order * window` raw rows (all zeros: fresh streams).
+/// Output row k of an entry is the feature row of stream time `seen + k - order * window`; rows of negative times are zeros.
+pub fn try_add_deltas_stream_packed(vec: ArrayView2<f32>, row_offsets: &[i64], slots: &[i32], order: usize, window: usize,
+                                    pool: &mut Array2<f32>) -> Result<Array2<f32>, Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    let len = try_add_deltas_stream_state_len(cols, order, window)?;
+    if row_offsets.len() != slots.len() + 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "row_offsets must have one entry more than slots".to_string() });
+    }
+    if pool.ncols() != len || !pool.is_standard_layout() {
+        return Err(Error { status: SS_ERR_ARG, detail: "pool must be a standard-layout [pool_streams, state_len] block".to_string() });
+    }
+    if row_offsets[slots.len()] < 0 || row_offsets[slots.len()] as usize > rows {
+        return Err(Error { status: SS_ERR_ARG, detail: "row_offsets ends past the block".to_string() });
+    }
+    let mut out = Array2::<f32>::zeros((rows, (order + 1) * cols));
+    check(unsafe {
+        ss_add_deltas_stream_packed(x.as_ptr(), slots.len(), row_offsets.as_ptr(), slots.as_ptr(), pool.nrows(), cols, order, window,
+                                    pool.as_mut_ptr(), out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// The last `order * window` rows of the streams in `slots` (entry i: rows `i * order * window ..` of the result, right clamping at
+/// the stream's last row, zeros for negative times); afterwards their pool rows are zero (fresh streams).
+pub fn try_add_deltas_stream_flush(slots: &[i32], cols: usize, order: usize, window: usize, pool: &mut Array2<f32>) -> Result<Array2<f32>, Error> {
+    let len = try_add_deltas_stream_state_len(cols, order, window)?;
+    if pool.ncols() != len || !pool.is_standard_layout() {
+        return Err(Error { status: SS_ERR_ARG, detail: "pool must be a standard-layout [pool_streams, state_len] block".to_string() });
+    }
+    let mut out = Array2::<f32>::zeros((slots.len() * order * window, (order + 1) * cols));
+    check(unsafe {
+        ss_add_deltas_stream_flush(slots.len(), slots.as_ptr(), pool.nrows(), cols, order, window, pool.as_mut_ptr(), out.as_mut_ptr())
     })?;
     Ok(out)
 }

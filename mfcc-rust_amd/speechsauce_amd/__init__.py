@@ -26,6 +26,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "mel_spectrogram_list", "log_mel_spectrogram", "log_mel_spectrogram_packed", "log_mel_spectrogram_list", "stft_packed", "cmvn_packed", "cmvnw_packed", "power_to_db_packed", "lmfe_packed",
            "MelSpectrogramStream", "StftStream",
            "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool", "CmvnStreamPool",
+           "add_deltas", "add_deltas_packed", "AddDeltasStreamPool",
            "SpeechConfig", "SpeechSauceError"]
 
 
@@ -1732,3 +1733,194 @@ def power_to_db_packed(S, offsets, cols=None, ref=1.0, amin=1e-10, top_db=80.0):
     return _post_packed(S, offsets, cols, "power_to_db_packed",
                         lambda p, n, t, r, c, o: lib.ss_power_to_db_packed(p, n, t, r, c, rf, am, td, o),
                         lambda p, n, t, r, c, o, s: lib.ss_power_to_db_packed_device(p, n, t, r, c, rf, am, td, o, s))
+
+
+# ---- time-axis delta features (Kaldi's add-deltas; ss_add_deltas_*) -----------------------------------------------------------
+# derivative_extraction / extract_derivative_feature above are the reference's, along the FEATURE axis; these append the regression
+# deltas over neighbouring FRAMES: out row = [x[t] | d1[t] | d2[t]], (order + 1) * cols floats.
+
+def _check_delta_params(order, window, what):
+    order, window = int(order), int(window)
+    if order not in (1, 2):
+        raise ValueError(f"{what}: order must be 1 or 2")
+    if window < 1:
+        raise ValueError(f"{what}: window must be at least 1")
+    if order * window > 32:
+        raise ValueError(f"{what}: order * window must be at most 32")
+    return order, window
+
+
+def add_deltas_packed(vec, offsets, order=2, window=2):
+    """Kaldi ``add-deltas`` of every clip of a packed block [sum T_b, cols] on its own rows (edge replication at the clip's own first
+    and last row), one launch for all clips: -> [sum T_b, (order + 1) * cols], row t = [x[t] | delta | delta-delta].  Order 1 equals
+    HTK, ``python_speech_features.delta`` and ``torchaudio.functional.compute_deltas(mode="replicate")``; the second delta is the
+    composite filter on the raw rows.  numpy in -> the host-pointer call; a ROCm tensor stays on the device (current stream), and
+    ``offsets`` may be the device tensor ``mfcc_packed`` returned or a host array, as for ``cmvn_packed``.  Rows that the table does
+    not cover are left uninitialised.  See ``ss_add_deltas_packed`` in ``include/speechsauce_amd.h``."""
+    what = "add_deltas_packed"
+    order, window = _check_delta_params(order, window, what)
+    lib = _lib.lib()
+    x, on_device, rows, cols = _packed_block(vec, None, what)
+    table, n = _segment_table(offsets, on_device, x.device if on_device else None, rows, what)
+    if on_device:
+        import torch
+
+        out = torch.empty((rows, (order + 1) * cols), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.ss_add_deltas_packed_device(x.data_ptr(), n, table.data_ptr(), rows, cols, order, window, out.data_ptr(), _stream_ptr()))
+            for t in (x, table):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                t.record_stream(torch.cuda.current_stream())
+        return out
+    out = np.empty((rows, (order + 1) * cols), dtype=np.float32)
+    _lib.check(lib.ss_add_deltas_packed(x.ctypes.data, n, table.ctypes.data, rows, cols, order, window, out.ctypes.data))
+    return out
+
+
+def add_deltas(feat, order=2, window=2):
+    """``add_deltas_packed`` of one matrix [T, cols] -> [T, (order + 1) * cols], or of every matrix of a batch [..., T, cols] on its
+    own rows (equal-length clips of one packed block, one launch)."""
+    x = _require_f32(feat, tuple(range(2, 9)), "add_deltas")
+    shape = tuple(int(v) for v in x.shape)
+    T, cols = shape[-2], shape[-1]
+    n = int(np.prod(shape[:-2], dtype=np.int64))
+    offsets = np.arange(n + 1, dtype=np.int64) * T
+    out = add_deltas_packed(x.reshape(n * T, cols), offsets, order, window)
+    return out.reshape(shape[:-1] + ((int(order) + 1) * cols,))
+
+
+class AddDeltasStreamPool:
+    """Kaldi ``add-deltas`` over the rows of live streams, with a fixed latency of ``lag = order * window`` rows: deltas need ``lag``
+    rows of look-ahead, so output row k of an entry is the feature row of stream time ``rows_seen + k - lag`` (all zeros while that is
+    negative: the first ``lag`` rows after a reset are warm-up rows).  ``pool(rows, row_offsets, slots)`` takes the ``(rows,
+    row_offsets)`` pair of a ``MfccStreamPool`` / ``CmvnStreamPool`` call and the ``slots`` that call was given and returns
+    ``[total_rows, (order + 1) * cols]``: an entry gets exactly as many rows as it brought.  ``flush(slots)`` returns the last ``lag``
+    rows of those streams, ``[len(slots) * lag, (order + 1) * cols]``, and makes them fresh.  However a stream is cut into calls, its
+    rows plus the flush, the first ``lag`` dropped, are bit for bit ``add_deltas`` of the whole clip.  ``rows_seen`` (int64 per slot,
+    on the host) dates every row; it moves only after a call went through.  numpy in -> the host-pointer calls, ROCm tensors in ->
+    the device calls on the current stream.  See ``ss_add_deltas_stream_packed`` in ``include/speechsauce_amd.h``."""
+
+    _what = "AddDeltasStreamPool"
+
+    def __init__(self, pool_streams, cols, order=2, window=2):
+        what = self._what
+        if int(pool_streams) < 1:
+            raise ValueError(f"{what}: pool_streams must be at least 1")
+        if int(cols) < 1:
+            raise ValueError(f"{what}: cols must be at least 1")
+        self.order, self.window = _check_delta_params(order, window, what)
+        self.pool_streams = int(pool_streams)
+        self.cols = int(cols)
+        self.lag = self.order * self.window
+        self.out_cols = (self.order + 1) * self.cols
+        L = C.c_size_t()
+        _lib.check(_lib.lib().ss_add_deltas_stream_state_len(self.cols, self.order, self.window, C.byref(L)))
+        self.state_len = L.value
+        self.rows_seen = np.zeros(self.pool_streams, dtype=np.int64)
+        self._state = None
+        self._where = None
+
+    @property
+    def state(self):
+        """[pool_streams, 2 * lag * cols + 1] float32: a torch tensor on the device of the first rows, or a numpy array; None before
+        the first call."""
+        return self._state
+
+    def _slots(self, slots):
+        slot_list = [int(v) for v in slots]
+        seen = set()
+        for i, v in enumerate(slot_list):
+            if not 0 <= v < self.pool_streams:
+                raise ValueError(f"{self._what}: slot {v} of entry {i} is outside the pool of {self.pool_streams} streams")
+            if v in seen:
+                raise ValueError(f"{self._what}: slot {v} is named twice in one call")
+            seen.add(v)
+        return slot_list
+
+    def reset(self, slots=None):
+        """Zero the state (and ``rows_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
+        idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
+        if slots is None:
+            self.rows_seen[:] = 0
+            if self._state is not None:
+                self._state[...] = 0
+        elif idx:
+            self.rows_seen[idx] = 0
+            if self._state is not None:
+                self._state[idx] = 0
+
+    def __call__(self, rows, row_offsets, slots):
+        what = self._what
+        x = _require_f32(rows, (2,), what)
+        if int(x.shape[1]) != self.cols:
+            raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool takes {self.cols}")
+        total_rows = int(x.shape[0])
+        ro = np.asarray(row_offsets.cpu() if _is_torch(row_offsets) else row_offsets)
+        if ro.ndim != 1 or ro.size < 1:
+            raise ValueError(f"{what}: row_offsets must be 1-D with one entry more than slots")
+        if not np.issubdtype(ro.dtype, np.integer):
+            raise TypeError(f"{what}: row_offsets must be integers, got {ro.dtype}")
+        ro = np.ascontiguousarray(ro, dtype=np.int64)
+        slot_list = self._slots(slots)
+        if len(slot_list) != ro.size - 1:
+            raise ValueError(f"{what}: {ro.size - 1} entries in row_offsets but {len(slot_list)} slots")
+        if ro[0] != 0 or (np.diff(ro) < 0).any() or ro[-1] > total_rows:
+            raise ValueError(f"{what}: row_offsets must start at 0, not decrease and end within the block's {total_rows} rows")
+        on_dev = _is_torch(x)
+        where = ("cuda", x.device.index) if on_dev else ("host",)
+        if self._where is not None and where != self._where:
+            raise ValueError(f"{what}: the pool lives on {self._where}, these rows on {where}")
+        lib, n_active = _lib.lib(), len(slot_list)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        if on_dev:
+            import torch
+
+            x = x.contiguous()
+            state = self._state if self._state is not None else torch.zeros((self.pool_streams, self.state_len), dtype=torch.float32,
+                                                                            device=x.device)
+            out = torch.empty((total_rows, self.out_cols), dtype=torch.float32, device=x.device)
+            if n_active and total_rows:
+                with torch.cuda.device(x.device):
+                    d_ro, d_sl = torch.from_numpy(ro).to(x.device), torch.from_numpy(sl).to(x.device)
+                    _lib.check(lib.ss_add_deltas_stream_packed_device(x.data_ptr(), n_active, d_ro.data_ptr(), total_rows, d_sl.data_ptr(),
+                                                                      self.pool_streams, self.cols, self.order, self.window, state.data_ptr(),
+                                                                      out.data_ptr(), _stream_ptr()))
+                    for t in (x, d_ro, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                        t.record_stream(torch.cuda.current_stream())
+        else:
+            x = np.ascontiguousarray(x)
+            state = self._state if self._state is not None else np.zeros((self.pool_streams, self.state_len), dtype=np.float32)
+            out = np.empty((total_rows, self.out_cols), dtype=np.float32)
+            if n_active and total_rows:
+                _lib.check(lib.ss_add_deltas_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, self.pool_streams, self.cols,
+                                                           self.order, self.window, state.ctypes.data, out.ctypes.data))
+        self._state, self._where = state, where  # only once the call went through
+        if n_active:
+            self.rows_seen[sl] += np.diff(ro)
+        return out
+
+    def flush(self, slots):
+        """The last ``lag`` rows of the given streams, ``[len(slots) * lag, (order + 1) * cols]`` (entry i: rows i * lag .. (i + 1) *
+        lag, stream times rows_seen - lag .. rows_seen - 1, zeros where that is negative); afterwards those streams are fresh.  Before
+        the pool's first call there is no state anywhere: the rows are zeros in a numpy array."""
+        slot_list = self._slots(slots)
+        lib, n_active = _lib.lib(), len(slot_list)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        if self._state is None or not _is_torch(self._state):
+            out = np.zeros((n_active * self.lag, self.out_cols), dtype=np.float32)
+            if n_active and self._state is not None:
+                _lib.check(lib.ss_add_deltas_stream_flush(n_active, sl.ctypes.data, self.pool_streams, self.cols, self.order, self.window,
+                                                          self._state.ctypes.data, out.ctypes.data))
+        else:
+            import torch
+
+            state = self._state
+            out = torch.empty((n_active * self.lag, self.out_cols), dtype=torch.float32, device=state.device)
+            if n_active:
+                with torch.cuda.device(state.device):
+                    d_sl = torch.from_numpy(sl).to(state.device)
+                    _lib.check(lib.ss_add_deltas_stream_flush_device(n_active, d_sl.data_ptr(), self.pool_streams, self.cols, self.order,
+                                                                     self.window, state.data_ptr(), out.data_ptr(), _stream_ptr()))
+                    d_sl.record_stream(torch.cuda.current_stream())
+        if n_active:
+            self.rows_seen[sl] = 0
+        return out

@@ -199,6 +199,14 @@ PROTOTYPES = {
     "ss_cmvn_stream_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
                                                _fp, _fp, C.c_void_p]),
     "ss_cmvn_stream_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _fp, _fp]),
+    "ss_add_deltas_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, C.c_void_p]),
+    "ss_add_deltas_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp]),
+    "ss_add_deltas_stream_state_len": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, _P(C.c_size_t)]),
+    "ss_add_deltas_stream_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                     C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_add_deltas_stream_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp]),
+    "ss_add_deltas_stream_flush_device": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_add_deltas_stream_flush": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp]),
     "ss_shard_bounds": (C.c_int, [C.c_size_t, C.c_int, C.c_int, _P(C.c_size_t), _P(C.c_size_t)]),
     "ss_all_gather_features": (C.c_int, [C.c_void_p, _fp, C.c_size_t, _fp, C.c_void_p]),
     "ss_gather_features": (C.c_int, [C.c_void_p, _fp, C.c_size_t, _fp, C.c_int, C.c_int, C.c_int, C.c_void_p]),
