@@ -847,6 +847,133 @@ int ss_add_deltas_stream_flush_device(size_t n_active, const int32_t *d_slots, s
 int ss_add_deltas_stream_flush(size_t n_active, const int32_t *slots, size_t pool_streams, size_t cols, size_t order, size_t window,
                                float *pool, float *out);
 
+/* ---- polyphase windowed-sinc resampling ahead of the feature calls ----
+ * Every call above takes audio at the rate its ss_params was built for; these calls bring telephony (8 kHz), capture (48 kHz) and
+ * corpus (44.1 kHz) audio to it on the device, on the packed layout and the stream pools of the feature calls, from floats or 16-bit
+ * PCM.  The reference crate has no resampler: this comment is the specification.  The filter is torchaudio.functional.resample's
+ * default, resampling_method = "sinc_interp_hann" (lowpass_filter_width = 6, rolloff = 0.99).
+ *   g = gcd(orig_rate, new_rate), o = orig_rate / g, n = new_rate / g, lpw = lowpass_filter_width;
+ *   base = min(o, n) * rolloff;  width = ceil(lpw * o / base);  for phase i in 0 .. n-1 and tap k in 0 .. 2*width+o-1, all in f64:
+ *     t = (-i / n + (k - width) / o) * base
+ *     h[i][k] = 0                                                                      where |t| >= lpw (an exact zero)
+ *             = (t == 0 ? 1 : sin(pi t) / (pi t)) * cos(pi t / (2 lpw))^2 * (base / o)  otherwise, rounded once to f32
+ *     out[j*n + i] = sum_k h[i][k] * x[j*o + k - width]   (x outside the clip = +0.0);   out_len(L) = ceil(n * L / o)
+ *   rolloff crosses the ABI as a float and is read as the decimal the caller wrote: the double nearest to the float's
+ *   seven-significant-digit decimal (0.99f means 0.99, torchaudio's double).
+ *   Per phase the taps with |t| < lpw are one run first[i] .. first[i] + count[i] - 1; taps = max count.  The table is compact:
+ *   [n x taps] floats, row i holding the run of phase i, zero-padded on the right.
+ *   lookback = max_i(width - first[i]), lookahead = max_i(first[i] + count[i] - 1 - width): how far left and right of sample j*o the
+ *   outputs of period j reach.  A period is o samples in and n outputs out.
+ *   Arithmetic of one output (normative): acc = +0.0f; for the taps of the phase's run in ascending k (the padding excluded):
+ *   acc = fmaf(h, x, acc); a sample outside the clip is +0.0f and its fma is executed.  Dense, packed, pool and flush outputs are
+ *   therefore the same bits: a stream's zero history is the clip's zero padding.
+ * Arguments of every call that takes the four filter parameters, decided before any device is touched: SS_ERR_ARG for a rate of 0,
+ * equal rates, lpw outside 1 .. 64, rolloff outside (0, 1], o or n above 1024; SS_ERR_UNSUPPORTED for taps > 256 or a compact table
+ * above 40960 bytes (n * taps * 4). */
+typedef struct ss_resample_info {
+    uint32_t o, n, width, taps, lookback, lookahead;
+    uint32_t latency_periods; /* D of the pool calls below */
+    uint32_t tile_outputs;    /* outputs per workgroup tile of the kernels (a whole number of periods); results do not depend on it */
+} ss_resample_info;
+typedef struct ss_resampler ss_resampler; /* opaque: the filter and, after the first device call, its device copy */
+
+/* host only, no device */
+int ss_resample_sizes(uint32_t orig_rate, uint32_t new_rate, uint32_t lowpass_filter_width, float rolloff, ss_resample_info *info);
+/* h: [n x taps]; first, count (may be NULL): [n] */
+int ss_resample_taps(uint32_t orig_rate, uint32_t new_rate, uint32_t lowpass_filter_width, float rolloff, float *h, int32_t *first,
+                     int32_t *count);
+/* out_len = ceil(n * n_samples / o) */
+int ss_resample_len(uint32_t orig_rate, uint32_t new_rate, size_t n_samples, size_t *out_len);
+/* sample offsets [n_clips + 1] (offsets[0] == 0, not decreasing, clips shorter than 2^31) -> out offsets [n_clips + 1]: what
+ * ss_resample_packed* take as out_offsets, and the sample_offsets of a feature call on the resampled block */
+int ss_resample_packed_offsets(uint32_t orig_rate, uint32_t new_rate, size_t n_clips, const int64_t *sample_offsets, int64_t *out_offsets);
+
+/* The handle owns the table; creation needs no device.  The first device call uploads the table, once, to the device that is current
+ * then (a later call under another current device is SS_ERR_ARG); after that warm call nothing is allocated or copied inside a
+ * launch, so the *_device forms are graph-capturable.  A handle may be used from several threads / streams concurrently. */
+int ss_resampler_create(uint32_t orig_rate, uint32_t new_rate, uint32_t lowpass_filter_width, float rolloff, ss_resampler **out);
+void ss_resampler_destroy(ss_resampler *rs);
+int ss_resampler_info(const ss_resampler *rs, ss_resample_info *info);
+
+/* Dense batch: x [batch x ld] (n_samples <= ld used per row) -> out [batch x ld_out], row b = the resampled row b, out_len(n_samples)
+ * <= ld_out samples; the rest of an out row is left unwritten.  One launch (ss_resample_kernel<dense,f32>).  batch == 0 is SS_OK
+ * without a device.  SS_ERR_ARG: null buffers, batch or n_samples or out_len >= 2^31, ld < n_samples, ld_out < out_len, out
+ * overlapping x.  The _i16 forms take int16 samples and a scale behind the sample-layout arguments: sample = (float)pcm * scale,
+ * converted on load (no conversion launch; 2-byte alignment is enough, an odd address is SS_ERR_ARG), scale a power of two in
+ * [2^-64, 2^64] else SS_ERR_ARG; every output is bit for bit that of the float call on x_f[k] = (float)pcm[k] * scale. */
+int ss_resample_device(const ss_resampler *rs, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out, size_t ld_out,
+                       void *stream);
+int ss_resample(const ss_resampler *rs, const float *x, size_t batch, size_t n_samples, size_t ld, float *out, size_t ld_out);
+int ss_resample_i16_device(const ss_resampler *rs, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale, float *d_out,
+                           size_t ld_out, void *stream);
+int ss_resample_i16(const ss_resampler *rs, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, float *out,
+                    size_t ld_out);
+
+/* Packed clips: clip b owns x[so[b] .. so[b+1]) of x [total_in] and out[oo[b] .. oo[b+1]) of out [total_out].  Contract and containment
+ * are those of ss_add_deltas_packed*: the tables are device arrays that only the kernel reads; one launch (ss_resample_kernel<packed,
+ * f32>) whatever the clip count; a clip is skipped unless 0 <= so[b] <= so[b+1] <= total_in, 0 <= oo[b], oo[b+1] <= total_out and
+ * oo[b+1] - oo[b] == out_len(so[b+1] - so[b]) (and the clip is shorter than 2^31 samples in and out); nothing outside the two blocks is
+ * touched; outputs in no valid clip are left unwritten; a clip's bits depend on its own samples and the handle only -- not on its
+ * place, not on its neighbours' contents: taps past a clip's end read zeros, never the next clip.  Empty clips are legal.  n_clips
+ * == 0 is SS_OK without a device.  SS_ERR_ARG: null buffers, n_clips >= 2^31, out overlapping x, the PCM scale rule.  The host forms
+ * (total_in = so[n_clips], total_out = oo[n_clips]) check the tables first -- offsets[0] != 0, a decreasing pair, an output span that
+ * is not out_len long -- and name the first bad clip in ss_last_error_string().
+ * out_offsets (ss_resample_packed_offsets) is by construction the sample_offsets of a following ss_mfcc_packed_device call on out:
+ * INTEGRATION.md shows the chain. */
+int ss_resample_packed_device(const ss_resampler *rs, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                              const int64_t *d_out_offsets, size_t total_in, size_t total_out, float *d_out, void *stream);
+int ss_resample_packed(const ss_resampler *rs, const float *x, size_t n_clips, const int64_t *sample_offsets, const int64_t *out_offsets,
+                       float *out);
+int ss_resample_packed_i16_device(const ss_resampler *rs, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                                  const int64_t *d_out_offsets, size_t total_in, size_t total_out, float *d_out, void *stream);
+int ss_resample_packed_i16(const ss_resampler *rs, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale,
+                           const int64_t *out_offsets, float *out);
+
+/* Pool of stream states, fixed latency of D = ceil((lookahead + 1) / o) periods (ss_resample_stream_*): a stream is fed whole periods,
+ * as the feature pools take whole hops (441 samples = 10 ms at 44.1 kHz -> 16 kHz, 3 samples at 48 kHz -> 16 kHz), and gets its
+ * outputs D * n outputs late.  Pool: a caller-owned block [pool_streams x len] of floats, len = ss_resample_stream_state_len = D * o +
+ * lookback + 1: the stream's last D * o + lookback samples as floats, oldest first, right-aligned, zeros in front, then the count word
+ * min(periods seen, D) as a float.  All zeros = fresh stream.  A count word that is not an integer in [0, D] (NaN included) is read
+ * as 0.
+ *   Entry i owns x[so[i] .. so[i+1]) of x [total_in], P_i = (so[i+1] - so[i]) / o >= 0 periods, pool row slots[i], and exactly P_i * n
+ *   outputs: out[so[i] / o * n .. so[i+1] / o * n) of out [total_in / o * n].  Output k of the entry is stream output time tau = seen_out
+ *   + k - D * n (seen_out: outputs of the stream before this call).  tau < 0: +0.0, a forced warm-up output (not the filter's
+ *   pre-ringing).  tau >= 0: the output defined above with zeros to the left of the stream's first sample.  P_i == 0 writes nothing
+ *   and leaves the pool row bit for bit.
+ *   Flush (ss_resample_stream_flush*): entry i gets exactly D * n outputs, out[i * D * n .. (i + 1) * D * n): the stream's last outputs,
+ *   with zeros to the right of its last sample (forced +0.0 where tau < 0).  Afterwards the pool row is all zeros.
+ *   Invariant: however a stream is cut into calls (empty entries included, float and PCM calls mixed), the outputs of all its calls
+ *   plus the flush, the first D * n dropped, are bit for bit ss_resample_packed* on the whole clip of P * o samples (out_len(P * o)
+ *   = P * n).
+ *   One launch each (ss_resample_stream_kernel), one workgroup per entry, asynchronous on `stream`, no scratch, graph-capturable as a
+ *   single kernel node whose grid depends on n_active only.  Containment as ss_add_deltas_stream_packed*: an entry is skipped -- no
+ *   output written, its pool row untouched -- unless 0 <= so[i] <= so[i+1] <= total_in, so[i] and so[i+1] are multiples of o, the
+ *   entry brings fewer than 2^20 periods and 0 <= slots[i] < pool_streams (flush: the slot rule); whatever the tables and count words
+ *   hold, nothing outside the blocks is read or written.  Duplicate slots in a device-form call are a caller error that is NOT
+ *   detected (results of those entries unspecified, everything stays inside the pool); the host forms reject them.
+ *   The float output of this pool is the x of ss_mfcc_stream_packed_device; the caller still buffers it to whole hops, since a period
+ *   of n outputs and a hop are different granularities.
+ * Arguments: n_active == 0 is SS_OK with nothing launched, also without a device.  SS_ERR_ARG, decided before the device is touched,
+ * pool and out untouched: null buffers; n_active or pool_streams >= 2^31, total_in >= 2^40; pool_streams == 0; out overlapping x; the
+ * pool overlapping x or out; the PCM scale rule.  The host forms (total_in = so[n_active]) also check the tables first -- so[0] != 0,
+ * a decreasing pair, an entry that is not whole periods, a slot outside the pool, a slot named twice; ss_last_error_string() names
+ * the first bad entry -- and move only what the call touches; the caller's pool is written only after everything before it
+ * succeeded. */
+int ss_resample_stream_state_len(const ss_resampler *rs, size_t *state_len);
+int ss_resample_stream_packed_device(const ss_resampler *rs, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                     size_t total_in, const int32_t *d_slots, size_t pool_streams, float *d_pool, float *d_out,
+                                     void *stream);
+int ss_resample_stream_packed(const ss_resampler *rs, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                              size_t pool_streams, float *pool, float *out);
+int ss_resample_stream_packed_i16_device(const ss_resampler *rs, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                         size_t total_in, const int32_t *d_slots, size_t pool_streams, float scale, float *d_pool,
+                                         float *d_out, void *stream);
+int ss_resample_stream_packed_i16(const ss_resampler *rs, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
+                                  const int32_t *slots, size_t pool_streams, float scale, float *pool, float *out);
+int ss_resample_stream_flush_device(const ss_resampler *rs, size_t n_active, const int32_t *d_slots, size_t pool_streams, float *d_pool,
+                                    float *d_out, void *stream);
+int ss_resample_stream_flush(const ss_resampler *rs, size_t n_active, const int32_t *slots, size_t pool_streams, float *pool, float *out);
+
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`
  * computes clips [lo, hi) of ss_shard_bounds on its own device with the *_device entry points.  The north-star's "RCCL

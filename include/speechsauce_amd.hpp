@@ -599,6 +599,46 @@ inline std::vector<float> power_to_db_packed(const std::vector<float> &s, const 
     return out;
 }
 
+// Polyphase windowed-sinc resampler for one pair of rates (ss_resample*; not in the reference crate): torchaudio's default
+// sinc_interp_hann filter.  The handle is shared by copies; the first call that runs uploads its table.
+class Resampler {
+public:
+    Resampler(uint32_t orig_rate, uint32_t new_rate, uint32_t lowpass_filter_width = 6, float rolloff = 0.99f) : orig_(orig_rate), new_(new_rate)
+    {
+        ss_resampler *raw = nullptr;
+        check(ss_resampler_create(orig_rate, new_rate, lowpass_filter_width, rolloff, &raw));
+        h_ = std::shared_ptr<ss_resampler>(raw, ss_resampler_destroy);
+        check(ss_resampler_info(raw, &info_));
+    }
+    const ss_resample_info &info() const { return info_; }
+    const ss_resampler *handle() const { return h_.get(); }
+    size_t out_len(size_t n_samples) const { return (n_samples * info_.n + info_.o - 1) / info_.o; }
+    // one clip -> its out_len(x.size()) resampled samples
+    std::vector<float> resample(const std::vector<float> &x) const
+    {
+        std::vector<float> out(out_len(x.size()));
+        check(ss_resample(h_.get(), x.data(), 1, x.size(), x.size(), out.data(), out.size()));
+        return out;
+    }
+    // clips packed end to end, clip b = x[sample_offsets[b] .. sample_offsets[b+1]) -> the resampled block; out_offsets receives
+    // its offsets, which are the sample_offsets of the packed feature calls on that block
+    std::vector<float> resample_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, std::vector<int64_t> &out_offsets) const
+    {
+        if (sample_offsets.empty() || sample_offsets.back() < 0 || static_cast<size_t>(sample_offsets.back()) > x.size())
+            throw Error(SS_ERR_ARG, "resample_packed: shape mismatch");
+        out_offsets.assign(sample_offsets.size(), 0);
+        check(ss_resample_packed_offsets(orig_, new_, sample_offsets.size() - 1, sample_offsets.data(), out_offsets.data()));
+        std::vector<float> out(static_cast<size_t>(out_offsets.back()));
+        check(ss_resample_packed(h_.get(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), out_offsets.data(), out.data()));
+        return out;
+    }
+
+private:
+    uint32_t orig_, new_;
+    std::shared_ptr<ss_resampler> h_;
+    ss_resample_info info_{};
+};
+
 // processing.rs:222-254
 inline std::vector<float> derivative_extraction(const std::vector<float> &feat, size_t rows, size_t cols, size_t delta_windows)
 {

@@ -1753,6 +1753,10 @@ int stft_host(const ss_config *cfg, int out_kind, const T *x, size_t channels, s
 
 }  // namespace
 
+namespace ss {
+void note_kernel(const char *name) { g_last_kernel = name; }
+}  // namespace ss
+
 extern "C" {
 
 int ss_device_count(int *count)

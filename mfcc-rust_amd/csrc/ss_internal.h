@@ -53,6 +53,8 @@ struct HostTables {
 
 void set_error(const std::string &msg);
 int fail(int status, const std::string &msg);
+// what ss_last_kernel_name() reports on this thread, for launchers outside ss_api.hip (`name` must outlive the process: a literal)
+void note_kernel(const char *name);
 
 int validate(const ss_params &p);
 int derive(const ss_params &p, Derived &d);

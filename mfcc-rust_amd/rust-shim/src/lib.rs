@@ -179,6 +179,20 @@ extern "C" {
                                    cols: usize, order: usize, window: usize, pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_add_deltas_stream_flush(n_active: usize, slots: *const i32, pool_streams: usize, cols: usize, order: usize, window: usize,
                                   pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_resample_packed_offsets(orig_rate: u32, new_rate: u32, n_clips: usize, sample_offsets: *const i64, out_offsets: *mut i64) -> c_int;
+    fn ss_resampler_create(orig_rate: u32, new_rate: u32, lowpass_filter_width: u32, rolloff: f32, out: *mut *mut c_void) -> c_int;
+    fn ss_resampler_destroy(rs: *mut c_void);
+    fn ss_resampler_info(rs: *const c_void, info: *mut ResampleInfo) -> c_int;
+    fn ss_resample(rs: *const c_void, x: *const f32, batch: usize, n_samples: usize, ld: usize, out: *mut f32, ld_out: usize) -> c_int;
+    fn ss_resample_packed(rs: *const c_void, x: *const f32, n_clips: usize, sample_offsets: *const i64, out_offsets: *const i64,
+                          out: *mut f32) -> c_int;
+    fn ss_resample_packed_i16(rs: *const c_void, x: *const i16, n_clips: usize, sample_offsets: *const i64, scale: f32,
+                              out_offsets: *const i64, out: *mut f32) -> c_int;
+    fn ss_resample_stream_state_len(rs: *const c_void, state_len: *mut usize) -> c_int;
+    fn ss_resample_stream_packed(rs: *const c_void, x: *const f32, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                                 pool_streams: usize, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_resample_stream_flush(rs: *const c_void, n_active: usize, slots: *const i32, pool_streams: usize, pool: *mut f32,
+                                out: *mut f32) -> c_int;
     fn ss_derivative_extraction(feat: *const f32, rows: usize, cols: usize, delta_windows: usize, out: *mut f32) -> c_int;
     fn ss_extract_derivative_feature(feat: *const f32, rows: usize, cols: usize, cube: *mut f32) -> c_int;
     fn ss_shard_bounds(n_items: usize, world: c_int, rank: c_int, lo: *mut usize, hi: *mut usize) -> c_int;
@@ -1150,6 +1164,139 @@ impl<A: num_traits::real::Real, I: Dimension> ArrayLog<A, I> for Array<A, I> {
 // ---------------------------------------------------------------------------------------------------------------------------
 // The reference's module paths (speechsauce/src/lib.rs:2-6).  Re-exports only: one implementation, two spellings.
 // ---------------------------------------------------------------------------------------------------------------------------
+
+/// `ss_resample_info`: the sizes of one conversion (see `ss_resample_sizes` in the C header).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct ResampleInfo {
+    pub o: u32,
+    pub n: u32,
+    pub width: u32,
+    pub taps: u32,
+    pub lookback: u32,
+    pub lookahead: u32,
+    pub latency_periods: u32,
+    pub tile_outputs: u32,
+}
+
+/// Polyphase windowed-sinc resampler for one pair of rates: torchaudio's default `sinc_interp_hann` filter (`lowpass_filter_width = 6`,
+/// `rolloff = 0.99`).  Not in the reference crate.  Owns an `ss_resampler`; the table is uploaded by the first call that runs.
+pub struct Resampler {
+    raw: *mut c_void,
+    orig_rate: u32,
+    new_rate: u32,
+    info: ResampleInfo,
+}
+
+unsafe impl Send for Resampler {}
+unsafe impl Sync for Resampler {}
+
+impl Drop for Resampler {
+    fn drop(&mut self) {
+        unsafe { ss_resampler_destroy(self.raw) }
+    }
+}
+
+impl Resampler {
+    pub fn new(orig_rate: u32, new_rate: u32, lowpass_filter_width: u32, rolloff: f32) -> Result<Resampler, Error> {
+        let mut raw: *mut c_void = std::ptr::null_mut();
+        check(unsafe { ss_resampler_create(orig_rate, new_rate, lowpass_filter_width, rolloff, &mut raw) })?;
+        let mut rs = Resampler { raw, orig_rate, new_rate, info: ResampleInfo::default() };
+        check(unsafe { ss_resampler_info(rs.raw, &mut rs.info) })?;
+        Ok(rs)
+    }
+
+    pub fn info(&self) -> ResampleInfo {
+        self.info
+    }
+
+    /// `ceil(n * n_samples / o)`
+    pub fn out_len(&self, n_samples: usize) -> usize {
+        (n_samples * self.info.n as usize + self.info.o as usize - 1) / self.info.o as usize
+    }
+
+    /// One clip -> its `out_len` resampled samples.
+    pub fn resample(&self, x: &[f32]) -> Result<Vec<f32>, Error> {
+        let mut out = vec![0f32; self.out_len(x.len())];
+        check(unsafe { ss_resample(self.raw, x.as_ptr(), 1, x.len(), x.len(), out.as_mut_ptr(), out.len()) })?;
+        Ok(out)
+    }
+
+    /// Out offsets of packed clips: also the sample offsets of the packed feature calls on the resampled block.
+    pub fn packed_offsets(&self, sample_offsets: &[i64]) -> Result<Vec<i64>, Error> {
+        if sample_offsets.is_empty() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must not be empty".to_string() });
+        }
+        let mut oo = vec![0i64; sample_offsets.len()];
+        check(unsafe { ss_resample_packed_offsets(self.orig_rate, self.new_rate, sample_offsets.len() - 1, sample_offsets.as_ptr(), oo.as_mut_ptr()) })?;
+        Ok(oo)
+    }
+
+    /// Clips packed end to end (clip b = `x[sample_offsets[b] .. sample_offsets[b + 1]]`) -> (the resampled block, its offsets); every
+    /// clip is resampled on its own samples, one launch for all.
+    pub fn resample_packed(&self, x: &[f32], sample_offsets: &[i64]) -> Result<(Vec<f32>, Vec<i64>), Error> {
+        let oo = self.packed_offsets(sample_offsets)?;
+        if sample_offsets[sample_offsets.len() - 1] as usize > x.len() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets ends past the block".to_string() });
+        }
+        let mut out = vec![0f32; oo[oo.len() - 1] as usize];
+        check(unsafe { ss_resample_packed(self.raw, x.as_ptr(), oo.len() - 1, sample_offsets.as_ptr(), oo.as_ptr(), out.as_mut_ptr()) })?;
+        Ok((out, oo))
+    }
+
+    /// The same from 16-bit PCM: sample = `pcm * scale`, `scale` a power of two (`2^-15` for normalised audio).
+    pub fn resample_packed_i16(&self, x: &[i16], sample_offsets: &[i64], scale: f32) -> Result<(Vec<f32>, Vec<i64>), Error> {
+        let oo = self.packed_offsets(sample_offsets)?;
+        if sample_offsets[sample_offsets.len() - 1] as usize > x.len() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets ends past the block".to_string() });
+        }
+        let mut out = vec![0f32; oo[oo.len() - 1] as usize];
+        check(unsafe { ss_resample_packed_i16(self.raw, x.as_ptr(), oo.len() - 1, sample_offsets.as_ptr(), scale, oo.as_ptr(), out.as_mut_ptr()) })?;
+        Ok((out, oo))
+    }
+
+    /// Floats per stream of the pool `stream_packed` carries: `latency_periods * o + lookback + 1`.
+    pub fn stream_state_len(&self) -> Result<usize, Error> {
+        let mut len = 0usize;
+        check(unsafe { ss_resample_stream_state_len(self.raw, &mut len) })?;
+        Ok(len)
+    }
+
+    /// Live streams fed whole periods of `o` samples: entry i owns `x[sample_offsets[i] .. sample_offsets[i + 1]]`, row `slots[i]` of
+    /// `pool` (`[pool_streams, stream_state_len]`, all zeros: fresh streams) and `n` outputs per period, `latency_periods * n` outputs
+    /// late (zeros while the stream's output time is negative).
+    pub fn stream_packed(&self, x: &[f32], sample_offsets: &[i64], slots: &[i32], pool: &mut Array2<f32>) -> Result<Vec<f32>, Error> {
+        let len = self.stream_state_len()?;
+        if sample_offsets.len() != slots.len() + 1 {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must have one entry more than slots".to_string() });
+        }
+        if pool.ncols() != len || !pool.is_standard_layout() {
+            return Err(Error { status: SS_ERR_ARG, detail: "pool must be a standard-layout [pool_streams, state_len] block".to_string() });
+        }
+        let total = sample_offsets[slots.len()];
+        if total < 0 || total as usize > x.len() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets ends past the block".to_string() });
+        }
+        let mut out = vec![0f32; total as usize / self.info.o as usize * self.info.n as usize];
+        check(unsafe {
+            ss_resample_stream_packed(self.raw, x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool.nrows(), pool.as_mut_ptr(),
+                                      out.as_mut_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// The last `latency_periods * n` outputs of the streams in `slots` (entry i: that many outputs from `i * latency_periods * n` on);
+    /// afterwards their pool rows are zero (fresh streams).
+    pub fn stream_flush(&self, slots: &[i32], pool: &mut Array2<f32>) -> Result<Vec<f32>, Error> {
+        let len = self.stream_state_len()?;
+        if pool.ncols() != len || !pool.is_standard_layout() {
+            return Err(Error { status: SS_ERR_ARG, detail: "pool must be a standard-layout [pool_streams, state_len] block".to_string() });
+        }
+        let mut out = vec![0f32; slots.len() * self.info.latency_periods as usize * self.info.n as usize];
+        check(unsafe { ss_resample_stream_flush(self.raw, slots.len(), slots.as_ptr(), pool.nrows(), pool.as_mut_ptr(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+}
 
 /// speechsauce::config (config.rs)
 pub mod config {

@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import SpeechSauceError, SsParams, make_params  # noqa: F401
+from ._lib import SpeechSauceError, SsParams, SsResampleInfo, make_params  # noqa: F401
 
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
@@ -27,6 +27,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "MelSpectrogramStream", "StftStream",
            "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool", "CmvnStreamPool",
            "add_deltas", "add_deltas_packed", "AddDeltasStreamPool",
+           "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
            "SpeechConfig", "SpeechSauceError"]
 
 
@@ -1923,4 +1924,303 @@ class AddDeltasStreamPool:
                     d_sl.record_stream(torch.cuda.current_stream())
         if n_active:
             self.rows_seen[sl] = 0
+        return out
+
+
+# ---- polyphase sinc resampling ahead of the feature calls (ss_resample* in include/speechsauce_amd.h) -------------
+
+class Resampler:
+    """Owns an ``ss_resampler`` handle: the windowed-sinc filter of ``torchaudio.functional.resample`` (``sinc_interp_hann``) for one
+    pair of rates, and -- after the first device call -- its device copy.  ``info`` holds o, n, width, taps, lookback, lookahead,
+    latency_periods and tile_outputs."""
+
+    def __init__(self, orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99):
+        self._h = C.c_void_p()
+        self._owner = _lib.lib()  # the build that created the handle destroys it
+        _lib.check(self._owner.ss_resampler_create(int(orig_rate), int(new_rate), int(lowpass_filter_width), float(rolloff), C.byref(self._h)))
+        self.orig_rate, self.new_rate = int(orig_rate), int(new_rate)
+        self.info = SsResampleInfo()
+        _lib.check(self._owner.ss_resampler_info(self._h, C.byref(self.info)))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                self._owner.ss_resampler_destroy(h)
+            except Exception:
+                pass
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    def out_len(self, n_samples: int) -> int:
+        """ceil(n * n_samples / o)"""
+        return (int(n_samples) * self.info.n + self.info.o - 1) // self.info.o
+
+
+@lru_cache(maxsize=32)
+def _get_resampler(orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99, device: int = -1) -> Resampler:
+    """Memoised handle factory; ``device`` is part of the key as for ``_get_speech_config``: the handle's table lives in the memory
+    of the device of its first device call."""
+    return Resampler(orig_rate, new_rate, lowpass_filter_width, rolloff)
+
+
+_lib._on_switch.append(_get_resampler.cache_clear)  # a handle belongs to the library that created it
+
+
+def _check_rates(orig_rate, new_rate, what):
+    if int(orig_rate) != orig_rate or int(new_rate) != new_rate or int(orig_rate) <= 0 or int(new_rate) <= 0:
+        raise ValueError(f"{what}: the rates must be positive integers, got {orig_rate!r} and {new_rate!r}")
+    return int(orig_rate), int(new_rate)
+
+
+def _resample_packed(sig, so, rs: Resampler, scale):
+    """packed samples [N], sample offsets so (host int64) -> (out [sum out_len], out offsets (host int64))"""
+    lib = _lib.lib()
+    i16, sc = ("", []) if scale is None else ("_i16", [scale])
+    n = so.size - 1
+    oo = np.empty_like(so)
+    _lib.check(lib.ss_resample_packed_offsets(rs.orig_rate, rs.new_rate, n, so.ctypes.data, oo.ctypes.data))
+    total_in, total_out = int(so[-1]), int(oo[-1])
+    if _is_torch(sig):
+        import torch
+
+        x = sig.contiguous()
+        out = torch.empty((total_out,), dtype=torch.float32, device=x.device)
+        if n and total_out:
+            with torch.cuda.device(x.device):
+                dso, doo = torch.from_numpy(so).to(x.device), torch.from_numpy(oo).to(x.device)
+                _lib.check(getattr(lib, f"ss_resample_packed{i16}_device")(rs.handle, x.data_ptr(), n, dso.data_ptr(), *sc, doo.data_ptr(), total_in,
+                                                                          total_out, out.data_ptr(), _stream_ptr()))
+                for t in (x, dso, doo):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                    t.record_stream(torch.cuda.current_stream())
+        return out, oo
+    x = np.ascontiguousarray(sig)
+    out = np.empty((total_out,), dtype=np.float32)
+    if n and total_out:
+        _lib.check(getattr(lib, f"ss_resample_packed{i16}")(rs.handle, x.ctypes.data, n, so.ctypes.data, *sc, oo.ctypes.data, out.ctypes.data))
+    return out, oo
+
+
+def resample(x, orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99, pcm_scale=None):
+    """``torchaudio.functional.resample(x, orig_rate, new_rate)`` with its default ``sinc_interp_hann`` filter, of one clip [L] or of
+    every row of a batch [B, L] -> [ceil(n L / o)] or [B, ceil(n L / o)] float32.  numpy in -> the host-pointer call; a ROCm tensor
+    stays on the device (current stream, one launch).  ``pcm_scale``: the samples are int16 PCM, sample = int16 * pcm_scale (a power
+    of two), converted on load.  Equal rates return ``x`` unchanged, as torchaudio does."""
+    what = "resample"
+    orig_rate, new_rate = _check_rates(orig_rate, new_rate, what)
+    if orig_rate == new_rate:
+        return x
+    sig, scale = _require_signal(x, (1, 2), what, pcm_scale)
+    rs = _get_resampler(orig_rate, new_rate, int(lowpass_filter_width), float(rolloff), _device_key(sig))
+    lib = _lib.lib()
+    i16, sc = ("", []) if scale is None else ("_i16", [scale])
+    one = len(sig.shape) == 1
+    batch, L = (1, int(sig.shape[0])) if one else (int(sig.shape[0]), int(sig.shape[1]))
+    out_len = rs.out_len(L)
+    if _is_torch(sig):
+        import torch
+
+        v = sig.reshape(1, L) if one else sig
+        if L and v.stride(1) != 1:
+            v = v.contiguous()
+        ld = int(v.stride(0)) if batch > 1 and L else L
+        if ld < L:
+            v, ld = v.contiguous(), L
+        out = torch.empty((batch, out_len), dtype=torch.float32, device=v.device)
+        if batch and out_len:
+            with torch.cuda.device(v.device):
+                _lib.check(getattr(lib, f"ss_resample{i16}_device")(rs.handle, v.data_ptr(), batch, L, ld, *sc, out.data_ptr(), out_len, _stream_ptr()))
+                v.record_stream(torch.cuda.current_stream())
+        return out[0] if one else out
+    v = np.ascontiguousarray(sig).reshape(batch, L)
+    out = np.empty((batch, out_len), dtype=np.float32)
+    if batch and out_len:
+        _lib.check(getattr(lib, f"ss_resample{i16}")(rs.handle, v.ctypes.data, batch, L, L, *sc, out.ctypes.data, out_len))
+    return out[0] if one else out
+
+
+def resample_packed(signal, lengths, orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99, pcm_scale=None):
+    """``resample`` of clips of different lengths packed end to end in one 1-D signal (float32, or int16 with ``pcm_scale``) ->
+    (out [sum out_len_b] float32, out_lengths [n] int64 on the host): clip b's samples are what ``resample`` returns for that clip
+    alone, bit for bit -- taps past a clip's end read zeros, never the next clip.  One launch for all clips.  ``(out, out_lengths)``
+    is the ``(signal, lengths)`` of ``mfcc_packed`` and the other packed feature calls at ``new_rate``."""
+    what = "resample_packed"
+    orig_rate, new_rate = _check_rates(orig_rate, new_rate, what)
+    sig, scale = _require_signal(signal, (1,), what, pcm_scale)
+    so = _sample_offsets(lengths, sig.shape[0], what)
+    if orig_rate == new_rate:
+        return signal, np.diff(so)
+    rs = _get_resampler(orig_rate, new_rate, int(lowpass_filter_width), float(rolloff), _device_key(sig))
+    out, oo = _resample_packed(sig, so, rs, scale)
+    return out, np.diff(oo)
+
+
+def resample_list(signals, orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99, pcm_scale=None):
+    """A list of 1-D clips of any lengths -> the list of their resampled clips (views of one block): the clips are packed once and
+    served by one ``resample_packed`` call."""
+    what = "resample_list"
+    sigs = [_require_signal(x, (1,), what, pcm_scale)[0] for x in signals]
+    if not sigs:
+        return []
+    on_device = [_is_torch(x) for x in sigs]
+    if any(on_device) and not all(on_device):
+        raise ValueError(f"{what}: the clips of one call must all be device tensors or all host arrays")
+    if all(on_device):
+        import torch
+
+        if any(x.device != sigs[0].device for x in sigs):
+            raise ValueError(f"{what}: the clips of one call must live on one device")
+        packed = torch.cat(sigs)
+    else:
+        packed = np.concatenate(sigs)
+    out, lens = resample_packed(packed, [int(x.shape[0]) for x in sigs], orig_rate, new_rate, lowpass_filter_width, rolloff, pcm_scale)
+    oo = np.concatenate([[0], np.cumsum(lens)]).tolist()
+    return [out[oo[b]:oo[b + 1]] for b in range(len(sigs))]
+
+
+class ResampleStreamPool:
+    """``resample`` over the samples of live streams, with a fixed latency of ``latency_periods`` periods: a stream is fed whole
+    periods of ``o`` samples (``period_in``; 441 samples = 10 ms for 44.1 kHz -> 16 kHz) and gets ``n`` outputs (``period_out``) per
+    period, ``lag = latency_periods * n`` outputs late (zeros while the stream's output time is negative: the first ``lag`` outputs
+    after a reset are warm-up).  ``pool.push(samples, sample_offsets, slots)`` takes a packed block, the offsets of its entries and the
+    pool rows they belong to, and returns ``[total / o * n]`` outputs: entry i's are ``out[sample_offsets[i] // o * n :
+    sample_offsets[i + 1] // o * n]``.  ``flush(slots)`` returns the last ``lag`` outputs of those streams, ``[len(slots), lag]``, and
+    makes them fresh.  However a stream is cut into calls, its outputs plus the flush, the first ``lag`` dropped, are bit for bit
+    ``resample`` of the whole clip.  float32 samples, or int16 with ``pcm_scale`` (a stream may mix both).  numpy in -> the
+    host-pointer calls, ROCm tensors in -> the device calls on the current stream.  The output feeds ``MfccStreamPool`` once the
+    caller has buffered it to whole hops.  See ``ss_resample_stream_packed`` in ``include/speechsauce_amd.h``."""
+
+    _what = "ResampleStreamPool"
+
+    def __init__(self, pool_streams, orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99):
+        what = self._what
+        if int(pool_streams) < 1:
+            raise ValueError(f"{what}: pool_streams must be at least 1")
+        orig_rate, new_rate = _check_rates(orig_rate, new_rate, what)
+        self.pool_streams = int(pool_streams)
+        self._args = (orig_rate, new_rate, int(lowpass_filter_width), float(rolloff))
+        rs = _get_resampler(*self._args)
+        self.period_in, self.period_out, self.latency_periods = rs.info.o, rs.info.n, rs.info.latency_periods
+        self.lag = self.latency_periods * self.period_out
+        L = C.c_size_t()
+        _lib.check(_lib.lib().ss_resample_stream_state_len(rs.handle, C.byref(L)))
+        self.state_len = L.value
+        self.periods_seen = np.zeros(self.pool_streams, dtype=np.int64)
+        self._state = None
+        self._where = None
+
+    @property
+    def state(self):
+        """[pool_streams, state_len] float32: a torch tensor on the device of the first samples, or a numpy array; None before the
+        first call."""
+        return self._state
+
+    def _slots(self, slots):
+        slot_list = [int(v) for v in slots]
+        seen = set()
+        for i, v in enumerate(slot_list):
+            if not 0 <= v < self.pool_streams:
+                raise ValueError(f"{self._what}: slot {v} of entry {i} is outside the pool of {self.pool_streams} streams")
+            if v in seen:
+                raise ValueError(f"{self._what}: slot {v} is named twice in one call")
+            seen.add(v)
+        return slot_list
+
+    def reset(self, slots=None):
+        """Zero the state (and ``periods_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
+        idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
+        if slots is None:
+            self.periods_seen[:] = 0
+            if self._state is not None:
+                self._state[...] = 0
+        elif idx:
+            self.periods_seen[idx] = 0
+            if self._state is not None:
+                self._state[idx] = 0
+
+    def push(self, samples, sample_offsets, slots, pcm_scale=None):
+        what = self._what
+        x, scale = _require_signal(samples, (1,), what, pcm_scale)
+        total = int(x.shape[0])
+        so = np.asarray(sample_offsets.cpu() if _is_torch(sample_offsets) else sample_offsets)
+        if so.ndim != 1 or so.size < 1:
+            raise ValueError(f"{what}: sample_offsets must be 1-D with one entry more than slots")
+        if not np.issubdtype(so.dtype, np.integer):
+            raise TypeError(f"{what}: sample_offsets must be integers, got {so.dtype}")
+        so = np.ascontiguousarray(so, dtype=np.int64)
+        slot_list = self._slots(slots)
+        if len(slot_list) != so.size - 1:
+            raise ValueError(f"{what}: {so.size - 1} entries in sample_offsets but {len(slot_list)} slots")
+        if so[0] != 0 or (np.diff(so) < 0).any() or so[-1] > total:
+            raise ValueError(f"{what}: sample_offsets must start at 0, not decrease and end within the block's {total} samples")
+        if (np.diff(so) % self.period_in).any():
+            raise ValueError(f"{what}: every entry must bring whole periods of {self.period_in} samples")
+        on_dev = _is_torch(x)
+        where = ("cuda", x.device.index) if on_dev else ("host",)
+        if self._where is not None and where != self._where:
+            raise ValueError(f"{what}: the pool lives on {self._where}, these samples on {where}")
+        lib, n_active = _lib.lib(), len(slot_list)
+        rs = _get_resampler(*self._args, _device_key(x))
+        i16, sc = ("", []) if scale is None else ("_i16", [scale])
+        sl = np.asarray(slot_list, dtype=np.int32)
+        n_in = int(so[-1])
+        n_out = n_in // self.period_in * self.period_out
+        if on_dev:
+            import torch
+
+            x = x.contiguous()
+            state = self._state if self._state is not None else torch.zeros((self.pool_streams, self.state_len), dtype=torch.float32,
+                                                                            device=x.device)
+            out = torch.empty((n_out,), dtype=torch.float32, device=x.device)
+            if n_active and n_in:
+                with torch.cuda.device(x.device):
+                    d_so, d_sl = torch.from_numpy(so).to(x.device), torch.from_numpy(sl).to(x.device)
+                    _lib.check(getattr(lib, f"ss_resample_stream_packed{i16}_device")(rs.handle, x.data_ptr(), n_active, d_so.data_ptr(), n_in,
+                                                                                      d_sl.data_ptr(), self.pool_streams, *sc, state.data_ptr(),
+                                                                                      out.data_ptr(), _stream_ptr()))
+                    for t in (x, d_so, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                        t.record_stream(torch.cuda.current_stream())
+        else:
+            x = np.ascontiguousarray(x)
+            state = self._state if self._state is not None else np.zeros((self.pool_streams, self.state_len), dtype=np.float32)
+            out = np.empty((n_out,), dtype=np.float32)
+            if n_active and n_in:
+                _lib.check(getattr(lib, f"ss_resample_stream_packed{i16}")(rs.handle, x.ctypes.data, n_active, so.ctypes.data, sl.ctypes.data,
+                                                                           self.pool_streams, *sc, state.ctypes.data, out.ctypes.data))
+        self._state, self._where = state, where  # only once the call went through
+        if n_active:
+            self.periods_seen[sl] += np.diff(so) // self.period_in
+        return out
+
+    __call__ = push
+
+    def flush(self, slots):
+        """The last ``lag`` outputs of the given streams, ``[len(slots), lag]`` (zeros where the stream's output time is negative);
+        afterwards those streams are fresh.  Before the pool's first call there is no state anywhere: the outputs are zeros in a numpy
+        array."""
+        slot_list = self._slots(slots)
+        lib, n_active = _lib.lib(), len(slot_list)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        if self._state is None or not _is_torch(self._state):
+            out = np.zeros((n_active, self.lag), dtype=np.float32)
+            if n_active and self._state is not None:
+                rs = _get_resampler(*self._args, _device_key(self._state))
+                _lib.check(lib.ss_resample_stream_flush(rs.handle, n_active, sl.ctypes.data, self.pool_streams, self._state.ctypes.data,
+                                                        out.ctypes.data))
+        else:
+            import torch
+
+            state = self._state
+            out = torch.empty((n_active, self.lag), dtype=torch.float32, device=state.device)
+            if n_active:
+                with torch.cuda.device(state.device):
+                    rs = _get_resampler(*self._args, _device_key(state))
+                    d_sl = torch.from_numpy(sl).to(state.device)
+                    _lib.check(lib.ss_resample_stream_flush_device(rs.handle, n_active, d_sl.data_ptr(), self.pool_streams, state.data_ptr(),
+                                                                   out.data_ptr(), _stream_ptr()))
+                    d_sl.record_stream(torch.cuda.current_stream())
+        if n_active:
+            self.periods_seen[sl] = 0
         return out

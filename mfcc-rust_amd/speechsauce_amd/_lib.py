@@ -54,6 +54,12 @@ class SsParams(C.Structure):
     ]
 
 
+class SsResampleInfo(C.Structure):
+    """ss_resample_info (include/speechsauce_amd.h)."""
+
+    _fields_ = [(name, C.c_uint32) for name in ("o", "n", "width", "taps", "lookback", "lookahead", "latency_periods", "tile_outputs")]
+
+
 class SpeechSauceError(RuntimeError):
     """Raised where the reference would panic (or where HIP fails)."""
 
@@ -68,6 +74,7 @@ _lib = None
 # name -> (restype, argtypes); every symbol include/speechsauce_amd.h declares (LAB_PROTOTYPES: include/speechsauce_amd_debug.h)
 _P = C.POINTER
 _cfg = C.c_void_p
+_rs = C.c_void_p  # ss_resampler *
 _fp = C.c_void_p  # float* passed as an address (numpy .ctypes.data or a device pointer)
 PROTOTYPES = {
     "ss_params_default": (C.c_int, [_P(SsParams), C.c_uint32]),
@@ -207,6 +214,30 @@ PROTOTYPES = {
     "ss_add_deltas_stream_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp]),
     "ss_add_deltas_stream_flush_device": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp, C.c_void_p]),
     "ss_add_deltas_stream_flush": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp]),
+    "ss_resample_sizes": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _P(SsResampleInfo)]),
+    "ss_resample_taps": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _fp, C.c_void_p, C.c_void_p]),
+    "ss_resample_len": (C.c_int, [C.c_uint32, C.c_uint32, C.c_size_t, _P(C.c_size_t)]),
+    "ss_resample_packed_offsets": (C.c_int, [C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ss_resampler_create": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _P(_rs)]),
+    "ss_resampler_destroy": (None, [_rs]),
+    "ss_resampler_info": (C.c_int, [_rs, _P(SsResampleInfo)]),
+    "ss_resample_device": (C.c_int, [_rs, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp, C.c_size_t, C.c_void_p]),
+    "ss_resample": (C.c_int, [_rs, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp, C.c_size_t]),
+    "ss_resample_i16_device": (C.c_int, [_rs, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_size_t, C.c_void_p]),
+    "ss_resample_i16": (C.c_int, [_rs, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_size_t]),
+    "ss_resample_packed_device": (C.c_int, [_rs, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, _fp, C.c_void_p]),
+    "ss_resample_packed": (C.c_int, [_rs, _fp, C.c_size_t, C.c_void_p, C.c_void_p, _fp]),
+    "ss_resample_packed_i16_device": (C.c_int, [_rs, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_size_t, _fp,
+                                                C.c_void_p]),
+    "ss_resample_packed_i16": (C.c_int, [_rs, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, _fp]),
+    "ss_resample_stream_state_len": (C.c_int, [_rs, _P(C.c_size_t)]),
+    "ss_resample_stream_packed_device": (C.c_int, [_rs, _fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_resample_stream_packed": (C.c_int, [_rs, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, _fp]),
+    "ss_resample_stream_packed_i16_device": (C.c_int, [_rs, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float,
+                                                       _fp, _fp, C.c_void_p]),
+    "ss_resample_stream_packed_i16": (C.c_int, [_rs, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp]),
+    "ss_resample_stream_flush_device": (C.c_int, [_rs, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_resample_stream_flush": (C.c_int, [_rs, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp]),
     "ss_shard_bounds": (C.c_int, [C.c_size_t, C.c_int, C.c_int, _P(C.c_size_t), _P(C.c_size_t)]),
     "ss_all_gather_features": (C.c_int, [C.c_void_p, _fp, C.c_size_t, _fp, C.c_void_p]),
     "ss_gather_features": (C.c_int, [C.c_void_p, _fp, C.c_size_t, _fp, C.c_int, C.c_int, C.c_int, C.c_void_p]),
