@@ -778,8 +778,15 @@ int port_mfe_f32(const orc_params *p, const float *x, size_t n, float *feat, flo
     const size_t N = p->fft_points, F = N / 2 + 1, M = p->num_filters;
     if (flen > N || !is_pow2(N) || N < 4) return ORC_ERR_BAD_CONFIG;
     if (p->spectrum_exponent != 1 && p->spectrum_exponent != 2) return ORC_ERR_BAD_CONFIG;
+    /* a framing or pad mode this port does not implement is refused: it never returns numbers for another framing's frames */
+    if (p->framing != ORC_FRAMING_CONTRACT && p->framing != ORC_FRAMING_LITERAL && p->framing != ORC_FRAMING_CENTER &&
+        p->framing != ORC_FRAMING_PADDED) return ORC_ERR_BAD_CONFIG;
+    if (p->framing == ORC_FRAMING_CENTER && p->pad_mode != ORC_PAD_REFLECT && p->pad_mode != ORC_PAD_CONSTANT) return ORC_ERR_BAD_CONFIG;
+    /* one reflection must reach every padded sample (np.pad would reflect again) */
+    if (p->framing == ORC_FRAMING_CENTER && p->pad_mode == ORC_PAD_REFLECT && (T - 1) * step + (flen - 1 - flen / 2) > 2 * (n - 1))
+        return ORC_ERR_SHORT_SIGNAL;
 
-    /* pass 1: stack_frames -> frames[T, flen] (contract framing; literal handled as in the oracle) */
+    /* pass 1: stack_frames -> frames[T, flen] (contract / padded framing; literal and centred handled as in the oracle) */
     float *frames = (float *)calloc(T * flen, sizeof(float));
     float *pre = NULL;
     const float *src = x;
@@ -792,6 +799,18 @@ int port_mfe_f32(const orc_params *p, const float *x, size_t n, float *feat, flo
     for (size_t t = 0; t < T; ++t) {
         if (p->framing == ORC_FRAMING_LITERAL) {
             if (T <= 2) memcpy(frames + t * flen, src, (flen & ~(size_t)1) * sizeof(float));
+        } else if (p->framing == ORC_FRAMING_CENTER) {
+            /* The reference's stack_frames has no centred framing: this branch follows the f64 oracle's definition
+             * (orc_power_spectrum): frame t is centred on t*step, np.pad(y, flen/2, mode) semantics outside the clip, and y is
+             * the pre-emphasised clip (pre-emphasis over the clip first, then the padding). */
+            for (size_t i = 0; i < flen; ++i) {
+                long long pos = (long long)(t * step + i) - (long long)(flen / 2);
+                if (pos < 0 || pos >= (long long)n) {
+                    if (p->pad_mode != ORC_PAD_REFLECT) continue; /* zeros */
+                    pos = pos < 0 ? -pos : 2 * ((long long)n - 1) - pos;
+                }
+                frames[t * flen + i] = src[pos];
+            }
         } else {
             const size_t have = t * step >= n ? 0 : (n - t * step < flen ? n - t * step : flen); /* PADDED: zeros past the signal */
             memcpy(frames + t * flen, src + t * step, have * sizeof(float));

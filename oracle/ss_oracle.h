@@ -112,7 +112,9 @@ int orc_extract_derivative_feature(const float *feat, size_t rows, size_t cols, 
 
 /* Reference-shaped single-thread f32 port: pass-for-pass the structure of the Rust code
  * (materialised frames, pad copy, per-row FFT, magnitude pass, dense mel GEMM, full DCT).
- * This is the timed CPU stand-in ("cpu_baseline.kind = port"). */
+ * This is the timed CPU stand-in ("cpu_baseline.kind = port").  Framing: contract, literal, padded, and centred with
+ * reflect or constant padding (the reference has no centred framing: that branch follows orc_power_spectrum); any other
+ * framing or pad mode is ORC_ERR_BAD_CONFIG -- the port never returns numbers for a framing it does not implement. */
 int port_mfcc_f32(const orc_params *p, const float *x, size_t n, float *out /* T x C */);
 int port_mfe_f32(const orc_params *p, const float *x, size_t n, float *feat, float *energy);
 int port_mel_spectrogram_f32(const orc_params *p, const float *x, size_t channels, size_t n,

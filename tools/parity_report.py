@@ -25,6 +25,14 @@ ONE batch call per output kind, the kernel the call reached by name, and the met
 those of signals() with a tone that is never bin-centred, an impulse train at the family's hop and a tilted-noise class
 (family_signals).  tests/test_parity_families_cpu.py holds the f32 port to the same metrics (which cases are well-posed),
 tests/test_gpu_parity_families.py the kernels.
+
+    python tools/parity_report.py --variants profiles/parity_variants.json        (on the GPU box)
+
+The same per switch set (VARIANTS) and alternative frame length (LENGTHS) of every family: EXPECT lists, per family, the rows
+and the kernel -- prefix and tags of ss_last_kernel_name() -- that the MFCC, the mfe and the mel call of each row must reach
+(each tag is a template argument: other device code).  Per row the report holds the kernels reached, the worst value with its
+signal class and the bar per bar metric, and the cases that do not count.  tests/test_parity_variants_cpu.py is the CPU side,
+tests/test_gpu_parity_variants.py holds the kernels to the bars.
 """
 import datetime
 import json
@@ -152,7 +160,15 @@ def family_hop(fam):
     return fam["step"] if fam["path"] == "frame" else fam["hop"]
 
 
-def family_samples(fam):
+def variant_family(fam, variant):
+    """The family with the frame length / filter count of a LENGTHS row in place of its own."""
+    over = {k: variant[k] for k in ("flen", "M") if variant is not None and variant.get(k) is not None}
+    return dict(fam, **over) if over else fam
+
+
+def family_samples(fam, variant=None):
+    """Samples per clip.  Centred framing keeps this count (the oracle then gives 1 + n // hop rows)."""
+    fam = variant_family(fam, variant)
     return (fam["flen"] if fam["path"] == "frame" else fam["fft"]) + (ROWS - 1) * family_hop(fam) + 3
 
 
@@ -185,8 +201,10 @@ def family_signals(fam):
     }
 
 
-def family_kwargs(fam):
-    """(keywords of oracle.make_params, keywords of the Python front's calls)"""
+def family_kwargs(fam, variant=None):
+    """(keywords of oracle.make_params, keywords of the Python front's calls); `variant`: a row of variant_rows() -- its
+    switches go to both, its frame length / filter count replace the family's."""
+    fam = variant_family(fam, variant)
     sr = fam["sr"]
     if fam["path"] == "frame":
         okw = dict(sample_rate=sr, fft_points=fam["fft"], frame_length=fam["flen"] / sr, frame_stride=fam["step"] / sr,
@@ -195,14 +213,19 @@ def family_kwargs(fam):
         okw = dict(sample_rate=sr, fft_points=fam["fft"], frame_length=fam["hop"] / sr, frame_stride=fam["hop"] / sr, num_filters=fam["M"])
         if fam["high_frequency"] is not None:
             okw["high_frequency"] = fam["high_frequency"]
+    if variant is not None:
+        okw.update(variant["switches"])
     skw = {{"fft_points": "fft_length"}.get(k, k): v for k, v in okw.items() if k != "sample_rate"}
     return okw, skw
 
 
-def family_reference(oracle, fam, X, port=False):
+MFE_DROPS = ("num_cepstral", "dc_elimination", "dct_norm")  # what the Python front's mfe calls do not take
+
+
+def family_reference(oracle, fam, X, port=False, variant=None):
     """{kind: [S, ...] f64 oracle block} for the clips X [S, n]; port=True: the f32 port's, None where it refuses the
     configuration (fft_points that are not a power of two)."""
-    p = oracle.make_params(**family_kwargs(fam)[0])
+    p = oracle.make_params(**family_kwargs(fam, variant)[0])
     try:
         if fam["path"] == "stft":
             return {"mel": np.asarray((oracle.port_mel_spectrogram if port else oracle.mel_spectrogram)(p, X), np.float64)}
@@ -214,9 +237,9 @@ def family_reference(oracle, fam, X, port=False):
         raise
 
 
-def family_outputs(ss, fam, X):
+def family_outputs(ss, fam, X, variant=None):
     """{kind: [S, ...] block} of ONE batch call per output kind on the clips X [S, n], and {kind: kernel name}."""
-    skw = family_kwargs(fam)[1]
+    skw = family_kwargs(fam, variant)[1]
     last = ss._lib.lib().ss_last_kernel_name
     out, names = {}, {}
     if fam["path"] == "stft":
@@ -225,7 +248,7 @@ def family_outputs(ss, fam, X):
         return out, names
     out["mfcc"] = np.asarray(ss.mfcc_batch(X, fam["sr"], **skw))
     names["mfcc"] = last().decode()
-    out["mfe"] = np.asarray(ss.mfe_batch(X, fam["sr"], **{k: v for k, v in skw.items() if k != "num_cepstral"})[0])
+    out["mfe"] = np.asarray(ss.mfe_batch(X, fam["sr"], **{k: v for k, v in skw.items() if k not in MFE_DROPS})[0])
     names["mfe"] = last().decode()
     return out, names
 
@@ -238,36 +261,265 @@ def block_metrics(kind, got, want):
     return metrics(got, want, kind == "mfcc", band_axis=1 if kind == "mfe" else 0)
 
 
-def port_families(oracle, families=None):
-    """{family: {signal: {kind: metrics of the f32 port against the f64 oracle}}}; None for a family the port refuses."""
+def port_families(oracle, families=None, variant=None):
+    """{family: {signal: {kind: metrics of the f32 port against the f64 oracle}}}; None for a family the port refuses.
+    `variant`: every family of `families` under that row of variant_rows()."""
     rep = {}
     for name, fam in (families or FAMILIES).items():
-        sig = family_signals(fam)
+        sig = family_signals(variant_family(fam, variant))
         X = np.stack(list(sig.values()))
-        want, port = family_reference(oracle, fam, X), family_reference(oracle, fam, X, port=True)
+        want, port = family_reference(oracle, fam, X, variant=variant), family_reference(oracle, fam, X, port=True, variant=variant)
         rep[name] = None if port is None else {s: {k: block_metrics(k, port[k][i], want[k][i]) for k in want} for i, s in enumerate(sig)}
     return rep
 
 
-def counted(port_rep, name):
+def _keys(name, variant):
+    """Where a report keeps (family, variant) and the 128-point generic family under the same switches: the family name
+    alone without a variant (port_families), (family, variant name) with one (port_variants)."""
+    return (name, "front_generic") if variant is None else ((name, variant["name"]), ("front_generic", variant["name"]))
+
+
+def counted(port_rep, name, variant=None):
     """The (signal, kind, metric) cases of a family that count: the port's own value is at most TOL.  The chirp-z families
-    have no port: they take the signal classes of which every case counts for the 128-point generic family, minus `dc`."""
-    if port_rep.get(name) is None:
-        base = port_rep["front_generic"]
+    have no port: they take the signal classes of which every case counts for the 128-point generic family (under the same
+    variant), minus `dc`."""
+    key, generic = _keys(name, variant)
+    if port_rep.get(key) is None:
+        base = port_rep[generic]
         ok = [s for s, kinds in base.items() if s != "dc" and all(kinds[k][m] <= TOL for k in kinds for m in BAR_METRICS[k])]
         return {(s, k, m) for s in ok for k in family_kinds(FAMILIES[name]) for m in BAR_METRICS[k]}
-    return {(s, k, m) for s, kinds in port_rep[name].items() for k in kinds for m in BAR_METRICS[k] if kinds[k][m] <= TOL}
+    return {(s, k, m) for s, kinds in port_rep[key].items() for k in kinds for m in BAR_METRICS[k] if kinds[k][m] <= TOL}
 
 
-def bars(port_rep, name):
+def bars(port_rep, name, variant=None):
     """{(kind, metric): bar}: max(TOL, 1.5 x the port's worst value over the family's counted cases) -- the HIP path may not
     be worse than the reference's own arithmetic; TOL where there is no port."""
     fam = FAMILIES[name]
+    key = _keys(name, variant)[0]
     out = {(k, m): TOL for k in family_kinds(fam) for m in BAR_METRICS[k]}
-    if port_rep.get(name) is not None:
-        for s, k, m in counted(port_rep, name):
-            out[(k, m)] = max(out[(k, m)], 1.5 * port_rep[name][s][k][m])
+    if port_rep.get(key) is not None:
+        for s, k, m in counted(port_rep, name, variant):
+            out[(k, m)] = max(out[(k, m)], 1.5 * port_rep[key][s][k][m])
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the switch and frame-length builds of every family
+# ---------------------------------------------------------------------------------------------------------------------
+
+_LIB = dict(mfcc_window="hann", spectrum_exponent=2, mel_scale="slaney", mel_norm="slaney", dct_norm="ortho")
+# switch-set name -> keywords (of oracle.make_params and of the Python front alike)
+VARIANTS = {
+    "win": dict(mfcc_window="hann"),
+    "vorbis": dict(mfcc_window="vorbis"),
+    "pre": dict(preemph_coef=0.97),
+    "winpre": dict(mfcc_window="hann", preemph_coef=0.97),
+    "pow2": dict(spectrum_exponent=2),
+    "ortho": dict(dct_norm="ortho"),
+    "slaney": dict(mel_scale="slaney", mel_norm="slaney"),
+    "htk": dict(mel_scale="htk"),
+    "lib": dict(_LIB),
+    "nodc": dict(dc_elimination=False),
+    "band": dict(low_frequency=300.0),
+    "padded": dict(framing="padded"),
+    "center_reflect": dict(framing="center", pad_mode="reflect"),
+    "center_constant": dict(framing="center", pad_mode="constant"),
+    "center_lib": dict(_LIB, framing="center", pad_mode="reflect"),
+    "center_pre": dict(framing="center", pad_mode="reflect", preemph_coef=0.97),
+}
+# Alternative frame lengths (and one filter count) per family: one per first-pass class of the family's launcher.
+#   ss_mfcc_c256x2: flen <= 160 -> 10 inputs, else 16            ss_mfcc_c256 / ss_mfcc_c256w: <= 320 -> 10, <= 416 -> 13, else 16
+#   ss_mfcc_c256: flen == 320 is the `exact` build, 40 filters the symmetric-DCT builds (M = 39: `res2`, the default bank's tap counts
+#   without the symmetric DCT; M = 26: other tap counts, the run-time bank build)
+#   ss_mfcc_c512 / ss_mfcc_c1024: the frame length is a run-time argument     ss_mfcc_c2048: flen == 4096 is `exact`
+LENGTHS = {
+    "mfcc_c256x2": (dict(flen=200),),
+    "mfcc_c256": (dict(flen=256), dict(flen=400), dict(flen=512), dict(M=26), dict(M=39)),
+    "mfcc_c256w": (dict(flen=320), dict(flen=512)),
+    "mfcc_c512": (dict(flen=700),),
+    "mfcc_c1024": (dict(flen=1500),),
+    "mfcc_c2048": (dict(flen=3000),),
+    "front_generic": (dict(flen=100),),
+}
+# The switch tags each frame family's launcher has builds for (template arguments: different device code); every one of them
+# must be named by a row of the family that stays on its kernel.
+LAUNCHER_TAGS = {
+    "mfcc_c256x2": ("10", "16", "pow2", "mfe", "win"),
+    "mfcc_c256": ("win", "pre", "mfe", "pow2", "fullp", "center", "10", "13", "16", "exact", "bank421", "sym", "res2"),
+    "mfcc_c256w": ("10", "13", "16", "pow2", "mfe", "win"),
+    "mfcc_c512": ("pow2", "mfe", "win", "lib"),
+    "mfcc_c1024": ("pow2", "mfe", "win", "lib", "pre"),
+    "mfcc_c2048": ("exact", "pow2", "mfe", "win", "pre"),
+    "front_generic": (),
+    "front_generic_chirpz": ("chirpz",),
+}
+
+
+def _k(prefix, tags=""):
+    """What ss_last_kernel_name() must report: the prefix, and the tags that must be among those between its < >."""
+    return (prefix, tuple(t for t in tags.split(",") if t))
+
+
+def _same(kernel, *names):
+    return {n: kernel for n in names}
+
+
+_X2, _C, _W, _K5, _G1, _H2, _GEN = ("ss_mfcc_c256x2<", "ss_mfcc_c256<", "ss_mfcc_c256w<", "ss_mfcc_c512", "ss_mfcc_c1024",
+                                    "ss_mfcc_c2048", "ss_front_generic<")
+# family -> row name -> (MFCC kernel, mfe kernel) / (mel kernel,).  A row name is a VARIANTS name, "flenN" / "MN" (a LENGTHS
+# entry alone) or "flenN+win".  Written from the launchers (launch_frames / launch_stft in ss_api.hip and each kernel file's
+# launch_*): a build the family's kernel does not have sends the call down the ladder -- in ss_mfcc_c256's launcher `fullp` or
+# `center` with the mfe output or fused pre-emphasis, a window or pre-emphasis off the 320-sample frame, power spectra with the
+# mfe output (the wide-bank kernel takes those); padded framing everywhere and centred frames on the 256- and 4096-point
+# kernels (the generic kernel takes those).  The MFCC and the mfe call are different builds.
+EXPECT = {
+    "mfcc_c256x2": {
+        **_same((_k(_X2, "10,win"), _k(_X2, "10,mfe,win")), "win", "vorbis", "winpre"),
+        **_same((_k(_X2, "10"), _k(_X2, "10,mfe")), "pre", "ortho", "nodc", "band", "slaney"),
+        "pow2": (_k(_X2, "10,pow2"), _k(_X2, "10,pow2,mfe")),
+        "flen200": (_k(_X2, "16"), _k(_X2, "16,mfe")),
+        "flen200+win": (_k(_X2, "16,win"), _k(_X2, "16,mfe,win")),
+    },
+    "mfcc_c256": {
+        **_same((_k(_C, "10,exact,bank421,win"), _k(_C, "10,exact,bank421,mfe,win")), "win", "vorbis"),
+        "pre": (_k(_C, "10,exact,bank421,pre"), _k(_C, "10,exact,bank421,mfe,pre")),
+        "winpre": (_k(_C, "10,exact,bank421,win,pre"), _k(_C, "10,exact,bank421,mfe,win,pre")),
+        "pow2": (_k(_C, "10,exact,pow2"), _k(_W, "10,pow2,mfe")),
+        **_same((_k(_C, "10,exact,bank421,sym"), _k(_C, "10,exact,bank421,mfe")), "ortho", "nodc", "band"),
+        **_same((_k(_C, "16,fullp"), _k(_W, "10,mfe")), "slaney", "htk"),
+        "lib": (_k(_C, "16,pow2,win,fullp"), _k(_W, "10,pow2,mfe,win")),
+        "padded": (_k(_GEN, "8"), _k(_GEN, "8")),
+        **_same((_k(_C, "16,center"), _k(_W, "10,mfe")), "center_reflect", "center_constant"),
+        "center_lib": (_k(_C, "16,pow2,win,fullp,center"), _k(_W, "10,pow2,mfe,win")),
+        "center_pre": (_k(_W, "10"), _k(_W, "10,mfe")),
+        "flen256": (_k(_C, "10"), _k(_W, "10,mfe")),
+        "flen400": (_k(_C, "13,bank421,sym"), _k(_W, "13,mfe")),
+        "flen400+win": (_k(_W, "13,win"), _k(_W, "13,mfe,win")),
+        "flen512": (_k(_C, "16"), _k(_W, "16,mfe")),
+        "M26": (_k(_C, "10,exact"), _k(_W, "10,mfe")),  # tap counts 6 / 2: not the default bank's 4 / 2 / 1
+        "M39": (_k(_C, "10,exact,bank421,res2"), _k(_C, "10,exact,bank421,mfe")),  # 4 / 2 / 1, but not the 40 filters of `sym`
+    },
+    "mfcc_c256w": {
+        **_same((_k(_W, "13,win"), _k(_W, "13,mfe,win")), "win", "vorbis", "winpre"),
+        **_same((_k(_W, "13"), _k(_W, "13,mfe")), "pre", "ortho", "slaney", "htk", "nodc", "band", "center_reflect", "center_constant",
+                "center_pre"),
+        "pow2": (_k(_W, "13,pow2"), _k(_W, "13,pow2,mfe")),
+        **_same((_k(_W, "13,pow2,win"), _k(_W, "13,pow2,mfe,win")), "lib", "center_lib"),
+        "padded": (_k(_GEN, "8"), _k(_GEN, "8")),
+        "flen320": (_k(_W, "10"), _k(_W, "10,mfe")),
+        "flen512": (_k(_W, "16"), _k(_W, "16,mfe")),
+        "flen512+win": (_k(_W, "16,win"), _k(_W, "16,mfe,win")),
+    },
+    "mfcc_c512": {
+        **_same((_k(_K5, "win"), _k(_K5, "mfe,win")), "win", "vorbis", "winpre", "flen700+win"),
+        **_same((_k(_K5), _k(_K5, "mfe")), "pre", "ortho", "nodc", "band", "flen700"),
+        "pow2": (_k(_K5, "pow2"), _k(_K5, "pow2,mfe")),
+        **_same((_k(_K5, "lib"), _k(_K5, "mfe,lib")), "slaney", "htk", "center_reflect", "center_constant", "center_pre"),
+        **_same((_k(_K5, "pow2,win,lib"), _k(_K5, "pow2,mfe,win,lib")), "lib", "center_lib"),
+    },
+    "mfcc_c1024": {
+        **_same((_k(_G1, "win"), _k(_G1, "mfe,win")), "win", "vorbis", "flen1500+win"),
+        **_same((_k(_G1), _k(_G1, "mfe")), "ortho", "nodc", "band", "flen1500"),
+        "pre": (_k(_G1, "lib,pre"), _k(_G1, "mfe,lib,pre")),
+        "winpre": (_k(_G1, "win,lib,pre"), _k(_G1, "mfe,win,lib,pre")),
+        "center_pre": (_k(_G1, "lib,pre"), _k(_G1, "mfe,lib,pre")),
+        "pow2": (_k(_G1, "pow2"), _k(_G1, "pow2,mfe")),
+        **_same((_k(_G1, "lib"), _k(_G1, "mfe,lib")), "slaney", "htk", "center_reflect", "center_constant"),
+        **_same((_k(_G1, "pow2,win,lib"), _k(_G1, "pow2,mfe,win,lib")), "lib", "center_lib"),
+    },
+    "mfcc_c2048": {
+        **_same((_k(_H2, "exact,win"), _k(_H2, "exact,mfe,win")), "win", "vorbis"),
+        "pre": (_k(_H2, "pre"), _k(_H2, "mfe,pre")),
+        "winpre": (_k(_H2, "win,pre"), _k(_H2, "mfe,win,pre")),
+        "pow2": (_k(_H2, "exact,pow2"), _k(_H2, "exact,pow2,mfe")),
+        **_same((_k(_H2, "exact"), _k(_H2, "exact,mfe")), "ortho", "nodc", "band"),
+        "flen3000": (_k(_H2), _k(_H2, "mfe")),
+        "flen3000+win": (_k(_H2, "win"), _k(_H2, "mfe,win")),
+    },
+    "front_generic": _same((_k(_GEN, "6"), _k(_GEN, "6")), *VARIANTS, "flen100", "flen100+win"),
+    "front_generic_chirpz": _same((_k(_GEN, "chirpz"), _k(_GEN, "chirpz")), "win", "pre", "pow2", "slaney", "center_reflect"),
+    "mel_c256": _same((_k("ss_mel_c256"),), "slaney", "htk", "band"),
+    "mel_c512": _same((_k("ss_mel_c512"),), "slaney", "htk", "band"),
+    "mel_c1024": {**_same((_k("ss_mel_c1024", "fullp"),), "slaney", "htk"), "band": (_k("ss_mel_c1024"),)},
+    # a bank up to fs / 2 does not fit the 4096-point kernel's P rows of 1025 bins: the generic kernel
+    "mel_c2048": {**_same((_k(_GEN, "11"),), "slaney", "htk"), "band": (_k("ss_mel_c2048"),)},
+    "mel_generic_chirpz": _same((_k("ss_front_generic", "chirpz"),), "slaney"),
+}
+
+
+def variant_rows(families=None):
+    """{(family, row name): row}.  A row: family, name, switches (keywords), flen / M (None: the family's own) and
+    kernels {kind: (prefix, tags)}."""
+    rows = {}
+    for fname, table in EXPECT.items():
+        if families is not None and fname not in families:
+            continue
+        for vname, kernels in table.items():
+            shape, _, sw = vname.partition("+")
+            if shape in VARIANTS:
+                shape, sw = "", shape
+            row = dict(family=fname, name=vname, switches=dict(VARIANTS[sw]) if sw else {}, flen=None, M=None,
+                       kernels=dict(zip(family_kinds(FAMILIES[fname]), kernels)))
+            if shape:
+                row["flen" if shape.startswith("flen") else "M"] = int(shape.lstrip("flenM"))
+            rows[(fname, vname)] = row
+    return rows
+
+
+def kernel_tags(name):
+    """The tags between the < > of a kernel name."""
+    return set(name[name.index("<") + 1: name.rindex(">")].split(",")) if "<" in name else set()
+
+
+def reaches_variant(expect, name):
+    return name.startswith(expect[0]) and set(expect[1]) <= kernel_tags(name)
+
+
+def port_variants(oracle, rows):
+    """The f32 port under every row: {(family, row name): as port_families}.  A row of a family without a port (chirp-z) brings
+    the 128-point generic family under the same row name along: counted() takes its classes."""
+    rep = {}
+    for (fname, vname), row in rows.items():
+        rep[(fname, vname)] = port_families(oracle, {fname: FAMILIES[fname]}, variant=row)[fname]
+        if rep[(fname, vname)] is None and ("front_generic", vname) not in rep:
+            base = variant_rows(("front_generic",))[("front_generic", vname)]
+            rep[("front_generic", vname)] = port_families(oracle, {"front_generic": FAMILIES["front_generic"]}, variant=base)["front_generic"]
+    return rep
+
+
+def run_variants(ss, oracle, rows=None):
+    """run_families over the rows of variant_rows(): {"family/row": config, kernels reached and expected, cases}."""
+    rep = {}
+    for (fname, vname), row in (rows or variant_rows()).items():
+        fam = FAMILIES[fname]
+        sig = family_signals(variant_family(fam, row))
+        X = np.stack(list(sig.values()))
+        got, kernels = family_outputs(ss, fam, X, row)
+        want = family_reference(oracle, fam, X, variant=row)
+        cases = {s: {k: block_metrics(k, got[k][i], want[k][i]) for k in want} for i, s in enumerate(sig)}
+        rep[f"{fname}/{vname}"] = {"switches": row["switches"], "flen": row["flen"], "M": row["M"], "kernels": kernels,
+                                   "expected": {k: [e[0], list(e[1])] for k, e in row["kernels"].items()}, "cases": cases}
+    return rep
+
+
+def variants_doc(rep, port_rep, rows=None):
+    """The report as written to profiles/parity_variants.json: per (family, row) the kernels reached, the counted cases' worst
+    value per bar metric with its bar, and the cases that do not count."""
+    out = {}
+    for (fname, vname), row in (rows or variant_rows()).items():
+        r = rep[f"{fname}/{vname}"]
+        cnt, bar = counted(port_rep, fname, row), bars(port_rep, fname, row)
+        worst = {}
+        for (k, m), b in sorted(bar.items()):
+            v, s = max((r["cases"][s][k][m], s) for s, kk, mm in cnt if (kk, mm) == (k, m))
+            worst[f"{k}.{m}"] = {"worst": v, "at": s, "bar": b}
+        out[f"{fname}/{vname}"] = {
+            "kernels": r["kernels"],
+            "worst": worst,
+            "not_counted": sorted(f"{s}.{k}.{m}" for s in r["cases"] for k in r["cases"][s] for m in BAR_METRICS[k] if (s, k, m) not in cnt)}
+    return {"date": datetime.date.today().isoformat(), "kernel_library": "mfcc-rust_amd/lib/libspeechsauce_amd.so",
+            "bar": "max(1e-4, 1.5 x the f32 port's worst value over the (family, variant)'s counted cases); 1e-4 without a port",
+            "variants": out}
 
 
 def run_families(ss, oracle, families=None):
@@ -318,6 +570,21 @@ if __name__ == "__main__":
         for name, r in doc["families"].items():
             assert all(reaches(FAMILIES[name], k) for k in r["kernels"].values()), (name, r["kernels"])
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "--variants":
+        out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "parity_variants.json")
+        rows = variant_rows()
+        rep = run_variants(ss, oracle_c, rows)
+        doc = variants_doc(rep, port_variants(oracle_c, rows), rows)
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        json.dump(doc, open(out, "w"), indent=1)
+        bad = 0
+        for key, v in doc["variants"].items():
+            over = {m: w for m, w in v["worst"].items() if not w["worst"] <= w["bar"]}
+            off = {k: (n, rep[key]["expected"][k]) for k, n in v["kernels"].items() if not reaches_variant(rep[key]["expected"][k], n)}
+            print(key, v["kernels"], " ".join(f"{m}={w['worst']:.2e}/{w['bar']:.2e}" for m, w in v["worst"].items()),
+                  *(["OVER THE BAR", over] if over else []), *(["NOT THE EXPECTED KERNEL", off] if off else []), flush=True)
+            bad += bool(off)
+        sys.exit(1 if bad else 0)  # (a value over its bar is reported; tests/test_gpu_parity_variants.py judges it)
     rep = run(ss, oracle_c)
     worst = {c: {k: max(v[k] for v in sig.values()) for k in next(iter(sig.values()))} for c, sig in rep.items()}
     doc = {"kernel_library": "mfcc-rust_amd/lib/libspeechsauce_amd.so", "tolerance": "1e-4 (BASELINE.json north_star)", "worst": worst, "cases": rep}
