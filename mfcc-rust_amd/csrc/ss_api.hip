@@ -19,6 +19,8 @@
 #include <vector>
 
 #include "ss_device.h"
+#include "ss_hip_staging.h"
+#include "ss_host_checks.h"
 #include "ss_internal.h"
 #include "ss_launch_args.h"
 
@@ -121,10 +123,9 @@ std::atomic<int> g_force_generic{0}, g_mel_tile_off{0};
 std::atomic<unsigned> g_tile_fault{0};
 #endif
 
-int hip_fail(hipError_t e, const char *what)
-{
-    return ss::fail(SS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
+using ss::DeviceBuf;
+using ss::hip_fail;
+using ss::ranges_overlap;
 
 #define SS_HIP(call)                                  \
     do {                                              \
@@ -141,21 +142,6 @@ int upload(T **dst, const void *src, size_t bytes)
     SS_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
     return SS_OK;
 }
-
-struct DeviceBuf {
-    void *p = nullptr;
-    ~DeviceBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t bytes)
-    {
-        SS_HIP(hipMalloc(&p, bytes ? bytes : 16));
-        return SS_OK;
-    }
-    template <typename T>
-    T *as() { return static_cast<T *>(p); }
-};
 
 int check_device(const ss_config *cfg);
 
@@ -740,12 +726,6 @@ int launch_batches(size_t n_batches, const float *const *d_x, const size_t *coun
 // Streaming STFT-path launch (ss_*_stream_device): the rows of one call over a carried state per stream, then the state advance --
 // two kernels on `stream`, nothing else (a captured call is a linear chain of two nodes).  Candidate order as launch_stft's: the
 // streaming build of the 2048-point mel kernel where mel2048.ok, else the streaming build of the generic kernel.
-bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 int launch_stft_stream(const ss_config *cfg, int out_kind, int mode, const float *d_x, size_t n_streams, size_t n, size_t ld,
                        float *d_state, float *out0, hipStream_t stream)
 {
@@ -1063,28 +1043,13 @@ int frame_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunk
         return ss::fail(SS_ERR_ARG, "norm_frames must be >= 1: the reference DCT scaling needs a frame count");
     std::vector<int64_t> ro(n_active + 1);
     if ((rc = ss_frame_stream_packed_row_offsets(&h.params, n_active, so, ro.data()))) return rc;
-    {
-        std::unordered_set<int32_t> seen;
-        seen.reserve(n_active);
-        for (size_t i = 0; i < n_active; ++i) {
-            if (slots[i] < 0 || static_cast<size_t>(slots[i]) >= pool_streams)
-                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is outside the pool of " +
-                                                std::to_string(pool_streams) + " rows");
-            if (!seen.insert(slots[i]).second)
-                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is named twice in one call");
-        }
-    }
+    if ((rc = ss::check_slots(slots, n_active, pool_streams))) return rc;
     const size_t rows = static_cast<size_t>(ro[n_active]), samples = static_cast<size_t>(so[n_active]);
     if (rows >= 0x80000000ull) return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
     const size_t cols = out_kind == ss::OUT_MFCC ? h.params.num_cepstral : h.params.num_filters;
     if ((rc = check_device(cfg))) return rc;
-    // the named pool rows, row i = entry i's
-    std::vector<float> rows_host(n_active * S);
-    std::vector<int32_t> iota(n_active);
-    for (size_t i = 0; i < n_active; ++i) {
-        iota[i] = static_cast<int32_t>(i);
-        if (S > 0) std::memcpy(rows_host.data() + i * S, pool + static_cast<size_t>(slots[i]) * S, S * sizeof(float));
-    }
+    ss::PoolRows named;  // the named pool rows, row i = entry i's
+    named.gather(pool, slots, n_active, S);
     ss_config::HostPipe &hp = cfg->pipe;
     std::lock_guard<std::mutex> lock(hp.mu);
     if (!hp.stream[0]) {
@@ -1101,8 +1066,8 @@ int frame_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunk
     hipError_t e = samples ? hipMemcpyAsync(dx.p, x.ptr(), samples * x.sample_bytes(), hipMemcpyHostToDevice, st) : hipSuccess;
     if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, tbytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dro.p, ro.data(), tbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dsl.p, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && S > 0) e = hipMemcpyAsync(dp.p, rows_host.data(), sbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dsl.p, named.iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && S > 0) e = hipMemcpyAsync(dp.p, named.rows_host.data(), sbytes, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
     if (rc == SS_OK)
         rc = launch_frame_stream_packed(cfg, out_kind, x.is_pcm ? PoolChunks(dx.as<const int16_t>(), x.scale) : PoolChunks(dx.as<const float>()),
@@ -1119,12 +1084,10 @@ int frame_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunk
     if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "frame stream pool host call");
     if (rc == SS_OK) rc = pending_device_error(cfg);
     if (rc == SS_OK && S > 0) {
-        e = hipMemcpyAsync(rows_host.data(), dp.p, sbytes, hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(named.rows_host.data(), dp.p, sbytes, hipMemcpyDeviceToHost, st);
         const hipError_t es = hipStreamSynchronize(st);
         if (e != hipSuccess || es != hipSuccess) rc = hip_fail(e != hipSuccess ? e : es, "hipMemcpyAsync (pool rows D2H)");
-        if (rc == SS_OK)
-            for (size_t i = 0; i < n_active; ++i)
-                std::memcpy(pool + static_cast<size_t>(slots[i]) * S, rows_host.data() + i * S, S * sizeof(float));
+        if (rc == SS_OK) named.scatter(pool, slots);
     }
     return rc;
 }
@@ -1207,18 +1170,7 @@ int stft_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunks
     if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
     std::vector<int64_t> ro(n_active + 1);
     rc = ss_stream_packed_row_offsets(&h.params, n_active, so, ro.data());
-    if (rc) return rc;
-    {
-        std::unordered_set<int32_t> seen;
-        seen.reserve(n_active);
-        for (size_t i = 0; i < n_active; ++i) {
-            if (slots[i] < 0 || static_cast<size_t>(slots[i]) >= pool_streams)
-                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is outside the pool of " +
-                                                std::to_string(pool_streams) + " rows");
-            if (!seen.insert(slots[i]).second)
-                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is named twice in one call");
-        }
-    }
+    if (rc || (rc = ss::check_slots(slots, n_active, pool_streams))) return rc;
     const size_t rows = static_cast<size_t>(ro[n_active]), samples = static_cast<size_t>(so[n_active]);
     if (rows >= 0x80000000ull) return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
     const size_t S = h.params.fft_points - h.d.hop;
@@ -1227,13 +1179,8 @@ int stft_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunks
     if (ranges_overlap(pool, pbytes, x.ptr(), samples * x.sample_bytes()) || ranges_overlap(pool, pbytes, out0, out_floats * sizeof(float)))
         return ss::fail(SS_ERR_ARG, "the pool overlaps the input or the output");
     if ((rc = check_device(cfg))) return rc;
-    // the named pool rows, row i = entry i's
-    std::vector<float> rows_host(n_active * S);
-    std::vector<int32_t> iota(n_active);
-    for (size_t i = 0; i < n_active; ++i) {
-        iota[i] = static_cast<int32_t>(i);
-        std::memcpy(rows_host.data() + i * S, pool + static_cast<size_t>(slots[i]) * S, S * sizeof(float));
-    }
+    ss::PoolRows named;  // the named pool rows, row i = entry i's
+    named.gather(pool, slots, n_active, S);
     ss_config::HostPipe &hp = cfg->pipe;
     std::lock_guard<std::mutex> lock(hp.mu);
     if (!hp.stream[0]) {
@@ -1250,8 +1197,8 @@ int stft_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunks
     hipError_t e = samples ? hipMemcpyAsync(dx.p, x.ptr(), samples * x.sample_bytes(), hipMemcpyHostToDevice, st) : hipSuccess;
     if (e == hipSuccess) e = hipMemcpyAsync(dso.p, so, tbytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dro.p, ro.data(), tbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dsl.p, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dp.p, rows_host.data(), sbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dsl.p, named.iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dp.p, named.rows_host.data(), sbytes, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (H2D)");
     if (rc == SS_OK)
         rc = launch_stft_stream_packed(cfg, out_kind, x.is_pcm ? PoolChunks(dx.as<const int16_t>(), x.scale) : PoolChunks(dx.as<const float>()), n_active, dso.as<const int64_t>(), dro.as<const int64_t>(), rows,
@@ -1265,12 +1212,10 @@ int stft_stream_packed_host(const ss_config *cfg, int out_kind, const PoolChunks
     if (e != hipSuccess && rc == SS_OK) rc = hip_fail(e, "stream pool host call");
     if (rc == SS_OK) rc = pending_device_error(cfg);
     if (rc == SS_OK) {
-        e = hipMemcpyAsync(rows_host.data(), dp.p, sbytes, hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(named.rows_host.data(), dp.p, sbytes, hipMemcpyDeviceToHost, st);
         const hipError_t es = hipStreamSynchronize(st);
         if (e != hipSuccess || es != hipSuccess) rc = hip_fail(e != hipSuccess ? e : es, "hipMemcpyAsync (pool rows D2H)");
-        if (rc == SS_OK)
-            for (size_t i = 0; i < n_active; ++i)
-                std::memcpy(pool + static_cast<size_t>(slots[i]) * S, rows_host.data() + i * S, S * sizeof(float));
+        if (rc == SS_OK) named.scatter(pool, slots);
     }
     return rc;
 }
@@ -1785,10 +1730,7 @@ int ss_config_create(const ss_params *p, ss_config **out)
     std::unique_ptr<ss_config> cfg(new ss_config());
     int rc = ss::build_tables(*p, cfg->host);
     if (rc) return rc;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0)
-        return ss::fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd hot path has no CPU fallback");
+    if (!ss::have_device()) return ss::no_device("hot path");
     SS_HIP(hipGetDevice(&cfg->device));
     hipDeviceProp_t prop;
     SS_HIP(hipGetDeviceProperties(&prop, cfg->device));
@@ -2440,9 +2382,7 @@ int ss_stack_frames_signal(const float *x, size_t n_samples, uint32_t sample_rat
     int rc = frames_shape(n_samples, sample_rate, frame_length, frame_stride, zero_padding, T, flen, step);
     if (rc) return rc;
     if (!x || !frames) return ss::fail(SS_ERR_ARG, "null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return ss::fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd hot path has no CPU fallback");
+    if (!ss::have_device()) return ss::no_device("hot path");
     // a cold path (no config, so no staging pipeline to reuse): plain allocations and synchronous copies
     DeviceBuf dx, dw, df;
     const size_t out_bytes = T * static_cast<size_t>(flen) * sizeof(float);
@@ -2878,9 +2818,7 @@ int ss_preemphasis(const float *x, size_t n_samples, long shift, float cof, floa
 {
     if (!x || !y) return ss::fail(SS_ERR_ARG, "null argument");
     if (n_samples == 0 || shift <= 0 || static_cast<size_t>(shift) > n_samples) return ss::fail(SS_ERR_ARG, "shift must be in [1, n_samples]");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return ss::fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd hot path has no CPU fallback");
+    if (!ss::have_device()) return ss::no_device("hot path");
     DeviceBuf dx, dy;
     int rc;
     if ((rc = dx.alloc(n_samples * sizeof(float))) || (rc = dy.alloc(n_samples * sizeof(float)))) return rc;

@@ -4,8 +4,10 @@
 // exact, so an output's bits depend on the values under its taps and on nothing else -- not on the tile it was computed in, the
 // clip's place in the block, the entry's place in the call or how a stream was cut into calls.
 // The reference crate differences along the feature axis (processing.rs:222-254, ss_derivative_extraction* in ss_post.hip); it has
-// no time-axis counterpart, so this file restates nothing of it.  The small table decoders are those of ss_post.hip, restated here
-// so that the existing objects build exactly as before.
+// no time-axis counterpart, so this file restates nothing of it.
+#include "ss_device.h"
+#include "ss_hip_staging.h"
+#include "ss_host_checks.h"
 #include "ss_internal.h"
 
 #include <hip/hip_runtime.h>
@@ -14,7 +16,6 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
-#include <unordered_set>
 #include <vector>
 
 namespace ss {
@@ -50,23 +51,8 @@ __device__ __forceinline__ float delta_at(const float *p, int stride, const Delt
 // ---- packed clips ----
 // Clip b owns rows off[b] .. off[b+1].  Workgroup (b, y) takes the row tiles y, y + gridDim.y, ... of clip b: a tile of kRowTile
 // rows plus L halo rows on either side (indices clamped to the clip's own first and last row while staging: edge replication of
-// the raw rows) goes to LDS once per 32-column tile, columns fastest; every element then walks its taps there.
-struct Segment {
-    unsigned long long row0;
-    unsigned rows;  // 0: nothing to do (empty or rejected segment)
-};
-
-__device__ __forceinline__ Segment packed_segment(const long long *__restrict__ off, unsigned long long total_rows)
-{
-    const long long lo = off[blockIdx.x], hi = off[blockIdx.x + 1];
-    Segment s{0, 0};
-    if (lo >= 0 && lo < hi && static_cast<unsigned long long>(hi) <= total_rows) {  // total_rows < 2^31: the row count fits
-        s.row0 = static_cast<unsigned long long>(lo);
-        s.rows = static_cast<unsigned>(hi - lo);
-    }
-    return s;
-}
-
+// the raw rows) goes to LDS once per 32-column tile, columns fastest; every element then walks its taps there.  (packed_segment:
+// ss_device.h)
 constexpr unsigned kRowTile = 64;                          // output rows per tile
 constexpr unsigned kColTile = 32;                          // columns staged at a time
 constexpr unsigned kTileRows = kRowTile + 2 * kMaxLag;     // staged rows at the largest lag: 128 x 32 floats = 16 KiB
@@ -268,14 +254,6 @@ __global__ __launch_bounds__(256) void ss_add_deltas_stream_kernel(const float *
 
 // ---- host side ----
 
-int hip_err(hipError_t e, const char *what) { return fail(SS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // order / window -> the integer taps of every order by repeated convolution with [-window .. window] (the non-zero ones kept), and 1 / D_o
 int make_taps(size_t order, size_t window, DeltaTaps &tp)
 {
@@ -320,25 +298,6 @@ int check_packed(const float *vec, const void *off, const float *out, size_t n_c
     return SS_OK;
 }
 
-// the segment table of a host-pointer call, checked before the device is touched
-int check_table(const int64_t *off, size_t n_clips, size_t total_rows)
-{
-    if (off[0] != 0) return fail(SS_ERR_ARG, "offsets[0] must be 0 (clip 0)");
-    for (size_t b = 0; b < n_clips; ++b)
-        if (off[b + 1] < off[b]) return fail(SS_ERR_ARG, "decreasing offsets at clip " + std::to_string(b));
-    for (size_t b = 0; b < n_clips; ++b)
-        if (static_cast<uint64_t>(off[b + 1]) > total_rows) return fail(SS_ERR_ARG, "clip " + std::to_string(b) + " ends past total_rows");
-    return SS_OK;
-}
-
-// workgroups per clip (gridDim.y), as the packed post-processing calls size it: about 8192 workgroups in all, at most 64 per clip and
-// never more than the longest possible clip has row tiles.  The bits of the results do not depend on it.
-unsigned packed_split(size_t n_clips, unsigned long long most_useful)
-{
-    const unsigned long long want = std::max<unsigned long long>(1, 8192 / n_clips);
-    return static_cast<unsigned>(std::min<unsigned long long>(64, std::min(want, std::max<unsigned long long>(1, most_useful))));
-}
-
 int stream_len(size_t cols, size_t order, size_t window, DeltaTaps &tp, size_t &len)
 {
     if (cols == 0) return fail(SS_ERR_ARG, "empty feature matrix (cols == 0)");
@@ -369,73 +328,44 @@ int check_stream(bool flush, const float *vec, const void *ro, const void *slots
     return SS_OK;
 }
 
-// the slots of a host-pointer call: inside the pool, none named twice
-int check_slots(const int32_t *slots, size_t n_active, size_t pool_streams)
-{
-    std::unordered_set<int32_t> seen;
-    seen.reserve(n_active);
-    for (size_t i = 0; i < n_active; ++i) {
-        if (slots[i] < 0 || static_cast<size_t>(slots[i]) >= pool_streams)
-            return fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is outside the pool of " +
-                                        std::to_string(pool_streams) + " rows");
-        if (!seen.insert(slots[i]).second)
-            return fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is named twice in one call");
-    }
-    return SS_OK;
-}
-
-bool have_device()
-{
-    int ndev = 0;
-    return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
-}
-
 // Host staging of both pool calls: vec (in_rows rows, none for the flush) and the row offsets go up with the n_active named pool
 // rows, gathered into a compact block whose row i is entry i's (the device call runs on slots 0 .. n_active - 1); out_rows rows of
 // out and the pool rows come down.  The caller's pool is written only once everything before it succeeded.
 int stream_via_device(bool flush, const float *vec, size_t n_active, const int64_t *row_offsets, const int32_t *slots, size_t in_rows, size_t out_rows,
                       size_t cols, size_t order, size_t window, size_t len, float *pool, float *out)
 {
-    if (!have_device()) return fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd path has no CPU fallback");
-    std::vector<float> rows_host(n_active * len);
-    std::vector<int32_t> iota(n_active);
-    for (size_t i = 0; i < n_active; ++i) {
-        iota[i] = static_cast<int32_t>(i);
-        std::memcpy(rows_host.data() + i * len, pool + static_cast<size_t>(slots[i]) * len, len * sizeof(float));
-    }
+    if (!have_device()) return no_device();
+    PoolRows named;
+    named.gather(pool, slots, n_active, len);
     const size_t bytes = in_rows * cols * sizeof(float), obytes = out_rows * cols * (order + 1) * sizeof(float);
-    const size_t tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * len * sizeof(float);
-    void *d_vec = nullptr, *d_out = nullptr, *d_ro = nullptr, *d_sl = nullptr, *d_pool = nullptr;
-    hipError_t e = hipMalloc(&d_out, obytes);
-    if (e == hipSuccess) e = hipMalloc(&d_sl, n_active * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_pool, sbytes);
+    const size_t tbytes = (n_active + 1) * sizeof(int64_t), ibytes = n_active * sizeof(int32_t);
+    DeviceBuf d_vec, d_out, d_ro, d_sl, d_pool;
+    hipError_t e = d_out.hip_alloc(obytes);
+    if (e == hipSuccess) e = d_sl.hip_alloc(ibytes);
+    if (e == hipSuccess) e = d_pool.hip_alloc(named.bytes());
     if (!flush) {
-        if (e == hipSuccess) e = hipMalloc(&d_vec, bytes);
-        if (e == hipSuccess) e = hipMalloc(&d_ro, tbytes);
-        if (e == hipSuccess) e = hipMemcpy(d_vec, vec, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_ro, row_offsets, tbytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = d_vec.hip_alloc(bytes);
+        if (e == hipSuccess) e = d_ro.hip_alloc(tbytes);
+        if (e == hipSuccess) e = hipMemcpy(d_vec.p, vec, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_ro.p, row_offsets, tbytes, hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess) e = hipMemcpy(d_sl, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pool, rows_host.data(), sbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_sl.p, named.iota.data(), ibytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_pool.p, named.rows_host.data(), named.bytes(), hipMemcpyHostToDevice);
     int rc = SS_OK;
-    if (e != hipSuccess) rc = hip_err(e, "host staging");
+    if (e != hipSuccess) rc = hip_fail(e, "host staging");
     else if (flush)
-        rc = ss_add_deltas_stream_flush_device(n_active, static_cast<const int32_t *>(d_sl), n_active, cols, order, window, static_cast<float *>(d_pool),
-                                               static_cast<float *>(d_out), nullptr);
+        rc = ss_add_deltas_stream_flush_device(n_active, d_sl.as<const int32_t>(), n_active, cols, order, window, d_pool.as<float>(), d_out.as<float>(),
+                                               nullptr);
     else
-        rc = ss_add_deltas_stream_packed_device(static_cast<const float *>(d_vec), n_active, static_cast<const int64_t *>(d_ro), in_rows,
-                                                static_cast<const int32_t *>(d_sl), n_active, cols, order, window, static_cast<float *>(d_pool),
-                                                static_cast<float *>(d_out), nullptr);
+        rc = ss_add_deltas_stream_packed_device(d_vec.as<const float>(), n_active, d_ro.as<const int64_t>(), in_rows, d_sl.as<const int32_t>(), n_active,
+                                                cols, order, window, d_pool.as<float>(), d_out.as<float>(), nullptr);
     if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_add_deltas_stream: device error");
     if (rc == SS_OK) {
-        e = hipMemcpy(rows_host.data(), d_pool, sbytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_err(e, "hipMemcpy D2H");
+        e = hipMemcpy(named.rows_host.data(), d_pool.p, named.bytes(), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out, d_out.p, obytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
     }
-    if (rc == SS_OK)
-        for (size_t i = 0; i < n_active; ++i) std::memcpy(pool + static_cast<size_t>(slots[i]) * len, rows_host.data() + i * len, len * sizeof(float));
-    for (void *p : {d_vec, d_out, d_ro, d_sl, d_pool})
-        if (p) (void)hipFree(p);
+    if (rc == SS_OK) named.scatter(pool, slots);
     return rc;
 }
 
@@ -458,7 +388,7 @@ int ss_add_deltas_packed_device(const float *d_vec, size_t n_clips, const int64_
     hipLaunchKernelGGL(ss::ss_add_deltas_packed_kernel, dim3(static_cast<unsigned>(n_clips), split), dim3(256), 0, static_cast<hipStream_t>(stream), d_vec,
                        reinterpret_cast<const long long *>(d_offsets), d_out, static_cast<unsigned long long>(total_rows), static_cast<unsigned>(cols), tp);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_add_deltas_packed_kernel");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_add_deltas_packed_kernel");
 }
 
 // host-pointer form (synchronous): the table is checked on the host before the device is touched; the block and the table go up, the
@@ -469,26 +399,24 @@ int ss_add_deltas_packed(const float *vec, size_t n_clips, const int64_t *offset
     if (n_clips == 0) return SS_OK;
     ss::DeltaTaps tp;
     int rc = ss::check_packed(vec, offsets, out, n_clips, total_rows, cols, order, window, tp);
-    if (rc || (rc = ss::check_table(offsets, n_clips, total_rows))) return rc;
+    if (rc || (rc = ss::check_clip_table(offsets, n_clips, total_rows))) return rc;
     if (offsets[n_clips] == 0) return SS_OK;
-    if (!ss::have_device()) return ss::fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd path has no CPU fallback");
+    if (!ss::have_device()) return ss::no_device();
     const size_t bytes = total_rows * cols * sizeof(float), tbytes = (n_clips + 1) * sizeof(int64_t);
-    void *d_in = nullptr, *d_out = nullptr, *d_off = nullptr;
-    hipError_t e = hipMalloc(&d_in, bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_out, bytes * (order + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_off, tbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in, vec, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_off, offsets, tbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? ss_add_deltas_packed_device(static_cast<const float *>(d_in), n_clips, static_cast<const int64_t *>(d_off), total_rows, cols,
-                                                       order, window, static_cast<float *>(d_out), nullptr)
-                         : ss::hip_err(e, "host staging");
+    ss::DeviceBuf d_in, d_out, d_off;
+    hipError_t e = d_in.hip_alloc(bytes);
+    if (e == hipSuccess) e = d_out.hip_alloc(bytes * (order + 1));
+    if (e == hipSuccess) e = d_off.hip_alloc(tbytes);
+    if (e == hipSuccess) e = hipMemcpy(d_in.p, vec, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off.p, offsets, tbytes, hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? ss_add_deltas_packed_device(d_in.as<const float>(), n_clips, d_off.as<const int64_t>(), total_rows, cols, order, window,
+                                                       d_out.as<float>(), nullptr)
+                         : ss::hip_fail(e, "host staging");
     if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_add_deltas_packed: device error");
     if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out, static_cast<size_t>(offsets[n_clips]) * cols * (order + 1) * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = ss::hip_err(e, "hipMemcpy D2H");
+        e = hipMemcpy(out, d_out.p, static_cast<size_t>(offsets[n_clips]) * cols * (order + 1) * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = ss::hip_fail(e, "hipMemcpy D2H");
     }
-    for (void *p : {d_in, d_out, d_off})
-        if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -517,7 +445,7 @@ int ss_add_deltas_stream_packed_device(const float *d_vec, size_t n_active, cons
                        reinterpret_cast<const long long *>(d_row_offsets), reinterpret_cast<const int *>(d_slots), d_out, d_pool,
                        static_cast<unsigned long long>(total_rows), static_cast<unsigned>(pool_streams), static_cast<unsigned>(cols), tp);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_add_deltas_stream_kernel");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_add_deltas_stream_kernel");
 }
 
 int ss_add_deltas_stream_packed(const float *vec, size_t n_active, const int64_t *row_offsets, const int32_t *slots, size_t pool_streams, size_t cols,
@@ -526,13 +454,12 @@ int ss_add_deltas_stream_packed(const float *vec, size_t n_active, const int64_t
     if (n_active == 0) return SS_OK;
     if (!row_offsets) return ss::fail(SS_ERR_ARG, "null buffer");
     if (n_active >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
-    if (row_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "row_offsets[0] must be 0 (entry 0)");
-    for (size_t i = 0; i < n_active; ++i)
-        if (row_offsets[i + 1] < row_offsets[i]) return ss::fail(SS_ERR_ARG, "decreasing row offsets at entry " + std::to_string(i));
+    int rc = ss::check_row_offsets(row_offsets, n_active);
+    if (rc) return rc;
     size_t rows = static_cast<size_t>(row_offsets[n_active]);
     ss::DeltaTaps tp;
     size_t len = 0;
-    int rc = ss::check_stream(false, vec, row_offsets, slots, n_active, rows, pool_streams, cols, order, window, pool, out, tp, len);
+    rc = ss::check_stream(false, vec, row_offsets, slots, n_active, rows, pool_streams, cols, order, window, pool, out, tp, len);
     if (rc || (rc = ss::check_slots(slots, n_active, pool_streams))) return rc;
     if (rows == 0) return SS_OK;  // entries without rows only: nothing moves
     return ss::stream_via_device(false, vec, n_active, row_offsets, slots, rows, rows, cols, order, window, len, pool, out);
@@ -551,7 +478,7 @@ int ss_add_deltas_stream_flush_device(size_t n_active, const int32_t *d_slots, s
                        nullptr, reinterpret_cast<const int *>(d_slots), d_out, d_pool, static_cast<unsigned long long>(rows),
                        static_cast<unsigned>(pool_streams), static_cast<unsigned>(cols), tp);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_add_deltas_stream_kernel");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_add_deltas_stream_kernel");
 }
 
 int ss_add_deltas_stream_flush(size_t n_active, const int32_t *slots, size_t pool_streams, size_t cols, size_t order, size_t window, float *pool,

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <type_traits>
 
@@ -305,6 +306,31 @@ hipError_t launch_db_keys_init(int *max_key, size_t clips, hipStream_t stream);
 hipError_t launch_db_floor_equal(float *out, size_t clips, size_t seg, float top_db, const int *max_key, hipStream_t stream);
 hipError_t launch_db_floor_varrows(float *out, const VarRowsArgs &v, size_t cols, float top_db, const int *max_key, hipStream_t stream);
 hipError_t launch_power_to_db_equal(float *x, size_t clips, size_t seg, const DbArgs &db, hipStream_t stream);
+
+// Packed feature rows (the packed calls of ss_post.hip and ss_deltas.hip): clip b = blockIdx.x owns rows off[b] .. off[b+1] of a
+// block of total_rows rows.  A segment that is reversed, starts below 0 or ends past total_rows comes back empty.
+struct Segment {
+    unsigned long long row0;
+    unsigned rows;  // 0: nothing to do (empty or rejected segment)
+};
+__device__ __forceinline__ Segment packed_segment(const long long *__restrict__ off, unsigned long long total_rows)
+{
+    const long long lo = off[blockIdx.x], hi = off[blockIdx.x + 1];
+    Segment s{0, 0};
+    if (lo >= 0 && lo < hi && static_cast<unsigned long long>(hi) <= total_rows) {  // total_rows < 2^31: the row count fits
+        s.row0 = static_cast<unsigned long long>(lo);
+        s.rows = static_cast<unsigned>(hi - lo);
+    }
+    return s;
+}
+// Workgroups per clip (gridDim.y) of a launch over packed clips: about 8192 workgroups in all, so that a block of few long clips still
+// fills the device, at most 64 per clip and never more than the longest possible clip has work for (most_useful).  Sized from what
+// the host knows; the bits of the results do not depend on it.
+inline unsigned packed_split(size_t n_clips, unsigned long long most_useful)
+{
+    const unsigned long long want = std::max<unsigned long long>(1, 8192 / n_clips);
+    return static_cast<unsigned>(std::min<unsigned long long>(64, std::min(want, std::max<unsigned long long>(1, most_useful))));
+}
 
 // the streaming build of ss_front_generic's STFT / mel path (any fft_points, chirp-z included): a as for launch_front_generic's
 // STFT path, on the chunk (n_pad 0 and real_rows = rows in continuous mode)

@@ -8,6 +8,8 @@
 // cmvn sums chunks of rows per thread and normalises per element (two launches, no atomics: bit-reproducible); cmvnw slides
 // its window sums over a chunk of rows per thread (O(rows + win) loads per column chunk instead of O(rows * win)).
 #include "ss_device.h"
+#include "ss_hip_staging.h"
+#include "ss_host_checks.h"
 #include "ss_internal.h"
 #include "speechsauce_amd.h"
 
@@ -16,10 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 #include <string>
-#include <unordered_set>
-#include <vector>
 
 namespace ss {
 
@@ -245,23 +244,7 @@ __global__ __launch_bounds__(256) void ss_derivative_cube_kernel(const float *__
 // row and depends on its row count and the scalar arguments only, so a clip's bits do not depend on where it sits in the block.
 // gridDim.y workgroups share a long clip (strided over its tasks); for a short clip the ones past its work return at once.
 // Containment: a segment that is reversed, starts below 0 or ends past total_rows is skipped, and every address a workgroup forms
-// lies inside its own validated segment.
-struct Segment {
-    unsigned long long row0;
-    unsigned rows;  // 0: nothing to do (empty or rejected segment)
-};
-
-__device__ __forceinline__ Segment packed_segment(const long long *__restrict__ off, unsigned long long total_rows)
-{
-    const long long lo = off[blockIdx.x], hi = off[blockIdx.x + 1];
-    Segment s{0, 0};
-    if (lo >= 0 && lo < hi && static_cast<unsigned long long>(hi) <= total_rows) {  // total_rows < 2^31: the row count fits
-        s.row0 = static_cast<unsigned long long>(lo);
-        s.rows = static_cast<unsigned>(hi - lo);
-    }
-    return s;
-}
-
+// lies inside its own validated segment (packed_segment, ss_device.h).
 constexpr unsigned kCmvnChunks = 64;   // chunks = min(64, ceil(rows / 32)), as ss_cmvn_batch_device
 constexpr unsigned kCmvnTile = 32;     // columns whose chunk partials sit in LDS at a time: 64 x 32 x 2 doubles = 32 KiB
 constexpr unsigned kCmvnSplitRows = 2048;  // a clip gets one workgroup per 2048 rows (up to gridDim.y)
@@ -629,8 +612,6 @@ __global__ __launch_bounds__(256) void ss_power_to_db_equal_kernel(float *x, uns
     }
 }
 
-int hip_err(hipError_t e, const char *what) { return fail(SS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
 unsigned blocks_for(unsigned long long n) { return static_cast<unsigned>((n + 255) / 256); }
 
 int check_shape(const void *a, const void *b, size_t batch, size_t rows, size_t cols)
@@ -645,20 +626,16 @@ int check_shape(const void *a, const void *b, size_t batch, size_t rows, size_t 
 template <typename F>
 int via_device(const float *in, size_t n_in, float *out, size_t n_out, F &&run)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd path has no CPU fallback");
-    float *d_in = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_in), n_in * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), n_out * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, n_in * sizeof(float), hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? run(d_in, d_out) : hip_err(e, "host staging");
+    if (!have_device()) return no_device();
+    DeviceBuf d_in, d_out;
+    hipError_t e = d_in.hip_alloc(n_in * sizeof(float));
+    if (e == hipSuccess) e = d_out.hip_alloc(n_out * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d_in.p, in, n_in * sizeof(float), hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? run(d_in.as<const float>(), d_out.as<float>()) : hip_fail(e, "host staging");
     if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_err(e, "hipMemcpy D2H");
+        e = hipMemcpy(out, d_out.p, n_out * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
     }
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
     return rc;
 }
 
@@ -672,63 +649,30 @@ int check_packed(const void *a, const void *off, const void *b, size_t n_clips, 
     return SS_OK;
 }
 
-// the segment table of a host-pointer call, checked before the device is touched
-int check_table(const int64_t *off, size_t n_clips, size_t total_rows)
-{
-    if (off[0] != 0) return fail(SS_ERR_ARG, "offsets[0] must be 0 (clip 0)");
-    for (size_t b = 0; b < n_clips; ++b)
-        if (off[b + 1] < off[b]) return fail(SS_ERR_ARG, "decreasing offsets at clip " + std::to_string(b));
-    if (static_cast<uint64_t>(off[n_clips]) > total_rows)
-        for (size_t b = 0; b < n_clips; ++b)
-            if (static_cast<uint64_t>(off[b + 1]) > total_rows)
-                return fail(SS_ERR_ARG, "clip " + std::to_string(b) + " ends past total_rows");
-    return SS_OK;
-}
-
-// Workgroups per clip (gridDim.y): about 8192 workgroups in all, so that a block of few long clips still fills the device, and
-// never more than the longest possible clip (all of total_rows) has work for.  Sized from what the host knows; the bits of the
-// results do not depend on it.
-unsigned packed_split(size_t n_clips, unsigned long long most_useful)
-{
-    const unsigned long long want = std::max<unsigned long long>(1, 8192 / n_clips);
-    return static_cast<unsigned>(std::min<unsigned long long>(64, std::min(want, std::max<unsigned long long>(1, most_useful))));
-}
-
 // host-pointer wrapper of the packed calls: upload the block (n floats) and the checked table, run the device entry point,
 // download the rows the table covers (n_written floats from the start: a host table is gap-free; rows past offsets[n_clips] stay
 // as the caller left them)
 template <typename F>
 int via_device_packed(const float *in, const int64_t *off, size_t n_clips, size_t n, size_t n_written, float *out, F &&run)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd path has no CPU fallback");
-    float *d_in = nullptr, *d_out = nullptr;
-    int64_t *d_off = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_in), n * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), n * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_off), (n_clips + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_off, off, (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? run(d_in, d_off, d_out) : hip_err(e, "host staging");
+    if (!have_device()) return no_device();
+    const size_t tbytes = (n_clips + 1) * sizeof(int64_t);
+    DeviceBuf d_in, d_out, d_off;
+    hipError_t e = d_in.hip_alloc(n * sizeof(float));
+    if (e == hipSuccess) e = d_out.hip_alloc(n * sizeof(float));
+    if (e == hipSuccess) e = d_off.hip_alloc(tbytes);
+    if (e == hipSuccess) e = hipMemcpy(d_in.p, in, n * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off.p, off, tbytes, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? run(d_in.as<const float>(), d_off.as<const int64_t>(), d_out.as<float>()) : hip_fail(e, "host staging");
     if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "packed post-processing: device error");
     if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out, n_written * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_err(e, "hipMemcpy D2H");
+        e = hipMemcpy(out, d_out.p, n_written * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
     }
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_off) (void)hipFree(d_off);
     return rc;
 }
 
 // ---- causal CMVN over a pool of stream states: argument checks ----
-
-bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
 
 // L = (win_size - 1) * cols + 1 floats per pool row; the count word is a float, so the window stays below 2^24 rows
 int cmvn_stream_len(size_t cols, size_t win_size, size_t &len)
@@ -806,15 +750,15 @@ int ss_cmvn_batch_device(const float *d_vec, size_t batch, size_t rows, size_t c
     const unsigned long long n = static_cast<unsigned long long>(batch) * rows * cols;
     double *d_part = nullptr;
     hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&d_part), np * 2 * sizeof(double), s);
-    if (e != hipSuccess) return ss::hip_err(e, "hipMallocAsync");
+    if (e != hipSuccess) return ss::hip_fail(e, "hipMallocAsync");
     hipLaunchKernelGGL(ss::ss_cmvn_partial_kernel, dim3(ss::blocks_for(np)), dim3(256), 0, s, d_vec, d_part, np, static_cast<unsigned>(rows),
                        static_cast<unsigned>(cols), chunks, rpc);
     hipLaunchKernelGGL(ss::ss_cmvn_apply_kernel, dim3(ss::blocks_for(n)), dim3(256), 0, s, d_vec, d_part, d_out, n, static_cast<unsigned>(rows),
                        static_cast<unsigned>(cols), chunks, variance_normalization);
     e = hipFreeAsync(d_part, s);
-    if (e != hipSuccess) return ss::hip_err(e, "hipFreeAsync");
+    if (e != hipSuccess) return ss::hip_fail(e, "hipFreeAsync");
     e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_cmvn kernels");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_cmvn kernels");
 }
 
 int ss_cmvnw_batch_device(const float *d_vec, size_t batch, size_t rows, size_t cols, size_t win_size, int variance_normalization,
@@ -838,14 +782,14 @@ int ss_cmvnw_batch_device(const float *d_vec, size_t batch, size_t rows, size_t 
         // the second pass reads its neighbours' mean-subtracted values: they go through a stream-ordered scratch block
         float *d_ms = nullptr;
         hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&d_ms), n * sizeof(float), s);
-        if (e != hipSuccess) return ss::hip_err(e, "hipMallocAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipMallocAsync");
         hipLaunchKernelGGL(ss::ss_cmvnw_mean_kernel, dim3(ss::blocks_for(nt)), dim3(256), 0, s, d_vec, d_ms, nt, r, c, w, chunks, rpc);
         hipLaunchKernelGGL(ss::ss_cmvnw_var_kernel, dim3(ss::blocks_for(nt)), dim3(256), 0, s, d_ms, d_out, nt, r, c, w, chunks, rpc);
         e = hipFreeAsync(d_ms, s);
-        if (e != hipSuccess) return ss::hip_err(e, "hipFreeAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipFreeAsync");
     }
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_cmvnw kernels");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_cmvnw kernels");
 }
 
 int ss_derivative_extraction_device(const float *d_feat, size_t rows, size_t cols, size_t delta_windows, float *d_out, void *stream)
@@ -859,7 +803,7 @@ int ss_derivative_extraction_device(const float *d_feat, size_t rows, size_t col
     hipLaunchKernelGGL(ss::ss_derivative_kernel, dim3(ss::blocks_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), d_feat, d_out, n,
                        static_cast<unsigned>(cols), static_cast<unsigned>(delta_windows), static_cast<float>(1.0 / scale));
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_derivative_kernel");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_derivative_kernel");
 }
 
 int ss_extract_derivative_feature_device(const float *d_feat, size_t rows, size_t cols, float *d_cube, void *stream)
@@ -870,7 +814,7 @@ int ss_extract_derivative_feature_device(const float *d_feat, size_t rows, size_
     hipLaunchKernelGGL(ss::ss_derivative_cube_kernel, dim3(ss::blocks_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), d_feat, d_cube,
                        n, static_cast<unsigned>(cols));
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_derivative_cube_kernel");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_derivative_cube_kernel");
 }
 
 // ---- host-pointer variants (synchronous) ----
@@ -927,7 +871,7 @@ int ss_ln_device(float *d_x, size_t n, void *stream)
     if (!d_x) return ss::fail(SS_ERR_ARG, "null buffer");
     hipLaunchKernelGGL(ss::ss_ln_kernel, dim3(ss::blocks_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), d_x, static_cast<unsigned long long>(n));
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_ln_kernel");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_ln_kernel");
 }
 
 int ss_power_to_db_device(const float *d_s, size_t n, float ref, float amin, float top_db, float *d_out, void *stream)
@@ -941,19 +885,19 @@ int ss_power_to_db_device(const float *d_s, size_t n, float ref, float amin, flo
     int *d_max = nullptr;
     if (top_db >= 0.0f) {
         hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&d_max), sizeof(int), st);
-        if (e != hipSuccess) return ss::hip_err(e, "hipMallocAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipMallocAsync");
         e = hipMemsetAsync(d_max, 0x80, sizeof(int), st);  // 0x80808080: below the key of every finite float
-        if (e != hipSuccess) return ss::hip_err(e, "hipMemsetAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipMemsetAsync");
     }
     hipLaunchKernelGGL(ss::ss_power_to_db_kernel, dim3(ss::blocks_for(n)), dim3(256), 0, st, d_s, d_out, static_cast<unsigned long long>(n), amin,
                        ref_db, d_max);
     if (d_max) {
         hipLaunchKernelGGL(ss::ss_db_floor_kernel, dim3(ss::blocks_for(n)), dim3(256), 0, st, d_out, static_cast<unsigned long long>(n), top_db, d_max);
         const hipError_t e = hipFreeAsync(d_max, st);
-        if (e != hipSuccess) return ss::hip_err(e, "hipFreeAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipFreeAsync");
     }
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_power_to_db kernels");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_power_to_db kernels");
 }
 
 int ss_power_to_db(const float *s, size_t n, float ref, float amin, float top_db, float *out)
@@ -981,7 +925,7 @@ int ss_cmvn_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_o
                        reinterpret_cast<const long long *>(d_offsets), d_out, static_cast<unsigned long long>(total_rows), static_cast<unsigned>(cols),
                        variance_normalization);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_cmvn_packed_kernel");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_cmvn_packed_kernel");
 }
 
 int ss_cmvnw_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols, size_t win_size,
@@ -1006,14 +950,14 @@ int ss_cmvnw_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_
         // the second pass reads its neighbours' mean-subtracted values: they go through a stream-ordered scratch block
         float *d_ms = nullptr;
         hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&d_ms), total_rows * cols * sizeof(float), s);
-        if (e != hipSuccess) return ss::hip_err(e, "hipMallocAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipMallocAsync");
         hipLaunchKernelGGL(ss::ss_cmvnw_packed_kernel<false>, grid, dim3(256), 0, s, d_vec, off, d_ms, tr, c, w, rpc);
         hipLaunchKernelGGL(ss::ss_cmvnw_packed_kernel<true>, grid, dim3(256), 0, s, d_ms, off, d_out, tr, c, w, rpc);
         e = hipFreeAsync(d_ms, s);
-        if (e != hipSuccess) return ss::hip_err(e, "hipFreeAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipFreeAsync");
     }
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_cmvnw_packed kernels");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_cmvnw_packed kernels");
 }
 
 int ss_power_to_db_packed_device(const float *d_s, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols, float ref,
@@ -1033,18 +977,18 @@ int ss_power_to_db_packed_device(const float *d_s, size_t n_clips, const int64_t
     int *d_max = nullptr;  // one ordered-integer maximum per clip
     if (top_db >= 0.0f) {
         hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&d_max), n_clips * sizeof(int), st);
-        if (e != hipSuccess) return ss::hip_err(e, "hipMallocAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipMallocAsync");
         e = hipMemsetAsync(d_max, 0x80, n_clips * sizeof(int), st);  // 0x80808080: below the key of every finite float
-        if (e != hipSuccess) return ss::hip_err(e, "hipMemsetAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipMemsetAsync");
     }
     hipLaunchKernelGGL(ss::ss_power_to_db_packed_kernel, grid, dim3(256), 0, st, d_s, off, d_out, tr, static_cast<unsigned>(cols), amin, ref_db, d_max);
     if (d_max) {
         hipLaunchKernelGGL(ss::ss_db_floor_packed_kernel, grid, dim3(256), 0, st, d_out, off, tr, static_cast<unsigned>(cols), top_db, d_max);
         const hipError_t e = hipFreeAsync(d_max, st);
-        if (e != hipSuccess) return ss::hip_err(e, "hipFreeAsync");
+        if (e != hipSuccess) return ss::hip_fail(e, "hipFreeAsync");
     }
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_power_to_db_packed kernels");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_power_to_db_packed kernels");
 }
 
 // host-pointer forms (synchronous): the table is checked on the host before the device is touched
@@ -1054,7 +998,7 @@ int ss_cmvn_packed(const float *vec, size_t n_clips, const int64_t *offsets, siz
 {
     if (n_clips == 0) return SS_OK;
     int rc = ss::check_packed(vec, offsets, out, n_clips, total_rows, cols);
-    if (rc || (rc = ss::check_table(offsets, n_clips, total_rows))) return rc;
+    if (rc || (rc = ss::check_clip_table(offsets, n_clips, total_rows))) return rc;
     if (offsets[n_clips] == 0) return SS_OK;
     return ss::via_device_packed(vec, offsets, n_clips, total_rows * cols, static_cast<size_t>(offsets[n_clips]) * cols, out,
                                  [&](const float *di, const int64_t *doff, float *dout) {
@@ -1070,7 +1014,7 @@ int ss_cmvnw_packed(const float *vec, size_t n_clips, const int64_t *offsets, si
     if (rc) return rc;
     if (win_size % 2 != 1) return ss::fail(SS_ERR_BAD_CONFIG, "Windows size must be odd!");
     if (win_size >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "window too large");
-    if ((rc = ss::check_table(offsets, n_clips, total_rows))) return rc;
+    if ((rc = ss::check_clip_table(offsets, n_clips, total_rows))) return rc;
     if (offsets[n_clips] == 0) return SS_OK;
     return ss::via_device_packed(vec, offsets, n_clips, total_rows * cols, static_cast<size_t>(offsets[n_clips]) * cols, out,
                                  [&](const float *di, const int64_t *doff, float *dout) {
@@ -1086,7 +1030,7 @@ int ss_power_to_db_packed(const float *s, size_t n_clips, const int64_t *offsets
     if (rc) return rc;
     if (!(amin > 0.0f)) return ss::fail(SS_ERR_ARG, "amin must be strictly positive");
     if (ref != ref) return ss::fail(SS_ERR_ARG, "ref must not be NaN");
-    if ((rc = ss::check_table(offsets, n_clips, total_rows))) return rc;
+    if ((rc = ss::check_clip_table(offsets, n_clips, total_rows))) return rc;
     if (offsets[n_clips] == 0) return SS_OK;
     return ss::via_device_packed(s, offsets, n_clips, total_rows * cols, static_cast<size_t>(offsets[n_clips]) * cols, out,
                                  [&](const float *di, const int64_t *doff, float *dout) {
@@ -1121,7 +1065,7 @@ int ss_cmvn_stream_packed_device(const float *d_vec, size_t n_active, const int6
                        static_cast<unsigned long long>(total_rows), static_cast<unsigned>(pool_streams), static_cast<unsigned>(cols),
                        static_cast<unsigned>(win_size), variance_normalization);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : ss::hip_err(e, "ss_cmvn_stream_packed_kernel");
+    return e == hipSuccess ? SS_OK : ss::hip_fail(e, "ss_cmvn_stream_packed_kernel");
 }
 
 // Host-pointer form: the tables are checked here, before anything touches the device; then vec, the row offsets and the n_active
@@ -1133,59 +1077,39 @@ int ss_cmvn_stream_packed(const float *vec, size_t n_active, const int64_t *row_
     if (n_active == 0) return SS_OK;
     if (!row_offsets) return ss::fail(SS_ERR_ARG, "null buffer");
     if (n_active >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
-    if (row_offsets[0] != 0) return ss::fail(SS_ERR_ARG, "row_offsets[0] must be 0 (entry 0)");
-    for (size_t i = 0; i < n_active; ++i)
-        if (row_offsets[i + 1] < row_offsets[i]) return ss::fail(SS_ERR_ARG, "decreasing row offsets at entry " + std::to_string(i));
+    int rc = ss::check_row_offsets(row_offsets, n_active);
+    if (rc) return rc;
     const size_t rows = static_cast<size_t>(row_offsets[n_active]);
     size_t len = 0;
-    int rc = ss::check_cmvn_stream(vec, row_offsets, slots, n_active, rows, pool_streams, cols, win_size, pool, out, len);
-    if (rc) return rc;
-    {
-        std::unordered_set<int32_t> seen;
-        seen.reserve(n_active);
-        for (size_t i = 0; i < n_active; ++i) {
-            if (slots[i] < 0 || static_cast<size_t>(slots[i]) >= pool_streams)
-                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is outside the pool of " +
-                                                std::to_string(pool_streams) + " rows");
-            if (!seen.insert(slots[i]).second)
-                return ss::fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is named twice in one call");
-        }
-    }
+    if ((rc = ss::check_cmvn_stream(vec, row_offsets, slots, n_active, rows, pool_streams, cols, win_size, pool, out, len)) ||
+        (rc = ss::check_slots(slots, n_active, pool_streams)))
+        return rc;
     if (rows == 0) return SS_OK;  // entries without rows only: nothing moves
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return ss::fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd path has no CPU fallback");
-    std::vector<float> rows_host(n_active * len);
-    std::vector<int32_t> iota(n_active);
-    for (size_t i = 0; i < n_active; ++i) {
-        iota[i] = static_cast<int32_t>(i);
-        std::memcpy(rows_host.data() + i * len, pool + static_cast<size_t>(slots[i]) * len, len * sizeof(float));
-    }
-    const size_t bytes = rows * cols * sizeof(float), tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * len * sizeof(float);
-    void *d_vec = nullptr, *d_out = nullptr, *d_ro = nullptr, *d_sl = nullptr, *d_pool = nullptr;
-    hipError_t e = hipMalloc(&d_vec, bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_out, bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_ro, tbytes);
-    if (e == hipSuccess) e = hipMalloc(&d_sl, n_active * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_pool, sbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_vec, vec, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_ro, row_offsets, tbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_sl, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pool, rows_host.data(), sbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? ss_cmvn_stream_packed_device(static_cast<const float *>(d_vec), n_active, static_cast<const int64_t *>(d_ro), rows,
-                                                        static_cast<const int32_t *>(d_sl), n_active, cols, win_size, variance_normalization,
-                                                        static_cast<float *>(d_pool), static_cast<float *>(d_out), nullptr)
-                         : ss::hip_err(e, "host staging");
+    if (!ss::have_device()) return ss::no_device();
+    ss::PoolRows named;
+    named.gather(pool, slots, n_active, len);
+    const size_t bytes = rows * cols * sizeof(float), tbytes = (n_active + 1) * sizeof(int64_t), ibytes = n_active * sizeof(int32_t);
+    ss::DeviceBuf d_vec, d_out, d_ro, d_sl, d_pool;
+    hipError_t e = d_vec.hip_alloc(bytes);
+    if (e == hipSuccess) e = d_out.hip_alloc(bytes);
+    if (e == hipSuccess) e = d_ro.hip_alloc(tbytes);
+    if (e == hipSuccess) e = d_sl.hip_alloc(ibytes);
+    if (e == hipSuccess) e = d_pool.hip_alloc(named.bytes());
+    if (e == hipSuccess) e = hipMemcpy(d_vec.p, vec, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_ro.p, row_offsets, tbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_sl.p, named.iota.data(), ibytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_pool.p, named.rows_host.data(), named.bytes(), hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? ss_cmvn_stream_packed_device(d_vec.as<const float>(), n_active, d_ro.as<const int64_t>(), rows, d_sl.as<const int32_t>(),
+                                                        n_active, cols, win_size, variance_normalization, d_pool.as<float>(), d_out.as<float>(),
+                                                        nullptr)
+                         : ss::hip_fail(e, "host staging");
     if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_cmvn_stream_packed: device error");
     if (rc == SS_OK) {
-        e = hipMemcpy(rows_host.data(), d_pool, sbytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = ss::hip_err(e, "hipMemcpy D2H");
+        e = hipMemcpy(named.rows_host.data(), d_pool.p, named.bytes(), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = ss::hip_fail(e, "hipMemcpy D2H");
     }
-    if (rc == SS_OK)
-        for (size_t i = 0; i < n_active; ++i) std::memcpy(pool + static_cast<size_t>(slots[i]) * len, rows_host.data() + i * len, len * sizeof(float));
-    for (void *p : {d_vec, d_out, d_ro, d_sl, d_pool})
-        if (p) (void)hipFree(p);
+    if (rc == SS_OK) named.scatter(pool, slots);
     return rc;
 }
 

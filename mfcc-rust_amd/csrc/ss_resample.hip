@@ -6,6 +6,9 @@
 // the tile it was computed in, the clip's place in the block, the entry's place in the call or how a stream was cut into calls.
 // The reference crate has no resampler, so this file restates nothing of it.  The PCM scale rule is that of ss_api.hip, restated
 // here so that the existing objects build exactly as before.
+#include "ss_device.h"
+#include "ss_hip_staging.h"
+#include "ss_host_checks.h"
 #include "ss_internal.h"
 
 #include <hip/hip_runtime.h>
@@ -19,7 +22,6 @@
 #include <mutex>
 #include <numeric>
 #include <string>
-#include <unordered_set>
 #include <vector>
 
 namespace ss {
@@ -273,22 +275,6 @@ __global__ __launch_bounds__(kLanes) void ss_resample_stream_kernel(const T *__r
 
 // ---- host side ----
 
-int hip_err(hipError_t e, const char *what) { return fail(SS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
-bool have_device()
-{
-    int ndev = 0;
-    return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
-}
-
-int no_device() { return fail(SS_ERR_HIP, "no usable HIP device: the speechsauce_amd path has no CPU fallback"); }
-
 // a power of two in [2^-64, 2^64]: the product with an int16 is exact (and never subnormal)
 int check_pcm_scale(float scale)
 {
@@ -442,7 +428,7 @@ int device_table(const ss_resampler *rs_c, const unsigned **d_tab)
         if (e == hipSuccess) e = hipMemcpy(p, rs->tab.data(), rs->tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             if (p) (void)hipFree(p);
-            return hip_err(e, "resampler table upload");
+            return hip_fail(e, "resampler table upload");
         }
         rs->d_tab = static_cast<unsigned *>(p);
         rs->device = dev;
@@ -457,14 +443,6 @@ unsigned lds_bytes(const Geom &g)
 {
     const unsigned span_cap = ((g.tile - 1) * g.o + g.lookback + g.lookahead + 1 + 3) & ~3u;
     return 4u * (span_cap + (g.n <= kUniPhases ? 0u : g.tab_words));
-}
-
-// workgroups per clip (gridDim.y), as the packed post-processing calls size it: about 8192 workgroups in all, at most 64 per clip
-// and never more than the longest possible clip has tiles.  The bits of the results do not depend on it.
-unsigned clip_split(size_t n_clips, unsigned long long most_useful)
-{
-    const unsigned long long want = std::max<unsigned long long>(1, 8192 / n_clips);
-    return static_cast<unsigned>(std::min<unsigned long long>(64, std::min(want, std::max<unsigned long long>(1, most_useful))));
 }
 
 template <typename T>
@@ -484,14 +462,14 @@ int launch_clips(const ss_resampler *rs, const T *d_x, size_t n_clips, const int
     const Geom &g = rs->f.g;
     const unsigned long long longest_out = PACKED ? total_out : (static_cast<unsigned long long>(n_samples) * g.n + g.o - 1) / g.o;
     const unsigned long long tile_out = static_cast<unsigned long long>(g.tile) * g.n;
-    const dim3 grid(static_cast<unsigned>(n_clips), clip_split(n_clips, (longest_out + tile_out - 1) / tile_out));
+    const dim3 grid(static_cast<unsigned>(n_clips), packed_split(n_clips, (longest_out + tile_out - 1) / tile_out));
     auto kernel = g.n <= kUniPhases ? ss_resample_kernel<T, PACKED, true> : ss_resample_kernel<T, PACKED, false>;
     hipLaunchKernelGGL(kernel, grid, dim3(kLanes), lds_bytes(g), static_cast<hipStream_t>(stream), d_x, reinterpret_cast<const long long *>(d_so),
                        reinterpret_cast<const long long *>(d_oo), d_out, d_tab, g, static_cast<unsigned long long>(total_in),
                        static_cast<unsigned long long>(total_out), static_cast<unsigned>(n_samples), static_cast<unsigned long long>(ld),
                        static_cast<unsigned long long>(ld_out), scale);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_err(e, "ss_resample_kernel");
+    if (e != hipSuccess) return hip_fail(e, "ss_resample_kernel");
     note_kernel(kernel_name<T>(PACKED));
     return SS_OK;
 }
@@ -544,19 +522,17 @@ int dense_host(const ss_resampler *rs, const T *x, size_t batch, size_t n_sample
     if (rc) return rc;
     if (out_len == 0) return SS_OK;
     if (!have_device()) return no_device();
-    void *d_in = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc(&d_in, batch * n_samples * sizeof(T));
-    if (e == hipSuccess) e = hipMalloc(&d_out, batch * out_len * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy2D(d_in, n_samples * sizeof(T), x, ld * sizeof(T), n_samples * sizeof(T), batch, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? dense_device<T>(rs, static_cast<const T *>(d_in), batch, n_samples, n_samples, scale, static_cast<float *>(d_out), out_len, nullptr)
-                         : hip_err(e, "host staging");
+    DeviceBuf d_in, d_out;
+    hipError_t e = d_in.hip_alloc(batch * n_samples * sizeof(T));
+    if (e == hipSuccess) e = d_out.hip_alloc(batch * out_len * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy2D(d_in.p, n_samples * sizeof(T), x, ld * sizeof(T), n_samples * sizeof(T), batch, hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? dense_device<T>(rs, d_in.as<const T>(), batch, n_samples, n_samples, scale, d_out.as<float>(), out_len, nullptr)
+                         : hip_fail(e, "host staging");
     if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_resample: device error");
     if (rc == SS_OK) {
-        e = hipMemcpy2D(out, ld_out * sizeof(float), d_out, out_len * sizeof(float), out_len * sizeof(float), batch, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_err(e, "hipMemcpy D2H");
+        e = hipMemcpy2D(out, ld_out * sizeof(float), d_out.p, out_len * sizeof(float), out_len * sizeof(float), batch, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
     }
-    for (void *p : {d_in, d_out})
-        if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -615,24 +591,22 @@ int packed_host(const ss_resampler *rs, const T *x, size_t n_clips, const int64_
     if (total_out == 0) return SS_OK;
     if (!have_device()) return no_device();
     const size_t tbytes = (n_clips + 1) * sizeof(int64_t);
-    void *d_in = nullptr, *d_out = nullptr, *d_so = nullptr, *d_oo = nullptr;
-    hipError_t e = hipMalloc(&d_in, total_in * sizeof(T));
-    if (e == hipSuccess) e = hipMalloc(&d_out, total_out * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_so, tbytes);
-    if (e == hipSuccess) e = hipMalloc(&d_oo, tbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in, x, total_in * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_so, so, tbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_oo, oo, tbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? packed_device<T>(rs, static_cast<const T *>(d_in), n_clips, static_cast<const int64_t *>(d_so), scale,
-                                            static_cast<const int64_t *>(d_oo), total_in, total_out, static_cast<float *>(d_out), nullptr)
-                         : hip_err(e, "host staging");
+    DeviceBuf d_in, d_out, d_so, d_oo;
+    hipError_t e = d_in.hip_alloc(total_in * sizeof(T));
+    if (e == hipSuccess) e = d_out.hip_alloc(total_out * sizeof(float));
+    if (e == hipSuccess) e = d_so.hip_alloc(tbytes);
+    if (e == hipSuccess) e = d_oo.hip_alloc(tbytes);
+    if (e == hipSuccess) e = hipMemcpy(d_in.p, x, total_in * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_so.p, so, tbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_oo.p, oo, tbytes, hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? packed_device<T>(rs, d_in.as<const T>(), n_clips, d_so.as<const int64_t>(), scale, d_oo.as<const int64_t>(), total_in,
+                                            total_out, d_out.as<float>(), nullptr)
+                         : hip_fail(e, "host staging");
     if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_resample_packed: device error");
     if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out, total_out * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_err(e, "hipMemcpy D2H");
+        e = hipMemcpy(out, d_out.p, total_out * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
     }
-    for (void *p : {d_in, d_out, d_so, d_oo})
-        if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -675,7 +649,7 @@ int stream_launch(const ss_resampler *rs, const T *d_x, size_t n_active, const i
                        reinterpret_cast<const long long *>(d_so), reinterpret_cast<const int *>(d_slots), d_out, d_pool, d_tab, g,
                        static_cast<unsigned long long>(total_in), static_cast<unsigned>(pool_streams), scale);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_err(e, "ss_resample_stream_kernel");
+    if (e != hipSuccess) return hip_fail(e, "ss_resample_stream_kernel");
     note_kernel(FLUSH ? "ss_resample_stream_kernel<flush>" : sizeof(T) == 4 ? "ss_resample_stream_kernel<f32>" : "ss_resample_stream_kernel<i16>");
     return SS_OK;
 }
@@ -691,21 +665,6 @@ int stream_device(const ss_resampler *rs, const T *d_x, size_t n_active, const i
     return stream_launch<T, false>(rs, d_x, n_active, d_so, total_in, d_slots, pool_streams, scale, d_pool, d_out, stream);
 }
 
-// the slots of a host-pointer call: inside the pool, none named twice
-int check_slots(const int32_t *slots, size_t n_active, size_t pool_streams)
-{
-    std::unordered_set<int32_t> seen;
-    seen.reserve(n_active);
-    for (size_t i = 0; i < n_active; ++i) {
-        if (slots[i] < 0 || static_cast<size_t>(slots[i]) >= pool_streams)
-            return fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is outside the pool of " +
-                                        std::to_string(pool_streams) + " rows");
-        if (!seen.insert(slots[i]).second)
-            return fail(SS_ERR_ARG, "entry " + std::to_string(i) + ": slot " + std::to_string(slots[i]) + " is named twice in one call");
-    }
-    return SS_OK;
-}
-
 // Host staging of both pool calls: x (none for the flush) and the offsets go up with the n_active named pool rows, gathered into a
 // compact block whose row i is entry i's (the device call runs on slots 0 .. n_active - 1); the outputs and the pool rows come down.
 // The caller's pool is written only once everything before it succeeded.
@@ -714,44 +673,36 @@ int stream_via_device(bool flush, const ss_resampler *rs, const T *x, size_t n_a
                       float scale, float *pool, float *out)
 {
     if (!have_device()) return no_device();
-    const size_t len = static_cast<size_t>(rs->f.g.hist) + 1;
-    std::vector<float> rows_host(n_active * len);
-    std::vector<int32_t> iota(n_active);
-    for (size_t i = 0; i < n_active; ++i) {
-        iota[i] = static_cast<int32_t>(i);
-        std::memcpy(rows_host.data() + i * len, pool + static_cast<size_t>(slots[i]) * len, len * sizeof(float));
-    }
-    const size_t bytes = n_in * sizeof(T), obytes = n_out * sizeof(float), tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * len * sizeof(float);
-    void *d_x = nullptr, *d_out = nullptr, *d_so = nullptr, *d_sl = nullptr, *d_pool = nullptr;
-    hipError_t e = hipMalloc(&d_out, obytes);
-    if (e == hipSuccess) e = hipMalloc(&d_sl, n_active * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_pool, sbytes);
+    PoolRows named;
+    named.gather(pool, slots, n_active, static_cast<size_t>(rs->f.g.hist) + 1);
+    const size_t bytes = n_in * sizeof(T), obytes = n_out * sizeof(float), tbytes = (n_active + 1) * sizeof(int64_t), ibytes = n_active * sizeof(int32_t);
+    DeviceBuf d_x, d_out, d_so, d_sl, d_pool;
+    hipError_t e = d_out.hip_alloc(obytes);
+    if (e == hipSuccess) e = d_sl.hip_alloc(ibytes);
+    if (e == hipSuccess) e = d_pool.hip_alloc(named.bytes());
     if (!flush) {
-        if (e == hipSuccess) e = hipMalloc(&d_x, bytes);
-        if (e == hipSuccess) e = hipMalloc(&d_so, tbytes);
-        if (e == hipSuccess) e = hipMemcpy(d_x, x, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_so, so, tbytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = d_x.hip_alloc(bytes);
+        if (e == hipSuccess) e = d_so.hip_alloc(tbytes);
+        if (e == hipSuccess) e = hipMemcpy(d_x.p, x, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_so.p, so, tbytes, hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess) e = hipMemcpy(d_sl, iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pool, rows_host.data(), sbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_sl.p, named.iota.data(), ibytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_pool.p, named.rows_host.data(), named.bytes(), hipMemcpyHostToDevice);
     int rc = SS_OK;
-    if (e != hipSuccess) rc = hip_err(e, "host staging");
+    if (e != hipSuccess) rc = hip_fail(e, "host staging");
     else if (flush)
-        rc = stream_launch<float, true>(rs, nullptr, n_active, nullptr, 0, static_cast<const int32_t *>(d_sl), n_active, 1.0f, static_cast<float *>(d_pool),
-                                        static_cast<float *>(d_out), nullptr);
+        rc = stream_launch<float, true>(rs, nullptr, n_active, nullptr, 0, d_sl.as<const int32_t>(), n_active, 1.0f, d_pool.as<float>(), d_out.as<float>(),
+                                        nullptr);
     else
-        rc = stream_device<T>(rs, static_cast<const T *>(d_x), n_active, static_cast<const int64_t *>(d_so), n_in, static_cast<const int32_t *>(d_sl), n_active,
-                              scale, static_cast<float *>(d_pool), static_cast<float *>(d_out), nullptr);
+        rc = stream_device<T>(rs, d_x.as<const T>(), n_active, d_so.as<const int64_t>(), n_in, d_sl.as<const int32_t>(), n_active, scale, d_pool.as<float>(),
+                              d_out.as<float>(), nullptr);
     if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_resample_stream: device error");
     if (rc == SS_OK) {
-        e = hipMemcpy(rows_host.data(), d_pool, sbytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_err(e, "hipMemcpy D2H");
+        e = hipMemcpy(named.rows_host.data(), d_pool.p, named.bytes(), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out, d_out.p, obytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
     }
-    if (rc == SS_OK)
-        for (size_t i = 0; i < n_active; ++i) std::memcpy(pool + static_cast<size_t>(slots[i]) * len, rows_host.data() + i * len, len * sizeof(float));
-    for (void *p : {d_x, d_out, d_so, d_sl, d_pool})
-        if (p) (void)hipFree(p);
+    if (rc == SS_OK) named.scatter(pool, slots);
     return rc;
 }
 

@@ -1046,6 +1046,19 @@ class MfeStream(_FrameStreamBase):
 
 # ---- ragged streaming over a pool of stream states ---------------------------------------------------------------------------
 
+def _pool_slots(slots, pool_streams, what, entry="entry"):
+    """The slot rule of every pool call: integers inside the pool, none named twice -> the list."""
+    slot_list = [int(v) for v in slots]
+    seen = set()
+    for i, v in enumerate(slot_list):
+        if not 0 <= v < pool_streams:
+            raise ValueError(f"{what}: slot {v} of {entry} {i} is outside the pool of {pool_streams} streams")
+        if v in seen:
+            raise ValueError(f"{what}: slot {v} is named twice in one call")
+        seen.add(v)
+    return slot_list
+
+
 class _StreamPoolMixin:
     """The pool plumbing of the ragged streaming classes, in front of a dense streaming base (``_FrameStreamBase`` or
     ``_StreamBase``) whose ``n_streams`` is the pool size: the argument rules of ``pool(chunks, slots, lengths=None)``, the pool
@@ -1089,13 +1102,7 @@ class _StreamPoolMixin:
         for i, n in enumerate(lens):
             if n % self.hop:
                 raise ValueError(f"{what}: chunk {i} has {n} samples, not a multiple of the hop {self.hop}")
-        seen = set()
-        for i, v in enumerate(slot_list):
-            if not 0 <= v < self.pool_streams:
-                raise ValueError(f"{what}: slot {v} of chunk {i} is outside the pool of {self.pool_streams} streams")
-            if v in seen:
-                raise ValueError(f"{what}: slot {v} is named twice in one call")
-            seen.add(v)
+        _pool_slots(slot_list, self.pool_streams, what, "chunk")
         first = packed if packed is not None else (parts[0] if parts else None)
         on_dev = first is not None and _is_torch(first)
         if first is None:  # nothing to serve: the place of the pool decides, the host before any call
@@ -1297,9 +1304,54 @@ class StftStreamPool(_StftStreamPoolBase):
         return out.view(np.complex64)[..., 0], ro
 
 
+# ---- the pools of the side stages (CMVN, add-deltas, resampling): a block, its offset table and the slots of its entries ------
+
+class _SidePool:
+    """What ``CmvnStreamPool``, ``AddDeltasStreamPool`` and ``ResampleStreamPool`` share: the slot rule, the rules of the offset
+    table (``_table`` names it, ``_noun`` what it counts), the place of the pool and its allocation by the first call.  A class
+    sets ``_what``, ``pool_streams`` and ``state_len``, and ``_state`` / ``_where`` to None."""
+
+    _table, _noun = "row_offsets", "rows"
+
+    def _slots(self, slots):
+        return _pool_slots(slots, self.pool_streams, self._what)
+
+    def _offsets(self, offsets):
+        """The offset table as a host int64 array (its shape and dtype checked, not yet its values)."""
+        off = np.asarray(offsets.cpu() if _is_torch(offsets) else offsets)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError(f"{self._what}: {self._table} must be 1-D with one entry more than slots")
+        if not np.issubdtype(off.dtype, np.integer):
+            raise TypeError(f"{self._what}: {self._table} must be integers, got {off.dtype}")
+        return np.ascontiguousarray(off, dtype=np.int64)
+
+    def _check_offsets(self, off, n_slots, total):
+        if n_slots != off.size - 1:
+            raise ValueError(f"{self._what}: {off.size - 1} entries in {self._table} but {n_slots} slots")
+        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] > total:
+            raise ValueError(f"{self._what}: {self._table} must start at 0, not decrease and end within the block's {total} {self._noun}")
+
+    def _place(self, x):
+        """Where ``x`` lives; it must be where the pool lives once a call has placed it."""
+        where = ("cuda", x.device.index) if _is_torch(x) else ("host",)
+        if self._where is not None and where != self._where:
+            raise ValueError(f"{self._what}: the pool lives on {self._where}, these {self._noun} on {where}")
+        return where
+
+    def _state_for(self, x):
+        """The pool's state, or zeros next to ``x`` for the first call (which keeps them only once it went through)."""
+        if self._state is not None:
+            return self._state
+        if _is_torch(x):
+            import torch
+
+            return torch.zeros((self.pool_streams, self.state_len), dtype=torch.float32, device=x.device)
+        return np.zeros((self.pool_streams, self.state_len), dtype=np.float32)
+
+
 # ---- causal sliding-window CMVN over a pool of stream states (ss_cmvn_stream_packed*) ---------------------------------------
 
-class CmvnStreamPool:
+class CmvnStreamPool(_SidePool):
     """Causal mean (and variance) normalisation of the rows of live streams: every row over the trailing ``win_size`` rows of its
     own stream (the row itself the newest, no padding at a stream's start), with the last ``win_size - 1`` raw rows of each of
     ``pool_streams`` streams carried from call to call.  ``pool(rows, row_offsets, slots)`` takes the ``(rows, row_offsets)`` pair
@@ -1351,37 +1403,19 @@ class CmvnStreamPool:
         if int(x.shape[1]) != self.cols:
             raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool normalises {self.cols}")
         total_rows = int(x.shape[0])
-        ro = np.asarray(row_offsets.cpu() if _is_torch(row_offsets) else row_offsets)
-        if ro.ndim != 1 or ro.size < 1:
-            raise ValueError(f"{what}: row_offsets must be 1-D with one entry more than slots")
-        if not np.issubdtype(ro.dtype, np.integer):
-            raise TypeError(f"{what}: row_offsets must be integers, got {ro.dtype}")
-        ro = np.ascontiguousarray(ro, dtype=np.int64)
+        ro = self._offsets(row_offsets)
         slot_list = [int(v) for v in slots]
-        if len(slot_list) != ro.size - 1:
-            raise ValueError(f"{what}: {ro.size - 1} entries in row_offsets but {len(slot_list)} slots")
-        if ro[0] != 0 or (np.diff(ro) < 0).any() or ro[-1] > total_rows:
-            raise ValueError(f"{what}: row_offsets must start at 0, not decrease and end within the block's {total_rows} rows")
-        seen = set()
-        for i, v in enumerate(slot_list):
-            if not 0 <= v < self.pool_streams:
-                raise ValueError(f"{what}: slot {v} of entry {i} is outside the pool of {self.pool_streams} streams")
-            if v in seen:
-                raise ValueError(f"{what}: slot {v} is named twice in one call")
-            seen.add(v)
-        on_dev = _is_torch(x)
-        where = ("cuda", x.device.index) if on_dev else ("host",)
-        if self._where is not None and where != self._where:
-            raise ValueError(f"{what}: the pool lives on {self._where}, these rows on {where}")
+        self._check_offsets(ro, len(slot_list), total_rows)
+        self._slots(slot_list)  # (this pool decides the table before the slots)
+        where = self._place(x)
         lib, n_active = _lib.lib(), len(slot_list)
         sl = np.asarray(slot_list, dtype=np.int32)
         var = int(self.variance_normalization)
-        if on_dev:
+        state = self._state_for(x)
+        if _is_torch(x):
             import torch
 
             x = x.contiguous()
-            state = self._state if self._state is not None else torch.zeros((self.pool_streams, self.state_len), dtype=torch.float32,
-                                                                            device=x.device)
             out = torch.empty_like(x)
             if n_active and total_rows:
                 with torch.cuda.device(x.device):
@@ -1393,7 +1427,6 @@ class CmvnStreamPool:
                         t.record_stream(torch.cuda.current_stream())
         else:
             x = np.ascontiguousarray(x)
-            state = self._state if self._state is not None else np.zeros((self.pool_streams, self.state_len), dtype=np.float32)
             out = np.empty_like(x)
             if n_active and total_rows:
                 _lib.check(lib.ss_cmvn_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, self.pool_streams, self.cols,
@@ -1789,7 +1822,7 @@ def add_deltas(feat, order=2, window=2):
     return out.reshape(shape[:-1] + ((int(order) + 1) * cols,))
 
 
-class AddDeltasStreamPool:
+class AddDeltasStreamPool(_SidePool):
     """Kaldi ``add-deltas`` over the rows of live streams, with a fixed latency of ``lag = order * window`` rows: deltas need ``lag``
     rows of look-ahead, so output row k of an entry is the feature row of stream time ``rows_seen + k - lag`` (all zeros while that is
     negative: the first ``lag`` rows after a reset are warm-up rows).  ``pool(rows, row_offsets, slots)`` takes the ``(rows,
@@ -1826,17 +1859,6 @@ class AddDeltasStreamPool:
         the first call."""
         return self._state
 
-    def _slots(self, slots):
-        slot_list = [int(v) for v in slots]
-        seen = set()
-        for i, v in enumerate(slot_list):
-            if not 0 <= v < self.pool_streams:
-                raise ValueError(f"{self._what}: slot {v} of entry {i} is outside the pool of {self.pool_streams} streams")
-            if v in seen:
-                raise ValueError(f"{self._what}: slot {v} is named twice in one call")
-            seen.add(v)
-        return slot_list
-
     def reset(self, slots=None):
         """Zero the state (and ``rows_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
         idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
@@ -1855,29 +1877,17 @@ class AddDeltasStreamPool:
         if int(x.shape[1]) != self.cols:
             raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool takes {self.cols}")
         total_rows = int(x.shape[0])
-        ro = np.asarray(row_offsets.cpu() if _is_torch(row_offsets) else row_offsets)
-        if ro.ndim != 1 or ro.size < 1:
-            raise ValueError(f"{what}: row_offsets must be 1-D with one entry more than slots")
-        if not np.issubdtype(ro.dtype, np.integer):
-            raise TypeError(f"{what}: row_offsets must be integers, got {ro.dtype}")
-        ro = np.ascontiguousarray(ro, dtype=np.int64)
+        ro = self._offsets(row_offsets)
         slot_list = self._slots(slots)
-        if len(slot_list) != ro.size - 1:
-            raise ValueError(f"{what}: {ro.size - 1} entries in row_offsets but {len(slot_list)} slots")
-        if ro[0] != 0 or (np.diff(ro) < 0).any() or ro[-1] > total_rows:
-            raise ValueError(f"{what}: row_offsets must start at 0, not decrease and end within the block's {total_rows} rows")
-        on_dev = _is_torch(x)
-        where = ("cuda", x.device.index) if on_dev else ("host",)
-        if self._where is not None and where != self._where:
-            raise ValueError(f"{what}: the pool lives on {self._where}, these rows on {where}")
+        self._check_offsets(ro, len(slot_list), total_rows)
+        where = self._place(x)
         lib, n_active = _lib.lib(), len(slot_list)
         sl = np.asarray(slot_list, dtype=np.int32)
-        if on_dev:
+        state = self._state_for(x)
+        if _is_torch(x):
             import torch
 
             x = x.contiguous()
-            state = self._state if self._state is not None else torch.zeros((self.pool_streams, self.state_len), dtype=torch.float32,
-                                                                            device=x.device)
             out = torch.empty((total_rows, self.out_cols), dtype=torch.float32, device=x.device)
             if n_active and total_rows:
                 with torch.cuda.device(x.device):
@@ -1889,7 +1899,6 @@ class AddDeltasStreamPool:
                         t.record_stream(torch.cuda.current_stream())
         else:
             x = np.ascontiguousarray(x)
-            state = self._state if self._state is not None else np.zeros((self.pool_streams, self.state_len), dtype=np.float32)
             out = np.empty((total_rows, self.out_cols), dtype=np.float32)
             if n_active and total_rows:
                 _lib.check(lib.ss_add_deltas_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, self.pool_streams, self.cols,
@@ -2080,7 +2089,7 @@ def resample_list(signals, orig_rate, new_rate, lowpass_filter_width=6, rolloff=
     return [out[oo[b]:oo[b + 1]] for b in range(len(sigs))]
 
 
-class ResampleStreamPool:
+class ResampleStreamPool(_SidePool):
     """``resample`` over the samples of live streams, with a fixed latency of ``latency_periods`` periods: a stream is fed whole
     periods of ``o`` samples (``period_in``; 441 samples = 10 ms for 44.1 kHz -> 16 kHz) and gets ``n`` outputs (``period_out``) per
     period, ``lag = latency_periods * n`` outputs late (zeros while the stream's output time is negative: the first ``lag`` outputs
@@ -2093,6 +2102,7 @@ class ResampleStreamPool:
     caller has buffered it to whole hops.  See ``ss_resample_stream_packed`` in ``include/speechsauce_amd.h``."""
 
     _what = "ResampleStreamPool"
+    _table, _noun = "sample_offsets", "samples"
 
     def __init__(self, pool_streams, orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99):
         what = self._what
@@ -2117,17 +2127,6 @@ class ResampleStreamPool:
         first call."""
         return self._state
 
-    def _slots(self, slots):
-        slot_list = [int(v) for v in slots]
-        seen = set()
-        for i, v in enumerate(slot_list):
-            if not 0 <= v < self.pool_streams:
-                raise ValueError(f"{self._what}: slot {v} of entry {i} is outside the pool of {self.pool_streams} streams")
-            if v in seen:
-                raise ValueError(f"{self._what}: slot {v} is named twice in one call")
-            seen.add(v)
-        return slot_list
-
     def reset(self, slots=None):
         """Zero the state (and ``periods_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
         idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
@@ -2144,35 +2143,23 @@ class ResampleStreamPool:
         what = self._what
         x, scale = _require_signal(samples, (1,), what, pcm_scale)
         total = int(x.shape[0])
-        so = np.asarray(sample_offsets.cpu() if _is_torch(sample_offsets) else sample_offsets)
-        if so.ndim != 1 or so.size < 1:
-            raise ValueError(f"{what}: sample_offsets must be 1-D with one entry more than slots")
-        if not np.issubdtype(so.dtype, np.integer):
-            raise TypeError(f"{what}: sample_offsets must be integers, got {so.dtype}")
-        so = np.ascontiguousarray(so, dtype=np.int64)
+        so = self._offsets(sample_offsets)
         slot_list = self._slots(slots)
-        if len(slot_list) != so.size - 1:
-            raise ValueError(f"{what}: {so.size - 1} entries in sample_offsets but {len(slot_list)} slots")
-        if so[0] != 0 or (np.diff(so) < 0).any() or so[-1] > total:
-            raise ValueError(f"{what}: sample_offsets must start at 0, not decrease and end within the block's {total} samples")
+        self._check_offsets(so, len(slot_list), total)
         if (np.diff(so) % self.period_in).any():
             raise ValueError(f"{what}: every entry must bring whole periods of {self.period_in} samples")
-        on_dev = _is_torch(x)
-        where = ("cuda", x.device.index) if on_dev else ("host",)
-        if self._where is not None and where != self._where:
-            raise ValueError(f"{what}: the pool lives on {self._where}, these samples on {where}")
+        where = self._place(x)
         lib, n_active = _lib.lib(), len(slot_list)
         rs = _get_resampler(*self._args, _device_key(x))
         i16, sc = ("", []) if scale is None else ("_i16", [scale])
         sl = np.asarray(slot_list, dtype=np.int32)
         n_in = int(so[-1])
         n_out = n_in // self.period_in * self.period_out
-        if on_dev:
+        state = self._state_for(x)
+        if _is_torch(x):
             import torch
 
             x = x.contiguous()
-            state = self._state if self._state is not None else torch.zeros((self.pool_streams, self.state_len), dtype=torch.float32,
-                                                                            device=x.device)
             out = torch.empty((n_out,), dtype=torch.float32, device=x.device)
             if n_active and n_in:
                 with torch.cuda.device(x.device):
@@ -2184,7 +2171,6 @@ class ResampleStreamPool:
                         t.record_stream(torch.cuda.current_stream())
         else:
             x = np.ascontiguousarray(x)
-            state = self._state if self._state is not None else np.zeros((self.pool_streams, self.state_len), dtype=np.float32)
             out = np.empty((n_out,), dtype=np.float32)
             if n_active and n_in:
                 _lib.check(getattr(lib, f"ss_resample_stream_packed{i16}")(rs.handle, x.ctypes.data, n_active, so.ctypes.data, sl.ctypes.data,
