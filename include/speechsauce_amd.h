@@ -974,6 +974,123 @@ int ss_resample_stream_flush_device(const ss_resampler *rs, size_t n_active, con
                                     float *d_out, void *stream);
 int ss_resample_stream_flush(const ss_resampler *rs, size_t n_active, const int32_t *slots, size_t pool_streams, float *pool, float *out);
 
+/* ---- Kaldi-compatible fbank / MFCC front end (compute-fbank-feats / compute-mfcc-feats as torchaudio.compliance.kaldi.fbank / .mfcc
+ * restate them) for frames that pad to 512 points ----
+ * The stage that ss_resample*, ss_cmvn_stream_packed* and ss_add_deltas* wrap in a Kaldi-shaped pipeline.  The reference crate has no
+ * such path and no combination of ss_params switches gives it, so it has its own parameter structure, its own handle and this comment
+ * as its specification.  Arithmetic is f32 on the device unless stated; tables are formed in f64 on the host and rounded once.
+ *   Sizes: flen = (int)(sample_rate * 0.001 * frame_length_ms), shift = (int)(sample_rate * 0.001 * frame_shift_ms), in double;
+ *   N = the smallest power of two >= flen.  This version serves N == 512 only (256 < flen <= 512: 16 kHz at 20 / 25 / 32 ms, 11.025 kHz
+ *   at 25 ms); every other N is SS_ERR_UNSUPPORTED and is the next step.  shift >= 1, of either parity, may exceed flen.
+ *   Frames (snip_edges = true): T = 0 if L < flen, else 1 + (L - flen) / shift; frame t is x[t * shift : t * shift + flen].
+ *   Per frame, in this order:
+ *    1. s[i] = x[i] * input_scale (skipped when input_scale == 1).
+ *    2. remove_dc_offset: m = (sum s[i]) / flen -- a true division -- and s[i] -= m.
+ *    3. raw energy Er = sum s[i]^2 (used when raw_energy).
+ *    4. pre-emphasis with c = preemph_coef, when c != 0: y[i] = s[i] - c * s[i-1] for i >= 1, y[0] = s[0] - c * s[0]: the predecessor
+ *       is the frame's own sample, never the clip's.
+ *    5. window: y[i] *= w[i]; with a = 2 pi i / (flen - 1): povey (0.5 - 0.5 cos a)^0.85, hanning 0.5 - 0.5 cos a, hamming
+ *       0.54 - 0.46 cos a, rectangular 1, blackman b - 0.5 cos a + (0.5 - b) cos 2a with b = blackman_coeff.  Without raw_energy the
+ *       energy is sum y[i]^2 taken here.
+ *    6. zero-pad to N, real FFT, P[k] = |X[k]|^2 (use_power) or |X[k]| for k = 0 .. N/2 - 1: no 1/N, the Nyquist bin is not used.
+ *    7. mel bank: mel(f) = 1127 ln(1 + f / 700); high_freq <= 0 means sample_rate / 2 + high_freq; delta = (mel(high) - mel(low)) /
+ *       (num_mel_bins + 1); filter b has left, centre, right at mel(low) + b delta, + (b+1) delta, + (b+2) delta; bin k at mu =
+ *       mel(k sample_rate / N) has a weight only if left < mu < right (strict): (mu - left) / (centre - left) if mu <= centre, else
+ *       (right - mu) / (right - centre).  No normalisation, no VTLN.  e[b] = sum_k weight[b][k] P[k].
+ *    8. fbank[b] = ln(max(e[b], eps)), eps = 1.1920929e-7: a floor (not the reference's == 0 patch); an empty filter gives ln eps.
+ *    9. log energy = ln(max(E, eps)), and the maximum of that and ln(energy_floor) if energy_floor > 0.
+ *   10. MFCC: c[k] = lift[k] sum_b D[k][b] fbank[b], k < num_ceps; D[0][b] = sqrt(1/M), D[k][b] = sqrt(2/M) cos(pi/M (b + 0.5) k);
+ *       lift[k] = 1 + 0.5 Q sin(pi k / Q), Q = cepstral_lifter (Q == 0: no lifter), folded into the host table; use_energy: c[0] = the
+ *       log energy.
+ * Not in this version: _i16 entry points (use input_scale = 32768 on normalised floats, or feed integer-valued floats), stream pools,
+ * snip_edges = false, non-zero dither, VTLN, htk_compat, subtract_mean (ss_cmvn_packed does that), N != 512. */
+enum {
+    SS_KALDI_WINDOW_POVEY = 0,
+    SS_KALDI_WINDOW_HANNING = 1,
+    SS_KALDI_WINDOW_HAMMING = 2,
+    SS_KALDI_WINDOW_RECTANGULAR = 3,
+    SS_KALDI_WINDOW_BLACKMAN = 4
+};
+/* every field is 4 bytes wide, no padding.  ss_kaldi_params_default fills TORCHAUDIO's defaults (in the comments below); they differ
+ * from the Kaldi binaries' in dither = 0 (Kaldi: 1), energy_floor = 1 (Kaldi: 0) and use_energy = 0 (compute-mfcc-feats: true). */
+typedef struct ss_kaldi_params {
+    uint32_t struct_size;     /* sizeof(ss_kaldi_params) */
+    uint32_t sample_rate;
+    float frame_length_ms;    /* 25 */
+    float frame_shift_ms;     /* 10 */
+    uint32_t num_mel_bins;    /* 23 */
+    uint32_t num_ceps;        /* 13; the mfcc calls only, <= num_mel_bins */
+    float low_freq;           /* 20 */
+    float high_freq;          /* 0: <= 0 is an offset from sample_rate / 2 */
+    float preemph_coef;       /* 0.97 */
+    float cepstral_lifter;    /* 22 */
+    int32_t window_type;      /* SS_KALDI_WINDOW_POVEY */
+    float blackman_coeff;     /* 0.42 */
+    int32_t remove_dc_offset; /* 1 */
+    int32_t use_power;        /* 1 */
+    int32_t use_energy;       /* 0; the mfcc calls: c[0] = the log energy */
+    int32_t raw_energy;       /* 1 */
+    float energy_floor;       /* 1.0 */
+    float input_scale;        /* 1.0 */
+    float dither;             /* 0.0: the only value served */
+} ss_kaldi_params;
+typedef struct ss_kaldi_config ss_kaldi_config; /* opaque: the parameters, the device tables and a device error word */
+
+/* host only, no device.  Validation: SS_ERR_BAD_CONFIG for num_mel_bins < 3, low_freq < 0, a resolved high_freq <= low_freq or above
+ * sample_rate / 2, flen < 2, shift < 1, num_ceps > num_mel_bins, input_scale not finite or <= 0, energy_floor < 0, a window_type outside
+ * the enum; SS_ERR_UNSUPPORTED for a padded size other than 512, num_mel_bins > 80, num_ceps > 32, dither != 0. */
+int ss_kaldi_params_default(ss_kaldi_params *p, uint32_t sample_rate);
+int ss_kaldi_params_validate(const ss_kaldi_params *p);
+int ss_kaldi_sizes(const ss_kaldi_params *p, size_t *frame_len, size_t *frame_shift, size_t *padded);
+/* T == 0 is SS_ERR_SHORT_SIGNAL, as for ss_num_frames */
+int ss_kaldi_num_frames(const ss_kaldi_params *p, size_t n_samples, size_t *n_frames);
+/* the rules of ss_packed_frame_offsets */
+int ss_kaldi_packed_frame_offsets(const ss_kaldi_params *p, size_t n_clips, const int64_t *sample_offsets, int64_t *frame_offsets);
+/* w: [frame_len];  bank: [num_mel_bins x 256] dense (bins 0 .. 255);  dct: [num_ceps x num_mel_bins], the lifter folded in */
+int ss_kaldi_window(const ss_kaldi_params *p, float *w);
+int ss_kaldi_mel_bank(const ss_kaldi_params *p, float *bank);
+int ss_kaldi_dct(const ss_kaldi_params *p, float *dct);
+
+/* The handle: validated parameters, the kernel's tables uploaded at creation (to the current device: SS_ERR_HIP without one, after the
+ * parameter rules) and a pinned device error word, as ss_config owns one.  Immutable afterwards: usable from several streams and
+ * threads at once.  ss_kaldi_config_device_status has ss_config_device_status's contract: SS_ERR_DEVICE once if a launch on the handle
+ * reported a bad packed clip since the last look, then SS_OK. */
+int ss_kaldi_config_create(const ss_kaldi_params *p, ss_kaldi_config **out);
+void ss_kaldi_config_destroy(ss_kaldi_config *cfg);
+int ss_kaldi_config_params(const ss_kaldi_config *cfg, ss_kaldi_params *out);
+int ss_kaldi_config_device_status(const ss_kaldi_config *cfg);
+
+/* Equal-length clips: x [batch x ld] (n_samples <= ld used per row) -> out [batch x T x num_mel_bins] (fbank) or [batch x T x num_ceps]
+ * (mfcc; num_ceps >= 1), T = ss_kaldi_num_frames(n_samples).  log_energy ([batch x T], may be NULL) is written whenever the pointer
+ * is non-null, whatever use_energy says.  One launch of ss_kaldi_c256<NE,...> (ss_last_kernel_name(): NE = 10 / 13 / 16 live input
+ * pairs for flen <= 320 / 416 / 512, then "pow2" with use_power, "mfcc" or "fbank").  The _device forms are asynchronous on `stream`
+ * and graph-capturable; the host forms stage through device buffers and return when the results are in place.  Any ld, any base
+ * alignment of 4 bytes and either parity of shift are served.  batch == 0 is SS_OK; SS_ERR_SHORT_SIGNAL for n_samples < flen;
+ * SS_ERR_ARG for null buffers, ld < n_samples, n_samples >= 2^31, batch * T >= 2^32 - 8. */
+int ss_kaldi_fbank_device(const ss_kaldi_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out,
+                          float *d_log_energy, void *stream);
+int ss_kaldi_fbank(const ss_kaldi_config *cfg, const float *x, size_t batch, size_t n_samples, size_t ld, float *out, float *log_energy);
+int ss_kaldi_mfcc_device(const ss_kaldi_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out,
+                         void *stream);
+int ss_kaldi_mfcc(const ss_kaldi_config *cfg, const float *x, size_t batch, size_t n_samples, size_t ld, float *out);
+
+/* Packed clips: the contract of ss_mfcc_packed*.  Clip b is x[so[b] : so[b+1]], its T_b frames are rows fo[b] .. fo[b+1] of the output
+ * (fo from ss_kaldi_packed_frame_offsets, or computed by the caller on the device); one launch (ss_kaldi_c256<...,v>) whatever the
+ * clip count; n_clips == 0 is SS_OK.  The _device forms' tables are DEVICE arrays of n_clips + 1 entries that only the kernel reads:
+ * it recomputes every T_b from so, and a clip whose rows are not those T_b frames, or end past total_frames, is skipped -- its rows are
+ * left untouched, nothing is written outside d_out / d_log_energy -- and the handle's error word is raised (SS_ERR_DEVICE through
+ * ss_kaldi_config_device_status or the next call on the handle).  A clip's rows are bit for bit those of the equal-length call on that
+ * clip alone, whatever the parity of its offset.  The out_offsets of ss_resample_packed_offsets are valid sample_offsets as they
+ * stand: INTEGRATION.md shows the chain.  The host forms take sample_offsets alone, check them (ss_kaldi_packed_frame_offsets) and
+ * write out [so-implied rows x cols]. */
+int ss_kaldi_fbank_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                 const int64_t *d_frame_offsets, size_t total_frames, float *d_out, float *d_log_energy, void *stream);
+int ss_kaldi_fbank_packed(const ss_kaldi_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out,
+                          float *log_energy);
+int ss_kaldi_mfcc_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream);
+int ss_kaldi_mfcc_packed(const ss_kaldi_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out);
+
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`
  * computes clips [lo, hi) of ss_shard_bounds on its own device with the *_device entry points.  The north-star's "RCCL

@@ -639,6 +639,78 @@ private:
     ss_resample_info info_{};
 };
 
+// Kaldi's compute-fbank-feats / compute-mfcc-feats as torchaudio.compliance.kaldi restates them (ss_kaldi_*; not in the reference
+// crate), for frames that pad to 512 points.  The handle is shared by copies.
+inline ss_kaldi_params kaldi_params(uint32_t sample_rate)  // torchaudio's defaults
+{
+    ss_kaldi_params p;
+    check(ss_kaldi_params_default(&p, sample_rate));
+    return p;
+}
+class KaldiFrontEnd {
+public:
+    explicit KaldiFrontEnd(const ss_kaldi_params &p) : p_(p)
+    {
+        ss_kaldi_config *raw = nullptr;
+        check(ss_kaldi_config_create(&p, &raw));
+        h_ = std::shared_ptr<ss_kaldi_config>(raw, ss_kaldi_config_destroy);
+    }
+    const ss_kaldi_params &params() const { return p_; }
+    const ss_kaldi_config *handle() const { return h_.get(); }
+    size_t num_frames(size_t n_samples) const
+    {
+        size_t t = 0;
+        check(ss_kaldi_num_frames(&p_, n_samples, &t));
+        return t;
+    }
+    // one clip -> [T x num_mel_bins] log-mel rows; log_energy (may be null) receives the [T] log energies
+    std::vector<float> fbank(const std::vector<float> &x, std::vector<float> *log_energy = nullptr) const
+    {
+        const size_t t = num_frames(x.size());
+        std::vector<float> out(t * p_.num_mel_bins);
+        if (log_energy) log_energy->assign(t, 0.0f);
+        check(ss_kaldi_fbank(h_.get(), x.data(), 1, x.size(), x.size(), out.data(), log_energy ? log_energy->data() : nullptr));
+        return out;
+    }
+    // one clip -> [T x num_ceps] cepstra
+    std::vector<float> mfcc(const std::vector<float> &x) const
+    {
+        std::vector<float> out(num_frames(x.size()) * p_.num_ceps);
+        check(ss_kaldi_mfcc(h_.get(), x.data(), 1, x.size(), x.size(), out.data()));
+        return out;
+    }
+    // clips packed end to end, clip b = x[sample_offsets[b] .. sample_offsets[b+1]) -> the [sum T_b x cols] rows; frame_offsets
+    // receives the row offsets
+    std::vector<float> fbank_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, std::vector<int64_t> &frame_offsets,
+                                    std::vector<float> *log_energy = nullptr) const
+    {
+        const size_t rows = packed_rows(x, sample_offsets, frame_offsets);
+        std::vector<float> out(rows * p_.num_mel_bins);
+        if (log_energy) log_energy->assign(rows, 0.0f);
+        check(ss_kaldi_fbank_packed(h_.get(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), out.data(),
+                                    log_energy ? log_energy->data() : nullptr));
+        return out;
+    }
+    std::vector<float> mfcc_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, std::vector<int64_t> &frame_offsets) const
+    {
+        std::vector<float> out(packed_rows(x, sample_offsets, frame_offsets) * p_.num_ceps);
+        check(ss_kaldi_mfcc_packed(h_.get(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), out.data()));
+        return out;
+    }
+
+private:
+    size_t packed_rows(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, std::vector<int64_t> &frame_offsets) const
+    {
+        if (sample_offsets.empty() || sample_offsets.back() < 0 || static_cast<size_t>(sample_offsets.back()) > x.size())
+            throw Error(SS_ERR_ARG, "kaldi packed call: shape mismatch");
+        frame_offsets.assign(sample_offsets.size(), 0);
+        check(ss_kaldi_packed_frame_offsets(&p_, sample_offsets.size() - 1, sample_offsets.data(), frame_offsets.data()));
+        return static_cast<size_t>(frame_offsets.back());
+    }
+    ss_kaldi_params p_;
+    std::shared_ptr<ss_kaldi_config> h_;
+};
+
 // processing.rs:222-254
 inline std::vector<float> derivative_extraction(const std::vector<float> &feat, size_t rows, size_t cols, size_t delta_windows)
 {

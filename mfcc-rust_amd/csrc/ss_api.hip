@@ -3175,3 +3175,290 @@ int ss_time_mel_spectrogram_device(const ss_config *cfg, const float *d_x, size_
 }
 
 }  // extern "C"
+
+// ---- Kaldi-compatible fbank / MFCC front end (ss_kaldi_*; kernel: ss_kaldi512.hip) ------------------------------------------
+// The handle: the validated parameters, the kernel's table block on the device it was created on, and a pinned device error word
+// of its own (the packed calls' containment, as ss_config's).  Immutable after creation.
+struct ss_kaldi_config {
+    ss_kaldi_params params{};
+    ss::KaldiTables tabs;
+    int device = -1;
+    int num_cus = 256;
+    float *d_tab = nullptr;
+    unsigned *h_err = nullptr, *d_err = nullptr;
+};
+
+namespace {
+
+int kaldi_pending_error(const ss_kaldi_config *cfg)
+{
+    if (!cfg->h_err || __atomic_load_n(cfg->h_err, __ATOMIC_ACQUIRE) == 0) return SS_OK;
+    const unsigned w = __atomic_exchange_n(cfg->h_err, 0u, __ATOMIC_ACQ_REL);
+    if (w == 0) return SS_OK;
+    return ss::fail(SS_ERR_DEVICE, "a kernel launched on this handle skipped a packed clip whose offsets are inconsistent (error word " +
+                                       std::to_string(w) + "): the rows of that clip were left untouched");
+}
+
+int kaldi_ready(const ss_kaldi_config *cfg)
+{
+    int dev = -1;
+    SS_HIP(hipGetDevice(&dev));
+    if (dev != cfg->device) return ss::fail(SS_ERR_ARG, "the handle was created on a different HIP device than the current one");
+    return kaldi_pending_error(cfg);
+}
+
+// the handle's part of the kernel's argument block
+ss::KaldiArgs kaldi_args(const ss_kaldi_config *cfg, bool mfcc, const float *x, float *out, float *log_energy)
+{
+    const ss_kaldi_params &p = cfg->params;
+    ss::KaldiArgs a{};
+    a.x = x;
+    a.flen = cfg->tabs.s.flen;
+    a.step = cfg->tabs.s.shift;
+    a.tab = cfg->d_tab;
+    a.mel_wpitch = cfg->tabs.wpitch;
+    std::copy(cfg->tabs.q4, cfg->tabs.q4 + 5, a.mel_q4);
+    a.n_filters = p.num_mel_bins;
+    a.n_ceps = p.num_ceps;
+    a.input_scale = p.input_scale;
+    a.preemph = p.preemph_coef;
+    a.flen_f = static_cast<float>(cfg->tabs.s.flen);
+    a.log_floor = p.energy_floor > 0.0f ? std::log(p.energy_floor) : -INFINITY;
+    a.remove_dc = p.remove_dc_offset != 0;
+    a.raw_energy = p.raw_energy != 0;
+    a.use_energy = p.use_energy != 0;
+    a.out_mfcc = mfcc;
+    a.use_power = p.use_power != 0;
+    a.out = out;
+    a.out_energy = mfcc ? nullptr : log_energy;
+    return a;
+}
+
+int kaldi_launched(hipError_t e, const ss::LaunchInfo &info)
+{
+    if (e != hipSuccess) return hip_fail(e, "launch_kaldi_c256");
+    g_last_kernel = info.kernel_name;
+    return SS_OK;
+}
+
+int kaldi_check_call(const ss_kaldi_config *cfg, bool mfcc)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null handle");
+    if (mfcc && cfg->params.num_ceps == 0) return ss::fail(SS_ERR_ARG, "the handle was created with num_ceps = 0: it serves the fbank calls only");
+    return SS_OK;
+}
+
+// equal-length clips; T: the rows per clip
+int kaldi_check_dense(const ss_kaldi_config *cfg, bool mfcc, const float *x, size_t batch, size_t n_samples, size_t ld, const float *out, size_t &T)
+{
+    if (int rc = kaldi_check_call(cfg, mfcc)) return rc;
+    if (!x || !out) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (ld < n_samples) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
+    if (n_samples >= (1ull << 31) || batch >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "batch and n_samples must be below 2^31");
+    T = ss::kaldi_frames(cfg->tabs.s, n_samples);
+    if (T == 0) return ss::fail(SS_ERR_SHORT_SIGNAL, "signal shorter than one frame");
+    if (static_cast<unsigned long long>(batch) * T + 8 >= 0xffffffffull) return ss::fail(SS_ERR_ARG, "batch * frames must be below 2^32 - 8");
+    return SS_OK;
+}
+
+int kaldi_dense_device(const ss_kaldi_config *cfg, bool mfcc, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out,
+                       float *d_log_energy, hipStream_t stream)
+{
+    if (batch == 0) return cfg ? SS_OK : ss::fail(SS_ERR_ARG, "null handle");
+    size_t T = 0;
+    if (int rc = kaldi_check_dense(cfg, mfcc, d_x, batch, n_samples, ld, d_out, T)) return rc;
+    if (int rc = kaldi_ready(cfg)) return rc;
+    ss::KaldiArgs a = kaldi_args(cfg, mfcc, d_x, d_out, d_log_energy);
+    a.ld = ld;
+    a.n_samples = static_cast<uint32_t>(n_samples);
+    a.batch = static_cast<uint32_t>(batch);
+    a.n_frames = static_cast<uint32_t>(T);
+    ss::LaunchInfo info{};
+    return kaldi_launched(ss::launch_kaldi_c256(a, stream, cfg->num_cus, &info), info);
+}
+
+int kaldi_dense_host(const ss_kaldi_config *cfg, bool mfcc, const float *x, size_t batch, size_t n_samples, size_t ld, float *out, float *log_energy)
+{
+    if (batch == 0) return cfg ? SS_OK : ss::fail(SS_ERR_ARG, "null handle");
+    size_t T = 0;
+    int rc = kaldi_check_dense(cfg, mfcc, x, batch, n_samples, ld, out, T);
+    if (rc) return rc;
+    if (!ss::have_device()) return ss::no_device("hot path");
+    const size_t cols = mfcc ? cfg->params.num_ceps : cfg->params.num_mel_bins, rows = batch * T;
+    DeviceBuf d_in, d_out, d_en;
+    hipError_t e = d_in.hip_alloc(batch * n_samples * sizeof(float));
+    if (e == hipSuccess) e = d_out.hip_alloc(rows * cols * sizeof(float));
+    if (e == hipSuccess && log_energy) e = d_en.hip_alloc(rows * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy2D(d_in.p, n_samples * sizeof(float), x, ld * sizeof(float), n_samples * sizeof(float), batch, hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? kaldi_dense_device(cfg, mfcc, d_in.as<const float>(), batch, n_samples, n_samples, d_out.as<float>(),
+                                              log_energy ? d_en.as<float>() : nullptr, nullptr)
+                         : hip_fail(e, "host staging");
+    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_kaldi: device error");
+    if (rc == SS_OK) {
+        e = hipMemcpy(out, d_out.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && log_energy) e = hipMemcpy(log_energy, d_en.p, rows * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
+    }
+    return rc;
+}
+
+int kaldi_packed_device(const ss_kaldi_config *cfg, bool mfcc, const float *d_x, size_t n_clips, const int64_t *d_so, const int64_t *d_fo,
+                        size_t total_frames, float *d_out, float *d_log_energy, hipStream_t stream)
+{
+    if (int rc = kaldi_check_call(cfg, mfcc)) return rc;
+    if (n_clips == 0) return SS_OK;
+    if (!d_x || !d_so || !d_fo || !d_out) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_clips >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "n_clips must be below 2^31");
+    if (static_cast<unsigned long long>(total_frames) + 8 >= 0xffffffffull) return ss::fail(SS_ERR_ARG, "total_frames must be below 2^32 - 8");
+    if (int rc = kaldi_ready(cfg)) return rc;
+    if (total_frames == 0) return SS_OK;  // no clip can own a row
+    const ss::KaldiArgs a = kaldi_args(cfg, mfcc, d_x, d_out, d_log_energy);
+    ss::KaldiVarlenArgs v{};
+    v.so = reinterpret_cast<const long long *>(d_so);
+    v.fo = reinterpret_cast<const long long *>(d_fo);
+    v.total_frames = total_frames;
+    v.n_clips = static_cast<uint32_t>(n_clips);
+    v.err = cfg->d_err;
+    ss::LaunchInfo info{};
+    return kaldi_launched(ss::launch_kaldi_c256_varlen(a, v, stream, cfg->num_cus, &info), info);
+}
+
+int kaldi_packed_host(const ss_kaldi_config *cfg, bool mfcc, const float *x, size_t n_clips, const int64_t *so, float *out, float *log_energy)
+{
+    if (int rc = kaldi_check_call(cfg, mfcc)) return rc;
+    if (n_clips == 0) return SS_OK;
+    if (!x || !so || !out) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_clips >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "n_clips must be below 2^31");
+    std::vector<int64_t> fo(n_clips + 1);
+    int rc = ss_kaldi_packed_frame_offsets(&cfg->params, n_clips, so, fo.data());
+    if (rc) return rc;
+    const size_t total_in = static_cast<size_t>(so[n_clips]), rows = static_cast<size_t>(fo[n_clips]);
+    const size_t cols = mfcc ? cfg->params.num_ceps : cfg->params.num_mel_bins, tbytes = (n_clips + 1) * sizeof(int64_t);
+    if (!ss::have_device()) return ss::no_device("hot path");
+    DeviceBuf d_in, d_out, d_en, d_so, d_fo;
+    hipError_t e = d_in.hip_alloc(total_in * sizeof(float));
+    if (e == hipSuccess) e = d_out.hip_alloc(rows * cols * sizeof(float));
+    if (e == hipSuccess && log_energy) e = d_en.hip_alloc(rows * sizeof(float));
+    if (e == hipSuccess) e = d_so.hip_alloc(tbytes);
+    if (e == hipSuccess) e = d_fo.hip_alloc(tbytes);
+    if (e == hipSuccess) e = hipMemcpy(d_in.p, x, total_in * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_so.p, so, tbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_fo.p, fo.data(), tbytes, hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? kaldi_packed_device(cfg, mfcc, d_in.as<const float>(), n_clips, d_so.as<const int64_t>(), d_fo.as<const int64_t>(), rows,
+                                               d_out.as<float>(), log_energy ? d_en.as<float>() : nullptr, nullptr)
+                         : hip_fail(e, "host staging");
+    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_kaldi: device error");
+    if (rc == SS_OK) rc = kaldi_pending_error(cfg);
+    if (rc == SS_OK) {
+        e = hipMemcpy(out, d_out.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && log_energy) e = hipMemcpy(log_energy, d_en.p, rows * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ss_kaldi_config_create(const ss_kaldi_params *p, ss_kaldi_config **out)
+{
+    if (!p || !out) return ss::fail(SS_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (int rc = ss::kaldi_validate(*p, nullptr)) return rc;
+    std::unique_ptr<ss_kaldi_config> cfg(new ss_kaldi_config());
+    cfg->params = *p;
+    ss::build_kaldi512(*p, cfg->tabs);
+    if (!cfg->tabs.ok) return ss::fail(SS_ERR_UNSUPPORTED, "the mel bank does not fit the kernel's five filter slots per lane");
+    if (!ss::have_device()) return ss::no_device("hot path");
+    SS_HIP(hipGetDevice(&cfg->device));
+    hipDeviceProp_t prop;
+    SS_HIP(hipGetDeviceProperties(&prop, cfg->device));
+    cfg->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (int rc = upload(&cfg->d_tab, cfg->tabs.tab.data(), cfg->tabs.tab.size() * sizeof(float))) {
+        ss_kaldi_config_destroy(cfg.release());
+        return rc;
+    }
+    void *hp = nullptr, *dp = nullptr;
+    hipError_t e = hipHostMalloc(&hp, 64, hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&dp, hp, 0);
+    if (e != hipSuccess) {
+        if (hp) (void)hipHostFree(hp);
+        ss_kaldi_config_destroy(cfg.release());
+        return hip_fail(e, "hipHostMalloc (device error word)");
+    }
+    std::memset(hp, 0, 64);
+    cfg->h_err = static_cast<unsigned *>(hp);
+    cfg->d_err = static_cast<unsigned *>(dp);
+    *out = cfg.release();
+    return SS_OK;
+}
+
+void ss_kaldi_config_destroy(ss_kaldi_config *cfg)
+{
+    if (!cfg) return;
+    if (cfg->d_tab) (void)hipFree(cfg->d_tab);
+    if (cfg->h_err) (void)hipHostFree(cfg->h_err);
+    delete cfg;
+}
+
+int ss_kaldi_config_params(const ss_kaldi_config *cfg, ss_kaldi_params *out)
+{
+    if (!cfg || !out) return ss::fail(SS_ERR_ARG, "null argument");
+    *out = cfg->params;
+    return SS_OK;
+}
+
+int ss_kaldi_config_device_status(const ss_kaldi_config *cfg)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null handle");
+    return kaldi_pending_error(cfg);
+}
+
+int ss_kaldi_fbank_device(const ss_kaldi_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out,
+                          float *d_log_energy, void *stream)
+{
+    return kaldi_dense_device(cfg, false, d_x, batch, n_samples, ld, d_out, d_log_energy, static_cast<hipStream_t>(stream));
+}
+
+int ss_kaldi_fbank(const ss_kaldi_config *cfg, const float *x, size_t batch, size_t n_samples, size_t ld, float *out, float *log_energy)
+{
+    return kaldi_dense_host(cfg, false, x, batch, n_samples, ld, out, log_energy);
+}
+
+int ss_kaldi_mfcc_device(const ss_kaldi_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out, void *stream)
+{
+    return kaldi_dense_device(cfg, true, d_x, batch, n_samples, ld, d_out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int ss_kaldi_mfcc(const ss_kaldi_config *cfg, const float *x, size_t batch, size_t n_samples, size_t ld, float *out)
+{
+    return kaldi_dense_host(cfg, true, x, batch, n_samples, ld, out, nullptr);
+}
+
+int ss_kaldi_fbank_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                 const int64_t *d_frame_offsets, size_t total_frames, float *d_out, float *d_log_energy, void *stream)
+{
+    return kaldi_packed_device(cfg, false, d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, d_log_energy,
+                               static_cast<hipStream_t>(stream));
+}
+
+int ss_kaldi_fbank_packed(const ss_kaldi_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out,
+                          float *log_energy)
+{
+    return kaldi_packed_host(cfg, false, x, n_clips, sample_offsets, out, log_energy);
+}
+
+int ss_kaldi_mfcc_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream)
+{
+    return kaldi_packed_device(cfg, true, d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, nullptr,
+                               static_cast<hipStream_t>(stream));
+}
+
+int ss_kaldi_mfcc_packed(const ss_kaldi_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out)
+{
+    return kaldi_packed_host(cfg, true, x, n_clips, sample_offsets, out, nullptr);
+}
+
+}  // extern "C"

@@ -773,4 +773,37 @@ hipError_t launch_mfcc_c2048(const Mfcc4096Args &a, hipStream_t stream, int num_
 hipError_t launch_mfcc_c2048_multi(const Mfcc4096Args &a, int n_batches, const float *const *d_x, float *const *d_out, const size_t *clips,
                                    hipStream_t stream, int num_cus, LaunchInfo *info);
 
+// Arguments of the Kaldi-compatible 512-point fbank / MFCC kernel (ss_kaldi512.hip; the specification is the ss_kaldi_* comment of
+// include/speechsauce_amd.h).
+struct KaldiArgs {
+    const float *x;
+    unsigned long long ld;
+    uint32_t n_samples, batch, flen, step, n_frames;
+    const float *tab;    // table block (ss::KaldiTables: mfcc512w_layout + the frame window [512]), copied verbatim into LDS
+    int32_t mel_wpitch;  // floats per lane weight row
+    int32_t mel_q4[5];   // taps / 4 per slot
+    uint32_t n_filters, n_ceps;
+    float input_scale;   // step 1 (1: skipped)
+    float preemph;       // step 4 (0: skipped)
+    float flen_f;        // the divisor of the frame mean
+    float log_floor;     // ln(energy_floor), -inf where energy_floor == 0
+    int32_t remove_dc, raw_energy, use_energy;
+    int32_t out_mfcc;    // 0: fbank rows [frames x n_filters] (+ out_energy where non-null); 1: cepstra [frames x n_ceps]
+    int32_t use_power;
+    float *out;
+    float *out_energy;   // fbank builds: log energy [frames], or null
+    uint32_t nf_magic, nf_shift;  // set by the launcher: frame -> (clip, t) by multiply-high
+};
+// Packed clips of the Kaldi kernel: VarlenArgs' layout with Kaldi's frame count (1 + (L - flen) / shift in integers).
+struct KaldiVarlenArgs {
+    const long long *so;  // [n_clips + 1] sample offsets
+    const long long *fo;  // [n_clips + 1] frame (output row) offsets
+    unsigned long long total_frames;
+    uint32_t n_clips;
+    unsigned *err;        // the handle's device error word (set to kVarlenError on a bad clip)
+};
+hipError_t launch_kaldi_c256(const KaldiArgs &a, hipStream_t stream, int num_cus, LaunchInfo *info);
+// a: x / out = the packed blocks; batch / n_samples / n_frames / ld are unused
+hipError_t launch_kaldi_c256_varlen(const KaldiArgs &a, const KaldiVarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
+
 }  // namespace ss

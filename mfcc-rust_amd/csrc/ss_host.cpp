@@ -991,6 +991,128 @@ static void build_4096(const HostTables &t, Mfcc4096Tables &f, bool mel)
 }
 
 void build_mfcc4096(const HostTables &t, Mfcc4096Tables &f) { build_4096(t, f, false); }
+// ---- Kaldi-compatible front end: the rules, sizes and tables of include/speechsauce_amd.h ("ss_kaldi_*"), all in f64 ----
+
+static uint32_t kaldi_pow2_at_least(uint32_t n)
+{
+    uint32_t p = 1;
+    while (p < n) p *= 2;
+    return p;
+}
+
+int kaldi_validate(const ss_kaldi_params &p, KaldiSizes *out)
+{
+    if (p.struct_size != sizeof(ss_kaldi_params)) return fail(SS_ERR_ARG, "ss_kaldi_params.struct_size mismatch (ABI)");
+    if (p.sample_rate == 0) return fail(SS_ERR_BAD_CONFIG, "sample_rate must be > 0");
+    const double sr = static_cast<double>(p.sample_rate);
+    const double fl = sr * 0.001 * static_cast<double>(p.frame_length_ms), sh = sr * 0.001 * static_cast<double>(p.frame_shift_ms);
+    if (!(fl >= 2.0) || fl > 16777216.0) return fail(SS_ERR_BAD_CONFIG, "frame_length_ms gives fewer than 2 samples (or an absurd count)");
+    if (!(sh >= 1.0) || sh > 16777216.0) return fail(SS_ERR_BAD_CONFIG, "frame_shift_ms gives less than 1 sample (or an absurd count)");
+    KaldiSizes s;
+    s.flen = static_cast<uint32_t>(fl);
+    s.shift = static_cast<uint32_t>(sh);
+    s.padded = kaldi_pow2_at_least(s.flen);
+    if (p.num_mel_bins < 3) return fail(SS_ERR_BAD_CONFIG, "num_mel_bins must be at least 3");
+    if (!(p.low_freq >= 0.0f)) return fail(SS_ERR_BAD_CONFIG, "low_freq cannot be less than zero");
+    const double nyq = 0.5 * sr, high = p.high_freq > 0.0f ? static_cast<double>(p.high_freq) : nyq + static_cast<double>(p.high_freq);
+    if (!(high > static_cast<double>(p.low_freq)) || !(high <= nyq))
+        return fail(SS_ERR_BAD_CONFIG, "high_freq must lie above low_freq and at or below half the sample rate");
+    if (p.num_ceps > p.num_mel_bins) return fail(SS_ERR_BAD_CONFIG, "num_ceps must be at most num_mel_bins");
+    if (!std::isfinite(p.input_scale) || !(p.input_scale > 0.0f)) return fail(SS_ERR_BAD_CONFIG, "input_scale must be finite and positive");
+    if (!(p.energy_floor >= 0.0f)) return fail(SS_ERR_BAD_CONFIG, "energy_floor cannot be negative");
+    if (p.window_type < SS_KALDI_WINDOW_POVEY || p.window_type > SS_KALDI_WINDOW_BLACKMAN) return fail(SS_ERR_BAD_CONFIG, "window_type switch");
+    if (s.padded != 512)
+        return fail(SS_ERR_UNSUPPORTED, "frames of " + std::to_string(s.flen) + " samples pad to " + std::to_string(s.padded) +
+                                            " points: only 512 (256 < frame length <= 512) is served");
+    if (p.num_mel_bins > 80) return fail(SS_ERR_UNSUPPORTED, "more than 80 mel bins");
+    if (p.num_ceps > 32) return fail(SS_ERR_UNSUPPORTED, "more than 32 cepstra");
+    if (p.dither != 0.0f) return fail(SS_ERR_UNSUPPORTED, "dither is not offered: add it to the samples ahead of the call");
+    if (out) *out = s;
+    return SS_OK;
+}
+
+size_t kaldi_frames(const KaldiSizes &s, size_t n) { return n < s.flen ? 0 : 1 + (n - s.flen) / s.shift; }
+
+void kaldi_window(const ss_kaldi_params &p, const KaldiSizes &s, float *w)
+{
+    const double PI = 3.14159265358979323846, b = static_cast<double>(p.blackman_coeff);
+    for (uint32_t i = 0; i < s.flen; ++i) {
+        const double a = 2.0 * PI * i / static_cast<double>(s.flen - 1);
+        double v = 1.0;
+        switch (p.window_type) {
+        case SS_KALDI_WINDOW_POVEY: v = std::pow(0.5 - 0.5 * std::cos(a), 0.85); break;
+        case SS_KALDI_WINDOW_HANNING: v = 0.5 - 0.5 * std::cos(a); break;
+        case SS_KALDI_WINDOW_HAMMING: v = 0.54 - 0.46 * std::cos(a); break;
+        case SS_KALDI_WINDOW_BLACKMAN: v = b - 0.5 * std::cos(a) + (0.5 - b) * std::cos(2.0 * a); break;
+        default: break;  // rectangular
+        }
+        w[i] = static_cast<float>(v);
+    }
+}
+
+static double kaldi_mel(double f) { return 1127.0 * std::log(1.0 + f / 700.0); }
+
+void kaldi_mel_bank(const ss_kaldi_params &p, const KaldiSizes &s, float *bank)
+{
+    const size_t M = p.num_mel_bins, F = s.padded / 2;  // bins 0 .. N/2 - 1: the Nyquist bin carries no weight
+    const double sr = static_cast<double>(p.sample_rate);
+    const double high = p.high_freq > 0.0f ? static_cast<double>(p.high_freq) : 0.5 * sr + static_cast<double>(p.high_freq);
+    const double mlow = kaldi_mel(static_cast<double>(p.low_freq)), delta = (kaldi_mel(high) - mlow) / static_cast<double>(M + 1);
+    for (size_t b = 0; b < M; ++b) {
+        const double left = mlow + b * delta, centre = mlow + (b + 1) * delta, right = mlow + (b + 2) * delta;
+        for (size_t k = 0; k < F; ++k) {
+            const double mu = kaldi_mel(static_cast<double>(k) * sr / static_cast<double>(s.padded));
+            double wgt = 0.0;
+            if (mu > left && mu < right) wgt = mu <= centre ? (mu - left) / (centre - left) : (right - mu) / (right - centre);
+            bank[b * F + k] = static_cast<float>(wgt);
+        }
+    }
+}
+
+void kaldi_dct(const ss_kaldi_params &p, float *dct)
+{
+    const size_t M = p.num_mel_bins, Cc = p.num_ceps;
+    const double PI = 3.14159265358979323846, Q = static_cast<double>(p.cepstral_lifter);
+    for (size_t k = 0; k < Cc; ++k) {
+        const double lift = Q == 0.0 ? 1.0 : 1.0 + 0.5 * Q * std::sin(PI * static_cast<double>(k) / Q);
+        for (size_t b = 0; b < M; ++b) {
+            const double d = k == 0 ? std::sqrt(1.0 / M) : std::sqrt(2.0 / M) * std::cos(PI / M * (b + 0.5) * static_cast<double>(k));
+            dct[k * M + b] = static_cast<float>(lift * d);
+        }
+    }
+}
+
+// The kernel's block through the wide-bank builder: the dense bank widened to the 257 bins of a P row (the Nyquist column stays
+// zero), sparsified and dealt to the five slots per lane; the liftered DCT as the cosine rows; the window always appended.
+void build_kaldi512(const ss_kaldi_params &p, KaldiTables &f)
+{
+    f = KaldiTables{};
+    if (kaldi_validate(p, &f.s) != SS_OK) return;
+    const size_t M = p.num_mel_bins, Cc = std::max<uint32_t>(p.num_ceps, 1u), F = 257;
+    HostTables t;
+    t.params.num_filters = static_cast<uint32_t>(M);
+    t.params.num_cepstral = static_cast<uint32_t>(Cc);
+    t.d.n_fft = 512;
+    std::vector<float> dense(M * 256);
+    kaldi_mel_bank(p, f.s, dense.data());
+    t.fb_dense.assign(M * F, 0.0f);
+    for (size_t b = 0; b < M; ++b) std::copy(dense.begin() + b * 256, dense.begin() + (b + 1) * 256, t.fb_dense.begin() + b * F);
+    sparsify(t.fb_dense, M, F, t.bank);
+    ss_kaldi_params pc = p;
+    pc.num_ceps = static_cast<uint32_t>(Cc);  // a handle made for the fbank calls alone (num_ceps = 0) still gets one cosine row
+    t.dct.resize(Cc * M);
+    kaldi_dct(pc, t.dct.data());
+    t.window_mfcc.resize(f.s.flen);
+    kaldi_window(p, f.s, t.window_mfcc.data());
+    Mfcc512wTables w;
+    build_mfcc512w(t, w);
+    if (!w.ok || !w.windowed) return;
+    f.tab = std::move(w.tab);
+    std::copy(w.q4, w.q4 + 5, f.q4);
+    f.wpitch = w.wpitch;
+    f.ok = true;
+}
+
 void build_mel4096(const HostTables &t, Mfcc4096Tables &f)
 {
     build_or_stft_only(t, f, [](const HostTables &tt, Mfcc4096Tables &ff) { build_4096(tt, ff, true); });
@@ -1240,6 +1362,102 @@ int ss_vorbis_window(size_t n, float *w)
 {
     if (!w || n < 2) return ss::fail(SS_ERR_ARG, "bad window request");
     ss::vorbis_window(n, w);
+    return SS_OK;
+}
+
+// ---- Kaldi-compatible front end: host-only calls ----
+
+int ss_kaldi_params_default(ss_kaldi_params *p, uint32_t sample_rate)
+{
+    if (!p) return ss::fail(SS_ERR_ARG, "null params");
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = static_cast<uint32_t>(sizeof(ss_kaldi_params));
+    p->sample_rate = sample_rate;
+    // torchaudio.compliance.kaldi's defaults (Kaldi's binaries: dither 1, energy_floor 0; compute-mfcc-feats: use_energy true)
+    p->frame_length_ms = 25.0f;
+    p->frame_shift_ms = 10.0f;
+    p->num_mel_bins = 23;
+    p->num_ceps = 13;
+    p->low_freq = 20.0f;
+    p->high_freq = 0.0f;
+    p->preemph_coef = 0.97f;
+    p->cepstral_lifter = 22.0f;
+    p->window_type = SS_KALDI_WINDOW_POVEY;
+    p->blackman_coeff = 0.42f;
+    p->remove_dc_offset = 1;
+    p->use_power = 1;
+    p->use_energy = 0;
+    p->raw_energy = 1;
+    p->energy_floor = 1.0f;
+    p->input_scale = 1.0f;
+    p->dither = 0.0f;
+    return SS_OK;
+}
+
+int ss_kaldi_params_validate(const ss_kaldi_params *p)
+{
+    if (!p) return ss::fail(SS_ERR_ARG, "null params");
+    return ss::kaldi_validate(*p, nullptr);
+}
+
+int ss_kaldi_sizes(const ss_kaldi_params *p, size_t *frame_len, size_t *frame_shift, size_t *padded)
+{
+    if (!p || !frame_len || !frame_shift || !padded) return ss::fail(SS_ERR_ARG, "null argument");
+    ss::KaldiSizes s;
+    if (int rc = ss::kaldi_validate(*p, &s)) return rc;
+    *frame_len = s.flen;
+    *frame_shift = s.shift;
+    *padded = s.padded;
+    return SS_OK;
+}
+
+int ss_kaldi_num_frames(const ss_kaldi_params *p, size_t n_samples, size_t *n_frames)
+{
+    if (!p || !n_frames) return ss::fail(SS_ERR_ARG, "null argument");
+    ss::KaldiSizes s;
+    if (int rc = ss::kaldi_validate(*p, &s)) return rc;
+    const size_t t = ss::kaldi_frames(s, n_samples);
+    if (t == 0) return ss::fail(SS_ERR_SHORT_SIGNAL, "signal shorter than one frame");
+    *n_frames = t;
+    return SS_OK;
+}
+
+int ss_kaldi_packed_frame_offsets(const ss_kaldi_params *p, size_t n_clips, const int64_t *sample_offsets, int64_t *frame_offsets)
+{
+    if (!p || !sample_offsets || !frame_offsets) return ss::fail(SS_ERR_ARG, "null argument");
+    ss::KaldiSizes s;
+    if (int rc = ss::kaldi_validate(*p, &s)) return rc;
+    return walk_offsets(n_clips, sample_offsets, frame_offsets, "clip", [&](size_t b, int64_t len, int64_t &r) -> int {
+        r = static_cast<int64_t>(ss::kaldi_frames(s, static_cast<size_t>(len)));
+        if (r == 0)
+            return ss::fail(SS_ERR_SHORT_SIGNAL, "clip " + std::to_string(b) + " (" + std::to_string(len) + " samples): signal shorter than one frame");
+        return SS_OK;
+    });
+}
+
+int ss_kaldi_window(const ss_kaldi_params *p, float *w)
+{
+    if (!p || !w) return ss::fail(SS_ERR_ARG, "null argument");
+    ss::KaldiSizes s;
+    if (int rc = ss::kaldi_validate(*p, &s)) return rc;
+    ss::kaldi_window(*p, s, w);
+    return SS_OK;
+}
+
+int ss_kaldi_mel_bank(const ss_kaldi_params *p, float *bank)
+{
+    if (!p || !bank) return ss::fail(SS_ERR_ARG, "null argument");
+    ss::KaldiSizes s;
+    if (int rc = ss::kaldi_validate(*p, &s)) return rc;
+    ss::kaldi_mel_bank(*p, s, bank);
+    return SS_OK;
+}
+
+int ss_kaldi_dct(const ss_kaldi_params *p, float *dct)
+{
+    if (!p || !dct) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::kaldi_validate(*p, nullptr)) return rc;
+    ss::kaldi_dct(*p, dct);
     return SS_OK;
 }
 

@@ -248,4 +248,30 @@ struct Mfcc4096Tables {
 void build_mfcc4096(const HostTables &t, Mfcc4096Tables &f);
 void build_mel4096(const HostTables &t, Mfcc4096Tables &f);  // the mel-spectrogram kernel's block: no cosines, Vorbis window appended
 
+// ---- Kaldi-compatible front end (ss_kaldi_* in include/speechsauce_amd.h; kernel: ss_kaldi512.hip) ----
+struct KaldiSizes {
+    uint32_t flen = 0, shift = 0, padded = 0;  // samples per frame, per hop, and the power of two the frame is padded to
+};
+// the parameter rules of the header; `s` (may be null) gets the sizes.  rc: SS_OK, SS_ERR_ARG (struct_size), SS_ERR_BAD_CONFIG,
+// SS_ERR_UNSUPPORTED
+int kaldi_validate(const ss_kaldi_params &p, KaldiSizes *s);
+// T = 0 if n < flen, else 1 + (n - flen) / shift (snip_edges = true)
+size_t kaldi_frames(const KaldiSizes &s, size_t n);
+// the three tables of the specification, formed in f64 and rounded once (p validated by the caller)
+void kaldi_window(const ss_kaldi_params &p, const KaldiSizes &s, float *w);      // [flen]
+void kaldi_mel_bank(const ss_kaldi_params &p, const KaldiSizes &s, float *bank); // [num_mel_bins x padded / 2] dense
+void kaldi_dct(const ss_kaldi_params &p, float *dct);                            // [num_ceps x num_mel_bins], lifter folded in
+
+// Table block of ss_kaldi_c256: the layout of the wide-bank 512-point kernel (mfcc512w_layout: twiddles, cosine rows = the
+// liftered DCT in (slot, lane) order, five host-sorted filter slots per lane) with the frame window [512] (zero beyond flen,
+// rectangular included) always behind the mel rows.
+struct KaldiTables {
+    bool ok = false;
+    KaldiSizes s{};
+    std::vector<float> tab;
+    int32_t q4[5] = {0, 0, 0, 0, 0};
+    int32_t wpitch = 0;
+};
+void build_kaldi512(const ss_kaldi_params &p, KaldiTables &f);
+
 }  // namespace ss

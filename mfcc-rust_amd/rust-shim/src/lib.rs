@@ -193,6 +193,16 @@ extern "C" {
                                  pool_streams: usize, pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_resample_stream_flush(rs: *const c_void, n_active: usize, slots: *const i32, pool_streams: usize, pool: *mut f32,
                                 out: *mut f32) -> c_int;
+    fn ss_kaldi_params_default(p: *mut KaldiParams, sample_rate: u32) -> c_int;
+    fn ss_kaldi_num_frames(p: *const KaldiParams, n_samples: usize, n_frames: *mut usize) -> c_int;
+    fn ss_kaldi_packed_frame_offsets(p: *const KaldiParams, n_clips: usize, sample_offsets: *const i64, frame_offsets: *mut i64) -> c_int;
+    fn ss_kaldi_config_create(p: *const KaldiParams, out: *mut *mut c_void) -> c_int;
+    fn ss_kaldi_config_destroy(cfg: *mut c_void);
+    fn ss_kaldi_fbank(cfg: *const c_void, x: *const f32, batch: usize, n_samples: usize, ld: usize, out: *mut f32, log_energy: *mut f32) -> c_int;
+    fn ss_kaldi_mfcc(cfg: *const c_void, x: *const f32, batch: usize, n_samples: usize, ld: usize, out: *mut f32) -> c_int;
+    fn ss_kaldi_fbank_packed(cfg: *const c_void, x: *const f32, n_clips: usize, sample_offsets: *const i64, out: *mut f32,
+                             log_energy: *mut f32) -> c_int;
+    fn ss_kaldi_mfcc_packed(cfg: *const c_void, x: *const f32, n_clips: usize, sample_offsets: *const i64, out: *mut f32) -> c_int;
     fn ss_derivative_extraction(feat: *const f32, rows: usize, cols: usize, delta_windows: usize, out: *mut f32) -> c_int;
     fn ss_extract_derivative_feature(feat: *const f32, rows: usize, cols: usize, cube: *mut f32) -> c_int;
     fn ss_shard_bounds(n_items: usize, world: c_int, rank: c_int, lo: *mut usize, hi: *mut usize) -> c_int;
@@ -1164,6 +1174,121 @@ impl<A: num_traits::real::Real, I: Dimension> ArrayLog<A, I> for Array<A, I> {
 // ---------------------------------------------------------------------------------------------------------------------------
 // The reference's module paths (speechsauce/src/lib.rs:2-6).  Re-exports only: one implementation, two spellings.
 // ---------------------------------------------------------------------------------------------------------------------------
+
+/// `ss_kaldi_params`: the Kaldi-compatible front end's parameters (field order is ABI; see `ss_kaldi_*` in the C header).
+/// `KaldiParams::new` fills torchaudio's defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct KaldiParams {
+    pub struct_size: u32,
+    pub sample_rate: u32,
+    pub frame_length_ms: f32,
+    pub frame_shift_ms: f32,
+    pub num_mel_bins: u32,
+    pub num_ceps: u32,
+    pub low_freq: f32,
+    pub high_freq: f32,
+    pub preemph_coef: f32,
+    pub cepstral_lifter: f32,
+    pub window_type: i32,
+    pub blackman_coeff: f32,
+    pub remove_dc_offset: i32,
+    pub use_power: i32,
+    pub use_energy: i32,
+    pub raw_energy: i32,
+    pub energy_floor: f32,
+    pub input_scale: f32,
+    pub dither: f32,
+}
+
+impl KaldiParams {
+    pub fn new(sample_rate: u32) -> KaldiParams {
+        let mut p: KaldiParams = unsafe { std::mem::zeroed() };
+        unsafe { ss_kaldi_params_default(&mut p, sample_rate) };
+        p
+    }
+}
+
+/// Kaldi's `compute-fbank-feats` / `compute-mfcc-feats` (as `torchaudio.compliance.kaldi` restates them) for frames that pad to 512
+/// points.  Not in the reference crate.  Owns an `ss_kaldi_config`.
+pub struct KaldiFrontEnd {
+    raw: *mut c_void,
+    params: KaldiParams,
+}
+
+unsafe impl Send for KaldiFrontEnd {}
+unsafe impl Sync for KaldiFrontEnd {}
+
+impl Drop for KaldiFrontEnd {
+    fn drop(&mut self) {
+        unsafe { ss_kaldi_config_destroy(self.raw) }
+    }
+}
+
+impl KaldiFrontEnd {
+    pub fn new(params: KaldiParams) -> Result<KaldiFrontEnd, Error> {
+        let mut raw: *mut c_void = std::ptr::null_mut();
+        check(unsafe { ss_kaldi_config_create(&params, &mut raw) })?;
+        Ok(KaldiFrontEnd { raw, params })
+    }
+
+    pub fn num_frames(&self, n_samples: usize) -> Result<usize, Error> {
+        let mut t = 0usize;
+        check(unsafe { ss_kaldi_num_frames(&self.params, n_samples, &mut t) })?;
+        Ok(t)
+    }
+
+    /// One clip -> (`[T x num_mel_bins]` log-mel rows, `[T]` log energies).
+    pub fn fbank(&self, x: &[f32]) -> Result<(Array2<f32>, Vec<f32>), Error> {
+        let t = self.num_frames(x.len())?;
+        let mut out = Array2::<f32>::zeros((t, self.params.num_mel_bins as usize));
+        let mut en = vec![0f32; t];
+        check(unsafe { ss_kaldi_fbank(self.raw, x.as_ptr(), 1, x.len(), x.len(), out.as_mut_ptr(), en.as_mut_ptr()) })?;
+        Ok((out, en))
+    }
+
+    /// One clip -> `[T x num_ceps]` cepstra.
+    pub fn mfcc(&self, x: &[f32]) -> Result<Array2<f32>, Error> {
+        let t = self.num_frames(x.len())?;
+        let mut out = Array2::<f32>::zeros((t, self.params.num_ceps as usize));
+        check(unsafe { ss_kaldi_mfcc(self.raw, x.as_ptr(), 1, x.len(), x.len(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// Frame offsets of packed clips (`ss_kaldi_packed_frame_offsets`).
+    pub fn packed_frame_offsets(&self, sample_offsets: &[i64]) -> Result<Vec<i64>, Error> {
+        if sample_offsets.is_empty() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must not be empty".to_string() });
+        }
+        let mut fo = vec![0i64; sample_offsets.len()];
+        check(unsafe { ss_kaldi_packed_frame_offsets(&self.params, sample_offsets.len() - 1, sample_offsets.as_ptr(), fo.as_mut_ptr()) })?;
+        Ok(fo)
+    }
+
+    /// Clips packed end to end -> (the `[sum T_b x num_mel_bins]` rows, the `[sum T_b]` log energies, the frame offsets); one launch.
+    pub fn fbank_packed(&self, x: &[f32], sample_offsets: &[i64]) -> Result<(Array2<f32>, Vec<f32>, Vec<i64>), Error> {
+        let fo = self.packed_frame_offsets(sample_offsets)?;
+        if sample_offsets[sample_offsets.len() - 1] as usize > x.len() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets ends past the block".to_string() });
+        }
+        let rows = fo[fo.len() - 1] as usize;
+        let mut out = Array2::<f32>::zeros((rows, self.params.num_mel_bins as usize));
+        let mut en = vec![0f32; rows];
+        check(unsafe { ss_kaldi_fbank_packed(self.raw, x.as_ptr(), fo.len() - 1, sample_offsets.as_ptr(), out.as_mut_ptr(), en.as_mut_ptr()) })?;
+        Ok((out, en, fo))
+    }
+
+    /// Clips packed end to end -> (the `[sum T_b x num_ceps]` cepstra, the frame offsets); one launch.
+    pub fn mfcc_packed(&self, x: &[f32], sample_offsets: &[i64]) -> Result<(Array2<f32>, Vec<i64>), Error> {
+        let fo = self.packed_frame_offsets(sample_offsets)?;
+        if sample_offsets[sample_offsets.len() - 1] as usize > x.len() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets ends past the block".to_string() });
+        }
+        let mut out = Array2::<f32>::zeros((fo[fo.len() - 1] as usize, self.params.num_ceps as usize));
+        check(unsafe { ss_kaldi_mfcc_packed(self.raw, x.as_ptr(), fo.len() - 1, sample_offsets.as_ptr(), out.as_mut_ptr()) })?;
+        Ok((out, fo))
+    }
+}
 
 /// `ss_resample_info`: the sizes of one conversion (see `ss_resample_sizes` in the C header).
 #[repr(C)]

@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import SpeechSauceError, SsParams, SsResampleInfo, make_params  # noqa: F401
+from ._lib import SpeechSauceError, SsKaldiParams, SsParams, SsResampleInfo, make_params  # noqa: F401
 
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
@@ -28,6 +28,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool", "CmvnStreamPool",
            "add_deltas", "add_deltas_packed", "AddDeltasStreamPool",
            "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
+           "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "SpeechConfig", "SpeechSauceError"]
 
 
@@ -2210,3 +2211,264 @@ class ResampleStreamPool(_SidePool):
         if n_active:
             self.periods_seen[sl] = 0
         return out
+
+
+# ---- Kaldi-compatible fbank / MFCC front end (ss_kaldi_* in include/speechsauce_amd.h) ---------------------------
+
+class KaldiConfig:
+    """Owns an ``ss_kaldi_config`` handle: the validated ``ss_kaldi_params``, the kernel's tables on the device that was current at
+    creation and a device error word for the packed calls."""
+
+    def __init__(self, params: SsKaldiParams):
+        self.params = params
+        self._h = C.c_void_p()
+        self._owner = _lib.lib()  # the build that created the handle destroys it
+        _lib.check(self._owner.ss_kaldi_config_create(C.byref(params), C.byref(self._h)))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                self._owner.ss_kaldi_config_destroy(h)
+            except Exception:
+                pass
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    def num_frames(self, n_samples: int) -> int:
+        t = C.c_size_t()
+        _lib.check(_lib.lib().ss_kaldi_num_frames(C.byref(self.params), n_samples, C.byref(t)))
+        return t.value
+
+    def device_status(self) -> None:
+        """Raises SpeechSauceError (SS_ERR_DEVICE) if a packed launch on this handle has skipped an inconsistent clip since the last
+        look.  Meaningful after the stream has been synchronised."""
+        _lib.check(_lib.lib().ss_kaldi_config_device_status(self._h))
+
+
+def _kaldi_params(sample_frequency, frame_length, frame_shift, num_mel_bins, num_ceps, low_freq, high_freq, preemphasis_coefficient,
+                  cepstral_lifter, window_type, blackman_coeff, remove_dc_offset, use_power, use_energy, raw_energy, energy_floor,
+                  input_scale) -> SsKaldiParams:
+    if int(sample_frequency) != sample_frequency or int(sample_frequency) <= 0:
+        raise ValueError(f"sample_frequency must be a positive integer number of Hz, got {sample_frequency!r}")
+    if window_type not in _lib.KALDI_WINDOW:
+        raise ValueError(f"window_type must be one of {sorted(_lib.KALDI_WINDOW)}, got {window_type!r}")
+    p = SsKaldiParams()
+    _lib.check(_lib.lib().ss_kaldi_params_default(C.byref(p), int(sample_frequency)))
+    p.frame_length_ms, p.frame_shift_ms = float(frame_length), float(frame_shift)
+    p.num_mel_bins, p.num_ceps = int(num_mel_bins), int(num_ceps)
+    p.low_freq, p.high_freq = float(low_freq), float(high_freq)
+    p.preemph_coef, p.cepstral_lifter = float(preemphasis_coefficient), float(cepstral_lifter)
+    p.window_type, p.blackman_coeff = _lib.KALDI_WINDOW[window_type], float(blackman_coeff)
+    p.remove_dc_offset, p.use_power, p.use_energy, p.raw_energy = int(bool(remove_dc_offset)), int(bool(use_power)), int(bool(use_energy)), int(bool(raw_energy))
+    p.energy_floor, p.input_scale = float(energy_floor), float(input_scale)
+    return p
+
+
+@lru_cache(maxsize=32)
+def _get_kaldi_config(key: tuple, device: int = -1) -> KaldiConfig:
+    """Memoised handle factory, keyed like ``_get_resampler``: the parameters and the device the tables live on."""
+    return KaldiConfig(_kaldi_params(*key))
+
+
+_lib._on_switch.append(_get_kaldi_config.cache_clear)  # a handle belongs to the library that created it
+
+# what torchaudio.compliance.kaldi takes and this front end does not serve; the value that changes nothing is accepted
+_KALDI_NEUTRAL = {"dither": 0.0, "snip_edges": True, "htk_compat": False, "subtract_mean": False, "vtln_warp": 1.0}
+
+
+def _kaldi_reject(what, unsupported):
+    for k, v in unsupported.items():
+        if k == "channel":
+            raise ValueError(f"{what}: channel is not offered: pass the channel's samples (a 2-D input is a batch of clips)")
+        if k in _KALDI_NEUTRAL or k.startswith("vtln_"):
+            if k in _KALDI_NEUTRAL and v == _KALDI_NEUTRAL[k]:
+                continue
+            raise ValueError(f"{what}: {k}={v!r} is not offered by this front end (dither, snip_edges=False, htk_compat, subtract_mean "
+                             "and VTLN are out of scope: see ss_kaldi_* in include/speechsauce_amd.h)")
+        raise TypeError(f"{what}() got an unexpected keyword argument {k!r}")
+
+
+def _kaldi_cfg(what, sig, mfcc, sample_frequency, frame_length, frame_shift, num_mel_bins, num_ceps, low_freq, high_freq,
+               preemphasis_coefficient, cepstral_lifter, window_type, blackman_coeff, remove_dc_offset, use_power, use_energy, raw_energy,
+               energy_floor, input_scale, unsupported) -> KaldiConfig:
+    _kaldi_reject(what, unsupported)
+    # the fbank calls put the energy column in place themselves: their handles are made with use_energy = 0 and no cepstra
+    key = (sample_frequency, float(frame_length), float(frame_shift), int(num_mel_bins), int(num_ceps) if mfcc else 0, float(low_freq),
+           float(high_freq), float(preemphasis_coefficient), float(cepstral_lifter) if mfcc else 0.0, window_type, float(blackman_coeff),
+           bool(remove_dc_offset), bool(use_power), bool(use_energy) if mfcc else False, bool(raw_energy), float(energy_floor), float(input_scale))
+    return _get_kaldi_config(key, _device_key(sig))
+
+
+def _kaldi_dense(sig, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
+    """sig [L] or [B, L] -> [T, cols] or [B, T, cols]; fbank with_energy: the log energy as column 0 (torchaudio's layout)"""
+    lib = _lib.lib()
+    one = len(sig.shape) == 1
+    batch, L = (1, int(sig.shape[0])) if one else (int(sig.shape[0]), int(sig.shape[1]))
+    T = cfg.num_frames(L)
+    cols = cfg.params.num_ceps if mfcc else cfg.params.num_mel_bins
+    if _is_torch(sig):
+        import torch
+
+        v = sig.reshape(1, L) if one else sig
+        if v.stride(1) != 1:
+            v = v.contiguous()
+        ld = int(v.stride(0)) if batch > 1 else L
+        if ld < L:
+            v, ld = v.contiguous(), L
+        out = torch.empty((batch, T, cols), dtype=torch.float32, device=v.device)
+        en = torch.empty((batch, T), dtype=torch.float32, device=v.device) if with_energy else None
+        if batch:
+            with torch.cuda.device(v.device):
+                if mfcc:
+                    _lib.check(lib.ss_kaldi_mfcc_device(cfg.handle, v.data_ptr(), batch, L, ld, out.data_ptr(), _stream_ptr()))
+                else:
+                    _lib.check(lib.ss_kaldi_fbank_device(cfg.handle, v.data_ptr(), batch, L, ld, out.data_ptr(), en.data_ptr() if with_energy else None,
+                                                         _stream_ptr()))
+                v.record_stream(torch.cuda.current_stream())
+        if with_energy:
+            out = torch.cat([en.unsqueeze(-1), out], dim=-1)
+        return out[0] if one else out
+    v = np.ascontiguousarray(sig).reshape(batch, L)
+    out = np.empty((batch, T, cols), dtype=np.float32)
+    en = np.empty((batch, T), dtype=np.float32) if with_energy else None
+    if batch:
+        if mfcc:
+            _lib.check(lib.ss_kaldi_mfcc(cfg.handle, v.ctypes.data, batch, L, L, out.ctypes.data))
+        else:
+            _lib.check(lib.ss_kaldi_fbank(cfg.handle, v.ctypes.data, batch, L, L, out.ctypes.data, en.ctypes.data if with_energy else None))
+    if with_energy:
+        out = np.concatenate([en[..., None], out], axis=-1)
+    return out[0] if one else out
+
+
+def _kaldi_packed(sig, so, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
+    """packed samples [N], sample offsets so (host int64, used as they stand) -> (rows [sum T_b, cols], frame offsets (host int64))"""
+    lib = _lib.lib()
+    n = so.size - 1
+    fo = np.empty_like(so)
+    _lib.check(lib.ss_kaldi_packed_frame_offsets(C.byref(cfg.params), n, so.ctypes.data, fo.ctypes.data))
+    rows = int(fo[-1])
+    cols = cfg.params.num_ceps if mfcc else cfg.params.num_mel_bins
+    if _is_torch(sig):
+        import torch
+
+        x = sig.contiguous()
+        out = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
+        en = torch.empty((rows,), dtype=torch.float32, device=x.device) if with_energy else None
+        if n and rows:
+            with torch.cuda.device(x.device):
+                dso, dfo = torch.from_numpy(so).to(x.device), torch.from_numpy(fo).to(x.device)
+                if mfcc:
+                    _lib.check(lib.ss_kaldi_mfcc_packed_device(cfg.handle, x.data_ptr(), n, dso.data_ptr(), dfo.data_ptr(), rows, out.data_ptr(),
+                                                               _stream_ptr()))
+                else:
+                    _lib.check(lib.ss_kaldi_fbank_packed_device(cfg.handle, x.data_ptr(), n, dso.data_ptr(), dfo.data_ptr(), rows, out.data_ptr(),
+                                                                en.data_ptr() if with_energy else None, _stream_ptr()))
+                for t in (x, dso, dfo):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                    t.record_stream(torch.cuda.current_stream())
+        if with_energy:
+            out = torch.cat([en.unsqueeze(-1), out], dim=-1)
+        return out, fo
+    x = np.ascontiguousarray(sig)
+    out = np.empty((rows, cols), dtype=np.float32)
+    en = np.empty((rows,), dtype=np.float32) if with_energy else None
+    if n and rows:
+        if mfcc:
+            _lib.check(lib.ss_kaldi_mfcc_packed(cfg.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data))
+        else:
+            _lib.check(lib.ss_kaldi_fbank_packed(cfg.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data, en.ctypes.data if with_energy else None))
+    if with_energy:
+        out = np.concatenate([en[:, None], out], axis=-1)
+    return out, fo
+
+
+def kaldi_fbank(waveform, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0, high_freq=0.0,
+                preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True, use_power=True,
+                use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, **unsupported):
+    """``torchaudio.compliance.kaldi.fbank`` (Kaldi's compute-fbank-feats) of one clip [L] -> [T, num_mel_bins] or of every row of a
+    batch [B, L] -> [B, T, num_mel_bins], float32; the names and defaults are torchaudio's.  ``use_energy=True`` puts the log energy
+    in column 0 ([.., num_mel_bins + 1]), as torchaudio does.  numpy in -> the host-pointer call; a ROCm tensor stays on the device
+    (current stream, one launch).  ``input_scale``: every sample is multiplied by it first (32768 for normalised floats that stand
+    for 16-bit PCM).  Served for frames that pad to 512 points (256 < samples per frame <= 512); dither, snip_edges=False, htk_compat,
+    subtract_mean, vtln_* and channel raise."""
+    what = "kaldi_fbank"
+    sig = _require_f32(waveform, (1, 2), what)
+    cfg = _kaldi_cfg(what, sig, False, sample_frequency, frame_length, frame_shift, num_mel_bins, 0, low_freq, high_freq, preemphasis_coefficient,
+                     0.0, window_type, blackman_coeff, remove_dc_offset, use_power, False, raw_energy, energy_floor, input_scale, unsupported)
+    return _kaldi_dense(sig, cfg, False, bool(use_energy))
+
+
+def kaldi_mfcc(waveform, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0, high_freq=0.0,
+               preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True, use_energy=False,
+               raw_energy=True, energy_floor=1.0, input_scale=1.0, num_ceps=13, cepstral_lifter=22.0, **unsupported):
+    """``torchaudio.compliance.kaldi.mfcc`` (Kaldi's compute-mfcc-feats) of one clip [L] -> [T, num_ceps] or of a batch [B, L] ->
+    [B, T, num_ceps]: the orthonormal DCT of ``kaldi_fbank``'s power-spectrum log-mel row with the cepstral lifter; ``use_energy=True``
+    replaces coefficient 0 by the log energy.  See ``kaldi_fbank`` for the inputs and for what is not served."""
+    what = "kaldi_mfcc"
+    sig = _require_f32(waveform, (1, 2), what)
+    cfg = _kaldi_cfg(what, sig, True, sample_frequency, frame_length, frame_shift, num_mel_bins, num_ceps, low_freq, high_freq,
+                     preemphasis_coefficient, cepstral_lifter, window_type, blackman_coeff, remove_dc_offset, True, use_energy, raw_energy,
+                     energy_floor, input_scale, unsupported)
+    return _kaldi_dense(sig, cfg, True, False)
+
+
+def kaldi_fbank_packed(signal, lengths, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0,
+                       high_freq=0.0, preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True,
+                       use_power=True, use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, **unsupported):
+    """``kaldi_fbank`` of clips of different lengths packed end to end in one 1-D float32 signal -> (rows [sum T_b, cols],
+    frame_offsets [n + 1] int64 on the host): clip b's rows are frame_offsets[b] : frame_offsets[b + 1], bit for bit what
+    ``kaldi_fbank`` returns for that clip alone.  One launch for all clips.  ``(out, out_lengths)`` of ``resample_packed`` are valid
+    ``(signal, lengths)`` as they stand."""
+    what = "kaldi_fbank_packed"
+    sig = _require_f32(signal, (1,), what)
+    so = _sample_offsets(lengths, sig.shape[0], what)
+    cfg = _kaldi_cfg(what, sig, False, sample_frequency, frame_length, frame_shift, num_mel_bins, 0, low_freq, high_freq, preemphasis_coefficient,
+                     0.0, window_type, blackman_coeff, remove_dc_offset, use_power, False, raw_energy, energy_floor, input_scale, unsupported)
+    return _kaldi_packed(sig, so, cfg, False, bool(use_energy))
+
+
+def kaldi_mfcc_packed(signal, lengths, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0,
+                      high_freq=0.0, preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True,
+                      use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, num_ceps=13, cepstral_lifter=22.0, **unsupported):
+    """``kaldi_mfcc`` of packed clips (see ``kaldi_fbank_packed``) -> (rows [sum T_b, num_ceps], frame_offsets [n + 1])."""
+    what = "kaldi_mfcc_packed"
+    sig = _require_f32(signal, (1,), what)
+    so = _sample_offsets(lengths, sig.shape[0], what)
+    cfg = _kaldi_cfg(what, sig, True, sample_frequency, frame_length, frame_shift, num_mel_bins, num_ceps, low_freq, high_freq,
+                     preemphasis_coefficient, cepstral_lifter, window_type, blackman_coeff, remove_dc_offset, True, use_energy, raw_energy,
+                     energy_floor, input_scale, unsupported)
+    return _kaldi_packed(sig, so, cfg, True, False)
+
+
+def _kaldi_list(what, signals, packed_fn, kw):
+    sigs = [_require_f32(x, (1,), what) for x in signals]
+    if not sigs:
+        return []
+    on_device = [_is_torch(x) for x in sigs]
+    if any(on_device) and not all(on_device):
+        raise ValueError(f"{what}: the clips of one call must all be device tensors or all host arrays")
+    if all(on_device):
+        import torch
+
+        if any(x.device != sigs[0].device for x in sigs):
+            raise ValueError(f"{what}: the clips of one call must live on one device")
+        packed = torch.cat(sigs)
+    else:
+        packed = np.concatenate(sigs)
+    out, fo = packed_fn(packed, [int(x.shape[0]) for x in sigs], **kw)
+    fo = fo.tolist()
+    return [out[fo[b]:fo[b + 1]] for b in range(len(sigs))]
+
+
+def kaldi_fbank_list(signals, **kw):
+    """A list of 1-D float32 clips of any lengths -> the list of their ``kaldi_fbank`` rows (views of one block): the clips are packed
+    once and served by one ``kaldi_fbank_packed`` call, whose keyword arguments this takes."""
+    return _kaldi_list("kaldi_fbank_list", signals, kaldi_fbank_packed, kw)
+
+
+def kaldi_mfcc_list(signals, **kw):
+    """``kaldi_fbank_list`` for ``kaldi_mfcc_packed``."""
+    return _kaldi_list("kaldi_mfcc_list", signals, kaldi_mfcc_packed, kw)

@@ -60,6 +60,35 @@ class SsResampleInfo(C.Structure):
     _fields_ = [(name, C.c_uint32) for name in ("o", "n", "width", "taps", "lookback", "lookahead", "latency_periods", "tile_outputs")]
 
 
+KALDI_WINDOW = {"povey": 0, "hanning": 1, "hamming": 2, "rectangular": 3, "blackman": 4}
+
+
+class SsKaldiParams(C.Structure):
+    """ss_kaldi_params (include/speechsauce_amd.h); field order is ABI."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("sample_rate", C.c_uint32),
+        ("frame_length_ms", C.c_float),
+        ("frame_shift_ms", C.c_float),
+        ("num_mel_bins", C.c_uint32),
+        ("num_ceps", C.c_uint32),
+        ("low_freq", C.c_float),
+        ("high_freq", C.c_float),
+        ("preemph_coef", C.c_float),
+        ("cepstral_lifter", C.c_float),
+        ("window_type", C.c_int32),
+        ("blackman_coeff", C.c_float),
+        ("remove_dc_offset", C.c_int32),
+        ("use_power", C.c_int32),
+        ("use_energy", C.c_int32),
+        ("raw_energy", C.c_int32),
+        ("energy_floor", C.c_float),
+        ("input_scale", C.c_float),
+        ("dither", C.c_float),
+    ]
+
+
 class SpeechSauceError(RuntimeError):
     """Raised where the reference would panic (or where HIP fails)."""
 
@@ -75,6 +104,7 @@ _lib = None
 _P = C.POINTER
 _cfg = C.c_void_p
 _rs = C.c_void_p  # ss_resampler *
+_kc = C.c_void_p  # ss_kaldi_config *
 _fp = C.c_void_p  # float* passed as an address (numpy .ctypes.data or a device pointer)
 PROTOTYPES = {
     "ss_params_default": (C.c_int, [_P(SsParams), C.c_uint32]),
@@ -238,6 +268,26 @@ PROTOTYPES = {
     "ss_resample_stream_packed_i16": (C.c_int, [_rs, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp]),
     "ss_resample_stream_flush_device": (C.c_int, [_rs, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp, C.c_void_p]),
     "ss_resample_stream_flush": (C.c_int, [_rs, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp]),
+    "ss_kaldi_params_default": (C.c_int, [_P(SsKaldiParams), C.c_uint32]),
+    "ss_kaldi_params_validate": (C.c_int, [_P(SsKaldiParams)]),
+    "ss_kaldi_sizes": (C.c_int, [_P(SsKaldiParams), _P(C.c_size_t), _P(C.c_size_t), _P(C.c_size_t)]),
+    "ss_kaldi_num_frames": (C.c_int, [_P(SsKaldiParams), C.c_size_t, _P(C.c_size_t)]),
+    "ss_kaldi_packed_frame_offsets": (C.c_int, [_P(SsKaldiParams), C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ss_kaldi_window": (C.c_int, [_P(SsKaldiParams), _fp]),
+    "ss_kaldi_mel_bank": (C.c_int, [_P(SsKaldiParams), _fp]),
+    "ss_kaldi_dct": (C.c_int, [_P(SsKaldiParams), _fp]),
+    "ss_kaldi_config_create": (C.c_int, [_P(SsKaldiParams), _P(_kc)]),
+    "ss_kaldi_config_destroy": (None, [_kc]),
+    "ss_kaldi_config_params": (C.c_int, [_kc, _P(SsKaldiParams)]),
+    "ss_kaldi_config_device_status": (C.c_int, [_kc]),
+    "ss_kaldi_fbank_device": (C.c_int, [_kc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_kaldi_fbank": (C.c_int, [_kc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp]),
+    "ss_kaldi_mfcc_device": (C.c_int, [_kc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp, C.c_void_p]),
+    "ss_kaldi_mfcc": (C.c_int, [_kc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp]),
+    "ss_kaldi_fbank_packed_device": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_kaldi_fbank_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, _fp, _fp]),
+    "ss_kaldi_mfcc_packed_device": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
+    "ss_kaldi_mfcc_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, _fp]),
     "ss_shard_bounds": (C.c_int, [C.c_size_t, C.c_int, C.c_int, _P(C.c_size_t), _P(C.c_size_t)]),
     "ss_all_gather_features": (C.c_int, [C.c_void_p, _fp, C.c_size_t, _fp, C.c_void_p]),
     "ss_gather_features": (C.c_int, [C.c_void_p, _fp, C.c_size_t, _fp, C.c_int, C.c_int, C.c_int, C.c_void_p]),
