@@ -63,7 +63,7 @@ __device__ __forceinline__ KClip kaldi_clip(const KaldiVarlenArgs &v, uint32_t f
 }
 
 // Where this lane group's frame starts and whether it exists.  Dense: lanes past the last frame redo it.  VARLEN: `cursor` is the
-// wave's clip of its last quad's first row (claims only increase); a lane's frame lies at most three clips further on.
+// wave's clip of its last quad's first row (claims only increase); a lane's frame lies at most three clips WITH rows further on.
 template <bool VARLEN>
 __device__ __forceinline__ const float *frame_src(const KaldiArgs &a, const KaldiVarlenArgs &v, unsigned quad, unsigned total, int f, unsigned &cursor, bool &ok)
 {
@@ -72,8 +72,15 @@ __device__ __forceinline__ const float *frame_src(const KaldiArgs &a, const Kald
     if constexpr (VARLEN) {
         unsigned c = offset_seek(v.fo, v.n_clips, cursor, q4);
         cursor = c;
+        bool step = true;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) c += (c + 1 < v.n_clips && v.fo[c + 1] <= static_cast<long long>(g)) ? 1u : 0u;
+        for (int k = 0; k < 3; ++k) {
+            step = c + 1 < v.n_clips && v.fo[c + 1] <= static_cast<long long>(g);
+            c += step ? 1u : 0u;
+        }
+        // entries without rows inside the quad (fo[b] == fo[b + 1]) take steps of their own: a lane that took all three looks once
+        // more, and searches where they did not get there
+        if (step && c + 1 < v.n_clips && v.fo[c + 1] <= static_cast<long long>(g)) c = offset_find(v.fo, v.n_clips, static_cast<long long>(g));
         const KClip cl = kaldi_clip(v, a.flen, a.step, c);
         const long long tl = static_cast<long long>(g) - cl.f0;
         ok = cl.ok && tl >= 0 && tl < static_cast<long long>(cl.T);

@@ -1,6 +1,7 @@
 """Host-side table builders under AddressSanitizer + UBSan (CPU only): tools/hosttest/fuzz_tables.cpp builds the LDS blocks of
 every kernel for pseudo-random valid configurations and checks that each filter's weights reach exactly one (slot, lane) bit
-for bit, that no lane reads past its P row and that the cosine rows are the host DCT table in the kernel's layout.  Its --digest
+for bit, that no lane reads past its P row and that the cosine rows are the host DCT table in the kernel's layout -- and, for
+pseudo-random valid ss_kaldi_params, the same of the Kaldi front end's block with its appended window.  Its --digest
 mode (one line of flags, sizes and a hash of the table bytes per block: what two builds of ss_host.cpp are compared by) runs here
 too, twice, so that it stays buildable, clean under the sanitizers and deterministic."""
 import os
@@ -27,5 +28,7 @@ def test_table_builders_sanitized(tmp_path):
     for r in digests:
         assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
     assert digests[0].stdout and digests[0].stdout == digests[1].stdout
-    # the named configurations and the random ones, ten blocks each, none rejected by build_tables
-    assert digests[0].stdout.count("\n") >= 10 * 60 and " fnv " in digests[0].stdout
+    # the named configurations and the random ones, ten blocks each, none rejected by build_tables; then the Kaldi front end's block,
+    # one line for each of its random configurations
+    assert digests[0].stdout.count("\n") >= 11 * 60 and " fnv " in digests[0].stdout
+    assert digests[0].stdout.count("| kaldi512 ok 1 ") >= 60 and "| kaldi512 ok 0 " not in digests[0].stdout

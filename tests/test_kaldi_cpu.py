@@ -184,9 +184,17 @@ def test_defaults_are_torchaudios(sslib):
     assert sslib.ss_kaldi_params_validate(C.byref(sp)) == SS_OK
 
 
+# the frame lengths of tests/test_kaldi_builds.py: the smallest and the largest of every NE class of the kernel (live input pairs
+# 10 / 13 / 16 for flen <= 320 / 416 / 512) beside the everyday ones.  id -> (sample_rate, frame_length_ms, flen, shift, NE)
+FRAME_LENGTHS = {"257": (16000, 16.0625, 257, 160, 10), "320": (16000, 20.0, 320, 160, 10), "321": (16000, 20.0625, 321, 160, 13),
+                 "400": (16000, 25.0, 400, 160, 13), "416": (16000, 26.0, 416, 160, 13), "417": (16000, 26.0625, 417, 160, 16),
+                 "511": (16000, 31.9375, 511, 160, 16), "512": (16000, 32.0, 512, 160, 16), "275": (11025, 25.0, 275, 110, 10)}
+
+
 @pytest.mark.parametrize("sr,fl,fs,want", [(16000, 25.0, 10.0, (400, 160, 512)), (16000, 20.0, 10.0, (320, 160, 512)),
                                            (16000, 32.0, 10.0, (512, 160, 512)), (11025, 25.0, 10.0, (275, 110, 512)),
-                                           (16000, 25.0, 10.0625, (400, 161, 512))])
+                                           (16000, 25.0, 10.0625, (400, 161, 512))] +
+                         [(sr, fl, 10.0, (flen, shift, 512)) for sr, fl, flen, shift, _ in FRAME_LENGTHS.values()])
 def test_sizes(sslib, sr, fl, fs, want):
     sp = make_kaldi_params(sslib, sample_rate=sr, frame_length_ms=fl, frame_shift_ms=fs)
     assert lib_sizes(sslib, sp) == (SS_OK, want)
@@ -393,3 +401,82 @@ def test_the_specification_is_well_posed_in_f32(kind):
     c0, ck = block_metric(c32[:, 0], c64[:, 0]), block_metric(c32[:, 1:], c64[:, 1:])
     print(f"f32 restatement vs f64, {kind}: fbank-80 {fb:.3g}, mfcc column 0 {c0:.3g}, columns 1.. {ck:.3g}")
     assert fb < 1e-5 and c0 < 1e-5 and ck < 1e-5
+
+
+# ---- the shapes of tests/test_kaldi_loop.py: which calls reach the kernel's persistent loop, which stay one quad per wave ---------
+
+KALDI_WAVES = 12  # waves per workgroup of ss_kaldi_c256; a quad is four consecutive rows of the flat frame list
+LOOP_T = 5        # frames per clip of the dense loop tests: no multiple of four, so quads straddle clips
+
+
+def kaldi_grid(quads, cus):
+    """cu_capped_grid(quads, 12, cus) of ss_launch_plan.h: one workgroup per CU, fewer where there is no quad for every wave"""
+    return min(-(-quads // KALDI_WAVES), cus)
+
+
+def workgroup_quads(quads, cus):
+    """[q_lo, q_hi) of every workgroup, as the kernel's prologue computes them"""
+    grid = kaldi_grid(quads, cus)
+    return [(quads * b // grid, quads * (b + 1) // grid) for b in range(grid)]
+
+
+def loop_dense_clips(cus, T=LOOP_T):
+    """clips of T frames in a BIG dense call: at least 3 * 12 * cus + 5 quads, so every wave goes round the loop at least twice more"""
+    return -(-4 * (3 * KALDI_WAVES * cus + 5) // T) + 1
+
+
+def covered_clips(cus, T=LOOP_T):
+    """clips of T frames in a COVERED dense call: at most 12 * cus quads, one per wave -- what the small-shape tests hold to f64"""
+    return 4 * KALDI_WAVES * cus // T
+
+
+def loop_packed_frames(cus, seed=0):
+    """T_b of the clips of a BIG packed call: runs of one-frame clips (a quad over four clips), 1 .. 7 frames otherwise (offset_seek's
+    steps), a clip of about 98 frames now and then (behind it the next claim is past the steps: offset_seek's binary search)"""
+    rng = np.random.default_rng(seed)
+    Ts, rows, want = [], 0, 4 * (3 * KALDI_WAVES * cus + 5)
+    while rows < want:
+        block = [1] * 9 + rng.integers(1, 8, 40).tolist() + [int(rng.integers(95, 102))] + rng.integers(1, 8, 7).tolist()
+        Ts += block
+        rows += sum(block)
+    if rows % 4 == 0:
+        Ts.append(3)
+    return Ts
+
+
+def packed_chunks(Ts, cus):
+    """consecutive runs [i0, i1) of clips with at most 12 * cus quads each: the COVERED calls a big packed call is compared with"""
+    cap, runs, i0, rows = 4 * KALDI_WAVES * cus, [], 0, 0
+    for i, T in enumerate(Ts):
+        if rows + T > cap:
+            runs.append((i0, i))
+            i0, rows = i, 0
+        rows += T
+    runs.append((i0, len(Ts)))
+    return runs
+
+
+@pytest.mark.parametrize("cus", [64, 256, 304])
+def test_loop_test_shapes_reach_the_loop(cus):
+    """Every shape of tests/test_kaldi_loop.py: in a big call each workgroup owns at least 3 x 12 quads -- a first quad and two further
+    claims for each of its waves -- and in the calls it is compared with no workgroup owns more than 12: one quad per wave, no claim
+    taken, the regime of tests/test_kaldi.py and tests/test_kaldi_builds.py."""
+    def quads_of(rows):
+        return -(-rows // 4)
+
+    def check(big_rows, covered_rows):
+        quads = quads_of(big_rows)
+        assert quads >= 3 * KALDI_WAVES * cus + 5 and big_rows % 4 != 0
+        spans = [hi - lo for lo, hi in workgroup_quads(quads, cus)]
+        assert len(spans) == cus and min(spans) >= 3 * KALDI_WAVES
+        assert len(covered_rows) >= 2  # the big call is more than one covered call
+        for rows in covered_rows:
+            assert rows > 0 and max(hi - lo for lo, hi in workgroup_quads(quads_of(rows), cus)) <= KALDI_WAVES
+
+    B, Bc = loop_dense_clips(cus), covered_clips(cus)
+    check(B * LOOP_T, [min(Bc, B - i) * LOOP_T for i in range(0, B, Bc)])
+    Ts = loop_packed_frames(cus)
+    assert Ts.count(1) > 9 and max(Ts) >= 95 and {2, 3, 4, 5, 6, 7} <= set(Ts)
+    check(sum(Ts), [sum(Ts[i0:i1]) for i0, i1 in packed_chunks(Ts, cus)])
+    # the equal-length clips of the dense case, packed: the same rows
+    check(B * LOOP_T, [(i1 - i0) * LOOP_T for i0, i1 in packed_chunks([LOOP_T] * B, cus)])

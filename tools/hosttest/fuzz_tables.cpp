@@ -7,6 +7,9 @@
 //     block, starting at the P bin in the start table -- are, bit for bit, the dense bank's row (zero outside);
 //   * no (slot, lane) reads past the P row the kernel keeps;
 //   * the cosine rows equal the host DCT table in the layout the kernel indexes (twice-folded per-lane rows of the 4096 kernel).
+// Then the same number of pseudo-random valid ss_kaldi_params (M 3..80, every served frame length, bands, windows, cepstra 1..32,
+// lifter) for the Kaldi front end's block: the same bank checks inside P bins 0..259, the cosine rows against kaldi_dct in
+// (slot, lane) order, the appended window against kaldi_window with zeros from flen to 512, and no valid configuration rejected.
 // `fuzz_tables --digest [cases] [seed]` checks nothing and prints, for a fixed list of named configurations and then the same
 // pseudo-random ones, one line per kernel block: every flag and integer of its struct, the table's size and a 64-bit FNV-1a hash of
 // its bytes.  Two builds of ss_host.cpp compute the same tables exactly when these outputs are equal (the hashes depend on the
@@ -106,6 +109,88 @@ static ss_params random_params()
     p.dc_elimination = rnd() % 2;
     p.framing = rnd() % 8 == 0 ? SS_FRAMING_CENTER : SS_FRAMING_CONTRACT;
     return p;
+}
+
+// ---- the Kaldi front end's block (ss_kaldi_c256): its own parameter structure, so its own draws and its own checks ----
+
+// valid by the header's rules and served (256 < flen <= 512, M 3..80, cepstra 1..32): build_kaldi512 may reject none of these
+static ss_kaldi_params random_kaldi_params()
+{
+    static const unsigned rates[] = {11025, 12000, 16000, 22050};
+    ss_kaldi_params p;
+    const unsigned sr = rates[rnd() % 4];
+    ss_kaldi_params_default(&p, sr);
+    static const unsigned edges[] = {257, 320, 321, 400, 416, 417, 511, 512};
+    const unsigned flen = rnd() % 3 == 0 ? edges[rnd() % 8] : 257 + rnd() % 256;
+    p.frame_length_ms = static_cast<float>((flen + 0.5) * 1000.0 / sr);
+    p.frame_shift_ms = static_cast<float>((1 + rnd() % 600 + 0.5) * 1000.0 / sr);
+    p.num_mel_bins = rnd() % 4 == 0 ? 3 + rnd() % 6 : 3 + rnd() % 78;
+    p.num_ceps = 1 + rnd() % (p.num_mel_bins < 32 ? p.num_mel_bins : 32);
+    p.low_freq = rnd() % 3 == 0 ? 0.0f : static_cast<float>(urand() * sr / 8);
+    switch (rnd() % 3) {
+    case 0: p.high_freq = 0.0f; break;
+    case 1: p.high_freq = static_cast<float>(-urand() * sr / 8); break;
+    default: p.high_freq = static_cast<float>(p.low_freq + 50.0 + urand() * (sr / 2.0 - p.low_freq - 50.0)); break;
+    }
+    p.window_type = static_cast<int32_t>(rnd() % 5);
+    p.blackman_coeff = static_cast<float>(0.35 + 0.1 * urand());
+    p.cepstral_lifter = rnd() % 3 == 0 ? 0.0f : static_cast<float>(1.0 + 40.0 * urand());
+    p.use_power = rnd() % 2;
+    return p;
+}
+
+// true: the block was built.  The bank reaches (slot, lane) bit for bit inside P bins 0 .. 259, the cosine rows are kaldi_dct in
+// (slot, lane) order (zero where the pair has no filter), the appended window is kaldi_window with zeros from flen to 512.
+static bool check_kaldi_block(const std::string &what, const ss_kaldi_params &p)
+{
+    namespace L = ss::mfcc512w_layout;
+    ss::KaldiSizes s;
+    const int rc = ss::kaldi_validate(p, &s);
+    CHECK(rc == SS_OK, "a valid draw fails kaldi_validate with %d", rc);
+    if (rc != SS_OK) return false;
+    ss::KaldiTables f;
+    ss::build_kaldi512(p, f);
+    CHECK(f.ok, "build_kaldi512 rejects a valid configuration (pitch %d)", f.wpitch);
+    if (!f.ok) return false;
+    const size_t M = p.num_mel_bins, Cc = p.num_ceps, F = 257, flen = s.flen;
+    CHECK(f.s.flen == s.flen && f.s.shift == s.shift && f.s.padded == 512, "sizes %u %u %u", f.s.flen, f.s.shift, f.s.padded);
+    CHECK(f.wpitch > 0 && f.wpitch <= 320 && f.wpitch % 4 == 0, "weight pitch %d", f.wpitch);
+    const size_t win0 = static_cast<size_t>(L::kMelW) + 16 * static_cast<size_t>(f.wpitch);
+    CHECK(f.tab.size() == win0 + 512, "table of %zu floats, want %zu", f.tab.size(), win0 + 512);
+    if (f.tab.size() != win0 + 512) return true;
+    // the dense bank, widened to the 257 bins of a P row: the Nyquist column carries no weight
+    ss::HostTables t;
+    t.params.num_filters = static_cast<uint32_t>(M);
+    t.d.n_bins = static_cast<uint32_t>(F);
+    std::vector<float> dense(M * 256);
+    ss::kaldi_mel_bank(p, s, dense.data());
+    t.fb_dense.assign(M * F, 0.0f);
+    for (size_t b = 0; b < M; ++b) std::copy(dense.begin() + b * 256, dense.begin() + (b + 1) * 256, t.fb_dense.begin() + b * F);
+    check_mel_block(what, t, f.tab, L::kStart, L::kFilt, L::kMelW, 5, 16, f.q4, f.wpitch, 260);
+    std::vector<float> dct(Cc * M);
+    ss::kaldi_dct(p, dct.data());
+    const int32_t *filt = reinterpret_cast<const int32_t *>(f.tab.data() + L::kFilt);
+    for (size_t c = 0; c < 32; ++c)
+        for (size_t q = 0; q < 80; ++q) {
+            const int32_t m = filt[q];
+            const float want = c < Cc && m >= 0 && m < static_cast<int32_t>(M) ? dct[c * M + m] : 0.f, got = f.tab[L::kCos + c * L::kCosPitch + q];
+            CHECK(std::memcmp(&want, &got, 4) == 0 || (want == 0.f && got == 0.f), "cosine row %zu slot-lane %zu (filter %d): %.9g, kaldi_dct %.9g", c, q, m, got, want);
+        }
+    std::vector<float> w(flen);
+    ss::kaldi_window(p, s, w.data());
+    for (size_t i = 0; i < 512; ++i) {
+        const float want = i < flen ? w[i] : 0.f, got = f.tab[win0 + i];
+        CHECK(std::memcmp(&want, &got, 4) == 0, "window sample %zu: %.9g, kaldi_window %.9g (flen %zu)", i, got, want, flen);
+    }
+    return true;
+}
+
+static std::string kaldi_name(int it, const ss_kaldi_params &p)
+{
+    char name[256];
+    std::snprintf(name, sizeof name, "kaldi case %d (sr %u flen-ms %.4f M %u C %u lo %.1f hi %.1f win %d lifter %.2f)", it, p.sample_rate, p.frame_length_ms,
+                  p.num_mel_bins, p.num_ceps, p.low_freq, p.high_freq, p.window_type, p.cepstral_lifter);
+    return name;
 }
 
 // ---- digest mode ----
@@ -258,6 +343,27 @@ static int digest_main(int cases)
         std::snprintf(name, sizeof name, "case %d", it);
         digest_config(name, p);
     }
+    // the Kaldi front end's block: the defaults at the everyday shapes, then pseudo-random draws
+    static const struct { const char *name; unsigned sr; float ms; unsigned M, C; } kKaldiNamed[] = {
+        {"kaldi 16k 25ms 80", 16000, 25.0f, 80, 13}, {"kaldi 16k 25ms 23", 16000, 25.0f, 23, 13}, {"kaldi 16k 20ms 40 x 32", 16000, 20.0f, 40, 32},
+        {"kaldi 16k 32ms 80", 16000, 32.0f, 80, 20}, {"kaldi 11k 25ms 40", 11025, 25.0f, 40, 13}, {"kaldi 16k 25ms 3", 16000, 25.0f, 3, 3}};
+    auto kaldi_line = [](const char *name, const ss_kaldi_params &p) {
+        ss::KaldiTables f;
+        ss::build_kaldi512(p, f);
+        digest_line(name, "kaldi512", f, f.q4, Digest{});
+    };
+    for (const auto &n : kKaldiNamed) {
+        ss_kaldi_params p;
+        ss_kaldi_params_default(&p, n.sr);
+        p.frame_length_ms = n.ms;
+        p.num_mel_bins = n.M;
+        p.num_ceps = n.C;
+        kaldi_line(n.name, p);
+    }
+    for (int it = 0; it < cases; ++it) {
+        const ss_kaldi_params p = random_kaldi_params();
+        kaldi_line(kaldi_name(it, p).c_str(), p);
+    }
     return 0;
 }
 
@@ -386,8 +492,18 @@ int main(int argc, char **argv)
             }
         }
     }
-    std::printf("%d configurations, %d valid; blocks built: fast512 %d, mfcc512w %d, mel512 %d, mfcc256 %d, mfcc1024 %d, mel1024 %d, mfcc2048 %d, mel2048 %d, mfcc4096 %d, mel4096 %d\n",
-                cases, valid, built[0], built[1], built[2], built[3], built[4], built[5], built[6], built[7], built[8], built[9]);
+    int kaldi_built = 0;  // after the others: their draws stay what they were
+    for (int it = 0; it < cases; ++it) {
+        const ss_kaldi_params p = random_kaldi_params();
+        kaldi_built += check_kaldi_block(kaldi_name(it, p), p);
+    }
+    {
+        const std::string what = "kaldi";
+        CHECK(kaldi_built == cases, "%d of %d valid Kaldi configurations built", kaldi_built, cases);
+    }
+    std::printf("%d configurations, %d valid; blocks built: fast512 %d, mfcc512w %d, mel512 %d, mfcc256 %d, mfcc1024 %d, mel1024 %d, mfcc2048 %d, mel2048 %d, mfcc4096 %d, mel4096 %d; "
+                "kaldi512 %d of %d\n",
+                cases, valid, built[0], built[1], built[2], built[3], built[4], built[5], built[6], built[7], built[8], built[9], kaldi_built, cases);
     std::printf(g_fail ? "%d check(s) FAILED\n" : "all checks passed\n", g_fail);
     return g_fail ? 1 : 0;
 }
