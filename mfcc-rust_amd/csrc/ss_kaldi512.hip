@@ -2,17 +2,15 @@
 // torchaudio.compliance.kaldi restates them) for frames that pad to 512 points, on gfx950.  The specification is the ss_kaldi_*
 // comment of include/speechsauce_amd.h; the reference crate has no such path, so this file restates nothing of it.
 //
-// Skeleton of ss_mfcc_c256w (ss_mfcc512w.hip), table block ss::KaldiTables (mfcc512w_layout + the window):
-//   * Work unit: a QUAD of 4 consecutive frames of the flat frame list; 16 lanes (one DPP row) own a frame = 256 packed complex
-//     points, 16 per lane.  One persistent 12-wave workgroup per CU, quads from an LDS counter, the next quad's samples prefetched
-//     into the dead input registers.  Zero padding is compile-time (template NE).
-//   * NEW, between the load and the first butterfly, on the input registers: the per-frame conditioning stage -- input scale, DC
+// The quad skeleton (a QUAD of 4 consecutive frames of the flat frame list per wave, 16 lanes per frame, persistent 12-wave
+// workgroups, the two radix-16 passes and the untangle) is ss_quad256.h; the table block is ss::KaldiTables (mfcc512w_layout + the
+// window).  Zero padding is compile-time (template NE).  What is this file's own:
+//   * between the load and the first butterfly, on the input registers: the per-frame conditioning stage -- input scale, DC
 //     removal (frame sum by row16_sum, a true division, the pad kept at zero), raw energy, per-frame pre-emphasis (the predecessor
 //     of s[2n] is the neighbouring lane's .y: one row_ror:1 DPP move per pair and a select for lane 0, whose predecessor sits one
 //     register earlier in lane 15), window, windowed energy.
-//   * FFT / untangle as in ss_mfcc512w.hip (radix-16, one transposing exchange through the frame's wave-private slot, twiddle,
-//     radix-16; partner Z[256-k] by ds_bpermute_b32).  The P row holds the unscaled |2X|^2 or |2X|; the 1/4 or 1/2 rides on the
-//     mel sums (exact: a power of two).  No 1/N, no T-dependent scale; the Nyquist bin has no weight in the bank.
+//   * The P row holds the unscaled |2X|^2 or |2X|; the 1/4 or 1/2 rides on the mel sums (exact: a power of two).  No 1/N, no
+//     T-dependent scale; the Nyquist bin has no weight in the bank.
 //   * banded mel, five filters per lane, max(., eps) and v_log_f32 (eps is a normal f32: no pre-scale), then either the [T x M]
 //     row (+ the log energy) or the DCT against the lane's liftered table row, c[0] replaced by the log energy under use_energy.
 //   * VARLEN: the flat frame index is the output row of a packed launch; clip and frame come from fo / so by offset_seek /
@@ -22,6 +20,7 @@
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 #include "ss_internal.h"
+#include "ss_quad256.h"
 #include "ss_wave.h"
 
 namespace ss {
@@ -29,11 +28,10 @@ namespace ss {
 namespace {
 
 using namespace wv;
+using namespace q256;  // the slot holds, after the exchange, P row [260] | ln(mel) row [80]
 
 namespace L = mfcc512w_layout;
-constexpr int kSlotFloats = 576;        // per frame: exchange slot (288 float2); afterwards P row [260] | ln(mel) row [80]
-constexpr int kWaveFloatsX = 4 * kSlotFloats;
-constexpr int kPRowX = 260;             // bins 0..256 + three zero pad bins
+constexpr int kPRowX = 260;            // bins 0..256 + three zero pad bins
 constexpr float kLn2 = 0.69314718055994530942f;
 
 // ln(max(v, eps)): eps = 2^-23 is a normal number, v_log_f32 needs no denormal care
@@ -87,16 +85,7 @@ __device__ __forceinline__ const float *frame_src(const KaldiArgs &a, const Kald
         return a.x + (ok ? cl.s0 + tl * static_cast<long long>(a.step) : 0ll);
     } else {
         unsigned clip, t;
-        if (a.nf_magic) {
-            clip = __umulhi(q4, a.nf_magic) >> a.nf_shift;
-            t = q4 - clip * a.n_frames + (g - q4);
-            const bool wrap = t >= a.n_frames;
-            t -= wrap ? a.n_frames : 0u;
-            clip += wrap ? 1u : 0u;
-        } else {
-            clip = g / a.n_frames;
-            t = g - clip * a.n_frames;
-        }
+        locate_frame(q4, g - q4, a.n_frames, a.nf_magic, a.nf_shift, clip, t);
         ok = true;
         return a.x + static_cast<unsigned long long>(clip) * a.ld + static_cast<unsigned long long>(t) * a.step;
     }
@@ -150,9 +139,9 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
     const int f = lane >> 4;  // frame within the quad
     const int j = lane & 15;  // lane within the frame (DPP row)
 
-    float *slot = reinterpret_cast<float *>(smem) + wave * kWaveFloatsX + f * kSlotFloats;
+    float *slot = reinterpret_cast<float *>(smem) + wave * kWaveFloats + f * kSlotFloats;
     float2 *zh = reinterpret_cast<float2 *>(slot);
-    float *s_tab = reinterpret_cast<float *>(smem) + WAVES * kWaveFloatsX;
+    float *s_tab = reinterpret_cast<float *>(smem) + WAVES * kWaveFloats;
     const float4 *s_tw2 = reinterpret_cast<const float4 *>(s_tab + L::kTw2);
     const float2 *s_twn = reinterpret_cast<const float2 *>(s_tab + L::kTwn);
     const float *s_cos = s_tab + L::kCos;
@@ -166,11 +155,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
     const unsigned quads = (total + 3) / 4;
     const unsigned q_lo = static_cast<unsigned>(static_cast<unsigned long long>(quads) * blockIdx.x / gridDim.x);
     const unsigned q_hi = static_cast<unsigned>(static_cast<unsigned long long>(quads) * (blockIdx.x + 1) / gridDim.x);
-    {
-        const int n4 = (L::kMelW + 16 * a.mel_wpitch + 512) / 4;
-        for (int i = tid; i < n4; i += WAVES * 64) reinterpret_cast<float4 *>(s_tab)[i] = reinterpret_cast<const float4 *>(a.tab)[i];
-        if (tid == 0) *s_next = q_lo + WAVES;
-    }
+    stage_tables(s_tab, a.tab, (L::kMelW + 16 * a.mel_wpitch + 512) / 4, tid, WAVES * 64);
+    if (tid == 0) *s_next = q_lo + WAVES;
     if constexpr (VARLEN) {
         // one pass over the clips, spread over the grid: an inconsistent clip raises the error word (a vector store to the pinned word)
         bool bad = false;
@@ -187,8 +173,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
         load_quad_k<NE, VARLEN>(src, ok_next, a.flen, j, vin);
     }
 
-    const int paddr = ((lane & 48) | ((16 - j) & 15)) << 2;  // lane holding Z[256 - k]
-    const int wbase1 = 34 * (j >> 1) + (j & 1);              // exchange write base (float2 units)
+    const int paddr = partner_addr(lane, j), wbase1 = exchange_write_base(j);
     const int Cc = static_cast<int>(a.n_ceps), M = static_cast<int>(a.n_filters);
     // the P row holds |2X|^2 or |2X|: the 1/4 or 1/2 of the untangle rides on the mel sums
     const float hscale = POW2 ? 0.25f : 0.5f;
@@ -207,9 +192,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
     for (int r = 0; r < 8; ++r) twn[r] = s_twn[r * 16 + j];
 
     while (quad < q_hi) {
-        unsigned next = 0;
-        if (lane == 0) next = atomicAdd(s_next, 1u);
-        next = __builtin_amdgcn_readfirstlane(next);
+        const unsigned next = claim_next(s_next, lane);
         const bool ok_cur = ok_next;
 
         // ---- conditioning stage (steps 1-5 of the specification) on the input registers ----
@@ -274,49 +257,24 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
             }
             energy = fmaxf(ln_floored(row16_sum(esum)), a.log_floor);  // steps 3 / 5 and 9
         }
-        // ---- 256-point complex FFT of the packed frame: radix-16, transpose through LDS, twiddle, radix-16 ----
-        fft16_reg(v);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) zh[wbase1 + 2 * r] = v[r];
-        wave_order();
+        // ---- 256-point complex FFT of the packed frame; the next quad's samples go into the dead input registers ----
+        pass1(v, zh, wbase1);
         if (next < q_hi) {
             const float *src = frame_src<VARLEN>(a, vl, next, total, f, cursor, ok_next);
             load_quad_k<NE, VARLEN>(src, ok_next, a.flen, j, vin);
         }
         float2 u[16];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const float4 t4 = *reinterpret_cast<const float4 *>(&zh[34 * p + 2 * j]);
-            u[2 * p] = make_float2(t4.x, t4.y);
-            u[2 * p + 1] = make_float2(t4.z, t4.w);
-        }
-        wave_order();
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const float4 w2 = s_tw2[p * 16 + j];
-            u[2 * p + 1] = cmul(u[2 * p + 1], make_float2(w2.x, w2.y));
-            if (p < 7) u[2 * p + 2] = cmul(u[2 * p + 2], make_float2(w2.z, w2.w));
-        }
-        fft16_reg(u);  // u[r] = Z[j + 16 r]
+        pass2(u, zh, j, s_tw2);
 
         // ---- untangle Z -> 2X; |2X|^2 or |2X| into the P row ----
         float2 zcs[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) zcs[r] = make_float2(bperm(paddr, u[15 - r].x), bperm(paddr, u[15 - r].y));
+        fetch_partners(u, paddr, zcs);
         float *prow = slot;
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const float2 zk = u[r];
-            // lane 0 pairs with itself: Z[256 - 16 r] = own register (16 - r) & 15
-            const float2 zc = j == 0 ? u[(16 - r) & 15] : zcs[r];
-            const float2 w = twn[r];
-            const float2 s = make_float2(zk.x + zc.x, zk.y - zc.y);  // 2 E[k]
-            const float2 d = make_float2(zk.x - zc.x, zk.y + zc.y);
-            // 2 X[k] = s - i w d, 2 conj X[256-k] = 2 s - 2 X[k]
-            const float xa_r = fmaf(w.y, d.x, fmaf(w.x, d.y, s.x));
-            const float xa_i = fmaf(w.y, d.y, fmaf(-w.x, d.x, s.y));
-            const float xb_r = fmaf(2.f, s.x, -xa_r), xb_i = fmaf(2.f, s.y, -xa_i);
-            const float na = fmaf(xa_r, xa_r, xa_i * xa_i), nb = fmaf(xb_r, xb_r, xb_i * xb_i);
+            const Bin b = untangle(u, zcs, twn[r], j, r);
+            const float xb_r = fmaf(2.f, b.s.x, -b.xr), xb_i = fmaf(2.f, b.s.y, -b.xi);  // 2 conj X[256-k]
+            const float na = fmaf(b.xr, b.xr, b.xi * b.xi), nb = fmaf(xb_r, xb_r, xb_i * xb_i);
             prow[j + 16 * r] = POW2 ? na : __builtin_amdgcn_sqrtf(na);
             prow[256 - j - 16 * r] = POW2 ? nb : __builtin_amdgcn_sqrtf(nb);  // (bin 256, the Nyquist bin, has no weight in the bank)
         }
@@ -333,12 +291,9 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
         {
             float *frow = slot + kPRowX;
             float m[5];
-            int off = 0;
+            mel_raw_sums(w4, prow, st, a.mel_q4, m);
 #pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                m[k] = ln_floored(hscale * mel_slot1(w4 + off, prow + st[k], a.mel_q4[k]));
-                off += a.mel_q4[k];
-            }
+            for (int k = 0; k < 5; ++k) m[k] = ln_floored(hscale * m[k]);
             const unsigned gf = quad * 4 + f;
             const bool store = gf < total && ok_cur;
             if (!MFCC) {
@@ -400,20 +355,14 @@ hipError_t launch_k(const KaldiArgs &a_in, const KaldiVarlenArgs &v, hipStream_t
     constexpr int WAVES = 12;
     KaldiArgs a = a_in;
     const unsigned long long total = VARLEN ? v.total_frames : static_cast<unsigned long long>(a.batch) * a.n_frames;
-    a.nf_magic = a.nf_shift = 0;
-    // floor(x / n_frames) by multiply-high where the kernel's one-wrap lane fix-up holds (n_frames >= 4); else it divides
-    if (!VARLEN && a.n_frames >= 4 && a.n_frames < (1u << 31) && total + 4 < (1ull << 31)) {
-        const FrameReciprocal r = frame_reciprocal(a.n_frames);
-        a.nf_magic = r.magic;
-        a.nf_shift = r.shift;
-    }
     if (a.flen <= 256 || a.flen > 512 || a.step == 0 || a.n_filters > 80 || a.n_ceps > 32) return hipErrorInvalidValue;
-    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloatsX + L::kMelW + 16 * static_cast<size_t>(a.mel_wpitch) + 512 + 4) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (total == 0) return hipSuccess;
-    if (total + 8 >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned grid = cu_capped_grid((total + 3) / 4, WAVES, num_cus);
-    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, grid, WAVES, lds, stream, info, a, v); };
+    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * static_cast<size_t>(a.mel_wpitch) + 512 + 4) * sizeof(float);
+    GroupPlan plan;
+    const PlanStatus ps = plan_groups(total, a.n_frames, 4, !VARLEN, lds, WAVES, num_cus, plan);
+    if (ps != PlanStatus::Launch) return ps == PlanStatus::Empty ? hipSuccess : hipErrorInvalidValue;
+    a.nf_magic = plan.nf_magic;
+    a.nf_shift = plan.nf_shift;
+    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, plan.grid, WAVES, lds, stream, info, a, v); };
     const bool pow2 = a.use_power != 0, mfcc = a.out_mfcc != 0;
 #define SS_K(NE, P, C, NAME) go(ss_kaldi_c256<NE, P, C, VARLEN, WAVES>, VARLEN ? NAME ",v>" : NAME ">")
 #define SS_KN(NE, TAG)                                                                                                     \

@@ -8,8 +8,7 @@
 //   * Row r of a clip covers the 512 samples that end at chunk r + n_pad (functions.rs:137-151): zero initial state,
 //     zero tail, rows past the real ones are all zero (D3).  Windows inside the clip load as 8-byte pairs at constant
 //     offsets; at the clip edges one masked range per lane.  Vorbis window pairs come from the table block in LDS.
-//   * FFT / untangle exactly as in ss_mfcc512.hip (radix-16, one transposing exchange through the row's wave-private
-//     2304-B slot, twiddle, radix-16; partner by ds_bpermute_b32).  |X|^2 wnorm^2 of bins 0..128 -- or all 257 when the
+//   * FFT / untangle: the shared quad skeleton of ss_quad256.h.  |X|^2 wnorm^2 of bins 0..128 -- or all 257 when the
 //     bank reaches past (F+1)/2 -- goes to a P row inside the slot.
 //   * banded mel, up to 5 filters per lane (80 filters), host-sorted by tap count; the four rows of a wave are adjacent
 //     words of out[clip][m][.].  No zero handling, no log (feature.rs:164-173).
@@ -18,6 +17,7 @@
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 #include "ss_internal.h"
+#include "ss_quad256.h"
 #include "ss_wave.h"
 
 namespace ss {
@@ -25,11 +25,9 @@ namespace ss {
 namespace {
 
 using namespace wv;
+using namespace q256;  // the slot holds, after the exchange, the P row [260]
 
 namespace L = mel512_layout;
-constexpr int kSlotFloatsE = 576;  // per row: exchange slot (288 float2); afterwards the P row [260]
-constexpr int kWaveFloatsE = 4 * kSlotFloatsE;
-
 
 template <int WAVES, bool STFT>
 __global__ __launch_bounds__(WAVES * 64) void ss_mel_c256(const Mel512Args a)
@@ -41,10 +39,10 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c256(const Mel512Args a)
     const int f = lane >> 4;  // row within the quad
     const int j = lane & 15;  // lane within the row (DPP row)
 
-    float *slot = reinterpret_cast<float *>(smem) + wave * kWaveFloatsE + f * kSlotFloatsE;
+    float *slot = reinterpret_cast<float *>(smem) + wave * kWaveFloats + f * kSlotFloats;
     float2 *zh = reinterpret_cast<float2 *>(slot);
     float *prow = slot;
-    float *s_tab = reinterpret_cast<float *>(smem) + WAVES * kWaveFloatsE;
+    float *s_tab = reinterpret_cast<float *>(smem) + WAVES * kWaveFloats;
     const float4 *s_tw2 = reinterpret_cast<const float4 *>(s_tab + L::kTw2);
     const float2 *s_twn = reinterpret_cast<const float2 *>(s_tab + L::kTwn);
     const float2 *s_win = reinterpret_cast<const float2 *>(s_tab + L::kWin);
@@ -59,11 +57,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c256(const Mel512Args a)
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * qpc;
     const unsigned u_lo = static_cast<unsigned>(units * blockIdx.x / gridDim.x);
     const unsigned u_hi = static_cast<unsigned>(units * (blockIdx.x + 1) / gridDim.x);
-    {
-        const int n4 = (L::kMelW + 16 * a.mel_wpitch) / 4;
-        for (int i = tid; i < n4; i += WAVES * 64) reinterpret_cast<float4 *>(s_tab)[i] = reinterpret_cast<const float4 *>(a.tab)[i];
-        if (tid == 0) *s_next = u_lo + WAVES;
-    }
+    stage_tables(s_tab, a.tab, (L::kMelW + 16 * a.mel_wpitch) / 4, tid, WAVES * 64);
+    if (tid == 0) *s_next = u_lo + WAVES;
     // (clip, row) of this lane group within a unit, and the loads of its window: functions.rs:137-151, the window covers
     // the last 512 samples ending at chunk r + n_pad
     auto load_unit = [&](unsigned un, float2 (&vv)[16]) {
@@ -106,8 +101,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c256(const Mel512Args a)
     float2 vin[16];
     if (unit < u_hi) load_unit(unit, vin);
 
-    const int paddr = ((lane & 48) | ((16 - j) & 15)) << 2;  // lane holding Z[256 - k]
-    const int wbase1 = 34 * (j >> 1) + (j & 1);              // exchange write base (float2 units)
+    const int paddr = partner_addr(lane, j), wbase1 = exchange_write_base(j);
     const float hs = 0.25f * a.scale * a.scale;              // |X wnorm|^2 = (wnorm^2 / 4) |2X|^2
     __syncthreads();
     int st[5], fi[5];
@@ -122,9 +116,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c256(const Mel512Args a)
     for (int r = 0; r < 8; ++r) twn[r] = s_twn[r * 16 + j];
 
     while (unit < u_hi) {
-        unsigned next = 0;
-        if (lane == 0) next = atomicAdd(s_next, 1u);
-        next = __builtin_amdgcn_readfirstlane(next);
+        const unsigned next = claim_next(s_next, lane);
         const unsigned clip = unit / qpc;
         const int r = static_cast<int>(unit - clip * qpc) * 4 + f;
 
@@ -134,27 +126,11 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c256(const Mel512Args a)
             const float2 w = s_win[j + 16 * e];
             v[e] = make_float2(vin[e].x * w.x, vin[e].y * w.y);
         }
-        // ---- 256-point complex FFT: radix-16, transpose through LDS, twiddle, radix-16 ----
-        fft16_reg(v);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) zh[wbase1 + 2 * q] = v[q];
-        wave_order();
+        // ---- 256-point complex FFT; the next unit's samples go into the dead window registers ----
+        pass1(v, zh, wbase1);
         if (next < u_hi) load_unit(next, vin);
         float2 u[16];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const float4 t4 = *reinterpret_cast<const float4 *>(&zh[34 * p + 2 * j]);
-            u[2 * p] = make_float2(t4.x, t4.y);
-            u[2 * p + 1] = make_float2(t4.z, t4.w);
-        }
-        wave_order();
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const float4 w2 = s_tw2[p * 16 + j];
-            u[2 * p + 1] = cmul(u[2 * p + 1], make_float2(w2.x, w2.y));
-            if (p < 7) u[2 * p + 2] = cmul(u[2 * p + 2], make_float2(w2.z, w2.w));
-        }
-        fft16_reg(u);  // u[q] = Z[j + 16 q]
+        pass2(u, zh, j, s_tw2);
 
         // ---- untangle Z -> X; (|X| wnorm)^2 (functions.rs:166-169 + feature.rs:164) ----
         // stft build (functions.rs:86-123, :166-169): X[k] * wnorm for all 257 bins of the row, interleaved re / im
@@ -162,19 +138,12 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c256(const Mel512Args a)
         if (STFT && r < R) srow = reinterpret_cast<float2 *>(a.out) + (static_cast<unsigned long long>(clip) * R + r) * 257ull;
         const float cs = 0.5f * a.scale;
         float2 zcs[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) zcs[q] = make_float2(bperm(paddr, u[15 - q].x), bperm(paddr, u[15 - q].y));
+        fetch_partners(u, paddr, zcs);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            const float2 zk = u[q];
-            // lane 0 pairs with itself: Z[256 - 16 q] = own register (16 - q) & 15
-            const float2 zc = j == 0 ? u[(16 - q) & 15] : zcs[q];
-            const float2 w = twn[q];
-            const float2 s = make_float2(zk.x + zc.x, zk.y - zc.y);  // 2 E[k]
-            const float2 d = make_float2(zk.x - zc.x, zk.y + zc.y);
-            // 2 X[k] = s - i w d, 2 conj X[256-k] = 2 s - 2 X[k]
-            const float xr = fmaf(w.y, d.x, fmaf(w.x, d.y, s.x));
-            const float xi = fmaf(w.y, d.y, fmaf(-w.x, d.x, s.y));
+            const Bin b = untangle(u, zcs, twn[q], j, q);  // the mirrored bin, 2 conj X[256-k] = 2 s - 2 X[k], only where it is wanted
+            const float xr = b.xr, xi = b.xi;
+            const float2 s = b.s;
             if (STFT) {
                 if (srow) {
                     srow[j + 16 * q] = make_float2(cs * xr, cs * xi);
@@ -226,8 +195,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c256(const Mel512Args a)
 hipError_t launch_mel_c256(const Mel512Args &a, hipStream_t stream, int num_cus, LaunchInfo *info)
 {
     constexpr int WAVES = 12;
-    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloatsE + L::kMelW + 4 + 16 * static_cast<size_t>(a.mel_wpitch)) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 4 + 16 * static_cast<size_t>(a.mel_wpitch)) * sizeof(float);
+    if (lds > kLdsLimit) return hipErrorInvalidValue;
     if (a.batch == 0 || a.rows == 0) return hipSuccess;
     const unsigned long long units = static_cast<unsigned long long>(a.batch) * ((a.rows + 3) / 4);
     if (units >= 0xffffffffull) return hipErrorInvalidValue;

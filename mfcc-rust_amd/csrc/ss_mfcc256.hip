@@ -12,10 +12,9 @@
 //     complex points per lane.  One persistent workgroup per CU, waves pull octs from an LDS counter, the next oct's
 //     samples are prefetched into the dead input registers.  Samples load as single floats (one per frame of the pair),
 //     so frame starts need no alignment.
-//   * FFT: radix-16, one transposing exchange through the pair's wave-private 2304-B slot (ds_write_b64 scatter to
-//     34*(n1>>1) + 2*k1 + (n1&1), ds_read_b128 back), twiddle, radix-16.  No workgroup barrier in the main loop.
-//   * Partner Z[256-k] by ds_bpermute_b32 (lane 16-j, register 15-r); all 129 bins of both frames go to P rows inside
-//     the slot (the exchange is over by then), so banks over the whole spectrum need no separate build.
+//   * FFT and partner fetch: the shared quad skeleton of ss_quad256.h (the split above replaces its untangle).  All 129
+//     bins of both frames go to P rows inside the slot (the exchange is over by then), so banks over the whole spectrum
+//     need no separate build.
 //   * banded mel (3 filters per lane, host-sorted by tap count), zero handling, ln -> (slot, lane)-ordered row; DCT-II as
 //     a 48-term product per lane with the lane's cosine row;
 //     reference scaling and column-0 replacement.  mfe builds stop after the mel stage.
@@ -23,6 +22,7 @@
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 #include "ss_internal.h"
+#include "ss_quad256.h"
 #include "ss_wave.h"
 
 namespace ss {
@@ -30,19 +30,16 @@ namespace ss {
 namespace {
 
 using namespace wv;
+using namespace q256;  // the slot holds, after the exchange, P rows [2][132] | ln(mel) rows [2][48]
 
 namespace L = mfcc256_layout;
-constexpr int kSlotFloats = 576;        // per frame pair: exchange slot (288 float2); afterwards P rows [2][132] | ln(mel) rows [2][48]
-constexpr int kWaveFloatsX = 4 * kSlotFloats;
-constexpr int kPRowX = 132;             // bins 0..128 + three zero pad bins
+constexpr int kPRowX = 132;            // bins 0..128 + three zero pad bins
 constexpr float kPairGuard = 1000.f;    // energy ratio (30 dB) beyond which the two frames of a pair are transformed one at a time
 // A pair transform leaves rounding noise of ~3e-7 of the pair's largest bin in EVERY bin of both frames.  A bin below
 // kTinyBin of that maximum (squared form: kTinyBin^2) -- in particular a bin that cancels exactly in a transform of its own
 // (full-scale square wave, pure tones on bin centres: the reference then has an exact 0 -> f32::EPSILON, functions.rs:66-71) --
 // would come out with a visible relative error, so an oct in which any pair has such a bin is run again, each frame alone.
 constexpr float kTinyBin = 1e-4f;
-
-
 
 // Issues the loads of one oct: vin[e] = (a[n], b[n]), n = j + 16 e, of this lane group's frame pair (zero beyond flen,
 // processing.rs:147-156).  Returns the pair's frame indices within their clips in tA / tB.
@@ -59,18 +56,7 @@ __device__ __forceinline__ void load_oct(const Mfcc256Args &a, unsigned oct, uns
     for (int s = 0; s < 2; ++s) {
         const unsigned fl = min(static_cast<unsigned>(2 * f + s), total - 1 - o8);  // lanes past the last frame redo it
         unsigned clip, t;
-        if (a.nf_magic) {
-            // scalar quotient of the oct's first frame (multiply-high by the host's reciprocal), one conditional wrap per lane
-            clip = __umulhi(o8, a.nf_magic) >> a.nf_shift;
-            t = o8 - clip * a.n_frames + fl;
-            const bool wrap = t >= a.n_frames;
-            t -= wrap ? a.n_frames : 0u;
-            clip += wrap ? 1u : 0u;
-        } else {
-            const unsigned gf = o8 + fl;
-            clip = gf / a.n_frames;
-            t = gf - clip * a.n_frames;
-        }
+        locate_frame(o8, fl, a.n_frames, a.nf_magic, a.nf_shift, clip, t);
         // stack_frames (processing.rs:65-129, contract framing): frame t starts at sample t*step
         xcl[s] = a.x + static_cast<unsigned long long>(clip) * a.ld;
         src[s] = xcl[s] + static_cast<unsigned long long>(t) * a.step + j;
@@ -99,9 +85,9 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256x2(const Mfcc256Args a
     const int f = lane >> 4;  // frame pair within the oct
     const int j = lane & 15;  // lane within the pair (DPP row)
 
-    float *slot = reinterpret_cast<float *>(smem) + wave * kWaveFloatsX + f * kSlotFloats;
+    float *slot = reinterpret_cast<float *>(smem) + wave * kWaveFloats + f * kSlotFloats;
     float2 *zh = reinterpret_cast<float2 *>(slot);
-    float *s_tab = reinterpret_cast<float *>(smem) + WAVES * kWaveFloatsX;
+    float *s_tab = reinterpret_cast<float *>(smem) + WAVES * kWaveFloats;
     const float4 *s_tw2 = reinterpret_cast<const float4 *>(s_tab + L::kTw2);
     const float *s_cos = s_tab + L::kCos;
     const int *s_start = reinterpret_cast<const int *>(s_tab + L::kStart);
@@ -114,19 +100,15 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256x2(const Mfcc256Args a
     const unsigned octs = (total + 7) / 8;
     const unsigned o_lo = static_cast<unsigned>(static_cast<unsigned long long>(octs) * blockIdx.x / gridDim.x);
     const unsigned o_hi = static_cast<unsigned>(static_cast<unsigned long long>(octs) * (blockIdx.x + 1) / gridDim.x);
-    {
-        const int n4 = (L::kMelW + 16 * a.mel_wpitch + (WIN ? 256 : 0)) / 4;
-        for (int i = tid; i < n4; i += WAVES * 64) reinterpret_cast<float4 *>(s_tab)[i] = reinterpret_cast<const float4 *>(a.tab)[i];
-        if (tid == 0) *s_next = o_lo + WAVES;
-    }
+    stage_tables(s_tab, a.tab, (L::kMelW + 16 * a.mel_wpitch + (WIN ? 256 : 0)) / 4, tid, WAVES * 64);
+    if (tid == 0) *s_next = o_lo + WAVES;
     unsigned oct = __builtin_amdgcn_readfirstlane(o_lo + wave);  // uniform: kept scalar
     float2 vin[NE];
     unsigned tA_next = 0, tB_next = 0;
     const bool pre = a.preemph != 0.f;  // pre-emphasised samples are formed at load time: no prefetch across the iteration then
     if (!pre && oct < o_hi) load_oct<NE>(a, oct, total, f, j, vin, tA_next, tB_next);
 
-    const int paddr = ((lane & 48) | ((16 - j) & 15)) << 2;  // lane holding Z[256 - k]
-    const int wbase1 = 34 * (j >> 1) + (j & 1);              // exchange write base (float2 units)
+    const int paddr = partner_addr(lane, j), wbase1 = exchange_write_base(j);
     const int Cc = static_cast<int>(a.n_ceps), M = static_cast<int>(a.n_filters);
     // |2A| = |s|: the 1/2 of the untangle is folded into the scale (1/4 for the squared form)
     const float hscale32 = (POW2 ? 0.25f * a.scale : 0.5f * a.scale) * kTwo32;
@@ -160,8 +142,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256x2(const Mfcc256Args a
             next = held;
             held = kNone;
         } else {
-            if (lane == 0) next = atomicAdd(s_next, 1u);
-            next = __builtin_amdgcn_readfirstlane(next);
+            next = claim_next(s_next, lane);
         }
         if (pre) load_oct<NE>(a, oct, total, f, j, vin, tA_next, tB_next);
         const unsigned tA = tA_next, tB = tB_next;
@@ -191,40 +172,21 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256x2(const Mfcc256Args a
             if (WIN && e < NE) s = make_float2(s.x * wn[e], s.y * wn[e]);
             v[e] = s;
         }
-        // ---- 256-point complex FFT of a + i b: radix-16, transpose through LDS, twiddle, radix-16 ----
-        fft16_reg(v);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) zh[wbase1 + 2 * r] = v[r];
-        wave_order();
+        // ---- 256-point complex FFT of a + i b ----
+        pass1(v, zh, wbase1);
         if (!pre && pass == npass - 1 && next < o_hi) load_oct<NE>(a, next, total, f, j, vin, tA_next, tB_next);  // the input registers are dead now
         float2 u[16];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const float4 t4 = *reinterpret_cast<const float4 *>(&zh[34 * p + 2 * j]);
-            u[2 * p] = make_float2(t4.x, t4.y);
-            u[2 * p + 1] = make_float2(t4.z, t4.w);
-        }
-        wave_order();
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const float4 w2 = RES_TW ? tw2r[RES_TW ? p : 0] : s_tw2[p * 16 + j];
-            u[2 * p + 1] = cmul(u[2 * p + 1], make_float2(w2.x, w2.y));
-            if (p < 7) u[2 * p + 2] = cmul(u[2 * p + 2], make_float2(w2.z, w2.w));
-        }
-        fft16_reg(u);  // u[r] = Z[j + 16 r]
+        pass2<RES_TW>(u, zh, j, RES_TW ? tw2r : s_tw2);
 
         // ---- split Z into the two frames' spectra; |X| (processing.rs:168) * 1/N (:180); row sums (feature.rs:216) ----
         float2 zcs[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) zcs[r] = make_float2(bperm(paddr, u[15 - r].x), bperm(paddr, u[15 - r].y));
+        fetch_partners(u, paddr, zcs);
         float *prA = slot, *prB = slot + kPRowX;
         float esA = 0.f, esB = 0.f;
         float pmin = 3.0e38f, pmax = 0.f;  // smallest and largest bin of the pair (both frames)
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const float2 zk = u[r];
-            // lane 0 pairs with itself: Z[256 - 16 r] = own register (16 - r) & 15
-            const float2 zc = j == 0 ? u[(16 - r) & 15] : zcs[r];
+            const float2 zk = u[r], zc = partner(u, zcs, j, r);
             const float sx = zk.x + zc.x, sy = zk.y - zc.y;  // 2 A[k]
             const float dx = zk.x - zc.x, dy = zk.y + zc.y;  // 2 i B[k]
             const float na = fmaf(sx, sx, sy * sy), nb = fmaf(dx, dx, dy * dy);
@@ -276,12 +238,11 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256x2(const Mfcc256Args a
             const float *pr = slot + s * kPRowX;
             float *frow = slot + 2 * kPRowX + 48 * s;
             float m[3];
-            int off = 0;
+            mel_raw_sums(w4, pr, st, a.mel_q4, m);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                m[k] = hscale32 * mel_slot1(w4 + off, pr + st[k], a.mel_q4[k]);
+                m[k] = hscale32 * m[k];
                 m[k] = m[k] == 0.f ? kEps * kTwo32 : m[k];
-                off += a.mel_q4[k];
             }
             const unsigned gf = oct * 8 + 2 * f + s;
             if (MFE) {
@@ -361,19 +322,13 @@ hipError_t launch_x(const Mfcc256Args &a_in, hipStream_t stream, int num_cus, La
 {
     Mfcc256Args a = a_in;
     const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
-    a.nf_magic = a.nf_shift = 0;
-    // floor(x / n_frames) by multiply-high where the kernel's one-wrap lane fix-up holds (n_frames >= 8); else it divides
-    if (a.n_frames >= 8 && a.n_frames < (1u << 31) && total + 8 < (1ull << 31)) {
-        const FrameReciprocal r = frame_reciprocal(a.n_frames);
-        a.nf_magic = r.magic;
-        a.nf_shift = r.shift;
-    }
-    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloatsX + L::kMelW + 16 * static_cast<size_t>(a.mel_wpitch) + (a.windowed ? 256 : 0) + 4) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (total == 0) return hipSuccess;
-    if (total + 8 >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned grid = cu_capped_grid((total + 7) / 8, WAVES, num_cus);
-    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, grid, WAVES, lds, stream, info, a); };
+    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * static_cast<size_t>(a.mel_wpitch) + (a.windowed ? 256 : 0) + 4) * sizeof(float);
+    GroupPlan plan;
+    const PlanStatus ps = plan_groups(total, a.n_frames, 8, true, lds, WAVES, num_cus, plan);
+    if (ps != PlanStatus::Launch) return ps == PlanStatus::Empty ? hipSuccess : hipErrorInvalidValue;
+    a.nf_magic = plan.nf_magic;
+    a.nf_shift = plan.nf_shift;
+    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, plan.grid, WAVES, lds, stream, info, a); };
     const bool pow2 = a.spectrum_exponent == 2, win = a.windowed != 0;
 #define SS_X(NE, P, M, W, NAME) go(ss_mfcc_c256x2<NE, P, M, W, WAVES>, NAME)
 #define SS_XN(NE, TAG)                                                                                                                          \

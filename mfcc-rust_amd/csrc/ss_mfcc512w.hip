@@ -5,9 +5,8 @@
 //   * Work unit: a QUAD of 4 consecutive frames of the flat frame list; 16 lanes (one DPP row) own a frame = 256 packed
 //     complex points, 16 per lane.  One persistent 12-wave workgroup per CU, quads from an LDS counter, the next quad's
 //     samples prefetched into the dead input registers.  Zero padding is compile-time (template NE).
-//   * FFT / untangle exactly as in ss_mfcc512.hip (radix-16, one transposing exchange through the frame's wave-private
-//     2304-B slot, twiddle, radix-16; partner Z[256-k] by ds_bpermute_b32).  All 257 bins go to the P row inside the slot
-//     and to the frame energy.
+//   * FFT / untangle: the shared quad skeleton of ss_quad256.h.  All 257 bins go to the P row inside the slot and to the
+//     frame energy.
 //   * banded mel, five filters per lane (host-sorted by tap count), zero handling, ln -> (slot, lane)-ordered row of 80;
 //     DCT-II as an 80-term product per lane with the lane's cosine row; reference scaling and column-0 replacement.
 //     mfe builds stop after the mel stage.  Optional frame window from the table block; centred frames (librosa
@@ -17,6 +16,7 @@
 #include "ss_device.h"
 #include "ss_fft_reg.h"
 #include "ss_internal.h"
+#include "ss_quad256.h"
 #include "ss_wave.h"
 
 namespace ss {
@@ -24,13 +24,10 @@ namespace ss {
 namespace {
 
 using namespace wv;
+using namespace q256;  // the slot holds, after the exchange, P row [260] | ln(mel) row [80]
 
 namespace L = mfcc512w_layout;
-constexpr int kSlotFloats = 576;        // per frame: exchange slot (288 float2); afterwards P row [260] | ln(mel) row [80]
-constexpr int kWaveFloatsX = 4 * kSlotFloats;
 constexpr int kPRowX = 260;             // bins 0..256 + three zero pad bins
-
-
 
 // Issues the loads of one quad: vin[e] = (x[2n], x[2n+1]), n = j + 16 e, of this lane group's frame (zero beyond flen,
 // processing.rs:147-156).  Returns the frame's index within its clip.
@@ -40,18 +37,7 @@ __device__ __forceinline__ unsigned load_quad_w(const Mfcc256Args &a, unsigned q
     const unsigned q4 = quad * 4;  // uniform
     const unsigned fl = min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last frame redo it
     unsigned clip, t;
-    if (a.nf_magic) {
-        // scalar quotient of the quad's first frame (multiply-high by the host's reciprocal), one conditional wrap per lane
-        clip = __umulhi(q4, a.nf_magic) >> a.nf_shift;
-        t = q4 - clip * a.n_frames + fl;
-        const bool wrap = t >= a.n_frames;
-        t -= wrap ? a.n_frames : 0u;
-        clip += wrap ? 1u : 0u;
-    } else {
-        const unsigned gf = q4 + fl;
-        clip = gf / a.n_frames;
-        t = gf - clip * a.n_frames;
-    }
+    locate_frame(q4, fl, a.n_frames, a.nf_magic, a.nf_shift, clip, t);
     const float *xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
     const bool pre = a.preemph != 0.f;  // fused pre-emphasis: the caller then loads at the top of the loop (no prefetch)
     const unsigned sh = a.preemph_shift % a.n_samples;
@@ -105,9 +91,9 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256w(const Mfcc256Args a)
     const int f = lane >> 4;  // frame within the quad
     const int j = lane & 15;  // lane within the frame (DPP row)
 
-    float *slot = reinterpret_cast<float *>(smem) + wave * kWaveFloatsX + f * kSlotFloats;
+    float *slot = reinterpret_cast<float *>(smem) + wave * kWaveFloats + f * kSlotFloats;
     float2 *zh = reinterpret_cast<float2 *>(slot);
-    float *s_tab = reinterpret_cast<float *>(smem) + WAVES * kWaveFloatsX;
+    float *s_tab = reinterpret_cast<float *>(smem) + WAVES * kWaveFloats;
     const float4 *s_tw2 = reinterpret_cast<const float4 *>(s_tab + L::kTw2);
     const float2 *s_twn = reinterpret_cast<const float2 *>(s_tab + L::kTwn);
     const float *s_cos = s_tab + L::kCos;
@@ -121,19 +107,15 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256w(const Mfcc256Args a)
     const unsigned quads = (total + 3) / 4;
     const unsigned q_lo = static_cast<unsigned>(static_cast<unsigned long long>(quads) * blockIdx.x / gridDim.x);
     const unsigned q_hi = static_cast<unsigned>(static_cast<unsigned long long>(quads) * (blockIdx.x + 1) / gridDim.x);
-    {
-        const int n4 = (L::kMelW + 16 * a.mel_wpitch + (WIN ? 512 : 0)) / 4;
-        for (int i = tid; i < n4; i += WAVES * 64) reinterpret_cast<float4 *>(s_tab)[i] = reinterpret_cast<const float4 *>(a.tab)[i];
-        if (tid == 0) *s_next = q_lo + WAVES;
-    }
+    stage_tables(s_tab, a.tab, (L::kMelW + 16 * a.mel_wpitch + (WIN ? 512 : 0)) / 4, tid, WAVES * 64);
+    if (tid == 0) *s_next = q_lo + WAVES;
     unsigned quad = __builtin_amdgcn_readfirstlane(q_lo + wave);  // uniform: kept scalar
     float2 vin[NE];
     unsigned t_next = 0;
     const bool pre = a.preemph != 0.f;  // pre-emphasised samples are formed at load time: no prefetch across the iteration then
     if (!pre && quad < q_hi) t_next = load_quad_w<NE>(a, quad, total, f, j, vin);
 
-    const int paddr = ((lane & 48) | ((16 - j) & 15)) << 2;  // lane holding Z[256 - k]
-    const int wbase1 = 34 * (j >> 1) + (j & 1);              // exchange write base (float2 units)
+    const int paddr = partner_addr(lane, j), wbase1 = exchange_write_base(j);
     const int Cc = static_cast<int>(a.n_ceps), M = static_cast<int>(a.n_filters);
     // |X| = (1/2)|2X|: the 1/2 of the untangle is folded into the scale (1/4 for the squared form)
     const float hscale32 = (POW2 ? 0.25f * a.scale : 0.5f * a.scale) * kTwo32;
@@ -151,9 +133,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256w(const Mfcc256Args a)
     for (int r = 0; r < 8; ++r) twn[r] = s_twn[r * 16 + j];
 
     while (quad < q_hi) {
-        unsigned next = 0;
-        if (lane == 0) next = atomicAdd(s_next, 1u);
-        next = __builtin_amdgcn_readfirstlane(next);
+        const unsigned next = claim_next(s_next, lane);
         if (pre) t_next = load_quad_w<NE>(a, quad, total, f, j, vin);
         const unsigned t_cur = t_next;
 
@@ -167,47 +147,22 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256w(const Mfcc256Args a)
             }
             v[e] = s;
         }
-        // ---- 256-point complex FFT of the packed frame: radix-16, transpose through LDS, twiddle, radix-16 ----
-        fft16_reg(v);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) zh[wbase1 + 2 * r] = v[r];
-        wave_order();
+        // ---- 256-point complex FFT of the packed frame; the next quad's samples go into the dead input registers ----
+        pass1(v, zh, wbase1);
         if (!pre && next < q_hi) t_next = load_quad_w<NE>(a, next, total, f, j, vin);
         float2 u[16];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const float4 t4 = *reinterpret_cast<const float4 *>(&zh[34 * p + 2 * j]);
-            u[2 * p] = make_float2(t4.x, t4.y);
-            u[2 * p + 1] = make_float2(t4.z, t4.w);
-        }
-        wave_order();
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const float4 w2 = s_tw2[p * 16 + j];
-            u[2 * p + 1] = cmul(u[2 * p + 1], make_float2(w2.x, w2.y));
-            if (p < 7) u[2 * p + 2] = cmul(u[2 * p + 2], make_float2(w2.z, w2.w));
-        }
-        fft16_reg(u);  // u[r] = Z[j + 16 r]
+        pass2(u, zh, j, s_tw2);
 
         // ---- untangle Z -> X; |X| (processing.rs:168) * 1/N (:180); row sum (feature.rs:216) ----
         float2 zcs[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) zcs[r] = make_float2(bperm(paddr, u[15 - r].x), bperm(paddr, u[15 - r].y));
+        fetch_partners(u, paddr, zcs);
         float *prow = slot;
         float esum = 0.f;
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const float2 zk = u[r];
-            // lane 0 pairs with itself: Z[256 - 16 r] = own register (16 - r) & 15
-            const float2 zc = j == 0 ? u[(16 - r) & 15] : zcs[r];
-            const float2 w = twn[r];
-            const float2 s = make_float2(zk.x + zc.x, zk.y - zc.y);  // 2 E[k]
-            const float2 d = make_float2(zk.x - zc.x, zk.y + zc.y);
-            // 2 X[k] = s - i w d, 2 conj X[256-k] = 2 s - 2 X[k]
-            const float xa_r = fmaf(w.y, d.x, fmaf(w.x, d.y, s.x));
-            const float xa_i = fmaf(w.y, d.y, fmaf(-w.x, d.x, s.y));
-            const float xb_r = fmaf(2.f, s.x, -xa_r), xb_i = fmaf(2.f, s.y, -xa_i);
-            const float na = fmaf(xa_r, xa_r, xa_i * xa_i), nb = fmaf(xb_r, xb_r, xb_i * xb_i);
+            const Bin b = untangle(u, zcs, twn[r], j, r);
+            const float xb_r = fmaf(2.f, b.s.x, -b.xr), xb_i = fmaf(2.f, b.s.y, -b.xi);  // 2 conj X[256-k]
+            const float na = fmaf(b.xr, b.xr, b.xi * b.xi), nb = fmaf(xb_r, xb_r, xb_i * xb_i);
             const float pa = POW2 ? na : __builtin_amdgcn_sqrtf(na);  // unscaled; hscale is applied to the sums below
             const float pb = POW2 ? nb : __builtin_amdgcn_sqrtf(nb);
             prow[j + 16 * r] = pa;
@@ -231,12 +186,11 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c256w(const Mfcc256Args a)
         {
             float *frow = slot + kPRowX;
             float m[5];
-            int off = 0;
+            mel_raw_sums(w4, prow, st, a.mel_q4, m);
 #pragma unroll
             for (int k = 0; k < 5; ++k) {
-                m[k] = hscale32 * mel_slot1(w4 + off, prow + st[k], a.mel_q4[k]);
+                m[k] = hscale32 * m[k];
                 m[k] = m[k] == 0.f ? kEps * kTwo32 : m[k];
-                off += a.mel_q4[k];
             }
             const unsigned gf = quad * 4 + f;
             if (MFE) {
@@ -318,19 +272,13 @@ hipError_t launch_w5(const Mfcc256Args &a_in, hipStream_t stream, int num_cus, L
 {
     Mfcc256Args a = a_in;
     const unsigned long long total = static_cast<unsigned long long>(a.batch) * a.n_frames;
-    a.nf_magic = a.nf_shift = 0;
-    // floor(x / n_frames) by multiply-high where the kernel's one-wrap lane fix-up holds (n_frames >= 4); else it divides
-    if (a.n_frames >= 4 && a.n_frames < (1u << 31) && total + 4 < (1ull << 31)) {
-        const FrameReciprocal r = frame_reciprocal(a.n_frames);
-        a.nf_magic = r.magic;
-        a.nf_shift = r.shift;
-    }
-    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloatsX + L::kMelW + 16 * static_cast<size_t>(a.mel_wpitch) + (a.windowed ? 512 : 0) + 4) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (total == 0) return hipSuccess;
-    if (total + 8 >= 0xffffffffull) return hipErrorInvalidValue;
-    const unsigned grid = cu_capped_grid((total + 3) / 4, WAVES, num_cus);
-    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, grid, WAVES, lds, stream, info, a); };
+    const size_t lds = (static_cast<size_t>(WAVES) * kWaveFloats + L::kMelW + 16 * static_cast<size_t>(a.mel_wpitch) + (a.windowed ? 512 : 0) + 4) * sizeof(float);
+    GroupPlan plan;
+    const PlanStatus ps = plan_groups(total, a.n_frames, 4, true, lds, WAVES, num_cus, plan);
+    if (ps != PlanStatus::Launch) return ps == PlanStatus::Empty ? hipSuccess : hipErrorInvalidValue;
+    a.nf_magic = plan.nf_magic;
+    a.nf_shift = plan.nf_shift;
+    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, plan.grid, WAVES, lds, stream, info, a); };
     const bool pow2 = a.spectrum_exponent == 2, win = a.windowed != 0;
 #define SS_W(NE, P, M, W, NAME) go(ss_mfcc_c256w<NE, P, M, W, WAVES>, NAME)
 #define SS_WN(NE, TAG)                                                                                                                          \

@@ -2,7 +2,9 @@
 tools/hosttest/test_launch_plan.cpp includes that header alone and checks that the multiply-high reciprocal of n_frames divides
 exactly (every d in 2..4096, a few thousand random d < 2^31, x at the edges of the quotient steps and at random), that the
 CU-capped grid and the unit split keep their invariants, that the quad_src address-range test flips at its three boundaries and
-that the plans of the headline shapes are the literal ones worked out by hand."""
+that the plans of the headline shapes are the literal ones worked out by hand.  It also includes ss_quad256.h, whose host part is
+the quad kernels' frame locate and launch plan: locate_frame against plain division for groups of 4 and 8 frames at and next to
+the clip boundaries, with the reciprocal exactly where plan_groups enables it."""
 import os
 import shutil
 import subprocess

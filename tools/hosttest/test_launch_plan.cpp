@@ -1,10 +1,12 @@
 // Host-side check of the launch arithmetic in mfcc-rust_amd/csrc/ss_launch_plan.h (no GPU, no HIP header): the multiply-high
 // reciprocal divides exactly, the CU-capped grid and the unit split keep their invariants, the quad_src address-range test flips
-// at its three boundaries, and the plans of the headline shapes are the pinned ones.  tests/test_launch_plan.py builds it with
+// at its three boundaries, the plans of the headline shapes are the pinned ones, and the quad kernels' shared frame locate and
+// launch plan (the plain C++ part of ss_quad256.h) agree with plain division.  tests/test_launch_plan.py builds it with
 // AddressSanitizer + UBSan and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -Imfcc-rust_amd/csrc
 //       tools/hosttest/test_launch_plan.cpp -o /tmp/lp && /tmp/lp
 #include "ss_launch_plan.h"
+#include "ss_quad256.h"
 
 #include <cstdio>
 #include <initializer_list>
@@ -139,8 +141,77 @@ static void check_pinned()
     }
 }
 
+// locate_frame of ss_quad256.h, the frame locate the quad kernels share, against plain division: with the reciprocal exactly where
+// plan_groups enables it (n_frames >= group, n_frames < 2^31, total + group < 2^31) and with the dividing fallback elsewhere.
+// Group starts: the first groups, the last ones, and every group at or next to a clip boundary of the first and last clips.
+static void check_locate(uint32_t n_frames, unsigned group)
+{
+    const uint64_t room = kTwo31 - group - 1;  // the largest total with a reciprocal
+    const uint64_t batches[] = {1, 2, 3, 1000, room / n_frames, room / n_frames + 1};
+    for (uint64_t batch : batches) {
+        const uint64_t total = batch * n_frames;
+        if (batch == 0 || total + 8 >= 0xffffffffull) continue;
+        ss::q256::GroupPlan p;
+        const ss::q256::PlanStatus st = ss::q256::plan_groups(total, n_frames, group, true, 1024, 12, 256, p);
+        const bool want_magic = n_frames >= group && total + group < kTwo31;
+        CHECK(st == ss::q256::PlanStatus::Launch && (p.nf_magic != 0) == want_magic && p.grid == ss::cu_capped_grid((total + group - 1) / group, 12, 256),
+              "n_frames %u x %llu, group %u: status %d magic %u grid %u", n_frames, (unsigned long long)batch, group, static_cast<int>(st), p.nf_magic, p.grid);
+        if (want_magic) {
+            const ss::FrameReciprocal r = ss::frame_reciprocal(n_frames);
+            CHECK(p.nf_magic == r.magic && p.nf_shift == r.shift, "n_frames %u: magic %u shift %u", n_frames, p.nf_magic, p.nf_shift);
+        }
+        ss::q256::GroupPlan packed;
+        ss::q256::plan_groups(total, n_frames, group, false, 1024, 12, 256, packed);
+        CHECK(packed.nf_magic == 0 && packed.grid == p.grid, "a packed launch takes no reciprocal");
+        const uint64_t groups = (total + group - 1) / group;
+        auto check_group = [&](uint64_t gi) {
+            if (gi >= groups) return;
+            const uint32_t first = static_cast<uint32_t>(gi * group);
+            for (uint32_t fl = 0; fl < group && first + static_cast<uint64_t>(fl) < total; ++fl) {
+                uint32_t clip = ~0u, t = ~0u;
+                ss::q256::locate_frame(first, fl, n_frames, p.nf_magic, p.nf_shift, clip, t);
+                const uint32_t g = first + fl;
+                CHECK(clip == g / n_frames && t == g % n_frames, "frame %u of %u-frame clips (group %u, magic %u): clip %u t %u", g, n_frames, group,
+                      p.nf_magic, clip, t);
+            }
+        };
+        for (uint64_t gi = 0; gi < 40; ++gi) check_group(gi);
+        for (uint64_t gi = groups > 40 ? groups - 40 : 0; gi < groups; ++gi) check_group(gi);
+        const uint64_t clips[] = {1, 2, 3, batch / 2, batch - 2, batch - 1, batch};
+        for (uint64_t c : clips) {
+            if (c > batch) continue;
+            const uint64_t at = c * n_frames / group;  // the group that holds (or ends at) the boundary, and its neighbours
+            for (uint64_t gi = at >= 2 ? at - 2 : 0; gi <= at + 2; ++gi) check_group(gi);
+        }
+    }
+}
+
+static void check_plan_status()
+{
+    using namespace ss::q256;
+    GroupPlan p;
+    CHECK(plan_groups(400, 100, 4, true, kLdsLimit, 12, 256, p) == PlanStatus::Launch && p.grid == 9, "LDS at the limit");
+    CHECK(plan_groups(400, 100, 4, true, kLdsLimit + 1, 12, 256, p) == PlanStatus::Invalid, "LDS beyond the limit");
+    CHECK(plan_groups(0, 100, 4, true, kLdsLimit + 1, 12, 256, p) == PlanStatus::Invalid, "the LDS check comes before the empty launch");
+    CHECK(plan_groups(0, 100, 4, true, 1024, 12, 256, p) == PlanStatus::Empty && p.grid == 0, "no frames");
+    CHECK(plan_groups(0xffffffffull - 9, 1, 8, true, 1024, 12, 256, p) == PlanStatus::Launch && p.nf_magic == 0, "the largest total");
+    CHECK(plan_groups(0xffffffffull - 8, 1, 8, true, 1024, 12, 256, p) == PlanStatus::Invalid, "total + 8 reaches 2^32 - 1");
+    // the reciprocal's three conditions, each at its edge (group 4 and 8)
+    for (unsigned group : {4u, 8u}) {
+        CHECK(plan_groups(10ull * (group - 1), group - 1, group, true, 1024, 12, 256, p) == PlanStatus::Launch && p.nf_magic == 0, "n_frames < group");
+        CHECK(plan_groups(10ull * group, group, group, true, 1024, 12, 256, p) == PlanStatus::Launch && p.nf_magic != 0, "n_frames == group");
+        CHECK(plan_groups(kTwo31 - group - 1, static_cast<uint32_t>(kTwo31 - group - 1), group, true, 1024, 12, 256, p) == PlanStatus::Launch && p.nf_magic != 0,
+              "total + group == 2^31 - 1");
+        CHECK(plan_groups(kTwo31 - group, static_cast<uint32_t>(kTwo31 - group), group, true, 1024, 12, 256, p) == PlanStatus::Launch && p.nf_magic == 0,
+              "total + group == 2^31");
+    }
+}
+
 int main()
 {
+    for (unsigned group : {4u, 8u})
+        for (uint32_t n : {1u, 3u, 4u, 5u, 7u, 8u, 9u, 98u, static_cast<uint32_t>(kTwo31 - 1)}) check_locate(n, group);
+    check_plan_status();
     for (uint32_t d = 2; d <= 4096; ++d) check_reciprocal(d);
     for (int i = 0; i < 4000; ++i) check_reciprocal(2 + static_cast<uint32_t>(rnd() % (kTwo31 - 2)));
     for (int s = 2; s < 31; ++s)
