@@ -1002,7 +1002,8 @@ int ss_resample_stream_flush(const ss_resampler *rs, size_t n_active, const int3
  *   10. MFCC: c[k] = lift[k] sum_b D[k][b] fbank[b], k < num_ceps; D[0][b] = sqrt(1/M), D[k][b] = sqrt(2/M) cos(pi/M (b + 0.5) k);
  *       lift[k] = 1 + 0.5 Q sin(pi k / Q), Q = cepstral_lifter (Q == 0: no lifter), folded into the host table; use_energy: c[0] = the
  *       log energy.
- * Not in this version: _i16 entry points (use input_scale = 32768 on normalised floats, or feed integer-valued floats), stream pools,
+ * Stream pools, fed floats or 16-bit PCM: the ss_kstream_* section below.
+ * Not in this version: one-shot _i16 entry points (use input_scale = 32768 on normalised floats, or feed integer-valued floats),
  * snip_edges = false, non-zero dither, VTLN, htk_compat, subtract_mean (ss_cmvn_packed does that), N != 512. */
 enum {
     SS_KALDI_WINDOW_POVEY = 0,
@@ -1090,6 +1091,67 @@ int ss_kaldi_fbank_packed(const ss_kaldi_config *cfg, const float *x, size_t n_c
 int ss_kaldi_mfcc_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
                                 const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream);
 int ss_kaldi_mfcc_packed(const ss_kaldi_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out);
+
+/* ---- ss_kstream_*: the Kaldi front end over a pool of stream states (live audio) -----------------------------------
+ * The online form of ss_kaldi_fbank / ss_kaldi_mfcc, on the tables of the other stream pools (ss_resample_stream_packed*,
+ * ss_cmvn_stream_packed*, ss_add_deltas_stream_packed*): one set of sample_offsets / row_offsets / slots serves the whole chain
+ * (INTEGRATION.md).  The handle is an ss_kaldi_config; the arithmetic is the ss_kaldi_* specification above, on the same kernel body.
+ * Sizes: flen and shift from ss_kaldi_sizes; D = ceil(flen / shift) - 1 is the delay in rows (0 where shift >= flen) and S = D * shift
+ *   the carried samples per stream (ss_kstream_state_len; 16 kHz, 25 / 10 ms: D = 2, S = 320).  S is a whole number of hops, not
+ *   flen - shift: only then do a stream's rows land on Kaldi's own frame grid.
+ * Pool: a caller-owned [pool_streams x S] block of floats.  An all-zero row is a fresh stream; zeroing a row resets it.  S == 0 allows
+ *   a NULL pool.
+ * Entries (the rules of ss_mfcc_stream_packed*): a call serves n_active entries.  Entry i's chunk is x[so[i] : so[i+1]], R_i = n_i /
+ *   shift whole hops (R_i = 0 is legal); its state is pool row slots[i]; its rows are rows ro[i] .. ro[i+1] of the packed output
+ *   (ss_kstream_row_offsets); total_rows >= ro[n_active], rows past ro[n_active] are left alone.  Row t of an entry is the Kaldi frame
+ *   of length flen that starts at chunk sample t * shift - S, a sample at position p < 0 being pool[slot * S + S + p].  Afterwards the
+ *   pool row is the last S samples of (old row ++ chunk).
+ * Equivalence: all of a stream's rows over all calls, however the stream was cut into calls, are bit for bit the rows (and the log
+ *   energy) of ss_kaldi_fbank_device / ss_kaldi_mfcc_device on zeros(S) ++ stream, whatever else shares the call and whatever the
+ *   entry's place or slot.  Every per-frame stage of the specification (DC removal, pre-emphasis from the frame's own first sample,
+ *   window) is frame-local, and a clip of K hops has exactly K - D offline frames: with the first D rows after a reset dropped, the
+ *   rows are ss_kaldi_fbank / ss_kaldi_mfcc of the stream itself.  THE FIRST D ROWS AFTER A RESET ARE WARM-UP ROWS over the zero
+ *   prefix.  A caller who chains CMVN behind the call primes a new stream: its first D hops go through a call of their own whose
+ *   rows are discarded, and in the chained call that stream is an R_i = 0 entry.
+ * Containment: the skip rules are the frame pool's.  A bad entry (not whole hops, ro inconsistent, ro[i+1] > total_rows, slot outside
+ *   the pool) is skipped by both launches -- its rows and its pool row stay untouched -- and raises the handle's error word:
+ *   SS_ERR_DEVICE once, through ss_kaldi_config_device_status or the next call on the handle.  Nothing is read outside the entries'
+ *   chunk ranges and the named pool rows; nothing is written outside rows [0, total_rows) and the named pool rows.
+ * Arguments: n_active == 0 is SS_OK with no launch.  SS_ERR_ARG, with nothing touched, for null buffers, sizes >= 2^31, a pool range
+ *   that overlaps an output, and a handle with num_ceps == 0 on the MFCC calls.  The host forms check the tables first and name the
+ *   first bad entry (ss_kstream_row_offsets' rules: so[0] == 0, no decreasing pair, whole hops), reject duplicate slots, and write
+ *   the caller's pool only after everything else succeeded.
+ * shift of either parity is served: S, so[i] and a row's first sample may be odd.
+ * _i16 forms: sample = (float)pcm * scale, scale a power of two in [2^-64, 2^64] (else SS_ERR_ARG); input_scale still applies
+ *   afterwards.  The results are bit for bit the float call on the converted samples; the pool stays float, so a stream may alternate
+ *   between PCM and float chunks.  The device forms need 2-byte alignment of d_x only.
+ * The device forms are a linear chain of two launches on `stream` (one where S == 0) -- ss_kaldi_c256<NE,[pow2,]fbank|mfcc,sp> (,spi>
+ *   for PCM) and the frame pool's state advance -- whose grids depend on n_active and total_rows only: capturable, and replayable over
+ *   changed table contents.  d_log_energy ([total_rows], may be NULL) as in ss_kaldi_fbank_device.
+ * Not served: one-shot _i16 Kaldi calls, snip_edges = false, dither, VTLN, padded sizes other than 512 (N != 512), and a dense
+ *   (non-ragged) Kaldi stream call. */
+int ss_kstream_state_len(const ss_kaldi_params *p, size_t *state_len, size_t *delay_rows); /* host only */
+int ss_kstream_row_offsets(const ss_kaldi_params *p, size_t n_active, const int64_t *sample_offsets, int64_t *row_offsets); /* host only */
+int ss_kstream_fbank_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                   const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float *d_pool,
+                                   float *d_out, float *d_log_energy, void *stream);
+int ss_kstream_mfcc_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                  const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float *d_pool,
+                                  float *d_out, void *stream);
+int ss_kstream_fbank_packed_i16_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                       const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float scale,
+                                       float *d_pool, float *d_out, float *d_log_energy, void *stream);
+int ss_kstream_mfcc_packed_i16_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                      const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float scale,
+                                      float *d_pool, float *d_out, void *stream);
+int ss_kstream_fbank_packed(const ss_kaldi_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                            size_t pool_streams, float *pool, float *out, float *log_energy);
+int ss_kstream_mfcc_packed(const ss_kaldi_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                           size_t pool_streams, float *pool, float *out);
+int ss_kstream_fbank_packed_i16(const ss_kaldi_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
+                                const int32_t *slots, size_t pool_streams, float scale, float *pool, float *out, float *log_energy);
+int ss_kstream_mfcc_packed_i16(const ss_kaldi_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
+                               const int32_t *slots, size_t pool_streams, float scale, float *pool, float *out);
 
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`

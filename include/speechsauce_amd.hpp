@@ -698,7 +698,78 @@ public:
         return out;
     }
 
+    // The stream pool (ss_kstream_*): S = the floats of a pool row, D = the warm-up rows after a reset.
+    size_t stream_state_len(size_t *delay_rows = nullptr) const
+    {
+        size_t S = 0, D = 0;
+        check(ss_kstream_state_len(&p_, &S, &D));
+        if (delay_rows) *delay_rows = D;
+        return S;
+    }
+    // Entry i is the chunk x[sample_offsets[i] .. sample_offsets[i+1]) (whole hops, floats or 16-bit PCM times the power-of-two
+    // `scale`) of the stream whose state is row slots[i] of pool [pool_streams x S] (all-zero rows: fresh streams) -> the packed
+    // rows; row_offsets receives the entries' row offsets.  The first D rows of a fresh stream are warm-up rows.
+    std::vector<float> fbank_stream_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, const std::vector<int32_t> &slots,
+                                           std::vector<float> &pool, std::vector<int64_t> &row_offsets, std::vector<float> *log_energy = nullptr) const
+    {
+        const size_t rows = stream_rows(x.size(), sample_offsets, slots, row_offsets);
+        std::vector<float> out(rows * p_.num_mel_bins);
+        if (log_energy) log_energy->assign(rows, 0.0f);
+        check(ss_kstream_fbank_packed(h_.get(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_rows(pool, slots), pool.data(),
+                                      out.data(), log_energy ? log_energy->data() : nullptr));
+        return out;
+    }
+    std::vector<float> mfcc_stream_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, const std::vector<int32_t> &slots,
+                                          std::vector<float> &pool, std::vector<int64_t> &row_offsets) const
+    {
+        std::vector<float> out(stream_rows(x.size(), sample_offsets, slots, row_offsets) * p_.num_ceps);
+        check(ss_kstream_mfcc_packed(h_.get(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_rows(pool, slots), pool.data(),
+                                     out.data()));
+        return out;
+    }
+    std::vector<float> fbank_stream_packed_i16(const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
+                                               const std::vector<int32_t> &slots, float scale, std::vector<float> &pool,
+                                               std::vector<int64_t> &row_offsets, std::vector<float> *log_energy = nullptr) const
+    {
+        const size_t rows = stream_rows(x.size(), sample_offsets, slots, row_offsets);
+        std::vector<float> out(rows * p_.num_mel_bins);
+        if (log_energy) log_energy->assign(rows, 0.0f);
+        check(ss_kstream_fbank_packed_i16(h_.get(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_rows(pool, slots), scale,
+                                          pool.data(), out.data(), log_energy ? log_energy->data() : nullptr));
+        return out;
+    }
+    std::vector<float> mfcc_stream_packed_i16(const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
+                                              const std::vector<int32_t> &slots, float scale, std::vector<float> &pool,
+                                              std::vector<int64_t> &row_offsets) const
+    {
+        std::vector<float> out(stream_rows(x.size(), sample_offsets, slots, row_offsets) * p_.num_ceps);
+        check(ss_kstream_mfcc_packed_i16(h_.get(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_rows(pool, slots), scale,
+                                         pool.data(), out.data()));
+        return out;
+    }
+
 private:
+    size_t stream_rows(size_t n_samples, const std::vector<int64_t> &sample_offsets, const std::vector<int32_t> &slots,
+                       std::vector<int64_t> &row_offsets) const
+    {
+        if (sample_offsets.size() != slots.size() + 1 || sample_offsets.back() < 0 || static_cast<size_t>(sample_offsets.back()) > n_samples)
+            throw Error(SS_ERR_ARG, "kaldi pool call: shape mismatch");
+        row_offsets.assign(sample_offsets.size(), 0);
+        check(ss_kstream_row_offsets(&p_, slots.size(), sample_offsets.data(), row_offsets.data()));
+        return static_cast<size_t>(row_offsets.back());
+    }
+    // the pool's row count (S == 0, a pool without state: one more than the largest slot)
+    size_t pool_rows(const std::vector<float> &pool, const std::vector<int32_t> &slots) const
+    {
+        const size_t S = stream_state_len();
+        if (S > 0) {
+            if (pool.empty() || pool.size() % S) throw Error(SS_ERR_ARG, "kaldi pool call: the pool is not a whole number of rows");
+            return pool.size() / S;
+        }
+        int32_t top = 0;
+        for (int32_t v : slots) top = v > top ? v : top;
+        return static_cast<size_t>(top) + 1;
+    }
     size_t packed_rows(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, std::vector<int64_t> &frame_offsets) const
     {
         if (sample_offsets.empty() || sample_offsets.back() < 0 || static_cast<size_t>(sample_offsets.back()) > x.size())

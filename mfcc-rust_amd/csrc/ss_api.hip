@@ -3357,6 +3357,118 @@ int kaldi_packed_host(const ss_kaldi_config *cfg, bool mfcc, const float *x, siz
     return rc;
 }
 
+// Ragged streaming fbank / MFCC over a pool of stream states (ss_kstream_*_packed*_device): the rows of n_active entries of different
+// hop counts, each over the pool row its slot names, then the advance of the named rows -- a linear chain of two kernels on `stream`
+// (none for the advance where S == 0), the pool build of ss_kaldi_c256 and the frame pool's ss_stream_advance_packed over one entry
+// block (state_len = S, step = shift).  The tables are device arrays read by the kernels only; the grids come from n_active and
+// total_rows.  x: the packed chunks, floats or 16-bit PCM.
+int kaldi_pool_device(const ss_kaldi_config *cfg, bool mfcc, const PoolChunks &x, size_t n_active, const int64_t *d_so, const int64_t *d_ro,
+                      size_t total_rows, const int32_t *d_slots, size_t pool_streams, float *d_pool, float *d_out, float *d_log_energy,
+                      hipStream_t stream)
+{
+    if (int rc = kaldi_check_call(cfg, mfcc)) return rc;
+    if (n_active == 0) return SS_OK;
+    size_t S = 0, D = 0;
+    if (int rc = ss_kstream_state_len(&cfg->params, &S, &D)) return rc;
+    if (!x.ptr() || !d_so || !d_ro || !d_slots || !d_out || (S > 0 && !d_pool)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (x.is_pcm) {
+        if (int rc = check_pcm_scale(x.scale)) return rc;
+        if (reinterpret_cast<uintptr_t>(x.pcm) & 1u) return ss::fail(SS_ERR_ARG, "the PCM buffer must be 2-byte aligned");
+    }
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull || total_rows >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
+    const size_t cols = mfcc ? cfg->params.num_ceps : cfg->params.num_mel_bins;
+    const size_t pbytes = pool_streams * S * sizeof(float);
+    if (S > 0 && (ranges_overlap(d_pool, pbytes, d_out, total_rows * cols * sizeof(float)) ||
+                  (!mfcc && d_log_energy && ranges_overlap(d_pool, pbytes, d_log_energy, total_rows * sizeof(float)))))
+        return ss::fail(SS_ERR_ARG, "the pool overlaps an output");
+    if (int rc = kaldi_ready(cfg)) return rc;
+    const ss::KaldiArgs a = kaldi_args(cfg, mfcc, x.f, d_out, d_log_energy);
+    ss::FrameStreamPackedPcmArgs sp{};
+    sp.e.pool = d_pool;
+    sp.e.state_len = static_cast<uint32_t>(S);
+    sp.e.lead = static_cast<int32_t>(S);
+    sp.e.so = reinterpret_cast<const long long *>(d_so);
+    sp.e.ro = reinterpret_cast<const long long *>(d_ro);
+    sp.e.slots = d_slots;
+    sp.e.n_active = static_cast<uint32_t>(n_active);
+    sp.e.pool_streams = static_cast<uint32_t>(pool_streams);
+    sp.e.total_rows = static_cast<uint32_t>(total_rows);
+    sp.e.step = a.step;
+    sp.e.err = cfg->d_err;
+    sp.x = x.pcm;
+    sp.scale = x.scale;
+    ss::LaunchInfo info{};
+    if (int rc = kaldi_launched(ss::launch_kaldi_c256_stream_packed(a, sp, x.is_pcm, stream, cfg->num_cus, &info), info)) return rc;
+    const hipError_t e = x.is_pcm ? ss::launch_stream_advance_packed(sp, stream) : ss::launch_stream_advance_packed(sp.e, x.f, stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_stream_advance_packed");
+    return SS_OK;
+}
+
+// Host-pointer form, as frame_stream_packed_host: the tables are checked here, before anything touches the device; then x, the
+// tables and the n_active named pool rows (a compact block whose row i is entry i's: the device call runs on slots 0 .. n_active - 1)
+// go up, the outputs and the named rows come down.  The caller's pool is written only once everything before it succeeded.
+int kaldi_pool_host(const ss_kaldi_config *cfg, bool mfcc, const PoolChunks &x, size_t n_active, const int64_t *so, const int32_t *slots,
+                    size_t pool_streams, float *pool, float *out, float *log_energy)
+{
+    if (int rc = kaldi_check_call(cfg, mfcc)) return rc;
+    if (n_active == 0) return SS_OK;
+    size_t S = 0, D = 0;
+    int rc = ss_kstream_state_len(&cfg->params, &S, &D);
+    if (rc) return rc;
+    if (!x.ptr() || !so || !slots || !out || (S > 0 && !pool)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (x.is_pcm && (rc = check_pcm_scale(x.scale))) return rc;
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
+    std::vector<int64_t> ro(n_active + 1);
+    if ((rc = ss_kstream_row_offsets(&cfg->params, n_active, so, ro.data()))) return rc;
+    if ((rc = ss::check_slots(slots, n_active, pool_streams))) return rc;
+    const size_t rows = static_cast<size_t>(ro[n_active]), samples = static_cast<size_t>(so[n_active]);
+    if (rows >= 0x80000000ull) return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    const size_t cols = mfcc ? cfg->params.num_ceps : cfg->params.num_mel_bins;
+    const size_t pbytes = pool_streams * S * sizeof(float);
+    if (S > 0 && (ranges_overlap(pool, pbytes, x.ptr(), samples * x.sample_bytes()) || ranges_overlap(pool, pbytes, out, rows * cols * sizeof(float)) ||
+                  (log_energy && ranges_overlap(pool, pbytes, log_energy, rows * sizeof(float)))))
+        return ss::fail(SS_ERR_ARG, "the pool overlaps the input or an output");
+    if (!ss::have_device()) return ss::no_device("hot path");
+    ss::PoolRows named;  // the named pool rows, row i = entry i's
+    named.gather(pool, slots, n_active, S);
+    const size_t tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * S * sizeof(float);
+    // (hip_alloc of 0 bytes: give every block at least one element)
+    DeviceBuf dx, dso, dro, dsl, dp, d0, d1;
+    hipError_t e = dx.hip_alloc(std::max<size_t>(samples, 1) * x.sample_bytes());
+    if (e == hipSuccess) e = dso.hip_alloc(tbytes);
+    if (e == hipSuccess) e = dro.hip_alloc(tbytes);
+    if (e == hipSuccess) e = dsl.hip_alloc(n_active * sizeof(int32_t));
+    if (e == hipSuccess && S > 0) e = dp.hip_alloc(sbytes);
+    if (e == hipSuccess) e = d0.hip_alloc(std::max<size_t>(rows * cols, 1) * sizeof(float));
+    if (e == hipSuccess && log_energy) e = d1.hip_alloc(std::max<size_t>(rows, 1) * sizeof(float));
+    if (e == hipSuccess && samples) e = hipMemcpy(dx.p, x.ptr(), samples * x.sample_bytes(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dso.p, so, tbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dro.p, ro.data(), tbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dsl.p, named.iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && S > 0) e = hipMemcpy(dp.p, named.rows_host.data(), sbytes, hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? kaldi_pool_device(cfg, mfcc, x.is_pcm ? PoolChunks(dx.as<const int16_t>(), x.scale) : PoolChunks(dx.as<const float>()),
+                                             n_active, dso.as<const int64_t>(), dro.as<const int64_t>(), rows, dsl.as<const int32_t>(), n_active,
+                                             S > 0 ? dp.as<float>() : nullptr, d0.as<float>(), log_energy ? d1.as<float>() : nullptr, nullptr)
+                         : hip_fail(e, "host staging");
+    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_kstream: device error");
+    if (rc == SS_OK) rc = kaldi_pending_error(cfg);
+    if (rc == SS_OK && rows > 0) {
+        e = hipMemcpy(out, d0.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && log_energy) e = hipMemcpy(log_energy, d1.p, rows * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
+    }
+    if (rc == SS_OK && S > 0) {
+        e = hipMemcpy(named.rows_host.data(), dp.p, sbytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H (pool rows)");
+        if (rc == SS_OK) named.scatter(pool, slots);
+    }
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3459,6 +3571,62 @@ int ss_kaldi_mfcc_packed_device(const ss_kaldi_config *cfg, const float *d_x, si
 int ss_kaldi_mfcc_packed(const ss_kaldi_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out)
 {
     return kaldi_packed_host(cfg, true, x, n_clips, sample_offsets, out, nullptr);
+}
+
+int ss_kstream_fbank_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                   const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float *d_pool,
+                                   float *d_out, float *d_log_energy, void *stream)
+{
+    return kaldi_pool_device(cfg, false, PoolChunks(d_x), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams, d_pool, d_out,
+                             d_log_energy, static_cast<hipStream_t>(stream));
+}
+
+int ss_kstream_mfcc_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                  const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float *d_pool,
+                                  float *d_out, void *stream)
+{
+    return kaldi_pool_device(cfg, true, PoolChunks(d_x), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams, d_pool, d_out,
+                             nullptr, static_cast<hipStream_t>(stream));
+}
+
+int ss_kstream_fbank_packed_i16_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                       const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float scale,
+                                       float *d_pool, float *d_out, float *d_log_energy, void *stream)
+{
+    return kaldi_pool_device(cfg, false, PoolChunks(d_x, scale), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams, d_pool,
+                             d_out, d_log_energy, static_cast<hipStream_t>(stream));
+}
+
+int ss_kstream_mfcc_packed_i16_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                      const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float scale,
+                                      float *d_pool, float *d_out, void *stream)
+{
+    return kaldi_pool_device(cfg, true, PoolChunks(d_x, scale), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams, d_pool,
+                             d_out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int ss_kstream_fbank_packed(const ss_kaldi_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                            size_t pool_streams, float *pool, float *out, float *log_energy)
+{
+    return kaldi_pool_host(cfg, false, PoolChunks(x), n_active, sample_offsets, slots, pool_streams, pool, out, log_energy);
+}
+
+int ss_kstream_mfcc_packed(const ss_kaldi_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                           size_t pool_streams, float *pool, float *out)
+{
+    return kaldi_pool_host(cfg, true, PoolChunks(x), n_active, sample_offsets, slots, pool_streams, pool, out, nullptr);
+}
+
+int ss_kstream_fbank_packed_i16(const ss_kaldi_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                                size_t pool_streams, float scale, float *pool, float *out, float *log_energy)
+{
+    return kaldi_pool_host(cfg, false, PoolChunks(x, scale), n_active, sample_offsets, slots, pool_streams, pool, out, log_energy);
+}
+
+int ss_kstream_mfcc_packed_i16(const ss_kaldi_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                               size_t pool_streams, float scale, float *pool, float *out)
+{
+    return kaldi_pool_host(cfg, true, PoolChunks(x, scale), n_active, sample_offsets, slots, pool_streams, pool, out, nullptr);
 }
 
 }  // extern "C"

@@ -805,5 +805,12 @@ struct KaldiVarlenArgs {
 hipError_t launch_kaldi_c256(const KaldiArgs &a, hipStream_t stream, int num_cus, LaunchInfo *info);
 // a: x / out = the packed blocks; batch / n_samples / n_frames / ld are unused
 hipError_t launch_kaldi_c256_varlen(const KaldiArgs &a, const KaldiVarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
+// The stream-pool builds (ss_kaldi512_pool.hip; ss_kstream_*_packed*_device): the packed output rows of a ragged streaming launch
+// over the frame pool's entry block -- step = the frame shift, state_len = S = D * shift, D = ceil(flen / shift) - 1; lead unused:
+// row t of an entry starts at chunk sample t * step - S.  pcm: the chunks are sp.x (2-byte aligned) times sp.scale, else a.x
+// (sp.x / sp.scale unused); batch / n_samples / n_frames / ld are unused.  The grid comes from total_rows (one workgroup where it
+// is 0: the entry pass).  The advance is launch_stream_advance_packed over the same block.
+hipError_t launch_kaldi_c256_stream_packed(const KaldiArgs &a, const FrameStreamPackedPcmArgs &sp, bool pcm, hipStream_t stream, int num_cus,
+                                           LaunchInfo *info);
 
 }  // namespace ss

@@ -1435,6 +1435,27 @@ int ss_kaldi_packed_frame_offsets(const ss_kaldi_params *p, size_t n_clips, cons
     });
 }
 
+// the stream pool of the Kaldi front end: D = ceil(flen / shift) - 1 rows of delay, S = D * shift carried samples -- whole hops, so
+// that a stream's rows land on Kaldi's own frame grid
+int ss_kstream_state_len(const ss_kaldi_params *p, size_t *state_len, size_t *delay_rows)
+{
+    if (!p || !state_len || !delay_rows) return ss::fail(SS_ERR_ARG, "null argument");
+    ss::KaldiSizes s;
+    if (int rc = ss::kaldi_validate(*p, &s)) return rc;
+    const size_t D = (static_cast<size_t>(s.flen) + s.shift - 1) / s.shift - 1;
+    *delay_rows = D;
+    *state_len = D * s.shift;
+    return SS_OK;
+}
+
+int ss_kstream_row_offsets(const ss_kaldi_params *p, size_t n_active, const int64_t *sample_offsets, int64_t *row_offsets)
+{
+    if (!p || !sample_offsets || !row_offsets) return ss::fail(SS_ERR_ARG, "null argument");
+    ss::KaldiSizes s;
+    if (int rc = ss::kaldi_validate(*p, &s)) return rc;
+    return walk_stream_offsets(n_active, sample_offsets, row_offsets, static_cast<int64_t>(s.shift), "the Kaldi stream pool");
+}
+
 int ss_kaldi_window(const ss_kaldi_params *p, float *w)
 {
     if (!p || !w) return ss::fail(SS_ERR_ARG, "null argument");

@@ -203,6 +203,16 @@ extern "C" {
     fn ss_kaldi_fbank_packed(cfg: *const c_void, x: *const f32, n_clips: usize, sample_offsets: *const i64, out: *mut f32,
                              log_energy: *mut f32) -> c_int;
     fn ss_kaldi_mfcc_packed(cfg: *const c_void, x: *const f32, n_clips: usize, sample_offsets: *const i64, out: *mut f32) -> c_int;
+    fn ss_kstream_state_len(p: *const KaldiParams, state_len: *mut usize, delay_rows: *mut usize) -> c_int;
+    fn ss_kstream_row_offsets(p: *const KaldiParams, n_active: usize, sample_offsets: *const i64, row_offsets: *mut i64) -> c_int;
+    fn ss_kstream_fbank_packed(cfg: *const c_void, x: *const f32, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                               pool_streams: usize, pool: *mut f32, out: *mut f32, log_energy: *mut f32) -> c_int;
+    fn ss_kstream_mfcc_packed(cfg: *const c_void, x: *const f32, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                              pool_streams: usize, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_kstream_fbank_packed_i16(cfg: *const c_void, x: *const i16, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                                   pool_streams: usize, scale: f32, pool: *mut f32, out: *mut f32, log_energy: *mut f32) -> c_int;
+    fn ss_kstream_mfcc_packed_i16(cfg: *const c_void, x: *const i16, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                                  pool_streams: usize, scale: f32, pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_derivative_extraction(feat: *const f32, rows: usize, cols: usize, delta_windows: usize, out: *mut f32) -> c_int;
     fn ss_extract_derivative_feature(feat: *const f32, rows: usize, cols: usize, cube: *mut f32) -> c_int;
     fn ss_shard_bounds(n_items: usize, world: c_int, rank: c_int, lo: *mut usize, hi: *mut usize) -> c_int;
@@ -1287,6 +1297,91 @@ impl KaldiFrontEnd {
         let mut out = Array2::<f32>::zeros((fo[fo.len() - 1] as usize, self.params.num_ceps as usize));
         check(unsafe { ss_kaldi_mfcc_packed(self.raw, x.as_ptr(), fo.len() - 1, sample_offsets.as_ptr(), out.as_mut_ptr()) })?;
         Ok((out, fo))
+    }
+
+    /// The stream pool's sizes (`ss_kstream_state_len`): (S, the carried samples per stream = the floats of a pool row; D, the
+    /// warm-up rows after a reset).
+    pub fn stream_state_len(&self) -> Result<(usize, usize), Error> {
+        let (mut s, mut d) = (0usize, 0usize);
+        check(unsafe { ss_kstream_state_len(&self.params, &mut s, &mut d) })?;
+        Ok((s, d))
+    }
+
+    /// Row offsets of the entries of a pool call (`ss_kstream_row_offsets`): every chunk is whole hops.
+    pub fn stream_row_offsets(&self, sample_offsets: &[i64]) -> Result<Vec<i64>, Error> {
+        if sample_offsets.is_empty() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must not be empty".to_string() });
+        }
+        let mut ro = vec![0i64; sample_offsets.len()];
+        check(unsafe { ss_kstream_row_offsets(&self.params, sample_offsets.len() - 1, sample_offsets.as_ptr(), ro.as_mut_ptr()) })?;
+        Ok(ro)
+    }
+
+    // the checks the pool wrappers share: the tables against the block and the pool -> (row offsets, pool rows)
+    fn stream_shape<T>(&self, x: &[T], sample_offsets: &[i64], slots: &[i32], pool: &[f32]) -> Result<(Vec<i64>, usize), Error> {
+        let ro = self.stream_row_offsets(sample_offsets)?;
+        let (s, _) = self.stream_state_len()?;
+        if slots.len() != sample_offsets.len() - 1 || sample_offsets[sample_offsets.len() - 1] as usize > x.len() {
+            return Err(Error { status: SS_ERR_ARG, detail: "pool call: shape mismatch".to_string() });
+        }
+        if s > 0 && (pool.is_empty() || pool.len() % s != 0) {
+            return Err(Error { status: SS_ERR_ARG, detail: "pool call: the pool is not a whole number of rows".to_string() });
+        }
+        // (s == 0: a pool without state; one row stands for any slot count the caller uses)
+        Ok((ro, if s > 0 { pool.len() / s } else { (slots.iter().copied().max().unwrap_or(0).max(0) as usize) + 1 }))
+    }
+
+    /// Ragged streaming fbank over a pool of stream states (`ss_kstream_fbank_packed`): entry i is the chunk
+    /// `x[sample_offsets[i] .. sample_offsets[i+1])` (whole hops) of the stream whose state is pool row `slots[i]`; `pool` is
+    /// `[pool_streams x S]`, all-zero rows are fresh streams.  -> (rows, log energies, row offsets); the first D rows of a fresh
+    /// stream are warm-up rows.
+    pub fn fbank_stream_packed(&self, x: &[f32], sample_offsets: &[i64], slots: &[i32], pool: &mut [f32]) -> Result<(Array2<f32>, Vec<f32>, Vec<i64>), Error> {
+        let (ro, pool_streams) = self.stream_shape(x, sample_offsets, slots, pool)?;
+        let rows = ro[ro.len() - 1] as usize;
+        let mut out = Array2::<f32>::zeros((rows, self.params.num_mel_bins as usize));
+        let mut en = vec![0f32; rows];
+        check(unsafe {
+            ss_kstream_fbank_packed(self.raw, x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams, pool.as_mut_ptr(),
+                                    out.as_mut_ptr(), en.as_mut_ptr())
+        })?;
+        Ok((out, en, ro))
+    }
+
+    /// Ragged streaming MFCC over a pool of stream states (`ss_kstream_mfcc_packed`); see `fbank_stream_packed`.
+    pub fn mfcc_stream_packed(&self, x: &[f32], sample_offsets: &[i64], slots: &[i32], pool: &mut [f32]) -> Result<(Array2<f32>, Vec<i64>), Error> {
+        let (ro, pool_streams) = self.stream_shape(x, sample_offsets, slots, pool)?;
+        let mut out = Array2::<f32>::zeros((ro[ro.len() - 1] as usize, self.params.num_ceps as usize));
+        check(unsafe {
+            ss_kstream_mfcc_packed(self.raw, x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams, pool.as_mut_ptr(),
+                                   out.as_mut_ptr())
+        })?;
+        Ok((out, ro))
+    }
+
+    /// `fbank_stream_packed` fed signed 16-bit PCM: sample = `pcm as f32 * scale`, `scale` a power of two (`ss_kstream_fbank_packed_i16`).
+    pub fn fbank_stream_packed_i16(&self, x: &[i16], sample_offsets: &[i64], slots: &[i32], scale: f32, pool: &mut [f32])
+                                   -> Result<(Array2<f32>, Vec<f32>, Vec<i64>), Error> {
+        let (ro, pool_streams) = self.stream_shape(x, sample_offsets, slots, pool)?;
+        let rows = ro[ro.len() - 1] as usize;
+        let mut out = Array2::<f32>::zeros((rows, self.params.num_mel_bins as usize));
+        let mut en = vec![0f32; rows];
+        check(unsafe {
+            ss_kstream_fbank_packed_i16(self.raw, x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams, scale,
+                                        pool.as_mut_ptr(), out.as_mut_ptr(), en.as_mut_ptr())
+        })?;
+        Ok((out, en, ro))
+    }
+
+    /// `mfcc_stream_packed` fed signed 16-bit PCM (`ss_kstream_mfcc_packed_i16`).
+    pub fn mfcc_stream_packed_i16(&self, x: &[i16], sample_offsets: &[i64], slots: &[i32], scale: f32, pool: &mut [f32])
+                                  -> Result<(Array2<f32>, Vec<i64>), Error> {
+        let (ro, pool_streams) = self.stream_shape(x, sample_offsets, slots, pool)?;
+        let mut out = Array2::<f32>::zeros((ro[ro.len() - 1] as usize, self.params.num_ceps as usize));
+        check(unsafe {
+            ss_kstream_mfcc_packed_i16(self.raw, x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams, scale,
+                                       pool.as_mut_ptr(), out.as_mut_ptr())
+        })?;
+        Ok((out, ro))
     }
 }
 

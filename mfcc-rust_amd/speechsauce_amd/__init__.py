@@ -29,6 +29,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "add_deltas", "add_deltas_packed", "AddDeltasStreamPool",
            "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
+           "KaldiFbankStreamPool", "KaldiMfccStreamPool",
            "SpeechConfig", "SpeechSauceError"]
 
 
@@ -1123,8 +1124,7 @@ class _StreamPoolMixin:
             where = ("host",)
         if self._where is not None and where != self._where:
             raise ValueError(f"{what}: the pool lives on {self._where}, these chunks on {where}")
-        a = self._args
-        config = _cfg(*a[:9], a[9], packed)
+        config = self._config_for(packed)
         if self._state is None:
             if on_dev:
                 self._state = torch.zeros((self.pool_streams, self.state_len), dtype=torch.float32, device=packed.device)
@@ -1135,6 +1135,11 @@ class _StreamPoolMixin:
         np.cumsum(lens, out=so[1:])
         ro = so // self.hop
         return packed, so, ro, np.asarray(slot_list, dtype=np.int32), config
+
+    def _config_for(self, packed):
+        """The handle that serves ``packed`` where it lives."""
+        a = self._args
+        return _cfg(*a[:9], a[9], packed)
 
     def _prepare_pcm(self, chunks, slots, lengths, pcm_scale):
         """``_prepare_pool`` of either chunk format, and what ``_call_pool`` needs for it: the suffix of the entry points' names
@@ -2441,6 +2446,136 @@ def kaldi_mfcc_packed(signal, lengths, sample_frequency=16000.0, frame_length=25
                      preemphasis_coefficient, cepstral_lifter, window_type, blackman_coeff, remove_dc_offset, True, use_energy, raw_energy,
                      energy_floor, input_scale, unsupported)
     return _kaldi_packed(sig, so, cfg, True, False)
+
+
+# ---- the Kaldi front end over a pool of stream states (ss_kstream_*) ----------------------------------------------------------
+
+class _KaldiStreamPoolBase(_StreamPoolMixin):
+    """A pool of ``pool_streams`` live audio streams through ``kaldi_fbank`` / ``kaldi_mfcc``: the constructor takes torchaudio's
+    keyword names (see ``kaldi_fbank``) plus ``pool_streams``; every stream carries its last ``state_len = delay_rows * hop`` samples,
+    ``delay_rows = ceil(frame / hop) - 1``.  ``pool(chunks, lengths_or_offsets, slots, pcm_scale=None)``: ``chunks`` is one packed
+    1-D float32 buffer (int16 with ``pcm_scale``, a power of two: sample = ``int16 * pcm_scale``) with the chunk lengths -- or the
+    ``len(slots) + 1`` sample offsets -- of the entries, every chunk a whole number of hops (zero included), or a list of 1-D
+    chunks with ``lengths_or_offsets=None``; ``slots`` names each chunk's pool row (distinct).  Returns ``(rows, row_offsets)``,
+    the pair the ``CmvnStreamPool`` / ``AddDeltasStreamPool`` calls take with the same ``slots``.
+
+    A stream's rows over all calls, however it was cut, are bit for bit ``kaldi_fbank`` / ``kaldi_mfcc`` of ``zeros(state_len) ++
+    stream``: the first ``delay_rows`` rows after a reset are warm-up rows over the zero prefix, the rows after them are the offline
+    call's on the stream itself.  numpy in -> the host-pointer call, ROCm tensors in -> the device call on the current stream.
+    See ``ss_kstream_*`` in ``include/speechsauce_amd.h``."""
+
+    _mfcc = False
+
+    def __init__(self, pool_streams, kaldi_args, unsupported):
+        what = self._what
+        _kaldi_reject(what, unsupported)
+        if int(pool_streams) < 1:
+            raise ValueError(f"{what}: pool_streams must be at least 1")
+        self.pool_streams = int(pool_streams)
+        self._kaldi_args = kaldi_args
+        self._params = _kaldi_params(*self._key())
+        lib = _lib.lib()
+        _lib.check(lib.ss_kaldi_params_validate(C.byref(self._params)))
+        S, D, fl, sh, pad = (C.c_size_t() for _ in range(5))
+        _lib.check(lib.ss_kaldi_sizes(C.byref(self._params), C.byref(fl), C.byref(sh), C.byref(pad)))
+        _lib.check(lib.ss_kstream_state_len(C.byref(self._params), C.byref(S), C.byref(D)))
+        self.state_len, self.delay_rows, self.hop = S.value, D.value, sh.value
+        self._state = None
+        self._where = None
+
+    def _key(self):
+        (sample_frequency, frame_length, frame_shift, num_mel_bins, num_ceps, low_freq, high_freq, preemphasis_coefficient, cepstral_lifter,
+         window_type, blackman_coeff, remove_dc_offset, use_power, use_energy, raw_energy, energy_floor, input_scale) = self._kaldi_args
+        mfcc = self._mfcc
+        return (sample_frequency, float(frame_length), float(frame_shift), int(num_mel_bins), int(num_ceps) if mfcc else 0, float(low_freq),
+                float(high_freq), float(preemphasis_coefficient), float(cepstral_lifter) if mfcc else 0.0, window_type, float(blackman_coeff),
+                bool(remove_dc_offset), bool(use_power), bool(use_energy) if mfcc else False, bool(raw_energy), float(energy_floor),
+                float(input_scale))
+
+    def _config_for(self, packed):
+        return _get_kaldi_config(self._key(), _device_key(packed))
+
+    def reset(self, slots=None):
+        """Zero the state of every stream of the pool, or of the given slots (fresh streams: their next ``delay_rows`` rows are
+        warm-up rows again)."""
+        if self._state is None:
+            return
+        if slots is None:
+            self._state[...] = 0
+        else:
+            idx = list(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
+            if idx:
+                self._state[idx] = 0
+
+    def _lengths(self, lengths_or_offsets, n_slots):
+        if lengths_or_offsets is None:
+            return None
+        v = np.asarray(lengths_or_offsets.cpu() if _is_torch(lengths_or_offsets) else lengths_or_offsets)
+        if v.ndim != 1 or not (np.issubdtype(v.dtype, np.integer) or v.size == 0):
+            raise TypeError(f"{self._what}: lengths_or_offsets must be a 1-D sequence of integers")
+        v = v.astype(np.int64)
+        if v.size == n_slots + 1:  # sample offsets
+            if v[0] != 0:
+                raise ValueError(f"{self._what}: sample offsets must start at 0")
+            return np.diff(v)
+        return v
+
+    def _run(self, chunks, lengths_or_offsets, slots, pcm_scale, cols, with_energy):
+        slot_list = [int(v) for v in slots]
+        (packed, so, ro, sl, config), i16, scale = self._prepare_pcm(chunks, slot_list, self._lengths(lengths_or_offsets, len(slot_list)), pcm_scale)
+        R = int(ro[-1])
+        kind = "mfcc" if self._mfcc else "fbank"
+        if _is_torch(packed):
+            import torch
+
+            outs = [torch.empty((R, cols), dtype=torch.float32, device=packed.device)]
+            if not self._mfcc:
+                outs.append(torch.empty((R,), dtype=torch.float32, device=packed.device))
+        else:
+            outs = [np.empty((R, cols), dtype=np.float32)]
+            if not self._mfcc:
+                outs.append(np.empty((R,), dtype=np.float32))
+        self._call_pool(packed, so, ro, sl, config, outs, f"ss_kstream_{kind}_packed{i16}_device", f"ss_kstream_{kind}_packed{i16}", scale)
+        if with_energy:
+            return outs[0], outs[1], ro
+        return outs[0], ro
+
+
+class KaldiFbankStreamPool(_KaldiStreamPoolBase):
+    """Ragged streaming ``kaldi_fbank``: ``pool(chunks, lengths_or_offsets, slots)`` -> ``(rows [total_rows, num_mel_bins],
+    row_offsets)``; ``pool(..., with_energy=True)`` -> ``(rows, log_energy [total_rows], row_offsets)``."""
+
+    _what = "KaldiFbankStreamPool"
+
+    def __init__(self, pool_streams, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0,
+                 high_freq=0.0, preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True,
+                 use_power=True, raw_energy=True, energy_floor=1.0, input_scale=1.0, **unsupported):
+        super().__init__(pool_streams, (sample_frequency, frame_length, frame_shift, num_mel_bins, 0, low_freq, high_freq,
+                                        preemphasis_coefficient, 0.0, window_type, blackman_coeff, remove_dc_offset, use_power, False,
+                                        raw_energy, energy_floor, input_scale), unsupported)
+        self.cols = int(num_mel_bins)
+
+    def __call__(self, chunks, lengths_or_offsets, slots, pcm_scale=None, with_energy=False):
+        return self._run(chunks, lengths_or_offsets, slots, pcm_scale, self.cols, bool(with_energy))
+
+
+class KaldiMfccStreamPool(_KaldiStreamPoolBase):
+    """Ragged streaming ``kaldi_mfcc``: ``pool(chunks, lengths_or_offsets, slots)`` -> ``(rows [total_rows, num_ceps],
+    row_offsets)``."""
+
+    _what = "KaldiMfccStreamPool"
+    _mfcc = True
+
+    def __init__(self, pool_streams, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0,
+                 high_freq=0.0, preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True,
+                 use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, num_ceps=13, cepstral_lifter=22.0, **unsupported):
+        super().__init__(pool_streams, (sample_frequency, frame_length, frame_shift, num_mel_bins, num_ceps, low_freq, high_freq,
+                                        preemphasis_coefficient, cepstral_lifter, window_type, blackman_coeff, remove_dc_offset, True,
+                                        use_energy, raw_energy, energy_floor, input_scale), unsupported)
+        self.cols = int(num_ceps)
+
+    def __call__(self, chunks, lengths_or_offsets, slots, pcm_scale=None):
+        return self._run(chunks, lengths_or_offsets, slots, pcm_scale, self.cols, False)
 
 
 def _kaldi_list(what, signals, packed_fn, kw):

@@ -288,6 +288,20 @@ PROTOTYPES = {
     "ss_kaldi_fbank_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, _fp, _fp]),
     "ss_kaldi_mfcc_packed_device": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
     "ss_kaldi_mfcc_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, _fp]),
+    "ss_kstream_state_len": (C.c_int, [_P(SsKaldiParams), _P(C.c_size_t), _P(C.c_size_t)]),
+    "ss_kstream_row_offsets": (C.c_int, [_P(SsKaldiParams), C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ss_kstream_fbank_packed_device": (
+        C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp, _fp, C.c_void_p]),
+    "ss_kstream_mfcc_packed_device": (
+        C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_kstream_fbank_packed_i16_device": (
+        C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp, _fp, C.c_void_p]),
+    "ss_kstream_mfcc_packed_i16_device": (
+        C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp, C.c_void_p]),
+    "ss_kstream_fbank_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, _fp, _fp]),
+    "ss_kstream_mfcc_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, _fp]),
+    "ss_kstream_fbank_packed_i16": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp, _fp]),
+    "ss_kstream_mfcc_packed_i16": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp]),
     "ss_shard_bounds": (C.c_int, [C.c_size_t, C.c_int, C.c_int, _P(C.c_size_t), _P(C.c_size_t)]),
     "ss_all_gather_features": (C.c_int, [C.c_void_p, _fp, C.c_size_t, _fp, C.c_void_p]),
     "ss_gather_features": (C.c_int, [C.c_void_p, _fp, C.c_size_t, _fp, C.c_int, C.c_int, C.c_int, C.c_void_p]),
