@@ -847,6 +847,78 @@ int ss_add_deltas_stream_flush_device(size_t n_active, const int32_t *d_slots, s
 int ss_add_deltas_stream_flush(size_t n_active, const int32_t *slots, size_t pool_streams, size_t cols, size_t order, size_t window,
                                float *pool, float *out);
 
+/* ---- frame splicing and subsampling on packed clips and over a pool of stream states ----
+ * The stage a neural acoustic model takes behind normalised rows (with or without deltas): context splicing (Kaldi splice-feats
+ * --left-context --right-context), frame subsampling (Kaldi subsample-feats --n) and low frame rate, the two combined: stack m
+ * frames, skip n (FunASR / Paraformer lfr_m = 7, lfr_n = 6; "stack 4 skip 3").  The reference crate has none: this comment is the
+ * specification.
+ *   Parameters: cols >= 1; left, right in [0, 32]; stride in [1, 32] (the bound of ss_add_deltas*' L).  W = left + 1 + right; an
+ *   output row has W * cols floats.
+ *   One clip or stream with raw rows x[0 .. T-1]: T_out = ceil(T / stride) (T = 0: no rows); output row k is the concatenation, for
+ *   c = -left .. +right ascending, of x[clamp(k * stride + c, 0, T - 1)].  Every output float is a BIT COPY of an input float: no
+ *   arithmetic touches it, so NaN payloads, -0.0, infinities and denormals come through unchanged.
+ *   stride = 1 is splice-feats; left = right = 0 is subsample-feats --n=stride; left = (m-1)/2, right = m-1-left, stride = n is
+ *   FunASR's apply_lfr(m, n).
+ * Packed clips (ss_splice_packed*): vec is [total_rows x cols], clip b owns rows ro[b] .. ro[b+1]; out is [total_out_rows x
+ * W*cols], clip b owns rows oo[b] .. oo[b+1].  Both tables are device arrays of n_clips + 1 entries that only the kernel reads; oo
+ * may be the same array as ro when stride == 1.  A clip is served iff 0 <= ro[b] <= ro[b+1] <= total_rows, oo[b] >= 0, oo[b+1] -
+ * oo[b] == ceil((ro[b+1] - ro[b]) / stride) and oo[b+1] <= total_out_rows; any other clip is skipped whole.  Nothing outside the
+ * two blocks is read or written; rows in no served clip stay unwritten.  One launch (ss_splice_packed_kernel) whatever the clip
+ * count; a clip's bits depend on its own rows and the scalars only.  n_clips == 0 is SS_OK without a device.  SS_ERR_ARG, decided
+ * before the device is touched: null buffers; cols == 0; a parameter outside its range; n_clips, total_rows, total_out_rows, cols
+ * or W * cols >= 2^31; out overlapping vec.  ss_splice_packed_offsets (host only) forms oo from ro: oo[0] = 0, oo[b+1] = oo[b] +
+ * ceil((ro[b+1] - ro[b]) / stride); it rejects null tables, a stride outside its range, n_clips >= 2^31 and a decreasing pair
+ * (nothing is written then), and out_offsets may be row_offsets.  The host form takes row_offsets alone and forms oo itself; it
+ * checks the table first and names the first bad clip (the rules of ss_add_deltas_packed) and writes the rows the table covers. */
+int ss_splice_packed_offsets(size_t n_clips, const int64_t *row_offsets, size_t stride, int64_t *out_offsets);
+int ss_splice_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_row_offsets, size_t total_rows,
+                            const int64_t *d_out_offsets, size_t total_out_rows, size_t cols, size_t left, size_t right,
+                            size_t stride, float *d_out, void *stream);
+int ss_splice_packed(const float *vec, size_t n_clips, const int64_t *row_offsets, size_t total_rows, size_t cols, size_t left,
+                     size_t right, size_t stride, float *out);
+/* Pool of stream states (ss_splice_stream_*): a live stream is fed WHOLE PERIODS of `stride` rows and gets one output row per
+ * period, D = right / stride periods late (integer division; right = 3, stride = 6: D = 0, the centre's right context lies inside
+ * its own period; right = 5, stride = 1: D = 5).  It carries H = D * stride + left raw rows.  Pool: a caller-owned block
+ * [pool_streams x len] of floats, len = ss_splice_stream_state_len = H * cols + 1, laid out as the add-deltas pool: the stream's
+ * last H raw rows, oldest first, right-aligned, zeros in front, then the count word min(rows seen, H) as a float.  All zeros =
+ * fresh stream.  A count word that is not an integer in [0, H] (NaN included) is read as 0.  H = 0 keeps the one count word.
+ *   Entry i owns rows ro[i] .. ro[i+1] of vec [total_rows x cols] and pool row slots[i]; its R_i rows are R_i / stride whole
+ *   periods (zero is legal) and its output rows are rows ro[i] / stride .. ro[i+1] / stride of out [total_rows / stride x W*cols].
+ *   Every ro[i] is a multiple of stride, so the row_offsets / slots of the feature call are reused unchanged: there is no second
+ *   table.  Output row k of the entry has output index m = seen / stride + k - D (seen: rows of the stream before this call).
+ *   m < 0: the whole row is +0.0, a warm-up row.  m >= 0: the row defined above with left clamping at stream row 0 and no right
+ *   clamping (its last row m * stride + right <= seen + (k + 1) * stride - 1 has arrived).  Afterwards the pool row is the last H
+ *   rows of (history ++ entry) and the new count.  R_i == 0 writes nothing and leaves the pool row bit for bit.
+ *   Flush (ss_splice_stream_flush*): entry i gets exactly D rows, out[i*D .. (i+1)*D): output indices seen / stride - D .. seen /
+ *   stride - 1 with right clamping at the stream's last row; indices below 0 are +0.0 rows.  Afterwards the pool row is all zeros.
+ *   D == 0: no rows, d_out may be NULL, and the pool rows are still zeroed.
+ *   Invariant: however a stream of K * stride rows is cut into calls (empty entries included), the rows of all its calls plus the
+ *   flush, the first D dropped, are bit for bit ss_splice_packed* on the whole clip.
+ *   A stream's end: a stream whose length is not a whole number of periods is padded by the caller, who repeats its last row up
+ *   to a whole period before the last call.  That gives exactly the packed call on the unpadded clip, because the clamp replicates
+ *   the same row.
+ *   One launch each (ss_splice_stream_kernel), one workgroup per entry, one kernel node whose grid depends on n_active only,
+ *   asynchronous on `stream`, no allocation, no scratch.  Containment as ss_add_deltas_stream_*: an entry is served only if 0 <=
+ *   ro[i] <= ro[i+1] <= total_rows, ro[i] and R_i are multiples of stride and 0 <= slots[i] < pool_streams (flush: the slot rule);
+ *   a skipped entry has no row written and its pool row untouched.  Whatever tables and count words hold, nothing outside the
+ *   blocks is touched.  Duplicate slots in a device-form call are a caller error that is NOT detected; the host forms reject them.
+ * Arguments: n_active == 0 is SS_OK with nothing launched, also without a device.  SS_ERR_ARG, decided before the device is
+ * touched, pool and out untouched: null buffers; cols == 0; left, right or stride outside its range; n_active, pool_streams,
+ * total_rows, cols or W * cols >= 2^31 (len is never more); pool_streams == 0; out overlapping vec; the pool overlapping vec or out.  The host
+ * forms also check the tables first -- ro[0] != 0, a decreasing pair, an entry that is not whole periods, a slot outside the pool,
+ * a slot named twice; ss_last_error_string() names the first bad entry -- and write the caller's pool last. */
+/* host only, no device: len = (right / stride * stride + left) * cols + 1, delay_rows = right / stride */
+int ss_splice_stream_state_len(size_t cols, size_t left, size_t right, size_t stride, size_t *state_len, size_t *delay_rows);
+int ss_splice_stream_packed_device(const float *d_vec, size_t n_active, const int64_t *d_row_offsets, size_t total_rows,
+                                   const int32_t *d_slots, size_t pool_streams, size_t cols, size_t left, size_t right,
+                                   size_t stride, float *d_pool, float *d_out, void *stream);
+int ss_splice_stream_packed(const float *vec, size_t n_active, const int64_t *row_offsets, const int32_t *slots,
+                            size_t pool_streams, size_t cols, size_t left, size_t right, size_t stride, float *pool, float *out);
+int ss_splice_stream_flush_device(size_t n_active, const int32_t *d_slots, size_t pool_streams, size_t cols, size_t left,
+                                  size_t right, size_t stride, float *d_pool, float *d_out, void *stream);
+int ss_splice_stream_flush(size_t n_active, const int32_t *slots, size_t pool_streams, size_t cols, size_t left, size_t right,
+                           size_t stride, float *pool, float *out);
+
 /* ---- polyphase windowed-sinc resampling ahead of the feature calls ----
  * Every call above takes audio at the rate its ss_params was built for; these calls bring telephony (8 kHz), capture (48 kHz) and
  * corpus (44.1 kHz) audio to it on the device, on the packed layout and the stream pools of the feature calls, from floats or 16-bit

@@ -579,6 +579,20 @@ inline std::vector<float> add_deltas_packed(const std::vector<float> &vec, const
     return out;
 }
 
+// Frame splicing and subsampling of every clip of a packed block on its own rows (ss_splice_packed): output row k of a clip is its rows
+// k * stride - left .. k * stride + right side by side, clamped to the clip (bit copies); ceil(T_b / stride) rows of (left + 1 + right)
+// * cols floats per clip, in the clips' order.  left, right at most 32, stride 1 .. 32.  A dense matrix: offsets = {0, rows}
+inline std::vector<float> splice_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t left, size_t right,
+                                        size_t stride = 1)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty() || left > 32 || right > 32) throw Error(SS_ERR_ARG, "splice_packed: shape mismatch");
+    std::vector<int64_t> out_offsets(offsets.size());
+    check(ss_splice_packed_offsets(offsets.size() - 1, offsets.data(), stride, out_offsets.data()));
+    std::vector<float> out(static_cast<size_t>(out_offsets.back()) * (left + 1 + right) * cols);
+    check(ss_splice_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, left, right, stride, out.data()));
+    return out;
+}
+
 inline std::vector<float> cmvnw_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t win_size = 301,
                                        bool variance_normalization = false)
 {

@@ -98,35 +98,7 @@ __global__ __launch_bounds__(256) void ss_add_deltas_packed_kernel(const float *
 // the history is the whole stream, so row 0 is stream row 0 and clamping there is the definition's; where count == 2L no tap
 // reaches below row 0.  Output row k is centred on row v = count + k - L (v < 0: a warm-up row of zeros); its last tap is row
 // count + k, which has just arrived.  The flush build has no new rows: it writes the L rows centred on count - L .. count - 1,
-// clamped at the stream's last row, and zeroes the pool row.
-struct StreamEntry {
-    unsigned long long row0;  // first row of the entry in vec / out (flush: in out)
-    unsigned rows;            // new rows
-    unsigned count;           // valid history rows, 0 .. 2L
-    float *state;             // the entry's pool row; nullptr: a rejected entry
-};
-
-template <bool FLUSH>
-__device__ __forceinline__ StreamEntry delta_stream_entry(const long long *__restrict__ ro, const int *__restrict__ slots, unsigned long long total_rows,
-                                                          unsigned pool_streams, float *pool, unsigned state_len, unsigned hist, unsigned lag)
-{
-    StreamEntry e{0, 0, 0, nullptr};
-    const int slot = slots[blockIdx.x];
-    if (slot < 0 || static_cast<unsigned>(slot) >= pool_streams) return e;
-    if (FLUSH) {
-        e.row0 = static_cast<unsigned long long>(blockIdx.x) * lag;
-    } else {
-        const long long lo = ro[blockIdx.x], hi = ro[blockIdx.x + 1];
-        if (!(lo >= 0 && lo < hi && static_cast<unsigned long long>(hi) <= total_rows)) return e;
-        e.row0 = static_cast<unsigned long long>(lo);
-        e.rows = static_cast<unsigned>(hi - lo);  // total_rows < 2^31: the row count fits
-    }
-    e.state = pool + static_cast<size_t>(slot) * state_len;
-    const float cw = e.state[state_len - 1];
-    if (cw >= 0.0f && cw <= static_cast<float>(hist) && cw == floorf(cw)) e.count = static_cast<unsigned>(cw);
-    return e;
-}
-
+// clamped at the stream's last row, and zeroes the pool row.  (RowPoolEntry, row_pool_entry: ss_device.h)
 constexpr unsigned kStreamRows = 128;  // rows (history + new) an entry may stage per column tile: 128 x 32 floats = 16 KiB
 constexpr unsigned kStreamMove = 4;    // pool-row floats a thread moves per step of the advance in global memory
 
@@ -158,7 +130,7 @@ __global__ __launch_bounds__(256) void ss_add_deltas_stream_kernel(const float *
 {
     __shared__ float tile[kStreamRows * kColTile];
     const unsigned L = tp.lag, hist = 2 * L, state_len = hist * cols + 1, ocols = (tp.order + 1) * cols;
-    const StreamEntry e = delta_stream_entry<FLUSH>(ro, slots, total_rows, pool_streams, pool, state_len, hist, L);
+    const RowPoolEntry e = row_pool_entry<FLUSH>(ro, slots, total_rows, pool_streams, pool, state_len, hist, L);
     if (!e.state || (!FLUSH && e.rows == 0)) return;  // the whole workgroup: the pool row stays as it is
     const unsigned rows = e.rows, count = e.count;
     const unsigned n_out = FLUSH ? L : rows;

@@ -332,6 +332,37 @@ inline unsigned packed_split(size_t n_clips, unsigned long long most_useful)
     return static_cast<unsigned>(std::min<unsigned long long>(64, std::min(want, std::max<unsigned long long>(1, most_useful))));
 }
 
+// The pools of raw feature rows (ss_deltas.hip, ss_splice.hip): entry i = blockIdx.x owns rows ro[i] .. ro[i+1] of the blocks and
+// pool row slots[i] of state_len = hist * cols + 1 floats -- the stream's last `hist` raw rows (oldest first, right-aligned, zeros
+// in front) and, in the last float, how many of them are valid.  An entry with a slot outside the pool, or (not the flush) a pair
+// that is empty, reversed, starts below 0 or ends past total_rows, comes back with state == nullptr; a count word that is not an
+// integer in [0, hist] is read as 0.  The flush build has no table: entry i owns rows i * flush_rows .. of out.
+struct RowPoolEntry {
+    unsigned long long row0;  // first row of the entry in vec / out (flush: in out)
+    unsigned rows;            // new rows
+    unsigned count;           // valid history rows, 0 .. hist
+    float *state;             // the entry's pool row; nullptr: a rejected entry
+};
+template <bool FLUSH>
+__device__ __forceinline__ RowPoolEntry row_pool_entry(const long long *__restrict__ ro, const int *__restrict__ slots, unsigned long long total_rows,
+                                                      unsigned pool_streams, float *pool, unsigned state_len, unsigned hist, unsigned flush_rows)
+{
+    RowPoolEntry e{0, 0, 0, nullptr};
+    const int slot = slots[blockIdx.x];
+    if (slot < 0 || static_cast<unsigned>(slot) >= pool_streams) return e;
+    if (FLUSH) {
+        e.row0 = static_cast<unsigned long long>(blockIdx.x) * flush_rows;
+    } else {
+        const long long lo = ro[blockIdx.x], hi = ro[blockIdx.x + 1];
+        if (!(lo >= 0 && lo < hi && static_cast<unsigned long long>(hi) <= total_rows)) return e;
+        e.row0 = static_cast<unsigned long long>(lo);
+        e.rows = static_cast<unsigned>(hi - lo);  // total_rows < 2^31: the row count fits
+    }
+    e.state = pool + static_cast<size_t>(slot) * state_len;
+    const float cw = e.state[state_len - 1];
+    if (cw >= 0.0f && cw <= static_cast<float>(hist) && cw == floorf(cw)) e.count = static_cast<unsigned>(cw);
+    return e;
+}
 // the streaming build of ss_front_generic's STFT / mel path (any fft_points, chirp-z included): a as for launch_front_generic's
 // STFT path, on the chunk (n_pad 0 and real_rows = rows in continuous mode)
 hipError_t launch_front_generic_stream(const FrontArgs &a, const StreamArgs &s, uint32_t log2c, hipStream_t stream, int num_cus,

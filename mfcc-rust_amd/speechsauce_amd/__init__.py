@@ -27,6 +27,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "MelSpectrogramStream", "StftStream",
            "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool", "CmvnStreamPool",
            "add_deltas", "add_deltas_packed", "AddDeltasStreamPool",
+           "splice", "splice_packed", "lfr", "lfr_packed", "SpliceStreamPool",
            "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "KaldiFbankStreamPool", "KaldiMfccStreamPool",
@@ -1936,6 +1937,200 @@ class AddDeltasStreamPool(_SidePool):
                     d_sl = torch.from_numpy(sl).to(state.device)
                     _lib.check(lib.ss_add_deltas_stream_flush_device(n_active, d_sl.data_ptr(), self.pool_streams, self.cols, self.order,
                                                                      self.window, state.data_ptr(), out.data_ptr(), _stream_ptr()))
+                    d_sl.record_stream(torch.cuda.current_stream())
+        if n_active:
+            self.rows_seen[sl] = 0
+        return out
+
+
+# ---- frame splicing and subsampling (Kaldi's splice-feats / subsample-feats, low frame rate; ss_splice_*) ----------------------
+# out row k = [x[k * stride - left] | .. | x[k * stride] | .. | x[k * stride + right]], indices clamped to the clip's own rows:
+# (left + 1 + right) * cols floats, every one a bit copy; ceil(T / stride) rows.
+
+def _check_splice_params(left, right, stride, what):
+    left, right, stride = int(left), int(right), int(stride)
+    if not 0 <= left <= 32 or not 0 <= right <= 32:
+        raise ValueError(f"{what}: left and right must be in 0 .. 32")
+    if not 1 <= stride <= 32:
+        raise ValueError(f"{what}: stride must be in 1 .. 32")
+    return left, right, stride
+
+
+def _lfr_params(m, n, what):
+    m = int(m)
+    if m < 1:
+        raise ValueError(f"{what}: m must be at least 1")
+    return (m - 1) // 2, m - 1 - (m - 1) // 2, n
+
+
+def splice_packed(rows, row_offsets, left, right, stride=1):
+    """Context splicing and frame subsampling of every clip of a packed block [sum T_b, cols] on its own rows, one launch for all
+    clips: -> (out [sum ceil(T_b / stride), (left + 1 + right) * cols], out_offsets).  Output row k of a clip is its rows ``k *
+    stride - left .. k * stride + right`` side by side, the index clamped to the clip's first and last row; every float is a bit
+    copy.  ``stride = 1`` is Kaldi's ``splice-feats``, ``left = right = 0`` its ``subsample-feats``.  numpy in -> the host-pointer
+    call and a numpy ``out_offsets``; a ROCm tensor stays on the device (current stream) and ``out_offsets`` is a device tensor.
+    ``row_offsets`` may be the device tensor ``mfcc_packed`` returned (it is read back: the output's size depends on it) or a host
+    array.  See ``ss_splice_packed`` in ``include/speechsauce_amd.h``."""
+    what = "splice_packed"
+    left, right, stride = _check_splice_params(left, right, stride, what)
+    lib = _lib.lib()
+    x, on_device, total_rows, cols = _packed_block(rows, None, what)
+    ro, n = _segment_table(row_offsets, False, None, total_rows, what)  # on the host, validated
+    oo = np.empty_like(ro)
+    _lib.check(lib.ss_splice_packed_offsets(n, ro.ctypes.data, stride, oo.ctypes.data))
+    out_rows, ocols = int(oo[-1]), (left + 1 + right) * cols
+    if on_device:
+        import torch
+
+        out = torch.empty((out_rows, ocols), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            d_ro, d_oo = torch.from_numpy(ro).to(x.device), torch.from_numpy(oo).to(x.device)
+            _lib.check(lib.ss_splice_packed_device(x.data_ptr(), n, d_ro.data_ptr(), total_rows, d_oo.data_ptr(), out_rows, cols, left, right, stride,
+                                                   out.data_ptr(), _stream_ptr()))
+            for t in (x, d_ro, d_oo):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                t.record_stream(torch.cuda.current_stream())
+        return out, d_oo
+    out = np.empty((out_rows, ocols), dtype=np.float32)
+    _lib.check(lib.ss_splice_packed(x.ctypes.data, n, ro.ctypes.data, total_rows, cols, left, right, stride, out.ctypes.data))
+    return out, oo
+
+
+def splice(x, left, right, stride=1):
+    """``splice_packed`` of one matrix [T, cols] -> [ceil(T / stride), (left + 1 + right) * cols], or of every matrix of a batch
+    [..., T, cols] on its own rows (equal-length clips of one packed block, one launch)."""
+    x = _require_f32(x, tuple(range(2, 9)), "splice")
+    shape = tuple(int(v) for v in x.shape)
+    T, cols = shape[-2], shape[-1]
+    n = int(np.prod(shape[:-2], dtype=np.int64))
+    out, _ = splice_packed(x.reshape(n * T, cols), np.arange(n + 1, dtype=np.int64) * T, left, right, stride)
+    return out.reshape(shape[:-2] + (-(-T // int(stride)), out.shape[1]))
+
+
+def lfr_packed(rows, row_offsets, m, n):
+    """Low frame rate on packed clips: stack ``m`` frames, skip ``n`` (FunASR's ``apply_lfr(m, n)``) = ``splice_packed`` with ``left =
+    (m - 1) // 2, right = m - 1 - left, stride = n``."""
+    return splice_packed(rows, row_offsets, *_lfr_params(m, n, "lfr_packed"))
+
+
+def lfr(x, m, n):
+    """Low frame rate of one matrix or a batch: ``splice`` with ``left = (m - 1) // 2, right = m - 1 - left, stride = n``."""
+    return splice(x, *_lfr_params(m, n, "lfr"))
+
+
+class SpliceStreamPool(_SidePool):
+    """``splice`` over the rows of live streams.  A stream is fed whole periods of ``stride`` rows and gets one output row per period,
+    ``delay_rows = right // stride`` periods late (all zeros while the output index is negative: the first ``delay_rows`` rows after
+    a reset are warm-up rows); it carries ``delay_rows * stride + left`` raw rows.  ``pool(rows, row_offsets, slots)`` takes the
+    ``(rows, row_offsets)`` pair of a feature / ``CmvnStreamPool`` / ``AddDeltasStreamPool`` call and the ``slots`` that call was
+    given and returns ``[total_rows // stride, (left + 1 + right) * cols]``: entry i's rows are ``row_offsets[i] // stride ..
+    row_offsets[i + 1] // stride``.  ``flush(slots)`` returns the last ``delay_rows`` rows of those streams, ``[len(slots) *
+    delay_rows, out_cols]``, and makes them fresh.  However a stream is cut into calls, its rows plus the flush, the first
+    ``delay_rows`` dropped, are bit for bit ``splice`` of the whole clip; a stream whose length is not a whole number of periods
+    repeats its last row up to one before its last call.  ``rows_seen`` (int64 per slot, on the host) moves only after a call went
+    through.  numpy in -> the host-pointer calls, ROCm tensors in -> the device calls on the current stream.  See
+    ``ss_splice_stream_packed`` in ``include/speechsauce_amd.h``."""
+
+    _what = "SpliceStreamPool"
+
+    def __init__(self, pool_streams, cols, left, right, stride=1):
+        what = self._what
+        if int(pool_streams) < 1:
+            raise ValueError(f"{what}: pool_streams must be at least 1")
+        if int(cols) < 1:
+            raise ValueError(f"{what}: cols must be at least 1")
+        self.left, self.right, self.stride = _check_splice_params(left, right, stride, what)
+        self.pool_streams = int(pool_streams)
+        self.cols = int(cols)
+        self.out_cols = (self.left + 1 + self.right) * self.cols
+        L, D = C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.lib().ss_splice_stream_state_len(self.cols, self.left, self.right, self.stride, C.byref(L), C.byref(D)))
+        self.state_len, self.delay_rows = L.value, D.value
+        self.rows_seen = np.zeros(self.pool_streams, dtype=np.int64)
+        self._state = None
+        self._where = None
+
+    @property
+    def state(self):
+        """[pool_streams, (delay_rows * stride + left) * cols + 1] float32: a torch tensor on the device of the first rows, or a
+        numpy array; None before the first call."""
+        return self._state
+
+    def reset(self, slots=None):
+        """Zero the state (and ``rows_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
+        idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
+        if slots is None:
+            self.rows_seen[:] = 0
+            if self._state is not None:
+                self._state[...] = 0
+        elif idx:
+            self.rows_seen[idx] = 0
+            if self._state is not None:
+                self._state[idx] = 0
+
+    def _scalars(self):
+        return self.pool_streams, self.cols, self.left, self.right, self.stride
+
+    def __call__(self, rows, row_offsets, slots):
+        what = self._what
+        x = _require_f32(rows, (2,), what)
+        if int(x.shape[1]) != self.cols:
+            raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool takes {self.cols}")
+        total_rows = int(x.shape[0])
+        ro = self._offsets(row_offsets)
+        slot_list = self._slots(slots)
+        self._check_offsets(ro, len(slot_list), total_rows)
+        if (np.diff(ro) % self.stride).any():
+            raise ValueError(f"{what}: every entry must bring whole periods of {self.stride} rows")
+        where = self._place(x)
+        lib, n_active = _lib.lib(), len(slot_list)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        state = self._state_for(x)
+        out_rows = total_rows // self.stride
+        if _is_torch(x):
+            import torch
+
+            x = x.contiguous()
+            out = torch.empty((out_rows, self.out_cols), dtype=torch.float32, device=x.device)
+            if n_active and total_rows:
+                with torch.cuda.device(x.device):
+                    d_ro, d_sl = torch.from_numpy(ro).to(x.device), torch.from_numpy(sl).to(x.device)
+                    _lib.check(lib.ss_splice_stream_packed_device(x.data_ptr(), n_active, d_ro.data_ptr(), total_rows, d_sl.data_ptr(),
+                                                                  *self._scalars(), state.data_ptr(), out.data_ptr(), _stream_ptr()))
+                    for t in (x, d_ro, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                        t.record_stream(torch.cuda.current_stream())
+        else:
+            x = np.ascontiguousarray(x)
+            out = np.empty((out_rows, self.out_cols), dtype=np.float32)
+            if n_active and total_rows:
+                _lib.check(lib.ss_splice_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, *self._scalars(), state.ctypes.data,
+                                                       out.ctypes.data))
+        self._state, self._where = state, where  # only once the call went through
+        if n_active:
+            self.rows_seen[sl] += np.diff(ro)
+        return out
+
+    def flush(self, slots):
+        """The last ``delay_rows`` rows of the given streams, ``[len(slots) * delay_rows, out_cols]`` (entry i: rows i * delay_rows ..
+        (i + 1) * delay_rows; zeros where the output index is negative); afterwards those streams are fresh.  Before the pool's first
+        call there is no state anywhere: the rows are zeros in a numpy array."""
+        slot_list = self._slots(slots)
+        lib, n_active = _lib.lib(), len(slot_list)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        D = self.delay_rows
+        if self._state is None or not _is_torch(self._state):
+            out = np.zeros((n_active * D, self.out_cols), dtype=np.float32)
+            if n_active and self._state is not None:
+                _lib.check(lib.ss_splice_stream_flush(n_active, sl.ctypes.data, *self._scalars(), self._state.ctypes.data, out.ctypes.data))
+        else:
+            import torch
+
+            state = self._state
+            out = torch.empty((n_active * D, self.out_cols), dtype=torch.float32, device=state.device)
+            if n_active:
+                with torch.cuda.device(state.device):
+                    d_sl = torch.from_numpy(sl).to(state.device)
+                    _lib.check(lib.ss_splice_stream_flush_device(n_active, d_sl.data_ptr(), *self._scalars(), state.data_ptr(), out.data_ptr(),
+                                                                 _stream_ptr()))
                     d_sl.record_stream(torch.cuda.current_stream())
         if n_active:
             self.rows_seen[sl] = 0
