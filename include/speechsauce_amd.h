@@ -919,6 +919,101 @@ int ss_splice_stream_flush_device(size_t n_active, const int32_t *d_slots, size_
 int ss_splice_stream_flush(size_t n_active, const int32_t *slots, size_t pool_streams, size_t cols, size_t left, size_t right,
                            size_t stride, float *pool, float *out);
 
+/* ---- energy voice-activity decision and voiced-row selection on packed clips and over a pool of stream states ----
+ * The two stages a speaker-recognition front end (x-vector / i-vector recipes, diarisation) takes behind the feature rows: Kaldi's
+ * compute-vad-energy, a per-frame speech / non-speech decision from the log-energy column, and select-voiced-frames, which drops
+ * the unvoiced rows of every clip.  The reference crate has neither: this comment is the specification.
+ *   Parameters: cols >= 1; energy_col < cols; energy_threshold and energy_mean_scale finite; L = frames_context in [0, 32] (the
+ *   bound of ss_add_deltas*' lag); 0 < proportion_threshold < 1 (Kaldi's assertion).  Kaldi's defaults are 5.0 / 0.5 / 0 / 0.6,
+ *   the x-vector recipes use 5.5 / 0.5 / 2 / 0.12.
+ *   One clip of T rows, e[t] = vec[t][energy_col]:
+ *     thr = (double)energy_threshold + (double)energy_mean_scale * mean, a rounded f64 product and a rounded f64 sum; mean = s1 / T
+ *     in f64, where s1 is formed in exactly the order in which ss_cmvn_packed* forms a column's sum: chunks = min(64, ceil(T / 32)),
+ *     rpc = ceil(T / chunks), every chunk a serial f64 sum of its rpc rows (the last chunks may be short or empty), the chunk sums
+ *     added serially in chunk order.  So the mean is bit for bit the mean ss_cmvn_packed* subtracts from that column.  Where
+ *     energy_mean_scale == 0 the mean is not formed: thr = (double)energy_threshold, whatever the column holds elsewhere.
+ *     Row u is raw-voiced iff (double)e[u] > thr (a NaN energy, or a NaN thr, compares false).
+ *     num[t] = raw-voiced rows among t - L .. t + L that lie inside the clip; den[t] = the rows among them inside the clip.
+ *     mask[t] = ((float)num[t] >= (float)den[t] * proportion_threshold) ? 1 : 0, the product ONE f32 multiply (Kaldi's int x float).
+ *   THE ONE DEPARTURE FROM KALDI: thr is kept in f64, where Kaldi rounds energy_threshold + energy_mean_scale * mean to float
+ *   before comparing.  A decision can differ from Kaldi's only for an energy within one float ulp of the threshold.
+ * Packed clips, the decision (ss_vad_energy_packed*): vec is [total_rows x cols], clip b owns rows offsets[b] .. offsets[b+1] (a
+ * device table of n_clips + 1 entries that only the kernel reads); d_mask [total_rows] gets one byte 0 / 1 per row, d_counts
+ * [n_clips] (may be NULL) the voiced rows of every clip.  One launch (ss_vad_energy_packed_kernel) whatever the clip count; long
+ * clips share workgroups and the bits do not depend on the split; no atomics.  Containment is that of ss_cmvn_packed_device: a
+ * segment that is reversed, starts below 0 or ends past total_rows is skipped -- its mask bytes and its count word are left
+ * unwritten -- and nothing outside [0, total_rows) is touched.  A valid clip without rows writes count 0.  n_clips == 0 is SS_OK
+ * without a device.  SS_ERR_ARG, decided before the device is touched: null buffers (d_counts apart); cols == 0; energy_col >=
+ * cols; L > 32; proportion_threshold outside (0, 1) or not finite; a non-finite threshold or mean scale; n_clips, total_rows or
+ * cols >= 2^31.  The host form checks the table first and names the first bad clip (the rules of ss_cmvn_packed). */
+int ss_vad_energy_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols,
+                                size_t energy_col, float energy_threshold, float energy_mean_scale, size_t frames_context,
+                                float proportion_threshold, uint8_t *d_mask, int64_t *d_counts, void *stream);
+int ss_vad_energy_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols,
+                         size_t energy_col, float energy_threshold, float energy_mean_scale, size_t frames_context,
+                         float proportion_threshold, uint8_t *mask, int64_t *counts);
+/* Packed clips, the selection (ss_select_rows_packed*): d_mask [total_rows] is ANY byte mask, a byte != 0 keeps its row.  The call
+ * writes d_out_offsets [n_clips + 1]: oo[0] = 0, oo[b+1] = oo[b] + kept rows of clip b (a skipped segment contributes 0); clip b's
+ * kept rows, in order, are rows oo[b] .. oo[b+1] of d_out [total_rows x cols] (the caller gives room for every row).  Every float is
+ * a BIT COPY, as in ss_splice_*.  Rows at and past oo[n_clips] are left unwritten.  The device form is asynchronous with no
+ * read-back: three launches (count, scan, move) whatever n_clips and total_rows, and one stream-ordered scratch block as
+ * ss_cmvnw_packed_device uses; total_rows == 0 is one memset of the table.  d_out_offsets with total_rows as the bound is a valid
+ * table for ss_cmvn_packed_device, ss_cmvnw_packed_device, ss_add_deltas_packed_device and ss_splice_packed_device, so the chain
+ * goes on without the host ever learning the sizes.  Containment: a segment that is reversed, starts below 0 or ends past
+ * total_rows keeps no row; a clip whose rows would end past total_rows (only a table whose clips overlap can ask for that) has no
+ * row written; nothing outside the blocks is touched.  n_clips == 0 is SS_OK without a device (nothing is written).  SS_ERR_ARG,
+ * decided before the device is touched: null buffers; cols == 0; n_clips, total_rows or cols >= 2^31; out overlapping vec or the
+ * mask.  The host form checks the table first, names the first bad clip, and returns the table and the rows it covers. */
+int ss_select_rows_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_row_offsets, size_t total_rows, size_t cols,
+                                 const uint8_t *d_mask, int64_t *d_out_offsets, float *d_out, void *stream);
+int ss_select_rows_packed(const float *vec, size_t n_clips, const int64_t *row_offsets, size_t total_rows, size_t cols,
+                          const uint8_t *mask, int64_t *out_offsets, float *out);
+/* Pool of stream states, the decision only (ss_vad_energy_stream_*), on the row_offsets / slots of the feature pool call, with a
+ * fixed latency of L = frames_context rows exactly as the add-deltas pool: an entry gets as many mask bytes as it brought rows,
+ * the first L bytes of a fresh stream are 0 (warm-up), and the flush gives a stream's last L decisions.
+ *   The causal threshold: the decision for stream row t uses thr_t = energy_threshold + energy_mean_scale * (S_n / n) in f64 (a
+ *   division, a product and a sum, each rounded), n = min(t + L + 1, rows seen): every row that has arrived when t is decided, all
+ *   rows in the flush.  S_n is ONE f64 accumulator advanced row by row in stream order -- that order is the definition.  Every
+ *   member of the window t - L .. t + L is compared against thr_t; the window is clipped at the stream's first row and, in the
+ *   flush, at its last.  With energy_mean_scale == 0 thr_t = energy_threshold (the accumulator is still advanced).
+ *   Pool: a caller-owned block [pool_streams x len] of floats, len = ss_vad_energy_stream_state_len = 2 L + 4: the low and the high
+ *   half of the f64 sum, bit-cast; the rows seen as a bit-cast uint32 (a stream of more than 2^32 - 1 rows is out of contract);
+ *   the stream's last 2 L energies, oldest first, right-aligned, zeros in front; the count word min(rows seen, 2 L) as a float,
+ *   last.  All zeros = fresh stream.  A count word that is not an integer in [0, 2 L], or rows seen below the count, reads as fresh.
+ *   Entry i owns rows ro[i] .. ro[i+1] of vec, the same bytes of mask and pool row slots[i].  Byte k is the decision for stream row
+ *   seen + k - L (0 where that is negative).  An entry without rows writes nothing and leaves its pool row bit for bit.
+ *   Flush: entry i gets exactly L bytes, mask[i*L .. (i+1)*L): the decisions for rows seen - L .. seen - 1 (0 where negative);
+ *   afterwards the pool row is all zeros.  L == 0: no bytes, d_mask may be NULL, and the pool rows are still zeroed.
+ *   Invariants: with energy_mean_scale == 0, all of a stream's bytes plus the flush, the first L dropped, are ss_vad_energy_packed*
+ *   on the whole clip byte for byte, however the stream was cut.  With a non-zero scale they are the causal definition's bytes,
+ *   and the final pool rows do not depend on the cut.
+ *   One launch each (ss_vad_energy_stream_kernel), one workgroup per entry, one kernel node whose grid depends on n_active only,
+ *   asynchronous on `stream`, no allocation, no scratch.  Containment as ss_add_deltas_stream_*: an entry is served only if 0 <=
+ *   ro[i] <= ro[i+1] <= total_rows and 0 <= slots[i] < pool_streams (flush: the slot rule); a skipped entry has no byte written and
+ *   its pool row untouched.  Duplicate slots in a device-form call are a caller error that is NOT detected; the host forms reject
+ *   them.
+ * Arguments: n_active == 0 is SS_OK with nothing launched, also without a device.  SS_ERR_ARG, decided before the device is
+ * touched, pool and mask untouched: null buffers; the scalar rules above; n_active, pool_streams, total_rows or cols >= 2^31;
+ * pool_streams == 0; mask overlapping vec; the pool overlapping vec or mask.  The host forms also check the tables first -- ro[0] !=
+ * 0, a decreasing pair, a slot outside the pool, a slot named twice; ss_last_error_string() names the first bad entry -- gather and
+ * scatter the named pool rows, and write the caller's pool last. */
+/* host only, no device: len = 2 * frames_context + 4 */
+int ss_vad_energy_stream_state_len(size_t frames_context, size_t *state_len);
+int ss_vad_energy_stream_packed_device(const float *d_vec, size_t n_active, const int64_t *d_row_offsets, size_t total_rows,
+                                       const int32_t *d_slots, size_t pool_streams, size_t cols, size_t energy_col,
+                                       float energy_threshold, float energy_mean_scale, size_t frames_context,
+                                       float proportion_threshold, float *d_pool, uint8_t *d_mask, void *stream);
+int ss_vad_energy_stream_packed(const float *vec, size_t n_active, const int64_t *row_offsets, const int32_t *slots,
+                                size_t pool_streams, size_t cols, size_t energy_col, float energy_threshold,
+                                float energy_mean_scale, size_t frames_context, float proportion_threshold, float *pool,
+                                uint8_t *mask);
+int ss_vad_energy_stream_flush_device(size_t n_active, const int32_t *d_slots, size_t pool_streams, float energy_threshold,
+                                      float energy_mean_scale, size_t frames_context, float proportion_threshold, float *d_pool,
+                                      uint8_t *d_mask, void *stream);
+int ss_vad_energy_stream_flush(size_t n_active, const int32_t *slots, size_t pool_streams, float energy_threshold,
+                               float energy_mean_scale, size_t frames_context, float proportion_threshold, float *pool,
+                               uint8_t *mask);
+
 /* ---- polyphase windowed-sinc resampling ahead of the feature calls ----
  * Every call above takes audio at the rate its ss_params was built for; these calls bring telephony (8 kHz), capture (48 kHz) and
  * corpus (44.1 kHz) audio to it on the device, on the packed layout and the stream pools of the feature calls, from floats or 16-bit

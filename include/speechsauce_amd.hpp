@@ -593,6 +593,34 @@ inline std::vector<float> splice_packed(const std::vector<float> &vec, const std
     return out;
 }
 
+// Kaldi compute-vad-energy of every clip of a packed block on its own rows (ss_vad_energy_packed): one byte 0 / 1 per row, and (where
+// `counts` is given) the voiced rows of every clip.  The defaults are Kaldi's; the x-vector recipes use 5.5 / 0.5 / 2 / 0.12.  A dense
+// matrix: offsets = {0, rows}
+inline std::vector<uint8_t> vad_energy_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t energy_col = 0,
+                                              float energy_threshold = 5.0f, float energy_mean_scale = 0.5f, size_t frames_context = 0,
+                                              float proportion_threshold = 0.6f, std::vector<int64_t> *counts = nullptr)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty()) throw Error(SS_ERR_ARG, "vad_energy_packed: shape mismatch");
+    std::vector<uint8_t> mask(vec.size() / cols);
+    if (counts) counts->assign(offsets.size() - 1, 0);
+    check(ss_vad_energy_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, energy_col, energy_threshold, energy_mean_scale,
+                               frames_context, proportion_threshold, mask.data(), counts ? counts->data() : nullptr));
+    return mask;
+}
+
+// Kaldi select-voiced-frames on a packed block (ss_select_rows_packed): the rows whose mask byte is not 0, clip by clip in order (bit
+// copies), and in `out_offsets` the table of the result.  `mask` is any byte mask with one entry per row, vad_energy_packed's or another
+inline std::vector<float> select_rows_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols,
+                                             const std::vector<uint8_t> &mask, std::vector<int64_t> &out_offsets)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty() || mask.size() != vec.size() / cols) throw Error(SS_ERR_ARG, "select_rows_packed: shape mismatch");
+    std::vector<float> out(vec.size());
+    out_offsets.assign(offsets.size(), 0);
+    check(ss_select_rows_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, mask.data(), out_offsets.data(), out.data()));
+    out.resize(static_cast<size_t>(out_offsets.back()) * cols);
+    return out;
+}
+
 inline std::vector<float> cmvnw_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t win_size = 301,
                                        bool variance_normalization = false)
 {

@@ -179,6 +179,30 @@ extern "C" {
                                    cols: usize, order: usize, window: usize, pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_add_deltas_stream_flush(n_active: usize, slots: *const i32, pool_streams: usize, cols: usize, order: usize, window: usize,
                                   pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_vad_energy_packed_device(d_vec: *const f32, n_clips: usize, d_offsets: *const i64, total_rows: usize, cols: usize,
+                                   energy_col: usize, energy_threshold: f32, energy_mean_scale: f32, frames_context: usize,
+                                   proportion_threshold: f32, d_mask: *mut u8, d_counts: *mut i64, stream: *mut c_void) -> c_int;
+    fn ss_vad_energy_packed(vec: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize, energy_col: usize,
+                            energy_threshold: f32, energy_mean_scale: f32, frames_context: usize, proportion_threshold: f32,
+                            mask: *mut u8, counts: *mut i64) -> c_int;
+    fn ss_select_rows_packed_device(d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize,
+                                    d_mask: *const u8, d_out_offsets: *mut i64, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_select_rows_packed(vec: *const f32, n_clips: usize, row_offsets: *const i64, total_rows: usize, cols: usize,
+                             mask: *const u8, out_offsets: *mut i64, out: *mut f32) -> c_int;
+    fn ss_vad_energy_stream_state_len(frames_context: usize, state_len: *mut usize) -> c_int;
+    fn ss_vad_energy_stream_packed_device(d_vec: *const f32, n_active: usize, d_row_offsets: *const i64, total_rows: usize,
+                                          d_slots: *const i32, pool_streams: usize, cols: usize, energy_col: usize,
+                                          energy_threshold: f32, energy_mean_scale: f32, frames_context: usize,
+                                          proportion_threshold: f32, d_pool: *mut f32, d_mask: *mut u8, stream: *mut c_void) -> c_int;
+    fn ss_vad_energy_stream_packed(vec: *const f32, n_active: usize, row_offsets: *const i64, slots: *const i32, pool_streams: usize,
+                                   cols: usize, energy_col: usize, energy_threshold: f32, energy_mean_scale: f32,
+                                   frames_context: usize, proportion_threshold: f32, pool: *mut f32, mask: *mut u8) -> c_int;
+    fn ss_vad_energy_stream_flush_device(n_active: usize, d_slots: *const i32, pool_streams: usize, energy_threshold: f32,
+                                         energy_mean_scale: f32, frames_context: usize, proportion_threshold: f32, d_pool: *mut f32,
+                                         d_mask: *mut u8, stream: *mut c_void) -> c_int;
+    fn ss_vad_energy_stream_flush(n_active: usize, slots: *const i32, pool_streams: usize, energy_threshold: f32,
+                                  energy_mean_scale: f32, frames_context: usize, proportion_threshold: f32, pool: *mut f32,
+                                  mask: *mut u8) -> c_int;
     fn ss_resample_packed_offsets(orig_rate: u32, new_rate: u32, n_clips: usize, sample_offsets: *const i64, out_offsets: *mut i64) -> c_int;
     fn ss_resampler_create(orig_rate: u32, new_rate: u32, lowpass_filter_width: u32, rolloff: f32, out: *mut *mut c_void) -> c_int;
     fn ss_resampler_destroy(rs: *mut c_void);
@@ -1107,6 +1131,150 @@ pub fn try_add_deltas_stream_flush(slots: &[i32], cols: usize, order: usize, win
         ss_add_deltas_stream_flush(slots.len(), slots.as_ptr(), pool.nrows(), cols, order, window, pool.as_mut_ptr(), out.as_mut_ptr())
     })?;
     Ok(out)
+}
+
+/// The scalars of Kaldi's compute-vad-energy: a row is raw-voiced where its energy (column `energy_col`) is above `energy_threshold +
+/// energy_mean_scale * mean energy`, and voiced where at least `proportion_threshold` of the rows `t - frames_context .. t +
+/// frames_context` inside the clip are raw-voiced.  `Default` is Kaldi's (5.0 / 0.5 / 0 / 0.6); the x-vector recipes use 5.5 / 0.5 / 2
+/// / 0.12.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct VadEnergyOptions {
+    pub energy_col: usize,
+    pub energy_threshold: f32,
+    pub energy_mean_scale: f32,
+    pub frames_context: usize,
+    pub proportion_threshold: f32,
+}
+
+impl Default for VadEnergyOptions {
+    fn default() -> Self {
+        VadEnergyOptions { energy_col: 0, energy_threshold: 5.0, energy_mean_scale: 0.5, frames_context: 0, proportion_threshold: 0.6 }
+    }
+}
+
+/// Kaldi compute-vad-energy of every clip of a packed block on its own rows: one byte 0 / 1 per row and the voiced rows of every
+/// clip.  A dense matrix is the one-clip call `offsets = [0, rows]`.
+pub fn try_vad_energy_packed(vec: ArrayView2<f32>, offsets: &[i64], opts: VadEnergyOptions) -> Result<(Array1<u8>, Array1<i64>), Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    if offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "vad_energy_packed: offsets must not be empty".to_string() });
+    }
+    let mut mask = Array1::<u8>::zeros(rows);
+    let mut counts = Array1::<i64>::zeros(offsets.len() - 1);
+    check(unsafe {
+        ss_vad_energy_packed(x.as_ptr(), offsets.len() - 1, offsets.as_ptr(), rows, cols, opts.energy_col, opts.energy_threshold,
+                             opts.energy_mean_scale, opts.frames_context, opts.proportion_threshold, mask.as_mut_ptr(), counts.as_mut_ptr())
+    })?;
+    Ok((mask, counts))
+}
+
+/// Kaldi select-voiced-frames on a packed block: the rows whose `mask` byte is not 0, clip by clip in order (bit copies), and the
+/// table of the result.  `mask` is any byte mask with one entry per row.
+pub fn try_select_rows_packed(vec: ArrayView2<f32>, row_offsets: &[i64], mask: &[u8]) -> Result<(Array2<f32>, Vec<i64>), Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    if row_offsets.is_empty() || mask.len() != rows {
+        return Err(Error { status: SS_ERR_ARG, detail: "select_rows_packed: row_offsets must not be empty and mask needs one byte per row".to_string() });
+    }
+    let mut full = vec![0f32; rows * cols];
+    let mut out_offsets = vec![0i64; row_offsets.len()];
+    check(unsafe {
+        ss_select_rows_packed(x.as_ptr(), row_offsets.len() - 1, row_offsets.as_ptr(), rows, cols, mask.as_ptr(), out_offsets.as_mut_ptr(),
+                              full.as_mut_ptr())
+    })?;
+    let kept = out_offsets[row_offsets.len() - 1] as usize;
+    full.truncate(kept * cols);
+    let out = Array2::from_shape_vec((kept, cols), full).map_err(|e| Error { status: SS_ERR_ARG, detail: e.to_string() })?;
+    Ok((out, out_offsets))
+}
+
+/// Floats per stream of the pool `try_vad_energy_stream_packed` carries: `2 * frames_context + 4`.
+pub fn try_vad_energy_stream_state_len(frames_context: usize) -> Result<usize, Error> {
+    let mut len = 0usize;
+    check(unsafe { ss_vad_energy_stream_state_len(frames_context, &mut len) })?;
+    Ok(len)
+}
+
+/// The decision over the rows of live streams with a fixed latency of `frames_context` rows and a causal threshold: entry i owns rows
+/// `row_offsets[i] .. row_offsets[i + 1]` of `vec` and the same bytes of the result, and row `slots[i]` of `pool`, a `[pool_streams,
+/// try_vad_energy_stream_state_len]` block (all zeros: fresh streams).  Byte k of an entry is the decision for stream row `seen + k -
+/// frames_context`, 0 while that is negative.
+pub fn try_vad_energy_stream_packed(vec: ArrayView2<f32>, row_offsets: &[i64], slots: &[i32], opts: VadEnergyOptions,
+                                    pool: &mut Array2<f32>) -> Result<Array1<u8>, Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    let len = try_vad_energy_stream_state_len(opts.frames_context)?;
+    if row_offsets.len() != slots.len() + 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "row_offsets must have one entry more than slots".to_string() });
+    }
+    if pool.ncols() != len || !pool.is_standard_layout() {
+        return Err(Error { status: SS_ERR_ARG, detail: "pool must be a standard-layout [pool_streams, state_len] block".to_string() });
+    }
+    if row_offsets[slots.len()] < 0 || row_offsets[slots.len()] as usize > rows {
+        return Err(Error { status: SS_ERR_ARG, detail: "row_offsets ends past the block".to_string() });
+    }
+    let mut mask = Array1::<u8>::zeros(rows);
+    check(unsafe {
+        ss_vad_energy_stream_packed(x.as_ptr(), slots.len(), row_offsets.as_ptr(), slots.as_ptr(), pool.nrows(), cols, opts.energy_col,
+                                    opts.energy_threshold, opts.energy_mean_scale, opts.frames_context, opts.proportion_threshold,
+                                    pool.as_mut_ptr(), mask.as_mut_ptr())
+    })?;
+    Ok(mask)
+}
+
+/// The last `frames_context` decisions of the streams in `slots` (entry i: bytes `i * frames_context ..` of the result, the window
+/// clipped at the stream's last row, 0 for negative rows); afterwards their pool rows are zero (fresh streams).
+pub fn try_vad_energy_stream_flush(slots: &[i32], opts: VadEnergyOptions, pool: &mut Array2<f32>) -> Result<Array1<u8>, Error> {
+    let len = try_vad_energy_stream_state_len(opts.frames_context)?;
+    if pool.ncols() != len || !pool.is_standard_layout() {
+        return Err(Error { status: SS_ERR_ARG, detail: "pool must be a standard-layout [pool_streams, state_len] block".to_string() });
+    }
+    let mut mask = Array1::<u8>::zeros(slots.len() * opts.frames_context);
+    check(unsafe {
+        ss_vad_energy_stream_flush(slots.len(), slots.as_ptr(), pool.nrows(), opts.energy_threshold, opts.energy_mean_scale,
+                                   opts.frames_context, opts.proportion_threshold, pool.as_mut_ptr(), mask.as_mut_ptr())
+    })?;
+    Ok(mask)
+}
+
+/// The device forms of the five calls above (include/speechsauce_amd.h has the contracts): every pointer is a device pointer, the
+/// calls are asynchronous on `stream`, and nothing is read back.  `d_counts` may be null.
+///
+/// # Safety
+/// The pointers must be device allocations of the sizes the header names, alive until the stream has passed the call.
+pub unsafe fn vad_energy_packed_device(d_vec: *const f32, n_clips: usize, d_offsets: *const i64, total_rows: usize, cols: usize,
+                                       opts: VadEnergyOptions, d_mask: *mut u8, d_counts: *mut i64, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_vad_energy_packed_device(d_vec, n_clips, d_offsets, total_rows, cols, opts.energy_col, opts.energy_threshold, opts.energy_mean_scale,
+                                      opts.frames_context, opts.proportion_threshold, d_mask, d_counts, stream))
+}
+
+/// `d_out_offsets [n_clips + 1]` is written by the call; with `total_rows` as the bound it is a valid table for the packed calls
+/// behind it.  `d_out` has room for `total_rows` rows.
+///
+/// # Safety
+/// As `vad_energy_packed_device`.
+pub unsafe fn select_rows_packed_device(d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize,
+                                        d_mask: *const u8, d_out_offsets: *mut i64, d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_select_rows_packed_device(d_vec, n_clips, d_row_offsets, total_rows, cols, d_mask, d_out_offsets, d_out, stream))
+}
+
+/// # Safety
+/// As `vad_energy_packed_device`; no slot may be named twice in one call.
+pub unsafe fn vad_energy_stream_packed_device(d_vec: *const f32, n_active: usize, d_row_offsets: *const i64, total_rows: usize,
+                                              d_slots: *const i32, pool_streams: usize, cols: usize, opts: VadEnergyOptions, d_pool: *mut f32,
+                                              d_mask: *mut u8, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_vad_energy_stream_packed_device(d_vec, n_active, d_row_offsets, total_rows, d_slots, pool_streams, cols, opts.energy_col,
+                                             opts.energy_threshold, opts.energy_mean_scale, opts.frames_context, opts.proportion_threshold, d_pool,
+                                             d_mask, stream))
+}
+
+/// # Safety
+/// As `vad_energy_stream_packed_device`.
+pub unsafe fn vad_energy_stream_flush_device(n_active: usize, d_slots: *const i32, pool_streams: usize, opts: VadEnergyOptions, d_pool: *mut f32,
+                                             d_mask: *mut u8, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_vad_energy_stream_flush_device(n_active, d_slots, pool_streams, opts.energy_threshold, opts.energy_mean_scale, opts.frames_context,
+                                            opts.proportion_threshold, d_pool, d_mask, stream))
 }
 
 /// librosa's power_to_db of every clip of a packed block with the clip's own `top_db` floor (`None`: no floor); clip b's segment

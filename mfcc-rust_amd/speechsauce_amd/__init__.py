@@ -28,6 +28,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool", "CmvnStreamPool",
            "add_deltas", "add_deltas_packed", "AddDeltasStreamPool",
            "splice", "splice_packed", "lfr", "lfr_packed", "SpliceStreamPool",
+           "vad_energy", "vad_energy_packed", "select_rows", "select_rows_packed", "VadEnergyStreamPool",
            "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "KaldiFbankStreamPool", "KaldiMfccStreamPool",
@@ -2135,6 +2136,263 @@ class SpliceStreamPool(_SidePool):
         if n_active:
             self.rows_seen[sl] = 0
         return out
+
+
+# ---- energy voice-activity decision and voiced-row selection (Kaldi's compute-vad-energy / select-voiced-frames; ss_vad_* /
+# ss_select_rows_*) ---------------------------------------------------------------------------------------------------------------
+# mask[t] = (voiced rows among t - L .. t + L inside the clip) >= (rows among them inside the clip) * proportion_threshold, a row
+# being voiced where its energy is above energy_threshold + energy_mean_scale * (the clip's mean energy).
+
+def _check_vad_params(energy_col, cols, energy_threshold, energy_mean_scale, frames_context, proportion_threshold, what):
+    energy_col, L = int(energy_col), int(frames_context)
+    thr, scale, prop = float(energy_threshold), float(energy_mean_scale), float(proportion_threshold)
+    if cols is not None and not 0 <= energy_col < cols:
+        raise ValueError(f"{what}: energy_col must be in 0 .. {cols - 1}")
+    if energy_col < 0:
+        raise ValueError(f"{what}: energy_col must not be negative")
+    if not 0 <= L <= 32:
+        raise ValueError(f"{what}: frames_context must be in 0 .. 32")
+    if not (np.isfinite(np.float32(thr)) and np.isfinite(np.float32(scale))):
+        raise ValueError(f"{what}: energy_threshold and energy_mean_scale must be finite")
+    if not 0.0 < float(np.float32(prop)) < 1.0:
+        raise ValueError(f"{what}: proportion_threshold must lie strictly between 0 and 1")
+    return energy_col, thr, scale, L, prop
+
+
+def vad_energy_packed(vec, offsets, energy_col=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0, proportion_threshold=0.6):
+    """Kaldi ``compute-vad-energy`` of every clip of a packed block [sum T_b, cols] on its own rows, one launch for all clips: ->
+    (mask uint8 [sum T_b], counts int64 [n_clips]).  Row t of a clip is voiced where, among its rows ``t - frames_context .. t +
+    frames_context``, at least ``proportion_threshold`` of them have an energy (column ``energy_col``) above ``energy_threshold +
+    energy_mean_scale * mean energy of the clip``; ``counts`` are the voiced rows per clip.  The defaults are Kaldi's; the x-vector
+    recipes use 5.5 / 0.5 / 2 / 0.12.  numpy in -> the host-pointer call; a ROCm tensor stays on the device (current stream), and
+    ``offsets`` may be a device tensor or a host array, as for ``cmvn_packed``.  Bytes of rows that the table does not cover are left
+    uninitialised.  See ``ss_vad_energy_packed`` in ``include/speechsauce_amd.h``."""
+    what = "vad_energy_packed"
+    lib = _lib.lib()
+    x, on_device, rows, cols = _packed_block(vec, None, what)
+    if cols < 1:
+        raise ValueError(f"{what}: the block has no columns")
+    scalars = _check_vad_params(energy_col, cols, energy_threshold, energy_mean_scale, frames_context, proportion_threshold, what)
+    table, n = _segment_table(offsets, on_device, x.device if on_device else None, rows, what)
+    if rows == 0:  # no clip has a row: nothing for the device to do
+        if on_device:
+            import torch
+
+            return torch.empty(0, dtype=torch.uint8, device=x.device), torch.zeros(n, dtype=torch.int64, device=x.device)
+        return np.empty(0, dtype=np.uint8), np.zeros(n, dtype=np.int64)
+    if on_device:
+        import torch
+
+        mask = torch.empty(rows, dtype=torch.uint8, device=x.device)
+        counts = torch.empty(n, dtype=torch.int64, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.ss_vad_energy_packed_device(x.data_ptr(), n, table.data_ptr(), rows, cols, *scalars, mask.data_ptr(), counts.data_ptr(),
+                                                       _stream_ptr()))
+            for t in (x, table):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                t.record_stream(torch.cuda.current_stream())
+        return mask, counts
+    mask, counts = np.empty(rows, dtype=np.uint8), np.empty(n, dtype=np.int64)
+    _lib.check(lib.ss_vad_energy_packed(x.ctypes.data, n, table.ctypes.data, rows, cols, *scalars, mask.ctypes.data, counts.ctypes.data))
+    return mask, counts
+
+
+def vad_energy(feat, energy_col=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0, proportion_threshold=0.6):
+    """``vad_energy_packed`` of one matrix [T, cols] -> bool [T], or of every matrix of a batch [..., T, cols] on its own rows -> bool
+    [..., T] (equal-length clips of one packed block, one launch)."""
+    x = _require_f32(feat, tuple(range(2, 9)), "vad_energy")
+    shape = tuple(int(v) for v in x.shape)
+    T, cols = shape[-2], shape[-1]
+    n = int(np.prod(shape[:-2], dtype=np.int64))
+    mask, _ = vad_energy_packed(x.reshape(n * T, cols), np.arange(n + 1, dtype=np.int64) * T, energy_col, energy_threshold, energy_mean_scale,
+                                frames_context, proportion_threshold)
+    if _is_torch(mask):
+        return mask.bool().reshape(shape[:-1])
+    return mask.astype(bool).reshape(shape[:-1])
+
+
+def _row_mask(mask, on_device, device, total_rows, what):
+    """The byte mask of a selection next to its block: uint8 or bool, one entry per row."""
+    if _is_torch(mask):
+        import torch
+
+        if mask.dtype not in (torch.uint8, torch.bool):
+            raise TypeError(f"{what}: mask must be uint8 or bool, got {mask.dtype}")
+        if mask.dim() != 1 or int(mask.numel()) != total_rows:
+            raise ValueError(f"{what}: mask must have one entry for each of the block's {total_rows} rows")
+        if on_device:
+            if mask.is_cuda and mask.device != device:
+                raise ValueError(f"{what}: mask and the block live on different devices")
+            return mask.to(device).contiguous().view(torch.uint8)
+        mask = mask.cpu().numpy()
+    m = np.asarray(mask)
+    if m.dtype not in (np.uint8, np.bool_):
+        raise TypeError(f"{what}: mask must be uint8 or bool, got {m.dtype}")
+    if m.ndim != 1 or m.size != total_rows:
+        raise ValueError(f"{what}: mask must have one entry for each of the block's {total_rows} rows")
+    m = np.ascontiguousarray(m).view(np.uint8)
+    if on_device:
+        import torch
+
+        return torch.from_numpy(m).to(device)
+    return m
+
+
+def select_rows_packed(vec, row_offsets, mask, trim=True):
+    """Kaldi ``select-voiced-frames`` on a packed block [sum T_b, cols]: the rows whose ``mask`` entry is not 0, clip by clip in
+    order, and the table of the result -> (out, out_offsets), ``out_offsets[b + 1] - out_offsets[b]`` the kept rows of clip b.  Every
+    float is a bit copy.  ``mask`` is any uint8 / bool vector with one entry per row, ``vad_energy_packed``'s or another.  numpy in ->
+    the host-pointer call.  A ROCm tensor stays on the device (current stream) and ``out_offsets`` is a device tensor that
+    ``cmvn_packed``, ``add_deltas_packed`` ... accept as it is; the result is trimmed to ``out_offsets[-1]`` rows with one read of
+    that number, and ``trim=False`` returns the full-capacity block [sum T_b, cols] (rows past ``out_offsets[-1]`` uninitialised)
+    without any synchronisation.  See ``ss_select_rows_packed`` in ``include/speechsauce_amd.h``."""
+    what = "select_rows_packed"
+    lib = _lib.lib()
+    x, on_device, total_rows, cols = _packed_block(vec, None, what)
+    table, n = _segment_table(row_offsets, on_device, x.device if on_device else None, total_rows, what)
+    m = _row_mask(mask, on_device, x.device if on_device else None, total_rows, what)
+    if on_device:
+        import torch
+
+        out = torch.empty_like(x)
+        oo = torch.zeros(n + 1, dtype=torch.int64, device=x.device)
+        if n and cols and total_rows:
+            with torch.cuda.device(x.device):
+                _lib.check(lib.ss_select_rows_packed_device(x.data_ptr(), n, table.data_ptr(), total_rows, cols, m.data_ptr(), oo.data_ptr(),
+                                                            out.data_ptr(), _stream_ptr()))
+                for t in (x, table, m):  # the launches are asynchronous: keep the temporaries until the stream has passed them
+                    t.record_stream(torch.cuda.current_stream())
+        if not trim:
+            return out, oo
+        return out[:int(oo[-1])], oo
+    out, oo = np.empty_like(x), np.zeros(n + 1, dtype=np.int64)
+    if n and cols and total_rows:
+        _lib.check(lib.ss_select_rows_packed(x.ctypes.data, n, table.ctypes.data, total_rows, cols, m.ctypes.data, oo.ctypes.data, out.ctypes.data))
+    return (out[:int(oo[-1])] if trim else out), oo
+
+
+def select_rows(x, mask):
+    """``select_rows_packed`` of one matrix [T, cols]: the rows whose ``mask`` entry is not 0 -> [kept, cols]."""
+    x = _require_f32(x, (2,), "select_rows")
+    out, _ = select_rows_packed(x, np.array([0, int(x.shape[0])], dtype=np.int64), mask)
+    return out
+
+
+class VadEnergyStreamPool(_SidePool):
+    """``vad_energy`` over the rows of live streams, with a fixed latency of ``delay_rows = frames_context`` rows: byte k of an entry
+    is the decision for stream row ``rows_seen + k - delay_rows`` (0 while that is negative: the first ``delay_rows`` bytes after a
+    reset are warm-up).  ``pool(rows, row_offsets, slots)`` takes the ``(rows, row_offsets)`` pair of a feature pool call and the
+    ``slots`` that call was given and returns uint8 ``[total_rows]``: an entry gets exactly as many bytes as it brought rows.
+    ``flush(slots)`` returns the last ``delay_rows`` decisions of those streams, ``[len(slots) * delay_rows]``, and makes them fresh.
+    The threshold is causal: the decision for row t compares with ``energy_threshold + energy_mean_scale *`` the mean energy of the
+    rows that have arrived when t is decided.  With ``energy_mean_scale = 0`` a stream's bytes plus the flush, the first
+    ``delay_rows`` dropped, are ``vad_energy`` of the whole clip however it was cut.  ``rows_seen`` (int64 per slot, on the host)
+    moves only after a call went through.  numpy in -> the host-pointer calls, ROCm tensors in -> the device calls on the current
+    stream.  See ``ss_vad_energy_stream_packed`` in ``include/speechsauce_amd.h``."""
+
+    _what = "VadEnergyStreamPool"
+
+    def __init__(self, pool_streams, cols, energy_col=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0, proportion_threshold=0.6):
+        what = self._what
+        if int(pool_streams) < 1:
+            raise ValueError(f"{what}: pool_streams must be at least 1")
+        if int(cols) < 1:
+            raise ValueError(f"{what}: cols must be at least 1")
+        self.pool_streams = int(pool_streams)
+        self.cols = int(cols)
+        (self.energy_col, self.energy_threshold, self.energy_mean_scale, self.frames_context,
+         self.proportion_threshold) = _check_vad_params(energy_col, self.cols, energy_threshold, energy_mean_scale, frames_context, proportion_threshold, what)
+        L = C.c_size_t()
+        _lib.check(_lib.lib().ss_vad_energy_stream_state_len(self.frames_context, C.byref(L)))
+        self.state_len, self.delay_rows = L.value, self.frames_context
+        self.rows_seen = np.zeros(self.pool_streams, dtype=np.int64)
+        self._state = None
+        self._where = None
+
+    @property
+    def state(self):
+        """[pool_streams, 2 * frames_context + 4] float32: a torch tensor on the device of the first rows, or a numpy array; None
+        before the first call."""
+        return self._state
+
+    def reset(self, slots=None):
+        """Zero the state (and ``rows_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
+        idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
+        if slots is None:
+            self.rows_seen[:] = 0
+            if self._state is not None:
+                self._state[...] = 0
+        elif idx:
+            self.rows_seen[idx] = 0
+            if self._state is not None:
+                self._state[idx] = 0
+
+    def _decision(self):
+        return self.energy_threshold, self.energy_mean_scale, self.frames_context, self.proportion_threshold
+
+    def __call__(self, rows, row_offsets, slots):
+        what = self._what
+        x = _require_f32(rows, (2,), what)
+        if int(x.shape[1]) != self.cols:
+            raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool takes {self.cols}")
+        total_rows = int(x.shape[0])
+        ro = self._offsets(row_offsets)
+        slot_list = self._slots(slots)
+        self._check_offsets(ro, len(slot_list), total_rows)
+        where = self._place(x)
+        lib, n_active = _lib.lib(), len(slot_list)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        state = self._state_for(x)
+        if _is_torch(x):
+            import torch
+
+            x = x.contiguous()
+            mask = torch.empty(total_rows, dtype=torch.uint8, device=x.device)
+            if n_active and total_rows:
+                with torch.cuda.device(x.device):
+                    d_ro, d_sl = torch.from_numpy(ro).to(x.device), torch.from_numpy(sl).to(x.device)
+                    _lib.check(lib.ss_vad_energy_stream_packed_device(x.data_ptr(), n_active, d_ro.data_ptr(), total_rows, d_sl.data_ptr(),
+                                                                      self.pool_streams, self.cols, self.energy_col, *self._decision(),
+                                                                      state.data_ptr(), mask.data_ptr(), _stream_ptr()))
+                    for t in (x, d_ro, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                        t.record_stream(torch.cuda.current_stream())
+        else:
+            x = np.ascontiguousarray(x)
+            mask = np.empty(total_rows, dtype=np.uint8)
+            if n_active and total_rows:
+                _lib.check(lib.ss_vad_energy_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, self.pool_streams, self.cols,
+                                                           self.energy_col, *self._decision(), state.ctypes.data, mask.ctypes.data))
+        self._state, self._where = state, where  # only once the call went through
+        if n_active:
+            self.rows_seen[sl] += np.diff(ro)
+        return mask
+
+    def flush(self, slots):
+        """The last ``delay_rows`` decisions of the given streams, uint8 ``[len(slots) * delay_rows]`` (entry i: bytes i * delay_rows ..
+        (i + 1) * delay_rows, stream rows rows_seen - delay_rows .. rows_seen - 1, 0 where that is negative); afterwards those streams
+        are fresh.  Before the pool's first call there is no state anywhere: the bytes are zeros in a numpy array."""
+        slot_list = self._slots(slots)
+        lib, n_active = _lib.lib(), len(slot_list)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        D = self.delay_rows
+        if self._state is None or not _is_torch(self._state):
+            mask = np.zeros(n_active * D, dtype=np.uint8)
+            if n_active and self._state is not None:
+                _lib.check(lib.ss_vad_energy_stream_flush(n_active, sl.ctypes.data, self.pool_streams, *self._decision(), self._state.ctypes.data,
+                                                          mask.ctypes.data))
+        else:
+            import torch
+
+            state = self._state
+            mask = torch.empty(n_active * D, dtype=torch.uint8, device=state.device)
+            if n_active:
+                with torch.cuda.device(state.device):
+                    d_sl = torch.from_numpy(sl).to(state.device)
+                    _lib.check(lib.ss_vad_energy_stream_flush_device(n_active, d_sl.data_ptr(), self.pool_streams, *self._decision(), state.data_ptr(),
+                                                                     mask.data_ptr(), _stream_ptr()))
+                    d_sl.record_stream(torch.cuda.current_stream())
+        if n_active:
+            self.rows_seen[sl] = 0
+        return mask
 
 
 # ---- polyphase sinc resampling ahead of the feature calls (ss_resample* in include/speechsauce_amd.h) -------------

@@ -256,6 +256,20 @@ PROTOTYPES = {
     "ss_splice_stream_flush_device": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp,
                                                 C.c_void_p]),
     "ss_splice_stream_flush": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp]),
+    "ss_vad_energy_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_size_t,
+                                              C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ss_vad_energy_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_size_t, C.c_float,
+                                       C.c_void_p, C.c_void_p]),
+    "ss_select_rows_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, _fp, C.c_void_p]),
+    "ss_select_rows_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, _fp]),
+    "ss_vad_energy_stream_state_len": (C.c_int, [C.c_size_t, _P(C.c_size_t)]),
+    "ss_vad_energy_stream_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                     C.c_float, C.c_float, C.c_size_t, C.c_float, _fp, C.c_void_p, C.c_void_p]),
+    "ss_vad_energy_stream_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_float,
+                                              C.c_size_t, C.c_float, _fp, C.c_void_p]),
+    "ss_vad_energy_stream_flush_device": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_size_t, C.c_float, _fp, C.c_void_p,
+                                                    C.c_void_p]),
+    "ss_vad_energy_stream_flush": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_size_t, C.c_float, _fp, C.c_void_p]),
     "ss_resample_sizes": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _P(SsResampleInfo)]),
     "ss_resample_taps": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _fp, C.c_void_p, C.c_void_p]),
     "ss_resample_len": (C.c_int, [C.c_uint32, C.c_uint32, C.c_size_t, _P(C.c_size_t)]),
