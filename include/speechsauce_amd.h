@@ -1014,6 +1014,47 @@ int ss_vad_energy_stream_flush(size_t n_active, const int32_t *slots, size_t poo
                                float energy_mean_scale, size_t frames_context, float proportion_threshold, float *pool,
                                uint8_t *mask);
 
+/* ---- padded-batch collation of packed rows ----
+ * The last stage of the packed chain: every model the rows are meant for takes a rectangular batch [B x T_max x C] (time-major
+ * rows) or [B x C x T_max] (channels first: conv front ends, Whisper-style encoders) plus a lengths vector, almost always in f16 or
+ * bf16.  One launch takes packed float rows and a device offset table and writes that batch: the dtype conversion, the optional
+ * transpose, the pad filling and the per-clip lengths.  The reference crate has none: this comment is the specification.
+ *   Clip b owns rows ro[b] .. ro[b+1] of vec [total_rows x cols]; T_b = ro[b+1] - ro[b]; kept_b = min(T_b, max_rows): a clip longer
+ *   than max_rows is truncated to its first max_rows rows, which is legal (max_rows is the static shape a captured graph needs).
+ *   out[b][t][c] (SS_PAD_BTC: [n_clips x max_rows x cols]) or out[b][c][t] (SS_PAD_BCT: [n_clips x cols x max_rows]) is
+ *   conv(vec[ro[b] + t][c]) for t < kept_b and conv(pad_value) for kept_b <= t < max_rows; lengths[b] = kept_b.
+ *   conv, by the element type of out:
+ *     SS_PAD_F32   a bit copy: NaN payloads, -0.0 and denormals are unchanged, as in ss_splice_*.
+ *     SS_PAD_F16   IEEE round-to-nearest-even, bit for bit numpy's astype(float16): |x| >= 65520 gives +-inf, results in the f16
+ *                  denormal range are produced, not flushed.
+ *     SS_PAD_BF16  round-to-nearest-even, (bits + 0x7FFF + ((bits >> 16) & 1)) >> 16 on the f32 bit pattern: f32 denormal inputs are
+ *                  not flushed, +-inf stays.
+ *     For both 16-bit types a NaN gives a NaN; its payload is not specified.
+ *   Bad segments (device form): a segment that is reversed, starts below 0 or ends past total_rows is contained -- its whole block
+ *   of out is conv(pad_value) and lengths[b] = -1, distinguishable from a valid clip without rows (0).  Nothing of vec outside
+ *   [0, total_rows) x cols is read, whatever the table holds.  There is no error word: the stage has no handle.
+ *   Every element of out and of lengths is written by every call (the caller needs no memset and the result never depends on what
+ *   the buffers held), nothing is written outside them, and a clip's block depends on its own rows, max_rows and the scalars only
+ *   -- not on its place in the block, its row offset or the workgroup split.
+ *   One launch (ss_pad_packed_kernel<btc|bct,f32|f16|bf16>) whatever n_clips and the table hold, with a grid that depends on
+ *   n_clips, max_rows and cols only; asynchronous on `stream`, no allocation, no read-back: graph-capturable and replayable over
+ *   changed table contents.  The d_out_offsets of ss_select_rows_packed_device and the out_offsets of ss_splice_packed_offsets are
+ *   valid tables as they stand, with total_rows as the bound; so are the row_offsets of a stream-pool call, whose entries then act
+ *   as clips: max_rows = the largest chunk gives the [n_active x R_max x cols] tick batch of a streaming model.
+ * Arguments: n_clips == 0 is SS_OK and writes nothing, also without a device.  pad_value may be any float, NaN and inf included.
+ * SS_ERR_ARG, decided before the device is touched: null buffers; cols == 0; max_rows == 0; a layout or dtype outside its enum;
+ * n_clips, total_rows, cols or max_rows >= 2^31; an output byte count that overflows size_t; out not aligned to its element size;
+ * (device form) out or lengths overlapping vec.  The host form stages through device buffers; it checks the table first as the
+ * other host forms do and names the first bad clip.  ss_pad_packed_out_bytes (host only, no device) returns n_clips * max_rows *
+ * cols * (4 or 2) and SS_ERR_ARG where that overflows size_t. */
+enum { SS_PAD_F32 = 0, SS_PAD_F16 = 1, SS_PAD_BF16 = 2 }; /* element type of out */
+enum { SS_PAD_BTC = 0, SS_PAD_BCT = 1 };                   /* [n_clips x max_rows x cols] / [n_clips x cols x max_rows] */
+int ss_pad_packed_out_bytes(size_t n_clips, size_t max_rows, size_t cols, int dtype, size_t *bytes);
+int ss_pad_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_row_offsets, size_t total_rows, size_t cols,
+                         size_t max_rows, int layout, int dtype, float pad_value, void *d_out, int32_t *d_lengths, void *stream);
+int ss_pad_packed(const float *vec, size_t n_clips, const int64_t *row_offsets, size_t total_rows, size_t cols, size_t max_rows,
+                  int layout, int dtype, float pad_value, void *out, int32_t *lengths);
+
 /* ---- polyphase windowed-sinc resampling ahead of the feature calls ----
  * Every call above takes audio at the rate its ss_params was built for; these calls bring telephony (8 kHz), capture (48 kHz) and
  * corpus (44.1 kHz) audio to it on the device, on the packed layout and the stream pools of the feature calls, from floats or 16-bit

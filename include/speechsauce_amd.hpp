@@ -621,6 +621,23 @@ inline std::vector<float> select_rows_packed(const std::vector<float> &vec, cons
     return out;
 }
 
+// The padded batch of a packed block (ss_pad_packed): [n_clips x max_rows x cols] (SS_PAD_BTC) or [n_clips x cols x max_rows]
+// (SS_PAD_BCT) as raw bytes of `dtype` (SS_PAD_F32: bit copies; SS_PAD_F16 / SS_PAD_BF16: round to nearest even), clip b's first
+// min(T_b, max_rows) rows with pad_value behind them, and in `lengths` the rows kept of every clip
+inline std::vector<uint8_t> pad_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t max_rows,
+                                       std::vector<int32_t> &lengths, int layout = SS_PAD_BTC, int dtype = SS_PAD_F32, float pad_value = 0.0f)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty()) throw Error(SS_ERR_ARG, "pad_packed: shape mismatch");
+    size_t bytes = 0;
+    check(ss_pad_packed_out_bytes(offsets.size() - 1, max_rows, cols, dtype, &bytes));
+    std::vector<uint8_t> out(bytes);
+    lengths.assign(offsets.size() - 1, 0);
+    const float none = 0.0f;  // a block without rows still needs an address
+    check(ss_pad_packed(vec.empty() ? &none : vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, max_rows, layout, dtype, pad_value,
+                        out.data(), lengths.data()));
+    return out;
+}
+
 inline std::vector<float> cmvnw_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t win_size = 301,
                                        bool variance_normalization = false)
 {

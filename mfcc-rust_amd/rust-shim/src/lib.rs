@@ -203,6 +203,12 @@ extern "C" {
     fn ss_vad_energy_stream_flush(n_active: usize, slots: *const i32, pool_streams: usize, energy_threshold: f32,
                                   energy_mean_scale: f32, frames_context: usize, proportion_threshold: f32, pool: *mut f32,
                                   mask: *mut u8) -> c_int;
+    fn ss_pad_packed_out_bytes(n_clips: usize, max_rows: usize, cols: usize, dtype: c_int, bytes: *mut usize) -> c_int;
+    fn ss_pad_packed_device(d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize, max_rows: usize,
+                            layout: c_int, dtype: c_int, pad_value: f32, d_out: *mut c_void, d_lengths: *mut i32,
+                            stream: *mut c_void) -> c_int;
+    fn ss_pad_packed(vec: *const f32, n_clips: usize, row_offsets: *const i64, total_rows: usize, cols: usize, max_rows: usize,
+                     layout: c_int, dtype: c_int, pad_value: f32, out: *mut c_void, lengths: *mut i32) -> c_int;
     fn ss_resample_packed_offsets(orig_rate: u32, new_rate: u32, n_clips: usize, sample_offsets: *const i64, out_offsets: *mut i64) -> c_int;
     fn ss_resampler_create(orig_rate: u32, new_rate: u32, lowpass_filter_width: u32, rolloff: f32, out: *mut *mut c_void) -> c_int;
     fn ss_resampler_destroy(rs: *mut c_void);
@@ -1275,6 +1281,59 @@ pub unsafe fn vad_energy_stream_flush_device(n_active: usize, d_slots: *const i3
                                              d_mask: *mut u8, stream: *mut c_void) -> Result<(), Error> {
     check(ss_vad_energy_stream_flush_device(n_active, d_slots, pool_streams, opts.energy_threshold, opts.energy_mean_scale, opts.frames_context,
                                             opts.proportion_threshold, d_pool, d_mask, stream))
+}
+
+/// Layout of a padded batch: `Btc` is `[n_clips, max_rows, cols]`, `Bct` is `[n_clips, cols, max_rows]` (`SS_PAD_BTC` / `SS_PAD_BCT`).
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum PadLayout {
+    Btc = 0,
+    Bct = 1,
+}
+
+/// Element type of a padded batch (`SS_PAD_F32` / `SS_PAD_F16` / `SS_PAD_BF16`): `F32` is a bit copy, the others round to nearest even.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum PadDtype {
+    F32 = 0,
+    F16 = 1,
+    Bf16 = 2,
+}
+
+/// Bytes of the padded batch of `n_clips` clips: `n_clips * max_rows * cols * (4 or 2)`.
+pub fn try_pad_packed_out_bytes(n_clips: usize, max_rows: usize, cols: usize, dtype: PadDtype) -> Result<usize, Error> {
+    let mut bytes = 0usize;
+    check(unsafe { ss_pad_packed_out_bytes(n_clips, max_rows, cols, dtype as c_int, &mut bytes) })?;
+    Ok(bytes)
+}
+
+/// The padded batch of a packed block, the last stage of the packed chain: clip b's first `min(T_b, max_rows)` rows with `pad_value`
+/// behind them, as the raw bytes of `dtype` in `layout`, and the rows kept of every clip.
+pub fn try_pad_packed(vec: ArrayView2<f32>, row_offsets: &[i64], max_rows: usize, layout: PadLayout, dtype: PadDtype,
+                      pad_value: f32) -> Result<(Vec<u8>, Vec<i32>), Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    if row_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "pad_packed: row_offsets must not be empty".to_string() });
+    }
+    let n_clips = row_offsets.len() - 1;
+    let mut out = vec![0u8; try_pad_packed_out_bytes(n_clips, max_rows, cols, dtype)?];
+    let mut lengths = vec![0i32; n_clips];
+    check(unsafe {
+        ss_pad_packed(x.as_ptr(), n_clips, row_offsets.as_ptr(), rows, cols, max_rows, layout as c_int, dtype as c_int, pad_value,
+                      out.as_mut_ptr() as *mut c_void, lengths.as_mut_ptr())
+    })?;
+    Ok((out, lengths))
+}
+
+/// The device form of `try_pad_packed` (include/speechsauce_amd.h has the contract): one asynchronous launch on `stream`, nothing
+/// read back; a bad segment of the device table gives an all-pad block and length -1.
+///
+/// # Safety
+/// As `vad_energy_packed_device`; `d_out` holds `try_pad_packed_out_bytes` bytes, `d_lengths` `n_clips` words.
+pub unsafe fn pad_packed_device(d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize, max_rows: usize,
+                                layout: PadLayout, dtype: PadDtype, pad_value: f32, d_out: *mut c_void, d_lengths: *mut i32,
+                                stream: *mut c_void) -> Result<(), Error> {
+    check(ss_pad_packed_device(d_vec, n_clips, d_row_offsets, total_rows, cols, max_rows, layout as c_int, dtype as c_int, pad_value, d_out,
+                               d_lengths, stream))
 }
 
 /// librosa's power_to_db of every clip of a packed block with the clip's own `top_db` floor (`None`: no floor); clip b's segment

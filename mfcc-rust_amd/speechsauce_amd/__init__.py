@@ -29,6 +29,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "add_deltas", "add_deltas_packed", "AddDeltasStreamPool",
            "splice", "splice_packed", "lfr", "lfr_packed", "SpliceStreamPool",
            "vad_energy", "vad_energy_packed", "select_rows", "select_rows_packed", "VadEnergyStreamPool",
+           "pad", "pad_packed",
            "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "KaldiFbankStreamPool", "KaldiMfccStreamPool",
@@ -2393,6 +2394,103 @@ class VadEnergyStreamPool(_SidePool):
         if n_active:
             self.rows_seen[sl] = 0
         return mask
+
+
+# ---- padded-batch collation of packed rows (ss_pad_packed*): the rectangular batch a model takes ---------------------------------
+# out[b, t, c] ("btc") or out[b, c, t] ("bct") = the clip's row t for t < min(T_b, max_rows), pad_value behind it; float32 is a bit
+# copy, float16 / bfloat16 round to nearest even.
+
+_PAD_LAYOUTS = {"btc": 0, "bct": 1}
+_PAD_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
+
+
+def _pad_dtype(dtype, what):
+    """-> (SS_PAD_* code, name) of a dtype given as a string, a torch dtype or a numpy dtype"""
+    name = dtype if isinstance(dtype, str) else None
+    if name is None and type(dtype).__module__.split(".")[0] == "torch":
+        name = str(dtype).split(".")[-1]
+    if name is None:
+        try:
+            name = np.dtype(dtype).name
+        except TypeError:
+            name = repr(dtype)
+    if name not in _PAD_DTYPES:
+        raise ValueError(f"{what}: dtype must be float32, float16 or bfloat16, got {dtype!r}")
+    return _PAD_DTYPES[name], name
+
+
+def pad_packed(vec, row_offsets, max_rows=None, layout="btc", dtype="float32", pad_value=0.0):
+    """The padded batch of a packed block [sum T_b, cols], one launch for all clips: -> (out, lengths).  ``out`` is ``[n_clips,
+    max_rows, cols]`` (``layout="btc"``) or ``[n_clips, cols, max_rows]`` (``"bct"``) in ``dtype`` (``"float32"``, ``"float16"``,
+    ``"bfloat16"`` or the torch dtypes): clip b's first ``min(T_b, max_rows)`` rows, ``pad_value`` behind them; ``lengths`` (int32)
+    holds that row count, -1 for a segment a device table got wrong.  float32 is a bit copy, the 16-bit types round to nearest
+    even.  numpy in -> the host-pointer call; float16 comes back as ``np.float16``, bfloat16 as its ``np.uint16`` bit patterns.  A
+    ROCm tensor stays on the device (current stream): ``out`` is a tensor of the torch dtype, ``lengths`` an int32 device tensor.
+    ``row_offsets`` may be a device tensor, used as it is (``select_rows_packed(..., trim=False)``'s, for example), or a host array.
+    ``max_rows=None`` takes the longest clip from a host table; a device table needs an explicit ``max_rows`` (nothing is read
+    back).  See ``ss_pad_packed`` in ``include/speechsauce_amd.h``."""
+    what = "pad_packed"
+    if layout not in _PAD_LAYOUTS:
+        raise ValueError(f"{what}: layout must be 'btc' or 'bct', got {layout!r}")
+    code, name = _pad_dtype(dtype, what)
+    if max_rows is None and _is_torch(row_offsets) and row_offsets.is_cuda:
+        raise ValueError(f"{what}: a device row_offsets table needs an explicit max_rows (the table is not read back)")
+    if max_rows is not None and int(max_rows) < 1:
+        raise ValueError(f"{what}: max_rows must be at least 1")
+    lib = _lib.lib()
+    x, on_device, total_rows, cols = _packed_block(vec, None, what)
+    if cols < 1:
+        raise ValueError(f"{what}: the block has no columns")
+    table, n = _segment_table(row_offsets, on_device, x.device if on_device else None, total_rows, what)
+    if max_rows is None:  # a host table, validated above: the longest clip
+        host = np.asarray(row_offsets.numpy() if _is_torch(row_offsets) else row_offsets)
+        max_rows = int(np.diff(host).max()) if n else 0
+    max_rows = int(max_rows)
+    shape = (n, max_rows, cols) if layout == "btc" else (n, cols, max_rows)
+    pad_value = float(pad_value)
+    if on_device:
+        import torch
+
+        out = torch.empty(shape, dtype=getattr(torch, name), device=x.device)
+        lengths = torch.zeros(n, dtype=torch.int32, device=x.device)
+        if n and max_rows:
+            with torch.cuda.device(x.device):
+                if total_rows == 0:  # every clip is empty: the call still wants a block
+                    x = torch.zeros((1, cols), dtype=torch.float32, device=x.device)
+                _lib.check(lib.ss_pad_packed_device(x.data_ptr(), n, table.data_ptr(), total_rows, cols, max_rows, _PAD_LAYOUTS[layout], code, pad_value,
+                                                    out.data_ptr(), lengths.data_ptr(), _stream_ptr()))
+                for t in (x, table):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                    t.record_stream(torch.cuda.current_stream())
+        return out, lengths
+    out = np.empty(shape, dtype={"float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}[name])
+    lengths = np.zeros(n, dtype=np.int32)
+    if n and max_rows:
+        if total_rows == 0:
+            x = np.zeros((1, cols), dtype=np.float32)
+        _lib.check(lib.ss_pad_packed(x.ctypes.data, n, table.ctypes.data, total_rows, cols, max_rows, _PAD_LAYOUTS[layout], code, pad_value,
+                                     out.ctypes.data, lengths.ctypes.data))
+    return out, lengths
+
+
+def pad(matrices, max_rows=None, layout="btc", dtype="float32", pad_value=0.0):
+    """``pad_packed`` of a list of matrices ``[T_i, cols]`` (all numpy arrays or all tensors of one device): -> (out, lengths)."""
+    what = "pad"
+    mats = list(matrices)
+    if not mats:
+        raise ValueError(f"{what}: the list is empty")
+    for m in mats:
+        if len(m.shape) != 2 or int(m.shape[1]) != int(mats[0].shape[1]):
+            raise ValueError(f"{what}: every matrix must be [T_i, cols] with the same cols")
+    if any(_is_torch(m) for m in mats) != all(_is_torch(m) for m in mats):
+        raise TypeError(f"{what}: the matrices must be all numpy arrays or all tensors")
+    ro = np.concatenate([[0], np.cumsum([int(m.shape[0]) for m in mats])]).astype(np.int64)
+    if _is_torch(mats[0]):
+        import torch
+
+        block = torch.cat(mats)
+    else:
+        block = np.concatenate([np.asarray(m) for m in mats])
+    return pad_packed(block, ro, max_rows, layout, dtype, pad_value)
 
 
 # ---- polyphase sinc resampling ahead of the feature calls (ss_resample* in include/speechsauce_amd.h) -------------

@@ -262,6 +262,11 @@ PROTOTYPES = {
                                        C.c_void_p, C.c_void_p]),
     "ss_select_rows_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, _fp, C.c_void_p]),
     "ss_select_rows_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, _fp]),
+    "ss_pad_packed_out_bytes": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _P(C.c_size_t)]),
+    "ss_pad_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "ss_pad_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                C.c_void_p]),
     "ss_vad_energy_stream_state_len": (C.c_int, [C.c_size_t, _P(C.c_size_t)]),
     "ss_vad_energy_stream_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
                                                      C.c_float, C.c_float, C.c_size_t, C.c_float, _fp, C.c_void_p, C.c_void_p]),
