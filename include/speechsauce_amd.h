@@ -645,14 +645,25 @@ int ss_stack_frames_signal_device(const float *d_x, size_t n_samples, uint32_t s
 /* ---- post-processing on the feature matrix (row-major [rows x cols] f32) ---------- */
 
 /* speechsauce::processing::cmvn(ArrayView2<f32>, variance_normalization) -> Array2<f32>  (processing.rs:265-300):
- * subtract the column means; optionally divide by (population std + 2^-30). */
+ * subtract the column means; optionally divide by (population std + 2^-30).  The std is the deviation about the column's mean,
+ * evaluated in f64 as sqrt(sum((x - K)^2) / rows - (mean - K)^2) with K the column's first row: both terms are of the order of the
+ * column's spread, so a column that moves by a few ulps around a large offset (a log-mel band at its floor) is normalised as the
+ * two-pass definition says; only a first row that lies more than about 1e6 spreads from the rest costs digits.  A column that
+ * holds a NaN or an infinity comes out non-finite in every row (as the reference's does); the other columns are not touched. */
 int ss_cmvn(const float *vec, size_t rows, size_t cols, int variance_normalization, float *out);
 /* the same for `batch` matrices stored back to back ([batch x rows x cols], e.g. the block ss_mfcc_batch_device wrote) */
 int ss_cmvn_batch_device(const float *d_vec, size_t batch, size_t rows, size_t cols, int variance_normalization,
                          float *d_out, void *stream);
 /* speechsauce::processing::cmvnw(Array2<f32>, win_size = 301, variance_normalization)  (processing.rs:315-371):
  * sliding-window normalisation over win_size rows of the symmetric-padded matrix (np.pad 'symmetric', util.rs:108-115).
- * SS_ERR_BAD_CONFIG for an even win_size (the reference asserts). */
+ * SS_ERR_BAD_CONFIG for an even win_size (the reference asserts).
+ * The window sums slide over the rows in f64 (add the row that enters, subtract the row that leaves).  Domain: a finite value
+ * more than about 1e7 times the spread of the rows around it leaves a rounding residue of its square in those sums for the rest
+ * of its chunk of rows (1e8 in N(1, 3) data: up to 6e-4 of an element at win_size 3; 1e12: garbage); up to 1e6 times the spread
+ * the rows behind it are unaffected (tested).  A NaN or an infinity makes exactly the rows non-finite whose window holds it --
+ * within (win_size - 1) / 2 rows of it, twice that with variance normalisation, as in the reference: a window that holds a NaN
+ * gives NaN, never a number, and sums that are not finite after a step are formed afresh from the window, so the rows behind the
+ * value are normalised as if it had never been there.  Finite input never takes that path. */
 int ss_cmvnw(const float *vec, size_t rows, size_t cols, size_t win_size, int variance_normalization, float *out);
 int ss_cmvnw_batch_device(const float *d_vec, size_t batch, size_t rows, size_t cols, size_t win_size,
                           int variance_normalization, float *d_out, void *stream);
@@ -685,7 +696,8 @@ int ss_power_to_db_device(const float *d_s, size_t n, float ref, float amin, flo
  * n_clips + 1 non-decreasing entries with offsets[0] = 0 (fo of ss_packed_frame_offsets, ro of ss_packed_row_offsets); clip b owns
  * rows offsets[b] .. offsets[b+1] of a row-major [total_rows x cols] float block.  Per clip, every result is what the one-matrix
  * call returns for that clip alone:
- *   cmvn_packed         ss_cmvn on the clip's rows: its own column means and population std (+ 2^-30).
+ *   cmvn_packed         ss_cmvn on the clip's rows: its own column means and population std (+ 2^-30), the std evaluated as in
+ *                       ss_cmvn about the CLIP's first row of the column, so it depends on the clip's own rows only.
  *   cmvnw_packed        ss_cmvnw on the clip's rows: the np.pad 'symmetric' reflection happens at the clip's own first and last row
  *                       (period 2 * rows_b: a window wider than the clip wraps inside the clip, never into a neighbour).  An even
  *                       win_size is SS_ERR_BAD_CONFIG.
@@ -736,13 +748,19 @@ int ss_lmfe_packed_device(const ss_config *cfg, const float *d_x, size_t n_clips
  *     n_t = min(t + 1, win),  W_t = rows x[t - n_t + 1 .. t] (the row itself is the newest member),  mean_t = sum(W_t) / n_t
  *     out[t] = x[t] - mean_t                                    variance_normalization == 0
  *     out[t] = (x[t] - mean_t) / (std_t + 2^-30)                variance_normalization != 0
- *     std_t  = sqrt(max(sum(W_t^2) / n_t - mean_t^2, 0))        population, the eps of processing.rs:324
+ *     std_t  = sqrt(sum((W_t - mean_t)^2) / n_t)                the population deviation about the window's mean; the eps of
+ *                                                               processing.rs:324.  Evaluated in one walk of the window as
+ *                                                               sqrt(max(sum((W_t - x[t])^2) / n_t - (mean_t - x[t])^2, 0)):
+ *                                                               the squares are taken about the row itself, a member of the
+ *                                                               window, so a window that moves by a few ulps around a large
+ *                                                               offset keeps its digits (about the origin it would not, and
+ *                                                               the bound below would fail).  A NaN passes the max.
  *   No padding at the start: the first rows use the rows that exist (as Kaldi's online CMVN).  win = 1 gives exact zeros; a column
  *   that is constant over the window gives exact zeros; with variance normalisation |out| <= sqrt(n_t).
- *   Arithmetic: both sums of every element are formed afresh in f64, oldest row first, from the f32 values -- never a running sum
- *   carried between rows or calls -- then static_cast<float>((double(x) - mean) * inv), inv = 1 / (std + 2^-30) or 1.  So a row's
- *   bits depend on its window's values only: not on how the stream was cut into calls, on the entry's place in the call or on its
- *   slot.
+ *   Arithmetic: both sums of every element (of the values, and with variance normalisation of their squared distances from x[t])
+ *   are formed afresh in f64, oldest row first, from the f32 values -- never a running sum carried between rows or calls -- then
+ *   static_cast<float>((double(x) - mean) * inv), inv = 1 / (std + 2^-30) or 1.  So a row's bits depend on its window's values
+ *   only: not on how the stream was cut into calls, on the entry's place in the call or on its slot.
  *   Pool: a caller-owned block [pool_streams x L] of floats, L = ss_cmvn_stream_state_len = (win_size - 1) * cols + 1.  Floats
  *   0 .. (win_size - 1) * cols - 1 of a row are the stream's last win_size - 1 raw rows, oldest first, right-aligned (the newest row
  *   at the end, unused leading rows zero); the last float is the number of valid history rows, min(rows seen, win_size - 1), as a

@@ -7,6 +7,9 @@
 // for the statistics (full rate on gfx950; it keeps the result within an ulp of the f64 oracle for 6 000-row matrices too):
 // cmvn sums chunks of rows per thread and normalises per element (two launches, no atomics: bit-reproducible); cmvnw slides
 // its window sums over a chunk of rows per thread (O(rows + win) loads per column chunk instead of O(rows * win)).
+// cmvn, its packed form and the stream pool take the squares about a value of the column itself (var_about): the mean is formed
+// from the plain sum as before (ss_vad.hip and the mean-only outputs rest on its bits), the variance keeps its digits on a column
+// that barely moves around a large offset.
 #include "ss_device.h"
 #include "ss_hip_staging.h"
 #include "ss_host_checks.h"
@@ -52,6 +55,18 @@ struct SymWalk {
     }
 };
 
+// Population variance of n values from their mean and s2k = sum (v - K)^2, K one of the values: s2k / n - (mean - K)^2.  Both
+// terms are of the order of the column's spread squared (about the origin they are of the order of mean^2, and a column that
+// moves by a few ulps around 1000 is lost in their difference).  Clamped at 0; a NaN passes (fmax would turn it into 0).
+__device__ __forceinline__ double var_about(double s2k, double n, double mean, double K)
+{
+    const double d = mean - K;
+    const double var = fma(-d, d, s2k / n);
+    return var < 0.0 ? 0.0 : var;
+}
+
+__device__ __forceinline__ bool finite_sum(double s) { return fabs(s) < INFINITY; }  // false for NaN
+
 // ---- element-wise logarithms: lmfe's ln (feature.rs:242-245 -> util.rs:372-381) and librosa's power_to_db ----
 __global__ __launch_bounds__(256) void ss_ln_kernel(float *__restrict__ x, unsigned long long n)
 {
@@ -83,7 +98,8 @@ __global__ __launch_bounds__(256) void ss_db_floor_kernel(float *__restrict__ ou
 }
 
 // ---- cmvn: column statistics in two kernels, no atomics (bit-reproducible) ----
-// partial sums of x and x^2 over a chunk of rows; thread = (clip, chunk, column), columns fastest
+// partial sums of x and (x - K)^2 over a chunk of rows, K the clip's first row of the column; thread = (clip, chunk, column),
+// columns fastest
 __global__ __launch_bounds__(256) void ss_cmvn_partial_kernel(const float *__restrict__ x, double *__restrict__ part, unsigned long long total,
                                                              unsigned rows, unsigned cols, unsigned chunks, unsigned rpc)
 {
@@ -95,17 +111,20 @@ __global__ __launch_bounds__(256) void ss_cmvn_partial_kernel(const float *__res
     const unsigned long long clip = cc / chunks;
     const unsigned r0 = chunk * rpc, r1 = min(rows, r0 + rpc);
     const float *src = x + clip * rows * cols + c;
+    const double K = static_cast<double>(src[0]);
     double s1 = 0.0, s2 = 0.0;
     for (unsigned r = r0; r < r1; ++r) {
         const double v = static_cast<double>(src[static_cast<size_t>(r) * cols]);
+        const double d = v - K;
         s1 += v;
-        s2 += v * v;
+        s2 += d * d;
     }
     part[2 * g] = s1;
     part[2 * g + 1] = s2;
 }
 
-// thread = output element: mean (and population std) of its column from the chunk partials, then (x - mean) / (std + 2^-30)
+// thread = output element: mean (and population std, about the clip's first row) of its column from the chunk partials, then
+// (x - mean) / (std + 2^-30)
 __global__ __launch_bounds__(256) void ss_cmvn_apply_kernel(const float *__restrict__ x, const double *__restrict__ part, float *__restrict__ out,
                                                            unsigned long long total, unsigned rows, unsigned cols, unsigned chunks, int variance)
 {
@@ -123,26 +142,36 @@ __global__ __launch_bounds__(256) void ss_cmvn_apply_kernel(const float *__restr
     const double mean = s1 / rows;
     double inv = 1.0;
     if (variance) {
-        const double var = fmax(s2 / rows - mean * mean, 0.0);  // std_axis(Axis(0), 0.) of the mean-subtracted column (processing.rs:283)
+        // std_axis(Axis(0), 0.) of the mean-subtracted column (processing.rs:283)
+        const double var = var_about(s2, rows, mean, static_cast<double>(x[clip * per_clip + c]));
         inv = 1.0 / (sqrt(var) + kEps30);
     }
     out[g] = static_cast<float>((static_cast<double>(x[g]) - mean) * inv);
 }
 
 // ---- cmvnw: sliding window sums over the symmetric-padded rows; thread = (clip, chunk of rows, column) ----
-// pass 1: ms[i] = x[i] - mean of the win rows centred on i
-__global__ __launch_bounds__(256) void ss_cmvnw_mean_kernel(const float *__restrict__ x, float *__restrict__ ms, unsigned long long total,
-                                                            unsigned rows, unsigned cols, unsigned win, unsigned chunks, unsigned rpc)
+// The chunk bodies: rows i0 .. i1 of a column of ONE clip (src / dst point at that clip's column; rows is the clip's own row count,
+// so the symmetric reflection wraps inside the clip).  The sums slide: the row that enters is added, the row that leaves is
+// subtracted.  A NaN or an infinity cannot be subtracted out again (inf - inf), so sums that are not finite after a step are
+// formed afresh from the window (cmvnw_window_sums): a finite window behind a bad row is normalised as if the row had never been
+// there, and finite input never takes that branch.
+template <bool SQUARES>
+__device__ __forceinline__ void cmvnw_window_sums(const float *__restrict__ src, unsigned cols, unsigned win, SymWalk w, double &s1, double &s2)
 {
-    const unsigned long long g = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (g >= total) return;
-    const unsigned c = static_cast<unsigned>(g % cols);
-    const unsigned long long cc = g / cols;
-    const unsigned chunk = static_cast<unsigned>(cc % chunks);
-    const unsigned long long clip = cc / chunks;
-    const unsigned i0 = chunk * rpc, i1 = min(rows, i0 + rpc);
-    const float *src = x + clip * rows * cols + c;
-    float *dst = ms + clip * rows * cols + c;
+    s1 = 0.0;
+    s2 = 0.0;
+    for (unsigned k = 0; k < win; ++k) {
+        const double v = static_cast<double>(src[static_cast<size_t>(w.idx) * cols]);
+        s1 += v;
+        if (SQUARES) s2 += v * v;
+        w.step();
+    }
+}
+
+// pass 1: ms[i] = x[i] - mean of the win rows centred on i
+__device__ __forceinline__ void cmvnw_mean_chunk(const float *__restrict__ src, float *__restrict__ dst, unsigned rows, unsigned cols, unsigned win,
+                                                 unsigned i0, unsigned i1)
+{
     const long long pad = (win - 1) / 2;
     SymWalk head(static_cast<long long>(i0) - pad, rows), tail = head;  // tail: oldest row of the window, head: next row to enter
     double s = 0.0;
@@ -156,22 +185,18 @@ __global__ __launch_bounds__(256) void ss_cmvnw_mean_kernel(const float *__restr
         s += static_cast<double>(src[static_cast<size_t>(head.idx) * cols]) - static_cast<double>(src[static_cast<size_t>(tail.idx) * cols]);
         head.step();
         tail.step();
+        if (!finite_sum(s)) {
+            double unused;
+            cmvnw_window_sums<false>(src, cols, win, tail, s, unused);
+        }
     }
 }
 
-// pass 2 (variance_normalization): ms / (population std of ms over the same symmetric window + 2^-30)
-__global__ __launch_bounds__(256) void ss_cmvnw_var_kernel(const float *__restrict__ ms, float *__restrict__ out, unsigned long long total,
-                                                           unsigned rows, unsigned cols, unsigned win, unsigned chunks, unsigned rpc)
+// pass 2 (variance_normalization): ms / (population std of ms over the same symmetric window + 2^-30).  The window's mean of ms is
+// small against its spread (ms is mean-subtracted), so the squares are summed about the origin.
+__device__ __forceinline__ void cmvnw_var_chunk(const float *__restrict__ src, float *__restrict__ dst, unsigned rows, unsigned cols, unsigned win,
+                                                unsigned i0, unsigned i1)
 {
-    const unsigned long long g = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (g >= total) return;
-    const unsigned c = static_cast<unsigned>(g % cols);
-    const unsigned long long cc = g / cols;
-    const unsigned chunk = static_cast<unsigned>(cc % chunks);
-    const unsigned long long clip = cc / chunks;
-    const unsigned i0 = chunk * rpc, i1 = min(rows, i0 + rpc);
-    const float *src = ms + clip * rows * cols + c;
-    float *dst = out + clip * rows * cols + c;
     const long long pad = (win - 1) / 2;
     SymWalk head(static_cast<long long>(i0) - pad, rows), tail = head;
     double s1 = 0.0, s2 = 0.0;
@@ -184,7 +209,8 @@ __global__ __launch_bounds__(256) void ss_cmvnw_var_kernel(const float *__restri
     }
     for (unsigned i = i0; i < i1; ++i) {
         const double m = s1 / win;
-        const double var = fmax(s2 / win - m * m, 0.0);
+        const double d = s2 / win - m * m;
+        const double var = d < 0.0 ? 0.0 : d;  // a NaN passes: a window that holds one gives NaN, as the reference does
         dst[static_cast<size_t>(i) * cols] = static_cast<float>(static_cast<double>(src[static_cast<size_t>(i) * cols]) / (sqrt(var) + kEps30));
         const double vin = static_cast<double>(src[static_cast<size_t>(head.idx) * cols]);
         const double vout = static_cast<double>(src[static_cast<size_t>(tail.idx) * cols]);
@@ -192,7 +218,34 @@ __global__ __launch_bounds__(256) void ss_cmvnw_var_kernel(const float *__restri
         s2 += vin * vin - vout * vout;
         head.step();
         tail.step();
+        if (!finite_sum(s1) || !finite_sum(s2)) cmvnw_window_sums<true>(src, cols, win, tail, s1, s2);
     }
+}
+
+__global__ __launch_bounds__(256) void ss_cmvnw_mean_kernel(const float *__restrict__ x, float *__restrict__ ms, unsigned long long total,
+                                                            unsigned rows, unsigned cols, unsigned win, unsigned chunks, unsigned rpc)
+{
+    const unsigned long long g = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    const unsigned c = static_cast<unsigned>(g % cols);
+    const unsigned long long cc = g / cols;
+    const unsigned chunk = static_cast<unsigned>(cc % chunks);
+    const unsigned long long clip = cc / chunks;
+    const unsigned i0 = chunk * rpc, i1 = min(rows, i0 + rpc);
+    cmvnw_mean_chunk(x + clip * rows * cols + c, ms + clip * rows * cols + c, rows, cols, win, i0, i1);
+}
+
+__global__ __launch_bounds__(256) void ss_cmvnw_var_kernel(const float *__restrict__ ms, float *__restrict__ out, unsigned long long total,
+                                                           unsigned rows, unsigned cols, unsigned win, unsigned chunks, unsigned rpc)
+{
+    const unsigned long long g = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    const unsigned c = static_cast<unsigned>(g % cols);
+    const unsigned long long cc = g / cols;
+    const unsigned chunk = static_cast<unsigned>(cc % chunks);
+    const unsigned long long clip = cc / chunks;
+    const unsigned i0 = chunk * rpc, i1 = min(rows, i0 + rpc);
+    cmvnw_var_chunk(ms + clip * rows * cols + c, out + clip * rows * cols + c, rows, cols, win, i0, i1);
 }
 
 // derivative along the FEATURE axis with edge clamping, literal reference arithmetic: sum_R (R f[c+R] - f[c-R]) / sum_R 2R^2
@@ -272,11 +325,13 @@ __global__ __launch_bounds__(256) void ss_cmvn_packed_kernel(const float *__rest
             const unsigned chunk = k / ct, c = k - chunk * ct;
             const unsigned r0 = chunk * rpc, r1 = min(rows, r0 + rpc);
             const float *p = src + c0 + c;
+            const double K = static_cast<double>(p[0]);  // the clip's first row of the column
             double s1 = 0.0, s2 = 0.0;
             for (unsigned r = r0; r < r1; ++r) {
                 const double v = static_cast<double>(p[static_cast<size_t>(r) * cols]);
+                const double d = v - K;
                 s1 += v;
-                s2 += v * v;
+                s2 += d * d;
             }
             part[2 * k] = s1;
             part[2 * k + 1] = s2;
@@ -291,7 +346,7 @@ __global__ __launch_bounds__(256) void ss_cmvn_packed_kernel(const float *__rest
             const double mean = s1 / rows;
             double inv = 1.0;
             if (variance) {
-                const double var = fmax(s2 / rows - mean * mean, 0.0);  // as ss_cmvn_apply_kernel
+                const double var = var_about(s2, rows, mean, static_cast<double>(src[c0 + threadIdx.x]));  // as ss_cmvn_apply_kernel
                 inv = 1.0 / (sqrt(var) + kEps30);
             }
             stat[2 * threadIdx.x] = mean;
@@ -309,55 +364,8 @@ __global__ __launch_bounds__(256) void ss_cmvn_packed_kernel(const float *__rest
     }
 }
 
-// cmvnw: the chunk bodies of ss_cmvnw_mean_kernel / ss_cmvnw_var_kernel on rows i0 .. i1 of a column of ONE clip (src / dst point
-// at that clip's column; rows is the clip's own row count, so the symmetric reflection wraps inside the clip)
-__device__ __forceinline__ void cmvnw_mean_chunk(const float *__restrict__ src, float *__restrict__ dst, unsigned rows, unsigned cols, unsigned win,
-                                                 unsigned i0, unsigned i1)
-{
-    const long long pad = (win - 1) / 2;
-    SymWalk head(static_cast<long long>(i0) - pad, rows), tail = head;
-    double s = 0.0;
-#pragma unroll 4
-    for (unsigned w = 0; w < win; ++w) {
-        s += static_cast<double>(src[static_cast<size_t>(head.idx) * cols]);
-        head.step();
-    }
-    for (unsigned i = i0; i < i1; ++i) {
-        dst[static_cast<size_t>(i) * cols] = static_cast<float>(static_cast<double>(src[static_cast<size_t>(i) * cols]) - s / win);
-        s += static_cast<double>(src[static_cast<size_t>(head.idx) * cols]) - static_cast<double>(src[static_cast<size_t>(tail.idx) * cols]);
-        head.step();
-        tail.step();
-    }
-}
-
-__device__ __forceinline__ void cmvnw_var_chunk(const float *__restrict__ src, float *__restrict__ dst, unsigned rows, unsigned cols, unsigned win,
-                                                unsigned i0, unsigned i1)
-{
-    const long long pad = (win - 1) / 2;
-    SymWalk head(static_cast<long long>(i0) - pad, rows), tail = head;
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll 4
-    for (unsigned w = 0; w < win; ++w) {
-        const double v = static_cast<double>(src[static_cast<size_t>(head.idx) * cols]);
-        s1 += v;
-        s2 += v * v;
-        head.step();
-    }
-    for (unsigned i = i0; i < i1; ++i) {
-        const double m = s1 / win;
-        const double var = fmax(s2 / win - m * m, 0.0);
-        dst[static_cast<size_t>(i) * cols] = static_cast<float>(static_cast<double>(src[static_cast<size_t>(i) * cols]) / (sqrt(var) + kEps30));
-        const double vin = static_cast<double>(src[static_cast<size_t>(head.idx) * cols]);
-        const double vout = static_cast<double>(src[static_cast<size_t>(tail.idx) * cols]);
-        s1 += vin - vout;
-        s2 += vin * vin - vout * vout;
-        head.step();
-        tail.step();
-    }
-}
-
-// pass 1 (VAR = false) or pass 2 (VAR = true) of cmvnw over packed clips: task = (chunk of rpc rows counted from the clip's first
-// row, column), columns fastest; the gridDim.y workgroups of a clip stride over its tasks
+// pass 1 (VAR = false) or pass 2 (VAR = true) of cmvnw over packed clips (cmvnw_mean_chunk / cmvnw_var_chunk above): task = (chunk
+// of rpc rows counted from the clip's first row, column), columns fastest; the gridDim.y workgroups of a clip stride over its tasks
 template <bool VAR>
 __global__ __launch_bounds__(256) void ss_cmvnw_packed_kernel(const float *__restrict__ in, const long long *__restrict__ off, float *__restrict__ out,
                                                              unsigned long long total_rows, unsigned cols, unsigned win, unsigned rpc)
@@ -382,8 +390,9 @@ __global__ __launch_bounds__(256) void ss_cmvnw_packed_kernel(const float *__res
 // Entry i owns rows ro[i] .. ro[i+1] of the [total_rows x cols] blocks and pool row slots[i]: L = (win - 1) * cols + 1 floats, the
 // last win - 1 raw rows of its stream (oldest first, right-aligned, zeros in front) and, in the last float, how many of them are
 // valid.  Row t of the stream is normalised over its own trailing window, rows max(t - win + 1, 0) .. t: the valid history rows,
-// then the entry's rows up to the row itself.  Both sums are formed afresh for every element, oldest row first, so an element's
-// bits depend on the window's values only -- not on how the stream was cut into calls, the entry's place in the call or its slot.
+// then the entry's rows up to the row itself.  Both sums (the squares about the row itself) are formed afresh for every element,
+// oldest row first, so an element's bits depend on the window's values only -- not on how the stream was cut into calls, the
+// entry's place in the call or its slot.
 // One workgroup per entry, one launch: the workgroup owns its pool row, normalises the entry's rows and then moves the row on.
 // Containment: an entry is skipped unless 0 <= ro[i] <= ro[i+1] <= total_rows and 0 <= slots[i] < pool_streams; a count word that
 // is not an integer in [0, win - 1] (NaN included) is read as 0, so the window never reaches in front of the pool row.
@@ -414,14 +423,20 @@ constexpr unsigned kStreamMove = 4;      // pool-row floats a thread moves per s
 constexpr unsigned kStreamTile = 32;     // columns staged in LDS at a time, as kCmvnTile
 constexpr unsigned kStreamLds = 10240;   // floats of LDS (40 KiB: four workgroups per CU): win = 301 with up to 20 new rows per tile
 
-// the two sums of one element over n values `stride` floats apart, oldest first (fma written out: the same bits from every caller)
-__device__ __forceinline__ void stream_window_sums(const float *p, unsigned n, size_t stride, double &s1, double &s2)
+// the two sums of one element over n values `stride` floats apart, oldest first: s1 of the values, s2 of their squared distances
+// from K, the row being normalised (fma written out: the same bits from every caller).  Without variance normalisation nobody reads
+// s2: SQUARES = false leaves it alone (s1 is formed in the same order either way).
+template <bool SQUARES>
+__device__ __forceinline__ void stream_window_sums(const float *p, unsigned n, size_t stride, double K, double &s1, double &s2)
 {
 #pragma unroll 8
     for (unsigned j = 0; j < n; ++j, p += stride) {
         const double v = static_cast<double>(*p);
         s1 += v;
-        s2 = fma(v, v, s2);
+        if (SQUARES) {
+            const double d = v - K;
+            s2 = fma(d, d, s2);
+        }
     }
 }
 
@@ -431,7 +446,7 @@ __device__ __forceinline__ float stream_normalise(float x, double s1, double s2,
     const double mean = s1 / n;
     double inv = 1.0;
     if (variance) {
-        const double var = fmax(fma(-mean, mean, s2 / n), 0.0);
+        const double var = var_about(s2, n, mean, static_cast<double>(x));
         inv = 1.0 / (sqrt(var) + kEps30);
     }
     return static_cast<float>((static_cast<double>(x) - mean) * inv);
@@ -468,9 +483,12 @@ __global__ __launch_bounds__(256) void ss_cmvn_stream_packed_kernel(const float 
             for (unsigned k = threadIdx.x; k < rows * ct; k += 256) {  // task = (row, column), columns fastest
                 const unsigned t = k / ct, c = k - t * ct;
                 const unsigned n = min(count + t + 1, win);  // rows in the window, the row itself the newest
+                const float xt = tile[(count + t) * ct + c];
                 double s1 = 0.0, s2 = 0.0;
-                stream_window_sums(tile + (count + t + 1 - n) * ct + c, n, ct, s1, s2);
-                dst[static_cast<size_t>(t) * cols + c0 + c] = stream_normalise(tile[(count + t) * ct + c], s1, s2, n, variance);
+                const float *oldest = tile + (count + t + 1 - n) * ct + c;
+                if (variance) stream_window_sums<true>(oldest, n, ct, static_cast<double>(xt), s1, s2);
+                else stream_window_sums<false>(oldest, n, ct, 0.0, s1, s2);
+                dst[static_cast<size_t>(t) * cols + c0 + c] = stream_normalise(xt, s1, s2, n, variance);
             }
             for (unsigned i = threadIdx.x; i < hist * ct; i += 256) {
                 const unsigned r = i / ct, c = i - r * ct;
@@ -488,10 +506,17 @@ __global__ __launch_bounds__(256) void ss_cmvn_stream_packed_kernel(const float 
             const unsigned n = min(count + t + 1, win);
             const unsigned first = count + t + 1 - n;   // the window's oldest row
             const unsigned h0 = min(first, count);      // history rows h0 .. count - 1, then the entry's rows first - h0 .. t
+            const float xt = src[k];
             double s1 = 0.0, s2 = 0.0;
-            stream_window_sums(old + static_cast<size_t>(h0) * cols + c, count - h0, cols, s1, s2);
-            stream_window_sums(src + static_cast<size_t>(first - h0) * cols + c, n - (count - h0), cols, s1, s2);
-            dst[k] = stream_normalise(src[k], s1, s2, n, variance);
+            const float *hist_rows = old + static_cast<size_t>(h0) * cols + c, *new_rows = src + static_cast<size_t>(first - h0) * cols + c;
+            if (variance) {
+                stream_window_sums<true>(hist_rows, count - h0, cols, static_cast<double>(xt), s1, s2);
+                stream_window_sums<true>(new_rows, n - (count - h0), cols, static_cast<double>(xt), s1, s2);
+            } else {
+                stream_window_sums<false>(hist_rows, count - h0, cols, 0.0, s1, s2);
+                stream_window_sums<false>(new_rows, n - (count - h0), cols, 0.0, s1, s2);
+            }
+            dst[k] = stream_normalise(xt, s1, s2, n, variance);
         }
         // A history row moves towards the front of the pool row it is read from, so the row is rewritten in ascending steps of
         // 256 * kStreamMove floats, every step read in full before it is written: a later step reads only what lies behind
