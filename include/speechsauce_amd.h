@@ -796,6 +796,83 @@ int ss_cmvn_stream_packed_device(const float *d_vec, size_t n_active, const int6
 int ss_cmvn_stream_packed(const float *vec, size_t n_active, const int64_t *row_offsets, const int32_t *slots,
                           size_t pool_streams, size_t cols, size_t win_size, int variance_normalization, float *pool, float *out);
 
+/* ---- grouped CMVN: per-speaker and global statistics of packed rows, accumulated, merged, stored and applied ----
+ * ss_cmvn_packed* normalises a clip by its own statistics, ss_cmvnw_packed* and the pool above by a sliding window.  These calls
+ * are the other two normalisations in use: PER-SPEAKER CMVN (Kaldi's compute-cmvn-stats --spk2utt followed by apply-cmvn
+ * --utt2spk: one set of column statistics over all of a speaker's utterances) and GLOBAL CMVN (WeNet global_cmvn, ESPnet
+ * global_mvn, apply-cmvn with a stats file: statistics accumulated over a training set batch by batch, stored, and applied
+ * unchanged at inference, live streams included).  The reference crate has neither: this comment is the specification.
+ *   Statistics block: a group's statistics are one row of ss_cmvn_stats_len(cols) = 2 * cols + 1 doubles
+ *       [ n | mean[cols] | var[cols] ]
+ *   n the number of rows seen, held as a double; var the POPULATION variance.  All zeros = a fresh group; an n that is not finite
+ *   or is below 1 is read as 0 (fresh), as the pools read a bad count word.  The block of a call is [n_groups x stats_len],
+ *   caller-owned, updated in place.  clip_group is an int32 table [n_clips]: clip b belongs to group clip_group[b]; NULL means
+ *   group 0 for every clip (global CMVN); -1 leaves a clip out.
+ *   Per-clip statistics: clip b of T rows has exactly the statistics ss_cmvn_packed* forms: chunks = min(64, ceil(T / 32)) serial
+ *   f64 sums of ceil(T / chunks) rows each, added in chunk order, the squares taken about the clip's own first row K of the column;
+ *   mean_b = s1 / T, var_b = max(s2 / T - (mean_b - K)^2, 0).  mean_b is bit for bit the mean ss_cmvn_packed* subtracts.
+ *   Merge: a group's row is the left fold of its clips into the prior row, in ascending clip index, in f64, every operation
+ *   rounded on its own (no fused multiply-add), in this order (na, ma, va the row; nb = T, mb, vb the clip):
+ *       n = na + nb;  wa = na / n;  wb = nb / n;  d = mb - ma;
+ *       mean = ma + d * wb;
+ *       var  = (wa * va + wb * vb) + (d * d) * (wa * wb);
+ *   For na == 0 the clip's statistics are copied.  An empty or skipped clip takes no step.  This is Chan's merge in variance form:
+ *   both terms of var are of the order of the spread squared, so a column that barely moves around a large offset keeps its
+ *   digits.  It is a strict left fold: the bits do not depend on how the clips were cut into calls (two calls over a split of the
+ *   clips equal one call), on the other groups' clips or on a clip's place in the block.  A group with no valid clip in a call
+ *   keeps its row bit for bit.
+ *   Apply: out = (float)(((double)x - mean_g) * inv_g), inv_g = 1 / (sqrt(var_g) + 2^-30) with variance normalisation and 1
+ *   without: the finishing arithmetic of ss_cmvn_packed*.  out == vec is allowed (the call is element-wise); a partial overlap is
+ *   SS_ERR_ARG.  A clip whose group has n < 1 is skipped.
+ *   ss_cmvn_grouped_packed* is the per-speaker CMVN of one batch: statistics from fresh plus apply in one call on a stream-ordered
+ *   scratch block; bit for bit ss_cmvn_stats_packed* on a zeroed block followed by ss_cmvn_apply_packed*.
+ *   Device forms: asynchronous on `stream`, the tables are DEVICE arrays that only the kernels read, graph-capturable as a linear
+ *   chain, and a captured graph replays over changed tables.  The launch count does not depend on n_clips or n_groups: statistics
+ *   two kernels and one scratch block [n_clips x 2 cols] of doubles, apply one kernel, the combined call three kernels and a
+ *   memset.  No float atomics: results are bit-reproducible.  The scratch is a stream-ordered allocation, except inside a stream
+ *   capture: there it is one plain device block per device, which every statistics or combined call OUTSIDE a capture grows to
+ *   its own scratch size.  So run the call once with the capture's sizes (or larger) before capturing it, as a warm-up does; a
+ *   captured call that finds the block too small is SS_ERR_HIP with nothing put on the stream.  Graphs that hold a statistics or
+ *   combined call share the block: replay them one after the other, not concurrently.  (Apply has no scratch.)
+ *   Containment (device forms): a clip is skipped if its segment is reversed, starts below 0 or ends past total_rows, or if its
+ *   group id lies outside [0, n_groups); under apply also if its group has n < 1.  A skipped clip contributes nothing and its rows
+ *   are left unwritten; no address outside the blocks is formed whatever the tables hold.  The apply kernel finds the clip of a
+ *   row by binary search in d_offsets: where the table is not non-decreasing, rows of otherwise valid clips may be left
+ *   unwritten too (never written wrongly, never outside the block).
+ *   Arguments: n_clips == 0 is SS_OK with nothing launched, also on a host without a device.  SS_ERR_ARG: null vec / offsets /
+ *   stats / out; cols == 0; n_groups == 0; total_rows, n_clips or n_groups >= 2^31, cols >= 2^30; the statistics block overlapping
+ *   vec (stats) or out (apply); out overlapping vec other than out == vec.  Host-pointer forms (synchronous) check the tables
+ *   before they touch the device -- offsets[0] != 0, a decreasing pair, a clip past total_rows, a group id below -1 or >= n_groups
+ *   -- and name the first bad clip in ss_last_error_string(); rows of clips that are left out keep the caller's bytes.
+ *   The stream pools need no state for this: a pool tick's output is a packed block with its row_offsets, so
+ *   ss_cmvn_apply_packed_device(d_rows, n_active, d_row_offsets, total_rows, cols, NULL or a per-entry speaker table, ...) is the
+ *   online global (or per-speaker) CMVN of the tick, and can be captured behind the tick's call.
+ *   Kaldi interchange (host only, f64): one row converts to and from Kaldi's [2 x (cols + 1)] accumulator, row 0 = sum x | count,
+ *   row 1 = sum x^2 | 0 -- the layout of cmvn.ark and of WeNet's mean_stat / var_stat / frame_num.  to_kaldi: sum x = n * mean,
+ *   sum x^2 = n * (var + mean^2).  from_kaldi: mean = sum x / n, var = max(sum x^2 / n - mean^2, 0); count < 1 (or not finite)
+ *   gives a fresh row.  Only from_kaldi carries Kaldi's own one-pass conditioning (the difference of two numbers of the order of
+ *   mean^2); rows formed by ss_cmvn_stats_packed* do not, and to_kaldi followed by from_kaldi loses what the accumulator form
+ *   cannot hold.
+ *   Not offered: weighted frames, --norm-means=false, 16-bit rows, a decaying or online-updating global statistic. */
+/* host only, no device: *len = 2 * cols + 1.  SS_ERR_ARG: cols == 0, cols >= 2^30 */
+int ss_cmvn_stats_len(size_t cols, size_t *len);
+int ss_cmvn_stats_to_kaldi(const double *stats, size_t cols, double *kaldi);
+int ss_cmvn_stats_from_kaldi(const double *kaldi, size_t cols, double *stats);
+int ss_cmvn_stats_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols,
+                                const int32_t *d_clip_group, size_t n_groups, double *d_stats, void *stream);
+int ss_cmvn_apply_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols,
+                                const int32_t *d_clip_group, size_t n_groups, const double *d_stats, int variance_normalization,
+                                float *d_out, void *stream);
+int ss_cmvn_grouped_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_offsets, size_t total_rows, size_t cols,
+                                  const int32_t *d_clip_group, size_t n_groups, int variance_normalization, float *d_out,
+                                  void *stream);
+int ss_cmvn_stats_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols,
+                         const int32_t *clip_group, size_t n_groups, double *stats);
+int ss_cmvn_apply_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols,
+                         const int32_t *clip_group, size_t n_groups, const double *stats, int variance_normalization, float *out);
+int ss_cmvn_grouped_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols,
+                           const int32_t *clip_group, size_t n_groups, int variance_normalization, float *out);
+
 /* ---- time-axis delta features (Kaldi's add-deltas) on packed clips and over a pool of stream states ----
  * ss_derivative_extraction* above mirror the reference, which differences along the FEATURE axis.  These calls append the
  * regression deltas over neighbouring FRAMES that HTK, Kaldi add-deltas, python_speech_features.delta and

@@ -568,6 +568,65 @@ inline std::vector<float> cmvn_packed(const std::vector<float> &vec, const std::
     return out;
 }
 
+// Grouped CMVN (ss_cmvn_stats_packed / ss_cmvn_apply_packed / ss_cmvn_grouped_packed): per-speaker and global statistics.  A group's
+// statistics are a row [n | mean | var] of cmvn_stats_len(cols) = 2 * cols + 1 doubles; `stats` is [n_groups x that], all zeros =
+// fresh; groups[b] is clip b's group, -1 leaves the clip out, an empty `groups` puts every clip into group 0.
+inline size_t cmvn_stats_len(size_t cols)
+{
+    size_t len = 0;
+    check(ss_cmvn_stats_len(cols, &len));
+    return len;
+}
+inline void cmvn_stats_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, const std::vector<int32_t> &groups,
+                              size_t n_groups, std::vector<double> &stats)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty() || (!groups.empty() && groups.size() != offsets.size() - 1) ||
+        stats.size() != n_groups * (2 * cols + 1))
+        throw Error(SS_ERR_ARG, "cmvn_stats_packed: shape mismatch");
+    check(ss_cmvn_stats_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, groups.empty() ? nullptr : groups.data(),
+                               n_groups, stats.data()));
+}
+// rows of clips that are left out (group -1, a group that has seen no row) come back as zeros
+inline std::vector<float> cmvn_apply_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols,
+                                            const std::vector<int32_t> &groups, size_t n_groups, const std::vector<double> &stats,
+                                            bool variance_normalization = false)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty() || (!groups.empty() && groups.size() != offsets.size() - 1) ||
+        stats.size() != n_groups * (2 * cols + 1))
+        throw Error(SS_ERR_ARG, "cmvn_apply_packed: shape mismatch");
+    std::vector<float> out(vec.size());
+    check(ss_cmvn_apply_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, groups.empty() ? nullptr : groups.data(),
+                               n_groups, stats.data(), variance_normalization ? 1 : 0, out.data()));
+    return out;
+}
+inline std::vector<float> cmvn_grouped_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols,
+                                              const std::vector<int32_t> &groups, size_t n_groups, bool variance_normalization = false)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty() || (!groups.empty() && groups.size() != offsets.size() - 1))
+        throw Error(SS_ERR_ARG, "cmvn_grouped_packed: shape mismatch");
+    std::vector<float> out(vec.size());
+    check(ss_cmvn_grouped_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, groups.empty() ? nullptr : groups.data(),
+                                 n_groups, variance_normalization ? 1 : 0, out.data()));
+    return out;
+}
+// one statistics row <-> Kaldi's [2 x (cols + 1)] accumulator (sum x | count, then sum x^2 | 0)
+inline std::vector<double> cmvn_stats_to_kaldi(const std::vector<double> &stats_row)
+{
+    if (stats_row.size() < 3 || stats_row.size() % 2 == 0) throw Error(SS_ERR_ARG, "cmvn_stats_to_kaldi: a row has 2 * cols + 1 doubles");
+    const size_t cols = (stats_row.size() - 1) / 2;
+    std::vector<double> kaldi(2 * (cols + 1));
+    check(ss_cmvn_stats_to_kaldi(stats_row.data(), cols, kaldi.data()));
+    return kaldi;
+}
+inline std::vector<double> cmvn_stats_from_kaldi(const std::vector<double> &kaldi)
+{
+    if (kaldi.size() < 4 || kaldi.size() % 2) throw Error(SS_ERR_ARG, "cmvn_stats_from_kaldi: an accumulator has 2 * (cols + 1) doubles");
+    const size_t cols = kaldi.size() / 2 - 1;
+    std::vector<double> row(2 * cols + 1);
+    check(ss_cmvn_stats_from_kaldi(kaldi.data(), cols, row.data()));
+    return row;
+}
+
 // Kaldi add-deltas of every clip of a packed block on its own rows (ss_add_deltas_packed): -> [total_rows x (order + 1) * cols], row t =
 // [x[t] | delta | delta-delta] over neighbouring frames; order 1 or 2, order * window at most 32.  A dense matrix: offsets = {0, rows}
 inline std::vector<float> add_deltas_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t order = 2,

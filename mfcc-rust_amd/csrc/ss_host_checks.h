@@ -47,6 +47,16 @@ inline int check_clip_table(const int64_t *off, size_t n_clips, size_t total_row
     return SS_OK;
 }
 
+// the group table of a host-pointer grouped-CMVN call: every id in [0, n_groups), or -1 (the clip is left out)
+inline int check_clip_groups(const int32_t *groups, size_t n_clips, size_t n_groups)
+{
+    for (size_t b = 0; b < n_clips; ++b)
+        if (groups[b] < -1 || (groups[b] >= 0 && static_cast<size_t>(groups[b]) >= n_groups))
+            return fail(SS_ERR_ARG, "clip " + std::to_string(b) + ": group " + std::to_string(groups[b]) + " is outside the " +
+                                        std::to_string(n_groups) + " groups (-1 leaves a clip out)");
+    return SS_OK;
+}
+
 // the row offsets of a host-pointer pool call (n_active + 1 of them; the block's row count is their last)
 inline int check_row_offsets(const int64_t *ro, size_t n_active)
 {

@@ -172,6 +172,16 @@ extern "C" {
     fn ss_cmvn_stream_state_len(cols: usize, win_size: usize, state_len: *mut usize) -> c_int;
     fn ss_cmvn_stream_packed(vec: *const f32, n_active: usize, row_offsets: *const i64, slots: *const i32, pool_streams: usize,
                              cols: usize, win_size: usize, variance_normalization: c_int, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_cmvn_stats_len(cols: usize, len: *mut usize) -> c_int;
+    fn ss_cmvn_stats_to_kaldi(stats: *const f64, cols: usize, kaldi: *mut f64) -> c_int;
+    fn ss_cmvn_stats_from_kaldi(kaldi: *const f64, cols: usize, stats: *mut f64) -> c_int;
+    fn ss_cmvn_stats_packed(vec: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize,
+                            clip_group: *const i32, n_groups: usize, stats: *mut f64) -> c_int;
+    fn ss_cmvn_apply_packed(vec: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize,
+                            clip_group: *const i32, n_groups: usize, stats: *const f64, variance_normalization: c_int,
+                            out: *mut f32) -> c_int;
+    fn ss_cmvn_grouped_packed(vec: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize,
+                              clip_group: *const i32, n_groups: usize, variance_normalization: c_int, out: *mut f32) -> c_int;
     fn ss_add_deltas_packed(vec: *const f32, n_clips: usize, offsets: *const i64, total_rows: usize, cols: usize, order: usize,
                             window: usize, out: *mut f32) -> c_int;
     fn ss_add_deltas_stream_state_len(cols: usize, order: usize, window: usize, state_len: *mut usize) -> c_int;
@@ -1043,6 +1053,89 @@ pub fn try_cmvnw_packed(vec: ArrayView2<f32>, offsets: &[i64], win_size: usize, 
                         variance_normalization as c_int, out.as_mut_ptr())
     })?;
     Ok(out)
+}
+
+/// Doubles per group of a grouped-CMVN statistics block: `2 * cols + 1`, a row `[n | mean | var]`.
+pub fn try_cmvn_stats_len(cols: usize) -> Result<usize, Error> {
+    let mut len = 0usize;
+    check(unsafe { ss_cmvn_stats_len(cols, &mut len) })?;
+    Ok(len)
+}
+
+fn group_ptr(groups: Option<&[i32]>, n_clips: usize) -> Result<*const i32, Error> {
+    match groups {
+        None => Ok(std::ptr::null()),
+        Some(g) if g.len() == n_clips => Ok(g.as_ptr()),
+        Some(_) => Err(Error { status: SS_ERR_ARG, detail: "groups must name one group per clip".to_string() }),
+    }
+}
+
+/// Folds every clip of a packed block into the statistics row of its group (`groups[b]`, -1 leaves a clip out, `None`: group 0 for
+/// every clip).  `stats` is the caller's `[n_groups x try_cmvn_stats_len(cols)]` block, updated in place; all zeros is fresh.
+pub fn try_cmvn_stats_packed(vec: ArrayView2<f32>, offsets: &[i64], groups: Option<&[i32]>, n_groups: usize, stats: &mut [f64]) -> Result<(), Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    let n_clips = offsets.len().saturating_sub(1);
+    if stats.len() != n_groups * try_cmvn_stats_len(cols)? {
+        return Err(Error { status: SS_ERR_ARG, detail: "stats must hold n_groups rows of 2 * cols + 1 doubles".to_string() });
+    }
+    let g = group_ptr(groups, n_clips)?;
+    check(unsafe { ss_cmvn_stats_packed(x.as_ptr(), n_clips, offsets.as_ptr(), rows, cols, g, n_groups, stats.as_mut_ptr()) })
+}
+
+/// Normalises every clip by the stored statistics of its group: `(x - mean_g) / (sqrt(var_g) + 2^-30)`, or `x - mean_g`.  Rows of
+/// clips that are left out (group -1, a group that has seen no row) come back as zeros.
+pub fn try_cmvn_apply_packed(vec: ArrayView2<f32>, offsets: &[i64], groups: Option<&[i32]>, n_groups: usize, stats: &[f64],
+                             variance_normalization: bool) -> Result<Array2<f32>, Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    let n_clips = offsets.len().saturating_sub(1);
+    if stats.len() != n_groups * try_cmvn_stats_len(cols)? {
+        return Err(Error { status: SS_ERR_ARG, detail: "stats must hold n_groups rows of 2 * cols + 1 doubles".to_string() });
+    }
+    let g = group_ptr(groups, n_clips)?;
+    let mut out = Array2::<f32>::zeros((rows, cols));
+    check(unsafe {
+        ss_cmvn_apply_packed(x.as_ptr(), n_clips, offsets.as_ptr(), rows, cols, g, n_groups, stats.as_ptr(), variance_normalization as c_int,
+                             out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// Per-speaker CMVN of one batch: the statistics of every group from the batch's own clips, then the apply, in one call.
+pub fn try_cmvn_grouped_packed(vec: ArrayView2<f32>, offsets: &[i64], groups: Option<&[i32]>, n_groups: usize,
+                               variance_normalization: bool) -> Result<Array2<f32>, Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    let n_clips = offsets.len().saturating_sub(1);
+    let g = group_ptr(groups, n_clips)?;
+    let mut out = Array2::<f32>::zeros((rows, cols));
+    check(unsafe {
+        ss_cmvn_grouped_packed(x.as_ptr(), n_clips, offsets.as_ptr(), rows, cols, g, n_groups, variance_normalization as c_int, out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// One statistics row -> Kaldi's `[2 x (cols + 1)]` accumulator (`sum x | count`, then `sum x^2 | 0`), row-major.
+pub fn try_cmvn_stats_to_kaldi(stats_row: &[f64]) -> Result<Vec<f64>, Error> {
+    if stats_row.len() < 3 || stats_row.len() % 2 == 0 {
+        return Err(Error { status: SS_ERR_ARG, detail: "a statistics row has 2 * cols + 1 doubles".to_string() });
+    }
+    let cols = (stats_row.len() - 1) / 2;
+    let mut kaldi = vec![0f64; 2 * (cols + 1)];
+    check(unsafe { ss_cmvn_stats_to_kaldi(stats_row.as_ptr(), cols, kaldi.as_mut_ptr()) })?;
+    Ok(kaldi)
+}
+
+/// Kaldi's `[2 x (cols + 1)]` accumulator -> one statistics row; a count below 1 gives a fresh (all-zero) row.
+pub fn try_cmvn_stats_from_kaldi(kaldi: &[f64]) -> Result<Vec<f64>, Error> {
+    if kaldi.len() < 4 || kaldi.len() % 2 == 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "a Kaldi accumulator has 2 * (cols + 1) doubles".to_string() });
+    }
+    let cols = kaldi.len() / 2 - 1;
+    let mut row = vec![0f64; 2 * cols + 1];
+    check(unsafe { ss_cmvn_stats_from_kaldi(kaldi.as_ptr(), cols, row.as_mut_ptr()) })?;
+    Ok(row)
 }
 
 /// Floats per stream of the pool `try_cmvn_stream_packed` carries: `(win_size - 1) * cols + 1`.

@@ -23,7 +23,8 @@ from ._lib import SpeechSauceError, SsKaldiParams, SsParams, SsResampleInfo, mak
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
            "power_spectrum_of_signal", "mfcc_packed", "mfe_packed", "mfcc_list", "mel_spectrogram_packed",
-           "mel_spectrogram_list", "log_mel_spectrogram", "log_mel_spectrogram_packed", "log_mel_spectrogram_list", "stft_packed", "cmvn_packed", "cmvnw_packed", "power_to_db_packed", "lmfe_packed",
+           "mel_spectrogram_list", "log_mel_spectrogram", "log_mel_spectrogram_packed", "log_mel_spectrogram_list", "stft_packed", "cmvn_packed", "cmvnw_packed", "cmvn_stats_packed", "cmvn_apply_packed", "cmvn_grouped_packed",
+           "cmvn_stats_to_kaldi", "cmvn_stats_from_kaldi", "power_to_db_packed", "lmfe_packed",
            "MelSpectrogramStream", "StftStream",
            "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool", "CmvnStreamPool",
            "add_deltas", "add_deltas_packed", "AddDeltasStreamPool",
@@ -1763,6 +1764,183 @@ def cmvnw_packed(vec, offsets, win_size=301, variance_normalization=False):
     lib, var, w = _lib.lib(), int(bool(variance_normalization)), int(win_size)
     return _post_packed(vec, offsets, None, "cmvnw_packed", lambda p, n, t, r, c, o: lib.ss_cmvnw_packed(p, n, t, r, c, w, var, o),
                         lambda p, n, t, r, c, o, s: lib.ss_cmvnw_packed_device(p, n, t, r, c, w, var, o, s))
+
+
+def _group_table(groups, n, on_device, device, what):
+    """-> the int32 table of a grouped-CMVN call on the block's side (None stays None: every clip in group 0)"""
+    if groups is None:
+        return None
+    if _is_torch(groups):
+        import torch
+
+        if groups.dtype != torch.int32:
+            raise TypeError(f"{what}: groups must be int32, got {groups.dtype}")
+        if groups.dim() != 1 or groups.numel() != n:
+            raise ValueError(f"{what}: groups must be 1-D with n_clips = {n} entries")
+        if on_device:
+            return groups.to(device).contiguous()
+        groups = groups.cpu().numpy()
+    g = np.asarray(groups)
+    if g.ndim != 1 or g.size != n:
+        raise ValueError(f"{what}: groups must be 1-D with n_clips = {n} entries")
+    if not np.issubdtype(g.dtype, np.integer):
+        raise TypeError(f"{what}: groups must be integers, got {g.dtype}")
+    g = np.ascontiguousarray(g, dtype=np.int32)
+    if on_device:
+        import torch
+
+        return torch.from_numpy(g).to(device)
+    return g
+
+
+def _stats_block(stats, n_groups, cols, on_device, device, what, fresh):
+    """-> the float64 [n_groups, 2 * cols + 1] block on the block's side; None gives a zeroed one where `fresh` allows it"""
+    shape = (int(n_groups), 2 * cols + 1)
+    if stats is None:
+        if not fresh:
+            raise ValueError(f"{what}: stats is required")
+        if on_device:
+            import torch
+
+            return torch.zeros(shape, dtype=torch.float64, device=device)
+        return np.zeros(shape, np.float64)
+    if _is_torch(stats):
+        import torch
+
+        if stats.dtype != torch.float64:
+            raise TypeError(f"{what}: stats must be float64, got {stats.dtype}")
+        st = stats.to(device) if on_device else stats.detach().cpu().numpy()
+    else:
+        st = np.asarray(stats)
+        if st.dtype != np.float64:
+            raise TypeError(f"{what}: stats must be float64, got {st.dtype}")
+        if on_device:
+            import torch
+
+            st = torch.from_numpy(np.ascontiguousarray(st)).to(device)
+    if tuple(st.shape) == shape[1:]:
+        st = st.reshape(shape) if shape[0] == 1 else st
+    if tuple(st.shape) != shape:
+        raise ValueError(f"{what}: stats must be [n_groups, 2 * cols + 1] = {list(shape)}, got {list(st.shape)}")
+    return st.contiguous() if on_device else np.ascontiguousarray(st)
+
+
+def _ptr(a):
+    return None if a is None else a.data_ptr() if _is_torch(a) else a.ctypes.data
+
+
+def cmvn_stats_packed(vec, offsets, groups, n_groups, stats=None):
+    """Fold every clip of a packed block [sum T_b, cols] into the statistics row of its group: ``stats`` is the float64 block
+    [n_groups, 2 * cols + 1] of rows ``[n | mean | var]`` (None: a fresh, zeroed one) and the updated block is returned -- a device
+    tensor or a writable numpy array handed in is updated in place and returned itself.  ``groups`` is an int32 table with one group
+    id per clip (-1 leaves a clip out; None puts every clip into group 0).  Statistics can be accumulated batch by batch, stored,
+    and applied with ``cmvn_apply_packed``: per-speaker CMVN with one group per speaker, global CMVN with n_groups = 1."""
+    what = "cmvn_stats_packed"
+    x, on_device, rows, cols = _packed_block(vec, None, what)
+    dev = x.device if on_device else None
+    table, n = _segment_table(offsets, on_device, dev, rows, what)
+    g = _group_table(groups, n, on_device, dev, what)
+    st = _stats_block(stats, n_groups, cols, on_device, dev, what, True)
+    lib = _lib.lib()
+    if on_device:
+        import torch
+
+        with torch.cuda.device(dev):
+            _lib.check(lib.ss_cmvn_stats_packed_device(x.data_ptr(), n, table.data_ptr(), rows, cols, _ptr(g), int(n_groups), st.data_ptr(),
+                                                       _stream_ptr()))
+        return st
+    if not st.flags.writeable:
+        st = st.copy()
+    _lib.check(lib.ss_cmvn_stats_packed(x.ctypes.data, n, table.ctypes.data, rows, cols, _ptr(g), int(n_groups), st.ctypes.data))
+    return st
+
+
+def cmvn_apply_packed(vec, offsets, stats, groups=None, variance_normalization=False, out=None):
+    """Normalise every clip of a packed block by the stored statistics of its group: ``(x - mean_g) / (sqrt(var_g) + 2^-30)``, or
+    ``x - mean_g`` without variance normalisation.  ``stats`` is the block ``cmvn_stats_packed`` returns (or one row, for
+    ``groups=None``: global CMVN); ``out`` may be the block itself (in place).  Clips with group id -1, or whose group has seen no
+    row, are left as ``out`` held them (uninitialised for a fresh ``out``).  A pool tick's rows with its ``row_offsets`` are a
+    packed block too: this is the online global CMVN of a stream pool."""
+    what = "cmvn_apply_packed"
+    x, on_device, rows, cols = _packed_block(vec, None, what)
+    dev = x.device if on_device else None
+    table, n = _segment_table(offsets, on_device, dev, rows, what)
+    g = _group_table(groups, n, on_device, dev, what)
+    n_groups = int(stats.shape[0]) if getattr(stats, "ndim", 0) == 2 else 1
+    st = _stats_block(stats, n_groups, cols, on_device, dev, what, False)
+    var, lib = int(bool(variance_normalization)), _lib.lib()
+    if on_device:
+        import torch
+
+        if out is None:
+            out = torch.empty_like(x)
+        elif not (_is_torch(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape):
+            raise ValueError(f"{what}: out must be a contiguous float32 device tensor of the block's shape")
+        with torch.cuda.device(dev):
+            _lib.check(lib.ss_cmvn_apply_packed_device(x.data_ptr(), n, table.data_ptr(), rows, cols, _ptr(g), n_groups, st.data_ptr(), var,
+                                                       out.data_ptr(), _stream_ptr()))
+        return out
+    if out is None:
+        out = np.empty_like(x)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == x.shape):
+        raise ValueError(f"{what}: out must be a contiguous float32 array of the block's shape")
+    _lib.check(lib.ss_cmvn_apply_packed(x.ctypes.data, n, table.ctypes.data, rows, cols, _ptr(g), n_groups, st.ctypes.data, var, out.ctypes.data))
+    return out
+
+
+def cmvn_grouped_packed(vec, offsets, groups, n_groups=None, variance_normalization=False):
+    """Per-speaker CMVN of one batch: statistics of every group from the batch's own clips, then ``cmvn_apply_packed``, in one call.
+    ``n_groups`` defaults to max(groups) + 1 for a host table (a device table needs it stated: nothing is read back)."""
+    what = "cmvn_grouped_packed"
+    x, on_device, rows, cols = _packed_block(vec, None, what)
+    dev = x.device if on_device else None
+    table, n = _segment_table(offsets, on_device, dev, rows, what)
+    if n_groups is None:
+        if groups is None:
+            n_groups = 1
+        elif _is_torch(groups) and groups.is_cuda:
+            raise ValueError(f"{what}: a device table of groups needs n_groups")
+        else:
+            n_groups = max(1, int(np.asarray(groups.cpu() if _is_torch(groups) else groups).max(initial=-1)) + 1)
+    g = _group_table(groups, n, on_device, dev, what)
+    var, lib = int(bool(variance_normalization)), _lib.lib()
+    if on_device:
+        import torch
+
+        out = torch.empty_like(x)
+        with torch.cuda.device(dev):
+            _lib.check(lib.ss_cmvn_grouped_packed_device(x.data_ptr(), n, table.data_ptr(), rows, cols, _ptr(g), int(n_groups), var, out.data_ptr(),
+                                                         _stream_ptr()))
+        return out
+    out = np.empty_like(x)
+    _lib.check(lib.ss_cmvn_grouped_packed(x.ctypes.data, n, table.ctypes.data, rows, cols, _ptr(g), int(n_groups), var, out.ctypes.data))
+    return out
+
+
+def _kaldi_convert(a, what, fn, in_len, out_len):
+    a = np.ascontiguousarray(np.asarray(a.detach().cpu().numpy() if _is_torch(a) else a), dtype=np.float64)
+    cols = in_len(a.size)
+    if cols is None or cols < 1:
+        raise ValueError(f"{what}: not a statistics row or a Kaldi accumulator ({a.size} values)")
+    out = np.empty(out_len(cols), np.float64)
+    _lib.check(fn(a.ctypes.data, cols, out.ctypes.data))
+    return out
+
+
+def cmvn_stats_to_kaldi(stats_row):
+    """One statistics row ``[n | mean | var]`` -> Kaldi's float64 accumulator [2, cols + 1]: ``sum x | count``, then ``sum x^2 | 0``
+    (cmvn.ark; WeNet's mean_stat / var_stat / frame_num)."""
+    lib = _lib.lib()
+    out = _kaldi_convert(stats_row, "cmvn_stats_to_kaldi", lib.ss_cmvn_stats_to_kaldi,
+                         lambda k: (k - 1) // 2 if k % 2 == 1 else None, lambda c: 2 * (c + 1))
+    return out.reshape(2, -1)
+
+
+def cmvn_stats_from_kaldi(kaldi):
+    """Kaldi's accumulator [2, cols + 1] -> one statistics row ``[n | mean | var]``; a count below 1 gives a fresh (all-zero) row."""
+    lib = _lib.lib()
+    return _kaldi_convert(kaldi, "cmvn_stats_from_kaldi", lib.ss_cmvn_stats_from_kaldi,
+                          lambda k: k // 2 - 1 if k % 2 == 0 else None, lambda c: 2 * c + 1)
 
 
 def power_to_db_packed(S, offsets, cols=None, ref=1.0, amin=1e-10, top_db=80.0):

@@ -236,6 +236,16 @@ PROTOTYPES = {
     "ss_cmvn_stream_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
                                                _fp, _fp, C.c_void_p]),
     "ss_cmvn_stream_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _fp, _fp]),
+    "ss_cmvn_stats_len": (C.c_int, [C.c_size_t, _P(C.c_size_t)]),
+    "ss_cmvn_stats_to_kaldi": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ss_cmvn_stats_from_kaldi": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ss_cmvn_stats_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ss_cmvn_apply_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, _fp,
+                                              C.c_void_p]),
+    "ss_cmvn_grouped_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, _fp, C.c_void_p]),
+    "ss_cmvn_stats_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ss_cmvn_apply_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, _fp]),
+    "ss_cmvn_grouped_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, _fp]),
     "ss_add_deltas_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, C.c_void_p]),
     "ss_add_deltas_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp]),
     "ss_add_deltas_stream_state_len": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, _P(C.c_size_t)]),

@@ -74,6 +74,19 @@ static void check_clip_table_rule()
     expect(ss::check_clip_table(zero, 1, 0), nullptr, "an empty block");
 }
 
+static void check_clip_group_rule()
+{
+    const int32_t ok[] = {0, 3, -1, 2, 3, 0};
+    expect(ss::check_clip_groups(ok, 6, 4), nullptr, "ids inside the groups, -1 leaves a clip out");
+    expect(ss::check_clip_groups(ok, 0, 4), nullptr, "n_clips == 0");
+    const int32_t edge[] = {0, 4, 5};
+    expect(ss::check_clip_groups(edge, 3, 4), "clip 1: group 4 is outside the 4 groups (-1 leaves a clip out)", "== n_groups: the first is named");
+    const int32_t neg[] = {1, -1, -2};
+    expect(ss::check_clip_groups(neg, 3, 4), "clip 2: group -2 is outside the 4 groups (-1 leaves a clip out)", "below -1");
+    const int32_t big[] = {2147483647};
+    expect(ss::check_clip_groups(big, 1, 1), "clip 0: group 2147483647 is outside the 1 groups (-1 leaves a clip out)", "INT32_MAX");
+}
+
 static void check_row_offset_rule()
 {
     const int64_t first[] = {1, 2, 3, 4};
@@ -149,6 +162,7 @@ int main()
 {
     check_slot_rule();
     check_clip_table_rule();
+    check_clip_group_rule();
     check_row_offset_rule();
     check_overlap();
     for (size_t len : {size_t{4}, size_t{1}, size_t{0}}) check_pool_rows(len);
