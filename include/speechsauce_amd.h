@@ -1150,6 +1150,67 @@ int ss_pad_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_ro
 int ss_pad_packed(const float *vec, size_t n_clips, const int64_t *row_offsets, size_t total_rows, size_t cols, size_t max_rows,
                   int layout, int dtype, float pad_value, void *out, int32_t *lengths);
 
+/* ---- SpecAugment: time / frequency masking of packed rows, seeded on the device ----
+ * The augmentation every training recipe applies between CMVN and collation (WeNet spec_aug, ESPnet SpecAug, torchaudio
+ * TimeMasking / FrequencyMasking): n_time spans of rows and n_freq spans of columns of every clip are overwritten with mask_value.
+ * The spans are drawn on the device from a counter-based generator, so the stage reads nothing back, needs no host lengths and
+ * draws fresh masks on every replay of a captured graph.  The reference crate has none: this comment is the specification.
+ *   Clip b owns rows ro[b] .. ro[b+1] of vec [total_rows x cols]; T_b = ro[b+1] - ro[b].
+ *   Scalars: n_time, n_freq (0 .. 16 each); max_time_width, max_freq_width; time_ratio (a float in [0, 1]; 1 = no cap by the clip's
+ *   length); mask_value (any float, NaN and -0.0 included: it is written as its bit pattern); clip_base (the id of clip 0).
+ *   rng: two uint64 words {seed, epoch}.
+ *   Generator: Philox4x32-10 (Salmon et al., Random123; csrc/ss_philox.h), philox(counter[4], key[2]) -> four 32-bit words.
+ *   Bounds: W_b = min(max_time_width, (uint32)floor((double)time_ratio * (double)T_b)) -- one f64 product, truncated;
+ *           F = min(max_freq_width, cols).
+ *   Draw of mask index k (k = time mask k for k < n_time; k = 0x10000 + j for frequency mask j):
+ *     (u0, u1, -, -) = philox((low32(clip_base + b), k, low32(epoch), high32(epoch)), (low32(seed), high32(seed)))
+ *     width = (u0 * (bound + 1)) >> 32 in 64-bit integers, so width is in [0, bound]             (bound = W_b or F)
+ *     start = (u1 * (extent - width + 1)) >> 32, so start is in [0, extent - width]                (extent = T_b or cols)
+ *     words 2 and 3 are reserved.
+ *   Spans table: int32 [n_clips x (n_time + n_freq) x 2], (start, width) pairs, time masks first.  A segment that is reversed,
+ *   starts below 0 or ends past total_rows has (-1, 0) in every one of its spans.
+ *   out[r][c] = mask_value where row r - ro[b] lies in any time span of its clip or c lies in any frequency span of its clip, and
+ *   a bit copy of vec[r][c] otherwise (NaN payloads, -0.0 and denormals unchanged); overlapping spans are a union.
+ *   A clip's spans depend on (seed, epoch, clip_base + b, T_b, cols, the scalars) only -- not on its offset or its neighbours: the
+ *   clips [B, C] at clip_base 1 get the spans they have as clips 1 and 2 of [A, B, C] at clip_base 0.
+ *   Worked pin: seed 2026, epoch 0, clip_base 0, T_b = 200, max_time_width = 40, time_ratio 1, n_time = 2: clips 0, 1, 2 have
+ *   (start, width) = (96, 17) (1, 29) | (56, 40) (105, 31) | (124, 28) (130, 13).
+ * Calls:
+ *   ss_specaug_spans               host only, no device: the spans table the plan launch writes, from the same code.
+ *   ss_specaug_plan_packed_device  the plan launch alone (ss_specaug_plan_kernel, one lane per clip and mask); epoch is not touched.
+ *   ss_mask_spans_packed[_device]  the apply launch alone (ss_specaug_apply_kernel<copy|inplace>) on any spans table -- the caller's
+ *                                  own, or one plan applied to two blocks.  A span that is out of range (start < 0, width < 0 or start
+ *                                  + width > its extent) is skipped whole.
+ *   ss_specaug_packed[_device]     plan + apply, two launches, and the epoch bump: lane 0 of the apply launch stores epoch + 1, so
+ *                                  the next call -- or the next replay of a captured graph -- draws other masks with no host
+ *                                  involvement.  d_spans is caller-owned and always written; the host form updates rng[1].
+ *   d_out == d_vec is the in-place call: nothing of vec is loaded and only the masked elements are stored.  Otherwise out must not
+ *   overlap vec.  Rows of a bad segment and rows in no clip are left untouched (out of place: left unwritten); nothing outside [0,
+ *   total_rows) x cols is read or written, whatever the table or the spans hold.  The grids depend on n_clips, n_time and n_freq
+ *   only; the device forms are asynchronous on `stream`, allocate nothing and read nothing back.
+ *   One rng block serves one stream of calls: concurrent calls that share a block race on epoch (give every stream its own block,
+ *   with its own seed or a disjoint clip_base range).
+ * Arguments: n_clips == 0 is SS_OK, also without a device.  SS_ERR_ARG, decided before the device is touched: null buffers (spans
+ * may be null when n_time + n_freq == 0); cols == 0; n_time or n_freq > 16; time_ratio outside [0, 1] or NaN; n_clips, total_rows,
+ * cols, max_time_width or max_freq_width >= 2^31; clip_base + n_clips > 2^32; vec, out or spans not 4-byte, rng not 8-byte aligned;
+ * out partly overlapping vec (equal is in place); spans or rng overlapping vec, out or each other.  The host forms check the table
+ * first as the other host forms do and name the first bad clip in ss_last_error_string(); they write rows 0 .. ro[n_clips) of out. */
+int ss_specaug_spans(const uint64_t *rng, size_t clip_base, size_t n_clips, const int64_t *row_offsets, size_t total_rows, size_t cols,
+                     size_t n_time, size_t max_time_width, float time_ratio, size_t n_freq, size_t max_freq_width, int32_t *spans);
+int ss_specaug_plan_packed_device(const uint64_t *d_rng, size_t clip_base, size_t n_clips, const int64_t *d_row_offsets,
+                                  size_t total_rows, size_t cols, size_t n_time, size_t max_time_width, float time_ratio,
+                                  size_t n_freq, size_t max_freq_width, int32_t *d_spans, void *stream);
+int ss_mask_spans_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_row_offsets, size_t total_rows, size_t cols,
+                                const int32_t *d_spans, size_t n_time, size_t n_freq, float mask_value, float *d_out, void *stream);
+int ss_mask_spans_packed(const float *vec, size_t n_clips, const int64_t *row_offsets, size_t total_rows, size_t cols,
+                         const int32_t *spans, size_t n_time, size_t n_freq, float mask_value, float *out);
+int ss_specaug_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_row_offsets, size_t total_rows, size_t cols,
+                             uint64_t *d_rng, size_t clip_base, size_t n_time, size_t max_time_width, float time_ratio, size_t n_freq,
+                             size_t max_freq_width, float mask_value, float *d_out, int32_t *d_spans, void *stream);
+int ss_specaug_packed(const float *vec, size_t n_clips, const int64_t *row_offsets, size_t total_rows, size_t cols, uint64_t *rng,
+                      size_t clip_base, size_t n_time, size_t max_time_width, float time_ratio, size_t n_freq, size_t max_freq_width,
+                      float mask_value, float *out, int32_t *spans);
+
 /* ---- polyphase windowed-sinc resampling ahead of the feature calls ----
  * Every call above takes audio at the rate its ss_params was built for; these calls bring telephony (8 kHz), capture (48 kHz) and
  * corpus (44.1 kHz) audio to it on the device, on the packed layout and the stream pools of the feature calls, from floats or 16-bit

@@ -697,6 +697,55 @@ inline std::vector<uint8_t> pad_packed(const std::vector<float> &vec, const std:
     return out;
 }
 
+// SpecAugment of a packed block (ss_specaug_*): n_time spans of at most min(max_time_width, time_ratio * T_b) rows and n_freq spans of
+// at most max_freq_width columns of every clip are overwritten with mask_value; the spans are Philox4x32-10 draws of rng = {seed,
+// epoch} and clip_base + b.  The defaults are the LibriSpeech policy.
+struct SpecAugPolicy {
+    size_t n_time = 2, max_time_width = 100;
+    float time_ratio = 1.0f;
+    size_t n_freq = 2, max_freq_width = 27;
+    float mask_value = 0.0f;
+    size_t clip_base = 0;
+};
+
+// the spans table [n_clips x (n_time + n_freq) x 2] of (start, width) pairs that spec_augment_packed draws: host only, no device
+inline std::vector<int32_t> spec_augment_spans(const uint64_t (&rng)[2], const std::vector<int64_t> &offsets, size_t total_rows, size_t cols,
+                                               const SpecAugPolicy &policy = SpecAugPolicy())
+{
+    if (offsets.empty()) throw Error(SS_ERR_ARG, "spec_augment_spans: shape mismatch");
+    std::vector<int32_t> spans((offsets.size() - 1) * (policy.n_time + policy.n_freq) * 2);
+    check(ss_specaug_spans(rng, policy.clip_base, offsets.size() - 1, offsets.data(), total_rows, cols, policy.n_time, policy.max_time_width, policy.time_ratio,
+                           policy.n_freq, policy.max_freq_width, spans.data()));
+    return spans;
+}
+
+// the block with the spans of `spans` overwritten (time spans first); a span outside its clip is skipped whole
+inline std::vector<float> mask_spans_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, const std::vector<int32_t> &spans,
+                                            size_t n_time, size_t n_freq, float mask_value = 0.0f)
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty() || spans.size() != (offsets.size() - 1) * (n_time + n_freq) * 2)
+        throw Error(SS_ERR_ARG, "mask_spans_packed: shape mismatch");
+    std::vector<float> out(vec);
+    if (!vec.empty())
+        check(ss_mask_spans_packed(vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, spans.data(), n_time, n_freq, mask_value, out.data()));
+    return out;
+}
+
+// plan + apply; rng[1] (the epoch) is advanced by one and `spans` receives the table that was applied
+inline std::vector<float> spec_augment_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, uint64_t (&rng)[2],
+                                              std::vector<int32_t> &spans, const SpecAugPolicy &policy = SpecAugPolicy())
+{
+    if (cols == 0 || vec.size() % cols || offsets.empty()) throw Error(SS_ERR_ARG, "spec_augment_packed: shape mismatch");
+    std::vector<float> out(vec);
+    spans.assign((offsets.size() - 1) * (policy.n_time + policy.n_freq) * 2, 0);
+    const float none = 0.0f;  // a block without rows still needs an address
+    float spare = 0.0f;
+    check(ss_specaug_packed(vec.empty() ? &none : vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, rng, policy.clip_base, policy.n_time,
+                            policy.max_time_width, policy.time_ratio, policy.n_freq, policy.max_freq_width, policy.mask_value,
+                            vec.empty() ? &spare : out.data(), spans.data()));
+    return out;
+}
+
 inline std::vector<float> cmvnw_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t win_size = 301,
                                        bool variance_normalization = false)
 {

@@ -219,6 +219,22 @@ extern "C" {
                             stream: *mut c_void) -> c_int;
     fn ss_pad_packed(vec: *const f32, n_clips: usize, row_offsets: *const i64, total_rows: usize, cols: usize, max_rows: usize,
                      layout: c_int, dtype: c_int, pad_value: f32, out: *mut c_void, lengths: *mut i32) -> c_int;
+    fn ss_specaug_spans(rng: *const u64, clip_base: usize, n_clips: usize, row_offsets: *const i64, total_rows: usize, cols: usize, n_time: usize,
+                        max_time_width: usize, time_ratio: f32, n_freq: usize, max_freq_width: usize, spans: *mut i32) -> c_int;
+    fn ss_specaug_plan_packed_device(d_rng: *const u64, clip_base: usize, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize,
+                                     n_time: usize, max_time_width: usize, time_ratio: f32, n_freq: usize, max_freq_width: usize,
+                                     d_spans: *mut i32, stream: *mut c_void) -> c_int;
+    fn ss_mask_spans_packed_device(d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize,
+                                   d_spans: *const i32, n_time: usize, n_freq: usize, mask_value: f32, d_out: *mut f32,
+                                   stream: *mut c_void) -> c_int;
+    fn ss_mask_spans_packed(vec: *const f32, n_clips: usize, row_offsets: *const i64, total_rows: usize, cols: usize, spans: *const i32,
+                            n_time: usize, n_freq: usize, mask_value: f32, out: *mut f32) -> c_int;
+    fn ss_specaug_packed_device(d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize, d_rng: *mut u64,
+                                clip_base: usize, n_time: usize, max_time_width: usize, time_ratio: f32, n_freq: usize, max_freq_width: usize,
+                                mask_value: f32, d_out: *mut f32, d_spans: *mut i32, stream: *mut c_void) -> c_int;
+    fn ss_specaug_packed(vec: *const f32, n_clips: usize, row_offsets: *const i64, total_rows: usize, cols: usize, rng: *mut u64,
+                         clip_base: usize, n_time: usize, max_time_width: usize, time_ratio: f32, n_freq: usize, max_freq_width: usize,
+                         mask_value: f32, out: *mut f32, spans: *mut i32) -> c_int;
     fn ss_resample_packed_offsets(orig_rate: u32, new_rate: u32, n_clips: usize, sample_offsets: *const i64, out_offsets: *mut i64) -> c_int;
     fn ss_resampler_create(orig_rate: u32, new_rate: u32, lowpass_filter_width: u32, rolloff: f32, out: *mut *mut c_void) -> c_int;
     fn ss_resampler_destroy(rs: *mut c_void);
@@ -1427,6 +1443,110 @@ pub unsafe fn pad_packed_device(d_vec: *const f32, n_clips: usize, d_row_offsets
                                 stream: *mut c_void) -> Result<(), Error> {
     check(ss_pad_packed_device(d_vec, n_clips, d_row_offsets, total_rows, cols, max_rows, layout as c_int, dtype as c_int, pad_value, d_out,
                                d_lengths, stream))
+}
+
+/// The SpecAugment policy of one call: `n_time` spans of at most `min(max_time_width, time_ratio * T_b)` rows and `n_freq` spans of at
+/// most `max_freq_width` columns of every clip are overwritten with `mask_value` (written as its bit pattern).  `clip_base` is the id
+/// of clip 0: a shard that starts at global clip `clip_base` draws what the whole batch would.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct SpecAugPolicy {
+    pub n_time: usize,
+    pub max_time_width: usize,
+    pub time_ratio: f32,
+    pub n_freq: usize,
+    pub max_freq_width: usize,
+    pub mask_value: f32,
+    pub clip_base: usize,
+}
+
+impl Default for SpecAugPolicy {
+    /// The LibriSpeech policy: 2 x 100 rows, 2 x 27 columns, no cap by length, zeros.
+    fn default() -> Self {
+        SpecAugPolicy { n_time: 2, max_time_width: 100, time_ratio: 1.0, n_freq: 2, max_freq_width: 27, mask_value: 0.0, clip_base: 0 }
+    }
+}
+
+/// The spans `try_spec_augment_packed` draws for `rng = [seed, epoch]`, computed on the host (no device): `(start, width)` pairs,
+/// `[n_clips x (n_time + n_freq) x 2]`, time masks first; a bad segment of the table has `(-1, 0)` in every span.
+pub fn try_spec_augment_spans(rng: [u64; 2], row_offsets: &[i64], total_rows: usize, cols: usize, policy: &SpecAugPolicy) -> Result<Vec<i32>, Error> {
+    if row_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "spec_augment_spans: row_offsets must not be empty".to_string() });
+    }
+    let n_clips = row_offsets.len() - 1;
+    let mut spans = vec![0i32; n_clips * (policy.n_time + policy.n_freq) * 2];
+    check(unsafe {
+        ss_specaug_spans(rng.as_ptr(), policy.clip_base, n_clips, row_offsets.as_ptr(), total_rows, cols, policy.n_time, policy.max_time_width,
+                         policy.time_ratio, policy.n_freq, policy.max_freq_width, spans.as_mut_ptr())
+    })?;
+    Ok(spans)
+}
+
+/// Overwrite the spans of `spans` (`[n_clips x (n_time + n_freq) x 2]`, time spans first) in every clip of a packed block with
+/// `mask_value`; a span outside its clip is skipped whole.  Every other element is a bit copy.
+pub fn try_mask_spans_packed(vec: ArrayView2<f32>, row_offsets: &[i64], spans: &[i32], n_time: usize, n_freq: usize,
+                             mask_value: f32) -> Result<Array2<f32>, Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    if row_offsets.is_empty() || spans.len() != (row_offsets.len() - 1) * (n_time + n_freq) * 2 {
+        return Err(Error { status: SS_ERR_ARG, detail: "mask_spans_packed: row_offsets or spans have the wrong length".to_string() });
+    }
+    let mut out = x.to_owned();
+    check(unsafe {
+        ss_mask_spans_packed(x.as_ptr(), row_offsets.len() - 1, row_offsets.as_ptr(), rows, cols, spans.as_ptr(), n_time, n_freq, mask_value,
+                             out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
+/// SpecAugment of every clip of a packed block: the masked block and the spans that were applied.  `rng = [seed, epoch]`; the call
+/// advances `rng[1]` by one, so the next call draws other masks.
+pub fn try_spec_augment_packed(vec: ArrayView2<f32>, row_offsets: &[i64], rng: &mut [u64; 2],
+                               policy: &SpecAugPolicy) -> Result<(Array2<f32>, Vec<i32>), Error> {
+    let x = vec.as_standard_layout();
+    let (rows, cols) = x.dim();
+    if row_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: "spec_augment_packed: row_offsets must not be empty".to_string() });
+    }
+    let n_clips = row_offsets.len() - 1;
+    let mut out = x.to_owned();
+    let mut spans = vec![0i32; n_clips * (policy.n_time + policy.n_freq) * 2];
+    check(unsafe {
+        ss_specaug_packed(x.as_ptr(), n_clips, row_offsets.as_ptr(), rows, cols, rng.as_mut_ptr(), policy.clip_base, policy.n_time,
+                          policy.max_time_width, policy.time_ratio, policy.n_freq, policy.max_freq_width, policy.mask_value, out.as_mut_ptr(),
+                          spans.as_mut_ptr())
+    })?;
+    Ok((out, spans))
+}
+
+/// The plan launch alone (include/speechsauce_amd.h has the contract): writes the spans table, does not touch the epoch.
+///
+/// # Safety
+/// As `vad_energy_packed_device`; `d_rng` is the 16-byte device block `{seed, epoch}`, `d_spans` holds `n_clips * (n_time + n_freq)` pairs.
+pub unsafe fn spec_augment_plan_packed_device(d_rng: *const u64, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize,
+                                              policy: &SpecAugPolicy, d_spans: *mut i32, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_specaug_plan_packed_device(d_rng, policy.clip_base, n_clips, d_row_offsets, total_rows, cols, policy.n_time, policy.max_time_width,
+                                        policy.time_ratio, policy.n_freq, policy.max_freq_width, d_spans, stream))
+}
+
+/// The apply launch alone, on any spans table; `d_out == d_vec` masks in place.
+///
+/// # Safety
+/// As `spec_augment_plan_packed_device`; `d_out` holds `total_rows * cols` floats and is `d_vec` itself or does not overlap it.
+pub unsafe fn mask_spans_packed_device(d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize,
+                                       d_spans: *const i32, n_time: usize, n_freq: usize, mask_value: f32, d_out: *mut f32,
+                                       stream: *mut c_void) -> Result<(), Error> {
+    check(ss_mask_spans_packed_device(d_vec, n_clips, d_row_offsets, total_rows, cols, d_spans, n_time, n_freq, mask_value, d_out, stream))
+}
+
+/// Plan, apply and the epoch bump: two asynchronous launches on `stream`, nothing read back; replays of a captured graph draw fresh masks.
+///
+/// # Safety
+/// As `mask_spans_packed_device`; one `d_rng` block serves one stream of calls (concurrent calls on one block race on its epoch).
+pub unsafe fn spec_augment_packed_device(d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, cols: usize,
+                                         d_rng: *mut u64, policy: &SpecAugPolicy, d_out: *mut f32, d_spans: *mut i32,
+                                         stream: *mut c_void) -> Result<(), Error> {
+    check(ss_specaug_packed_device(d_vec, n_clips, d_row_offsets, total_rows, cols, d_rng, policy.clip_base, policy.n_time, policy.max_time_width,
+                                   policy.time_ratio, policy.n_freq, policy.max_freq_width, policy.mask_value, d_out, d_spans, stream))
 }
 
 /// librosa's power_to_db of every clip of a packed block with the clip's own `top_db` floor (`None`: no floor); clip b's segment

@@ -31,6 +31,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "splice", "splice_packed", "lfr", "lfr_packed", "SpliceStreamPool",
            "vad_energy", "vad_energy_packed", "select_rows", "select_rows_packed", "VadEnergyStreamPool",
            "pad", "pad_packed",
+           "spec_augment_spans", "mask_spans_packed", "spec_augment_packed", "SpecAugment",
            "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "KaldiFbankStreamPool", "KaldiMfccStreamPool",
@@ -2669,6 +2670,205 @@ def pad(matrices, max_rows=None, layout="btc", dtype="float32", pad_value=0.0):
     else:
         block = np.concatenate([np.asarray(m) for m in mats])
     return pad_packed(block, ro, max_rows, layout, dtype, pad_value)
+
+
+# ---- SpecAugment: time / frequency masking of packed rows, seeded on the device (ss_specaug_* / ss_mask_spans_*) ------------------
+# A clip's spans are a pure function of (seed, epoch, clip_base + b, T_b, cols, the scalars): Philox4x32-10, no generator state.
+
+def _specaug_scalars(time_masks, time_width, time_ratio, freq_masks, freq_width, clip_base, what):
+    nt, nf, tw, fw, base, ratio = int(time_masks), int(freq_masks), int(time_width), int(freq_width), int(clip_base), float(time_ratio)
+    if not (0 <= nt <= 16 and 0 <= nf <= 16):
+        raise ValueError(f"{what}: time_masks and freq_masks must lie in 0 .. 16")
+    if not (0 <= tw < 1 << 31 and 0 <= fw < 1 << 31):
+        raise ValueError(f"{what}: time_width and freq_width must lie in 0 .. 2^31 - 1")
+    if not 0.0 <= ratio <= 1.0:
+        raise ValueError(f"{what}: time_ratio must lie in [0, 1]")
+    if not 0 <= base <= 1 << 32:
+        raise ValueError(f"{what}: clip_base must lie in 0 .. 2^32")
+    return nt, tw, ratio, nf, fw, base
+
+
+def _rng_words(rng, what):
+    """-> the uint64 pair {seed, epoch} of a host-side rng: a SpecAugment (read back), a pair of ints or an array of two"""
+    if isinstance(rng, SpecAugment):
+        return np.array([rng.seed, rng.epoch], np.uint64)
+    if isinstance(rng, np.ndarray) and rng.dtype == np.uint64 and rng.shape == (2,):
+        return np.ascontiguousarray(rng)
+    try:
+        seed, epoch = (int(v) for v in rng)
+    except (TypeError, ValueError):
+        raise TypeError(f"{what}: rng must be a SpecAugment, a (seed, epoch) pair or a uint64 array of two") from None
+    if not (0 <= seed < 1 << 64 and 0 <= epoch < 1 << 64):
+        raise ValueError(f"{what}: seed and epoch must lie in 0 .. 2^64 - 1")
+    return np.array([seed, epoch], np.uint64)
+
+
+def spec_augment_spans(rng, row_offsets, cols, time_masks=2, time_width=100, time_ratio=1.0, freq_masks=2, freq_width=27, clip_base=0,
+                       total_rows=None):
+    """The spans ``spec_augment_packed`` draws, computed on the host (no device): int32 ``[n_clips, time_masks + freq_masks, 2]`` of
+    ``(start, width)`` pairs, time masks first.  ``rng`` is a ``(seed, epoch)`` pair, a uint64 array of two or a ``SpecAugment``
+    (read back); ``row_offsets`` a host table, taken as it is: a segment that is reversed, starts below 0 or ends past
+    ``total_rows`` (default: the table's last entry) has ``(-1, 0)`` in every span, as on the device."""
+    what = "spec_augment_spans"
+    nt, tw, ratio, nf, fw, base = _specaug_scalars(time_masks, time_width, time_ratio, freq_masks, freq_width, clip_base, what)
+    words = _rng_words(rng, what)
+    off = np.asarray(row_offsets.cpu().numpy() if _is_torch(row_offsets) else row_offsets)
+    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError(f"{what}: row_offsets must be 1-D integers with n_clips + 1 entries")
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    if int(cols) < 1:
+        raise ValueError(f"{what}: cols must be at least 1")
+    total = max(int(off[-1]), 0) if total_rows is None else int(total_rows)
+    n = off.size - 1
+    spans = np.zeros((n, nt + nf, 2), np.int32)
+    if n and nt + nf:
+        _lib.check(_lib.lib().ss_specaug_spans(words.ctypes.data, base, n, off.ctypes.data, total, int(cols), nt, tw, ratio, nf, fw, spans.ctypes.data))
+    return spans
+
+
+def _mask_block(rows, row_offsets, out, what):
+    """-> (x, on_device, total_rows, cols, table, n, out) of a masking call; ``out`` None is a fresh block, ``out`` on the block's own
+    memory is the in-place call"""
+    x, on_device, total_rows, cols = _packed_block(rows, None, what)
+    if cols < 1:
+        raise ValueError(f"{what}: the block has no columns")
+    table, n = _segment_table(row_offsets, on_device, x.device if on_device else None, total_rows, what)
+    if on_device:
+        import torch
+
+        if out is None:
+            out = torch.empty_like(x)
+        elif not (_is_torch(out) and out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape):
+            raise ValueError(f"{what}: out must be a contiguous float32 device tensor of the block's shape")
+    elif out is None:
+        out = np.empty_like(x)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable and out.shape == x.shape):
+        raise ValueError(f"{what}: out must be a writable contiguous float32 array of the block's shape")
+    return x, on_device, total_rows, cols, table, n, out
+
+
+def mask_spans_packed(rows, row_offsets, spans, n_time, n_freq, mask_value=0.0, out=None):
+    """Overwrite spans of rows and of columns of every clip of a packed block [sum T_b, cols] with ``mask_value``: ``spans`` is the
+    int32 table ``[n_clips, n_time + n_freq, 2]`` of ``(start, width)`` pairs, time spans (rows of the clip) first, then frequency
+    spans (columns) -- the table ``spec_augment_packed`` returns, so that one plan can be applied to a second block, or the caller's
+    own.  A span that does not lie inside its clip is skipped whole.  ``out=rows`` masks in place (only the masked elements are
+    written); a fresh ``out`` holds a bit copy of every unmasked element, and rows that no clip covers are uninitialised.  numpy in
+    -> the host-pointer call; a ROCm tensor stays on the device (current stream, nothing is read back)."""
+    what = "mask_spans_packed"
+    nt, nf = int(n_time), int(n_freq)
+    if not (0 <= nt <= 16 and 0 <= nf <= 16):
+        raise ValueError(f"{what}: n_time and n_freq must lie in 0 .. 16")
+    x, on_device, total_rows, cols, table, n, out = _mask_block(rows, row_offsets, out, what)
+    lib, mask_value = _lib.lib(), float(mask_value)
+    if on_device:
+        import torch
+
+        if _is_torch(spans):
+            if spans.dtype != torch.int32:
+                raise TypeError(f"{what}: spans must be int32, got {spans.dtype}")
+            sp = spans.to(x.device).contiguous()
+        else:
+            sp = torch.from_numpy(np.ascontiguousarray(spans, dtype=np.int32)).to(x.device)
+        if sp.numel() != n * (nt + nf) * 2:
+            raise ValueError(f"{what}: spans must hold n_clips * (n_time + n_freq) pairs")
+        if n and total_rows:
+            with torch.cuda.device(x.device):
+                _lib.check(lib.ss_mask_spans_packed_device(x.data_ptr(), n, table.data_ptr(), total_rows, cols, _ptr(sp) or None, nt, nf, mask_value,
+                                                           out.data_ptr(), _stream_ptr()))
+                for t in (x, table, sp):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                    t.record_stream(torch.cuda.current_stream())
+        return out
+    sp = np.ascontiguousarray(spans.cpu().numpy() if _is_torch(spans) else spans)
+    if sp.dtype != np.int32:
+        raise TypeError(f"{what}: spans must be int32, got {sp.dtype}")
+    if sp.size != n * (nt + nf) * 2:
+        raise ValueError(f"{what}: spans must hold n_clips * (n_time + n_freq) pairs")
+    if n and total_rows:
+        _lib.check(lib.ss_mask_spans_packed(x.ctypes.data, n, table.ctypes.data, total_rows, cols, sp.ctypes.data if sp.size else None, nt, nf, mask_value,
+                                            out.ctypes.data))
+    return out
+
+
+def spec_augment_packed(rows, row_offsets, rng, time_masks=2, time_width=100, time_ratio=1.0, freq_masks=2, freq_width=27, mask_value=0.0,
+                        clip_base=0, out=None):
+    """SpecAugment of every clip of a packed block [sum T_b, cols]: -> (out, spans).  ``time_masks`` spans of at most ``min(time_width,
+    time_ratio * T_b)`` rows and ``freq_masks`` spans of at most ``freq_width`` columns of every clip are overwritten with
+    ``mask_value`` (after CMVN the mean is 0); widths and starts are uniform draws of Philox4x32-10 keyed by ``rng``'s seed and counted
+    by its epoch and ``clip_base + b``, so a clip's masks depend on neither its place in the block nor its neighbours, and a shard
+    that starts at global clip ``clip_base`` draws what the whole batch would.  The call advances the epoch by one: the next call,
+    or the next replay of a captured graph, draws other masks.  ``spans`` is the int32 table ``[n_clips, time_masks + freq_masks, 2]``
+    of ``(start, width)`` pairs that was applied.  On the device (ROCm tensors, current stream, nothing read back) ``rng`` is a
+    ``SpecAugment`` or its int64 device block of two words; for numpy input it is a ``SpecAugment`` or a writable uint64 array
+    ``[seed, epoch]``, updated in place.  ``out=rows`` masks in place; see ``mask_spans_packed``.  One ``rng`` serves one stream of
+    calls: concurrent calls on one block race on its epoch."""
+    what = "spec_augment_packed"
+    nt, tw, ratio, nf, fw, base = _specaug_scalars(time_masks, time_width, time_ratio, freq_masks, freq_width, clip_base, what)
+    x, on_device, total_rows, cols, table, n, out = _mask_block(rows, row_offsets, out, what)
+    lib, mask_value = _lib.lib(), float(mask_value)
+    if on_device:
+        import torch
+
+        block = rng._block if isinstance(rng, SpecAugment) else rng
+        if not (_is_torch(block) and block.is_cuda and block.device == x.device and block.dtype == torch.int64 and block.numel() == 2 and block.is_contiguous()):
+            raise TypeError(f"{what}: on the device rng must be a SpecAugment or a contiguous int64 tensor of two words on the block's device")
+        spans = torch.zeros((n, nt + nf, 2), dtype=torch.int32, device=x.device)
+        if n:
+            with torch.cuda.device(x.device):
+                xin, xout = (x, out) if total_rows else (torch.zeros((1, cols), device=x.device),) * 2  # no rows: the call still wants a block
+                _lib.check(lib.ss_specaug_packed_device(xin.data_ptr(), n, table.data_ptr(), total_rows, cols, block.data_ptr(), base, nt, tw, ratio, nf, fw,
+                                                        mask_value, xout.data_ptr(), _ptr(spans) or None, _stream_ptr()))
+                for t in (xin, table):
+                    t.record_stream(torch.cuda.current_stream())
+        return out, spans
+    words = _rng_words(rng, what)
+    spans = np.zeros((n, nt + nf, 2), np.int32)
+    if n:
+        xin, xout = (x, out) if total_rows else (np.zeros((1, cols), np.float32),) * 2
+        _lib.check(lib.ss_specaug_packed(xin.ctypes.data, n, table.ctypes.data, total_rows, cols, words.ctypes.data, base, nt, tw, ratio, nf, fw, mask_value,
+                                         xout.ctypes.data, spans.ctypes.data if spans.size else None))
+        if isinstance(rng, SpecAugment):
+            rng.epoch = int(words[1])
+        elif isinstance(rng, np.ndarray) and rng is not words:
+            rng[1] = words[1]
+    return out, spans
+
+
+class SpecAugment:
+    """The generator state of ``spec_augment_packed``: owns the 16-byte device block ``{seed, epoch}`` that the kernels read and
+    advance.  ``augment = SpecAugment(seed)``; ``out, spans = augment(rows, row_offsets, time_masks=2, ...)`` -- every call, and
+    every replay of a graph that captured one, advances ``epoch`` by one on the device.  ``seed`` and ``epoch`` read the block back
+    (a synchronisation: for tests and checkpoints); assigning ``epoch`` restores a checkpoint."""
+
+    def __init__(self, seed, epoch=0, device=None):
+        import torch
+
+        seed, epoch = int(seed), int(epoch)
+        if not (0 <= seed < 1 << 64 and 0 <= epoch < 1 << 64):
+            raise ValueError("SpecAugment: seed and epoch must lie in 0 .. 2^64 - 1")
+        self._block = torch.from_numpy(np.array([seed, epoch], np.uint64).view(np.int64)).to(device if device is not None else "cuda")
+
+    def _words(self):
+        return self._block.cpu().numpy().view(np.uint64)
+
+    @property
+    def seed(self):
+        return int(self._words()[0])
+
+    @property
+    def epoch(self):
+        return int(self._words()[1])
+
+    @epoch.setter
+    def epoch(self, value):
+        import torch
+
+        value = int(value)
+        if not 0 <= value < 1 << 64:
+            raise ValueError("SpecAugment: epoch must lie in 0 .. 2^64 - 1")
+        self._block[1:].copy_(torch.from_numpy(np.array([value], np.uint64).view(np.int64)))
+
+    def __call__(self, rows, row_offsets, **kwargs):
+        return spec_augment_packed(rows, row_offsets, self, **kwargs)
 
 
 # ---- polyphase sinc resampling ahead of the feature calls (ss_resample* in include/speechsauce_amd.h) -------------

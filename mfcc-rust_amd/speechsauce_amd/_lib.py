@@ -277,6 +277,17 @@ PROTOTYPES = {
                                        C.c_void_p, C.c_void_p]),
     "ss_pad_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                 C.c_void_p]),
+    "ss_specaug_spans": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float,
+                                   C.c_size_t, C.c_size_t, C.c_void_p]),
+    "ss_specaug_plan_packed_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                C.c_float, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ss_mask_spans_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, _fp,
+                                              C.c_void_p]),
+    "ss_mask_spans_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, _fp]),
+    "ss_specaug_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                           C.c_float, C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_void_p, C.c_void_p]),
+    "ss_specaug_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float,
+                                    C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_void_p]),
     "ss_vad_energy_stream_state_len": (C.c_int, [C.c_size_t, _P(C.c_size_t)]),
     "ss_vad_energy_stream_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
                                                      C.c_float, C.c_float, C.c_size_t, C.c_float, _fp, C.c_void_p, C.c_void_p]),
