@@ -1517,6 +1517,77 @@ int ss_kstream_fbank_packed_i16(const ss_kaldi_config *cfg, const int16_t *x, si
 int ss_kstream_mfcc_packed_i16(const ss_kaldi_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
                                const int32_t *slots, size_t pool_streams, float scale, float *pool, float *out);
 
+/* ---- Whisper log-mel front end (whisper.audio.log_mel_spectrogram / transformers.WhisperFeatureExtractor) ------------------
+ * The model input of Whisper and of the speech encoders built on it.  The reference crate has no such stage; this comment is the
+ * definition and tests/whisper_model.py restates it in numpy f64.  For one clip x of len samples and a frame count n_frames >= 2:
+ *     N   = n_frames * 160
+ *     a   = x[:N] followed by zeros up to N                              (pad_or_trim)
+ *     p   = np.pad(a, 200, mode="reflect")
+ *     w   = 0.5 - 0.5 cos(2 pi n / 400), n = 0 .. 399                    (periodic Hann, formed in f64, rounded once)
+ *     P[t, k] = |rfft(p[160 t : 160 t + 400] * w)[k]|^2, t = 0 .. n_frames - 1, k = 0 .. 200   (the frame at t = n_frames is never formed)
+ *     mel = B @ P^T,  B = librosa.filters.mel(sr=16000, n_fft=400, n_mels=M, htk=False, norm="slaney"), [M x 201], f64 rounded once
+ *     l   = log10(max(mel, 1e-10));  l = max(l, max(l over the whole [M x n_frames] block) - 8);  out = (l + 4) / 4
+ *   out is [M x n_frames] per clip, mels outermost.  An empty or all-zero clip gives -1.5 everywhere.
+ *   Arithmetic (f32): one 200-point complex transform of z[n] = p[2n] w[2n] + i p[2n+1] w[2n+1] per frame and the real-FFT untangle;
+ *   mel[m] is the sum over the filter's non-zero taps in ascending k, each step one fmaf; a sum <= 1e-10 gives l = -10 exactly; the
+ *   last step is out = conv(fmaf(max(l, mx - 8), 0.25f, 1.0f)) -- ONE fmaf -- with conv of ss_pad_packed (SS_PAD_F32 / _F16 / _BF16,
+ *   bit for bit its rounding rules).  The dense and the packed call run the same kernel code: they cannot round differently.
+ *   A SILENT frame is one whose every sample index, after reflection, lies at or beyond min(len, N): t >= 2 with 160 t - 200 >=
+ *   min(len, N), or any t of an empty clip.  Its l is the constant -10; no sample of it is loaded and no transform is run.
+ * Served: sample_rate 16000, n_fft 400, hop_length 160 exactly, 1 <= n_mels <= 128.  Any other valid combination (n_fft even,
+ *   1 <= hop_length <= n_fft, sample_rate >= 1, n_mels >= 1) is SS_ERR_UNSUPPORTED; anything else SS_ERR_BAD_CONFIG; a struct_size
+ *   other than sizeof(ss_whisper_params) SS_ERR_ARG.
+ * The handle is opaque and immutable: the tables go to the device it was created on at creation, with a pinned device error word
+ *   of its own (ss_whisper_config_device_status has ss_config_device_status's contract) and a block of per-clip maximum keys for
+ *   SS_WHISPER_MAX_CLIPS clips.  Calls on ONE handle must be ordered on one stream (they share the keys block); use one handle per
+ *   stream otherwise.
+ * Dense call: every row of d_x ([batch] rows of n_samples, row stride ld >= n_samples) is a clip, padded or trimmed to n_frames * 160.
+ * Packed call: clip b is d_x[so[b] .. so[b + 1]) (int64 table of n_clips + 1 entries on the device); every clip is padded or trimmed
+ *   to the same n_frames, so out is the rectangular [n_clips x M x n_frames] model input.  d_lengths (int32 [n_clips], may be NULL)
+ *   gets min(len / 160, n_frames), or -1 for a bad table entry (so[b] < 0 or so[b + 1] < so[b]): that clip's block is all -1.5, the
+ *   handle's error word is raised and reported once (SS_ERR_DEVICE, by ss_whisper_config_device_status or the next call on the
+ *   handle).  The grids depend on n_clips, n_frames and M only and nothing is read back: the call replays as a captured graph over
+ *   changed device tables.  Every element of out and of d_lengths is written by every call.
+ * Three launches on `stream`: ss_whisper_keys_kernel (keys, lengths, table check), ss_whisper_c200 (ss_last_kernel_name(); the
+ *   log10 block in f32) and ss_whisper_floor_kernel<f32|f16|bf16> (floor, scale, conversion, 16-byte stores).  For SS_PAD_F32 the
+ *   log10 block lives in d_out itself and d_work is NULL (it is not read); for the 16-bit types the caller passes
+ *   ss_whisper_work_bytes of f32 scratch, 16-byte aligned.  Nothing is allocated inside a call.
+ * Errors: n_frames < 2, n_frames * 160 >= 2^31, more than SS_WHISPER_MAX_CLIPS clips, null buffers, d_x not 4-byte or d_out /
+ *   d_work not 16-byte aligned, ld < n_samples: SS_ERR_ARG.  batch or n_clips of zero: SS_OK, nothing launched.
+ * Not served: streaming and pool forms (a stream has no clip maximum), 16-bit PCM input, dither, other sizes. */
+#define SS_WHISPER_MAX_CLIPS 1048576
+typedef struct ss_whisper_params {
+    uint32_t struct_size; /* sizeof(ss_whisper_params) */
+    uint32_t sample_rate; /* 16000 */
+    uint32_t n_fft;       /* 400 */
+    uint32_t hop_length;  /* 160 */
+    uint32_t n_mels;      /* 80 (Whisper up to large-v2) or 128 (large-v3) */
+} ss_whisper_params;
+typedef struct ss_whisper_config ss_whisper_config; /* opaque */
+
+/* host only, no device */
+int ss_whisper_params_default(ss_whisper_params *p, uint32_t n_mels);
+int ss_whisper_params_validate(const ss_whisper_params *p);
+int ss_whisper_num_frames(size_t n_samples, size_t *n_frames);                     /* n_samples / 160 */
+int ss_whisper_first_silent_frame(size_t len, size_t n_frames, size_t *t_silent);  /* n_frames if no frame is silent */
+int ss_whisper_window(const ss_whisper_params *p, float *w);                       /* [400] */
+int ss_whisper_mel_bank(const ss_whisper_params *p, float *bank);                  /* [n_mels x 201] */
+int ss_whisper_work_bytes(const ss_whisper_params *p, size_t batch, size_t n_frames, int dtype, size_t *bytes); /* 0 for SS_PAD_F32 */
+
+int ss_whisper_config_create(const ss_whisper_params *p, ss_whisper_config **out);
+void ss_whisper_config_destroy(ss_whisper_config *cfg);
+int ss_whisper_config_params(const ss_whisper_config *cfg, ss_whisper_params *out);
+int ss_whisper_config_device_status(const ss_whisper_config *cfg);
+
+int ss_whisper_log_mel_device(const ss_whisper_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld, size_t n_frames,
+                              int dtype, void *d_work, void *d_out, void *stream);
+int ss_whisper_log_mel(const ss_whisper_config *cfg, const float *x, size_t batch, size_t n_samples, size_t ld, size_t n_frames, int dtype,
+                       void *out);
+int ss_whisper_log_mel_packed_device(const ss_whisper_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                     size_t n_frames, int dtype, void *d_work, void *d_out, int32_t *d_lengths, void *stream);
+int ss_whisper_log_mel_packed(const ss_whisper_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, size_t n_frames,
+                              int dtype, void *out, int32_t *lengths);
+
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`
  * computes clips [lo, hi) of ss_shard_bounds on its own device with the *_device entry points.  The north-star's "RCCL

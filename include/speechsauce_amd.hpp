@@ -949,6 +949,79 @@ private:
     std::shared_ptr<ss_kaldi_config> h_;
 };
 
+// The Whisper log-mel block (ss_whisper_*; not in the reference crate): [n_mels x n_frames] per clip, every clip padded or trimmed to
+// n_frames * 160 samples.  The handle is shared by copies; calls on one handle must be ordered on one stream.
+inline ss_whisper_params whisper_params(uint32_t n_mels)  // 16000 / 400 / 160
+{
+    ss_whisper_params p;
+    check(ss_whisper_params_default(&p, n_mels));
+    return p;
+}
+class WhisperFrontEnd {
+public:
+    explicit WhisperFrontEnd(uint32_t n_mels = 80) : p_(whisper_params(n_mels))
+    {
+        ss_whisper_config *raw = nullptr;
+        check(ss_whisper_config_create(&p_, &raw));
+        h_ = std::shared_ptr<ss_whisper_config>(raw, ss_whisper_config_destroy);
+    }
+    const ss_whisper_params &params() const { return p_; }
+    const ss_whisper_config *handle() const { return h_.get(); }
+    static size_t num_frames(size_t n_samples)  // n_samples / 160
+    {
+        size_t t = 0;
+        check(ss_whisper_num_frames(n_samples, &t));
+        return t;
+    }
+    // bytes of f32 scratch the device calls take for a 16-bit dtype (0 for SS_PAD_F32)
+    size_t work_bytes(size_t batch, size_t n_frames, int dtype) const
+    {
+        size_t n = 0;
+        check(ss_whisper_work_bytes(&p_, batch, n_frames, dtype, &n));
+        return n;
+    }
+    // throws Error(SS_ERR_DEVICE) once if a packed launch has met a bad table entry since the last look
+    void device_status() const { check(ss_whisper_config_device_status(h_.get())); }
+    // one clip -> [n_mels x n_frames], f32
+    std::vector<float> log_mel(const std::vector<float> &x, size_t n_frames) const
+    {
+        std::vector<float> out(p_.n_mels * n_frames);
+        const float keep[4] = {0, 0, 0, 0};  // an empty clip reads nothing: any address will do
+        check(ss_whisper_log_mel(h_.get(), x.empty() ? keep : x.data(), 1, x.size(), x.size(), n_frames, SS_PAD_F32, out.data()));
+        return out;
+    }
+    // clips packed end to end, clip b = x[sample_offsets[b] .. sample_offsets[b+1]) -> [n_clips x n_mels x n_frames]; lengths (may be
+    // null) receives min(len_b / 160, n_frames)
+    std::vector<float> log_mel_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, size_t n_frames,
+                                      std::vector<int32_t> *lengths = nullptr) const
+    {
+        if (sample_offsets.empty() || sample_offsets.back() < 0 || static_cast<size_t>(sample_offsets.back()) > x.size())
+            throw Error(SS_ERR_ARG, "whisper packed call: shape mismatch");
+        const size_t n = sample_offsets.size() - 1;
+        std::vector<float> out(n * p_.n_mels * n_frames);
+        if (lengths) lengths->assign(n, 0);
+        const float keep[4] = {0, 0, 0, 0};
+        check(ss_whisper_log_mel_packed(h_.get(), x.empty() ? keep : x.data(), n, sample_offsets.data(), n_frames, SS_PAD_F32, out.data(),
+                                        lengths ? lengths->data() : nullptr));
+        return out;
+    }
+    // the device calls on `stream`: device pointers, nothing is copied or allocated
+    void log_mel_device(const float *d_x, size_t batch, size_t n_samples, size_t ld, size_t n_frames, int dtype, void *d_work, void *d_out,
+                        void *stream) const
+    {
+        check(ss_whisper_log_mel_device(h_.get(), d_x, batch, n_samples, ld, n_frames, dtype, d_work, d_out, stream));
+    }
+    void log_mel_packed_device(const float *d_x, size_t n_clips, const int64_t *d_sample_offsets, size_t n_frames, int dtype, void *d_work, void *d_out,
+                               int32_t *d_lengths, void *stream) const
+    {
+        check(ss_whisper_log_mel_packed_device(h_.get(), d_x, n_clips, d_sample_offsets, n_frames, dtype, d_work, d_out, d_lengths, stream));
+    }
+
+private:
+    ss_whisper_params p_;
+    std::shared_ptr<ss_whisper_config> h_;
+};
+
 // processing.rs:222-254
 inline std::vector<float> derivative_extraction(const std::vector<float> &feat, size_t rows, size_t cols, size_t delta_windows)
 {

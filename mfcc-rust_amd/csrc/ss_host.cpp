@@ -5,6 +5,7 @@
 // Build with -ffp-contract=off: the mel bank indices sit on integer boundaries after an f32
 // ln -> exp round trip, so the f32 operation order below is part of the contract.
 #include "ss_internal.h"
+#include "ss_whisper.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1082,6 +1083,72 @@ void kaldi_dct(const ss_kaldi_params &p, float *dct)
     }
 }
 
+// ---- Whisper log-mel front end (ss_whisper_* in include/speechsauce_amd.h; kernel: ss_whisper400.hip) ----
+int whisper_validate(const ss_whisper_params &p)
+{
+    if (p.struct_size != sizeof(ss_whisper_params)) return fail(SS_ERR_ARG, "ss_whisper_params.struct_size mismatch (ABI)");
+    if (p.sample_rate == 0) return fail(SS_ERR_BAD_CONFIG, "sample_rate must be > 0");
+    if (p.n_fft < 2 || p.n_fft % 2) return fail(SS_ERR_BAD_CONFIG, "n_fft must be even and at least 2");
+    if (p.hop_length == 0 || p.hop_length > p.n_fft) return fail(SS_ERR_BAD_CONFIG, "hop_length must lie in [1, n_fft]");
+    if (p.n_mels == 0) return fail(SS_ERR_BAD_CONFIG, "n_mels must be at least 1");
+    if (p.sample_rate != whisper::kSampleRate || p.n_fft != whisper::kNfft || p.hop_length != whisper::kHop)
+        return fail(SS_ERR_UNSUPPORTED, "only sample_rate 16000, n_fft 400, hop_length 160 is served");
+    if (p.n_mels > whisper::kMaxMels) return fail(SS_ERR_UNSUPPORTED, "more than 128 mels");
+    return SS_OK;
+}
+
+void whisper_window(float *w) { hann_window(whisper::kNfft, w); }
+
+// librosa.filters.mel(sr = 16000, n_fft = 400, n_mels = M, htk = False, norm = "slaney"): the builder behind SS_MEL_SLANEY
+void whisper_mel_bank(const ss_whisper_params &p, std::vector<float> &bank)
+{
+    ss_params q{};
+    q.sample_rate = p.sample_rate;
+    q.fft_points = p.n_fft;
+    q.num_filters = p.n_mels;
+    q.low_frequency = 0.0f;
+    q.high_frequency = 0.5f * static_cast<float>(p.sample_rate);
+    q.mel_scale = SS_MEL_SLANEY;
+    q.mel_norm = SS_MEL_NORM_SLANEY;
+    std::vector<int32_t> idx;
+    (void)build_filterbank(q, bank, idx);
+}
+
+void build_whisper_tables(const ss_whisper_params &p, std::vector<float> &tab)
+{
+    using namespace whisper;
+    const double PI = 3.14159265358979323846;
+    tab.assign(layout::kFloats, 0.0f);
+    float w[kNfft];
+    whisper_window(w);
+    for (uint32_t m = 0; m < kPointsPerLane; ++m)
+        for (uint32_t j = 0; j < kLanesPerFrame; ++j) {
+            const uint32_t e = 2 * (m * 8 + j);
+            tab[layout::kWin + e] = w[16 * m + 2 * j];
+            tab[layout::kWin + e + 1] = w[16 * m + 2 * j + 1];
+            const double a2 = -2.0 * PI * static_cast<double>(j * m) / 200.0;  // m plays k1 here
+            tab[layout::kTw2 + e] = static_cast<float>(std::cos(a2));
+            tab[layout::kTw2 + e + 1] = static_cast<float>(std::sin(a2));
+            const double an = -2.0 * PI * static_cast<double>(25 * bitrev3(j) + m) / 400.0;
+            tab[layout::kTwn + e] = static_cast<float>(std::cos(an));
+            tab[layout::kTwn + e + 1] = static_cast<float>(std::sin(an));
+        }
+    std::vector<float> bank;
+    whisper_mel_bank(p, bank);
+    SparseBank sb;
+    sparsify(bank, p.n_mels, kBins, sb);
+    int32_t *start = reinterpret_cast<int32_t *>(tab.data() + layout::kStart), *len = reinterpret_cast<int32_t *>(tab.data() + layout::kLen),
+            *off = reinterpret_cast<int32_t *>(tab.data() + layout::kOff);
+    for (uint32_t m = 0; m < p.n_mels; ++m) {
+        start[m] = sb.start[m];
+        len[m] = sb.len[m];
+        off[m] = sb.off[m];
+    }
+    // a bin lies under at most two triangles, so the taps fit; a run of interior zeros inside a filter's span cannot occur
+    const size_t n = std::min<size_t>(sb.w.size(), layout::kMelWMax);
+    std::copy(sb.w.begin(), sb.w.begin() + n, tab.begin() + layout::kMelW);
+}
+
 // The kernel's block through the wide-bank builder: the dense bank widened to the 257 bins of a P row (the Nyquist column stays
 // zero), sparsified and dealt to the five slots per lane; the liftered DCT as the cosine rows; the window always appended.
 void build_kaldi512(const ss_kaldi_params &p, KaldiTables &f)
@@ -1479,6 +1546,72 @@ int ss_kaldi_dct(const ss_kaldi_params *p, float *dct)
     if (!p || !dct) return ss::fail(SS_ERR_ARG, "null argument");
     if (int rc = ss::kaldi_validate(*p, nullptr)) return rc;
     ss::kaldi_dct(*p, dct);
+    return SS_OK;
+}
+
+// ---- Whisper log-mel front end: host-only calls ----
+
+int ss_whisper_params_default(ss_whisper_params *p, uint32_t n_mels)
+{
+    if (!p) return ss::fail(SS_ERR_ARG, "null params");
+    p->struct_size = static_cast<uint32_t>(sizeof(ss_whisper_params));
+    p->sample_rate = ss::whisper::kSampleRate;
+    p->n_fft = ss::whisper::kNfft;
+    p->hop_length = ss::whisper::kHop;
+    p->n_mels = n_mels;
+    return SS_OK;
+}
+
+int ss_whisper_params_validate(const ss_whisper_params *p)
+{
+    if (!p) return ss::fail(SS_ERR_ARG, "null params");
+    return ss::whisper_validate(*p);
+}
+
+int ss_whisper_num_frames(size_t n_samples, size_t *n_frames)
+{
+    if (!n_frames) return ss::fail(SS_ERR_ARG, "null argument");
+    *n_frames = n_samples / ss::whisper::kHop;
+    return SS_OK;
+}
+
+int ss_whisper_first_silent_frame(size_t len, size_t n_frames, size_t *t_silent)
+{
+    if (!t_silent) return ss::fail(SS_ERR_ARG, "null argument");
+    if (n_frames < 2 || n_frames > 0x7fffffffu / ss::whisper::kHop) return ss::fail(SS_ERR_ARG, "n_frames must be at least 2 and n_frames * 160 below 2^31");
+    const size_t N = n_frames * ss::whisper::kHop;
+    *t_silent = ss::whisper::first_silent(static_cast<uint32_t>(len < N ? len : N), static_cast<uint32_t>(n_frames));
+    return SS_OK;
+}
+
+int ss_whisper_window(const ss_whisper_params *p, float *w)
+{
+    if (!p || !w) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::whisper_validate(*p)) return rc;
+    ss::whisper_window(w);
+    return SS_OK;
+}
+
+int ss_whisper_mel_bank(const ss_whisper_params *p, float *bank)
+{
+    if (!p || !bank) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::whisper_validate(*p)) return rc;
+    std::vector<float> b;
+    ss::whisper_mel_bank(*p, b);
+    std::copy(b.begin(), b.end(), bank);
+    return SS_OK;
+}
+
+int ss_whisper_work_bytes(const ss_whisper_params *p, size_t batch, size_t n_frames, int dtype, size_t *bytes)
+{
+    if (!p || !bytes) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::whisper_validate(*p)) return rc;
+    if (dtype != SS_PAD_F32 && dtype != SS_PAD_F16 && dtype != SS_PAD_BF16) return ss::fail(SS_ERR_ARG, "dtype must be SS_PAD_F32, SS_PAD_F16 or SS_PAD_BF16");
+    size_t n = 0;
+    if (__builtin_mul_overflow(batch, static_cast<size_t>(p->n_mels), &n) || __builtin_mul_overflow(n, n_frames, &n) ||
+        __builtin_mul_overflow(n, sizeof(float), &n))
+        return ss::fail(SS_ERR_ARG, "batch * n_mels * n_frames overflows");
+    *bytes = dtype == SS_PAD_F32 ? 0 : n;
     return SS_OK;
 }
 

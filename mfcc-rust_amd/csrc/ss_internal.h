@@ -274,4 +274,11 @@ struct KaldiTables {
 };
 void build_kaldi512(const ss_kaldi_params &p, KaldiTables &f);
 
+// ---- Whisper log-mel front end (ss_whisper_* in include/speechsauce_amd.h; kernel: ss_whisper400.hip; shared sizes: ss_whisper.h) ----
+// rc: SS_OK, SS_ERR_ARG (struct_size), SS_ERR_BAD_CONFIG, SS_ERR_UNSUPPORTED
+int whisper_validate(const ss_whisper_params &p);
+void whisper_window(float *w);                                                  // [400] periodic Hann, f64 rounded once
+void whisper_mel_bank(const ss_whisper_params &p, std::vector<float> &bank);   // [n_mels x 201] dense (p validated by the caller)
+void build_whisper_tables(const ss_whisper_params &p, std::vector<float> &tab); // whisper::layout
+
 }  // namespace ss

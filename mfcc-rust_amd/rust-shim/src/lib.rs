@@ -269,6 +269,20 @@ extern "C" {
                                    pool_streams: usize, scale: f32, pool: *mut f32, out: *mut f32, log_energy: *mut f32) -> c_int;
     fn ss_kstream_mfcc_packed_i16(cfg: *const c_void, x: *const i16, n_active: usize, sample_offsets: *const i64, slots: *const i32,
                                   pool_streams: usize, scale: f32, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_whisper_params_default(p: *mut SsWhisperParams, n_mels: u32) -> c_int;
+    fn ss_whisper_num_frames(n_samples: usize, n_frames: *mut usize) -> c_int;
+    fn ss_whisper_work_bytes(p: *const SsWhisperParams, batch: usize, n_frames: usize, dtype: c_int, bytes: *mut usize) -> c_int;
+    fn ss_whisper_config_create(p: *const SsWhisperParams, out: *mut *mut c_void) -> c_int;
+    fn ss_whisper_config_destroy(cfg: *mut c_void);
+    fn ss_whisper_config_device_status(cfg: *const c_void) -> c_int;
+    fn ss_whisper_log_mel_device(cfg: *const c_void, d_x: *const f32, batch: usize, n_samples: usize, ld: usize, n_frames: usize, dtype: c_int,
+                                 d_work: *mut c_void, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn ss_whisper_log_mel(cfg: *const c_void, x: *const f32, batch: usize, n_samples: usize, ld: usize, n_frames: usize, dtype: c_int,
+                          out: *mut c_void) -> c_int;
+    fn ss_whisper_log_mel_packed_device(cfg: *const c_void, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, n_frames: usize,
+                                        dtype: c_int, d_work: *mut c_void, d_out: *mut c_void, d_lengths: *mut i32, stream: *mut c_void) -> c_int;
+    fn ss_whisper_log_mel_packed(cfg: *const c_void, x: *const f32, n_clips: usize, sample_offsets: *const i64, n_frames: usize, dtype: c_int,
+                                 out: *mut c_void, lengths: *mut i32) -> c_int;
     fn ss_derivative_extraction(feat: *const f32, rows: usize, cols: usize, delta_windows: usize, out: *mut f32) -> c_int;
     fn ss_extract_derivative_feature(feat: *const f32, rows: usize, cols: usize, cube: *mut f32) -> c_int;
     fn ss_shard_bounds(n_items: usize, world: c_int, rank: c_int, lo: *mut usize, hi: *mut usize) -> c_int;
@@ -1959,6 +1973,117 @@ impl Resampler {
 }
 
 /// speechsauce::config (config.rs)
+/// `ss_whisper_params`: the Whisper log-mel front end's parameters (field order is ABI; see `ss_whisper_*` in the C header).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SsWhisperParams {
+    pub struct_size: u32,
+    pub sample_rate: u32,
+    pub n_fft: u32,
+    pub hop_length: u32,
+    pub n_mels: u32,
+}
+
+impl SsWhisperParams {
+    /// 16000 / 400 / 160 with `n_mels` mels (80, or 128 for large-v3).
+    pub fn new(n_mels: u32) -> SsWhisperParams {
+        let mut p: SsWhisperParams = unsafe { std::mem::zeroed() };
+        unsafe { ss_whisper_params_default(&mut p, n_mels) };
+        p
+    }
+}
+
+/// Element type of the output block (`SS_PAD_F32` / `SS_PAD_F16` / `SS_PAD_BF16`).
+pub const SS_PAD_F32: c_int = 0;
+pub const SS_PAD_F16: c_int = 1;
+pub const SS_PAD_BF16: c_int = 2;
+
+/// The Whisper log-mel block (`whisper.audio.log_mel_spectrogram`): `[n_mels x n_frames]` per clip, every clip padded or trimmed to
+/// `n_frames * 160` samples.  Not in the reference crate.  Owns an `ss_whisper_config`; calls on one front end must be ordered on one
+/// stream.
+pub struct WhisperFrontEnd {
+    raw: *mut c_void,
+    params: SsWhisperParams,
+}
+
+unsafe impl Send for WhisperFrontEnd {}
+
+impl Drop for WhisperFrontEnd {
+    fn drop(&mut self) {
+        unsafe { ss_whisper_config_destroy(self.raw) }
+    }
+}
+
+impl WhisperFrontEnd {
+    pub fn new(n_mels: u32) -> Result<WhisperFrontEnd, Error> {
+        let params = SsWhisperParams::new(n_mels);
+        let mut raw: *mut c_void = std::ptr::null_mut();
+        check(unsafe { ss_whisper_config_create(&params, &mut raw) })?;
+        Ok(WhisperFrontEnd { raw, params })
+    }
+
+    pub fn n_mels(&self) -> usize {
+        self.params.n_mels as usize
+    }
+
+    /// `n_samples / 160`: the frames Whisper keeps of a clip.
+    pub fn num_frames(n_samples: usize) -> Result<usize, Error> {
+        let mut t = 0usize;
+        check(unsafe { ss_whisper_num_frames(n_samples, &mut t) })?;
+        Ok(t)
+    }
+
+    /// Bytes of f32 scratch the device calls take for a 16-bit `dtype` (0 for `SS_PAD_F32`).
+    pub fn work_bytes(&self, batch: usize, n_frames: usize, dtype: c_int) -> Result<usize, Error> {
+        let mut n = 0usize;
+        check(unsafe { ss_whisper_work_bytes(&self.params, batch, n_frames, dtype, &mut n) })?;
+        Ok(n)
+    }
+
+    /// `SS_ERR_DEVICE` once if a packed launch has met a bad table entry since the last look.
+    pub fn device_status(&self) -> Result<(), Error> {
+        check(unsafe { ss_whisper_config_device_status(self.raw) })
+    }
+
+    /// One clip -> `[n_mels x n_frames]`, f32.
+    pub fn log_mel(&self, x: &[f32], n_frames: usize) -> Result<Array2<f32>, Error> {
+        let mut out = Array2::<f32>::zeros((self.n_mels(), n_frames));
+        let keep = [0f32; 4]; // an empty clip reads nothing: any address will do
+        let ptr = if x.is_empty() { keep.as_ptr() } else { x.as_ptr() };
+        check(unsafe { ss_whisper_log_mel(self.raw, ptr, 1, x.len(), x.len(), n_frames, SS_PAD_F32, out.as_mut_ptr() as *mut c_void) })?;
+        Ok(out)
+    }
+
+    /// Clips packed end to end -> (`[n_clips * n_mels x n_frames]`, block b = rows `b * n_mels ..`; the `[n_clips]` lengths
+    /// `min(len / 160, n_frames)`).
+    pub fn log_mel_packed(&self, x: &[f32], sample_offsets: &[i64], n_frames: usize) -> Result<(Array2<f32>, Vec<i32>), Error> {
+        if sample_offsets.is_empty() || sample_offsets[sample_offsets.len() - 1] as usize > x.len() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets is empty or ends past the block".to_string() });
+        }
+        let n = sample_offsets.len() - 1;
+        let mut out = Array2::<f32>::zeros((n * self.n_mels(), n_frames));
+        let mut lens = vec![0i32; n];
+        let keep = [0f32; 4];
+        let ptr = if x.is_empty() { keep.as_ptr() } else { x.as_ptr() };
+        check(unsafe {
+            ss_whisper_log_mel_packed(self.raw, ptr, n, sample_offsets.as_ptr(), n_frames, SS_PAD_F32, out.as_mut_ptr() as *mut c_void, lens.as_mut_ptr())
+        })?;
+        Ok((out, lens))
+    }
+
+    /// The dense device call on `stream`: device pointers, nothing is copied or allocated (`ss_whisper_log_mel_device`).
+    pub unsafe fn log_mel_device(&self, d_x: *const f32, batch: usize, n_samples: usize, ld: usize, n_frames: usize, dtype: c_int, d_work: *mut c_void,
+                                 d_out: *mut c_void, stream: *mut c_void) -> Result<(), Error> {
+        check(ss_whisper_log_mel_device(self.raw, d_x, batch, n_samples, ld, n_frames, dtype, d_work, d_out, stream))
+    }
+
+    /// The packed device call on `stream` (`ss_whisper_log_mel_packed_device`): replays as a captured graph over changed tables.
+    pub unsafe fn log_mel_packed_device(&self, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, n_frames: usize, dtype: c_int,
+                                        d_work: *mut c_void, d_out: *mut c_void, d_lengths: *mut i32, stream: *mut c_void) -> Result<(), Error> {
+        check(ss_whisper_log_mel_packed_device(self.raw, d_x, n_clips, d_sample_offsets, n_frames, dtype, d_work, d_out, d_lengths, stream))
+    }
+}
+
 pub mod config {
     pub use super::{SpeechConfig, SpeechConfigBuilder};
 }

@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import SpeechSauceError, SsKaldiParams, SsParams, SsResampleInfo, make_params  # noqa: F401
+from ._lib import SpeechSauceError, SsKaldiParams, SsParams, SsResampleInfo, SsWhisperParams, make_params  # noqa: F401
 
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
@@ -35,6 +35,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "KaldiFbankStreamPool", "KaldiMfccStreamPool",
+           "whisper_log_mel", "whisper_log_mel_packed", "whisper_log_mel_list", "whisper_num_frames", "WhisperConfig",
            "SpeechConfig", "SpeechSauceError"]
 
 
@@ -3536,3 +3537,184 @@ def kaldi_fbank_list(signals, **kw):
 def kaldi_mfcc_list(signals, **kw):
     """``kaldi_fbank_list`` for ``kaldi_mfcc_packed``."""
     return _kaldi_list("kaldi_mfcc_list", signals, kaldi_mfcc_packed, kw)
+
+
+# ---- Whisper log-mel front end (ss_whisper_* in include/speechsauce_amd.h) ------------------------------------------
+
+class WhisperConfig:
+    """Owns an ``ss_whisper_config`` handle: the tables and the per-clip keys on the device that was current at creation, a device
+    error word for the packed calls, and the f32 scratch block that the 16-bit output types take (grown on demand, never inside a
+    captured region: call once eagerly with the largest shape before capturing)."""
+
+    def __init__(self, n_mels: int):
+        self.params = SsWhisperParams()
+        self._h = C.c_void_p()
+        self._owner = _lib.lib()
+        _lib.check(self._owner.ss_whisper_params_default(C.byref(self.params), int(n_mels)))
+        _lib.check(self._owner.ss_whisper_config_create(C.byref(self.params), C.byref(self._h)))
+        self._work = None
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                self._owner.ss_whisper_config_destroy(h)
+            except Exception:
+                pass
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    def work_bytes(self, batch: int, n_frames: int, code: int) -> int:
+        n = C.c_size_t()
+        _lib.check(_lib.lib().ss_whisper_work_bytes(C.byref(self.params), batch, n_frames, code, C.byref(n)))
+        return n.value
+
+    def work(self, batch: int, n_frames: int, code: int, device):
+        """the cached scratch block as a device pointer (None for float32)"""
+        need = self.work_bytes(batch, n_frames, code)
+        if need == 0:
+            return None
+        import torch
+
+        if self._work is None or self._work.numel() * 4 < need or self._work.device != device:
+            self._work = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=device)
+        return self._work.data_ptr()
+
+    def device_status(self) -> None:
+        """Raises SpeechSauceError (SS_ERR_DEVICE) if a packed launch on this handle has met a bad table entry since the last look.
+        Meaningful after the stream has been synchronised."""
+        _lib.check(_lib.lib().ss_whisper_config_device_status(self._h))
+
+
+@lru_cache(maxsize=8)
+def _get_whisper_config(n_mels: int, device: int = -1) -> WhisperConfig:
+    return WhisperConfig(n_mels)
+
+
+_lib._on_switch.append(_get_whisper_config.cache_clear)
+
+
+def whisper_num_frames(n_samples: int) -> int:
+    """``n_samples // 160``: the frames Whisper keeps of a clip (no device needed)."""
+    t = C.c_size_t()
+    _lib.check(_lib.lib().ss_whisper_num_frames(int(n_samples), C.byref(t)))
+    return t.value
+
+
+def _whisper_frames(n_frames, longest: int, what: str) -> int:
+    n = whisper_num_frames(longest) if n_frames is None else int(n_frames)
+    if n < 2:
+        raise ValueError(f"{what}: n_frames must be at least 2, got {n} (a clip of fewer than 320 samples needs an explicit n_frames)")
+    return n
+
+
+def _whisper_out(shape, name, device):
+    """(the output block, its address); numpy has no bfloat16: a host bfloat16 result is a uint16 array of the bit patterns"""
+    if device is not None:
+        import torch
+
+        out = torch.empty(shape, dtype=getattr(torch, name), device=device)
+        return out, out.data_ptr()
+    out = np.empty(shape, dtype={"float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}[name])
+    return out, out.ctypes.data
+
+
+def whisper_log_mel(x, n_mels=80, n_frames=None, dtype="float32"):
+    """The Whisper log-mel block (``whisper.audio.log_mel_spectrogram``, ``transformers.WhisperFeatureExtractor``) of one 16 kHz clip
+    [L] -> [n_mels, n_frames] or of every row of a batch [B, L] -> [B, n_mels, n_frames].  ``n_frames=None`` keeps ``L // 160``
+    frames; ``3000`` is the 30 s window (the clip is padded with zeros or trimmed).  ``dtype``: float32, float16 or bfloat16 (a host
+    bfloat16 result is a uint16 array of bit patterns)."""
+    what = "whisper_log_mel"
+    sig = _require_f32(x, (1, 2), what)
+    code, name = _pad_dtype(dtype, what)
+    one = len(sig.shape) == 1
+    batch, L = (1, int(sig.shape[0])) if one else (int(sig.shape[0]), int(sig.shape[1]))
+    T = _whisper_frames(n_frames, L, what)
+    cfg = _get_whisper_config(int(n_mels), _device_key(sig))
+    M = cfg.params.n_mels
+    lib = _lib.lib()
+    if _is_torch(sig):
+        import torch
+
+        v = sig.reshape(1, L) if one else sig
+        if L and v.stride(1) != 1:
+            v = v.contiguous()
+        ld = int(v.stride(0)) if batch > 1 and L else L
+        if ld < L:
+            v, ld = v.contiguous(), L
+        out, optr = _whisper_out((batch, M, T), name, v.device)
+        if batch:
+            with torch.cuda.device(v.device):
+                keep = v if L else torch.zeros(4, dtype=torch.float32, device=v.device)  # an empty clip reads nothing: any address will do
+                _lib.check(lib.ss_whisper_log_mel_device(cfg.handle, keep.data_ptr(), batch, L, ld, T, code, cfg.work(batch, T, code, v.device), optr,
+                                                         _stream_ptr()))
+                keep.record_stream(torch.cuda.current_stream())
+        return out[0] if one else out
+    v = np.ascontiguousarray(sig).reshape(batch, L)
+    if L == 0:
+        v = np.zeros((batch, 4), np.float32)
+    out, optr = _whisper_out((batch, M, T), name, None)
+    if batch:
+        _lib.check(lib.ss_whisper_log_mel(cfg.handle, v.ctypes.data, batch, L, v.shape[1], T, code, optr))
+    return out[0] if one else out
+
+
+def whisper_log_mel_packed(signal, lengths, n_mels=80, n_frames=None, dtype="float32"):
+    """Clips of different lengths end to end in ``signal`` [N] -> ``(out [n_clips, n_mels, n_frames], lengths int32 [n_clips])``: every
+    clip padded or trimmed to the same ``n_frames`` (None: the longest clip's ``len // 160``), ``lengths[b] = min(len_b // 160,
+    n_frames)`` the frames that come from the clip's own samples.  One call of three launches whatever the lengths."""
+    what = "whisper_log_mel_packed"
+    sig = _require_f32(signal, (1,), what)
+    code, name = _pad_dtype(dtype, what)
+    so = _sample_offsets(lengths, int(sig.shape[0]), what)
+    n = so.size - 1
+    T = _whisper_frames(n_frames, int(np.diff(so).max()) if n else 320, what)
+    cfg = _get_whisper_config(int(n_mels), _device_key(sig))
+    M = cfg.params.n_mels
+    lib = _lib.lib()
+    if _is_torch(sig):
+        import torch
+
+        x = sig.contiguous()
+        out, optr = _whisper_out((n, M, T), name, x.device)
+        lens = torch.empty((n,), dtype=torch.int32, device=x.device)
+        if n:
+            with torch.cuda.device(x.device):
+                dso = torch.from_numpy(so).to(x.device)
+                keep = x if x.numel() else torch.zeros(4, dtype=torch.float32, device=x.device)
+                _lib.check(lib.ss_whisper_log_mel_packed_device(cfg.handle, keep.data_ptr(), n, dso.data_ptr(), T, code, cfg.work(n, T, code, x.device), optr,
+                                                                lens.data_ptr(), _stream_ptr()))
+                for t in (keep, dso):
+                    t.record_stream(torch.cuda.current_stream())
+        return out, lens
+    x = np.ascontiguousarray(sig)
+    if x.size == 0:
+        x = np.zeros(4, np.float32)
+    out, optr = _whisper_out((n, M, T), name, None)
+    lens = np.empty((n,), dtype=np.int32)
+    if n:
+        _lib.check(lib.ss_whisper_log_mel_packed(cfg.handle, x.ctypes.data, n, so.ctypes.data, T, code, optr, lens.ctypes.data))
+    return out, lens
+
+
+def whisper_log_mel_list(signals, n_mels=80, n_frames=None, dtype="float32"):
+    """A list of 1-D float32 clips of any lengths -> ``(out [n_clips, n_mels, n_frames], lengths)``: the clips are packed once and
+    served by one ``whisper_log_mel_packed`` call."""
+    what = "whisper_log_mel_list"
+    sigs = [_require_f32(x, (1,), what) for x in signals]
+    if not sigs:
+        raise ValueError(f"{what}: no clips")
+    on_device = [_is_torch(x) for x in sigs]
+    if any(on_device) and not all(on_device):
+        raise ValueError(f"{what}: the clips of one call must all be device tensors or all host arrays")
+    if all(on_device):
+        import torch
+
+        if any(x.device != sigs[0].device for x in sigs):
+            raise ValueError(f"{what}: the clips of one call must live on one device")
+        packed = torch.cat(sigs)
+    else:
+        packed = np.concatenate(sigs)
+    return whisper_log_mel_packed(packed, [int(x.shape[0]) for x in sigs], n_mels=n_mels, n_frames=n_frames, dtype=dtype)

@@ -89,6 +89,12 @@ class SsKaldiParams(C.Structure):
     ]
 
 
+class SsWhisperParams(C.Structure):
+    """ss_whisper_params (include/speechsauce_amd.h); field order is ABI."""
+
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "sample_rate", "n_fft", "hop_length", "n_mels")]
+
+
 class SpeechSauceError(RuntimeError):
     """Raised where the reference would panic (or where HIP fails)."""
 
@@ -105,6 +111,7 @@ _P = C.POINTER
 _cfg = C.c_void_p
 _rs = C.c_void_p  # ss_resampler *
 _kc = C.c_void_p  # ss_kaldi_config *
+_wc = C.c_void_p  # ss_whisper_config *
 _fp = C.c_void_p  # float* passed as an address (numpy .ctypes.data or a device pointer)
 PROTOTYPES = {
     "ss_params_default": (C.c_int, [_P(SsParams), C.c_uint32]),
@@ -340,6 +347,21 @@ PROTOTYPES = {
     "ss_kaldi_fbank_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, _fp, _fp]),
     "ss_kaldi_mfcc_packed_device": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
     "ss_kaldi_mfcc_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, _fp]),
+    "ss_whisper_params_default": (C.c_int, [_P(SsWhisperParams), C.c_uint32]),
+    "ss_whisper_params_validate": (C.c_int, [_P(SsWhisperParams)]),
+    "ss_whisper_num_frames": (C.c_int, [C.c_size_t, _P(C.c_size_t)]),
+    "ss_whisper_first_silent_frame": (C.c_int, [C.c_size_t, C.c_size_t, _P(C.c_size_t)]),
+    "ss_whisper_window": (C.c_int, [_P(SsWhisperParams), _fp]),
+    "ss_whisper_mel_bank": (C.c_int, [_P(SsWhisperParams), _fp]),
+    "ss_whisper_work_bytes": (C.c_int, [_P(SsWhisperParams), C.c_size_t, C.c_size_t, C.c_int, _P(C.c_size_t)]),
+    "ss_whisper_config_create": (C.c_int, [_P(SsWhisperParams), _P(_wc)]),
+    "ss_whisper_config_destroy": (None, [_wc]),
+    "ss_whisper_config_params": (C.c_int, [_wc, _P(SsWhisperParams)]),
+    "ss_whisper_config_device_status": (C.c_int, [_wc]),
+    "ss_whisper_log_mel_device": (C.c_int, [_wc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ss_whisper_log_mel": (C.c_int, [_wc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]),
+    "ss_whisper_log_mel_packed_device": (C.c_int, [_wc, _fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ss_whisper_log_mel_packed": (C.c_int, [_wc, _fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "ss_kstream_state_len": (C.c_int, [_P(SsKaldiParams), _P(C.c_size_t), _P(C.c_size_t)]),
     "ss_kstream_row_offsets": (C.c_int, [_P(SsKaldiParams), C.c_size_t, C.c_void_p, C.c_void_p]),
     "ss_kstream_fbank_packed_device": (
