@@ -1262,7 +1262,8 @@ int ss_resampler_info(const ss_resampler *rs, ss_resample_info *info);
 /* Dense batch: x [batch x ld] (n_samples <= ld used per row) -> out [batch x ld_out], row b = the resampled row b, out_len(n_samples)
  * <= ld_out samples; the rest of an out row is left unwritten.  One launch (ss_resample_kernel<dense,f32>).  batch == 0 is SS_OK
  * without a device.  SS_ERR_ARG: null buffers, batch or n_samples or out_len >= 2^31, ld < n_samples, ld_out < out_len, out
- * overlapping x.  The _i16 forms take int16 samples and a scale behind the sample-layout arguments: sample = (float)pcm * scale,
+ * overlapping x.  The last row ends with its samples, not a whole stride behind its start: x is (batch - 1) * ld + n_samples
+ * floats, out (batch - 1) * ld_out + out_len, and those two ranges are what must not overlap.  The _i16 forms take int16 samples and a scale behind the sample-layout arguments: sample = (float)pcm * scale,
  * converted on load (no conversion launch; 2-byte alignment is enough, an odd address is SS_ERR_ARG), scale a power of two in
  * [2^-64, 2^64] else SS_ERR_ARG; every output is bit for bit that of the float call on x_f[k] = (float)pcm[k] * scale. */
 int ss_resample_device(const ss_resampler *rs, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out, size_t ld_out,

@@ -63,7 +63,8 @@ __global__ __launch_bounds__(256) void ss_add_deltas_packed_kernel(const float *
     __shared__ float tile[kTileRows * kColTile];
     const Segment seg = packed_segment(off, total_rows);
     if (seg.rows == 0) return;
-    const unsigned rows = seg.rows, L = tp.lag, ocols = (tp.order + 1) * cols;
+    const unsigned rows = seg.rows, L = tp.lag;
+    const size_t ocols = static_cast<size_t>(tp.order + 1) * cols;  // cols < 2^31, order 2: three times that does not fit 32 bits
     const unsigned n_tiles = (rows + kRowTile - 1) / kRowTile;
     const float *src = x + seg.row0 * cols;
     float *dst = out + seg.row0 * ocols;
@@ -129,6 +130,8 @@ __global__ __launch_bounds__(256) void ss_add_deltas_stream_kernel(const float *
                                                                   unsigned long long total_rows, unsigned pool_streams, unsigned cols, const DeltaTaps tp)
 {
     __shared__ float tile[kStreamRows * kColTile];
+    // 32 bits hold both: the host refuses a state length 2 L * cols + 1 >= 2^31 (stream_len), so cols < 2^30 / L and, with L >= order,
+    // ocols = (order + 1) * cols < 2^31 -- unlike the packed kernel, whose cols is bounded by 2^31 alone
     const unsigned L = tp.lag, hist = 2 * L, state_len = hist * cols + 1, ocols = (tp.order + 1) * cols;
     const RowPoolEntry e = row_pool_entry<FLUSH>(ro, slots, total_rows, pool_streams, pool, state_len, hist, L);
     if (!e.state || (!FLUSH && e.rows == 0)) return;  // the whole workgroup: the pool row stays as it is

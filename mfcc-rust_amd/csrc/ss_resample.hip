@@ -497,7 +497,10 @@ int check_dense(const ss_resampler *rs, const T *x, size_t batch, size_t n_sampl
     if (out_len >= (1ull << 31)) return fail(SS_ERR_ARG, "a clip's output must be shorter than 2^31 samples");
     if (ld < n_samples) return fail(SS_ERR_ARG, "ld < n_samples");
     if (ld_out < out_len) return fail(SS_ERR_ARG, "ld_out < ss_resample_len(n_samples)");
-    if (ranges_overlap(x, batch * ld * sizeof(T), out, batch * ld_out * sizeof(float))) return fail(SS_ERR_ARG, "out overlaps x: the call is not in place");
+    // what the call touches: the last row ends n_samples (out_len) behind its start, not a whole stride -- a block of (batch - 1) *
+    // ld + n_samples floats is a whole batch, and what the allocator put behind it is not part of it
+    const size_t x_span = batch ? (batch - 1) * ld + n_samples : 0, out_span = batch ? (batch - 1) * ld_out + out_len : 0;
+    if (ranges_overlap(x, x_span * sizeof(T), out, out_span * sizeof(float))) return fail(SS_ERR_ARG, "out overlaps x: the call is not in place");
     return SS_OK;
 }
 
