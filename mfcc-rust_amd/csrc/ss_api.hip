@@ -3285,21 +3285,16 @@ int kaldi_dense_host(const ss_kaldi_config *cfg, bool mfcc, const float *x, size
     if (rc) return rc;
     if (!ss::have_device()) return ss::no_device("hot path");
     const size_t cols = mfcc ? cfg->params.num_ceps : cfg->params.num_mel_bins, rows = batch * T;
-    DeviceBuf d_in, d_out, d_en;
-    hipError_t e = d_in.hip_alloc(batch * n_samples * sizeof(float));
-    if (e == hipSuccess) e = d_out.hip_alloc(rows * cols * sizeof(float));
-    if (e == hipSuccess && log_energy) e = d_en.hip_alloc(rows * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy2D(d_in.p, n_samples * sizeof(float), x, ld * sizeof(float), n_samples * sizeof(float), batch, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? kaldi_dense_device(cfg, mfcc, d_in.as<const float>(), batch, n_samples, n_samples, d_out.as<float>(),
-                                              log_energy ? d_en.as<float>() : nullptr, nullptr)
-                         : hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_kaldi: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && log_energy) e = hipMemcpy(log_energy, d_en.p, rows * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    return rc;
+    ss::HostStage st("ss_kaldi");
+    float *d_in = st.room<float>(batch * n_samples * sizeof(float));
+    float *d_out = st.room<float>(rows * cols * sizeof(float));
+    float *d_en = log_energy ? st.room<float>(rows * sizeof(float)) : nullptr;
+    st.up_rows(d_in, x, ld * sizeof(float), n_samples * sizeof(float), batch);
+    if (st.ok()) st.ran(kaldi_dense_device(cfg, mfcc, d_in, batch, n_samples, n_samples, d_out, d_en, nullptr));
+    st.sync();
+    st.down(out, d_out, rows * cols * sizeof(float));
+    if (log_energy) st.down(log_energy, d_en, rows * sizeof(float));
+    return st.status();
 }
 
 int kaldi_packed_device(const ss_kaldi_config *cfg, bool mfcc, const float *d_x, size_t n_clips, const int64_t *d_so, const int64_t *d_fo,
@@ -3335,26 +3330,17 @@ int kaldi_packed_host(const ss_kaldi_config *cfg, bool mfcc, const float *x, siz
     const size_t total_in = static_cast<size_t>(so[n_clips]), rows = static_cast<size_t>(fo[n_clips]);
     const size_t cols = mfcc ? cfg->params.num_ceps : cfg->params.num_mel_bins, tbytes = (n_clips + 1) * sizeof(int64_t);
     if (!ss::have_device()) return ss::no_device("hot path");
-    DeviceBuf d_in, d_out, d_en, d_so, d_fo;
-    hipError_t e = d_in.hip_alloc(total_in * sizeof(float));
-    if (e == hipSuccess) e = d_out.hip_alloc(rows * cols * sizeof(float));
-    if (e == hipSuccess && log_energy) e = d_en.hip_alloc(rows * sizeof(float));
-    if (e == hipSuccess) e = d_so.hip_alloc(tbytes);
-    if (e == hipSuccess) e = d_fo.hip_alloc(tbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in.p, x, total_in * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_so.p, so, tbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_fo.p, fo.data(), tbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? kaldi_packed_device(cfg, mfcc, d_in.as<const float>(), n_clips, d_so.as<const int64_t>(), d_fo.as<const int64_t>(), rows,
-                                               d_out.as<float>(), log_energy ? d_en.as<float>() : nullptr, nullptr)
-                         : hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_kaldi: device error");
-    if (rc == SS_OK) rc = kaldi_pending_error(cfg);
-    if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && log_energy) e = hipMemcpy(log_energy, d_en.p, rows * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    return rc;
+    ss::HostStage st("ss_kaldi");
+    const float *d_in = st.up(x, total_in * sizeof(float));
+    float *d_out = st.room<float>(rows * cols * sizeof(float));
+    float *d_en = log_energy ? st.room<float>(rows * sizeof(float)) : nullptr;
+    const int64_t *d_so = st.up(so, tbytes), *d_fo = st.up(fo.data(), tbytes);
+    if (st.ok()) st.ran(kaldi_packed_device(cfg, mfcc, d_in, n_clips, d_so, d_fo, rows, d_out, d_en, nullptr));
+    st.sync();
+    if (st.ok()) st.ran(kaldi_pending_error(cfg));
+    st.down(out, d_out, rows * cols * sizeof(float));
+    if (log_energy) st.down(log_energy, d_en, rows * sizeof(float));
+    return st.status();
 }
 
 // Ragged streaming fbank / MFCC over a pool of stream states (ss_kstream_*_packed*_device): the rows of n_active entries of different
@@ -3435,38 +3421,24 @@ int kaldi_pool_host(const ss_kaldi_config *cfg, bool mfcc, const PoolChunks &x, 
     if (!ss::have_device()) return ss::no_device("hot path");
     ss::PoolRows named;  // the named pool rows, row i = entry i's
     named.gather(pool, slots, n_active, S);
-    const size_t tbytes = (n_active + 1) * sizeof(int64_t), sbytes = n_active * S * sizeof(float);
-    // (hip_alloc of 0 bytes: give every block at least one element)
-    DeviceBuf dx, dso, dro, dsl, dp, d0, d1;
-    hipError_t e = dx.hip_alloc(std::max<size_t>(samples, 1) * x.sample_bytes());
-    if (e == hipSuccess) e = dso.hip_alloc(tbytes);
-    if (e == hipSuccess) e = dro.hip_alloc(tbytes);
-    if (e == hipSuccess) e = dsl.hip_alloc(n_active * sizeof(int32_t));
-    if (e == hipSuccess && S > 0) e = dp.hip_alloc(sbytes);
-    if (e == hipSuccess) e = d0.hip_alloc(std::max<size_t>(rows * cols, 1) * sizeof(float));
-    if (e == hipSuccess && log_energy) e = d1.hip_alloc(std::max<size_t>(rows, 1) * sizeof(float));
-    if (e == hipSuccess && samples) e = hipMemcpy(dx.p, x.ptr(), samples * x.sample_bytes(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dso.p, so, tbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dro.p, ro.data(), tbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dsl.p, named.iota.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && S > 0) e = hipMemcpy(dp.p, named.rows_host.data(), sbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? kaldi_pool_device(cfg, mfcc, x.is_pcm ? PoolChunks(dx.as<const int16_t>(), x.scale) : PoolChunks(dx.as<const float>()),
-                                             n_active, dso.as<const int64_t>(), dro.as<const int64_t>(), rows, dsl.as<const int32_t>(), n_active,
-                                             S > 0 ? dp.as<float>() : nullptr, d0.as<float>(), log_energy ? d1.as<float>() : nullptr, nullptr)
-                         : hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_kstream: device error");
-    if (rc == SS_OK) rc = kaldi_pending_error(cfg);
-    if (rc == SS_OK && rows > 0) {
-        e = hipMemcpy(out, d0.p, rows * cols * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && log_energy) e = hipMemcpy(log_energy, d1.p, rows * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    if (rc == SS_OK && S > 0) {
-        e = hipMemcpy(named.rows_host.data(), dp.p, sbytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H (pool rows)");
-        if (rc == SS_OK) named.scatter(pool, slots);
-    }
-    return rc;
+    const size_t tbytes = (n_active + 1) * sizeof(int64_t);
+    ss::HostStage st("ss_kstream");
+    const void *dx = st.up(x.ptr(), samples * x.sample_bytes());
+    const int64_t *dso = st.up(so, tbytes), *dro = st.up(ro.data(), tbytes);
+    const auto d_named = st.up_pool(named);  // no rows where the pool has no state (S == 0)
+    float *d0 = st.room<float>(rows * cols * sizeof(float));
+    float *d1 = log_energy ? st.room<float>(rows * sizeof(float)) : nullptr;
+    if (st.ok())
+        st.ran(kaldi_pool_device(cfg, mfcc,
+                                 x.is_pcm ? PoolChunks(static_cast<const int16_t *>(dx), x.scale) : PoolChunks(static_cast<const float *>(dx)),
+                                 n_active, dso, dro, rows, d_named.slots, n_active, d_named.rows, d0, d1, nullptr));
+    st.sync();
+    if (st.ok()) st.ran(kaldi_pending_error(cfg));
+    st.down(out, d0, rows * cols * sizeof(float));
+    if (log_energy) st.down(log_energy, d1, rows * sizeof(float));
+    st.down_pool(named, d_named, " (pool rows)");
+    st.scatter(named, pool, slots);
+    return st.status();
 }
 
 }  // namespace

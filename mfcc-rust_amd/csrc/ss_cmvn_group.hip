@@ -493,37 +493,6 @@ int check_host_tables(const int64_t *offsets, const int32_t *clip_group, size_t 
     return rc;
 }
 
-// the uploads every host-pointer form needs: the block, the two tables and the statistics rows
-struct GroupStaging {
-    DeviceBuf vec, off, grp, stats, out;
-    hipError_t up(const float *v, size_t n_floats, const int64_t *o, const int32_t *g, size_t n_clips, const double *st, size_t st_bytes, bool want_out)
-    {
-        hipError_t e = vec.hip_alloc(n_floats * sizeof(float));
-        if (e == hipSuccess) e = off.hip_alloc((n_clips + 1) * sizeof(int64_t));
-        if (e == hipSuccess && g) e = grp.hip_alloc(n_clips * sizeof(int32_t));
-        if (e == hipSuccess && st_bytes) e = stats.hip_alloc(st_bytes);
-        if (e == hipSuccess && want_out) e = out.hip_alloc(n_floats * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(vec.p, v, n_floats * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(off.p, o, (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess && g) e = hipMemcpy(grp.p, g, n_clips * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess && st) e = hipMemcpy(stats.p, st, st_bytes, hipMemcpyHostToDevice);
-        return e;
-    }
-};
-
-int finish(int rc, const char *what)
-{
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, std::string(what) + ": device error");
-    return rc;
-}
-
-int down(int rc, void *dst, const void *src, size_t bytes)
-{
-    if (rc != SS_OK || bytes == 0) return rc;
-    const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? SS_OK : hip_fail(e, "hipMemcpy D2H");
-}
-
 }  // namespace
 
 }  // namespace ss
@@ -643,12 +612,15 @@ int ss_cmvn_stats_packed(const float *vec, size_t n_clips, const int64_t *offset
     if (offsets[n_clips] == 0) return SS_OK;
     if (!ss::have_device()) return ss::no_device();
     const size_t sb = ss::stats_bytes(n_groups, cols);
-    ss::GroupStaging d;
-    const hipError_t e = d.up(vec, total_rows * cols, offsets, clip_group, n_clips, stats, sb, false);
-    rc = e == hipSuccess ? ss_cmvn_stats_packed_device(d.vec.as<const float>(), n_clips, d.off.as<const int64_t>(), total_rows, cols,
-                                                       clip_group ? d.grp.as<const int32_t>() : nullptr, n_groups, d.stats.as<double>(), nullptr)
-                         : ss::hip_fail(e, "host staging");
-    return ss::down(ss::finish(rc, "ss_cmvn_stats_packed"), stats, d.stats.p, sb);
+    ss::HostStage st("ss_cmvn_stats_packed");
+    const float *d_vec = st.up(vec, total_rows * cols * sizeof(float));
+    const int64_t *d_off = st.up(offsets, (n_clips + 1) * sizeof(int64_t));
+    const int32_t *d_grp = clip_group ? st.up(clip_group, n_clips * sizeof(int32_t)) : nullptr;
+    double *d_stats = st.up(stats, sb);
+    if (st.ok()) st.ran(ss_cmvn_stats_packed_device(d_vec, n_clips, d_off, total_rows, cols, d_grp, n_groups, d_stats, nullptr));
+    st.sync();
+    st.down(stats, d_stats, sb);
+    return st.status();
 }
 
 int ss_cmvn_apply_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, const int32_t *clip_group,
@@ -662,15 +634,19 @@ int ss_cmvn_apply_packed(const float *vec, size_t n_clips, const int64_t *offset
     if (offsets[n_clips] == 0) return SS_OK;
     if (!ss::have_device()) return ss::no_device();
     // the rows of a clip that is left out (id -1, a group without statistics) keep the caller's bytes: out goes up first
-    ss::GroupStaging d;
-    hipError_t e = d.up(vec, total_rows * cols, offsets, clip_group, n_clips, stats, ss::stats_bytes(n_groups, cols), true);
-    const size_t written = static_cast<size_t>(offsets[n_clips]) * cols * sizeof(float);
-    if (e == hipSuccess) e = hipMemcpy(d.out.p, out, written, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? ss_cmvn_apply_packed_device(d.vec.as<const float>(), n_clips, d.off.as<const int64_t>(), total_rows, cols,
-                                                       clip_group ? d.grp.as<const int32_t>() : nullptr, n_groups, d.stats.as<const double>(),
-                                                       variance_normalization, d.out.as<float>(), nullptr)
-                         : ss::hip_fail(e, "host staging");
-    return ss::down(ss::finish(rc, "ss_cmvn_apply_packed"), out, d.out.p, written);
+    const size_t bytes = total_rows * cols * sizeof(float), written = static_cast<size_t>(offsets[n_clips]) * cols * sizeof(float);
+    ss::HostStage st("ss_cmvn_apply_packed");
+    const float *d_vec = st.up(vec, bytes);
+    const int64_t *d_off = st.up(offsets, (n_clips + 1) * sizeof(int64_t));
+    const int32_t *d_grp = clip_group ? st.up(clip_group, n_clips * sizeof(int32_t)) : nullptr;
+    const double *d_stats = st.up(stats, ss::stats_bytes(n_groups, cols));
+    float *d_out = st.room<float>(bytes);
+    st.fill(d_out, out, written);
+    if (st.ok())
+        st.ran(ss_cmvn_apply_packed_device(d_vec, n_clips, d_off, total_rows, cols, d_grp, n_groups, d_stats, variance_normalization, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, written);
+    return st.status();
 }
 
 int ss_cmvn_grouped_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, const int32_t *clip_group,
@@ -684,15 +660,17 @@ int ss_cmvn_grouped_packed(const float *vec, size_t n_clips, const int64_t *offs
     if ((rc = ss::check_host_tables(offsets, clip_group, n_clips, total_rows, n_groups))) return rc;
     if (offsets[n_clips] == 0) return SS_OK;
     if (!ss::have_device()) return ss::no_device();
-    ss::GroupStaging d;
-    hipError_t e = d.up(vec, total_rows * cols, offsets, clip_group, n_clips, nullptr, 0, true);
     const size_t written = static_cast<size_t>(offsets[n_clips]) * cols * sizeof(float);
-    if (e == hipSuccess) e = hipMemcpy(d.out.p, out, written, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? ss_cmvn_grouped_packed_device(d.vec.as<const float>(), n_clips, d.off.as<const int64_t>(), total_rows, cols,
-                                                         clip_group ? d.grp.as<const int32_t>() : nullptr, n_groups, variance_normalization,
-                                                         d.out.as<float>(), nullptr)
-                         : ss::hip_fail(e, "host staging");
-    return ss::down(ss::finish(rc, "ss_cmvn_grouped_packed"), out, d.out.p, written);
+    ss::HostStage st("ss_cmvn_grouped_packed");
+    const float *d_vec = st.up(vec, bytes);
+    const int64_t *d_off = st.up(offsets, (n_clips + 1) * sizeof(int64_t));
+    const int32_t *d_grp = clip_group ? st.up(clip_group, n_clips * sizeof(int32_t)) : nullptr;
+    float *d_out = st.room<float>(bytes);
+    st.fill(d_out, out, written);
+    if (st.ok()) st.ran(ss_cmvn_grouped_packed_device(d_vec, n_clips, d_off, total_rows, cols, d_grp, n_groups, variance_normalization, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, written);
+    return st.status();
 }
 
 }  // extern "C"

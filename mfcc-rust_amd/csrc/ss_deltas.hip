@@ -313,35 +313,20 @@ int stream_via_device(bool flush, const float *vec, size_t n_active, const int64
     PoolRows named;
     named.gather(pool, slots, n_active, len);
     const size_t bytes = in_rows * cols * sizeof(float), obytes = out_rows * cols * (order + 1) * sizeof(float);
-    const size_t tbytes = (n_active + 1) * sizeof(int64_t), ibytes = n_active * sizeof(int32_t);
-    DeviceBuf d_vec, d_out, d_ro, d_sl, d_pool;
-    hipError_t e = d_out.hip_alloc(obytes);
-    if (e == hipSuccess) e = d_sl.hip_alloc(ibytes);
-    if (e == hipSuccess) e = d_pool.hip_alloc(named.bytes());
-    if (!flush) {
-        if (e == hipSuccess) e = d_vec.hip_alloc(bytes);
-        if (e == hipSuccess) e = d_ro.hip_alloc(tbytes);
-        if (e == hipSuccess) e = hipMemcpy(d_vec.p, vec, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_ro.p, row_offsets, tbytes, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(d_sl.p, named.iota.data(), ibytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pool.p, named.rows_host.data(), named.bytes(), hipMemcpyHostToDevice);
-    int rc = SS_OK;
-    if (e != hipSuccess) rc = hip_fail(e, "host staging");
-    else if (flush)
-        rc = ss_add_deltas_stream_flush_device(n_active, d_sl.as<const int32_t>(), n_active, cols, order, window, d_pool.as<float>(), d_out.as<float>(),
-                                               nullptr);
-    else
-        rc = ss_add_deltas_stream_packed_device(d_vec.as<const float>(), n_active, d_ro.as<const int64_t>(), in_rows, d_sl.as<const int32_t>(), n_active,
-                                                cols, order, window, d_pool.as<float>(), d_out.as<float>(), nullptr);
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_add_deltas_stream: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(named.rows_host.data(), d_pool.p, named.bytes(), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out, d_out.p, obytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    if (rc == SS_OK) named.scatter(pool, slots);
-    return rc;
+    HostStage st("ss_add_deltas_stream");
+    float *d_out = st.room<float>(obytes);
+    const auto d_named = st.up_pool(named);
+    const float *d_vec = flush ? nullptr : st.up(vec, bytes);
+    const int64_t *d_ro = flush ? nullptr : st.up(row_offsets, (n_active + 1) * sizeof(int64_t));
+    if (st.ok())
+        st.ran(flush ? ss_add_deltas_stream_flush_device(n_active, d_named.slots, n_active, cols, order, window, d_named.rows, d_out, nullptr)
+                     : ss_add_deltas_stream_packed_device(d_vec, n_active, d_ro, in_rows, d_named.slots, n_active, cols, order, window, d_named.rows, d_out,
+                                                          nullptr));
+    st.sync();
+    st.down_pool(named, d_named);
+    st.down(out, d_out, obytes);
+    st.scatter(named, pool, slots);
+    return st.status();
 }
 
 }  // namespace
@@ -377,22 +362,15 @@ int ss_add_deltas_packed(const float *vec, size_t n_clips, const int64_t *offset
     if (rc || (rc = ss::check_clip_table(offsets, n_clips, total_rows))) return rc;
     if (offsets[n_clips] == 0) return SS_OK;
     if (!ss::have_device()) return ss::no_device();
-    const size_t bytes = total_rows * cols * sizeof(float), tbytes = (n_clips + 1) * sizeof(int64_t);
-    ss::DeviceBuf d_in, d_out, d_off;
-    hipError_t e = d_in.hip_alloc(bytes);
-    if (e == hipSuccess) e = d_out.hip_alloc(bytes * (order + 1));
-    if (e == hipSuccess) e = d_off.hip_alloc(tbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in.p, vec, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_off.p, offsets, tbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? ss_add_deltas_packed_device(d_in.as<const float>(), n_clips, d_off.as<const int64_t>(), total_rows, cols, order, window,
-                                                       d_out.as<float>(), nullptr)
-                         : ss::hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_add_deltas_packed: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out.p, static_cast<size_t>(offsets[n_clips]) * cols * (order + 1) * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = ss::hip_fail(e, "hipMemcpy D2H");
-    }
-    return rc;
+    const size_t bytes = total_rows * cols * sizeof(float);
+    ss::HostStage st("ss_add_deltas_packed");
+    const float *d_in = st.up(vec, bytes);
+    float *d_out = st.room<float>(bytes * (order + 1));
+    const int64_t *d_off = st.up(offsets, (n_clips + 1) * sizeof(int64_t));
+    if (st.ok()) st.ran(ss_add_deltas_packed_device(d_in, n_clips, d_off, total_rows, cols, order, window, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, static_cast<size_t>(offsets[n_clips]) * cols * (order + 1) * sizeof(float));
+    return st.status();
 }
 
 int ss_add_deltas_stream_state_len(size_t cols, size_t order, size_t window, size_t *state_len)

@@ -1,10 +1,12 @@
-// What the host-pointer wrappers share on the HIP side: a HIP error as a status, the device probe and an owned device buffer.
+// What the host-pointer wrappers share on the HIP side: a HIP error as a status, the device probe, an owned device buffer and
+// HostStage, the staging of one host-pointer call (ss_host_stage.h) over the HIP runtime.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <string>
 
+#include "ss_host_stage.h"
 #include "ss_internal.h"
 
 namespace ss {
@@ -33,14 +35,37 @@ struct DeviceBuf {
     {
         if (p) (void)hipFree(p);
     }
-    hipError_t hip_alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }  // for a chain of HIP calls with one message
     int alloc(size_t bytes)
     {
-        const hipError_t e = hip_alloc(bytes);
+        const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
         return e == hipSuccess ? SS_OK : hip_fail(e, "hipMalloc(&p, bytes ? bytes : 16)");
     }
     template <typename T>
     T *as() { return static_cast<T *>(p); }
+};
+
+// HostStageT's steps as blocking HIP calls
+struct HipStageBackend {
+    static const char *text(hipError_t e) { return e == hipSuccess ? nullptr : hipGetErrorString(e); }
+    const char *alloc(void **p, size_t bytes) { return text(hipMalloc(p, bytes)); }
+    void free(void *p) { (void)hipFree(p); }
+    const char *up(void *dev, const void *host, size_t bytes) { return text(hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice)); }
+    const char *down(void *host, const void *dev, size_t bytes) { return text(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost)); }
+    const char *sync() { return text(hipDeviceSynchronize()); }
+};
+
+// The stager of the library's host-pointer calls.  The two strided copies of the dense forms: `rows` rows of `width` bytes between
+// the caller's block (pitch bytes from row to row) and a compact device block.
+struct HostStage : HostStageT<HipStageBackend> {
+    using HostStageT::HostStageT;
+    void up_rows(void *dev, const void *host, size_t pitch, size_t width, size_t rows)
+    {
+        if (ok()) staged(HipStageBackend::text(hipMemcpy2D(dev, width, host, pitch, width, rows, hipMemcpyHostToDevice)));
+    }
+    void down_rows(void *host, size_t pitch, const void *dev, size_t width, size_t rows)
+    {
+        if (ok()) downed(HipStageBackend::text(hipMemcpy2D(host, pitch, dev, width, width, rows, hipMemcpyDeviceToHost)));
+    }
 };
 
 }  // namespace ss

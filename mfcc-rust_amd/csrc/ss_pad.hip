@@ -347,24 +347,17 @@ int ss_pad_packed(const float *vec, size_t n_clips, const int64_t *row_offsets, 
     int rc = ss::check_scalars(n_clips, total_rows, cols, max_rows, layout, dtype, out, bytes);
     if (rc || (rc = ss::check_clip_table(row_offsets, n_clips, total_rows))) return rc;
     if (!ss::have_device()) return ss::no_device();
-    const size_t vbytes = total_rows * cols * sizeof(float), tbytes = (n_clips + 1) * sizeof(int64_t), lbytes = n_clips * sizeof(int32_t);
-    ss::DeviceBuf d_in, d_out, d_ro, d_len;
-    hipError_t e = d_in.hip_alloc(vbytes);
-    if (e == hipSuccess) e = d_out.hip_alloc(bytes);
-    if (e == hipSuccess) e = d_ro.hip_alloc(tbytes);
-    if (e == hipSuccess) e = d_len.hip_alloc(lbytes);
-    if (e == hipSuccess && vbytes) e = hipMemcpy(d_in.p, vec, vbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_ro.p, row_offsets, tbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? ss_pad_packed_device(d_in.as<const float>(), n_clips, d_ro.as<const int64_t>(), total_rows, cols, max_rows, layout, dtype, pad_value,
-                                                d_out.p, d_len.as<int32_t>(), nullptr)
-                         : ss::hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_pad_packed: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(lengths, d_len.p, lbytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = ss::hip_fail(e, "hipMemcpy D2H");
-    }
-    return rc;
+    const size_t lbytes = n_clips * sizeof(int32_t);
+    ss::HostStage st("ss_pad_packed");
+    const float *d_in = st.up(vec, total_rows * cols * sizeof(float));
+    void *d_out = st.room<void>(bytes);
+    const int64_t *d_ro = st.up(row_offsets, (n_clips + 1) * sizeof(int64_t));
+    int32_t *d_len = st.room<int32_t>(lbytes);
+    if (st.ok()) st.ran(ss_pad_packed_device(d_in, n_clips, d_ro, total_rows, cols, max_rows, layout, dtype, pad_value, d_out, d_len, nullptr));
+    st.sync();
+    st.down(out, d_out, bytes);
+    st.down(lengths, d_len, lbytes);
+    return st.status();
 }
 
 }  // extern "C"

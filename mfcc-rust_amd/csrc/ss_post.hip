@@ -647,24 +647,7 @@ int check_shape(const void *a, const void *b, size_t batch, size_t rows, size_t 
     return SS_OK;
 }
 
-// host-pointer wrapper: upload, run the device entry point, download
-template <typename F>
-int via_device(const float *in, size_t n_in, float *out, size_t n_out, F &&run)
-{
-    if (!have_device()) return no_device();
-    DeviceBuf d_in, d_out;
-    hipError_t e = d_in.hip_alloc(n_in * sizeof(float));
-    if (e == hipSuccess) e = d_out.hip_alloc(n_out * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d_in.p, in, n_in * sizeof(float), hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? run(d_in.as<const float>(), d_out.as<float>()) : hip_fail(e, "host staging");
-    if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out.p, n_out * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    return rc;
-}
-
-// ---- packed clips: argument checks, grid shape, host staging ----
+// ---- packed clips: argument checks, grid shape ----
 
 int check_packed(const void *a, const void *off, const void *b, size_t n_clips, size_t total_rows, size_t cols)
 {
@@ -672,29 +655,6 @@ int check_packed(const void *a, const void *off, const void *b, size_t n_clips, 
     if (cols == 0) return fail(SS_ERR_ARG, "empty feature matrix (cols == 0)");
     if (total_rows >= (1ull << 31) || cols >= (1ull << 31) || n_clips >= (1ull << 31)) return fail(SS_ERR_ARG, "feature block too large");
     return SS_OK;
-}
-
-// host-pointer wrapper of the packed calls: upload the block (n floats) and the checked table, run the device entry point,
-// download the rows the table covers (n_written floats from the start: a host table is gap-free; rows past offsets[n_clips] stay
-// as the caller left them)
-template <typename F>
-int via_device_packed(const float *in, const int64_t *off, size_t n_clips, size_t n, size_t n_written, float *out, F &&run)
-{
-    if (!have_device()) return no_device();
-    const size_t tbytes = (n_clips + 1) * sizeof(int64_t);
-    DeviceBuf d_in, d_out, d_off;
-    hipError_t e = d_in.hip_alloc(n * sizeof(float));
-    if (e == hipSuccess) e = d_out.hip_alloc(n * sizeof(float));
-    if (e == hipSuccess) e = d_off.hip_alloc(tbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in.p, in, n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_off.p, off, tbytes, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? run(d_in.as<const float>(), d_off.as<const int64_t>(), d_out.as<float>()) : hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "packed post-processing: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out.p, n_written * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    return rc;
 }
 
 // ---- causal CMVN over a pool of stream states: argument checks ----
@@ -848,11 +808,14 @@ int ss_cmvn(const float *vec, size_t rows, size_t cols, int variance_normalizati
 {
     int rc = ss::check_shape(vec, out, 1, rows, cols);
     if (rc) return rc;
-    return ss::via_device(vec, rows * cols, out, rows * cols, [&](const float *di, float *dout) {
-        int r = ss_cmvn_batch_device(di, 1, rows, cols, variance_normalization, dout, nullptr);
-        if (r == SS_OK && hipDeviceSynchronize() != hipSuccess) r = ss::fail(SS_ERR_HIP, "ss_cmvn: device error");
-        return r;
-    });
+    if (!ss::have_device()) return ss::no_device();
+    ss::HostStage st("ss_cmvn");
+    const float *d_in = st.up(vec, rows * cols * sizeof(float));
+    float *d_out = st.room<float>(rows * cols * sizeof(float));
+    if (st.ok()) st.ran(ss_cmvn_batch_device(d_in, 1, rows, cols, variance_normalization, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, rows * cols * sizeof(float));
+    return st.status();
 }
 
 int ss_cmvnw(const float *vec, size_t rows, size_t cols, size_t win_size, int variance_normalization, float *out)
@@ -860,11 +823,14 @@ int ss_cmvnw(const float *vec, size_t rows, size_t cols, size_t win_size, int va
     int rc = ss::check_shape(vec, out, 1, rows, cols);
     if (rc) return rc;
     if (win_size % 2 != 1) return ss::fail(SS_ERR_BAD_CONFIG, "Windows size must be odd!");
-    return ss::via_device(vec, rows * cols, out, rows * cols, [&](const float *di, float *dout) {
-        int r = ss_cmvnw_batch_device(di, 1, rows, cols, win_size, variance_normalization, dout, nullptr);
-        if (r == SS_OK && hipDeviceSynchronize() != hipSuccess) r = ss::fail(SS_ERR_HIP, "ss_cmvnw: device error");
-        return r;
-    });
+    if (!ss::have_device()) return ss::no_device();
+    ss::HostStage st("ss_cmvnw");
+    const float *d_in = st.up(vec, rows * cols * sizeof(float));
+    float *d_out = st.room<float>(rows * cols * sizeof(float));
+    if (st.ok()) st.ran(ss_cmvnw_batch_device(d_in, 1, rows, cols, win_size, variance_normalization, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, rows * cols * sizeof(float));
+    return st.status();
 }
 
 int ss_derivative_extraction(const float *feat, size_t rows, size_t cols, size_t delta_windows, float *out)
@@ -872,22 +838,28 @@ int ss_derivative_extraction(const float *feat, size_t rows, size_t cols, size_t
     int rc = ss::check_shape(feat, out, 1, rows, cols);
     if (rc) return rc;
     if (delta_windows == 0) return ss::fail(SS_ERR_ARG, "delta_windows must be >= 1");
-    return ss::via_device(feat, rows * cols, out, rows * cols, [&](const float *di, float *dout) {
-        int r = ss_derivative_extraction_device(di, rows, cols, delta_windows, dout, nullptr);
-        if (r == SS_OK && hipDeviceSynchronize() != hipSuccess) r = ss::fail(SS_ERR_HIP, "ss_derivative_extraction: device error");
-        return r;
-    });
+    if (!ss::have_device()) return ss::no_device();
+    ss::HostStage st("ss_derivative_extraction");
+    const float *d_in = st.up(feat, rows * cols * sizeof(float));
+    float *d_out = st.room<float>(rows * cols * sizeof(float));
+    if (st.ok()) st.ran(ss_derivative_extraction_device(d_in, rows, cols, delta_windows, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, rows * cols * sizeof(float));
+    return st.status();
 }
 
 int ss_extract_derivative_feature(const float *feat, size_t rows, size_t cols, float *cube)
 {
     int rc = ss::check_shape(feat, cube, 1, rows, cols);
     if (rc) return rc;
-    return ss::via_device(feat, rows * cols, cube, 3 * rows * cols, [&](const float *di, float *dout) {
-        int r = ss_extract_derivative_feature_device(di, rows, cols, dout, nullptr);
-        if (r == SS_OK && hipDeviceSynchronize() != hipSuccess) r = ss::fail(SS_ERR_HIP, "ss_extract_derivative_feature: device error");
-        return r;
-    });
+    if (!ss::have_device()) return ss::no_device();
+    ss::HostStage st("ss_extract_derivative_feature");
+    const float *d_in = st.up(feat, rows * cols * sizeof(float));
+    float *d_out = st.room<float>(3 * rows * cols * sizeof(float));
+    if (st.ok()) st.ran(ss_extract_derivative_feature_device(d_in, rows, cols, d_out, nullptr));
+    st.sync();
+    st.down(cube, d_out, 3 * rows * cols * sizeof(float));
+    return st.status();
 }
 
 int ss_ln_device(float *d_x, size_t n, void *stream)
@@ -929,11 +901,14 @@ int ss_power_to_db(const float *s, size_t n, float ref, float amin, float top_db
 {
     if (n == 0) return SS_OK;
     if (!s || !out) return ss::fail(SS_ERR_ARG, "null buffer");
-    return ss::via_device(s, n, out, n, [&](const float *di, float *dout) {
-        int r = ss_power_to_db_device(di, n, ref, amin, top_db, dout, nullptr);
-        if (r == SS_OK && hipDeviceSynchronize() != hipSuccess) r = ss::fail(SS_ERR_HIP, "ss_power_to_db: device error");
-        return r;
-    });
+    if (!ss::have_device()) return ss::no_device();
+    ss::HostStage st("ss_power_to_db");
+    const float *d_in = st.up(s, n * sizeof(float));
+    float *d_out = st.room<float>(n * sizeof(float));
+    if (st.ok()) st.ran(ss_power_to_db_device(d_in, n, ref, amin, top_db, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, n * sizeof(float));
+    return st.status();
 }
 
 // ---- packed variable-length clips: clip b owns rows offsets[b] .. offsets[b+1] of the [total_rows x cols] block ----
@@ -1025,10 +1000,16 @@ int ss_cmvn_packed(const float *vec, size_t n_clips, const int64_t *offsets, siz
     int rc = ss::check_packed(vec, offsets, out, n_clips, total_rows, cols);
     if (rc || (rc = ss::check_clip_table(offsets, n_clips, total_rows))) return rc;
     if (offsets[n_clips] == 0) return SS_OK;
-    return ss::via_device_packed(vec, offsets, n_clips, total_rows * cols, static_cast<size_t>(offsets[n_clips]) * cols, out,
-                                 [&](const float *di, const int64_t *doff, float *dout) {
-                                     return ss_cmvn_packed_device(di, n_clips, doff, total_rows, cols, variance_normalization, dout, nullptr);
-                                 });
+    if (!ss::have_device()) return ss::no_device();
+    const size_t bytes = total_rows * cols * sizeof(float);
+    ss::HostStage st("packed post-processing");
+    const float *d_in = st.up(vec, bytes);
+    const int64_t *d_off = st.up(offsets, (n_clips + 1) * sizeof(int64_t));
+    float *d_out = st.room<float>(bytes);
+    if (st.ok()) st.ran(ss_cmvn_packed_device(d_in, n_clips, d_off, total_rows, cols, variance_normalization, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, static_cast<size_t>(offsets[n_clips]) * cols * sizeof(float));  // the rows the table covers
+    return st.status();
 }
 
 int ss_cmvnw_packed(const float *vec, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, size_t win_size,
@@ -1041,10 +1022,16 @@ int ss_cmvnw_packed(const float *vec, size_t n_clips, const int64_t *offsets, si
     if (win_size >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "window too large");
     if ((rc = ss::check_clip_table(offsets, n_clips, total_rows))) return rc;
     if (offsets[n_clips] == 0) return SS_OK;
-    return ss::via_device_packed(vec, offsets, n_clips, total_rows * cols, static_cast<size_t>(offsets[n_clips]) * cols, out,
-                                 [&](const float *di, const int64_t *doff, float *dout) {
-                                     return ss_cmvnw_packed_device(di, n_clips, doff, total_rows, cols, win_size, variance_normalization, dout, nullptr);
-                                 });
+    if (!ss::have_device()) return ss::no_device();
+    const size_t bytes = total_rows * cols * sizeof(float);
+    ss::HostStage st("packed post-processing");
+    const float *d_in = st.up(vec, bytes);
+    const int64_t *d_off = st.up(offsets, (n_clips + 1) * sizeof(int64_t));
+    float *d_out = st.room<float>(bytes);
+    if (st.ok()) st.ran(ss_cmvnw_packed_device(d_in, n_clips, d_off, total_rows, cols, win_size, variance_normalization, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, static_cast<size_t>(offsets[n_clips]) * cols * sizeof(float));  // the rows the table covers
+    return st.status();
 }
 
 int ss_power_to_db_packed(const float *s, size_t n_clips, const int64_t *offsets, size_t total_rows, size_t cols, float ref, float amin,
@@ -1057,10 +1044,16 @@ int ss_power_to_db_packed(const float *s, size_t n_clips, const int64_t *offsets
     if (ref != ref) return ss::fail(SS_ERR_ARG, "ref must not be NaN");
     if ((rc = ss::check_clip_table(offsets, n_clips, total_rows))) return rc;
     if (offsets[n_clips] == 0) return SS_OK;
-    return ss::via_device_packed(s, offsets, n_clips, total_rows * cols, static_cast<size_t>(offsets[n_clips]) * cols, out,
-                                 [&](const float *di, const int64_t *doff, float *dout) {
-                                     return ss_power_to_db_packed_device(di, n_clips, doff, total_rows, cols, ref, amin, top_db, dout, nullptr);
-                                 });
+    if (!ss::have_device()) return ss::no_device();
+    const size_t bytes = total_rows * cols * sizeof(float);
+    ss::HostStage st("packed post-processing");
+    const float *d_in = st.up(s, bytes);
+    const int64_t *d_off = st.up(offsets, (n_clips + 1) * sizeof(int64_t));
+    float *d_out = st.room<float>(bytes);
+    if (st.ok()) st.ran(ss_power_to_db_packed_device(d_in, n_clips, d_off, total_rows, cols, ref, amin, top_db, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, static_cast<size_t>(offsets[n_clips]) * cols * sizeof(float));  // the rows the table covers
+    return st.status();
 }
 
 // ---- causal sliding-window CMVN over a pool of stream states: entry i owns rows ro[i] .. ro[i+1] and pool row slots[i] ----
@@ -1113,29 +1106,20 @@ int ss_cmvn_stream_packed(const float *vec, size_t n_active, const int64_t *row_
     if (!ss::have_device()) return ss::no_device();
     ss::PoolRows named;
     named.gather(pool, slots, n_active, len);
-    const size_t bytes = rows * cols * sizeof(float), tbytes = (n_active + 1) * sizeof(int64_t), ibytes = n_active * sizeof(int32_t);
-    ss::DeviceBuf d_vec, d_out, d_ro, d_sl, d_pool;
-    hipError_t e = d_vec.hip_alloc(bytes);
-    if (e == hipSuccess) e = d_out.hip_alloc(bytes);
-    if (e == hipSuccess) e = d_ro.hip_alloc(tbytes);
-    if (e == hipSuccess) e = d_sl.hip_alloc(ibytes);
-    if (e == hipSuccess) e = d_pool.hip_alloc(named.bytes());
-    if (e == hipSuccess) e = hipMemcpy(d_vec.p, vec, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_ro.p, row_offsets, tbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_sl.p, named.iota.data(), ibytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pool.p, named.rows_host.data(), named.bytes(), hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? ss_cmvn_stream_packed_device(d_vec.as<const float>(), n_active, d_ro.as<const int64_t>(), rows, d_sl.as<const int32_t>(),
-                                                        n_active, cols, win_size, variance_normalization, d_pool.as<float>(), d_out.as<float>(),
-                                                        nullptr)
-                         : ss::hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_cmvn_stream_packed: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(named.rows_host.data(), d_pool.p, named.bytes(), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = ss::hip_fail(e, "hipMemcpy D2H");
-    }
-    if (rc == SS_OK) named.scatter(pool, slots);
-    return rc;
+    const size_t bytes = rows * cols * sizeof(float);
+    ss::HostStage st("ss_cmvn_stream_packed");
+    const float *d_vec = st.up(vec, bytes);
+    float *d_out = st.room<float>(bytes);
+    const int64_t *d_ro = st.up(row_offsets, (n_active + 1) * sizeof(int64_t));
+    const auto d_named = st.up_pool(named);
+    if (st.ok())
+        st.ran(ss_cmvn_stream_packed_device(d_vec, n_active, d_ro, rows, d_named.slots, n_active, cols, win_size, variance_normalization, d_named.rows,
+                                            d_out, nullptr));
+    st.sync();
+    st.down_pool(named, d_named);
+    st.down(out, d_out, bytes);
+    st.scatter(named, pool, slots);
+    return st.status();
 }
 
 }  // extern "C"

@@ -525,18 +525,14 @@ int dense_host(const ss_resampler *rs, const T *x, size_t batch, size_t n_sample
     if (rc) return rc;
     if (out_len == 0) return SS_OK;
     if (!have_device()) return no_device();
-    DeviceBuf d_in, d_out;
-    hipError_t e = d_in.hip_alloc(batch * n_samples * sizeof(T));
-    if (e == hipSuccess) e = d_out.hip_alloc(batch * out_len * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy2D(d_in.p, n_samples * sizeof(T), x, ld * sizeof(T), n_samples * sizeof(T), batch, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? dense_device<T>(rs, d_in.as<const T>(), batch, n_samples, n_samples, scale, d_out.as<float>(), out_len, nullptr)
-                         : hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_resample: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy2D(out, ld_out * sizeof(float), d_out.p, out_len * sizeof(float), out_len * sizeof(float), batch, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    return rc;
+    HostStage st("ss_resample");
+    T *d_in = st.room<T>(batch * n_samples * sizeof(T));
+    float *d_out = st.room<float>(batch * out_len * sizeof(float));
+    st.up_rows(d_in, x, ld * sizeof(T), n_samples * sizeof(T), batch);
+    if (st.ok()) st.ran(dense_device<T>(rs, d_in, batch, n_samples, n_samples, scale, d_out, out_len, nullptr));
+    st.sync();
+    st.down_rows(out, ld_out * sizeof(float), d_out, out_len * sizeof(float), batch);
+    return st.status();
 }
 
 // ---- packed ----
@@ -594,23 +590,14 @@ int packed_host(const ss_resampler *rs, const T *x, size_t n_clips, const int64_
     if (total_out == 0) return SS_OK;
     if (!have_device()) return no_device();
     const size_t tbytes = (n_clips + 1) * sizeof(int64_t);
-    DeviceBuf d_in, d_out, d_so, d_oo;
-    hipError_t e = d_in.hip_alloc(total_in * sizeof(T));
-    if (e == hipSuccess) e = d_out.hip_alloc(total_out * sizeof(float));
-    if (e == hipSuccess) e = d_so.hip_alloc(tbytes);
-    if (e == hipSuccess) e = d_oo.hip_alloc(tbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in.p, x, total_in * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_so.p, so, tbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_oo.p, oo, tbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? packed_device<T>(rs, d_in.as<const T>(), n_clips, d_so.as<const int64_t>(), scale, d_oo.as<const int64_t>(), total_in,
-                                            total_out, d_out.as<float>(), nullptr)
-                         : hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_resample_packed: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(out, d_out.p, total_out * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    return rc;
+    HostStage st("ss_resample_packed");
+    const T *d_in = st.up(x, total_in * sizeof(T));
+    float *d_out = st.room<float>(total_out * sizeof(float));
+    const int64_t *d_so = st.up(so, tbytes), *d_oo = st.up(oo, tbytes);
+    if (st.ok()) st.ran(packed_device<T>(rs, d_in, n_clips, d_so, scale, d_oo, total_in, total_out, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, total_out * sizeof(float));
+    return st.status();
 }
 
 // ---- pool ----
@@ -678,35 +665,20 @@ int stream_via_device(bool flush, const ss_resampler *rs, const T *x, size_t n_a
     if (!have_device()) return no_device();
     PoolRows named;
     named.gather(pool, slots, n_active, static_cast<size_t>(rs->f.g.hist) + 1);
-    const size_t bytes = n_in * sizeof(T), obytes = n_out * sizeof(float), tbytes = (n_active + 1) * sizeof(int64_t), ibytes = n_active * sizeof(int32_t);
-    DeviceBuf d_x, d_out, d_so, d_sl, d_pool;
-    hipError_t e = d_out.hip_alloc(obytes);
-    if (e == hipSuccess) e = d_sl.hip_alloc(ibytes);
-    if (e == hipSuccess) e = d_pool.hip_alloc(named.bytes());
-    if (!flush) {
-        if (e == hipSuccess) e = d_x.hip_alloc(bytes);
-        if (e == hipSuccess) e = d_so.hip_alloc(tbytes);
-        if (e == hipSuccess) e = hipMemcpy(d_x.p, x, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_so.p, so, tbytes, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(d_sl.p, named.iota.data(), ibytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pool.p, named.rows_host.data(), named.bytes(), hipMemcpyHostToDevice);
-    int rc = SS_OK;
-    if (e != hipSuccess) rc = hip_fail(e, "host staging");
-    else if (flush)
-        rc = stream_launch<float, true>(rs, nullptr, n_active, nullptr, 0, d_sl.as<const int32_t>(), n_active, 1.0f, d_pool.as<float>(), d_out.as<float>(),
-                                        nullptr);
-    else
-        rc = stream_device<T>(rs, d_x.as<const T>(), n_active, d_so.as<const int64_t>(), n_in, d_sl.as<const int32_t>(), n_active, scale, d_pool.as<float>(),
-                              d_out.as<float>(), nullptr);
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_resample_stream: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(named.rows_host.data(), d_pool.p, named.bytes(), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out, d_out.p, obytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    if (rc == SS_OK) named.scatter(pool, slots);
-    return rc;
+    const size_t obytes = n_out * sizeof(float);
+    HostStage st("ss_resample_stream");
+    float *d_out = st.room<float>(obytes);
+    const auto d_named = st.up_pool(named);
+    const T *d_x = flush ? nullptr : st.up(x, n_in * sizeof(T));
+    const int64_t *d_so = flush ? nullptr : st.up(so, (n_active + 1) * sizeof(int64_t));
+    if (st.ok())
+        st.ran(flush ? stream_launch<float, true>(rs, nullptr, n_active, nullptr, 0, d_named.slots, n_active, 1.0f, d_named.rows, d_out, nullptr)
+                     : stream_device<T>(rs, d_x, n_active, d_so, n_in, d_named.slots, n_active, scale, d_named.rows, d_out, nullptr));
+    st.sync();
+    st.down_pool(named, d_named);
+    st.down(out, d_out, obytes);
+    st.scatter(named, pool, slots);
+    return st.status();
 }
 
 template <typename T>

@@ -336,44 +336,6 @@ int launch_apply(const float *d_vec, size_t n_clips, const int64_t *d_ro, size_t
     return SS_OK;
 }
 
-// The host forms: block, table and spans on the device for the length of one call.  A checked host table covers rows 0 .. ro[n_clips)
-// without a gap, so exactly those rows come down; the rows behind them are in no clip and stay as the caller's out holds them.
-struct Staged {
-    DeviceBuf vec, out, ro, spans, rng;
-    size_t vbytes = 0, sbytes = 0, covered = 0;
-    bool inplace = false;
-
-    int up(const float *h_vec, const float *h_out, size_t n_clips, const int64_t *h_ro, size_t total_rows, size_t cols, size_t n_masks, const int32_t *h_spans,
-           const uint64_t *h_rng)
-    {
-        vbytes = total_rows * cols * sizeof(float);
-        sbytes = n_clips * n_masks * 2 * sizeof(int32_t);
-        covered = static_cast<size_t>(h_ro[n_clips]) * cols * sizeof(float);
-        inplace = h_out == h_vec;
-        const size_t tbytes = (n_clips + 1) * sizeof(int64_t);
-        hipError_t e = vec.hip_alloc(vbytes);
-        if (e == hipSuccess && !inplace) e = out.hip_alloc(vbytes);
-        if (e == hipSuccess) e = ro.hip_alloc(tbytes);
-        if (e == hipSuccess) e = spans.hip_alloc(sbytes);
-        if (e == hipSuccess && h_rng) e = rng.hip_alloc(16);
-        if (e == hipSuccess && vbytes) e = hipMemcpy(vec.p, h_vec, vbytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(ro.p, h_ro, tbytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && h_spans && sbytes) e = hipMemcpy(spans.p, h_spans, sbytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && h_rng) e = hipMemcpy(rng.p, h_rng, 16, hipMemcpyHostToDevice);
-        return e == hipSuccess ? SS_OK : hip_fail(e, "host staging");
-    }
-    float *d_out() { return inplace ? vec.as<float>() : out.as<float>(); }
-    int down(int rc, const char *what, float *h_out, int32_t *h_spans, uint64_t *h_rng)
-    {
-        if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, std::string(what) + ": device error");
-        if (rc != SS_OK) return rc;
-        hipError_t e = covered ? hipMemcpy(h_out, d_out(), covered, hipMemcpyDeviceToHost) : hipSuccess;
-        if (e == hipSuccess && h_spans && sbytes) e = hipMemcpy(h_spans, spans.p, sbytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && h_rng) e = hipMemcpy(h_rng + 1, rng.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost);
-        return e == hipSuccess ? SS_OK : hip_fail(e, "hipMemcpy D2H");
-    }
-};
-
 }  // namespace
 
 }  // namespace ss
@@ -447,12 +409,18 @@ int ss_mask_spans_packed(const float *vec, size_t n_clips, const int64_t *row_of
         (rc = ss::check_clip_table(row_offsets, n_clips, total_rows)))
         return rc;
     if (!ss::have_device()) return ss::no_device();
-    ss::Staged d;
-    rc = d.up(vec, out, n_clips, row_offsets, total_rows, cols, n_time + n_freq, spans, nullptr);
-    if (rc == SS_OK)
-        rc = ss_mask_spans_packed_device(d.vec.as<const float>(), n_clips, d.ro.as<const int64_t>(), total_rows, cols, d.spans.as<const int32_t>(), n_time, n_freq,
-                                         mask_value, d.d_out(), nullptr);
-    return d.down(rc, "ss_mask_spans_packed", out, nullptr, nullptr);
+    // A checked host table covers rows 0 .. ro[n_clips) without a gap, so exactly those rows come down; the rows behind them are in
+    // no clip and stay as the caller's out holds them.  In place (out == vec) the call runs on one device block.
+    const size_t vbytes = total_rows * cols * sizeof(float), covered = static_cast<size_t>(row_offsets[n_clips]) * cols * sizeof(float);
+    ss::HostStage st("ss_mask_spans_packed");
+    float *d_vec = st.up(vec, vbytes);
+    float *d_out = out == vec ? d_vec : st.room<float>(vbytes);
+    const int64_t *d_ro = st.up(row_offsets, (n_clips + 1) * sizeof(int64_t));
+    const int32_t *d_spans = st.up(spans, n_clips * (n_time + n_freq) * 2 * sizeof(int32_t));
+    if (st.ok()) st.ran(ss_mask_spans_packed_device(d_vec, n_clips, d_ro, total_rows, cols, d_spans, n_time, n_freq, mask_value, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, covered);
+    return st.status();
 }
 
 int ss_specaug_packed(const float *vec, size_t n_clips, const int64_t *row_offsets, size_t total_rows, size_t cols, uint64_t *rng, size_t clip_base, size_t n_time,
@@ -465,12 +433,23 @@ int ss_specaug_packed(const float *vec, size_t n_clips, const int64_t *row_offse
         (rc = ss::check_clip_table(row_offsets, n_clips, total_rows)))
         return rc;
     if (!ss::have_device()) return ss::no_device();
-    ss::Staged d;
-    rc = d.up(vec, out, n_clips, row_offsets, total_rows, cols, n_time + n_freq, nullptr, rng);
-    if (rc == SS_OK)
-        rc = ss_specaug_packed_device(d.vec.as<const float>(), n_clips, d.ro.as<const int64_t>(), total_rows, cols, d.rng.as<uint64_t>(), clip_base, n_time,
-                                      max_time_width, time_ratio, n_freq, max_freq_width, mask_value, d.d_out(), d.spans.as<int32_t>(), nullptr);
-    return d.down(rc, "ss_specaug_packed", out, spans, rng);
+    // as ss_mask_spans_packed; the spans come down here, and of the generator's two words the advanced counter alone
+    const size_t vbytes = total_rows * cols * sizeof(float), covered = static_cast<size_t>(row_offsets[n_clips]) * cols * sizeof(float);
+    const size_t sbytes = n_clips * (n_time + n_freq) * 2 * sizeof(int32_t);
+    ss::HostStage st("ss_specaug_packed");
+    float *d_vec = st.up(vec, vbytes);
+    float *d_out = out == vec ? d_vec : st.room<float>(vbytes);
+    const int64_t *d_ro = st.up(row_offsets, (n_clips + 1) * sizeof(int64_t));
+    int32_t *d_spans = st.room<int32_t>(sbytes);
+    uint64_t *d_rng = st.up(rng, 16);
+    if (st.ok())
+        st.ran(ss_specaug_packed_device(d_vec, n_clips, d_ro, total_rows, cols, d_rng, clip_base, n_time, max_time_width, time_ratio, n_freq, max_freq_width,
+                                        mask_value, d_out, d_spans, nullptr));
+    st.sync();
+    st.down(out, d_out, covered);
+    st.down(spans, d_spans, sbytes);
+    st.down(rng + 1, d_rng + 1, 8);
+    return st.status();
 }
 
 }  // extern "C"

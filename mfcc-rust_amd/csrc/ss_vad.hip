@@ -427,33 +427,19 @@ int stream_via_device(bool flush, const float *vec, size_t n_active, const int64
     if (!have_device()) return no_device();
     PoolRows named;
     named.gather(pool, slots, n_active, len);
-    const size_t bytes = in_rows * sh.cols * sizeof(float), tbytes = (n_active + 1) * sizeof(int64_t), ibytes = n_active * sizeof(int32_t);
-    DeviceBuf d_vec, d_mask, d_ro, d_sl, d_pool;
-    hipError_t e = d_mask.hip_alloc(out_bytes);
-    if (e == hipSuccess) e = d_sl.hip_alloc(ibytes);
-    if (e == hipSuccess) e = d_pool.hip_alloc(named.bytes());
-    if (!flush) {
-        if (e == hipSuccess) e = d_vec.hip_alloc(bytes);
-        if (e == hipSuccess) e = d_ro.hip_alloc(tbytes);
-        if (e == hipSuccess) e = hipMemcpy(d_vec.p, vec, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_ro.p, row_offsets, tbytes, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(d_sl.p, named.iota.data(), ibytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pool.p, named.rows_host.data(), named.bytes(), hipMemcpyHostToDevice);
-    int rc = SS_OK;
-    if (e != hipSuccess) rc = hip_fail(e, "host staging");
-    else if (flush) rc = launch_stream<true>(nullptr, n_active, nullptr, out_bytes, d_sl.as<const int32_t>(), n_active, sh, d_pool.as<float>(), d_mask.as<uint8_t>(), nullptr);
-    else
-        rc = launch_stream<false>(d_vec.as<const float>(), n_active, d_ro.as<const int64_t>(), in_rows, d_sl.as<const int32_t>(), n_active, sh,
-                                  d_pool.as<float>(), d_mask.as<uint8_t>(), nullptr);
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_vad_energy_stream: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(named.rows_host.data(), d_pool.p, named.bytes(), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && out_bytes) e = hipMemcpy(mask, d_mask.p, out_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy D2H");
-    }
-    if (rc == SS_OK) named.scatter(pool, slots);
-    return rc;
+    HostStage st("ss_vad_energy_stream");
+    uint8_t *d_mask = st.room<uint8_t>(out_bytes);
+    const auto d_named = st.up_pool(named);
+    const float *d_vec = flush ? nullptr : st.up(vec, in_rows * sh.cols * sizeof(float));
+    const int64_t *d_ro = flush ? nullptr : st.up(row_offsets, (n_active + 1) * sizeof(int64_t));
+    if (st.ok())
+        st.ran(flush ? launch_stream<true>(nullptr, n_active, nullptr, out_bytes, d_named.slots, n_active, sh, d_named.rows, d_mask, nullptr)
+                     : launch_stream<false>(d_vec, n_active, d_ro, in_rows, d_named.slots, n_active, sh, d_named.rows, d_mask, nullptr));
+    st.sync();
+    st.down_pool(named, d_named);
+    st.down(mask, d_mask, out_bytes);
+    st.scatter(named, pool, slots);
+    return st.status();
 }
 
 }  // namespace
@@ -499,25 +485,19 @@ int ss_vad_energy_packed(const float *vec, size_t n_clips, const int64_t *offset
         return SS_OK;
     }
     if (!ss::have_device()) return ss::no_device();
-    const size_t bytes = rows * cols * sizeof(float), tbytes = (n_clips + 1) * sizeof(int64_t), cbytes = n_clips * sizeof(int64_t);
-    ss::DeviceBuf d_in, d_mask, d_off, d_cnt;
-    hipError_t e = d_in.hip_alloc(bytes);
-    if (e == hipSuccess) e = d_mask.hip_alloc(rows);
-    if (e == hipSuccess) e = d_off.hip_alloc(tbytes);
-    if (e == hipSuccess) e = d_cnt.hip_alloc(cbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in.p, vec, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_off.p, offsets, tbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? ss_vad_energy_packed_device(d_in.as<const float>(), n_clips, d_off.as<const int64_t>(), rows, cols, energy_col, energy_threshold,
-                                                       energy_mean_scale, frames_context, proportion_threshold, d_mask.as<uint8_t>(),
-                                                       counts ? d_cnt.as<int64_t>() : nullptr, nullptr)
-                         : ss::hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_vad_energy_packed: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(mask, d_mask.p, rows, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && counts) e = hipMemcpy(counts, d_cnt.p, cbytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = ss::hip_fail(e, "hipMemcpy D2H");
-    }
-    return rc;
+    const size_t cbytes = n_clips * sizeof(int64_t);
+    ss::HostStage st("ss_vad_energy_packed");
+    const float *d_in = st.up(vec, rows * cols * sizeof(float));
+    uint8_t *d_mask = st.room<uint8_t>(rows);
+    const int64_t *d_off = st.up(offsets, (n_clips + 1) * sizeof(int64_t));
+    int64_t *d_cnt = st.room<int64_t>(cbytes);
+    if (st.ok())
+        st.ran(ss_vad_energy_packed_device(d_in, n_clips, d_off, rows, cols, energy_col, energy_threshold, energy_mean_scale, frames_context,
+                                           proportion_threshold, d_mask, counts ? d_cnt : nullptr, nullptr));
+    st.sync();
+    st.down(mask, d_mask, rows);
+    if (counts) st.down(counts, d_cnt, cbytes);
+    return st.status();
 }
 
 int ss_select_rows_packed_device(const float *d_vec, size_t n_clips, const int64_t *d_row_offsets, size_t total_rows, size_t cols, const uint8_t *d_mask,
@@ -567,26 +547,18 @@ int ss_select_rows_packed(const float *vec, size_t n_clips, const int64_t *row_o
     if (!ss::have_device()) return ss::no_device();
     const size_t bytes = rows * cols * sizeof(float), tbytes = (n_clips + 1) * sizeof(int64_t);
     std::vector<int64_t> oo(n_clips + 1);
-    ss::DeviceBuf d_in, d_out, d_mask, d_ro, d_oo;
-    hipError_t e = d_in.hip_alloc(bytes);
-    if (e == hipSuccess) e = d_out.hip_alloc(bytes);
-    if (e == hipSuccess) e = d_mask.hip_alloc(rows);
-    if (e == hipSuccess) e = d_ro.hip_alloc(tbytes);
-    if (e == hipSuccess) e = d_oo.hip_alloc(tbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in.p, vec, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_mask.p, mask, rows, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_ro.p, row_offsets, tbytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? ss_select_rows_packed_device(d_in.as<const float>(), n_clips, d_ro.as<const int64_t>(), rows, cols, d_mask.as<const uint8_t>(),
-                                                        d_oo.as<int64_t>(), d_out.as<float>(), nullptr)
-                         : ss::hip_fail(e, "host staging");
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = ss::fail(SS_ERR_HIP, "ss_select_rows_packed: device error");
-    if (rc == SS_OK) {
-        e = hipMemcpy(oo.data(), d_oo.p, tbytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && oo[n_clips] > 0) e = hipMemcpy(out, d_out.p, static_cast<size_t>(oo[n_clips]) * cols * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = ss::hip_fail(e, "hipMemcpy D2H");
-    }
-    if (rc == SS_OK) std::copy(oo.begin(), oo.end(), out_offsets);
-    return rc;
+    ss::HostStage st("ss_select_rows_packed");
+    const float *d_in = st.up(vec, bytes);
+    float *d_out = st.room<float>(bytes);
+    const uint8_t *d_mask = st.up(mask, rows);
+    const int64_t *d_ro = st.up(row_offsets, tbytes);
+    int64_t *d_oo = st.room<int64_t>(tbytes);
+    if (st.ok()) st.ran(ss_select_rows_packed_device(d_in, n_clips, d_ro, rows, cols, d_mask, d_oo, d_out, nullptr));
+    st.sync();
+    st.down(oo.data(), d_oo, tbytes);  // the output table first: it says how many rows come down
+    if (st.ok()) st.down(out, d_out, static_cast<size_t>(oo[n_clips]) * cols * sizeof(float));
+    if (st.ok()) std::copy(oo.begin(), oo.end(), out_offsets);
+    return st.status();
 }
 
 int ss_vad_energy_stream_state_len(size_t frames_context, size_t *state_len)

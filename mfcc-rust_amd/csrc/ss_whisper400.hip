@@ -605,17 +605,14 @@ int ss_whisper_log_mel(const ss_whisper_config *cfg, const float *x, size_t batc
     if (ld < n_samples) return fail(SS_ERR_ARG, "ld must be at least n_samples");
     if (!ss::have_device()) return ss::no_device("hot path");
     const size_t in_floats = (batch - 1) * ld + n_samples, block = batch * cfg->params.n_mels * n_frames;
-    ss::DeviceBuf d_in, d_out, d_work;
-    hipError_t e = d_in.hip_alloc(in_floats * sizeof(float));
-    if (e == hipSuccess) e = d_out.hip_alloc(block * elem_bytes(dtype));
-    if (e == hipSuccess && dtype != SS_PAD_F32) e = d_work.hip_alloc(block * sizeof(float));
-    if (e == hipSuccess && in_floats) e = hipMemcpy(d_in.p, x, in_floats * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail(e, "host staging");
-    int rc = ss_whisper_log_mel_device(cfg, d_in.as<const float>(), batch, n_samples, ld, n_frames, dtype, d_work.p, d_out.p, nullptr);
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_whisper_log_mel: device error");
-    if (rc != SS_OK) return rc;
-    e = hipMemcpy(out, d_out.p, block * elem_bytes(dtype), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? SS_OK : hip_fail(e, "hipMemcpy D2H");
+    ss::HostStage st("ss_whisper_log_mel");
+    const float *d_in = st.up(x, in_floats * sizeof(float));
+    void *d_out = st.room<void>(block * elem_bytes(dtype));
+    void *d_work = dtype != SS_PAD_F32 ? st.room<void>(block * sizeof(float)) : nullptr;
+    if (st.ok()) st.ran(ss_whisper_log_mel_device(cfg, d_in, batch, n_samples, ld, n_frames, dtype, d_work, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, block * elem_bytes(dtype));
+    return st.status();
 }
 
 int ss_whisper_log_mel_packed(const ss_whisper_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, size_t n_frames, int dtype, void *out,
@@ -632,23 +629,17 @@ int ss_whisper_log_mel_packed(const ss_whisper_config *cfg, const float *x, size
         if (sample_offsets[b] >= 0 && sample_offsets[b + 1] >= sample_offsets[b] && sample_offsets[b + 1] > top) top = sample_offsets[b + 1];
     if (!ss::have_device()) return ss::no_device("hot path");
     const size_t in_floats = static_cast<size_t>(top), block = n_clips * cfg->params.n_mels * n_frames;
-    ss::DeviceBuf d_in, d_out, d_work, d_so, d_len;
-    hipError_t e = d_in.hip_alloc(in_floats * sizeof(float));
-    if (e == hipSuccess) e = d_out.hip_alloc(block * elem_bytes(dtype));
-    if (e == hipSuccess && dtype != SS_PAD_F32) e = d_work.hip_alloc(block * sizeof(float));
-    if (e == hipSuccess) e = d_so.hip_alloc((n_clips + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = d_len.hip_alloc(n_clips * sizeof(int32_t));
-    if (e == hipSuccess && in_floats) e = hipMemcpy(d_in.p, x, in_floats * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_so.p, sample_offsets, (n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail(e, "host staging");
-    int rc = ss_whisper_log_mel_packed_device(cfg, d_in.as<const float>(), n_clips, d_so.as<const int64_t>(), n_frames, dtype, d_work.p, d_out.p,
-                                              d_len.as<int32_t>(), nullptr);
-    if (rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SS_ERR_HIP, "ss_whisper_log_mel_packed: device error");
-    if (rc != SS_OK) return rc;
-    e = hipMemcpy(out, d_out.p, block * elem_bytes(dtype), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && lengths) e = hipMemcpy(lengths, d_len.p, n_clips * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
-    return whisper_pending_error(cfg);
+    ss::HostStage st("ss_whisper_log_mel_packed");
+    const float *d_in = st.up(x, in_floats * sizeof(float));
+    void *d_out = st.room<void>(block * elem_bytes(dtype));
+    void *d_work = dtype != SS_PAD_F32 ? st.room<void>(block * sizeof(float)) : nullptr;
+    const int64_t *d_so = st.up(sample_offsets, (n_clips + 1) * sizeof(int64_t));
+    int32_t *d_len = st.room<int32_t>(n_clips * sizeof(int32_t));
+    if (st.ok()) st.ran(ss_whisper_log_mel_packed_device(cfg, d_in, n_clips, d_so, n_frames, dtype, d_work, d_out, d_len, nullptr));
+    st.sync();
+    st.down(out, d_out, block * elem_bytes(dtype));
+    if (lengths) st.down(lengths, d_len, n_clips * sizeof(int32_t));
+    return st.ok() ? whisper_pending_error(cfg) : st.status();
 }
 
 }  // extern "C"
