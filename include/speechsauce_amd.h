@@ -1014,6 +1014,53 @@ int ss_splice_stream_flush_device(size_t n_active, const int32_t *d_slots, size_
 int ss_splice_stream_flush(size_t n_active, const int32_t *slots, size_t pool_streams, size_t cols, size_t left, size_t right,
                            size_t stride, float *pool, float *out);
 
+/* ---- fused splice + affine transform of packed rows (Kaldi splice-feats | transform-feats) ----
+ * The matrix product that always follows the splice stage -- an LDA / LDA+MLLT matrix (40 x (7 * 13), 40 x (11 * 40 + 1)), the
+ * linear input projection of a low-frame-rate front end, a PCA / whitening matrix, a global CMVN folded into a diagonal affine --
+ * applied to the spliced row WITHOUT the spliced block ever being written: the rows are read once and out_dim floats per output
+ * row are stored.  The reference crate has none: this comment is the specification.
+ *   For every served clip b and output row k < ceil(T_b / stride): s_k is the spliced row ss_splice_packed* defines (rows k * stride
+ *   - left .. k * stride + right of the clip side by side, clamped to the clip's own first and last row), K = (left + 1 + right) *
+ *   cols its length, K4 = 4 * ceil(K / 4).  Output element i < out_dim of the row is the strict serial chain
+ *       acc = bias[i]   (+0.0f without a bias);   for k = 0, 1, .., K4 - 1 ascending: acc = fmaf(M[i][k], s[k], acc);   out = acc
+ *   in f32, one rounding per step, where BOTH factors are +0.0f for K <= k < K4.  The pad steps belong to the contract: fmaf(+0, +0,
+ *   -0.0) is +0.0, so they are not invisible.  One accumulator per output element runs through all of k; K is never split across
+ *   accumulators, lanes or waves.  So a row's bits are a pure function of its clip's rows, the matrix and the scalars -- not of
+ *   its place in the block or the launch shape -- and a NaN / Inf in a row reaches exactly the outputs whose context holds that
+ *   row.  (v_mfma_f32_16x16x4_f32 of gfx950 is this chain, four steps per instruction.)
+ * The handle (ss_affine): ss_affine_create takes the matrix row-major [out_dim x in_dim] with row pitch ld >= in_dim floats and a
+ * bias [out_dim] or NULL, re-lays it into the kernel's operand order and keeps that copy; the caller's arrays are not needed
+ * afterwards.  Creation needs no device.  Limits: 1 <= out_dim <= 256 and 1 <= in_dim <= 4096, anything else is SS_ERR_UNSUPPORTED
+ * (checked first, without a device); a null matrix, a null `out` or ld < in_dim is SS_ERR_ARG.  The first device call uploads the
+ * table, once, to the device that is current then (a later call under another current device is SS_ERR_ARG); after that warm call
+ * nothing is allocated or copied inside a launch.  A handle may be used from several threads / streams concurrently.
+ * ss_affine_dims reports (out_dim, in_dim); ss_affine_chain_len (host only) is K4 for an in_dim inside the limit.
+ * Packed clips (ss_affine_splice_packed*): vec is [total_rows x cols], clip b owns rows ro[b] .. ro[b+1]; out is [total_out_rows x
+ * out_dim], clip b owns rows oo[b] .. oo[b+1].  Everything else is ss_splice_packed*'s: both tables are device arrays of n_clips +
+ * 1 entries that only the kernel reads (ss_splice_packed_offsets forms oo; oo may be the same array as ro when stride == 1); a
+ * clip is served iff 0 <= ro[b] <= ro[b+1] <= total_rows, oo[b] >= 0, oo[b+1] - oo[b] == ceil((ro[b+1] - ro[b]) / stride) and
+ * oo[b+1] <= total_out_rows; any other clip is skipped whole.  Nothing outside the two blocks is read or written; rows in no served
+ * clip stay unwritten.  The clip of an output row is looked up in oo, which therefore must not decrease across the served clips (the
+ * tables of ss_splice_packed_offsets, of ss_select_rows_packed_device and a pool tick's row_offsets are valid as they stand; with
+ * left = right = 0 and stride = 1 the call is plain transform-feats on any packed rows, e.g. behind ss_splice_stream_packed*).
+ * One launch (ss_affine_splice_kernel) whose grid depends on total_out_rows, out_dim and in_dim only, asynchronous on `stream`, no
+ * allocation, no read-back, no scratch: graph-capturable after the warm call and replayable over changed table contents.
+ * n_clips == 0 is SS_OK without a device.  SS_ERR_ARG, decided before the device is touched: null buffers or handle; cols == 0; left
+ * or right outside [0, 32], stride outside [1, 32]; n_clips, total_rows, total_out_rows, cols or W * cols >= 2^31; in_dim != (left +
+ * 1 + right) * cols; out overlapping vec.  The host form takes row_offsets alone and forms oo itself; it checks the table first and
+ * names the first bad clip (the rules of ss_splice_packed) and writes the rows the table covers. */
+typedef struct ss_affine ss_affine; /* opaque: the matrix in operand order and, after the first device call, its device copy */
+int ss_affine_create(const float *matrix, size_t out_dim, size_t in_dim, size_t ld, const float *bias_or_null, ss_affine **out);
+void ss_affine_destroy(ss_affine *t);
+int ss_affine_dims(const ss_affine *t, size_t *out_dim, size_t *in_dim);
+/* host only, no device: k4 = 4 * ceil(in_dim / 4) */
+int ss_affine_chain_len(size_t in_dim, size_t *k4);
+int ss_affine_splice_packed_device(const ss_affine *t, const float *d_vec, size_t n_clips, const int64_t *d_row_offsets,
+                                   size_t total_rows, const int64_t *d_out_offsets, size_t total_out_rows, size_t cols, size_t left,
+                                   size_t right, size_t stride, float *d_out, void *stream);
+int ss_affine_splice_packed(const ss_affine *t, const float *vec, size_t n_clips, const int64_t *row_offsets, size_t total_rows,
+                            size_t cols, size_t left, size_t right, size_t stride, float *out);
+
 /* ---- energy voice-activity decision and voiced-row selection on packed clips and over a pool of stream states ----
  * The two stages a speaker-recognition front end (x-vector / i-vector recipes, diarisation) takes behind the feature rows: Kaldi's
  * compute-vad-energy, a per-frame speech / non-speech decision from the log-energy column, and select-voiced-frames, which drops

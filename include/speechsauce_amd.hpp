@@ -652,6 +652,47 @@ inline std::vector<float> splice_packed(const std::vector<float> &vec, const std
     return out;
 }
 
+// An affine transform [out_dim x in_dim] (+ bias) applied behind the splice stage without the spliced block ever being written
+// (ss_affine_*, ss_affine_splice_packed; not in the reference crate): Kaldi's splice-feats | transform-feats.  The handle is shared
+// by copies; the first call that runs uploads the matrix.
+class Affine {
+public:
+    // matrix: row-major [out_dim x in_dim] (1 .. 256 by 1 .. 4096); bias: empty, or [out_dim]
+    Affine(const std::vector<float> &matrix, size_t out_dim, size_t in_dim, const std::vector<float> &bias = {}) : out_dim_(out_dim), in_dim_(in_dim)
+    {
+        if (matrix.size() != out_dim * in_dim || (!bias.empty() && bias.size() != out_dim)) throw Error(SS_ERR_ARG, "Affine: shape mismatch");
+        ss_affine *raw = nullptr;
+        check(ss_affine_create(matrix.data(), out_dim, in_dim, in_dim, bias.empty() ? nullptr : bias.data(), &raw));
+        h_ = std::shared_ptr<ss_affine>(raw, ss_affine_destroy);
+    }
+    const ss_affine *handle() const { return h_.get(); }
+    size_t out_dim() const { return out_dim_; }
+    size_t in_dim() const { return in_dim_; }
+    // 4 * ceil(in_dim / 4): the steps of every output element's fmaf chain
+    size_t chain_len() const
+    {
+        size_t k4 = 0;
+        check(ss_affine_chain_len(in_dim_, &k4));
+        return k4;
+    }
+    // splice_packed followed by the transform, in one launch: ceil(T_b / stride) rows of out_dim floats per clip, in the clips' order;
+    // in_dim must be (left + 1 + right) * cols.  left = right = 0, stride = 1 is transform-feats.  A dense matrix: offsets = {0, rows}
+    std::vector<float> splice_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t left, size_t right,
+                                     size_t stride = 1) const
+    {
+        if (cols == 0 || vec.size() % cols || offsets.empty() || left > 32 || right > 32) throw Error(SS_ERR_ARG, "Affine::splice_packed: shape mismatch");
+        std::vector<int64_t> out_offsets(offsets.size());
+        check(ss_splice_packed_offsets(offsets.size() - 1, offsets.data(), stride, out_offsets.data()));
+        std::vector<float> out(static_cast<size_t>(out_offsets.back()) * out_dim_);
+        check(ss_affine_splice_packed(h_.get(), vec.data(), offsets.size() - 1, offsets.data(), vec.size() / cols, cols, left, right, stride, out.data()));
+        return out;
+    }
+
+private:
+    std::shared_ptr<ss_affine> h_;
+    size_t out_dim_, in_dim_;
+};
+
 // Kaldi compute-vad-energy of every clip of a packed block on its own rows (ss_vad_energy_packed): one byte 0 / 1 per row, and (where
 // `counts` is given) the voiced rows of every clip.  The defaults are Kaldi's; the x-vector recipes use 5.5 / 0.5 / 2 / 0.12.  A dense
 // matrix: offsets = {0, rows}

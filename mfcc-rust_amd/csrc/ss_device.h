@@ -844,4 +844,26 @@ hipError_t launch_kaldi_c256_varlen(const KaldiArgs &a, const KaldiVarlenArgs &v
 hipError_t launch_kaldi_c256_stream_packed(const KaldiArgs &a, const FrameStreamPackedPcmArgs &sp, bool pcm, hipStream_t stream, int num_cus,
                                            LaunchInfo *info);
 
+// The fused splice + affine transform of packed rows (ss_affine.hip; ss_affine_splice_packed*): out[g] = M * (spliced row g) + bias
+// on the f32 matrix instruction.  x / ro and out / oo are the two packed blocks and their tables as ss_splice_packed_device takes
+// them (total_rows, total_out_rows, n_clips < 2^31).  table: the handle's device block -- the bias padded with zeros to bias_len =
+// 16 * (feature tiles) floats, then the matrix in operand order [feature tile][group][lane][4]: steps = ceil(in_dim / 4) k-steps in
+// groups = ceil(steps / 4) groups of four, a lane's four values of a group side by side.
+struct AffineArgs {
+    const float *x;
+    const long long *ro, *oo;
+    const float *table;
+    float *out;
+    unsigned long long total_rows, total_out_rows;
+    uint32_t n_clips;
+    uint32_t cols, left, stride;
+    uint32_t width;             // left + 1 + right
+    uint32_t step_c, step_col;  // n / cols, n % cols: how (context row, column) moves on by n elements (vec4: 16, else 4)
+    uint32_t steps, groups, bias_len, out_dim;
+    int32_t vec4;               // cols % 4 == 0 and x is 16-byte aligned: a lane loads four elements of a spliced row at once
+    int32_t store16;            // out_dim % 4 == 0 and out is 16-byte aligned: a lane's four features go out as one store
+};
+// one launch; the grid depends on total_out_rows, out_dim and in_dim only
+hipError_t launch_affine_splice(const AffineArgs &a, hipStream_t stream);
+
 }  // namespace ss

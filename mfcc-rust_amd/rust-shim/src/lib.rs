@@ -249,6 +249,15 @@ extern "C" {
                                  pool_streams: usize, pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_resample_stream_flush(rs: *const c_void, n_active: usize, slots: *const i32, pool_streams: usize, pool: *mut f32,
                                 out: *mut f32) -> c_int;
+    fn ss_affine_create(matrix: *const f32, out_dim: usize, in_dim: usize, ld: usize, bias_or_null: *const f32, out: *mut *mut c_void) -> c_int;
+    fn ss_affine_destroy(t: *mut c_void);
+    fn ss_affine_dims(t: *const c_void, out_dim: *mut usize, in_dim: *mut usize) -> c_int;
+    fn ss_affine_chain_len(in_dim: usize, k4: *mut usize) -> c_int;
+    fn ss_affine_splice_packed_device(t: *const c_void, d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize,
+                                      d_out_offsets: *const i64, total_out_rows: usize, cols: usize, left: usize, right: usize, stride: usize,
+                                      d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_affine_splice_packed(t: *const c_void, vec: *const f32, n_clips: usize, row_offsets: *const i64, total_rows: usize, cols: usize,
+                               left: usize, right: usize, stride: usize, out: *mut f32) -> c_int;
     fn ss_kaldi_params_default(p: *mut KaldiParams, sample_rate: u32) -> c_int;
     fn ss_kaldi_num_frames(p: *const KaldiParams, n_samples: usize, n_frames: *mut usize) -> c_int;
     fn ss_kaldi_packed_frame_offsets(p: *const KaldiParams, n_clips: usize, sample_offsets: *const i64, frame_offsets: *mut i64) -> c_int;
@@ -1851,6 +1860,77 @@ pub struct ResampleInfo {
     pub lookahead: u32,
     pub latency_periods: u32,
     pub tile_outputs: u32,
+}
+
+/// An affine transform `[out_dim x in_dim]` (+ bias) applied behind the splice stage without the spliced block ever being written:
+/// Kaldi's `splice-feats | transform-feats` (LDA / LDA+MLLT), a PCA matrix, the input projection of a low-frame-rate front end.  Not in
+/// the reference crate.  Owns an `ss_affine`; the matrix is uploaded by the first call that runs.
+pub struct Affine {
+    raw: *mut c_void,
+}
+
+unsafe impl Send for Affine {}
+unsafe impl Sync for Affine {}
+
+impl Drop for Affine {
+    fn drop(&mut self) {
+        unsafe { ss_affine_destroy(self.raw) }
+    }
+}
+
+impl Affine {
+    /// `matrix`: row-major `[out_dim x in_dim]` (1 ..= 256 by 1 ..= 4096); `bias`: `[out_dim]`.
+    pub fn new(matrix: &[f32], out_dim: usize, in_dim: usize, bias: Option<&[f32]>) -> Result<Affine, Error> {
+        if matrix.len() != out_dim * in_dim || bias.map_or(false, |b| b.len() != out_dim) {
+            return Err(Error { status: SS_ERR_ARG, detail: "matrix must be out_dim * in_dim floats, bias out_dim".to_string() });
+        }
+        let mut raw: *mut c_void = std::ptr::null_mut();
+        let b = bias.map_or(std::ptr::null(), |b| b.as_ptr());
+        check(unsafe { ss_affine_create(matrix.as_ptr(), out_dim, in_dim, in_dim, b, &mut raw) })?;
+        Ok(Affine { raw })
+    }
+
+    /// `(out_dim, in_dim)`
+    pub fn dims(&self) -> Result<(usize, usize), Error> {
+        let (mut o, mut i) = (0usize, 0usize);
+        check(unsafe { ss_affine_dims(self.raw, &mut o, &mut i) })?;
+        Ok((o, i))
+    }
+
+    /// `4 * ceil(in_dim / 4)`: the steps of every output element's fmaf chain.
+    pub fn chain_len(&self) -> Result<usize, Error> {
+        let mut k4 = 0usize;
+        check(unsafe { ss_affine_chain_len(self.dims()?.1, &mut k4) })?;
+        Ok(k4)
+    }
+
+    /// Clips packed end to end (clip b = rows `row_offsets[b] .. row_offsets[b + 1]` of `vec [total_rows x cols]`) -> the block
+    /// `[sum ceil(T_b / stride) x out_dim]`: row k of a clip is the transform of its rows `k * stride - left ..= k * stride + right`
+    /// side by side, clamped to the clip.  `in_dim` must be `(left + 1 + right) * cols`.
+    pub fn splice_packed(&self, vec: &[f32], row_offsets: &[i64], cols: usize, left: usize, right: usize, stride: usize) -> Result<Vec<f32>, Error> {
+        if row_offsets.is_empty() || cols == 0 || stride == 0 || vec.len() % cols != 0 {
+            return Err(Error { status: SS_ERR_ARG, detail: "splice_packed: shape mismatch".to_string() });
+        }
+        let s = stride as i64;
+        let out_rows: i64 = row_offsets.windows(2).map(|w| if w[1] > w[0] { (w[1] - w[0] + s - 1) / s } else { 0 }).sum();
+        let mut out = vec![0f32; out_rows as usize * self.dims()?.0];
+        check(unsafe {
+            ss_affine_splice_packed(self.raw, vec.as_ptr(), row_offsets.len() - 1, row_offsets.as_ptr(), vec.len() / cols, cols, left, right, stride,
+                                    out.as_mut_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// The device form on device pointers (`d_out_offsets`: `ss_splice_packed_offsets` of the row offsets); asynchronous on `stream`.
+    ///
+    /// # Safety
+    /// Every pointer is a device pointer to a block of the size the header states.
+    pub unsafe fn splice_packed_device(&self, d_vec: *const f32, n_clips: usize, d_row_offsets: *const i64, total_rows: usize, d_out_offsets: *const i64,
+                                       total_out_rows: usize, cols: usize, left: usize, right: usize, stride: usize, d_out: *mut f32,
+                                       stream: *mut c_void) -> Result<(), Error> {
+        check(ss_affine_splice_packed_device(self.raw, d_vec, n_clips, d_row_offsets, total_rows, d_out_offsets, total_out_rows, cols, left, right,
+                                             stride, d_out, stream))
+    }
 }
 
 /// Polyphase windowed-sinc resampler for one pair of rates: torchaudio's default `sinc_interp_hann` filter (`lowpass_filter_width = 6`,

@@ -29,6 +29,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "MfccStream", "MfeStream", "MfccStreamPool", "MfeStreamPool", "MelSpectrogramStreamPool", "StftStreamPool", "CmvnStreamPool",
            "add_deltas", "add_deltas_packed", "AddDeltasStreamPool",
            "splice", "splice_packed", "lfr", "lfr_packed", "SpliceStreamPool",
+           "Affine", "splice_affine", "splice_affine_packed", "transform_feats_packed",
            "vad_energy", "vad_energy_packed", "select_rows", "select_rows_packed", "VadEnergyStreamPool",
            "pad", "pad_packed",
            "spec_augment_spans", "mask_spans_packed", "spec_augment_packed", "SpecAugment",
@@ -2197,6 +2198,124 @@ def lfr_packed(rows, row_offsets, m, n):
 def lfr(x, m, n):
     """Low frame rate of one matrix or a batch: ``splice`` with ``left = (m - 1) // 2, right = m - 1 - left, stride = n``."""
     return splice(x, *_lfr_params(m, n, "lfr"))
+
+
+# ---- fused splice + affine transform (Kaldi's splice-feats | transform-feats; ss_affine_* / ss_affine_splice_packed*) ---------
+# out row k = M @ (the spliced row k) + bias, one serial f32 fmaf chain per element; the spliced block is never written.
+
+class Affine:
+    """Owns an ``ss_affine`` handle: a matrix ``[out_dim, in_dim]`` (1 <= out_dim <= 256, 1 <= in_dim <= 4096) and an optional bias
+    ``[out_dim]``, re-laid into the kernel's operand order at creation and -- after the first device call -- its device copy.  The
+    arrays handed in are not kept."""
+
+    def __init__(self, matrix, bias=None):
+        m = np.ascontiguousarray(_affine_host(matrix, "Affine: matrix"), dtype=np.float32)
+        if m.ndim != 2:
+            raise ValueError("Affine: the matrix must be [out_dim, in_dim]")
+        b = None
+        if bias is not None:
+            b = np.ascontiguousarray(_affine_host(bias, "Affine: bias"), dtype=np.float32)
+            if b.shape != (m.shape[0],):
+                raise ValueError(f"Affine: the bias must have out_dim = {m.shape[0]} entries")
+        self._h = C.c_void_p()
+        self._owner = _lib.lib()  # the build that created the handle destroys it
+        _lib.check(self._owner.ss_affine_create(m.ctypes.data, m.shape[0], m.shape[1], m.shape[1], b.ctypes.data if b is not None else None,
+                                                C.byref(self._h)))
+        self.out_dim, self.in_dim = int(m.shape[0]), int(m.shape[1])
+
+    @classmethod
+    def from_kaldi(cls, mat, in_dim=None):
+        """A Kaldi transform matrix as ``transform-feats`` reads it.  ``in_dim`` is the length of the rows it will meet (the spliced
+        row): a matrix of ``in_dim`` columns is linear, one of ``in_dim + 1`` columns carries the offset in its LAST column (Kaldi's
+        affine convention).  Without ``in_dim`` the matrix is taken as linear."""
+        m = np.asarray(_affine_host(mat, "Affine.from_kaldi"), dtype=np.float32)
+        if m.ndim != 2:
+            raise ValueError("Affine.from_kaldi: the matrix must be 2-D")
+        k = m.shape[1] if in_dim is None else int(in_dim)
+        if m.shape[1] == k:
+            return cls(m)
+        if m.shape[1] == k + 1:
+            return cls(m[:, :k], m[:, k])
+        raise ValueError(f"Affine.from_kaldi: the matrix has {m.shape[1]} columns, rows of {k} take {k} (linear) or {k + 1} (affine)")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                self._owner.ss_affine_destroy(h)
+            except Exception:
+                pass
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    @property
+    def chain_len(self) -> int:
+        """K4 = 4 * ceil(in_dim / 4): the steps of every output element's fmaf chain."""
+        k4 = C.c_size_t()
+        _lib.check(self._owner.ss_affine_chain_len(self.in_dim, C.byref(k4)))
+        return int(k4.value)
+
+
+def _affine_host(a, what):
+    if _is_torch(a):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise TypeError(f"{what}: expected float32, got {a.dtype}")
+    return a
+
+
+def splice_affine_packed(rows, row_offsets, transform: Affine, left, right, stride=1):
+    """``splice_packed`` followed by ``transform`` (an ``Affine`` of ``in_dim = (left + 1 + right) * cols``) in one launch, the
+    spliced block never written: -> (out [sum ceil(T_b / stride), out_dim], out_offsets).  Element i of an output row is the serial
+    f32 chain ``acc = bias[i]; acc = fmaf(M[i][k], s[k], acc)`` over the spliced row s, k ascending (``ss_affine_splice_packed`` in
+    ``include/speechsauce_amd.h``).  numpy in -> the host-pointer call; a ROCm tensor stays on the device (current stream).
+    ``row_offsets`` as for ``splice_packed``."""
+    what = "splice_affine_packed"
+    if not isinstance(transform, Affine):
+        raise TypeError(f"{what}: transform must be an Affine")
+    left, right, stride = _check_splice_params(left, right, stride, what)
+    lib = _lib.lib()
+    x, on_device, total_rows, cols = _packed_block(rows, None, what)
+    if (left + 1 + right) * cols != transform.in_dim:
+        raise ValueError(f"{what}: the transform takes {transform.in_dim} inputs, a spliced row has {(left + 1 + right) * cols}")
+    ro, n = _segment_table(row_offsets, False, None, total_rows, what)  # on the host, validated
+    oo = np.empty_like(ro)
+    _lib.check(lib.ss_splice_packed_offsets(n, ro.ctypes.data, stride, oo.ctypes.data))
+    out_rows = int(oo[-1])
+    if on_device:
+        import torch
+
+        out = torch.empty((out_rows, transform.out_dim), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            d_ro, d_oo = torch.from_numpy(ro).to(x.device), torch.from_numpy(oo).to(x.device)
+            _lib.check(lib.ss_affine_splice_packed_device(transform.handle, x.data_ptr(), n, d_ro.data_ptr(), total_rows, d_oo.data_ptr(), out_rows,
+                                                          cols, left, right, stride, out.data_ptr(), _stream_ptr()))
+            for t in (x, d_ro, d_oo):  # the launch is asynchronous: keep the temporaries until the stream has passed them
+                t.record_stream(torch.cuda.current_stream())
+        return out, d_oo
+    out = np.empty((out_rows, transform.out_dim), dtype=np.float32)
+    _lib.check(lib.ss_affine_splice_packed(transform.handle, x.ctypes.data, n, ro.ctypes.data, total_rows, cols, left, right, stride, out.ctypes.data))
+    return out, oo
+
+
+def splice_affine(x, transform: Affine, left, right, stride=1):
+    """``splice_affine_packed`` of one matrix [T, cols] -> [ceil(T / stride), out_dim], or of every matrix of a batch [..., T, cols]
+    on its own rows (equal-length clips of one packed block, one launch)."""
+    x = _require_f32(x, tuple(range(2, 9)), "splice_affine")
+    shape = tuple(int(v) for v in x.shape)
+    T, cols = shape[-2], shape[-1]
+    n = int(np.prod(shape[:-2], dtype=np.int64))
+    out, _ = splice_affine_packed(x.reshape(n * T, cols), np.arange(n + 1, dtype=np.int64) * T, transform, left, right, stride)
+    return out.reshape(shape[:-2] + (-(-T // int(stride)), out.shape[1]))
+
+
+def transform_feats_packed(rows, row_offsets, transform: Affine):
+    """Kaldi's ``transform-feats`` on packed rows: ``splice_affine_packed`` without context (``left = right = 0, stride = 1``), e.g.
+    behind ``SpliceStreamPool`` on a tick's rows.  -> out [total_rows, out_dim]."""
+    return splice_affine_packed(rows, row_offsets, transform, 0, 0, 1)[0]
 
 
 class SpliceStreamPool(_SidePool):

@@ -110,6 +110,7 @@ _lib = None
 _P = C.POINTER
 _cfg = C.c_void_p
 _rs = C.c_void_p  # ss_resampler *
+_af = C.c_void_p  # ss_affine *
 _kc = C.c_void_p  # ss_kaldi_config *
 _wc = C.c_void_p  # ss_whisper_config *
 _fp = C.c_void_p  # float* passed as an address (numpy .ctypes.data or a device pointer)
@@ -273,6 +274,13 @@ PROTOTYPES = {
     "ss_splice_stream_flush_device": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp,
                                                 C.c_void_p]),
     "ss_splice_stream_flush": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _fp]),
+    "ss_affine_create": (C.c_int, [_fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp, _P(_af)]),
+    "ss_affine_destroy": (None, [_af]),
+    "ss_affine_dims": (C.c_int, [_af, _P(C.c_size_t), _P(C.c_size_t)]),
+    "ss_affine_chain_len": (C.c_int, [C.c_size_t, _P(C.c_size_t)]),
+    "ss_affine_splice_packed_device": (C.c_int, [_af, _fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                 C.c_size_t, C.c_size_t, _fp, C.c_void_p]),
+    "ss_affine_splice_packed": (C.c_int, [_af, _fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _fp]),
     "ss_vad_energy_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_size_t,
                                               C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ss_vad_energy_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_size_t, C.c_float,
