@@ -44,23 +44,40 @@ def _is_torch(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
 
 
-class SpeechConfig:
-    """Owns an ``ss_config`` handle: the counterpart of ``PySpeechSauce(SpeechConfig)``
-    (py-speechsauce/src/lib.rs:7-10; speechsauce/src/config.rs:99-185)."""
+class _Handle:
+    """What the owners of a handle of the C ABI share: the handle ``_h`` (null until the class's create call has filled it), the
+    build ``_owner`` that creates it and therefore destroys it (tests run the front on the lab build too), and its release through
+    the entry point ``_destroy`` names."""
 
-    def __init__(self, params: SsParams):
-        self.params = params
+    _destroy = ""
+
+    def __init__(self):
         self._h = C.c_void_p()
-        self._owner = _lib.lib()  # the build that created the handle destroys it (tests run the front on the lab build too)
-        _lib.check(self._owner.ss_config_create(C.byref(params), C.byref(self._h)))
+        self._owner = _lib.lib()
 
-    def __del__(self):
+    def __del__(self):  # (a half-built object has no handle, or a null one; a failing destroy must not raise from here)
         h, self._h = getattr(self, "_h", None), None
         if h:
             try:
-                self._owner.ss_config_destroy(h)
+                getattr(self._owner, self._destroy)(h)
             except Exception:
                 pass
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+
+class SpeechConfig(_Handle):
+    """Owns an ``ss_config`` handle: the counterpart of ``PySpeechSauce(SpeechConfig)``
+    (py-speechsauce/src/lib.rs:7-10; speechsauce/src/config.rs:99-185)."""
+
+    _destroy = "ss_config_destroy"
+
+    def __init__(self, params: SsParams):
+        super().__init__()
+        self.params = params
+        _lib.check(self._owner.ss_config_create(C.byref(params), C.byref(self._h)))
 
     # ---- derived sizes -------------------------------------------------------------------
     def num_frames(self, n_samples: int) -> int:
@@ -72,10 +89,6 @@ class SpeechConfig:
         r, rr = C.c_size_t(), C.c_size_t()
         _lib.check(_lib.lib().ss_stft_rows(C.byref(self.params), n_samples, C.byref(r), C.byref(rr)))
         return r.value, rr.value
-
-    @property
-    def handle(self) -> C.c_void_p:
-        return self._h
 
     def device_status(self) -> None:
         """Raises SpeechSauceError (SS_ERR_DEVICE) if a kernel of an asynchronous launch on this config has reported a
@@ -191,6 +204,32 @@ def _stream_ptr():
     import torch
 
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _launch(device, fn, *args):
+    """One device call that holds temporaries: ``fn(*args, stream)`` with ``device`` current, on torch's current stream there, run
+    through ``_lib.check``.  A tensor among ``args`` is an input: it goes in as its address.  A numpy array is a host table: it is
+    uploaded to ``device`` first.  Everything else passes through -- outputs and carried state go in as ``data_ptr()``, which also
+    keeps them out of what follows.  The launch is asynchronous, so once the call went through every input and every uploaded table
+    is recorded on the stream: they are often temporaries, and the allocator must keep them until the stream has passed them.
+    -> the uploaded tables, in the order of ``args``."""
+    import torch
+
+    with torch.cuda.device(device):
+        held, tables, call = [], [], []
+        for a in args:
+            if isinstance(a, np.ndarray):
+                a = torch.from_numpy(a).to(device)
+                tables.append(a)
+            if isinstance(a, torch.Tensor):
+                held.append(a)
+                a = a.data_ptr()
+            call.append(a)
+        stream = torch.cuda.current_stream()  # (looked up once: what ``_stream_ptr()`` would hand over is what gets recorded)
+        _lib.check(fn(*call, C.c_void_p(stream.cuda_stream)))
+        for t in held:
+            t.record_stream(stream)
+    return tables
 
 
 # ---- internal entry points (the `_internal` pyfns, py-speechsauce/src/lib.rs:167-204) -------------
@@ -1163,18 +1202,11 @@ class _StreamPoolMixin:
             return
         ptrs = [o.data_ptr() if _is_torch(o) else o.ctypes.data for o in outs]
         if _is_torch(packed):
-            import torch
-
             x = packed.contiguous()
             if x.data_ptr() & 3:  # (int16 only: the device form reads sample pairs as dwords)
                 x = x.clone()
-            with torch.cuda.device(x.device):
-                d_so, d_ro, d_sl = (torch.from_numpy(t).to(x.device) for t in (so, ro, sl))
-                st = self._state.data_ptr() if self.state_len else None
-                _lib.check(getattr(lib, dev_fn)(config.handle, x.data_ptr(), n_active, d_so.data_ptr(), d_ro.data_ptr(), int(ro[-1]),
-                                                d_sl.data_ptr(), self.pool_streams, *extra, st, *ptrs, _stream_ptr()))
-                for t in (x, d_so, d_ro, d_sl):  # the launches are asynchronous: keep the temporaries until the stream has passed them
-                    t.record_stream(torch.cuda.current_stream())
+            st = self._state.data_ptr() if self.state_len else None
+            _launch(x.device, getattr(lib, dev_fn), config.handle, x, n_active, so, ro, int(ro[-1]), sl, self.pool_streams, *extra, st, *ptrs)
         else:
             x = np.ascontiguousarray(packed)
             st = self._state.ctypes.data if self.state_len else None
@@ -1317,14 +1349,139 @@ class StftStreamPool(_StftStreamPoolBase):
         return out.view(np.complex64)[..., 0], ro
 
 
-# ---- the pools of the side stages (CMVN, add-deltas, resampling): a block, its offset table and the slots of its entries ------
+# ---- the pools of the side stages (CMVN, add-deltas, splice, VAD, resampling): a block, its offset table and the slots of its entries ------
 
 class _SidePool:
-    """What ``CmvnStreamPool``, ``AddDeltasStreamPool`` and ``ResampleStreamPool`` share: the slot rule, the rules of the offset
-    table (``_table`` names it, ``_noun`` what it counts), the place of the pool and its allocation by the first call.  A class
-    sets ``_what``, ``pool_streams`` and ``state_len``, and ``_state`` / ``_where`` to None."""
+    """The skeleton of ``CmvnStreamPool``, ``AddDeltasStreamPool``, ``SpliceStreamPool``, ``VadEnergyStreamPool`` and
+    ``ResampleStreamPool``: the argument rules, the place of the pool and its allocation by the first call, the counter, ``reset``,
+    and the two calls ``ss_<_stem>_stream_packed*`` (``_run``) and ``ss_<_stem>_stream_flush*`` (``_flush``) in their host and device
+    forms.  A pool class checks its own parameters, sets ``state_len`` and describes its calls: ``_stem``; ``_scalars()``, what stands
+    between ``pool_streams`` and the state in ``include/speechsauce_amd.h`` (``_flush_scalars()`` where the flush takes others);
+    ``_out_shape(n)`` and ``_flush_shape(n_active)`` of ``_dtype``; ``_period``, what every entry must be a multiple of; ``_counter``,
+    the name of its int64 per-slot counter on the host (None: none), which moves by ``_count(np.diff(offsets))``.  What one pool
+    does differently from the others (``_table_first``, ``_whole_block``, ``_owner_for``, its own ``reset``) is stated at that pool.
 
-    _table, _noun = "row_offsets", "rows"
+    State, place and counter move only once a call went through ``_lib.check``, in this order and on both paths, also where there
+    was nothing to launch: a failed first call leaves the pool unplaced and unallocated."""
+
+    _table, _noun, _verb = "row_offsets", "rows", "takes"
+    _stem, _dtype, _period, _counter = "", "float32", 1, "rows_seen"
+    _table_first = False  # the slot rule is decided before the values of the offset table
+    _whole_block = True  # a call counts every row of the block it is handed, not only those the table covers
+
+    def __init__(self, pool_streams, cols=None):
+        if int(pool_streams) < 1:
+            raise ValueError(f"{self._what}: pool_streams must be at least 1")
+        if cols is not None and int(cols) < 1:
+            raise ValueError(f"{self._what}: cols must be at least 1")
+        self.pool_streams = int(pool_streams)
+        if cols is not None:
+            self.cols = int(cols)
+        if self._counter:
+            setattr(self, self._counter, np.zeros(self.pool_streams, dtype=np.int64))
+        self._state = None
+        self._where = None
+
+    @property
+    def state(self):
+        """[pool_streams, state_len] float32: a torch tensor on the device of the first call's block, or a numpy array; None before
+        the first call."""
+        return self._state
+
+    def reset(self, slots=None):
+        """Zero the state (and the counter) of every stream of the pool, or of the given slots (fresh streams)."""
+        if slots is None:
+            idx = ...
+        else:
+            idx = self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
+            if not idx:
+                return
+        getattr(self, self._counter)[idx] = 0
+        if self._state is not None:
+            self._state[idx] = 0
+
+    def _scalars(self):
+        return ()
+
+    def _flush_scalars(self):
+        return self._scalars()
+
+    def _count(self, diff):
+        return diff
+
+    def _owner_for(self, x):
+        """The owner of the handle that leads the calls' arguments, for the place of ``x``: these calls take none."""
+        return None
+
+    def __call__(self, rows, row_offsets, slots):
+        x = _require_f32(rows, (2,), self._what)
+        if int(x.shape[1]) != self.cols:
+            raise ValueError(f"{self._what}: rows has {int(x.shape[1])} columns, this pool {self._verb} {self.cols}")
+        return self._run(x, row_offsets, slots)
+
+    def _run(self, x, offsets, slots, suffix="", scalars=None):
+        """The block ``x`` with its offset table and slots through ``ss_<_stem>_stream_packed<suffix>[_device]``; ``scalars``
+        stand in for ``_scalars()``."""
+        off = self._offsets(offsets)
+        slot_list = [int(v) for v in slots]
+        if not self._table_first:
+            self._slots(slot_list)
+        self._check_offsets(off, len(slot_list), int(x.shape[0]))
+        if self._table_first:
+            self._slots(slot_list)
+        if (np.diff(off) % self._period).any():
+            raise ValueError(f"{self._what}: every entry must bring whole periods of {self._period} {self._noun}")
+        where = self._place(x)
+        lib, n_active = _lib.lib(), len(slot_list)
+        owner = self._owner_for(x)
+        head = () if owner is None else (owner.handle,)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        n = int(x.shape[0]) if self._whole_block else int(off[-1])
+        name = f"ss_{self._stem}_stream_packed{suffix}"
+        scalars = (self.pool_streams, *(self._scalars() if scalars is None else scalars))
+        state = self._state_for(x)
+        if _is_torch(x):
+            import torch
+
+            x = x.contiguous()
+            out = torch.empty(self._out_shape(n), dtype=getattr(torch, self._dtype), device=x.device)
+            if n_active and n:
+                _launch(x.device, getattr(lib, name + "_device"), *head, x, n_active, off, n, sl, *scalars, state.data_ptr(), out.data_ptr())
+        else:
+            x = np.ascontiguousarray(x)
+            out = np.empty(self._out_shape(n), dtype=self._dtype)
+            if n_active and n:
+                _lib.check(getattr(lib, name)(*head, x.ctypes.data, n_active, off.ctypes.data, sl.ctypes.data, *scalars, state.ctypes.data,
+                                              out.ctypes.data))
+        self._state, self._where = state, where  # only once the call went through
+        if n_active and self._counter:
+            getattr(self, self._counter)[sl] += self._count(np.diff(off))
+        return out
+
+    def _flush(self, slots):
+        """The given slots through ``ss_<_stem>_stream_flush[_device]``, where the pool lives; before the first call there is no
+        state anywhere and nothing is called: zeros in a numpy array.  Afterwards the slots' counter is zero."""
+        slot_list = self._slots(slots)
+        lib, n_active = _lib.lib(), len(slot_list)
+        sl = np.asarray(slot_list, dtype=np.int32)
+        state, shape = self._state, self._flush_shape(n_active)
+        name = f"ss_{self._stem}_stream_flush"
+        scalars = (self.pool_streams, *self._flush_scalars())
+        owner = self._owner_for(state) if n_active and state is not None else None
+        head = () if owner is None else (owner.handle,)
+        if not _is_torch(state):
+            out = np.zeros(shape, dtype=self._dtype)
+            if n_active and state is not None:
+                _lib.check(getattr(lib, name)(*head, n_active, sl.ctypes.data, *scalars, state.ctypes.data, out.ctypes.data))
+        else:
+            import torch
+
+            out = torch.empty(shape, dtype=getattr(torch, self._dtype), device=state.device)
+            if n_active:
+                _launch(state.device, getattr(lib, name + "_device"), *head, n_active, sl, *scalars, state.data_ptr(), out.data_ptr())
+        if n_active:
+            getattr(self, self._counter)[sl] = 0
+        return out
 
     def _slots(self, slots):
         return _pool_slots(slots, self.pool_streams, self._what)
@@ -1373,35 +1530,23 @@ class CmvnStreamPool(_SidePool):
     tensors in -> the device call on the current stream.  A row's bits depend on its window's values only, however the stream was
     cut into calls.  See ``ss_cmvn_stream_packed`` in ``include/speechsauce_amd.h``."""
 
-    _what = "CmvnStreamPool"
+    _what, _stem, _verb = "CmvnStreamPool", "cmvn", "normalises"
+    _counter = None  # the window needs no dates: no counter, and with nothing delayed no ``flush``
+    _table_first = True  # this pool decides the offset table before the slots
 
     def __init__(self, pool_streams, cols, win_size=301, variance_normalization=False):
-        what = self._what
-        if int(pool_streams) < 1:
-            raise ValueError(f"{what}: pool_streams must be at least 1")
-        if int(cols) < 1:
-            raise ValueError(f"{what}: cols must be at least 1")
+        super().__init__(pool_streams, cols)
         if int(win_size) < 1:
-            raise ValueError(f"{what}: win_size must be at least 1")
-        self.pool_streams = int(pool_streams)
-        self.cols = int(cols)
+            raise ValueError(f"{self._what}: win_size must be at least 1")
         self.win_size = int(win_size)
         self.variance_normalization = bool(variance_normalization)
         L = C.c_size_t()
         _lib.check(_lib.lib().ss_cmvn_stream_state_len(self.cols, self.win_size, C.byref(L)))
-        self.state_len = L.value
-        self._state = None
-        self._where = None
-
-    @property
-    def state(self):
-        """[pool_streams, (win_size - 1) * cols + 1] float32: a torch tensor on the device of the first rows, or a numpy array;
-        None before the first call."""
-        return self._state
+        self.state_len = L.value  # (win_size - 1) * cols + 1
 
     def reset(self, slots=None):
         """Zero the state of every stream of the pool, or of the given slots (fresh streams)."""
-        if self._state is None:
+        if self._state is None:  # (nothing to zero and no counter: the slots are not even looked at, and never held to the slot rule)
             return
         if slots is None:
             self._state[...] = 0
@@ -1410,42 +1555,11 @@ class CmvnStreamPool(_SidePool):
             if idx:
                 self._state[idx] = 0
 
-    def __call__(self, rows, row_offsets, slots):
-        what = self._what
-        x = _require_f32(rows, (2,), what)
-        if int(x.shape[1]) != self.cols:
-            raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool normalises {self.cols}")
-        total_rows = int(x.shape[0])
-        ro = self._offsets(row_offsets)
-        slot_list = [int(v) for v in slots]
-        self._check_offsets(ro, len(slot_list), total_rows)
-        self._slots(slot_list)  # (this pool decides the table before the slots)
-        where = self._place(x)
-        lib, n_active = _lib.lib(), len(slot_list)
-        sl = np.asarray(slot_list, dtype=np.int32)
-        var = int(self.variance_normalization)
-        state = self._state_for(x)
-        if _is_torch(x):
-            import torch
+    def _scalars(self):
+        return self.cols, self.win_size, int(self.variance_normalization)
 
-            x = x.contiguous()
-            out = torch.empty_like(x)
-            if n_active and total_rows:
-                with torch.cuda.device(x.device):
-                    d_ro, d_sl = torch.from_numpy(ro).to(x.device), torch.from_numpy(sl).to(x.device)
-                    _lib.check(lib.ss_cmvn_stream_packed_device(x.data_ptr(), n_active, d_ro.data_ptr(), total_rows, d_sl.data_ptr(),
-                                                                self.pool_streams, self.cols, self.win_size, var, state.data_ptr(),
-                                                                out.data_ptr(), _stream_ptr()))
-                    for t in (x, d_ro, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                        t.record_stream(torch.cuda.current_stream())
-        else:
-            x = np.ascontiguousarray(x)
-            out = np.empty_like(x)
-            if n_active and total_rows:
-                _lib.check(lib.ss_cmvn_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, self.pool_streams, self.cols,
-                                                     self.win_size, var, state.ctypes.data, out.ctypes.data))
-        self._state, self._where = state, where  # only once the call went through
-        return out
+    def _out_shape(self, n):
+        return n, self.cols
 
 
 def stack_frames(signal, sampling_frequency, frame_length=0.020, frame_stride=0.020, filter=None, zero_padding=False, **switches):
@@ -1504,13 +1618,8 @@ def stack_frames(signal, sampling_frequency, frame_length=0.020, frame_stride=0.
 
         x = sig.contiguous()
         out = torch.empty((T.value, fl.value), dtype=torch.float32, device=x.device)
-        wd = torch.from_numpy(win).to(x.device) if win is not None else None
-        with torch.cuda.device(x.device):
-            _lib.check(lib.ss_stack_frames_signal_device(x.data_ptr(), L, int(sampling_frequency), float(frame_length), float(frame_stride),
-                                                         wd.data_ptr() if wd is not None else None, int(bool(zero_padding)), out.data_ptr(),
-                                                         _stream_ptr()))
-        if wd is not None:
-            wd.record_stream(torch.cuda.current_stream(x.device))
+        _launch(x.device, lib.ss_stack_frames_signal_device, x, L, int(sampling_frequency), float(frame_length), float(frame_stride), win,
+                int(bool(zero_padding)), out.data_ptr())
         return out
     x = np.ascontiguousarray(sig)
     out = np.empty((T.value, fl.value), dtype=np.float32)
@@ -1990,10 +2099,7 @@ def add_deltas_packed(vec, offsets, order=2, window=2):
         import torch
 
         out = torch.empty((rows, (order + 1) * cols), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.ss_add_deltas_packed_device(x.data_ptr(), n, table.data_ptr(), rows, cols, order, window, out.data_ptr(), _stream_ptr()))
-            for t in (x, table):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                t.record_stream(torch.cuda.current_stream())
+        _launch(x.device, lib.ss_add_deltas_packed_device, x, n, table, rows, cols, order, window, out.data_ptr())
         return out
     out = np.empty((rows, (order + 1) * cols), dtype=np.float32)
     _lib.check(lib.ss_add_deltas_packed(x.ctypes.data, n, table.ctypes.data, rows, cols, order, window, out.ctypes.data))
@@ -2023,107 +2129,31 @@ class AddDeltasStreamPool(_SidePool):
     on the host) dates every row; it moves only after a call went through.  numpy in -> the host-pointer calls, ROCm tensors in ->
     the device calls on the current stream.  See ``ss_add_deltas_stream_packed`` in ``include/speechsauce_amd.h``."""
 
-    _what = "AddDeltasStreamPool"
+    _what, _stem = "AddDeltasStreamPool", "add_deltas"
 
     def __init__(self, pool_streams, cols, order=2, window=2):
-        what = self._what
-        if int(pool_streams) < 1:
-            raise ValueError(f"{what}: pool_streams must be at least 1")
-        if int(cols) < 1:
-            raise ValueError(f"{what}: cols must be at least 1")
-        self.order, self.window = _check_delta_params(order, window, what)
-        self.pool_streams = int(pool_streams)
-        self.cols = int(cols)
+        super().__init__(pool_streams, cols)
+        self.order, self.window = _check_delta_params(order, window, self._what)
         self.lag = self.order * self.window
         self.out_cols = (self.order + 1) * self.cols
         L = C.c_size_t()
         _lib.check(_lib.lib().ss_add_deltas_stream_state_len(self.cols, self.order, self.window, C.byref(L)))
-        self.state_len = L.value
-        self.rows_seen = np.zeros(self.pool_streams, dtype=np.int64)
-        self._state = None
-        self._where = None
+        self.state_len = L.value  # 2 * lag * cols + 1
 
-    @property
-    def state(self):
-        """[pool_streams, 2 * lag * cols + 1] float32: a torch tensor on the device of the first rows, or a numpy array; None before
-        the first call."""
-        return self._state
+    def _scalars(self):
+        return self.cols, self.order, self.window
 
-    def reset(self, slots=None):
-        """Zero the state (and ``rows_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
-        idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
-        if slots is None:
-            self.rows_seen[:] = 0
-            if self._state is not None:
-                self._state[...] = 0
-        elif idx:
-            self.rows_seen[idx] = 0
-            if self._state is not None:
-                self._state[idx] = 0
+    def _out_shape(self, n):
+        return n, self.out_cols
 
-    def __call__(self, rows, row_offsets, slots):
-        what = self._what
-        x = _require_f32(rows, (2,), what)
-        if int(x.shape[1]) != self.cols:
-            raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool takes {self.cols}")
-        total_rows = int(x.shape[0])
-        ro = self._offsets(row_offsets)
-        slot_list = self._slots(slots)
-        self._check_offsets(ro, len(slot_list), total_rows)
-        where = self._place(x)
-        lib, n_active = _lib.lib(), len(slot_list)
-        sl = np.asarray(slot_list, dtype=np.int32)
-        state = self._state_for(x)
-        if _is_torch(x):
-            import torch
-
-            x = x.contiguous()
-            out = torch.empty((total_rows, self.out_cols), dtype=torch.float32, device=x.device)
-            if n_active and total_rows:
-                with torch.cuda.device(x.device):
-                    d_ro, d_sl = torch.from_numpy(ro).to(x.device), torch.from_numpy(sl).to(x.device)
-                    _lib.check(lib.ss_add_deltas_stream_packed_device(x.data_ptr(), n_active, d_ro.data_ptr(), total_rows, d_sl.data_ptr(),
-                                                                      self.pool_streams, self.cols, self.order, self.window, state.data_ptr(),
-                                                                      out.data_ptr(), _stream_ptr()))
-                    for t in (x, d_ro, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                        t.record_stream(torch.cuda.current_stream())
-        else:
-            x = np.ascontiguousarray(x)
-            out = np.empty((total_rows, self.out_cols), dtype=np.float32)
-            if n_active and total_rows:
-                _lib.check(lib.ss_add_deltas_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, self.pool_streams, self.cols,
-                                                           self.order, self.window, state.ctypes.data, out.ctypes.data))
-        self._state, self._where = state, where  # only once the call went through
-        if n_active:
-            self.rows_seen[sl] += np.diff(ro)
-        return out
+    def _flush_shape(self, n_active):
+        return n_active * self.lag, self.out_cols
 
     def flush(self, slots):
         """The last ``lag`` rows of the given streams, ``[len(slots) * lag, (order + 1) * cols]`` (entry i: rows i * lag .. (i + 1) *
         lag, stream times rows_seen - lag .. rows_seen - 1, zeros where that is negative); afterwards those streams are fresh.  Before
         the pool's first call there is no state anywhere: the rows are zeros in a numpy array."""
-        slot_list = self._slots(slots)
-        lib, n_active = _lib.lib(), len(slot_list)
-        sl = np.asarray(slot_list, dtype=np.int32)
-        if self._state is None or not _is_torch(self._state):
-            out = np.zeros((n_active * self.lag, self.out_cols), dtype=np.float32)
-            if n_active and self._state is not None:
-                _lib.check(lib.ss_add_deltas_stream_flush(n_active, sl.ctypes.data, self.pool_streams, self.cols, self.order, self.window,
-                                                          self._state.ctypes.data, out.ctypes.data))
-        else:
-            import torch
-
-            state = self._state
-            out = torch.empty((n_active * self.lag, self.out_cols), dtype=torch.float32, device=state.device)
-            if n_active:
-                with torch.cuda.device(state.device):
-                    d_sl = torch.from_numpy(sl).to(state.device)
-                    _lib.check(lib.ss_add_deltas_stream_flush_device(n_active, d_sl.data_ptr(), self.pool_streams, self.cols, self.order,
-                                                                     self.window, state.data_ptr(), out.data_ptr(), _stream_ptr()))
-                    d_sl.record_stream(torch.cuda.current_stream())
-        if n_active:
-            self.rows_seen[sl] = 0
-        return out
+        return self._flush(slots)
 
 
 # ---- frame splicing and subsampling (Kaldi's splice-feats / subsample-feats, low frame rate; ss_splice_*) ----------------------
@@ -2166,12 +2196,7 @@ def splice_packed(rows, row_offsets, left, right, stride=1):
         import torch
 
         out = torch.empty((out_rows, ocols), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            d_ro, d_oo = torch.from_numpy(ro).to(x.device), torch.from_numpy(oo).to(x.device)
-            _lib.check(lib.ss_splice_packed_device(x.data_ptr(), n, d_ro.data_ptr(), total_rows, d_oo.data_ptr(), out_rows, cols, left, right, stride,
-                                                   out.data_ptr(), _stream_ptr()))
-            for t in (x, d_ro, d_oo):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                t.record_stream(torch.cuda.current_stream())
+        _, d_oo = _launch(x.device, lib.ss_splice_packed_device, x, n, ro, total_rows, oo, out_rows, cols, left, right, stride, out.data_ptr())
         return out, d_oo
     out = np.empty((out_rows, ocols), dtype=np.float32)
     _lib.check(lib.ss_splice_packed(x.ctypes.data, n, ro.ctypes.data, total_rows, cols, left, right, stride, out.ctypes.data))
@@ -2203,10 +2228,12 @@ def lfr(x, m, n):
 # ---- fused splice + affine transform (Kaldi's splice-feats | transform-feats; ss_affine_* / ss_affine_splice_packed*) ---------
 # out row k = M @ (the spliced row k) + bias, one serial f32 fmaf chain per element; the spliced block is never written.
 
-class Affine:
+class Affine(_Handle):
     """Owns an ``ss_affine`` handle: a matrix ``[out_dim, in_dim]`` (1 <= out_dim <= 256, 1 <= in_dim <= 4096) and an optional bias
     ``[out_dim]``, re-laid into the kernel's operand order at creation and -- after the first device call -- its device copy.  The
     arrays handed in are not kept."""
+
+    _destroy = "ss_affine_destroy"
 
     def __init__(self, matrix, bias=None):
         m = np.ascontiguousarray(_affine_host(matrix, "Affine: matrix"), dtype=np.float32)
@@ -2217,8 +2244,7 @@ class Affine:
             b = np.ascontiguousarray(_affine_host(bias, "Affine: bias"), dtype=np.float32)
             if b.shape != (m.shape[0],):
                 raise ValueError(f"Affine: the bias must have out_dim = {m.shape[0]} entries")
-        self._h = C.c_void_p()
-        self._owner = _lib.lib()  # the build that created the handle destroys it
+        super().__init__()
         _lib.check(self._owner.ss_affine_create(m.ctypes.data, m.shape[0], m.shape[1], m.shape[1], b.ctypes.data if b is not None else None,
                                                 C.byref(self._h)))
         self.out_dim, self.in_dim = int(m.shape[0]), int(m.shape[1])
@@ -2237,18 +2263,6 @@ class Affine:
         if m.shape[1] == k + 1:
             return cls(m[:, :k], m[:, k])
         raise ValueError(f"Affine.from_kaldi: the matrix has {m.shape[1]} columns, rows of {k} take {k} (linear) or {k + 1} (affine)")
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                self._owner.ss_affine_destroy(h)
-            except Exception:
-                pass
-
-    @property
-    def handle(self) -> C.c_void_p:
-        return self._h
 
     @property
     def chain_len(self) -> int:
@@ -2289,12 +2303,8 @@ def splice_affine_packed(rows, row_offsets, transform: Affine, left, right, stri
         import torch
 
         out = torch.empty((out_rows, transform.out_dim), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            d_ro, d_oo = torch.from_numpy(ro).to(x.device), torch.from_numpy(oo).to(x.device)
-            _lib.check(lib.ss_affine_splice_packed_device(transform.handle, x.data_ptr(), n, d_ro.data_ptr(), total_rows, d_oo.data_ptr(), out_rows,
-                                                          cols, left, right, stride, out.data_ptr(), _stream_ptr()))
-            for t in (x, d_ro, d_oo):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                t.record_stream(torch.cuda.current_stream())
+        _, d_oo = _launch(x.device, lib.ss_affine_splice_packed_device, transform.handle, x, n, ro, total_rows, oo, out_rows, cols, left, right, stride,
+                          out.data_ptr())
         return out, d_oo
     out = np.empty((out_rows, transform.out_dim), dtype=np.float32)
     _lib.check(lib.ss_affine_splice_packed(transform.handle, x.ctypes.data, n, ro.ctypes.data, total_rows, cols, left, right, stride, out.ctypes.data))
@@ -2331,111 +2341,34 @@ class SpliceStreamPool(_SidePool):
     through.  numpy in -> the host-pointer calls, ROCm tensors in -> the device calls on the current stream.  See
     ``ss_splice_stream_packed`` in ``include/speechsauce_amd.h``."""
 
-    _what = "SpliceStreamPool"
+    _what, _stem = "SpliceStreamPool", "splice"
 
     def __init__(self, pool_streams, cols, left, right, stride=1):
-        what = self._what
-        if int(pool_streams) < 1:
-            raise ValueError(f"{what}: pool_streams must be at least 1")
-        if int(cols) < 1:
-            raise ValueError(f"{what}: cols must be at least 1")
-        self.left, self.right, self.stride = _check_splice_params(left, right, stride, what)
-        self.pool_streams = int(pool_streams)
-        self.cols = int(cols)
+        super().__init__(pool_streams, cols)
+        self.left, self.right, self.stride = _check_splice_params(left, right, stride, self._what)
         self.out_cols = (self.left + 1 + self.right) * self.cols
         L, D = C.c_size_t(), C.c_size_t()
         _lib.check(_lib.lib().ss_splice_stream_state_len(self.cols, self.left, self.right, self.stride, C.byref(L), C.byref(D)))
-        self.state_len, self.delay_rows = L.value, D.value
-        self.rows_seen = np.zeros(self.pool_streams, dtype=np.int64)
-        self._state = None
-        self._where = None
+        self.state_len, self.delay_rows = L.value, D.value  # (delay_rows * stride + left) * cols + 1
 
     @property
-    def state(self):
-        """[pool_streams, (delay_rows * stride + left) * cols + 1] float32: a torch tensor on the device of the first rows, or a
-        numpy array; None before the first call."""
-        return self._state
-
-    def reset(self, slots=None):
-        """Zero the state (and ``rows_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
-        idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
-        if slots is None:
-            self.rows_seen[:] = 0
-            if self._state is not None:
-                self._state[...] = 0
-        elif idx:
-            self.rows_seen[idx] = 0
-            if self._state is not None:
-                self._state[idx] = 0
+    def _period(self):  # an entry brings whole periods of ``stride`` rows (``rows_seen`` still counts rows)
+        return self.stride
 
     def _scalars(self):
-        return self.pool_streams, self.cols, self.left, self.right, self.stride
+        return self.cols, self.left, self.right, self.stride
 
-    def __call__(self, rows, row_offsets, slots):
-        what = self._what
-        x = _require_f32(rows, (2,), what)
-        if int(x.shape[1]) != self.cols:
-            raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool takes {self.cols}")
-        total_rows = int(x.shape[0])
-        ro = self._offsets(row_offsets)
-        slot_list = self._slots(slots)
-        self._check_offsets(ro, len(slot_list), total_rows)
-        if (np.diff(ro) % self.stride).any():
-            raise ValueError(f"{what}: every entry must bring whole periods of {self.stride} rows")
-        where = self._place(x)
-        lib, n_active = _lib.lib(), len(slot_list)
-        sl = np.asarray(slot_list, dtype=np.int32)
-        state = self._state_for(x)
-        out_rows = total_rows // self.stride
-        if _is_torch(x):
-            import torch
+    def _out_shape(self, n):
+        return n // self.stride, self.out_cols
 
-            x = x.contiguous()
-            out = torch.empty((out_rows, self.out_cols), dtype=torch.float32, device=x.device)
-            if n_active and total_rows:
-                with torch.cuda.device(x.device):
-                    d_ro, d_sl = torch.from_numpy(ro).to(x.device), torch.from_numpy(sl).to(x.device)
-                    _lib.check(lib.ss_splice_stream_packed_device(x.data_ptr(), n_active, d_ro.data_ptr(), total_rows, d_sl.data_ptr(),
-                                                                  *self._scalars(), state.data_ptr(), out.data_ptr(), _stream_ptr()))
-                    for t in (x, d_ro, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                        t.record_stream(torch.cuda.current_stream())
-        else:
-            x = np.ascontiguousarray(x)
-            out = np.empty((out_rows, self.out_cols), dtype=np.float32)
-            if n_active and total_rows:
-                _lib.check(lib.ss_splice_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, *self._scalars(), state.ctypes.data,
-                                                       out.ctypes.data))
-        self._state, self._where = state, where  # only once the call went through
-        if n_active:
-            self.rows_seen[sl] += np.diff(ro)
-        return out
+    def _flush_shape(self, n_active):
+        return n_active * self.delay_rows, self.out_cols
 
     def flush(self, slots):
         """The last ``delay_rows`` rows of the given streams, ``[len(slots) * delay_rows, out_cols]`` (entry i: rows i * delay_rows ..
         (i + 1) * delay_rows; zeros where the output index is negative); afterwards those streams are fresh.  Before the pool's first
         call there is no state anywhere: the rows are zeros in a numpy array."""
-        slot_list = self._slots(slots)
-        lib, n_active = _lib.lib(), len(slot_list)
-        sl = np.asarray(slot_list, dtype=np.int32)
-        D = self.delay_rows
-        if self._state is None or not _is_torch(self._state):
-            out = np.zeros((n_active * D, self.out_cols), dtype=np.float32)
-            if n_active and self._state is not None:
-                _lib.check(lib.ss_splice_stream_flush(n_active, sl.ctypes.data, *self._scalars(), self._state.ctypes.data, out.ctypes.data))
-        else:
-            import torch
-
-            state = self._state
-            out = torch.empty((n_active * D, self.out_cols), dtype=torch.float32, device=state.device)
-            if n_active:
-                with torch.cuda.device(state.device):
-                    d_sl = torch.from_numpy(sl).to(state.device)
-                    _lib.check(lib.ss_splice_stream_flush_device(n_active, d_sl.data_ptr(), *self._scalars(), state.data_ptr(), out.data_ptr(),
-                                                                 _stream_ptr()))
-                    d_sl.record_stream(torch.cuda.current_stream())
-        if n_active:
-            self.rows_seen[sl] = 0
-        return out
+        return self._flush(slots)
 
 
 # ---- energy voice-activity decision and voiced-row selection (Kaldi's compute-vad-energy / select-voiced-frames; ss_vad_* /
@@ -2485,11 +2418,7 @@ def vad_energy_packed(vec, offsets, energy_col=0, energy_threshold=5.0, energy_m
 
         mask = torch.empty(rows, dtype=torch.uint8, device=x.device)
         counts = torch.empty(n, dtype=torch.int64, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.ss_vad_energy_packed_device(x.data_ptr(), n, table.data_ptr(), rows, cols, *scalars, mask.data_ptr(), counts.data_ptr(),
-                                                       _stream_ptr()))
-            for t in (x, table):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                t.record_stream(torch.cuda.current_stream())
+        _launch(x.device, lib.ss_vad_energy_packed_device, x, n, table, rows, cols, *scalars, mask.data_ptr(), counts.data_ptr())
         return mask, counts
     mask, counts = np.empty(rows, dtype=np.uint8), np.empty(n, dtype=np.int64)
     _lib.check(lib.ss_vad_energy_packed(x.ctypes.data, n, table.ctypes.data, rows, cols, *scalars, mask.ctypes.data, counts.ctypes.data))
@@ -2556,11 +2485,7 @@ def select_rows_packed(vec, row_offsets, mask, trim=True):
         out = torch.empty_like(x)
         oo = torch.zeros(n + 1, dtype=torch.int64, device=x.device)
         if n and cols and total_rows:
-            with torch.cuda.device(x.device):
-                _lib.check(lib.ss_select_rows_packed_device(x.data_ptr(), n, table.data_ptr(), total_rows, cols, m.data_ptr(), oo.data_ptr(),
-                                                            out.data_ptr(), _stream_ptr()))
-                for t in (x, table, m):  # the launches are asynchronous: keep the temporaries until the stream has passed them
-                    t.record_stream(torch.cuda.current_stream())
+            _launch(x.device, lib.ss_select_rows_packed_device, x, n, table, total_rows, cols, m, oo.data_ptr(), out.data_ptr())
         if not trim:
             return out, oo
         return out[:int(oo[-1])], oo
@@ -2589,110 +2514,34 @@ class VadEnergyStreamPool(_SidePool):
     moves only after a call went through.  numpy in -> the host-pointer calls, ROCm tensors in -> the device calls on the current
     stream.  See ``ss_vad_energy_stream_packed`` in ``include/speechsauce_amd.h``."""
 
-    _what = "VadEnergyStreamPool"
+    _what, _stem, _dtype = "VadEnergyStreamPool", "vad_energy", "uint8"
 
     def __init__(self, pool_streams, cols, energy_col=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0, proportion_threshold=0.6):
-        what = self._what
-        if int(pool_streams) < 1:
-            raise ValueError(f"{what}: pool_streams must be at least 1")
-        if int(cols) < 1:
-            raise ValueError(f"{what}: cols must be at least 1")
-        self.pool_streams = int(pool_streams)
-        self.cols = int(cols)
+        super().__init__(pool_streams, cols)
         (self.energy_col, self.energy_threshold, self.energy_mean_scale, self.frames_context,
-         self.proportion_threshold) = _check_vad_params(energy_col, self.cols, energy_threshold, energy_mean_scale, frames_context, proportion_threshold, what)
+         self.proportion_threshold) = _check_vad_params(energy_col, self.cols, energy_threshold, energy_mean_scale, frames_context, proportion_threshold,
+                                                        self._what)
         L = C.c_size_t()
         _lib.check(_lib.lib().ss_vad_energy_stream_state_len(self.frames_context, C.byref(L)))
-        self.state_len, self.delay_rows = L.value, self.frames_context
-        self.rows_seen = np.zeros(self.pool_streams, dtype=np.int64)
-        self._state = None
-        self._where = None
+        self.state_len, self.delay_rows = L.value, self.frames_context  # 2 * frames_context + 4
 
-    @property
-    def state(self):
-        """[pool_streams, 2 * frames_context + 4] float32: a torch tensor on the device of the first rows, or a numpy array; None
-        before the first call."""
-        return self._state
-
-    def reset(self, slots=None):
-        """Zero the state (and ``rows_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
-        idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
-        if slots is None:
-            self.rows_seen[:] = 0
-            if self._state is not None:
-                self._state[...] = 0
-        elif idx:
-            self.rows_seen[idx] = 0
-            if self._state is not None:
-                self._state[idx] = 0
-
-    def _decision(self):
+    def _flush_scalars(self):  # the decision's: the flush reads no row
         return self.energy_threshold, self.energy_mean_scale, self.frames_context, self.proportion_threshold
 
-    def __call__(self, rows, row_offsets, slots):
-        what = self._what
-        x = _require_f32(rows, (2,), what)
-        if int(x.shape[1]) != self.cols:
-            raise ValueError(f"{what}: rows has {int(x.shape[1])} columns, this pool takes {self.cols}")
-        total_rows = int(x.shape[0])
-        ro = self._offsets(row_offsets)
-        slot_list = self._slots(slots)
-        self._check_offsets(ro, len(slot_list), total_rows)
-        where = self._place(x)
-        lib, n_active = _lib.lib(), len(slot_list)
-        sl = np.asarray(slot_list, dtype=np.int32)
-        state = self._state_for(x)
-        if _is_torch(x):
-            import torch
+    def _scalars(self):
+        return self.cols, self.energy_col, *self._flush_scalars()
 
-            x = x.contiguous()
-            mask = torch.empty(total_rows, dtype=torch.uint8, device=x.device)
-            if n_active and total_rows:
-                with torch.cuda.device(x.device):
-                    d_ro, d_sl = torch.from_numpy(ro).to(x.device), torch.from_numpy(sl).to(x.device)
-                    _lib.check(lib.ss_vad_energy_stream_packed_device(x.data_ptr(), n_active, d_ro.data_ptr(), total_rows, d_sl.data_ptr(),
-                                                                      self.pool_streams, self.cols, self.energy_col, *self._decision(),
-                                                                      state.data_ptr(), mask.data_ptr(), _stream_ptr()))
-                    for t in (x, d_ro, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                        t.record_stream(torch.cuda.current_stream())
-        else:
-            x = np.ascontiguousarray(x)
-            mask = np.empty(total_rows, dtype=np.uint8)
-            if n_active and total_rows:
-                _lib.check(lib.ss_vad_energy_stream_packed(x.ctypes.data, n_active, ro.ctypes.data, sl.ctypes.data, self.pool_streams, self.cols,
-                                                           self.energy_col, *self._decision(), state.ctypes.data, mask.ctypes.data))
-        self._state, self._where = state, where  # only once the call went through
-        if n_active:
-            self.rows_seen[sl] += np.diff(ro)
-        return mask
+    def _out_shape(self, n):
+        return (n,)
+
+    def _flush_shape(self, n_active):
+        return (n_active * self.delay_rows,)
 
     def flush(self, slots):
         """The last ``delay_rows`` decisions of the given streams, uint8 ``[len(slots) * delay_rows]`` (entry i: bytes i * delay_rows ..
         (i + 1) * delay_rows, stream rows rows_seen - delay_rows .. rows_seen - 1, 0 where that is negative); afterwards those streams
         are fresh.  Before the pool's first call there is no state anywhere: the bytes are zeros in a numpy array."""
-        slot_list = self._slots(slots)
-        lib, n_active = _lib.lib(), len(slot_list)
-        sl = np.asarray(slot_list, dtype=np.int32)
-        D = self.delay_rows
-        if self._state is None or not _is_torch(self._state):
-            mask = np.zeros(n_active * D, dtype=np.uint8)
-            if n_active and self._state is not None:
-                _lib.check(lib.ss_vad_energy_stream_flush(n_active, sl.ctypes.data, self.pool_streams, *self._decision(), self._state.ctypes.data,
-                                                          mask.ctypes.data))
-        else:
-            import torch
-
-            state = self._state
-            mask = torch.empty(n_active * D, dtype=torch.uint8, device=state.device)
-            if n_active:
-                with torch.cuda.device(state.device):
-                    d_sl = torch.from_numpy(sl).to(state.device)
-                    _lib.check(lib.ss_vad_energy_stream_flush_device(n_active, d_sl.data_ptr(), self.pool_streams, *self._decision(), state.data_ptr(),
-                                                                     mask.data_ptr(), _stream_ptr()))
-                    d_sl.record_stream(torch.cuda.current_stream())
-        if n_active:
-            self.rows_seen[sl] = 0
-        return mask
+        return self._flush(slots)
 
 
 # ---- padded-batch collation of packed rows (ss_pad_packed*): the rectangular batch a model takes ---------------------------------
@@ -2753,13 +2602,10 @@ def pad_packed(vec, row_offsets, max_rows=None, layout="btc", dtype="float32", p
         out = torch.empty(shape, dtype=getattr(torch, name), device=x.device)
         lengths = torch.zeros(n, dtype=torch.int32, device=x.device)
         if n and max_rows:
-            with torch.cuda.device(x.device):
-                if total_rows == 0:  # every clip is empty: the call still wants a block
-                    x = torch.zeros((1, cols), dtype=torch.float32, device=x.device)
-                _lib.check(lib.ss_pad_packed_device(x.data_ptr(), n, table.data_ptr(), total_rows, cols, max_rows, _PAD_LAYOUTS[layout], code, pad_value,
-                                                    out.data_ptr(), lengths.data_ptr(), _stream_ptr()))
-                for t in (x, table):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                    t.record_stream(torch.cuda.current_stream())
+            if total_rows == 0:  # every clip is empty: the call still wants a block
+                x = torch.zeros((1, cols), dtype=torch.float32, device=x.device)
+            _launch(x.device, lib.ss_pad_packed_device, x, n, table, total_rows, cols, max_rows, _PAD_LAYOUTS[layout], code, pad_value, out.data_ptr(),
+                    lengths.data_ptr())
         return out, lengths
     out = np.empty(shape, dtype={"float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}[name])
     lengths = np.zeros(n, dtype=np.int32)
@@ -2892,11 +2738,7 @@ def mask_spans_packed(rows, row_offsets, spans, n_time, n_freq, mask_value=0.0, 
         if sp.numel() != n * (nt + nf) * 2:
             raise ValueError(f"{what}: spans must hold n_clips * (n_time + n_freq) pairs")
         if n and total_rows:
-            with torch.cuda.device(x.device):
-                _lib.check(lib.ss_mask_spans_packed_device(x.data_ptr(), n, table.data_ptr(), total_rows, cols, _ptr(sp) or None, nt, nf, mask_value,
-                                                           out.data_ptr(), _stream_ptr()))
-                for t in (x, table, sp):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                    t.record_stream(torch.cuda.current_stream())
+            _launch(x.device, lib.ss_mask_spans_packed_device, x, n, table, total_rows, cols, sp, nt, nf, mask_value, out.data_ptr())
         return out
     sp = np.ascontiguousarray(spans.cpu().numpy() if _is_torch(spans) else spans)
     if sp.dtype != np.int32:
@@ -2933,12 +2775,9 @@ def spec_augment_packed(rows, row_offsets, rng, time_masks=2, time_width=100, ti
             raise TypeError(f"{what}: on the device rng must be a SpecAugment or a contiguous int64 tensor of two words on the block's device")
         spans = torch.zeros((n, nt + nf, 2), dtype=torch.int32, device=x.device)
         if n:
-            with torch.cuda.device(x.device):
-                xin, xout = (x, out) if total_rows else (torch.zeros((1, cols), device=x.device),) * 2  # no rows: the call still wants a block
-                _lib.check(lib.ss_specaug_packed_device(xin.data_ptr(), n, table.data_ptr(), total_rows, cols, block.data_ptr(), base, nt, tw, ratio, nf, fw,
-                                                        mask_value, xout.data_ptr(), _ptr(spans) or None, _stream_ptr()))
-                for t in (xin, table):
-                    t.record_stream(torch.cuda.current_stream())
+            xin, xout = (x, out) if total_rows else (torch.zeros((1, cols), device=x.device),) * 2  # no rows: the call still wants a block
+            _launch(x.device, lib.ss_specaug_packed_device, xin, n, table, total_rows, cols, block.data_ptr(), base, nt, tw, ratio, nf, fw, mask_value,
+                    xout.data_ptr(), _ptr(spans) or None)
         return out, spans
     words = _rng_words(rng, what)
     spans = np.zeros((n, nt + nf, 2), np.int32)
@@ -2993,30 +2832,19 @@ class SpecAugment:
 
 # ---- polyphase sinc resampling ahead of the feature calls (ss_resample* in include/speechsauce_amd.h) -------------
 
-class Resampler:
+class Resampler(_Handle):
     """Owns an ``ss_resampler`` handle: the windowed-sinc filter of ``torchaudio.functional.resample`` (``sinc_interp_hann``) for one
     pair of rates, and -- after the first device call -- its device copy.  ``info`` holds o, n, width, taps, lookback, lookahead,
     latency_periods and tile_outputs."""
 
+    _destroy = "ss_resampler_destroy"
+
     def __init__(self, orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99):
-        self._h = C.c_void_p()
-        self._owner = _lib.lib()  # the build that created the handle destroys it
+        super().__init__()
         _lib.check(self._owner.ss_resampler_create(int(orig_rate), int(new_rate), int(lowpass_filter_width), float(rolloff), C.byref(self._h)))
         self.orig_rate, self.new_rate = int(orig_rate), int(new_rate)
         self.info = SsResampleInfo()
         _lib.check(self._owner.ss_resampler_info(self._h, C.byref(self.info)))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                self._owner.ss_resampler_destroy(h)
-            except Exception:
-                pass
-
-    @property
-    def handle(self) -> C.c_void_p:
-        return self._h
 
     def out_len(self, n_samples: int) -> int:
         """ceil(n * n_samples / o)"""
@@ -3053,12 +2881,7 @@ def _resample_packed(sig, so, rs: Resampler, scale):
         x = sig.contiguous()
         out = torch.empty((total_out,), dtype=torch.float32, device=x.device)
         if n and total_out:
-            with torch.cuda.device(x.device):
-                dso, doo = torch.from_numpy(so).to(x.device), torch.from_numpy(oo).to(x.device)
-                _lib.check(getattr(lib, f"ss_resample_packed{i16}_device")(rs.handle, x.data_ptr(), n, dso.data_ptr(), *sc, doo.data_ptr(), total_in,
-                                                                          total_out, out.data_ptr(), _stream_ptr()))
-                for t in (x, dso, doo):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                    t.record_stream(torch.cuda.current_stream())
+            _launch(x.device, getattr(lib, f"ss_resample_packed{i16}_device"), rs.handle, x, n, so, *sc, oo, total_in, total_out, out.data_ptr())
         return out, oo
     x = np.ascontiguousarray(sig)
     out = np.empty((total_out,), dtype=np.float32)
@@ -3094,9 +2917,7 @@ def resample(x, orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99, pcm_s
             v, ld = v.contiguous(), L
         out = torch.empty((batch, out_len), dtype=torch.float32, device=v.device)
         if batch and out_len:
-            with torch.cuda.device(v.device):
-                _lib.check(getattr(lib, f"ss_resample{i16}_device")(rs.handle, v.data_ptr(), batch, L, ld, *sc, out.data_ptr(), out_len, _stream_ptr()))
-                v.record_stream(torch.cuda.current_stream())
+            _launch(v.device, getattr(lib, f"ss_resample{i16}_device"), rs.handle, v, batch, L, ld, *sc, out.data_ptr(), out_len)
         return out[0] if one else out
     v = np.ascontiguousarray(sig).reshape(batch, L)
     out = np.empty((batch, out_len), dtype=np.float32)
@@ -3156,15 +2977,13 @@ class ResampleStreamPool(_SidePool):
     host-pointer calls, ROCm tensors in -> the device calls on the current stream.  The output feeds ``MfccStreamPool`` once the
     caller has buffered it to whole hops.  See ``ss_resample_stream_packed`` in ``include/speechsauce_amd.h``."""
 
-    _what = "ResampleStreamPool"
+    _what, _stem, _counter = "ResampleStreamPool", "resample", "periods_seen"
     _table, _noun = "sample_offsets", "samples"
+    _whole_block = False  # a call counts the samples up to ``sample_offsets[-1]``, and launches nothing where that is 0
 
     def __init__(self, pool_streams, orig_rate, new_rate, lowpass_filter_width=6, rolloff=0.99):
-        what = self._what
-        if int(pool_streams) < 1:
-            raise ValueError(f"{what}: pool_streams must be at least 1")
-        orig_rate, new_rate = _check_rates(orig_rate, new_rate, what)
-        self.pool_streams = int(pool_streams)
+        super().__init__(pool_streams)
+        orig_rate, new_rate = _check_rates(orig_rate, new_rate, self._what)
         self._args = (orig_rate, new_rate, int(lowpass_filter_width), float(rolloff))
         rs = _get_resampler(*self._args)
         self.period_in, self.period_out, self.latency_periods = rs.info.o, rs.info.n, rs.info.latency_periods
@@ -3172,68 +2991,28 @@ class ResampleStreamPool(_SidePool):
         L = C.c_size_t()
         _lib.check(_lib.lib().ss_resample_stream_state_len(rs.handle, C.byref(L)))
         self.state_len = L.value
-        self.periods_seen = np.zeros(self.pool_streams, dtype=np.int64)
-        self._state = None
-        self._where = None
 
     @property
-    def state(self):
-        """[pool_streams, state_len] float32: a torch tensor on the device of the first samples, or a numpy array; None before the
-        first call."""
-        return self._state
+    def _period(self):
+        return self.period_in
 
-    def reset(self, slots=None):
-        """Zero the state (and ``periods_seen``) of every stream of the pool, or of the given slots (fresh streams)."""
-        idx = None if slots is None else self._slots(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
-        if slots is None:
-            self.periods_seen[:] = 0
-            if self._state is not None:
-                self._state[...] = 0
-        elif idx:
-            self.periods_seen[idx] = 0
-            if self._state is not None:
-                self._state[idx] = 0
+    def _count(self, diff):  # ``periods_seen`` counts periods, not samples
+        return diff // self.period_in
+
+    def _owner_for(self, x):  # the filter's tables live on one device: every device has its own handle
+        return _get_resampler(*self._args, _device_key(x))
+
+    def _out_shape(self, n):
+        return (n // self.period_in * self.period_out,)
+
+    def _flush_shape(self, n_active):
+        return n_active, self.lag
 
     def push(self, samples, sample_offsets, slots, pcm_scale=None):
-        what = self._what
-        x, scale = _require_signal(samples, (1,), what, pcm_scale)
-        total = int(x.shape[0])
-        so = self._offsets(sample_offsets)
-        slot_list = self._slots(slots)
-        self._check_offsets(so, len(slot_list), total)
-        if (np.diff(so) % self.period_in).any():
-            raise ValueError(f"{what}: every entry must bring whole periods of {self.period_in} samples")
-        where = self._place(x)
-        lib, n_active = _lib.lib(), len(slot_list)
-        rs = _get_resampler(*self._args, _device_key(x))
-        i16, sc = ("", []) if scale is None else ("_i16", [scale])
-        sl = np.asarray(slot_list, dtype=np.int32)
-        n_in = int(so[-1])
-        n_out = n_in // self.period_in * self.period_out
-        state = self._state_for(x)
-        if _is_torch(x):
-            import torch
-
-            x = x.contiguous()
-            out = torch.empty((n_out,), dtype=torch.float32, device=x.device)
-            if n_active and n_in:
-                with torch.cuda.device(x.device):
-                    d_so, d_sl = torch.from_numpy(so).to(x.device), torch.from_numpy(sl).to(x.device)
-                    _lib.check(getattr(lib, f"ss_resample_stream_packed{i16}_device")(rs.handle, x.data_ptr(), n_active, d_so.data_ptr(), n_in,
-                                                                                      d_sl.data_ptr(), self.pool_streams, *sc, state.data_ptr(),
-                                                                                      out.data_ptr(), _stream_ptr()))
-                    for t in (x, d_so, d_sl):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                        t.record_stream(torch.cuda.current_stream())
-        else:
-            x = np.ascontiguousarray(x)
-            out = np.empty((n_out,), dtype=np.float32)
-            if n_active and n_in:
-                _lib.check(getattr(lib, f"ss_resample_stream_packed{i16}")(rs.handle, x.ctypes.data, n_active, so.ctypes.data, sl.ctypes.data,
-                                                                           self.pool_streams, *sc, state.ctypes.data, out.ctypes.data))
-        self._state, self._where = state, where  # only once the call went through
-        if n_active:
-            self.periods_seen[sl] += np.diff(so) // self.period_in
-        return out
+        x, scale = _require_signal(samples, (1,), self._what, pcm_scale)
+        if scale is None:
+            return self._run(x, sample_offsets, slots)
+        return self._run(x, sample_offsets, slots, "_i16", (scale,))  # the PCM entry point takes the scale behind pool_streams
 
     __call__ = push
 
@@ -3241,55 +3020,21 @@ class ResampleStreamPool(_SidePool):
         """The last ``lag`` outputs of the given streams, ``[len(slots), lag]`` (zeros where the stream's output time is negative);
         afterwards those streams are fresh.  Before the pool's first call there is no state anywhere: the outputs are zeros in a numpy
         array."""
-        slot_list = self._slots(slots)
-        lib, n_active = _lib.lib(), len(slot_list)
-        sl = np.asarray(slot_list, dtype=np.int32)
-        if self._state is None or not _is_torch(self._state):
-            out = np.zeros((n_active, self.lag), dtype=np.float32)
-            if n_active and self._state is not None:
-                rs = _get_resampler(*self._args, _device_key(self._state))
-                _lib.check(lib.ss_resample_stream_flush(rs.handle, n_active, sl.ctypes.data, self.pool_streams, self._state.ctypes.data,
-                                                        out.ctypes.data))
-        else:
-            import torch
-
-            state = self._state
-            out = torch.empty((n_active, self.lag), dtype=torch.float32, device=state.device)
-            if n_active:
-                with torch.cuda.device(state.device):
-                    rs = _get_resampler(*self._args, _device_key(state))
-                    d_sl = torch.from_numpy(sl).to(state.device)
-                    _lib.check(lib.ss_resample_stream_flush_device(rs.handle, n_active, d_sl.data_ptr(), self.pool_streams, state.data_ptr(),
-                                                                   out.data_ptr(), _stream_ptr()))
-                    d_sl.record_stream(torch.cuda.current_stream())
-        if n_active:
-            self.periods_seen[sl] = 0
-        return out
+        return self._flush(slots)
 
 
 # ---- Kaldi-compatible fbank / MFCC front end (ss_kaldi_* in include/speechsauce_amd.h) ---------------------------
 
-class KaldiConfig:
+class KaldiConfig(_Handle):
     """Owns an ``ss_kaldi_config`` handle: the validated ``ss_kaldi_params``, the kernel's tables on the device that was current at
     creation and a device error word for the packed calls."""
 
+    _destroy = "ss_kaldi_config_destroy"
+
     def __init__(self, params: SsKaldiParams):
+        super().__init__()
         self.params = params
-        self._h = C.c_void_p()
-        self._owner = _lib.lib()  # the build that created the handle destroys it
         _lib.check(self._owner.ss_kaldi_config_create(C.byref(params), C.byref(self._h)))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                self._owner.ss_kaldi_config_destroy(h)
-            except Exception:
-                pass
-
-    @property
-    def handle(self) -> C.c_void_p:
-        return self._h
 
     def num_frames(self, n_samples: int) -> int:
         t = C.c_size_t()
@@ -3374,14 +3119,10 @@ def _kaldi_dense(sig, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
             v, ld = v.contiguous(), L
         out = torch.empty((batch, T, cols), dtype=torch.float32, device=v.device)
         en = torch.empty((batch, T), dtype=torch.float32, device=v.device) if with_energy else None
-        if batch:
-            with torch.cuda.device(v.device):
-                if mfcc:
-                    _lib.check(lib.ss_kaldi_mfcc_device(cfg.handle, v.data_ptr(), batch, L, ld, out.data_ptr(), _stream_ptr()))
-                else:
-                    _lib.check(lib.ss_kaldi_fbank_device(cfg.handle, v.data_ptr(), batch, L, ld, out.data_ptr(), en.data_ptr() if with_energy else None,
-                                                         _stream_ptr()))
-                v.record_stream(torch.cuda.current_stream())
+        if batch and mfcc:
+            _launch(v.device, lib.ss_kaldi_mfcc_device, cfg.handle, v, batch, L, ld, out.data_ptr())
+        elif batch:
+            _launch(v.device, lib.ss_kaldi_fbank_device, cfg.handle, v, batch, L, ld, out.data_ptr(), en.data_ptr() if with_energy else None)
         if with_energy:
             out = torch.cat([en.unsqueeze(-1), out], dim=-1)
         return out[0] if one else out
@@ -3412,17 +3153,10 @@ def _kaldi_packed(sig, so, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
         x = sig.contiguous()
         out = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
         en = torch.empty((rows,), dtype=torch.float32, device=x.device) if with_energy else None
-        if n and rows:
-            with torch.cuda.device(x.device):
-                dso, dfo = torch.from_numpy(so).to(x.device), torch.from_numpy(fo).to(x.device)
-                if mfcc:
-                    _lib.check(lib.ss_kaldi_mfcc_packed_device(cfg.handle, x.data_ptr(), n, dso.data_ptr(), dfo.data_ptr(), rows, out.data_ptr(),
-                                                               _stream_ptr()))
-                else:
-                    _lib.check(lib.ss_kaldi_fbank_packed_device(cfg.handle, x.data_ptr(), n, dso.data_ptr(), dfo.data_ptr(), rows, out.data_ptr(),
-                                                                en.data_ptr() if with_energy else None, _stream_ptr()))
-                for t in (x, dso, dfo):  # the launch is asynchronous: keep the temporaries until the stream has passed them
-                    t.record_stream(torch.cuda.current_stream())
+        if n and rows and mfcc:
+            _launch(x.device, lib.ss_kaldi_mfcc_packed_device, cfg.handle, x, n, so, fo, rows, out.data_ptr())
+        elif n and rows:
+            _launch(x.device, lib.ss_kaldi_fbank_packed_device, cfg.handle, x, n, so, fo, rows, out.data_ptr(), en.data_ptr() if with_energy else None)
         if with_energy:
             out = torch.cat([en.unsqueeze(-1), out], dim=-1)
         return out, fo
@@ -3660,30 +3394,19 @@ def kaldi_mfcc_list(signals, **kw):
 
 # ---- Whisper log-mel front end (ss_whisper_* in include/speechsauce_amd.h) ------------------------------------------
 
-class WhisperConfig:
+class WhisperConfig(_Handle):
     """Owns an ``ss_whisper_config`` handle: the tables and the per-clip keys on the device that was current at creation, a device
     error word for the packed calls, and the f32 scratch block that the 16-bit output types take (grown on demand, never inside a
     captured region: call once eagerly with the largest shape before capturing)."""
 
+    _destroy = "ss_whisper_config_destroy"
+
     def __init__(self, n_mels: int):
+        super().__init__()
         self.params = SsWhisperParams()
-        self._h = C.c_void_p()
-        self._owner = _lib.lib()
         _lib.check(self._owner.ss_whisper_params_default(C.byref(self.params), int(n_mels)))
         _lib.check(self._owner.ss_whisper_config_create(C.byref(self.params), C.byref(self._h)))
         self._work = None
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                self._owner.ss_whisper_config_destroy(h)
-            except Exception:
-                pass
-
-    @property
-    def handle(self) -> C.c_void_p:
-        return self._h
 
     def work_bytes(self, batch: int, n_frames: int, code: int) -> int:
         n = C.c_size_t()
@@ -3765,11 +3488,8 @@ def whisper_log_mel(x, n_mels=80, n_frames=None, dtype="float32"):
             v, ld = v.contiguous(), L
         out, optr = _whisper_out((batch, M, T), name, v.device)
         if batch:
-            with torch.cuda.device(v.device):
-                keep = v if L else torch.zeros(4, dtype=torch.float32, device=v.device)  # an empty clip reads nothing: any address will do
-                _lib.check(lib.ss_whisper_log_mel_device(cfg.handle, keep.data_ptr(), batch, L, ld, T, code, cfg.work(batch, T, code, v.device), optr,
-                                                         _stream_ptr()))
-                keep.record_stream(torch.cuda.current_stream())
+            keep = v if L else torch.zeros(4, dtype=torch.float32, device=v.device)  # an empty clip reads nothing: any address will do
+            _launch(v.device, lib.ss_whisper_log_mel_device, cfg.handle, keep, batch, L, ld, T, code, cfg.work(batch, T, code, v.device), optr)
         return out[0] if one else out
     v = np.ascontiguousarray(sig).reshape(batch, L)
     if L == 0:
@@ -3800,13 +3520,9 @@ def whisper_log_mel_packed(signal, lengths, n_mels=80, n_frames=None, dtype="flo
         out, optr = _whisper_out((n, M, T), name, x.device)
         lens = torch.empty((n,), dtype=torch.int32, device=x.device)
         if n:
-            with torch.cuda.device(x.device):
-                dso = torch.from_numpy(so).to(x.device)
-                keep = x if x.numel() else torch.zeros(4, dtype=torch.float32, device=x.device)
-                _lib.check(lib.ss_whisper_log_mel_packed_device(cfg.handle, keep.data_ptr(), n, dso.data_ptr(), T, code, cfg.work(n, T, code, x.device), optr,
-                                                                lens.data_ptr(), _stream_ptr()))
-                for t in (keep, dso):
-                    t.record_stream(torch.cuda.current_stream())
+            keep = x if x.numel() else torch.zeros(4, dtype=torch.float32, device=x.device)
+            _launch(x.device, lib.ss_whisper_log_mel_packed_device, cfg.handle, keep, n, so, T, code, cfg.work(n, T, code, x.device), optr,
+                    lens.data_ptr())
         return out, lens
     x = np.ascontiguousarray(sig)
     if x.size == 0:
