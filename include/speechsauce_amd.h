@@ -1414,9 +1414,8 @@ int ss_resample_stream_flush(const ss_resampler *rs, size_t n_active, const int3
  *   10. MFCC: c[k] = lift[k] sum_b D[k][b] fbank[b], k < num_ceps; D[0][b] = sqrt(1/M), D[k][b] = sqrt(2/M) cos(pi/M (b + 0.5) k);
  *       lift[k] = 1 + 0.5 Q sin(pi k / Q), Q = cepstral_lifter (Q == 0: no lifter), folded into the host table; use_energy: c[0] = the
  *       log energy.
- * Stream pools, fed floats or 16-bit PCM: the ss_kstream_* section below.
- * Not in this version: one-shot _i16 entry points (use input_scale = 32768 on normalised floats, or feed integer-valued floats),
- * snip_edges = false, non-zero dither, VTLN, htk_compat, subtract_mean (ss_cmvn_packed does that), N != 512. */
+ * Stream pools, fed floats or 16-bit PCM: the ss_kstream_* section below.  The one-shot calls fed 16-bit PCM: ss_kpcm_* below.
+ * Not in this version: snip_edges = false, non-zero dither, VTLN, htk_compat, subtract_mean (ss_cmvn_packed does that), N != 512. */
 enum {
     SS_KALDI_WINDOW_POVEY = 0,
     SS_KALDI_WINDOW_HANNING = 1,
@@ -1504,6 +1503,33 @@ int ss_kaldi_mfcc_packed_device(const ss_kaldi_config *cfg, const float *d_x, si
                                 const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream);
 int ss_kaldi_mfcc_packed(const ss_kaldi_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out);
 
+/* ---- ss_kpcm_*: the eight one-shot calls above, fed signed 16-bit PCM ------------------------------------------------------
+ * (The prefix is ss_kpcm_, not ss_kaldi_: the set of ss_kaldi_* names is closed, as it was for ss_kstream_*.)  Sample k of the call is
+ * (float)x[k] * scale, scale a power of two in [2^-64, 2^64] (else SS_ERR_ARG, checked first among the data checks); the product is
+ * exact.  scale = 1.0 is Kaldi's own sample convention (integer-valued floats), scale = 2^-15 torchaudio's; input_scale still applies
+ * afterwards.  `scale` stands behind ld (equal-length clips) or behind the sample offsets (packed clips), as in ss_mfcc_batch_i16* /
+ * ss_mfcc_packed_i16*.  Every output bit -- the rows, the log energy, the handle's error status -- is that of the float call on the
+ * converted samples with the same handle; every other argument rule and return code is the float call's.  ld, n_samples and the
+ * offsets stay in samples; x needs 2-byte alignment only, device and host form alike (any ld, any clip offset, either parity of
+ * shift).  One launch of the kernel's PCM build: ss_kaldi_c256<NE,...,i> (equal-length clips) or <NE,...,vi> (packed), which fetches
+ * a sample pair as one dword and converts it in registers -- no float copy of the samples exists anywhere; the host forms cross the
+ * link as int16.  Graph-capturable and contained exactly as the float calls. */
+int ss_kpcm_fbank_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale,
+                         float *d_out, float *d_log_energy, void *stream);
+int ss_kpcm_fbank(const ss_kaldi_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, float *out,
+                  float *log_energy);
+int ss_kpcm_mfcc_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale,
+                        float *d_out, void *stream);
+int ss_kpcm_mfcc(const ss_kaldi_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, float *out);
+int ss_kpcm_fbank_packed_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                                const int64_t *d_frame_offsets, size_t total_frames, float *d_out, float *d_log_energy, void *stream);
+int ss_kpcm_fbank_packed(const ss_kaldi_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale,
+                         float *out, float *log_energy);
+int ss_kpcm_mfcc_packed_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                               const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream);
+int ss_kpcm_mfcc_packed(const ss_kaldi_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale,
+                        float *out);
+
 /* ---- ss_kstream_*: the Kaldi front end over a pool of stream states (live audio) -----------------------------------
  * The online form of ss_kaldi_fbank / ss_kaldi_mfcc, on the tables of the other stream pools (ss_resample_stream_packed*,
  * ss_cmvn_stream_packed*, ss_add_deltas_stream_packed*): one set of sample_offsets / row_offsets / slots serves the whole chain
@@ -1540,7 +1566,7 @@ int ss_kaldi_mfcc_packed(const ss_kaldi_config *cfg, const float *x, size_t n_cl
  * The device forms are a linear chain of two launches on `stream` (one where S == 0) -- ss_kaldi_c256<NE,[pow2,]fbank|mfcc,sp> (,spi>
  *   for PCM) and the frame pool's state advance -- whose grids depend on n_active and total_rows only: capturable, and replayable over
  *   changed table contents.  d_log_energy ([total_rows], may be NULL) as in ss_kaldi_fbank_device.
- * Not served: one-shot _i16 Kaldi calls, snip_edges = false, dither, VTLN, padded sizes other than 512 (N != 512), and a dense
+ * Not served: snip_edges = false, dither, VTLN, padded sizes other than 512 (N != 512), and a dense
  *   (non-ragged) Kaldi stream call. */
 int ss_kstream_state_len(const ss_kaldi_params *p, size_t *state_len, size_t *delay_rows); /* host only */
 int ss_kstream_row_offsets(const ss_kaldi_params *p, size_t n_active, const int64_t *sample_offsets, int64_t *row_offsets); /* host only */
@@ -1602,7 +1628,13 @@ int ss_kstream_mfcc_packed_i16(const ss_kaldi_config *cfg, const int16_t *x, siz
  *   ss_whisper_work_bytes of f32 scratch, 16-byte aligned.  Nothing is allocated inside a call.
  * Errors: n_frames < 2, n_frames * 160 >= 2^31, more than SS_WHISPER_MAX_CLIPS clips, null buffers, d_x not 4-byte or d_out /
  *   d_work not 16-byte aligned, ld < n_samples: SS_ERR_ARG.  batch or n_clips of zero: SS_OK, nothing launched.
- * Not served: streaming and pool forms (a stream has no clip maximum), 16-bit PCM input, dither, other sizes. */
+ * _i16 forms (16-bit PCM): sample k is (float)x[k] * scale, scale a power of two in [2^-64, 2^64] (else SS_ERR_ARG, checked first
+ *   among the data checks; 2^-15 is Whisper's own convention); `scale` stands behind ld (dense) or behind the sample offsets (packed).
+ *   out in all three dtypes, d_lengths and the error status are bit for bit the float call's on the converted samples; every other
+ *   rule is the float call's, except that d_x needs 2-byte alignment only.  The middle launch is the kernel's PCM build,
+ *   ss_whisper_c200i: a sample pair is one dword at either parity of the clip's first sample.  No float copy of the samples exists;
+ *   the host forms cross the link as int16.
+ * Not served: streaming and pool forms (a stream has no clip maximum), dither, other sizes. */
 #define SS_WHISPER_MAX_CLIPS 1048576
 typedef struct ss_whisper_params {
     uint32_t struct_size; /* sizeof(ss_whisper_params) */
@@ -1635,6 +1667,14 @@ int ss_whisper_log_mel_packed_device(const ss_whisper_config *cfg, const float *
                                      size_t n_frames, int dtype, void *d_work, void *d_out, int32_t *d_lengths, void *stream);
 int ss_whisper_log_mel_packed(const ss_whisper_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, size_t n_frames,
                               int dtype, void *out, int32_t *lengths);
+int ss_whisper_log_mel_i16_device(const ss_whisper_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale,
+                                  size_t n_frames, int dtype, void *d_work, void *d_out, void *stream);
+int ss_whisper_log_mel_i16(const ss_whisper_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale,
+                           size_t n_frames, int dtype, void *out);
+int ss_whisper_log_mel_packed_i16_device(const ss_whisper_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                         float scale, size_t n_frames, int dtype, void *d_work, void *d_out, int32_t *d_lengths, void *stream);
+int ss_whisper_log_mel_packed_i16(const ss_whisper_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale,
+                                  size_t n_frames, int dtype, void *out, int32_t *lengths);
 
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`

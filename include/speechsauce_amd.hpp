@@ -905,6 +905,39 @@ public:
         check(ss_kaldi_mfcc_packed(h_.get(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), out.data()));
         return out;
     }
+    // The same four calls fed signed 16-bit PCM (ss_kpcm_*): sample = pcm * scale, scale a power of two (1.0: Kaldi's integer-valued
+    // samples, 2^-15: normalised ones); bit for bit the float call on the converted samples
+    std::vector<float> fbank_i16(const std::vector<int16_t> &x, float scale, std::vector<float> *log_energy = nullptr) const
+    {
+        const size_t t = num_frames(x.size());
+        std::vector<float> out(t * p_.num_mel_bins);
+        if (log_energy) log_energy->assign(t, 0.0f);
+        check(ss_kpcm_fbank(h_.get(), x.data(), 1, x.size(), x.size(), scale, out.data(), log_energy ? log_energy->data() : nullptr));
+        return out;
+    }
+    std::vector<float> mfcc_i16(const std::vector<int16_t> &x, float scale) const
+    {
+        std::vector<float> out(num_frames(x.size()) * p_.num_ceps);
+        check(ss_kpcm_mfcc(h_.get(), x.data(), 1, x.size(), x.size(), scale, out.data()));
+        return out;
+    }
+    std::vector<float> fbank_packed_i16(const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets, float scale,
+                                        std::vector<int64_t> &frame_offsets, std::vector<float> *log_energy = nullptr) const
+    {
+        const size_t rows = packed_rows(x, sample_offsets, frame_offsets);
+        std::vector<float> out(rows * p_.num_mel_bins);
+        if (log_energy) log_energy->assign(rows, 0.0f);
+        check(ss_kpcm_fbank_packed(h_.get(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), scale, out.data(),
+                                   log_energy ? log_energy->data() : nullptr));
+        return out;
+    }
+    std::vector<float> mfcc_packed_i16(const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets, float scale,
+                                       std::vector<int64_t> &frame_offsets) const
+    {
+        std::vector<float> out(packed_rows(x, sample_offsets, frame_offsets) * p_.num_ceps);
+        check(ss_kpcm_mfcc_packed(h_.get(), x.data(), sample_offsets.size() - 1, sample_offsets.data(), scale, out.data()));
+        return out;
+    }
 
     // The stream pool (ss_kstream_*): S = the floats of a pool row, D = the warm-up rows after a reset.
     size_t stream_state_len(size_t *delay_rows = nullptr) const
@@ -978,7 +1011,8 @@ private:
         for (int32_t v : slots) top = v > top ? v : top;
         return static_cast<size_t>(top) + 1;
     }
-    size_t packed_rows(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, std::vector<int64_t> &frame_offsets) const
+    template <typename T>  // T: float, or int16_t (the _i16 forms)
+    size_t packed_rows(const std::vector<T> &x, const std::vector<int64_t> &sample_offsets, std::vector<int64_t> &frame_offsets) const
     {
         if (sample_offsets.empty() || sample_offsets.back() < 0 || static_cast<size_t>(sample_offsets.back()) > x.size())
             throw Error(SS_ERR_ARG, "kaldi packed call: shape mismatch");
@@ -1056,6 +1090,38 @@ public:
                                int32_t *d_lengths, void *stream) const
     {
         check(ss_whisper_log_mel_packed_device(h_.get(), d_x, n_clips, d_sample_offsets, n_frames, dtype, d_work, d_out, d_lengths, stream));
+    }
+    // The same four calls fed signed 16-bit PCM: sample = pcm * scale, scale a power of two (2^-15: Whisper's convention); bit for bit
+    // the float call on the converted samples
+    std::vector<float> log_mel_i16(const std::vector<int16_t> &x, float scale, size_t n_frames) const
+    {
+        std::vector<float> out(p_.n_mels * n_frames);
+        const int16_t keep[4] = {0, 0, 0, 0};
+        check(ss_whisper_log_mel_i16(h_.get(), x.empty() ? keep : x.data(), 1, x.size(), x.size(), scale, n_frames, SS_PAD_F32, out.data()));
+        return out;
+    }
+    std::vector<float> log_mel_packed_i16(const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets, float scale, size_t n_frames,
+                                          std::vector<int32_t> *lengths = nullptr) const
+    {
+        if (sample_offsets.empty() || sample_offsets.back() < 0 || static_cast<size_t>(sample_offsets.back()) > x.size())
+            throw Error(SS_ERR_ARG, "whisper packed call: shape mismatch");
+        const size_t n = sample_offsets.size() - 1;
+        std::vector<float> out(n * p_.n_mels * n_frames);
+        if (lengths) lengths->assign(n, 0);
+        const int16_t keep[4] = {0, 0, 0, 0};
+        check(ss_whisper_log_mel_packed_i16(h_.get(), x.empty() ? keep : x.data(), n, sample_offsets.data(), scale, n_frames, SS_PAD_F32, out.data(),
+                                            lengths ? lengths->data() : nullptr));
+        return out;
+    }
+    void log_mel_i16_device(const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale, size_t n_frames, int dtype, void *d_work,
+                            void *d_out, void *stream) const
+    {
+        check(ss_whisper_log_mel_i16_device(h_.get(), d_x, batch, n_samples, ld, scale, n_frames, dtype, d_work, d_out, stream));
+    }
+    void log_mel_packed_i16_device(const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale, size_t n_frames, int dtype,
+                                   void *d_work, void *d_out, int32_t *d_lengths, void *stream) const
+    {
+        check(ss_whisper_log_mel_packed_i16_device(h_.get(), d_x, n_clips, d_sample_offsets, scale, n_frames, dtype, d_work, d_out, d_lengths, stream));
     }
 
 private:

@@ -125,6 +125,7 @@ std::atomic<unsigned> g_tile_fault{0};
 
 using ss::DeviceBuf;
 using ss::hip_fail;
+using ss::check_pcm_scale;
 using ss::ranges_overlap;
 
 #define SS_HIP(call)                                  \
@@ -257,17 +258,6 @@ struct PoolChunks {
     const void *ptr() const { return is_pcm ? static_cast<const void *>(pcm) : f; }
     size_t sample_bytes() const { return is_pcm ? sizeof(int16_t) : sizeof(float); }
 };
-// a power of two in [2^-64, 2^64]: the product with an int16 is exact (and never subnormal)
-bool pcm_scale_ok(float scale)
-{
-    int ex = 0;
-    return std::isfinite(scale) && scale > 0.0f && std::frexp(scale, &ex) == 0.5f && ex - 1 >= -64 && ex - 1 <= 64;
-}
-// the _i16 entry points' check of it, before anything runs
-int check_pcm_scale(float scale)
-{
-    return pcm_scale_ok(scale) ? SS_OK : ss::fail(SS_ERR_ARG, "scale must be a power of two in [2^-64, 2^64]");
-}
 
 // The float copy of an equal-length PCM batch for a kernel without a PCM build (launch_frames, launch_stft): one conversion launch
 // into a stream-ordered temporary, freed in stream order when the call returns.  (Stream-ordered allocation: this path is not
@@ -3248,11 +3238,21 @@ int kaldi_check_call(const ss_kaldi_config *cfg, bool mfcc)
     return SS_OK;
 }
 
-// equal-length clips; T: the rows per clip
-int kaldi_check_dense(const ss_kaldi_config *cfg, bool mfcc, const float *x, size_t batch, size_t n_samples, size_t ld, const float *out, size_t &T)
+// the 16-bit PCM samples of an ss_kpcm_* call: the scale, first among the data checks, and 2-byte alignment
+int kaldi_check_pcm(const PoolChunks &x)
+{
+    if (!x.is_pcm) return SS_OK;
+    if (int rc = check_pcm_scale(x.scale)) return rc;
+    if (reinterpret_cast<uintptr_t>(x.pcm) & 1u) return ss::fail(SS_ERR_ARG, "the PCM buffer must be 2-byte aligned");
+    return SS_OK;
+}
+
+// equal-length clips; T: the rows per clip.  x: floats, or 16-bit PCM (ss_kpcm_*)
+int kaldi_check_dense(const ss_kaldi_config *cfg, bool mfcc, const PoolChunks &x, size_t batch, size_t n_samples, size_t ld, const float *out, size_t &T)
 {
     if (int rc = kaldi_check_call(cfg, mfcc)) return rc;
-    if (!x || !out) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (int rc = kaldi_check_pcm(x)) return rc;
+    if (!x.ptr() || !out) return ss::fail(SS_ERR_ARG, "null buffer");
     if (ld < n_samples) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
     if (n_samples >= (1ull << 31) || batch >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "batch and n_samples must be below 2^31");
     T = ss::kaldi_frames(cfg->tabs.s, n_samples);
@@ -3261,53 +3261,60 @@ int kaldi_check_dense(const ss_kaldi_config *cfg, bool mfcc, const float *x, siz
     return SS_OK;
 }
 
-int kaldi_dense_device(const ss_kaldi_config *cfg, bool mfcc, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out,
+int kaldi_dense_device(const ss_kaldi_config *cfg, bool mfcc, const PoolChunks &d_x, size_t batch, size_t n_samples, size_t ld, float *d_out,
                        float *d_log_energy, hipStream_t stream)
 {
-    if (batch == 0) return cfg ? SS_OK : ss::fail(SS_ERR_ARG, "null handle");
+    if (batch == 0) return cfg ? kaldi_check_pcm(d_x) : ss::fail(SS_ERR_ARG, "null handle");
     size_t T = 0;
     if (int rc = kaldi_check_dense(cfg, mfcc, d_x, batch, n_samples, ld, d_out, T)) return rc;
     if (int rc = kaldi_ready(cfg)) return rc;
-    ss::KaldiArgs a = kaldi_args(cfg, mfcc, d_x, d_out, d_log_energy);
+    ss::KaldiArgs a = kaldi_args(cfg, mfcc, d_x.f, d_out, d_log_energy);
     a.ld = ld;
     a.n_samples = static_cast<uint32_t>(n_samples);
     a.batch = static_cast<uint32_t>(batch);
     a.n_frames = static_cast<uint32_t>(T);
     ss::LaunchInfo info{};
+    if (d_x.is_pcm) return kaldi_launched(ss::launch_kaldi_c256(a, ss::KaldiPcmArgs{d_x.pcm, d_x.scale}, stream, cfg->num_cus, &info), info);
     return kaldi_launched(ss::launch_kaldi_c256(a, stream, cfg->num_cus, &info), info);
 }
 
-int kaldi_dense_host(const ss_kaldi_config *cfg, bool mfcc, const float *x, size_t batch, size_t n_samples, size_t ld, float *out, float *log_energy)
+// (PCM crosses the link as int16)
+int kaldi_dense_host(const ss_kaldi_config *cfg, bool mfcc, const PoolChunks &x, size_t batch, size_t n_samples, size_t ld, float *out, float *log_energy)
 {
-    if (batch == 0) return cfg ? SS_OK : ss::fail(SS_ERR_ARG, "null handle");
+    if (batch == 0) return cfg ? kaldi_check_pcm(x) : ss::fail(SS_ERR_ARG, "null handle");
     size_t T = 0;
     int rc = kaldi_check_dense(cfg, mfcc, x, batch, n_samples, ld, out, T);
     if (rc) return rc;
     if (!ss::have_device()) return ss::no_device("hot path");
     const size_t cols = mfcc ? cfg->params.num_ceps : cfg->params.num_mel_bins, rows = batch * T;
     ss::HostStage st("ss_kaldi");
-    float *d_in = st.room<float>(batch * n_samples * sizeof(float));
+    const size_t sb = x.sample_bytes();
+    void *d_in = st.room<void>(batch * n_samples * sb);
     float *d_out = st.room<float>(rows * cols * sizeof(float));
     float *d_en = log_energy ? st.room<float>(rows * sizeof(float)) : nullptr;
-    st.up_rows(d_in, x, ld * sizeof(float), n_samples * sizeof(float), batch);
-    if (st.ok()) st.ran(kaldi_dense_device(cfg, mfcc, d_in, batch, n_samples, n_samples, d_out, d_en, nullptr));
+    st.up_rows(d_in, x.ptr(), ld * sb, n_samples * sb, batch);
+    if (st.ok())
+        st.ran(kaldi_dense_device(cfg, mfcc,
+                                  x.is_pcm ? PoolChunks(static_cast<const int16_t *>(d_in), x.scale) : PoolChunks(static_cast<const float *>(d_in)), batch,
+                                  n_samples, n_samples, d_out, d_en, nullptr));
     st.sync();
     st.down(out, d_out, rows * cols * sizeof(float));
     if (log_energy) st.down(log_energy, d_en, rows * sizeof(float));
     return st.status();
 }
 
-int kaldi_packed_device(const ss_kaldi_config *cfg, bool mfcc, const float *d_x, size_t n_clips, const int64_t *d_so, const int64_t *d_fo,
+int kaldi_packed_device(const ss_kaldi_config *cfg, bool mfcc, const PoolChunks &d_x, size_t n_clips, const int64_t *d_so, const int64_t *d_fo,
                         size_t total_frames, float *d_out, float *d_log_energy, hipStream_t stream)
 {
     if (int rc = kaldi_check_call(cfg, mfcc)) return rc;
+    if (int rc = kaldi_check_pcm(d_x)) return rc;
     if (n_clips == 0) return SS_OK;
-    if (!d_x || !d_so || !d_fo || !d_out) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (!d_x.ptr() || !d_so || !d_fo || !d_out) return ss::fail(SS_ERR_ARG, "null buffer");
     if (n_clips >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "n_clips must be below 2^31");
     if (static_cast<unsigned long long>(total_frames) + 8 >= 0xffffffffull) return ss::fail(SS_ERR_ARG, "total_frames must be below 2^32 - 8");
     if (int rc = kaldi_ready(cfg)) return rc;
     if (total_frames == 0) return SS_OK;  // no clip can own a row
-    const ss::KaldiArgs a = kaldi_args(cfg, mfcc, d_x, d_out, d_log_energy);
+    const ss::KaldiArgs a = kaldi_args(cfg, mfcc, d_x.f, d_out, d_log_energy);
     ss::KaldiVarlenArgs v{};
     v.so = reinterpret_cast<const long long *>(d_so);
     v.fo = reinterpret_cast<const long long *>(d_fo);
@@ -3315,14 +3322,17 @@ int kaldi_packed_device(const ss_kaldi_config *cfg, bool mfcc, const float *d_x,
     v.n_clips = static_cast<uint32_t>(n_clips);
     v.err = cfg->d_err;
     ss::LaunchInfo info{};
+    if (d_x.is_pcm) return kaldi_launched(ss::launch_kaldi_c256_varlen(a, ss::KaldiVarlenPcmArgs{v, d_x.pcm, d_x.scale}, stream, cfg->num_cus, &info), info);
     return kaldi_launched(ss::launch_kaldi_c256_varlen(a, v, stream, cfg->num_cus, &info), info);
 }
 
-int kaldi_packed_host(const ss_kaldi_config *cfg, bool mfcc, const float *x, size_t n_clips, const int64_t *so, float *out, float *log_energy)
+int kaldi_packed_host(const ss_kaldi_config *cfg, bool mfcc, const PoolChunks &x, size_t n_clips, const int64_t *so, float *out, float *log_energy)
 {
     if (int rc = kaldi_check_call(cfg, mfcc)) return rc;
+    if (x.is_pcm)
+        if (int rc = check_pcm_scale(x.scale)) return rc;
     if (n_clips == 0) return SS_OK;
-    if (!x || !so || !out) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (!x.ptr() || !so || !out) return ss::fail(SS_ERR_ARG, "null buffer");
     if (n_clips >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "n_clips must be below 2^31");
     std::vector<int64_t> fo(n_clips + 1);
     int rc = ss_kaldi_packed_frame_offsets(&cfg->params, n_clips, so, fo.data());
@@ -3331,11 +3341,14 @@ int kaldi_packed_host(const ss_kaldi_config *cfg, bool mfcc, const float *x, siz
     const size_t cols = mfcc ? cfg->params.num_ceps : cfg->params.num_mel_bins, tbytes = (n_clips + 1) * sizeof(int64_t);
     if (!ss::have_device()) return ss::no_device("hot path");
     ss::HostStage st("ss_kaldi");
-    const float *d_in = st.up(x, total_in * sizeof(float));
+    const void *d_in = st.up(x.ptr(), total_in * x.sample_bytes());
     float *d_out = st.room<float>(rows * cols * sizeof(float));
     float *d_en = log_energy ? st.room<float>(rows * sizeof(float)) : nullptr;
     const int64_t *d_so = st.up(so, tbytes), *d_fo = st.up(fo.data(), tbytes);
-    if (st.ok()) st.ran(kaldi_packed_device(cfg, mfcc, d_in, n_clips, d_so, d_fo, rows, d_out, d_en, nullptr));
+    if (st.ok())
+        st.ran(kaldi_packed_device(cfg, mfcc,
+                                   x.is_pcm ? PoolChunks(static_cast<const int16_t *>(d_in), x.scale) : PoolChunks(static_cast<const float *>(d_in)),
+                                   n_clips, d_so, d_fo, rows, d_out, d_en, nullptr));
     st.sync();
     if (st.ok()) st.ran(kaldi_pending_error(cfg));
     st.down(out, d_out, rows * cols * sizeof(float));
@@ -3543,6 +3556,53 @@ int ss_kaldi_mfcc_packed_device(const ss_kaldi_config *cfg, const float *d_x, si
 int ss_kaldi_mfcc_packed(const ss_kaldi_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out)
 {
     return kaldi_packed_host(cfg, true, x, n_clips, sample_offsets, out, nullptr);
+}
+
+// 16-bit PCM forms of the eight calls above (sample k is (float)x[k] * scale): the PCM builds of the same kernel
+int ss_kpcm_fbank_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale, float *d_out,
+                         float *d_log_energy, void *stream)
+{
+    return kaldi_dense_device(cfg, false, PoolChunks(d_x, scale), batch, n_samples, ld, d_out, d_log_energy, static_cast<hipStream_t>(stream));
+}
+
+int ss_kpcm_fbank(const ss_kaldi_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, float *out, float *log_energy)
+{
+    return kaldi_dense_host(cfg, false, PoolChunks(x, scale), batch, n_samples, ld, out, log_energy);
+}
+
+int ss_kpcm_mfcc_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale, float *d_out, void *stream)
+{
+    return kaldi_dense_device(cfg, true, PoolChunks(d_x, scale), batch, n_samples, ld, d_out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int ss_kpcm_mfcc(const ss_kaldi_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, float *out)
+{
+    return kaldi_dense_host(cfg, true, PoolChunks(x, scale), batch, n_samples, ld, out, nullptr);
+}
+
+int ss_kpcm_fbank_packed_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                                const int64_t *d_frame_offsets, size_t total_frames, float *d_out, float *d_log_energy, void *stream)
+{
+    return kaldi_packed_device(cfg, false, PoolChunks(d_x, scale), n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, d_log_energy,
+                               static_cast<hipStream_t>(stream));
+}
+
+int ss_kpcm_fbank_packed(const ss_kaldi_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out,
+                         float *log_energy)
+{
+    return kaldi_packed_host(cfg, false, PoolChunks(x, scale), n_clips, sample_offsets, out, log_energy);
+}
+
+int ss_kpcm_mfcc_packed_device(const ss_kaldi_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                               const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream)
+{
+    return kaldi_packed_device(cfg, true, PoolChunks(d_x, scale), n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, nullptr,
+                               static_cast<hipStream_t>(stream));
+}
+
+int ss_kpcm_mfcc_packed(const ss_kaldi_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, float *out)
+{
+    return kaldi_packed_host(cfg, true, PoolChunks(x, scale), n_clips, sample_offsets, out, nullptr);
 }
 
 int ss_kstream_fbank_packed_device(const ss_kaldi_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,

@@ -836,6 +836,21 @@ struct KaldiVarlenArgs {
 hipError_t launch_kaldi_c256(const KaldiArgs &a, hipStream_t stream, int num_cus, LaunchInfo *info);
 // a: x / out = the packed blocks; batch / n_samples / n_frames / ld are unused
 hipError_t launch_kaldi_c256_varlen(const KaldiArgs &a, const KaldiVarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
+// The same two calls fed signed 16-bit PCM (ss_kpcm_*): sample k is (float)x[k] * scale, scale a power of two (the product is
+// exact).  Trailing argument packs of the kernel's PCM builds, as BatchPcmArgs / VarlenPcmArgs are for the generic kernel; a.x is
+// unused, and the packed pack carries the float layout's tables (kaldi_clip(), row_owner() and the error pass serve both: the
+// kernel's own KaldiVarlenArgs argument stays empty).  ld and the offsets stay in samples; x needs 2-byte alignment only.
+struct KaldiPcmArgs {
+    const int16_t *x;
+    float scale;
+};
+struct KaldiVarlenPcmArgs {
+    KaldiVarlenArgs v;
+    const int16_t *x;
+    float scale;
+};
+hipError_t launch_kaldi_c256(const KaldiArgs &a, const KaldiPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info);
+hipError_t launch_kaldi_c256_varlen(const KaldiArgs &a, const KaldiVarlenPcmArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
 // The stream-pool builds (ss_kaldi512_pool.hip; ss_kstream_*_packed*_device): the packed output rows of a ragged streaming launch
 // over the frame pool's entry block -- step = the frame shift, state_len = S = D * shift, D = ceil(flen / shift) - 1; lead unused:
 // row t of an entry starts at chunk sample t * step - S.  pcm: the chunks are sp.x (2-byte aligned) times sp.scale, else a.x

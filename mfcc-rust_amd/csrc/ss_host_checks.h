@@ -3,6 +3,7 @@
 // but ss::fail from ss_internal.h -- so tools/hosttest/test_host_checks.cpp runs it under the sanitizers without a device.
 #pragma once
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -18,6 +19,18 @@ inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t 
 {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
     return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// the sample scale of a 16-bit PCM call: a power of two in [2^-64, 2^64] -- the product with an int16 is exact (and never subnormal)
+inline bool pcm_scale_ok(float scale)
+{
+    int ex = 0;
+    return std::isfinite(scale) && scale > 0.0f && std::frexp(scale, &ex) == 0.5f && ex - 1 >= -64 && ex - 1 <= 64;
+}
+// the _i16 / ss_kpcm_* entry points' check of it, before anything runs
+inline int check_pcm_scale(float scale)
+{
+    return pcm_scale_ok(scale) ? SS_OK : fail(SS_ERR_ARG, "scale must be a power of two in [2^-64, 2^64]");
 }
 
 // the slots of a host-pointer pool call: inside the pool, none named twice

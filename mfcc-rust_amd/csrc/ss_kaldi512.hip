@@ -17,6 +17,10 @@
 //     offset_find, every T_b is recomputed from so, an inconsistent clip is skipped (no load, no store) and raises the error word.
 //   * Frame starts: a quad whose four frame starts are all 8-byte aligned loads sample pairs as float2; any other quad (odd
 //     shift, odd ld, odd clip offset, an unaligned base) loads single floats.  The choice is per quad and wave-uniform.
+//   * 16-bit PCM (ss_kpcm_*; a KaldiPcmArgs / KaldiVarlenPcmArgs behind the kernel's two arguments): a sample pair is one dword at
+//     2-byte alignment, so every frame start takes the one path; the dword stays raw until the conditioning stage converts it
+//     (exact: a power-of-two scale), which is what makes the rows bit for bit the float build's on the converted samples.
+//     Reported as ss_kaldi_c256<..,i> (dense) and <..,vi> (packed).
 // The kernel template itself is ss_kaldi_body.h, shared with the stream-pool builds of ss_kaldi512_pool.hip; this file holds the
 // launchers of the dense and packed builds.
 #include "ss_kaldi_body.h"
@@ -25,10 +29,12 @@ namespace ss {
 
 namespace {
 
-template <bool VARLEN>
-hipError_t launch_k(const KaldiArgs &a_in, const KaldiVarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+// PCM: nothing (float samples at a.x; v: the packed call's tables), or the call's PCM pack (v: the tables it carries)
+template <bool VARLEN, typename... PCM>
+hipError_t launch_k(const KaldiArgs &a_in, const KaldiVarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info, const PCM &...pcm)
 {
     constexpr int WAVES = 12;
+    constexpr bool I16 = sizeof...(PCM) > 0;
     KaldiArgs a = a_in;
     const unsigned long long total = VARLEN ? v.total_frames : static_cast<unsigned long long>(a.batch) * a.n_frames;
     if (a.flen <= 256 || a.flen > 512 || a.step == 0 || a.n_filters > 80 || a.n_ceps > 32) return hipErrorInvalidValue;
@@ -38,9 +44,10 @@ hipError_t launch_k(const KaldiArgs &a_in, const KaldiVarlenArgs &v, hipStream_t
     if (ps != PlanStatus::Launch) return ps == PlanStatus::Empty ? hipSuccess : hipErrorInvalidValue;
     a.nf_magic = plan.nf_magic;
     a.nf_shift = plan.nf_shift;
-    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, plan.grid, WAVES, lds, stream, info, a, v); };
+    // (a PCM pack's tables ride in the pack: the kernel's own table argument stays empty)
+    auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, plan.grid, WAVES, lds, stream, info, a, I16 ? KaldiVarlenArgs{} : v, pcm...); };
     const bool pow2 = a.use_power != 0, mfcc = a.out_mfcc != 0;
-#define SS_K(NE, P, C, NAME) go(ss_kaldi_c256<NE, P, C, VARLEN, WAVES>, VARLEN ? NAME ",v>" : NAME ">")
+#define SS_K(NE, P, C, NAME) go(ss_kaldi_c256<NE, P, C, VARLEN, WAVES, PCM...>, I16 ? (VARLEN ? NAME ",vi>" : NAME ",i>") : (VARLEN ? NAME ",v>" : NAME ">"))
 #define SS_KN(NE, TAG)                                                                                                     \
     if (pow2) return mfcc ? SS_K(NE, true, true, "ss_kaldi_c256<" TAG ",pow2,mfcc") : SS_K(NE, true, false, "ss_kaldi_c256<" TAG ",pow2,fbank"); \
     return mfcc ? SS_K(NE, false, true, "ss_kaldi_c256<" TAG ",mfcc") : SS_K(NE, false, false, "ss_kaldi_c256<" TAG ",fbank");
@@ -62,6 +69,18 @@ hipError_t launch_kaldi_c256_varlen(const KaldiArgs &a, const KaldiVarlenArgs &v
 {
     if (!v.so || !v.fo || v.n_clips == 0) return hipErrorInvalidValue;
     return launch_k<true>(a, v, stream, num_cus, info);
+}
+
+hipError_t launch_kaldi_c256(const KaldiArgs &a, const KaldiPcmArgs &p, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    if (!p.x || (reinterpret_cast<uintptr_t>(p.x) & 1u)) return hipErrorInvalidValue;
+    return launch_k<false>(a, KaldiVarlenArgs{}, stream, num_cus, info, p);
+}
+
+hipError_t launch_kaldi_c256_varlen(const KaldiArgs &a, const KaldiVarlenPcmArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info)
+{
+    if (!v.v.so || !v.v.fo || v.v.n_clips == 0 || !v.x || (reinterpret_cast<uintptr_t>(v.x) & 1u)) return hipErrorInvalidValue;
+    return launch_k<true>(a, v.v, stream, num_cus, info, v);
 }
 
 }  // namespace ss

@@ -2,7 +2,7 @@
 // stream states, fed ragged float or 16-bit PCM chunks.  The kernel is ss_kaldi_body.h's one template -- the same conditioning stage,
 // FFT, untangle, mel, ln and DCT as the dense and packed builds of ss_kaldi512.hip, which is what makes a stream's rows bit for bit
 // the dense call's on zeros(S) ++ stream -- with the pool's row lookup and loader (load_quad_pool) in front.  A translation unit of
-// its own: 24 more builds, {NE 10, 13, 16} x {pow2, magnitude} x {fbank, mfcc} x {float, PCM}, next to the 24 of ss_kaldi512.hip.
+// its own: 24 more builds, {NE 10, 13, 16} x {pow2, magnitude} x {fbank, mfcc} x {float, PCM}, next to the 48 of ss_kaldi512.hip.
 // The state advance is not here: it is the frame pool's second launch (launch_stream_advance_packed) over the same entry block.
 #include "ss_kaldi_body.h"
 

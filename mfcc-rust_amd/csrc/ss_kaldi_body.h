@@ -3,6 +3,8 @@
 // and the stores -- exists here once, so that a frame's bits do not depend on where its samples came from.  What a source kind
 // (KSrc) adds is its row lookup and its loader:
 //   * kDense / kVarlen: frame_src + load_quad_k (see ss_kaldi512.hip's header).
+//   * kDensePcm / kVarlenPcm (a KaldiPcmArgs / KaldiVarlenPcmArgs in the trailing pack): frame_src over the int16 buffer +
+//     load_quad_pcm -- one raw dword per sample pair at any parity, converted where the body consumes vin[].
 //   * kPool / kPoolPcm (a FrameStreamPackedArgs / FrameStreamPackedPcmArgs in the kernel's trailing argument pack): the flat work
 //     list is the packed output rows of a ragged streaming launch; a row is the tail of its entry's pool row followed by the head
 //     of its chunk (load_quad_pool below).
@@ -52,7 +54,7 @@ __device__ __forceinline__ KClip kaldi_clip(const KaldiVarlenArgs &v, uint32_t f
 }
 
 // The source kinds of the body
-enum KSrc : int { kDense = 0, kVarlen = 1, kPool = 2, kPoolPcm = 3 };
+enum KSrc : int { kDense = 0, kVarlen = 1, kPool = 2, kPoolPcm = 3, kDensePcm = 4, kVarlenPcm = 5 };
 
 // The owner (clip of a packed launch, entry of a pool launch) of row g = q4 + 0..3 over the row offsets `off`: the owner of the
 // quad's first row from the wave's forward cursor (claims only increase), then at most three owners WITH rows further on.
@@ -74,8 +76,11 @@ __device__ __forceinline__ unsigned row_owner(const long long *off, unsigned n, 
 
 // Where this lane group's frame starts and whether it exists.  Dense: lanes past the last frame redo it.  VARLEN: `cursor` is the
 // wave's clip of its last quad's first row (claims only increase); a lane's frame lies at most three clips WITH rows further on.
-template <bool VARLEN>
-__device__ __forceinline__ const float *frame_src(const KaldiArgs &a, const KaldiVarlenArgs &v, unsigned quad, unsigned total, int f, unsigned &cursor, bool &ok)
+// x: the call's samples, floats (a.x) or int16 (the PCM pack's): the offsets are in samples either way.  (Taken by reference, as
+// `a` is: the float builds then compile to the instruction streams they had when this read a.x itself.)
+template <bool VARLEN, typename T>
+__device__ __forceinline__ const T *frame_src(const T *const &x, const KaldiArgs &a, const KaldiVarlenArgs &v, unsigned quad, unsigned total, int f, unsigned &cursor,
+                                              bool &ok)
 {
     const unsigned q4 = quad * 4;                                           // uniform
     const unsigned g = q4 + min(static_cast<unsigned>(f), total - 1 - q4);  // lanes past the last row redo it
@@ -84,12 +89,12 @@ __device__ __forceinline__ const float *frame_src(const KaldiArgs &a, const Kald
         const KClip cl = kaldi_clip(v, a.flen, a.step, c);
         const long long tl = static_cast<long long>(g) - cl.f0;
         ok = cl.ok && tl >= 0 && tl < static_cast<long long>(cl.T);
-        return a.x + (ok ? cl.s0 + tl * static_cast<long long>(a.step) : 0ll);
+        return x + (ok ? cl.s0 + tl * static_cast<long long>(a.step) : 0ll);
     } else {
         unsigned clip, t;
         locate_frame(q4, g - q4, a.n_frames, a.nf_magic, a.nf_shift, clip, t);
         ok = true;
-        return a.x + static_cast<unsigned long long>(clip) * a.ld + static_cast<unsigned long long>(t) * a.step;
+        return x + static_cast<unsigned long long>(clip) * a.ld + static_cast<unsigned long long>(t) * a.step;
     }
 }
 
@@ -127,6 +132,31 @@ __device__ __forceinline__ void load_quad_k(const float *src, bool ok, uint32_t 
                 if (rem >= 1) vin[e].x = p[32 * e];
                 if (rem >= 2) vin[e].y = p[32 * e + 1];
             }
+        }
+    }
+}
+
+// The PCM form of load_quad_k: pair n = j + 16 e of the frame at src is ONE dword at 2-byte alignment (pcm_raw_pair), whatever the
+// parity of the frame start -- odd ld, odd clip offset, odd shift, odd base -- so there is no pair / single split.  The dword stays
+// raw in the pair's .x; the body converts it (pcm_pair) at the top of the iteration that consumes vin[]: converting here would wait
+// for the loads right behind pass 1.  An odd frame length's half pair is one 16-bit load, kept as the low half of a raw word whose
+// high half is zero (pcm_pair makes it (sample, 0)).  A raw zero is the pair (0, 0): beyond flen, and for a frame that does not
+// exist, nothing is fetched -- a frame that ends on the buffer's last sample reads nothing past it.
+template <int NE>
+__device__ __forceinline__ void load_quad_pcm(const int16_t *src, bool ok, uint32_t flen, int j, float2 (&vin)[NE])
+{
+#pragma unroll
+    for (int e = 0; e < NE; ++e) vin[e] = make_float2(0.f, 0.f);
+    if (!ok) return;
+    const int16_t *p = src + 2 * j;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        if (e < NE - 3) {
+            vin[e].x = pcm_raw_pair(p + 32 * e);
+        } else {
+            const int rem = static_cast<int>(flen) - 2 * (j + 16 * e);
+            if (rem >= 2) vin[e].x = pcm_raw_pair(p + 32 * e);
+            else if (rem == 1) vin[e].x = __int_as_float(static_cast<int>(static_cast<uint16_t>(p[32 * e])));
         }
     }
 }
@@ -211,35 +241,47 @@ __device__ __forceinline__ void load_quad_pool(const KaldiArgs &a, const SPT &sp
     }
 }
 
-// The pool argument of a launch: the one element of the kernel's trailing pack, or nothing
+// The trailing argument of a launch (the pool's, or the PCM samples'): the one element of the kernel's trailing pack, or nothing
 struct NoPool {};
 __device__ __forceinline__ NoPool pack_first() { return {}; }
 template <typename T>
 __device__ __forceinline__ const T &pack_first(const T &t) { return t; }
+
+// the clip tables of a packed launch: the kernel's own argument, or the ones the packed PCM pack carries
+template <typename PL>
+__device__ __forceinline__ const KaldiVarlenArgs &varlen_block(const KaldiVarlenArgs &vl, const PL &) { return vl; }
+__device__ __forceinline__ const KaldiVarlenArgs &varlen_block(const KaldiVarlenArgs &, const KaldiVarlenPcmArgs &p) { return p.v; }
 
 // the loads of `quad` for this lane group, whatever the source kind
 template <int NE, int SRC, typename PL>
 __device__ __forceinline__ void load_quad_any(const KaldiArgs &a, const KaldiVarlenArgs &vl, const PL &pl, unsigned quad, unsigned total, int f, int j,
                                               unsigned &cursor, float2 (&vin)[NE], bool &ok, int &raw_from)
 {
-    if constexpr (SRC >= kPool) {
+    if constexpr (SRC == kPool || SRC == kPoolPcm) {
         load_quad_pool<NE>(a, pl, quad, total, f, j, cursor, vin, ok, raw_from);
+    } else if constexpr (SRC == kDensePcm || SRC == kVarlenPcm) {
+        const int16_t *src = frame_src<SRC == kVarlenPcm>(pl.x, a, vl, quad, total, f, cursor, ok);
+        load_quad_pcm<NE>(src, ok, a.flen, j, vin);
     } else {
-        const float *src = frame_src<SRC == kVarlen>(a, vl, quad, total, f, cursor, ok);
+        const float *src = frame_src<SRC == kVarlen>(a.x, a, vl, quad, total, f, cursor, ok);
         load_quad_k<NE, SRC == kVarlen>(src, ok, a.flen, j, vin);
     }
 }
 
 // SP: empty (equal-length clips, or packed clips with VARLEN), or the pool's argument -- one FrameStreamPackedArgs (float chunks: a.x)
-// or one FrameStreamPackedPcmArgs (16-bit PCM chunks); the pool builds leave VARLEN false and vl unused.
+// or one FrameStreamPackedPcmArgs (16-bit PCM chunks); the pool builds leave VARLEN false and vl unused -- or the 16-bit PCM samples
+// of a one-shot call: one KaldiPcmArgs (equal-length clips), or with VARLEN one KaldiVarlenPcmArgs (packed clips: its tables, vl unused).
 template <int NE, bool POW2, bool MFCC, bool VARLEN, int WAVES, typename... SP>
 __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, const KaldiVarlenArgs vl, const SP... sp)
 {
     constexpr bool PCM = (std::is_same_v<SP, FrameStreamPackedPcmArgs> || ...);
     constexpr bool POOL = PCM || (std::is_same_v<SP, FrameStreamPackedArgs> || ...);
-    constexpr int SRC = PCM ? kPoolPcm : POOL ? kPool : VARLEN ? kVarlen : kDense;
-    static_assert(sizeof...(SP) == (POOL ? 1 : 0) && !(POOL && VARLEN), "one pool argument, or none");
+    constexpr bool DPCM = (std::is_same_v<SP, KaldiPcmArgs> || ...), VPCM = (std::is_same_v<SP, KaldiVarlenPcmArgs> || ...);
+    constexpr int SRC = PCM ? kPoolPcm : POOL ? kPool : VPCM ? kVarlenPcm : DPCM ? kDensePcm : VARLEN ? kVarlen : kDense;
+    static_assert(sizeof...(SP) == (POOL || DPCM || VPCM ? 1 : 0) && !(POOL && VARLEN), "one pool argument, or none");
+    static_assert(!(DPCM && VARLEN) && (!VPCM || VARLEN), "the PCM pack follows the layout");
     [[maybe_unused]] const auto &pl = pack_first(sp...);
+    [[maybe_unused]] const KaldiVarlenArgs &vt = varlen_block(vl, pl);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
@@ -261,7 +303,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
 
     unsigned total;
     if constexpr (POOL) total = pool_block(pl).total_rows;
-    else total = VARLEN ? static_cast<unsigned>(vl.total_frames) : a.batch * a.n_frames;
+    else total = VARLEN ? static_cast<unsigned>(vt.total_frames) : a.batch * a.n_frames;
     const unsigned quads = (total + 3) / 4;
     const unsigned q_lo = static_cast<unsigned>(static_cast<unsigned long long>(quads) * blockIdx.x / gridDim.x);
     const unsigned q_hi = static_cast<unsigned>(static_cast<unsigned long long>(quads) * (blockIdx.x + 1) / gridDim.x);
@@ -270,15 +312,15 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
     if constexpr (VARLEN) {
         // one pass over the clips, spread over the grid: an inconsistent clip raises the error word (a vector store to the pinned word)
         bool bad = false;
-        for (unsigned b = blockIdx.x * (WAVES * 64) + tid; b < vl.n_clips; b += gridDim.x * (WAVES * 64)) bad |= !kaldi_clip(vl, a.flen, a.step, b).ok;
-        if (bad && vl.err) __hip_atomic_store(vl.err, kVarlenError, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        for (unsigned b = blockIdx.x * (WAVES * 64) + tid; b < vt.n_clips; b += gridDim.x * (WAVES * 64)) bad |= !kaldi_clip(vt, a.flen, a.step, b).ok;
+        if (bad && vt.err) __hip_atomic_store(vt.err, kVarlenError, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     // one pass over the entries, spread over the grid: a bad entry raises the error word (stream_check_entries: a vector store)
     if constexpr (POOL) stream_check_entries(pool_block(pl), blockIdx.x * (WAVES * 64) + tid, gridDim.x * (WAVES * 64));
     unsigned quad = __builtin_amdgcn_readfirstlane(q_lo + wave);  // uniform: kept scalar
     unsigned cursor = 0;
     if constexpr (VARLEN) {
-        if (quad < q_hi) cursor = offset_find(vl.fo, vl.n_clips, static_cast<long long>(quad) * 4);
+        if (quad < q_hi) cursor = offset_find(vt.fo, vt.n_clips, static_cast<long long>(quad) * 4);
     }
     if constexpr (POOL) {
         if (quad < q_hi) cursor = offset_find(pool_block(pl).ro, pool_block(pl).n_active, static_cast<long long>(quad) * 4);
@@ -286,7 +328,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
     float2 vin[NE];
     bool ok_next = false;
     [[maybe_unused]] int raw_next = kNoRaw;  // PCM pool builds: which of vin[]'s pairs are raw dwords (load_quad_pool)
-    if (quad < q_hi) load_quad_any<NE, SRC>(a, vl, pl, quad, total, f, j, cursor, vin, ok_next, raw_next);
+    if (quad < q_hi) load_quad_any<NE, SRC>(a, vt, pl, quad, total, f, j, cursor, vin, ok_next, raw_next);
 
     const int paddr = partner_addr(lane, j), wbase1 = exchange_write_base(j);
     const int Cc = static_cast<int>(a.n_ceps), M = static_cast<int>(a.n_filters);
@@ -325,6 +367,11 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
 #pragma unroll
                 for (int e = 0; e < NE; ++e)
                     if (raw_next + 2 * (j + 16 * e) >= 0) s[e] = pcm_pair(__float_as_int(s[e].x), pl.scale);
+            }
+            if constexpr (SRC == kDensePcm || SRC == kVarlenPcm) {
+                // every pair is a raw dword (load_quad_pcm; a raw zero is the float loader's zero pair)
+#pragma unroll
+                for (int e = 0; e < NE; ++e) s[e] = pcm_pair(__float_as_int(s[e].x), pl.scale);
             }
             if (a.input_scale != 1.0f) {
 #pragma unroll
@@ -380,7 +427,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_kaldi_c256(const KaldiArgs a, c
         }
         // ---- 256-point complex FFT of the packed frame; the next quad's samples go into the dead input registers ----
         pass1(v, zh, wbase1);
-        if (next < q_hi) load_quad_any<NE, SRC>(a, vl, pl, next, total, f, j, cursor, vin, ok_next, raw_next);
+        if (next < q_hi) load_quad_any<NE, SRC>(a, vt, pl, next, total, f, j, cursor, vin, ok_next, raw_next);
         float2 u[16];
         pass2(u, zh, j, s_tw2);
 

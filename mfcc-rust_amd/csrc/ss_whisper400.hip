@@ -23,6 +23,12 @@
 // dropped when it is claimed, and so is a second pass.  ss_whisper_floor_kernel writes them: for every element of out it takes the
 // stored l, or -10 for a silent frame, and stores conv(fmaf(max(l, mx - 8), 0.25f, 1.0f)) with 16-byte stores.
 //
+// 16-bit PCM (ss_whisper_log_mel*_i16*): ss_whisper_c200<int16_t>, reported as ss_whisper_c200i.  Sample k is (float)x[k] * scale,
+// scale a power of two (the product is exact).  An interior pass fetches every pair as ONE dword at 2-byte alignment (pcm_raw_pair)
+// and converts it on the spot -- this kernel does not prefetch across iterations -- so one path serves either parity of the clip's
+// first sample; an edge pass reads single 16-bit samples through the same reflect / live tests.  Everything behind the load is the
+// float build's text, so the bits are the float call's on the converted samples.  The keys and floor kernels never read x.
+//
 // The whole file is compiled with fp contract(off): every fused operation is an explicit fmaf, and the dense and the packed call
 // are the SAME kernel (a null table selects the dense addressing), so they cannot round differently.
 #include "ss_device.h"
@@ -50,8 +56,9 @@ using namespace whisper;
 
 constexpr unsigned kWhisperError = 4u;  // the handle's error word after a bad table entry
 
+template <typename T>  // T: float, or int16_t (16-bit PCM times `scale`)
 struct WhisperArgs {
-    const float *x;
+    const T *x;
     const long long *so;  // [n_clips + 1] sample offsets of the packed call; null: dense rows
     unsigned long long ld;  // dense: row stride
     uint32_t n_samples;     // dense: min(n_samples, N)
@@ -60,22 +67,25 @@ struct WhisperArgs {
     float *inter;  // [n_clips x M x n_frames] f32: out itself (SS_PAD_F32) or the caller's scratch
     int *keys;     // [n_clips]
     uint32_t q_base, q_rem;  // split_units of n_clips * units_per_clip(n_frames) over the grid
+    float scale;             // PCM build: the power-of-two sample scale (float build: unused)
 };
 
 // live samples L = min(len, N) of clip c and its first sample; a bad table entry is an empty clip (ok = false)
+template <typename T>
 struct Clip {
-    const float *x;
+    const T *x;
     uint32_t L;
     bool ok;
 };
-__device__ __forceinline__ Clip clip_of(const float *x, const long long *so, unsigned long long ld, uint32_t n_samples, uint32_t n_frames, uint32_t c)
+template <typename T>
+__device__ __forceinline__ Clip<T> clip_of(const T *x, const long long *so, unsigned long long ld, uint32_t n_samples, uint32_t n_frames, uint32_t c)
 {
     const uint32_t N = n_frames * kHop;
-    if (!so) return Clip{x + static_cast<size_t>(c) * ld, n_samples < N ? n_samples : N, true};
+    if (!so) return Clip<T>{x + static_cast<size_t>(c) * ld, n_samples < N ? n_samples : N, true};
     const long long lo = so[c], hi = so[c + 1];
-    if (lo < 0 || hi < lo) return Clip{x, 0u, false};
+    if (lo < 0 || hi < lo) return Clip<T>{x, 0u, false};
     const unsigned long long len = static_cast<unsigned long long>(hi - lo);
-    return Clip{x + lo, len < N ? static_cast<uint32_t>(len) : N, true};
+    return Clip<T>{x + lo, len < N ? static_cast<uint32_t>(len) : N, true};
 }
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(fmaf(-a.y, b.y, a.x * b.x), fmaf(a.y, b.x, a.x * b.y)); }
@@ -166,8 +176,10 @@ __global__ __launch_bounds__(256) void ss_whisper_keys_kernel(const long long *_
     if (lengths) lengths[c] = len;
 }
 
-__global__ __launch_bounds__(kWaves * 64) void ss_whisper_c200(WhisperArgs a)
+template <typename T>
+__global__ __launch_bounds__(kWaves * 64) void ss_whisper_c200(WhisperArgs<T> a)
 {
+    constexpr bool PCM = std::is_same_v<T, int16_t>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *s_tab = reinterpret_cast<float *>(smem);
     unsigned *s_next = reinterpret_cast<unsigned *>(s_tab + layout::kFloats);
@@ -213,12 +225,13 @@ __global__ __launch_bounds__(kWaves * 64) void ss_whisper_c200(WhisperArgs a)
         if (u >= count) break;
         const uint32_t unit = b + u * gridDim.x;
         const uint32_t c = unit / upc, t0 = (unit - c * upc) * kUnitFrames;  // uniform
-        const Clip clip = clip_of(a.x, a.so, a.ld, a.n_samples, a.n_frames, c);
+        const Clip<T> clip = clip_of(a.x, a.so, a.ld, a.n_samples, a.n_frames, c);
         const uint32_t L = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(clip.L)));
         const uint32_t limit = first_silent(L, a.n_frames);  // frames t >= limit are silent (or past the end)
         if (t0 >= limit) continue;                            // a silent unit: nothing is loaded, transformed or stored
-        const float *xb = clip.x;
-        const bool pair_ok = (reinterpret_cast<uintptr_t>(xb) & 7u) == 0;  // uniform: the clip's even samples sit on 8-byte boundaries
+        const T *xb = clip.x;
+        // uniform: the clip's even samples sit on 8-byte boundaries (a PCM pair is one dword at any parity: no split)
+        [[maybe_unused]] const bool pair_ok = (reinterpret_cast<uintptr_t>(xb) & 7u) == 0;
         float lmax = kLogFloor;
 
 #pragma unroll 1
@@ -230,19 +243,24 @@ __global__ __launch_bounds__(kWaves * 64) void ss_whisper_c200(WhisperArgs a)
             const int i0 = t * static_cast<int>(kHop) - static_cast<int>(kHalf) + 2 * j;  // the lane's first raw sample index
             // interior: every raw index of the pass's eight frames is a live sample of the clip
             const bool interior = tp * kHop >= kHalf && (tp + kPassFrames - 1) * kHop + kHalf <= L;
-            if (interior && pair_ok) {
+            if (interior && (PCM || pair_ok)) {
 #pragma unroll
-                for (int m = 0; m < 25; ++m) v[m] = *reinterpret_cast<const float2 *>(xb + i0 + 16 * m);
-            } else if (interior) {
+                for (int m = 0; m < 25; ++m) {
+                    if constexpr (PCM) v[m] = pcm_pair(__float_as_int(pcm_raw_pair(xb + i0 + 16 * m)), a.scale);
+                    else v[m] = *reinterpret_cast<const float2 *>(xb + i0 + 16 * m);
+                }
+            } else if (interior) {  // (float build only: a PCM pair is one dword at either parity)
 #pragma unroll
-                for (int m = 0; m < 25; ++m) v[m] = make_float2(xb[i0 + 16 * m], xb[i0 + 16 * m + 1]);
+                for (int m = 0; m < 25; ++m) v[m] = make_float2(static_cast<float>(xb[i0 + 16 * m]), static_cast<float>(xb[i0 + 16 * m + 1]));
             } else {
                 const bool live = static_cast<uint32_t>(t) < a.n_frames;
 #pragma unroll
                 for (int m = 0; m < 25; ++m) {
                     const int ia = reflect(i0 + 16 * m, N), ib = reflect(i0 + 16 * m + 1, N);
                     const bool oka = live && static_cast<uint32_t>(ia) < L, okb = live && static_cast<uint32_t>(ib) < L;
-                    const float xa = xb[oka ? ia : 0], xc = xb[okb ? ib : 0];  // L > 0 here: sample 0 exists
+                    float xa, xc;  // L > 0 here: sample 0 exists
+                    if constexpr (PCM) xa = pcm_sample(xb, oka ? ia : 0, a.scale), xc = pcm_sample(xb, okb ? ib : 0, a.scale);
+                    else xa = xb[oka ? ia : 0], xc = xb[okb ? ib : 0];
                     v[m] = make_float2(oka ? xa : 0.f, okb ? xc : 0.f);
                 }
             }
@@ -354,7 +372,7 @@ __global__ __launch_bounds__(256) void ss_whisper_floor_kernel(const float *inte
 {
     constexpr unsigned ES = DT == SS_PAD_F32 ? 4 : 2, VE = 16 / ES;
     const uint32_t c = blockIdx.x;
-    const Clip clip = clip_of(nullptr, so, 0, dense_len, n_frames, c);
+    const Clip<float> clip = clip_of(static_cast<const float *>(nullptr), so, 0, dense_len, n_frames, c);
     const uint32_t limit = first_silent(clip.L, n_frames);
     const float thr = key_float(keys[c]) - 8.0f;
     const uint32_t block = n_mels * n_frames;  // < 2^31 (checked by the host)
@@ -439,8 +457,9 @@ size_t elem_bytes(int dtype) { return dtype == SS_PAD_F32 ? 4 : 2; }
 // the kernels form 160 (t + 16) in 32-bit integers
 constexpr size_t kMaxFrames = ((1ull << 31) - 1) / ss::whisper::kHop - 16;
 
-// what needs no device: the sizes, the types and the pointers' alignment
-int whisper_check(const ss_whisper_config *cfg, const float *x, size_t n_clips, size_t n_frames, int dtype, const void *work, const void *out)
+// what needs no device: the sizes, the types and the pointers' alignment (T: float samples, or int16_t -- 16-bit PCM)
+template <typename T>
+int whisper_check(const ss_whisper_config *cfg, const T *x, size_t n_clips, size_t n_frames, int dtype, const void *work, const void *out)
 {
     if (dtype != SS_PAD_F32 && dtype != SS_PAD_F16 && dtype != SS_PAD_BF16) return fail(SS_ERR_ARG, "dtype must be SS_PAD_F32, SS_PAD_F16 or SS_PAD_BF16");
     if (n_frames < 2) return fail(SS_ERR_ARG, "n_frames must be at least 2");
@@ -451,7 +470,7 @@ int whisper_check(const ss_whisper_config *cfg, const float *x, size_t n_clips, 
     if (static_cast<unsigned long long>(n_clips) * ss::whisper::units_per_clip(static_cast<uint32_t>(n_frames)) >= 0xffffffffull)
         return fail(SS_ERR_ARG, "n_clips * ceil(n_frames / 16) must fit the 32-bit unit counter");
     if (!x || !out || (dtype != SS_PAD_F32 && !work)) return fail(SS_ERR_ARG, "null buffer");
-    if (reinterpret_cast<uintptr_t>(x) % 4) return fail(SS_ERR_ARG, "x must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(x) % sizeof(T)) return fail(SS_ERR_ARG, sizeof(T) == 4 ? "x must be 4-byte aligned" : "x must be 2-byte aligned");
     if (reinterpret_cast<uintptr_t>(out) % 16 || (dtype != SS_PAD_F32 && reinterpret_cast<uintptr_t>(work) % 16))
         return fail(SS_ERR_ARG, "out and work must be 16-byte aligned");
     return SS_OK;
@@ -470,10 +489,14 @@ hipError_t launch_floor(const float *inter, const long long *so, uint32_t dense_
     return hipGetLastError();
 }
 
-// the three launches; so == nullptr: dense rows of n_samples with stride ld
-int whisper_launch(const ss_whisper_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_so, size_t n_samples, size_t ld, size_t n_frames, int dtype,
-                   void *d_work, void *d_out, int32_t *d_lengths, hipStream_t stream)
+// the three launches; so == nullptr: dense rows of n_samples with stride ld.  T = int16_t: the PCM build of the middle one (sample k is
+// (float)x[k] * scale; the keys and floor kernels never read x)
+template <typename T>
+int whisper_launch(const ss_whisper_config *cfg, const T *d_x, float scale, size_t n_clips, const int64_t *d_so, size_t n_samples, size_t ld, size_t n_frames,
+                   int dtype, void *d_work, void *d_out, int32_t *d_lengths, hipStream_t stream)
 {
+    constexpr bool PCM = std::is_same_v<T, int16_t>;
+    constexpr const char *kName = PCM ? "ss_whisper_c200i" : "ss_whisper_c200";
     using namespace ss::whisper;
     const uint32_t N = static_cast<uint32_t>(n_frames * kHop), nc = static_cast<uint32_t>(n_clips), nf = static_cast<uint32_t>(n_frames);
     const uint32_t dense_len = static_cast<uint32_t>(n_samples < N ? n_samples : N);
@@ -488,7 +511,7 @@ int whisper_launch(const ss_whisper_config *cfg, const float *d_x, size_t n_clip
     const unsigned long long units = static_cast<unsigned long long>(nc) * units_per_clip(nf);
     const unsigned grid = ss::cu_capped_grid(units, kWaves, cfg->num_cus);
     const ss::UnitSplit sp = ss::split_units(units, grid);
-    ss::WhisperArgs a{};
+    ss::WhisperArgs<T> a{};
     a.x = d_x;
     a.so = so;
     a.ld = ld;
@@ -501,15 +524,101 @@ int whisper_launch(const ss_whisper_config *cfg, const float *d_x, size_t n_clip
     a.keys = cfg->d_keys;
     a.q_base = sp.q_base;
     a.q_rem = sp.q_rem;
-    e = ss::launch_kernel(ss::ss_whisper_c200, "ss_whisper_c200", grid, kWaves, kLdsBytes, stream, nullptr, a);
-    if (e != hipSuccess) return hip_fail(e, "ss_whisper_c200");
+    a.scale = scale;
+    e = ss::launch_kernel(ss::ss_whisper_c200<T>, kName, grid, kWaves, kLdsBytes, stream, nullptr, a);
+    if (e != hipSuccess) return hip_fail(e, kName);
 
     if (dtype == SS_PAD_F32) e = launch_floor<SS_PAD_F32>(inter, so, dense_len, nc, nf, a.n_mels, cfg->d_keys, d_out, stream);
     else if (dtype == SS_PAD_F16) e = launch_floor<SS_PAD_F16>(inter, so, dense_len, nc, nf, a.n_mels, cfg->d_keys, d_out, stream);
     else e = launch_floor<SS_PAD_BF16>(inter, so, dense_len, nc, nf, a.n_mels, cfg->d_keys, d_out, stream);
     if (e != hipSuccess) return hip_fail(e, "ss_whisper_floor_kernel");
-    ss::note_kernel("ss_whisper_c200");
+    ss::note_kernel(kName);
     return SS_OK;
+}
+
+// The device and host forms, once for float samples and once for 16-bit PCM (pcm: the scale; checked first among the data checks,
+// every other rule in the float call's order).
+template <typename T>
+int whisper_dense_device(const ss_whisper_config *cfg, const T *d_x, const float *pcm, size_t batch, size_t n_samples, size_t ld, size_t n_frames, int dtype,
+                         void *d_work, void *d_out, hipStream_t stream)
+{
+    if (pcm)
+        if (int rc = ss::check_pcm_scale(*pcm)) return rc;
+    if (batch == 0) return SS_OK;
+    // a clip without samples reads nothing: any non-null x will do, and ld is not used
+    if (int rc = whisper_check(cfg, d_x, batch, n_frames, dtype, d_work, d_out)) return rc;
+    if (ld < n_samples) return fail(SS_ERR_ARG, "ld must be at least n_samples");
+    if (int rc = whisper_ready(cfg)) return rc;
+    return whisper_launch(cfg, d_x, pcm ? *pcm : 1.0f, batch, nullptr, n_samples, ld, n_frames, dtype, d_work, d_out, nullptr, stream);
+}
+
+template <typename T>
+int whisper_packed_device(const ss_whisper_config *cfg, const T *d_x, const float *pcm, size_t n_clips, const int64_t *d_sample_offsets, size_t n_frames,
+                          int dtype, void *d_work, void *d_out, int32_t *d_lengths, hipStream_t stream)
+{
+    if (pcm)
+        if (int rc = ss::check_pcm_scale(*pcm)) return rc;
+    if (n_clips == 0) return SS_OK;
+    if (int rc = whisper_check(cfg, d_x, n_clips, n_frames, dtype, d_work, d_out)) return rc;
+    if (!d_sample_offsets) return fail(SS_ERR_ARG, "null buffer");
+    if (reinterpret_cast<uintptr_t>(d_sample_offsets) % 8 || reinterpret_cast<uintptr_t>(d_lengths) % 4)
+        return fail(SS_ERR_ARG, "sample_offsets must be 8-byte and lengths 4-byte aligned");
+    if (int rc = whisper_ready(cfg)) return rc;
+    return whisper_launch(cfg, d_x, pcm ? *pcm : 1.0f, n_clips, d_sample_offsets, 0, 0, n_frames, dtype, d_work, d_out, d_lengths, stream);
+}
+
+// host-pointer forms (synchronous): everything on the device for the length of one call; PCM crosses the link as int16
+template <typename T>
+int whisper_dense_host(const ss_whisper_config *cfg, const T *x, const float *pcm, size_t batch, size_t n_samples, size_t ld, size_t n_frames, int dtype, void *out)
+{
+    if (pcm)
+        if (int rc = ss::check_pcm_scale(*pcm)) return rc;
+    if (batch == 0) return SS_OK;
+    if (!cfg) return fail(SS_ERR_ARG, "null handle");
+    if (dtype != SS_PAD_F32 && dtype != SS_PAD_F16 && dtype != SS_PAD_BF16) return fail(SS_ERR_ARG, "dtype must be SS_PAD_F32, SS_PAD_F16 or SS_PAD_BF16");
+    if (!x || !out) return fail(SS_ERR_ARG, "null buffer");
+    if (n_frames < 2 || n_frames > kMaxFrames) return fail(SS_ERR_ARG, "n_frames must be at least 2 and n_frames * 160 below 2^31");
+    if (ld < n_samples) return fail(SS_ERR_ARG, "ld must be at least n_samples");
+    if (!ss::have_device()) return ss::no_device("hot path");
+    const size_t in_samples = (batch - 1) * ld + n_samples, block = batch * cfg->params.n_mels * n_frames;
+    ss::HostStage st(pcm ? "ss_whisper_log_mel_i16" : "ss_whisper_log_mel");
+    const T *d_in = st.up(x, in_samples * sizeof(T));
+    void *d_out = st.room<void>(block * elem_bytes(dtype));
+    void *d_work = dtype != SS_PAD_F32 ? st.room<void>(block * sizeof(float)) : nullptr;
+    if (st.ok()) st.ran(whisper_dense_device(cfg, d_in, pcm, batch, n_samples, ld, n_frames, dtype, d_work, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, block * elem_bytes(dtype));
+    return st.status();
+}
+
+template <typename T>
+int whisper_packed_host(const ss_whisper_config *cfg, const T *x, const float *pcm, size_t n_clips, const int64_t *sample_offsets, size_t n_frames, int dtype,
+                        void *out, int32_t *lengths)
+{
+    if (pcm)
+        if (int rc = ss::check_pcm_scale(*pcm)) return rc;
+    if (n_clips == 0) return SS_OK;
+    if (!cfg) return fail(SS_ERR_ARG, "null handle");
+    if (dtype != SS_PAD_F32 && dtype != SS_PAD_F16 && dtype != SS_PAD_BF16) return fail(SS_ERR_ARG, "dtype must be SS_PAD_F32, SS_PAD_F16 or SS_PAD_BF16");
+    if (!x || !out || !sample_offsets) return fail(SS_ERR_ARG, "null buffer");
+    if (n_frames < 2 || n_frames > kMaxFrames) return fail(SS_ERR_ARG, "n_frames must be at least 2 and n_frames * 160 below 2^31");
+    // the host sees the table: the samples that come up are those of its good entries (a bad entry is contained on the device)
+    int64_t top = 0;
+    for (size_t b = 0; b < n_clips; ++b)
+        if (sample_offsets[b] >= 0 && sample_offsets[b + 1] >= sample_offsets[b] && sample_offsets[b + 1] > top) top = sample_offsets[b + 1];
+    if (!ss::have_device()) return ss::no_device("hot path");
+    const size_t in_samples = static_cast<size_t>(top), block = n_clips * cfg->params.n_mels * n_frames;
+    ss::HostStage st(pcm ? "ss_whisper_log_mel_packed_i16" : "ss_whisper_log_mel_packed");
+    const T *d_in = st.up(x, in_samples * sizeof(T));
+    void *d_out = st.room<void>(block * elem_bytes(dtype));
+    void *d_work = dtype != SS_PAD_F32 ? st.room<void>(block * sizeof(float)) : nullptr;
+    const int64_t *d_so = st.up(sample_offsets, (n_clips + 1) * sizeof(int64_t));
+    int32_t *d_len = st.room<int32_t>(n_clips * sizeof(int32_t));
+    if (st.ok()) st.ran(whisper_packed_device(cfg, d_in, pcm, n_clips, d_so, n_frames, dtype, d_work, d_out, d_len, nullptr));
+    st.sync();
+    st.down(out, d_out, block * elem_bytes(dtype));
+    if (lengths) st.down(lengths, d_len, n_clips * sizeof(int32_t));
+    return st.ok() ? whisper_pending_error(cfg) : st.status();
 }
 
 }  // namespace
@@ -574,72 +683,49 @@ int ss_whisper_config_device_status(const ss_whisper_config *cfg)
 int ss_whisper_log_mel_device(const ss_whisper_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld, size_t n_frames, int dtype, void *d_work,
                               void *d_out, void *stream)
 {
-    if (batch == 0) return SS_OK;
-    // a clip without samples reads nothing: any non-null x will do, and ld is not used
-    if (int rc = whisper_check(cfg, d_x, batch, n_frames, dtype, d_work, d_out)) return rc;
-    if (ld < n_samples) return fail(SS_ERR_ARG, "ld must be at least n_samples");
-    if (int rc = whisper_ready(cfg)) return rc;
-    return whisper_launch(cfg, d_x, batch, nullptr, n_samples, ld, n_frames, dtype, d_work, d_out, nullptr, static_cast<hipStream_t>(stream));
+    return whisper_dense_device(cfg, d_x, nullptr, batch, n_samples, ld, n_frames, dtype, d_work, d_out, static_cast<hipStream_t>(stream));
 }
 
 int ss_whisper_log_mel_packed_device(const ss_whisper_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets, size_t n_frames, int dtype,
                                      void *d_work, void *d_out, int32_t *d_lengths, void *stream)
 {
-    if (n_clips == 0) return SS_OK;
-    if (int rc = whisper_check(cfg, d_x, n_clips, n_frames, dtype, d_work, d_out)) return rc;
-    if (!d_sample_offsets) return fail(SS_ERR_ARG, "null buffer");
-    if (reinterpret_cast<uintptr_t>(d_sample_offsets) % 8 || reinterpret_cast<uintptr_t>(d_lengths) % 4)
-        return fail(SS_ERR_ARG, "sample_offsets must be 8-byte and lengths 4-byte aligned");
-    if (int rc = whisper_ready(cfg)) return rc;
-    return whisper_launch(cfg, d_x, n_clips, d_sample_offsets, 0, 0, n_frames, dtype, d_work, d_out, d_lengths, static_cast<hipStream_t>(stream));
+    return whisper_packed_device(cfg, d_x, nullptr, n_clips, d_sample_offsets, n_frames, dtype, d_work, d_out, d_lengths, static_cast<hipStream_t>(stream));
 }
 
-// host-pointer forms (synchronous): everything on the device for the length of one call
 int ss_whisper_log_mel(const ss_whisper_config *cfg, const float *x, size_t batch, size_t n_samples, size_t ld, size_t n_frames, int dtype, void *out)
 {
-    if (batch == 0) return SS_OK;
-    if (!cfg) return fail(SS_ERR_ARG, "null handle");
-    if (dtype != SS_PAD_F32 && dtype != SS_PAD_F16 && dtype != SS_PAD_BF16) return fail(SS_ERR_ARG, "dtype must be SS_PAD_F32, SS_PAD_F16 or SS_PAD_BF16");
-    if (!x || !out) return fail(SS_ERR_ARG, "null buffer");
-    if (n_frames < 2 || n_frames > kMaxFrames) return fail(SS_ERR_ARG, "n_frames must be at least 2 and n_frames * 160 below 2^31");
-    if (ld < n_samples) return fail(SS_ERR_ARG, "ld must be at least n_samples");
-    if (!ss::have_device()) return ss::no_device("hot path");
-    const size_t in_floats = (batch - 1) * ld + n_samples, block = batch * cfg->params.n_mels * n_frames;
-    ss::HostStage st("ss_whisper_log_mel");
-    const float *d_in = st.up(x, in_floats * sizeof(float));
-    void *d_out = st.room<void>(block * elem_bytes(dtype));
-    void *d_work = dtype != SS_PAD_F32 ? st.room<void>(block * sizeof(float)) : nullptr;
-    if (st.ok()) st.ran(ss_whisper_log_mel_device(cfg, d_in, batch, n_samples, ld, n_frames, dtype, d_work, d_out, nullptr));
-    st.sync();
-    st.down(out, d_out, block * elem_bytes(dtype));
-    return st.status();
+    return whisper_dense_host(cfg, x, nullptr, batch, n_samples, ld, n_frames, dtype, out);
 }
 
 int ss_whisper_log_mel_packed(const ss_whisper_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, size_t n_frames, int dtype, void *out,
                               int32_t *lengths)
 {
-    if (n_clips == 0) return SS_OK;
-    if (!cfg) return fail(SS_ERR_ARG, "null handle");
-    if (dtype != SS_PAD_F32 && dtype != SS_PAD_F16 && dtype != SS_PAD_BF16) return fail(SS_ERR_ARG, "dtype must be SS_PAD_F32, SS_PAD_F16 or SS_PAD_BF16");
-    if (!x || !out || !sample_offsets) return fail(SS_ERR_ARG, "null buffer");
-    if (n_frames < 2 || n_frames > kMaxFrames) return fail(SS_ERR_ARG, "n_frames must be at least 2 and n_frames * 160 below 2^31");
-    // the host sees the table: the samples that come up are those of its good entries (a bad entry is contained on the device)
-    int64_t top = 0;
-    for (size_t b = 0; b < n_clips; ++b)
-        if (sample_offsets[b] >= 0 && sample_offsets[b + 1] >= sample_offsets[b] && sample_offsets[b + 1] > top) top = sample_offsets[b + 1];
-    if (!ss::have_device()) return ss::no_device("hot path");
-    const size_t in_floats = static_cast<size_t>(top), block = n_clips * cfg->params.n_mels * n_frames;
-    ss::HostStage st("ss_whisper_log_mel_packed");
-    const float *d_in = st.up(x, in_floats * sizeof(float));
-    void *d_out = st.room<void>(block * elem_bytes(dtype));
-    void *d_work = dtype != SS_PAD_F32 ? st.room<void>(block * sizeof(float)) : nullptr;
-    const int64_t *d_so = st.up(sample_offsets, (n_clips + 1) * sizeof(int64_t));
-    int32_t *d_len = st.room<int32_t>(n_clips * sizeof(int32_t));
-    if (st.ok()) st.ran(ss_whisper_log_mel_packed_device(cfg, d_in, n_clips, d_so, n_frames, dtype, d_work, d_out, d_len, nullptr));
-    st.sync();
-    st.down(out, d_out, block * elem_bytes(dtype));
-    if (lengths) st.down(lengths, d_len, n_clips * sizeof(int32_t));
-    return st.ok() ? whisper_pending_error(cfg) : st.status();
+    return whisper_packed_host(cfg, x, nullptr, n_clips, sample_offsets, n_frames, dtype, out, lengths);
+}
+
+// 16-bit PCM: sample k is (float)x[k] * scale
+int ss_whisper_log_mel_i16_device(const ss_whisper_config *cfg, const int16_t *d_x, size_t batch, size_t n_samples, size_t ld, float scale, size_t n_frames,
+                                  int dtype, void *d_work, void *d_out, void *stream)
+{
+    return whisper_dense_device(cfg, d_x, &scale, batch, n_samples, ld, n_frames, dtype, d_work, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_whisper_log_mel_packed_i16_device(const ss_whisper_config *cfg, const int16_t *d_x, size_t n_clips, const int64_t *d_sample_offsets, float scale,
+                                         size_t n_frames, int dtype, void *d_work, void *d_out, int32_t *d_lengths, void *stream)
+{
+    return whisper_packed_device(cfg, d_x, &scale, n_clips, d_sample_offsets, n_frames, dtype, d_work, d_out, d_lengths, static_cast<hipStream_t>(stream));
+}
+
+int ss_whisper_log_mel_i16(const ss_whisper_config *cfg, const int16_t *x, size_t batch, size_t n_samples, size_t ld, float scale, size_t n_frames, int dtype,
+                           void *out)
+{
+    return whisper_dense_host(cfg, x, &scale, batch, n_samples, ld, n_frames, dtype, out);
+}
+
+int ss_whisper_log_mel_packed_i16(const ss_whisper_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale, size_t n_frames,
+                                  int dtype, void *out, int32_t *lengths)
+{
+    return whisper_packed_host(cfg, x, &scale, n_clips, sample_offsets, n_frames, dtype, out, lengths);
 }
 
 }  // extern "C"

@@ -3101,9 +3101,11 @@ def _kaldi_cfg(what, sig, mfcc, sample_frequency, frame_length, frame_shift, num
     return _get_kaldi_config(key, _device_key(sig))
 
 
-def _kaldi_dense(sig, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
-    """sig [L] or [B, L] -> [T, cols] or [B, T, cols]; fbank with_energy: the log energy as column 0 (torchaudio's layout)"""
+def _kaldi_dense(sig, cfg: KaldiConfig, mfcc: bool, with_energy: bool, scale=None):
+    """sig [L] or [B, L] -> [T, cols] or [B, T, cols]; fbank with_energy: the log energy as column 0 (torchaudio's layout).
+    scale: the signal is int16 PCM, sample = int16 * scale (the ``ss_kpcm_*`` entry points)"""
     lib = _lib.lib()
+    fam, sc = ("ss_kaldi", []) if scale is None else ("ss_kpcm", [scale])
     one = len(sig.shape) == 1
     batch, L = (1, int(sig.shape[0])) if one else (int(sig.shape[0]), int(sig.shape[1]))
     T = cfg.num_frames(L)
@@ -3120,9 +3122,10 @@ def _kaldi_dense(sig, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
         out = torch.empty((batch, T, cols), dtype=torch.float32, device=v.device)
         en = torch.empty((batch, T), dtype=torch.float32, device=v.device) if with_energy else None
         if batch and mfcc:
-            _launch(v.device, lib.ss_kaldi_mfcc_device, cfg.handle, v, batch, L, ld, out.data_ptr())
+            _launch(v.device, getattr(lib, f"{fam}_mfcc_device"), cfg.handle, v, batch, L, ld, *sc, out.data_ptr())
         elif batch:
-            _launch(v.device, lib.ss_kaldi_fbank_device, cfg.handle, v, batch, L, ld, out.data_ptr(), en.data_ptr() if with_energy else None)
+            _launch(v.device, getattr(lib, f"{fam}_fbank_device"), cfg.handle, v, batch, L, ld, *sc, out.data_ptr(),
+                    en.data_ptr() if with_energy else None)
         if with_energy:
             out = torch.cat([en.unsqueeze(-1), out], dim=-1)
         return out[0] if one else out
@@ -3131,17 +3134,20 @@ def _kaldi_dense(sig, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
     en = np.empty((batch, T), dtype=np.float32) if with_energy else None
     if batch:
         if mfcc:
-            _lib.check(lib.ss_kaldi_mfcc(cfg.handle, v.ctypes.data, batch, L, L, out.ctypes.data))
+            _lib.check(getattr(lib, f"{fam}_mfcc")(cfg.handle, v.ctypes.data, batch, L, L, *sc, out.ctypes.data))
         else:
-            _lib.check(lib.ss_kaldi_fbank(cfg.handle, v.ctypes.data, batch, L, L, out.ctypes.data, en.ctypes.data if with_energy else None))
+            _lib.check(getattr(lib, f"{fam}_fbank")(cfg.handle, v.ctypes.data, batch, L, L, *sc, out.ctypes.data,
+                                                    en.ctypes.data if with_energy else None))
     if with_energy:
         out = np.concatenate([en[..., None], out], axis=-1)
     return out[0] if one else out
 
 
-def _kaldi_packed(sig, so, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
-    """packed samples [N], sample offsets so (host int64, used as they stand) -> (rows [sum T_b, cols], frame offsets (host int64))"""
+def _kaldi_packed(sig, so, cfg: KaldiConfig, mfcc: bool, with_energy: bool, scale=None):
+    """packed samples [N], sample offsets so (host int64, used as they stand) -> (rows [sum T_b, cols], frame offsets (host int64));
+    scale: as for ``_kaldi_dense``"""
     lib = _lib.lib()
+    fam, sc = ("ss_kaldi", []) if scale is None else ("ss_kpcm", [scale])
     n = so.size - 1
     fo = np.empty_like(so)
     _lib.check(lib.ss_kaldi_packed_frame_offsets(C.byref(cfg.params), n, so.ctypes.data, fo.ctypes.data))
@@ -3154,9 +3160,10 @@ def _kaldi_packed(sig, so, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
         out = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
         en = torch.empty((rows,), dtype=torch.float32, device=x.device) if with_energy else None
         if n and rows and mfcc:
-            _launch(x.device, lib.ss_kaldi_mfcc_packed_device, cfg.handle, x, n, so, fo, rows, out.data_ptr())
+            _launch(x.device, getattr(lib, f"{fam}_mfcc_packed_device"), cfg.handle, x, n, so, *sc, fo, rows, out.data_ptr())
         elif n and rows:
-            _launch(x.device, lib.ss_kaldi_fbank_packed_device, cfg.handle, x, n, so, fo, rows, out.data_ptr(), en.data_ptr() if with_energy else None)
+            _launch(x.device, getattr(lib, f"{fam}_fbank_packed_device"), cfg.handle, x, n, so, *sc, fo, rows, out.data_ptr(),
+                    en.data_ptr() if with_energy else None)
         if with_energy:
             out = torch.cat([en.unsqueeze(-1), out], dim=-1)
         return out, fo
@@ -3165,9 +3172,10 @@ def _kaldi_packed(sig, so, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
     en = np.empty((rows,), dtype=np.float32) if with_energy else None
     if n and rows:
         if mfcc:
-            _lib.check(lib.ss_kaldi_mfcc_packed(cfg.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data))
+            _lib.check(getattr(lib, f"{fam}_mfcc_packed")(cfg.handle, x.ctypes.data, n, so.ctypes.data, *sc, out.ctypes.data))
         else:
-            _lib.check(lib.ss_kaldi_fbank_packed(cfg.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data, en.ctypes.data if with_energy else None))
+            _lib.check(getattr(lib, f"{fam}_fbank_packed")(cfg.handle, x.ctypes.data, n, so.ctypes.data, *sc, out.ctypes.data,
+                                                           en.ctypes.data if with_energy else None))
     if with_energy:
         out = np.concatenate([en[:, None], out], axis=-1)
     return out, fo
@@ -3175,60 +3183,64 @@ def _kaldi_packed(sig, so, cfg: KaldiConfig, mfcc: bool, with_energy: bool):
 
 def kaldi_fbank(waveform, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0, high_freq=0.0,
                 preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True, use_power=True,
-                use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, **unsupported):
+                use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, *, pcm_scale=None, **unsupported):
     """``torchaudio.compliance.kaldi.fbank`` (Kaldi's compute-fbank-feats) of one clip [L] -> [T, num_mel_bins] or of every row of a
     batch [B, L] -> [B, T, num_mel_bins], float32; the names and defaults are torchaudio's.  ``use_energy=True`` puts the log energy
     in column 0 ([.., num_mel_bins + 1]), as torchaudio does.  numpy in -> the host-pointer call; a ROCm tensor stays on the device
     (current stream, one launch).  ``input_scale``: every sample is multiplied by it first (32768 for normalised floats that stand
-    for 16-bit PCM).  Served for frames that pad to 512 points (256 < samples per frame <= 512); dither, snip_edges=False, htk_compat,
+    for 16-bit PCM).  ``pcm_scale``: the waveform is int16 PCM and a sample is int16 * pcm_scale, a power of two (1.0: Kaldi's own
+    integer-valued samples; 2**-15: torchaudio's normalised ones) -- the kernel converts on load, bit for bit the float call on the
+    converted samples, and ``input_scale`` still applies afterwards.  Served for frames that pad to 512 points (256 < samples per frame <= 512); dither, snip_edges=False, htk_compat,
     subtract_mean, vtln_* and channel raise."""
     what = "kaldi_fbank"
-    sig = _require_f32(waveform, (1, 2), what)
+    sig, scale = _require_signal(waveform, (1, 2), what, pcm_scale)
     cfg = _kaldi_cfg(what, sig, False, sample_frequency, frame_length, frame_shift, num_mel_bins, 0, low_freq, high_freq, preemphasis_coefficient,
                      0.0, window_type, blackman_coeff, remove_dc_offset, use_power, False, raw_energy, energy_floor, input_scale, unsupported)
-    return _kaldi_dense(sig, cfg, False, bool(use_energy))
+    return _kaldi_dense(sig, cfg, False, bool(use_energy), scale)
 
 
 def kaldi_mfcc(waveform, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0, high_freq=0.0,
                preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True, use_energy=False,
-               raw_energy=True, energy_floor=1.0, input_scale=1.0, num_ceps=13, cepstral_lifter=22.0, **unsupported):
+               raw_energy=True, energy_floor=1.0, input_scale=1.0, num_ceps=13, cepstral_lifter=22.0, *, pcm_scale=None, **unsupported):
     """``torchaudio.compliance.kaldi.mfcc`` (Kaldi's compute-mfcc-feats) of one clip [L] -> [T, num_ceps] or of a batch [B, L] ->
     [B, T, num_ceps]: the orthonormal DCT of ``kaldi_fbank``'s power-spectrum log-mel row with the cepstral lifter; ``use_energy=True``
     replaces coefficient 0 by the log energy.  See ``kaldi_fbank`` for the inputs and for what is not served."""
     what = "kaldi_mfcc"
-    sig = _require_f32(waveform, (1, 2), what)
+    sig, scale = _require_signal(waveform, (1, 2), what, pcm_scale)
     cfg = _kaldi_cfg(what, sig, True, sample_frequency, frame_length, frame_shift, num_mel_bins, num_ceps, low_freq, high_freq,
                      preemphasis_coefficient, cepstral_lifter, window_type, blackman_coeff, remove_dc_offset, True, use_energy, raw_energy,
                      energy_floor, input_scale, unsupported)
-    return _kaldi_dense(sig, cfg, True, False)
+    return _kaldi_dense(sig, cfg, True, False, scale)
 
 
 def kaldi_fbank_packed(signal, lengths, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0,
                        high_freq=0.0, preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True,
-                       use_power=True, use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, **unsupported):
+                       use_power=True, use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, *, pcm_scale=None,
+                       **unsupported):
     """``kaldi_fbank`` of clips of different lengths packed end to end in one 1-D float32 signal -> (rows [sum T_b, cols],
     frame_offsets [n + 1] int64 on the host): clip b's rows are frame_offsets[b] : frame_offsets[b + 1], bit for bit what
     ``kaldi_fbank`` returns for that clip alone.  One launch for all clips.  ``(out, out_lengths)`` of ``resample_packed`` are valid
-    ``(signal, lengths)`` as they stand."""
+    ``(signal, lengths)`` as they stand.  ``pcm_scale``: the signal is int16 PCM (see ``kaldi_fbank``)."""
     what = "kaldi_fbank_packed"
-    sig = _require_f32(signal, (1,), what)
+    sig, scale = _require_signal(signal, (1,), what, pcm_scale)
     so = _sample_offsets(lengths, sig.shape[0], what)
     cfg = _kaldi_cfg(what, sig, False, sample_frequency, frame_length, frame_shift, num_mel_bins, 0, low_freq, high_freq, preemphasis_coefficient,
                      0.0, window_type, blackman_coeff, remove_dc_offset, use_power, False, raw_energy, energy_floor, input_scale, unsupported)
-    return _kaldi_packed(sig, so, cfg, False, bool(use_energy))
+    return _kaldi_packed(sig, so, cfg, False, bool(use_energy), scale)
 
 
 def kaldi_mfcc_packed(signal, lengths, sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, low_freq=20.0,
                       high_freq=0.0, preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, remove_dc_offset=True,
-                      use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, num_ceps=13, cepstral_lifter=22.0, **unsupported):
+                      use_energy=False, raw_energy=True, energy_floor=1.0, input_scale=1.0, num_ceps=13, cepstral_lifter=22.0, *,
+                      pcm_scale=None, **unsupported):
     """``kaldi_mfcc`` of packed clips (see ``kaldi_fbank_packed``) -> (rows [sum T_b, num_ceps], frame_offsets [n + 1])."""
     what = "kaldi_mfcc_packed"
-    sig = _require_f32(signal, (1,), what)
+    sig, scale = _require_signal(signal, (1,), what, pcm_scale)
     so = _sample_offsets(lengths, sig.shape[0], what)
     cfg = _kaldi_cfg(what, sig, True, sample_frequency, frame_length, frame_shift, num_mel_bins, num_ceps, low_freq, high_freq,
                      preemphasis_coefficient, cepstral_lifter, window_type, blackman_coeff, remove_dc_offset, True, use_energy, raw_energy,
                      energy_floor, input_scale, unsupported)
-    return _kaldi_packed(sig, so, cfg, True, False)
+    return _kaldi_packed(sig, so, cfg, True, False, scale)
 
 
 # ---- the Kaldi front end over a pool of stream states (ss_kstream_*) ----------------------------------------------------------
@@ -3361,8 +3373,8 @@ class KaldiMfccStreamPool(_KaldiStreamPoolBase):
         return self._run(chunks, lengths_or_offsets, slots, pcm_scale, self.cols, False)
 
 
-def _kaldi_list(what, signals, packed_fn, kw):
-    sigs = [_require_f32(x, (1,), what) for x in signals]
+def _kaldi_list(what, signals, packed_fn, pcm_scale, kw):
+    sigs = [_require_signal(x, (1,), what, pcm_scale)[0] for x in signals]
     if not sigs:
         return []
     on_device = [_is_torch(x) for x in sigs]
@@ -3376,20 +3388,20 @@ def _kaldi_list(what, signals, packed_fn, kw):
         packed = torch.cat(sigs)
     else:
         packed = np.concatenate(sigs)
-    out, fo = packed_fn(packed, [int(x.shape[0]) for x in sigs], **kw)
+    out, fo = packed_fn(packed, [int(x.shape[0]) for x in sigs], pcm_scale=pcm_scale, **kw)
     fo = fo.tolist()
     return [out[fo[b]:fo[b + 1]] for b in range(len(sigs))]
 
 
-def kaldi_fbank_list(signals, **kw):
-    """A list of 1-D float32 clips of any lengths -> the list of their ``kaldi_fbank`` rows (views of one block): the clips are packed
-    once and served by one ``kaldi_fbank_packed`` call, whose keyword arguments this takes."""
-    return _kaldi_list("kaldi_fbank_list", signals, kaldi_fbank_packed, kw)
+def kaldi_fbank_list(signals, *, pcm_scale=None, **kw):
+    """A list of 1-D float32 clips of any lengths (int16 PCM with ``pcm_scale``) -> the list of their ``kaldi_fbank`` rows (views of one
+    block): the clips are packed once and served by one ``kaldi_fbank_packed`` call, whose keyword arguments this takes."""
+    return _kaldi_list("kaldi_fbank_list", signals, kaldi_fbank_packed, pcm_scale, kw)
 
 
-def kaldi_mfcc_list(signals, **kw):
+def kaldi_mfcc_list(signals, *, pcm_scale=None, **kw):
     """``kaldi_fbank_list`` for ``kaldi_mfcc_packed``."""
-    return _kaldi_list("kaldi_mfcc_list", signals, kaldi_mfcc_packed, kw)
+    return _kaldi_list("kaldi_mfcc_list", signals, kaldi_mfcc_packed, pcm_scale, kw)
 
 
 # ---- Whisper log-mel front end (ss_whisper_* in include/speechsauce_amd.h) ------------------------------------------
@@ -3463,13 +3475,15 @@ def _whisper_out(shape, name, device):
     return out, out.ctypes.data
 
 
-def whisper_log_mel(x, n_mels=80, n_frames=None, dtype="float32"):
+def whisper_log_mel(x, n_mels=80, n_frames=None, dtype="float32", *, pcm_scale=None):
     """The Whisper log-mel block (``whisper.audio.log_mel_spectrogram``, ``transformers.WhisperFeatureExtractor``) of one 16 kHz clip
     [L] -> [n_mels, n_frames] or of every row of a batch [B, L] -> [B, n_mels, n_frames].  ``n_frames=None`` keeps ``L // 160``
     frames; ``3000`` is the 30 s window (the clip is padded with zeros or trimmed).  ``dtype``: float32, float16 or bfloat16 (a host
-    bfloat16 result is a uint16 array of bit patterns)."""
+    bfloat16 result is a uint16 array of bit patterns).  ``pcm_scale``: x is int16 PCM and a sample is int16 * pcm_scale, a power of
+    two (2**-15: Whisper's own convention) -- the kernel converts on load, bit for bit the float call on the converted samples."""
     what = "whisper_log_mel"
-    sig = _require_f32(x, (1, 2), what)
+    sig, scale = _require_signal(x, (1, 2), what, pcm_scale)
+    i16, sc, zeros = ("", [], np.float32) if scale is None else ("_i16", [scale], np.int16)
     code, name = _pad_dtype(dtype, what)
     one = len(sig.shape) == 1
     batch, L = (1, int(sig.shape[0])) if one else (int(sig.shape[0]), int(sig.shape[1]))
@@ -3488,24 +3502,27 @@ def whisper_log_mel(x, n_mels=80, n_frames=None, dtype="float32"):
             v, ld = v.contiguous(), L
         out, optr = _whisper_out((batch, M, T), name, v.device)
         if batch:
-            keep = v if L else torch.zeros(4, dtype=torch.float32, device=v.device)  # an empty clip reads nothing: any address will do
-            _launch(v.device, lib.ss_whisper_log_mel_device, cfg.handle, keep, batch, L, ld, T, code, cfg.work(batch, T, code, v.device), optr)
+            keep = v if L else torch.zeros(4, dtype=v.dtype, device=v.device)  # an empty clip reads nothing: any address will do
+            _launch(v.device, getattr(lib, f"ss_whisper_log_mel{i16}_device"), cfg.handle, keep, batch, L, ld, *sc, T, code,
+                    cfg.work(batch, T, code, v.device), optr)
         return out[0] if one else out
     v = np.ascontiguousarray(sig).reshape(batch, L)
     if L == 0:
-        v = np.zeros((batch, 4), np.float32)
+        v = np.zeros((batch, 4), zeros)
     out, optr = _whisper_out((batch, M, T), name, None)
     if batch:
-        _lib.check(lib.ss_whisper_log_mel(cfg.handle, v.ctypes.data, batch, L, v.shape[1], T, code, optr))
+        _lib.check(getattr(lib, f"ss_whisper_log_mel{i16}")(cfg.handle, v.ctypes.data, batch, L, v.shape[1], *sc, T, code, optr))
     return out[0] if one else out
 
 
-def whisper_log_mel_packed(signal, lengths, n_mels=80, n_frames=None, dtype="float32"):
+def whisper_log_mel_packed(signal, lengths, n_mels=80, n_frames=None, dtype="float32", *, pcm_scale=None):
     """Clips of different lengths end to end in ``signal`` [N] -> ``(out [n_clips, n_mels, n_frames], lengths int32 [n_clips])``: every
     clip padded or trimmed to the same ``n_frames`` (None: the longest clip's ``len // 160``), ``lengths[b] = min(len_b // 160,
-    n_frames)`` the frames that come from the clip's own samples.  One call of three launches whatever the lengths."""
+    n_frames)`` the frames that come from the clip's own samples.  One call of three launches whatever the lengths.  ``pcm_scale``:
+    the signal is int16 PCM (see ``whisper_log_mel``)."""
     what = "whisper_log_mel_packed"
-    sig = _require_f32(signal, (1,), what)
+    sig, scale = _require_signal(signal, (1,), what, pcm_scale)
+    i16, sc, zeros = ("", [], np.float32) if scale is None else ("_i16", [scale], np.int16)
     code, name = _pad_dtype(dtype, what)
     so = _sample_offsets(lengths, int(sig.shape[0]), what)
     n = so.size - 1
@@ -3520,25 +3537,26 @@ def whisper_log_mel_packed(signal, lengths, n_mels=80, n_frames=None, dtype="flo
         out, optr = _whisper_out((n, M, T), name, x.device)
         lens = torch.empty((n,), dtype=torch.int32, device=x.device)
         if n:
-            keep = x if x.numel() else torch.zeros(4, dtype=torch.float32, device=x.device)
-            _launch(x.device, lib.ss_whisper_log_mel_packed_device, cfg.handle, keep, n, so, T, code, cfg.work(n, T, code, x.device), optr,
-                    lens.data_ptr())
+            keep = x if x.numel() else torch.zeros(4, dtype=x.dtype, device=x.device)
+            _launch(x.device, getattr(lib, f"ss_whisper_log_mel_packed{i16}_device"), cfg.handle, keep, n, so, *sc, T, code,
+                    cfg.work(n, T, code, x.device), optr, lens.data_ptr())
         return out, lens
     x = np.ascontiguousarray(sig)
     if x.size == 0:
-        x = np.zeros(4, np.float32)
+        x = np.zeros(4, zeros)
     out, optr = _whisper_out((n, M, T), name, None)
     lens = np.empty((n,), dtype=np.int32)
     if n:
-        _lib.check(lib.ss_whisper_log_mel_packed(cfg.handle, x.ctypes.data, n, so.ctypes.data, T, code, optr, lens.ctypes.data))
+        _lib.check(getattr(lib, f"ss_whisper_log_mel_packed{i16}")(cfg.handle, x.ctypes.data, n, so.ctypes.data, *sc, T, code, optr,
+                                                                   lens.ctypes.data))
     return out, lens
 
 
-def whisper_log_mel_list(signals, n_mels=80, n_frames=None, dtype="float32"):
-    """A list of 1-D float32 clips of any lengths -> ``(out [n_clips, n_mels, n_frames], lengths)``: the clips are packed once and
-    served by one ``whisper_log_mel_packed`` call."""
+def whisper_log_mel_list(signals, n_mels=80, n_frames=None, dtype="float32", *, pcm_scale=None):
+    """A list of 1-D float32 clips of any lengths (int16 PCM with ``pcm_scale``) -> ``(out [n_clips, n_mels, n_frames], lengths)``: the
+    clips are packed once and served by one ``whisper_log_mel_packed`` call."""
     what = "whisper_log_mel_list"
-    sigs = [_require_f32(x, (1,), what) for x in signals]
+    sigs = [_require_signal(x, (1,), what, pcm_scale)[0] for x in signals]
     if not sigs:
         raise ValueError(f"{what}: no clips")
     on_device = [_is_torch(x) for x in sigs]
@@ -3552,4 +3570,4 @@ def whisper_log_mel_list(signals, n_mels=80, n_frames=None, dtype="float32"):
         packed = torch.cat(sigs)
     else:
         packed = np.concatenate(sigs)
-    return whisper_log_mel_packed(packed, [int(x.shape[0]) for x in sigs], n_mels=n_mels, n_frames=n_frames, dtype=dtype)
+    return whisper_log_mel_packed(packed, [int(x.shape[0]) for x in sigs], n_mels=n_mels, n_frames=n_frames, dtype=dtype, pcm_scale=pcm_scale)

@@ -355,6 +355,14 @@ PROTOTYPES = {
     "ss_kaldi_fbank_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, _fp, _fp]),
     "ss_kaldi_mfcc_packed_device": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
     "ss_kaldi_mfcc_packed": (C.c_int, [_kc, _fp, C.c_size_t, C.c_void_p, _fp]),
+    "ss_kpcm_fbank_device": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, _fp, C.c_void_p]),
+    "ss_kpcm_fbank": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, _fp]),
+    "ss_kpcm_mfcc_device": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_void_p]),
+    "ss_kpcm_mfcc": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, _fp]),
+    "ss_kpcm_fbank_packed_device": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_kpcm_fbank_packed": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, _fp, _fp]),
+    "ss_kpcm_mfcc_packed_device": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
+    "ss_kpcm_mfcc_packed": (C.c_int, [_kc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, _fp]),
     "ss_whisper_params_default": (C.c_int, [_P(SsWhisperParams), C.c_uint32]),
     "ss_whisper_params_validate": (C.c_int, [_P(SsWhisperParams)]),
     "ss_whisper_num_frames": (C.c_int, [C.c_size_t, _P(C.c_size_t)]),
@@ -370,6 +378,12 @@ PROTOTYPES = {
     "ss_whisper_log_mel": (C.c_int, [_wc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]),
     "ss_whisper_log_mel_packed_device": (C.c_int, [_wc, _fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ss_whisper_log_mel_packed": (C.c_int, [_wc, _fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "ss_whisper_log_mel_i16_device": (
+        C.c_int, [_wc, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ss_whisper_log_mel_i16": (C.c_int, [_wc, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_size_t, C.c_int, C.c_void_p]),
+    "ss_whisper_log_mel_packed_i16_device": (
+        C.c_int, [_wc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ss_whisper_log_mel_packed_i16": (C.c_int, [_wc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "ss_kstream_state_len": (C.c_int, [_P(SsKaldiParams), _P(C.c_size_t), _P(C.c_size_t)]),
     "ss_kstream_row_offsets": (C.c_int, [_P(SsKaldiParams), C.c_size_t, C.c_void_p, C.c_void_p]),
     "ss_kstream_fbank_packed_device": (

@@ -1,7 +1,7 @@
 """µs per call of the Whisper log-mel front end (whisper_log_mel / whisper_log_mel_packed: ss_whisper_c200) beside today's route to
 the same numbers, from one process.
 
-    python tools/whisper_rate.py [--clips 256] [--mels 80] [--reps 5] [--rounds 5] [--ring 2]
+    python tools/whisper_rate.py [--clips 256] [--mels 80] [--reps 5] [--rounds 5] [--ring 2] [--pcm16]
 
 Today's route: log_mel_spectrogram(_packed) on fft_length = 400 with a 160-sample hop, centred reflect frames, the Slaney bank with
 Slaney norm and top_db = 80 (the chirp-z build of the generic kernel and its dB floor), plus the torch steps that turn its decibels
@@ -14,6 +14,13 @@ Protocol: every leg is warmed up, then `--rounds` rounds alternate the legs, eac
 one stream; every call takes the next of a ring of `--ring` input blocks.  Reported per leg: the median over the rounds, the fastest and
 the slowest round; per shape the ratio of the medians and whether the min-max ranges of the two sides overlap.
 Prints one JSON line.  Measuring only: not collected by pytest, not part of bench.py.
+
+--pcm16: the same two shapes and output types fed signed 16-bit PCM, three legs each under the same protocol (at least five rounds):
+  *_float (a)          whisper_log_mel(_packed) on a ready float buffer
+  *_convert_float (b)  pcm.to(float32).mul_(scale) and then that float call: what a caller with an int16 corpus ran before
+  *_pcm (c)            whisper_log_mel(_packed)(..., pcm_scale=2^-15) on the int16 buffer
+Every leg reports min / median / max over the rounds; then (c) over (b), (c) over (a), and whether (c)'s median lies above (b)'s by more
+than the spread (max - min) of (b)'s rounds -- the PCM build being slower than what it replaces.
 """
 import argparse
 import json
@@ -34,6 +41,81 @@ def first_silent(length, n_frames):
     return 0 if L == 0 else min(max(2, -(-(L + 200) // 160)), n_frames)
 
 
+def pcm16_report(args):
+    """the --pcm16 run: see the module docstring"""
+    import numpy as np
+    import torch
+
+    import speechsauce_amd as ss
+
+    n, M, scale = args.clips, args.mels, 2.0 ** -15
+    rounds = max(5, args.rounds)
+    rng = np.random.default_rng(0)
+    at = [0]
+    res = {"pcm16": True, "scale": scale, "clips": n, "n_mels": M, "window_frames": WINDOW, "reps": args.reps, "rounds": rounds, "ring": args.ring,
+           "device": torch.cuda.get_device_name()}
+
+    def rings(shape):
+        pcm = [torch.randint(-32768, 32768, shape, device="cuda", dtype=torch.int32).to(torch.int16) for _ in range(args.ring)]
+        return pcm, [p.to(torch.float32).mul_(scale) for p in pcm]
+
+    lens = rng.integers(16000, WINDOW * 160 + 1, n)
+    shapes = {"dense30": rings((n, WINDOW * 160)), "ragged": rings((int(lens.sum()),))}
+    res["ragged_seconds_mean"] = float(lens.mean() / 16000)
+
+    def call(shape, x, dtype, **kw):
+        if shape == "dense30":
+            return ss.whisper_log_mel(x, n_mels=M, n_frames=WINDOW, dtype=dtype, **kw)
+        return ss.whisper_log_mel_packed(x, lens, n_mels=M, n_frames=WINDOW, dtype=dtype, **kw)[0]
+
+    def leg(shape, kind, dtype):
+        pcm, flt = shapes[shape]
+
+        def fn():
+            at[0] += 1
+            i = at[0] % args.ring
+            if kind == "float":
+                return call(shape, flt[i], dtype)
+            if kind == "convert_float":
+                return call(shape, pcm[i].to(torch.float32).mul_(scale), dtype)
+            return call(shape, pcm[i], dtype, pcm_scale=scale)
+        return fn
+
+    legs = [(f"{shape}_{name}_{kind}", leg(shape, kind, dtype)) for shape in shapes for name, dtype in (("f32", torch.float32), ("bf16", torch.bfloat16))
+            for kind in ("float", "convert_float", "pcm")]
+    for shape, (pcm, flt) in shapes.items():  # what is compared computes the same bits
+        for dtype in (torch.float32, torch.bfloat16):
+            assert torch.equal(call(shape, pcm[0], dtype, pcm_scale=scale), call(shape, flt[0], dtype)), f"{shape}: the PCM call is not the float call"
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3
+
+    for _, fn in legs:
+        for _ in range(args.ring):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name, _ in legs}
+    for _ in range(rounds):
+        for name, fn in legs:
+            us[name].append(timed(fn, args.reps))
+    for name, _ in legs:
+        v = us[name]
+        res[name] = {"us_min": min(v), "us_median": statistics.median(v), "us_max": max(v)}
+    for shape in shapes:
+        for name in ("f32", "bf16"):
+            a, b, c = (res[f"{shape}_{name}_{kind}"] for kind in ("float", "convert_float", "pcm"))
+            c["pcm_over_convert_float"] = c["us_median"] / b["us_median"]
+            c["pcm_over_float"] = c["us_median"] / a["us_median"]
+            c["slower_than_convert_float"] = c["us_median"] - b["us_median"] > b["us_max"] - b["us_min"]
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=256)
@@ -41,7 +123,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--ring", type=int, default=2)
+    ap.add_argument("--pcm16", action="store_true", help="time the 16-bit PCM calls beside the float calls (see the module docstring)")
     args = ap.parse_args()
+    if args.pcm16:
+        return pcm16_report(args)
 
     import numpy as np
     import torch
