@@ -7,7 +7,8 @@
 //     12-wave workgroup per CU; the next unit's samples are prefetched into the dead window registers.
 //   * Row r of a clip covers the 512 samples that end at chunk r + n_pad (functions.rs:137-151): zero initial state,
 //     zero tail, rows past the real ones are all zero (D3).  Windows inside the clip load as 8-byte pairs at constant
-//     offsets; at the clip edges one masked range per lane.  Vorbis window pairs come from the table block in LDS.
+//     offsets; at the clip edges one masked range per lane (load_window of ss_frame32.h, shared with ss_mel_c512 and
+//     ss_mel_c2048).  Vorbis window pairs come from the table block in LDS.
 //   * FFT / untangle: the shared quad skeleton of ss_quad256.h.  |X|^2 wnorm^2 of bins 0..128 -- or all 257 when the
 //     bank reaches past (F+1)/2 -- goes to a P row inside the slot.
 //   * banded mel, up to 5 filters per lane (80 filters), host-sorted by tap count; the four rows of a wave are adjacent
@@ -16,6 +17,7 @@
 // Tables: ss::mel512_layout (ss_internal.h).
 #include "ss_device.h"
 #include "ss_fft_reg.h"
+#include "ss_frame32.h"
 #include "ss_internal.h"
 #include "ss_quad256.h"
 #include "ss_wave.h"
@@ -68,34 +70,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c256(const Mel512Args a)
         const bool active = r < Rreal;
         const int start = static_cast<int>(r + a.n_pad + 1) * static_cast<int>(a.hop) - 512;
         const bool inside = active && start >= 0 && start + 512 <= static_cast<int>(a.n_samples);
-        const float2 *src = reinterpret_cast<const float2 *>(xc + start) + j;
-        if (__all(inside)) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) vv[e] = src[16 * e];
-        } else {
-            // clip edges (zero initial state, zero padding of the last chunk, D3) and inactive rows.  start and n_samples are
-            // even, so a sample pair is inside or outside as a whole; the valid pairs form one range [e_lo, e_hi) per lane
-            // (the address of a masked load may lie outside the clip; it is never dereferenced)
-            const int base = start + 2 * j;
-            const int n = static_cast<int>(a.n_samples);
-            if (((start | n) & 1) == 0) {
-                const int e_lo = base >= 0 ? 0 : (31 - base) >> 5;
-                int e_hi = base >= n ? 0 : min(16, (n - base + 31) >> 5);
-                if (!active) e_hi = 0;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    float2 s = make_float2(0.f, 0.f);
-                    if (e >= e_lo && e < e_hi) s = src[16 * e];
-                    vv[e] = s;
-                }
-            } else {  // odd hop or clip length: a pair may straddle the clip edge, bounds per sample
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int p0 = base + 32 * e;
-                    vv[e] = make_float2(active && p0 >= 0 && p0 < n ? xc[p0] : 0.f, active && p0 + 1 >= 0 && p0 + 1 < n ? xc[p0 + 1] : 0.f);
-                }
-            }
-        }
+        // clip edges (zero initial state, zero padding of the last chunk, D3) and inactive rows: load_window's masked paths
+        fr32::load_window<16, 16>(vv, xc, start, static_cast<int>(a.n_samples), j, active, __all(inside));
     };
     unsigned unit = __builtin_amdgcn_readfirstlane(u_lo + wave);  // uniform: kept scalar
     float2 vin[16];

@@ -3,19 +3,24 @@
 //
 //   * 32 lanes own a frame, 32 complex points per lane; a wave carries two consecutive frames of the flat frame list.  One
 //     persistent 8-wave workgroup per CU; waves pull frame pairs from an LDS counter.
-//   * FFT exactly as in ss_mel2048.hip: radix-32, ONE transposing exchange through wave-private LDS in two register halves
-//     (ds_write_b64 scatter to 34*(n1>>1) + 2*k1' + (n1&1), ds_read_b128 back), twiddle, radix-32.  No workgroup barrier
-//     in the main loop.
-//   * untangle with ds_bpermute_b32 (partner = lane 32-j, register 31-r): bins 0..512 go to the P row (the mel bank ends at
-//     (F+1)/2, feature.rs:69-70), all 1025 feed the frame energy (feature.rs:216-219), summed over the half-wave.
-//   * banded mel (4 filters per lane, aligned float4 taps), zero handling, ln -> row in filter order; DCT-II with the
-//     m <-> M-1-m symmetry of the cosine (sum / difference rows, half the table), reference scaling, column-0 replacement.
-//   * optional frame window (mfcc_window switch) from the table block; mfe build stops after the mel stage.
+//   * FFT exactly as in ss_mel2048.hip (a local copy: that file holds a benchmark kernel): radix-32, ONE transposing exchange
+//     through wave-private LDS in two register halves (ds_write_b64 scatter to 34*(n1>>1) + 2*k1' + (n1&1), ds_read_b128
+//     back), twiddle, radix-32.  No workgroup barrier in the main loop.
+//   * untangle with ds_bpermute_b32 (partner = lane 32-j, register 31-r; untangle_bin of ss_wave.h): bins 0..512 go to the P
+//     row (the mel bank ends at (F+1)/2, feature.rs:69-70), all 1025 feed the frame energy (feature.rs:216-219), summed over
+//     the half-wave.
+//   * every other stage is a frame stage of ss_frame32.h, shared with ss_mfcc_c512 (ss_mfcc1024.hip): load_frame, apply_window
+//     (optional frame window, mfcc_window switch, from the table block), mel_ln_rows (banded mel, 4 filters per lane, aligned
+//     float4 taps; zero handling; ln -> row in filter order), store_mfe_energy (the mfe build stops there), dct_dot (DCT-II
+//     with the m <-> M-1-m symmetry of the cosine, half the table); the sum / difference rows, reference scaling and
+//     column-0 replacement stay here.
 //   * LIB builds (librosa-compatible switches): centred frames with reflect / zero padding at the clip edges, and P rows of
-//     all 1025 bins for banks over the whole spectrum; the rows then outgrow the exchange region (10304 B per wave).
+//     all 1025 bins for banks over the whole spectrum; the rows then outgrow the exchange region (10304 B per wave).  The
+//     pre-emphasis builds (PRE, a template parameter handed to load_frame) use the LIB layout.
 // Reference semantics as in ss_mfcc512.hip; tables: ss::mfcc2048_layout (ss_internal.h).
 #include "ss_device.h"
 #include "ss_fft_reg.h"
+#include "ss_frame32.h"
 #include "ss_internal.h"
 #include "ss_wave.h"
 
@@ -24,6 +29,7 @@ namespace ss {
 namespace {
 
 using namespace wv;
+using namespace fr32;
 
 namespace L = mfcc2048_layout;
 constexpr int kExSlotsG = 2 * 16 * 34;      // float2 in the wave's exchange region: two frames x half the columns (8704 B)
@@ -59,15 +65,7 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c1024(const Mfcc2048Args a
     unsigned *s_next = reinterpret_cast<unsigned *>(s_tab + L::kMelW + 32 * a.mel_wpitch);
 
     const unsigned total = a.batch * a.n_frames;
-    const unsigned units = (total + 1) / 2;
-    const unsigned u_lo = static_cast<unsigned>(static_cast<unsigned long long>(units) * blockIdx.x / gridDim.x);
-    const unsigned u_hi = static_cast<unsigned>(static_cast<unsigned long long>(units) * (blockIdx.x + 1) / gridDim.x);
-    {
-        const int n4 = (L::kMelW + 32 * a.mel_wpitch) / 4;
-        for (int i = tid; i < n4; i += WAVES * 64) reinterpret_cast<float4 *>(s_tab)[i] = reinterpret_cast<const float4 *>(a.tab)[i];
-        if (tid == 0) *s_next = u_lo + WAVES;
-    }
-    __syncthreads();
+    const UnitRange ur = split_and_stage((total + 1) / 2, s_tab, a.tab, (L::kMelW + 32 * a.mel_wpitch) / 4, s_next, tid, WAVES);
     int st[4], fi[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -77,73 +75,26 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c1024(const Mfcc2048Args a
     const float4 *w4 = reinterpret_cast<const float4 *>(s_melw + j * a.mel_wpitch);
     const int paddr = ((lane & 32) | ((32 - j) & 31)) << 2;  // lane holding Z[1024 - k]
     const float hscale32 = (POW2 ? 0.25f * a.scale : 0.5f * a.scale) * kTwo32;
-    const int M = static_cast<int>(a.n_filters), Cc = static_cast<int>(a.n_ceps), Mh = M / 2, Mc = (M + 1) / 2;
-    // valid sample pairs of this lane: n = j + 32 e with 2 n < flen (zero pad to fft_points, processing.rs:147-156)
-    const int e_hi = min(32, max(0, (static_cast<int>(a.flen) / 2 - j + 31) >> 5));
-    const int half_pairs = static_cast<int>(a.flen) / 2;
-    const bool odd_tail = (a.flen & 1) != 0;
-    constexpr bool pre = PRE;  // fused pre-emphasis: builds of their own (LIB layout: they also serve centred frames)
+    const int M = static_cast<int>(a.n_filters), Cc = static_cast<int>(a.n_ceps), Mh = M / 2, Mc = (M + 1) / 2, nq = (Mc + 3) / 4;
+    // fused pre-emphasis: builds of their own (LIB layout: they also serve centred frames)
     const unsigned psh = PRE ? a.preemph_shift % a.n_samples : 0u;
 
-    unsigned unit = __builtin_amdgcn_readfirstlane(u_lo + wave);  // uniform: kept scalar
-    while (unit < u_hi) {
-        unsigned next = 0;
-        if (lane == 0) next = atomicAdd(s_next, 1u);
-        next = __builtin_amdgcn_readfirstlane(next);
+    unsigned unit = __builtin_amdgcn_readfirstlane(ur.lo + wave);  // uniform: kept scalar
+    while (unit < ur.hi) {
+        const unsigned next = claim_next(s_next, lane);
 
         const unsigned gf_raw = 2 * unit + half;
         const bool live = gf_raw < total;
         const unsigned gf = live ? gf_raw : total - 1;
         const unsigned clip = gf / a.n_frames;
         const unsigned t = gf - clip * a.n_frames;
-        // stack_frames (processing.rs:65-129, contract framing): frame t starts at sample t*step
+        // stack_frames (processing.rs:65-129, contract framing): frame t starts at sample t*step; librosa center=True (LIB
+        // builds): it is centred on sample t*step
         const float *xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
-        float2 v[32];
-        // librosa center=True: frame t is centred on sample t*step; frames inside the clip load like contract frames from
-        // their (even) start, the few at the clip edges mirror (np.pad 'reflect') or zero their out-of-range samples
         const int s0 = static_cast<int>(t * a.step) - (LIB && a.center ? static_cast<int>(a.flen / 2) : 0);
-        const int ns = static_cast<int>(a.n_samples);
-        if (!LIB || __all(s0 >= 0 && s0 + static_cast<int>(a.flen) <= ns)) {
-            const float2 *src = reinterpret_cast<const float2 *>(xc + s0) + j;
-#pragma unroll
-            for (int e = 0; e < 32; ++e) {
-                float2 s = make_float2(0.f, 0.f);
-                if (e < e_hi) s = src[32 * e];
-                // odd frame length: the last sample is the first half of a pair (its partner is zero padding)
-                if (odd_tail && j + 32 * e == half_pairs) s = make_float2(xc[s0 + 2 * half_pairs], 0.f);
-                if (pre) {  // fused pre-emphasis (processing.rs:31-53) of the samples that exist
-                    const int pos = s0 + 2 * (j + 32 * e), rem = static_cast<int>(a.flen) - 2 * (j + 32 * e);
-                    if (rem >= 1) s.x = fmaf(-a.preemph, preemph_tap(xc, pos, psh, a.n_samples), s.x);
-                    if (rem >= 2) s.y = fmaf(-a.preemph, preemph_tap(xc, pos + 1, psh, a.n_samples), s.y);
-                }
-                v[e] = s;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 32; ++e) {
-                float sv[2] = {0.f, 0.f};
-                {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        int pos = s0 + 2 * (j + 32 * e) + h;
-                        bool ok = 2 * (j + 32 * e) + h < static_cast<int>(a.flen);  // zero pad; an odd frame length ends in a half pair
-                        if (pos < 0 || pos >= ns) {
-                            if (a.pad_reflect) pos = pos < 0 ? -pos : 2 * (ns - 1) - pos;
-                            else ok = false;
-                        }
-                        if (ok) sv[h] = pre ? fmaf(-a.preemph, preemph_tap(xc, pos, psh, a.n_samples), xc[pos]) : xc[pos];
-                    }
-                }
-                v[e] = make_float2(sv[0], sv[1]);
-            }
-        }
-        if (WIN) {
-#pragma unroll
-            for (int e = 0; e < 32; ++e) {
-                const float2 w = s_win[j + 32 * e];
-                v[e] = make_float2(v[e].x * w.x, v[e].y * w.y);
-            }
-        }
+        float2 v[32];
+        load_frame<32, LIB>(v, a, xc, s0, j, PRE, psh);
+        if (WIN) apply_window<32>(v, s_win, j);
         // ---- 1024-point complex FFT: radix-32, transpose through LDS (two register halves), twiddle, radix-32 ----
         fft_reg<32>(v);
         float2 u[32];
@@ -195,14 +146,9 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c1024(const Mfcc2048Args a
                 const float2 zk = u[q];
                 // lane 0 pairs with itself: Z[1024 - 32 q] = own register (32 - q) & 31
                 const float2 zc = j == 0 ? u[(32 - q) & 31] : zcs[qq];
-                const float2 w = s_twn[q * 32 + j];
-                const float2 s = make_float2(zk.x + zc.x, zk.y - zc.y);  // 2 E[k]
-                const float2 d = make_float2(zk.x - zc.x, zk.y + zc.y);
-                // 2 X[k] = s - i w d, 2 conj X[1024-k] = 2 s - 2 X[k]
-                const float xa_r = fmaf(w.y, d.x, fmaf(w.x, d.y, s.x));
-                const float xa_i = fmaf(w.y, d.y, fmaf(-w.x, d.x, s.y));
-                const float xb_r = fmaf(2.f, s.x, -xa_r), xb_i = fmaf(2.f, s.y, -xa_i);
-                const float na = xa_r * xa_r + xa_i * xa_i, nb = xb_r * xb_r + xb_i * xb_i;
+                const Bin b = untangle_bin(zk, zc, s_twn[q * 32 + j]);
+                const float xb_r = fmaf(2.f, b.s.x, -b.xr), xb_i = fmaf(2.f, b.s.y, -b.xi);  // 2 conj X[1024-k] = 2 s - 2 X[k]
+                const float na = b.xr * b.xr + b.xi * b.xi, nb = xb_r * xb_r + xb_i * xb_i;
                 const float pa = POW2 ? na : __builtin_amdgcn_sqrtf(na);
                 const float pb = POW2 ? nb : __builtin_amdgcn_sqrtf(nb);
                 prow[j + 32 * q] = pa;  // bins 0..511 (the bank ends at (F+1)/2, feature.rs:69-70); 512 below
@@ -222,32 +168,16 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c1024(const Mfcc2048Args a
         energy = energy == 0.f ? kEps * kTwo32 : energy;     // zero_handling, feature.rs:219
         wave_order();
 
-        // ---- banded mel reduction (feature.rs:229), zero handling (:230), ln (:105) -> row in filter order ----
-        {
-            int off = 0;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                float m = hscale32 * mel_slot4(w4 + off, reinterpret_cast<const float4 *>(prow + st[s]), a.mel_q4[s]);
-                m = m == 0.f ? kEps * kTwo32 : m;
-                if (fi[s] >= 0) {
-                    if (MFE) {
-                        if (live) a.out[static_cast<unsigned long long>(gf) * M + fi[s]] = m * (1.0f / kTwo32);  // exact: power of two
-                    } else {
-                        frow[fi[s]] = ln_scaled(m);
-                    }
-                }
-                off += a.mel_q4[s];
-            }
-        }
+        mel_ln_rows<MFE>(w4, prow, st, fi, a.mel_q4, hscale32, frow, a.out + static_cast<unsigned long long>(gf) * M, live);
         if (MFE) {
-            if (j == 0 && live) a.out_energy[gf] = energy * (1.0f / kTwo32);
+            store_mfe_energy(a.out_energy, gf, energy, j, live);
             wave_order();
             unit = next;
             continue;
         }
         wave_order();
-        // ---- DCT-II (feature.rs:120-123), cos(pi c (2(M-1-m)+1) / 2M) = (-1)^c cos(pi c (2m+1) / 2M), M even: sum and
-        // difference rows once per frame, then a M/2-term product per coefficient ----
+        // ---- DCT-II (feature.rs:120-123), cos(pi c (2(M-1-m)+1) / 2M) = (-1)^c cos(pi c (2m+1) / 2M): sum and difference rows
+        // once per frame (the text of ss_mfcc_c512's: see ss_frame32.h), then a (M+1)/2-term product per coefficient ----
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
             const int m = j + 32 * h2;
@@ -258,46 +188,25 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mfcc_c1024(const Mfcc2048Args a
             } else if (m < Mc) {  // odd filter count: the middle filter pairs with itself (its odd-coefficient cosines are zero)
                 srow[m] = frow[m];
                 drow[m] = 0.f;
-            } else if (m < ((Mc + 3) & ~3)) {  // the product below runs over whole float4s
+            } else if (m < ((Mc + 3) & ~3)) {  // dct_dot runs over whole float4s
                 srow[m] = 0.f;
                 drow[m] = 0.f;
             }
         }
         wave_order();
+        const float4 *r4 = reinterpret_cast<const float4 *>((j & 1) ? drow : srow);  // coefficients j and j + 32: same parity, same row
         if (j < Cc) {
-            const int c = j;
-            const float4 *r4 = reinterpret_cast<const float4 *>((j & 1) ? drow : srow);
-            const float4 *c4 = reinterpret_cast<const float4 *>(s_cos + c * L::kCosPitch);
-            float acc = 0.f;
-            const int nq = (Mc + 3) / 4;  // the rows are zero-padded to a multiple of 4 by the host table / the loop below
-            for (int i = 0; i < nq; ++i) {
-                const float4 r = r4[i], cw = c4[i];
-                acc = fmaf(r.x, cw.x, acc);
-                acc = fmaf(r.y, cw.y, acc);
-                acc = fmaf(r.z, cw.z, acc);
-                acc = fmaf(r.w, cw.w, acc);
-            }
+            const float acc = dct_dot(r4, reinterpret_cast<const float4 *>(s_cos + j * L::kCosPitch), nq);
             // scaling + column-0 replacement (feature.rs:126-146)
             float o = acc * a.dct_scale_k;
-            if (c == 0) o = a.dc_elimination ? ln_scaled(energy) : acc * (t == 0 ? a.dct_scale_00 : a.dct_scale_0);
-            if (live) a.out[static_cast<unsigned long long>(gf) * Cc + c] = o;
+            if (j == 0) o = a.dc_elimination ? ln_scaled(energy) : acc * (t == 0 ? a.dct_scale_00 : a.dct_scale_0);
+            if (live) a.out[static_cast<unsigned long long>(gf) * Cc + j] = o;
         }
-        if (Cc > 32) {  // 33..64 cepstra: the lane also forms coefficient c + 32 (same parity: same row)
+        if (Cc > 32) {  // 33..64 cepstra: the lane also forms coefficient j + 32
             wave_order();
             if (j + 32 < Cc) {
-                const int c = j + 32;
-                const float4 *r4 = reinterpret_cast<const float4 *>((j & 1) ? drow : srow);
-                const float4 *c4 = reinterpret_cast<const float4 *>(s_cos + c * L::kCosPitch);
-                float acc = 0.f;
-                const int nq = (Mc + 3) / 4;  // the rows are zero-padded to a multiple of 4 by the host table / the loop below
-                for (int i = 0; i < nq; ++i) {
-                    const float4 r = r4[i], cw = c4[i];
-                    acc = fmaf(r.x, cw.x, acc);
-                    acc = fmaf(r.y, cw.y, acc);
-                    acc = fmaf(r.z, cw.z, acc);
-                    acc = fmaf(r.w, cw.w, acc);
-                }
-                if (live) a.out[static_cast<unsigned long long>(gf) * Cc + c] = acc * a.dct_scale_k;
+                const float acc = dct_dot(r4, reinterpret_cast<const float4 *>(s_cos + (j + 32) * L::kCosPitch), nq);
+                if (live) a.out[static_cast<unsigned long long>(gf) * Cc + j + 32] = acc * a.dct_scale_k;
             }
         }
         wave_order();
@@ -318,31 +227,19 @@ hipError_t launch_g(const Mfcc2048Args &a, hipStream_t stream, int num_cus, Laun
     const unsigned grid = cu_capped_grid(units, WAVES, num_cus);
     auto go = [&](auto kern, const char *name) { return launch_kernel(kern, name, grid, WAVES, lds, stream, info, a); };
     const bool pow2 = a.spectrum_exponent == 2, win = a.windowed != 0;
-#define SS_G(P, M, W, LB, NAME) go(ss_mfcc_c1024<P, M, W, WAVES, LB>, NAME)
-#define SS_GP(P, M, W, NAME) go(ss_mfcc_c1024<P, M, W, WAVES, true, true>, NAME)
-    if (a.preemph != 0.f) {
-        if (a.out_mfe) {
-            if (pow2) return win ? SS_GP(true, true, true, "ss_mfcc_c1024<pow2,mfe,win,lib,pre>") : SS_GP(true, true, false, "ss_mfcc_c1024<pow2,mfe,lib,pre>");
-            return win ? SS_GP(false, true, true, "ss_mfcc_c1024<mfe,win,lib,pre>") : SS_GP(false, true, false, "ss_mfcc_c1024<mfe,lib,pre>");
-        }
-        if (pow2) return win ? SS_GP(true, false, true, "ss_mfcc_c1024<pow2,win,lib,pre>") : SS_GP(true, false, false, "ss_mfcc_c1024<pow2,lib,pre>");
-        return win ? SS_GP(false, false, true, "ss_mfcc_c1024<win,lib,pre>") : SS_GP(false, false, false, "ss_mfcc_c1024<lib,pre>");
-    }
-#undef SS_GP
-    if (lib) {
-        if (a.out_mfe) {
-            if (pow2) return win ? SS_G(true, true, true, true, "ss_mfcc_c1024<pow2,mfe,win,lib>") : SS_G(true, true, false, true, "ss_mfcc_c1024<pow2,mfe,lib>");
-            return win ? SS_G(false, true, true, true, "ss_mfcc_c1024<mfe,win,lib>") : SS_G(false, true, false, true, "ss_mfcc_c1024<mfe,lib>");
-        }
-        if (pow2) return win ? SS_G(true, false, true, true, "ss_mfcc_c1024<pow2,win,lib>") : SS_G(true, false, false, true, "ss_mfcc_c1024<pow2,lib>");
-        return win ? SS_G(false, false, true, true, "ss_mfcc_c1024<win,lib>") : SS_G(false, false, false, true, "ss_mfcc_c1024<lib>");
-    }
-    if (a.out_mfe) {
-        if (pow2) return win ? SS_G(true, true, true, false, "ss_mfcc_c1024<pow2,mfe,win>") : SS_G(true, true, false, false, "ss_mfcc_c1024<pow2,mfe>");
-        return win ? SS_G(false, true, true, false, "ss_mfcc_c1024<mfe,win>") : SS_G(false, true, false, false, "ss_mfcc_c1024<mfe>");
-    }
-    if (pow2) return win ? SS_G(true, false, true, false, "ss_mfcc_c1024<pow2,win>") : SS_G(true, false, false, false, "ss_mfcc_c1024<pow2>");
-    return win ? SS_G(false, false, true, false, "ss_mfcc_c1024<win>") : SS_G(false, false, false, false, "ss_mfcc_c1024");
+#define SS_G(P, M, W, LB, PR, NAME) go(ss_mfcc_c1024<P, M, W, WAVES, LB, PR>, NAME)
+// the eight builds of one layout; END closes a tag list (">" / ",lib>" / ",lib,pre>"), BARE is the list of the build without switches
+#define SS_GN(LB, PR, END, BARE)                                                                                                                            \
+    if (a.out_mfe) {                                                                                                                                        \
+        if (pow2) return win ? SS_G(true, true, true, LB, PR, "ss_mfcc_c1024<pow2,mfe,win" END) : SS_G(true, true, false, LB, PR, "ss_mfcc_c1024<pow2,mfe" END); \
+        return win ? SS_G(false, true, true, LB, PR, "ss_mfcc_c1024<mfe,win" END) : SS_G(false, true, false, LB, PR, "ss_mfcc_c1024<mfe" END);              \
+    }                                                                                                                                                       \
+    if (pow2) return win ? SS_G(true, false, true, LB, PR, "ss_mfcc_c1024<pow2,win" END) : SS_G(true, false, false, LB, PR, "ss_mfcc_c1024<pow2" END);      \
+    return win ? SS_G(false, false, true, LB, PR, "ss_mfcc_c1024<win" END) : SS_G(false, false, false, LB, PR, "ss_mfcc_c1024" BARE);
+    if (a.preemph != 0.f) { SS_GN(true, true, ",lib,pre>", "<lib,pre>") }
+    if (lib) { SS_GN(true, false, ",lib>", "<lib>") }
+    SS_GN(false, false, ">", "")
+#undef SS_GN
 #undef SS_G
 }
 

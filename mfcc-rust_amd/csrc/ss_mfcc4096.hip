@@ -19,6 +19,7 @@
 // Reference semantics: feature.rs:99-148 (mfcc), :200-233 (mfe), processing.rs:65-181.
 #include "ss_device.h"
 #include "ss_fft_reg.h"
+#include "ss_frame32.h"
 #include "ss_internal.h"
 #include "ss_wave.h"
 
@@ -656,8 +657,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void ss_mfcc_c2048(const Mfc
 // ss_mel_c2048: the mel-spectrogram path (frame_analysis + |X wnorm|^2 + mel einsum, functions.rs:125-170, feature.rs:151-174)
 // at fft_points = 4096 on the same FFT mapping: one wave owns one row (a 4096-sample window), the work unit is a (clip, row).
 // Row r covers the 4096 samples that end at chunk r + n_pad: zero initial state, zero tail, rows past the real ones all zero
-// (D3); windows inside the clip load at constant offsets, clip edges through one masked range per lane.  The table block is
-// mfcc4096_layout without cosine rows (the mel rows start at kCos) and with the Vorbis window behind the mel rows.
+// (D3) -- load_window of ss_frame32.h, which also holds this kernel's prologue (split_and_stage) and window multiply; the
+// untangle arithmetic is untangle_bin of ss_wave.h.  The table block is mfcc4096_layout without cosine rows (the mel rows
+// start at kCos) and with the Vorbis window behind the mel rows.
 template <int WAVES, bool STFT>
 __global__ __launch_bounds__(WAVES * 64) void ss_mel_c2048(const Mel2048Args a)
 {
@@ -681,15 +683,8 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c2048(const Mel2048Args a)
     unsigned *s_next = reinterpret_cast<unsigned *>(s_tab + L::kCos + 64 * a.mel_wpitch + 4096);
 
     const int R = static_cast<int>(a.rows), Rreal = static_cast<int>(a.real_rows), M = static_cast<int>(a.n_filters);
-    const unsigned total = a.batch * a.rows;
-    const unsigned f_lo = static_cast<unsigned>(static_cast<unsigned long long>(total) * blockIdx.x / gridDim.x);
-    const unsigned f_hi = static_cast<unsigned>(static_cast<unsigned long long>(total) * (blockIdx.x + 1) / gridDim.x);
-    {
-        const int n4 = (L::kCos + 64 * a.mel_wpitch + 4096) / 4;
-        for (int i = tid; i < n4; i += WAVES * 64) reinterpret_cast<float4 *>(s_tab)[i] = reinterpret_cast<const float4 *>(a.tab)[i];
-        if (tid == 0) *s_next = f_lo + WAVES;
-    }
-    __syncthreads();
+    const int n4 = (L::kCos + 64 * a.mel_wpitch + 4096) / 4;
+    const fr32::UnitRange ur = fr32::split_and_stage(a.batch * a.rows, s_tab, a.tab, n4, s_next, tid, WAVES);
     int st[4], fi[4];  // first P bin and filter index (-1: none) of this lane's four slots (one packed table word each)
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -704,52 +699,21 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c2048(const Mel2048Args a)
     const float hs = 0.25f * a.scale * a.scale;                      // |X wnorm|^2 = (wnorm^2 / 4) |2X|^2
     const bool k1z = k1 == 0;
 
-    unsigned row = __builtin_amdgcn_readfirstlane(f_lo + wave);  // uniform: kept scalar
-    while (row < f_hi) {
-        unsigned next = 0;
-        if (lane == 0) next = atomicAdd(s_next, 1u);
-        next = __builtin_amdgcn_readfirstlane(next);
+    unsigned row = __builtin_amdgcn_readfirstlane(ur.lo + wave);  // uniform: kept scalar
+    while (row < ur.hi) {
+        const unsigned next = claim_next(s_next, lane);
 
         const unsigned clip = row / a.rows;
         const int r = static_cast<int>(row - clip * a.rows);
         const float *xc = a.x + static_cast<unsigned long long>(clip) * a.ld;
         // functions.rs:137-151: the window covers the last 4096 samples ending at chunk r + n_pad
         const int start = static_cast<int>(r + a.n_pad + 1) * static_cast<int>(a.hop) - 4096;
-        const float2 *src = reinterpret_cast<const float2 *>(xc + start) + lane;
+        const int n = static_cast<int>(a.n_samples);
         float2 v[32];
-        if (r < Rreal && start >= 0 && start + 4096 <= static_cast<int>(a.n_samples)) {  // uniform: one row per wave
-#pragma unroll
-            for (int e = 0; e < 32; ++e) v[e] = src[64 * e];
-        } else {
-            // clip edges and inactive rows: start and n_samples are even, the valid sample pairs form one range per lane
-            // (the address of a masked load may lie outside the clip; it is never dereferenced)
-            const int base = start + 2 * lane;
-            const int n = static_cast<int>(a.n_samples);
-            if (((start | n) & 1) == 0) {
-                const int e_lo = base >= 0 ? 0 : (127 - base) >> 7;
-                int e_hi = base >= n ? 0 : min(32, (n - base + 127) >> 7);
-                if (r >= Rreal) e_hi = 0;
-#pragma unroll
-                for (int e = 0; e < 32; ++e) {
-                    float2 s = make_float2(0.f, 0.f);
-                    if (e >= e_lo && e < e_hi) s = src[64 * e];
-                    v[e] = s;
-                }
-            } else {  // odd hop or clip length: a pair may straddle the clip edge, bounds per sample
-                const bool act = r < Rreal;
-#pragma unroll
-                for (int e = 0; e < 32; ++e) {
-                    const int p0 = base + 128 * e;
-                    v[e] = make_float2(act && p0 >= 0 && p0 < n ? xc[p0] : 0.f, act && p0 + 1 >= 0 && p0 + 1 < n ? xc[p0 + 1] : 0.f);
-                }
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 32; ++e) {
-            const float2 w = s_win[lane + 64 * e];
-            v[e] = make_float2(v[e].x * w.x, v[e].y * w.y);
-        }
-        // ---- 2048-point complex FFT as in ss_mfcc_c2048 ----
+        const bool active = r < Rreal;  // uniform: one row per wave
+        fr32::load_window<32, 64>(v, xc, start, n, lane, active, active && start >= 0 && start + 4096 <= n);
+        fr32::apply_window<32, 64>(v, s_win, lane);
+        // ---- 2048-point complex FFT as in ss_mfcc_c2048 (shared with it by text only: that kernel is not touched) ----
         fft_reg<32>(v);
         float2 u[32];
 #pragma unroll
@@ -821,11 +785,9 @@ __global__ __launch_bounds__(WAVES * 64) void ss_mel_c2048(const Mel2048Args a)
                 const float2 zk = r0[i];
                 float2 zc = zcs[q];
                 if (i == 0) zc = k1z ? (d ? r1[0] : zk) : zc;
-                const float2 w = s_twn[i * 64 + lane];
-                const float2 s = make_float2(zk.x + zc.x, zk.y - zc.y);  // 2 E[k]
-                const float2 dd = make_float2(zk.x - zc.x, zk.y + zc.y);
-                const float xr = fmaf(w.y, dd.x, fmaf(w.x, dd.y, s.x));  // 2 X[k] = s - i w dd
-                const float xi = fmaf(w.y, dd.y, fmaf(-w.x, dd.x, s.y));
+                const Bin b = untangle_bin(zk, zc, s_twn[i * 64 + lane]);
+                const float xr = b.xr, xi = b.xi;
+                const float2 s = b.s;
                 if (STFT) {
                     srow[kb + 32 * i] = make_float2(cs * xr, cs * xi);
                     // 2 conj X[2048 - k] = 2 s - 2 X[k]

@@ -82,19 +82,7 @@ using namespace wv;
 __device__ __forceinline__ int partner_addr(int lane, int j) { return ((lane & 48) | ((16 - j) & 15)) << 2; }  // lane holding Z[256 - k]
 __device__ __forceinline__ int exchange_write_base(int j) { return 34 * (j >> 1) + (j & 1); }                  // float2 units
 
-// the table block to LDS, by the whole workgroup (n4 float4s)
-__device__ __forceinline__ void stage_tables(float *s_tab, const float *tab, int n4, int tid, int nthreads)
-{
-    for (int i = tid; i < n4; i += nthreads) reinterpret_cast<float4 *>(s_tab)[i] = reinterpret_cast<const float4 *>(tab)[i];
-}
-
-// the wave's next unit from the workgroup's LDS counter: lane 0 claims, the result is uniform
-__device__ __forceinline__ unsigned claim_next(unsigned *s_next, int lane)
-{
-    unsigned next = 0;
-    if (lane == 0) next = atomicAdd(s_next, 1u);
-    return __builtin_amdgcn_readfirstlane(next);
-}
+// (stage_tables and claim_next: ss_wave.h, shared with the frame stages of ss_frame32.h)
 
 // first radix-16 pass and the transposing scatter into the slot; v is dead afterwards (the caller's prefetch goes here)
 __device__ __forceinline__ void pass1(float2 (&v)[16], float2 *zh, int wbase1)
@@ -135,16 +123,11 @@ __device__ __forceinline__ void fetch_partners(const float2 (&u)[16], int paddr,
 // lane 0 pairs with itself: Z[256 - 16 r] = own register (16 - r) & 15
 __device__ __forceinline__ float2 partner(const float2 (&u)[16], const float2 (&zcs)[8], int j, int r) { return j == 0 ? u[(16 - r) & 15] : zcs[r]; }
 
-// Real-FFT untangle of k = j + 16 r with w = exp(-2 pi i k / 512): 2 X[k] = s - i w d = (xr, xi), s = 2 E[k].  The mirrored bin is
-// the caller's: 2 conj X[256-k] = 2 s - 2 X[k].
-struct Bin { float xr, xi; float2 s; };
+// Real-FFT untangle (untangle_bin, ss_wave.h) of k = j + 16 r with w = exp(-2 pi i k / 512): 2 X[k] = (xr, xi), s = 2 E[k].  The
+// mirrored bin is the caller's: 2 conj X[256-k] = 2 s - 2 X[k].
 __device__ __forceinline__ Bin untangle(const float2 (&u)[16], const float2 (&zcs)[8], float2 w, int j, int r)
 {
-    const float2 zk = u[r];
-    const float2 zc = partner(u, zcs, j, r);
-    const float2 s = make_float2(zk.x + zc.x, zk.y - zc.y);
-    const float2 d = make_float2(zk.x - zc.x, zk.y + zc.y);
-    return Bin{fmaf(w.y, d.x, fmaf(w.x, d.y, s.x)), fmaf(w.y, d.y, fmaf(-w.x, d.x, s.y)), s};
+    return untangle_bin(u[r], partner(u, zcs, j, r), w);
 }
 
 // raw banded-mel sums of a lane's N slots over the P row: slot k starts at bin st[k] and takes q4[k] float4s of the lane's

@@ -25,6 +25,20 @@ __device__ __forceinline__ void wg_barrier_lds()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// the table block to LDS, by the whole workgroup (n4 float4s)
+__device__ __forceinline__ void stage_tables(float *s_tab, const float *tab, int n4, int tid, int nthreads)
+{
+    for (int i = tid; i < n4; i += nthreads) reinterpret_cast<float4 *>(s_tab)[i] = reinterpret_cast<const float4 *>(tab)[i];
+}
+
+// the wave's next unit from the workgroup's LDS counter: lane 0 claims, the result is uniform
+__device__ __forceinline__ unsigned claim_next(unsigned *s_next, int lane)
+{
+    unsigned next = 0;
+    if (lane == 0) next = atomicAdd(s_next, 1u);
+    return __builtin_amdgcn_readfirstlane(next);
+}
+
 // Output stores that the compiler can COUNT.  vmcnt retires loads and stores together, in issue order (gfx9 family), and a store
 // is acknowledged only when it has reached L2 -- hundreds of nanoseconds under load.  A store inside `if (lane is valid)` sits
 // behind a branch, so the compiler cannot know whether it was issued and every later wait for the next unit's prefetched samples
@@ -191,6 +205,23 @@ __device__ __forceinline__ float half_sum(float v)
 __device__ __forceinline__ void swap_halves(float &a, float &b)
 {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+
+// v_permlane16_swap: the odd DPP rows (lanes 16..31, 48..63) of `a` trade places with the even rows of `b`
+// (tools/ubench/permlane16.hip).  Inline assembly with its own hazard s_nop, as above.
+__device__ __forceinline__ void swap_rows(float &a, float &b)
+{
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+
+// Real-FFT untangle of one bin of an N-point packed transform: zk = Z[k], zc = Z[N - k], w = exp(-2 pi i k / 2N).
+// 2 X[k] = s - i w d = (xr, xi) with s = 2 E[k]; the mirrored bin is the caller's: 2 conj X[N-k] = 2 s - 2 X[k].
+struct Bin { float xr, xi; float2 s; };
+__device__ __forceinline__ Bin untangle_bin(float2 zk, float2 zc, float2 w)
+{
+    const float2 s = make_float2(zk.x + zc.x, zk.y - zc.y);
+    const float2 d = make_float2(zk.x - zc.x, zk.y + zc.y);
+    return Bin{fmaf(w.y, d.x, fmaf(w.x, d.y, s.x)), fmaf(w.y, d.y, fmaf(-w.x, d.x, s.y)), s};
 }
 
 // A register that the compiler has to treat as defined, at no cost: an empty asm statement "writes" it.  For arrays that are

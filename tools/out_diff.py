@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Compare the OUTPUT BYTES of two builds of libspeechsauce_amd.so on a fixed list of small calls: the output-side sibling of
-tools/isa_diff.py, for a change that must not move a bit (a refactor of the quad kernels of ss_quad256.h).
+tools/isa_diff.py, for a change that must not move a bit (a refactor of the quad kernels of ss_quad256.h or of the frame stages of
+ss_frame32.h).
 
 usage: python tools/out_diff.py BEFORE_LIB AFTER_LIB      (needs a GPU)
 
@@ -19,6 +20,15 @@ Exit status 1 if any case differs.  The cases are at most a few hundred frames e
   ss_mfcc_c256x2   frame lengths 160 / 200 x 13 / 20 cepstra on 3 clips of 198 / 197 frames (594 / 591, not a multiple of 8), mfe, a
                    clip with a silent second half (the two-pass guard), a pure tone on a bin centre and a full-scale square wave
                    (the tiny-bin rerun)
+  ss_mfcc_c512     22050 Hz, fft 1024, frame length 883, hop 221, on 3 clips of 7 frames (21 frames = 11 pairs: a pair straddles each
+                   clip boundary, the last one is half dead; the clip length comes from SpeechConfig.num_frames): magnitude / power x
+                   mfcc / mfe x rect / hann x contract / centred (all 16 builds) and the same eight with fused pre-emphasis 0.97;
+                   centred frames with reflect and with constant padding, with and without pre-emphasis; a Slaney bank past bin
+                   fft_points / 4 (fullp); frame length 1024 (no zero tail); 41 and 127 filters; 33 and 64 cepstra; one clip of one frame
+  ss_mfcc_c1024    44100 Hz, fft 2048, frame length 1765, hop 441: the same list, over all 24 builds (the `pre` ones included)
+  ss_mel_c512      fft 1024, 16 kHz, hop 512: a bank to Nyquist and one held below bin 256, stft, an odd hop (441) at an odd clip
+                   length, a clip shorter than one window, an odd row count (the clip's last pair half dead)
+  ss_mel_c2048     fft 4096, 44.1 kHz, hop 1024: the same without the odd row count (one row per wave); odd hop 1103
 A measuring tool: not collected by pytest.
 """
 import ctypes as C
@@ -142,6 +152,75 @@ def cases(ss, np, torch):
     for sig, what in ((tone, "tone on a bin centre"), (square, "full-scale square wave")):
         front("ss_mfcc_c256x2", f"c256x2 mfcc {what}, 256-sample frames", ss._internal_mfcc_batch, sig, frame_length=0.032, **t8)
         front("ss_mfcc_c256x2", f"c256x2 mfe {what}, 256-sample frames", ss._internal_mfe_batch, sig, frame_length=0.032, spectrum_exponent=2, **t8)
+
+    # ---- ss_mfcc_c512 / ss_mfcc_c1024: two frames per wave ----
+    def clip_len(frames, **params):
+        """shortest clip that num_frames gives `frames` frames"""
+        cfg = ss.SpeechConfig(_lib.make_params(**params))
+
+        def count(n):
+            try:
+                return cfg.num_frames(n)
+            except _lib.SpeechSauceError:  # shorter than one frame
+                return 0
+
+        return next(n for n in range(1, 1 << 20) if count(n) == frames)
+
+    mfcc, mfe = (ss._internal_mfcc_batch, "mfcc"), (ss._internal_mfe_batch, "mfe")
+    for kernel, tag, sr, nfft, flen, hop, M in (("ss_mfcc_c512", "c512", 22050, 1024, 883, 221, 64), ("ss_mfcc_c1024", "c1024", 44100, 2048, 1765, 441, 128)):
+        b = dict(sample_rate=sr, fft_points=nfft, frame_length=flen / sr, frame_stride=hop / sr, num_filters=M, num_cepstral=20)
+        centred = dict(framing="center", pad_mode="reflect")
+        # 3 clips of 7 frames = 21 frames = 11 pairs: a pair straddles each clip boundary, the last one is half dead
+        x7, x7c = noise(3, clip_len(7, **b)), noise(3, clip_len(7, **b, **centred))
+        for pre in (0.0, 0.97):  # (ss_mfcc_c1024 has builds of its own for fused pre-emphasis)
+            for exp in (1, 2):
+                for fn, what in (mfcc, mfe):
+                    for win in ("rect", "hann"):
+                        sw = dict(spectrum_exponent=exp, mfcc_window=win, preemph_coef=pre)
+                        front(kernel, f"{tag} {what} exp{exp} {win} pre{pre} contract", fn, x7, **b, **sw)
+                        if pre == 0.0:
+                            front(kernel, f"{tag} {what} exp{exp} {win} centred reflect", fn, x7c, **b, **sw, **centred)
+        front(kernel, f"{tag} mfcc hann centred constant", mfcc[0], x7c, mfcc_window="hann", **dict(b, framing="center", pad_mode="constant"))
+        front(kernel, f"{tag} mfcc pre0.97 centred reflect", mfcc[0], x7c, preemph_coef=0.97, **b, **centred)
+        front(kernel, f"{tag} mfe pre0.97 hann centred constant", mfe[0], x7c, preemph_coef=0.97, mfcc_window="hann",
+              **dict(b, framing="center", pad_mode="constant"))
+        # a bank that reaches past bin fft_points / 4: the build with the whole P row, by its full name
+        for (fn, what), build in ((mfcc, "<lib>"), (mfe, "<mfe,lib>")):
+            front(kernel + build, f"{tag} {what} slaney bank to Nyquist (fullp)", fn, x7, mel_scale="slaney", mel_norm="slaney", **b)
+        full = dict(b, frame_length=nfft / sr)  # no zero tail
+        front(kernel, f"{tag} mfcc frame length {nfft}", mfcc[0], noise(3, clip_len(7, **full)), **full)
+        front(kernel, f"{tag} mfe frame length {nfft} hann", mfe[0], noise(3, clip_len(7, **full)), mfcc_window="hann", **full)
+        for filt in (41, 127):  # an odd count, and one whose DCT rows end in float4 padding
+            front(kernel, f"{tag} mfcc {filt} filters", mfcc[0], x7, **dict(b, num_filters=filt))
+        for ceps in (33, 64):
+            front(kernel, f"{tag} mfcc {ceps} cepstra", mfcc[0], x7, **dict(b, num_filters=127, num_cepstral=ceps))
+        front(kernel, f"{tag} mfcc one clip of one frame", mfcc[0], noise(1, clip_len(1, **b)), **b)
+        front(kernel, f"{tag} mfe one clip of one frame", mfe[0], noise(1, clip_len(1, **b)), **b)
+
+    # ---- ss_mel_c512 (two rows per wave) / ss_mel_c2048 (one) ----
+    for kernel, tag, sr, nfft, hop, odd_hop, M in (("ss_mel_c512", "mel1024", 16000, 1024, 512, 441, 80),
+                                                   ("ss_mel_c2048", "mel4096", 44100, 4096, 1024, 1103, 128)):
+        def mp(h):  # (a quarter sample over: the hop comes out as h whether the library truncates or rounds)
+            return dict(sample_rate=sr, fft_points=nfft, frame_length=(h + 0.25) / sr, frame_stride=(h + 0.25) / sr, num_filters=M)
+
+        def st(x, h, sr=sr, nfft=nfft):
+            return lambda: torch.view_as_real(ss.stft(x, sr, frame_length=(h + 0.25) / sr, fft_length=nfft))
+
+        rows = ss.SpeechConfig(_lib.make_params(**mp(hop))).stft_rows
+        xe = noise(3, next(n for n in range(6 * hop, 12 * hop, hop) if rows(n)[0] % 2 == 0))
+        front(kernel, f"{tag} mel bank to Nyquist", mel, xe, **mp(hop))
+        front(kernel, f"{tag} mel bank below bin {nfft // 4}", mel, xe, high_frequency=0.2 * sr, **mp(hop))
+        out.append((f"{tag} stft", kernel + "<stft>", st(xe, hop)))
+        xo = noise(3, 7 * odd_hop + 1 if odd_hop % 2 == 0 else 7 * odd_hop)  # an odd hop at an odd clip length
+        front(kernel, f"{tag} mel odd hop {odd_hop}, odd clip length", mel, xo, **mp(odd_hop))
+        out.append((f"{tag} stft odd hop {odd_hop}, odd clip length", kernel + "<stft>", st(xo, odd_hop)))
+        xs = noise(2, nfft // 2 + 188)
+        front(kernel, f"{tag} mel clip shorter than a window", mel, xs, **mp(hop))
+        out.append((f"{tag} stft clip shorter than a window", kernel + "<stft>", st(xs, hop)))
+        if kernel == "ss_mel_c512":  # an odd row count: the last pair of a clip is half dead
+            xr = noise(3, next(n for n in range(6 * hop, 12 * hop, hop) if rows(n)[0] % 2 == 1))
+            front(kernel, f"{tag} mel odd row count", mel, xr, **mp(hop))
+            out.append((f"{tag} stft odd row count", kernel + "<stft>", st(xr, hop)))
     return out
 
 
