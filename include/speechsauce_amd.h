@@ -1676,6 +1676,88 @@ int ss_whisper_log_mel_packed_i16_device(const ss_whisper_config *cfg, const int
 int ss_whisper_log_mel_packed_i16(const ss_whisper_config *cfg, const int16_t *x, size_t n_clips, const int64_t *sample_offsets, float scale,
                                   size_t n_frames, int dtype, void *out, int32_t *lengths);
 
+/* ---- NeMo / Parakeet log-mel front end (NeMo's AudioToMelSpectrogramPreprocessor / FilterbankFeatures;
+ *      transformers.ParakeetFeatureExtractor) ----------------------------------------------------------------------------------
+ * The model input of the NeMo family of encoders: Parakeet, Canary, FastConformer and the models built on them.  The reference
+ * crate has no such stage; this comment is the definition and tests/nemo_model.py restates it in numpy f64.  Sizes: sample_rate
+ * 16000, n_fft N = 512, hop_length H = 160, win_length W even in [258, 512] (default 400), lo = (N - W) / 2.  For one clip x of len
+ * samples:
+ *   1. T = len / H rounded down (the extractor's features_lengths: torch.stft yields one frame more, which is dropped).  T = 0 is
+ *      allowed: the clip has no rows.
+ *   2. y[i] = fmaf(-c, x[i - 1], x[i]) for 0 <= i < len with x[-1] = 0, c = preemph (0: the samples as they are); y[i] = 0 for every
+ *      other i -- the zero beyond len is applied AFTER the pre-emphasis, as the extractor's masked_fill does.
+ *   3. frame t, n = 0 .. W - 1: s[n] = y[t H - N / 2 + lo + n] * w[n], w[n] = 0.5 - 0.5 cos(2 pi n / (W - 1)) (the symmetric Hann
+ *      window, formed in f64, rounded once).  The frames are centred with ZERO padding: the first ones begin before the clip, the
+ *      last ones end behind it.
+ *   4. P[k] = |sum_n s[n] exp(-2 pi i k n / N)|^2, k = 0 .. 256: the live samples sit at positions 0 .. W - 1 of the transform (the
+ *      shift by lo that torch.stft applies changes the phase only).
+ *   5. mel[m] = sum_k B[m, k] P[k], B = librosa.filters.mel(sr=16000, n_fft=512, n_mels, fmin=0, fmax=8000, norm="slaney"),
+ *      [n_mels x 257], formed in f64 and rounded to f32; the Nyquist bin has weight 0 in it.
+ *   6. l = ln(mel + log_guard), log_guard = 2^-24.
+ *   7. normalize = SS_NEMO_NORM_NONE: row t = l.
+ *   8. SS_NEMO_NORM_PER_FEATURE: per band over the clip's own T rows, mean = sum l / T, var = sum (l - mean)^2 / (T - 1) (ddof = 1),
+ *      out = (l - mean) / (sqrt(var) + norm_eps), norm_eps = 1e-5 (the f32 value, widened).  Both sums are formed in f64 in row
+ *      order and the result is rounded to f32 once.  With T = 1 the deviation is taken as 0 and the row is all zeros: NeMo's own
+ *      rule for a single frame; the extractor's text divides by T - 1 = 0 there and gives NaN, which is not reproduced.
+ *   Output: packed float32 rows [total_frames x n_mels], the layout ss_specaug_packed / ss_pad_packed / ss_splice_packed take.
+ *   Arithmetic (f32): steps 2 and 3 round every product and sum on their own (step 2 is one fmaf); one 256-point complex transform
+ *   of the sample pairs and the real-FFT untangle; mel[m] over the filter's taps in ascending k, one fmaf a step; step 6 is
+ *   v_log_f32 of fmaf(0.25, sum |2X|^2 B, log_guard) times ln 2.  The dense and the packed call run the same kernel code.
+ * Served: sample_rate / n_fft / hop_length = 16000 / 512 / 160 and n_mels <= 128; anything else that is a valid combination is
+ *   SS_ERR_UNSUPPORTED.  SS_ERR_BAD_CONFIG: n_mels < 1, a win_length that is odd or outside [258, 512], a preemph, log_guard or
+ *   norm_eps that is negative or not finite, log_guard = 0, an unknown normalize, sample_rate / hop_length = 0, an odd n_fft.  A
+ *   struct_size other than sizeof(ss_nemo_params) is SS_ERR_ARG.
+ * The handle is opaque and immutable: the tables go to the device it was created on, with a pinned device error word of its own
+ *   (ss_nemo_config_device_status has ss_kaldi_config_device_status's contract).
+ * Dense call: every row of d_x ([batch] rows of n_samples, row stride ld >= n_samples) is a clip; out is [batch x T x n_mels].
+ * Packed call: clip b is d_x[so[b] .. so[b + 1]) and owns rows fo[b] .. fo[b + 1]; both tables are int64 [n_clips + 1] on the device
+ *   (ss_nemo_packed_frame_offsets computes fo on the host; the offsets ss_resample_packed_offsets wrote are valid sample offsets as
+ *   they stand).  A clip whose entries are inconsistent -- negative length, longer than 2^31 - 1 samples, rows that are not the
+ *   T its samples give, rows past total_frames -- is skipped by every launch: nothing of it is loaded and nothing stored, the
+ *   handle's error word is raised and reported once (SS_ERR_DEVICE, by ss_nemo_config_device_status or the next call on the
+ *   handle).  No sample outside [so[b], so[b + 1]) is fetched for clip b: what lies there belongs to the neighbour.
+ * One launch of ss_nemo_c256<NE[,v]> (ss_last_kernel_name(); NE = 10 / 13 / 16 live sample pairs per lane for W <= 320 / 416 / 512,
+ *   v: packed), then with SS_NEMO_NORM_PER_FEATURE ss_nemo_norm_kernel in place on the rows.  Both queue on `stream` only; the grids
+ *   depend on the row count, n_clips and n_mels; nothing is allocated or read back inside a call, so the calls replay as a captured
+ *   graph over changed device tables.
+ * The host forms stage through the device; the packed one refuses a bad sample table (SS_ERR_ARG) before any launch.
+ * Not served: 16-bit PCM twins, stream-pool forms, dither, other n_fft / hop_length / sample rates, normalize = "all_features",
+ *   narrow-band fmin / fmax, NaN for T = 1. */
+#define SS_NEMO_NORM_NONE 0
+#define SS_NEMO_NORM_PER_FEATURE 1
+typedef struct ss_nemo_params {
+    uint32_t struct_size; /* sizeof(ss_nemo_params) */
+    uint32_t sample_rate; /* 16000 */
+    uint32_t n_fft;       /* 512 */
+    uint32_t win_length;  /* even, 258 .. 512; 400 */
+    uint32_t hop_length;  /* 160 */
+    uint32_t n_mels;      /* 80 or 128 (1 .. 128) */
+    int32_t normalize;    /* SS_NEMO_NORM_* */
+    float preemph;        /* 0.97; 0: none */
+    float log_guard;      /* 2^-24 */
+    float norm_eps;       /* 1e-5 */
+} ss_nemo_params;
+typedef struct ss_nemo_config ss_nemo_config; /* opaque */
+
+/* host only, no device */
+int ss_nemo_params_default(ss_nemo_params *p, uint32_t n_mels);
+int ss_nemo_params_validate(const ss_nemo_params *p);
+int ss_nemo_num_frames(const ss_nemo_params *p, size_t n_samples, size_t *n_frames); /* n_samples / 160; 0 is a result */
+int ss_nemo_packed_frame_offsets(const ss_nemo_params *p, size_t n_clips, const int64_t *sample_offsets, int64_t *frame_offsets);
+int ss_nemo_window(const ss_nemo_params *p, float *w);      /* [win_length] */
+int ss_nemo_mel_bank(const ss_nemo_params *p, float *bank); /* [n_mels x 257] */
+
+int ss_nemo_config_create(const ss_nemo_params *p, ss_nemo_config **out);
+void ss_nemo_config_destroy(ss_nemo_config *cfg);
+int ss_nemo_config_params(const ss_nemo_config *cfg, ss_nemo_params *out);
+int ss_nemo_config_device_status(const ss_nemo_config *cfg);
+
+int ss_nemo_log_mel_device(const ss_nemo_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out, void *stream);
+int ss_nemo_log_mel(const ss_nemo_config *cfg, const float *x, size_t batch, size_t n_samples, size_t ld, float *out);
+int ss_nemo_log_mel_packed_device(const ss_nemo_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                  const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream);
+int ss_nemo_log_mel_packed(const ss_nemo_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out);
+
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`
  * computes clips [lo, hi) of ss_shard_bounds on its own device with the *_device entry points.  The north-star's "RCCL

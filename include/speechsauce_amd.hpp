@@ -1129,6 +1129,72 @@ private:
     std::shared_ptr<ss_whisper_config> h_;
 };
 
+// The NeMo / Parakeet log-mel rows (ss_nemo_*; not in the reference crate): [len / 160 x n_mels] per clip, packed rows for clips of
+// different lengths.
+inline ss_nemo_params nemo_params(uint32_t n_mels)  // 16000 / 512 / 400 / 160, pre-emphasis 0.97, per-feature normalisation
+{
+    ss_nemo_params p;
+    check(ss_nemo_params_default(&p, n_mels));
+    return p;
+}
+class NemoFrontEnd {
+public:
+    explicit NemoFrontEnd(const ss_nemo_params &p) : p_(p)
+    {
+        ss_nemo_config *raw = nullptr;
+        check(ss_nemo_config_create(&p_, &raw));
+        h_ = std::shared_ptr<ss_nemo_config>(raw, ss_nemo_config_destroy);
+    }
+    explicit NemoFrontEnd(uint32_t n_mels = 80) : NemoFrontEnd(nemo_params(n_mels)) {}
+    const ss_nemo_params &params() const { return p_; }
+    const ss_nemo_config *handle() const { return h_.get(); }
+    // n_samples / 160: the rows kept of a clip (0 for a clip shorter than one hop)
+    size_t num_frames(size_t n_samples) const
+    {
+        size_t t = 0;
+        check(ss_nemo_num_frames(&p_, n_samples, &t));
+        return t;
+    }
+    // SS_ERR_DEVICE once if a packed launch has skipped an inconsistent clip since the last look
+    void device_status() const { check(ss_nemo_config_device_status(h_.get())); }
+    // one clip -> [len / 160 x n_mels]
+    std::vector<float> log_mel(const std::vector<float> &x) const
+    {
+        std::vector<float> out(num_frames(x.size()) * p_.n_mels);
+        if (!out.empty()) check(ss_nemo_log_mel(h_.get(), x.data(), 1, x.size(), x.size(), out.data()));
+        return out;
+    }
+    // clips packed end to end, clip b = x[sample_offsets[b] .. sample_offsets[b+1]) -> the rows [sum T_b x n_mels]; frame_offsets (may
+    // be null) receives the n_clips + 1 row offsets
+    std::vector<float> log_mel_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets,
+                                      std::vector<int64_t> *frame_offsets = nullptr) const
+    {
+        if (sample_offsets.empty() || sample_offsets.back() < 0 || static_cast<size_t>(sample_offsets.back()) > x.size())
+            throw Error(SS_ERR_ARG, "nemo packed call: shape mismatch");
+        const size_t n = sample_offsets.size() - 1;
+        std::vector<int64_t> fo(n + 1);
+        check(ss_nemo_packed_frame_offsets(&p_, n, sample_offsets.data(), fo.data()));
+        std::vector<float> out(static_cast<size_t>(fo[n]) * p_.n_mels);
+        if (!out.empty()) check(ss_nemo_log_mel_packed(h_.get(), x.data(), n, sample_offsets.data(), out.data()));
+        if (frame_offsets) *frame_offsets = fo;
+        return out;
+    }
+    // the device calls on `stream`: device pointers, nothing is copied or allocated
+    void log_mel_device(const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out, void *stream) const
+    {
+        check(ss_nemo_log_mel_device(h_.get(), d_x, batch, n_samples, ld, d_out, stream));
+    }
+    void log_mel_packed_device(const float *d_x, size_t n_clips, const int64_t *d_sample_offsets, const int64_t *d_frame_offsets,
+                               size_t total_frames, float *d_out, void *stream) const
+    {
+        check(ss_nemo_log_mel_packed_device(h_.get(), d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, stream));
+    }
+
+private:
+    ss_nemo_params p_;
+    std::shared_ptr<ss_nemo_config> h_;
+};
+
 // processing.rs:222-254
 inline std::vector<float> derivative_extraction(const std::vector<float> &feat, size_t rows, size_t cols, size_t delta_windows)
 {

@@ -3662,3 +3662,225 @@ int ss_kstream_mfcc_packed_i16(const ss_kaldi_config *cfg, const int16_t *x, siz
 }
 
 }  // extern "C"
+
+// ---- NeMo / Parakeet log-mel front end (ss_nemo_*; kernels: ss_nemo512.hip) --------------------------------------------------
+// The handle, as ss_kaldi_config: the validated parameters, the kernel's table block on the device it was created on, and a pinned
+// device error word of its own.  Immutable after creation.
+struct ss_nemo_config {
+    ss_nemo_params params{};
+    ss::NemoTables tabs;
+    int device = -1;
+    int num_cus = 256;
+    float *d_tab = nullptr;
+    unsigned *h_err = nullptr, *d_err = nullptr;
+};
+
+namespace {
+
+int nemo_pending_error(const ss_nemo_config *cfg)
+{
+    if (!cfg->h_err || __atomic_load_n(cfg->h_err, __ATOMIC_ACQUIRE) == 0) return SS_OK;
+    const unsigned w = __atomic_exchange_n(cfg->h_err, 0u, __ATOMIC_ACQ_REL);
+    if (w == 0) return SS_OK;
+    return ss::fail(SS_ERR_DEVICE, "a kernel launched on this handle skipped a packed clip whose offsets are inconsistent (error word " +
+                                       std::to_string(w) + "): the rows of that clip were left untouched");
+}
+
+int nemo_ready(const ss_nemo_config *cfg)
+{
+    int dev = -1;
+    SS_HIP(hipGetDevice(&dev));
+    if (dev != cfg->device) return ss::fail(SS_ERR_ARG, "the handle was created on a different HIP device than the current one");
+    return nemo_pending_error(cfg);
+}
+
+// the handle's part of the kernels' argument block
+ss::NemoArgs nemo_args(const ss_nemo_config *cfg, const float *x, float *out)
+{
+    const ss_nemo_params &p = cfg->params;
+    ss::NemoArgs a{};
+    a.x = x;
+    a.win_len = p.win_length;
+    a.tab = cfg->d_tab;
+    a.mel_wpitch = cfg->tabs.wpitch;
+    std::copy(cfg->tabs.q4, cfg->tabs.q4 + ss::nemo512_layout::kSlots, a.mel_q4);
+    a.n_mels = p.n_mels;
+    a.preemph = p.preemph;
+    a.log_guard = p.log_guard;
+    a.norm_eps = p.norm_eps;
+    a.out = out;
+    return a;
+}
+
+// the rows, then (per-feature normalisation) step 8 in place on them: one or two launches on `stream`
+int nemo_launch(const ss_nemo_config *cfg, const ss::NemoArgs &a, const ss::NemoVarlenArgs *v, hipStream_t stream)
+{
+    ss::LaunchInfo info{};
+    const hipError_t e = v ? ss::launch_nemo_c256_varlen(a, *v, stream, cfg->num_cus, &info) : ss::launch_nemo_c256(a, stream, cfg->num_cus, &info);
+    if (e != hipSuccess) return hip_fail(e, "launch_nemo_c256");
+    g_last_kernel = info.kernel_name;
+    if (cfg->params.normalize == SS_NEMO_NORM_PER_FEATURE) {
+        const hipError_t n = ss::launch_nemo_norm(a, v, stream);
+        if (n != hipSuccess) return hip_fail(n, "launch_nemo_norm");
+    }
+    return SS_OK;
+}
+
+// equal-length clips; T: the rows per clip (0: nothing to do)
+int nemo_check_dense(const ss_nemo_config *cfg, const float *x, size_t n_samples, size_t batch, size_t ld, const float *out, size_t &T)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null handle");
+    if (!x || !out) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (ld < n_samples) return ss::fail(SS_ERR_ARG, "leading dimension smaller than n_samples");
+    if (n_samples >= (1ull << 31) || batch >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "batch and n_samples must be below 2^31");
+    T = n_samples / ss::kNemoHop;
+    if (static_cast<unsigned long long>(batch) * T + 8 >= 0xffffffffull) return ss::fail(SS_ERR_ARG, "batch * frames must be below 2^32 - 8");
+    return SS_OK;
+}
+
+int nemo_dense_device(const ss_nemo_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out, hipStream_t stream)
+{
+    if (batch == 0) return cfg ? SS_OK : ss::fail(SS_ERR_ARG, "null handle");
+    size_t T = 0;
+    if (int rc = nemo_check_dense(cfg, d_x, n_samples, batch, ld, d_out, T)) return rc;
+    if (int rc = nemo_ready(cfg)) return rc;
+    if (T == 0) return SS_OK;  // clips shorter than one hop have no rows
+    ss::NemoArgs a = nemo_args(cfg, d_x, d_out);
+    a.ld = ld;
+    a.n_samples = static_cast<uint32_t>(n_samples);
+    a.batch = static_cast<uint32_t>(batch);
+    a.n_frames = static_cast<uint32_t>(T);
+    return nemo_launch(cfg, a, nullptr, stream);
+}
+
+int nemo_packed_device(const ss_nemo_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_so, const int64_t *d_fo, size_t total_frames,
+                       float *d_out, hipStream_t stream)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null handle");
+    if (n_clips == 0) return SS_OK;
+    if (!d_x || !d_so || !d_fo || !d_out) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_clips >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "n_clips must be below 2^31");
+    if (static_cast<unsigned long long>(total_frames) + 8 >= 0xffffffffull) return ss::fail(SS_ERR_ARG, "total_frames must be below 2^32 - 8");
+    if (int rc = nemo_ready(cfg)) return rc;
+    if (total_frames == 0) return SS_OK;  // no clip can own a row
+    const ss::NemoArgs a = nemo_args(cfg, d_x, d_out);
+    ss::NemoVarlenArgs v{};
+    v.so = reinterpret_cast<const long long *>(d_so);
+    v.fo = reinterpret_cast<const long long *>(d_fo);
+    v.total_frames = total_frames;
+    v.n_clips = static_cast<uint32_t>(n_clips);
+    v.err = cfg->d_err;
+    return nemo_launch(cfg, a, &v, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ss_nemo_config_create(const ss_nemo_params *p, ss_nemo_config **out)
+{
+    if (!p || !out) return ss::fail(SS_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (int rc = ss::nemo_validate(*p)) return rc;
+    std::unique_ptr<ss_nemo_config> cfg(new ss_nemo_config());
+    cfg->params = *p;
+    ss::build_nemo512(*p, cfg->tabs);
+    if (!cfg->tabs.ok) return ss::fail(SS_ERR_UNSUPPORTED, "the mel bank does not fit the kernel's eight filter slots per lane");
+    if (!ss::have_device()) return ss::no_device("hot path");
+    SS_HIP(hipGetDevice(&cfg->device));
+    hipDeviceProp_t prop;
+    SS_HIP(hipGetDeviceProperties(&prop, cfg->device));
+    cfg->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (int rc = upload(&cfg->d_tab, cfg->tabs.tab.data(), cfg->tabs.tab.size() * sizeof(float))) {
+        ss_nemo_config_destroy(cfg.release());
+        return rc;
+    }
+    void *hp = nullptr, *dp = nullptr;
+    hipError_t e = hipHostMalloc(&hp, 64, hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&dp, hp, 0);
+    if (e != hipSuccess) {
+        if (hp) (void)hipHostFree(hp);
+        ss_nemo_config_destroy(cfg.release());
+        return hip_fail(e, "hipHostMalloc (device error word)");
+    }
+    std::memset(hp, 0, 64);
+    cfg->h_err = static_cast<unsigned *>(hp);
+    cfg->d_err = static_cast<unsigned *>(dp);
+    *out = cfg.release();
+    return SS_OK;
+}
+
+void ss_nemo_config_destroy(ss_nemo_config *cfg)
+{
+    if (!cfg) return;
+    if (cfg->d_tab) (void)hipFree(cfg->d_tab);
+    if (cfg->h_err) (void)hipHostFree(cfg->h_err);
+    delete cfg;
+}
+
+int ss_nemo_config_params(const ss_nemo_config *cfg, ss_nemo_params *out)
+{
+    if (!cfg || !out) return ss::fail(SS_ERR_ARG, "null argument");
+    *out = cfg->params;
+    return SS_OK;
+}
+
+int ss_nemo_config_device_status(const ss_nemo_config *cfg)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null handle");
+    return nemo_pending_error(cfg);
+}
+
+int ss_nemo_log_mel_device(const ss_nemo_config *cfg, const float *d_x, size_t batch, size_t n_samples, size_t ld, float *d_out, void *stream)
+{
+    return nemo_dense_device(cfg, d_x, batch, n_samples, ld, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_nemo_log_mel(const ss_nemo_config *cfg, const float *x, size_t batch, size_t n_samples, size_t ld, float *out)
+{
+    if (batch == 0) return cfg ? SS_OK : ss::fail(SS_ERR_ARG, "null handle");
+    size_t T = 0;
+    if (int rc = nemo_check_dense(cfg, x, n_samples, batch, ld, out, T)) return rc;
+    if (T == 0) return SS_OK;
+    if (!ss::have_device()) return ss::no_device("hot path");
+    const size_t obytes = batch * T * cfg->params.n_mels * sizeof(float);
+    ss::HostStage st("ss_nemo");
+    float *d_in = st.room<float>(batch * n_samples * sizeof(float));
+    float *d_out = st.room<float>(obytes);
+    st.up_rows(d_in, x, ld * sizeof(float), n_samples * sizeof(float), batch);
+    if (st.ok()) st.ran(nemo_dense_device(cfg, d_in, batch, n_samples, n_samples, d_out, nullptr));
+    st.sync();
+    st.down(out, d_out, obytes);
+    return st.status();
+}
+
+int ss_nemo_log_mel_packed_device(const ss_nemo_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
+                                  const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream)
+{
+    return nemo_packed_device(cfg, d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_nemo_log_mel_packed(const ss_nemo_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null handle");
+    if (n_clips == 0) return SS_OK;
+    if (!x || !sample_offsets || !out) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_clips >= (1ull << 31)) return ss::fail(SS_ERR_ARG, "n_clips must be below 2^31");
+    std::vector<int64_t> fo(n_clips + 1);
+    if (int rc = ss_nemo_packed_frame_offsets(&cfg->params, n_clips, sample_offsets, fo.data())) return rc;
+    const size_t total_in = static_cast<size_t>(sample_offsets[n_clips]), rows = static_cast<size_t>(fo[n_clips]);
+    if (rows == 0) return SS_OK;
+    if (!ss::have_device()) return ss::no_device("hot path");
+    const size_t obytes = rows * cfg->params.n_mels * sizeof(float), tbytes = (n_clips + 1) * sizeof(int64_t);
+    ss::HostStage st("ss_nemo");
+    const float *d_in = st.up(x, total_in * sizeof(float));
+    float *d_out = st.room<float>(obytes);
+    const int64_t *d_so = st.up(sample_offsets, tbytes), *d_fo = st.up(fo.data(), tbytes);
+    if (st.ok()) st.ran(nemo_packed_device(cfg, d_in, n_clips, d_so, d_fo, rows, d_out, nullptr));
+    st.sync();
+    if (st.ok()) st.ran(nemo_pending_error(cfg));
+    st.down(out, d_out, obytes);
+    return st.status();
+}
+
+}  // extern "C"

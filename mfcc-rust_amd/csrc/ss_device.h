@@ -153,6 +153,24 @@ __device__ __forceinline__ unsigned offset_seek(const long long *off, unsigned n
     if (c + 1 < n && off[c + 1] <= g) c = offset_find(off, n, g);
     return c;
 }
+// The quad kernels' form (ss_kaldi_c256, ss_nemo_c256): the owner (clip of a packed launch, entry of a pool launch) of row
+// g = q4 + 0..3 over the row offsets `off`: the owner of the quad's first row from the wave's forward cursor (claims only increase),
+// then at most three owners WITH rows further on.
+__device__ __forceinline__ unsigned row_owner(const long long *off, unsigned n, unsigned q4, unsigned g, unsigned &cursor)
+{
+    unsigned c = offset_seek(off, n, cursor, q4);
+    cursor = c;
+    bool step = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        step = c + 1 < n && off[c + 1] <= static_cast<long long>(g);
+        c += step ? 1u : 0u;
+    }
+    // owners without rows inside the quad (off[b] == off[b + 1]) take steps of their own: a lane that took all three looks once
+    // more, and searches where they did not get there
+    if (step && c + 1 < n && off[c + 1] <= static_cast<long long>(g)) c = offset_find(off, n, static_cast<long long>(g));
+    return c;
+}
 
 // Frames of a clip of L samples, as ss::num_frames computes them on the host (processing.rs:101 in f32; padded: ceil; centred:
 // 1 + L / step).  0: the clip yields none (the host rejects it) or is longer than 2^31 - 1 samples.
@@ -858,6 +876,38 @@ hipError_t launch_kaldi_c256_varlen(const KaldiArgs &a, const KaldiVarlenPcmArgs
 // is 0: the entry pass).  The advance is launch_stream_advance_packed over the same block.
 hipError_t launch_kaldi_c256_stream_packed(const KaldiArgs &a, const FrameStreamPackedPcmArgs &sp, bool pcm, hipStream_t stream, int num_cus,
                                            LaunchInfo *info);
+
+// Arguments of the NeMo / Parakeet log-mel kernels (ss_nemo512.hip; the specification is the ss_nemo_* comment of
+// include/speechsauce_amd.h).
+struct NemoArgs {
+    const float *x;
+    unsigned long long ld;
+    uint32_t n_samples, batch, n_frames;  // equal-length clips: n_frames = n_samples / 160 rows each
+    uint32_t win_len;    // W: live samples per frame (even); frame t starts at clip sample 160 t - W / 2
+    const float *tab;    // table block (ss::NemoTables, nemo512_layout), copied verbatim into LDS
+    int32_t mel_wpitch;  // floats per lane weight row
+    int32_t mel_q4[8];   // taps / 4 per slot
+    uint32_t n_mels;
+    float preemph;       // step 2 (0: skipped)
+    float log_guard;     // step 6
+    float norm_eps;      // step 8
+    float *out;          // [rows x n_mels]
+    uint32_t nf_magic, nf_shift;  // set by the launcher: frame -> (clip, t) by multiply-high
+};
+// Packed clips: KaldiVarlenArgs' layout with T = len / 160; a clip without rows is consistent.
+struct NemoVarlenArgs {
+    const long long *so;  // [n_clips + 1] sample offsets
+    const long long *fo;  // [n_clips + 1] frame (output row) offsets
+    unsigned long long total_frames;
+    uint32_t n_clips;
+    unsigned *err;        // the handle's device error word (set to kVarlenError on a bad clip)
+};
+hipError_t launch_nemo_c256(const NemoArgs &a, hipStream_t stream, int num_cus, LaunchInfo *info);
+// a: x / out = the packed blocks; batch / n_samples / n_frames / ld are unused
+hipError_t launch_nemo_c256_varlen(const NemoArgs &a, const NemoVarlenArgs &v, hipStream_t stream, int num_cus, LaunchInfo *info);
+// step 8 in place on a.out: the rows of a.batch clips of a.n_frames rows, or (v non-null) of the packed clips, a bad one skipped.
+// The grid depends on the clip count and n_mels only.
+hipError_t launch_nemo_norm(const NemoArgs &a, const NemoVarlenArgs *v, hipStream_t stream);
 
 // The fused splice + affine transform of packed rows (ss_affine.hip; ss_affine_splice_packed*): out[g] = M * (spliced row g) + bias
 // on the f32 matrix instruction.  x / ro and out / oo are the two packed blocks and their tables as ss_splice_packed_device takes

@@ -1180,6 +1180,70 @@ void build_kaldi512(const ss_kaldi_params &p, KaldiTables &f)
     f.ok = true;
 }
 
+// ---- NeMo / Parakeet log-mel front end (ss_nemo_* in include/speechsauce_amd.h; kernels: ss_nemo512.hip) ----
+int nemo_validate(const ss_nemo_params &p)
+{
+    if (p.struct_size != sizeof(ss_nemo_params)) return fail(SS_ERR_ARG, "ss_nemo_params.struct_size mismatch (ABI)");
+    if (p.sample_rate == 0) return fail(SS_ERR_BAD_CONFIG, "sample_rate must be > 0");
+    if (p.n_fft < 2 || p.n_fft % 2) return fail(SS_ERR_BAD_CONFIG, "n_fft must be even and at least 2");
+    if (p.hop_length == 0) return fail(SS_ERR_BAD_CONFIG, "hop_length must be at least 1");
+    if (p.n_mels == 0) return fail(SS_ERR_BAD_CONFIG, "n_mels must be at least 1");
+    if (p.win_length % 2) return fail(SS_ERR_BAD_CONFIG, "win_length must be even");
+    if (p.normalize != SS_NEMO_NORM_NONE && p.normalize != SS_NEMO_NORM_PER_FEATURE) return fail(SS_ERR_BAD_CONFIG, "normalize switch");
+    if (!std::isfinite(p.preemph) || p.preemph < 0.0f) return fail(SS_ERR_BAD_CONFIG, "preemph must be finite and not negative");
+    if (!std::isfinite(p.log_guard) || !(p.log_guard > 0.0f)) return fail(SS_ERR_BAD_CONFIG, "log_guard must be finite and positive");
+    if (!std::isfinite(p.norm_eps) || p.norm_eps < 0.0f) return fail(SS_ERR_BAD_CONFIG, "norm_eps must be finite and not negative");
+    if (p.sample_rate != kNemoSampleRate || p.n_fft != kNemoNfft || p.hop_length != kNemoHop)
+        return fail(SS_ERR_UNSUPPORTED, "only sample_rate 16000, n_fft 512, hop_length 160 is served");
+    if (p.n_mels > kNemoMaxMels) return fail(SS_ERR_UNSUPPORTED, "more than 128 mels");
+    if (p.win_length < 258 || p.win_length > kNemoNfft) return fail(SS_ERR_BAD_CONFIG, "win_length must lie in [258, 512]");
+    return SS_OK;
+}
+
+void nemo_window(const ss_nemo_params &p, float *w)
+{
+    const double PI = 3.14159265358979323846;
+    for (uint32_t n = 0; n < p.win_length; ++n) w[n] = static_cast<float>(0.5 - 0.5 * std::cos(2.0 * PI * n / static_cast<double>(p.win_length - 1)));
+}
+
+// librosa.filters.mel(sr = 16000, n_fft = 512, n_mels = M, fmin = 0, fmax = 8000, htk = False, norm = "slaney")
+void nemo_mel_bank(const ss_nemo_params &p, std::vector<float> &bank)
+{
+    ss_params q{};
+    q.sample_rate = p.sample_rate;
+    q.fft_points = p.n_fft;
+    q.num_filters = p.n_mels;
+    q.low_frequency = 0.0f;
+    q.high_frequency = 0.5f * static_cast<float>(p.sample_rate);
+    q.mel_scale = SS_MEL_SLANEY;
+    q.mel_norm = SS_MEL_NORM_SLANEY;
+    std::vector<int32_t> idx;
+    (void)build_filterbank(q, bank, idx);
+}
+
+void build_nemo512(const ss_nemo_params &p, NemoTables &f)
+{
+    namespace L = nemo512_layout;
+    f = NemoTables{};
+    if (nemo_validate(p) != SS_OK) return;
+    HostTables t;
+    t.params.num_filters = p.n_mels;
+    nemo_mel_bank(p, t.fb_dense);
+    sparsify(t.fb_dense, p.n_mels, kNemoBins, t.bank);
+    constexpr int32_t kRow = 260;  // P bins a tap may touch: 0..256 plus three zero pad bins
+    const std::vector<int32_t> order = sorted_deal(t, 16, L::kSlots, tap_span, f.q4);
+    f.wpitch = row_pitch(f.q4, L::kSlots, true);
+    if (f.wpitch > 320) return;
+    f.tab.assign(static_cast<size_t>(L::kMelW) + 16 * static_cast<size_t>(f.wpitch), 0.0f);
+    fill_pass_twiddles(&f.tab[L::kTw2], 16, 64, 4);
+    fill_untangle_twiddles(&f.tab[L::kTwn], 16, 8, 32, 2);
+    std::vector<float> w(p.win_length);
+    nemo_window(p, w.data());
+    copy_window(w, 512, &f.tab[L::kWin]);
+    place_slots_b32(t, L::kSlots, kRow, order, f.q4, f.wpitch, &f.tab[L::kMelW], words(f.tab, L::kStart), words(f.tab, L::kFilt));
+    f.ok = true;
+}
+
 void build_mel4096(const HostTables &t, Mfcc4096Tables &f)
 {
     build_or_stft_only(t, f, [](const HostTables &tt, Mfcc4096Tables &ff) { build_4096(tt, ff, true); });
@@ -1612,6 +1676,67 @@ int ss_whisper_work_bytes(const ss_whisper_params *p, size_t batch, size_t n_fra
         __builtin_mul_overflow(n, sizeof(float), &n))
         return ss::fail(SS_ERR_ARG, "batch * n_mels * n_frames overflows");
     *bytes = dtype == SS_PAD_F32 ? 0 : n;
+    return SS_OK;
+}
+
+// ---- NeMo / Parakeet log-mel front end: host-only calls ----
+
+int ss_nemo_params_default(ss_nemo_params *p, uint32_t n_mels)
+{
+    if (!p) return ss::fail(SS_ERR_ARG, "null params");
+    p->struct_size = static_cast<uint32_t>(sizeof(ss_nemo_params));
+    p->sample_rate = ss::kNemoSampleRate;
+    p->n_fft = ss::kNemoNfft;
+    p->win_length = 400;
+    p->hop_length = ss::kNemoHop;
+    p->n_mels = n_mels;
+    p->normalize = SS_NEMO_NORM_PER_FEATURE;
+    p->preemph = 0.97f;
+    p->log_guard = 5.9604644775390625e-8f;  // 2^-24
+    p->norm_eps = 1e-5f;
+    return SS_OK;
+}
+
+int ss_nemo_params_validate(const ss_nemo_params *p)
+{
+    if (!p) return ss::fail(SS_ERR_ARG, "null params");
+    return ss::nemo_validate(*p);
+}
+
+int ss_nemo_num_frames(const ss_nemo_params *p, size_t n_samples, size_t *n_frames)
+{
+    if (!p || !n_frames) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::nemo_validate(*p)) return rc;
+    *n_frames = n_samples / p->hop_length;
+    return SS_OK;
+}
+
+int ss_nemo_packed_frame_offsets(const ss_nemo_params *p, size_t n_clips, const int64_t *sample_offsets, int64_t *frame_offsets)
+{
+    if (!p || !sample_offsets || !frame_offsets) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::nemo_validate(*p)) return rc;
+    const int64_t hop = p->hop_length;
+    return walk_offsets(n_clips, sample_offsets, frame_offsets, "clip", [&](size_t, int64_t len, int64_t &r) -> int {
+        r = len / hop;  // (a clip shorter than one hop has no rows)
+        return SS_OK;
+    });
+}
+
+int ss_nemo_window(const ss_nemo_params *p, float *w)
+{
+    if (!p || !w) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::nemo_validate(*p)) return rc;
+    ss::nemo_window(*p, w);
+    return SS_OK;
+}
+
+int ss_nemo_mel_bank(const ss_nemo_params *p, float *bank)
+{
+    if (!p || !bank) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::nemo_validate(*p)) return rc;
+    std::vector<float> b;
+    ss::nemo_mel_bank(*p, b);
+    std::copy(b.begin(), b.end(), bank);
     return SS_OK;
 }
 

@@ -281,4 +281,31 @@ void whisper_window(float *w);                                                  
 void whisper_mel_bank(const ss_whisper_params &p, std::vector<float> &bank);   // [n_mels x 201] dense (p validated by the caller)
 void build_whisper_tables(const ss_whisper_params &p, std::vector<float> &tab); // whisper::layout
 
+// ---- NeMo / Parakeet log-mel front end (ss_nemo_* in include/speechsauce_amd.h; kernels: ss_nemo512.hip) ----
+constexpr uint32_t kNemoSampleRate = 16000, kNemoNfft = 512, kNemoHop = 160, kNemoBins = 257, kNemoMaxMels = 128;
+// rc: SS_OK, SS_ERR_ARG (struct_size), SS_ERR_BAD_CONFIG, SS_ERR_UNSUPPORTED
+int nemo_validate(const ss_nemo_params &p);
+void nemo_window(const ss_nemo_params &p, float *w);                      // [win_length] symmetric Hann, f64 rounded once
+void nemo_mel_bank(const ss_nemo_params &p, std::vector<float> &bank);   // [n_mels x 257] dense (p validated by the caller)
+
+// Table block of ss_nemo_c256, float offsets; global layout == LDS layout.  The 512-point skeleton's twiddles, the window as sample
+// pairs, and EIGHT host-sorted filter slots per lane (128 bands over 16 lanes).
+namespace nemo512_layout {
+constexpr int kSlots = 8;
+constexpr int kTw2 = 0;                  // [8][16] float4: (W^(j(2p+1)), W^(j(2p+2))), W = exp(-2 pi i / 256); last .zw unused
+constexpr int kTwn = kTw2 + 8 * 64;      // [8][16] float2: exp(-2 pi i (j + 16 r) / 512)
+constexpr int kWin = kTwn + 8 * 32;      // [256] float2: window pairs (w[2n], w[2n+1]), zero beyond win_length
+constexpr int kStart = kWin + 512;       // [8][16] int32: first P bin of the filter owned by (slot, lane)
+constexpr int kFilt = kStart + 128;      // [8][16] int32: filter index of (slot, lane), -1 if none
+constexpr int kMelW = kFilt + 128;       // [16][pitch]
+}  // namespace nemo512_layout
+
+struct NemoTables {
+    bool ok = false;
+    std::vector<float> tab;
+    int32_t q4[nemo512_layout::kSlots] = {0, 0, 0, 0, 0, 0, 0, 0};  // taps / 4 per slot
+    int32_t wpitch = 0;
+};
+void build_nemo512(const ss_nemo_params &p, NemoTables &f);
+
 }  // namespace ss

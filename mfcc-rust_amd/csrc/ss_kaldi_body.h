@@ -56,23 +56,7 @@ __device__ __forceinline__ KClip kaldi_clip(const KaldiVarlenArgs &v, uint32_t f
 // The source kinds of the body
 enum KSrc : int { kDense = 0, kVarlen = 1, kPool = 2, kPoolPcm = 3, kDensePcm = 4, kVarlenPcm = 5 };
 
-// The owner (clip of a packed launch, entry of a pool launch) of row g = q4 + 0..3 over the row offsets `off`: the owner of the
-// quad's first row from the wave's forward cursor (claims only increase), then at most three owners WITH rows further on.
-__device__ __forceinline__ unsigned row_owner(const long long *off, unsigned n, unsigned q4, unsigned g, unsigned &cursor)
-{
-    unsigned c = offset_seek(off, n, cursor, q4);
-    cursor = c;
-    bool step = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        step = c + 1 < n && off[c + 1] <= static_cast<long long>(g);
-        c += step ? 1u : 0u;
-    }
-    // owners without rows inside the quad (off[b] == off[b + 1]) take steps of their own: a lane that took all three looks once
-    // more, and searches where they did not get there
-    if (step && c + 1 < n && off[c + 1] <= static_cast<long long>(g)) c = offset_find(off, n, static_cast<long long>(g));
-    return c;
-}
+// (row_owner, the owner of a quad's row over a packed launch's or a pool launch's row offsets: ss_device.h, next to offset_seek)
 
 // Where this lane group's frame starts and whether it exists.  Dense: lanes past the last frame redo it.  VARLEN: `cursor` is the
 // wave's clip of its last quad's first row (claims only increase); a lane's frame lies at most three clips WITH rows further on.

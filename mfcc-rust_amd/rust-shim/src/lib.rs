@@ -292,6 +292,18 @@ extern "C" {
                                         dtype: c_int, d_work: *mut c_void, d_out: *mut c_void, d_lengths: *mut i32, stream: *mut c_void) -> c_int;
     fn ss_whisper_log_mel_packed(cfg: *const c_void, x: *const f32, n_clips: usize, sample_offsets: *const i64, n_frames: usize, dtype: c_int,
                                  out: *mut c_void, lengths: *mut i32) -> c_int;
+    fn ss_nemo_params_default(p: *mut SsNemoParams, n_mels: u32) -> c_int;
+    fn ss_nemo_num_frames(p: *const SsNemoParams, n_samples: usize, n_frames: *mut usize) -> c_int;
+    fn ss_nemo_packed_frame_offsets(p: *const SsNemoParams, n_clips: usize, sample_offsets: *const i64, frame_offsets: *mut i64) -> c_int;
+    fn ss_nemo_config_create(p: *const SsNemoParams, out: *mut *mut c_void) -> c_int;
+    fn ss_nemo_config_destroy(cfg: *mut c_void);
+    fn ss_nemo_config_device_status(cfg: *const c_void) -> c_int;
+    fn ss_nemo_log_mel_device(cfg: *const c_void, d_x: *const f32, batch: usize, n_samples: usize, ld: usize, d_out: *mut f32,
+                              stream: *mut c_void) -> c_int;
+    fn ss_nemo_log_mel(cfg: *const c_void, x: *const f32, batch: usize, n_samples: usize, ld: usize, out: *mut f32) -> c_int;
+    fn ss_nemo_log_mel_packed_device(cfg: *const c_void, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64,
+                                     d_frame_offsets: *const i64, total_frames: usize, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_nemo_log_mel_packed(cfg: *const c_void, x: *const f32, n_clips: usize, sample_offsets: *const i64, out: *mut f32) -> c_int;
     fn ss_derivative_extraction(feat: *const f32, rows: usize, cols: usize, delta_windows: usize, out: *mut f32) -> c_int;
     fn ss_extract_derivative_feature(feat: *const f32, rows: usize, cols: usize, cube: *mut f32) -> c_int;
     fn ss_shard_bounds(n_items: usize, world: c_int, rank: c_int, lo: *mut usize, hi: *mut usize) -> c_int;
@@ -2161,6 +2173,109 @@ impl WhisperFrontEnd {
     pub unsafe fn log_mel_packed_device(&self, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, n_frames: usize, dtype: c_int,
                                         d_work: *mut c_void, d_out: *mut c_void, d_lengths: *mut i32, stream: *mut c_void) -> Result<(), Error> {
         check(ss_whisper_log_mel_packed_device(self.raw, d_x, n_clips, d_sample_offsets, n_frames, dtype, d_work, d_out, d_lengths, stream))
+    }
+}
+
+/// `ss_nemo_params`: the NeMo / Parakeet log-mel front end's parameters (field order is ABI; see `ss_nemo_*` in the C header).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SsNemoParams {
+    pub struct_size: u32,
+    pub sample_rate: u32,
+    pub n_fft: u32,
+    pub win_length: u32,
+    pub hop_length: u32,
+    pub n_mels: u32,
+    pub normalize: i32,
+    pub preemph: f32,
+    pub log_guard: f32,
+    pub norm_eps: f32,
+}
+
+pub const SS_NEMO_NORM_NONE: i32 = 0;
+pub const SS_NEMO_NORM_PER_FEATURE: i32 = 1;
+
+impl SsNemoParams {
+    /// 16000 / 512 / 400 / 160 with `n_mels` mels (80 or 128), pre-emphasis 0.97, per-feature normalisation.
+    pub fn new(n_mels: u32) -> SsNemoParams {
+        let mut p: SsNemoParams = unsafe { std::mem::zeroed() };
+        unsafe { ss_nemo_params_default(&mut p, n_mels) };
+        p
+    }
+}
+
+/// The NeMo / Parakeet log-mel rows (`[len / 160 x n_mels]` per clip; NeMo's `AudioToMelSpectrogramPreprocessor`).  Not in the
+/// reference crate.  Owns an `ss_nemo_config`.
+pub struct NemoFrontEnd {
+    raw: *mut c_void,
+    params: SsNemoParams,
+}
+
+unsafe impl Send for NemoFrontEnd {}
+
+impl Drop for NemoFrontEnd {
+    fn drop(&mut self) {
+        unsafe { ss_nemo_config_destroy(self.raw) }
+    }
+}
+
+impl NemoFrontEnd {
+    pub fn new(params: SsNemoParams) -> Result<NemoFrontEnd, Error> {
+        let mut raw: *mut c_void = std::ptr::null_mut();
+        check(unsafe { ss_nemo_config_create(&params, &mut raw) })?;
+        Ok(NemoFrontEnd { raw, params })
+    }
+
+    pub fn n_mels(&self) -> usize {
+        self.params.n_mels as usize
+    }
+
+    /// `n_samples / 160`: the rows kept of a clip (0 for a clip shorter than one hop).
+    pub fn num_frames(&self, n_samples: usize) -> Result<usize, Error> {
+        let mut t = 0usize;
+        check(unsafe { ss_nemo_num_frames(&self.params, n_samples, &mut t) })?;
+        Ok(t)
+    }
+
+    /// `SS_ERR_DEVICE` once if a packed launch has skipped an inconsistent clip since the last look.
+    pub fn device_status(&self) -> Result<(), Error> {
+        check(unsafe { ss_nemo_config_device_status(self.raw) })
+    }
+
+    /// One clip -> `[len / 160 x n_mels]`.
+    pub fn log_mel(&self, x: &[f32]) -> Result<Array2<f32>, Error> {
+        let mut out = Array2::<f32>::zeros((self.num_frames(x.len())?, self.n_mels()));
+        if !out.is_empty() {
+            check(unsafe { ss_nemo_log_mel(self.raw, x.as_ptr(), 1, x.len(), x.len(), out.as_mut_ptr()) })?;
+        }
+        Ok(out)
+    }
+
+    /// Clips packed end to end -> (the rows `[sum T_b x n_mels]`, the `[n_clips + 1]` frame offsets).
+    pub fn log_mel_packed(&self, x: &[f32], sample_offsets: &[i64]) -> Result<(Array2<f32>, Vec<i64>), Error> {
+        if sample_offsets.is_empty() || sample_offsets[sample_offsets.len() - 1] as usize > x.len() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets is empty or ends past the block".to_string() });
+        }
+        let n = sample_offsets.len() - 1;
+        let mut fo = vec![0i64; n + 1];
+        check(unsafe { ss_nemo_packed_frame_offsets(&self.params, n, sample_offsets.as_ptr(), fo.as_mut_ptr()) })?;
+        let mut out = Array2::<f32>::zeros((fo[n] as usize, self.n_mels()));
+        if !out.is_empty() {
+            check(unsafe { ss_nemo_log_mel_packed(self.raw, x.as_ptr(), n, sample_offsets.as_ptr(), out.as_mut_ptr()) })?;
+        }
+        Ok((out, fo))
+    }
+
+    /// The dense device call on `stream`: device pointers, nothing is copied or allocated (`ss_nemo_log_mel_device`).
+    pub unsafe fn log_mel_device(&self, d_x: *const f32, batch: usize, n_samples: usize, ld: usize, d_out: *mut f32,
+                                 stream: *mut c_void) -> Result<(), Error> {
+        check(ss_nemo_log_mel_device(self.raw, d_x, batch, n_samples, ld, d_out, stream))
+    }
+
+    /// The packed device call on `stream` (`ss_nemo_log_mel_packed_device`): replays as a captured graph over changed tables.
+    pub unsafe fn log_mel_packed_device(&self, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, d_frame_offsets: *const i64,
+                                        total_frames: usize, d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+        check(ss_nemo_log_mel_packed_device(self.raw, d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, stream))
     }
 }
 

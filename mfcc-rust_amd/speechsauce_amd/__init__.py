@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import SpeechSauceError, SsKaldiParams, SsParams, SsResampleInfo, SsWhisperParams, make_params  # noqa: F401
+from ._lib import SpeechSauceError, SsKaldiParams, SsNemoParams, SsParams, SsResampleInfo, SsWhisperParams, make_params  # noqa: F401
 
 __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivative_extraction", "extract_derivative_feature",
            "mfe", "mfcc_batch", "mfe_batch", "lmfe", "lmfe_batch", "power_to_db", "stft", "stack_frames", "power_spectrum",
@@ -37,6 +37,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "KaldiFbankStreamPool", "KaldiMfccStreamPool",
            "whisper_log_mel", "whisper_log_mel_packed", "whisper_log_mel_list", "whisper_num_frames", "WhisperConfig",
+           "nemo_log_mel", "nemo_log_mel_packed", "nemo_log_mel_list", "nemo_num_frames", "NemoConfig",
            "SpeechConfig", "SpeechSauceError"]
 
 
@@ -3571,3 +3572,167 @@ def whisper_log_mel_list(signals, n_mels=80, n_frames=None, dtype="float32", *, 
     else:
         packed = np.concatenate(sigs)
     return whisper_log_mel_packed(packed, [int(x.shape[0]) for x in sigs], n_mels=n_mels, n_frames=n_frames, dtype=dtype, pcm_scale=pcm_scale)
+
+
+# ---- NeMo / Parakeet log-mel front end (ss_nemo_* in include/speechsauce_amd.h) ---------------------------------------
+
+class NemoConfig(_Handle):
+    """Owns an ``ss_nemo_config`` handle: the validated ``ss_nemo_params``, the kernel's tables on the device that was current at
+    creation and a device error word for the packed calls."""
+
+    _destroy = "ss_nemo_config_destroy"
+
+    def __init__(self, params: SsNemoParams):
+        super().__init__()
+        self.params = params
+        _lib.check(self._owner.ss_nemo_config_create(C.byref(params), C.byref(self._h)))
+
+    def device_status(self) -> None:
+        """Raises SpeechSauceError (SS_ERR_DEVICE) if a packed launch on this handle has skipped an inconsistent clip since the last
+        look.  Meaningful after the stream has been synchronised."""
+        _lib.check(_lib.lib().ss_nemo_config_device_status(self._h))
+
+
+def _nemo_params(n_mels, normalize, win_length, preemph, log_guard, norm_eps) -> SsNemoParams:
+    if normalize not in _lib.NEMO_NORMALIZE:
+        raise ValueError(f"normalize must be 'per_feature' or None ('all_features' is not offered), got {normalize!r}")
+    p = SsNemoParams()
+    _lib.check(_lib.lib().ss_nemo_params_default(C.byref(p), int(n_mels)))
+    p.win_length, p.normalize = int(win_length), _lib.NEMO_NORMALIZE[normalize]
+    p.preemph, p.log_guard, p.norm_eps = float(preemph), float(log_guard), float(norm_eps)
+    return p
+
+
+@lru_cache(maxsize=16)
+def _get_nemo_config(key: tuple, device: int = -1) -> NemoConfig:
+    """Memoised handle factory, keyed like ``_get_kaldi_config``: the parameters and the device the tables live on."""
+    return NemoConfig(_nemo_params(*key))
+
+
+_lib._on_switch.append(_get_nemo_config.cache_clear)
+
+
+def _nemo_cfg(sig, n_mels, normalize, win_length, preemph, log_guard, norm_eps) -> NemoConfig:
+    key = (int(n_mels), normalize, int(win_length), float(preemph), float(log_guard), float(norm_eps))
+    return _get_nemo_config(key, _device_key(sig))
+
+
+def nemo_num_frames(n_samples: int) -> int:
+    """``n_samples // 160``: the rows the NeMo front end keeps of a clip (the extractor's ``features_lengths``; no device needed)."""
+    p, t = SsNemoParams(), C.c_size_t()
+    _lib.check(_lib.lib().ss_nemo_params_default(C.byref(p), 80))
+    _lib.check(_lib.lib().ss_nemo_num_frames(C.byref(p), int(n_samples), C.byref(t)))
+    return t.value
+
+
+def nemo_log_mel(x, n_mels=80, normalize="per_feature", win_length=400, preemph=0.97, log_guard=2.0 ** -24, norm_eps=1e-5):
+    """The NeMo / Parakeet log-mel rows (NeMo's ``AudioToMelSpectrogramPreprocessor``, ``transformers.ParakeetFeatureExtractor``) of
+    one 16 kHz float32 clip [L] -> [L // 160, n_mels] or of every row of a batch [B, L] -> [B, L // 160, n_mels]: whole-clip
+    pre-emphasis, a ``win_length`` symmetric Hann window centred in 512-point frames at a 160-sample hop with zero padding, the power
+    spectrum, ``n_mels`` (up to 128) Slaney mels, ``ln(. + log_guard)`` and -- ``normalize="per_feature"`` -- each band's mean and
+    standard deviation (ddof = 1) over the clip's own rows taken out; ``normalize=None`` returns the log-mel rows.  numpy in -> the
+    host-pointer call; a ROCm tensor stays on the device (current stream: one launch, two with the normalisation)."""
+    what = "nemo_log_mel"
+    sig = _require_f32(x, (1, 2), what)
+    cfg = _nemo_cfg(sig, n_mels, normalize, win_length, preemph, log_guard, norm_eps)
+    lib = _lib.lib()
+    one = len(sig.shape) == 1
+    batch, L = (1, int(sig.shape[0])) if one else (int(sig.shape[0]), int(sig.shape[1]))
+    T, M = nemo_num_frames(L), cfg.params.n_mels
+    if _is_torch(sig):
+        import torch
+
+        v = sig.reshape(1, L) if one else sig
+        if L and v.stride(1) != 1:
+            v = v.contiguous()
+        ld = int(v.stride(0)) if batch > 1 and L else L
+        if ld < L:
+            v, ld = v.contiguous(), L
+        out = torch.empty((batch, T, M), dtype=torch.float32, device=v.device)
+        if batch and T:
+            _launch(v.device, lib.ss_nemo_log_mel_device, cfg.handle, v, batch, L, ld, out.data_ptr())
+        return out[0] if one else out
+    v = np.ascontiguousarray(sig).reshape(batch, L)
+    out = np.empty((batch, T, M), dtype=np.float32)
+    if batch and T:
+        _lib.check(lib.ss_nemo_log_mel(cfg.handle, v.ctypes.data, batch, L, L, out.ctypes.data))
+    return out[0] if one else out
+
+
+def nemo_log_mel_packed(signal, lengths, n_mels=80, normalize="per_feature", win_length=400, preemph=0.97, log_guard=2.0 ** -24,
+                        norm_eps=1e-5, *, device_tables=None):
+    """``nemo_log_mel`` of clips of different lengths packed end to end in one 1-D float32 signal -> (rows [sum T_b, n_mels],
+    frame_offsets [n + 1] int64 on the host): clip b's rows are frame_offsets[b] : frame_offsets[b + 1], bit for bit what
+    ``nemo_log_mel`` returns for that clip alone; a clip of fewer than 160 samples has none.  One call for all clips.  ``(out,
+    out_lengths)`` of ``resample_packed`` are valid ``(signal, lengths)`` as they stand, and ``(rows, frame_offsets)`` go on to
+    ``spec_augment_packed`` / ``pad_packed``.  ``device_tables=(sample_offsets, frame_offsets, total_frames)`` (with
+    ``lengths=None``; int64 device tensors of n + 1 entries): the tables are used as they stand and nothing is read back or
+    uploaded, so the call can be captured in a graph and replayed over changed tables -- the kernels skip a clip whose entries are
+    inconsistent and ``NemoConfig.device_status()`` reports it; ``frame_offsets`` is then returned as it was given."""
+    what = "nemo_log_mel_packed"
+    sig = _require_f32(signal, (1,), what)
+    if device_tables is not None and (lengths is not None or not (_is_torch(sig) and sig.is_cuda)):
+        raise ValueError(f"{what}: device_tables go with lengths=None and a device signal")
+    so = None if device_tables is not None else _sample_offsets(lengths, int(sig.shape[0]), what)
+    cfg = _nemo_cfg(sig, n_mels, normalize, win_length, preemph, log_guard, norm_eps)
+    lib, M = _lib.lib(), cfg.params.n_mels
+    if device_tables is not None:
+        import torch
+
+        dso, dfo, rows = device_tables
+        for t in (dso, dfo):
+            if not (_is_torch(t) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous() and t.device == sig.device):
+                raise TypeError(f"{what}: device_tables must be contiguous 1-D int64 tensors on the signal's device")
+        if dso.numel() != dfo.numel() or dso.numel() < 1:
+            raise ValueError(f"{what}: device_tables must both hold n_clips + 1 entries")
+        n, rows = dso.numel() - 1, int(rows)
+        x = sig.contiguous()
+        out = torch.empty((rows, M), dtype=torch.float32, device=x.device)
+        if n and rows:
+            _launch(x.device, lib.ss_nemo_log_mel_packed_device, cfg.handle, x, n, dso, dfo, rows, out.data_ptr())
+        return out, dfo
+    n = so.size - 1
+    fo = np.empty_like(so)
+    _lib.check(lib.ss_nemo_packed_frame_offsets(C.byref(cfg.params), n, so.ctypes.data, fo.ctypes.data))
+    rows = int(fo[-1])
+    if _is_torch(sig):
+        import torch
+
+        x = sig.contiguous()
+        out = torch.empty((rows, M), dtype=torch.float32, device=x.device)
+        if n and rows:
+            _launch(x.device, lib.ss_nemo_log_mel_packed_device, cfg.handle, x, n, so, fo, rows, out.data_ptr())
+        return out, fo
+    x = np.ascontiguousarray(sig)
+    out = np.empty((rows, M), dtype=np.float32)
+    if n and rows:
+        _lib.check(lib.ss_nemo_log_mel_packed(cfg.handle, x.ctypes.data, n, so.ctypes.data, out.ctypes.data))
+    return out, fo
+
+
+def nemo_log_mel_list(signals, n_mels=80, normalize="per_feature", win_length=400, preemph=0.97, log_guard=2.0 ** -24, norm_eps=1e-5, *,
+                      padded=False, layout="btc", dtype="float32", pad_value=0.0):
+    """A list of 1-D float32 clips of any lengths -> the list of their ``nemo_log_mel`` rows (views of one block): the clips are
+    packed once and served by one ``nemo_log_mel_packed`` call.  ``padded=True`` chains ``pad_packed`` and returns the model input
+    ``(out, lengths)`` instead: ``[n, T_max, n_mels]`` (``layout="btc"``, the ``transformers`` models) or ``[n, n_mels, T_max]``
+    (``"bct"``, NeMo's own) in ``dtype``."""
+    what = "nemo_log_mel_list"
+    sigs = [_require_f32(x, (1,), what) for x in signals]
+    if not sigs:
+        raise ValueError(f"{what}: no clips")
+    on_device = [_is_torch(x) for x in sigs]
+    if any(on_device) and not all(on_device):
+        raise ValueError(f"{what}: the clips of one call must all be device tensors or all host arrays")
+    if all(on_device):
+        import torch
+
+        if any(x.device != sigs[0].device for x in sigs):
+            raise ValueError(f"{what}: the clips of one call must live on one device")
+        packed = torch.cat(sigs)
+    else:
+        packed = np.concatenate(sigs)
+    rows, fo = nemo_log_mel_packed(packed, [int(x.shape[0]) for x in sigs], n_mels, normalize, win_length, preemph, log_guard, norm_eps)
+    if padded:
+        return pad_packed(rows, fo, None, layout, dtype, pad_value)
+    fo = fo.tolist()
+    return [rows[fo[b]:fo[b + 1]] for b in range(len(sigs))]

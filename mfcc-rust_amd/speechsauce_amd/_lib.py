@@ -95,6 +95,20 @@ class SsWhisperParams(C.Structure):
     _fields_ = [(name, C.c_uint32) for name in ("struct_size", "sample_rate", "n_fft", "hop_length", "n_mels")]
 
 
+NEMO_NORMALIZE = {None: 0, "none": 0, "per_feature": 1}
+
+
+class SsNemoParams(C.Structure):
+    """ss_nemo_params (include/speechsauce_amd.h); field order is ABI."""
+
+    _fields_ = [(name, C.c_uint32) for name in ("struct_size", "sample_rate", "n_fft", "win_length", "hop_length", "n_mels")] + [
+        ("normalize", C.c_int32),
+        ("preemph", C.c_float),
+        ("log_guard", C.c_float),
+        ("norm_eps", C.c_float),
+    ]
+
+
 class SpeechSauceError(RuntimeError):
     """Raised where the reference would panic (or where HIP fails)."""
 
@@ -113,6 +127,7 @@ _rs = C.c_void_p  # ss_resampler *
 _af = C.c_void_p  # ss_affine *
 _kc = C.c_void_p  # ss_kaldi_config *
 _wc = C.c_void_p  # ss_whisper_config *
+_nc = C.c_void_p  # ss_nemo_config *
 _fp = C.c_void_p  # float* passed as an address (numpy .ctypes.data or a device pointer)
 PROTOTYPES = {
     "ss_params_default": (C.c_int, [_P(SsParams), C.c_uint32]),
@@ -384,6 +399,20 @@ PROTOTYPES = {
     "ss_whisper_log_mel_packed_i16_device": (
         C.c_int, [_wc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ss_whisper_log_mel_packed_i16": (C.c_int, [_wc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "ss_nemo_params_default": (C.c_int, [_P(SsNemoParams), C.c_uint32]),
+    "ss_nemo_params_validate": (C.c_int, [_P(SsNemoParams)]),
+    "ss_nemo_num_frames": (C.c_int, [_P(SsNemoParams), C.c_size_t, _P(C.c_size_t)]),
+    "ss_nemo_packed_frame_offsets": (C.c_int, [_P(SsNemoParams), C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ss_nemo_window": (C.c_int, [_P(SsNemoParams), _fp]),
+    "ss_nemo_mel_bank": (C.c_int, [_P(SsNemoParams), _fp]),
+    "ss_nemo_config_create": (C.c_int, [_P(SsNemoParams), _P(_nc)]),
+    "ss_nemo_config_destroy": (None, [_nc]),
+    "ss_nemo_config_params": (C.c_int, [_nc, _P(SsNemoParams)]),
+    "ss_nemo_config_device_status": (C.c_int, [_nc]),
+    "ss_nemo_log_mel_device": (C.c_int, [_nc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp, C.c_void_p]),
+    "ss_nemo_log_mel": (C.c_int, [_nc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp]),
+    "ss_nemo_log_mel_packed_device": (C.c_int, [_nc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
+    "ss_nemo_log_mel_packed": (C.c_int, [_nc, _fp, C.c_size_t, C.c_void_p, _fp]),
     "ss_kstream_state_len": (C.c_int, [_P(SsKaldiParams), _P(C.c_size_t), _P(C.c_size_t)]),
     "ss_kstream_row_offsets": (C.c_int, [_P(SsKaldiParams), C.c_size_t, C.c_void_p, C.c_void_p]),
     "ss_kstream_fbank_packed_device": (
