@@ -1721,7 +1721,8 @@ int ss_whisper_log_mel_packed_i16(const ss_whisper_config *cfg, const int16_t *x
  *   depend on the row count, n_clips and n_mels; nothing is allocated or read back inside a call, so the calls replay as a captured
  *   graph over changed device tables.
  * The host forms stage through the device; the packed one refuses a bad sample table (SS_ERR_ARG) before any launch.
- * Not served: 16-bit PCM twins, stream-pool forms, dither, other n_fft / hop_length / sample rates, normalize = "all_features",
+ * Stream pools, fed floats or 16-bit PCM: the ss_nstream_* section below.
+ * Not served: 16-bit PCM twins of these one-shot calls, dither, other n_fft / hop_length / sample rates, normalize = "all_features",
  *   narrow-band fmin / fmax, NaN for T = 1. */
 #define SS_NEMO_NORM_NONE 0
 #define SS_NEMO_NORM_PER_FEATURE 1
@@ -1757,6 +1758,68 @@ int ss_nemo_log_mel(const ss_nemo_config *cfg, const float *x, size_t batch, siz
 int ss_nemo_log_mel_packed_device(const ss_nemo_config *cfg, const float *d_x, size_t n_clips, const int64_t *d_sample_offsets,
                                   const int64_t *d_frame_offsets, size_t total_frames, float *d_out, void *stream);
 int ss_nemo_log_mel_packed(const ss_nemo_config *cfg, const float *x, size_t n_clips, const int64_t *sample_offsets, float *out);
+
+/* ---- ss_nstream_*: the NeMo / Parakeet front end over a pool of stream states (live audio) -------------------------
+ * The online form of ss_nemo_log_mel with normalize = SS_NEMO_NORM_NONE -- the input of cache-aware FastConformer and the real-time
+ * Parakeet models -- on the tables of the other stream pools (ss_resample_stream_packed*, ss_kstream_*, ss_cmvn_stream_packed*,
+ * ss_splice_stream_packed*): one set of sample_offsets / row_offsets / slots serves the whole chain.  The handle is
+ * an ss_nemo_config; the arithmetic is steps 2 - 6 of the ss_nemo_* specification above, on the same kernel body.  (The prefix is
+ * ss_nstream_, not ss_nemo_: the set of ss_nemo_* names is closed.)
+ * Sizes, with W = win_length and H = 160: L = ceil(W / 320) - 1 is the delay in rows (0 for W <= 320, else 1) -- a centred frame
+ *   reaches W / 2 samples past its hop -- and S = L * 160 + W / 2 + 1 the carried samples per stream: the frame's reach plus the one
+ *   pre-emphasis predecessor (ss_nstream_state_len, which reads the sizes only; W = 400: L = 1, S = 361; W = 320: L = 0, S = 161;
+ *   W = 512: L = 1, S = 417).
+ * Pool: a caller-owned [pool_streams x S] block of floats.  An all-zero row is a fresh stream; zeroing a row resets it.
+ * Entries (the rules of ss_kstream_*): a call serves n_active entries.  Entry i's chunk is x[so[i] : so[i+1]], R_i = n_i / 160 whole
+ *   hops (R_i = 0 is legal); its state is pool row slots[i]; its rows are rows ro[i] .. ro[i+1] of the packed [total_rows x n_mels]
+ *   float32 output (ss_nstream_row_offsets); total_rows >= ro[n_active], rows past ro[n_active] are left alone.  Row t of an entry is
+ *   steps 2 - 6 on ONE frame: its first live sample is chunk position p0 = 160 (t - L) - W / 2, a position p < 0 being
+ *   pool[slot * S + S + p]; the pre-emphasis predecessor of the first sample is position p0 - 1.  Every position a row reads lies in
+ *   [-S, 160 (t + 1)); nothing is masked.  Afterwards the pool row is the last S samples of (old row ++ chunk).
+ * Flush (ss_nstream_flush*): takes no samples.  Entry i gets exactly L rows, out[i * L .. (i + 1) * L) of [n_active * L x n_mels]: row
+ *   u is the frame that starts at position 160 (u - L) - W / 2 relative to the stream's end, every position at or beyond the end being
+ *   zero AFTER the pre-emphasis (step 2's masked fill).  Afterwards the named pool rows are all zeros (as ss_resample_stream_flush*
+ *   leaves them): the slot is a fresh stream.  With L = 0 nothing is written (d_out may be NULL) and the rows are zeroed all the same.
+ * Equivalence: however a stream of K whole hops was cut into calls -- empty entries included, float and PCM calls mixed, whatever
+ *   else shares the call and whatever the entry's place or slot -- its K pool rows are bit for bit rows 0 .. K - 1 of
+ *   ss_nemo_log_mel_device (a SS_NEMO_NORM_NONE handle) on zeros(L * 160) ++ stream, and the pool rows with the first L dropped,
+ *   followed by the flush rows, are bit for bit ss_nemo_log_mel_device on the stream itself (K rows).  THE FIRST L ROWS AFTER A RESET
+ *   ARE WARM-UP ROWS over the zero prefix.  A trailing partial hop is the caller's to drop (or to keep for the next call): neither
+ *   call takes one.
+ * A handle with SS_NEMO_NORM_PER_FEATURE is SS_ERR_UNSUPPORTED on every call that takes a handle: a stream has no clip statistics.
+ *   ss_cmvn_stream_packed* or ss_cmvn_apply_packed* chains behind the pool instead.
+ * Containment: the skip rules are the frame pool's.  A bad entry (not whole hops, ro inconsistent, ro[i+1] > total_rows, slot outside
+ *   the pool; for the flush: slot outside the pool) is skipped by every launch -- its rows and its pool row stay untouched -- and
+ *   raises the handle's error word: SS_ERR_DEVICE once, through ss_nemo_config_device_status or the next call on the handle.
+ *   Nothing is read outside the entries' chunk ranges and the named pool rows; nothing is written outside rows [0, total_rows) and
+ *   the named pool rows.
+ * Arguments: n_active == 0 is SS_OK with no launch.  SS_ERR_ARG, with nothing touched, for null buffers, sizes >= 2^31 and a pool
+ *   range that overlaps an output.  The host forms check the tables first and name the first bad entry (ss_nstream_row_offsets'
+ *   rules: so[0] == 0, no decreasing pair, whole hops), reject duplicate slots, and write the caller's pool only after everything
+ *   else succeeded.
+ * _i16 forms: sample = (float)pcm * scale, scale a power of two in [2^-64, 2^64] (else SS_ERR_ARG).  The results are bit for bit
+ *   the float call on the converted samples; the pool stays float, so a stream may alternate between PCM and float chunks.  The
+ *   device forms need 2-byte alignment of d_x only (W / 2 may be odd: a frame starts at either parity).
+ * The pool call is a linear chain of two launches on `stream` -- ss_nemo_c256<NE,sp> (,spi> for PCM; ss_last_kernel_name()) and the
+ *   frame pool's state advance; the flush is ss_nemo_c256<NE,fl> (no launch where L = 0) and the zeroing of the named rows.  The grids
+ *   depend on n_active and total_rows only; nothing is allocated or read back: capturable, and replayable over changed table contents.
+ * Not served: a partial-hop tail in the flush, per-feature normalisation inside the pool, dither, 16-bit PCM twins of the one-shot
+ *   ss_nemo_* calls. */
+int ss_nstream_state_len(const ss_nemo_params *p, size_t *state_len, size_t *delay_rows); /* host only */
+int ss_nstream_row_offsets(const ss_nemo_params *p, size_t n_active, const int64_t *sample_offsets, int64_t *row_offsets); /* host only */
+int ss_nstream_log_mel_packed_device(const ss_nemo_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                     const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float *d_pool,
+                                     float *d_out, void *stream);
+int ss_nstream_log_mel_packed(const ss_nemo_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                              size_t pool_streams, float *pool, float *out);
+int ss_nstream_log_mel_packed_i16_device(const ss_nemo_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                         const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float scale,
+                                         float *d_pool, float *d_out, void *stream);
+int ss_nstream_log_mel_packed_i16(const ss_nemo_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets,
+                                  const int32_t *slots, size_t pool_streams, float scale, float *pool, float *out);
+int ss_nstream_flush_device(const ss_nemo_config *cfg, size_t n_active, const int32_t *d_slots, size_t pool_streams, float *d_pool, float *d_out,
+                            void *stream);
+int ss_nstream_flush(const ss_nemo_config *cfg, size_t n_active, const int32_t *slots, size_t pool_streams, float *pool, float *out);
 
 /* ---- multi-GPU callers below Python (one process or thread per GPU) -------------------------------------
  * Clips are independent, so a batch shards by contiguous blocks with no exchange inside the path: rank r of `world`

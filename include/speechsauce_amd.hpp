@@ -1190,7 +1190,62 @@ public:
         check(ss_nemo_log_mel_packed_device(h_.get(), d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, stream));
     }
 
+    // The stream pool (ss_nstream_*; a handle with normalize none): S = the floats of a pool row, L = the warm-up rows after a reset
+    // and the rows a flush returns per stream.
+    size_t stream_state_len(size_t *delay_rows = nullptr) const
+    {
+        size_t S = 0, L = 0;
+        check(ss_nstream_state_len(&p_, &S, &L));
+        if (delay_rows) *delay_rows = L;
+        return S;
+    }
+    // Entry i is the chunk x[sample_offsets[i] .. sample_offsets[i+1]) (whole 160-sample hops, floats or 16-bit PCM times the
+    // power-of-two `scale`) of the stream whose state is row slots[i] of pool [pool_streams x S] (all-zero rows: fresh streams) -> the
+    // packed rows; row_offsets receives the entries' row offsets.  The first L rows of a fresh stream are warm-up rows.
+    std::vector<float> log_mel_stream_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, const std::vector<int32_t> &slots,
+                                             std::vector<float> &pool, std::vector<int64_t> &row_offsets) const
+    {
+        std::vector<float> out(stream_rows(x.size(), sample_offsets, slots, row_offsets) * p_.n_mels);
+        check(ss_nstream_log_mel_packed(h_.get(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_rows(pool), pool.data(),
+                                        out.data()));
+        return out;
+    }
+    std::vector<float> log_mel_stream_packed_i16(const std::vector<int16_t> &x, const std::vector<int64_t> &sample_offsets,
+                                                 const std::vector<int32_t> &slots, float scale, std::vector<float> &pool,
+                                                 std::vector<int64_t> &row_offsets) const
+    {
+        std::vector<float> out(stream_rows(x.size(), sample_offsets, slots, row_offsets) * p_.n_mels);
+        check(ss_nstream_log_mel_packed_i16(h_.get(), x.data(), slots.size(), sample_offsets.data(), slots.data(), pool_rows(pool), scale,
+                                            pool.data(), out.data()));
+        return out;
+    }
+    // the end of the named streams -> [slots.size() * L x n_mels], stream i's last L rows at rows i * L ..; the named pool rows are zero
+    // (fresh streams) afterwards
+    std::vector<float> stream_flush(const std::vector<int32_t> &slots, std::vector<float> &pool) const
+    {
+        size_t L = 0;
+        stream_state_len(&L);
+        std::vector<float> out(slots.size() * L * p_.n_mels);
+        check(ss_nstream_flush(h_.get(), slots.size(), slots.data(), pool_rows(pool), pool.data(), out.data()));
+        return out;
+    }
+
 private:
+    size_t stream_rows(size_t n_samples, const std::vector<int64_t> &sample_offsets, const std::vector<int32_t> &slots,
+                       std::vector<int64_t> &row_offsets) const
+    {
+        if (sample_offsets.size() != slots.size() + 1 || sample_offsets.back() < 0 || static_cast<size_t>(sample_offsets.back()) > n_samples)
+            throw Error(SS_ERR_ARG, "nemo pool call: shape mismatch");
+        row_offsets.assign(sample_offsets.size(), 0);
+        check(ss_nstream_row_offsets(&p_, slots.size(), sample_offsets.data(), row_offsets.data()));
+        return static_cast<size_t>(row_offsets.back());
+    }
+    size_t pool_rows(const std::vector<float> &pool) const
+    {
+        const size_t S = stream_state_len();
+        if (pool.empty() || pool.size() % S) throw Error(SS_ERR_ARG, "nemo pool call: the pool is not a whole number of rows");
+        return pool.size() / S;
+    }
     ss_nemo_params p_;
     std::shared_ptr<ss_nemo_config> h_;
 };

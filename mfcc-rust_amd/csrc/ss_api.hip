@@ -3773,6 +3773,163 @@ int nemo_packed_device(const ss_nemo_config *cfg, const float *d_x, size_t n_cli
     return nemo_launch(cfg, a, &v, stream);
 }
 
+// ---- ss_nstream_*: the same front end over a pool of stream states (kernels: ss_nemo512_pool.hip) ----
+// what every ss_nstream_* call on a handle checks first; S and L are the handle's pool sizes
+int nstream_check_call(const ss_nemo_config *cfg, size_t &S, size_t &L)
+{
+    if (!cfg) return ss::fail(SS_ERR_ARG, "null handle");
+    if (cfg->params.normalize != SS_NEMO_NORM_NONE)
+        return ss::fail(SS_ERR_UNSUPPORTED, "per-feature normalisation needs a clip's statistics: a stream has none (chain ss_cmvn_* behind the pool)");
+    return ss_nstream_state_len(&cfg->params, &S, &L);
+}
+
+// Ragged streaming log-mel over a pool of stream states (ss_nstream_log_mel_packed*_device): the rows of n_active entries of different
+// hop counts, each over the pool row its slot names, then the advance of the named rows -- a linear chain of two kernels on `stream`,
+// the pool build of ss_nemo_c256 and the frame pool's ss_stream_advance_packed over one entry block (state_len = S, step = 160,
+// lead = S - 1).  The tables are device arrays read by the kernels only; the grids come from n_active and total_rows.  x: the packed
+// chunks, floats or 16-bit PCM.
+int nemo_pool_device(const ss_nemo_config *cfg, const PoolChunks &x, size_t n_active, const int64_t *d_so, const int64_t *d_ro, size_t total_rows,
+                     const int32_t *d_slots, size_t pool_streams, float *d_pool, float *d_out, hipStream_t stream)
+{
+    size_t S = 0, L = 0;
+    if (int rc = nstream_check_call(cfg, S, L)) return rc;
+    if (n_active == 0) return SS_OK;
+    if (!x.ptr() || !d_so || !d_ro || !d_slots || !d_out || !d_pool) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (x.is_pcm) {
+        if (int rc = check_pcm_scale(x.scale)) return rc;
+        if (reinterpret_cast<uintptr_t>(x.pcm) & 1u) return ss::fail(SS_ERR_ARG, "the PCM buffer must be 2-byte aligned");
+    }
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull || total_rows >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
+    if (ranges_overlap(d_pool, pool_streams * S * sizeof(float), d_out, total_rows * cfg->params.n_mels * sizeof(float)))
+        return ss::fail(SS_ERR_ARG, "the pool overlaps an output");
+    if (int rc = nemo_ready(cfg)) return rc;
+    const ss::NemoArgs a = nemo_args(cfg, x.f, d_out);
+    ss::FrameStreamPackedPcmArgs sp{};
+    sp.e.pool = d_pool;
+    sp.e.state_len = static_cast<uint32_t>(S);
+    sp.e.lead = static_cast<int32_t>(S - 1);
+    sp.e.so = reinterpret_cast<const long long *>(d_so);
+    sp.e.ro = reinterpret_cast<const long long *>(d_ro);
+    sp.e.slots = d_slots;
+    sp.e.n_active = static_cast<uint32_t>(n_active);
+    sp.e.pool_streams = static_cast<uint32_t>(pool_streams);
+    sp.e.total_rows = static_cast<uint32_t>(total_rows);
+    sp.e.step = ss::kNemoHop;
+    sp.e.err = cfg->d_err;
+    sp.x = x.pcm;
+    sp.scale = x.scale;
+    ss::LaunchInfo info{};
+    hipError_t e = ss::launch_nemo_c256_stream_packed(a, sp, x.is_pcm, stream, cfg->num_cus, &info);
+    if (e != hipSuccess) return hip_fail(e, "launch_nemo_c256_stream_packed");
+    g_last_kernel = info.kernel_name;
+    e = x.is_pcm ? ss::launch_stream_advance_packed(sp, stream) : ss::launch_stream_advance_packed(sp.e, x.f, stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_stream_advance_packed");
+    return SS_OK;
+}
+
+// Host-pointer form, as kaldi_pool_host: the tables are checked here, before anything touches the device; then x, the tables and the
+// n_active named pool rows (a compact block whose row i is entry i's) go up, the output and the named rows come down.  The caller's
+// pool is written only once everything before it succeeded.
+int nemo_pool_host(const ss_nemo_config *cfg, const PoolChunks &x, size_t n_active, const int64_t *so, const int32_t *slots, size_t pool_streams,
+                   float *pool, float *out)
+{
+    size_t S = 0, L = 0;
+    int rc = nstream_check_call(cfg, S, L);
+    if (rc) return rc;
+    if (n_active == 0) return SS_OK;
+    if (!x.ptr() || !so || !slots || !out || !pool) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (x.is_pcm && (rc = check_pcm_scale(x.scale))) return rc;
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
+    std::vector<int64_t> ro(n_active + 1);
+    if ((rc = ss_nstream_row_offsets(&cfg->params, n_active, so, ro.data()))) return rc;
+    if ((rc = ss::check_slots(slots, n_active, pool_streams))) return rc;
+    const size_t rows = static_cast<size_t>(ro[n_active]), samples = static_cast<size_t>(so[n_active]);
+    if (rows >= 0x80000000ull) return ss::fail(SS_ERR_ARG, "n_active, pool_streams and total_rows must be below 2^31");
+    const size_t obytes = rows * cfg->params.n_mels * sizeof(float), pbytes = pool_streams * S * sizeof(float);
+    if (ranges_overlap(pool, pbytes, x.ptr(), samples * x.sample_bytes()) || ranges_overlap(pool, pbytes, out, obytes))
+        return ss::fail(SS_ERR_ARG, "the pool overlaps the input or an output");
+    if (!ss::have_device()) return ss::no_device("hot path");
+    ss::PoolRows named;  // the named pool rows, row i = entry i's
+    named.gather(pool, slots, n_active, S);
+    const size_t tbytes = (n_active + 1) * sizeof(int64_t);
+    ss::HostStage st("ss_nstream");
+    const void *dx = st.up(x.ptr(), samples * x.sample_bytes());
+    const int64_t *dso = st.up(so, tbytes), *dro = st.up(ro.data(), tbytes);
+    const auto d_named = st.up_pool(named);
+    float *d0 = st.room<float>(obytes);
+    if (st.ok())
+        st.ran(nemo_pool_device(cfg, x.is_pcm ? PoolChunks(static_cast<const int16_t *>(dx), x.scale) : PoolChunks(static_cast<const float *>(dx)),
+                                n_active, dso, dro, rows, d_named.slots, n_active, d_named.rows, d0, nullptr));
+    st.sync();
+    if (st.ok()) st.ran(nemo_pending_error(cfg));
+    st.down(out, d0, obytes);
+    st.down_pool(named, d_named, " (pool rows)");
+    st.scatter(named, pool, slots);
+    return st.status();
+}
+
+// The flush: the L rows of every named stream (one launch, none where L == 0), then the zeroing of the named pool rows
+int nemo_flush_device(const ss_nemo_config *cfg, size_t n_active, const int32_t *d_slots, size_t pool_streams, float *d_pool, float *d_out,
+                      hipStream_t stream)
+{
+    size_t S = 0, L = 0;
+    if (int rc = nstream_check_call(cfg, S, L)) return rc;
+    if (n_active == 0) return SS_OK;
+    if (!d_slots || !d_pool || (L > 0 && !d_out)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull || n_active * L >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and the row count must be below 2^31");
+    if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
+    if (L > 0 && ranges_overlap(d_pool, pool_streams * S * sizeof(float), d_out, n_active * L * cfg->params.n_mels * sizeof(float)))
+        return ss::fail(SS_ERR_ARG, "the pool overlaps an output");
+    if (int rc = nemo_ready(cfg)) return rc;
+    const ss::NemoArgs a = nemo_args(cfg, nullptr, d_out);
+    ss::NemoFlushArgs s{};
+    s.pool = d_pool;
+    s.state_len = static_cast<uint32_t>(S);
+    s.delay = static_cast<uint32_t>(L);
+    s.slots = d_slots;
+    s.n_active = static_cast<uint32_t>(n_active);
+    s.pool_streams = static_cast<uint32_t>(pool_streams);
+    s.err = cfg->d_err;
+    ss::LaunchInfo info{};
+    const hipError_t e = ss::launch_nemo_c256_flush(a, s, stream, cfg->num_cus, &info);
+    if (e != hipSuccess) return hip_fail(e, "launch_nemo_c256_flush");
+    g_last_kernel = info.kernel_name;
+    return SS_OK;
+}
+
+int nemo_flush_host(const ss_nemo_config *cfg, size_t n_active, const int32_t *slots, size_t pool_streams, float *pool, float *out)
+{
+    size_t S = 0, L = 0;
+    int rc = nstream_check_call(cfg, S, L);
+    if (rc) return rc;
+    if (n_active == 0) return SS_OK;
+    if (!slots || !pool || (L > 0 && !out)) return ss::fail(SS_ERR_ARG, "null buffer");
+    if (n_active >= 0x80000000ull || pool_streams >= 0x80000000ull || n_active * L >= 0x80000000ull)
+        return ss::fail(SS_ERR_ARG, "n_active, pool_streams and the row count must be below 2^31");
+    if (pool_streams == 0) return ss::fail(SS_ERR_ARG, "the pool has no rows");
+    if ((rc = ss::check_slots(slots, n_active, pool_streams))) return rc;
+    const size_t obytes = n_active * L * cfg->params.n_mels * sizeof(float);
+    if (L > 0 && ranges_overlap(pool, pool_streams * S * sizeof(float), out, obytes)) return ss::fail(SS_ERR_ARG, "the pool overlaps an output");
+    if (!ss::have_device()) return ss::no_device("hot path");
+    ss::PoolRows named;
+    named.gather(pool, slots, n_active, S);
+    ss::HostStage st("ss_nstream");
+    const auto d_named = st.up_pool(named);
+    float *d0 = L > 0 ? st.room<float>(obytes) : nullptr;
+    if (st.ok()) st.ran(nemo_flush_device(cfg, n_active, d_named.slots, n_active, d_named.rows, d0, nullptr));
+    st.sync();
+    if (st.ok()) st.ran(nemo_pending_error(cfg));
+    if (L > 0) st.down(out, d0, obytes);
+    st.down_pool(named, d_named, " (pool rows)");
+    st.scatter(named, pool, slots);
+    return st.status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -3881,6 +4038,45 @@ int ss_nemo_log_mel_packed(const ss_nemo_config *cfg, const float *x, size_t n_c
     if (st.ok()) st.ran(nemo_pending_error(cfg));
     st.down(out, d_out, obytes);
     return st.status();
+}
+
+int ss_nstream_log_mel_packed_device(const ss_nemo_config *cfg, const float *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                     const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float *d_pool,
+                                     float *d_out, void *stream)
+{
+    return nemo_pool_device(cfg, PoolChunks(d_x), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams, d_pool, d_out,
+                            static_cast<hipStream_t>(stream));
+}
+
+int ss_nstream_log_mel_packed(const ss_nemo_config *cfg, const float *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                              size_t pool_streams, float *pool, float *out)
+{
+    return nemo_pool_host(cfg, PoolChunks(x), n_active, sample_offsets, slots, pool_streams, pool, out);
+}
+
+int ss_nstream_log_mel_packed_i16_device(const ss_nemo_config *cfg, const int16_t *d_x, size_t n_active, const int64_t *d_sample_offsets,
+                                         const int64_t *d_row_offsets, size_t total_rows, const int32_t *d_slots, size_t pool_streams, float scale,
+                                         float *d_pool, float *d_out, void *stream)
+{
+    return nemo_pool_device(cfg, PoolChunks(d_x, scale), n_active, d_sample_offsets, d_row_offsets, total_rows, d_slots, pool_streams, d_pool, d_out,
+                            static_cast<hipStream_t>(stream));
+}
+
+int ss_nstream_log_mel_packed_i16(const ss_nemo_config *cfg, const int16_t *x, size_t n_active, const int64_t *sample_offsets, const int32_t *slots,
+                                  size_t pool_streams, float scale, float *pool, float *out)
+{
+    return nemo_pool_host(cfg, PoolChunks(x, scale), n_active, sample_offsets, slots, pool_streams, pool, out);
+}
+
+int ss_nstream_flush_device(const ss_nemo_config *cfg, size_t n_active, const int32_t *d_slots, size_t pool_streams, float *d_pool, float *d_out,
+                            void *stream)
+{
+    return nemo_flush_device(cfg, n_active, d_slots, pool_streams, d_pool, d_out, static_cast<hipStream_t>(stream));
+}
+
+int ss_nstream_flush(const ss_nemo_config *cfg, size_t n_active, const int32_t *slots, size_t pool_streams, float *pool, float *out)
+{
+    return nemo_flush_host(cfg, n_active, slots, pool_streams, pool, out);
 }
 
 }  // extern "C"

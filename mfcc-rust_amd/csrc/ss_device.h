@@ -908,6 +908,28 @@ hipError_t launch_nemo_c256_varlen(const NemoArgs &a, const NemoVarlenArgs &v, h
 // step 8 in place on a.out: the rows of a.batch clips of a.n_frames rows, or (v non-null) of the packed clips, a bad one skipped.
 // The grid depends on the clip count and n_mels only.
 hipError_t launch_nemo_norm(const NemoArgs &a, const NemoVarlenArgs *v, hipStream_t stream);
+// The stream-pool builds (ss_nemo512_pool.hip; ss_nstream_log_mel_packed*_device): the packed output rows of a ragged streaming launch
+// over the frame pool's entry block -- step = 160, state_len = S = 160 L + W / 2 + 1 with L = ceil(W / 320) - 1, lead = S - 1: row t
+// of an entry starts at chunk sample 160 t - lead, and its pre-emphasis predecessor is the sample in front of that.  pcm: the chunks
+// are sp.x (2-byte aligned) times sp.scale, else a.x (sp.x / sp.scale unused); batch / n_samples / n_frames / ld are unused.  The
+// grid comes from total_rows (one workgroup where it is 0: the entry pass).  The advance is launch_stream_advance_packed over the
+// same block.
+hipError_t launch_nemo_c256_stream_packed(const NemoArgs &a, const FrameStreamPackedPcmArgs &sp, bool pcm, hipStream_t stream, int num_cus,
+                                          LaunchInfo *info);
+// The flush (ss_nstream_flush_device): row i * delay + u of a.out is row u of the stream whose state is pool row slots[i], the frame
+// that starts 160 (u - delay) - W / 2 from the stream's end; an entry whose slot lies outside the pool is skipped.
+struct NemoFlushArgs {
+    float *pool;           // [pool_streams][state_len]
+    uint32_t state_len;    // S
+    uint32_t delay;        // L: rows per entry
+    const int32_t *slots;  // [n_active]
+    uint32_t n_active;
+    uint32_t pool_streams;
+    unsigned *err;         // the handle's device error word (set to kVarlenError on a bad entry)
+};
+// Two launches: the n_active * delay rows (none where delay == 0), then the zeroing of the named pool rows, which also reports a bad
+// entry.  The grids depend on n_active and delay only.
+hipError_t launch_nemo_c256_flush(const NemoArgs &a, const NemoFlushArgs &s, hipStream_t stream, int num_cus, LaunchInfo *info);
 
 // The fused splice + affine transform of packed rows (ss_affine.hip; ss_affine_splice_packed*): out[g] = M * (spliced row g) + bias
 // on the f32 matrix instruction.  x / ro and out / oo are the two packed blocks and their tables as ss_splice_packed_device takes

@@ -1740,6 +1740,26 @@ int ss_nemo_mel_bank(const ss_nemo_params *p, float *bank)
     return SS_OK;
 }
 
+// the stream pool of the NeMo front end: L = ceil(W / 320) - 1 rows of delay (a centred frame reaches W / 2 samples past its hop),
+// S = 160 L + W / 2 + 1 carried samples: the frame's reach plus the one pre-emphasis predecessor.  Sizes only: normalize is not read.
+int ss_nstream_state_len(const ss_nemo_params *p, size_t *state_len, size_t *delay_rows)
+{
+    if (!p || !state_len || !delay_rows) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::nemo_validate(*p)) return rc;
+    const size_t W = p->win_length, H = p->hop_length;
+    const size_t L = (W + 2 * H - 1) / (2 * H) - 1;
+    *delay_rows = L;
+    *state_len = L * H + W / 2 + 1;
+    return SS_OK;
+}
+
+int ss_nstream_row_offsets(const ss_nemo_params *p, size_t n_active, const int64_t *sample_offsets, int64_t *row_offsets)
+{
+    if (!p || !sample_offsets || !row_offsets) return ss::fail(SS_ERR_ARG, "null argument");
+    if (int rc = ss::nemo_validate(*p)) return rc;
+    return walk_stream_offsets(n_active, sample_offsets, row_offsets, static_cast<int64_t>(p->hop_length), "the NeMo stream pool");
+}
+
 const char *ss_status_string(int status)
 {
     switch (status) {

@@ -304,6 +304,13 @@ extern "C" {
     fn ss_nemo_log_mel_packed_device(cfg: *const c_void, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64,
                                      d_frame_offsets: *const i64, total_frames: usize, d_out: *mut f32, stream: *mut c_void) -> c_int;
     fn ss_nemo_log_mel_packed(cfg: *const c_void, x: *const f32, n_clips: usize, sample_offsets: *const i64, out: *mut f32) -> c_int;
+    fn ss_nstream_state_len(p: *const SsNemoParams, state_len: *mut usize, delay_rows: *mut usize) -> c_int;
+    fn ss_nstream_row_offsets(p: *const SsNemoParams, n_active: usize, sample_offsets: *const i64, row_offsets: *mut i64) -> c_int;
+    fn ss_nstream_log_mel_packed(cfg: *const c_void, x: *const f32, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                                 pool_streams: usize, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_nstream_log_mel_packed_i16(cfg: *const c_void, x: *const i16, n_active: usize, sample_offsets: *const i64, slots: *const i32,
+                                     pool_streams: usize, scale: f32, pool: *mut f32, out: *mut f32) -> c_int;
+    fn ss_nstream_flush(cfg: *const c_void, n_active: usize, slots: *const i32, pool_streams: usize, pool: *mut f32, out: *mut f32) -> c_int;
     fn ss_derivative_extraction(feat: *const f32, rows: usize, cols: usize, delta_windows: usize, out: *mut f32) -> c_int;
     fn ss_extract_derivative_feature(feat: *const f32, rows: usize, cols: usize, cube: *mut f32) -> c_int;
     fn ss_shard_bounds(n_items: usize, world: c_int, rank: c_int, lo: *mut usize, hi: *mut usize) -> c_int;
@@ -2276,6 +2283,75 @@ impl NemoFrontEnd {
     pub unsafe fn log_mel_packed_device(&self, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, d_frame_offsets: *const i64,
                                         total_frames: usize, d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
         check(ss_nemo_log_mel_packed_device(self.raw, d_x, n_clips, d_sample_offsets, d_frame_offsets, total_frames, d_out, stream))
+    }
+
+    /// The stream pool's sizes (`ss_nstream_state_len`): (S, the carried samples per stream = the floats of a pool row; L, the
+    /// warm-up rows after a reset and the rows a flush returns per stream).
+    pub fn stream_state_len(&self) -> Result<(usize, usize), Error> {
+        let (mut s, mut l) = (0usize, 0usize);
+        check(unsafe { ss_nstream_state_len(&self.params, &mut s, &mut l) })?;
+        Ok((s, l))
+    }
+
+    /// Row offsets of the entries of a pool call (`ss_nstream_row_offsets`): every chunk is whole 160-sample hops.
+    pub fn stream_row_offsets(&self, sample_offsets: &[i64]) -> Result<Vec<i64>, Error> {
+        if sample_offsets.is_empty() {
+            return Err(Error { status: SS_ERR_ARG, detail: "sample_offsets must not be empty".to_string() });
+        }
+        let mut ro = vec![0i64; sample_offsets.len()];
+        check(unsafe { ss_nstream_row_offsets(&self.params, sample_offsets.len() - 1, sample_offsets.as_ptr(), ro.as_mut_ptr()) })?;
+        Ok(ro)
+    }
+
+    // the checks the pool wrappers share: the tables against the block and the pool -> (row offsets, pool rows)
+    fn stream_shape<T>(&self, x: &[T], sample_offsets: &[i64], slots: &[i32], pool: &[f32]) -> Result<(Vec<i64>, usize), Error> {
+        let ro = self.stream_row_offsets(sample_offsets)?;
+        let (s, _) = self.stream_state_len()?;
+        if slots.len() != sample_offsets.len() - 1 || sample_offsets[sample_offsets.len() - 1] as usize > x.len() {
+            return Err(Error { status: SS_ERR_ARG, detail: "pool call: shape mismatch".to_string() });
+        }
+        if pool.is_empty() || pool.len() % s != 0 {
+            return Err(Error { status: SS_ERR_ARG, detail: "pool call: the pool is not a whole number of rows".to_string() });
+        }
+        Ok((ro, pool.len() / s))
+    }
+
+    /// Ragged streaming log-mel over a pool of stream states (`ss_nstream_log_mel_packed`; a handle with `normalize` none): entry i
+    /// is the chunk `x[sample_offsets[i] .. sample_offsets[i+1])` (whole hops) of the stream whose state is pool row `slots[i]`;
+    /// `pool` is `[pool_streams x S]`, all-zero rows are fresh streams.  -> (rows, row offsets); the first L rows of a fresh stream
+    /// are warm-up rows.
+    pub fn log_mel_stream_packed(&self, x: &[f32], sample_offsets: &[i64], slots: &[i32], pool: &mut [f32]) -> Result<(Array2<f32>, Vec<i64>), Error> {
+        let (ro, pool_streams) = self.stream_shape(x, sample_offsets, slots, pool)?;
+        let mut out = Array2::<f32>::zeros((ro[ro.len() - 1] as usize, self.n_mels()));
+        check(unsafe {
+            ss_nstream_log_mel_packed(self.raw, x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams, pool.as_mut_ptr(),
+                                      out.as_mut_ptr())
+        })?;
+        Ok((out, ro))
+    }
+
+    /// `log_mel_stream_packed` fed signed 16-bit PCM: sample = `pcm as f32 * scale`, `scale` a power of two (`ss_nstream_log_mel_packed_i16`).
+    pub fn log_mel_stream_packed_i16(&self, x: &[i16], sample_offsets: &[i64], slots: &[i32], scale: f32, pool: &mut [f32])
+                                     -> Result<(Array2<f32>, Vec<i64>), Error> {
+        let (ro, pool_streams) = self.stream_shape(x, sample_offsets, slots, pool)?;
+        let mut out = Array2::<f32>::zeros((ro[ro.len() - 1] as usize, self.n_mels()));
+        check(unsafe {
+            ss_nstream_log_mel_packed_i16(self.raw, x.as_ptr(), slots.len(), sample_offsets.as_ptr(), slots.as_ptr(), pool_streams, scale,
+                                          pool.as_mut_ptr(), out.as_mut_ptr())
+        })?;
+        Ok((out, ro))
+    }
+
+    /// The end of the named streams (`ss_nstream_flush`): `[slots.len() * L x n_mels]`, stream i's last L rows at rows `i * L ..`;
+    /// the named pool rows are zero (fresh streams) afterwards.
+    pub fn stream_flush(&self, slots: &[i32], pool: &mut [f32]) -> Result<Array2<f32>, Error> {
+        let (s, l) = self.stream_state_len()?;
+        if pool.is_empty() || pool.len() % s != 0 {
+            return Err(Error { status: SS_ERR_ARG, detail: "flush: the pool is not a whole number of rows".to_string() });
+        }
+        let mut out = Array2::<f32>::zeros((slots.len() * l, self.n_mels()));
+        check(unsafe { ss_nstream_flush(self.raw, slots.len(), slots.as_ptr(), pool.len() / s, pool.as_mut_ptr(), out.as_mut_ptr()) })?;
+        Ok(out)
     }
 }
 

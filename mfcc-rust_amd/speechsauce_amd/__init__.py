@@ -37,7 +37,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "KaldiFbankStreamPool", "KaldiMfccStreamPool",
            "whisper_log_mel", "whisper_log_mel_packed", "whisper_log_mel_list", "whisper_num_frames", "WhisperConfig",
-           "nemo_log_mel", "nemo_log_mel_packed", "nemo_log_mel_list", "nemo_num_frames", "NemoConfig",
+           "nemo_log_mel", "nemo_log_mel_packed", "nemo_log_mel_list", "nemo_num_frames", "NemoConfig", "NemoLogMelStreamPool",
            "SpeechConfig", "SpeechSauceError"]
 
 
@@ -3246,7 +3246,37 @@ def kaldi_mfcc_packed(signal, lengths, sample_frequency=16000.0, frame_length=25
 
 # ---- the Kaldi front end over a pool of stream states (ss_kstream_*) ----------------------------------------------------------
 
-class _KaldiStreamPoolBase(_StreamPoolMixin):
+class _FrontStreamPoolBase(_StreamPoolMixin):
+    """What the pools of the handle-based front ends (``Kaldi*StreamPool``, ``NemoLogMelStreamPool``) share: they own their pool block
+    and sizes themselves (no dense streaming base behind the mixin), zero rows in place, and take chunk lengths or sample offsets."""
+
+    def reset(self, slots=None):
+        """Zero the state of every stream of the pool, or of the given slots (fresh streams: their next ``delay_rows`` rows are
+        warm-up rows again)."""
+        if self._state is None:
+            return
+        if slots is None:
+            self._state[...] = 0
+        else:
+            idx = list(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
+            if idx:
+                self._state[idx] = 0
+
+    def _lengths(self, lengths_or_offsets, n_slots):
+        if lengths_or_offsets is None:
+            return None
+        v = np.asarray(lengths_or_offsets.cpu() if _is_torch(lengths_or_offsets) else lengths_or_offsets)
+        if v.ndim != 1 or not (np.issubdtype(v.dtype, np.integer) or v.size == 0):
+            raise TypeError(f"{self._what}: lengths_or_offsets must be a 1-D sequence of integers")
+        v = v.astype(np.int64)
+        if v.size == n_slots + 1:  # sample offsets
+            if v[0] != 0:
+                raise ValueError(f"{self._what}: sample offsets must start at 0")
+            return np.diff(v)
+        return v
+
+
+class _KaldiStreamPoolBase(_FrontStreamPoolBase):
     """A pool of ``pool_streams`` live audio streams through ``kaldi_fbank`` / ``kaldi_mfcc``: the constructor takes torchaudio's
     keyword names (see ``kaldi_fbank``) plus ``pool_streams``; every stream carries its last ``state_len = delay_rows * hop`` samples,
     ``delay_rows = ceil(frame / hop) - 1``.  ``pool(chunks, lengths_or_offsets, slots, pcm_scale=None)``: ``chunks`` is one packed
@@ -3290,31 +3320,6 @@ class _KaldiStreamPoolBase(_StreamPoolMixin):
 
     def _config_for(self, packed):
         return _get_kaldi_config(self._key(), _device_key(packed))
-
-    def reset(self, slots=None):
-        """Zero the state of every stream of the pool, or of the given slots (fresh streams: their next ``delay_rows`` rows are
-        warm-up rows again)."""
-        if self._state is None:
-            return
-        if slots is None:
-            self._state[...] = 0
-        else:
-            idx = list(np.atleast_1d(np.asarray(slots, dtype=np.int64)))
-            if idx:
-                self._state[idx] = 0
-
-    def _lengths(self, lengths_or_offsets, n_slots):
-        if lengths_or_offsets is None:
-            return None
-        v = np.asarray(lengths_or_offsets.cpu() if _is_torch(lengths_or_offsets) else lengths_or_offsets)
-        if v.ndim != 1 or not (np.issubdtype(v.dtype, np.integer) or v.size == 0):
-            raise TypeError(f"{self._what}: lengths_or_offsets must be a 1-D sequence of integers")
-        v = v.astype(np.int64)
-        if v.size == n_slots + 1:  # sample offsets
-            if v[0] != 0:
-                raise ValueError(f"{self._what}: sample offsets must start at 0")
-            return np.diff(v)
-        return v
 
     def _run(self, chunks, lengths_or_offsets, slots, pcm_scale, cols, with_energy):
         slot_list = [int(v) for v in slots]
@@ -3736,3 +3741,75 @@ def nemo_log_mel_list(signals, n_mels=80, normalize="per_feature", win_length=40
         return pad_packed(rows, fo, None, layout, dtype, pad_value)
     fo = fo.tolist()
     return [rows[fo[b]:fo[b + 1]] for b in range(len(sigs))]
+
+
+class NemoLogMelStreamPool(_FrontStreamPoolBase):
+    """A pool of ``pool_streams`` live audio streams through ``nemo_log_mel(..., normalize=None)``: the log-mel input of cache-aware
+    FastConformer and the real-time Parakeet models, hop by hop.  Every stream carries its last ``state_len = delay_rows * 160 +
+    win_length // 2 + 1`` samples, ``delay_rows = ceil(win_length / 320) - 1`` (1 for the default 400-sample window).
+    ``pool(chunks, lengths_or_offsets, slots, pcm_scale=None)`` takes what ``KaldiFbankStreamPool`` takes -- one packed 1-D float32
+    buffer (int16 with ``pcm_scale``, a power of two) with the chunk lengths or the ``len(slots) + 1`` sample offsets, every chunk a
+    whole number of 160-sample hops (zero included), or a list of 1-D chunks with ``lengths_or_offsets=None`` -- and returns ``(rows
+    [total_rows, n_mels], row_offsets)``, the pair ``CmvnStreamPool`` / ``SpliceStreamPool`` take with the same ``slots``.
+    ``flush(slots)`` ends the named streams: ``[len(slots) * delay_rows, n_mels]``, stream ``i``'s last ``delay_rows`` rows at
+    ``[i * delay_rows, (i + 1) * delay_rows)`` -- the frames that overhang the stream's end -- and the slots are fresh afterwards.
+
+    The first ``delay_rows`` rows of a stream after a reset are warm-up rows (the rows of ``zeros(delay_rows * 160) ++ stream``);
+    the rows after them, followed by the flush rows, are bit for bit ``nemo_log_mel(stream, normalize=None)``, however the stream
+    was cut into calls.  A trailing partial hop is the caller's to hold back.  Per-feature normalisation needs a whole clip: chain
+    ``CmvnStreamPool`` instead.  numpy in -> the host-pointer call, ROCm tensors in -> the device call on the current stream.  See
+    ``ss_nstream_*`` in ``include/speechsauce_amd.h``."""
+
+    _what = "NemoLogMelStreamPool"
+
+    def __init__(self, pool_streams, n_mels=80, win_length=400, preemph=0.97, log_guard=2.0 ** -24):
+        if int(pool_streams) < 1:
+            raise ValueError(f"{self._what}: pool_streams must be at least 1")
+        self.pool_streams = int(pool_streams)
+        self._key = (int(n_mels), None, int(win_length), float(preemph), float(log_guard), 1e-5)
+        self._params = _nemo_params(*self._key)
+        lib = _lib.lib()
+        _lib.check(lib.ss_nemo_params_validate(C.byref(self._params)))
+        S, L = C.c_size_t(), C.c_size_t()
+        _lib.check(lib.ss_nstream_state_len(C.byref(self._params), C.byref(S), C.byref(L)))
+        self.state_len, self.delay_rows, self.hop, self.cols = S.value, L.value, int(self._params.hop_length), int(n_mels)
+        self._state = None
+        self._where = None
+
+    def _config_for(self, packed):
+        return _get_nemo_config(self._key, _device_key(packed))
+
+    def __call__(self, chunks, lengths_or_offsets, slots, pcm_scale=None):
+        slot_list = [int(v) for v in slots]
+        (packed, so, ro, sl, config), i16, scale = self._prepare_pcm(chunks, slot_list, self._lengths(lengths_or_offsets, len(slot_list)), pcm_scale)
+        R = int(ro[-1])
+        if _is_torch(packed):
+            import torch
+
+            out = torch.empty((R, self.cols), dtype=torch.float32, device=packed.device)
+        else:
+            out = np.empty((R, self.cols), dtype=np.float32)
+        self._call_pool(packed, so, ro, sl, config, [out], f"ss_nstream_log_mel_packed{i16}_device", f"ss_nstream_log_mel_packed{i16}", scale)
+        return out, ro
+
+    def flush(self, slots):
+        """The last ``delay_rows`` rows of every named stream -> ``[len(slots) * delay_rows, n_mels]``; the slots are fresh
+        afterwards.  Before the first ``pool`` call every stream is fresh: the rows are those of silence, on the host."""
+        sl = np.asarray(_pool_slots(slots, self.pool_streams, self._what), dtype=np.int32)
+        n, lib = sl.size, _lib.lib()
+        if self._state is None:  # nothing was pushed yet: the flush of fresh streams, served by a host pool of zeros
+            self._state = np.zeros((self.pool_streams, self.state_len), dtype=np.float32)
+            self._where = ("host",)
+        if _is_torch(self._state):
+            import torch
+
+            out = torch.empty((n * self.delay_rows, self.cols), dtype=torch.float32, device=self._state.device)
+            if n:
+                _launch(self._state.device, lib.ss_nstream_flush_device, self._config_for(self._state).handle, n, sl, self.pool_streams,
+                        self._state.data_ptr(), out.data_ptr())
+        else:
+            out = np.empty((n * self.delay_rows, self.cols), dtype=np.float32)
+            if n:
+                _lib.check(lib.ss_nstream_flush(self._config_for(self._state).handle, n, sl.ctypes.data, self.pool_streams,
+                                                self._state.ctypes.data, out.ctypes.data))
+        return out

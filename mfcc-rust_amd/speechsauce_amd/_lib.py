@@ -413,6 +413,16 @@ PROTOTYPES = {
     "ss_nemo_log_mel": (C.c_int, [_nc, _fp, C.c_size_t, C.c_size_t, C.c_size_t, _fp]),
     "ss_nemo_log_mel_packed_device": (C.c_int, [_nc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
     "ss_nemo_log_mel_packed": (C.c_int, [_nc, _fp, C.c_size_t, C.c_void_p, _fp]),
+    "ss_nstream_state_len": (C.c_int, [_P(SsNemoParams), _P(C.c_size_t), _P(C.c_size_t)]),
+    "ss_nstream_row_offsets": (C.c_int, [_P(SsNemoParams), C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ss_nstream_log_mel_packed_device": (
+        C.c_int, [_nc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_nstream_log_mel_packed": (C.c_int, [_nc, _fp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, _fp, _fp]),
+    "ss_nstream_log_mel_packed_i16_device": (
+        C.c_int, [_nc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp, C.c_void_p]),
+    "ss_nstream_log_mel_packed_i16": (C.c_int, [_nc, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, _fp, _fp]),
+    "ss_nstream_flush_device": (C.c_int, [_nc, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp, C.c_void_p]),
+    "ss_nstream_flush": (C.c_int, [_nc, C.c_size_t, C.c_void_p, C.c_size_t, _fp, _fp]),
     "ss_kstream_state_len": (C.c_int, [_P(SsKaldiParams), _P(C.c_size_t), _P(C.c_size_t)]),
     "ss_kstream_row_offsets": (C.c_int, [_P(SsKaldiParams), C.c_size_t, C.c_void_p, C.c_void_p]),
     "ss_kstream_fbank_packed_device": (
