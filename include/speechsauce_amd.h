@@ -1258,6 +1258,122 @@ int ss_specaug_packed(const float *vec, size_t n_clips, const int64_t *row_offse
                       size_t clip_base, size_t n_time, size_t max_time_width, float time_ratio, size_t n_freq, size_t max_freq_width,
                       float mask_value, float *out, int32_t *spans);
 
+/* ---- additive noise at a drawn SNR and gain perturbation of packed clips, seeded on the device ----
+ * The waveform augmentation of the training recipes (Kaldi wav-reverberate --additive-signals --snrs and sox vol, ESPnet
+ * noise_apply_prob / noise_db_range, NeMo NoisePerturbation / GainPerturbation, lhotse mix, torchaudio.functional.add_noise), ahead of
+ * the front end: with probability prob a clip gets a segment of a drawn noise clip added at a drawn SNR, and every clip a drawn gain.
+ * The stage reads nothing back and draws fresh noise on every replay of a captured graph.  The reference crate has none: this comment
+ * is the specification.
+ *   Speech: x, packed samples; clip b owns samples so[b] .. so[b+1] (the sample_offsets of ss_mfcc_packed*, the out_offsets of
+ *   ss_resample_packed*); L_b = so[b+1] - so[b] < 2^31.  Noise bank: nz, packed samples; noise clip c owns no[c] .. no[c+1] of its
+ *   total_noise samples, N_c = no[c+1] - no[c] < 2^31; the bank is never written.  rng: two uint64 words {seed, epoch}, the block of
+ *   ss_specaug_packed* with the same rules.  clip_base: the id of clip 0.  Scalars: prob in [0, 1]; snr_lo_db <= snr_hi_db and
+ *   gain_lo_db <= gain_hi_db, finite (0, 0: no gain perturbation).
+ *   Plan: one ss_noise_plan_row per clip (40 bytes, 8-byte aligned), caller-owned and always written.
+ *   Draws (integers and f64 only: host and device agree exactly), with id = low32(clip_base + b), key = (low32(seed), high32(seed)):
+ *     (u0, u1, u2, u3) = philox((id, 0x20000, low32(epoch), high32(epoch)), key);  (v0, -, -, -) = philox((id, 0x20001, ..), key)
+ *     -- counter words apart from SpecAugment's mask indices, so that one seed may serve both stages.
+ *     mixed = (uint64)u0 < (uint64)((double)prob * 4294967296.0) and n_noise > 0;  c = (u1 * n_noise) >> 32;
+ *     a drawn noise clip that is empty, reversed or not inside [0, total_noise]: mixed = false;  start = (u2 * N_c) >> 32;
+ *     snr_db = (float)((double)snr_lo_db + ((double)snr_hi_db - (double)snr_lo_db) * (u3 * 2^-32)) -- the product and the sum each
+ *     rounded once in f64, the result once to f32; gain_db likewise from v0 and the gain range.
+ *     Not mixed: noise_clip = -1, start = 0.  A speech segment that is reversed, starts below 0 or ends past total_samples:
+ *     noise_clip = -2, start = 0, both gains and both energies 0, and its samples are untouched (out of place: left unwritten).
+ *   Energies (f64): speech_energy = sum (double)x_i^2 over the clip; noise_energy = sum (double)n_i^2 over the segment the clip gets,
+ *     n_i = nz[no[c] + (start + i) mod N_c], i = 0 .. L_b - 1 (the noise clip repeats); 0, and the bank unread, when not mixed.
+ *     Each square is exact.  The order of the additions is a function of L_b alone: chunks of 2048 clip-relative samples; within a
+ *     chunk 256 partials, partial l = ((0 + s_l) + s_{l+256}) + .. in ascending order over the samples the clip has; the tree
+ *     p[l] += p[l + h] for h = 128, 64, .. 1; the energy = ((0 + chunk_0) + chunk_1) + ..  No atomics.
+ *   Gains, formed in f64 and rounded once: G = 10^(gain_db / 20), exactly 1 when gain_db == 0;  speech_gain = (float)G;
+ *     noise_gain = (float)((G * sqrt(speech_energy / noise_energy)) * 10^(-snr_db / 20)) when the clip is mixed and both energies
+ *     are > 0, else 0.  The device's pow is not correctly rounded: these two words are specified to the f32 nearest the f64 value or
+ *     its neighbour; every other word and every output bit is exact.
+ *   Mix, bit for bit a function of the plan row: out[i] = fmaf(noise_gain, n_i, speech_gain * x_i), the product rounded on its own.
+ *     A row with noise_gain == 0, or whose noise_clip or start is out of range for the bank (a caller's plan), is not mixed: out[i] =
+ *     speech_gain * x_i and the bank is not read.  A row with noise_clip == -2 leaves its samples untouched.
+ *   A clip's row and output depend on (seed, epoch, clip_base + b), its own samples, the bank and the scalars only -- not on its
+ *   offset or its neighbours: the clips [B, C] at clip_base 1 get what they get as clips 1 and 2 of [A, B, C] at clip_base 0.
+ *   Worked pin: seed 2026, epoch 0, clip_base 0, prob 0.5, SNR 10 .. 30 dB, gain -6 .. 6 dB, three speech clips of 16000 samples, a
+ *   bank of noise clips of 8000, 1, 0, 50001 and 32000 samples: (noise_clip, start, snr_db, gain_db) of clips 0, 1, 2 =
+ *   (3, 24801, 28.130686, -3.0997949) | (0, 4033, 14.968082, -1.3559483) | (-1, 0, 11.51598, 4.993896) -- the shortest decimals
+ *   that round to the f32 words.
+ * Calls:
+ *   ss_noise_draws                   host only, no device: the four draw fields of every row from the same code; gains and energies 0.
+ *   ss_noise_mix_work_bytes          the size of the caller-owned scratch of the device plan and mix forms (f64 partial sums: two words
+ *                                    per chunk, total_samples / 2048 + n_clips chunk slots), 8-byte aligned.
+ *   ss_noise_plan_packed[_i16]_device    draws, energies and gains into the plan: ss_noise_energy_kernel (workgroups (clip, share): a block
+ *                                    of few long clips still fills the device) and ss_noise_fold_kernel.  epoch is not touched.
+ *   ss_noise_apply_packed[_i16][_device] the mix alone (ss_noise_apply_kernel, a flat walk over the block) on any plan table: the
+ *                                    caller's own for fixed gains, or one plan applied twice.
+ *   ss_noise_mix_packed[_i16][_device]   plan + apply, three launches, and the epoch bump: lane 0 of the apply launch stores epoch + 1.
+ *                                    The host forms update rng[1] and allocate their own scratch.
+ *   The _i16 forms take x and the bank as 16-bit PCM with x_scale and noise_scale (powers of two, as in ss_mfcc_packed_i16): sample k
+ *   is (float)pcm[k] * scale, out is float, and every plan word and output bit is that of the float call on the converted arrays;
+ *   2-byte alignment is enough.  There is no mixed float / PCM form.
+ *   d_out == d_x is the in-place call of the float form; any other overlap of out and x is an error, and the bank, the plan, rng and
+ *   the scratch may overlap neither.  Samples in no clip are left untouched; nothing outside the blocks is read or written, whatever
+ *   the tables or the plan hold.  The device forms expect speech segments that do not overlap one another (a sample in two segments
+ *   is mixed as part of one of them, and the two clips' energies are unspecified).  The grids depend on n_clips and total_samples
+ *   only; the device forms are asynchronous on `stream`, allocate nothing and read nothing back.  One rng block serves one stream of
+ *   calls.
+ * Arguments: n_clips == 0 is SS_OK, also without a device.  SS_ERR_ARG, decided before the device is touched: null buffers (the bank
+ * and noise_offsets may be null when n_noise == 0); prob outside [0, 1] or NaN; a reversed or non-finite dB range; n_clips,
+ * total_samples, n_noise or total_noise >= 2^31; clip_base + n_clips > 2^32; a scale that is not a power of two; samples, bank or
+ * out not aligned to their element, tables, plan, rng or work not 8-byte aligned; work_bytes below ss_noise_mix_work_bytes; the
+ * overlaps above.  The host forms check both tables first as the other host forms do (the speech table names the first bad clip)
+ * and write samples 0 .. so[n_clips) of out. */
+typedef struct ss_noise_plan_row {
+    int32_t noise_clip; /* the bank's clip; -1: not mixed; -2: a bad speech segment */
+    int32_t start;      /* first noise sample, 0 .. N_c - 1 */
+    float snr_db;
+    float gain_db;
+    float speech_gain;
+    float noise_gain;
+    double speech_energy;
+    double noise_energy;
+} ss_noise_plan_row;
+int ss_noise_draws(const uint64_t *rng, size_t clip_base, size_t n_clips, const int64_t *sample_offsets, size_t total_samples,
+                   size_t n_noise, const int64_t *noise_offsets, size_t total_noise, float prob, float snr_lo_db, float snr_hi_db,
+                   float gain_lo_db, float gain_hi_db, ss_noise_plan_row *plan);
+int ss_noise_mix_work_bytes(size_t n_clips, size_t total_samples, size_t *bytes);
+int ss_noise_plan_packed_device(const float *d_x, size_t n_clips, const int64_t *d_sample_offsets, size_t total_samples,
+                                const float *d_bank, size_t n_noise, const int64_t *d_noise_offsets, size_t total_noise,
+                                const uint64_t *d_rng, size_t clip_base, float prob, float snr_lo_db, float snr_hi_db, float gain_lo_db,
+                                float gain_hi_db, ss_noise_plan_row *d_plan, void *d_work, size_t work_bytes, void *stream);
+int ss_noise_plan_packed_i16_device(const int16_t *d_x, float x_scale, size_t n_clips, const int64_t *d_sample_offsets,
+                                    size_t total_samples, const int16_t *d_bank, float noise_scale, size_t n_noise,
+                                    const int64_t *d_noise_offsets, size_t total_noise, const uint64_t *d_rng, size_t clip_base,
+                                    float prob, float snr_lo_db, float snr_hi_db, float gain_lo_db, float gain_hi_db,
+                                    ss_noise_plan_row *d_plan, void *d_work, size_t work_bytes, void *stream);
+int ss_noise_apply_packed_device(const float *d_x, size_t n_clips, const int64_t *d_sample_offsets, size_t total_samples,
+                                 const float *d_bank, size_t n_noise, const int64_t *d_noise_offsets, size_t total_noise,
+                                 const ss_noise_plan_row *d_plan, float *d_out, void *stream);
+int ss_noise_apply_packed(const float *x, size_t n_clips, const int64_t *sample_offsets, size_t total_samples, const float *bank,
+                          size_t n_noise, const int64_t *noise_offsets, size_t total_noise, const ss_noise_plan_row *plan, float *out);
+int ss_noise_apply_packed_i16_device(const int16_t *d_x, float x_scale, size_t n_clips, const int64_t *d_sample_offsets,
+                                     size_t total_samples, const int16_t *d_bank, float noise_scale, size_t n_noise,
+                                     const int64_t *d_noise_offsets, size_t total_noise, const ss_noise_plan_row *d_plan, float *d_out,
+                                     void *stream);
+int ss_noise_apply_packed_i16(const int16_t *x, float x_scale, size_t n_clips, const int64_t *sample_offsets, size_t total_samples,
+                              const int16_t *bank, float noise_scale, size_t n_noise, const int64_t *noise_offsets, size_t total_noise,
+                              const ss_noise_plan_row *plan, float *out);
+int ss_noise_mix_packed_device(const float *d_x, size_t n_clips, const int64_t *d_sample_offsets, size_t total_samples,
+                               const float *d_bank, size_t n_noise, const int64_t *d_noise_offsets, size_t total_noise, uint64_t *d_rng,
+                               size_t clip_base, float prob, float snr_lo_db, float snr_hi_db, float gain_lo_db, float gain_hi_db,
+                               float *d_out, ss_noise_plan_row *d_plan, void *d_work, size_t work_bytes, void *stream);
+int ss_noise_mix_packed(const float *x, size_t n_clips, const int64_t *sample_offsets, size_t total_samples, const float *bank,
+                        size_t n_noise, const int64_t *noise_offsets, size_t total_noise, uint64_t *rng, size_t clip_base, float prob,
+                        float snr_lo_db, float snr_hi_db, float gain_lo_db, float gain_hi_db, float *out, ss_noise_plan_row *plan);
+int ss_noise_mix_packed_i16_device(const int16_t *d_x, float x_scale, size_t n_clips, const int64_t *d_sample_offsets,
+                                   size_t total_samples, const int16_t *d_bank, float noise_scale, size_t n_noise,
+                                   const int64_t *d_noise_offsets, size_t total_noise, uint64_t *d_rng, size_t clip_base, float prob,
+                                   float snr_lo_db, float snr_hi_db, float gain_lo_db, float gain_hi_db, float *d_out,
+                                   ss_noise_plan_row *d_plan, void *d_work, size_t work_bytes, void *stream);
+int ss_noise_mix_packed_i16(const int16_t *x, float x_scale, size_t n_clips, const int64_t *sample_offsets, size_t total_samples,
+                            const int16_t *bank, float noise_scale, size_t n_noise, const int64_t *noise_offsets, size_t total_noise,
+                            uint64_t *rng, size_t clip_base, float prob, float snr_lo_db, float snr_hi_db, float gain_lo_db,
+                            float gain_hi_db, float *out, ss_noise_plan_row *plan);
+
 /* ---- polyphase windowed-sinc resampling ahead of the feature calls ----
  * Every call above takes audio at the rate its ss_params was built for; these calls bring telephony (8 kHz), capture (48 kHz) and
  * corpus (44.1 kHz) audio to it on the device, on the packed layout and the stream pools of the feature calls, from floats or 16-bit

@@ -787,6 +787,94 @@ inline std::vector<float> spec_augment_packed(const std::vector<float> &vec, con
     return out;
 }
 
+// Additive noise at a drawn SNR and gain perturbation of packed clips (ss_noise_*): with probability prob a clip gets a segment of a
+// drawn clip of the bank at an SNR drawn from snr_db, and every clip a gain drawn from gain_db; the draws are Philox4x32-10 of rng =
+// {seed, epoch} and clip_base + b.  The plan rows are ss_noise_plan_row of the C header.
+using NoisePlanRow = ss_noise_plan_row;
+static_assert(sizeof(NoisePlanRow) == 40 && alignof(NoisePlanRow) == 8, "ss_noise_plan_row is 40 bytes, 8-byte aligned");
+struct NoisePolicy {
+    float prob = 1.0f;
+    float snr_lo_db = 10.0f, snr_hi_db = 30.0f;
+    float gain_lo_db = 0.0f, gain_hi_db = 0.0f;
+    size_t clip_base = 0;
+};
+
+// the draw fields of the plan noise_mix_packed writes (gains and energies 0): host only, no device
+inline std::vector<NoisePlanRow> noise_draws(const uint64_t (&rng)[2], const std::vector<int64_t> &sample_offsets, size_t total_samples,
+                                             const std::vector<int64_t> &noise_offsets, size_t total_noise, const NoisePolicy &policy = NoisePolicy())
+{
+    if (sample_offsets.empty() || noise_offsets.empty()) throw Error(SS_ERR_ARG, "noise_draws: shape mismatch");
+    std::vector<NoisePlanRow> plan(sample_offsets.size() - 1);
+    check(ss_noise_draws(rng, policy.clip_base, plan.size(), sample_offsets.data(), total_samples, noise_offsets.size() - 1, noise_offsets.data(), total_noise,
+                         policy.prob, policy.snr_lo_db, policy.snr_hi_db, policy.gain_lo_db, policy.gain_hi_db, plan.data()));
+    return plan;
+}
+
+// bytes of the caller-owned scratch of the device plan and mix forms
+inline size_t noise_mix_work_bytes(size_t n_clips, size_t total_samples)
+{
+    size_t n = 0;
+    check(ss_noise_mix_work_bytes(n_clips, total_samples, &n));
+    return n;
+}
+
+// the mix alone, on any plan table: out[i] = fma(noise_gain, noise[(start + i) mod N], speech_gain * x[i])
+inline std::vector<float> noise_apply_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, const std::vector<float> &bank,
+                                             const std::vector<int64_t> &noise_offsets, const std::vector<NoisePlanRow> &plan)
+{
+    if (sample_offsets.empty() || noise_offsets.empty() || plan.size() != sample_offsets.size() - 1) throw Error(SS_ERR_ARG, "noise_apply_packed: shape mismatch");
+    std::vector<float> out(x);
+    if (!x.empty())
+        check(ss_noise_apply_packed(x.data(), plan.size(), sample_offsets.data(), x.size(), bank.data(), noise_offsets.size() - 1, noise_offsets.data(),
+                                    bank.size(), plan.data(), out.data()));
+    return out;
+}
+
+// ... on 16-bit PCM: a sample is pcm * scale, both scales powers of two; out is float
+inline std::vector<float> noise_apply_packed_i16(const std::vector<int16_t> &x, float x_scale, const std::vector<int64_t> &sample_offsets,
+                                                 const std::vector<int16_t> &bank, float noise_scale, const std::vector<int64_t> &noise_offsets,
+                                                 const std::vector<NoisePlanRow> &plan)
+{
+    if (sample_offsets.empty() || noise_offsets.empty() || plan.size() != sample_offsets.size() - 1)
+        throw Error(SS_ERR_ARG, "noise_apply_packed_i16: shape mismatch");
+    std::vector<float> out(x.size());
+    for (size_t i = 0; i < x.size(); ++i) out[i] = static_cast<float>(x[i]) * x_scale;  // samples in no clip: the converted signal
+    if (!x.empty())
+        check(ss_noise_apply_packed_i16(x.data(), x_scale, plan.size(), sample_offsets.data(), x.size(), bank.data(), noise_scale, noise_offsets.size() - 1,
+                                        noise_offsets.data(), bank.size(), plan.data(), out.data()));
+    return out;
+}
+
+// plan + apply; rng[1] (the epoch) is advanced by one and `plan` receives the table that was applied
+inline std::vector<float> noise_mix_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, const std::vector<float> &bank,
+                                           const std::vector<int64_t> &noise_offsets, uint64_t (&rng)[2], std::vector<NoisePlanRow> &plan,
+                                           const NoisePolicy &policy = NoisePolicy())
+{
+    if (sample_offsets.empty() || noise_offsets.empty()) throw Error(SS_ERR_ARG, "noise_mix_packed: shape mismatch");
+    std::vector<float> out(x);
+    plan.assign(sample_offsets.size() - 1, NoisePlanRow{});
+    if (!x.empty())
+        check(ss_noise_mix_packed(x.data(), plan.size(), sample_offsets.data(), x.size(), bank.data(), noise_offsets.size() - 1, noise_offsets.data(),
+                                  bank.size(), rng, policy.clip_base, policy.prob, policy.snr_lo_db, policy.snr_hi_db, policy.gain_lo_db, policy.gain_hi_db,
+                                  out.data(), plan.data()));
+    return out;
+}
+
+inline std::vector<float> noise_mix_packed_i16(const std::vector<int16_t> &x, float x_scale, const std::vector<int64_t> &sample_offsets,
+                                               const std::vector<int16_t> &bank, float noise_scale, const std::vector<int64_t> &noise_offsets,
+                                               uint64_t (&rng)[2], std::vector<NoisePlanRow> &plan, const NoisePolicy &policy = NoisePolicy())
+{
+    if (sample_offsets.empty() || noise_offsets.empty()) throw Error(SS_ERR_ARG, "noise_mix_packed_i16: shape mismatch");
+    std::vector<float> out(x.size());
+    for (size_t i = 0; i < x.size(); ++i) out[i] = static_cast<float>(x[i]) * x_scale;
+    plan.assign(sample_offsets.size() - 1, NoisePlanRow{});
+    if (!x.empty())
+        check(ss_noise_mix_packed_i16(x.data(), x_scale, plan.size(), sample_offsets.data(), x.size(), bank.data(), noise_scale, noise_offsets.size() - 1,
+                                      noise_offsets.data(), bank.size(), rng, policy.clip_base, policy.prob, policy.snr_lo_db, policy.snr_hi_db,
+                                      policy.gain_lo_db, policy.gain_hi_db, out.data(), plan.data()));
+    return out;
+}
+
 inline std::vector<float> cmvnw_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t win_size = 301,
                                        bool variance_normalization = false)
 {

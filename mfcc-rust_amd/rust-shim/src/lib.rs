@@ -235,6 +235,46 @@ extern "C" {
     fn ss_specaug_packed(vec: *const f32, n_clips: usize, row_offsets: *const i64, total_rows: usize, cols: usize, rng: *mut u64,
                          clip_base: usize, n_time: usize, max_time_width: usize, time_ratio: f32, n_freq: usize, max_freq_width: usize,
                          mask_value: f32, out: *mut f32, spans: *mut i32) -> c_int;
+    fn ss_noise_draws(rng: *const u64, clip_base: usize, n_clips: usize, sample_offsets: *const i64, total_samples: usize, n_noise: usize,
+                      noise_offsets: *const i64, total_noise: usize, prob: f32, snr_lo_db: f32, snr_hi_db: f32, gain_lo_db: f32, gain_hi_db: f32,
+                      plan: *mut NoisePlanRow) -> c_int;
+    fn ss_noise_mix_work_bytes(n_clips: usize, total_samples: usize, bytes: *mut usize) -> c_int;
+    fn ss_noise_plan_packed_device(d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize, d_bank: *const f32,
+                                   n_noise: usize, d_noise_offsets: *const i64, total_noise: usize, d_rng: *const u64, clip_base: usize, prob: f32,
+                                   snr_lo_db: f32, snr_hi_db: f32, gain_lo_db: f32, gain_hi_db: f32, d_plan: *mut NoisePlanRow, d_work: *mut c_void,
+                                   work_bytes: usize, stream: *mut c_void) -> c_int;
+    fn ss_noise_plan_packed_i16_device(d_x: *const i16, x_scale: f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize,
+                                       d_bank: *const i16, noise_scale: f32, n_noise: usize, d_noise_offsets: *const i64, total_noise: usize,
+                                       d_rng: *const u64, clip_base: usize, prob: f32, snr_lo_db: f32, snr_hi_db: f32, gain_lo_db: f32,
+                                       gain_hi_db: f32, d_plan: *mut NoisePlanRow, d_work: *mut c_void, work_bytes: usize,
+                                       stream: *mut c_void) -> c_int;
+    fn ss_noise_apply_packed_device(d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize, d_bank: *const f32,
+                                    n_noise: usize, d_noise_offsets: *const i64, total_noise: usize, d_plan: *const NoisePlanRow, d_out: *mut f32,
+                                    stream: *mut c_void) -> c_int;
+    fn ss_noise_apply_packed(x: *const f32, n_clips: usize, sample_offsets: *const i64, total_samples: usize, bank: *const f32, n_noise: usize,
+                             noise_offsets: *const i64, total_noise: usize, plan: *const NoisePlanRow, out: *mut f32) -> c_int;
+    fn ss_noise_apply_packed_i16_device(d_x: *const i16, x_scale: f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize,
+                                        d_bank: *const i16, noise_scale: f32, n_noise: usize, d_noise_offsets: *const i64, total_noise: usize,
+                                        d_plan: *const NoisePlanRow, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_noise_apply_packed_i16(x: *const i16, x_scale: f32, n_clips: usize, sample_offsets: *const i64, total_samples: usize, bank: *const i16,
+                                 noise_scale: f32, n_noise: usize, noise_offsets: *const i64, total_noise: usize, plan: *const NoisePlanRow,
+                                 out: *mut f32) -> c_int;
+    fn ss_noise_mix_packed_device(d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize, d_bank: *const f32,
+                                  n_noise: usize, d_noise_offsets: *const i64, total_noise: usize, d_rng: *mut u64, clip_base: usize, prob: f32,
+                                  snr_lo_db: f32, snr_hi_db: f32, gain_lo_db: f32, gain_hi_db: f32, d_out: *mut f32, d_plan: *mut NoisePlanRow,
+                                  d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+    fn ss_noise_mix_packed(x: *const f32, n_clips: usize, sample_offsets: *const i64, total_samples: usize, bank: *const f32, n_noise: usize,
+                           noise_offsets: *const i64, total_noise: usize, rng: *mut u64, clip_base: usize, prob: f32, snr_lo_db: f32,
+                           snr_hi_db: f32, gain_lo_db: f32, gain_hi_db: f32, out: *mut f32, plan: *mut NoisePlanRow) -> c_int;
+    fn ss_noise_mix_packed_i16_device(d_x: *const i16, x_scale: f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize,
+                                      d_bank: *const i16, noise_scale: f32, n_noise: usize, d_noise_offsets: *const i64, total_noise: usize,
+                                      d_rng: *mut u64, clip_base: usize, prob: f32, snr_lo_db: f32, snr_hi_db: f32, gain_lo_db: f32,
+                                      gain_hi_db: f32, d_out: *mut f32, d_plan: *mut NoisePlanRow, d_work: *mut c_void, work_bytes: usize,
+                                      stream: *mut c_void) -> c_int;
+    fn ss_noise_mix_packed_i16(x: *const i16, x_scale: f32, n_clips: usize, sample_offsets: *const i64, total_samples: usize, bank: *const i16,
+                               noise_scale: f32, n_noise: usize, noise_offsets: *const i64, total_noise: usize, rng: *mut u64, clip_base: usize,
+                               prob: f32, snr_lo_db: f32, snr_hi_db: f32, gain_lo_db: f32, gain_hi_db: f32, out: *mut f32,
+                               plan: *mut NoisePlanRow) -> c_int;
     fn ss_resample_packed_offsets(orig_rate: u32, new_rate: u32, n_clips: usize, sample_offsets: *const i64, out_offsets: *mut i64) -> c_int;
     fn ss_resampler_create(orig_rate: u32, new_rate: u32, lowpass_filter_width: u32, rolloff: f32, out: *mut *mut c_void) -> c_int;
     fn ss_resampler_destroy(rs: *mut c_void);
@@ -1589,6 +1629,212 @@ pub unsafe fn spec_augment_packed_device(d_vec: *const f32, n_clips: usize, d_ro
                                          stream: *mut c_void) -> Result<(), Error> {
     check(ss_specaug_packed_device(d_vec, n_clips, d_row_offsets, total_rows, cols, d_rng, policy.clip_base, policy.n_time, policy.max_time_width,
                                    policy.time_ratio, policy.n_freq, policy.max_freq_width, policy.mask_value, d_out, d_spans, stream))
+}
+
+/// One row of a noise-mix plan (`ss_noise_plan_row`): 40 bytes, 8-byte aligned.  `noise_clip` is the bank's clip, -1 for a clip that is
+/// not mixed and -2 for a bad speech segment; the gains are what the mix multiplies by, the energies the f64 sums they were formed from.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct NoisePlanRow {
+    pub noise_clip: i32,
+    pub start: i32,
+    pub snr_db: f32,
+    pub gain_db: f32,
+    pub speech_gain: f32,
+    pub noise_gain: f32,
+    pub speech_energy: f64,
+    pub noise_energy: f64,
+}
+
+/// The draws of one noise-mix call: a clip is mixed with probability `prob` at an SNR drawn from `snr_db` and scaled by a gain drawn
+/// from `gain_db` (both `(low, high)` in dB; `(0, 0)`: no gain perturbation).  `clip_base` is the id of clip 0.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct NoisePolicy {
+    pub prob: f32,
+    pub snr_db: (f32, f32),
+    pub gain_db: (f32, f32),
+    pub clip_base: usize,
+}
+
+impl Default for NoisePolicy {
+    fn default() -> Self {
+        NoisePolicy { prob: 1.0, snr_db: (10.0, 30.0), gain_db: (0.0, 0.0), clip_base: 0 }
+    }
+}
+
+fn noise_tables_ok(sample_offsets: &[i64], noise_offsets: &[i64], what: &str) -> Result<(), Error> {
+    if sample_offsets.is_empty() || noise_offsets.is_empty() {
+        return Err(Error { status: SS_ERR_ARG, detail: format!("{}: an offset table has n + 1 entries", what) });
+    }
+    Ok(())
+}
+
+/// The draw fields `try_noise_mix_packed` writes for `rng = [seed, epoch]`, computed on the host (no device); gains and energies are 0.
+pub fn try_noise_draws(rng: [u64; 2], sample_offsets: &[i64], total_samples: usize, noise_offsets: &[i64], total_noise: usize,
+                       policy: &NoisePolicy) -> Result<Vec<NoisePlanRow>, Error> {
+    noise_tables_ok(sample_offsets, noise_offsets, "noise_draws")?;
+    let mut plan = vec![NoisePlanRow::default(); sample_offsets.len() - 1];
+    check(unsafe {
+        ss_noise_draws(rng.as_ptr(), policy.clip_base, plan.len(), sample_offsets.as_ptr(), total_samples, noise_offsets.len() - 1,
+                       noise_offsets.as_ptr(), total_noise, policy.prob, policy.snr_db.0, policy.snr_db.1, policy.gain_db.0, policy.gain_db.1,
+                       plan.as_mut_ptr())
+    })?;
+    Ok(plan)
+}
+
+/// Bytes of the caller-owned scratch of the device plan and mix forms.
+pub fn try_noise_mix_work_bytes(n_clips: usize, total_samples: usize) -> Result<usize, Error> {
+    let mut n = 0usize;
+    check(unsafe { ss_noise_mix_work_bytes(n_clips, total_samples, &mut n) })?;
+    Ok(n)
+}
+
+/// The mix alone on any plan table: `out[i] = fma(noise_gain, noise[(start + i) mod N], speech_gain * x[i])` of every clip.
+pub fn try_noise_apply_packed(x: &[f32], sample_offsets: &[i64], bank: &[f32], noise_offsets: &[i64],
+                              plan: &[NoisePlanRow]) -> Result<Vec<f32>, Error> {
+    noise_tables_ok(sample_offsets, noise_offsets, "noise_apply_packed")?;
+    if plan.len() != sample_offsets.len() - 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "noise_apply_packed: the plan holds one row per clip".to_string() });
+    }
+    let mut out = x.to_vec();
+    if !x.is_empty() {
+        check(unsafe {
+            ss_noise_apply_packed(x.as_ptr(), plan.len(), sample_offsets.as_ptr(), x.len(), bank.as_ptr(), noise_offsets.len() - 1,
+                                  noise_offsets.as_ptr(), bank.len(), plan.as_ptr(), out.as_mut_ptr())
+        })?;
+    }
+    Ok(out)
+}
+
+/// As `try_noise_apply_packed` on 16-bit PCM: a sample is `pcm * scale`, both scales powers of two; the output is float.
+pub fn try_noise_apply_packed_i16(x: &[i16], x_scale: f32, sample_offsets: &[i64], bank: &[i16], noise_scale: f32, noise_offsets: &[i64],
+                                  plan: &[NoisePlanRow]) -> Result<Vec<f32>, Error> {
+    noise_tables_ok(sample_offsets, noise_offsets, "noise_apply_packed_i16")?;
+    if plan.len() != sample_offsets.len() - 1 {
+        return Err(Error { status: SS_ERR_ARG, detail: "noise_apply_packed_i16: the plan holds one row per clip".to_string() });
+    }
+    let mut out: Vec<f32> = x.iter().map(|&v| v as f32 * x_scale).collect();
+    if !x.is_empty() {
+        check(unsafe {
+            ss_noise_apply_packed_i16(x.as_ptr(), x_scale, plan.len(), sample_offsets.as_ptr(), x.len(), bank.as_ptr(), noise_scale,
+                                      noise_offsets.len() - 1, noise_offsets.as_ptr(), bank.len(), plan.as_ptr(), out.as_mut_ptr())
+        })?;
+    }
+    Ok(out)
+}
+
+/// Additive noise at a drawn SNR and gain perturbation of every clip of a packed signal: the mixed samples and the plan that was
+/// applied.  `rng = [seed, epoch]`; the call advances `rng[1]` by one, so the next call draws other noise.
+pub fn try_noise_mix_packed(x: &[f32], sample_offsets: &[i64], bank: &[f32], noise_offsets: &[i64], rng: &mut [u64; 2],
+                            policy: &NoisePolicy) -> Result<(Vec<f32>, Vec<NoisePlanRow>), Error> {
+    noise_tables_ok(sample_offsets, noise_offsets, "noise_mix_packed")?;
+    let mut out = x.to_vec();
+    let mut plan = vec![NoisePlanRow::default(); sample_offsets.len() - 1];
+    if !x.is_empty() {
+        check(unsafe {
+            ss_noise_mix_packed(x.as_ptr(), plan.len(), sample_offsets.as_ptr(), x.len(), bank.as_ptr(), noise_offsets.len() - 1,
+                                noise_offsets.as_ptr(), bank.len(), rng.as_mut_ptr(), policy.clip_base, policy.prob, policy.snr_db.0,
+                                policy.snr_db.1, policy.gain_db.0, policy.gain_db.1, out.as_mut_ptr(), plan.as_mut_ptr())
+        })?;
+    }
+    Ok((out, plan))
+}
+
+/// As `try_noise_mix_packed` on 16-bit PCM (see `try_noise_apply_packed_i16`).
+pub fn try_noise_mix_packed_i16(x: &[i16], x_scale: f32, sample_offsets: &[i64], bank: &[i16], noise_scale: f32, noise_offsets: &[i64],
+                                rng: &mut [u64; 2], policy: &NoisePolicy) -> Result<(Vec<f32>, Vec<NoisePlanRow>), Error> {
+    noise_tables_ok(sample_offsets, noise_offsets, "noise_mix_packed_i16")?;
+    let mut out: Vec<f32> = x.iter().map(|&v| v as f32 * x_scale).collect();
+    let mut plan = vec![NoisePlanRow::default(); sample_offsets.len() - 1];
+    if !x.is_empty() {
+        check(unsafe {
+            ss_noise_mix_packed_i16(x.as_ptr(), x_scale, plan.len(), sample_offsets.as_ptr(), x.len(), bank.as_ptr(), noise_scale,
+                                    noise_offsets.len() - 1, noise_offsets.as_ptr(), bank.len(), rng.as_mut_ptr(), policy.clip_base, policy.prob,
+                                    policy.snr_db.0, policy.snr_db.1, policy.gain_db.0, policy.gain_db.1, out.as_mut_ptr(), plan.as_mut_ptr())
+        })?;
+    }
+    Ok((out, plan))
+}
+
+/// The device tables of a noise-mix call: packed speech (`total_samples` samples, `n_clips + 1` offsets) and the bank.
+#[derive(Clone, Copy, Debug)]
+pub struct NoiseDeviceBlocks<T> {
+    pub d_x: *const T,
+    pub n_clips: usize,
+    pub d_sample_offsets: *const i64,
+    pub total_samples: usize,
+    pub d_bank: *const T,
+    pub n_noise: usize,
+    pub d_noise_offsets: *const i64,
+    pub total_noise: usize,
+}
+
+/// Draws, energies and gains into `d_plan` (include/speechsauce_amd.h has the contract); the epoch is not touched.
+///
+/// # Safety
+/// As `vad_energy_packed_device`; `d_rng` is the 16-byte device block `{seed, epoch}`, `d_plan` holds `n_clips` rows and `d_work`
+/// `work_bytes >= try_noise_mix_work_bytes(n_clips, total_samples)` bytes, 8-byte aligned.
+pub unsafe fn noise_plan_packed_device(b: &NoiseDeviceBlocks<f32>, d_rng: *const u64, policy: &NoisePolicy, d_plan: *mut NoisePlanRow,
+                                       d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_noise_plan_packed_device(b.d_x, b.n_clips, b.d_sample_offsets, b.total_samples, b.d_bank, b.n_noise, b.d_noise_offsets, b.total_noise,
+                                      d_rng, policy.clip_base, policy.prob, policy.snr_db.0, policy.snr_db.1, policy.gain_db.0, policy.gain_db.1,
+                                      d_plan, d_work, work_bytes, stream))
+}
+
+/// As `noise_plan_packed_device` on 16-bit PCM.
+///
+/// # Safety
+/// As `noise_plan_packed_device`.
+pub unsafe fn noise_plan_packed_i16_device(b: &NoiseDeviceBlocks<i16>, x_scale: f32, noise_scale: f32, d_rng: *const u64, policy: &NoisePolicy,
+                                           d_plan: *mut NoisePlanRow, d_work: *mut c_void, work_bytes: usize,
+                                           stream: *mut c_void) -> Result<(), Error> {
+    check(ss_noise_plan_packed_i16_device(b.d_x, x_scale, b.n_clips, b.d_sample_offsets, b.total_samples, b.d_bank, noise_scale, b.n_noise,
+                                          b.d_noise_offsets, b.total_noise, d_rng, policy.clip_base, policy.prob, policy.snr_db.0, policy.snr_db.1,
+                                          policy.gain_db.0, policy.gain_db.1, d_plan, d_work, work_bytes, stream))
+}
+
+/// The mix alone, on any plan table; `d_out == d_x` mixes in place.
+///
+/// # Safety
+/// As `noise_plan_packed_device`; `d_out` holds `total_samples` floats and is `d_x` itself or does not overlap it.
+pub unsafe fn noise_apply_packed_device(b: &NoiseDeviceBlocks<f32>, d_plan: *const NoisePlanRow, d_out: *mut f32,
+                                        stream: *mut c_void) -> Result<(), Error> {
+    check(ss_noise_apply_packed_device(b.d_x, b.n_clips, b.d_sample_offsets, b.total_samples, b.d_bank, b.n_noise, b.d_noise_offsets, b.total_noise,
+                                       d_plan, d_out, stream))
+}
+
+/// As `noise_apply_packed_device` on 16-bit PCM; `d_out` is float and overlaps nothing.
+///
+/// # Safety
+/// As `noise_apply_packed_device`.
+pub unsafe fn noise_apply_packed_i16_device(b: &NoiseDeviceBlocks<i16>, x_scale: f32, noise_scale: f32, d_plan: *const NoisePlanRow,
+                                            d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+    check(ss_noise_apply_packed_i16_device(b.d_x, x_scale, b.n_clips, b.d_sample_offsets, b.total_samples, b.d_bank, noise_scale, b.n_noise,
+                                           b.d_noise_offsets, b.total_noise, d_plan, d_out, stream))
+}
+
+/// Plan, apply and the epoch bump: three asynchronous launches on `stream`, nothing read back; replays of a captured graph draw fresh noise.
+///
+/// # Safety
+/// As `noise_apply_packed_device` and `noise_plan_packed_device`; one `d_rng` block serves one stream of calls.
+pub unsafe fn noise_mix_packed_device(b: &NoiseDeviceBlocks<f32>, d_rng: *mut u64, policy: &NoisePolicy, d_out: *mut f32,
+                                      d_plan: *mut NoisePlanRow, d_work: *mut c_void, work_bytes: usize,
+                                      stream: *mut c_void) -> Result<(), Error> {
+    check(ss_noise_mix_packed_device(b.d_x, b.n_clips, b.d_sample_offsets, b.total_samples, b.d_bank, b.n_noise, b.d_noise_offsets, b.total_noise,
+                                     d_rng, policy.clip_base, policy.prob, policy.snr_db.0, policy.snr_db.1, policy.gain_db.0, policy.gain_db.1, d_out,
+                                     d_plan, d_work, work_bytes, stream))
+}
+
+/// As `noise_mix_packed_device` on 16-bit PCM.
+///
+/// # Safety
+/// As `noise_mix_packed_device`.
+pub unsafe fn noise_mix_packed_i16_device(b: &NoiseDeviceBlocks<i16>, x_scale: f32, noise_scale: f32, d_rng: *mut u64, policy: &NoisePolicy,
+                                          d_out: *mut f32, d_plan: *mut NoisePlanRow, d_work: *mut c_void, work_bytes: usize,
+                                          stream: *mut c_void) -> Result<(), Error> {
+    check(ss_noise_mix_packed_i16_device(b.d_x, x_scale, b.n_clips, b.d_sample_offsets, b.total_samples, b.d_bank, noise_scale, b.n_noise,
+                                         b.d_noise_offsets, b.total_noise, d_rng, policy.clip_base, policy.prob, policy.snr_db.0, policy.snr_db.1,
+                                         policy.gain_db.0, policy.gain_db.1, d_out, d_plan, d_work, work_bytes, stream))
 }
 
 /// librosa's power_to_db of every clip of a packed block with the clip's own `top_db` floor (`None`: no floor); clip b's segment

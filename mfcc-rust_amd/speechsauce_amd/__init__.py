@@ -33,6 +33,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "vad_energy", "vad_energy_packed", "select_rows", "select_rows_packed", "VadEnergyStreamPool",
            "pad", "pad_packed",
            "spec_augment_spans", "mask_spans_packed", "spec_augment_packed", "SpecAugment",
+           "NOISE_PLAN_DTYPE", "noise_plan_rows", "noise_draws", "noise_plan_packed", "noise_apply_packed", "noise_mix_packed", "NoiseMix",
            "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "KaldiFbankStreamPool", "KaldiMfccStreamPool",
@@ -2829,6 +2830,296 @@ class SpecAugment:
 
     def __call__(self, rows, row_offsets, **kwargs):
         return spec_augment_packed(rows, row_offsets, self, **kwargs)
+
+
+# ---- additive noise at a drawn SNR and gain perturbation of packed clips, seeded on the device (ss_noise_*) --------------------
+# A clip's plan row is a function of (seed, epoch, clip_base + b), its own samples, the bank and the scalars; the mix is a function
+# of the row.  The generator block is SpecAugment's: one seed may serve both stages (the counter words differ).
+
+#: ``ss_noise_plan_row``: one row per clip of the plan tables below (40 bytes)
+NOISE_PLAN_DTYPE = np.dtype([("noise_clip", np.int32), ("start", np.int32), ("snr_db", np.float32), ("gain_db", np.float32),
+                             ("speech_gain", np.float32), ("noise_gain", np.float32), ("speech_energy", np.float64), ("noise_energy", np.float64)])
+
+
+def noise_plan_rows(plan):
+    """A plan table as a numpy record array of ``NOISE_PLAN_DTYPE``: a device plan (int64 ``[n_clips, 5]``, the 40-byte rows as
+    they lie in memory) is read back (a synchronisation); a host plan is returned as it is."""
+    if _is_torch(plan):
+        return plan.detach().cpu().contiguous().numpy().reshape(-1).view(NOISE_PLAN_DTYPE)
+    return np.ascontiguousarray(plan).reshape(-1).view(NOISE_PLAN_DTYPE)
+
+
+class _NoiseBank:
+    """The noise bank of one call, or of a ``NoiseMix``: packed samples (float32, or int16 with its scale), the offset table and
+    the counts; with ``device`` both live there."""
+
+    def __init__(self, bank, bank_lengths, noise_pcm_scale, what, device=None):
+        nz, self.scale = _require_signal(bank, (1,), what, noise_pcm_scale)
+        self.total = int(nz.shape[0])
+        table = _sample_offsets(bank_lengths, self.total, what)
+        self.n_noise = table.size - 1
+        if device is not None or _is_torch(nz):
+            import torch
+
+            device = nz.device if device is None else torch.device(device)
+            self.nz = (nz if _is_torch(nz) else torch.from_numpy(np.ascontiguousarray(nz))).to(device).contiguous()
+            self.table = torch.from_numpy(table).to(device)
+        else:
+            self.nz, self.table = np.ascontiguousarray(nz), table
+        self.on_device = _is_torch(self.nz)
+
+    def args(self, on_device, scale, what):
+        """the bank's part of a call's argument list, for a signal on the device or not, float or PCM (``scale``)"""
+        if (scale is None) != (self.scale is None):
+            raise ValueError(f"{what}: the signal and the bank must both be float32 or both int16 PCM (pcm_scale and noise_pcm_scale)")
+        if on_device != self.on_device:
+            raise ValueError(f"{what}: the signal and the bank must both be on the device or both on the host")
+        sc = [] if scale is None else [self.scale]
+        if on_device:
+            return [self.nz if self.total else None, *sc, self.n_noise, self.table, self.total]
+        return [self.nz.ctypes.data if self.total else None, *sc, self.n_noise, self.table.ctypes.data, self.total]
+
+
+def _noise_scalars(prob, snr_db, gain_db, clip_base, what):
+    try:
+        (snr_lo, snr_hi), (gain_lo, gain_hi) = (tuple(float(np.float32(v)) for v in pair) for pair in (snr_db, gain_db))
+    except (TypeError, ValueError):
+        raise TypeError(f"{what}: snr_db and gain_db must be (low, high) pairs of numbers") from None
+    prob, base = float(prob), int(clip_base)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"{what}: prob must lie in [0, 1]")
+    for name, lo, hi in (("snr_db", snr_lo, snr_hi), ("gain_db", gain_lo, gain_hi)):
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+            raise ValueError(f"{what}: {name} must be a finite (low, high) pair with low <= high")
+    if not 0 <= base <= 1 << 32:
+        raise ValueError(f"{what}: clip_base must lie in 0 .. 2^32")
+    return base, [prob, snr_lo, snr_hi, gain_lo, gain_hi]
+
+
+def _noise_rng(rng):
+    return rng.rng if isinstance(rng, NoiseMix) else rng
+
+
+def noise_draws(rng, lengths, bank_lengths, prob=1.0, snr_db=(10, 30), gain_db=(0, 0), clip_base=0, *, sample_offsets=None, noise_offsets=None,
+                total_samples=None, total_noise=None):
+    """The draw fields ``noise_mix_packed`` writes, computed on the host (no device): a record array of ``NOISE_PLAN_DTYPE`` whose
+    ``noise_clip``, ``start``, ``snr_db`` and ``gain_db`` are those of the device plan (the gains and energies are 0).  ``rng`` is
+    a ``(seed, epoch)`` pair, a uint64 array of two, a ``SpecAugment`` or a ``NoiseMix`` (read back).  ``sample_offsets`` /
+    ``noise_offsets`` (with ``lengths`` / ``bank_lengths`` None) are offset tables taken as they stand, with ``total_samples`` /
+    ``total_noise`` (default: the table's last entry): a bad speech segment has ``noise_clip == -2``, as on the device."""
+    what = "noise_draws"
+    base, scalars = _noise_scalars(prob, snr_db, gain_db, clip_base, what)
+    words = _rng_words(_noise_rng(rng), what)
+    tables = []
+    for lens, off, total in ((lengths, sample_offsets, total_samples), (bank_lengths, noise_offsets, total_noise)):
+        if (lens is None) == (off is None):
+            raise ValueError(f"{what}: give lengths or an offset table, not both")
+        off = _sample_offsets(lens, 1 << 62, what) if off is None else np.ascontiguousarray(off.cpu().numpy() if _is_torch(off) else off, dtype=np.int64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError(f"{what}: an offset table has n + 1 entries")
+        tables.append((off, max(int(off[-1]), 0) if total is None else int(total)))
+    (so, total), (no, ntotal) = tables
+    plan = np.zeros(so.size - 1, NOISE_PLAN_DTYPE)
+    if plan.size:
+        _lib.check(_lib.lib().ss_noise_draws(words.ctypes.data, base, plan.size, so.ctypes.data, total, no.size - 1, no.ctypes.data, ntotal, *scalars,
+                                             plan.ctypes.data))
+    return plan
+
+
+def _noise_signal(signal, lengths, pcm_scale, device_tables, what):
+    """-> (x, scale, on_device, total_samples, table, n_clips) of a noise call"""
+    x, scale = _require_signal(signal, (1,), what, pcm_scale)
+    on_device, total = _is_torch(x), int(x.shape[0])
+    if device_tables is not None:
+        import torch
+
+        t = device_tables[0] if isinstance(device_tables, (tuple, list)) else device_tables
+        if lengths is not None or not on_device:
+            raise ValueError(f"{what}: device_tables go with lengths=None and a device signal")
+        if not (_is_torch(t) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous() and t.device == x.device and t.numel() >= 1):
+            raise TypeError(f"{what}: device_tables is the sample offsets, a contiguous 1-D int64 tensor of n_clips + 1 entries on the signal's device")
+        return x.contiguous(), scale, True, total, t, t.numel() - 1
+    table = _sample_offsets(lengths, total, what)
+    return (x.contiguous() if on_device else np.ascontiguousarray(x)), scale, on_device, total, table, table.size - 1
+
+
+def _noise_out(x, scale, on_device, out, what):
+    if on_device:
+        import torch
+
+        if out is None:
+            return torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        if not (_is_torch(out) and out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape):
+            raise ValueError(f"{what}: out must be a contiguous float32 device tensor of the signal's shape")
+        return out
+    if out is None:
+        return np.empty(x.shape, np.float32)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable and out.shape == x.shape):
+        raise ValueError(f"{what}: out must be a writable contiguous float32 array of the signal's shape")
+    return out
+
+
+def _noise_block(x, out, total, on_device):
+    """the blocks a call hands over: a signal without samples still wants a block"""
+    if total:
+        return x, out
+    if on_device:
+        import torch
+
+        return torch.zeros(1, dtype=x.dtype, device=x.device), torch.zeros(1, dtype=torch.float32, device=x.device)
+    return np.zeros(1, x.dtype), np.zeros(1, np.float32)
+
+
+def _noise_device_rng(rng, x, what):
+    import torch
+
+    rng = _noise_rng(rng)
+    block = rng._block if isinstance(rng, SpecAugment) else rng
+    if not (_is_torch(block) and block.is_cuda and block.device == x.device and block.dtype == torch.int64 and block.numel() == 2 and block.is_contiguous()):
+        raise TypeError(f"{what}: on the device rng must be a NoiseMix, a SpecAugment or a contiguous int64 tensor of two words on the signal's device")
+    return block
+
+
+def _noise_work(n, total, device, work=None):
+    import torch
+
+    need = C.c_size_t()
+    _lib.check(_lib.lib().ss_noise_mix_work_bytes(n, total, C.byref(need)))
+    if work is None or work.numel() * 8 < need.value or work.device != device:
+        work = torch.empty(max(need.value // 8, 1), dtype=torch.float64, device=device)
+    return work
+
+
+def _noise_plan_or_mix(what, mix, signal, lengths, bank, rng, prob, snr_db, gain_db, clip_base, pcm_scale, out, device_tables, work=None):
+    base, scalars = _noise_scalars(prob, snr_db, gain_db, clip_base, what)
+    x, scale, on_device, total, table, n = _noise_signal(signal, lengths, pcm_scale, device_tables, what)
+    bank_args = bank.args(on_device, scale, what)
+    if mix:
+        out = _noise_out(x, scale, on_device, out, what)
+    lib, i16, sc = _lib.lib(), "" if scale is None else "_i16", [] if scale is None else [scale]
+    if on_device:
+        import torch
+
+        block = _noise_device_rng(rng, x, what)
+        plan = torch.zeros((n, 5), dtype=torch.int64, device=x.device)
+        if n:
+            work = _noise_work(n, total, x.device, work)
+            xin, xout = _noise_block(x, out, total, True)
+            outs = [xout.data_ptr()] if mix else []
+            _launch(x.device, getattr(lib, f"ss_noise_{'mix' if mix else 'plan'}_packed{i16}_device"), xin, *sc, n, table, total, *bank_args, block.data_ptr(),
+                    base, *scalars, *outs, plan.data_ptr(), work.data_ptr(), work.numel() * 8)
+            work.record_stream(torch.cuda.current_stream(x.device))
+        return out, plan, work
+    if not mix:
+        raise TypeError(f"{what}: the plan alone is a device call; numpy input is served by noise_draws and noise_mix_packed")
+    words = _rng_words(_noise_rng(rng), what)
+    plan = np.zeros(n, NOISE_PLAN_DTYPE)
+    if n:
+        xin, xout = _noise_block(x, out, total, False)
+        _lib.check(getattr(lib, f"ss_noise_mix_packed{i16}")(xin.ctypes.data, *sc, n, table.ctypes.data, total, *bank_args, words.ctypes.data, base, *scalars,
+                                                           xout.ctypes.data, plan.ctypes.data))
+        rng = _noise_rng(rng)
+        if isinstance(rng, SpecAugment):
+            rng.epoch = int(words[1])
+        elif isinstance(rng, np.ndarray) and rng is not words:
+            rng[1] = words[1]
+    return out, plan, None
+
+
+def noise_plan_packed(signal, lengths, bank, bank_lengths, rng, prob=1.0, snr_db=(10, 30), gain_db=(0, 0), clip_base=0, pcm_scale=None,
+                      noise_pcm_scale=None, device_tables=None):
+    """The plan of ``noise_mix_packed`` alone, on the device: draws, f64 energies and gains of every clip -> the plan table (int64
+    ``[n_clips, 5]``: 40-byte rows, see ``noise_plan_rows``).  The epoch is not advanced and nothing is mixed."""
+    what = "noise_plan_packed"
+    return _noise_plan_or_mix(what, False, signal, lengths, _NoiseBank(bank, bank_lengths, noise_pcm_scale, what), rng, prob, snr_db, gain_db, clip_base,
+                              pcm_scale, None, device_tables)[1]
+
+
+def _noise_apply(what, signal, lengths, bank, plan, pcm_scale, out, device_tables):
+    x, scale, on_device, total, table, n = _noise_signal(signal, lengths, pcm_scale, device_tables, what)
+    bank_args = bank.args(on_device, scale, what)
+    out = _noise_out(x, scale, on_device, out, what)
+    lib, i16, sc = _lib.lib(), "" if scale is None else "_i16", [] if scale is None else [scale]
+    if on_device:
+        import torch
+
+        if _is_torch(plan):
+            if plan.dtype != torch.int64:
+                raise TypeError(f"{what}: a device plan is the int64 table [n_clips, 5] the plan and mix calls return")
+            rows = plan.to(x.device).contiguous()
+        else:
+            rows = torch.from_numpy(noise_plan_rows(plan).view(np.int64).copy()).to(x.device)
+        if rows.numel() != n * 5:
+            raise ValueError(f"{what}: the plan must hold one row per clip")
+        if n:
+            xin, xout = _noise_block(x, out, total, True)
+            _launch(x.device, getattr(lib, f"ss_noise_apply_packed{i16}_device"), xin, *sc, n, table, total, *bank_args, rows, xout.data_ptr())
+        return out
+    rows = noise_plan_rows(plan)
+    if rows.size != n:
+        raise ValueError(f"{what}: the plan must hold one row per clip")
+    if n:
+        xin, xout = _noise_block(x, out, total, False)
+        _lib.check(getattr(lib, f"ss_noise_apply_packed{i16}")(xin.ctypes.data, *sc, n, table.ctypes.data, total, *bank_args, rows.ctypes.data, xout.ctypes.data))
+    return out
+
+
+def noise_apply_packed(signal, lengths, bank, bank_lengths, plan, pcm_scale=None, noise_pcm_scale=None, out=None, device_tables=None):
+    """The mix of ``noise_mix_packed`` alone, on any plan table -- the one a plan or mix call returned (one plan applied twice gives
+    equal outputs) or the caller's own record array of ``NOISE_PLAN_DTYPE`` with fixed ``speech_gain`` / ``noise_gain`` /
+    ``noise_clip`` / ``start``: ``out[i] = fma(noise_gain, noise[(start + i) mod N], speech_gain * x[i])``.  A row whose
+    ``noise_clip`` or ``start`` is out of range for the bank, or whose ``noise_gain`` is 0, is not mixed; ``noise_clip == -2``
+    leaves the clip untouched.  ``out=signal`` (float32) mixes in place."""
+    what = "noise_apply_packed"
+    return _noise_apply(what, signal, lengths, _NoiseBank(bank, bank_lengths, noise_pcm_scale, what), plan, pcm_scale, out, device_tables)
+
+
+def noise_mix_packed(signal, lengths, bank, bank_lengths, rng, prob=1.0, snr_db=(10, 30), gain_db=(0, 0), clip_base=0, pcm_scale=None,
+                     noise_pcm_scale=None, out=None, device_tables=None):
+    """Additive noise and gain perturbation of every clip of a packed 1-D signal, ahead of the front ends: -> (out, plan).  With
+    probability ``prob`` a clip gets a segment of a uniformly drawn clip of ``bank`` (packed like the signal, ``bank_lengths``), from
+    a uniformly drawn start and repeated as often as the clip needs, at an SNR drawn uniformly from ``snr_db`` (dB, measured on the
+    clip's own f64 energies); every clip is scaled by a gain drawn from ``gain_db`` (``(0, 0)``: none).  The draws are Philox4x32-10
+    keyed by ``rng``'s seed and counted by its epoch and ``clip_base + b``: a clip's noise depends on neither its place in the block
+    nor its neighbours.  The call advances the epoch by one, so the next call, or the next replay of a captured graph, draws other
+    noise.  ``plan`` is the table that was applied (``noise_plan_rows``).  ``pcm_scale`` and ``noise_pcm_scale`` (both or neither):
+    signal and bank are int16 PCM, a sample is int16 * scale (a power of two); ``out`` is float32, bit for bit the float call on
+    the converted arrays.  On the device (ROCm tensors, current stream, nothing read back) ``rng`` is a ``NoiseMix``, a
+    ``SpecAugment`` or its int64 block; for numpy input also a writable uint64 array ``[seed, epoch]``, updated in place.
+    ``device_tables``: the sample offsets as an int64 device tensor (with ``lengths=None``), used as they stand -- nothing is
+    uploaded, so a captured graph can be replayed over changed tables.  ``(out, lengths)`` go on to every packed front end."""
+    what = "noise_mix_packed"
+    out, plan, _ = _noise_plan_or_mix(what, True, signal, lengths, _NoiseBank(bank, bank_lengths, noise_pcm_scale, what), rng, prob, snr_db, gain_db,
+                                      clip_base, pcm_scale, out, device_tables)
+    return out, plan
+
+
+class NoiseMix:
+    """``noise_mix_packed`` with its state: owns the generator block (``rng``, a ``SpecAugment``: pass it on to share the seed),
+    the device copy of the noise bank and its offsets, and the scratch of the partial sums.  ``mix = NoiseMix(seed, bank,
+    bank_lengths)``; ``out, plan = mix(signal, lengths, prob=0.5, snr_db=(10, 30))`` -- every call, and every replay of a graph that
+    captured one, advances the epoch on the device."""
+
+    def __init__(self, seed, bank, bank_lengths, noise_pcm_scale=None, epoch=0, device=None):
+        self.rng = SpecAugment(seed, epoch, device)
+        self.bank = _NoiseBank(bank, bank_lengths, noise_pcm_scale, "NoiseMix", self.rng._block.device)
+        self._work = None
+
+    seed = property(lambda self: self.rng.seed)
+    epoch = property(lambda self: self.rng.epoch, lambda self, value: setattr(self.rng, "epoch", value))
+
+    def plan(self, signal, lengths, prob=1.0, snr_db=(10, 30), gain_db=(0, 0), clip_base=0, pcm_scale=None, device_tables=None):
+        _, plan, self._work = _noise_plan_or_mix("NoiseMix.plan", False, signal, lengths, self.bank, self.rng, prob, snr_db, gain_db, clip_base, pcm_scale,
+                                                 None, device_tables, self._work)
+        return plan
+
+    def apply(self, signal, lengths, plan, pcm_scale=None, out=None, device_tables=None):
+        return _noise_apply("NoiseMix.apply", signal, lengths, self.bank, plan, pcm_scale, out, device_tables)
+
+    def __call__(self, signal, lengths, prob=1.0, snr_db=(10, 30), gain_db=(0, 0), clip_base=0, pcm_scale=None, out=None, device_tables=None):
+        out, plan, self._work = _noise_plan_or_mix("NoiseMix", True, signal, lengths, self.bank, self.rng, prob, snr_db, gain_db, clip_base, pcm_scale, out,
+                                                   device_tables, self._work)
+        return out, plan
 
 
 # ---- polyphase sinc resampling ahead of the feature calls (ss_resample* in include/speechsauce_amd.h) -------------

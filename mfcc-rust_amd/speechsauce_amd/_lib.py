@@ -109,6 +109,13 @@ class SsNemoParams(C.Structure):
     ]
 
 
+class SsNoisePlanRow(C.Structure):
+    """ss_noise_plan_row (include/speechsauce_amd.h): 40 bytes, 8-byte aligned; field order is ABI."""
+
+    _fields_ = [("noise_clip", C.c_int32), ("start", C.c_int32), ("snr_db", C.c_float), ("gain_db", C.c_float), ("speech_gain", C.c_float),
+                ("noise_gain", C.c_float), ("speech_energy", C.c_double), ("noise_energy", C.c_double)]
+
+
 class SpeechSauceError(RuntimeError):
     """Raised where the reference would panic (or where HIP fails)."""
 
@@ -129,6 +136,9 @@ _kc = C.c_void_p  # ss_kaldi_config *
 _wc = C.c_void_p  # ss_whisper_config *
 _nc = C.c_void_p  # ss_nemo_config *
 _fp = C.c_void_p  # float* passed as an address (numpy .ctypes.data or a device pointer)
+# the shared head of the ss_noise_* calls: samples, n_clips, sample_offsets, total_samples, bank, n_noise, noise_offsets, total_noise
+_NOISE_F32 = [_fp, C.c_size_t, C.c_void_p, C.c_size_t, _fp, C.c_size_t, C.c_void_p, C.c_size_t]
+_NOISE_I16 = [C.c_void_p, C.c_float, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_size_t, C.c_void_p, C.c_size_t]
 PROTOTYPES = {
     "ss_params_default": (C.c_int, [_P(SsParams), C.c_uint32]),
     "ss_config_create": (C.c_int, [_P(SsParams), _P(_cfg)]),
@@ -318,6 +328,20 @@ PROTOTYPES = {
                                            C.c_float, C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_void_p, C.c_void_p]),
     "ss_specaug_packed": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float,
                                     C.c_size_t, C.c_size_t, C.c_float, _fp, C.c_void_p]),
+    "ss_noise_draws": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_float] * 5 +
+                       [C.c_void_p]),
+    "ss_noise_mix_work_bytes": (C.c_int, [C.c_size_t, C.c_size_t, _P(C.c_size_t)]),
+    "ss_noise_plan_packed_device": (C.c_int, _NOISE_F32 + [C.c_void_p, C.c_size_t] + [C.c_float] * 5 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ss_noise_plan_packed_i16_device": (C.c_int, _NOISE_I16 + [C.c_void_p, C.c_size_t] + [C.c_float] * 5 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ss_noise_apply_packed_device": (C.c_int, _NOISE_F32 + [C.c_void_p, _fp, C.c_void_p]),
+    "ss_noise_apply_packed": (C.c_int, _NOISE_F32 + [C.c_void_p, _fp]),
+    "ss_noise_apply_packed_i16_device": (C.c_int, _NOISE_I16 + [C.c_void_p, _fp, C.c_void_p]),
+    "ss_noise_apply_packed_i16": (C.c_int, _NOISE_I16 + [C.c_void_p, _fp]),
+    "ss_noise_mix_packed_device": (C.c_int, _NOISE_F32 + [C.c_void_p, C.c_size_t] + [C.c_float] * 5 + [_fp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ss_noise_mix_packed": (C.c_int, _NOISE_F32 + [C.c_void_p, C.c_size_t] + [C.c_float] * 5 + [_fp, C.c_void_p]),
+    "ss_noise_mix_packed_i16_device": (C.c_int, _NOISE_I16 + [C.c_void_p, C.c_size_t] + [C.c_float] * 5 + [_fp, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                                                                          C.c_void_p]),
+    "ss_noise_mix_packed_i16": (C.c_int, _NOISE_I16 + [C.c_void_p, C.c_size_t] + [C.c_float] * 5 + [_fp, C.c_void_p]),
     "ss_vad_energy_stream_state_len": (C.c_int, [C.c_size_t, _P(C.c_size_t)]),
     "ss_vad_energy_stream_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
                                                      C.c_float, C.c_float, C.c_size_t, C.c_float, _fp, C.c_void_p, C.c_void_p]),
