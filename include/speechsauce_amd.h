@@ -1374,6 +1374,106 @@ int ss_noise_mix_packed_i16(const int16_t *x, float x_scale, size_t n_clips, con
                             uint64_t *rng, size_t clip_base, float prob, float snr_lo_db, float snr_hi_db, float gain_lo_db,
                             float gain_hi_db, float *out, ss_noise_plan_row *plan);
 
+/* ---- reverberation of packed clips from a bank of room impulse responses, seeded on the device ----
+ * The convolution step of the multi-condition recipes (Kaldi wav-reverberate --impulse-response, NeMo ImpulsePerturbation, lhotse
+ * reverb_rir, ESPnet rir_scp / rir_apply_prob, torchaudio fftconvolve(x, rir)), ahead of ss_noise_mix_packed*: with probability prob a
+ * clip is convolved with a drawn response of the bank.  The stage reads nothing back and draws afresh on every replay of a captured
+ * graph.  The reference crate has none: this comment is the specification.
+ *   Bank handle (ss_reverb_bank): ss_reverb_bank_create takes the responses packed on the host, response c = rir[ro[c] .. ro[c+1]) of
+ *   total_rir floats, K_c = ro[c+1] - ro[c] in 1 .. 16384 finite taps; ro[0] == 0.  normalize: 0 = as given; 1 = unit energy,
+ *   h / sqrt(sum h^2); 2 = peak magnitude 1, h / max |h| -- the squares, their sum in ascending order, the root and the quotient in
+ *   f64, the quotient rounded once to f32; a response of zeros stays as it is.  peak_c = the first index of max |h|.  The handle's
+ *   shift of response c is peak_c with align_peak = 1 (Kaldi's --shift-output=true: the direct path stays where it was) and 0 with
+ *   align_peak = 0 (fftconvolve(x, h)[:L]).  At creation the host forms the partition spectra: partition p = taps [pB, pB + B) of the
+ *   normalised response, B = 512, zero-padded to N = 1024 points, transformed in f64 (exp(-2 pi i nk / N)) and rounded once to f32.
+ *   The handle works without a device; the first device call uploads the spectra to the device that is current then (a first call
+ *   inside a graph capture therefore fails: make one call of the handle before capturing).
+ *     ss_reverb_bank_info      n_rir, the block B, the longest K_c and the number of partition spectra.
+ *     ss_reverb_bank_rir       n_taps = K_c and peak = peak_c of response c, and with taps != NULL (cap >= K_c floats) the normalised
+ *                              f32 taps exactly as the spectra were made from them: references are built from these.
+ *     ss_reverb_bank_spectrum  partition p of response c as N interleaved (re, im) pairs, bin 0 first.
+ *   Speech: x, packed samples; clip b owns samples so[b] .. so[b+1] (the sample_offsets of ss_noise_mix_packed*); L_b < 2^31.  rng and
+ *   clip_base: as in ss_noise_mix_packed*.
+ *   Plan: one ss_reverb_plan_row {rir, shift} per clip (8 bytes, 8-byte aligned table), caller-owned and always written.
+ *   Draws (integers and f64 only: host and device agree exactly), with id = low32(clip_base + b), key = (low32(seed), high32(seed)):
+ *     (u0, u1, -, -) = philox((id, 0x30000, low32(epoch), high32(epoch)), key) -- a counter word apart from SpecAugment's mask indices
+ *     (below 0x20000) and the noise stage's 0x20000 / 0x20001, so that one {seed, epoch} block may serve all three stages.
+ *     reverberated = (uint64)u0 < (uint64)((double)prob * 4294967296.0) and n_rir > 0;  rir = (u1 * n_rir) >> 32, shift = the handle's
+ *     shift of that response.  Not reverberated: rir = -1, shift = 0.  A speech segment that is reversed, starts below 0 or ends past
+ *     total_samples: rir = -2, shift = 0.
+ *   Output, a pure function of the clip's samples and its row: out[i] = sum_k h[k] * x[i + shift - k], i = 0 .. L_b - 1, k = 0 ..
+ *     K - 1, samples outside the clip's own segment taken as +0.0: the same length as the clip, and a clip never reads its neighbour.
+ *     Computed by partitioned overlap-save in f32 (ss_reverb_apply_kernel): per block pair of 2B clip-relative outputs one forward
+ *     transform per partition whose window meets the clip, products with the partition spectra accumulated in ascending p, one
+ *     inverse transform.  Specified to max |out - ref| <= 1e-4 * max |ref| per clip against the f64 direct sum over the taps
+ *     ss_reverb_bank_rir returns; not bit-exact against it, also not for a delta response (h = [1], or a lone 1 at the peak with
+ *     align_peak: x comes back within the same bound, a transform pair in between).  Bit-exact are: a clip against the same clip at
+ *     any other place of any other block (the blocks are clip-relative), the PCM forms against the float forms, the host forms
+ *     against the device forms, and one plan applied twice.
+ *     A row with rir == -1, or whose rir is not in [0, n_rir) or whose shift is not in [0, K_rir) (a caller's plan), is not
+ *     reverberated: its samples are copied bit for bit (NaN payloads, -0.0 and denormals kept).  A row with rir == -2 leaves its
+ *     samples unwritten, and so are samples in no clip.
+ *   A clip's row and output depend on (seed, epoch, clip_base + b), its own samples and the bank only: the clips [B, C] at clip_base 1
+ *   get what they get as clips 1 and 2 of [A, B, C] at clip_base 0.
+ *   Worked pin: seed 2026, epoch 0, clip_base 0, prob 0.5, a bank of five responses whose peaks lie at 0, 7, 100, 3 and 11 with
+ *   align_peak = 1, three speech clips of 16000 samples: (rir, shift) of clips 0, 1, 2 =
+ *   (2, 100) | (-1, 0) | (0, 0).
+ * Calls:
+ *   ss_reverb_draws                        host only, no device: every plan row from the same code.
+ *   ss_reverb_plan_packed_device           the rows on the device (ss_reverb_plan_kernel).  epoch is not touched.
+ *   ss_reverb_apply_packed[_i16][_device]  the convolution alone on any plan table: the caller's own, or one plan applied twice.
+ *   ss_reverb_packed[_i16][_device]        plan + apply, two launches, and the epoch bump: lane 0 of the apply launch stores epoch + 1.
+ *                                          The host forms update rng[1].
+ *   The _i16 forms take x as 16-bit PCM with x_scale (a power of two, as in ss_mfcc_packed_i16): sample k is (float)pcm[k] * x_scale,
+ *   out is float, and every output bit is that of the float call on the converted array; 2-byte alignment is enough.
+ *   out may not overlap x (an in-place convolution is an error), and the plan and rng may overlap neither.  Nothing outside the
+ *   blocks is read or written, whatever the table or the plan hold.  The device forms expect speech segments that do not overlap one
+ *   another.  The grids depend on n_clips and total_samples only; the device forms are asynchronous on `stream`, allocate nothing
+ *   (the handle's first device call apart) and read nothing back.  One rng block serves one stream of calls.
+ *   Not served: Kaldi's --normalize-output power matching (a following ss_noise_mix_packed* measures the reverberated speech's energy
+ *   itself and applies the gain), multi-channel responses, responses over 16384 taps, stream pools.
+ * Arguments: n_clips == 0 is SS_OK, also without a device.  SS_ERR_ARG, decided before the device is touched: null buffers; prob
+ * outside [0, 1] or NaN; n_clips or total_samples >= 2^31; clip_base + n_clips > 2^32; a scale that is not a power of two; samples or
+ * out not aligned to their element, the table, plan or rng not 8-byte aligned; the overlaps above; at creation a response that is
+ * empty, reversed, longer than 16384 taps, past total_rir or not finite (the message names it), normalize outside 0 .. 2, align_peak
+ * outside 0 .. 1, n_rir >= 2^26.  The host forms check the table first as the other host forms do (the first bad clip is named),
+ * write samples 0 .. so[n_clips) of out, and hand the caller's out to the device first, so that rows a caller's plan leaves
+ * unwritten keep what they held. */
+typedef struct ss_reverb_bank ss_reverb_bank; /* opaque: taps, partition spectra and, after the first device call, their device copy */
+typedef struct ss_reverb_plan_row {
+    int32_t rir;   /* the bank's response; -1: not reverberated; -2: a bad speech segment */
+    int32_t shift; /* first tap index that lands on the output sample itself, 0 .. K - 1 */
+} ss_reverb_plan_row;
+int ss_reverb_bank_create(const float *rir, size_t n_rir, const int64_t *rir_offsets, size_t total_rir, int normalize, int align_peak,
+                          ss_reverb_bank **bank);
+void ss_reverb_bank_destroy(ss_reverb_bank *bank);
+int ss_reverb_bank_info(const ss_reverb_bank *bank, size_t *n_rir, size_t *block, size_t *max_taps, size_t *n_partitions);
+int ss_reverb_bank_rir(const ss_reverb_bank *bank, size_t c, float *taps, size_t cap, size_t *n_taps, size_t *peak);
+int ss_reverb_bank_spectrum(const ss_reverb_bank *bank, size_t c, size_t p, float *out);
+int ss_reverb_draws(const uint64_t *rng, size_t clip_base, size_t n_clips, const int64_t *sample_offsets, size_t total_samples,
+                    const ss_reverb_bank *bank, float prob, ss_reverb_plan_row *plan);
+int ss_reverb_plan_packed_device(size_t n_clips, const int64_t *d_sample_offsets, size_t total_samples, const ss_reverb_bank *bank,
+                                 const uint64_t *d_rng, size_t clip_base, float prob, ss_reverb_plan_row *d_plan, void *stream);
+int ss_reverb_apply_packed_device(const float *d_x, size_t n_clips, const int64_t *d_sample_offsets, size_t total_samples,
+                                  const ss_reverb_bank *bank, const ss_reverb_plan_row *d_plan, float *d_out, void *stream);
+int ss_reverb_apply_packed(const float *x, size_t n_clips, const int64_t *sample_offsets, size_t total_samples,
+                           const ss_reverb_bank *bank, const ss_reverb_plan_row *plan, float *out);
+int ss_reverb_apply_packed_i16_device(const int16_t *d_x, float x_scale, size_t n_clips, const int64_t *d_sample_offsets,
+                                      size_t total_samples, const ss_reverb_bank *bank, const ss_reverb_plan_row *d_plan, float *d_out,
+                                      void *stream);
+int ss_reverb_apply_packed_i16(const int16_t *x, float x_scale, size_t n_clips, const int64_t *sample_offsets, size_t total_samples,
+                               const ss_reverb_bank *bank, const ss_reverb_plan_row *plan, float *out);
+int ss_reverb_packed_device(const float *d_x, size_t n_clips, const int64_t *d_sample_offsets, size_t total_samples,
+                            const ss_reverb_bank *bank, uint64_t *d_rng, size_t clip_base, float prob, float *d_out,
+                            ss_reverb_plan_row *d_plan, void *stream);
+int ss_reverb_packed(const float *x, size_t n_clips, const int64_t *sample_offsets, size_t total_samples, const ss_reverb_bank *bank,
+                     uint64_t *rng, size_t clip_base, float prob, float *out, ss_reverb_plan_row *plan);
+int ss_reverb_packed_i16_device(const int16_t *d_x, float x_scale, size_t n_clips, const int64_t *d_sample_offsets, size_t total_samples,
+                                const ss_reverb_bank *bank, uint64_t *d_rng, size_t clip_base, float prob, float *d_out,
+                                ss_reverb_plan_row *d_plan, void *stream);
+int ss_reverb_packed_i16(const int16_t *x, float x_scale, size_t n_clips, const int64_t *sample_offsets, size_t total_samples,
+                         const ss_reverb_bank *bank, uint64_t *rng, size_t clip_base, float prob, float *out, ss_reverb_plan_row *plan);
+
 /* ---- polyphase windowed-sinc resampling ahead of the feature calls ----
  * Every call above takes audio at the rate its ss_params was built for; these calls bring telephony (8 kHz), capture (48 kHz) and
  * corpus (44.1 kHz) audio to it on the device, on the packed layout and the stream pools of the feature calls, from floats or 16-bit

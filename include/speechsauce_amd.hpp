@@ -875,6 +875,110 @@ inline std::vector<float> noise_mix_packed_i16(const std::vector<int16_t> &x, fl
     return out;
 }
 
+// Reverberation of packed clips from a bank of room impulse responses (ss_reverb_*): with probability prob a clip is convolved with a
+// drawn response, out[i] = sum_k h[k] x[i + shift - k], the clip's length kept; the draws are Philox4x32-10 of rng = {seed, epoch} and
+// clip_base + b (counter word 0x30000: one block may serve SpecAugment, the noise stage and this one).  The handle is shared by
+// copies; the first call that runs uploads the partition spectra.
+using ReverbPlanRow = ss_reverb_plan_row;
+static_assert(sizeof(ReverbPlanRow) == 8, "ss_reverb_plan_row is 8 bytes");
+class ReverbBank {
+public:
+    enum Normalize { kAsGiven = 0, kUnitEnergy = 1, kUnitPeak = 2 };
+    // rirs: the responses packed; offsets: n_rir + 1 entries from 0; every response has 1 .. 16384 finite taps
+    ReverbBank(const std::vector<float> &rirs, const std::vector<int64_t> &offsets, Normalize normalize = kUnitEnergy, bool align_peak = true)
+    {
+        if (offsets.empty()) throw Error(SS_ERR_ARG, "ReverbBank: shape mismatch");
+        ss_reverb_bank *raw = nullptr;
+        check(ss_reverb_bank_create(rirs.data(), offsets.size() - 1, offsets.data(), rirs.size(), static_cast<int>(normalize), align_peak ? 1 : 0, &raw));
+        h_ = std::shared_ptr<ss_reverb_bank>(raw, ss_reverb_bank_destroy);
+    }
+    const ss_reverb_bank *handle() const { return h_.get(); }
+    size_t size() const { return info(0); }
+    size_t block() const { return info(1); }
+    size_t max_taps() const { return info(2); }
+    size_t partitions() const { return info(3); }
+    // the normalised taps of response c as the spectra were made from them, and the first index of their largest magnitude
+    std::vector<float> rir(size_t c, size_t *peak = nullptr) const
+    {
+        size_t n = 0, pk = 0;
+        check(ss_reverb_bank_rir(h_.get(), c, nullptr, 0, &n, &pk));
+        std::vector<float> taps(n);
+        check(ss_reverb_bank_rir(h_.get(), c, taps.data(), taps.size(), &n, &pk));
+        if (peak) *peak = pk;
+        return taps;
+    }
+    // partition p of response c: 2 * 2 * block() floats, (re, im) of bin 0 first
+    std::vector<float> spectrum(size_t c, size_t p) const
+    {
+        std::vector<float> out(4 * block());
+        check(ss_reverb_bank_spectrum(h_.get(), c, p, out.data()));
+        return out;
+    }
+
+private:
+    size_t info(int which) const
+    {
+        size_t v[4] = {0, 0, 0, 0};
+        check(ss_reverb_bank_info(h_.get(), &v[0], &v[1], &v[2], &v[3]));
+        return v[which];
+    }
+    std::shared_ptr<ss_reverb_bank> h_;
+};
+
+// the plan reverb_packed writes: host only, no device
+inline std::vector<ReverbPlanRow> reverb_draws(const uint64_t (&rng)[2], const std::vector<int64_t> &sample_offsets, size_t total_samples, const ReverbBank &bank,
+                                               float prob = 1.0f, size_t clip_base = 0)
+{
+    if (sample_offsets.empty()) throw Error(SS_ERR_ARG, "reverb_draws: shape mismatch");
+    std::vector<ReverbPlanRow> plan(sample_offsets.size() - 1);
+    check(ss_reverb_draws(rng, clip_base, plan.size(), sample_offsets.data(), total_samples, bank.handle(), prob, plan.data()));
+    return plan;
+}
+
+// the convolution alone, on any plan table; rows with rir == -1 (or out of range for the bank) are copies
+inline std::vector<float> reverb_apply_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, const ReverbBank &bank,
+                                              const std::vector<ReverbPlanRow> &plan)
+{
+    if (sample_offsets.empty() || plan.size() != sample_offsets.size() - 1) throw Error(SS_ERR_ARG, "reverb_apply_packed: shape mismatch");
+    std::vector<float> out(x);
+    if (!x.empty()) check(ss_reverb_apply_packed(x.data(), plan.size(), sample_offsets.data(), x.size(), bank.handle(), plan.data(), out.data()));
+    return out;
+}
+
+// ... on 16-bit PCM: a sample is pcm * x_scale, a power of two; out is float
+inline std::vector<float> reverb_apply_packed_i16(const std::vector<int16_t> &x, float x_scale, const std::vector<int64_t> &sample_offsets, const ReverbBank &bank,
+                                                  const std::vector<ReverbPlanRow> &plan)
+{
+    if (sample_offsets.empty() || plan.size() != sample_offsets.size() - 1) throw Error(SS_ERR_ARG, "reverb_apply_packed_i16: shape mismatch");
+    std::vector<float> out(x.size());
+    for (size_t i = 0; i < x.size(); ++i) out[i] = static_cast<float>(x[i]) * x_scale;  // samples in no clip: the converted signal
+    if (!x.empty()) check(ss_reverb_apply_packed_i16(x.data(), x_scale, plan.size(), sample_offsets.data(), x.size(), bank.handle(), plan.data(), out.data()));
+    return out;
+}
+
+// plan + apply; rng[1] (the epoch) is advanced by one and `plan` receives the table that was applied
+inline std::vector<float> reverb_packed(const std::vector<float> &x, const std::vector<int64_t> &sample_offsets, const ReverbBank &bank, uint64_t (&rng)[2],
+                                        std::vector<ReverbPlanRow> &plan, float prob = 1.0f, size_t clip_base = 0)
+{
+    if (sample_offsets.empty()) throw Error(SS_ERR_ARG, "reverb_packed: shape mismatch");
+    std::vector<float> out(x);
+    plan.assign(sample_offsets.size() - 1, ReverbPlanRow{});
+    if (!x.empty()) check(ss_reverb_packed(x.data(), plan.size(), sample_offsets.data(), x.size(), bank.handle(), rng, clip_base, prob, out.data(), plan.data()));
+    return out;
+}
+
+inline std::vector<float> reverb_packed_i16(const std::vector<int16_t> &x, float x_scale, const std::vector<int64_t> &sample_offsets, const ReverbBank &bank,
+                                            uint64_t (&rng)[2], std::vector<ReverbPlanRow> &plan, float prob = 1.0f, size_t clip_base = 0)
+{
+    if (sample_offsets.empty()) throw Error(SS_ERR_ARG, "reverb_packed_i16: shape mismatch");
+    std::vector<float> out(x.size());
+    for (size_t i = 0; i < x.size(); ++i) out[i] = static_cast<float>(x[i]) * x_scale;
+    plan.assign(sample_offsets.size() - 1, ReverbPlanRow{});
+    if (!x.empty())
+        check(ss_reverb_packed_i16(x.data(), x_scale, plan.size(), sample_offsets.data(), x.size(), bank.handle(), rng, clip_base, prob, out.data(), plan.data()));
+    return out;
+}
+
 inline std::vector<float> cmvnw_packed(const std::vector<float> &vec, const std::vector<int64_t> &offsets, size_t cols, size_t win_size = 301,
                                        bool variance_normalization = false)
 {

@@ -5,6 +5,7 @@
 // Build with -ffp-contract=off: the mel bank indices sit on integer boundaries after an f32
 // ln -> exp round trip, so the f32 operation order below is part of the contract.
 #include "ss_internal.h"
+#include "ss_reverb.h"
 #include "ss_whisper.h"
 
 #include <algorithm>
@@ -1248,6 +1249,90 @@ void build_mel4096(const HostTables &t, Mfcc4096Tables &f)
 {
     build_or_stft_only(t, f, [](const HostTables &tt, Mfcc4096Tables &ff) { build_4096(tt, ff, true); });
 }
+
+// ---- the reverberation stage's host tables (ss_reverb.h) ----
+
+namespace reverb {
+
+void build_twiddles(std::vector<float> &tw)
+{
+    const double PI = 3.14159265358979323846;
+    tw.assign(kPartFloats, 0.0f);
+    for (unsigned j = 0; j < 32; ++j)
+        for (unsigned r = 0; r < 32; ++r) {
+            const double a = -2.0 * PI * static_cast<double>(j * r) / static_cast<double>(kFft);
+            tw[part_slot(r, j)] = static_cast<float>(std::cos(a));
+            tw[part_slot(r, j) + 1] = static_cast<float>(std::sin(a));
+        }
+}
+
+// in-place radix-2 decimation in time over N = 1024 points in f64, exp(-2 pi i nk / N)
+static void fft_f64(std::vector<double> &re, std::vector<double> &im)
+{
+    const double PI = 3.14159265358979323846;
+    const unsigned n = kFft;
+    for (unsigned i = 1, j = 0; i < n; ++i) {
+        unsigned bit = n >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) {
+            std::swap(re[i], re[j]);
+            std::swap(im[i], im[j]);
+        }
+    }
+    for (unsigned len = 2; len <= n; len <<= 1) {
+        const unsigned half = len / 2, step = n / len;
+        for (unsigned i = 0; i < n; i += len)
+            for (unsigned k = 0; k < half; ++k) {
+                const double a = -2.0 * PI * static_cast<double>(k * step) / static_cast<double>(n);  // every twiddle from its own angle
+                const double wr = std::cos(a), wi = std::sin(a);
+                const double xr = re[i + k + half] * wr - im[i + k + half] * wi, xi = re[i + k + half] * wi + im[i + k + half] * wr;
+                re[i + k + half] = re[i + k] - xr;
+                im[i + k + half] = im[i + k] - xi;
+                re[i + k] += xr;
+                im[i + k] += xi;
+            }
+    }
+}
+
+void append_partition_spectra(const float *taps, size_t n, std::vector<float> &out)
+{
+    const size_t parts = (n + kBlock - 1) / kBlock;
+    std::vector<double> re(kFft), im(kFft);
+    for (size_t p = 0; p < parts; ++p) {
+        std::fill(re.begin(), re.end(), 0.0);
+        std::fill(im.begin(), im.end(), 0.0);
+        for (size_t k = 0; k < kBlock && p * kBlock + k < n; ++k) re[k] = static_cast<double>(taps[p * kBlock + k]);
+        fft_f64(re, im);
+        const size_t base = out.size();
+        out.resize(base + kPartFloats);
+        for (unsigned j = 0; j < 32; ++j)
+            for (unsigned r = 0; r < 32; ++r) {
+                out[base + part_slot(r, j)] = static_cast<float>(re[j + 32 * r]);
+                out[base + part_slot(r, j) + 1] = static_cast<float>(im[j + 32 * r]);
+            }
+    }
+}
+
+size_t normalise_taps(const float *h, size_t n, int mode, std::vector<float> &out)
+{
+    size_t peak = 0;
+    double top = 0.0, energy = 0.0;
+    for (size_t k = 0; k < n; ++k) {
+        const double v = static_cast<double>(h[k]), a = std::fabs(v);
+        if (a > top) {  // the first index of the largest magnitude; a NaN tap is never a peak
+            top = a;
+            peak = k;
+        }
+        energy += v * v;  // ascending order
+    }
+    const double div = mode == 1 ? std::sqrt(energy) : mode == 2 ? top : 1.0;
+    out.resize(n);
+    for (size_t k = 0; k < n; ++k) out[k] = mode != 0 && div > 0.0 ? static_cast<float>(static_cast<double>(h[k]) / div) : h[k];
+    return peak;
+}
+
+}  // namespace reverb
 
 }  // namespace ss
 

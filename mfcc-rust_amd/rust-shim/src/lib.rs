@@ -275,6 +275,34 @@ extern "C" {
                                noise_scale: f32, n_noise: usize, noise_offsets: *const i64, total_noise: usize, rng: *mut u64, clip_base: usize,
                                prob: f32, snr_lo_db: f32, snr_hi_db: f32, gain_lo_db: f32, gain_hi_db: f32, out: *mut f32,
                                plan: *mut NoisePlanRow) -> c_int;
+    fn ss_reverb_bank_create(rir: *const f32, n_rir: usize, rir_offsets: *const i64, total_rir: usize, normalize: c_int, align_peak: c_int,
+                             bank: *mut *mut c_void) -> c_int;
+    fn ss_reverb_bank_destroy(bank: *mut c_void);
+    fn ss_reverb_bank_info(bank: *const c_void, n_rir: *mut usize, block: *mut usize, max_taps: *mut usize, n_partitions: *mut usize) -> c_int;
+    fn ss_reverb_bank_rir(bank: *const c_void, c: usize, taps: *mut f32, cap: usize, n_taps: *mut usize, peak: *mut usize) -> c_int;
+    fn ss_reverb_bank_spectrum(bank: *const c_void, c: usize, p: usize, out: *mut f32) -> c_int;
+    fn ss_reverb_draws(rng: *const u64, clip_base: usize, n_clips: usize, sample_offsets: *const i64, total_samples: usize, bank: *const c_void,
+                       prob: f32, plan: *mut ReverbPlanRow) -> c_int;
+    fn ss_reverb_plan_packed_device(n_clips: usize, d_sample_offsets: *const i64, total_samples: usize, bank: *const c_void, d_rng: *const u64,
+                                    clip_base: usize, prob: f32, d_plan: *mut ReverbPlanRow, stream: *mut c_void) -> c_int;
+    fn ss_reverb_apply_packed_device(d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize, bank: *const c_void,
+                                     d_plan: *const ReverbPlanRow, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_reverb_apply_packed(x: *const f32, n_clips: usize, sample_offsets: *const i64, total_samples: usize, bank: *const c_void,
+                              plan: *const ReverbPlanRow, out: *mut f32) -> c_int;
+    fn ss_reverb_apply_packed_i16_device(d_x: *const i16, x_scale: f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize,
+                                         bank: *const c_void, d_plan: *const ReverbPlanRow, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    fn ss_reverb_apply_packed_i16(x: *const i16, x_scale: f32, n_clips: usize, sample_offsets: *const i64, total_samples: usize,
+                                  bank: *const c_void, plan: *const ReverbPlanRow, out: *mut f32) -> c_int;
+    fn ss_reverb_packed_device(d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize, bank: *const c_void,
+                               d_rng: *mut u64, clip_base: usize, prob: f32, d_out: *mut f32, d_plan: *mut ReverbPlanRow,
+                               stream: *mut c_void) -> c_int;
+    fn ss_reverb_packed(x: *const f32, n_clips: usize, sample_offsets: *const i64, total_samples: usize, bank: *const c_void, rng: *mut u64,
+                        clip_base: usize, prob: f32, out: *mut f32, plan: *mut ReverbPlanRow) -> c_int;
+    fn ss_reverb_packed_i16_device(d_x: *const i16, x_scale: f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize,
+                                   bank: *const c_void, d_rng: *mut u64, clip_base: usize, prob: f32, d_out: *mut f32,
+                                   d_plan: *mut ReverbPlanRow, stream: *mut c_void) -> c_int;
+    fn ss_reverb_packed_i16(x: *const i16, x_scale: f32, n_clips: usize, sample_offsets: *const i64, total_samples: usize, bank: *const c_void,
+                            rng: *mut u64, clip_base: usize, prob: f32, out: *mut f32, plan: *mut ReverbPlanRow) -> c_int;
     fn ss_resample_packed_offsets(orig_rate: u32, new_rate: u32, n_clips: usize, sample_offsets: *const i64, out_offsets: *mut i64) -> c_int;
     fn ss_resampler_create(orig_rate: u32, new_rate: u32, lowpass_filter_width: u32, rolloff: f32, out: *mut *mut c_void) -> c_int;
     fn ss_resampler_destroy(rs: *mut c_void);
@@ -2195,6 +2223,194 @@ impl Affine {
                                        stream: *mut c_void) -> Result<(), Error> {
         check(ss_affine_splice_packed_device(self.raw, d_vec, n_clips, d_row_offsets, total_rows, d_out_offsets, total_out_rows, cols, left, right,
                                              stride, d_out, stream))
+    }
+}
+
+/// One row of a reverberation plan (`ss_reverb_plan_row`): 8 bytes.  `rir` is the bank's response, -1 for a clip that is not reverberated
+/// and -2 for a bad speech segment; `shift` is the tap index that lands on the output sample itself.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct ReverbPlanRow {
+    pub rir: i32,
+    pub shift: i32,
+}
+
+/// How `ReverbBank::new` scales every response: as given, to unit energy, or to a largest magnitude of 1.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub enum ReverbNormalize {
+    AsGiven = 0,
+    UnitEnergy = 1,
+    UnitPeak = 2,
+}
+
+/// A bank of room impulse responses (1 ..= 16384 taps each) with their partition spectra: the convolution step of the multi-condition
+/// recipes, `out[i] = sum_k h[k] * x[i + shift - k]` per clip, the clip's length kept.  Not in the reference crate.  Owns an
+/// `ss_reverb_bank`; the spectra are uploaded by the first call that runs.
+pub struct ReverbBank {
+    raw: *mut c_void,
+}
+
+unsafe impl Send for ReverbBank {}
+unsafe impl Sync for ReverbBank {}
+
+impl Drop for ReverbBank {
+    fn drop(&mut self) {
+        unsafe { ss_reverb_bank_destroy(self.raw) }
+    }
+}
+
+fn reverb_tables_ok(sample_offsets: &[i64], plan_len: Option<usize>, what: &str) -> Result<(), Error> {
+    if sample_offsets.is_empty() || plan_len.map_or(false, |n| n != sample_offsets.len() - 1) {
+        return Err(Error { status: SS_ERR_ARG, detail: format!("{}: an offset table has n + 1 entries and the plan one row per clip", what) });
+    }
+    Ok(())
+}
+
+impl ReverbBank {
+    /// `rirs`: the responses packed; `offsets`: `n_rir + 1` entries from 0.  `align_peak`: the output is shifted by each response's peak
+    /// index (the direct path stays where it was) instead of being the head of the full convolution.
+    pub fn new(rirs: &[f32], offsets: &[i64], normalize: ReverbNormalize, align_peak: bool) -> Result<ReverbBank, Error> {
+        if offsets.is_empty() {
+            return Err(Error { status: SS_ERR_ARG, detail: "ReverbBank: an offset table has n + 1 entries".to_string() });
+        }
+        let mut raw: *mut c_void = std::ptr::null_mut();
+        check(unsafe {
+            ss_reverb_bank_create(rirs.as_ptr(), offsets.len() - 1, offsets.as_ptr(), rirs.len(), normalize as c_int, align_peak as c_int, &mut raw)
+        })?;
+        Ok(ReverbBank { raw })
+    }
+
+    /// `(n_rir, block, max_taps, n_partitions)`
+    pub fn info(&self) -> Result<(usize, usize, usize, usize), Error> {
+        let (mut n, mut b, mut k, mut p) = (0usize, 0usize, 0usize, 0usize);
+        check(unsafe { ss_reverb_bank_info(self.raw, &mut n, &mut b, &mut k, &mut p) })?;
+        Ok((n, b, k, p))
+    }
+
+    /// The normalised taps of response `c` exactly as the spectra were made from them, and the first index of their largest magnitude.
+    pub fn rir(&self, c: usize) -> Result<(Vec<f32>, usize), Error> {
+        let (mut n, mut peak) = (0usize, 0usize);
+        check(unsafe { ss_reverb_bank_rir(self.raw, c, std::ptr::null_mut(), 0, &mut n, &mut peak) })?;
+        let mut taps = vec![0f32; n];
+        check(unsafe { ss_reverb_bank_rir(self.raw, c, taps.as_mut_ptr(), taps.len(), &mut n, &mut peak) })?;
+        Ok((taps, peak))
+    }
+
+    /// Partition `p` of response `c`: `2 * block` interleaved `(re, im)` pairs, bin 0 first.
+    pub fn spectrum(&self, c: usize, p: usize) -> Result<Vec<f32>, Error> {
+        let mut out = vec![0f32; 4 * self.info()?.1];
+        check(unsafe { ss_reverb_bank_spectrum(self.raw, c, p, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// The plan `packed` writes for `rng = [seed, epoch]`, computed on the host (no device).
+    pub fn draws(&self, rng: [u64; 2], sample_offsets: &[i64], total_samples: usize, prob: f32, clip_base: usize) -> Result<Vec<ReverbPlanRow>, Error> {
+        reverb_tables_ok(sample_offsets, None, "reverb_draws")?;
+        let mut plan = vec![ReverbPlanRow::default(); sample_offsets.len() - 1];
+        check(unsafe {
+            ss_reverb_draws(rng.as_ptr(), clip_base, plan.len(), sample_offsets.as_ptr(), total_samples, self.raw, prob, plan.as_mut_ptr())
+        })?;
+        Ok(plan)
+    }
+
+    /// The convolution alone on any plan table; rows with `rir == -1` (or out of range for the bank) are copies.
+    pub fn apply_packed(&self, x: &[f32], sample_offsets: &[i64], plan: &[ReverbPlanRow]) -> Result<Vec<f32>, Error> {
+        reverb_tables_ok(sample_offsets, Some(plan.len()), "reverb_apply_packed")?;
+        let mut out = x.to_vec();
+        if !x.is_empty() {
+            check(unsafe {
+                ss_reverb_apply_packed(x.as_ptr(), plan.len(), sample_offsets.as_ptr(), x.len(), self.raw, plan.as_ptr(), out.as_mut_ptr())
+            })?;
+        }
+        Ok(out)
+    }
+
+    /// As `apply_packed` on 16-bit PCM: a sample is `pcm * x_scale`, a power of two; the output is float.
+    pub fn apply_packed_i16(&self, x: &[i16], x_scale: f32, sample_offsets: &[i64], plan: &[ReverbPlanRow]) -> Result<Vec<f32>, Error> {
+        reverb_tables_ok(sample_offsets, Some(plan.len()), "reverb_apply_packed_i16")?;
+        let mut out: Vec<f32> = x.iter().map(|&v| v as f32 * x_scale).collect();
+        if !x.is_empty() {
+            check(unsafe {
+                ss_reverb_apply_packed_i16(x.as_ptr(), x_scale, plan.len(), sample_offsets.as_ptr(), x.len(), self.raw, plan.as_ptr(), out.as_mut_ptr())
+            })?;
+        }
+        Ok(out)
+    }
+
+    /// Reverberation of every clip of a packed signal with probability `prob`: the output and the plan that was applied.  The call
+    /// advances `rng[1]` by one, so the next call draws afresh.
+    pub fn packed(&self, x: &[f32], sample_offsets: &[i64], rng: &mut [u64; 2], prob: f32, clip_base: usize) -> Result<(Vec<f32>, Vec<ReverbPlanRow>), Error> {
+        reverb_tables_ok(sample_offsets, None, "reverb_packed")?;
+        let mut out = x.to_vec();
+        let mut plan = vec![ReverbPlanRow::default(); sample_offsets.len() - 1];
+        if !x.is_empty() {
+            check(unsafe {
+                ss_reverb_packed(x.as_ptr(), plan.len(), sample_offsets.as_ptr(), x.len(), self.raw, rng.as_mut_ptr(), clip_base, prob, out.as_mut_ptr(),
+                                 plan.as_mut_ptr())
+            })?;
+        }
+        Ok((out, plan))
+    }
+
+    /// As `packed` on 16-bit PCM (see `apply_packed_i16`).
+    pub fn packed_i16(&self, x: &[i16], x_scale: f32, sample_offsets: &[i64], rng: &mut [u64; 2], prob: f32,
+                      clip_base: usize) -> Result<(Vec<f32>, Vec<ReverbPlanRow>), Error> {
+        reverb_tables_ok(sample_offsets, None, "reverb_packed_i16")?;
+        let mut out: Vec<f32> = x.iter().map(|&v| v as f32 * x_scale).collect();
+        let mut plan = vec![ReverbPlanRow::default(); sample_offsets.len() - 1];
+        if !x.is_empty() {
+            check(unsafe {
+                ss_reverb_packed_i16(x.as_ptr(), x_scale, plan.len(), sample_offsets.as_ptr(), x.len(), self.raw, rng.as_mut_ptr(), clip_base, prob,
+                                     out.as_mut_ptr(), plan.as_mut_ptr())
+            })?;
+        }
+        Ok((out, plan))
+    }
+
+    /// The plan rows on the device (include/speechsauce_amd.h has the contract); the epoch is not touched.
+    ///
+    /// # Safety
+    /// Every pointer is a device pointer to a block of the size the header states; `d_rng` is the 16-byte device block `{seed, epoch}`.
+    pub unsafe fn plan_packed_device(&self, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize, d_rng: *const u64, clip_base: usize,
+                                     prob: f32, d_plan: *mut ReverbPlanRow, stream: *mut c_void) -> Result<(), Error> {
+        check(ss_reverb_plan_packed_device(n_clips, d_sample_offsets, total_samples, self.raw, d_rng, clip_base, prob, d_plan, stream))
+    }
+
+    /// The convolution alone, on any plan table; `d_out` does not overlap `d_x`.
+    ///
+    /// # Safety
+    /// As `plan_packed_device`; `d_out` holds `total_samples` floats.
+    pub unsafe fn apply_packed_device(&self, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize,
+                                      d_plan: *const ReverbPlanRow, d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+        check(ss_reverb_apply_packed_device(d_x, n_clips, d_sample_offsets, total_samples, self.raw, d_plan, d_out, stream))
+    }
+
+    /// As `apply_packed_device` on 16-bit PCM.
+    ///
+    /// # Safety
+    /// As `apply_packed_device`.
+    pub unsafe fn apply_packed_i16_device(&self, d_x: *const i16, x_scale: f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize,
+                                          d_plan: *const ReverbPlanRow, d_out: *mut f32, stream: *mut c_void) -> Result<(), Error> {
+        check(ss_reverb_apply_packed_i16_device(d_x, x_scale, n_clips, d_sample_offsets, total_samples, self.raw, d_plan, d_out, stream))
+    }
+
+    /// Plan, apply and the epoch bump: two asynchronous launches on `stream`, nothing read back; replays of a captured graph draw afresh.
+    ///
+    /// # Safety
+    /// As `apply_packed_device` and `plan_packed_device`; one `d_rng` block serves one stream of calls.
+    pub unsafe fn packed_device(&self, d_x: *const f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize, d_rng: *mut u64,
+                                clip_base: usize, prob: f32, d_out: *mut f32, d_plan: *mut ReverbPlanRow, stream: *mut c_void) -> Result<(), Error> {
+        check(ss_reverb_packed_device(d_x, n_clips, d_sample_offsets, total_samples, self.raw, d_rng, clip_base, prob, d_out, d_plan, stream))
+    }
+
+    /// As `packed_device` on 16-bit PCM.
+    ///
+    /// # Safety
+    /// As `packed_device`.
+    pub unsafe fn packed_i16_device(&self, d_x: *const i16, x_scale: f32, n_clips: usize, d_sample_offsets: *const i64, total_samples: usize,
+                                    d_rng: *mut u64, clip_base: usize, prob: f32, d_out: *mut f32, d_plan: *mut ReverbPlanRow,
+                                    stream: *mut c_void) -> Result<(), Error> {
+        check(ss_reverb_packed_i16_device(d_x, x_scale, n_clips, d_sample_offsets, total_samples, self.raw, d_rng, clip_base, prob, d_out, d_plan, stream))
     }
 }
 

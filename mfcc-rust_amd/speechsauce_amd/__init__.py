@@ -34,6 +34,7 @@ __all__ = ["mfcc", "mel_spectrogram", "preemphasis", "cmvn", "cmvnw", "derivativ
            "pad", "pad_packed",
            "spec_augment_spans", "mask_spans_packed", "spec_augment_packed", "SpecAugment",
            "NOISE_PLAN_DTYPE", "noise_plan_rows", "noise_draws", "noise_plan_packed", "noise_apply_packed", "noise_mix_packed", "NoiseMix",
+           "REVERB_PLAN_DTYPE", "reverb_plan_rows", "reverb_draws", "reverb_plan_packed", "reverb_apply_packed", "reverb_packed", "ReverbBank", "Reverb",
            "resample", "resample_packed", "resample_list", "ResampleStreamPool", "Resampler",
            "kaldi_fbank", "kaldi_mfcc", "kaldi_fbank_packed", "kaldi_mfcc_packed", "kaldi_fbank_list", "kaldi_mfcc_list", "KaldiConfig",
            "KaldiFbankStreamPool", "KaldiMfccStreamPool",
@@ -3120,6 +3121,250 @@ class NoiseMix:
         out, plan, self._work = _noise_plan_or_mix("NoiseMix", True, signal, lengths, self.bank, self.rng, prob, snr_db, gain_db, clip_base, pcm_scale, out,
                                                    device_tables, self._work)
         return out, plan
+
+
+# ---- reverberation of packed clips from a bank of room impulse responses, seeded on the device (ss_reverb_*) --------------------
+# A clip's plan row is a function of (seed, epoch, clip_base + b), its segment and the bank; the output is a function of the row and
+# the clip's own samples.  The generator block is SpecAugment's: one seed may serve SpecAugment, NoiseMix and Reverb (the counter
+# words differ).
+
+#: ``ss_reverb_plan_row``: one row per clip of the plan tables below (8 bytes)
+REVERB_PLAN_DTYPE = np.dtype([("rir", np.int32), ("shift", np.int32)])
+_REVERB_NORMALIZE = {"none": 0, "energy": 1, "peak": 2}
+
+
+def reverb_plan_rows(plan):
+    """A plan table as a numpy record array of ``REVERB_PLAN_DTYPE``: a device plan (int32 ``[n_clips, 2]``, the 8-byte rows as they
+    lie in memory) is read back (a synchronisation); a host plan is returned as it is."""
+    if _is_torch(plan):
+        return plan.detach().cpu().contiguous().numpy().reshape(-1).view(REVERB_PLAN_DTYPE)
+    return np.ascontiguousarray(plan).reshape(-1).view(REVERB_PLAN_DTYPE)
+
+
+class ReverbBank(_Handle):
+    """Owns an ``ss_reverb_bank`` handle: impulse responses of 1 .. 16384 taps each, packed in the 1-D float32 ``rirs`` with their
+    ``lengths``, normalised (``normalize``: "energy" -- unit energy, torchaudio's and lhotse's rule --, "peak" -- largest magnitude 1
+    --, or "none"), their partition spectra formed on the host in f64 and -- after the first device call -- the device copy of those.
+    ``align_peak=True`` keeps the direct path where it was (the output is shifted by each response's peak index, Kaldi's
+    ``--shift-output=true``); ``False`` is ``fftconvolve(x, h)[:len(x)]``.  The arrays handed in are not kept."""
+
+    _destroy = "ss_reverb_bank_destroy"
+
+    def __init__(self, rirs, lengths, normalize="energy", align_peak=True):
+        h = np.ascontiguousarray(_affine_host(rirs, "ReverbBank: rirs"), dtype=np.float32)
+        if h.ndim != 1:
+            raise ValueError("ReverbBank: rirs must be the responses packed in one 1-D array")
+        if normalize not in _REVERB_NORMALIZE:
+            raise ValueError('ReverbBank: normalize must be "energy", "peak" or "none"')
+        table = _sample_offsets(lengths, int(h.shape[0]), "ReverbBank")
+        super().__init__()
+        _lib.check(self._owner.ss_reverb_bank_create(h.ctypes.data if h.size else None, table.size - 1, table.ctypes.data, int(h.shape[0]),
+                                                     _REVERB_NORMALIZE[normalize], 1 if align_peak else 0, C.byref(self._h)))
+        info = [C.c_size_t() for _ in range(4)]
+        _lib.check(self._owner.ss_reverb_bank_info(self._h, *(C.byref(v) for v in info)))
+        self.n_rir, self.block, self.max_taps, self.n_partitions = (int(v.value) for v in info)
+        self.normalize, self.align_peak = normalize, bool(align_peak)
+
+    def __len__(self):
+        return self.n_rir
+
+    def rir(self, c):
+        """-> (taps, peak): the normalised float32 taps of response ``c`` exactly as the spectra were made from them, and the first
+        index of their largest magnitude."""
+        n, peak = C.c_size_t(), C.c_size_t()
+        _lib.check(self._owner.ss_reverb_bank_rir(self._h, int(c), None, 0, C.byref(n), C.byref(peak)))
+        taps = np.empty(n.value, np.float32)
+        _lib.check(self._owner.ss_reverb_bank_rir(self._h, int(c), taps.ctypes.data, taps.size, C.byref(n), C.byref(peak)))
+        return taps, int(peak.value)
+
+    def shift(self, c):
+        """the shift a plan row of response ``c`` carries: its peak index with ``align_peak``, else 0"""
+        return self.rir(c)[1] if self.align_peak else 0
+
+    def spectrum(self, c, p):
+        """partition ``p`` of response ``c`` as the kernel multiplies by it: complex64 ``[2 * block]``"""
+        out = np.empty(4 * self.block, np.float32)
+        _lib.check(self._owner.ss_reverb_bank_spectrum(self._h, int(c), int(p), out.ctypes.data))
+        return out.view(np.complex64)
+
+
+def _reverb_rng(rng):
+    return rng.rng if isinstance(rng, (Reverb, NoiseMix)) else rng
+
+
+def _reverb_scalars(prob, clip_base, bank, what):
+    if not isinstance(bank, ReverbBank):
+        raise TypeError(f"{what}: bank must be a ReverbBank")
+    prob, base = float(prob), int(clip_base)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"{what}: prob must lie in [0, 1]")
+    if not 0 <= base <= 1 << 32:
+        raise ValueError(f"{what}: clip_base must lie in 0 .. 2^32")
+    return prob, base
+
+
+def reverb_draws(rng, lengths, bank, prob=1.0, clip_base=0, *, sample_offsets=None, total_samples=None):
+    """The plan ``reverb_packed`` writes, computed on the host (no device): a record array of ``REVERB_PLAN_DTYPE``.  ``rng`` is a
+    ``(seed, epoch)`` pair, a uint64 array of two, a ``SpecAugment``, a ``NoiseMix`` or a ``Reverb`` (read back).  ``sample_offsets``
+    (with ``lengths`` None) is an offset table taken as it stands, with ``total_samples`` (default: the table's last entry): a bad
+    speech segment has ``rir == -2``, as on the device."""
+    what = "reverb_draws"
+    prob, base = _reverb_scalars(prob, clip_base, bank, what)
+    words = _rng_words(_reverb_rng(rng), what)
+    if (lengths is None) == (sample_offsets is None):
+        raise ValueError(f"{what}: give lengths or an offset table, not both")
+    if sample_offsets is None:
+        so = _sample_offsets(lengths, 1 << 62, what)
+    else:
+        so = np.ascontiguousarray(sample_offsets.cpu().numpy() if _is_torch(sample_offsets) else sample_offsets, dtype=np.int64)
+    if so.ndim != 1 or so.size < 1:
+        raise ValueError(f"{what}: an offset table has n + 1 entries")
+    total = max(int(so[-1]), 0) if total_samples is None else int(total_samples)
+    plan = np.zeros(so.size - 1, REVERB_PLAN_DTYPE)
+    if plan.size:
+        _lib.check(_lib.lib().ss_reverb_draws(words.ctypes.data, base, plan.size, so.ctypes.data, total, bank.handle, prob, plan.ctypes.data))
+    return plan
+
+
+def _reverb_out(x, scale, on_device, out, what):
+    out = _noise_out(x, scale, on_device, out, what)
+    if out is x:
+        raise ValueError(f"{what}: out must not be the signal: the convolution is not in place")
+    return out
+
+
+def reverb_plan_packed(lengths, bank, rng, prob=1.0, clip_base=0, device_tables=None, total_samples=None):
+    """The plan of ``reverb_packed`` alone, on the device: -> the plan table (int32 ``[n_clips, 2]``, see ``reverb_plan_rows``).
+    The epoch is not advanced.  ``rng`` is a ``Reverb``, a ``NoiseMix``, a ``SpecAugment`` or its int64 block; the table comes from
+    ``lengths``, or from ``device_tables`` (the sample offsets on the device, used as they stand, with ``total_samples`` the size of
+    the block they index)."""
+    import torch
+
+    what = "reverb_plan_packed"
+    prob, base = _reverb_scalars(prob, clip_base, bank, what)
+    block = _reverb_rng(rng)
+    block = block._block if isinstance(block, SpecAugment) else block
+    if not (_is_torch(block) and block.is_cuda and block.dtype == torch.int64 and block.numel() == 2 and block.is_contiguous()):
+        raise TypeError(f"{what}: rng must be a Reverb, a NoiseMix, a SpecAugment or a contiguous int64 device tensor of two words")
+    if device_tables is not None:
+        table = device_tables[0] if isinstance(device_tables, (tuple, list)) else device_tables
+        if lengths is not None or total_samples is None:
+            raise ValueError(f"{what}: device_tables go with lengths=None and total_samples")
+        if not (_is_torch(table) and table.is_cuda and table.dtype == torch.int64 and table.dim() == 1 and table.is_contiguous() and table.numel() >= 1):
+            raise TypeError(f"{what}: device_tables is the sample offsets, a contiguous 1-D int64 device tensor of n_clips + 1 entries")
+        n, total = table.numel() - 1, int(total_samples)
+    else:
+        table = _sample_offsets(lengths, 1 << 62, what)
+        n, total = table.size - 1, int(table[-1]) if total_samples is None else int(total_samples)
+    plan = torch.zeros((n, 2), dtype=torch.int32, device=block.device)
+    if n:
+        _launch(block.device, _lib.lib().ss_reverb_plan_packed_device, n, table, total, bank.handle, block.data_ptr(), base, prob, plan.data_ptr())
+    return plan
+
+
+def _reverb_device_plan(plan, n, device, what):
+    import torch
+
+    if _is_torch(plan):
+        if plan.dtype != torch.int32:
+            raise TypeError(f"{what}: a device plan is the int32 table [n_clips, 2] the plan and combined calls return")
+        rows = plan.to(device).contiguous()
+    else:
+        rows = torch.from_numpy(reverb_plan_rows(plan).view(np.int32).copy()).to(device)
+    if rows.numel() != n * 2:
+        raise ValueError(f"{what}: the plan must hold one row per clip")
+    return rows
+
+
+def reverb_apply_packed(signal, lengths, bank, plan, pcm_scale=None, out=None, device_tables=None):
+    """The convolution of ``reverb_packed`` alone, on any plan table -- the one a plan or combined call returned (one plan applied
+    twice gives equal outputs) or the caller's own record array of ``REVERB_PLAN_DTYPE``: ``out[i] = sum_k h[k] x[i + shift - k]``
+    over the clip's own samples.  A row with ``rir == -1``, or whose ``rir`` or ``shift`` is out of range for the bank, is copied bit
+    for bit; ``rir == -2`` leaves the clip's samples of ``out`` as they were.  ``out`` must not be the signal."""
+    what = "reverb_apply_packed"
+    _reverb_scalars(0.0, 0, bank, what)
+    x, scale, on_device, total, table, n = _noise_signal(signal, lengths, pcm_scale, device_tables, what)
+    out = _reverb_out(x, scale, on_device, out, what)
+    lib, i16, sc = _lib.lib(), "" if scale is None else "_i16", [] if scale is None else [scale]
+    if on_device:
+        rows = _reverb_device_plan(plan, n, x.device, what)
+        if n:
+            xin, xout = _noise_block(x, out, total, True)
+            _launch(x.device, getattr(lib, f"ss_reverb_apply_packed{i16}_device"), xin, *sc, n, table, total, bank.handle, rows, xout.data_ptr())
+        return out
+    rows = reverb_plan_rows(plan)
+    if rows.size != n:
+        raise ValueError(f"{what}: the plan must hold one row per clip")
+    if n:
+        xin, xout = _noise_block(x, out, total, False)
+        _lib.check(getattr(lib, f"ss_reverb_apply_packed{i16}")(xin.ctypes.data, *sc, n, table.ctypes.data, total, bank.handle, rows.ctypes.data, xout.ctypes.data))
+    return out
+
+
+def reverb_packed(signal, lengths, bank, rng, prob=1.0, clip_base=0, pcm_scale=None, out=None, device_tables=None):
+    """Reverberation of every clip of a packed 1-D signal, ahead of ``noise_mix_packed`` and the front ends: -> (out, plan).  With
+    probability ``prob`` a clip is convolved with a uniformly drawn response of ``bank`` (a ``ReverbBank``); its length stays, and no
+    clip reads its neighbour.  The draws are Philox4x32-10 keyed by ``rng``'s seed and counted by its epoch and ``clip_base + b``; the
+    call advances the epoch by one, so the next call, or the next replay of a captured graph, draws afresh.  ``plan`` is the table
+    that was applied (``reverb_plan_rows``).  ``pcm_scale``: the signal is int16 PCM, a sample is int16 * scale (a power of two);
+    ``out`` is float32, bit for bit the float call on the converted array.  On the device (ROCm tensors, current stream, nothing read
+    back) ``rng`` is a ``Reverb``, a ``NoiseMix``, a ``SpecAugment`` or its int64 block; for numpy input also a writable uint64 array
+    ``[seed, epoch]``, updated in place.  ``device_tables``: the sample offsets as an int64 device tensor (with ``lengths=None``),
+    used as they stand.  The bank's first device call uploads its spectra: make one call before capturing a graph.
+    ``(out, lengths)`` go straight into ``noise_mix_packed`` and every packed front end."""
+    what = "reverb_packed"
+    prob, base = _reverb_scalars(prob, clip_base, bank, what)
+    x, scale, on_device, total, table, n = _noise_signal(signal, lengths, pcm_scale, device_tables, what)
+    out = _reverb_out(x, scale, on_device, out, what)
+    lib, i16, sc = _lib.lib(), "" if scale is None else "_i16", [] if scale is None else [scale]
+    if on_device:
+        import torch
+
+        block = _noise_device_rng(_reverb_rng(rng), x, what)
+        plan = torch.zeros((n, 2), dtype=torch.int32, device=x.device)
+        if n:
+            xin, xout = _noise_block(x, out, total, True)
+            _launch(x.device, getattr(lib, f"ss_reverb_packed{i16}_device"), xin, *sc, n, table, total, bank.handle, block.data_ptr(), base, prob,
+                    xout.data_ptr(), plan.data_ptr())
+        return out, plan
+    rng = _reverb_rng(rng)
+    words = _rng_words(rng, what)
+    plan = np.zeros(n, REVERB_PLAN_DTYPE)
+    if n:
+        xin, xout = _noise_block(x, out, total, False)
+        _lib.check(getattr(lib, f"ss_reverb_packed{i16}")(xin.ctypes.data, *sc, n, table.ctypes.data, total, bank.handle, words.ctypes.data, base, prob,
+                                                         xout.ctypes.data, plan.ctypes.data))
+        if isinstance(rng, SpecAugment):
+            rng.epoch = int(words[1])
+        elif isinstance(rng, np.ndarray) and rng is not words:
+            rng[1] = words[1]
+    return out, plan
+
+
+class Reverb:
+    """``reverb_packed`` with its state: the generator block (``rng``, a ``SpecAugment``) and the bank.  ``reverb = Reverb(seed,
+    bank)``, or ``Reverb(augment, bank)`` / ``Reverb(noise_mix, bank)`` to share the block of a ``SpecAugment`` or a ``NoiseMix`` (the
+    stages' counter words differ, and each call of each stage advances the shared epoch); ``out, plan = reverb(signal, lengths,
+    prob=0.5)`` -- every call, and every replay of a graph that captured one, advances the epoch on the device."""
+
+    def __init__(self, seed, bank, epoch=0, device=None):
+        if not isinstance(bank, ReverbBank):
+            raise TypeError("Reverb: bank must be a ReverbBank")
+        shared = seed.rng if isinstance(seed, NoiseMix) else seed
+        self.rng = shared if isinstance(shared, SpecAugment) else SpecAugment(seed, epoch, device)
+        self.bank = bank
+
+    seed = property(lambda self: self.rng.seed)
+    epoch = property(lambda self: self.rng.epoch, lambda self, value: setattr(self.rng, "epoch", value))
+
+    def plan(self, lengths, prob=1.0, clip_base=0, device_tables=None, total_samples=None):
+        return reverb_plan_packed(lengths, self.bank, self.rng, prob, clip_base, device_tables, total_samples)
+
+    def apply(self, signal, lengths, plan, pcm_scale=None, out=None, device_tables=None):
+        return reverb_apply_packed(signal, lengths, self.bank, plan, pcm_scale, out, device_tables)
+
+    def __call__(self, signal, lengths, prob=1.0, clip_base=0, pcm_scale=None, out=None, device_tables=None):
+        return reverb_packed(signal, lengths, self.bank, self.rng, prob, clip_base, pcm_scale, out, device_tables)
 
 
 # ---- polyphase sinc resampling ahead of the feature calls (ss_resample* in include/speechsauce_amd.h) -------------

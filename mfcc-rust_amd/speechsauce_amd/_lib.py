@@ -137,6 +137,10 @@ _wc = C.c_void_p  # ss_whisper_config *
 _nc = C.c_void_p  # ss_nemo_config *
 _fp = C.c_void_p  # float* passed as an address (numpy .ctypes.data or a device pointer)
 # the shared head of the ss_noise_* calls: samples, n_clips, sample_offsets, total_samples, bank, n_noise, noise_offsets, total_noise
+_rb = C.c_void_p  # ss_reverb_bank *
+# the shared head of the ss_reverb_* sample calls: samples, n_clips, sample_offsets, total_samples, bank
+_REVERB_F32 = [_fp, C.c_size_t, C.c_void_p, C.c_size_t, _rb]
+_REVERB_I16 = [C.c_void_p, C.c_float, C.c_size_t, C.c_void_p, C.c_size_t, _rb]
 _NOISE_F32 = [_fp, C.c_size_t, C.c_void_p, C.c_size_t, _fp, C.c_size_t, C.c_void_p, C.c_size_t]
 _NOISE_I16 = [C.c_void_p, C.c_float, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_size_t, C.c_void_p, C.c_size_t]
 PROTOTYPES = {
@@ -342,6 +346,21 @@ PROTOTYPES = {
     "ss_noise_mix_packed_i16_device": (C.c_int, _NOISE_I16 + [C.c_void_p, C.c_size_t] + [C.c_float] * 5 + [_fp, C.c_void_p, C.c_void_p, C.c_size_t,
                                                                                                           C.c_void_p]),
     "ss_noise_mix_packed_i16": (C.c_int, _NOISE_I16 + [C.c_void_p, C.c_size_t] + [C.c_float] * 5 + [_fp, C.c_void_p]),
+    "ss_reverb_bank_create": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, _P(_rb)]),
+    "ss_reverb_bank_destroy": (None, [_rb]),
+    "ss_reverb_bank_info": (C.c_int, [_rb, _P(C.c_size_t), _P(C.c_size_t), _P(C.c_size_t), _P(C.c_size_t)]),
+    "ss_reverb_bank_rir": (C.c_int, [_rb, C.c_size_t, _fp, C.c_size_t, _P(C.c_size_t), _P(C.c_size_t)]),
+    "ss_reverb_bank_spectrum": (C.c_int, [_rb, C.c_size_t, C.c_size_t, _fp]),
+    "ss_reverb_draws": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, _rb, C.c_float, C.c_void_p]),
+    "ss_reverb_plan_packed_device": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, _rb, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
+    "ss_reverb_apply_packed_device": (C.c_int, _REVERB_F32 + [C.c_void_p, _fp, C.c_void_p]),
+    "ss_reverb_apply_packed": (C.c_int, _REVERB_F32 + [C.c_void_p, _fp]),
+    "ss_reverb_apply_packed_i16_device": (C.c_int, _REVERB_I16 + [C.c_void_p, _fp, C.c_void_p]),
+    "ss_reverb_apply_packed_i16": (C.c_int, _REVERB_I16 + [C.c_void_p, _fp]),
+    "ss_reverb_packed_device": (C.c_int, _REVERB_F32 + [C.c_void_p, C.c_size_t, C.c_float, _fp, C.c_void_p, C.c_void_p]),
+    "ss_reverb_packed": (C.c_int, _REVERB_F32 + [C.c_void_p, C.c_size_t, C.c_float, _fp, C.c_void_p]),
+    "ss_reverb_packed_i16_device": (C.c_int, _REVERB_I16 + [C.c_void_p, C.c_size_t, C.c_float, _fp, C.c_void_p, C.c_void_p]),
+    "ss_reverb_packed_i16": (C.c_int, _REVERB_I16 + [C.c_void_p, C.c_size_t, C.c_float, _fp, C.c_void_p]),
     "ss_vad_energy_stream_state_len": (C.c_int, [C.c_size_t, _P(C.c_size_t)]),
     "ss_vad_energy_stream_packed_device": (C.c_int, [_fp, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
                                                      C.c_float, C.c_float, C.c_size_t, C.c_float, _fp, C.c_void_p, C.c_void_p]),
